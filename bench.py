@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput bench of the hot path: ResNet-50 fp32 forward, batch 256 per GPU.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,7 +12,16 @@ batch of N*256 (batch split, weights replicated, NO data-path collective -- the
 forward has no cross-image reduction); value = N*256*K / t
 where t is the MAX over ranks of the barrier-bracketed wall time of K steps.
 
-The JSON line also carries
+A plain run does only what that figure needs: set-up (weights, inputs, the per-layer tile tuning), W warm-up
+steps, the K timed steps, and the JSON line (metric, value, unit, ms_per_step, dtype, config, world).
+  --dump-outputs DIR  writes the logits of the last timed step, the array a caller of the timed path
+                      receives, as DIR/logits.npy (float32; per rank DIR/logits_rank<r>.npy when N > 1).
+                      Weights and inputs are seeded, so two builds run with the same arguments can be
+                      compared output for output.
+  --full              also runs every leg below (each can still be left out with its --no-* option).
+
+With --full the JSON line also carries
+  ms_per_step_one_stream  the same K steps with the whole batch on one stream;
   roofline      the dominant kernel family (the implicit-GEMM contraction): algorithmic
                 FLOPs of its launches in one forward / their summed HIP-event durations,
                 measured on the library's stream in per-op instrumented forwards run
@@ -23,6 +32,7 @@ The JSON line also carries
   hbm_kernels   the same for the bandwidth-bound kernels (GB/s against 8 TB/s): those of the timed
                 (fused) forward plus, from a short leg in the one-kernel-per-reference-op mode run
                 after the timed region, batch-norm / ReLU / add / max-pool;
+  host_pipeline (N=1 only) the PCIe-inclusive rate: upload, forward and logits download per batch;
   cpu_baseline  oracle/torch_port.py (a torch.nn.functional port of the reference's
                 pytorch_inference.py, pinned by the golden logits) timed on this host's
                 CPU cores on a bounded sample, rank 0 at N=1 only.
@@ -376,6 +386,26 @@ def dropin_route(arch: str, state, x_dev, B: int, steps: int):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, logits, rank: int, world: int):
+    """The logits of the last timed step as <out_dir>/logits.npy (float32).  A batch whose logits exceed
+    DUMP_MAX_BYTES is written as a fixed, seeded sample of its rows (sorted), with the row indices beside
+    it as logits_rows.npy."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    max_rows = max(1, DUMP_MAX_BYTES // max(1, logits[0].nbytes))
+    if logits.shape[0] > max_rows:
+        rows = np.sort(np.random.default_rng(0).choice(logits.shape[0], size=max_rows, replace=False))
+        logits = logits[rows]
+        np.save(os.path.join(out_dir, f"logits_rows{suffix}.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, f"logits{suffix}.npy"), logits)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -403,7 +433,15 @@ def main():
     ap.add_argument("--front-parts", type=int, default=1,
                     help="stem + max-pool + first stage in this many slices per batch part (Infinity-Cache reuse)")
     ap.add_argument("--profile-forwards", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: one-stream steps, the instrumented "
+                         "forwards of roofline / hbm_kernels (+ the ops leg), the PCIe-inclusive leg, the drop-in "
+                         "route and the CPU baseline; without it a run sets up, warms up, times and reports")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the logits of the last timed step to DIR/logits.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import numpy as np
     import torch
@@ -480,6 +518,73 @@ def main():
 
     out = logits.numpy()
     assert np.isfinite(out).all(), "non-finite logits"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
+
+    if args.full:
+        ms_one_stream, fam, ops_fam, kernel_launches = full_legs(args, model, ctx, x_dev, logits, B, fused, parts,
+                                                                 cfg_streams, elapsed, out)
+    if rank != 0:
+        return
+    images = world * B * args.steps
+    value = images / elapsed
+    peak = PEAK_F32_MFMA_TFLOPS if args.dtype == "f32" else PEAK_BF16_MFMA_TFLOPS
+    prec = "fp32" if args.dtype == "f32" else "bf16"
+    result = {
+        "metric": "images/sec ResNet-50 224x224 fp32 batch=256"
+                  if args.arch == "resnet50" and B == 256 and args.dtype == "f32"
+                  else f"images/sec {args.arch} 224x224 {prec} batch={B}",
+        "value": round(value, 2),
+        "unit": "images/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+    }
+    if args.full:
+        result["ms_per_step_one_stream"] = round(ms_one_stream, 4)
+    result.update({
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": args.dtype,
+        "data": "synthetic (seeded uniform [-2,2) images, generated weights in the reference's "
+                "weights_bin format; inputs resident in HBM)",
+        "config": {"workload": f"{args.arch} {prec} forward, batch {B} per GPU, 224x224 "
+                               + ("(BASELINE.json configs[2])" if args.dtype == "f32" and args.arch == "resnet50"
+                                  else "(BASELINE.json configs[3], per-GPU shard)" if args.dtype == "bf16"
+                                  else "(BASELINE.json configs[4])"),
+                   "global_batch": world * B, "batch_per_gpu": B,
+                   "mode": "fused conv+bn+relu(+add) epilogues" if fused else "one kernel per reference op",
+                   "streams_per_gpu": parts, "streams_configured": cfg_streams or "library default",
+                   "front_parts": args.front_parts,
+                   "parallelism": f"batch split over {world} GPU(s), weights replicated, no collective"},
+    })
+    if args.full:
+        result["roofline"], hbm = roofline_block(args, fam, ops_fam, kernel_launches, peak)
+    result["world"] = world_block(ranks, dist_world, dist_backend)
+    result["whole_step_mfma_frac"] = round(value / world * GFLOP_PER_IMAGE[args.arch] / 1e3 / peak, 4)
+    if args.full:
+        result["hbm_kernels"] = hbm
+        if world == 1 and not args.no_pipeline:
+            result["host_pipeline"] = host_pipeline(model, x_host, B, fused, args.steps)
+        if world == 1 and args.dtype == "f32" and not args.no_dropin:
+            result["dropin_route"] = dropin_route(args.arch, state, x_dev, B, args.steps)
+        if world == 1 and not args.no_cpu_baseline:
+            result["cpu_baseline"] = cpu_baseline(args.arch, state, batch=B,
+                                                  engine=lambda a: model.forward(a, fused=fused))
+            diff = result["cpu_baseline"]["max_abs_diff_vs_gpu_logits_on_4_images"]
+            assert diff is not None and diff <= (1e-4 if args.dtype == "f32" else 0.25), diff
+    print(json.dumps(result))
+
+
+def full_legs(args, model, ctx, x_dev, logits, B, fused, parts, cfg_streams, elapsed, out):
+    """The --full legs on the device right behind the timed region, on every rank: the K steps again with
+    the whole batch on one stream, then the instrumented forwards (and the ops-mode leg) that the roofline
+    and hbm_kernels blocks are computed from.  Returns (ms_one_stream, fam, ops_fam, kernel_launches)."""
+    import numpy as np
+
+    import resnet_c_amd as R
 
     # the same steps with the whole batch on ONE stream (what the roofline block below describes)
     ms_one_stream = elapsed / args.steps * 1e3
@@ -519,11 +624,14 @@ def main():
             orecs += model.profile()
         ops_fam = summarize_profile(orecs, max(1, args.profile_forwards))
     model.set_profiling(False)
+    return ms_one_stream, fam, ops_fam, kernel_launches
 
-    if rank != 0:
-        return
-    images = world * B * args.steps
-    value = images / elapsed
+
+def roofline_block(args, fam, ops_fam, kernel_launches, peak):
+    """The --full line's `roofline` block (the contraction family) and `hbm_kernels` (the bandwidth-bound
+    kernels) from the instrumented forwards of full_legs()."""
+    import resnet_c_amd as R
+
     gemm_names = [k for k in fam if k.startswith("conv2d") or k == "linear"]
     g_flops = sum(fam[k]["flops"] for k in gemm_names)
     g_ms = sum(fam[k]["ms"] for k in gemm_names)
@@ -548,8 +656,6 @@ def main():
             hbm[k] = {"launches": f["launches"], "ms_per_forward": round(f["ms"], 4), "GBps": round(gbs, 1),
                       "frac": round(gbs / PEAK_HBM_GBS, 4),
                       "from": "ops-mode leg (one kernel per reference op) behind the timed region"}
-    peak = PEAK_F32_MFMA_TFLOPS if args.dtype == "f32" else PEAK_BF16_MFMA_TFLOPS
-    prec = "fp32" if args.dtype == "f32" else "bf16"
     g_gbps = g_bytes / (g_ms * 1e-3) / 1e9 if g_ms > 0 else 0.0
     # what binds the contraction family as a whole: the larger of its two roofline fractions
     # (fp32: the matrix pipe; bf16 storage: 16x the matrix rate on half the bytes -> HBM)
@@ -557,70 +663,31 @@ def main():
     bound = "mfma" if frac_mfma >= frac_hbm else "hbm"
     traffic, traffic_source, traffic_stale = pmc_traffic(args, g_launch)
     busy, busy_source, busy_stale = pmc_mfma_busy(args, g_launch)
-    result = {
-        "metric": "images/sec ResNet-50 224x224 fp32 batch=256"
-                  if args.arch == "resnet50" and B == 256 and args.dtype == "f32"
-                  else f"images/sec {args.arch} 224x224 {prec} batch={B}",
-        "value": round(value, 2),
-        "unit": "images/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "ms_per_step_one_stream": round(ms_one_stream, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": args.dtype,
-        "data": "synthetic (seeded uniform [-2,2) images, generated weights in the reference's "
-                "weights_bin format; inputs resident in HBM)",
-        "config": {"workload": f"{args.arch} {prec} forward, batch {B} per GPU, 224x224 "
-                               + ("(BASELINE.json configs[2])" if args.dtype == "f32" and args.arch == "resnet50"
-                                  else "(BASELINE.json configs[3], per-GPU shard)" if args.dtype == "bf16"
-                                  else "(BASELINE.json configs[4])"),
-                   "global_batch": world * B, "batch_per_gpu": B,
-                   "mode": "fused conv+bn+relu(+add) epilogues" if fused else "one kernel per reference op",
-                   "streams_per_gpu": parts, "streams_configured": cfg_streams or "library default",
-                   "front_parts": args.front_parts,
-                   "parallelism": f"batch split over {world} GPU(s), weights replicated, no collective"},
-        "roofline": {"bound": bound,
-                     "achieved": round(achieved, 2) if bound == "mfma" else round(g_gbps, 1),
-                     "peak": peak if bound == "mfma" else PEAK_HBM_GBS,
-                     "unit": "TFLOP/s" if bound == "mfma" else "GB/s",
-                     "frac": round(max(frac_mfma, frac_hbm), 4),
-                     "traffic": traffic, "traffic_source": traffic_source, "traffic_stale": traffic_stale,
-                     # share of the chip's SIMD-cycles with a matrix pipe busy during the contraction launches
-                     # (SQ_VALU_MFMA_BUSY_CYCLES; committed --pmc pass of this command, this build only)
-                     "mfma_busy": busy["mfma_busy"] if busy else None,
-                     "mfma_busy_detail": busy, "mfma_busy_source": busy_source, "mfma_busy_stale": busy_stale,
-                     "source_digest": R._lib.source_digest(),
-                     "kernel": "conv_gemm_kernel" + (" / conv_wide_kernel / conv_strip_kernel / chain_kernel" if args.dtype == "bf16" else " / chain32_kernel") +
-                               " (implicit-GEMM conv2d + fc on " +
-                               ("v_mfma_f32_32x32x2_f32)" if args.dtype == "f32" else "v_mfma_f32_32x32x16_bf16)"),
-                     "mfma_TFLOPs": round(achieved, 2), "mfma_frac": round(frac_mfma, 4),
-                     "hbm_GBps": round(g_gbps, 1), "hbm_frac": round(frac_hbm, 4),
-                     "ops_per_forward": g_ops, "launches_per_forward": g_launch,
-                     "avg_launch_us": round(g_ms * 1e3 / max(g_launch, 1), 2),
-                     "flops_per_forward": g_flops, "bytes_per_forward": g_bytes,
-                     "ms_per_forward": round(g_ms, 4),
-                     "measured_on": "HIP events around every op of %d instrumented forwards right after the "
-                                    "timed region, whole batch on ONE stream (with streams_per_gpu > 1 the timed "
-                                    "region overlaps the kernels of the batch parts, so their sum exceeds "
-                                    "ms_per_step)" % args.profile_forwards},
-        "world": world_block(ranks, dist_world, dist_backend),
-        "whole_step_mfma_frac": round(value / world * GFLOP_PER_IMAGE[args.arch] / 1e3 / peak, 4),
-        "hbm_kernels": hbm,
-    }
-    if world == 1 and not args.no_pipeline:
-        result["host_pipeline"] = host_pipeline(model, x_host, B, fused, args.steps)
-    if world == 1 and args.dtype == "f32" and not args.no_dropin:
-        result["dropin_route"] = dropin_route(args.arch, state, x_dev, B, args.steps)
-    if world == 1 and not args.no_cpu_baseline:
-        result["cpu_baseline"] = cpu_baseline(args.arch, state, batch=B,
-                                              engine=lambda a: model.forward(a, fused=fused))
-        diff = result["cpu_baseline"]["max_abs_diff_vs_gpu_logits_on_4_images"]
-        assert diff is not None and diff <= (1e-4 if args.dtype == "f32" else 0.25), diff
-    print(json.dumps(result))
+    roofline = {"bound": bound,
+                "achieved": round(achieved, 2) if bound == "mfma" else round(g_gbps, 1),
+                "peak": peak if bound == "mfma" else PEAK_HBM_GBS,
+                "unit": "TFLOP/s" if bound == "mfma" else "GB/s",
+                "frac": round(max(frac_mfma, frac_hbm), 4),
+                "traffic": traffic, "traffic_source": traffic_source, "traffic_stale": traffic_stale,
+                # share of the chip's SIMD-cycles with a matrix pipe busy during the contraction launches
+                # (SQ_VALU_MFMA_BUSY_CYCLES; committed --pmc pass of this command, this build only)
+                "mfma_busy": busy["mfma_busy"] if busy else None,
+                "mfma_busy_detail": busy, "mfma_busy_source": busy_source, "mfma_busy_stale": busy_stale,
+                "source_digest": R._lib.source_digest(),
+                "kernel": "conv_gemm_kernel" + (" / conv_wide_kernel / conv_strip_kernel / chain_kernel" if args.dtype == "bf16" else " / chain32_kernel") +
+                          " (implicit-GEMM conv2d + fc on " +
+                          ("v_mfma_f32_32x32x2_f32)" if args.dtype == "f32" else "v_mfma_f32_32x32x16_bf16)"),
+                "mfma_TFLOPs": round(achieved, 2), "mfma_frac": round(frac_mfma, 4),
+                "hbm_GBps": round(g_gbps, 1), "hbm_frac": round(frac_hbm, 4),
+                "ops_per_forward": g_ops, "launches_per_forward": g_launch,
+                "avg_launch_us": round(g_ms * 1e3 / max(g_launch, 1), 2),
+                "flops_per_forward": g_flops, "bytes_per_forward": g_bytes,
+                "ms_per_forward": round(g_ms, 4),
+                "measured_on": "HIP events around every op of %d instrumented forwards right after the "
+                               "timed region, whole batch on ONE stream (with streams_per_gpu > 1 the timed "
+                               "region overlaps the kernels of the batch parts, so their sum exceeds "
+                               "ms_per_step)" % args.profile_forwards}
+    return roofline, hbm
 
 
 if __name__ == "__main__":

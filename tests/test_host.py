@@ -68,10 +68,9 @@ def test_preprocessed_fixture_shape_and_range(finch):
     assert finch.shape == (1, 3, 224, 224) and finch.dtype == np.float32
     # ImageNet normalisation range: (0-0.485)/0.229 .. (1-0.406)/0.225
     assert finch.min() >= -2.1180 and finch.max() <= 2.6401
-    ref_img = "/root/reference/test_imgs/ILSVRC2012_val_00004749.jpeg"
-    if os.path.exists(ref_img):  # build container only
-        again = R.preprocess.preprocess_image(ref_img)
-        assert np.array_equal(again, finch)
+    # the fixture is the reference's test image through the preprocessing; the JPEG is stored beside it
+    again = R.preprocess.preprocess_image(os.path.join(ROOT, "tests", "golden", "ILSVRC2012_val_00004749.jpeg"))
+    assert np.array_equal(again, finch)
 
 
 def _declared_symbols():
