@@ -308,7 +308,12 @@ RN_API int rn_avgpool2d_nhwc_forward_dt(rn_ctx *ctx, int dtype, const void *inp,
                                         uint64_t channels, uint64_t H, uint64_t W);
 
 /* ---- model (main.cu driver) ---------------------------------------------- */
-/* arch: 50, 101 or 152 (block counts 3/4/6/3, 3/4/23/3, 3/8/36/3). */
+/* arch: 50, 101 or 152 (bottleneck blocks, counts 3/4/6/3, 3/4/23/3, 3/8/36/3), or 18 or 34
+ * (torchvision's basic blocks -- two 3x3 convolutions, expansion 1, final width 512 -- counts
+ * 2/2/2/2 and 3/4/6/3; tensor keys layerX.Y.{conv1,bn1,conv2,bn2,downsample.0,downsample.1}.*).
+ * Fused basic blocks: conv1 + bn1 + ReLU, conv2 + bn2 + shortcut + ReLU; with pair fusion, block 0
+ * of stages 2-4 runs conv2 and the downsample as one contraction (not bit-neutral, like the
+ * bottleneck pair).  No chained launches in basic-block networks. */
 RN_API int rn_model_create(rn_ctx *ctx, rn_model **out, int arch);
 RN_API int rn_model_destroy(rn_model *m);
 /* state_dict key -> host data; numel must match the layer table. */
@@ -331,13 +336,14 @@ RN_API const char *rn_model_tensor_key(const rn_model *m, uint64_t index, uint64
  *   - images are 3 x 224 x 224 fp32, NCHW; there is no size argument, so a buffer of another
  *     geometry cannot be expressed: callers that read files check the element count first
  *     (rn_infer does and reports RN_ERR_UNSUPPORTED's text for anything but B*3*224*224 floats);
- *   - 1000 classes, bottleneck depths 50 / 101 / 152;
+ *   - 1000 classes, bottleneck depths 50 / 101 / 152, basic-block depths 18 / 34;
  *   - any B >= 1: the kernels address a tensor with 32-bit byte offsets (2^29 fp32 elements; the
  *     stem output of 669 images is the first to pass it), so a batch runs as sub-batches of at
  *     most 512 images through the same arenas, each as `streams` parts (rn_model_set_streams);
  *     every image's logits are independent of that split, bit for bit;
  *   - arenas: 13.6 MB (fp32) / 6.8 MB (bf16) of activations per image of the largest sub-batch
- *     seen, allocated on first use (RN_ERR_NOMEM when the device cannot hold them). */
+ *     seen (basic-block networks: 8.5 / 4.2 MB), allocated on first use (RN_ERR_NOMEM when the
+ *     device cannot hold them). */
 RN_API int rn_model_forward(rn_model *m, const float *input_nchw, uint64_t B, float *logits,
                             int mode);
 /* Run one forward, then time every tile candidate of every convolution at batch B on the

@@ -462,9 +462,15 @@ void launch(rn_ctx *ctx, const GemmParams &p, bool dual)
 //
 // Same k order per output element as the tile kernels (tap-major, 16 channels per MFMA), same
 // products (a*b commutes), so the bits are the same as every other candidate's.
+//
+// Residual (conv2 of a basic block: bn2 + shortcut + ReLU): a template switch, so the kernel without
+// one is the same code as before.  Each lane loads the residual in the accumulator's own map (4 x 8
+// bytes per pixel, zeros for padding positions) right after the step's taps, and the epilogue runs
+// the 4-wave kernel's order: fmaf(acc, scale, shift), + residual in fp32, ReLU, one rounding to bf16.
 struct StripParams {
     const void *in, *w;
     void *out;
+    const void *residual;  // bf16 NHWC, the output's shape, or null
     const float *scale, *shift;
     int relu;
     int B, H, W;
@@ -476,9 +482,21 @@ struct StripParams {
     unsigned long long *stamps;  // diagnostic only (tools/conv_stamps.py --raw)
 };
 
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+
+// v[c] += the c-th of four bf16 values packed low half first (the widening is exact, the sum one fp32 add)
+__device__ __forceinline__ void add_bf16x4(float (&v)[4], const u32x2 r)
+{
+    v[0] += __uint_as_float(r[0] << 16);
+    v[1] += __uint_as_float(r[0] & 0xffff0000u);
+    v[2] += __uint_as_float(r[1] << 16);
+    v[3] += __uint_as_float(r[1] & 0xffff0000u);
+}
+
 constexpr int kRing = 640;       // positions in the LDS ring (5 x 128: 256-position steps wrap every 5)
 constexpr int kStripMargin = 64;  // ring position of a block's first output position; >= W + 3
 
+template <bool RES>
 __global__ __launch_bounds__(512, 2) void conv_strip_kernel(const StripParams p)
 {
     // ring | scale[64], shift[64] | the weights as they lie in memory (start-up only)
@@ -510,6 +528,8 @@ __global__ __launch_bounds__(512, 2) void conv_strip_kernel(const StripParams p)
 
     const i32x4 srd_in = make_srd(p.in, p.in_bytes);
     const __amdgpu_buffer_rsrc_t rsrc_o = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, p.out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_r =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.residual), 0, RES ? p.out_bytes : 0, 0x00020000);
     const unsigned lds_base = (unsigned)(uintptr_t)((lds_void *)lds);
 
     // Weights: 72 KB, the same for every block.  Fetched coalesced (1-KiB DMA pieces) and picked
@@ -651,8 +671,20 @@ __global__ __launch_bounds__(512, 2) void conv_strip_kernel(const StripParams p)
         if (s == 4) tk[3] = wall_clock64();
 
         // results: lane (li, lh) holds channels 32nf + 8j + 4lh + {0..3}, j = 0..3, of pixel li of
-        // each fragment.  Affine + ReLU, bf16, then the half-waves trade 4-channel groups so that
-        // each lane owns channels 32nf + 16h + 8lh + {0..7}: two 16-byte stores per fragment.
+        // each fragment.  Affine (+ residual) + ReLU, bf16, then the half-waves trade 4-channel groups
+        // so that each lane owns channels 32nf + 16h + 8lh + {0..7}: two 16-byte stores per fragment.
+        int gpx[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) gpx[i] = pixel_of(ub + 256 * s + 64 * mq + 32 * i + li);
+        u32x2 rres[2][4];
+        if constexpr (RES) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    rres[i][j] = __builtin_amdgcn_raw_buffer_load_b64(
+                        rsrc_r, gpx[i] < 0 ? kOob : gpx[i] * 128 + (32 * nf + 8 * j + 4 * lh) * 2, 0, 0);
+        }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             unsigned d[4][2];
@@ -662,6 +694,7 @@ __global__ __launch_bounds__(512, 2) void conv_strip_kernel(const StripParams p)
                 const float4 sh = *reinterpret_cast<const float4 *>(ssl + 64 + 32 * nf + 8 * j + 4 * lh);
                 float v[4] = {fmaf(acc[i][4 * j], sc.x, sh.x), fmaf(acc[i][4 * j + 1], sc.y, sh.y),
                               fmaf(acc[i][4 * j + 2], sc.z, sh.z), fmaf(acc[i][4 * j + 3], sc.w, sh.w)};
+                if constexpr (RES) add_bf16x4(v, rres[i][j]);
                 typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
@@ -678,8 +711,7 @@ __global__ __launch_bounds__(512, 2) void conv_strip_kernel(const StripParams p)
                 const auto x1 = __builtin_amdgcn_permlane32_swap(d[2 * h][1], d[2 * h + 1][1], false, false);
                 pend[i][h] = i32x4{(int)x0[0], (int)x1[0], (int)x0[1], (int)x1[1]};
             }
-            const int g = pixel_of(ub + 256 * s + 64 * mq + 32 * i + li);
-            pend_off[i] = g < 0 ? kOob : g * 128 + (32 * nf + 8 * lh) * 2;
+            pend_off[i] = gpx[i] < 0 ? kOob : gpx[i] * 128 + (32 * nf + 8 * lh) * 2;
         }
         relbase = relbase + 256 >= kRing ? relbase + 256 - kRing : relbase + 256;
         if (s == 4) tk[4] = wall_clock64();
@@ -707,6 +739,7 @@ __global__ __launch_bounds__(512, 2) void conv_strip_kernel(const StripParams p)
 // LDS in two halves before the ring is in use.
 constexpr int kRing2 = 320, kMargin2 = 32, kSeg2 = kRing2 * 128;  // W + 3 <= 32
 
+template <bool RES>
 __global__ __launch_bounds__(256) void conv_strip128_kernel(const StripParams p)
 {
     __shared__ __attribute__((aligned(16))) char lds[64 * 145 * 16];  // >= 2 * kSeg2: weight staging is the larger
@@ -726,6 +759,8 @@ __global__ __launch_bounds__(256) void conv_strip128_kernel(const StripParams p)
     }
     const i32x4 srd_in = make_srd(p.in, p.in_bytes);
     const __amdgpu_buffer_rsrc_t rsrc_o = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, p.out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_r =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.residual), 0, RES ? p.out_bytes : 0, 0x00020000);
     const unsigned lds_base = (unsigned)(uintptr_t)((lds_void *)lds);
 
     // weights: two rounds of 64 output channels; LDS rows of 145 chunks (144 + 1: 145r mod 16 differs
@@ -854,6 +889,18 @@ __global__ __launch_bounds__(256) void conv_strip128_kernel(const StripParams p)
         }
 
         if (s == 0) stamp(p.stamps, 3);
+        int gpx[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) gpx[i] = pixel_of(ub + 128 * s + 32 * i + li);
+        u32x2 rres[4][4];
+        if constexpr (RES) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    rres[i][j] = __builtin_amdgcn_raw_buffer_load_b64(
+                        rsrc_r, gpx[i] < 0 ? kOob : gpx[i] * 256 + (32 * wave + 8 * j + 4 * lh) * 2, 0, 0);
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             unsigned d[4][2];
@@ -861,6 +908,7 @@ __global__ __launch_bounds__(256) void conv_strip128_kernel(const StripParams p)
             for (int j = 0; j < 4; ++j) {
                 float v[4] = {fmaf(acc[i][4 * j], sc[j].x, sh[j].x), fmaf(acc[i][4 * j + 1], sc[j].y, sh[j].y),
                               fmaf(acc[i][4 * j + 2], sc[j].z, sh[j].z), fmaf(acc[i][4 * j + 3], sc[j].w, sh[j].w)};
+                if constexpr (RES) add_bf16x4(v, rres[i][j]);
                 typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
@@ -876,8 +924,7 @@ __global__ __launch_bounds__(256) void conv_strip128_kernel(const StripParams p)
                 const auto x1 = __builtin_amdgcn_permlane32_swap(d[2 * h][1], d[2 * h + 1][1], false, false);
                 pend[i][h] = i32x4{(int)x0[0], (int)x1[0], (int)x0[1], (int)x1[1]};
             }
-            const int g = pixel_of(ub + 128 * s + 32 * i + li);
-            pend_off[i] = g < 0 ? kOob : g * 256 + (32 * wave + 8 * lh) * 2;
+            pend_off[i] = gpx[i] < 0 ? kOob : gpx[i] * 256 + (32 * wave + 8 * lh) * 2;
         }
         relbase = relbase + 128 >= kRing2 ? relbase + 128 - kRing2 : relbase + 128;
         if (s == 0) stamp(p.stamps, 4);
@@ -922,7 +969,8 @@ void rn_conv_wide_launch(rn_ctx *ctx, GemmParams &p, int which, bool dual)
 bool rn_conv_strip_eligible(const GemmParams &p)
 {
     const bool common = p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1 && p.chunk_dw == 0 && p.kreal == 0 &&
-                        p.tap_rows == 1 && p.residual == nullptr && p.Ho == p.H && p.Wo == p.W &&
+                        p.tap_rows == 1 && (reinterpret_cast<uintptr_t>(p.residual) & 15) == 0 &&
+                        p.Ho == p.H && p.Wo == p.W &&
                         (uint64_t)(p.M / (p.H * p.W) * (p.H + 1) + 1) * (uint64_t)(p.W + 2) < (1ull << 30);
     if (!common) return false;
     if (p.Cs == 64 && p.Cout == 64 && p.cseg == 1 && p.Ktot == 576) return p.W + 3 <= kStripMargin;
@@ -932,7 +980,8 @@ bool rn_conv_strip_eligible(const GemmParams &p)
 void rn_conv_strip_launch(rn_ctx *ctx, const GemmParams &g)
 {
     StripParams p;
-    p.in = g.in, p.w = g.w, p.out = g.out, p.scale = g.scale, p.shift = g.shift, p.relu = g.relu;
+    p.in = g.in, p.w = g.w, p.out = g.out, p.residual = g.residual, p.scale = g.scale, p.shift = g.shift,
+    p.relu = g.relu;
     p.H = g.H, p.W = g.W, p.B = g.M / (g.H * g.W);
     p.Wp = p.W + 2, p.Hq = p.H + 1;
     rn_fast_div((unsigned)p.Wp, &p.mul_wp, &p.shr_wp);
@@ -942,10 +991,17 @@ void rn_conv_strip_launch(rn_ctx *ctx, const GemmParams &g)
     p.stamps = g.stamps;
     if (g.Cs == 128) {
         p.nsteps = (p.U + 127) / 128;
-        conv_strip128_kernel<<<dim3(p.nsteps < 256 ? p.nsteps : 256), dim3(256), 0, ctx->stream>>>(p);
+        const dim3 grid(p.nsteps < 256 ? p.nsteps : 256);
+        if (p.residual)
+            conv_strip128_kernel<true><<<grid, dim3(256), 0, ctx->stream>>>(p);
+        else
+            conv_strip128_kernel<false><<<grid, dim3(256), 0, ctx->stream>>>(p);
         return;
     }
     p.nsteps = (p.U + 255) / 256;
     const int blocks = p.nsteps < 256 ? p.nsteps : 256;  // one block per CU
-    conv_strip_kernel<<<dim3(blocks), dim3(512), 0, ctx->stream>>>(p);
+    if (p.residual)
+        conv_strip_kernel<true><<<dim3(blocks), dim3(512), 0, ctx->stream>>>(p);
+    else
+        conv_strip_kernel<false><<<dim3(blocks), dim3(512), 0, ctx->stream>>>(p);
 }

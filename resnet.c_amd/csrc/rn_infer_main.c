@@ -4,7 +4,7 @@
  * print "max index is N" per image.  The reference hard-codes everything (ResNet-152,
  * B = 1, paths); here the same defaults can be overridden from the command line.
  *
- *   rn_infer [--arch 50|101|152] [--weights DIR] [--input FILE] [--batch B]
+ *   rn_infer [--arch 18|34|50|101|152] [--weights DIR] [--input FILE] [--batch B]
  *            [--mode fused|ops] [--device N | --devices a,b,c,...]
  *
  * --devices shards the batch contiguously over the listed devices (rn_shard_*: one host
@@ -110,7 +110,7 @@ int main(int argc, char **argv)
         }
         else if (!strcmp(a, "--mode") && v) { mode = strcmp(v, "ops") ? RN_FWD_FUSED : RN_FWD_REFERENCE_OPS; ++i; }
         else {
-            fprintf(stderr, "usage: %s [--arch 50|101|152] [--weights DIR] [--input FILE] "
+            fprintf(stderr, "usage: %s [--arch 18|34|50|101|152] [--weights DIR] [--input FILE] "
                             "[--batch B] [--mode fused|ops] [--device N | --devices a,b,...]\n", argv[0]);
             return 2;
         }

@@ -5,7 +5,9 @@
  *   createLayer / createResnet152   main.cu:53-89,109-125  -> rn_model_create + set_tensor/load_dir
  *   layerForward                    main.cu:127-166        -> block_forward
  *   resnet152Forward                main.cu:168-226        -> rn_model_forward
- * generalised over the block counts (ResNet-50/101/152) and the batch size.
+ * generalised over the block counts (ResNet-50/101/152) and the batch size, plus the basic-block
+ * networks ResNet-18/34 (torchvision's layout: two 3x3 convolutions per block, expansion 1; the
+ * reference ships bottleneck networks only).
  *
  * Differences that are deliberate (MI355X-first):
  *   - activations are NHWC inside; the NCHW input image is converted once (to a
@@ -54,8 +56,9 @@ typedef struct {
 
 typedef struct {
     char name[RN_MAX_KEY];
-    int conv1, conv2, conv3, ds; /* indices into convs; ds = -1 when absent */
-    /* blocks with a downsample branch: conv3 and downsample as one contraction
+    int conv1, conv2, conv3, ds; /* indices into convs; ds = -1 when absent, conv3 = -1 in a basic block */
+    int tail;                    /* the convolution that carries the residual: conv3, or conv2 of a basic block */
+    /* blocks with a downsample branch: the tail convolution and downsample as one contraction
      * (rn_conv2d_nhwc_pair_forward_dt): rows [Cout][K3 + Kd] with both batch-norm scales
      * folded in, and the sum of the two shifts */
     void *pair_packed;
@@ -86,7 +89,12 @@ typedef struct {
 struct rn_model {
     rn_ctx *ctx;
     int arch;
+    int basic;        /* ResNet-18/34: basic blocks (two 3x3 convolutions, expansion 1) */
     int depths[4];
+    uint64_t feat;    /* width of the final feature map: 2048 (bottleneck) or 512 (basic) */
+    /* per-image element counts of the arenas (ensure_acts) */
+    uint64_t x4_img, p_img, ds_img, t1_img, t2_img;
+    uint64_t s1_img; /* the first stage's output per image (56*56*256, or 56*56*64): slices of a depth-first front */
     rn_param *params;
     uint64_t n_params;
     rn_conv *convs;
@@ -140,6 +148,7 @@ struct rn_model {
 static const uint64_t kWidths[4][3] = {{64, 64, 256}, {256, 128, 512}, {512, 256, 1024},
                                        {1024, 512, 2048}};
 static const uint64_t kStrides[4] = {1, 2, 2, 2};
+static const uint64_t kBasicWidths[4] = {64, 128, 256, 512};
 
 static int add_param(rn_model *m, const char *key, uint64_t numel)
 {
@@ -179,6 +188,7 @@ static int add_conv(rn_model *m, const char *name, const char *bn_name, uint64_t
 int rn_model_create(rn_ctx *ctx, rn_model **out, int arch)
 {
     static const int d50[4] = {3, 4, 6, 3}, d101[4] = {3, 4, 23, 3}, d152[4] = {3, 8, 36, 3};
+    static const int d18[4] = {2, 2, 2, 2}, d34[4] = {3, 4, 6, 3};
     const int *d;
     rn_model *m;
     int li, bi, total_blocks = 0, max_convs;
@@ -187,6 +197,8 @@ int rn_model_create(rn_ctx *ctx, rn_model **out, int arch)
     if (arch == 50) d = d50;
     else if (arch == 101) d = d101;
     else if (arch == 152) d = d152;
+    else if (arch == 18) d = d18;
+    else if (arch == 34) d = d34;
     else return RN_ERR_UNSUPPORTED;
     m = (rn_model *)calloc(1, sizeof(rn_model));
     if (m) m->pair_fusion = m->stem_exact = 1;
@@ -197,6 +209,16 @@ int rn_model_create(rn_ctx *ctx, rn_model **out, int arch)
     if (!m) return RN_ERR_NOMEM;
     m->ctx = ctx;
     m->arch = arch;
+    m->basic = arch == 18 || arch == 34;
+    m->feat = m->basic ? kBasicWidths[3] : kWidths[3][2];
+    /* arenas: x4 the input image, p0 / p1 the block outputs (and the 112x112x64 stem output), dsb the
+     * downsample branch, t1 / t2 the block-internal tensors (a basic block has one: conv1's output) */
+    m->x4_img = (uint64_t)230 * 230 * 4; /* bf16 models keep a 3-pixel zero border */
+    m->p_img = (uint64_t)112 * 112 * 64; /* == 56*56*256 */
+    m->ds_img = m->basic ? (uint64_t)28 * 28 * 128 : m->p_img;
+    m->t1_img = m->basic ? (uint64_t)56 * 56 * 64 : (uint64_t)56 * 56 * 128; /* layer2.0 conv1 of a bottleneck */
+    m->t2_img = m->basic ? 0 : m->t1_img;
+    m->s1_img = (uint64_t)56 * 56 * (m->basic ? kBasicWidths[0] : kWidths[0][2]);
     for (li = 0; li < 4; ++li) {
         m->depths[li] = d[li];
         total_blocks += d[li];
@@ -217,17 +239,35 @@ int rn_model_create(rn_ctx *ctx, rn_model **out, int arch)
         for (bi = 0; bi < d[li]; ++bi) {
             rn_block *b = &m->blocks[m->n_blocks++];
             char pre[RN_MAX_KEY], name[RN_MAX_KEY + 16], bn[RN_MAX_KEY + 16];
-            const uint64_t cin = bi == 0 ? kWidths[li][0] : kWidths[li][2];
-            const uint64_t mid = kWidths[li][1], cout = kWidths[li][2];
             const uint64_t stride = bi == 0 ? kStrides[li] : 1;
+            uint64_t cin, mid, cout;
+            if (m->basic) {
+                cout = mid = kBasicWidths[li];
+                cin = bi == 0 && li > 0 ? kBasicWidths[li - 1] : cout;
+            } else {
+                cin = bi == 0 ? kWidths[li][0] : kWidths[li][2];
+                mid = kWidths[li][1];
+                cout = kWidths[li][2];
+            }
             snprintf(pre, sizeof(pre), "layer%d.%d", li + 1, bi);
             snprintf(b->name, RN_MAX_KEY, "%s", pre);
             b->ds = -1;
+            b->conv3 = -1;
             /* projection shortcut iff block 0 and (stride != 1 or cin != cout): main.cu:71 */
             if (bi == 0 && (stride != 1 || cin != cout)) {
                 snprintf(name, sizeof(name), "%s.downsample.0", pre);
                 snprintf(bn, sizeof(bn), "%s.downsample.1", pre);
                 b->ds = add_conv(m, name, bn, cin, cout, 1, stride, 0);
+            }
+            if (m->basic) {
+                /* torchvision BasicBlock: conv1 3x3 / stride / pad 1, conv2 3x3 / 1 / 1 */
+                snprintf(name, sizeof(name), "%s.conv1", pre);
+                snprintf(bn, sizeof(bn), "%s.bn1", pre);
+                b->conv1 = add_conv(m, name, bn, cin, cout, 3, stride, 1);
+                snprintf(name, sizeof(name), "%s.conv2", pre);
+                snprintf(bn, sizeof(bn), "%s.bn2", pre);
+                b->conv2 = b->tail = add_conv(m, name, bn, cout, cout, 3, 1, 1);
+                continue;
             }
             snprintf(name, sizeof(name), "%s.conv1", pre);
             snprintf(bn, sizeof(bn), "%s.bn1", pre);
@@ -237,10 +277,10 @@ int rn_model_create(rn_ctx *ctx, rn_model **out, int arch)
             b->conv2 = add_conv(m, name, bn, mid, mid, 3, stride, 1); /* stride on the 3x3 */
             snprintf(name, sizeof(name), "%s.conv3", pre);
             snprintf(bn, sizeof(bn), "%s.bn3", pre);
-            b->conv3 = add_conv(m, name, bn, mid, cout, 1, 1, 0);
+            b->conv3 = b->tail = add_conv(m, name, bn, mid, cout, 1, 1, 0);
         }
     }
-    m->fc_w = add_param(m, "fc.weight", (uint64_t)RN_CLASSES * 2048);
+    m->fc_w = add_param(m, "fc.weight", (uint64_t)RN_CLASSES * m->feat);
     m->fc_b = add_param(m, "fc.bias", RN_CLASSES);
     *out = m;
     return RN_OK;
@@ -455,7 +495,7 @@ int rn_model_finalize(rn_model *m)
         rn_block *b = &m->blocks[c];
         const rn_conv *c3, *cd;
         if (b->ds < 0) continue;
-        c3 = &m->convs[b->conv3];
+        c3 = &m->convs[b->tail];
         cd = &m->convs[b->ds];
         if (!b->pair_packed) {
             st = rn_malloc(m->ctx, &b->pair_packed,
@@ -475,12 +515,12 @@ int rn_model_finalize(rn_model *m)
         if (st != RN_OK) return st;
     }
     if (m->dtype != RN_DTYPE_F32) {
-        /* fc.weight [1000][2048] is a 1x1 convolution panel: same packer, k = 1 */
+        /* fc.weight [1000][feat] is a 1x1 convolution panel: same packer, k = 1 */
         if (!m->fc_packed) {
-            st = rn_malloc(m->ctx, &m->fc_packed, (uint64_t)RN_CLASSES * 2048 * elem_size(m));
+            st = rn_malloc(m->ctx, &m->fc_packed, (uint64_t)RN_CLASSES * m->feat * elem_size(m));
             if (st != RN_OK) return st;
         }
-        st = rn_conv2d_pack_weight_dt(m->ctx, m->dtype, m->params[m->fc_w].dev, m->fc_packed, 2048,
+        st = rn_conv2d_pack_weight_dt(m->ctx, m->dtype, m->params[m->fc_w].dev, m->fc_packed, m->feat,
                                       RN_CLASSES, 1);
         if (st != RN_OK) return st;
     }
@@ -489,11 +529,6 @@ int rn_model_finalize(rn_model *m)
     m->finalized = 1;
     return RN_OK;
 }
-
-/* per-image element counts of the arenas (see the header comment) */
-#define X4_PER_IMG ((uint64_t)230 * 230 * 4) /* bf16 models keep a 3-pixel zero border */
-#define P_PER_IMG ((uint64_t)56 * 56 * 256) /* == 112*112*64, the stem output */
-#define T_PER_IMG ((uint64_t)56 * 56 * 128) /* layer2.0 conv1 output, the largest mid tensor */
 
 int rn_ctx_graphs_live(const rn_ctx *ctx); /* rn_ctx.hip */
 
@@ -506,20 +541,20 @@ static int ensure_acts(rn_model *m, uint64_t B)
     free_acts(m);
     {
         const uint64_t es = elem_size(m);
-        st = rn_malloc(m->ctx, (void **)&m->x4, B * X4_PER_IMG * es);
-        if (st == RN_OK) st = rn_malloc(m->ctx, (void **)&m->p0, B * P_PER_IMG * es);
-        if (st == RN_OK) st = rn_malloc(m->ctx, (void **)&m->p1, B * P_PER_IMG * es);
-        if (st == RN_OK) st = rn_malloc(m->ctx, (void **)&m->dsb, B * P_PER_IMG * es);
-        if (st == RN_OK) st = rn_malloc(m->ctx, (void **)&m->t1, B * T_PER_IMG * es);
-        if (st == RN_OK) st = rn_malloc(m->ctx, (void **)&m->t2, B * T_PER_IMG * es);
-        if (st == RN_OK) st = rn_malloc(m->ctx, (void **)&m->pooled, B * 2048 * es);
+        st = rn_malloc(m->ctx, (void **)&m->x4, B * m->x4_img * es);
+        if (st == RN_OK) st = rn_malloc(m->ctx, (void **)&m->p0, B * m->p_img * es);
+        if (st == RN_OK) st = rn_malloc(m->ctx, (void **)&m->p1, B * m->p_img * es);
+        if (st == RN_OK) st = rn_malloc(m->ctx, (void **)&m->dsb, B * m->ds_img * es);
+        if (st == RN_OK) st = rn_malloc(m->ctx, (void **)&m->t1, B * m->t1_img * es);
+        if (st == RN_OK && m->t2_img) st = rn_malloc(m->ctx, (void **)&m->t2, B * m->t2_img * es);
+        if (st == RN_OK) st = rn_malloc(m->ctx, (void **)&m->pooled, B * m->feat * es);
     }
     if (st != RN_OK) {
         free_acts(m);
         return st;
     }
     m->batch_cap = B;
-    m->act_bytes = B * (X4_PER_IMG + 3 * P_PER_IMG + 2 * T_PER_IMG + 2048) * elem_size(m);
+    m->act_bytes = B * (m->x4_img + 2 * m->p_img + m->ds_img + m->t1_img + m->t2_img + m->feat) * elem_size(m);
     return RN_OK;
 }
 
@@ -746,12 +781,13 @@ static int op_conv(rn_model *m, const rn_conv *cv, const void *x, void *y, uint6
     return prof_end(m);
 }
 
-/* conv3 (input t, [B,H,W,c3->cin]) + downsample (input x, [B,H2,W2,cd->cin]) + shifts + ReLU */
+/* conv3 (input t, [B,H,W,c3->cin]) + downsample (input x, [B,H2,W2,cd->cin]) + shifts + ReLU; in a
+ * basic block conv2 (3x3 / 1 / 1, same H x W in and out) takes conv3's place */
 static int op_pair(rn_model *m, rn_block *b, const void *t, const void *x, void *y, uint64_t B,
                    uint64_t H, uint64_t W, uint64_t H2, uint64_t W2)
 {
-    const rn_conv *c3 = &m->convs[b->conv3], *cd = &m->convs[b->ds];
-    const double M = (double)(B * H * W), K = (double)(c3->cin + cd->cin);
+    const rn_conv *c3 = &m->convs[b->tail], *cd = &m->convs[b->ds];
+    const double M = (double)(B * H * W), K = (double)(c3->cin * c3->k * c3->k + cd->cin);
     const double es = (double)elem_size(m);
     const double bytes = es * ((double)(B * H * W * c3->cin) + (double)(B * H2 * W2 * cd->cin) +
                                K * (double)c3->cout + M * (double)c3->cout);
@@ -765,11 +801,11 @@ static int op_pair(rn_model *m, rn_block *b, const void *t, const void *x, void 
     if (m->recording) {
         rn_conv_call *c = next_call(m);
         if (!c) return RN_ERR_NOMEM;
-        c->conv = b->conv3;
+        c->conv = b->tail;
         c->pair_block = (int)(b - m->blocks);
         c->exact = 0;
         c->x = t; c->x2 = x; c->y = y;
-        c->B = B; c->H = H; c->W = W; c->pad = 0; c->H2 = H2; c->W2 = W2;
+        c->B = B; c->H = H; c->W = W; c->pad = c3->pad; c->H2 = H2; c->W2 = W2;
         c->has_ep = 1;
         c->ep = ep;
     }
@@ -791,7 +827,9 @@ static int op_pair(rn_model *m, rn_block *b, const void *t, const void *x, void 
 static int chain_applies(const rn_model *m, const rn_block *b, int mode)
 {
     const int bi = (int)(b - m->blocks);
-    const rn_conv *c3 = &m->convs[b->conv3], *n1;
+    const rn_conv *c3, *n1;
+    if (m->basic) return 0; /* chains are 1x1 -> 1x1; a basic block ends in a 3x3 */
+    c3 = &m->convs[b->conv3];
     if (!m->chain || mode != RN_FWD_FUSED || m->recording) return 0;
     if (b->ds >= 0) { /* first block of a stage: only as the fused pair at equal resolution (stage 1) */
         const rn_conv *cd = &m->convs[b->ds];
@@ -885,9 +923,59 @@ static int op_stem_pool(rn_model *m, const rn_conv *stem, const float *input_nch
     return prof_end(m);
 }
 
+/* one basic block (torchvision BasicBlock): relu(bn2(conv2(relu(bn1(conv1(x))))) + shortcut).  The
+ * stride is on conv1.  Fused: conv1 + bn1 + ReLU, then conv2 + bn2 + shortcut + ReLU; with pair
+ * fusion, block 0 of stages 2-4 runs conv2 and the downsample branch as one contraction (one fp32 sum
+ * over both K ranges instead of two rounded results added: not bit-neutral, as for the bottleneck
+ * pair).  Reference ops: conv, bn, relu, conv, bn, [downsample conv, bn], add, relu. */
+static int basic_block_forward(rn_model *m, rn_block *b, const float *x, float *y, uint64_t B,
+                               uint64_t *H, uint64_t *W, int mode)
+{
+    const rn_conv *c1 = &m->convs[b->conv1], *c2 = &m->convs[b->conv2];
+    const uint64_t h = *H, w = *W;
+    const uint64_t ho = rn_conv_output_size(h, c1->k, c1->stride, c1->pad);
+    const uint64_t wo = rn_conv_output_size(w, c1->k, c1->stride, c1->pad);
+    const float *shortcut = x;
+    if (mode == RN_FWD_FUSED) {
+        rn_epilogue ep;
+        const int pair = b->ds >= 0 && m->pair_fusion;
+        if (b->ds >= 0 && !pair) {
+            const rn_conv *cd = &m->convs[b->ds];
+            ep.scale = cd->scale; ep.shift = cd->shift; ep.residual = NULL; ep.relu = 0;
+            TRY(op_conv(m, cd, x, m->v.dsb, B, h, w, &ep, -1));
+            shortcut = m->v.dsb;
+        }
+        ep.scale = c1->scale; ep.shift = c1->shift; ep.residual = NULL; ep.relu = 1;
+        TRY(op_conv(m, c1, x, m->v.t1, B, h, w, &ep, -1));
+        if (pair) {
+            TRY(op_pair(m, b, m->v.t1, x, y, B, ho, wo, h, w));
+        } else {
+            ep.scale = c2->scale; ep.shift = c2->shift; ep.residual = shortcut;
+            TRY(op_conv(m, c2, m->v.t1, y, B, ho, wo, &ep, -1));
+        }
+    } else {
+        TRY(op_conv(m, c1, x, m->v.t1, B, h, w, NULL, -1));
+        TRY(op_bn(m, c1, m->v.t1, B, ho * wo));
+        TRY(op_relu(m, c1->name, m->v.t1, B * ho * wo * c1->cout));
+        TRY(op_conv(m, c2, m->v.t1, y, B, ho, wo, NULL, -1));
+        TRY(op_bn(m, c2, y, B, ho * wo));
+        if (b->ds >= 0) {
+            const rn_conv *cd = &m->convs[b->ds];
+            TRY(op_conv(m, cd, x, m->v.dsb, B, h, w, NULL, -1));
+            TRY(op_bn(m, cd, m->v.dsb, B, ho * wo));
+            shortcut = m->v.dsb;
+        }
+        TRY(op_add(m, b->name, y, shortcut, B * ho * wo * c2->cout));
+        TRY(op_relu(m, b->name, y, B * ho * wo * c2->cout));
+    }
+    *H = ho;
+    *W = wo;
+    return RN_OK;
+}
+
 /* one bottleneck block (layerForward body, main.cu:131-164).  x -> y, both NHWC. */
-static int block_forward(rn_model *m, rn_block *b, const float *x, float *y, uint64_t B,
-                         uint64_t *H, uint64_t *W, int mode)
+static int bottleneck_block_forward(rn_model *m, rn_block *b, const float *x, float *y, uint64_t B,
+                                    uint64_t *H, uint64_t *W, int mode)
 {
     const rn_conv *c1 = &m->convs[b->conv1], *c2 = &m->convs[b->conv2], *c3 = &m->convs[b->conv3];
     const uint64_t h = *H, w = *W;
@@ -942,12 +1030,23 @@ static int block_forward(rn_model *m, rn_block *b, const float *x, float *y, uin
     return RN_OK;
 }
 
+static int block_forward(rn_model *m, rn_block *b, const float *x, float *y, uint64_t B,
+                         uint64_t *H, uint64_t *W, int mode)
+{
+    return m->basic ? basic_block_forward(m, b, x, y, B, H, W, mode)
+                    : bottleneck_block_forward(m, b, x, y, B, H, W, mode);
+}
+
 int rn_ctx_wait_event(rn_ctx *ctx, rn_event *ev); /* rn_ctx.hip: the stream waits, not the host */
 
 /* B images whose activations live at image offset img_off of the arenas, queued on `run`. */
 enum { RN_PHASE_ALL = 0, RN_PHASE_FRONT = 1, RN_PHASE_BACK = 2 };
 
-static int forward_sub(rn_model *m, rn_ctx *run, uint64_t img_off, const float *input_nchw,
+/* slice_off: images into the part of a slice of a depth-first front.  The back phase reads the first stage's
+ * output of all slices as one batch, so in the ping-pong arenas a slice starts slice_off first-stage outputs
+ * into its part (in a basic-block network 1/4 of an arena image; the slice's larger stem tensor then reaches
+ * into the room of the slices after it, which run later on the same stream). */
+static int forward_sub(rn_model *m, rn_ctx *run, uint64_t img_off, uint64_t slice_off, const float *input_nchw,
                        uint64_t B, float *logits, int mode, int phase)
 {
     const int nfront = m->depths[0]; /* blocks of the front phase: the first stage */
@@ -958,14 +1057,16 @@ static int forward_sub(rn_model *m, rn_ctx *run, uint64_t img_off, const float *
     int bi, saved_layout, st;
     {
         const uint64_t es = elem_size(m);
+        const uint64_t p_off = img_off * m->p_img + slice_off * m->s1_img;
         m->run = run;
-        m->v.x4 = (float *)((char *)m->x4 + img_off * X4_PER_IMG * es);
-        m->v.p0 = (float *)((char *)m->p0 + img_off * P_PER_IMG * es);
-        m->v.p1 = (float *)((char *)m->p1 + img_off * P_PER_IMG * es);
-        m->v.dsb = (float *)((char *)m->dsb + img_off * P_PER_IMG * es);
-        m->v.t1 = (float *)((char *)m->t1 + img_off * T_PER_IMG * es);
-        m->v.t2 = (float *)((char *)m->t2 + img_off * T_PER_IMG * es);
-        m->v.pooled = (float *)((char *)m->pooled + img_off * 2048 * es);
+        img_off += slice_off;
+        m->v.x4 = (float *)((char *)m->x4 + img_off * m->x4_img * es);
+        m->v.p0 = (float *)((char *)m->p0 + p_off * es);
+        m->v.p1 = (float *)((char *)m->p1 + p_off * es);
+        m->v.dsb = (float *)((char *)m->dsb + img_off * m->ds_img * es);
+        m->v.t1 = (float *)((char *)m->t1 + img_off * m->t1_img * es);
+        m->v.t2 = m->t2 ? (float *)((char *)m->t2 + img_off * m->t2_img * es) : NULL; /* none in a basic block */
+        m->v.pooled = (float *)((char *)m->pooled + img_off * m->feat * es);
     }
     m->cur_mode = mode;
     m->t1_ready = 0;
@@ -1063,23 +1164,23 @@ static int forward_sub(rn_model *m, rn_ctx *run, uint64_t img_off, const float *
         if (st != RN_OK || phase == RN_PHASE_FRONT) break;
     tail_ops:
         /* global 7x7 average (main.cu:120,213) then fc (main.cu:122,224) */
-        STEP(prof_begin(m, "avgpool2d", "avgpool", 0.0, es * (double)(B * 2048 * (H * W + 1))));
+        STEP(prof_begin(m, "avgpool2d", "avgpool", 0.0, es * (double)(B * m->feat * (H * W + 1))));
         STEP(rn_avgpool2d_nhwc_forward_dt(m->run, m->dtype, x, m->v.pooled, 7, 1, 0,
                                           rn_conv_output_size(H, 7, 1, 0),
-                                          rn_conv_output_size(W, 7, 1, 0), B, 2048, H, W));
+                                          rn_conv_output_size(W, 7, 1, 0), B, m->feat, H, W));
         STEP(prof_end(m));
-        STEP(prof_begin(m, "linear", "fc", 2.0 * (double)B * 2048.0 * RN_CLASSES,
-                        es * ((double)B * 2048.0 + 2048.0 * RN_CLASSES) +
+        STEP(prof_begin(m, "linear", "fc", 2.0 * (double)B * (double)m->feat * RN_CLASSES,
+                        es * ((double)(B * m->feat) + (double)m->feat * RN_CLASSES) +
                             4.0 * (RN_CLASSES + (double)B * RN_CLASSES)));
         if (bf16) {
             rn_epilogue ep;
             ep.scale = NULL; ep.shift = m->params[m->fc_b].dev; ep.residual = NULL; ep.relu = 0;
             STEP(rn_conv2d_nhwc_forward_dt(m->run, m->dtype, RN_DTYPE_F32, m->v.pooled, logits,
-                                           m->fc_packed, 1, 1, 0, 1, 1, B, 2048, RN_CLASSES, 1, 1,
+                                           m->fc_packed, 1, 1, 0, 1, 1, B, m->feat, RN_CLASSES, 1, 1,
                                            &ep));
         } else {
             STEP(rn_linear_forward(m->run, m->v.pooled, logits, m->params[m->fc_w].dev,
-                                   m->params[m->fc_b].dev, B, 2048, RN_CLASSES));
+                                   m->params[m->fc_b].dev, B, m->feat, RN_CLASSES));
         }
         STEP(prof_end(m));
 #undef STEP
@@ -1114,14 +1215,14 @@ static int forward_part(rn_model *m, rn_ctx *run, uint64_t img_off, const float 
     int fp = m->front_parts, j;
     uint64_t lo = 0;
     while (fp > 1 && B / (uint64_t)fp < RN_FRONT_MIN_SLICE) fp /= 2;
-    if (fp < 2) return forward_sub(m, run, img_off, input_nchw, B, logits, mode, RN_PHASE_ALL);
+    if (fp < 2) return forward_sub(m, run, img_off, 0, input_nchw, B, logits, mode, RN_PHASE_ALL);
     for (j = 0; j < fp; ++j) {
         const uint64_t hi = B * (uint64_t)(j + 1) / (uint64_t)fp;
-        TRY(forward_sub(m, run, img_off + lo, input_nchw + lo * 3 * 224 * 224, hi - lo, logits, mode,
+        TRY(forward_sub(m, run, img_off, lo, input_nchw + lo * 3 * 224 * 224, hi - lo, logits, mode,
                         RN_PHASE_FRONT));
         lo = hi;
     }
-    return forward_sub(m, run, img_off, input_nchw, B, logits, mode, RN_PHASE_BACK);
+    return forward_sub(m, run, img_off, 0, input_nchw, B, logits, mode, RN_PHASE_BACK);
 }
 
 /* One sub-batch: every tensor of it stays below the kernels' 2^29-element range.  Large enough,

@@ -20,7 +20,10 @@ from . import _lib as L
 from . import nn, weights
 from .tensor import Context, Device, FloatTensor, Shape, get_ctx
 
-ARCH_ID = {"resnet50": 50, "resnet101": 101, "resnet152": 152}
+# names the C driver takes (rn_model_create): the bottleneck networks, and the basic-block
+# ResNet-18/34 (NativeModel / ShardedModel only: the reference-shaped graph below is bottleneck-only,
+# like the reference)
+ARCH_ID = {"resnet18": 18, "resnet34": 34, "resnet50": 50, "resnet101": 101, "resnet152": 152}
 
 
 # ---------------------------------------------------------------------------

@@ -16,6 +16,9 @@ Two things live here:
 The layer table follows the reference's model factory
 (``cuda/inference/main.cu:53-89,109-125``): bottleneck blocks with the stride
 on the 3x3 convolution and a projection shortcut on block 0 of every stage.
+ResNet-18/34, which the reference does not ship, follow torchvision's
+``BasicBlock``: two 3x3 convolutions (the stride on the first), expansion 1,
+stage widths 64/128/256/512, a projection shortcut on block 0 of stages 2-4.
 """
 from __future__ import annotations
 
@@ -33,6 +36,12 @@ DEPTHS = {
     "resnet101": (3, 4, 23, 3),
     "resnet152": (3, 8, 36, 3),  # main.cu:116-119
 }
+# basic-block networks: not in DEPTHS, whose names are the bottleneck networks (depths_of)
+BASIC_DEPTHS = {
+    "resnet18": (2, 2, 2, 2),
+    "resnet34": (3, 4, 6, 3),
+}
+BASIC_WIDTHS = (64, 128, 256, 512)
 NUM_CLASSES = 1000
 BN_FIELDS = ("weight", "bias", "running_mean", "running_var")
 
@@ -44,9 +53,29 @@ def depths_of(arch: str) -> Tuple[int, int, int, int]:
         raise ValueError(f"unknown arch {arch!r}; expected one of {sorted(DEPTHS)}") from None
 
 
+def block_kind(arch: str) -> str:
+    """"bottleneck" (ResNet-50/101/152) or "basic" (ResNet-18/34)."""
+    if arch in BASIC_DEPTHS:
+        return "basic"
+    depths_of(arch)  # raises for an unknown name
+    return "bottleneck"
+
+
+def feature_width(arch: str) -> int:
+    """Channels of the last stage, the input width of fc: 2048 or 512."""
+    return BASIC_WIDTHS[-1] if block_kind(arch) == "basic" else STAGE_WIDTHS[-1][2]
+
+
 def conv_specs(arch: str) -> List[Tuple[str, int, int, int, int, int]]:
     """(name, cin, cout, k, stride, pad) for every convolution, in forward order."""
     out = [("conv1", 3, 64, 7, 2, 3)]
+    if block_kind(arch) == "basic":
+        for pre, cin, cout, stride, has_ds in iter_basic_blocks(arch):
+            if has_ds:
+                out.append((f"{pre}.downsample.0", cin, cout, 1, stride, 0))
+            out.append((f"{pre}.conv1", cin, cout, 3, stride, 1))
+            out.append((f"{pre}.conv2", cout, cout, 3, 1, 1))
+        return out
     for li, ((cin, mid, cout), stride, n) in enumerate(
         zip(STAGE_WIDTHS, STAGE_STRIDES, depths_of(arch)), start=1
     ):
@@ -78,13 +107,14 @@ def tensor_specs(arch: str) -> List[Tuple[str, Tuple[int, ...]]]:
         bn = bn_of(name)
         for f in BN_FIELDS:
             specs.append((f"{bn}.{f}", (cout,)))
-    specs.append(("fc.weight", (NUM_CLASSES, 2048)))
+    specs.append(("fc.weight", (NUM_CLASSES, feature_width(arch))))
     specs.append(("fc.bias", (NUM_CLASSES,)))
     return specs
 
 
 def param_count(arch: str) -> int:
-    """Learnable parameters (running stats excluded), e.g. 25,557,032 for resnet50."""
+    """Learnable parameters (running stats excluded), e.g. 25,557,032 for resnet50, 11,689,512 for
+    resnet18."""
     n = 0
     for key, shape in tensor_specs(arch):
         if key.endswith("running_mean") or key.endswith("running_var"):
@@ -137,7 +167,8 @@ def generate_tensor(key: str, shape, seed: int = 0) -> np.ndarray:
     conv: He-uniform over fan_in; BN gamma in [0.5,1.5), beta and running mean in
     [-0.1,0.1), running var in [0.5,1.5); fc uniform(+-1/sqrt(in)).  The last
     batch-norm of every block (bn3) gets a smaller gamma so the residual stream
-    of the 50-block network stays O(1).
+    of the 50-block network stays O(1).  The fc bound stays 1/sqrt(2048) for every
+    architecture.  Basic blocks: see generate_state.
     """
     if key.endswith("running_var"):
         return _uniform(key, shape, 0.5, 1.5, seed)
@@ -157,8 +188,23 @@ def generate_tensor(key: str, shape, seed: int = 0) -> np.ndarray:
     return _uniform(key, shape, 0.5, 1.5, seed)
 
 
+def _basic_last_bn(key: str) -> bool:
+    """gamma of a basic block's last batch-norm (layerX.Y.bn2.weight)"""
+    return key.startswith("layer") and key.endswith(".bn2.weight")
+
+
 def generate_state(arch: str, seed: int = 0) -> Dict[str, np.ndarray]:
-    return {k: generate_tensor(k, s, seed) for k, s in tensor_specs(arch)}
+    """Every tensor of `arch` from generate_tensor.  In a basic-block network the block's last
+    batch-norm is bn2: its gamma gets the damping bn3's gets (generate_tensor itself, and with it
+    every tensor of the bottleneck networks, is unchanged)."""
+    basic = block_kind(arch) == "basic"
+    out = {}
+    for k, s in tensor_specs(arch):
+        if basic and _basic_last_bn(k):
+            out[k] = _uniform(k, s, 0.02, 0.1, seed)
+        else:
+            out[k] = generate_tensor(k, s, seed)
+    return out
 
 
 def generate_input(batch: int, seed: int = 0, hw: int = 224, name: str = "input") -> np.ndarray:
@@ -205,3 +251,39 @@ def iter_blocks(arch: str) -> Iterator[Tuple[str, int, int, int, int, bool]]:
             b_stride = stride if bi == 0 else 1
             yield (f"layer{li}.{bi}", b_in, mid, cout, b_stride,
                    bi == 0 and (b_stride != 1 or b_in != cout))
+
+
+def iter_basic_blocks(arch: str) -> Iterator[Tuple[str, int, int, int, bool]]:
+    """(prefix, cin, cout, stride, has_downsample) per basic block of ResNet-18/34."""
+    try:
+        depths = BASIC_DEPTHS[arch]
+    except KeyError:
+        raise ValueError(f"{arch!r} is not a basic-block network; expected one of {sorted(BASIC_DEPTHS)}") from None
+    prev = 64
+    for li, (cout, stride, n) in enumerate(zip(BASIC_WIDTHS, STAGE_STRIDES, depths), start=1):
+        for bi in range(n):
+            b_in = prev if bi == 0 else cout
+            b_stride = stride if bi == 0 else 1
+            yield (f"layer{li}.{bi}", b_in, cout, b_stride, b_stride != 1 or b_in != cout)
+        prev = cout
+
+
+def forward_flops(arch: str, hw: int = 224) -> int:
+    """Algorithmic FLOPs of one image: 2 x MACs of every convolution (output sizes tracked through
+    the network) and of fc.  8,178,368,512 for resnet50, 3,628,146,688 for resnet18."""
+    def out(n, k, s, p):
+        return (n + 2 * p - k) // s + 1
+    total, block_in, last = 0, {}, hw
+    for name, cin, cout, k, s, p in conv_specs(arch):
+        if name == "conv1":
+            n_in = hw
+        else:
+            pre = name.rsplit(".", 2)[0] if name.endswith("downsample.0") else name.rsplit(".", 1)[0]
+            if pre not in block_in:   # first convolution of a block: the previous block's output
+                block_in[pre] = last if len(block_in) else out(last, 3, 2, 1)  # max-pool after the stem
+            first = name.endswith(("downsample.0", ".conv1"))
+            n_in = block_in[pre] if first else last
+        n_out = out(n_in, k, s, p)
+        total += 2 * n_out * n_out * cout * cin * k * k
+        last = n_out
+    return total + 2 * feature_width(arch) * NUM_CLASSES
