@@ -5,10 +5,9 @@ import ctypes
 
 import numpy as np
 import pytest
-import torch
-import torch.nn.functional as F
 
 import resnet_c_amd as R
+from oracle import netref as N
 from oracle import oracle as O
 from resnet_c_amd import _lib as L
 from resnet_c_amd import ops
@@ -20,59 +19,9 @@ ARCHS = ["resnet18", "resnet34"]
 
 
 # ---------------------------------------------------------------------------
-# fp64 reference (torchvision BasicBlock semantics, eval-mode batch-norm)
+# fp64 reference (oracle/netref.py: torchvision BasicBlock semantics, eval-mode batch-norm) and inputs
 # ---------------------------------------------------------------------------
-def _t(state, key):
-    return torch.from_numpy(np.asarray(state[key], dtype=np.float64))
-
-
-def _bn(state, name, x):
-    return F.batch_norm(x, _t(state, f"{name}.running_mean"), _t(state, f"{name}.running_var"),
-                        _t(state, f"{name}.weight"), _t(state, f"{name}.bias"), False, 0.0, 1e-5)
-
-
-def ref_features(arch, state, x):
-    """float64 pooled features [B, 512]."""
-    with torch.no_grad():
-        h = torch.from_numpy(np.asarray(x, dtype=np.float64))
-        h = F.relu(_bn(state, "bn1", F.conv2d(h, _t(state, "conv1.weight"), stride=2, padding=3)))
-        h = F.max_pool2d(h, 3, 2, 1)
-        for pre, _cin, _cout, stride, has_ds in R.weights.iter_basic_blocks(arch):
-            t = F.relu(_bn(state, f"{pre}.bn1", F.conv2d(h, _t(state, f"{pre}.conv1.weight"), stride=stride, padding=1)))
-            t = _bn(state, f"{pre}.bn2", F.conv2d(t, _t(state, f"{pre}.conv2.weight"), stride=1, padding=1))
-            sc = h
-            if has_ds:
-                sc = _bn(state, f"{pre}.downsample.1", F.conv2d(h, _t(state, f"{pre}.downsample.0.weight"), stride=stride))
-            h = F.relu(t + sc)
-        return h.mean(dim=(2, 3)).numpy()
-
-
-def ref_logits(state, feats):
-    return feats @ np.asarray(state["fc.weight"], np.float64).T + np.asarray(state["fc.bias"], np.float64)
-
-
-# ---------------------------------------------------------------------------
-# inputs and fixtures
-# ---------------------------------------------------------------------------
-def structured_inputs(finch):
-    """16 images with content: the finch, its mirror, six shifted crops, eight seeded low-frequency fields."""
-    f = finch[0]
-    imgs = [f, f[:, :, ::-1]]
-    pad = np.pad(f, ((0, 0), (24, 24), (24, 24)), mode="reflect")
-    for dy, dx in ((0, 0), (48, 48), (0, 48), (48, 0), (12, 36), (40, 8)):
-        if (dy, dx) == (0, 0):
-            dy, dx = 24, 0
-        imgs.append(pad[:, dy:dy + 224, dx:dx + 224])
-    yy, xx = np.meshgrid(np.linspace(0, 1, 224), np.linspace(0, 1, 224), indexing="ij")
-    for s in range(8):
-        g = np.random.default_rng(500 + s)
-        img = np.zeros((3, 224, 224))
-        for _ in range(6):
-            fy, fx = g.integers(0, 4, 2)
-            ph = g.random(2) * 2 * np.pi
-            img += g.standard_normal((3, 1, 1)) * np.cos(np.pi * fy * yy + ph[0]) * np.cos(np.pi * fx * xx + ph[1])
-        imgs.append(img)
-    return np.ascontiguousarray(np.stack(imgs), dtype=np.float32)
+ref_features, ref_logits, structured_inputs, top2_gap = N.features_f64, N.ref_logits, N.structured_inputs, N.top2_gap
 
 
 @pytest.fixture(scope="module", params=ARCHS)
@@ -89,19 +38,7 @@ def recentred(arch, state, x):
     """The state with fc re-centred on the fp64 pooled features of x (bias = -W f_mean, W scaled to a
     logit spread of about 1), and the fp64 logits of x under it.  The synthetic fc gives every input the
     same top-1; re-centred, the top-1 follows the image."""
-    feats = ref_features(arch, state, x)
-    w = np.asarray(state["fc.weight"], np.float64)
-    d = (feats - feats.mean(0)) @ w.T
-    w = w / d.std()
-    st = dict(state)
-    st["fc.weight"] = w.astype(np.float32)
-    st["fc.bias"] = (-(w.astype(np.float32).astype(np.float64) @ feats.mean(0))).astype(np.float32)
-    return st, ref_logits(st, feats)
-
-
-def top2_gap(logits):
-    s = np.sort(logits, axis=1)
-    return s[:, -1] - s[:, -2]
+    return N.recentre_fc(state, ref_features(arch, state, x), spread=1.0)
 
 
 # ---------------------------------------------------------------------------

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import resnet_c_amd as R
+from oracle import netref as N
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -725,23 +726,21 @@ def test_two_host_threads_two_contexts(state50):
     assert np.array_equal(np.concatenate(results), want)
 
 
-def test_config3_bf16_b2048_as_eight_shards_on_one_device(state50, model50):
-    """BASELINE.json configs[3] end to end, rehearsed on ONE device: ResNet-50 bf16, global batch
-    2048 = 8 shards x 256 (rn_shard_* over devices 0 x 8: eight host threads, contexts and models).
-    Every shard's rows must be the bits of a single bf16 B=256 forward of the same images; and
-    SURVEY 8(d)'s parity bar for this config is measured over ALL 2048 images: top-1 agreement
-    with the fp32 engine >= 99 %, with the observed rate, the logit error and the margins of the
-    disagreeing images printed (DESIGN.md section 3 quotes them)."""
+def _config3_rehearsal(state, x, f32_model, label):
+    """ResNet-50 bf16 over the 2048 images x as 8 shards x 256 on device 0 (rn_shard_*: eight host threads,
+    contexts and models): every shard's rows are the bits of a single bf16 B=256 forward of the same images;
+    against the fp32 engine (f32_model) the logit error is printed and bounded, and a top-1 disagreement
+    can only sit where the fp32 margin is below twice the logit error.  Returns (agreement rate, max logit
+    error, distinct fp32 classes, fp32 logits)."""
     B, G = 2048, 8
-    x = R.weights.generate_input(B, seed=2048)
-    sh = R.ShardedModel([0] * G, "resnet50", state=state50, dtype="bf16")
+    sh = R.ShardedModel([0] * G, "resnet50", state=state, dtype="bf16")
     try:
         logits, top1 = sh.forward(x, fused=True)
     finally:
         sh.close()
     assert logits.shape == (B, 1000) and np.isfinite(logits).all()
     assert np.array_equal(top1, logits.argmax(1).astype(np.uint64))   # first maximum wins == numpy
-    one = R.NativeModel("resnet50", state=state50, dtype="bf16")
+    one = R.NativeModel("resnet50", state=state, dtype="bf16")
     try:
         for r in range(G):
             lo, hi = R.ShardedModel.bounds(B, r, G)
@@ -749,21 +748,59 @@ def test_config3_bf16_b2048_as_eight_shards_on_one_device(state50, model50):
             assert np.array_equal(one.forward(x[lo:hi], fused=True), logits[lo:hi]), r
     finally:
         one.close()
-    f32 = np.concatenate([model50.forward(x[i:i + 256], fused=True) for i in range(0, B, 256)])
+    f32 = np.concatenate([f32_model.forward(x[i:i + 256], fused=True) for i in range(0, B, 256)])
     agree = logits.argmax(1) == f32.argmax(1)
     rate = float(agree.mean())
     err = np.abs(logits - f32)
     top2 = np.sort(f32, axis=1)[:, -2:]
     margin = top2[:, 1] - top2[:, 0]
     rel = float(np.linalg.norm(logits - f32) / np.linalg.norm(f32))
-    print(f"\nconfigs[3] rehearsal: bf16 vs fp32 top-1 agreement {int(agree.sum())}/{B} = {rate:.4%}; "
+    classes = len(set(f32.argmax(1).tolist()))
+    print(f"\nconfigs[3] rehearsal, {label}: bf16 vs fp32 top-1 agreement {int(agree.sum())}/{B} = {rate:.4%}; "
           f"max|dlogit| {err.max():.4f}, mean {err.mean():.5f}, relative L2 {rel:.3e}; logits range "
           f"[{f32.min():.2f}, {f32.max():.2f}]; fp32 top-2 margins of the disagreeing images: "
-          f"{np.sort(margin[~agree])[:12].round(4).tolist()} (median margin of all images {np.median(margin):.3f})")
+          f"{np.sort(margin[~agree])[:12].round(4).tolist()} (median margin of all images {np.median(margin):.3f}); "
+          f"{classes} distinct fp32 classes")
     assert err.max() <= 0.25
     # a disagreement can only sit where the fp32 margin is below twice the logit error
     assert (margin[~agree] <= 2 * err.max()).all()
+    return rate, float(err.max()), classes, f32
+
+
+def test_config3_bf16_b2048_as_eight_shards_on_one_device(state50, model50):
+    """BASELINE.json configs[3] end to end, rehearsed on ONE device: ResNet-50 bf16, global batch
+    2048 = 8 shards x 256 (_config3_rehearsal).  SURVEY 8(d)'s parity bar for this config is measured
+    over ALL 2048 images: top-1 agreement with the fp32 engine >= 99 %, with the observed rate, the
+    logit error and the margins of the disagreeing images printed (DESIGN.md section 3 quotes them).
+    On these generated weights and i.i.d. inputs nearly every image is one class: the structured
+    rehearsal below is the one whose agreement says something."""
+    x = R.weights.generate_input(2048, seed=2048)
+    rate, _, _, _ = _config3_rehearsal(state50, x, model50, "i.i.d. inputs")
     assert rate >= 0.99, rate
+
+
+def test_config3_bf16_b2048_structured_images_top1(state50, finch):
+    """The same rehearsal on 2048 structured images (1024 finch crops and flips, 1024 low-frequency fields,
+    oracle/netref.py) with the fc re-centred on the fp64 features of the 16-image set (W as generated): the
+    fp32 top-1 spreads over at least 100 classes (measured on the MI355X: 160), so the agreement rate is not
+    one class agreeing with itself.  bf16 storage does not reach 99 % here: the classes of near-identical
+    finch crops lie a few 1e-3 apart, within bf16's logit error (measured 1965/2048 = 95.9 %, max |dlogit|
+    0.028 against an input-dependent spread of 0.21; the host emulation of the bf16 roundings agrees 97 %
+    with fp64 on 256 of these images).  Asserted: the measured rate less 40 images, the logit error below
+    0.2 of the spread, and the margin rule of the rehearsal, which holds every disagreement to an image whose
+    fp32 margin is below twice that error."""
+    x = N.structured_inputs(finch, 2048)
+    st, _ = N.recentre_fc(state50, N.features_f64("resnet50", state50, N.structured_inputs(finch)))
+    m32 = R.NativeModel("resnet50", state=st)
+    try:
+        rate, err, classes, f32 = _config3_rehearsal(st, x, m32, "structured inputs, fc re-centred")
+    finally:
+        m32.close()
+    spread = N.logit_spread(f32)
+    print(f"input-dependent fp32 logit spread {spread:.4f}; max |dlogit| = {err / spread:.4f} spread")
+    assert classes >= 100, classes
+    assert err <= 0.2 * spread, (err, spread)
+    assert rate >= 0.94, rate
 
 
 def test_sharded_stream_keeps_two_batches_in_flight(state50, model50, finch):
