@@ -291,6 +291,15 @@ RN_API int rn_conv2d_pack_weight_dt(rn_ctx *ctx, int dtype, const float *weight_
 RN_API int rn_nchw_to_nhwc_pad_dt(rn_ctx *ctx, int dtype, const float *src, void *dst, uint64_t B,
                                   uint64_t C, uint64_t H, uint64_t W, uint64_t Cpad,
                                   uint64_t border);
+/* The same tensor from a decoder's output: 8-bit interleaved RGB [B,H,W,3] -> `dtype` NHWC
+ * [B, H+2*border, W+2*border, Cpad] (Cpad 3 or 4), every element of it written by this launch,
+ *     x = ((float)px / 255.0f - mean[c]) / std[c]
+ * in fp32 with correctly rounded divisions: bit for bit what rn_nchw_to_nhwc_pad_dt(C = 3) writes
+ * from the fp32 NCHW image that preprocess.py (the reference's) normalises on the host, for a
+ * quarter of the bytes uploaded and no host arithmetic.  mean / std: three host floats each. */
+RN_API int rn_image_u8_to_nhwc_pad_dt(rn_ctx *ctx, int dtype, const uint8_t *img, void *dst,
+                                      uint64_t B, uint64_t H, uint64_t W, uint64_t Cpad,
+                                      uint64_t border, const float mean[3], const float std[3]);
 /* inp/packed_weight of `dtype`, out and epilogue->residual of `out_dtype` */
 RN_API int rn_conv2d_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const void *inp,
                                      void *out, const void *packed_weight, uint64_t kernel_size,
@@ -346,6 +355,16 @@ RN_API const char *rn_model_tensor_key(const rn_model *m, uint64_t index, uint64
  *     device cannot hold them). */
 RN_API int rn_model_forward(rn_model *m, const float *input_nchw, uint64_t B, float *logits,
                             int mode);
+/* The same forward from 8-bit RGB crops, [B,224,224,3] on the device: the first launch
+ * (rn_image_u8_to_nhwc_pad_dt with the ImageNet mean (0.485, 0.456, 0.406) and std (0.229, 0.224,
+ * 0.225)) replaces the layout launch of the float route and writes the same first tensor, so the
+ * logits are those of rn_model_forward on the host-normalised image, bit for bit, for every
+ * architecture, dtype, mode and batch split.  With rn_model_set_stem_pool_fusion(m, 2) -- patches
+ * fetched from the caller's NCHW image -- there is no NCHW image to fetch from: the byte route
+ * runs the padded-image form of the fused stem, as with fusion 1.  Tuned tiles (rn_model_tune, on
+ * the float entry point) serve both routes. */
+RN_API int rn_model_forward_u8(rn_model *m, const uint8_t *input_nhwc, uint64_t B, float *logits,
+                               int mode);
 /* Run one forward, then time every tile candidate of every convolution at batch B on the
  * device (events on the context's stream, on the buffers that forward used) and remember the fastest per layer for
  * that batch size.  Results do not change (candidates are bit-identical), only speed. */
@@ -547,6 +566,14 @@ RN_API uint64_t rn_pipeline_in_flight(const rn_pipeline *p);
  * ([n]) and n may each be NULL. */
 RN_API int rn_pipeline_submit_n(rn_pipeline *p, const float *host_input_nchw, uint64_t n);
 RN_API int rn_pipeline_collect_n(rn_pipeline *p, float *host_logits, uint64_t *host_top1, uint64_t *n);
+/* A pipeline for 8-bit RGB input ([n,224,224,3], rn_model_forward_u8): pinned staging and device
+ * input buffers of B*150528 bytes, a quarter of the fp32 pipeline's upload and staging copy.
+ * Collect as above.  A pipeline takes the input format it was created for: the float calls on a
+ * byte pipeline, and these on a float pipeline, return RN_ERR_INVALID. */
+RN_API int rn_pipeline_create_u8(rn_model *m, rn_pipeline **out, uint64_t B, int mode);
+RN_API int rn_pipeline_input_buffer_u8(rn_pipeline *p, uint8_t **host_staging);
+/* host_input_nhwc: n*150528 bytes in any host memory, or NULL / the staging pointer; n <= B */
+RN_API int rn_pipeline_submit_u8_n(rn_pipeline *p, const uint8_t *host_input_nhwc, uint64_t n);
 
 /* ---- one batch over several devices of a node ---------------------------------------
  * The multi-device form of the reference's main() (main.cu:228-254).  The forward has no
@@ -606,6 +633,16 @@ RN_API int rn_shard_stream_buffer(rn_shard *g, int rank, float **host_staging, u
 RN_API int rn_shard_submit(rn_shard *g, const float *host_input_nchw /* NULL: staging filled */);
 RN_API int rn_shard_collect(rn_shard *g, float *host_logits, uint64_t *host_top1);
 RN_API int rn_shard_in_flight(const rn_shard *g);
+/* The same from 8-bit RGB input ([B,224,224,3] host bytes; same contiguous split, shard r's images
+ * start r's lo * 150528 bytes in): one call, or a stream opened for bytes, whose staging buffers a
+ * decoder fills directly.  collect, in_flight and close are those above; the float submit / buffer
+ * calls on a byte stream, and the reverse, return RN_ERR_INVALID. */
+RN_API int rn_shard_forward_u8(rn_shard *g, const uint8_t *host_input_nhwc, uint64_t B,
+                               float *host_logits, uint64_t *host_top1, int mode);
+RN_API int rn_shard_stream_open_u8(rn_shard *g, uint64_t B, int mode);
+RN_API int rn_shard_stream_buffer_u8(rn_shard *g, int rank, uint8_t **host_staging, uint64_t *lo,
+                                     uint64_t *hi);
+RN_API int rn_shard_submit_u8(rn_shard *g, const uint8_t *host_input_nhwc /* NULL: staging filled */);
 RN_API int rn_shard_stream_close(rn_shard *g);
 
 #ifdef __cplusplus

@@ -96,6 +96,8 @@ SIGNATURES = {
     "rn_conv2d_packed_weight_numel_dt": (u64, [c_int, u64, u64, u64]),
     "rn_conv2d_pack_weight_dt": (c_int, [c_void_p, c_int, fptr, fptr, u64, u64, u64]),
     "rn_nchw_to_nhwc_pad_dt": (c_int, [c_void_p, c_int, fptr, fptr] + [u64] * 6),
+    "rn_image_u8_to_nhwc_pad_dt": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [u64] * 5
+                                   + [POINTER(c_float), POINTER(c_float)]),
     "rn_conv2d_nhwc_forward_dt": (c_int, [c_void_p, c_int, c_int, fptr, fptr, fptr] + [u64] * 10
                                   + [POINTER(Epilogue)]),
     "rn_conv2d_packed_weight_numel_exact": (u64, [u64, u64, u64]),
@@ -132,6 +134,7 @@ SIGNATURES = {
     "rn_model_finalize": (c_int, [c_void_p]),
     "rn_model_tensor_key": (c_char_p, [c_void_p, u64, POINTER(u64)]),
     "rn_model_forward": (c_int, [c_void_p, fptr, u64, fptr, c_int]),
+    "rn_model_forward_u8": (c_int, [c_void_p, c_void_p, u64, fptr, c_int]),
     "rn_model_tune": (c_int, [c_void_p, fptr, u64, fptr, c_int]),
     "rn_model_export_tuning": (c_int, [c_void_p, POINTER(u64), u64, POINTER(u64)]),
     "rn_model_import_tuning": (c_int, [c_void_p, POINTER(u64), u64]),
@@ -152,6 +155,9 @@ SIGNATURES = {
     "rn_pipeline_in_flight": (u64, [c_void_p]),
     "rn_pipeline_submit_n": (c_int, [c_void_p, c_void_p, u64]),
     "rn_pipeline_collect_n": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(u64)]),
+    "rn_pipeline_create_u8": (c_int, [c_void_p, POINTER(c_void_p), u64, c_int]),
+    "rn_pipeline_input_buffer_u8": (c_int, [c_void_p, POINTER(c_void_p)]),
+    "rn_pipeline_submit_u8_n": (c_int, [c_void_p, c_void_p, u64]),
     "rn_shard_bounds": (None, [u64, c_int, c_int, POINTER(u64), POINTER(u64)]),
     "rn_shard_create": (c_int, [POINTER(c_void_p), POINTER(c_int), c_int, c_int]),
     "rn_shard_destroy": (c_int, [c_void_p]),
@@ -171,6 +177,10 @@ SIGNATURES = {
     "rn_shard_collect": (c_int, [c_void_p, c_void_p, c_void_p]),
     "rn_shard_in_flight": (c_int, [c_void_p]),
     "rn_shard_stream_close": (c_int, [c_void_p]),
+    "rn_shard_forward_u8": (c_int, [c_void_p, c_void_p, u64, c_void_p, c_void_p, c_int]),
+    "rn_shard_stream_open_u8": (c_int, [c_void_p, u64, c_int]),
+    "rn_shard_stream_buffer_u8": (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(u64), POINTER(u64)]),
+    "rn_shard_submit_u8": (c_int, [c_void_p, c_void_p]),
 }
 
 _lib = None

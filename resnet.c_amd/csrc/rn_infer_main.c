@@ -4,8 +4,12 @@
  * print "max index is N" per image.  The reference hard-codes everything (ResNet-152,
  * B = 1, paths); here the same defaults can be overridden from the command line.
  *
- *   rn_infer [--arch 18|34|50|101|152] [--weights DIR] [--input FILE] [--batch B]
- *            [--mode fused|ops] [--device N | --devices a,b,c,...]
+ *   rn_infer [--arch 18|34|50|101|152] [--weights DIR] [--input FILE | --u8 FILE] [--batch B]
+ *            [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,c,...]
+ *
+ * --u8 FILE reads B x 150528 raw bytes, the decoder's 8-bit RGB crops ([B,224,224,3]), instead of
+ * the preprocessed fp32 file: the device normalises them (rn_model_forward_u8), same lines out.
+ * --dtype bf16 stores activations and weights as bf16 (fused mode only).
  *
  * --devices shards the batch contiguously over the listed devices (rn_shard_*: one host
  * thread + context + model per device, no data moves between devices) and prints the class
@@ -27,14 +31,35 @@
         }                                                                                 \
     } while (0)
 
+/* the whole file, which must hold exactly `want` bytes; NULL (and a message) otherwise */
+static void *read_exact(const char *path, uint64_t want, uint64_t B, int u8)
+{
+    void *host = malloc(want);
+    FILE *f = fopen(path, "rb");
+    if (!host || !f || fread(host, 1, want, f) != want || fgetc(f) != EOF) {
+        if (u8)
+            fprintf(stderr, "rn_infer: %s: %s: --u8 takes 224 x 224 x 3 8-bit RGB images only; the file does not "
+                            "hold exactly %llu bytes (batch %llu)\n", rn_status_string(RN_ERR_UNSUPPORTED), path,
+                    (unsigned long long)want, (unsigned long long)B);
+        else
+            fprintf(stderr, "rn_infer: %s: %s: the model driver takes 3 x 224 x 224 fp32 images only; the file "
+                            "does not hold exactly %llu floats (batch %llu)\n", rn_status_string(RN_ERR_UNSUPPORTED),
+                    path, (unsigned long long)(want / sizeof(float)), (unsigned long long)B);
+        if (f) fclose(f);
+        free(host);
+        return NULL;
+    }
+    fclose(f);
+    return host;
+}
+
 static int run_sharded(const int *devices, int ndev, int arch, const char *weights,
-                       const char *input, uint64_t B, int mode)
+                       const char *input, int u8, uint64_t B, int mode, int dtype)
 {
     rn_shard *g = NULL;
-    float *host = NULL;
+    void *host = NULL;
     uint64_t *idx = NULL, b;
-    const uint64_t want = B * 3 * 224 * 224;
-    FILE *f;
+    const uint64_t want = B * 3 * 224 * 224 * (u8 ? 1 : sizeof(float));
     int st;
     st = rn_shard_create(&g, devices, ndev, arch);
     if (st != RN_OK) { fprintf(stderr, "rn_infer: rn_shard_create: %s\n", rn_status_string(st)); return 1; }
@@ -48,6 +73,7 @@ static int run_sharded(const int *devices, int ndev, int arch, const char *weigh
         }                                                                                    \
     } while (0)
     SCHECK(rn_shard_load_dir(g, weights));
+    if (dtype != RN_DTYPE_F32) SCHECK(rn_shard_set_dtype(g, dtype));
     SCHECK(rn_shard_finalize(g));
     printf("created model\n");
     {   /* where every shard's host thread runs (stderr: stdout stays what the single-device run prints) */
@@ -60,17 +86,13 @@ static int run_sharded(const int *devices, int ndev, int arch, const char *weigh
                         cpus[0] ? cpus : "not bound");
         }
     }
-    host = (float *)malloc(want * sizeof(float));
     idx = (uint64_t *)malloc(B * sizeof(uint64_t));
-    f = fopen(input, "rb");
-    if (!host || !idx || !f || fread(host, sizeof(float), want, f) != want || fgetc(f) != EOF) {
-        fprintf(stderr, "rn_infer: %s: %s: the model driver takes 3 x 224 x 224 fp32 images only; the file "
-                        "does not hold exactly %llu floats (batch %llu)\n", rn_status_string(RN_ERR_UNSUPPORTED),
-                input, (unsigned long long)want, (unsigned long long)B);
-        return 1;
-    }
-    fclose(f);
-    SCHECK(rn_shard_forward(g, host, B, NULL, idx, mode));
+    host = read_exact(input, want, B, u8);
+    if (!host || !idx) return 1;
+    if (u8)
+        SCHECK(rn_shard_forward_u8(g, (const uint8_t *)host, B, NULL, idx, mode));
+    else
+        SCHECK(rn_shard_forward(g, (const float *)host, B, NULL, idx, mode));
 #undef SCHECK
     printf("Finished\n");
     for (b = 0; b < B; ++b) printf("max index is %llu\n", (unsigned long long)idx[b]);
@@ -82,7 +104,7 @@ static int run_sharded(const int *devices, int ndev, int arch, const char *weigh
 
 int main(int argc, char **argv)
 {
-    int arch = 152, device = 0, mode = RN_FWD_FUSED, i;
+    int arch = 152, device = 0, mode = RN_FWD_FUSED, dtype = RN_DTYPE_F32, u8 = 0, i;
     int devices[64], ndev = 0;
     uint64_t B = 1, numel = 0, b;
     const char *weights = "weights_bin";
@@ -90,6 +112,7 @@ int main(int argc, char **argv)
     rn_ctx *ctx = NULL;
     rn_model *model = NULL;
     float *inp = NULL, *logits = NULL;
+    uint8_t *inp_u8 = NULL;
     uint64_t *idx_dev = NULL, *idx = NULL;
 
     for (i = 1; i < argc; ++i) {
@@ -97,7 +120,12 @@ int main(int argc, char **argv)
         const char *v = (i + 1 < argc) ? argv[i + 1] : NULL;
         if (!strcmp(a, "--arch") && v) { arch = atoi(v); ++i; }
         else if (!strcmp(a, "--weights") && v) { weights = v; ++i; }
-        else if (!strcmp(a, "--input") && v) { input = v; ++i; }
+        else if (!strcmp(a, "--input") && v) { input = v; u8 = 0; ++i; }
+        else if (!strcmp(a, "--u8") && v) { input = v; u8 = 1; ++i; }
+        else if (!strcmp(a, "--dtype") && v && (!strcmp(v, "f32") || !strcmp(v, "bf16"))) {
+            dtype = strcmp(v, "bf16") ? RN_DTYPE_F32 : RN_DTYPE_BF16;
+            ++i;
+        }
         else if (!strcmp(a, "--batch") && v) { B = strtoull(v, NULL, 10); ++i; }
         else if (!strcmp(a, "--device") && v) { device = atoi(v); ++i; }
         else if (!strcmp(a, "--devices") && v) {
@@ -110,21 +138,31 @@ int main(int argc, char **argv)
         }
         else if (!strcmp(a, "--mode") && v) { mode = strcmp(v, "ops") ? RN_FWD_FUSED : RN_FWD_REFERENCE_OPS; ++i; }
         else {
-            fprintf(stderr, "usage: %s [--arch 18|34|50|101|152] [--weights DIR] [--input FILE] "
-                            "[--batch B] [--mode fused|ops] [--device N | --devices a,b,...]\n", argv[0]);
+            fprintf(stderr, "usage: %s [--arch 18|34|50|101|152] [--weights DIR] [--input FILE | --u8 FILE] "
+                            "[--batch B] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,...]\n",
+                    argv[0]);
             return 2;
         }
     }
     printf("Started\n");
-    if (ndev > 0) return run_sharded(devices, ndev, arch, weights, input, B, mode);
+    if (ndev > 0) return run_sharded(devices, ndev, arch, weights, input, u8, B, mode, dtype);
     CHECK(ctx, rn_ctx_create(&ctx, device, NULL));
     CHECK(ctx, rn_model_create(ctx, &model, arch));
     CHECK(ctx, rn_model_load_dir(model, weights));
+    if (dtype != RN_DTYPE_F32) CHECK(ctx, rn_model_set_dtype(model, dtype));
     CHECK(ctx, rn_model_finalize(model));
     printf("created model\n");
 
-    CHECK(ctx, rn_load_f32_file(ctx, input, &inp, &numel));
-    if (numel != B * 3 * 224 * 224) {
+    if (u8) {
+        void *host = read_exact(input, B * 224 * 224 * 3, B, 1);
+        if (!host) return 1;
+        CHECK(ctx, rn_malloc(ctx, (void **)&inp_u8, B * 224 * 224 * 3));
+        CHECK(ctx, rn_memcpy_h2d(ctx, inp_u8, host, B * 224 * 224 * 3));
+        free(host);
+    } else {
+        CHECK(ctx, rn_load_f32_file(ctx, input, &inp, &numel));
+    }
+    if (!u8 && numel != B * 3 * 224 * 224) {
         fprintf(stderr, "rn_infer: %s: the model driver takes 3 x 224 x 224 fp32 images only; %s holds "
                         "%llu floats, expected %llu for batch %llu\n", rn_status_string(RN_ERR_UNSUPPORTED), input,
                 (unsigned long long)numel, (unsigned long long)(B * 3 * 224 * 224),
@@ -133,7 +171,10 @@ int main(int argc, char **argv)
     }
     CHECK(ctx, rn_malloc(ctx, (void **)&logits, B * 1000 * sizeof(float)));
     CHECK(ctx, rn_malloc(ctx, (void **)&idx_dev, B * sizeof(uint64_t)));
-    CHECK(ctx, rn_model_forward(model, inp, B, logits, mode));
+    if (u8)
+        CHECK(ctx, rn_model_forward_u8(model, inp_u8, B, logits, mode));
+    else
+        CHECK(ctx, rn_model_forward(model, inp, B, logits, mode));
     CHECK(ctx, rn_argmax_forward(ctx, logits, idx_dev, B, 1000));
     idx = (uint64_t *)malloc(B * sizeof(uint64_t));
     if (!idx) return 1;
@@ -145,6 +186,7 @@ int main(int argc, char **argv)
     rn_free(ctx, idx_dev);
     rn_free(ctx, logits);
     rn_free(ctx, inp);
+    rn_free(ctx, inp_u8);
     rn_model_destroy(model);
     rn_ctx_destroy(ctx);
     return 0;

@@ -111,6 +111,7 @@ struct rn_model {
     int chain;               /* fused bf16 mode: conv3 of a 64- / 128-channel block + conv1 of the next block as one launch (default on) */
     int t1_ready;            /* the previous block's chained launch has produced this block's conv1 output */
     int stem_pool;           /* fused mode: stem + batch-norm + ReLU + max-pool as one launch (default on) */
+    int in_u8;               /* the forward being queued reads 8-bit RGB [B,224,224,3] (rn_model_forward_u8) */
     void *stem_pool_packed;  /* its weight panel, model dtype */
     void *fc_packed;  /* fc.weight in the model dtype (bf16 models only) */
     /* activation arenas, sized for batch_cap images */
@@ -1042,13 +1043,28 @@ int rn_ctx_wait_event(rn_ctx *ctx, rn_event *ev); /* rn_ctx.hip: the stream wait
 /* B images whose activations live at image offset img_off of the arenas, queued on `run`. */
 enum { RN_PHASE_ALL = 0, RN_PHASE_FRONT = 1, RN_PHASE_BACK = 2 };
 
+/* The byte route's first launch: 8-bit RGB [B,224,224,3] -> the normalised, padded image in x4, the
+ * tensor the float route's layout launch writes from the host-normalised NCHW image (same bits). */
+static const float kImageMean[3] = {0.485f, 0.456f, 0.406f}, kImageStd[3] = {0.229f, 0.224f, 0.225f};
+
+static int op_input_u8(rn_model *m, const void *input, uint64_t B, uint64_t cpad, uint64_t border)
+{
+    const double side = (double)(224 + 2 * border);
+    TRY(prof_begin(m, cpad == 3 ? "image_u8_to_nhwc3" : "image_u8_to_nhwc4", "input", 0.0,
+                   (double)B * (3.0 * 224 * 224 + (double)elem_size(m) * side * side * (double)cpad)));
+    TRY(rn_image_u8_to_nhwc_pad_dt(m->run, m->dtype, (const uint8_t *)input, m->v.x4, B, 224, 224, cpad, border,
+                                   kImageMean, kImageStd));
+    return prof_end(m);
+}
+
 /* slice_off: images into the part of a slice of a depth-first front.  The back phase reads the first stage's
  * output of all slices as one batch, so in the ping-pong arenas a slice starts slice_off first-stage outputs
  * into its part (in a basic-block network 1/4 of an arena image; the slice's larger stem tensor then reaches
  * into the room of the slices after it, which run later on the same stream). */
-static int forward_sub(rn_model *m, rn_ctx *run, uint64_t img_off, uint64_t slice_off, const float *input_nchw,
+static int forward_sub(rn_model *m, rn_ctx *run, uint64_t img_off, uint64_t slice_off, const void *input,
                        uint64_t B, float *logits, int mode, int phase)
 {
+    const float *input_nchw = (const float *)input; /* the float route's view of it */
     const int nfront = m->depths[0]; /* blocks of the front phase: the first stage */
     int fused_pool = 0;
     const rn_conv *stem;
@@ -1093,8 +1109,10 @@ static int forward_sub(rn_model *m, rn_ctx *run, uint64_t img_off, uint64_t slic
         if (bf16) {
             /* bf16 stem: [B,230,230,4] image with its own 3-pixel zero border, padding 0 */
             const uint64_t border = stem->pad;
-            const int from_nchw = m->stem_pool == 2;
-            if (!from_nchw) {
+            const int from_nchw = m->stem_pool == 2 && !m->in_u8; /* bytes: the padded-image form */
+            if (m->in_u8) {
+                STEP(op_input_u8(m, input, B, 4, border));
+            } else if (!from_nchw) {
                 STEP(prof_begin(m, "nchw_to_nhwc4", "input", 0.0,
                                 (double)B * (4.0 * 3 * 224 * 224 + es * 230 * 230 * 4)));
                 STEP(rn_nchw_to_nhwc_pad_dt(m->run, m->dtype, input_nchw, m->v.x4, B, 3, H, W, 4, border));
@@ -1115,9 +1133,11 @@ static int forward_sub(rn_model *m, rn_ctx *run, uint64_t img_off, uint64_t slic
             const uint64_t border = m->stem_exact ? stem->pad : 0;
             const uint64_t sh = H + 2 * border, sw = W + 2 * border;
             const int64_t form = m->stem_exact ? RN_PAD_EXACT : -1;
-            const int from_nchw = mode == RN_FWD_FUSED && m->stem_pool == 2 && m->stem_exact;
+            const int from_nchw = mode == RN_FWD_FUSED && m->stem_pool == 2 && m->stem_exact && !m->in_u8;
             if (from_nchw) {
                 /* no layout launch */
+            } else if (m->in_u8) {
+                STEP(op_input_u8(m, input, B, m->stem_exact ? 3 : 4, border));
             } else if (m->stem_exact) {
                 STEP(prof_begin(m, "nchw_to_nhwc3", "input", 0.0,
                                 4.0 * (double)B * (3.0 * 224 * 224 + 3.0 * 230 * 230)));
@@ -1127,7 +1147,7 @@ static int forward_sub(rn_model *m, rn_ctx *run, uint64_t img_off, uint64_t slic
                 STEP(prof_begin(m, "nchw_to_nhwc4", "input", 0.0, 4.0 * (double)(B * 224 * 224 * 7)));
                 STEP(rn_nchw_to_nhwc_pad(m->run, input_nchw, m->v.x4, B, 3, H, W, 4));
             }
-            if (!from_nchw) STEP(prof_end(m));
+            if (!from_nchw && !m->in_u8) STEP(prof_end(m));
             ho = rn_conv_output_size(H, stem->k, stem->stride, stem->pad);
             wo = rn_conv_output_size(W, stem->k, stem->stride, stem->pad);
             if (mode == RN_FWD_FUSED && m->stem_pool && m->stem_exact) {
@@ -1208,33 +1228,39 @@ static int parts_of(const rn_model *m, uint64_t B)
 }
 #define RN_FRONT_MIN_SLICE 16
 
+/* image `lo` of the caller's input: fp32 NCHW, or 8-bit RGB on the byte route */
+static const void *input_at(const rn_model *m, const void *input, uint64_t lo)
+{
+    return (const char *)input + lo * 3 * 224 * 224 * (m->in_u8 ? 1 : sizeof(float));
+}
+
 /* B images at image offset img_off on `run`: whole, or depth-first through the front */
-static int forward_part(rn_model *m, rn_ctx *run, uint64_t img_off, const float *input_nchw,
+static int forward_part(rn_model *m, rn_ctx *run, uint64_t img_off, const void *input,
                         uint64_t B, float *logits, int mode)
 {
     int fp = m->front_parts, j;
     uint64_t lo = 0;
     while (fp > 1 && B / (uint64_t)fp < RN_FRONT_MIN_SLICE) fp /= 2;
-    if (fp < 2) return forward_sub(m, run, img_off, 0, input_nchw, B, logits, mode, RN_PHASE_ALL);
+    if (fp < 2) return forward_sub(m, run, img_off, 0, input, B, logits, mode, RN_PHASE_ALL);
     for (j = 0; j < fp; ++j) {
         const uint64_t hi = B * (uint64_t)(j + 1) / (uint64_t)fp;
-        TRY(forward_sub(m, run, img_off, lo, input_nchw + lo * 3 * 224 * 224, hi - lo, logits, mode,
+        TRY(forward_sub(m, run, img_off, lo, input_at(m, input, lo), hi - lo, logits, mode,
                         RN_PHASE_FRONT));
         lo = hi;
     }
-    return forward_sub(m, run, img_off, 0, input_nchw, B, logits, mode, RN_PHASE_BACK);
+    return forward_sub(m, run, img_off, 0, input, B, logits, mode, RN_PHASE_BACK);
 }
 
 /* One sub-batch: every tensor of it stays below the kernels' 2^29-element range.  Large enough,
  * it runs as `streams` contiguous parts on as many streams (see rn_model.streams). */
-static int forward_chunk(rn_model *m, const float *input_nchw, uint64_t B, float *logits, int mode)
+static int forward_chunk(rn_model *m, const void *input, uint64_t B, float *logits, int mode)
 {
     uint64_t lo = 0;
     int parts = parts_of(m, B), i;
     TRY(ensure_acts(m, B));
     m->n_prof = 0;
     if (parts < 2 || m->profiling || m->single_stream_only || m->recording)
-        return forward_part(m, m->ctx, 0, input_nchw, B, logits, mode);
+        return forward_part(m, m->ctx, 0, input, B, logits, mode);
     if (!m->ev_fork) TRY(rn_event_create(m->ctx, &m->ev_fork));
     for (i = 0; i < parts - 1; ++i) {
         if (m->ctxn[i]) continue;
@@ -1248,7 +1274,7 @@ static int forward_chunk(rn_model *m, const float *input_nchw, uint64_t B, float
         const uint64_t hi = B * (uint64_t)(i + 1) / (uint64_t)parts;
         rn_ctx *run = i == 0 ? m->ctx : m->ctxn[i - 1];
         if (i > 0) TRY(rn_ctx_wait_event(run, m->ev_fork));
-        TRY(forward_part(m, run, lo, input_nchw + lo * 3 * 224 * 224, hi - lo, logits + lo * RN_CLASSES,
+        TRY(forward_part(m, run, lo, input_at(m, input, lo), hi - lo, logits + lo * RN_CLASSES,
                          mode));
         if (i > 0) TRY(rn_event_record(run, m->ev_join[i - 1]));
         lo = hi;
@@ -1264,20 +1290,35 @@ static int forward_chunk(rn_model *m, const float *input_nchw, uint64_t B, float
  * what else is in its launch (batch invariance, bit for bit), so the split changes nothing.
  * (RN_MAX_SUB_BATCH is defined above, next to the stream split.) */
 
-int rn_model_forward(rn_model *m, const float *input_nchw, uint64_t B, float *logits, int mode)
+static int forward_any(rn_model *m, const void *input, uint64_t B, float *logits, int mode)
 {
     uint64_t done = 0;
-    if (!m || !input_nchw || !logits || B == 0) return RN_ERR_INVALID;
+    if (!m || !input || !logits || B == 0) return RN_ERR_INVALID;
     if (mode != RN_FWD_REFERENCE_OPS && mode != RN_FWD_FUSED) return RN_ERR_INVALID;
     if (!m->finalized) return RN_ERR_INVALID;
     /* bf16 storage exists only with the fused epilogues (no standalone bf16 bn/relu/add) */
     if (m->dtype != RN_DTYPE_F32 && mode != RN_FWD_FUSED) return RN_ERR_UNSUPPORTED;
     while (done < B) {
         const uint64_t nb = B - done < RN_MAX_SUB_BATCH ? B - done : RN_MAX_SUB_BATCH;
-        TRY(forward_chunk(m, input_nchw + done * 3 * 224 * 224, nb, logits + done * RN_CLASSES, mode));
+        TRY(forward_chunk(m, input_at(m, input, done), nb, logits + done * RN_CLASSES, mode));
         done += nb;
     }
     return RN_OK;
+}
+
+int rn_model_forward(rn_model *m, const float *input_nchw, uint64_t B, float *logits, int mode)
+{
+    return forward_any(m, input_nchw, B, logits, mode);
+}
+
+int rn_model_forward_u8(rn_model *m, const uint8_t *input_nhwc, uint64_t B, float *logits, int mode)
+{
+    int st;
+    if (!m) return RN_ERR_INVALID;
+    m->in_u8 = 1;
+    st = forward_any(m, input_nhwc, B, logits, mode);
+    m->in_u8 = 0;
+    return st;
 }
 
 #define RN_TUNE_ROUNDS 6

@@ -23,8 +23,8 @@ struct rn_graph {
 };
 
 struct rn_pipeline_slot {
-    float *h_in, *h_out;  // pinned
-    float *d_in, *d_out;
+    void *h_in, *d_in;  // pinned staging and device input: fp32 NCHW, or 8-bit RGB in a byte pipeline
+    float *h_out, *d_out;
     uint64_t *h_idx, *d_idx;  // class indices (first maximum wins, main.cu:243-249)
     uint64_t n;               // images of the batch in this slot (<= B)
     hipEvent_t uploaded, done;
@@ -36,6 +36,8 @@ struct rn_pipeline {
     rn_ctx *ctx;
     uint64_t B;
     int mode;
+    int u8;            // input format: 0 = fp32 NCHW, 1 = 8-bit RGB [B,224,224,3] (rn_pipeline_create_u8)
+    size_t img_bytes;  // of one image in that format
     hipStream_t copy_stream;
     int copy_threads;  // helper threads of the pageable -> pinned copy (RN_COPY_THREADS, default 3)
     rn_pipeline_slot slot[2];
@@ -149,7 +151,7 @@ int rn_pipeline_destroy(rn_pipeline *p)
     return RN_OK;
 }
 
-int rn_pipeline_create(rn_model *m, rn_pipeline **out, uint64_t B, int mode)
+static int pipeline_create(rn_model *m, rn_pipeline **out, uint64_t B, int mode, int u8)
 {
     if (!m || !out || B == 0) return RN_ERR_INVALID;
     *out = nullptr;
@@ -160,22 +162,24 @@ int rn_pipeline_create(rn_model *m, rn_pipeline **out, uint64_t B, int mode)
     p->ctx = ctx;
     p->B = B;
     p->mode = mode;
+    p->u8 = u8;
+    p->img_bytes = (size_t)3 * 224 * 224 * (u8 ? sizeof(uint8_t) : sizeof(float));
     {
         const char *ct = getenv("RN_COPY_THREADS");
         const int n = ct ? atoi(ct) : 3;
         p->copy_threads = n < 1 ? 1 : n > 16 ? 16 : n;
     }
-    const size_t in_bytes = (size_t)B * 3 * 224 * 224 * sizeof(float);
+    const size_t in_bytes = (size_t)B * p->img_bytes;
     const size_t out_bytes = (size_t)B * 1000 * sizeof(float);
     const size_t idx_bytes = (size_t)B * sizeof(uint64_t);
     hipError_t e = hipSetDevice(ctx->device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) {
         rn_pipeline_slot *s = &p->slot[i];
-        e = hipHostMalloc((void **)&s->h_in, in_bytes, hipHostMallocDefault);
+        e = hipHostMalloc(&s->h_in, in_bytes, hipHostMallocDefault);
         if (e == hipSuccess) e = hipHostMalloc((void **)&s->h_out, out_bytes, hipHostMallocDefault);
         if (e == hipSuccess) e = hipHostMalloc((void **)&s->h_idx, idx_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void **)&s->d_in, in_bytes);
+        if (e == hipSuccess) e = hipMalloc(&s->d_in, in_bytes);
         if (e == hipSuccess) e = hipMalloc((void **)&s->d_out, out_bytes);
         if (e == hipSuccess) e = hipMalloc((void **)&s->d_idx, idx_bytes);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&s->uploaded, hipEventDisableTiming);
@@ -190,44 +194,74 @@ int rn_pipeline_create(rn_model *m, rn_pipeline **out, uint64_t B, int mode)
     return RN_OK;
 }
 
+int rn_pipeline_create(rn_model *m, rn_pipeline **out, uint64_t B, int mode)
+{
+    return pipeline_create(m, out, B, mode, 0);
+}
+
+int rn_pipeline_create_u8(rn_model *m, rn_pipeline **out, uint64_t B, int mode)
+{
+    return pipeline_create(m, out, B, mode, 1);
+}
+
 uint64_t rn_pipeline_in_flight(const rn_pipeline *p) { return p ? p->head - p->tail : 0; }
 uint64_t rn_pipeline_batch(const rn_pipeline *p) { return p ? p->B : 0; }
 
-int rn_pipeline_input_buffer(rn_pipeline *p, float **host_staging)
+// a float call on a byte pipeline or the reverse
+static int wrong_format(rn_pipeline *p, const char *who)
+{
+    return rn_set_error(p->ctx, RN_ERR_INVALID, "%s: the pipeline was created for %s input", who,
+                        p->u8 ? "8-bit RGB (rn_pipeline_create_u8)" : "fp32 NCHW (rn_pipeline_create)");
+}
+
+static int input_buffer(rn_pipeline *p, void **host_staging, int u8, const char *who)
 {
     if (!p || !host_staging) return RN_ERR_INVALID;
+    if (p->u8 != u8) return wrong_format(p, who);
     if (p->head - p->tail >= 2)
-        return rn_set_error(p->ctx, RN_ERR_INVALID, "rn_pipeline_input_buffer: both slots busy, collect first");
+        return rn_set_error(p->ctx, RN_ERR_INVALID, "%s: both slots busy, collect first", who);
     *host_staging = p->slot[p->head & 1].h_in;
     return RN_OK;
 }
 
-int rn_pipeline_submit_n(rn_pipeline *p, const float *host_input_nchw, uint64_t n)
+int rn_pipeline_input_buffer(rn_pipeline *p, float **host_staging)
+{
+    return input_buffer(p, (void **)host_staging, 0, "rn_pipeline_input_buffer");
+}
+
+int rn_pipeline_input_buffer_u8(rn_pipeline *p, uint8_t **host_staging)
+{
+    return input_buffer(p, (void **)host_staging, 1, "rn_pipeline_input_buffer_u8");
+}
+
+// host_input: n images in the pipeline's input format
+static int submit_n(rn_pipeline *p, const void *host_input, uint64_t n, int u8, const char *who)
 {
     if (!p) return RN_ERR_INVALID;
     rn_ctx *ctx = p->ctx;
     RN_TRY(rn_bind_device(ctx));
+    if (p->u8 != u8) return wrong_format(p, who);
     if (n == 0 || n > p->B)
         return rn_set_error(ctx, RN_ERR_INVALID, "rn_pipeline_submit_n: %llu images, the pipeline holds 1..%llu",
                             (unsigned long long)n, (unsigned long long)p->B);
     if (p->head - p->tail >= 2)
         return rn_set_error(ctx, RN_ERR_INVALID, "rn_pipeline_submit: both slots busy, collect first");
     rn_pipeline_slot *s = &p->slot[p->head & 1];
-    const size_t in_bytes = (size_t)n * 3 * 224 * 224 * sizeof(float);
+    const size_t in_bytes = (size_t)n * p->img_bytes;
     const int st = [&]() -> int {
-        if (host_input_nchw && host_input_nchw != s->h_in) {
-            // pageable -> pinned -> device in pieces of 16 images (9.6 MB): the upload of piece i runs on the
+        if (host_input && host_input != s->h_in) {
+            // pageable -> pinned -> device in pieces of 16 images (9.6 MB of fp32, 2.4 MB of bytes): the upload of piece i runs on the
             // copy stream while piece i+1 is being copied, so a batch costs max(copy, upload) instead of their
             // sum before its forward can start.  One core copies a 154 MB fp32 batch in 6-7 ms (23 GB/s), which
             // is longer than its upload (3.8 ms) and than a bf16 forward (3.3 ms): the pieces are copied by
             // `copiers` helper threads (they inherit this thread's CPU affinity: the cores local to the device)
             // while this thread queues each piece's upload as soon as it has landed in staging.
-            const size_t piece = (size_t)16 * 3 * 224 * 224 * sizeof(float);
+            const size_t piece = (size_t)16 * p->img_bytes;
             const size_t npieces = (in_bytes + piece - 1) / piece;
             const int copiers = npieces >= 4 ? p->copy_threads : 1;
             auto copy_piece = [&](size_t i) {
                 const size_t at = i * piece, nb = in_bytes - at < piece ? in_bytes - at : piece;
-                memcpy((char *)s->h_in + at, (const char *)host_input_nchw + at, nb);
+                memcpy((char *)s->h_in + at, (const char *)host_input + at, nb);
             };
             auto upload_piece = [&](size_t i) -> hipError_t {
                 const size_t at = i * piece, nb = in_bytes - at < piece ? in_bytes - at : piece;
@@ -273,7 +307,10 @@ int rn_pipeline_submit_n(rn_pipeline *p, const float *host_input_nchw, uint64_t 
         // forward on the compute stream once the upload has landed; the other slot's forward may
         // still be running there, which is exactly the overlap
         RN_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s->uploaded, 0));
-        RN_TRY(rn_model_forward(p->model, s->d_in, n, s->d_out, p->mode));
+        if (p->u8)
+            RN_TRY(rn_model_forward_u8(p->model, (const uint8_t *)s->d_in, n, s->d_out, p->mode));
+        else
+            RN_TRY(rn_model_forward(p->model, (const float *)s->d_in, n, s->d_out, p->mode));
         RN_TRY(rn_argmax_forward(ctx, s->d_out, s->d_idx, n, 1000));
         RN_HIP_TRY(ctx, hipMemcpyAsync(s->h_out, s->d_out, (size_t)n * 1000 * sizeof(float), hipMemcpyDeviceToHost,
                                        ctx->stream));
@@ -293,6 +330,16 @@ int rn_pipeline_submit_n(rn_pipeline *p, const float *host_input_nchw, uint64_t 
     s->n = n;
     ++p->head;
     return RN_OK;
+}
+
+int rn_pipeline_submit_n(rn_pipeline *p, const float *host_input_nchw, uint64_t n)
+{
+    return submit_n(p, host_input_nchw, n, 0, "rn_pipeline_submit_n");
+}
+
+int rn_pipeline_submit_u8_n(rn_pipeline *p, const uint8_t *host_input_nhwc, uint64_t n)
+{
+    return submit_n(p, host_input_nhwc, n, 1, "rn_pipeline_submit_u8_n");
 }
 
 int rn_pipeline_submit(rn_pipeline *p, const float *host_input_nchw)

@@ -23,6 +23,7 @@
 #include "rn_hip.h"
 
 #define IMG_FLOATS ((uint64_t)3 * 224 * 224)
+#define IMG_BYTES ((uint64_t)224 * 224 * 3) /* one image as 8-bit RGB */
 #define RN_CLASSES 1000
 
 enum { JOB_NONE = 0, JOB_CREATE, JOB_SET_TENSOR, JOB_LOAD_DIR, JOB_SET_DTYPE, JOB_FINALIZE,
@@ -48,7 +49,7 @@ typedef struct rn_shard_worker {
      * consecutive chunks (rn_shard_forward) or batches (rn_shard_submit / _collect) overlap */
     rn_pipeline *pipe;
     uint64_t pipe_B;
-    int pipe_mode;
+    int pipe_mode, pipe_u8;
     uint64_t stream_lo, stream_hi; /* streaming form: this shard's image range of every batch */
     uint64_t seen; /* last job sequence number this worker ran */
     int numa_node;     /* of the device's PCI slot, -1 = unknown */
@@ -68,6 +69,8 @@ struct rn_shard {
     int kind;
     const char *text;       /* key or directory */
     const float *tensor;    /* SET_TENSOR: host data; FORWARD: host input */
+    const uint8_t *bytes;   /* FORWARD, SUBMIT with in_u8: host input as 8-bit RGB instead of `tensor` */
+    int in_u8;              /* FORWARD, STREAM_OPEN: the input format, 1 = 8-bit RGB */
     uint64_t numel;         /* SET_TENSOR: element count; FORWARD: B */
     float *logits;
     uint64_t *top1;
@@ -75,6 +78,7 @@ struct rn_shard {
     uint64_t *tuning;     /* rn_shard_tune: shard 0's table on its way to the others */
     uint64_t tuning_words, tuning_nb; /* its size; the launch batch it was measured at */
     uint64_t stream_B;    /* streaming form: batch size of rn_shard_stream_open, 0 = closed */
+    int stream_u8;        /* the open stream takes 8-bit RGB (rn_shard_stream_open_u8) */
     int stream_in_flight; /* batches submitted and not yet collected (0..2) */
     char err[640];
 };
@@ -122,18 +126,23 @@ static void drain(rn_shard_worker *w)
     }
 }
 
-/* the worker's pipeline for batches of up to B images in `mode` (rebuilt when either changes) */
-static int ensure_pipeline(rn_shard_worker *w, uint64_t B, int mode)
+/* the worker's pipeline for batches of up to B images in `mode`, fp32 or byte input (rebuilt when
+ * one of them changes) */
+static int ensure_pipeline(rn_shard_worker *w, uint64_t B, int mode, int u8)
 {
     drain(w);
-    if (w->pipe && w->pipe_B >= B && w->pipe_mode == mode) return RN_OK;
+    if (w->pipe && w->pipe_B >= B && w->pipe_mode == mode && w->pipe_u8 == u8) return RN_OK;
     if (w->pipe) {
         rn_pipeline_destroy(w->pipe);
         w->pipe = NULL;
     }
-    WTRY(w, rn_pipeline_create(w->model, &w->pipe, B, mode));
+    if (u8)
+        WTRY(w, rn_pipeline_create_u8(w->model, &w->pipe, B, mode));
+    else
+        WTRY(w, rn_pipeline_create(w->model, &w->pipe, B, mode));
     w->pipe_B = B;
     w->pipe_mode = mode;
+    w->pipe_u8 = u8;
     return RN_OK;
 }
 
@@ -263,12 +272,13 @@ static int run_job(rn_shard_worker *w, const struct rn_shard *g)
         uint64_t lo, hi, sent, got, n;
         rn_shard_bounds(g->numel, w->rank, g->n, &lo, &hi);
         if (hi == lo) return RN_OK;
-        WTRY(w, ensure_pipeline(w, hi - lo < RN_SHARD_CHUNK ? hi - lo : RN_SHARD_CHUNK, g->ivalue));
+        WTRY(w, ensure_pipeline(w, hi - lo < RN_SHARD_CHUNK ? hi - lo : RN_SHARD_CHUNK, g->ivalue, g->in_u8));
         for (sent = got = lo; got < hi;) {
             int st;
             if (sent < hi && rn_pipeline_in_flight(w->pipe) < 2) {
                 n = hi - sent < RN_SHARD_CHUNK ? hi - sent : RN_SHARD_CHUNK;
-                st = rn_pipeline_submit_n(w->pipe, g->tensor + sent * IMG_FLOATS, n);
+                st = g->in_u8 ? rn_pipeline_submit_u8_n(w->pipe, g->bytes + sent * IMG_BYTES, n)
+                              : rn_pipeline_submit_n(w->pipe, g->tensor + sent * IMG_FLOATS, n);
                 if (st != RN_OK) {
                     fail(w, st, "rn_pipeline_submit_n");
                     drain(w); /* the chunks already queued finish; nothing stays in flight behind an error */
@@ -289,7 +299,7 @@ static int run_job(rn_shard_worker *w, const struct rn_shard *g)
     case JOB_STREAM_OPEN: {
         rn_shard_bounds(g->numel, w->rank, g->n, &w->stream_lo, &w->stream_hi);
         if (w->stream_hi == w->stream_lo) return RN_OK;
-        WTRY(w, ensure_pipeline(w, w->stream_hi - w->stream_lo, g->ivalue));
+        WTRY(w, ensure_pipeline(w, w->stream_hi - w->stream_lo, g->ivalue, g->in_u8));
         return RN_OK;
     }
     case JOB_SUBMIT: {
@@ -297,7 +307,10 @@ static int run_job(rn_shard_worker *w, const struct rn_shard *g)
         if (nb == 0) return RN_OK;
         if (!w->pipe) return fail(w, RN_ERR_INVALID, "rn_shard_submit before rn_shard_stream_open");
         /* NULL: the caller filled the pinned staging buffers (rn_shard_stream_buffer) in place */
-        WTRY(w, rn_pipeline_submit_n(w->pipe, g->tensor ? g->tensor + w->stream_lo * IMG_FLOATS : NULL, nb));
+        if (g->stream_u8)
+            WTRY(w, rn_pipeline_submit_u8_n(w->pipe, g->bytes ? g->bytes + w->stream_lo * IMG_BYTES : NULL, nb));
+        else
+            WTRY(w, rn_pipeline_submit_n(w->pipe, g->tensor ? g->tensor + w->stream_lo * IMG_FLOATS : NULL, nb));
         return RN_OK;
     }
     case JOB_COLLECT: {
@@ -475,11 +488,13 @@ int rn_shard_finalize(rn_shard *g)
     return post(g, JOB_FINALIZE);
 }
 
-static int forward_like(rn_shard *g, int kind, const float *host_input_nchw, uint64_t B,
-                        float *host_logits, uint64_t *host_top1, int mode)
+static int forward_like(rn_shard *g, int kind, const float *host_input_nchw, const uint8_t *host_input_u8,
+                        uint64_t B, float *host_logits, uint64_t *host_top1, int mode)
 {
-    if (!g || !host_input_nchw || B == 0) return RN_ERR_INVALID;
+    if (!g || (!host_input_nchw && !host_input_u8) || B == 0) return RN_ERR_INVALID;
     g->tensor = host_input_nchw;
+    g->bytes = host_input_u8;
+    g->in_u8 = host_input_u8 != NULL;
     g->numel = B;
     g->logits = host_logits;
     g->top1 = host_top1;
@@ -487,8 +502,8 @@ static int forward_like(rn_shard *g, int kind, const float *host_input_nchw, uin
     return post(g, kind);
 }
 
-int rn_shard_forward(rn_shard *g, const float *host_input_nchw, uint64_t B, float *host_logits,
-                     uint64_t *host_top1, int mode)
+static int shard_forward(rn_shard *g, const float *host_input_nchw, const uint8_t *host_input_u8, uint64_t B,
+                         float *host_logits, uint64_t *host_top1, int mode)
 {
     if (g && g->stream_in_flight > 0) {
         snprintf(g->err, sizeof(g->err), "rn_shard_forward: %d submitted batch(es) in flight: collect them first",
@@ -496,7 +511,21 @@ int rn_shard_forward(rn_shard *g, const float *host_input_nchw, uint64_t B, floa
         return RN_ERR_INVALID;
     }
     if (g) g->stream_B = 0; /* the per-device pipelines are re-sized for this call's chunks */
-    return forward_like(g, JOB_FORWARD, host_input_nchw, B, host_logits, host_top1, mode);
+    return forward_like(g, JOB_FORWARD, host_input_nchw, host_input_u8, B, host_logits, host_top1, mode);
+}
+
+int rn_shard_forward(rn_shard *g, const float *host_input_nchw, uint64_t B, float *host_logits,
+                     uint64_t *host_top1, int mode)
+{
+    if (!host_input_nchw) return RN_ERR_INVALID;
+    return shard_forward(g, host_input_nchw, NULL, B, host_logits, host_top1, mode);
+}
+
+int rn_shard_forward_u8(rn_shard *g, const uint8_t *host_input_nhwc, uint64_t B, float *host_logits,
+                        uint64_t *host_top1, int mode)
+{
+    if (!host_input_nhwc) return RN_ERR_INVALID;
+    return shard_forward(g, NULL, host_input_nhwc, B, host_logits, host_top1, mode);
 }
 
 int rn_shard_tune(rn_shard *g, const float *host_input_nchw, uint64_t B, int mode)
@@ -512,7 +541,7 @@ int rn_shard_tune(rn_shard *g, const float *host_input_nchw, uint64_t B, int mod
                  (unsigned long long)g->stream_B, (unsigned long long)B);
         return RN_ERR_INVALID;
     }
-    st = forward_like(g, JOB_TUNE, host_input_nchw, B, NULL, NULL, mode); /* shard 0 measures */
+    st = forward_like(g, JOB_TUNE, host_input_nchw, NULL, B, NULL, NULL, mode); /* shard 0 measures */
     if (st != RN_OK) return st;
     /* its table, read from this thread while the workers are parked */
     free(g->tuning);
@@ -546,17 +575,30 @@ int rn_shard_placement(const rn_shard *g, int rank, int *device, int *numa_node,
 }
 
 /* ---- streaming form: consecutive batches of B images, two in flight per device ---------- */
-int rn_shard_stream_open(rn_shard *g, uint64_t B, int mode)
+static int stream_open(rn_shard *g, uint64_t B, int mode, int u8)
 {
     int st;
     if (!g || B == 0) return RN_ERR_INVALID;
     g->numel = B;
     g->ivalue = mode;
+    g->in_u8 = u8;
     g->stream_B = B;
+    g->stream_u8 = u8;
     g->stream_in_flight = 0;
     st = post(g, JOB_STREAM_OPEN);
     if (st != RN_OK) g->stream_B = 0; /* a device without its pipeline: the stream is not open */
     return st;
+}
+
+int rn_shard_stream_open(rn_shard *g, uint64_t B, int mode) { return stream_open(g, B, mode, 0); }
+int rn_shard_stream_open_u8(rn_shard *g, uint64_t B, int mode) { return stream_open(g, B, mode, 1); }
+
+/* a float call on a byte stream or the reverse */
+static int wrong_format(rn_shard *g, const char *who)
+{
+    snprintf(g->err, sizeof(g->err), "%s: the stream was opened for %s input", who,
+             g->stream_u8 ? "8-bit RGB (rn_shard_stream_open_u8)" : "fp32 NCHW (rn_shard_stream_open)");
+    return RN_ERR_INVALID;
 }
 
 int rn_shard_stream_close(rn_shard *g)
@@ -567,7 +609,7 @@ int rn_shard_stream_close(rn_shard *g)
     return post(g, JOB_STREAM_CLOSE);
 }
 
-int rn_shard_stream_buffer(rn_shard *g, int rank, float **host_staging, uint64_t *lo, uint64_t *hi)
+static int stream_buffer(rn_shard *g, int rank, void **host_staging, uint64_t *lo, uint64_t *hi, int u8)
 {
     rn_shard_worker *w;
     if (!g || rank < 0 || rank >= g->n || !host_staging) return RN_ERR_INVALID;
@@ -576,23 +618,40 @@ int rn_shard_stream_buffer(rn_shard *g, int rank, float **host_staging, uint64_t
     if (lo) *lo = w->stream_lo;
     if (hi) *hi = w->stream_hi;
     if (g->stream_B == 0) return RN_ERR_INVALID;
+    if (g->stream_u8 != u8) return wrong_format(g, u8 ? "rn_shard_stream_buffer_u8" : "rn_shard_stream_buffer");
     if (w->stream_hi == w->stream_lo) return RN_OK; /* an empty shard has no staging */
     /* between jobs the worker is parked: reading its pipeline from the caller's thread is safe */
-    return rn_pipeline_input_buffer(w->pipe, host_staging);
+    return u8 ? rn_pipeline_input_buffer_u8(w->pipe, (uint8_t **)host_staging)
+              : rn_pipeline_input_buffer(w->pipe, (float **)host_staging);
+}
+
+int rn_shard_stream_buffer(rn_shard *g, int rank, float **host_staging, uint64_t *lo, uint64_t *hi)
+{
+    return stream_buffer(g, rank, (void **)host_staging, lo, hi, 0);
+}
+
+int rn_shard_stream_buffer_u8(rn_shard *g, int rank, uint8_t **host_staging, uint64_t *lo, uint64_t *hi)
+{
+    return stream_buffer(g, rank, (void **)host_staging, lo, hi, 1);
 }
 
 /* A device that fails in the middle of a stream leaves the devices out of step (some hold a batch
  * the others do not): the stream is closed -- open it again (that drains every device) to go on. */
-int rn_shard_submit(rn_shard *g, const float *host_input_nchw)
+static int stream_submit(rn_shard *g, const float *host_input_nchw, const uint8_t *host_input_u8, int u8)
 {
     int st;
     if (!g || g->stream_B == 0 || g->stream_in_flight >= 2) return RN_ERR_INVALID;
+    if (g->stream_u8 != u8) return wrong_format(g, u8 ? "rn_shard_submit_u8" : "rn_shard_submit");
     g->tensor = host_input_nchw;
+    g->bytes = host_input_u8;
     st = post(g, JOB_SUBMIT);
     if (st == RN_OK) ++g->stream_in_flight;
     else g->stream_B = 0, g->stream_in_flight = 0;
     return st;
 }
+
+int rn_shard_submit(rn_shard *g, const float *host_input_nchw) { return stream_submit(g, host_input_nchw, NULL, 0); }
+int rn_shard_submit_u8(rn_shard *g, const uint8_t *host_input_nhwc) { return stream_submit(g, NULL, host_input_nhwc, 1); }
 
 int rn_shard_collect(rn_shard *g, float *host_logits, uint64_t *host_top1)
 {

@@ -258,6 +258,26 @@ class NativeModel:
         self.ctx.sync()
         return out.numpy()
 
+    def forward_u8_ptr(self, input_ptr: int, B: int, logits_ptr: int, fused: bool = True) -> None:
+        """Queue one forward from 8-bit RGB [B,224,224,3] on the device (asynchronous): the first
+        launch normalises the bytes (rn_model_forward_u8); same logits as forward_ptr on
+        preprocess.normalize_u8 of them, bit for bit."""
+        L.check(L.lib().rn_model_forward_u8(self.handle, input_ptr, B, logits_ptr,
+                                            L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS),
+                "rn_model_forward_u8", self.ctx.handle)
+
+    def forward_u8(self, px: np.ndarray, fused: bool = True) -> np.ndarray:
+        """uint8 RGB host array [B,224,224,3] -> logits host array (synchronous convenience)."""
+        from .ops import _up_raw
+        px = np.ascontiguousarray(px, dtype=np.uint8)
+        assert px.ndim == 4 and px.shape[1:] == (224, 224, 3), px.shape
+        B = px.shape[0]
+        xin = _up_raw(px)
+        out = FloatTensor((B, 1000), Device.GPU)
+        self.forward_u8_ptr(xin.ptr, B, out.data(), fused)
+        self.ctx.sync()
+        return out.numpy()
+
     def tune(self, input_ptr: int, B: int, logits_ptr: int, fused: bool = True) -> None:
         """Pick the fastest contraction tile per layer for batch B (results unchanged)."""
         L.check(L.lib().rn_model_tune(self.handle, input_ptr, B, logits_ptr,
@@ -370,6 +390,7 @@ class ShardedModel:
         L.check(lib.rn_shard_create(ctypes.byref(h), dev, len(devices), ARCH_ID[arch]), "rn_shard_create")
         self.handle, self.n = h, len(devices)
         self._stream_B = 0
+        self._stream_input = "f32"
         if weights_dir is not None:
             self._check(lib.rn_shard_load_dir(h, weights_dir.encode()), "rn_shard_load_dir")
         else:
@@ -406,6 +427,19 @@ class ShardedModel:
                     "rn_shard_forward")
         return logits, top1
 
+    def forward_u8(self, px: np.ndarray, fused: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """uint8 RGB host array [B,224,224,3] -> (logits [B,1000], top-1 [B]), image order."""
+        px = np.ascontiguousarray(px, dtype=np.uint8)
+        assert px.ndim == 4 and px.shape[1:] == (224, 224, 3), px.shape
+        B = px.shape[0]
+        logits = np.empty((B, 1000), dtype=np.float32)
+        top1 = np.empty(B, dtype=np.uint64)
+        self._check(L.lib().rn_shard_forward_u8(self.handle, px.ctypes.data, B, logits.ctypes.data,
+                                                top1.ctypes.data,
+                                                L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS),
+                    "rn_shard_forward_u8")
+        return logits, top1
+
     def tune(self, x: np.ndarray, fused: bool = True) -> None:
         x = np.ascontiguousarray(x, dtype=np.float32)
         self._check(L.lib().rn_shard_tune(self.handle, x.ctypes.data, x.shape[0],
@@ -431,19 +465,31 @@ class ShardedModel:
         return dev.value, node.value, buf.value.decode()
 
     # streaming form: consecutive batches of B images, two in flight on every device
-    def stream_open(self, B: int, fused: bool = True) -> None:
-        self._check(L.lib().rn_shard_stream_open(self.handle, B, L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS),
-                    "rn_shard_stream_open")
+    def stream_open(self, B: int, fused: bool = True, input: str = "f32") -> None:
+        """input: "f32" (NCHW floats: submit) or "u8" (RGB bytes [B,224,224,3]: submit_u8)."""
+        if input not in ("f32", "u8"):
+            raise ValueError(f"input must be 'f32' or 'u8', not {input!r}")
+        lib = L.lib()
+        opener = lib.rn_shard_stream_open_u8 if input == "u8" else lib.rn_shard_stream_open
+        self._check(opener(self.handle, B, L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS),
+                    "rn_shard_stream_open_u8" if input == "u8" else "rn_shard_stream_open")
         self._stream_B = B
+        self._stream_input = input
 
     def stream_buffer(self, rank: int):
-        """(pinned staging of shard `rank` for the next submit as [hi-lo,3,224,224], lo, hi)."""
+        """(pinned staging of shard `rank` for the next submit as [hi-lo,3,224,224] floats, or in a
+        byte stream as [hi-lo,224,224,3] uint8, lo, hi)."""
+        u8 = self._stream_input == "u8"
         ptr, lo, hi = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64()
-        self._check(L.lib().rn_shard_stream_buffer(self.handle, rank, ctypes.byref(ptr), ctypes.byref(lo),
-                                                   ctypes.byref(hi)), "rn_shard_stream_buffer")
+        fn = L.lib().rn_shard_stream_buffer_u8 if u8 else L.lib().rn_shard_stream_buffer
+        self._check(fn(self.handle, rank, ctypes.byref(ptr), ctypes.byref(lo), ctypes.byref(hi)),
+                    "rn_shard_stream_buffer_u8" if u8 else "rn_shard_stream_buffer")
         n = hi.value - lo.value
         if n == 0:
             return None, lo.value, hi.value
+        if u8:
+            buf = (ctypes.c_uint8 * (n * 224 * 224 * 3)).from_address(ptr.value)
+            return np.frombuffer(buf, dtype=np.uint8).reshape(n, 224, 224, 3), lo.value, hi.value
         buf = (ctypes.c_float * (n * 3 * 224 * 224)).from_address(ptr.value)
         return np.frombuffer(buf, dtype=np.float32).reshape(n, 3, 224, 224), lo.value, hi.value
 
@@ -454,6 +500,15 @@ class ShardedModel:
             assert self._stream_B == 0 or x.shape == (self._stream_B, 3, 224, 224)
             ptr = x.ctypes.data
         self._check(L.lib().rn_shard_submit(self.handle, ptr), "rn_shard_submit")
+
+    def submit_u8(self, px: Optional[np.ndarray] = None) -> None:
+        """px: [B,224,224,3] uint8, or None when the staging buffers were filled in place."""
+        ptr = None
+        if px is not None:
+            px = np.ascontiguousarray(px, dtype=np.uint8)
+            assert self._stream_B == 0 or px.shape == (self._stream_B, 224, 224, 3)
+            ptr = px.ctypes.data
+        self._check(L.lib().rn_shard_submit_u8(self.handle, ptr), "rn_shard_submit_u8")
 
     def collect(self) -> Tuple[np.ndarray, np.ndarray]:
         logits = np.empty((self._stream_B, 1000), dtype=np.float32)
@@ -512,18 +567,27 @@ class Pipeline:
     """Stream of host batches through a NativeModel with the upload of the next batch
     overlapped with the forward of the current one (rn_pipeline_*, two slots)."""
 
-    def __init__(self, model: NativeModel, batch: int, fused: bool = True):
-        self.model, self.batch = model, batch
+    def __init__(self, model: NativeModel, batch: int, fused: bool = True, input: str = "f32"):
+        """input: "f32" (NCHW floats, submit) or "u8" (RGB bytes [n,224,224,3], submit_u8: a
+        quarter of the upload, normalised on the device)."""
+        if input not in ("f32", "u8"):
+            raise ValueError(f"input must be 'f32' or 'u8', not {input!r}")
+        self.model, self.batch, self.input = model, batch, input
         h = ctypes.c_void_p()
-        L.check(L.lib().rn_pipeline_create(model.handle, ctypes.byref(h), batch,
-                                           L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS),
-                "rn_pipeline_create", model.ctx.handle)
+        create = L.lib().rn_pipeline_create_u8 if input == "u8" else L.lib().rn_pipeline_create
+        L.check(create(model.handle, ctypes.byref(h), batch, L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS),
+                "rn_pipeline_create_u8" if input == "u8" else "rn_pipeline_create", model.ctx.handle)
         self.handle = h
 
     def input_buffer(self) -> np.ndarray:
-        """The pinned staging buffer of the next slot as a [B,3,224,224] array: fill it in
-        place, then submit() without an argument."""
+        """The pinned staging buffer of the next slot as a [B,3,224,224] float array (a byte
+        pipeline: [B,224,224,3] uint8): fill it in place, then submit without an argument."""
         ptr = ctypes.c_void_p()
+        if self.input == "u8":
+            L.check(L.lib().rn_pipeline_input_buffer_u8(self.handle, ctypes.byref(ptr)),
+                    "rn_pipeline_input_buffer_u8", self.model.ctx.handle)
+            buf = (ctypes.c_uint8 * (self.batch * 224 * 224 * 3)).from_address(ptr.value)
+            return np.frombuffer(buf, dtype=np.uint8).reshape(self.batch, 224, 224, 3)
         L.check(L.lib().rn_pipeline_input_buffer(self.handle, ctypes.byref(ptr)),
                 "rn_pipeline_input_buffer", self.model.ctx.handle)
         n = self.batch * 3 * 224 * 224
@@ -539,6 +603,17 @@ class Pipeline:
             assert x.shape[1:] == (3, 224, 224)
             ptr, n = x.ctypes.data, x.shape[0]
         L.check(L.lib().rn_pipeline_submit_n(self.handle, ptr, n), "rn_pipeline_submit_n",
+                self.model.ctx.handle)
+
+    def submit_u8(self, px: np.ndarray | None = None) -> None:
+        """px: [n,224,224,3] uint8 with n <= batch, or None when the staging buffer was filled in
+        place (a whole batch).  Only on a pipeline created with input="u8"."""
+        ptr, n = None, self.batch
+        if px is not None:
+            px = np.ascontiguousarray(px, dtype=np.uint8)
+            assert px.shape[1:] == (224, 224, 3)
+            ptr, n = px.ctypes.data, px.shape[0]
+        L.check(L.lib().rn_pipeline_submit_u8_n(self.handle, ptr, n), "rn_pipeline_submit_u8_n",
                 self.model.ctx.handle)
 
     def collect(self) -> np.ndarray:
@@ -561,7 +636,7 @@ class Pipeline:
         for x in batches:
             if self.in_flight() == 2:
                 yield self.collect()
-            self.submit(x)
+            (self.submit_u8 if self.input == "u8" else self.submit)(x)
         while self.in_flight():
             yield self.collect()
 

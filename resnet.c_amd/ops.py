@@ -418,6 +418,31 @@ def pool_nhwc_bf16(x, k, stride=1, pad=0, is_max=True) -> np.ndarray:
     return y.reshape(B, ho, wo, C).transpose(0, 3, 1, 2).copy()
 
 
+def image_u8_to_nhwc_pad(px, cpad: int = 4, border: int = 0, bf16: bool = False, mean=None, std=None,
+                         prefill: Optional[int] = None) -> np.ndarray:
+    """rn_image_u8_to_nhwc_pad_dt: uint8 RGB [B,H,W,3] -> the normalised, padded first tensor
+    [B,H+2b,W+2b,cpad] as the device wrote it: fp32, or for ``bf16`` the raw bf16 bits (uint16).
+    ``mean`` / ``std`` default to the ImageNet values of preprocess.py; ``prefill`` fills the
+    destination with that byte first, so that an element the launch did not write shows."""
+    from . import preprocess
+    from .tensor import _DeviceBuffer
+    ctx, lib = get_ctx(), L.lib()
+    px = np.ascontiguousarray(px, dtype=np.uint8)
+    B, H, W, C = px.shape
+    assert C == 3
+    dt, es, ht = (L.RN_DTYPE_BF16, 2, np.uint16) if bf16 else (L.RN_DTYPE_F32, 4, np.float32)
+    n = B * (H + 2 * border) * (W + 2 * border) * cpad
+    src = _up_raw(px)
+    dst = _DeviceBuffer(ctx, max(n * es, 16))
+    if prefill is not None:
+        L.check(lib.rn_memset(ctx.handle, dst.ptr, prefill, max(n * es, 16)), "memset", ctx.handle)
+    m3 = (ctypes.c_float * 3)(*(preprocess.MEAN if mean is None else mean))
+    s3 = (ctypes.c_float * 3)(*(preprocess.STD if std is None else std))
+    L.check(lib.rn_image_u8_to_nhwc_pad_dt(ctx.handle, dt, src.ptr, dst.ptr, B, H, W, cpad, border, m3, s3),
+            "rn_image_u8_to_nhwc_pad_dt", ctx.handle)
+    return _down_raw(dst, ht, n).reshape(B, H + 2 * border, W + 2 * border, cpad)
+
+
 def stem_pool(x, w, scale=None, shift=None, relu_: bool = True, bf16: bool = False,
               from_nchw: bool = False) -> np.ndarray:
     """conv 7x7/2 pad 3 + per-channel affine + ReLU + max-pool 3x3/2/1 through the fused launch
