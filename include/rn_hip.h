@@ -43,6 +43,35 @@
  * inp1), as the reference driver uses them (main.cu:138,145-146,162-163).
  * conv, pool and linear must not alias.
  *
+ * Alignment.  Callers hand these entry points slices of larger buffers (t.data() + offset).
+ * The fp32 entry points -- the seven reference ops, rn_argmax_forward (logits; its idx: 8 bytes),
+ * rn_nchw_to_nhwc, rn_nhwc_to_nchw, rn_nchw_to_nhwc_pad(_dt), rn_conv2d_pack_weight,
+ * rn_batchnorm2d_fold, rn_conv2d_nhwc_forward with every operand of its epilogue -- accept any
+ * 4-byte-aligned pointer for every operand and compute the same values; they are fastest with
+ * every operand on a 16-byte boundary, where the float4 kernels and the matrix-core contraction
+ * run.  Off it they take an element-wise kernel with the same bits (ReLU, add, batch-norm, pools,
+ * layout changes) or, for rn_conv2d_forward, either the NCHW-native kernel (dword gathers and
+ * stores; NCHW context, 1x1 / padding 0, or k x k with rn_ctx_set_nchw_taps) or the direct kernel
+ * in the reference's summation order.  The contraction itself touches its operands in 16-byte
+ * pieces, so rn_linear_forward (inp, out, weight, bias) and rn_conv2d_nhwc_forward (inp, out,
+ * packed_weight, scale, shift, residual) run the direct kernel -- one thread per output, no matrix
+ * cores, the price of a slice nobody has measured on network-sized layers -- as soon as ONE of
+ * them is off a 16-byte boundary: a parameter arena that packs scale / shift vectors back to back
+ * wants channel counts that are multiples of 4.  rn_nchw_to_nhwc_pad_dt(BF16) takes a dst on any
+ * 2-byte boundary.
+ * These must be 16-byte aligned and are refused with RN_ERR_INVALID (nothing is launched,
+ * rn_last_error names the alignment) otherwise: every tensor, panel, scale / shift vector and
+ * residual of rn_conv2d_nhwc_forward_dt(BF16), rn_conv2d_nhwc_pair_forward_dt,
+ * rn_conv_chain_forward_dt, rn_conv_chain_pair_forward_dt; inp / out of
+ * rn_maxpool2d_nhwc_forward_dt(BF16) and rn_avgpool2d_nhwc_forward_dt(BF16); inp / out /
+ * packed_weight of rn_stem_pool_forward_dt and rn_stem_pool_nchw_forward_dt, and stem_out of
+ * rn_stem_conv_pool_nchw_forward (their scale / shift are read element by element: 4 bytes); of
+ * rn_conv2d_nhwc_exact_forward everything but inp_padded (dword gathers: 4 bytes).  The deferred
+ * route (rn_ctx_set_deferred) folds a convolution with the ops behind it only when inp, out and
+ * weight sit on 16-byte boundaries, the residual add only when its other operand does, and runs
+ * what it does not fold literally.  tests/test_views_gpu.py holds each sentence of this paragraph
+ * on views between guard bands.
+ *
  * Threading: one context per host thread; a context = (device, stream,
  * scratch).  No global mutable state.  A host thread may own contexts on
  * several devices: every entry point makes its context's device the calling

@@ -1316,6 +1316,14 @@ bool gemm_eligible(const void *inp, const void *out, const void *w, uint64_t Cin
     return al && k <= 15 && (Cin % 32 == 0 || rn_conv_is_c4(Cin, k));
 }
 
+// scale / shift / residual of an epilogue on boundaries of mask + 1 bytes; the contraction's epilogue fetches
+// all three in 16-byte pieces (mask 15), the direct kernel element by element (mask 3)
+bool epilogue_aligned(const rn_epilogue *ep, uintptr_t mask)
+{
+    return !ep || ((reinterpret_cast<uintptr_t>(ep->scale) | reinterpret_cast<uintptr_t>(ep->shift) |
+                    reinterpret_cast<uintptr_t>(ep->residual)) & mask) == 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1330,10 +1338,11 @@ int rn_conv2d_nhwc_forward(rn_ctx *ctx, const float *inp, float *out, const floa
     RN_TRY(check_conv_args(ctx, inp, out, packed_weight, kernel_size, stride, padding, h_out, w_out,
                            B, in_channels, out_channels, H, W));
     RN_REQUIRE(ctx, in_channels >= 1, "in_channels must be >= 1");
-    if (epilogue && epilogue->residual)
-        RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(epilogue->residual) & 3) == 0,
-                   "misaligned residual");
-    if (gemm_eligible(inp, out, packed_weight, in_channels, kernel_size,
+    RN_REQUIRE(ctx, epilogue_aligned(epilogue, 3),
+               "misaligned scale / shift / residual (fp32 tensors sit on 4-byte boundaries)");
+    // any operand off a 16-byte boundary, the epilogue's included: the element-wise kernel
+    if (epilogue_aligned(epilogue, 15) &&
+        gemm_eligible(inp, out, packed_weight, in_channels, kernel_size,
                       B * H * W * rn_conv2d_input_channels(in_channels),
                       rn_conv2d_packed_weight_numel(in_channels, out_channels, kernel_size),
                       B * h_out * w_out * out_channels)) {
@@ -1381,6 +1390,22 @@ int rn_conv2d_forward(rn_ctx *ctx, const float *inp, float *out, const float *we
                         rn_conv_nchw_eligible(kernel_size, stride, padding, B, in_channels, out_channels, H, W);
     if (native && kernel_size == 1 && padding == 0 && (reinterpret_cast<uintptr_t>(weight) & 15) == 0)
         return rn_conv_nchw_launch(ctx, inp, out, weight, 1, stride, 0, B, in_channels, out_channels, H, W);
+    // k x k on NCHW tensors: the taps gathered from the channel planes, the packed panel as the MFMA rows.
+    // Measured at B = 256 (tools/nchw_bench.py, RN_NCHW_TAPS=2 against 0): the gathering K loop is 15-25 % slower
+    // per tile than the NHWC one, the transpose it saves costs 70 us on a 56x56 tensor and 10-25 us on the
+    // 14x14 / 7x7 ones -- it pays on the large planes only (rn_ctx_set_nchw_taps: 1, the default)
+    const bool taps = native && (ctx->nchw_taps >= 2 || (ctx->nchw_taps == 1 && H * W >= 2048));
+    // The NCHW-native kernel takes tensors on any 4-byte boundary (dword gathers, dword stores).  The NHWC
+    // contraction reads the caller's input and writes its output -- NHWC rows or, behind the transpose, NCHW
+    // pixel quads -- in 16-byte pieces: tensors that do not sit on 16-byte boundaries go to the direct kernel,
+    // as in rn_conv2d_nhwc_forward and rn_linear_forward (gemm_eligible).
+    const uintptr_t wide = ctx->layout == RN_LAYOUT_NHWC
+                               ? (reinterpret_cast<uintptr_t>(inp) | reinterpret_cast<uintptr_t>(out))
+                               : reinterpret_cast<uintptr_t>(out);
+    if (!taps && (wide & 15) != 0)
+        return launch_direct(ctx, inp, out, weight, kernel_size, stride, padding, h_out, w_out, B, in_channels,
+                             in_channels, out_channels, H, W, ctx->layout == RN_LAYOUT_NHWC, 0, nullptr,
+                             "rn_conv2d_forward(direct)");
     // K-major panel of the OIHW weight: packed per call into scratch, or -- with the context's
     // weight cache on -- once per (weight buffer, shape) and kept until that buffer is freed or
     // written through the rn_* calls
@@ -1403,11 +1428,7 @@ int rn_conv2d_forward(rn_ctx *ctx, const float *inp, float *out, const float *we
                            padding, h_out, w_out, B, in_channels, out_channels, H, W, nullptr,
                            "rn_conv2d_forward(nhwc)");
     }
-    // k x k on NCHW tensors: the taps gathered from the channel planes, the packed panel as the MFMA rows.
-    // Measured at B = 256 (tools/nchw_bench.py, RN_NCHW_TAPS=2 against 0): the gathering K loop is 15-25 % slower
-    // per tile than the NHWC one, the transpose it saves costs 70 us on a 56x56 tensor and 10-25 us on the
-    // 14x14 / 7x7 ones -- it pays on the large planes only (rn_ctx_set_nchw_taps: 1, the default)
-    if (native && (ctx->nchw_taps >= 2 || (ctx->nchw_taps == 1 && H * W >= 2048)))
+    if (taps)
         return rn_conv_nchw_launch(ctx, inp, out, (const float *)wp, kernel_size, stride, padding, B, in_channels,
                                    out_channels, H, W);
     // anything else on NCHW tensors: transpose in, contract; the contraction's epilogue writes NCHW itself
@@ -1461,6 +1482,7 @@ int rn_conv2d_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const void 
     RN_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(inp) | reinterpret_cast<uintptr_t>(out) |
                       reinterpret_cast<uintptr_t>(packed_weight)) & 15) == 0,
                "bf16 tensors must be 16-byte aligned");
+    RN_REQUIRE(ctx, epilogue_aligned(epilogue, 15), "misaligned scale / shift / residual (16-byte alignment)");
     return launch_gemm(ctx, RN_DTYPE_BF16, out_dtype, inp, out, packed_weight, kernel_size, stride,
                        padding, h_out, w_out, B, in_channels, out_channels, H, W, epilogue,
                        "rn_conv2d_nhwc_forward_dt");
@@ -1491,9 +1513,7 @@ int rn_conv2d_nhwc_exact_forward(rn_ctx *ctx, const float *inp_padded, float *ou
                       reinterpret_cast<uintptr_t>(packed_exact_weight)) & 15) == 0 &&
                         (reinterpret_cast<uintptr_t>(inp_padded) & 3) == 0,
                "misaligned tensor");
-    if (epilogue && epilogue->residual)
-        RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(epilogue->residual) & 15) == 0,
-                   "misaligned residual");
+    RN_REQUIRE(ctx, epilogue_aligned(epilogue, 15), "misaligned scale / shift / residual (16-byte alignment)");
     return launch_gemm(ctx, RN_DTYPE_F32, RN_DTYPE_F32, inp_padded, out, packed_exact_weight,
                        kernel_size, stride, 0, h_out, w_out, B, in_channels, out_channels, Hp, Wp,
                        epilogue, "rn_conv2d_nhwc_exact_forward", nullptr, true);
@@ -1538,9 +1558,7 @@ int rn_conv2d_nhwc_pair_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const 
                       reinterpret_cast<uintptr_t>(packed_pair_weight) |
                       reinterpret_cast<uintptr_t>(second->inp)) & 15) == 0,
                "tensors must be 16-byte aligned");
-    if (epilogue && epilogue->residual)
-        RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(epilogue->residual) & 15) == 0,
-                   "misaligned residual");
+    RN_REQUIRE(ctx, epilogue_aligned(epilogue, 15), "misaligned scale / shift / residual (16-byte alignment)");
     return launch_gemm(ctx, dtype, out_dtype, inp, out, packed_pair_weight, kernel_size, stride,
                        padding, h_out, w_out, B, in_channels, out_channels, H, W, epilogue,
                        "rn_conv2d_nhwc_pair_forward_dt", second);
@@ -1561,7 +1579,7 @@ int rn_linear_forward(rn_ctx *ctx, const float *inp, float *out, const float *we
     RN_ENTER(ctx);
     rn_epilogue ep = {nullptr, bias, nullptr, 0};
     // W is [out][in] row-major == the K-major panel of a 1x1 convolution on a 1x1 image
-    if (in_features % 32 == 0 &&
+    if (in_features % 32 == 0 && epilogue_aligned(&ep, 15) &&  // (the bias is the epilogue's shift)
         gemm_eligible(inp, out, weight, in_features, 1, B * in_features, out_features * in_features,
                       B * out_features)) {
         return launch_gemm(ctx, RN_DTYPE_F32, RN_DTYPE_F32, inp, out, weight, 1, 1, 0, 1, 1, B,

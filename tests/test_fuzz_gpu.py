@@ -44,3 +44,9 @@ def test_defer_fuzz_short():
     out = run_tool("defer_fuzz.py", "--seconds", "10", "--seed", "104")
     assert "all within tolerance" in out
 
+
+def test_view_fuzz_short():
+    """Random fp32 entry points on views at random offsets of 0 / 4 / 8 / 12 bytes, guard bands always on
+    (tests/views.py)."""
+    out = run_tool("view_fuzz.py", "--seconds", "8", "--seed", "105")
+    assert "all guards clean" in out
