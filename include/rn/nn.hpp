@@ -31,18 +31,20 @@ inline void require(bool ok)
 class Conv2d
 {
 public:
-    Conv2d(FloatTensor w, uint64_t in_c, uint64_t out_c, uint64_t k, uint64_t s = 1, uint64_t p = 0)
+    // groups > 1: torch's grouped convolution, weight [out_c, in_c / groups, k, k] (not in the reference)
+    Conv2d(FloatTensor w, uint64_t in_c, uint64_t out_c, uint64_t k, uint64_t s = 1, uint64_t p = 0,
+           uint64_t g = 1)
         : weight(std::move(w)), in_channels(in_c), out_channels(out_c), kernel_size(k), stride(s),
-          padding(p)
+          padding(p), groups(g)
     {
     }
 
     static Conv2d loadWeightToCuda(std::string name, uint64_t in_c, uint64_t out_c, uint64_t k,
-                                   uint64_t s = 1, uint64_t p = 0)
+                                   uint64_t s = 1, uint64_t p = 0, uint64_t g = 1)
     {
         return Conv2d(FloatTensor::loadToCuda(rn::weights_dir() + name + ".weight")
-                          .view(Shape({out_c, in_c, k, k})),
-                      in_c, out_c, k, s, p);
+                          .view(Shape({out_c, in_c / g, k, k})),
+                      in_c, out_c, k, s, p, g);
     }
 
     Shape getOutShape(const Shape &x) const
@@ -59,12 +61,18 @@ public:
         (void)C, (void)ob, (void)oc;
         rn::use_layout(x);
         out.layout = x.layout;
+        if (groups != 1) {  // runs at once: the deferred route records dense convolutions only
+            gpuErrchk(rn_conv2d_grouped_forward(rn::context(), x.raw(), out.raw(), weight.raw(), kernel_size, stride,
+                                                padding, h_out, w_out, B, in_channels, out_channels, H, W, groups));
+            return;
+        }
         conv2dForwardKernel(x.raw(), out.raw(), weight.raw(), kernel_size, stride, padding, h_out,
                             w_out, B, in_channels, out_channels, H, W);
     }
 
     FloatTensor weight;
     const uint64_t in_channels, out_channels, kernel_size, stride, padding;
+    const uint64_t groups = 1;
 };
 
 class BatchNorm2d

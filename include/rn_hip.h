@@ -25,6 +25,9 @@
  *   rn_save_f32_file             <- Tensor::save                        tensor.cuh:154-163
  *   rn_sync                      <- cudaDeviceSynchronize + gpuAssert   nn.cu:14-15
  *
+ * Not in the reference: rn_conv2d_grouped_* (torch's `groups`, ResNeXt's conv2) and rn_model_create_ex
+ * (torchvision's ResNeXt / Wide ResNet networks on the same driver).
+ *
  * The model entry points replace the reference driver
  * (cuda/inference/main.cu:53-226,243-251): createLayer/createResnet152,
  * layerForward/resnet152Forward and the host argmax.
@@ -59,6 +62,9 @@
  * them is off a 16-byte boundary: a parameter arena that packs scale / shift vectors back to back
  * wants channel counts that are multiples of 4.  rn_nchw_to_nhwc_pad_dt(BF16) takes a dst on any
  * 2-byte boundary.
+ * The grouped convolution (rn_conv2d_grouped_forward, rn_conv2d_grouped_nhwc_forward_dt in fp32) follows the
+ * same rule: matrix cores with every operand on a 16-byte boundary, the direct kernel in the reference's
+ * summation order otherwise; its bf16 form is rn_conv2d_nhwc_forward_dt(BF16) and refuses like it.
  * These must be 16-byte aligned and are refused with RN_ERR_INVALID (nothing is launched,
  * rn_last_error names the alignment) otherwise: every tensor, panel, scale / shift vector and
  * residual of rn_conv2d_nhwc_forward_dt(BF16), rn_conv2d_nhwc_pair_forward_dt,
@@ -345,6 +351,52 @@ RN_API int rn_avgpool2d_nhwc_forward_dt(rn_ctx *ctx, int dtype, const void *inp,
                                         uint64_t h_out, uint64_t w_out, uint64_t B,
                                         uint64_t channels, uint64_t H, uint64_t W);
 
+/* ---- grouped convolution (torch's `groups`): ResNeXt's conv2 ---------------------------------
+ * weight [out_channels][in_channels / groups][k][k]; output channel o belongs to group
+ * o / (out_channels / groups) and reads the input channels of that group only.  groups >= 2 and a
+ * divisor of both channel counts (RN_ERR_INVALID otherwise; groups == 1 is rn_conv2d_forward /
+ * rn_conv2d_nhwc_forward, whose kernels these entry points never reach), h_out / w_out must be the
+ * convolution's output size.  Any kernel_size, stride and padding are computed.
+ * Fast path (rn_conv_group.hip, v_mfma_f32_32x32x2_f32): fp32, kernel_size 3, in_channels ==
+ * out_channels, a multiple of 32, Cg = in_channels / groups a divisor or a multiple of 32, every
+ * operand (inp, out, weight, scale, shift, residual) on a 16-byte boundary.  The weight is packed
+ * block-diagonally into super-groups of 32 output channels and the max(32, Cg) input channels they
+ * read, zeros where a channel belongs to another group: 32 / Cg times the algorithmic products for
+ * Cg < 32 (8x at Cg = 4), none wasted from Cg = 32 on.  Everything else -- other shapes, or ONE operand
+ * off a 16-byte boundary (any 4-byte boundary is accepted) -- runs a direct kernel, one thread per
+ * output in the reference's summation order (the ops.cu convolution loop over the group's channels,
+ * bit for bit); both kernels read the same packed weight.  The summation order of an output element
+ * depends on neither the batch size, the position in the batch nor the stream.
+ * Non-finite inputs: on the fast path the structural zeros are multiplied like any weight, so a NaN
+ * or an infinity in one group's input may surface in the other groups of its 32-channel super-group,
+ * never outside it; the direct kernel keeps it inside its group.
+ * bf16 storage (RN_DTYPE_BF16) has no grouped kernel of its own: pack_weight_dt expands the weight
+ * to the dense [out][in][k][k] form with zeros outside the groups and packs the panel of the dense
+ * bf16 contraction, forward_dt is rn_conv2d_nhwc_forward_dt on it (its conditions: in_channels % 64
+ * == 0, 16-byte alignment).  Correct for every Cg, `groups` times the products, and a non-finite
+ * input may surface in every output channel of the pixels that read it.
+ * rn_conv2d_grouped_forward is the reference's conv2d signature plus `groups`: OIHW weight, tensors
+ * in the context layout (NCHW: the input is transposed into scratch and the NHWC kernel writes
+ * NCHW); the weight is packed into scratch per call.  On a deferred context (rn_ctx_set_deferred) it
+ * runs what is recorded and then itself, at once: grouped convolutions are not recorded. */
+RN_API int rn_conv2d_grouped_forward(rn_ctx *ctx, const float *inp, float *out, const float *weight,
+                                     uint64_t kernel_size, uint64_t stride, uint64_t padding,
+                                     uint64_t h_out, uint64_t w_out, uint64_t B, uint64_t in_channels,
+                                     uint64_t out_channels, uint64_t H, uint64_t W, uint64_t groups);
+RN_API uint64_t rn_conv2d_grouped_packed_weight_numel_dt(int dtype, uint64_t in_channels,
+                                                         uint64_t out_channels, uint64_t kernel_size,
+                                                         uint64_t groups);
+RN_API int rn_conv2d_grouped_pack_weight_dt(rn_ctx *ctx, int dtype, const float *weight_oihw,
+                                            void *packed, uint64_t in_channels, uint64_t out_channels,
+                                            uint64_t kernel_size, uint64_t groups);
+/* NHWC in / NHWC out, packed weight, optional fused epilogue; out and epilogue->residual of out_dtype */
+RN_API int rn_conv2d_grouped_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const void *inp,
+                                             void *out, const void *packed_weight, uint64_t kernel_size,
+                                             uint64_t stride, uint64_t padding, uint64_t h_out,
+                                             uint64_t w_out, uint64_t B, uint64_t in_channels,
+                                             uint64_t out_channels, uint64_t H, uint64_t W,
+                                             uint64_t groups, const rn_epilogue *epilogue /* nullable */);
+
 /* ---- model (main.cu driver) ---------------------------------------------- */
 /* arch: 50, 101 or 152 (bottleneck blocks, counts 3/4/6/3, 3/4/23/3, 3/8/36/3), or 18 or 34
  * (torchvision's basic blocks -- two 3x3 convolutions, expansion 1, final width 512 -- counts
@@ -353,6 +405,16 @@ RN_API int rn_avgpool2d_nhwc_forward_dt(rn_ctx *ctx, int dtype, const void *inp,
  * of stages 2-4 runs conv2 and the downsample as one contraction (not bit-neutral, like the
  * bottleneck pair).  No chained launches in basic-block networks. */
 RN_API int rn_model_create(rn_ctx *ctx, rn_model **out, int arch);
+/* torchvision's bottleneck family by its constructor arguments: depth 50, 101 or 152 and
+ * (groups, width_per_group) = (1, 64) ResNet -- the same model as rn_model_create(depth) --, (32, 4),
+ * (32, 8), (64, 4) ResNeXt (resnext50_32x4d, resnext101_32x8d, resnext101_64x4d) or (1, 128) Wide ResNet
+ * (wide_resnet50_2, wide_resnet101_2); anything else RN_ERR_UNSUPPORTED.  The bottleneck's middle
+ * width is planes * width_per_group / 64 * groups; conv2 is a 3x3 convolution with `groups` groups
+ * (rn_conv2d_grouped_nhwc_forward_dt), weight [width][width / groups][3][3]; tensor keys, stem, pools
+ * and classifier are ResNet's.  Chained launches need (mid, channels) = (64, 256) / (128, 512) blocks:
+ * these networks have none and run conv3 and conv1 as separate launches.  The tuning table's header
+ * carries (groups, width_per_group): a table is refused by a model of another family. */
+RN_API int rn_model_create_ex(rn_ctx *ctx, rn_model **out, int depth, int groups, int width_per_group);
 RN_API int rn_model_destroy(rn_model *m);
 /* state_dict key -> host data; numel must match the layer table. */
 RN_API int rn_model_set_tensor(rn_model *m, const char *key, const float *host_data,
@@ -615,6 +677,9 @@ RN_API int rn_pipeline_submit_u8_n(rn_pipeline *p, const uint8_t *host_input_nhw
 typedef struct rn_shard rn_shard;
 RN_API void rn_shard_bounds(uint64_t B, int rank, int world, uint64_t *lo, uint64_t *hi);
 RN_API int rn_shard_create(rn_shard **out, const int *devices, int n_devices, int arch);
+/* the same group over models of rn_model_create_ex(depth, groups, width_per_group) */
+RN_API int rn_shard_create_ex(rn_shard **out, const int *devices, int n_devices, int depth, int groups,
+                              int width_per_group);
 RN_API int rn_shard_destroy(rn_shard *g);
 RN_API int rn_shard_count(const rn_shard *g);
 RN_API const char *rn_shard_last_error(const rn_shard *g);

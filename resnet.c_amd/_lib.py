@@ -100,6 +100,11 @@ SIGNATURES = {
                                    + [POINTER(c_float), POINTER(c_float)]),
     "rn_conv2d_nhwc_forward_dt": (c_int, [c_void_p, c_int, c_int, fptr, fptr, fptr] + [u64] * 10
                                   + [POINTER(Epilogue)]),
+    "rn_conv2d_grouped_forward": (c_int, [c_void_p, fptr, fptr, fptr] + [u64] * 11),
+    "rn_conv2d_grouped_packed_weight_numel_dt": (u64, [c_int, u64, u64, u64, u64]),
+    "rn_conv2d_grouped_pack_weight_dt": (c_int, [c_void_p, c_int, fptr, fptr, u64, u64, u64, u64]),
+    "rn_conv2d_grouped_nhwc_forward_dt": (c_int, [c_void_p, c_int, c_int, fptr, fptr, fptr] + [u64] * 11
+                                          + [POINTER(Epilogue)]),
     "rn_conv2d_packed_weight_numel_exact": (u64, [u64, u64, u64]),
     "rn_conv2d_pack_weight_exact": (c_int, [c_void_p, fptr, fptr, u64, u64, u64]),
     "rn_conv2d_nhwc_exact_forward": (c_int, [c_void_p, fptr, fptr, fptr] + [u64] * 9
@@ -127,6 +132,7 @@ SIGNATURES = {
     "rn_maxpool2d_nhwc_forward_dt": (c_int, [c_void_p, c_int, fptr, fptr] + [u64] * 9),
     "rn_avgpool2d_nhwc_forward_dt": (c_int, [c_void_p, c_int, fptr, fptr] + [u64] * 9),
     "rn_model_create": (c_int, [c_void_p, POINTER(c_void_p), c_int]),
+    "rn_model_create_ex": (c_int, [c_void_p, POINTER(c_void_p), c_int, c_int, c_int]),
     "rn_model_set_dtype": (c_int, [c_void_p, c_int]),
     "rn_model_destroy": (c_int, [c_void_p]),
     "rn_model_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, u64]),
@@ -160,6 +166,7 @@ SIGNATURES = {
     "rn_pipeline_submit_u8_n": (c_int, [c_void_p, c_void_p, u64]),
     "rn_shard_bounds": (None, [u64, c_int, c_int, POINTER(u64), POINTER(u64)]),
     "rn_shard_create": (c_int, [POINTER(c_void_p), POINTER(c_int), c_int, c_int]),
+    "rn_shard_create_ex": (c_int, [POINTER(c_void_p), POINTER(c_int), c_int, c_int, c_int, c_int]),
     "rn_shard_destroy": (c_int, [c_void_p]),
     "rn_shard_count": (c_int, [c_void_p]),
     "rn_shard_last_error": (c_char_p, [c_void_p]),

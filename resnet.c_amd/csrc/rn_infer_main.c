@@ -4,7 +4,7 @@
  * print "max index is N" per image.  The reference hard-codes everything (ResNet-152,
  * B = 1, paths); here the same defaults can be overridden from the command line.
  *
- *   rn_infer [--arch 18|34|50|101|152] [--weights DIR] [--input FILE | --u8 FILE] [--batch B]
+ *   rn_infer [--arch 18|34|50|101|152|resnext50_32x4d|resnext101_32x8d|resnext101_64x4d|wide_resnet50_2|wide_resnet101_2] [--weights DIR] [--input FILE | --u8 FILE] [--batch B]
  *            [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,c,...]
  *
  * --u8 FILE reads B x 150528 raw bytes, the decoder's 8-bit RGB crops ([B,224,224,3]), instead of
@@ -53,6 +53,24 @@ static void *read_exact(const char *path, uint64_t want, uint64_t B, int u8)
     return host;
 }
 
+/* --arch: a ResNet depth, or one of torchvision's ResNeXt / Wide ResNet names */
+static int groups_g = 0, wpg_g = 0; /* 0, 0: rn_model_create(arch) */
+static int parse_arch(const char *v)
+{
+    static const struct { const char *name; int depth, groups, wpg; } fam[] = {
+        {"resnext50_32x4d", 50, 32, 4}, {"resnext101_32x8d", 101, 32, 8}, {"resnext101_64x4d", 101, 64, 4},
+        {"wide_resnet50_2", 50, 1, 128}, {"wide_resnet101_2", 101, 1, 128}};
+    unsigned i;
+    for (i = 0; i < sizeof(fam) / sizeof(fam[0]); ++i)
+        if (!strcmp(v, fam[i].name)) {
+            groups_g = fam[i].groups;
+            wpg_g = fam[i].wpg;
+            return fam[i].depth;
+        }
+    groups_g = wpg_g = 0;
+    return atoi(!strncmp(v, "resnet", 6) ? v + 6 : v);
+}
+
 static int run_sharded(const int *devices, int ndev, int arch, const char *weights,
                        const char *input, int u8, uint64_t B, int mode, int dtype)
 {
@@ -61,7 +79,7 @@ static int run_sharded(const int *devices, int ndev, int arch, const char *weigh
     uint64_t *idx = NULL, b;
     const uint64_t want = B * 3 * 224 * 224 * (u8 ? 1 : sizeof(float));
     int st;
-    st = rn_shard_create(&g, devices, ndev, arch);
+    st = groups_g ? rn_shard_create_ex(&g, devices, ndev, arch, groups_g, wpg_g) : rn_shard_create(&g, devices, ndev, arch);
     if (st != RN_OK) { fprintf(stderr, "rn_infer: rn_shard_create: %s\n", rn_status_string(st)); return 1; }
 #define SCHECK(expr)                                                                         \
     do {                                                                                     \
@@ -118,7 +136,7 @@ int main(int argc, char **argv)
     for (i = 1; i < argc; ++i) {
         const char *a = argv[i];
         const char *v = (i + 1 < argc) ? argv[i + 1] : NULL;
-        if (!strcmp(a, "--arch") && v) { arch = atoi(v); ++i; }
+        if (!strcmp(a, "--arch") && v) { arch = parse_arch(v); ++i; }
         else if (!strcmp(a, "--weights") && v) { weights = v; ++i; }
         else if (!strcmp(a, "--input") && v) { input = v; u8 = 0; ++i; }
         else if (!strcmp(a, "--u8") && v) { input = v; u8 = 1; ++i; }
@@ -138,7 +156,7 @@ int main(int argc, char **argv)
         }
         else if (!strcmp(a, "--mode") && v) { mode = strcmp(v, "ops") ? RN_FWD_FUSED : RN_FWD_REFERENCE_OPS; ++i; }
         else {
-            fprintf(stderr, "usage: %s [--arch 18|34|50|101|152] [--weights DIR] [--input FILE | --u8 FILE] "
+            fprintf(stderr, "usage: %s [--arch 18|34|50|101|152|resnext50_32x4d|resnext101_32x8d|resnext101_64x4d|wide_resnet50_2|wide_resnet101_2] [--weights DIR] [--input FILE | --u8 FILE] "
                             "[--batch B] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,...]\n",
                     argv[0]);
             return 2;
@@ -147,7 +165,7 @@ int main(int argc, char **argv)
     printf("Started\n");
     if (ndev > 0) return run_sharded(devices, ndev, arch, weights, input, u8, B, mode, dtype);
     CHECK(ctx, rn_ctx_create(&ctx, device, NULL));
-    CHECK(ctx, rn_model_create(ctx, &model, arch));
+    CHECK(ctx, groups_g ? rn_model_create_ex(ctx, &model, arch, groups_g, wpg_g) : rn_model_create(ctx, &model, arch));
     CHECK(ctx, rn_model_load_dir(model, weights));
     if (dtype != RN_DTYPE_F32) CHECK(ctx, rn_model_set_dtype(model, dtype));
     CHECK(ctx, rn_model_finalize(model));

@@ -44,6 +44,7 @@ typedef struct {
 typedef struct {
     char name[RN_MAX_KEY];
     uint64_t cin, cout, k, stride, pad;
+    uint64_t groups;               /* > 1: a grouped convolution (ResNeXt's conv2), weight [cout][cin/groups][k][k] */
     int w, bn_w, bn_b, bn_m, bn_v; /* indices into params */
     void *packed;                  /* K-major panel, model dtype */
     float *scale, *shift;          /* folded batch-norm */
@@ -89,6 +90,7 @@ typedef struct {
 struct rn_model {
     rn_ctx *ctx;
     int arch;
+    int groups, width_per_group; /* torchvision's ResNet arguments: (1, 64) plain, (32, 4) ResNeXt, (1, 128) Wide ... */
     int basic;        /* ResNet-18/34: basic blocks (two 3x3 convolutions, expansion 1) */
     int depths[4];
     uint64_t feat;    /* width of the final feature map: 2048 (bottleneck) or 512 (basic) */
@@ -161,8 +163,8 @@ static int add_param(rn_model *m, const char *key, uint64_t numel)
     return (int)m->n_params++;
 }
 
-static int add_conv(rn_model *m, const char *name, const char *bn_name, uint64_t cin, uint64_t cout,
-                    uint64_t k, uint64_t stride, uint64_t pad)
+static int add_conv_grouped(rn_model *m, const char *name, const char *bn_name, uint64_t cin, uint64_t cout,
+                            uint64_t k, uint64_t stride, uint64_t pad, uint64_t groups)
 {
     rn_conv *c = &m->convs[m->n_convs];
     char key[RN_MAX_KEY + 16];
@@ -173,8 +175,9 @@ static int add_conv(rn_model *m, const char *name, const char *bn_name, uint64_t
     c->k = k;
     c->stride = stride;
     c->pad = pad;
+    c->groups = groups;
     snprintf(key, sizeof(key), "%s.weight", name);
-    c->w = add_param(m, key, cout * cin * k * k);
+    c->w = add_param(m, key, cout * (cin / groups) * k * k);
     snprintf(key, sizeof(key), "%s.weight", bn_name);
     c->bn_w = add_param(m, key, cout);
     snprintf(key, sizeof(key), "%s.bias", bn_name);
@@ -186,7 +189,19 @@ static int add_conv(rn_model *m, const char *name, const char *bn_name, uint64_t
     return m->n_convs++;
 }
 
-int rn_model_create(rn_ctx *ctx, rn_model **out, int arch)
+static int add_conv(rn_model *m, const char *name, const char *bn_name, uint64_t cin, uint64_t cout,
+                    uint64_t k, uint64_t stride, uint64_t pad)
+{
+    return add_conv_grouped(m, name, bn_name, cin, cout, k, stride, pad, 1);
+}
+
+/* bottleneck width of a stage (torchvision: int(planes * width_per_group / 64) * groups) */
+static uint64_t mid_width(const rn_model *m, int li)
+{
+    return kWidths[li][1] * (uint64_t)m->width_per_group / 64 * (uint64_t)m->groups;
+}
+
+static int model_create(rn_ctx *ctx, rn_model **out, int arch, int groups, int width_per_group)
 {
     static const int d50[4] = {3, 4, 6, 3}, d101[4] = {3, 4, 23, 3}, d152[4] = {3, 8, 36, 3};
     static const int d18[4] = {2, 2, 2, 2}, d34[4] = {3, 4, 6, 3};
@@ -210,6 +225,8 @@ int rn_model_create(rn_ctx *ctx, rn_model **out, int arch)
     if (!m) return RN_ERR_NOMEM;
     m->ctx = ctx;
     m->arch = arch;
+    m->groups = groups;
+    m->width_per_group = width_per_group;
     m->basic = arch == 18 || arch == 34;
     m->feat = m->basic ? kBasicWidths[3] : kWidths[3][2];
     /* arenas: x4 the input image, p0 / p1 the block outputs (and the 112x112x64 stem output), dsb the
@@ -217,7 +234,7 @@ int rn_model_create(rn_ctx *ctx, rn_model **out, int arch)
     m->x4_img = (uint64_t)230 * 230 * 4; /* bf16 models keep a 3-pixel zero border */
     m->p_img = (uint64_t)112 * 112 * 64; /* == 56*56*256 */
     m->ds_img = m->basic ? (uint64_t)28 * 28 * 128 : m->p_img;
-    m->t1_img = m->basic ? (uint64_t)56 * 56 * 64 : (uint64_t)56 * 56 * 128; /* layer2.0 conv1 of a bottleneck */
+    m->t1_img = m->basic ? (uint64_t)56 * 56 * 64 : (uint64_t)56 * 56 * mid_width(m, 1); /* layer2.0 conv1 of a bottleneck */
     m->t2_img = m->basic ? 0 : m->t1_img;
     m->s1_img = (uint64_t)56 * 56 * (m->basic ? kBasicWidths[0] : kWidths[0][2]);
     for (li = 0; li < 4; ++li) {
@@ -247,7 +264,7 @@ int rn_model_create(rn_ctx *ctx, rn_model **out, int arch)
                 cin = bi == 0 && li > 0 ? kBasicWidths[li - 1] : cout;
             } else {
                 cin = bi == 0 ? kWidths[li][0] : kWidths[li][2];
-                mid = kWidths[li][1];
+                mid = mid_width(m, li);
                 cout = kWidths[li][2];
             }
             snprintf(pre, sizeof(pre), "layer%d.%d", li + 1, bi);
@@ -275,7 +292,7 @@ int rn_model_create(rn_ctx *ctx, rn_model **out, int arch)
             b->conv1 = add_conv(m, name, bn, cin, mid, 1, 1, 0);
             snprintf(name, sizeof(name), "%s.conv2", pre);
             snprintf(bn, sizeof(bn), "%s.bn2", pre);
-            b->conv2 = add_conv(m, name, bn, mid, mid, 3, stride, 1); /* stride on the 3x3 */
+            b->conv2 = add_conv_grouped(m, name, bn, mid, mid, 3, stride, 1, (uint64_t)groups); /* stride on the 3x3 */
             snprintf(name, sizeof(name), "%s.conv3", pre);
             snprintf(bn, sizeof(bn), "%s.bn3", pre);
             b->conv3 = b->tail = add_conv(m, name, bn, mid, cout, 1, 1, 0);
@@ -285,6 +302,20 @@ int rn_model_create(rn_ctx *ctx, rn_model **out, int arch)
     m->fc_b = add_param(m, "fc.bias", RN_CLASSES);
     *out = m;
     return RN_OK;
+}
+
+int rn_model_create(rn_ctx *ctx, rn_model **out, int arch) { return model_create(ctx, out, arch, 1, 64); }
+
+/* torchvision's bottleneck family: (1, 64) ResNet, (32, 4) / (32, 8) / (64, 4) ResNeXt, (1, 128) Wide ResNet */
+int rn_model_create_ex(rn_ctx *ctx, rn_model **out, int depth, int groups, int width_per_group)
+{
+    const int ok = (groups == 1 && (width_per_group == 64 || width_per_group == 128)) ||
+                   (groups == 32 && (width_per_group == 4 || width_per_group == 8)) ||
+                   (groups == 64 && width_per_group == 4);
+    if (out) *out = NULL;
+    if (!ctx || !out) return RN_ERR_INVALID;
+    if (!ok || (depth != 50 && depth != 101 && depth != 152)) return RN_ERR_UNSUPPORTED;
+    return model_create(ctx, out, depth, groups, width_per_group);
 }
 
 static void free_acts(rn_model *m)
@@ -452,7 +483,9 @@ int rn_model_finalize(rn_model *m)
     }
     for (c = 0; c < m->n_convs; ++c) {
         rn_conv *cv = &m->convs[c];
-        const uint64_t pn = rn_conv2d_packed_weight_numel_dt(m->dtype, cv->cin, cv->cout, cv->k);
+        const uint64_t pn = cv->groups > 1 ? rn_conv2d_grouped_packed_weight_numel_dt(m->dtype, cv->cin, cv->cout,
+                                                                                     cv->k, cv->groups)
+                                           : rn_conv2d_packed_weight_numel_dt(m->dtype, cv->cin, cv->cout, cv->k);
         if (!cv->packed) {
             st = rn_malloc(m->ctx, &cv->packed, pn * elem_size(m));
             if (st != RN_OK) return st;
@@ -463,8 +496,10 @@ int rn_model_finalize(rn_model *m)
             st = rn_malloc(m->ctx, (void **)&cv->shift, cv->cout * sizeof(float));
             if (st != RN_OK) return st;
         }
-        st = rn_conv2d_pack_weight_dt(m->ctx, m->dtype, m->params[cv->w].dev, cv->packed, cv->cin,
-                                      cv->cout, cv->k);
+        st = cv->groups > 1 ? rn_conv2d_grouped_pack_weight_dt(m->ctx, m->dtype, m->params[cv->w].dev, cv->packed,
+                                                               cv->cin, cv->cout, cv->k, cv->groups)
+                            : rn_conv2d_pack_weight_dt(m->ctx, m->dtype, m->params[cv->w].dev, cv->packed, cv->cin,
+                                                       cv->cout, cv->k);
         if (st != RN_OK) return st;
         st = rn_batchnorm2d_fold(m->ctx, m->params[cv->bn_w].dev, m->params[cv->bn_b].dev,
                                  m->params[cv->bn_m].dev, m->params[cv->bn_v].dev, cv->scale,
@@ -746,7 +781,8 @@ static int op_conv(rn_model *m, const rn_conv *cv, const void *x, void *y, uint6
     const uint64_t pad = exact ? 0 : pad_override >= 0 ? (uint64_t)pad_override : cv->pad;
     const uint64_t ho = rn_conv_output_size(H, cv->k, cv->stride, pad);
     const uint64_t wo = rn_conv_output_size(W, cv->k, cv->stride, pad);
-    const double M = (double)(B * ho * wo), K = (double)(cv->cin * cv->k * cv->k);
+    /* a grouped convolution counts its algorithmic products: K = k*k*cin/groups per output */
+    const double M = (double)(B * ho * wo), K = (double)(cv->cin / cv->groups * cv->k * cv->k);
     const double es = (double)elem_size(m);
     double bytes = es * ((double)(B * H * W * cv->cin) + K * (double)cv->cout +
                          M * (double)cv->cout);
@@ -774,6 +810,9 @@ static int op_conv(rn_model *m, const rn_conv *cv, const void *x, void *y, uint6
             exact ? rn_conv2d_nhwc_exact_forward(m->run, (const float *)x, (float *)y,
                                                  m->stem_packed_exact, cv->k, cv->stride, ho, wo, B,
                                                  cv->cin, cv->cout, H, W, ep)
+            : cv->groups > 1
+                  ? rn_conv2d_grouped_nhwc_forward_dt(m->run, m->dtype, m->dtype, x, y, cv->packed, cv->k, cv->stride,
+                                                      pad, ho, wo, B, cv->cin, cv->cout, H, W, cv->groups, ep)
                   : rn_conv2d_nhwc_forward_dt(m->run, m->dtype, m->dtype, x, y, cv->packed, cv->k,
                                               cv->stride, pad, ho, wo, B, cv->cin, cv->cout, H, W, ep);
         rn_ctx_set_conv_tile(m->run, 0);
@@ -1343,6 +1382,10 @@ static int replay_call(rn_model *m, rn_ctx *run, const rn_conv_call *k)
         return rn_conv2d_nhwc_exact_forward(run, (const float *)k->x, (float *)k->y, m->stem_packed_exact,
                                             cv->k, cv->stride, ho, wo, k->B, cv->cin, cv->cout, k->H, k->W,
                                             k->has_ep ? &k->ep : NULL);
+    if (cv->groups > 1) /* one kernel, no tile candidates: every candidate times the same launch */
+        return rn_conv2d_grouped_nhwc_forward_dt(run, m->dtype, m->dtype, k->x, k->y, cv->packed, cv->k, cv->stride,
+                                                 k->pad, ho, wo, k->B, cv->cin, cv->cout, k->H, k->W, cv->groups,
+                                                 k->has_ep ? &k->ep : NULL);
     return rn_conv2d_nhwc_forward_dt(run, m->dtype, m->dtype, k->x, k->y, cv->packed, cv->k, cv->stride,
                                      k->pad, ho, wo, k->B, cv->cin, cv->cout, k->H, k->W,
                                      k->has_ep ? &k->ep : NULL);
@@ -1445,6 +1488,12 @@ int rn_model_tune(rn_model *m, const float *input_nchw, uint64_t B, float *logit
 #define RN_TUNING_MAGIC 0x726e54554e453034ull /* "rnTUNE04" */
 #define RN_TUNING_HEADER 10
 
+/* header word 9: 0 for the plain (1, 64) networks, whose tables keep their format */
+static uint64_t tuning_family(const rn_model *m)
+{
+    return m->groups == 1 && m->width_per_group == 64 ? 0 : (uint64_t)m->groups << 32 | (uint64_t)m->width_per_group;
+}
+
 static uint64_t tuning_settings(const rn_model *m)
 {
     return (uint64_t)m->pair_fusion | (uint64_t)m->stem_exact << 1 | (uint64_t)m->stem_pool << 2 |
@@ -1469,7 +1518,7 @@ int rn_model_export_tuning(const rn_model *m, uint64_t *words, uint64_t cap, uin
     words[at++] = (uint64_t)m->n_convs;
     words[at++] = (uint64_t)m->n_blocks;
     words[at++] = (uint64_t)rn_conv_tile_candidates();
-    words[at++] = 0;
+    words[at++] = tuning_family(m);
     for (c = 0; c < m->n_convs; ++c)
         for (k = 0; k < 2; ++k) {
             words[at++] = (uint64_t)m->convs[c].tile[k];
@@ -1490,7 +1539,7 @@ int rn_model_import_tuning(rn_model *m, const uint64_t *words, uint64_t n_words)
     if (!m || !words || n_words < RN_TUNING_HEADER) return RN_ERR_INVALID;
     if (words[0] != RN_TUNING_MAGIC || words[1] != (uint64_t)m->arch || words[2] != (uint64_t)m->dtype ||
         words[3] != tuning_settings(m) || words[6] != (uint64_t)m->n_convs || words[7] != (uint64_t)m->n_blocks ||
-        words[8] != (uint64_t)rn_conv_tile_candidates() ||
+        words[8] != (uint64_t)rn_conv_tile_candidates() || words[9] != tuning_family(m) ||
         n_words != RN_TUNING_HEADER + 4 * ((uint64_t)m->n_convs + (uint64_t)m->n_blocks))
         return RN_ERR_INVALID; /* measured for another model, setting or build */
     for (c = 0; c < m->n_convs + m->n_blocks; ++c) /* a candidate this build does not have */

@@ -60,6 +60,7 @@ typedef struct rn_shard_worker {
 
 struct rn_shard {
     int n, arch;
+    int groups, width_per_group; /* 0, 0: rn_model_create(arch); else rn_model_create_ex */
     rn_shard_worker *w;
     pthread_mutex_t mu;
     pthread_cond_t cv_job, cv_done;
@@ -231,7 +232,8 @@ static int run_job(rn_shard_worker *w, const struct rn_shard *g)
     case JOB_CREATE:
         WTRY(w, rn_ctx_create(&w->ctx, w->device, NULL));
         bind_near_device(w);
-        WTRY(w, rn_model_create(w->ctx, &w->model, g->arch));
+        WTRY(w, g->groups ? rn_model_create_ex(w->ctx, &w->model, g->arch, g->groups, g->width_per_group)
+                          : rn_model_create(w->ctx, &w->model, g->arch));
         return RN_OK;
     case JOB_SET_TENSOR:
         WTRY(w, rn_model_set_tensor(w->model, g->text, g->tensor, g->numel));
@@ -410,7 +412,20 @@ int rn_shard_destroy(rn_shard *g)
     return RN_OK;
 }
 
+static int shard_create(rn_shard **out, const int *devices, int n_devices, int arch, int groups, int width_per_group);
+
 int rn_shard_create(rn_shard **out, const int *devices, int n_devices, int arch)
+{
+    return shard_create(out, devices, n_devices, arch, 0, 0);
+}
+
+int rn_shard_create_ex(rn_shard **out, const int *devices, int n_devices, int depth, int groups, int width_per_group)
+{
+    if (groups < 1 || width_per_group < 1) return RN_ERR_UNSUPPORTED;
+    return shard_create(out, devices, n_devices, depth, groups, width_per_group);
+}
+
+static int shard_create(rn_shard **out, const int *devices, int n_devices, int arch, int groups, int width_per_group)
 {
     struct rn_shard *g;
     int i, st;
@@ -420,6 +435,8 @@ int rn_shard_create(rn_shard **out, const int *devices, int n_devices, int arch)
     if (!g) return RN_ERR_NOMEM;
     g->n = n_devices;
     g->arch = arch;
+    g->groups = groups;
+    g->width_per_group = width_per_group;
     pthread_mutex_init(&g->mu, NULL);
     pthread_cond_init(&g->cv_job, NULL);
     pthread_cond_init(&g->cv_done, NULL);

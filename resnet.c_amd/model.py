@@ -215,8 +215,12 @@ class NativeModel:
         self.arch = arch
         lib = L.lib()
         h = ctypes.c_void_p()
-        L.check(lib.rn_model_create(self.ctx.handle, ctypes.byref(h), ARCH_ID[arch]),
-                "rn_model_create", self.ctx.handle)
+        if arch in weights.FAMILY:  # ResNeXt / Wide ResNet: torchvision's (depth, groups, width_per_group)
+            L.check(lib.rn_model_create_ex(self.ctx.handle, ctypes.byref(h), *weights.FAMILY[arch]),
+                    "rn_model_create_ex", self.ctx.handle)
+        else:
+            L.check(lib.rn_model_create(self.ctx.handle, ctypes.byref(h), ARCH_ID[arch]),
+                    "rn_model_create", self.ctx.handle)
         self.handle = h
         if (state is None) == (weights_dir is None):
             raise ValueError("give exactly one of state / weights_dir")
@@ -387,7 +391,11 @@ class ShardedModel:
             raise ValueError("give exactly one of state / weights_dir")
         dev = (ctypes.c_int * len(devices))(*devices)
         h = ctypes.c_void_p()
-        L.check(lib.rn_shard_create(ctypes.byref(h), dev, len(devices), ARCH_ID[arch]), "rn_shard_create")
+        if arch in weights.FAMILY:
+            L.check(lib.rn_shard_create_ex(ctypes.byref(h), dev, len(devices), *weights.FAMILY[arch]),
+                    "rn_shard_create_ex")
+        else:
+            L.check(lib.rn_shard_create(ctypes.byref(h), dev, len(devices), ARCH_ID[arch]), "rn_shard_create")
         self.handle, self.n = h, len(devices)
         self._stream_B = 0
         self._stream_input = "f32"

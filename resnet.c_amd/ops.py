@@ -505,3 +505,78 @@ def stem_conv_pool(x, w, scale=None, shift=None):
     L.check(lib.rn_memcpy_d2h(ctx.handle, hp.ctypes.data, out.ptr, hp.nbytes), "d2h", ctx.handle)
     return (np.ascontiguousarray(hy.reshape(B, ho, wo, 64).transpose(0, 3, 1, 2)),
             np.ascontiguousarray(hp.reshape(B, ph, pw, 64).transpose(0, 3, 1, 2)))
+
+
+# ---------------------------------------------------------------------------
+# grouped convolution (torch's ``groups``)
+# ---------------------------------------------------------------------------
+def conv2d_grouped(x, w, stride: int = 1, pad: int = 0, groups: int = 1, layout: str = "nchw") -> np.ndarray:
+    """rn_conv2d_grouped_forward: w is [Cout, Cin / groups, k, k] (torch's layout)."""
+    B, Cin, H, W = x.shape
+    Cout, _, k, _ = w.shape
+    ho, wo = conv_output_size(H, k, stride, pad), conv_output_size(W, k, stride, pad)
+    dx, dw = _up(x, layout), _up(w, "nchw")
+    out = FloatTensor((B, Cout, ho, wo), Device.GPU)
+    _run("rn_conv2d_grouped_forward", layout, dx.data(), out.data(), dw.data(), k, stride, pad, ho, wo, B,
+         Cin, Cout, H, W, groups)
+    return _down(out, (B, Cout, ho, wo), layout)
+
+
+def conv2d_grouped_nhwc(x, w, stride=1, pad=0, groups=1, scale=None, shift=None, residual=None,
+                        relu_: bool = False) -> np.ndarray:
+    """rn_conv2d_grouped_pack_weight_dt + rn_conv2d_grouped_nhwc_forward_dt in fp32, with an epilogue
+    (NCHW host arrays)."""
+    ctx, lib = get_ctx(), L.lib()
+    B, Cin, H, W = x.shape
+    Cout, _, k, _ = w.shape
+    ho, wo = conv_output_size(H, k, stride, pad), conv_output_size(W, k, stride, pad)
+    dx, dw = _up(x, "nhwc"), _up(w, "nchw")
+    pn = int(lib.rn_conv2d_grouped_packed_weight_numel_dt(L.RN_DTYPE_F32, Cin, Cout, k, groups))
+    packed = FloatTensor((max(pn, 1),), Device.GPU)
+    L.check(lib.rn_conv2d_grouped_pack_weight_dt(ctx.handle, L.RN_DTYPE_F32, dw.data(), packed.data(), Cin, Cout,
+                                                 k, groups), "rn_conv2d_grouped_pack_weight_dt", ctx.handle)
+    keep = [_up(v, "nchw") if v is not None else None for v in (scale, shift)]
+    dres = _up(residual, "nhwc") if residual is not None else None
+    ep = L.Epilogue(keep[0].data() if keep[0] else None, keep[1].data() if keep[1] else None,
+                    dres.data() if dres else None, int(relu_))
+    out = FloatTensor((B, Cout, ho, wo), Device.GPU)
+    L.check(lib.rn_conv2d_grouped_nhwc_forward_dt(ctx.handle, L.RN_DTYPE_F32, L.RN_DTYPE_F32, dx.data(), out.data(),
+                                                  packed.data(), k, stride, pad, ho, wo, B, Cin, Cout, H, W, groups,
+                                                  ctypes.byref(ep)),
+            "rn_conv2d_grouped_nhwc_forward_dt", ctx.handle)
+    ctx.sync()
+    return _down(out, (B, Cout, ho, wo), "nhwc")
+
+
+def conv2d_grouped_nhwc_bf16(x, w, stride=1, pad=0, groups=1, scale=None, shift=None, residual=None,
+                             relu_: bool = False, out_f32: bool = False) -> np.ndarray:
+    """The bf16 route of the grouped convolution (dense panel with zeros outside the groups).  NCHW fp32
+    host arrays in (rounded to bf16 on upload), NCHW fp32 host array out."""
+    from .tensor import _DeviceBuffer
+    ctx, lib = get_ctx(), L.lib()
+    B, Cin, H, W = x.shape
+    Cout, _, k, _ = w.shape
+    ho, wo = conv_output_size(H, k, stride, pad), conv_output_size(W, k, stride, pad)
+    dx = _up_raw(to_bf16_bits(np.asarray(x, dtype=np.float32).transpose(0, 2, 3, 1)))
+    dw = _up(w, "nchw")
+    pn = int(lib.rn_conv2d_grouped_packed_weight_numel_dt(L.RN_DTYPE_BF16, Cin, Cout, k, groups))
+    packed = _DeviceBuffer(ctx, max(pn, 8) * 2)
+    L.check(lib.rn_conv2d_grouped_pack_weight_dt(ctx.handle, L.RN_DTYPE_BF16, dw.data(), packed.ptr, Cin, Cout, k,
+                                                 groups), "rn_conv2d_grouped_pack_weight_dt", ctx.handle)
+    keep = [_up(v, "nchw") if v is not None else None for v in (scale, shift)]
+    dres = None
+    if residual is not None:
+        r = np.asarray(residual, dtype=np.float32).transpose(0, 2, 3, 1)
+        dres = _up_raw(r if out_f32 else to_bf16_bits(r))
+    ep = L.Epilogue(keep[0].data() if keep[0] else None, keep[1].data() if keep[1] else None,
+                    dres.ptr if dres else None, int(relu_))
+    n_out = B * Cout * ho * wo
+    out = _DeviceBuffer(ctx, n_out * (4 if out_f32 else 2))
+    L.check(lib.rn_conv2d_grouped_nhwc_forward_dt(ctx.handle, L.RN_DTYPE_BF16,
+                                                  L.RN_DTYPE_F32 if out_f32 else L.RN_DTYPE_BF16, dx.ptr, out.ptr,
+                                                  packed.ptr, k, stride, pad, ho, wo, B, Cin, Cout, H, W, groups,
+                                                  ctypes.byref(ep)),
+            "rn_conv2d_grouped_nhwc_forward_dt", ctx.handle)
+    ctx.sync()
+    y = _down_raw(out, np.float32, n_out) if out_f32 else from_bf16_bits(_down_raw(out, np.uint16, n_out))
+    return y.reshape(B, ho, wo, Cout).transpose(0, 3, 1, 2).copy()

@@ -36,6 +36,16 @@ DEPTHS = {
     "resnet101": (3, 4, 23, 3),
     "resnet152": (3, 8, 36, 3),  # main.cu:116-119
 }
+# torchvision's other bottleneck networks: name -> (depth, groups, width_per_group).  The bottleneck's middle
+# width is planes * width_per_group // 64 * groups and conv2 is a 3x3 convolution with `groups` groups
+# (weight [width, width // groups, 3, 3]); everything else is the ResNet of that depth.
+FAMILY = {
+    "resnext50_32x4d": (50, 32, 4),
+    "resnext101_32x8d": (101, 32, 8),
+    "resnext101_64x4d": (101, 64, 4),
+    "wide_resnet50_2": (50, 1, 128),
+    "wide_resnet101_2": (101, 1, 128),
+}
 # basic-block networks: not in DEPTHS, whose names are the bottleneck networks (depths_of)
 BASIC_DEPTHS = {
     "resnet18": (2, 2, 2, 2),
@@ -48,9 +58,31 @@ BN_FIELDS = ("weight", "bias", "running_mean", "running_var")
 
 def depths_of(arch: str) -> Tuple[int, int, int, int]:
     try:
-        return DEPTHS[arch]
+        return DEPTHS[f"resnet{FAMILY[arch][0]}"] if arch in FAMILY else DEPTHS[arch]
     except KeyError:
-        raise ValueError(f"unknown arch {arch!r}; expected one of {sorted(DEPTHS)}") from None
+        raise ValueError(f"unknown arch {arch!r}; expected one of {sorted(list(DEPTHS) + list(FAMILY))}") from None
+
+
+def family_of(arch: str) -> Tuple[int, int, int]:
+    """(depth, groups, width_per_group) of a bottleneck network: (50, 1, 64) for resnet50,
+    (50, 32, 4) for resnext50_32x4d, (50, 1, 128) for wide_resnet50_2."""
+    if arch in FAMILY:
+        return FAMILY[arch]
+    depths_of(arch)  # raises for an unknown name
+    return (int(arch[len("resnet"):]), 1, 64)
+
+
+def stage_widths(arch: str) -> Tuple[Tuple[int, int, int], ...]:
+    """(in, mid, out) per stage; mid = planes * width_per_group // 64 * groups."""
+    _d, groups, wpg = family_of(arch)
+    return tuple((cin, mid * wpg // 64 * groups, cout) for cin, mid, cout in STAGE_WIDTHS)
+
+
+def conv_groups(arch: str, conv_name: str) -> int:
+    """groups of a convolution: the family's for a bottleneck's conv2, 1 everywhere else."""
+    if arch in FAMILY and conv_name.startswith("layer") and conv_name.endswith(".conv2"):
+        return FAMILY[arch][1]
+    return 1
 
 
 def block_kind(arch: str) -> str:
@@ -67,7 +99,8 @@ def feature_width(arch: str) -> int:
 
 
 def conv_specs(arch: str) -> List[Tuple[str, int, int, int, int, int]]:
-    """(name, cin, cout, k, stride, pad) for every convolution, in forward order."""
+    """(name, cin, cout, k, stride, pad) for every convolution, in forward order (conv_groups() gives
+    the groups of a ResNeXt's conv2: its weight is [cout, cin // groups, k, k])."""
     out = [("conv1", 3, 64, 7, 2, 3)]
     if block_kind(arch) == "basic":
         for pre, cin, cout, stride, has_ds in iter_basic_blocks(arch):
@@ -77,7 +110,7 @@ def conv_specs(arch: str) -> List[Tuple[str, int, int, int, int, int]]:
             out.append((f"{pre}.conv2", cout, cout, 3, 1, 1))
         return out
     for li, ((cin, mid, cout), stride, n) in enumerate(
-        zip(STAGE_WIDTHS, STAGE_STRIDES, depths_of(arch)), start=1
+        zip(stage_widths(arch), STAGE_STRIDES, depths_of(arch)), start=1
     ):
         for bi in range(n):
             pre = f"layer{li}.{bi}"
@@ -103,7 +136,7 @@ def tensor_specs(arch: str) -> List[Tuple[str, Tuple[int, ...]]]:
     """Every file the loader reads: (state_dict key, shape)."""
     specs: List[Tuple[str, Tuple[int, ...]]] = []
     for name, cin, cout, k, _s, _p in conv_specs(arch):
-        specs.append((f"{name}.weight", (cout, cin, k, k)))
+        specs.append((f"{name}.weight", (cout, cin // conv_groups(arch, name), k, k)))
         bn = bn_of(name)
         for f in BN_FIELDS:
             specs.append((f"{bn}.{f}", (cout,)))
@@ -244,7 +277,7 @@ def load_weights_bin(arch: str, dir_name: str) -> Dict[str, np.ndarray]:
 def iter_blocks(arch: str) -> Iterator[Tuple[str, int, int, int, int, bool]]:
     """(prefix, cin, mid, cout, stride, has_downsample) per bottleneck block."""
     for li, ((cin, mid, cout), stride, n) in enumerate(
-        zip(STAGE_WIDTHS, STAGE_STRIDES, depths_of(arch)), start=1
+        zip(stage_widths(arch), STAGE_STRIDES, depths_of(arch)), start=1
     ):
         for bi in range(n):
             b_in = cin if bi == 0 else cout
@@ -284,6 +317,6 @@ def forward_flops(arch: str, hw: int = 224) -> int:
             first = name.endswith(("downsample.0", ".conv1"))
             n_in = block_in[pre] if first else last
         n_out = out(n_in, k, s, p)
-        total += 2 * n_out * n_out * cout * cin * k * k
+        total += 2 * n_out * n_out * cout * (cin // conv_groups(arch, name)) * k * k
         last = n_out
     return total + 2 * feature_width(arch) * NUM_CLASSES
