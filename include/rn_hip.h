@@ -335,6 +335,57 @@ RN_API int rn_nchw_to_nhwc_pad_dt(rn_ctx *ctx, int dtype, const float *src, void
 RN_API int rn_image_u8_to_nhwc_pad_dt(rn_ctx *ctx, int dtype, const uint8_t *img, void *dst,
                                       uint64_t B, uint64_t H, uint64_t W, uint64_t Cpad,
                                       uint64_t border, const float mean[3], const float std[3]);
+/* ---- resize and centre-crop of decoded images (the preset's first half, on the device) -------
+ * What preprocess.preprocess_image_u8 does on the host with PIL -- short side to `resize` with the
+ * antialiased bilinear reducer, centre crop of crop x crop -- byte for byte, for images of any size.
+ * The arithmetic is PIL's 8-bit resample (preprocess.resize_crop_u8 restates it in numpy):
+ *   geometry      W <= H: (nw, nh) = (resize, (int)((double)(resize * H) / W)), otherwise
+ *                 (nw, nh) = ((int)((double)(resize * W) / H), resize);
+ *                 left = round-half-even((nw - crop) / 2.0), top likewise;
+ *   coefficients  per axis in -> out, in double: scale = in / out, fs = max(scale, 1), for output xx
+ *                 center = (xx + 0.5) * scale, xmin = max((int)(center - fs + 0.5), 0),
+ *                 xmax = min((int)(center + fs + 0.5), in) - xmin,
+ *                 w[x] = max(0, 1 - |(x + xmin - center + 0.5) / fs|), divided by their sum (added in
+ *                 index order), k[x] = (int)(0.5 + w[x] * 2^22); ksize = 2 * (int)ceil(fs) + 1;
+ *   one pass      out = clip8((2^21 + sum px * k) >> 22) in int32;
+ *   order         the horizontal pass first, rounded to 8 bits, the vertical pass on that result.
+ * The coefficients are computed on the host (plain C doubles, no contraction into fma) and uploaded
+ * with the batch; only the crop columns and crop rows that are read get any. */
+RN_API int rn_resize_crop_geometry(uint64_t H, uint64_t W, uint64_t resize, uint64_t crop, uint64_t *nh,
+                                   uint64_t *nw, uint64_t *top, uint64_t *left);
+/* Pure host code: the table of outputs [first, first + count) of one axis.  bounds_out: count pairs
+ * (xmin, xmax); coeffs_out: count rows of *ksize ints (the first xmax of a row are set, the rest 0);
+ * cap: ints coeffs_out holds -- RN_ERR_INVALID when count * ksize > cap (ksize is still returned, so
+ * a caller may ask with cap 0 first), or for a zero size or first + count > out_size. */
+RN_API int rn_resize_coefficients(uint64_t in_size, uint64_t out_size, uint64_t first, uint64_t count,
+                                  int32_t *bounds_out, int32_t *coeffs_out, uint64_t cap, uint64_t *ksize);
+/* A ragged batch: packed_dev holds B interleaved 8-bit RGB images, image i at byte offsets[i] (any
+ * offset: the loads assume no alignment) with heights[i] rows of widths[i] pixels; offsets, heights
+ * and widths are host arrays.  dst: [B, crop, crop, 3] bytes on the device, any alignment.  One
+ * launch (rn_resize.hip): a block owns a band of output rows of one image, runs the horizontal pass
+ * of the source rows that band reads into LDS as bytes (64 KB of rows at a time, so any scale fits)
+ * and the vertical pass out of LDS; nothing outside the crop is computed.  The call builds the
+ * tables on the host, uploads them into context scratch and waits for that upload (the launch itself
+ * is asynchronous), so it cannot be captured into a graph.
+ * RN_ERR_INVALID, nothing launched, rn_ctx_launch_count unchanged: a null pointer (B > 0), an image
+ * with a zero dimension, crop == 0, crop > resize, an image whose resized short or long side is
+ * smaller than crop (the short side is `resize`, so never), or a dimension over the limits below.
+ * B == 0 is RN_OK.  Limits: image sides <= 16384 (offsets and tap positions stay in 32 bits),
+ * resize <= 16384, crop <= 2048 (a thread keeps 24 accumulators: one row of 3 * crop <= 256 * 24
+ * bytes), scale = side / resized side <= 64 (the table of one image stays under 2 * crop * 133 ints;
+ * a row of taps is at most 131 long). */
+RN_API int rn_image_u8_resize_crop(rn_ctx *ctx, const uint8_t *packed_dev, const uint64_t *offsets,
+                                   const uint64_t *heights, const uint64_t *widths, uint64_t B,
+                                   uint8_t *dst_dev, uint64_t resize, uint64_t crop);
+/* The two halves of that call, for callers that stage the table themselves (the host pipeline puts
+ * it into its pinned staging behind the images): _table fills host memory (pure host code; with
+ * table == NULL or cap too small it only returns the size in *bytes, and RN_ERR_INVALID for the
+ * latter), _launch runs the kernel on a table that is already on the device, 16-byte aligned. */
+RN_API int rn_image_u8_resize_crop_table(const uint64_t *offsets, const uint64_t *heights,
+                                         const uint64_t *widths, uint64_t B, uint64_t resize, uint64_t crop,
+                                         void *table, uint64_t cap, uint64_t *bytes);
+RN_API int rn_image_u8_resize_crop_launch(rn_ctx *ctx, const uint8_t *packed_dev, const void *table_dev,
+                                          uint64_t B, uint8_t *dst_dev, uint64_t crop);
 /* inp/packed_weight of `dtype`, out and epilogue->residual of `out_dtype` */
 RN_API int rn_conv2d_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const void *inp,
                                      void *out, const void *packed_weight, uint64_t kernel_size,
@@ -456,6 +507,18 @@ RN_API int rn_model_forward(rn_model *m, const float *input_nchw, uint64_t B, fl
  * the float entry point) serve both routes. */
 RN_API int rn_model_forward_u8(rn_model *m, const uint8_t *input_nhwc, uint64_t B, float *logits,
                                int mode);
+/* The same forward from decoded images of any size: rn_image_u8_resize_crop(resize 256, crop 224) into
+ * a buffer the model owns ([B,224,224,3] of the largest sub-batch seen), then exactly the launches of
+ * rn_model_forward_u8 on it -- the logits are those of rn_model_forward_u8 on the crops PIL makes on
+ * the host, bit for bit.  Same sub-batches (<= 512), streams and profiling (the launch is the op
+ * "image_u8_resize_crop" of layer "input", the first record of a profiled forward) as the byte
+ * route; the resize of a sub-batch runs on the model's own stream before the parts fork.  The
+ * coefficient tables come from host memory that the call frees, so a stream that is being captured
+ * is refused with RN_ERR_UNSUPPORTED.  Refusals of rn_image_u8_resize_crop apply (checked for the
+ * whole batch before anything is launched). */
+RN_API int rn_model_forward_images_u8(rn_model *m, const uint8_t *packed_dev, const uint64_t *offsets,
+                                      const uint64_t *heights, const uint64_t *widths, uint64_t B,
+                                      float *logits, int mode);
 /* Run one forward, then time every tile candidate of every convolution at batch B on the
  * device (events on the context's stream, on the buffers that forward used) and remember the fastest per layer for
  * that batch size.  Results do not change (candidates are bit-identical), only speed. */
@@ -665,6 +728,16 @@ RN_API int rn_pipeline_create_u8(rn_model *m, rn_pipeline **out, uint64_t B, int
 RN_API int rn_pipeline_input_buffer_u8(rn_pipeline *p, uint8_t **host_staging);
 /* host_input_nhwc: n*150528 bytes in any host memory, or NULL / the staging pointer; n <= B */
 RN_API int rn_pipeline_submit_u8_n(rn_pipeline *p, const uint8_t *host_input_nhwc, uint64_t n);
+/* A pipeline for decoded images of any size (rn_model_forward_images_u8): pinned staging and device
+ * input buffers hold the packed batch -- at most max_batch_bytes of pixels -- and behind it the
+ * coefficient tables, uploaded together on the copy stream.  host_imgs: n <= B pointers to the images
+ * in any host memory (image i: heights[i] x widths[i] x 3 bytes); they are packed back to back into
+ * staging.  Collect as above.  A batch of more than max_batch_bytes, or the call on a pipeline of
+ * another input format (and the float / byte calls on this one), is RN_ERR_INVALID. */
+RN_API int rn_pipeline_create_images_u8(rn_model *m, rn_pipeline **out, uint64_t B, int mode,
+                                        uint64_t max_batch_bytes);
+RN_API int rn_pipeline_submit_images_u8_n(rn_pipeline *p, const uint8_t *const *host_imgs,
+                                          const uint64_t *heights, const uint64_t *widths, uint64_t n);
 
 /* ---- one batch over several devices of a node ---------------------------------------
  * The multi-device form of the reference's main() (main.cu:228-254).  The forward has no

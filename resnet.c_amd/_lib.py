@@ -98,6 +98,13 @@ SIGNATURES = {
     "rn_nchw_to_nhwc_pad_dt": (c_int, [c_void_p, c_int, fptr, fptr] + [u64] * 6),
     "rn_image_u8_to_nhwc_pad_dt": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [u64] * 5
                                    + [POINTER(c_float), POINTER(c_float)]),
+    "rn_resize_crop_geometry": (c_int, [u64] * 4 + [POINTER(u64)] * 4),
+    "rn_resize_coefficients": (c_int, [u64] * 4 + [c_void_p, c_void_p, u64, POINTER(u64)]),
+    "rn_image_u8_resize_crop": (c_int, [c_void_p, c_void_p, POINTER(u64), POINTER(u64), POINTER(u64), u64,
+                                        c_void_p, u64, u64]),
+    "rn_image_u8_resize_crop_table": (c_int, [POINTER(u64), POINTER(u64), POINTER(u64), u64, u64, u64, c_void_p,
+                                              u64, POINTER(u64)]),
+    "rn_image_u8_resize_crop_launch": (c_int, [c_void_p, c_void_p, c_void_p, u64, c_void_p, u64]),
     "rn_conv2d_nhwc_forward_dt": (c_int, [c_void_p, c_int, c_int, fptr, fptr, fptr] + [u64] * 10
                                   + [POINTER(Epilogue)]),
     "rn_conv2d_grouped_forward": (c_int, [c_void_p, fptr, fptr, fptr] + [u64] * 11),
@@ -141,6 +148,8 @@ SIGNATURES = {
     "rn_model_tensor_key": (c_char_p, [c_void_p, u64, POINTER(u64)]),
     "rn_model_forward": (c_int, [c_void_p, fptr, u64, fptr, c_int]),
     "rn_model_forward_u8": (c_int, [c_void_p, c_void_p, u64, fptr, c_int]),
+    "rn_model_forward_images_u8": (c_int, [c_void_p, c_void_p, POINTER(u64), POINTER(u64), POINTER(u64), u64, fptr,
+                                           c_int]),
     "rn_model_tune": (c_int, [c_void_p, fptr, u64, fptr, c_int]),
     "rn_model_export_tuning": (c_int, [c_void_p, POINTER(u64), u64, POINTER(u64)]),
     "rn_model_import_tuning": (c_int, [c_void_p, POINTER(u64), u64]),
@@ -164,6 +173,8 @@ SIGNATURES = {
     "rn_pipeline_create_u8": (c_int, [c_void_p, POINTER(c_void_p), u64, c_int]),
     "rn_pipeline_input_buffer_u8": (c_int, [c_void_p, POINTER(c_void_p)]),
     "rn_pipeline_submit_u8_n": (c_int, [c_void_p, c_void_p, u64]),
+    "rn_pipeline_create_images_u8": (c_int, [c_void_p, POINTER(c_void_p), u64, c_int, u64]),
+    "rn_pipeline_submit_images_u8_n": (c_int, [c_void_p, POINTER(c_void_p), POINTER(u64), POINTER(u64), u64]),
     "rn_shard_bounds": (None, [u64, c_int, c_int, POINTER(u64), POINTER(u64)]),
     "rn_shard_create": (c_int, [POINTER(c_void_p), POINTER(c_int), c_int, c_int]),
     "rn_shard_create_ex": (c_int, [POINTER(c_void_p), POINTER(c_int), c_int, c_int, c_int, c_int]),

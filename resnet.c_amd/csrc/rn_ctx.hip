@@ -38,7 +38,7 @@ int rn_after_launch(rn_ctx *ctx, const char *what)
 
 int rn_scratch(rn_ctx *ctx, int slot, uint64_t bytes, void **ptr)
 {
-    if (slot < 0 || slot >= 5) return rn_set_error(ctx, RN_ERR_INVALID, "bad scratch slot");
+    if (slot < 0 || slot >= 6) return rn_set_error(ctx, RN_ERR_INVALID, "bad scratch slot");
     if (ctx->scratch_bytes[slot] < bytes) {
         if (ctx->graphs_live > 0)
             return rn_set_error(ctx, RN_ERR_INVALID,
@@ -235,7 +235,7 @@ int rn_ctx_destroy(rn_ctx *ctx)
     (void)rn_defer_flush(ctx);  // recorded ops run (their outputs may be read through other contexts later)
     (void)hipStreamSynchronize(ctx->stream);
     rn_defer_destroy(ctx);
-    for (int i = 0; i < 5; ++i) {
+    for (int i = 0; i < 6; ++i) {
         if (ctx->scratch[i]) (void)hipFree(ctx->scratch[i]);
     }
     for (int i = 0; i < ctx->wcache_n; ++i) (void)hipFree(ctx->wcache[i].packed);
@@ -282,6 +282,28 @@ int rn_conv_tile_candidates(void) { return 8 + rn_conv_wide_count() + 1; }  // +
 
 // library-internal (rn_model.c is plain C and sees the context only through functions)
 int rn_ctx_graphs_live(const rn_ctx *ctx) { return ctx ? ctx->graphs_live : 0; }
+int rn_ctx_scratch_slot(rn_ctx *ctx, int slot, uint64_t bytes, void **ptr)
+{
+    if (!ctx || !ptr) return RN_ERR_INVALID;
+    RN_TRY(rn_bind_device(ctx));
+    return rn_scratch(ctx, slot, bytes, ptr);
+}
+int rn_ctx_is_capturing(rn_ctx *ctx)
+{
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (!ctx || rn_bind_device(ctx) != RN_OK) return 0;
+    if (hipStreamIsCapturing(ctx->stream, &cap) != hipSuccess) return 0;
+    return cap != hipStreamCaptureStatusNone;
+}
+// pageable host memory -> device on the context's stream, over when the call returns (the caller frees `host`)
+int rn_ctx_upload_sync(rn_ctx *ctx, void *dev, const void *host, uint64_t bytes)
+{
+    if (!ctx || !dev || !host) return RN_ERR_INVALID;
+    RN_TRY(rn_bind_device(ctx));
+    RN_HIP_TRY(ctx, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    RN_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return RN_OK;
+}
 
 int rn_ctx_set_split_k(rn_ctx *ctx, int max_splits)
 {

@@ -4,11 +4,14 @@
  * print "max index is N" per image.  The reference hard-codes everything (ResNet-152,
  * B = 1, paths); here the same defaults can be overridden from the command line.
  *
- *   rn_infer [--arch 18|34|50|101|152|resnext50_32x4d|resnext101_32x8d|resnext101_64x4d|wide_resnet50_2|wide_resnet101_2] [--weights DIR] [--input FILE | --u8 FILE] [--batch B]
+ *   rn_infer [--arch 18|34|50|101|152|resnext50_32x4d|resnext101_32x8d|resnext101_64x4d|wide_resnet50_2|wide_resnet101_2] [--weights DIR] [--input FILE | --u8 FILE | --rgb FILE --hw H,W] [--batch B]
  *            [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,c,...]
  *
  * --u8 FILE reads B x 150528 raw bytes, the decoder's 8-bit RGB crops ([B,224,224,3]), instead of
  * the preprocessed fp32 file: the device normalises them (rn_model_forward_u8), same lines out.
+ * --rgb FILE --hw H,W reads the H x W x 3 raw bytes of ONE decoded image of any size: the device resizes
+ * (short side 256, PIL's antialiased bilinear bits) and centre-crops it (rn_model_forward_images_u8) and
+ * the line printed is the one --u8 prints on the crop PIL makes.  Single device only.
  * --dtype bf16 stores activations and weights as bf16 (fused mode only).
  *
  * --devices shards the batch contiguously over the listed devices (rn_shard_*: one host
@@ -124,7 +127,8 @@ int main(int argc, char **argv)
 {
     int arch = 152, device = 0, mode = RN_FWD_FUSED, dtype = RN_DTYPE_F32, u8 = 0, i;
     int devices[64], ndev = 0;
-    uint64_t B = 1, numel = 0, b;
+    uint64_t B = 1, numel = 0, b, rgb_h = 0, rgb_w = 0;
+    int rgb = 0;
     const char *weights = "weights_bin";
     const char *input = "test_bins/ILSVRC2012_val_00004749.bin";
     rn_ctx *ctx = NULL;
@@ -140,6 +144,13 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--weights") && v) { weights = v; ++i; }
         else if (!strcmp(a, "--input") && v) { input = v; u8 = 0; ++i; }
         else if (!strcmp(a, "--u8") && v) { input = v; u8 = 1; ++i; }
+        else if (!strcmp(a, "--rgb") && v) { input = v; rgb = 1; ++i; }
+        else if (!strcmp(a, "--hw") && v) {
+            char *q = NULL;
+            rgb_h = strtoull(v, &q, 10);
+            rgb_w = (q && *q == ',') ? strtoull(q + 1, NULL, 10) : 0;
+            ++i;
+        }
         else if (!strcmp(a, "--dtype") && v && (!strcmp(v, "f32") || !strcmp(v, "bf16"))) {
             dtype = strcmp(v, "bf16") ? RN_DTYPE_F32 : RN_DTYPE_BF16;
             ++i;
@@ -156,13 +167,18 @@ int main(int argc, char **argv)
         }
         else if (!strcmp(a, "--mode") && v) { mode = strcmp(v, "ops") ? RN_FWD_FUSED : RN_FWD_REFERENCE_OPS; ++i; }
         else {
-            fprintf(stderr, "usage: %s [--arch 18|34|50|101|152|resnext50_32x4d|resnext101_32x8d|resnext101_64x4d|wide_resnet50_2|wide_resnet101_2] [--weights DIR] [--input FILE | --u8 FILE] "
+            fprintf(stderr, "usage: %s [--arch 18|34|50|101|152|resnext50_32x4d|resnext101_32x8d|resnext101_64x4d|wide_resnet50_2|wide_resnet101_2] [--weights DIR] [--input FILE | --u8 FILE | --rgb FILE --hw H,W] "
                             "[--batch B] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,...]\n",
                     argv[0]);
             return 2;
         }
     }
     printf("Started\n");
+    if (rgb && (ndev > 0 || B != 1 || rgb_h == 0 || rgb_w == 0 || rgb_h > 16384 || rgb_w > 16384)) {
+        fprintf(stderr, "rn_infer: %s: --rgb takes one decoded image on one device and needs --hw H,W (sides 1..16384)\n",
+                rn_status_string(RN_ERR_UNSUPPORTED));
+        return 1;
+    }
     if (ndev > 0) return run_sharded(devices, ndev, arch, weights, input, u8, B, mode, dtype);
     CHECK(ctx, rn_ctx_create(&ctx, device, NULL));
     CHECK(ctx, groups_g ? rn_model_create_ex(ctx, &model, arch, groups_g, wpg_g) : rn_model_create(ctx, &model, arch));
@@ -171,7 +187,21 @@ int main(int argc, char **argv)
     CHECK(ctx, rn_model_finalize(model));
     printf("created model\n");
 
-    if (u8) {
+    if (rgb) {
+        const uint64_t want = rgb_h * rgb_w * 3;
+        void *host = malloc(want);
+        FILE *f = fopen(input, "rb");
+        if (!host || !f || fread(host, 1, want, f) != want || fgetc(f) != EOF) {
+            fprintf(stderr, "rn_infer: %s: %s: --rgb with --hw %llu,%llu takes exactly %llu bytes of 8-bit RGB\n",
+                    rn_status_string(RN_ERR_UNSUPPORTED), input, (unsigned long long)rgb_h, (unsigned long long)rgb_w,
+                    (unsigned long long)want);
+            return 1;
+        }
+        fclose(f);
+        CHECK(ctx, rn_malloc(ctx, (void **)&inp_u8, want));
+        CHECK(ctx, rn_memcpy_h2d(ctx, inp_u8, host, want));
+        free(host);
+    } else if (u8) {
         void *host = read_exact(input, B * 224 * 224 * 3, B, 1);
         if (!host) return 1;
         CHECK(ctx, rn_malloc(ctx, (void **)&inp_u8, B * 224 * 224 * 3));
@@ -180,7 +210,7 @@ int main(int argc, char **argv)
     } else {
         CHECK(ctx, rn_load_f32_file(ctx, input, &inp, &numel));
     }
-    if (!u8 && numel != B * 3 * 224 * 224) {
+    if (!u8 && !rgb && numel != B * 3 * 224 * 224) {
         fprintf(stderr, "rn_infer: %s: the model driver takes 3 x 224 x 224 fp32 images only; %s holds "
                         "%llu floats, expected %llu for batch %llu\n", rn_status_string(RN_ERR_UNSUPPORTED), input,
                 (unsigned long long)numel, (unsigned long long)(B * 3 * 224 * 224),
@@ -189,7 +219,10 @@ int main(int argc, char **argv)
     }
     CHECK(ctx, rn_malloc(ctx, (void **)&logits, B * 1000 * sizeof(float)));
     CHECK(ctx, rn_malloc(ctx, (void **)&idx_dev, B * sizeof(uint64_t)));
-    if (u8)
+    if (rgb) {
+        const uint64_t zero = 0;
+        CHECK(ctx, rn_model_forward_images_u8(model, inp_u8, &zero, &rgb_h, &rgb_w, 1, logits, mode));
+    } else if (u8)
         CHECK(ctx, rn_model_forward_u8(model, inp_u8, B, logits, mode));
     else
         CHECK(ctx, rn_model_forward(model, inp, B, logits, mode));

@@ -114,6 +114,9 @@ struct rn_model {
     int t1_ready;            /* the previous block's chained launch has produced this block's conv1 output */
     int stem_pool;           /* fused mode: stem + batch-norm + ReLU + max-pool as one launch (default on) */
     int in_u8;               /* the forward being queued reads 8-bit RGB [B,224,224,3] (rn_model_forward_u8) */
+    uint8_t *crops;          /* [crops_cap,224,224,3]: what rn_model_forward_images_u8 resizes decoded images into */
+    uint64_t crops_cap;
+    int prof_keep;           /* the next sub-batch keeps the profile records queued before it (the resize launch) */
     void *stem_pool_packed;  /* its weight panel, model dtype */
     void *fc_packed;  /* fc.weight in the model dtype (bf16 models only) */
     /* activation arenas, sized for batch_cap images */
@@ -372,6 +375,7 @@ int rn_model_destroy(rn_model *m)
     rn_free(m->ctx, m->fc_packed);
     rn_free(m->ctx, m->stem_packed_exact);
     rn_free(m->ctx, m->stem_pool_packed);
+    if (m->crops) rn_free(m->ctx, m->crops);
     free_acts(m);
     free_prof(m);
     {
@@ -1297,7 +1301,8 @@ static int forward_chunk(rn_model *m, const void *input, uint64_t B, float *logi
     uint64_t lo = 0;
     int parts = parts_of(m, B), i;
     TRY(ensure_acts(m, B));
-    m->n_prof = 0;
+    if (!m->prof_keep) m->n_prof = 0;
+    m->prof_keep = 0;
     if (parts < 2 || m->profiling || m->single_stream_only || m->recording)
         return forward_part(m, m->ctx, 0, input, B, logits, mode);
     if (!m->ev_fork) TRY(rn_event_create(m->ctx, &m->ev_fork));
@@ -1358,6 +1363,66 @@ int rn_model_forward_u8(rn_model *m, const uint8_t *input_nhwc, uint64_t B, floa
     st = forward_any(m, input_nhwc, B, logits, mode);
     m->in_u8 = 0;
     return st;
+}
+
+/* rn_resize.hip */
+int rn_image_u8_resize_crop_launch(rn_ctx *ctx, const uint8_t *packed_dev, const void *table_dev, uint64_t B,
+                                   uint8_t *dst_dev, uint64_t crop);
+int rn_ctx_scratch_slot(rn_ctx *ctx, int slot, uint64_t bytes, void **ptr); /* rn_ctx.hip */
+int rn_ctx_is_capturing(rn_ctx *ctx);                                      /* rn_ctx.hip */
+int rn_ctx_upload_sync(rn_ctx *ctx, void *dev, const void *host, uint64_t bytes); /* rn_ctx.hip */
+
+/* Decoded images whose tables are on the device already (the host pipeline stages them with the batch):
+ * one resize launch for the whole batch on the model's stream, then the byte route on the crops.
+ * src_bytes: what the launch reads, for the profile record. */
+int rn_model_forward_images_table(rn_model *m, const uint8_t *packed_dev, const void *table_dev, uint64_t B,
+                                  double src_bytes, float *logits, int mode)
+{
+    if (!m || !packed_dev || !table_dev || !logits || B == 0) return RN_ERR_INVALID;
+    if (mode != RN_FWD_REFERENCE_OPS && mode != RN_FWD_FUSED) return RN_ERR_INVALID;
+    if (!m->finalized) return RN_ERR_INVALID;
+    if (m->dtype != RN_DTYPE_F32 && mode != RN_FWD_FUSED) return RN_ERR_UNSUPPORTED;
+    if (B > m->crops_cap) {
+        if (m->crops_cap > 0 && rn_ctx_graphs_live(m->ctx) > 0) return RN_ERR_INVALID;
+        if (m->crops) TRY(rn_free(m->ctx, m->crops));
+        m->crops = NULL;
+        m->crops_cap = 0;
+        TRY(rn_malloc(m->ctx, (void **)&m->crops, B * 3 * 224 * 224));
+        m->crops_cap = B;
+    }
+    m->run = m->ctx;
+    m->n_prof = 0;
+    TRY(prof_begin(m, "image_u8_resize_crop", "input", 0.0, src_bytes + (double)B * 3.0 * 224 * 224));
+    TRY(rn_image_u8_resize_crop_launch(m->ctx, packed_dev, table_dev, B, m->crops, 224));
+    TRY(prof_end(m));
+    m->prof_keep = 1;
+    {
+        const int st = rn_model_forward_u8(m, m->crops, B, logits, mode);
+        m->prof_keep = 0;
+        return st;
+    }
+}
+
+int rn_model_forward_images_u8(rn_model *m, const uint8_t *packed_dev, const uint64_t *offsets,
+                               const uint64_t *heights, const uint64_t *widths, uint64_t B, float *logits, int mode)
+{
+    uint64_t bytes = 0, i;
+    double src_bytes = 0.0;
+    void *host, *dev = NULL;
+    int st;
+    if (!m || !packed_dev || !offsets || !heights || !widths || !logits || B == 0) return RN_ERR_INVALID;
+    if (rn_image_u8_resize_crop_table(offsets, heights, widths, B, 256, 224, NULL, 0, &bytes) != RN_OK)
+        return RN_ERR_INVALID;
+    if (rn_ctx_is_capturing(m->ctx)) return RN_ERR_UNSUPPORTED; /* the tables come from host memory freed below */
+    host = malloc(bytes);
+    if (!host) return RN_ERR_NOMEM;
+    st = rn_image_u8_resize_crop_table(offsets, heights, widths, B, 256, 224, host, bytes, &bytes);
+    if (st == RN_OK) st = rn_ctx_scratch_slot(m->ctx, 5, bytes, &dev);
+    if (st == RN_OK) st = rn_ctx_upload_sync(m->ctx, dev, host, bytes);
+    free(host);
+    if (st != RN_OK) return st;
+    for (i = 0; i < B; ++i) src_bytes += 3.0 * (double)heights[i] * (double)widths[i] * (224.0 / 256.0) * (224.0 / 256.0);
+    return rn_model_forward_images_table(m, packed_dev, dev, B, src_bytes, logits, mode);
 }
 
 #define RN_TUNE_ROUNDS 6

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "rn_internal.h"
+#include "rn_resize.h"
 
 struct rn_graph {
     rn_ctx *ctx;
@@ -36,8 +37,11 @@ struct rn_pipeline {
     rn_ctx *ctx;
     uint64_t B;
     int mode;
-    int u8;            // input format: 0 = fp32 NCHW, 1 = 8-bit RGB [B,224,224,3] (rn_pipeline_create_u8)
-    size_t img_bytes;  // of one image in that format
+    int u8;            // input format: 0 = fp32 NCHW, 1 = 8-bit RGB [B,224,224,3] (rn_pipeline_create_u8),
+                       // 2 = decoded 8-bit RGB images of any size (rn_pipeline_create_images_u8)
+    size_t img_bytes;  // of one image in that format (formats 0 and 1)
+    size_t max_bytes;  // format 2: pixels of one batch; the tables sit at table_off = max_bytes rounded up to 16
+    size_t table_off, table_room;
     hipStream_t copy_stream;
     int copy_threads;  // helper threads of the pageable -> pinned copy (RN_COPY_THREADS, default 3)
     rn_pipeline_slot slot[2];
@@ -53,6 +57,8 @@ int rn_model_profiling_enabled(const rn_model *m);
 // the contexts the model has queued batch parts on so far (rn_model.c)
 int rn_model_contexts(rn_model *m, rn_ctx **out, int cap);
 void rn_model_graph_ref(rn_model *m, int delta);
+int rn_model_forward_images_table(rn_model *m, const uint8_t *packed_dev, const void *table_dev, uint64_t B,
+                                  double src_bytes, float *logits, int mode);
 
 int rn_graph_destroy(rn_graph *g)
 {
@@ -151,9 +157,9 @@ int rn_pipeline_destroy(rn_pipeline *p)
     return RN_OK;
 }
 
-static int pipeline_create(rn_model *m, rn_pipeline **out, uint64_t B, int mode, int u8)
+static int pipeline_create(rn_model *m, rn_pipeline **out, uint64_t B, int mode, int u8, uint64_t max_batch_bytes = 0)
 {
-    if (!m || !out || B == 0) return RN_ERR_INVALID;
+    if (!m || !out || B == 0 || (u8 == 2 && max_batch_bytes == 0)) return RN_ERR_INVALID;
     *out = nullptr;
     rn_ctx *ctx = rn_model_context(m);
     rn_pipeline *p = (rn_pipeline *)calloc(1, sizeof(rn_pipeline));
@@ -169,7 +175,13 @@ static int pipeline_create(rn_model *m, rn_pipeline **out, uint64_t B, int mode,
         const int n = ct ? atoi(ct) : 3;
         p->copy_threads = n < 1 ? 1 : n > 16 ? 16 : n;
     }
-    const size_t in_bytes = (size_t)B * p->img_bytes;
+    // format 2: behind the pixels the tables.  One image's table is 12 descriptor words plus, per axis, 224 x
+    // (2 + ksize) words with ksize <= 2 * scale + 3; its pixels are at least 3 * (256 * scale)^2 bytes, so
+    // everything a table holds beyond the scale-1 size (12,544 bytes) is less than 1/16 of the batch's pixels
+    p->max_bytes = (size_t)max_batch_bytes;
+    p->table_off = ((size_t)max_batch_bytes + 15) & ~(size_t)15;
+    p->table_room = (size_t)B * (RN_RS_DESC * 4 + 12544) + (size_t)max_batch_bytes / 16 + 64;
+    const size_t in_bytes = u8 == 2 ? p->table_off + p->table_room : (size_t)B * p->img_bytes;
     const size_t out_bytes = (size_t)B * 1000 * sizeof(float);
     const size_t idx_bytes = (size_t)B * sizeof(uint64_t);
     hipError_t e = hipSetDevice(ctx->device);
@@ -204,6 +216,11 @@ int rn_pipeline_create_u8(rn_model *m, rn_pipeline **out, uint64_t B, int mode)
     return pipeline_create(m, out, B, mode, 1);
 }
 
+int rn_pipeline_create_images_u8(rn_model *m, rn_pipeline **out, uint64_t B, int mode, uint64_t max_batch_bytes)
+{
+    return pipeline_create(m, out, B, mode, 2, max_batch_bytes);
+}
+
 uint64_t rn_pipeline_in_flight(const rn_pipeline *p) { return p ? p->head - p->tail : 0; }
 uint64_t rn_pipeline_batch(const rn_pipeline *p) { return p ? p->B : 0; }
 
@@ -211,7 +228,9 @@ uint64_t rn_pipeline_batch(const rn_pipeline *p) { return p ? p->B : 0; }
 static int wrong_format(rn_pipeline *p, const char *who)
 {
     return rn_set_error(p->ctx, RN_ERR_INVALID, "%s: the pipeline was created for %s input", who,
-                        p->u8 ? "8-bit RGB (rn_pipeline_create_u8)" : "fp32 NCHW (rn_pipeline_create)");
+                        p->u8 == 2   ? "decoded images (rn_pipeline_create_images_u8)"
+                        : p->u8 == 1 ? "8-bit RGB (rn_pipeline_create_u8)"
+                                     : "fp32 NCHW (rn_pipeline_create)");
 }
 
 static int input_buffer(rn_pipeline *p, void **host_staging, int u8, const char *who)
@@ -340,6 +359,79 @@ int rn_pipeline_submit_n(rn_pipeline *p, const float *host_input_nchw, uint64_t 
 int rn_pipeline_submit_u8_n(rn_pipeline *p, const uint8_t *host_input_nhwc, uint64_t n)
 {
     return submit_n(p, host_input_nhwc, n, 1, "rn_pipeline_submit_u8_n");
+}
+
+int rn_pipeline_submit_images_u8_n(rn_pipeline *p, const uint8_t *const *host_imgs, const uint64_t *heights,
+                                   const uint64_t *widths, uint64_t n)
+{
+    if (!p) return RN_ERR_INVALID;
+    rn_ctx *ctx = p->ctx;
+    RN_TRY(rn_bind_device(ctx));
+    if (p->u8 != 2) return wrong_format(p, "rn_pipeline_submit_images_u8_n");
+    if (!host_imgs || !heights || !widths) return rn_set_error(ctx, RN_ERR_INVALID, "rn_pipeline_submit_images_u8_n: null pointer");
+    if (n == 0 || n > p->B)
+        return rn_set_error(ctx, RN_ERR_INVALID, "rn_pipeline_submit_images_u8_n: %llu images, the pipeline holds 1..%llu",
+                            (unsigned long long)n, (unsigned long long)p->B);
+    if (p->head - p->tail >= 2)
+        return rn_set_error(ctx, RN_ERR_INVALID, "rn_pipeline_submit_images_u8_n: both slots busy, collect first");
+    std::vector<uint64_t> offs(n);
+    uint64_t total = 0, tbytes = 0;
+    double src_bytes = 0.0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (!host_imgs[i] || heights[i] > RN_RS_MAX_SIDE || widths[i] > RN_RS_MAX_SIDE)
+            return rn_set_error(ctx, RN_ERR_INVALID, "rn_pipeline_submit_images_u8_n: image %llu: null or too large", (unsigned long long)i);
+        offs[i] = total;
+        total += heights[i] * widths[i] * 3;
+        src_bytes += 3.0 * (double)heights[i] * (double)widths[i] * (224.0 / 256.0) * (224.0 / 256.0);
+    }
+    if (total > p->max_bytes)
+        return rn_set_error(ctx, RN_ERR_INVALID, "rn_pipeline_submit_images_u8_n: the batch holds %llu bytes, the pipeline was "
+                            "created for %llu (max_batch_bytes)", (unsigned long long)total, (unsigned long long)p->max_bytes);
+    rn_pipeline_slot *s = &p->slot[p->head & 1];
+    char *tab = (char *)s->h_in + p->table_off;
+    if (rn_image_u8_resize_crop_table(offs.data(), heights, widths, n, 256, 224, tab, p->table_room, &tbytes) != RN_OK)
+        return rn_set_error(ctx, RN_ERR_INVALID, "rn_pipeline_submit_images_u8_n: an image the resize refuses (sides 1..16384, "
+                            "at most 64 times their resized length)");
+    const int st = [&]() -> int {
+        // pageable -> pinned: the images are dealt to the helper threads, this thread takes its share
+        const int copiers = n >= 4 ? p->copy_threads : 1;
+        auto copy_share = [&](int t) {
+            for (uint64_t i = (uint64_t)t; i < n; i += (uint64_t)copiers)
+                memcpy((char *)s->h_in + offs[i], host_imgs[i], (size_t)(heights[i] * widths[i] * 3));
+        };
+        std::vector<std::thread> pool;
+        int started = 1;
+        try {
+            for (int t = 1; t < copiers; ++t) {
+                pool.emplace_back(copy_share, t);
+                ++started;
+            }
+        } catch (...) {
+        }
+        copy_share(0);
+        for (auto &th : pool) th.join();
+        for (int t = started; t < copiers; ++t) copy_share(t);
+        RN_HIP_TRY(ctx, hipMemcpyAsync(s->d_in, s->h_in, (size_t)total, hipMemcpyHostToDevice, p->copy_stream));
+        RN_HIP_TRY(ctx, hipMemcpyAsync((char *)s->d_in + p->table_off, tab, (size_t)tbytes, hipMemcpyHostToDevice, p->copy_stream));
+        RN_HIP_TRY(ctx, hipEventRecord(s->uploaded, p->copy_stream));
+        RN_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s->uploaded, 0));
+        RN_TRY(rn_model_forward_images_table(p->model, (const uint8_t *)s->d_in, (char *)s->d_in + p->table_off, n, src_bytes,
+                                             s->d_out, p->mode));
+        RN_TRY(rn_argmax_forward(ctx, s->d_out, s->d_idx, n, 1000));
+        RN_HIP_TRY(ctx, hipMemcpyAsync(s->h_out, s->d_out, (size_t)n * 1000 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        RN_HIP_TRY(ctx, hipMemcpyAsync(s->h_idx, s->d_idx, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        RN_HIP_TRY(ctx, hipEventRecord(s->done, ctx->stream));
+        return RN_OK;
+    }();
+    if (st != RN_OK) {
+        (void)hipStreamSynchronize(p->copy_stream);
+        (void)hipStreamSynchronize(ctx->stream);
+        return st;
+    }
+    s->busy = 1;
+    s->n = n;
+    ++p->head;
+    return RN_OK;
 }
 
 int rn_pipeline_submit(rn_pipeline *p, const float *host_input_nchw)

@@ -282,6 +282,21 @@ class NativeModel:
         self.ctx.sync()
         return out.numpy()
 
+    def forward_images(self, images, fused: bool = True) -> np.ndarray:
+        """A list of decoded [H,W,3] uint8 RGB arrays of any sizes -> logits host array: the device
+        resizes (short side 256) and centre-crops (224) them to PIL's bytes, then runs forward_u8's
+        launches (rn_model_forward_images_u8).  Synchronous convenience."""
+        from .ops import _u64p, _up_raw, pack_images
+        packed, offsets, heights, widths = pack_images(images)
+        B = len(heights)
+        xin = _up_raw(packed)
+        out = FloatTensor((B, 1000), Device.GPU)
+        L.check(L.lib().rn_model_forward_images_u8(self.handle, xin.ptr, _u64p(offsets), _u64p(heights), _u64p(widths),
+                                                   B, out.data(), L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS),
+                "rn_model_forward_images_u8", self.ctx.handle)
+        self.ctx.sync()
+        return out.numpy()
+
     def tune(self, input_ptr: int, B: int, logits_ptr: int, fused: bool = True) -> None:
         """Pick the fastest contraction tile per layer for batch B (results unchanged)."""
         L.check(L.lib().rn_model_tune(self.handle, input_ptr, B, logits_ptr,
@@ -575,16 +590,25 @@ class Pipeline:
     """Stream of host batches through a NativeModel with the upload of the next batch
     overlapped with the forward of the current one (rn_pipeline_*, two slots)."""
 
-    def __init__(self, model: NativeModel, batch: int, fused: bool = True, input: str = "f32"):
-        """input: "f32" (NCHW floats, submit) or "u8" (RGB bytes [n,224,224,3], submit_u8: a
-        quarter of the upload, normalised on the device)."""
-        if input not in ("f32", "u8"):
-            raise ValueError(f"input must be 'f32' or 'u8', not {input!r}")
+    def __init__(self, model: NativeModel, batch: int, fused: bool = True, input: str = "f32",
+                 max_batch_bytes: Optional[int] = None):
+        """input: "f32" (NCHW floats, submit), "u8" (RGB bytes [n,224,224,3], submit_u8: a
+        quarter of the upload, normalised on the device) or "images" (decoded RGB images of any
+        size, submit_images: resized and cropped on the device; ``max_batch_bytes`` is the room for
+        one batch's pixels, default 1 MB per image)."""
+        if input not in ("f32", "u8", "images"):
+            raise ValueError(f"input must be 'f32', 'u8' or 'images', not {input!r}")
         self.model, self.batch, self.input = model, batch, input
         h = ctypes.c_void_p()
-        create = L.lib().rn_pipeline_create_u8 if input == "u8" else L.lib().rn_pipeline_create
-        L.check(create(model.handle, ctypes.byref(h), batch, L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS),
-                "rn_pipeline_create_u8" if input == "u8" else "rn_pipeline_create", model.ctx.handle)
+        mode = L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS
+        if input == "images":
+            self.max_batch_bytes = int(max_batch_bytes) if max_batch_bytes is not None else batch << 20
+            L.check(L.lib().rn_pipeline_create_images_u8(model.handle, ctypes.byref(h), batch, mode, self.max_batch_bytes),
+                    "rn_pipeline_create_images_u8", model.ctx.handle)
+        else:
+            create = L.lib().rn_pipeline_create_u8 if input == "u8" else L.lib().rn_pipeline_create
+            L.check(create(model.handle, ctypes.byref(h), batch, mode),
+                    "rn_pipeline_create_u8" if input == "u8" else "rn_pipeline_create", model.ctx.handle)
         self.handle = h
 
     def input_buffer(self) -> np.ndarray:
@@ -624,6 +648,21 @@ class Pipeline:
         L.check(L.lib().rn_pipeline_submit_u8_n(self.handle, ptr, n), "rn_pipeline_submit_u8_n",
                 self.model.ctx.handle)
 
+    def submit_images(self, images) -> None:
+        """images: a list of n <= batch decoded [H,W,3] uint8 arrays of any sizes (pageable memory: the
+        library packs them into its pinned staging).  Only on a pipeline created with input="images"."""
+        imgs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
+        for a in imgs:
+            assert a.ndim == 3 and a.shape[2] == 3, a.shape
+        n = len(imgs)
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data for a in imgs])
+        heights = np.array([a.shape[0] for a in imgs], dtype=np.uint64)
+        widths = np.array([a.shape[1] for a in imgs], dtype=np.uint64)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        L.check(L.lib().rn_pipeline_submit_images_u8_n(self.handle, ptrs, heights.ctypes.data_as(u64p),
+                                                       widths.ctypes.data_as(u64p), n),
+                "rn_pipeline_submit_images_u8_n", self.model.ctx.handle)
+
     def collect(self) -> np.ndarray:
         return self.collect_top1()[0]
 
@@ -644,7 +683,7 @@ class Pipeline:
         for x in batches:
             if self.in_flight() == 2:
                 yield self.collect()
-            (self.submit_u8 if self.input == "u8" else self.submit)(x)
+            {"u8": self.submit_u8, "images": self.submit_images}.get(self.input, self.submit)(x)
         while self.in_flight():
             yield self.collect()
 

@@ -443,6 +443,40 @@ def image_u8_to_nhwc_pad(px, cpad: int = 4, border: int = 0, bf16: bool = False,
     return _down_raw(dst, ht, n).reshape(B, H + 2 * border, W + 2 * border, cpad)
 
 
+def pack_images(images):
+    """A list of [H,W,3] uint8 arrays -> (packed bytes back to back, offsets, heights, widths as uint64)."""
+    imgs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
+    for a in imgs:
+        assert a.ndim == 3 and a.shape[2] == 3, a.shape
+    sizes = np.array([a.size for a in imgs], dtype=np.uint64)
+    offsets = np.concatenate([np.zeros(1, np.uint64), np.cumsum(sizes)[:-1]]).astype(np.uint64) if imgs \
+        else np.zeros(0, np.uint64)
+    packed = np.concatenate([a.reshape(-1) for a in imgs]) if imgs else np.zeros(0, np.uint8)
+    heights = np.array([a.shape[0] for a in imgs], dtype=np.uint64)
+    widths = np.array([a.shape[1] for a in imgs], dtype=np.uint64)
+    return packed, offsets, heights, widths
+
+
+def _u64p(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+
+
+def image_u8_resize_crop(images, resize: int = 256, crop: int = 224) -> np.ndarray:
+    """rn_image_u8_resize_crop: a list of [H,W,3] uint8 RGB arrays of any sizes -> [B,crop,crop,3] uint8,
+    PIL's antialiased bilinear resize (short side ``resize``) and centre crop, on the device."""
+    from .tensor import _DeviceBuffer
+    ctx, lib = get_ctx(), L.lib()
+    packed, offsets, heights, widths = pack_images(images)
+    B = len(heights)
+    n = B * crop * crop * 3
+    src = _up_raw(packed)
+    dst = _DeviceBuffer(ctx, max(n, 16))
+    L.check(lib.rn_image_u8_resize_crop(ctx.handle, src.ptr, _u64p(offsets), _u64p(heights), _u64p(widths), B,
+                                        dst.ptr, resize, crop), "rn_image_u8_resize_crop", ctx.handle)
+    ctx.sync()
+    return _down_raw(dst, np.uint8, n).reshape(B, crop, crop, 3)
+
+
 def stem_pool(x, w, scale=None, shift=None, relu_: bool = True, bf16: bool = False,
               from_nchw: bool = False) -> np.ndarray:
     """conv 7x7/2 pad 3 + per-channel affine + ReLU + max-pool 3x3/2/1 through the fused launch
