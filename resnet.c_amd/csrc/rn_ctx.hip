@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "rn_conv_params.h"
+#include "rn_private.h"
 
 int rn_set_error(rn_ctx *ctx, int status, const char *fmt, ...)
 {
@@ -280,7 +281,7 @@ int rn_ctx_set_conv_tile(rn_ctx *ctx, int candidate)
 
 int rn_conv_tile_candidates(void) { return 8 + rn_conv_wide_count() + 1; }  // + the bf16 strip kernels
 
-// library-internal (rn_model.c is plain C and sees the context only through functions)
+// library-internal, declared in rn_private.h (rn_model.c is plain C and sees the context only through functions)
 int rn_ctx_graphs_live(const rn_ctx *ctx) { return ctx ? ctx->graphs_live : 0; }
 int rn_ctx_scratch_slot(rn_ctx *ctx, int slot, uint64_t bytes, void **ptr)
 {

@@ -4,7 +4,7 @@
  * Replaces the reference driver cuda/inference/main.cu:
  *   createLayer / createResnet152   main.cu:53-89,109-125  -> rn_model_create + set_tensor/load_dir
  *   layerForward                    main.cu:127-166        -> block_forward
- *   resnet152Forward                main.cu:168-226        -> rn_model_forward
+ *   resnet152Forward                main.cu:168-226        -> rn_model_forward (run_front, run_blocks, run_head)
  * generalised over the block counts (ResNet-50/101/152) and the batch size, plus the basic-block
  * networks ResNet-18/34 (torchvision's layout: two 3x3 convolutions per block, expansion 1; the
  * reference ships bottleneck networks only).
@@ -28,8 +28,14 @@
 #include <string.h>
 
 #include "rn_hip.h"
+#include "rn_private.h"
 
 #define RN_MAX_KEY 96
+/* the fixed geometry: 224 x 224 RGB images, a 64-channel stem, 1000 classes */
+#define RN_IMAGE_SIDE 224
+#define RN_IMAGE_NUMEL (3 * RN_IMAGE_SIDE * RN_IMAGE_SIDE)
+#define RN_RESIZE_SIDE 256 /* decoded images: the shorter side before the centre crop */
+#define RN_STEM_WIDTH 64
 #define RN_CLASSES 1000
 
 #define RN_MAX_STREAMS 4
@@ -76,16 +82,26 @@ typedef struct {
     float ms;
 } rn_prof;
 
+/* One contraction launch: what op_conv / op_pair build and launch_call runs, in a forward and again,
+ * from the call list, when the tiles are tuned. */
 typedef struct {
-    int conv;
-    int pair_block; /* >= 0: the fused conv3 + downsample call of that block (x2, H2, W2) */
+    int conv;       /* the convolution; of a pair, its tail */
+    int pair_block; /* >= 0: the fused tail + downsample call of that block (x2, H2, W2) */
     int exact;      /* the stem in its exact-K form (x = physically padded image) */
     const void *x, *x2;
     void *y;
-    uint64_t B, H, W, pad, H2, W2;
+    uint64_t B, H, W, pad, H2, W2; /* H, W: the input's; the output size follows from them and pad */
     rn_epilogue ep;
     int has_ep;
 } rn_conv_call;
+
+/* What the ops of the forward_sub call being queued run on: set by run_begin, nowhere else. */
+typedef struct {
+    rn_ctx *ctx;
+    int mode;
+    int t1_ready; /* the previous block's chained launch has produced this block's conv1 output */
+    float *x4, *p0, *p1, *dsb, *t1, *t2, *pooled; /* views into the arenas */
+} rn_run;
 
 struct rn_model {
     rn_ctx *ctx;
@@ -94,6 +110,7 @@ struct rn_model {
     int basic;        /* ResNet-18/34: basic blocks (two 3x3 convolutions, expansion 1) */
     int depths[4];
     uint64_t feat;    /* width of the final feature map: 2048 (bottleneck) or 512 (basic) */
+    uint64_t stem_side, pool_side; /* the stem's output (112) and the max-pool's (56), which the first stage keeps */
     /* per-image element counts of the arenas (ensure_acts) */
     uint64_t x4_img, p_img, ds_img, t1_img, t2_img;
     uint64_t s1_img; /* the first stage's output per image (56*56*256, or 56*56*64): slices of a depth-first front */
@@ -111,12 +128,9 @@ struct rn_model {
     float *stem_packed_exact;
     int graphs_live;         /* graphs captured from this model that still live (rn_model_capture / rn_graph_destroy) */
     int chain;               /* fused bf16 mode: conv3 of a 64- / 128-channel block + conv1 of the next block as one launch (default on) */
-    int t1_ready;            /* the previous block's chained launch has produced this block's conv1 output */
     int stem_pool;           /* fused mode: stem + batch-norm + ReLU + max-pool as one launch (default on) */
-    int in_u8;               /* the forward being queued reads 8-bit RGB [B,224,224,3] (rn_model_forward_u8) */
     uint8_t *crops;          /* [crops_cap,224,224,3]: what rn_model_forward_images_u8 resizes decoded images into */
     uint64_t crops_cap;
-    int prof_keep;           /* the next sub-batch keeps the profile records queued before it (the resize launch) */
     void *stem_pool_packed;  /* its weight panel, model dtype */
     void *fc_packed;  /* fc.weight in the model dtype (bf16 models only) */
     /* activation arenas, sized for batch_cap images */
@@ -137,14 +151,12 @@ struct rn_model {
      * writes is still in the 256 MB Infinity Cache when the next reads it; the rest of the
      * network then runs on the whole batch.  1 = off. */
     int front_parts;
-    /* what the ops of the sub-batch being queued run on: context, and views into the arenas */
-    rn_ctx *run;
-    struct { float *x4, *p0, *p1, *dsb, *t1, *t2, *pooled; } v;
+    rn_run run;
     /* tile tuning: calls of the last forward, and the batch size the tiles were tuned for */
     rn_conv_call *calls;
     int n_calls, cap_calls, recording;
     uint64_t tuned_B;
-    int tuned_mode, cur_mode;
+    int tuned_mode;
     /* profiling */
     int profiling;
     rn_prof *prof;
@@ -204,6 +216,27 @@ static uint64_t mid_width(const rn_model *m, int li)
     return kWidths[li][1] * (uint64_t)m->width_per_group / 64 * (uint64_t)m->groups;
 }
 
+/* The spatial sizes and, from them, the arenas per image: x4 the input image, p0 / p1 the block outputs
+ * (and the stem output), dsb the downsample branch, t1 / t2 the block-internal tensors (a basic block
+ * has one: conv1's output).  Max-pool 3x3 s2 p1 (main.cu:114,192); the first stage has stride 1. */
+static void set_geometry(rn_model *m)
+{
+    const rn_conv *stem = &m->convs[0];
+    const uint64_t padded = RN_IMAGE_SIDE + 2 * stem->pad; /* bf16 and exact-K stems keep a zero border */
+    uint64_t s1, s2, stem_img;
+    m->stem_side = rn_conv_output_size(RN_IMAGE_SIDE, stem->k, stem->stride, stem->pad);
+    m->pool_side = rn_conv_output_size(m->stem_side, 3, 2, 1);
+    s1 = m->pool_side * m->pool_side;
+    s2 = rn_conv_output_size(m->pool_side, 1, kStrides[1], 0); /* side of the second stage */
+    stem_img = m->stem_side * m->stem_side * stem->cout;
+    m->x4_img = padded * padded * 4;
+    m->s1_img = s1 * (m->basic ? kBasicWidths[0] : kWidths[0][2]);
+    m->p_img = stem_img > m->s1_img ? stem_img : m->s1_img;
+    m->ds_img = m->basic ? s2 * s2 * kBasicWidths[1] : m->s1_img; /* layer2.0's, or layer1.0's of a bottleneck */
+    m->t1_img = s1 * (m->basic ? kBasicWidths[0] : mid_width(m, 1)); /* layer2.0 conv1 of a bottleneck */
+    m->t2_img = m->basic ? 0 : m->t1_img;
+}
+
 static int model_create(rn_ctx *ctx, rn_model **out, int arch, int groups, int width_per_group)
 {
     static const int d50[4] = {3, 4, 6, 3}, d101[4] = {3, 4, 23, 3}, d152[4] = {3, 8, 36, 3};
@@ -232,14 +265,6 @@ static int model_create(rn_ctx *ctx, rn_model **out, int arch, int groups, int w
     m->width_per_group = width_per_group;
     m->basic = arch == 18 || arch == 34;
     m->feat = m->basic ? kBasicWidths[3] : kWidths[3][2];
-    /* arenas: x4 the input image, p0 / p1 the block outputs (and the 112x112x64 stem output), dsb the
-     * downsample branch, t1 / t2 the block-internal tensors (a basic block has one: conv1's output) */
-    m->x4_img = (uint64_t)230 * 230 * 4; /* bf16 models keep a 3-pixel zero border */
-    m->p_img = (uint64_t)112 * 112 * 64; /* == 56*56*256 */
-    m->ds_img = m->basic ? (uint64_t)28 * 28 * 128 : m->p_img;
-    m->t1_img = m->basic ? (uint64_t)56 * 56 * 64 : (uint64_t)56 * 56 * mid_width(m, 1); /* layer2.0 conv1 of a bottleneck */
-    m->t2_img = m->basic ? 0 : m->t1_img;
-    m->s1_img = (uint64_t)56 * 56 * (m->basic ? kBasicWidths[0] : kWidths[0][2]);
     for (li = 0; li < 4; ++li) {
         m->depths[li] = d[li];
         total_blocks += d[li];
@@ -255,7 +280,8 @@ static int model_create(rn_ctx *ctx, rn_model **out, int arch, int groups, int w
         return RN_ERR_NOMEM;
     }
     /* stem: conv1 7x7 s2 p3 + bn1 (main.cu:111-112) */
-    add_conv(m, "conv1", "bn1", 3, 64, 7, 2, 3);
+    add_conv(m, "conv1", "bn1", 3, RN_STEM_WIDTH, 7, 2, 3);
+    set_geometry(m);
     for (li = 0; li < 4; ++li) {
         for (bi = 0; bi < d[li]; ++bi) {
             rn_block *b = &m->blocks[m->n_blocks++];
@@ -570,8 +596,6 @@ int rn_model_finalize(rn_model *m)
     return RN_OK;
 }
 
-int rn_ctx_graphs_live(const rn_ctx *ctx); /* rn_ctx.hip */
-
 static int ensure_acts(rn_model *m, uint64_t B)
 {
     int st;
@@ -696,8 +720,8 @@ static int prof_begin(rn_model *m, const char *op, const char *layer, double flo
         for (i = m->cap_prof; i < ncap; ++i) {
             int st;
             memset(&np[i], 0, sizeof(rn_prof));
-            st = rn_event_create(m->run, &np[i].start);
-            if (st == RN_OK) st = rn_event_create(m->run, &np[i].stop);
+            st = rn_event_create(m->run.ctx, &np[i].start);
+            if (st == RN_OK) st = rn_event_create(m->run.ctx, &np[i].stop);
             if (st != RN_OK) {
                 m->cap_prof = i;
                 return st;
@@ -711,13 +735,13 @@ static int prof_begin(rn_model *m, const char *op, const char *layer, double flo
     r->flops = flops;
     r->bytes = bytes;
     r->ms = -1.f;
-    return rn_event_record(m->run, r->start);
+    return rn_event_record(m->run.ctx, r->start);
 }
 
 static int prof_end(rn_model *m)
 {
     if (!m->profiling) return RN_OK;
-    return rn_event_record(m->run, m->prof[m->n_prof++].stop);
+    return rn_event_record(m->run.ctx, m->prof[m->n_prof++].stop);
 }
 
 int rn_model_set_profiling(rn_model *m, int on)
@@ -754,9 +778,6 @@ int rn_model_profile_get(const rn_model *m, uint64_t index, const char **op_name
     } while (0)
 
 /* ---- ops with profiling brackets --------------------------------------- */
-/* pad_override >= 0 replaces the layer's padding (the bf16 stem reads an image that carries
- * its own zero border: H, W are then the padded sizes and the padding is 0); RN_PAD_EXACT: the
- * fp32 stem in its exact-K form, x = [B,H,W,cin] physically padded */
 /* next record of the tuning pass's call list (the slices of a depth-first front repeat calls) */
 static rn_conv_call *next_call(rn_model *m)
 {
@@ -773,16 +794,61 @@ static rn_conv_call *next_call(rn_model *m)
 /* the tile tuned for a launch of B images in the current mode, or 0 = per-launch choice */
 static int tuned_tile(const rn_model *m, const int tile[2], const uint64_t tile_B[2], uint64_t B)
 {
-    if (!m->tuned_B || m->tuned_mode != m->cur_mode) return 0;
+    if (!m->tuned_B || m->tuned_mode != m->run.mode) return 0;
     return tile_B[0] == B ? tile[0] : tile_B[1] == B ? tile[1] : 0;
 }
 
-#define RN_PAD_EXACT (-2)
-static int op_conv(rn_model *m, const rn_conv *cv, const void *x, void *y, uint64_t B, uint64_t H,
-                   uint64_t W, const rn_epilogue *ep, int64_t pad_override)
+/* the one place a contraction is launched: the exact-K stem, the fused pair, the grouped or the dense kernel */
+static int launch_call(const rn_model *m, rn_ctx *ctx, const rn_conv_call *k)
 {
-    const int exact = pad_override == RN_PAD_EXACT;
-    const uint64_t pad = exact ? 0 : pad_override >= 0 ? (uint64_t)pad_override : cv->pad;
+    const rn_conv *cv = &m->convs[k->conv];
+    const rn_epilogue *ep = k->has_ep ? &k->ep : NULL;
+    const uint64_t ho = rn_conv_output_size(k->H, cv->k, cv->stride, k->pad);
+    const uint64_t wo = rn_conv_output_size(k->W, cv->k, cv->stride, k->pad);
+    if (k->pair_block >= 0) {
+        const rn_block *pb = &m->blocks[k->pair_block];
+        const rn_conv *cd = &m->convs[pb->ds];
+        rn_conv_second second;
+        second.inp = k->x2; second.in_channels = cd->cin; second.H = k->H2; second.W = k->W2;
+        second.stride = cd->stride;
+        return rn_conv2d_nhwc_pair_forward_dt(ctx, m->dtype, m->dtype, k->x, k->y, pb->pair_packed, cv->k,
+                                              cv->stride, k->pad, ho, wo, k->B, cv->cin, cv->cout, k->H, k->W,
+                                              &second, ep);
+    }
+    if (k->exact)
+        return rn_conv2d_nhwc_exact_forward(ctx, (const float *)k->x, (float *)k->y, m->stem_packed_exact, cv->k,
+                                            cv->stride, ho, wo, k->B, cv->cin, cv->cout, k->H, k->W, ep);
+    if (cv->groups > 1) /* one kernel, no tile candidates: every candidate times the same launch */
+        return rn_conv2d_grouped_nhwc_forward_dt(ctx, m->dtype, m->dtype, k->x, k->y, cv->packed, cv->k, cv->stride,
+                                                 k->pad, ho, wo, k->B, cv->cin, cv->cout, k->H, k->W, cv->groups, ep);
+    return rn_conv2d_nhwc_forward_dt(ctx, m->dtype, m->dtype, k->x, k->y, cv->packed, cv->k, cv->stride, k->pad, ho,
+                                     wo, k->B, cv->cin, cv->cout, k->H, k->W, ep);
+}
+
+/* a contraction of the forward being queued: on the call list when recording, then inside its profile
+ * bracket and with its tuned tile through launch_call */
+static int op_call(rn_model *m, const rn_conv_call *k, const char *op, const char *layer, double flops,
+                   double bytes, const int tile[2], const uint64_t tile_B[2])
+{
+    int st;
+    if (m->recording) {
+        rn_conv_call *c = next_call(m);
+        if (!c) return RN_ERR_NOMEM;
+        *c = *k;
+    }
+    TRY(prof_begin(m, op, layer, flops, bytes));
+    rn_ctx_set_conv_tile(m->run.ctx, tuned_tile(m, tile, tile_B, k->B));
+    st = launch_call(m, m->run.ctx, k);
+    rn_ctx_set_conv_tile(m->run.ctx, 0);
+    if (st != RN_OK) return st;
+    return prof_end(m);
+}
+
+/* x [B,H,W,cin] -> y.  pad replaces the layer's padding where the image carries its own zero border
+ * (H, W are then the padded sizes and pad is 0); exact: the fp32 stem in its exact-K form */
+static int op_conv_at(rn_model *m, const rn_conv *cv, const void *x, void *y, uint64_t B, uint64_t H,
+                      uint64_t W, const rn_epilogue *ep, uint64_t pad, int exact)
+{
     const uint64_t ho = rn_conv_output_size(H, cv->k, cv->stride, pad);
     const uint64_t wo = rn_conv_output_size(W, cv->k, cv->stride, pad);
     /* a grouped convolution counts its algorithmic products: K = k*k*cin/groups per output */
@@ -790,39 +856,24 @@ static int op_conv(rn_model *m, const rn_conv *cv, const void *x, void *y, uint6
     const double es = (double)elem_size(m);
     double bytes = es * ((double)(B * H * W * cv->cin) + K * (double)cv->cout +
                          M * (double)cv->cout);
+    rn_conv_call k;
     if (ep && ep->residual) bytes += es * M * (double)cv->cout;
-    if (m->recording) {
-        rn_conv_call *c = next_call(m);
-        if (!c) return RN_ERR_NOMEM;
-        c->conv = (int)(cv - m->convs);
-        c->pair_block = -1;
-        c->exact = exact;
-        c->x = x;
-        c->y = y;
-        c->B = B;
-        c->H = H;
-        c->W = W;
-        c->pad = pad;
-        c->has_ep = ep != NULL;
-        if (ep) c->ep = *ep;
-    }
-    TRY(prof_begin(m, ep ? "conv2d+epilogue" : "conv2d", cv->name, 2.0 * M * (double)cv->cout * K,
-                   bytes));
-    rn_ctx_set_conv_tile(m->run, tuned_tile(m, cv->tile, cv->tile_B, B));
-    {
-        const int st =
-            exact ? rn_conv2d_nhwc_exact_forward(m->run, (const float *)x, (float *)y,
-                                                 m->stem_packed_exact, cv->k, cv->stride, ho, wo, B,
-                                                 cv->cin, cv->cout, H, W, ep)
-            : cv->groups > 1
-                  ? rn_conv2d_grouped_nhwc_forward_dt(m->run, m->dtype, m->dtype, x, y, cv->packed, cv->k, cv->stride,
-                                                      pad, ho, wo, B, cv->cin, cv->cout, H, W, cv->groups, ep)
-                  : rn_conv2d_nhwc_forward_dt(m->run, m->dtype, m->dtype, x, y, cv->packed, cv->k,
-                                              cv->stride, pad, ho, wo, B, cv->cin, cv->cout, H, W, ep);
-        rn_ctx_set_conv_tile(m->run, 0);
-        if (st != RN_OK) return st;
-    }
-    return prof_end(m);
+    memset(&k, 0, sizeof(k));
+    k.conv = (int)(cv - m->convs);
+    k.pair_block = -1;
+    k.exact = exact;
+    k.x = x; k.y = y;
+    k.B = B; k.H = H; k.W = W; k.pad = pad;
+    k.has_ep = ep != NULL;
+    if (ep) k.ep = *ep;
+    return op_call(m, &k, ep ? "conv2d+epilogue" : "conv2d", cv->name, 2.0 * M * (double)cv->cout * K, bytes,
+                   cv->tile, cv->tile_B);
+}
+
+static int op_conv(rn_model *m, const rn_conv *cv, const void *x, void *y, uint64_t B, uint64_t H,
+                   uint64_t W, const rn_epilogue *ep)
+{
+    return op_conv_at(m, cv, x, y, B, H, W, ep, cv->pad, 0);
 }
 
 /* conv3 (input t, [B,H,W,c3->cin]) + downsample (input x, [B,H2,W2,cd->cin]) + shifts + ReLU; in a
@@ -836,32 +887,17 @@ static int op_pair(rn_model *m, rn_block *b, const void *t, const void *x, void 
     const double bytes = es * ((double)(B * H * W * c3->cin) + (double)(B * H2 * W2 * cd->cin) +
                                K * (double)c3->cout + M * (double)c3->cout);
     char name[RN_MAX_KEY];
-    rn_conv_second second;
-    rn_epilogue ep;
-    int st;
-    second.inp = x; second.in_channels = cd->cin; second.H = H2; second.W = W2;
-    second.stride = cd->stride;
-    ep.scale = NULL; ep.shift = b->pair_shift; ep.residual = NULL; ep.relu = 1;
-    if (m->recording) {
-        rn_conv_call *c = next_call(m);
-        if (!c) return RN_ERR_NOMEM;
-        c->conv = b->tail;
-        c->pair_block = (int)(b - m->blocks);
-        c->exact = 0;
-        c->x = t; c->x2 = x; c->y = y;
-        c->B = B; c->H = H; c->W = W; c->pad = c3->pad; c->H2 = H2; c->W2 = W2;
-        c->has_ep = 1;
-        c->ep = ep;
-    }
+    rn_conv_call k;
+    memset(&k, 0, sizeof(k));
+    k.conv = b->tail;
+    k.pair_block = (int)(b - m->blocks);
+    k.x = t; k.x2 = x; k.y = y;
+    k.B = B; k.H = H; k.W = W; k.pad = c3->pad; k.H2 = H2; k.W2 = W2;
+    k.has_ep = 1;
+    k.ep.scale = NULL; k.ep.shift = b->pair_shift; k.ep.residual = NULL; k.ep.relu = 1;
     snprintf(name, sizeof(name), "%.*s+downsample", (int)(RN_MAX_KEY - 12), c3->name);
-    TRY(prof_begin(m, "conv2d+epilogue", name, 2.0 * M * (double)c3->cout * K, bytes));
-    rn_ctx_set_conv_tile(m->run, tuned_tile(m, b->pair_tile, b->pair_tile_B, B));
-    st = rn_conv2d_nhwc_pair_forward_dt(m->run, m->dtype, m->dtype, t, y, b->pair_packed, c3->k,
-                                        c3->stride, c3->pad, H, W, B, c3->cin, c3->cout, H, W,
-                                        &second, &ep);
-    rn_ctx_set_conv_tile(m->run, 0);
-    if (st != RN_OK) return st;
-    return prof_end(m);
+    return op_call(m, &k, "conv2d+epilogue", name, 2.0 * M * (double)c3->cout * K, bytes, b->pair_tile,
+                   b->pair_tile_B);
 }
 
 /* conv3 + bn3 + residual + ReLU of block b and conv1 + bn1 + ReLU of the block after it as one
@@ -909,14 +945,14 @@ static int op_chain(rn_model *m, const rn_block *b, const void *t2, const void *
                              (double)c3->cout * k1 + (double)(n1->cout * n1->cin))));
     }
     if (b->ds >= 0) /* shortcut = the block's input: the downsample branch rides in the first product */
-        TRY(rn_conv_chain_pair_forward_dt(m->run, m->dtype, t2, shortcut, y, b->pair_packed, b->pair_shift,
-                                          m->v.t1, n1->packed, n1->scale, n1->shift, B * H * W, c3->cin,
+        TRY(rn_conv_chain_pair_forward_dt(m->run.ctx, m->dtype, t2, shortcut, y, b->pair_packed, b->pair_shift,
+                                          m->run.t1, n1->packed, n1->scale, n1->shift, B * H * W, c3->cin,
                                           m->convs[b->ds].cin, c3->cout, n1->cout));
     else
-        TRY(rn_conv_chain_forward_dt(m->run, m->dtype, t2, shortcut, y, c3->packed, c3->scale, c3->shift,
-                                     m->v.t1, n1->packed, n1->scale, n1->shift, B * H * W, c3->cin,
+        TRY(rn_conv_chain_forward_dt(m->run.ctx, m->dtype, t2, shortcut, y, c3->packed, c3->scale, c3->shift,
+                                     m->run.t1, n1->packed, n1->scale, n1->shift, B * H * W, c3->cin,
                                      c3->cout, n1->cout));
-    m->t1_ready = 1;
+    m->run.t1_ready = 1;
     return prof_end(m);
 }
 
@@ -924,7 +960,7 @@ static int op_bn(rn_model *m, const rn_conv *cv, float *y, uint64_t B, uint64_t 
 {
     const double n = (double)(B * cv->cout * HW);
     TRY(prof_begin(m, "batchnorm2d", cv->name, 0.0, 8.0 * n + 16.0 * (double)cv->cout));
-    TRY(rn_batchnorm2d_forward(m->run, y, y, m->params[cv->bn_w].dev, m->params[cv->bn_b].dev,
+    TRY(rn_batchnorm2d_forward(m->run.ctx, y, y, m->params[cv->bn_w].dev, m->params[cv->bn_b].dev,
                                m->params[cv->bn_m].dev, m->params[cv->bn_v].dev, B, cv->cout, HW));
     return prof_end(m);
 }
@@ -932,14 +968,135 @@ static int op_bn(rn_model *m, const rn_conv *cv, float *y, uint64_t B, uint64_t 
 static int op_relu(rn_model *m, const char *layer, float *y, uint64_t n)
 {
     TRY(prof_begin(m, "relu", layer, 0.0, 8.0 * (double)n));
-    TRY(rn_relu_forward(m->run, y, y, n));
+    TRY(rn_relu_forward(m->run.ctx, y, y, n));
     return prof_end(m);
 }
 
 static int op_add(rn_model *m, const char *layer, float *y, const float *shortcut, uint64_t n)
 {
     TRY(prof_begin(m, "add", layer, 0.0, 12.0 * (double)n));
-    TRY(rn_add_forward(m->run, y, shortcut, y, n)); /* out aliases inp1: main.cu:162 */
+    TRY(rn_add_forward(m->run.ctx, y, shortcut, y, n)); /* out aliases inp1: main.cu:162 */
+    return prof_end(m);
+}
+
+/* the reference-ops downsample branch: conv + bn into dsb */
+static int op_downsample(rn_model *m, const rn_conv *cd, const float *x, uint64_t B, uint64_t h, uint64_t w,
+                         uint64_t HWo)
+{
+    TRY(op_conv(m, cd, x, m->run.dsb, B, h, w, NULL));
+    return op_bn(m, cd, m->run.dsb, B, HWo);
+}
+
+/* One residual block, x -> y, both NHWC (layerForward body, main.cu:131-164).
+ *   bottleneck: conv1 1x1, conv2 3x3 (carries the stride, may be grouped), tail conv3 1x1;
+ *   basic (torchvision BasicBlock): conv1 3x3 (carries the stride), no conv2 stage, tail conv2 3x3;
+ *   it never chains (chain_applies).
+ * Fused: each convolution with its batch-norm and ReLU, the tail with the shortcut.  With pair fusion,
+ * a block with a downsample branch runs the tail and that branch as one contraction: the downsample
+ * tensor is never materialised, its K rows ride in the tail's loop (one fp32 sum over both K ranges
+ * instead of two rounded results added: not bit-neutral).
+ * Reference ops: the reference's order; the downsample branch is queued first in a bottleneck block
+ * and after conv2 + bn2 in a basic block. */
+static int block_forward(rn_model *m, rn_block *b, const float *x, float *y, uint64_t B,
+                         uint64_t *H, uint64_t *W, int mode)
+{
+    const rn_conv *c1 = &m->convs[b->conv1], *ct = &m->convs[b->tail];
+    const rn_conv *c2 = m->basic ? NULL : &m->convs[b->conv2]; /* the middle stage */
+    const rn_conv *cd = b->ds >= 0 ? &m->convs[b->ds] : NULL;
+    const rn_conv *cs = c2 ? c2 : c1;                          /* where the stride sits */
+    const uint64_t h = *H, w = *W;
+    const uint64_t ho = rn_conv_output_size(h, cs->k, cs->stride, cs->pad);
+    const uint64_t wo = rn_conv_output_size(w, cs->k, cs->stride, cs->pad);
+    const uint64_t h1 = c2 ? h : ho, w1 = c2 ? w : wo;         /* conv1's output */
+    float *mid = c2 ? m->run.t2 : m->run.t1;                   /* the tail's input */
+    const float *shortcut = x;
+    if (mode == RN_FWD_FUSED) {
+        rn_epilogue ep;
+        const int pair = cd && m->pair_fusion;
+        if (cd && !pair) {
+            ep.scale = cd->scale; ep.shift = cd->shift; ep.residual = NULL; ep.relu = 0;
+            TRY(op_conv(m, cd, x, m->run.dsb, B, h, w, &ep));
+            shortcut = m->run.dsb;
+        }
+        ep.scale = c1->scale; ep.shift = c1->shift; ep.residual = NULL; ep.relu = 1;
+        if (m->run.t1_ready)
+            m->run.t1_ready = 0; /* the block before has left this conv1's output in t1 (op_chain) */
+        else
+            TRY(op_conv(m, c1, x, m->run.t1, B, h, w, &ep));
+        if (c2) {
+            ep.scale = c2->scale; ep.shift = c2->shift;
+            TRY(op_conv(m, c2, m->run.t1, m->run.t2, B, h, w, &ep));
+        }
+        if (chain_applies(m, b, mode)) {
+            TRY(op_chain(m, b, mid, pair ? x : shortcut, y, B, ho, wo));
+        } else if (pair) {
+            TRY(op_pair(m, b, mid, x, y, B, ho, wo, h, w));
+        } else {
+            ep.scale = ct->scale; ep.shift = ct->shift; ep.residual = shortcut;
+            TRY(op_conv(m, ct, mid, y, B, ho, wo, &ep));
+        }
+    } else {
+        if (cd) shortcut = m->run.dsb;
+        if (cd && c2) TRY(op_downsample(m, cd, x, B, h, w, ho * wo));
+        TRY(op_conv(m, c1, x, m->run.t1, B, h, w, NULL));
+        TRY(op_bn(m, c1, m->run.t1, B, h1 * w1));
+        TRY(op_relu(m, c1->name, m->run.t1, B * h1 * w1 * c1->cout));
+        if (c2) {
+            TRY(op_conv(m, c2, m->run.t1, m->run.t2, B, h, w, NULL));
+            TRY(op_bn(m, c2, m->run.t2, B, ho * wo));
+            TRY(op_relu(m, c2->name, m->run.t2, B * ho * wo * c2->cout));
+        }
+        TRY(op_conv(m, ct, mid, y, B, ho, wo, NULL));
+        TRY(op_bn(m, ct, y, B, ho * wo));
+        if (cd && !c2) TRY(op_downsample(m, cd, x, B, h, w, ho * wo));
+        TRY(op_add(m, b->name, y, shortcut, B * ho * wo * ct->cout));
+        TRY(op_relu(m, b->name, y, B * ho * wo * ct->cout));
+    }
+    *H = ho;
+    *W = wo;
+    return RN_OK;
+}
+
+/* ---- the three parts of a forward: input + stem + pool, a run of blocks, average pool + fc ---- */
+
+/* The form the stem reads its image in (x4).  bf16: [B,230,230,4] with its own 3-pixel zero border,
+ * padding 0.  fp32 exact-K: [B,230,230,3] with a physical border.  fp32 otherwise: [B,224,224,4] and the
+ * layer's padding.  With from_nchw the fused stem + pool fetches its patches from the caller's NCHW fp32
+ * image itself and no layout launch runs (a byte image always goes through x4). */
+typedef struct {
+    uint64_t cpad, border; /* channels 3 or 4; zero border 0 or 3 */
+    int exact, fused_pool, from_nchw;
+} rn_stem_form;
+
+static rn_stem_form stem_form(const rn_model *m, int in_u8, int mode)
+{
+    const int bf16 = m->dtype == RN_DTYPE_BF16;
+    rn_stem_form f;
+    f.exact = !bf16 && m->stem_exact;
+    f.cpad = f.exact ? 3 : 4;
+    f.border = bf16 || f.exact ? m->convs[0].pad : 0;
+    f.fused_pool = mode == RN_FWD_FUSED && m->stem_pool && (bf16 || f.exact);
+    f.from_nchw = f.fused_pool && m->stem_pool == 2 && !in_u8;
+    return f;
+}
+
+/* The first launch: the caller's image -> the normalised (byte route) NHWC image in x4, the same bits
+ * from 8-bit RGB [B,224,224,3] as from the host-normalised fp32 NCHW image. */
+static const float kImageMean[3] = {0.485f, 0.456f, 0.406f}, kImageStd[3] = {0.229f, 0.224f, 0.225f};
+
+static int op_input(rn_model *m, const void *input, int in_u8, uint64_t B, const rn_stem_form *f)
+{
+    const double side = (double)(RN_IMAGE_SIDE + 2 * f->border);
+    const double out = (double)elem_size(m) * side * side * (double)f->cpad;
+    TRY(prof_begin(m, in_u8 ? (f->cpad == 3 ? "image_u8_to_nhwc3" : "image_u8_to_nhwc4")
+                            : (f->cpad == 3 ? "nchw_to_nhwc3" : "nchw_to_nhwc4"),
+                   "input", 0.0, (double)B * ((in_u8 ? 1.0 : 4.0) * RN_IMAGE_NUMEL + out)));
+    if (in_u8)
+        TRY(rn_image_u8_to_nhwc_pad_dt(m->run.ctx, m->dtype, (const uint8_t *)input, m->run.x4, B, RN_IMAGE_SIDE,
+                                       RN_IMAGE_SIDE, f->cpad, f->border, kImageMean, kImageStd));
+    else
+        TRY(rn_nchw_to_nhwc_pad_dt(m->run.ctx, m->dtype, (const float *)input, m->run.x4, B, 3, RN_IMAGE_SIDE,
+                                   RN_IMAGE_SIDE, f->cpad, f->border));
     return prof_end(m);
 }
 
@@ -947,308 +1104,136 @@ static int op_add(rn_model *m, const char *layer, float *y, const float *shortcu
  * -> p0 (pooled, where the separate max-pool writes too).  Algorithmic work: the stem's FLOPs
  * (no halo), the image read once, the pooled tensor written once. */
 static int op_stem_pool(rn_model *m, const rn_conv *stem, const float *input_nchw, uint64_t B,
-                        uint64_t Hp, uint64_t Wp, uint64_t ho, uint64_t wo)
+                        const rn_stem_form *f)
 {
     const double es = (double)elem_size(m);
-    const uint64_t ph = rn_conv_output_size(ho, 3, 2, 1), pw = rn_conv_output_size(wo, 3, 2, 1);
-    const double cs = m->dtype == RN_DTYPE_BF16 ? 4.0 : 3.0;
+    const uint64_t S = RN_IMAGE_SIDE, Sp = S + 2 * f->border, ho = m->stem_side, hp = m->pool_side;
     TRY(prof_begin(m, "conv2d+epilogue+maxpool", "conv1+maxpool",
-                   2.0 * (double)(B * ho * wo) * (double)stem->cout * (double)(stem->cin * stem->k * stem->k),
-                   (input_nchw ? 4.0 * (double)(B * (Hp - 6) * (Wp - 6) * stem->cin)
-                               : es * (double)(B * Hp * Wp) * cs) +
+                   2.0 * (double)(B * ho * ho) * (double)stem->cout * (double)(stem->cin * stem->k * stem->k),
+                   (input_nchw ? 4.0 * (double)(B * S * S * stem->cin)
+                               : es * (double)(B * Sp * Sp) * (double)f->cpad) +
                        es * ((double)(stem->cout * stem->cin * stem->k * stem->k) +
-                             (double)(B * ph * pw * stem->cout))));
+                             (double)(B * hp * hp * stem->cout))));
     if (input_nchw) /* stem_pool == 2: the patch fetch reads the caller's NCHW fp32 image itself */
-        TRY(rn_stem_pool_nchw_forward_dt(m->run, m->dtype, input_nchw, m->v.p0, m->stem_pool_packed,
-                                         stem->scale, stem->shift, 1, B, stem->cin, Hp - 6, Wp - 6));
+        TRY(rn_stem_pool_nchw_forward_dt(m->run.ctx, m->dtype, input_nchw, m->run.p0, m->stem_pool_packed,
+                                         stem->scale, stem->shift, 1, B, stem->cin, S, S));
     else
-        TRY(rn_stem_pool_forward_dt(m->run, m->dtype, m->v.x4, m->v.p0, m->stem_pool_packed, stem->scale,
-                                    stem->shift, 1, B, Hp, Wp));
+        TRY(rn_stem_pool_forward_dt(m->run.ctx, m->dtype, m->run.x4, m->run.p0, m->stem_pool_packed, stem->scale,
+                                    stem->shift, 1, B, Sp, Sp));
     return prof_end(m);
 }
 
-/* one basic block (torchvision BasicBlock): relu(bn2(conv2(relu(bn1(conv1(x))))) + shortcut).  The
- * stride is on conv1.  Fused: conv1 + bn1 + ReLU, then conv2 + bn2 + shortcut + ReLU; with pair
- * fusion, block 0 of stages 2-4 runs conv2 and the downsample branch as one contraction (one fp32 sum
- * over both K ranges instead of two rounded results added: not bit-neutral, as for the bottleneck
- * pair).  Reference ops: conv, bn, relu, conv, bn, [downsample conv, bn], add, relu. */
-static int basic_block_forward(rn_model *m, rn_block *b, const float *x, float *y, uint64_t B,
-                               uint64_t *H, uint64_t *W, int mode)
+/* input + stem + max-pool: the caller's images -> p0 [B,pool_side,pool_side,64] */
+static int run_front(rn_model *m, const void *input, int in_u8, uint64_t B, int mode)
 {
-    const rn_conv *c1 = &m->convs[b->conv1], *c2 = &m->convs[b->conv2];
-    const uint64_t h = *H, w = *W;
-    const uint64_t ho = rn_conv_output_size(h, c1->k, c1->stride, c1->pad);
-    const uint64_t wo = rn_conv_output_size(w, c1->k, c1->stride, c1->pad);
-    const float *shortcut = x;
-    if (mode == RN_FWD_FUSED) {
-        rn_epilogue ep;
-        const int pair = b->ds >= 0 && m->pair_fusion;
-        if (b->ds >= 0 && !pair) {
-            const rn_conv *cd = &m->convs[b->ds];
-            ep.scale = cd->scale; ep.shift = cd->shift; ep.residual = NULL; ep.relu = 0;
-            TRY(op_conv(m, cd, x, m->v.dsb, B, h, w, &ep, -1));
-            shortcut = m->v.dsb;
-        }
-        ep.scale = c1->scale; ep.shift = c1->shift; ep.residual = NULL; ep.relu = 1;
-        TRY(op_conv(m, c1, x, m->v.t1, B, h, w, &ep, -1));
-        if (pair) {
-            TRY(op_pair(m, b, m->v.t1, x, y, B, ho, wo, h, w));
-        } else {
-            ep.scale = c2->scale; ep.shift = c2->shift; ep.residual = shortcut;
-            TRY(op_conv(m, c2, m->v.t1, y, B, ho, wo, &ep, -1));
-        }
-    } else {
-        TRY(op_conv(m, c1, x, m->v.t1, B, h, w, NULL, -1));
-        TRY(op_bn(m, c1, m->v.t1, B, ho * wo));
-        TRY(op_relu(m, c1->name, m->v.t1, B * ho * wo * c1->cout));
-        TRY(op_conv(m, c2, m->v.t1, y, B, ho, wo, NULL, -1));
-        TRY(op_bn(m, c2, y, B, ho * wo));
-        if (b->ds >= 0) {
-            const rn_conv *cd = &m->convs[b->ds];
-            TRY(op_conv(m, cd, x, m->v.dsb, B, h, w, NULL, -1));
-            TRY(op_bn(m, cd, m->v.dsb, B, ho * wo));
-            shortcut = m->v.dsb;
-        }
-        TRY(op_add(m, b->name, y, shortcut, B * ho * wo * c2->cout));
-        TRY(op_relu(m, b->name, y, B * ho * wo * c2->cout));
+    const rn_conv *stem = &m->convs[0];
+    const rn_stem_form f = stem_form(m, in_u8, mode);
+    const uint64_t Sp = RN_IMAGE_SIDE + 2 * f.border, ho = m->stem_side, hp = m->pool_side;
+    rn_epilogue ep;
+    if (!f.from_nchw) TRY(op_input(m, input, in_u8, B, &f));
+    if (f.fused_pool) return op_stem_pool(m, stem, f.from_nchw ? (const float *)input : NULL, B, &f);
+    ep.scale = stem->scale; ep.shift = stem->shift; ep.residual = NULL; ep.relu = 1;
+    TRY(op_conv_at(m, stem, m->run.x4, m->run.p1, B, Sp, Sp, mode == RN_FWD_FUSED ? &ep : NULL,
+                   f.border ? 0 : stem->pad, f.exact));
+    if (mode != RN_FWD_FUSED) {
+        TRY(op_bn(m, stem, m->run.p1, B, ho * ho));
+        TRY(op_relu(m, "conv1", m->run.p1, B * ho * ho * stem->cout));
     }
-    *H = ho;
-    *W = wo;
+    /* maxpool 3x3 s2 p1 (main.cu:114,192) */
+    TRY(prof_begin(m, "maxpool2d", "maxpool", 0.0,
+                   (double)elem_size(m) * (double)(B * stem->cout * (ho * ho + hp * hp))));
+    TRY(rn_maxpool2d_nhwc_forward_dt(m->run.ctx, m->dtype, m->run.p1, m->run.p0, 3, 2, 1, hp, hp, B, stem->cout, ho,
+                                     ho));
+    return prof_end(m);
+}
+
+/* block i reads ping-pong arena i & 1 and writes the other */
+static float *block_input(const rn_model *m, int i) { return (i & 1) ? m->run.p1 : m->run.p0; }
+
+/* blocks [first, last) on a side x side map; *side becomes that of block last's input */
+static int run_blocks(rn_model *m, int first, int last, uint64_t B, uint64_t *side, int mode)
+{
+    uint64_t H = *side, W = *side;
+    int bi;
+    for (bi = first; bi < last; ++bi)
+        TRY(block_forward(m, &m->blocks[bi], block_input(m, bi), block_input(m, bi + 1), B, &H, &W, mode));
+    *side = H;
     return RN_OK;
 }
 
-/* one bottleneck block (layerForward body, main.cu:131-164).  x -> y, both NHWC. */
-static int bottleneck_block_forward(rn_model *m, rn_block *b, const float *x, float *y, uint64_t B,
-                                    uint64_t *H, uint64_t *W, int mode)
+/* global average over the side x side map (main.cu:120,213) then fc (main.cu:122,224) */
+static int run_head(rn_model *m, const float *x, uint64_t B, uint64_t side, float *logits)
 {
-    const rn_conv *c1 = &m->convs[b->conv1], *c2 = &m->convs[b->conv2], *c3 = &m->convs[b->conv3];
-    const uint64_t h = *H, w = *W;
-    const uint64_t ho = rn_conv_output_size(h, c2->k, c2->stride, c2->pad);
-    const uint64_t wo = rn_conv_output_size(w, c2->k, c2->stride, c2->pad);
-    const float *shortcut = x;
-    if (mode == RN_FWD_FUSED) {
+    const double es = (double)elem_size(m);
+    TRY(prof_begin(m, "avgpool2d", "avgpool", 0.0, es * (double)(B * m->feat * (side * side + 1))));
+    TRY(rn_avgpool2d_nhwc_forward_dt(m->run.ctx, m->dtype, x, m->run.pooled, side, 1, 0,
+                                     rn_conv_output_size(side, side, 1, 0), rn_conv_output_size(side, side, 1, 0), B,
+                                     m->feat, side, side));
+    TRY(prof_end(m));
+    TRY(prof_begin(m, "linear", "fc", 2.0 * (double)B * (double)m->feat * RN_CLASSES,
+                   es * ((double)(B * m->feat) + (double)m->feat * RN_CLASSES) +
+                       4.0 * (RN_CLASSES + (double)B * RN_CLASSES)));
+    if (m->dtype == RN_DTYPE_BF16) {
         rn_epilogue ep;
-        const int pair = b->ds >= 0 && m->pair_fusion;
-        if (b->ds >= 0 && !pair) {
-            const rn_conv *cd = &m->convs[b->ds];
-            ep.scale = cd->scale; ep.shift = cd->shift; ep.residual = NULL; ep.relu = 0;
-            TRY(op_conv(m, cd, x, m->v.dsb, B, h, w, &ep, -1));
-            shortcut = m->v.dsb;
-        }
-        ep.scale = c1->scale; ep.shift = c1->shift; ep.residual = NULL; ep.relu = 1;
-        if (m->t1_ready)
-            m->t1_ready = 0; /* the block before has left this conv1's output in t1 (op_chain) */
-        else
-            TRY(op_conv(m, c1, x, m->v.t1, B, h, w, &ep, -1));
-        ep.scale = c2->scale; ep.shift = c2->shift;
-        TRY(op_conv(m, c2, m->v.t1, m->v.t2, B, h, w, &ep, -1));
-        if (chain_applies(m, b, mode)) {
-            TRY(op_chain(m, b, m->v.t2, pair ? x : shortcut, y, B, ho, wo));
-        } else if (pair) {
-            /* the downsample tensor is never materialised: its K rows ride in conv3's loop */
-            TRY(op_pair(m, b, m->v.t2, x, y, B, ho, wo, h, w));
-        } else {
-            ep.scale = c3->scale; ep.shift = c3->shift; ep.residual = shortcut;
-            TRY(op_conv(m, c3, m->v.t2, y, B, ho, wo, &ep, -1));
-        }
+        ep.scale = NULL; ep.shift = m->params[m->fc_b].dev; ep.residual = NULL; ep.relu = 0;
+        TRY(rn_conv2d_nhwc_forward_dt(m->run.ctx, m->dtype, RN_DTYPE_F32, m->run.pooled, logits, m->fc_packed, 1, 1, 0,
+                                      1, 1, B, m->feat, RN_CLASSES, 1, 1, &ep));
     } else {
-        if (b->ds >= 0) {
-            const rn_conv *cd = &m->convs[b->ds];
-            TRY(op_conv(m, cd, x, m->v.dsb, B, h, w, NULL, -1));
-            TRY(op_bn(m, cd, m->v.dsb, B, ho * wo));
-            shortcut = m->v.dsb;
-        }
-        TRY(op_conv(m, c1, x, m->v.t1, B, h, w, NULL, -1));
-        TRY(op_bn(m, c1, m->v.t1, B, h * w));
-        TRY(op_relu(m, c1->name, m->v.t1, B * h * w * c1->cout));
-        TRY(op_conv(m, c2, m->v.t1, m->v.t2, B, h, w, NULL, -1));
-        TRY(op_bn(m, c2, m->v.t2, B, ho * wo));
-        TRY(op_relu(m, c2->name, m->v.t2, B * ho * wo * c2->cout));
-        TRY(op_conv(m, c3, m->v.t2, y, B, ho, wo, NULL, -1));
-        TRY(op_bn(m, c3, y, B, ho * wo));
-        TRY(op_add(m, b->name, y, shortcut, B * ho * wo * c3->cout));
-        TRY(op_relu(m, b->name, y, B * ho * wo * c3->cout));
+        TRY(rn_linear_forward(m->run.ctx, m->run.pooled, logits, m->params[m->fc_w].dev, m->params[m->fc_b].dev, B,
+                              m->feat, RN_CLASSES));
     }
-    *H = ho;
-    *W = wo;
-    return RN_OK;
+    return prof_end(m);
 }
 
-static int block_forward(rn_model *m, rn_block *b, const float *x, float *y, uint64_t B,
-                         uint64_t *H, uint64_t *W, int mode)
+/* What the ops queued from here on run on: context `ctx`, mode, and the arenas from image img_off +
+ * slice_off on.  slice_off: images into the part of a slice of a depth-first front.  The back phase reads
+ * the first stage's output of all slices as one batch, so in the ping-pong arenas a slice starts slice_off
+ * first-stage outputs into its part (in a basic-block network 1/4 of an arena image; the slice's larger
+ * stem tensor then reaches into the room of the slices after it, which run later on the same stream). */
+static void run_begin(rn_model *m, rn_ctx *ctx, uint64_t img_off, uint64_t slice_off, int mode)
 {
-    return m->basic ? basic_block_forward(m, b, x, y, B, H, W, mode)
-                    : bottleneck_block_forward(m, b, x, y, B, H, W, mode);
+    const uint64_t es = elem_size(m);
+    const uint64_t p_off = img_off * m->p_img + slice_off * m->s1_img;
+    rn_run *r = &m->run;
+    img_off += slice_off;
+    r->ctx = ctx;
+    r->mode = mode;
+    r->t1_ready = 0;
+    r->x4 = (float *)((char *)m->x4 + img_off * m->x4_img * es);
+    r->p0 = (float *)((char *)m->p0 + p_off * es);
+    r->p1 = (float *)((char *)m->p1 + p_off * es);
+    r->dsb = (float *)((char *)m->dsb + img_off * m->ds_img * es);
+    r->t1 = (float *)((char *)m->t1 + img_off * m->t1_img * es);
+    r->t2 = m->t2 ? (float *)((char *)m->t2 + img_off * m->t2_img * es) : NULL; /* none in a basic block */
+    r->pooled = (float *)((char *)m->pooled + img_off * m->feat * es);
 }
 
-int rn_ctx_wait_event(rn_ctx *ctx, rn_event *ev); /* rn_ctx.hip: the stream waits, not the host */
-
-/* B images whose activations live at image offset img_off of the arenas, queued on `run`. */
+/* a whole forward, or the halves of a depth-first one: the front ends after the first stage, where the
+ * back (the front ran already, in slices) starts */
 enum { RN_PHASE_ALL = 0, RN_PHASE_FRONT = 1, RN_PHASE_BACK = 2 };
 
-/* The byte route's first launch: 8-bit RGB [B,224,224,3] -> the normalised, padded image in x4, the
- * tensor the float route's layout launch writes from the host-normalised NCHW image (same bits). */
-static const float kImageMean[3] = {0.485f, 0.456f, 0.406f}, kImageStd[3] = {0.229f, 0.224f, 0.225f};
-
-static int op_input_u8(rn_model *m, const void *input, uint64_t B, uint64_t cpad, uint64_t border)
+static int forward_phase(rn_model *m, const void *input, int in_u8, uint64_t B, float *logits, int mode,
+                         int phase)
 {
-    const double side = (double)(224 + 2 * border);
-    TRY(prof_begin(m, cpad == 3 ? "image_u8_to_nhwc3" : "image_u8_to_nhwc4", "input", 0.0,
-                   (double)B * (3.0 * 224 * 224 + (double)elem_size(m) * side * side * (double)cpad)));
-    TRY(rn_image_u8_to_nhwc_pad_dt(m->run, m->dtype, (const uint8_t *)input, m->v.x4, B, 224, 224, cpad, border,
-                                   kImageMean, kImageStd));
-    return prof_end(m);
+    const int first = phase == RN_PHASE_BACK ? m->depths[0] : 0;
+    const int last = phase == RN_PHASE_FRONT ? m->depths[0] : m->n_blocks;
+    uint64_t side = m->pool_side; /* the first stage keeps it (stride 1): the back starts there too */
+    if (phase != RN_PHASE_BACK) TRY(run_front(m, input, in_u8, B, mode));
+    TRY(run_blocks(m, first, last, B, &side, mode));
+    if (phase != RN_PHASE_FRONT) TRY(run_head(m, block_input(m, last), B, side, logits));
+    return RN_OK;
 }
 
-/* slice_off: images into the part of a slice of a depth-first front.  The back phase reads the first stage's
- * output of all slices as one batch, so in the ping-pong arenas a slice starts slice_off first-stage outputs
- * into its part (in a basic-block network 1/4 of an arena image; the slice's larger stem tensor then reaches
- * into the room of the slices after it, which run later on the same stream). */
+/* B images whose activations live at image offset img_off (+ slice_off) of the arenas, queued on `run` */
 static int forward_sub(rn_model *m, rn_ctx *run, uint64_t img_off, uint64_t slice_off, const void *input,
-                       uint64_t B, float *logits, int mode, int phase)
+                       int in_u8, uint64_t B, float *logits, int mode, int phase)
 {
-    const float *input_nchw = (const float *)input; /* the float route's view of it */
-    const int nfront = m->depths[0]; /* blocks of the front phase: the first stage */
-    int fused_pool = 0;
-    const rn_conv *stem;
-    uint64_t H = 224, W = 224, ho, wo, ph, pw;
-    float *x, *y, *tmp;
-    int bi, saved_layout, st;
-    {
-        const uint64_t es = elem_size(m);
-        const uint64_t p_off = img_off * m->p_img + slice_off * m->s1_img;
-        m->run = run;
-        img_off += slice_off;
-        m->v.x4 = (float *)((char *)m->x4 + img_off * m->x4_img * es);
-        m->v.p0 = (float *)((char *)m->p0 + p_off * es);
-        m->v.p1 = (float *)((char *)m->p1 + p_off * es);
-        m->v.dsb = (float *)((char *)m->dsb + img_off * m->ds_img * es);
-        m->v.t1 = (float *)((char *)m->t1 + img_off * m->t1_img * es);
-        m->v.t2 = m->t2 ? (float *)((char *)m->t2 + img_off * m->t2_img * es) : NULL; /* none in a basic block */
-        m->v.pooled = (float *)((char *)m->pooled + img_off * m->feat * es);
-    }
-    m->cur_mode = mode;
-    m->t1_ready = 0;
-    saved_layout = rn_ctx_get_layout(m->run);
-    rn_ctx_set_layout(m->run, RN_LAYOUT_NHWC);
-    st = RN_OK;
-    do {
-#define STEP(expr) if ((st = (expr)) != RN_OK) break
-        const double es = (double)elem_size(m);
-        const int bf16 = m->dtype == RN_DTYPE_BF16;
-        stem = &m->convs[0];
-        if (phase == RN_PHASE_BACK) {
-            /* the front ran already (in slices): x holds the first stage's output */
-            H = W = 56;
-            x = (nfront & 1) ? m->v.p1 : m->v.p0;
-            y = (nfront & 1) ? m->v.p0 : m->v.p1;
-            for (bi = nfront; bi < m->n_blocks; ++bi) {
-                STEP(block_forward(m, &m->blocks[bi], x, y, B, &H, &W, mode));
-                tmp = x; x = y; y = tmp;
-            }
-            if (st != RN_OK) break;
-            goto tail_ops;
-        }
-        if (bf16) {
-            /* bf16 stem: [B,230,230,4] image with its own 3-pixel zero border, padding 0 */
-            const uint64_t border = stem->pad;
-            const int from_nchw = m->stem_pool == 2 && !m->in_u8; /* bytes: the padded-image form */
-            if (m->in_u8) {
-                STEP(op_input_u8(m, input, B, 4, border));
-            } else if (!from_nchw) {
-                STEP(prof_begin(m, "nchw_to_nhwc4", "input", 0.0,
-                                (double)B * (4.0 * 3 * 224 * 224 + es * 230 * 230 * 4)));
-                STEP(rn_nchw_to_nhwc_pad_dt(m->run, m->dtype, input_nchw, m->v.x4, B, 3, H, W, 4, border));
-                STEP(prof_end(m));
-            }
-            ho = rn_conv_output_size(H + 2 * border, stem->k, stem->stride, 0);
-            wo = rn_conv_output_size(W + 2 * border, stem->k, stem->stride, 0);
-            if (m->stem_pool) {
-                STEP(op_stem_pool(m, stem, from_nchw ? input_nchw : NULL, B, H + 2 * border, W + 2 * border, ho, wo));
-                fused_pool = 1;
-            } else {
-                rn_epilogue ep;
-                ep.scale = stem->scale; ep.shift = stem->shift; ep.residual = NULL; ep.relu = 1;
-                STEP(op_conv(m, stem, m->v.x4, m->v.p1, B, H + 2 * border, W + 2 * border, &ep, 0));
-            }
-        } else {
-            /* exact-K form: [B,230,230,3] with a physical border; else [B,224,224,4] */
-            const uint64_t border = m->stem_exact ? stem->pad : 0;
-            const uint64_t sh = H + 2 * border, sw = W + 2 * border;
-            const int64_t form = m->stem_exact ? RN_PAD_EXACT : -1;
-            const int from_nchw = mode == RN_FWD_FUSED && m->stem_pool == 2 && m->stem_exact && !m->in_u8;
-            if (from_nchw) {
-                /* no layout launch */
-            } else if (m->in_u8) {
-                STEP(op_input_u8(m, input, B, m->stem_exact ? 3 : 4, border));
-            } else if (m->stem_exact) {
-                STEP(prof_begin(m, "nchw_to_nhwc3", "input", 0.0,
-                                4.0 * (double)B * (3.0 * 224 * 224 + 3.0 * 230 * 230)));
-                STEP(rn_nchw_to_nhwc_pad_dt(m->run, RN_DTYPE_F32, input_nchw, m->v.x4, B, 3, H, W, 3,
-                                            border));
-            } else {
-                STEP(prof_begin(m, "nchw_to_nhwc4", "input", 0.0, 4.0 * (double)(B * 224 * 224 * 7)));
-                STEP(rn_nchw_to_nhwc_pad(m->run, input_nchw, m->v.x4, B, 3, H, W, 4));
-            }
-            if (!from_nchw && !m->in_u8) STEP(prof_end(m));
-            ho = rn_conv_output_size(H, stem->k, stem->stride, stem->pad);
-            wo = rn_conv_output_size(W, stem->k, stem->stride, stem->pad);
-            if (mode == RN_FWD_FUSED && m->stem_pool && m->stem_exact) {
-                STEP(op_stem_pool(m, stem, from_nchw ? input_nchw : NULL, B, sh, sw, ho, wo));
-                fused_pool = 1;
-            } else if (mode == RN_FWD_FUSED) {
-                rn_epilogue ep;
-                ep.scale = stem->scale; ep.shift = stem->shift; ep.residual = NULL; ep.relu = 1;
-                STEP(op_conv(m, stem, m->v.x4, m->v.p1, B, sh, sw, &ep, form));
-            } else {
-                STEP(op_conv(m, stem, m->v.x4, m->v.p1, B, sh, sw, NULL, form));
-                STEP(op_bn(m, stem, m->v.p1, B, ho * wo));
-                STEP(op_relu(m, "conv1", m->v.p1, B * ho * wo * 64));
-            }
-        }
-        /* maxpool 3x3 s2 p1 (main.cu:114,192) */
-        ph = rn_conv_output_size(ho, 3, 2, 1);
-        pw = rn_conv_output_size(wo, 3, 2, 1);
-        if (!fused_pool) {
-            STEP(prof_begin(m, "maxpool2d", "maxpool", 0.0,
-                            es * (double)(B * 64 * (ho * wo + ph * pw))));
-            STEP(rn_maxpool2d_nhwc_forward_dt(m->run, m->dtype, m->v.p1, m->v.p0, 3, 2, 1, ph, pw, B, 64, ho,
-                                              wo));
-            STEP(prof_end(m));
-        }
-        H = ph;
-        W = pw;
-        x = m->v.p0;
-        y = m->v.p1;
-        for (bi = 0; bi < (phase == RN_PHASE_FRONT ? nfront : m->n_blocks); ++bi) {
-            STEP(block_forward(m, &m->blocks[bi], x, y, B, &H, &W, mode));
-            tmp = x; x = y; y = tmp;
-        }
-        if (st != RN_OK || phase == RN_PHASE_FRONT) break;
-    tail_ops:
-        /* global 7x7 average (main.cu:120,213) then fc (main.cu:122,224) */
-        STEP(prof_begin(m, "avgpool2d", "avgpool", 0.0, es * (double)(B * m->feat * (H * W + 1))));
-        STEP(rn_avgpool2d_nhwc_forward_dt(m->run, m->dtype, x, m->v.pooled, 7, 1, 0,
-                                          rn_conv_output_size(H, 7, 1, 0),
-                                          rn_conv_output_size(W, 7, 1, 0), B, m->feat, H, W));
-        STEP(prof_end(m));
-        STEP(prof_begin(m, "linear", "fc", 2.0 * (double)B * (double)m->feat * RN_CLASSES,
-                        es * ((double)(B * m->feat) + (double)m->feat * RN_CLASSES) +
-                            4.0 * (RN_CLASSES + (double)B * RN_CLASSES)));
-        if (bf16) {
-            rn_epilogue ep;
-            ep.scale = NULL; ep.shift = m->params[m->fc_b].dev; ep.residual = NULL; ep.relu = 0;
-            STEP(rn_conv2d_nhwc_forward_dt(m->run, m->dtype, RN_DTYPE_F32, m->v.pooled, logits,
-                                           m->fc_packed, 1, 1, 0, 1, 1, B, m->feat, RN_CLASSES, 1, 1,
-                                           &ep));
-        } else {
-            STEP(rn_linear_forward(m->run, m->v.pooled, logits, m->params[m->fc_w].dev,
-                                   m->params[m->fc_b].dev, B, m->feat, RN_CLASSES));
-        }
-        STEP(prof_end(m));
-#undef STEP
-    } while (0);
-    rn_ctx_set_layout(m->run, saved_layout);
+    const int saved_layout = rn_ctx_get_layout(run);
+    int st;
+    run_begin(m, run, img_off, slice_off, mode);
+    rn_ctx_set_layout(run, RN_LAYOUT_NHWC);
+    st = forward_phase(m, input, in_u8, B, logits, mode, phase);
+    rn_ctx_set_layout(run, saved_layout);
     return st;
 }
 
@@ -1272,39 +1257,40 @@ static int parts_of(const rn_model *m, uint64_t B)
 #define RN_FRONT_MIN_SLICE 16
 
 /* image `lo` of the caller's input: fp32 NCHW, or 8-bit RGB on the byte route */
-static const void *input_at(const rn_model *m, const void *input, uint64_t lo)
+static const void *input_at(const void *input, int in_u8, uint64_t lo)
 {
-    return (const char *)input + lo * 3 * 224 * 224 * (m->in_u8 ? 1 : sizeof(float));
+    return (const char *)input + lo * RN_IMAGE_NUMEL * (in_u8 ? 1 : sizeof(float));
 }
 
 /* B images at image offset img_off on `run`: whole, or depth-first through the front */
-static int forward_part(rn_model *m, rn_ctx *run, uint64_t img_off, const void *input,
+static int forward_part(rn_model *m, rn_ctx *run, uint64_t img_off, const void *input, int in_u8,
                         uint64_t B, float *logits, int mode)
 {
     int fp = m->front_parts, j;
     uint64_t lo = 0;
     while (fp > 1 && B / (uint64_t)fp < RN_FRONT_MIN_SLICE) fp /= 2;
-    if (fp < 2) return forward_sub(m, run, img_off, 0, input, B, logits, mode, RN_PHASE_ALL);
+    if (fp < 2) return forward_sub(m, run, img_off, 0, input, in_u8, B, logits, mode, RN_PHASE_ALL);
     for (j = 0; j < fp; ++j) {
         const uint64_t hi = B * (uint64_t)(j + 1) / (uint64_t)fp;
-        TRY(forward_sub(m, run, img_off, lo, input_at(m, input, lo), hi - lo, logits, mode,
+        TRY(forward_sub(m, run, img_off, lo, input_at(input, in_u8, lo), in_u8, hi - lo, logits, mode,
                         RN_PHASE_FRONT));
         lo = hi;
     }
-    return forward_sub(m, run, img_off, 0, input, B, logits, mode, RN_PHASE_BACK);
+    return forward_sub(m, run, img_off, 0, input, in_u8, B, logits, mode, RN_PHASE_BACK);
 }
 
 /* One sub-batch: every tensor of it stays below the kernels' 2^29-element range.  Large enough,
- * it runs as `streams` contiguous parts on as many streams (see rn_model.streams). */
-static int forward_chunk(rn_model *m, const void *input, uint64_t B, float *logits, int mode)
+ * it runs as `streams` contiguous parts on as many streams (see rn_model.streams).  prof_keep: the
+ * profile records queued before it (the resize launch) stay. */
+static int forward_chunk(rn_model *m, const void *input, int in_u8, uint64_t B, float *logits, int mode,
+                         int prof_keep)
 {
     uint64_t lo = 0;
     int parts = parts_of(m, B), i;
     TRY(ensure_acts(m, B));
-    if (!m->prof_keep) m->n_prof = 0;
-    m->prof_keep = 0;
+    if (!prof_keep) m->n_prof = 0;
     if (parts < 2 || m->profiling || m->single_stream_only || m->recording)
-        return forward_part(m, m->ctx, 0, input, B, logits, mode);
+        return forward_part(m, m->ctx, 0, input, in_u8, B, logits, mode);
     if (!m->ev_fork) TRY(rn_event_create(m->ctx, &m->ev_fork));
     for (i = 0; i < parts - 1; ++i) {
         if (m->ctxn[i]) continue;
@@ -1318,7 +1304,7 @@ static int forward_chunk(rn_model *m, const void *input, uint64_t B, float *logi
         const uint64_t hi = B * (uint64_t)(i + 1) / (uint64_t)parts;
         rn_ctx *run = i == 0 ? m->ctx : m->ctxn[i - 1];
         if (i > 0) TRY(rn_ctx_wait_event(run, m->ev_fork));
-        TRY(forward_part(m, run, lo, input_at(m, input, lo), hi - lo, logits + lo * RN_CLASSES,
+        TRY(forward_part(m, run, lo, input_at(input, in_u8, lo), in_u8, hi - lo, logits + lo * RN_CLASSES,
                          mode));
         if (i > 0) TRY(rn_event_record(run, m->ev_join[i - 1]));
         lo = hi;
@@ -1332,9 +1318,11 @@ static int forward_chunk(rn_model *m, const void *input, uint64_t B, float *logi
  * of 669 images is the first to pass it), so a larger batch runs as sub-batches of at most
  * RN_MAX_SUB_BATCH images through the same arenas.  Every image's logits are independent of
  * what else is in its launch (batch invariance, bit for bit), so the split changes nothing.
- * (RN_MAX_SUB_BATCH is defined above, next to the stream split.) */
-
-static int forward_any(rn_model *m, const void *input, uint64_t B, float *logits, int mode)
+ * (RN_MAX_SUB_BATCH is defined above, next to the stream split.)
+ * in_u8: the input is 8-bit RGB [B,224,224,3], not fp32 NCHW; prof_keep: see forward_chunk (the
+ * first sub-batch only). */
+static int forward_any(rn_model *m, const void *input, int in_u8, uint64_t B, float *logits, int mode,
+                       int prof_keep)
 {
     uint64_t done = 0;
     if (!m || !input || !logits || B == 0) return RN_ERR_INVALID;
@@ -1344,7 +1332,8 @@ static int forward_any(rn_model *m, const void *input, uint64_t B, float *logits
     if (m->dtype != RN_DTYPE_F32 && mode != RN_FWD_FUSED) return RN_ERR_UNSUPPORTED;
     while (done < B) {
         const uint64_t nb = B - done < RN_MAX_SUB_BATCH ? B - done : RN_MAX_SUB_BATCH;
-        TRY(forward_chunk(m, input_at(m, input, done), nb, logits + done * RN_CLASSES, mode));
+        TRY(forward_chunk(m, input_at(input, in_u8, done), in_u8, nb, logits + done * RN_CLASSES, mode,
+                          prof_keep && done == 0));
         done += nb;
     }
     return RN_OK;
@@ -1352,25 +1341,13 @@ static int forward_any(rn_model *m, const void *input, uint64_t B, float *logits
 
 int rn_model_forward(rn_model *m, const float *input_nchw, uint64_t B, float *logits, int mode)
 {
-    return forward_any(m, input_nchw, B, logits, mode);
+    return forward_any(m, input_nchw, 0, B, logits, mode, 0);
 }
 
 int rn_model_forward_u8(rn_model *m, const uint8_t *input_nhwc, uint64_t B, float *logits, int mode)
 {
-    int st;
-    if (!m) return RN_ERR_INVALID;
-    m->in_u8 = 1;
-    st = forward_any(m, input_nhwc, B, logits, mode);
-    m->in_u8 = 0;
-    return st;
+    return forward_any(m, input_nhwc, 1, B, logits, mode, 0);
 }
-
-/* rn_resize.hip */
-int rn_image_u8_resize_crop_launch(rn_ctx *ctx, const uint8_t *packed_dev, const void *table_dev, uint64_t B,
-                                   uint8_t *dst_dev, uint64_t crop);
-int rn_ctx_scratch_slot(rn_ctx *ctx, int slot, uint64_t bytes, void **ptr); /* rn_ctx.hip */
-int rn_ctx_is_capturing(rn_ctx *ctx);                                      /* rn_ctx.hip */
-int rn_ctx_upload_sync(rn_ctx *ctx, void *dev, const void *host, uint64_t bytes); /* rn_ctx.hip */
 
 /* Decoded images whose tables are on the device already (the host pipeline stages them with the batch):
  * one resize launch for the whole batch on the model's stream, then the byte route on the crops.
@@ -1387,74 +1364,42 @@ int rn_model_forward_images_table(rn_model *m, const uint8_t *packed_dev, const 
         if (m->crops) TRY(rn_free(m->ctx, m->crops));
         m->crops = NULL;
         m->crops_cap = 0;
-        TRY(rn_malloc(m->ctx, (void **)&m->crops, B * 3 * 224 * 224));
+        TRY(rn_malloc(m->ctx, (void **)&m->crops, B * RN_IMAGE_NUMEL));
         m->crops_cap = B;
     }
-    m->run = m->ctx;
+    run_begin(m, m->ctx, 0, 0, mode);
     m->n_prof = 0;
-    TRY(prof_begin(m, "image_u8_resize_crop", "input", 0.0, src_bytes + (double)B * 3.0 * 224 * 224));
-    TRY(rn_image_u8_resize_crop_launch(m->ctx, packed_dev, table_dev, B, m->crops, 224));
+    TRY(prof_begin(m, "image_u8_resize_crop", "input", 0.0, src_bytes + (double)B * RN_IMAGE_NUMEL));
+    TRY(rn_image_u8_resize_crop_launch(m->ctx, packed_dev, table_dev, B, m->crops, RN_IMAGE_SIDE));
     TRY(prof_end(m));
-    m->prof_keep = 1;
-    {
-        const int st = rn_model_forward_u8(m, m->crops, B, logits, mode);
-        m->prof_keep = 0;
-        return st;
-    }
+    return forward_any(m, m->crops, 1, B, logits, mode, 1); /* keeps the resize launch's record */
 }
 
 int rn_model_forward_images_u8(rn_model *m, const uint8_t *packed_dev, const uint64_t *offsets,
                                const uint64_t *heights, const uint64_t *widths, uint64_t B, float *logits, int mode)
 {
+    const double crop = (double)RN_IMAGE_SIDE / RN_RESIZE_SIDE;
     uint64_t bytes = 0, i;
     double src_bytes = 0.0;
     void *host, *dev = NULL;
     int st;
     if (!m || !packed_dev || !offsets || !heights || !widths || !logits || B == 0) return RN_ERR_INVALID;
-    if (rn_image_u8_resize_crop_table(offsets, heights, widths, B, 256, 224, NULL, 0, &bytes) != RN_OK)
+    if (rn_image_u8_resize_crop_table(offsets, heights, widths, B, RN_RESIZE_SIDE, RN_IMAGE_SIDE, NULL, 0, &bytes) !=
+        RN_OK)
         return RN_ERR_INVALID;
     if (rn_ctx_is_capturing(m->ctx)) return RN_ERR_UNSUPPORTED; /* the tables come from host memory freed below */
     host = malloc(bytes);
     if (!host) return RN_ERR_NOMEM;
-    st = rn_image_u8_resize_crop_table(offsets, heights, widths, B, 256, 224, host, bytes, &bytes);
+    st = rn_image_u8_resize_crop_table(offsets, heights, widths, B, RN_RESIZE_SIDE, RN_IMAGE_SIDE, host, bytes, &bytes);
     if (st == RN_OK) st = rn_ctx_scratch_slot(m->ctx, 5, bytes, &dev);
     if (st == RN_OK) st = rn_ctx_upload_sync(m->ctx, dev, host, bytes);
     free(host);
     if (st != RN_OK) return st;
-    for (i = 0; i < B; ++i) src_bytes += 3.0 * (double)heights[i] * (double)widths[i] * (224.0 / 256.0) * (224.0 / 256.0);
+    for (i = 0; i < B; ++i) src_bytes += 3.0 * (double)heights[i] * (double)widths[i] * crop * crop;
     return rn_model_forward_images_table(m, packed_dev, dev, B, src_bytes, logits, mode);
 }
 
 #define RN_TUNE_ROUNDS 6
-
-/* one recorded contraction call again, on context `run` */
-static int replay_call(rn_model *m, rn_ctx *run, const rn_conv_call *k)
-{
-    rn_conv *cv = &m->convs[k->conv];
-    const uint64_t ho = rn_conv_output_size(k->H, cv->k, cv->stride, k->pad);
-    const uint64_t wo = rn_conv_output_size(k->W, cv->k, cv->stride, k->pad);
-    if (k->pair_block >= 0) {
-        const rn_block *pb = &m->blocks[k->pair_block];
-        const rn_conv *cd = &m->convs[pb->ds];
-        rn_conv_second second;
-        second.inp = k->x2; second.in_channels = cd->cin; second.H = k->H2;
-        second.W = k->W2; second.stride = cd->stride;
-        return rn_conv2d_nhwc_pair_forward_dt(run, m->dtype, m->dtype, k->x, k->y, pb->pair_packed, cv->k,
-                                              cv->stride, k->pad, ho, wo, k->B, cv->cin, cv->cout, k->H,
-                                              k->W, &second, &k->ep);
-    }
-    if (k->exact)
-        return rn_conv2d_nhwc_exact_forward(run, (const float *)k->x, (float *)k->y, m->stem_packed_exact,
-                                            cv->k, cv->stride, ho, wo, k->B, cv->cin, cv->cout, k->H, k->W,
-                                            k->has_ep ? &k->ep : NULL);
-    if (cv->groups > 1) /* one kernel, no tile candidates: every candidate times the same launch */
-        return rn_conv2d_grouped_nhwc_forward_dt(run, m->dtype, m->dtype, k->x, k->y, cv->packed, cv->k, cv->stride,
-                                                 k->pad, ho, wo, k->B, cv->cin, cv->cout, k->H, k->W, cv->groups,
-                                                 k->has_ep ? &k->ep : NULL);
-    return rn_conv2d_nhwc_forward_dt(run, m->dtype, m->dtype, k->x, k->y, cv->packed, cv->k, cv->stride,
-                                     k->pad, ho, wo, k->B, cv->cin, cv->cout, k->H, k->W,
-                                     k->has_ep ? &k->ep : NULL);
-}
 
 /* time every tile candidate of every contraction of a forward of B images (one launch batch);
  * the winners go to slot `slot` of the layers' tile tables */
@@ -1493,7 +1438,7 @@ static int tune_at(rn_model *m, const float *input_nchw, uint64_t B, float *logi
                 float t = 0.f;
                 rn_ctx_set_conv_tile(m->ctx, c);
                 st = rn_event_record(m->ctx, e0);
-                if (st == RN_OK) st = replay_call(m, m->ctx, k);
+                if (st == RN_OK) st = launch_call(m, m->ctx, k);
                 if (st == RN_OK) st = rn_event_record(m->ctx, e1);
                 if (st == RN_OK) st = rn_event_elapsed_ms(e0, e1, &t);
                 if (r > 0 && t < cand_ms[c]) cand_ms[c] = t;

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "rn_internal.h"
+#include "rn_private.h"
 #include "rn_resize.h"
 
 struct rn_graph {
@@ -49,16 +50,6 @@ struct rn_pipeline {
 };
 
 extern "C" {
-
-// the model keeps its context private; the pipeline needs it for the compute stream
-rn_ctx *rn_model_context(rn_model *m);
-
-int rn_model_profiling_enabled(const rn_model *m);
-// the contexts the model has queued batch parts on so far (rn_model.c)
-int rn_model_contexts(rn_model *m, rn_ctx **out, int cap);
-void rn_model_graph_ref(rn_model *m, int delta);
-int rn_model_forward_images_table(rn_model *m, const uint8_t *packed_dev, const void *table_dev, uint64_t B,
-                                  double src_bytes, float *logits, int mode);
 
 int rn_graph_destroy(rn_graph *g)
 {

@@ -1,0 +1,40 @@
+/* rn_private.h -- library-internal functions that cross the C / HIP boundary (plain C).
+ *
+ * None of them is part of the C-ABI of rn_hip.h and none is exported.  Both the file that
+ * defines a function and the files that call it include this header, so a signature that
+ * drifts fails to compile instead of linking and misbehaving. */
+#ifndef RN_PRIVATE_H
+#define RN_PRIVATE_H
+
+#include "rn_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ---- rn_ctx.hip: rn_model.c is plain C and sees the context only through functions ---- */
+int rn_ctx_graphs_live(const rn_ctx *ctx);
+/* everything queued on ctx's stream after this call waits for the event (the stream, not the host) */
+int rn_ctx_wait_event(rn_ctx *ctx, rn_event *ev);
+int rn_ctx_scratch_slot(rn_ctx *ctx, int slot, uint64_t bytes, void **ptr);
+int rn_ctx_is_capturing(rn_ctx *ctx);
+/* pageable host memory -> device on the context's stream, over when the call returns */
+int rn_ctx_upload_sync(rn_ctx *ctx, void *dev, const void *host, uint64_t bytes);
+
+/* ---- rn_model.c: what the pipeline and the graph capture (rn_pipeline.hip) need of a model ---- */
+/* the model keeps its context private; the pipeline queues on its compute stream */
+rn_ctx *rn_model_context(rn_model *m);
+int rn_model_profiling_enabled(const rn_model *m);
+/* every context the model has queued batch parts on so far; returns how many were written to out */
+int rn_model_contexts(rn_model *m, rn_ctx **out, int cap);
+/* rn_model_capture / rn_graph_destroy count the graphs that hold the model */
+void rn_model_graph_ref(rn_model *m, int delta);
+/* decoded images whose resize tables are on the device already */
+int rn_model_forward_images_table(rn_model *m, const uint8_t *packed_dev, const void *table_dev, uint64_t B,
+                                  double src_bytes, float *logits, int mode);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* RN_PRIVATE_H */
