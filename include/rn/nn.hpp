@@ -192,4 +192,27 @@ inline void addForward(FloatTensor &a, FloatTensor &b, FloatTensor &out)
     addForwardKernel(a.raw(), b.raw(), out.raw(), a.numel());
 }
 
+// softmax / top-k of logits [B, classes] (rn_softmax_forward, rn_topk_forward, rn_softmax_topk_forward).  data()
+// observes the tensors: what was recorded for them runs first.  indices: B * k device uint64_t.
+inline void softmax(FloatTensor &logits, FloatTensor &probs)
+{
+    rn::require(logits.shape().size() == 2 && logits.shape() == probs.shape());
+    softmaxForwardKernel(logits.data(), probs.data(), logits.shape()[0], logits.shape()[1]);
+}
+
+inline void topk(FloatTensor &x, FloatTensor &values, uint64_t *indices, uint64_t k)
+{
+    rn::require(x.shape().size() == 2 && values.numel() == x.shape()[0] * k);
+    topkForwardKernel(x.data(), values.data(), indices, x.shape()[0], x.shape()[1], k);
+}
+
+inline void softmax_topk(FloatTensor &logits, FloatTensor *probs /* nullable */, FloatTensor &topk_prob,
+                         uint64_t *topk_idx, uint64_t k)
+{
+    rn::require(logits.shape().size() == 2 && topk_prob.numel() == logits.shape()[0] * k &&
+                (!probs || probs->shape() == logits.shape()));
+    softmaxTopkForwardKernel(logits.data(), probs ? probs->data() : nullptr, topk_prob.data(), topk_idx,
+                             logits.shape()[0], logits.shape()[1], k);
+}
+
 #endif  // RN_NN_HPP

@@ -62,4 +62,24 @@ inline void addForwardKernel(float *inp1, float *inp2, float *out, uint64_t N)
     gpuErrchk(rn_add_forward(rn::context(), inp1, inp2, out, N));
 }
 
+// ---- the head behind the logits (not in the reference: its main() takes a host argmax) ----
+// fp32 rows [B, classes]; the order, the shared probability expression and the limits are stated beside the
+// prototypes in rn_hip.h
+inline void softmaxForwardKernel(const float *logits, float *probs, uint64_t B, uint64_t classes)
+{
+    gpuErrchk(rn_softmax_forward(rn::context(), logits, probs, B, classes));
+}
+
+inline void topkForwardKernel(const float *x, float *values, uint64_t *indices, uint64_t B, uint64_t classes,
+                              uint64_t k)
+{
+    gpuErrchk(rn_topk_forward(rn::context(), x, values, indices, B, classes, k));
+}
+
+inline void softmaxTopkForwardKernel(const float *logits, float *probs /* nullable */, float *topk_prob,
+                                     uint64_t *topk_idx, uint64_t B, uint64_t classes, uint64_t k)
+{
+    gpuErrchk(rn_softmax_topk_forward(rn::context(), logits, probs, topk_prob, topk_idx, B, classes, k));
+}
+
 #endif  // RN_OPS_HPP

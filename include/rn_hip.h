@@ -270,6 +270,36 @@ RN_API int rn_add_forward(rn_ctx *ctx, const float *inp1, const float *inp2, flo
 RN_API int rn_argmax_forward(rn_ctx *ctx, const float *logits, uint64_t *idx, uint64_t B,
                              uint64_t classes);
 
+/* ---- the head behind the logits: softmax, top-k, both from one read (rn_head.hip) ----------------
+ * fp32 rows [B, classes].  Float operands on any 4-byte boundary, uint64_t operands on an 8-byte boundary
+ * (as rn_argmax_forward's idx); asynchronous on the context's stream, one launch each, counted by
+ * rn_ctx_launch_count.  B == 0: RN_OK, nothing launched.  A null operand (probs of the fused call may be
+ * NULL), an operand off its boundary, classes outside 1..65536 or k outside 1..min(classes, 64):
+ * RN_ERR_INVALID, nothing launched, rn_last_error names the argument.
+ *   Order.  (v_i, i) precedes (v_j, j) when v_i > v_j, or when v_i == v_j and i < j: a total order (-0.0 ==
+ *     +0.0: the lower index first), so the result depends on neither B, the row's place in the batch, the
+ *     alignment nor the launch.  Top-k is np.argsort(-x, kind="stable")[:k]; for finite rows k = 1 gives
+ *     rn_argmax_forward's index.  A NaN ranks as -inf (argmax_kernel's rule; its value is returned as it
+ *     is).  rn_argmax_forward's exception -- a NaN at index 0 is never displaced -- is taken for k = 1
+ *     only: with k > 1 a NaN at index 0 ranks as -inf like any other.
+ *   Probabilities.  p = expf(x - max) / sum, sum over expf(x - max) of the row: one max, one summation
+ *     order (fixed by the kernel's block of 256 threads, nothing else) and one correctly rounded division
+ *     in all three entry points, so rn_softmax_topk_forward's topk_prob[j] is bit for bit
+ *     probs[topk_idx[j]] and what rn_softmax_forward writes there.  -inf entries (masked classes) give
+ *     exactly 0; a row whose maximum is +inf and a row of -inf only give NaN, as torch does.
+ *   The fused call ranks BY LOGIT, not by probability: exp is monotone but rounds, two distinct logits can
+ *     share a probability; topk_idx is rn_topk_forward(logits)'s, bit for bit.
+ *   One block per row; a row of up to 4096 classes is read from memory once (it lives in LDS), a longer
+ *     one once per pass (maximum, sum, each top-k round, probabilities).  probs may alias logits. */
+/* probs[b][c] = exp(x[b][c] - max_b) / sum_c exp(x[b][c] - max_b) */
+RN_API int rn_softmax_forward(rn_ctx *ctx, const float *logits, float *probs, uint64_t B, uint64_t classes);
+/* the k largest of each row, descending; equal values in ascending index order: values / indices [B, k] */
+RN_API int rn_topk_forward(rn_ctx *ctx, const float *x, float *values, uint64_t *indices, uint64_t B,
+                           uint64_t classes, uint64_t k);
+/* one launch: probs (nullable, [B, classes]) and the k best classes ordered by logit with their probabilities */
+RN_API int rn_softmax_topk_forward(rn_ctx *ctx, const float *logits, float *probs /* nullable */, float *topk_prob,
+                                   uint64_t *topk_idx, uint64_t B, uint64_t classes, uint64_t k);
+
 /* ---- layout converters and weight packing -------------------------------- */
 RN_API int rn_nchw_to_nhwc(rn_ctx *ctx, const float *src, float *dst, uint64_t B, uint64_t C,
                            uint64_t H, uint64_t W);
@@ -467,6 +497,21 @@ RN_API int rn_model_create(rn_ctx *ctx, rn_model **out, int arch);
  * carries (groups, width_per_group): a table is refused by a model of another family. */
 RN_API int rn_model_create_ex(rn_ctx *ctx, rn_model **out, int depth, int groups, int width_per_group);
 RN_API int rn_model_destroy(rn_model *m);
+/* Rows of the classifier: 1..65536, default 1000 (a fine-tuned checkpoint has fc.weight [classes, features]).
+ * Legal until the first rn_model_set_tensor, rn_model_load_dir or rn_model_finalize; after any of those, and
+ * for a count out of range, RN_ERR_INVALID and nothing changes.  It re-sizes the fc.weight / fc.bias entries
+ * of the layer table (rn_model_tensor_key reports the new numel); the packed classifier panel, the logits
+ * strides of every forward entry point (rn_model_forward, _u8, _images_u8, _outputs, rn_model_tune,
+ * rn_model_capture, rn_pipeline_*) and the profile record follow it.  Tuning tables do not carry it: the
+ * classifier launch is not in them, and every tile candidate is valid for any out_channels.
+ * A count that is no multiple of 4 puts the logits rows of later sub-batches or parts off a 16-byte
+ * boundary, where the contraction cannot write them.  fp32 models then run the classifier of EVERY launch
+ * on the direct kernel (one thread per logit, the reference's summation order): correct, slow, and an
+ * image's logits stay independent of the part it runs in.  bf16 models refuse such a count at
+ * rn_model_finalize (RN_ERR_UNSUPPORTED).  rn_shard_* creates its own models and stays at 1000. */
+RN_API int rn_model_set_classes(rn_model *m, uint64_t classes);
+RN_API uint64_t rn_model_classes(const rn_model *m);
+RN_API uint64_t rn_model_features(const rn_model *m); /* 512 (ResNet-18/34) or 2048 */
 /* state_dict key -> host data; numel must match the layer table. */
 RN_API int rn_model_set_tensor(rn_model *m, const char *key, const float *host_data,
                                uint64_t numel);
@@ -480,14 +525,15 @@ RN_API int rn_model_set_dtype(rn_model *m, int dtype);
 RN_API int rn_model_finalize(rn_model *m);
 /* names of the tensors the loader expects, one per call; returns NULL past the end */
 RN_API const char *rn_model_tensor_key(const rn_model *m, uint64_t index, uint64_t *numel);
-/* input: device NCHW [B,3,224,224]; logits: device [B,1000]. Asynchronous on the stream.
+/* input: device NCHW [B,3,224,224]; logits: device [B,classes]. Asynchronous on the stream.
  *
  * Fixed geometry of the model driver (the op entry points above are general; the driver, like
  * the reference's -- main.cu:230 hard-codes {1, 3, 224, 224} -- is not):
  *   - images are 3 x 224 x 224 fp32, NCHW; there is no size argument, so a buffer of another
  *     geometry cannot be expressed: callers that read files check the element count first
  *     (rn_infer does and reports RN_ERR_UNSUPPORTED's text for anything but B*3*224*224 floats);
- *   - 1000 classes, bottleneck depths 50 / 101 / 152, basic-block depths 18 / 34;
+ *   - bottleneck depths 50 / 101 / 152, basic-block depths 18 / 34; the class count is NOT fixed
+ *     (rn_model_set_classes, default 1000), the 224 x 224 image is;
  *   - any B >= 1: the kernels address a tensor with 32-bit byte offsets (2^29 fp32 elements; the
  *     stem output of 669 images is the first to pass it), so a batch runs as sub-batches of at
  *     most 512 images through the same arenas, each as `streams` parts (rn_model_set_streams);
@@ -519,6 +565,28 @@ RN_API int rn_model_forward_u8(rn_model *m, const uint8_t *input_nhwc, uint64_t 
 RN_API int rn_model_forward_images_u8(rn_model *m, const uint8_t *packed_dev, const uint64_t *offsets,
                                       const uint64_t *heights, const uint64_t *widths, uint64_t B,
                                       float *logits, int mode);
+/* More than the logits from one forward.  Device pointers; any may be NULL; zero-initialise the struct. */
+typedef struct rn_model_outputs {
+    float *logits;       /* [B, classes]: bit for bit what rn_model_forward writes */
+    float *features;     /* [B, features] fp32: the pooled values the classifier reads */
+    float *probs;        /* [B, classes]: rn_softmax_forward of the logits */
+    float *topk_prob;    /* [B, k] */
+    uint64_t *topk_idx;  /* [B, k]: ordered by logit (rn_softmax_topk_forward) */
+    uint64_t k;          /* 0 = no top-k; otherwise 1..min(classes, 64) with both topk pointers set */
+} rn_model_outputs;
+/* Exactly the launches of rn_model_forward / rn_model_forward_u8 -- same sub-batches (<= 512 images), streams
+ * and profile records -- and behind each sub-batch, on the model's own stream: the features (fp32 models: a
+ * device-to-device copy out of the pooled arena; bf16 models: the bf16 values widened to fp32, exact; op
+ * "features" of layer "head"), then at most one rn_softmax_topk_forward (op "softmax_topk"), or
+ * rn_softmax_forward when k == 0 (op "softmax").  With logits == NULL the logits of a sub-batch go to a
+ * buffer the model owns ([min(B, 512), classes] of the largest call seen, grown on first use like the
+ * arenas: RN_ERR_INVALID while a captured graph of the context lives, RN_ERR_UNSUPPORTED on a stream that
+ * is being captured).  Nothing to write (every pointer NULL and k == 0), or k > 0 without both topk
+ * pointers or out of range: RN_ERR_INVALID.  Both forward modes. */
+RN_API int rn_model_forward_outputs(rn_model *m, const float *input_nchw, uint64_t B,
+                                    const rn_model_outputs *outs, int mode);
+RN_API int rn_model_forward_outputs_u8(rn_model *m, const uint8_t *input_nhwc, uint64_t B,
+                                       const rn_model_outputs *outs, int mode);
 /* Run one forward, then time every tile candidate of every convolution at batch B on the
  * device (events on the context's stream, on the buffers that forward used) and remember the fastest per layer for
  * that batch size.  Results do not change (candidates are bit-identical), only speed. */
@@ -712,11 +780,12 @@ RN_API int rn_pipeline_input_buffer(rn_pipeline *p, float **host_staging);
  * NULL / the pointer rn_pipeline_input_buffer returned when the staging buffer is already
  * filled. */
 RN_API int rn_pipeline_submit(rn_pipeline *p, const float *host_input_nchw);
-/* host_logits: B*1000 floats.  RN_ERR_INVALID when nothing is in flight. */
+/* host_logits: B*classes floats (rn_model_classes of the model when the pipeline was created).
+ * RN_ERR_INVALID when nothing is in flight. */
 RN_API int rn_pipeline_collect(rn_pipeline *p, float *host_logits);
 RN_API uint64_t rn_pipeline_in_flight(const rn_pipeline *p);
 /* The same for a batch of n <= B images (a ragged last batch), and with the class indices
- * (first maximum wins, main.cu:243-249) next to the logits; host_logits ([n,1000]), host_top1
+ * (first maximum wins, main.cu:243-249) next to the logits; host_logits ([n,classes]), host_top1
  * ([n]) and n may each be NULL. */
 RN_API int rn_pipeline_submit_n(rn_pipeline *p, const float *host_input_nchw, uint64_t n);
 RN_API int rn_pipeline_collect_n(rn_pipeline *p, float *host_logits, uint64_t *host_top1, uint64_t *n);

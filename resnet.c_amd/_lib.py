@@ -29,6 +29,12 @@ class ConvSecond(ctypes.Structure):
                 ("stride", c_uint64)]
 
 
+class ModelOutputs(ctypes.Structure):
+    """rn_model_outputs: device pointers, any may be NULL; k = 0 means no top-k."""
+    _fields_ = [("logits", c_void_p), ("features", c_void_p), ("probs", c_void_p), ("topk_prob", c_void_p),
+                ("topk_idx", c_void_p), ("k", c_uint64)]
+
+
 class Epilogue(ctypes.Structure):
     _fields_ = [("scale", c_void_p), ("shift", c_void_p), ("residual", c_void_p),
                 ("relu", c_int)]
@@ -84,6 +90,9 @@ SIGNATURES = {
     "rn_batchnorm2d_forward": (c_int, [c_void_p] + [fptr] * 6 + [u64] * 3),
     "rn_add_forward": (c_int, [c_void_p, fptr, fptr, fptr, u64]),
     "rn_argmax_forward": (c_int, [c_void_p, fptr, c_void_p, u64, u64]),
+    "rn_softmax_forward": (c_int, [c_void_p, fptr, fptr, u64, u64]),
+    "rn_topk_forward": (c_int, [c_void_p, fptr, fptr, c_void_p, u64, u64, u64]),
+    "rn_softmax_topk_forward": (c_int, [c_void_p, fptr, fptr, fptr, c_void_p, u64, u64, u64]),
     "rn_nchw_to_nhwc": (c_int, [c_void_p, fptr, fptr] + [u64] * 4),
     "rn_nhwc_to_nchw": (c_int, [c_void_p, fptr, fptr] + [u64] * 4),
     "rn_conv2d_input_channels": (u64, [u64]),
@@ -141,6 +150,11 @@ SIGNATURES = {
     "rn_model_create": (c_int, [c_void_p, POINTER(c_void_p), c_int]),
     "rn_model_create_ex": (c_int, [c_void_p, POINTER(c_void_p), c_int, c_int, c_int]),
     "rn_model_set_dtype": (c_int, [c_void_p, c_int]),
+    "rn_model_set_classes": (c_int, [c_void_p, u64]),
+    "rn_model_classes": (u64, [c_void_p]),
+    "rn_model_features": (u64, [c_void_p]),
+    "rn_model_forward_outputs": (c_int, [c_void_p, fptr, u64, POINTER(ModelOutputs), c_int]),
+    "rn_model_forward_outputs_u8": (c_int, [c_void_p, c_void_p, u64, POINTER(ModelOutputs), c_int]),
     "rn_model_destroy": (c_int, [c_void_p]),
     "rn_model_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, u64]),
     "rn_model_load_dir": (c_int, [c_void_p, c_char_p]),

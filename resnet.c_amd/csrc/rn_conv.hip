@@ -58,6 +58,7 @@
 #include <type_traits>
 
 #include "rn_conv_params.h"
+#include "rn_private.h"
 
 bool rn_conv_is_c4(uint64_t Cin, uint64_t k);
 
@@ -1587,6 +1588,25 @@ int rn_linear_forward(rn_ctx *ctx, const float *inp, float *out, const float *we
     }
     return launch_direct(ctx, inp, out, weight, 1, 1, 0, 1, 1, B, in_features, in_features,
                          out_features, 1, 1, 1, 0, &ep, "rn_linear_forward(direct)");
+}
+
+// library-internal (rn_private.h): rn_linear_forward through the direct kernel whatever the alignment.  The
+// model's classifier takes it when the class count is no multiple of 4: the logits rows of a later batch
+// part then start off a 16-byte boundary, where rn_linear_forward would change kernels (and summation
+// order) between the parts of one batch.
+int rn_linear_direct_forward(rn_ctx *ctx, const float *inp, float *out, const float *weight, const float *bias,
+                             uint64_t B, uint64_t in_features, uint64_t out_features)
+{
+    RN_ENTER(ctx);
+    if (B * out_features == 0) return RN_OK;
+    RN_REQUIRE(ctx, inp && out && weight && inp != out, "null or aliased tensor");
+    RN_REQUIRE(ctx, in_features >= 1, "in_features must be >= 1");
+    RN_REQUIRE(ctx, fits_i32(B * in_features) && fits_i32(B * out_features) &&
+                        fits_i32(out_features * in_features + 64),
+               "tensor has 2^31 or more elements");
+    rn_epilogue ep = {nullptr, bias, nullptr, 0};
+    return launch_direct(ctx, inp, out, weight, 1, 1, 0, 1, 1, B, in_features, in_features, out_features, 1, 1, 1, 0,
+                         &ep, "rn_linear_direct_forward");
 }
 
 }  // extern "C"

@@ -127,7 +127,9 @@ int main(int argc, char **argv)
 {
     int arch = 152, device = 0, mode = RN_FWD_FUSED, dtype = RN_DTYPE_F32, u8 = 0, i;
     int devices[64], ndev = 0;
-    uint64_t B = 1, numel = 0, b, rgb_h = 0, rgb_w = 0;
+    uint64_t B = 1, numel = 0, b, rgb_h = 0, rgb_w = 0, classes = 0, topk = 0, j;
+    float *top_prob_dev = NULL, *top_prob = NULL;
+    uint64_t *top_idx_dev = NULL, *top_idx = NULL;
     int rgb = 0;
     const char *weights = "weights_bin";
     const char *input = "test_bins/ILSVRC2012_val_00004749.bin";
@@ -156,6 +158,8 @@ int main(int argc, char **argv)
             ++i;
         }
         else if (!strcmp(a, "--batch") && v) { B = strtoull(v, NULL, 10); ++i; }
+        else if (!strcmp(a, "--classes") && v) { classes = strtoull(v, NULL, 10); ++i; }
+        else if (!strcmp(a, "--topk") && v) { topk = strtoull(v, NULL, 10); ++i; }
         else if (!strcmp(a, "--device") && v) { device = atoi(v); ++i; }
         else if (!strcmp(a, "--devices") && v) {
             const char *q = v;
@@ -168,7 +172,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--mode") && v) { mode = strcmp(v, "ops") ? RN_FWD_FUSED : RN_FWD_REFERENCE_OPS; ++i; }
         else {
             fprintf(stderr, "usage: %s [--arch 18|34|50|101|152|resnext50_32x4d|resnext101_32x8d|resnext101_64x4d|wide_resnet50_2|wide_resnet101_2] [--weights DIR] [--input FILE | --u8 FILE | --rgb FILE --hw H,W] "
-                            "[--batch B] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,...]\n",
+                            "[--batch B] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,...] [--classes N] [--topk K]\n",
                     argv[0]);
             return 2;
         }
@@ -179,9 +183,16 @@ int main(int argc, char **argv)
                 rn_status_string(RN_ERR_UNSUPPORTED));
         return 1;
     }
+    if (ndev > 0 && (classes || topk)) {
+        fprintf(stderr, "rn_infer: %s: --classes and --topk run on one device (--devices keeps 1000 classes)\n",
+                rn_status_string(RN_ERR_UNSUPPORTED));
+        return 1;
+    }
     if (ndev > 0) return run_sharded(devices, ndev, arch, weights, input, u8, B, mode, dtype);
     CHECK(ctx, rn_ctx_create(&ctx, device, NULL));
     CHECK(ctx, groups_g ? rn_model_create_ex(ctx, &model, arch, groups_g, wpg_g) : rn_model_create(ctx, &model, arch));
+    if (classes) CHECK(ctx, rn_model_set_classes(model, classes)); /* before the weights: fc.* take its size */
+    classes = rn_model_classes(model);
     CHECK(ctx, rn_model_load_dir(model, weights));
     if (dtype != RN_DTYPE_F32) CHECK(ctx, rn_model_set_dtype(model, dtype));
     CHECK(ctx, rn_model_finalize(model));
@@ -217,7 +228,7 @@ int main(int argc, char **argv)
                 (unsigned long long)B);
         return 1;
     }
-    CHECK(ctx, rn_malloc(ctx, (void **)&logits, B * 1000 * sizeof(float)));
+    CHECK(ctx, rn_malloc(ctx, (void **)&logits, B * classes * sizeof(float)));
     CHECK(ctx, rn_malloc(ctx, (void **)&idx_dev, B * sizeof(uint64_t)));
     if (rgb) {
         const uint64_t zero = 0;
@@ -226,14 +237,33 @@ int main(int argc, char **argv)
         CHECK(ctx, rn_model_forward_u8(model, inp_u8, B, logits, mode));
     else
         CHECK(ctx, rn_model_forward(model, inp, B, logits, mode));
-    CHECK(ctx, rn_argmax_forward(ctx, logits, idx_dev, B, 1000));
+    CHECK(ctx, rn_argmax_forward(ctx, logits, idx_dev, B, classes));
     idx = (uint64_t *)malloc(B * sizeof(uint64_t));
     if (!idx) return 1;
     CHECK(ctx, rn_memcpy_d2h(ctx, idx, idx_dev, B * sizeof(uint64_t)));
+    if (topk) { /* the K best classes by logit with their probabilities, one launch */
+        CHECK(ctx, rn_malloc(ctx, (void **)&top_prob_dev, B * topk * sizeof(float)));
+        CHECK(ctx, rn_malloc(ctx, (void **)&top_idx_dev, B * topk * sizeof(uint64_t)));
+        CHECK(ctx, rn_softmax_topk_forward(ctx, logits, NULL, top_prob_dev, top_idx_dev, B, classes, topk));
+        top_prob = (float *)malloc(B * topk * sizeof(float));
+        top_idx = (uint64_t *)malloc(B * topk * sizeof(uint64_t));
+        if (!top_prob || !top_idx) return 1;
+        CHECK(ctx, rn_memcpy_d2h(ctx, top_prob, top_prob_dev, B * topk * sizeof(float)));
+        CHECK(ctx, rn_memcpy_d2h(ctx, top_idx, top_idx_dev, B * topk * sizeof(uint64_t)));
+    }
     printf("Finished\n");
-    for (b = 0; b < B; ++b) printf("max index is %llu\n", (unsigned long long)idx[b]);
+    for (b = 0; b < B; ++b) {
+        printf("max index is %llu\n", (unsigned long long)idx[b]);
+        for (j = 0; j < topk; ++j)
+            printf("top%llu %llu %.6f\n", (unsigned long long)(j + 1), (unsigned long long)top_idx[b * topk + j],
+                   (double)top_prob[b * topk + j]);
+    }
 
     free(idx);
+    free(top_prob);
+    free(top_idx);
+    rn_free(ctx, top_prob_dev);
+    rn_free(ctx, top_idx_dev);
     rn_free(ctx, idx_dev);
     rn_free(ctx, logits);
     rn_free(ctx, inp);

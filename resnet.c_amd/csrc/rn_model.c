@@ -31,12 +31,13 @@
 #include "rn_private.h"
 
 #define RN_MAX_KEY 96
-/* the fixed geometry: 224 x 224 RGB images, a 64-channel stem, 1000 classes */
+/* the fixed geometry: 224 x 224 RGB images, a 64-channel stem; the class count is a field of the model */
 #define RN_IMAGE_SIDE 224
 #define RN_IMAGE_NUMEL (3 * RN_IMAGE_SIDE * RN_IMAGE_SIDE)
 #define RN_RESIZE_SIDE 256 /* decoded images: the shorter side before the centre crop */
 #define RN_STEM_WIDTH 64
-#define RN_CLASSES 1000
+#define RN_DEFAULT_CLASSES 1000
+#define RN_MAX_CLASSES 65536
 
 #define RN_MAX_STREAMS 4
 
@@ -110,6 +111,10 @@ struct rn_model {
     int basic;        /* ResNet-18/34: basic blocks (two 3x3 convolutions, expansion 1) */
     int depths[4];
     uint64_t feat;    /* width of the final feature map: 2048 (bottleneck) or 512 (basic) */
+    uint64_t classes; /* rows of fc.weight: 1000 unless rn_model_set_classes said otherwise */
+    int classes_locked; /* a tensor was set, a directory loaded or the model finalized: the count stays */
+    float *own_logits;  /* [own_logits_cap, classes]: where rn_model_forward_outputs keeps logits nobody asked for */
+    uint64_t own_logits_cap;
     uint64_t stem_side, pool_side; /* the stem's output (112) and the max-pool's (56), which the first stage keeps */
     /* per-image element counts of the arenas (ensure_acts) */
     uint64_t x4_img, p_img, ds_img, t1_img, t2_img;
@@ -327,8 +332,9 @@ static int model_create(rn_ctx *ctx, rn_model **out, int arch, int groups, int w
             b->conv3 = b->tail = add_conv(m, name, bn, mid, cout, 1, 1, 0);
         }
     }
-    m->fc_w = add_param(m, "fc.weight", (uint64_t)RN_CLASSES * m->feat);
-    m->fc_b = add_param(m, "fc.bias", RN_CLASSES);
+    m->classes = RN_DEFAULT_CLASSES;
+    m->fc_w = add_param(m, "fc.weight", m->classes * m->feat);
+    m->fc_b = add_param(m, "fc.bias", m->classes);
     *out = m;
     return RN_OK;
 }
@@ -346,6 +352,18 @@ int rn_model_create_ex(rn_ctx *ctx, rn_model **out, int depth, int groups, int w
     if (!ok || (depth != 50 && depth != 101 && depth != 152)) return RN_ERR_UNSUPPORTED;
     return model_create(ctx, out, depth, groups, width_per_group);
 }
+
+int rn_model_set_classes(rn_model *m, uint64_t classes)
+{
+    if (!m || m->classes_locked || classes < 1 || classes > RN_MAX_CLASSES) return RN_ERR_INVALID;
+    m->classes = classes;
+    m->params[m->fc_w].numel = classes * m->feat;
+    m->params[m->fc_b].numel = classes;
+    return RN_OK;
+}
+
+uint64_t rn_model_classes(const rn_model *m) { return m ? m->classes : 0; }
+uint64_t rn_model_features(const rn_model *m) { return m ? m->feat : 0; }
 
 static void free_acts(rn_model *m)
 {
@@ -402,6 +420,7 @@ int rn_model_destroy(rn_model *m)
     rn_free(m->ctx, m->stem_packed_exact);
     rn_free(m->ctx, m->stem_pool_packed);
     if (m->crops) rn_free(m->ctx, m->crops);
+    if (m->own_logits) rn_free(m->ctx, m->own_logits);
     free_acts(m);
     free_prof(m);
     {
@@ -437,6 +456,7 @@ int rn_model_set_tensor(rn_model *m, const char *key, const float *host_data, ui
         rn_param *p = &m->params[i];
         if (strcmp(p->key, key) != 0) continue;
         if (p->numel != numel) return RN_ERR_INVALID;
+        m->classes_locked = 1;
         if (!p->dev) {
             int st = rn_malloc(m->ctx, (void **)&p->dev, numel * sizeof(float));
             if (st != RN_OK) return st;
@@ -452,6 +472,7 @@ int rn_model_load_dir(rn_model *m, const char *weights_dir)
 {
     uint64_t i;
     if (!m || !weights_dir) return RN_ERR_INVALID;
+    m->classes_locked = 1;
     for (i = 0; i < m->n_params; ++i) {
         rn_param *p = &m->params[i];
         char path[1024];
@@ -508,9 +529,13 @@ int rn_model_finalize(rn_model *m)
     uint64_t i;
     int c, st;
     if (!m) return RN_ERR_INVALID;
+    m->classes_locked = 1;
     for (i = 0; i < m->n_params; ++i) {
         if (!m->params[i].is_set) return RN_ERR_INVALID;
     }
+    /* the bf16 classifier is the bf16 contraction, which refuses logits rows off a 16-byte boundary: those
+     * of the later parts of a batch when the class count is no multiple of 4 */
+    if (m->dtype != RN_DTYPE_F32 && m->classes % 4 != 0) return RN_ERR_UNSUPPORTED;
     for (c = 0; c < m->n_convs; ++c) {
         rn_conv *cv = &m->convs[c];
         const uint64_t pn = cv->groups > 1 ? rn_conv2d_grouped_packed_weight_numel_dt(m->dtype, cv->cin, cv->cout,
@@ -581,13 +606,13 @@ int rn_model_finalize(rn_model *m)
         if (st != RN_OK) return st;
     }
     if (m->dtype != RN_DTYPE_F32) {
-        /* fc.weight [1000][feat] is a 1x1 convolution panel: same packer, k = 1 */
+        /* fc.weight [classes][feat] is a 1x1 convolution panel: same packer, k = 1 */
         if (!m->fc_packed) {
-            st = rn_malloc(m->ctx, &m->fc_packed, (uint64_t)RN_CLASSES * m->feat * elem_size(m));
+            st = rn_malloc(m->ctx, &m->fc_packed, m->classes * m->feat * elem_size(m));
             if (st != RN_OK) return st;
         }
         st = rn_conv2d_pack_weight_dt(m->ctx, m->dtype, m->params[m->fc_w].dev, m->fc_packed, m->feat,
-                                      RN_CLASSES, 1);
+                                      m->classes, 1);
         if (st != RN_OK) return st;
     }
     st = rn_sync(m->ctx);
@@ -1170,17 +1195,23 @@ static int run_head(rn_model *m, const float *x, uint64_t B, uint64_t side, floa
                                      rn_conv_output_size(side, side, 1, 0), rn_conv_output_size(side, side, 1, 0), B,
                                      m->feat, side, side));
     TRY(prof_end(m));
-    TRY(prof_begin(m, "linear", "fc", 2.0 * (double)B * (double)m->feat * RN_CLASSES,
-                   es * ((double)(B * m->feat) + (double)m->feat * RN_CLASSES) +
-                       4.0 * (RN_CLASSES + (double)B * RN_CLASSES)));
+    TRY(prof_begin(m, "linear", "fc", 2.0 * (double)B * (double)m->feat * (double)m->classes,
+                   es * ((double)(B * m->feat) + (double)m->feat * (double)m->classes) +
+                       4.0 * ((double)m->classes + (double)B * (double)m->classes)));
     if (m->dtype == RN_DTYPE_BF16) {
         rn_epilogue ep;
         ep.scale = NULL; ep.shift = m->params[m->fc_b].dev; ep.residual = NULL; ep.relu = 0;
         TRY(rn_conv2d_nhwc_forward_dt(m->run.ctx, m->dtype, RN_DTYPE_F32, m->run.pooled, logits, m->fc_packed, 1, 1, 0,
-                                      1, 1, B, m->feat, RN_CLASSES, 1, 1, &ep));
+                                      1, 1, B, m->feat, m->classes, 1, 1, &ep));
+    } else if (m->classes % 4 != 0) {
+        /* the rows of a later part or sub-batch start off a 16-byte boundary, where rn_linear_forward takes the
+         * direct kernel: every launch of this layer takes it, so that an image's logits do not depend on the
+         * part it runs in */
+        TRY(rn_linear_direct_forward(m->run.ctx, m->run.pooled, logits, m->params[m->fc_w].dev,
+                                     m->params[m->fc_b].dev, B, m->feat, m->classes));
     } else {
         TRY(rn_linear_forward(m->run.ctx, m->run.pooled, logits, m->params[m->fc_w].dev, m->params[m->fc_b].dev, B,
-                              m->feat, RN_CLASSES));
+                              m->feat, m->classes));
     }
     return prof_end(m);
 }
@@ -1304,12 +1335,42 @@ static int forward_chunk(rn_model *m, const void *input, int in_u8, uint64_t B, 
         const uint64_t hi = B * (uint64_t)(i + 1) / (uint64_t)parts;
         rn_ctx *run = i == 0 ? m->ctx : m->ctxn[i - 1];
         if (i > 0) TRY(rn_ctx_wait_event(run, m->ev_fork));
-        TRY(forward_part(m, run, lo, input_at(input, in_u8, lo), in_u8, hi - lo, logits + lo * RN_CLASSES,
+        TRY(forward_part(m, run, lo, input_at(input, in_u8, lo), in_u8, hi - lo, logits + lo * m->classes,
                          mode));
         if (i > 0) TRY(rn_event_record(run, m->ev_join[i - 1]));
         lo = hi;
     }
     for (i = 0; i < parts - 1; ++i) TRY(rn_ctx_wait_event(m->ctx, m->ev_join[i]));
+    return RN_OK;
+}
+
+/* What rn_model_forward_outputs adds behind the launches of a sub-batch of nb images (the caller's image
+ * `done` on), on the model's own stream, which every part has joined: the features out of `pooled`, then at
+ * most one launch of the head kernel on the sub-batch's logits. */
+static int head_outputs(rn_model *m, const rn_model_outputs *o, uint64_t done, uint64_t nb, const float *logits)
+{
+    const uint64_t C = m->classes;
+    m->run.ctx = m->ctx; /* the profile brackets of these launches */
+    if (o->features) {
+        float *dst = o->features + done * m->feat;
+        TRY(prof_begin(m, "features", "head", 0.0, (double)(nb * m->feat) * (double)(elem_size(m) + 4)));
+        if (m->dtype == RN_DTYPE_BF16)
+            TRY(rn_widen_bf16_forward(m->ctx, m->pooled, dst, nb * m->feat));
+        else
+            TRY(rn_memcpy_d2d(m->ctx, dst, m->pooled, nb * m->feat * sizeof(float)));
+        TRY(prof_end(m));
+    }
+    if (o->k > 0) {
+        const double bytes = 4.0 * (double)(nb * C) * (o->probs ? 2.0 : 1.0) + 12.0 * (double)(nb * o->k);
+        TRY(prof_begin(m, "softmax_topk", "head", 0.0, bytes));
+        TRY(rn_softmax_topk_forward(m->ctx, logits, o->probs ? o->probs + done * C : NULL, o->topk_prob + done * o->k,
+                                    o->topk_idx + done * o->k, nb, C, o->k));
+        TRY(prof_end(m));
+    } else if (o->probs) {
+        TRY(prof_begin(m, "softmax", "head", 0.0, 8.0 * (double)(nb * C)));
+        TRY(rn_softmax_forward(m->ctx, logits, o->probs + done * C, nb, C));
+        TRY(prof_end(m));
+    }
     return RN_OK;
 }
 
@@ -1320,23 +1381,48 @@ static int forward_chunk(rn_model *m, const void *input, int in_u8, uint64_t B, 
  * what else is in its launch (batch invariance, bit for bit), so the split changes nothing.
  * (RN_MAX_SUB_BATCH is defined above, next to the stream split.)
  * in_u8: the input is 8-bit RGB [B,224,224,3], not fp32 NCHW; prof_keep: see forward_chunk (the
- * first sub-batch only). */
-static int forward_any(rn_model *m, const void *input, int in_u8, uint64_t B, float *logits, int mode,
-                       int prof_keep)
+ * first sub-batch only).  outs (rn_model_forward_outputs, NULL otherwise): what to write besides the
+ * logits; with logits == NULL those of a sub-batch go to a buffer the model owns. */
+static int forward_outputs(rn_model *m, const void *input, int in_u8, uint64_t B, float *logits,
+                           const rn_model_outputs *outs, int mode, int prof_keep)
 {
     uint64_t done = 0;
-    if (!m || !input || !logits || B == 0) return RN_ERR_INVALID;
+    if (!m || !input || (!logits && !outs) || B == 0) return RN_ERR_INVALID;
     if (mode != RN_FWD_REFERENCE_OPS && mode != RN_FWD_FUSED) return RN_ERR_INVALID;
     if (!m->finalized) return RN_ERR_INVALID;
     /* bf16 storage exists only with the fused epilogues (no standalone bf16 bn/relu/add) */
     if (m->dtype != RN_DTYPE_F32 && mode != RN_FWD_FUSED) return RN_ERR_UNSUPPORTED;
+    if (outs) {
+        if (!logits && !outs->features && !outs->probs && outs->k == 0) return RN_ERR_INVALID;
+        if (outs->k > 0 && (!outs->topk_prob || !outs->topk_idx || outs->k > 64 || outs->k > m->classes))
+            return RN_ERR_INVALID;
+    }
+    if (!logits) {
+        const uint64_t need = B < RN_MAX_SUB_BATCH ? B : RN_MAX_SUB_BATCH;
+        if (need > m->own_logits_cap) { /* grows like the arenas: never under a capture or a live graph */
+            if (rn_ctx_is_capturing(m->ctx)) return RN_ERR_UNSUPPORTED;
+            if (m->own_logits_cap > 0 && rn_ctx_graphs_live(m->ctx) > 0) return RN_ERR_INVALID;
+            if (m->own_logits) TRY(rn_free(m->ctx, m->own_logits));
+            m->own_logits = NULL;
+            m->own_logits_cap = 0;
+            TRY(rn_malloc(m->ctx, (void **)&m->own_logits, need * m->classes * sizeof(float)));
+            m->own_logits_cap = need;
+        }
+    }
     while (done < B) {
         const uint64_t nb = B - done < RN_MAX_SUB_BATCH ? B - done : RN_MAX_SUB_BATCH;
-        TRY(forward_chunk(m, input_at(input, in_u8, done), in_u8, nb, logits + done * RN_CLASSES, mode,
-                          prof_keep && done == 0));
+        float *sub = logits ? logits + done * m->classes : m->own_logits;
+        TRY(forward_chunk(m, input_at(input, in_u8, done), in_u8, nb, sub, mode, prof_keep && done == 0));
+        if (outs) TRY(head_outputs(m, outs, done, nb, sub));
         done += nb;
     }
     return RN_OK;
+}
+
+static int forward_any(rn_model *m, const void *input, int in_u8, uint64_t B, float *logits, int mode,
+                       int prof_keep)
+{
+    return forward_outputs(m, input, in_u8, B, logits, NULL, mode, prof_keep);
 }
 
 int rn_model_forward(rn_model *m, const float *input_nchw, uint64_t B, float *logits, int mode)
@@ -1347,6 +1433,19 @@ int rn_model_forward(rn_model *m, const float *input_nchw, uint64_t B, float *lo
 int rn_model_forward_u8(rn_model *m, const uint8_t *input_nhwc, uint64_t B, float *logits, int mode)
 {
     return forward_any(m, input_nhwc, 1, B, logits, mode, 0);
+}
+
+int rn_model_forward_outputs(rn_model *m, const float *input_nchw, uint64_t B, const rn_model_outputs *outs, int mode)
+{
+    if (!outs) return RN_ERR_INVALID;
+    return forward_outputs(m, input_nchw, 0, B, outs->logits, outs, mode, 0);
+}
+
+int rn_model_forward_outputs_u8(rn_model *m, const uint8_t *input_nhwc, uint64_t B, const rn_model_outputs *outs,
+                                int mode)
+{
+    if (!outs) return RN_ERR_INVALID;
+    return forward_outputs(m, input_nhwc, 1, B, outs->logits, outs, mode, 0);
 }
 
 /* Decoded images whose tables are on the device already (the host pipeline stages them with the batch):

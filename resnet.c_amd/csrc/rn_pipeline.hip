@@ -37,6 +37,7 @@ struct rn_pipeline {
     rn_model *model;
     rn_ctx *ctx;
     uint64_t B;
+    uint64_t classes;  // the model's class count when the pipeline was created: the row length of d_out / h_out
     int mode;
     int u8;            // input format: 0 = fp32 NCHW, 1 = 8-bit RGB [B,224,224,3] (rn_pipeline_create_u8),
                        // 2 = decoded 8-bit RGB images of any size (rn_pipeline_create_images_u8)
@@ -158,6 +159,7 @@ static int pipeline_create(rn_model *m, rn_pipeline **out, uint64_t B, int mode,
     p->model = m;
     p->ctx = ctx;
     p->B = B;
+    p->classes = rn_model_classes(m);
     p->mode = mode;
     p->u8 = u8;
     p->img_bytes = (size_t)3 * 224 * 224 * (u8 ? sizeof(uint8_t) : sizeof(float));
@@ -173,7 +175,7 @@ static int pipeline_create(rn_model *m, rn_pipeline **out, uint64_t B, int mode,
     p->table_off = ((size_t)max_batch_bytes + 15) & ~(size_t)15;
     p->table_room = (size_t)B * (RN_RS_DESC * 4 + 12544) + (size_t)max_batch_bytes / 16 + 64;
     const size_t in_bytes = u8 == 2 ? p->table_off + p->table_room : (size_t)B * p->img_bytes;
-    const size_t out_bytes = (size_t)B * 1000 * sizeof(float);
+    const size_t out_bytes = (size_t)B * p->classes * sizeof(float);
     const size_t idx_bytes = (size_t)B * sizeof(uint64_t);
     hipError_t e = hipSetDevice(ctx->device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking);
@@ -321,8 +323,8 @@ static int submit_n(rn_pipeline *p, const void *host_input, uint64_t n, int u8, 
             RN_TRY(rn_model_forward_u8(p->model, (const uint8_t *)s->d_in, n, s->d_out, p->mode));
         else
             RN_TRY(rn_model_forward(p->model, (const float *)s->d_in, n, s->d_out, p->mode));
-        RN_TRY(rn_argmax_forward(ctx, s->d_out, s->d_idx, n, 1000));
-        RN_HIP_TRY(ctx, hipMemcpyAsync(s->h_out, s->d_out, (size_t)n * 1000 * sizeof(float), hipMemcpyDeviceToHost,
+        RN_TRY(rn_argmax_forward(ctx, s->d_out, s->d_idx, n, p->classes));
+        RN_HIP_TRY(ctx, hipMemcpyAsync(s->h_out, s->d_out, (size_t)n * p->classes * sizeof(float), hipMemcpyDeviceToHost,
                                        ctx->stream));
         RN_HIP_TRY(ctx, hipMemcpyAsync(s->h_idx, s->d_idx, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost,
                                        ctx->stream));
@@ -408,8 +410,8 @@ int rn_pipeline_submit_images_u8_n(rn_pipeline *p, const uint8_t *const *host_im
         RN_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s->uploaded, 0));
         RN_TRY(rn_model_forward_images_table(p->model, (const uint8_t *)s->d_in, (char *)s->d_in + p->table_off, n, src_bytes,
                                              s->d_out, p->mode));
-        RN_TRY(rn_argmax_forward(ctx, s->d_out, s->d_idx, n, 1000));
-        RN_HIP_TRY(ctx, hipMemcpyAsync(s->h_out, s->d_out, (size_t)n * 1000 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        RN_TRY(rn_argmax_forward(ctx, s->d_out, s->d_idx, n, p->classes));
+        RN_HIP_TRY(ctx, hipMemcpyAsync(s->h_out, s->d_out, (size_t)n * p->classes * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
         RN_HIP_TRY(ctx, hipMemcpyAsync(s->h_idx, s->d_idx, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
         RN_HIP_TRY(ctx, hipEventRecord(s->done, ctx->stream));
         return RN_OK;
@@ -439,7 +441,7 @@ int rn_pipeline_collect_n(rn_pipeline *p, float *host_logits, uint64_t *host_top
     rn_pipeline_slot *s = &p->slot[p->tail & 1];
     RN_TRY(rn_bind_device(ctx));
     RN_HIP_TRY(ctx, hipEventSynchronize(s->done));
-    if (host_logits) memcpy(host_logits, s->h_out, (size_t)s->n * 1000 * sizeof(float));
+    if (host_logits) memcpy(host_logits, s->h_out, (size_t)s->n * p->classes * sizeof(float));
     if (host_top1) memcpy(host_top1, s->h_idx, (size_t)s->n * sizeof(uint64_t));
     if (n) *n = s->n;
     s->busy = 0;

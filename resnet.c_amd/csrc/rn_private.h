@@ -21,6 +21,13 @@ int rn_ctx_is_capturing(rn_ctx *ctx);
 /* pageable host memory -> device on the context's stream, over when the call returns */
 int rn_ctx_upload_sync(rn_ctx *ctx, void *dev, const void *host, uint64_t bytes);
 
+/* ---- rn_conv.hip / rn_head.hip: kernels only the model driver launches ---- */
+/* rn_linear_forward through the direct kernel whatever the alignment (class counts that are no multiple of 4) */
+int rn_linear_direct_forward(rn_ctx *ctx, const float *inp, float *out, const float *weight, const float *bias,
+                             uint64_t B, uint64_t in_features, uint64_t out_features);
+/* n bf16 values as fp32 (exact): the pooled features of a bf16 model */
+int rn_widen_bf16_forward(rn_ctx *ctx, const void *src_bf16, float *dst, uint64_t n);
+
 /* ---- rn_model.c: what the pipeline and the graph capture (rn_pipeline.hip) need of a model ---- */
 /* the model keeps its context private; the pipeline queues on its compute stream */
 rn_ctx *rn_model_context(rn_model *m);

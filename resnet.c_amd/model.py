@@ -210,7 +210,9 @@ def argmax(logits: np.ndarray) -> np.ndarray:
 class NativeModel:
     def __init__(self, arch: str = "resnet50", state: Optional[Dict[str, np.ndarray]] = None,
                  weights_dir: Optional[str] = None, ctx: Optional[Context] = None,
-                 dtype: str = "f32"):
+                 dtype: str = "f32", classes: Optional[int] = None):
+        """classes: rows of the classifier; None = state["fc.weight"].shape[0] when a state is given,
+        otherwise the library's 1000."""
         self.ctx = ctx or get_ctx()
         self.arch = arch
         lib = L.lib()
@@ -224,6 +226,10 @@ class NativeModel:
         self.handle = h
         if (state is None) == (weights_dir is None):
             raise ValueError("give exactly one of state / weights_dir")
+        if classes is None and state is not None:
+            classes = int(np.shape(state["fc.weight"])[0])
+        if classes is not None:  # before the first tensor: fc.* take their size from it
+            L.check(lib.rn_model_set_classes(h, int(classes)), "rn_model_set_classes: 1..65536", self.ctx.handle)
         if weights_dir is not None:
             L.check(lib.rn_model_load_dir(h, weights_dir.encode()), "rn_model_load_dir",
                     self.ctx.handle)
@@ -237,6 +243,51 @@ class NativeModel:
         L.check(lib.rn_model_set_dtype(h, {"f32": L.RN_DTYPE_F32, "bf16": L.RN_DTYPE_BF16}[dtype]),
                 "rn_model_set_dtype", self.ctx.handle)
         L.check(lib.rn_model_finalize(h), "rn_model_finalize", self.ctx.handle)
+
+    @property
+    def classes(self) -> int:
+        return int(L.lib().rn_model_classes(self.handle))
+
+    @property
+    def features(self) -> int:
+        """Width of the pooled feature vector: 512 (ResNet-18/34) or 2048."""
+        return int(L.lib().rn_model_features(self.handle))
+
+    def forward_outputs(self, x: np.ndarray, *, logits: bool = True, features: bool = False, probs: bool = False,
+                        topk: int = 0, fused: bool = True) -> dict:
+        """One forward, several outputs (rn_model_forward_outputs): a dict with the requested of
+        "logits" [B,classes], "features" [B,features], "probs" [B,classes], "topk_prob" / "topk_idx" [B,topk].
+        x: fp32 NCHW [B,3,224,224], or uint8 NHWC [B,224,224,3] (normalised on the device)."""
+        from .ops import _down_raw, _up_raw
+        from .tensor import _DeviceBuffer
+        x = np.asarray(x)
+        u8 = x.dtype == np.uint8
+        x = np.ascontiguousarray(x, dtype=np.uint8 if u8 else np.float32)
+        assert x.ndim == 4 and x.shape[1:] == ((224, 224, 3) if u8 else (3, 224, 224)), x.shape
+        B, C, F, k = x.shape[0], self.classes, self.features, int(topk)
+        xin = _up_raw(x)
+        bufs = {}
+
+        def buf(name, want, nbytes):
+            if want:
+                bufs[name] = _DeviceBuffer(self.ctx, max(nbytes, 16))
+            return bufs[name].ptr if want else None
+
+        o = L.ModelOutputs(buf("logits", logits, B * C * 4), buf("features", features, B * F * 4),
+                           buf("probs", probs, B * C * 4), buf("topk_prob", k > 0, B * k * 4),
+                           buf("topk_idx", k > 0, B * k * 8), k)
+        fn = L.lib().rn_model_forward_outputs_u8 if u8 else L.lib().rn_model_forward_outputs
+        L.check(fn(self.handle, xin.ptr, B, ctypes.byref(o), L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS),
+                "rn_model_forward_outputs", self.ctx.handle)
+        self.ctx.sync()
+        shapes = {"logits": (B, C), "features": (B, F), "probs": (B, C), "topk_prob": (B, k), "topk_idx": (B, k)}
+        out = {}
+        for name, b in bufs.items():
+            if name == "topk_idx":
+                out[name] = _down_raw(b, np.uint64, B * k).astype(np.int64).reshape(B, k)
+            else:
+                out[name] = _down_raw(b, np.float32, int(np.prod(shapes[name]))).reshape(shapes[name])
+        return out
 
     def tensor_keys(self) -> List[Tuple[str, int]]:
         out, i, n = [], 0, ctypes.c_uint64()
@@ -257,7 +308,7 @@ class NativeModel:
         """NCHW host array -> logits host array (synchronous convenience)."""
         xin = FloatTensor.from_numpy(x, Device.GPU)
         B = x.shape[0]
-        out = FloatTensor((B, 1000), Device.GPU)
+        out = FloatTensor((B, self.classes), Device.GPU)
         self.forward_ptr(xin.data(), B, out.data(), fused)
         self.ctx.sync()
         return out.numpy()
@@ -277,7 +328,7 @@ class NativeModel:
         assert px.ndim == 4 and px.shape[1:] == (224, 224, 3), px.shape
         B = px.shape[0]
         xin = _up_raw(px)
-        out = FloatTensor((B, 1000), Device.GPU)
+        out = FloatTensor((B, self.classes), Device.GPU)
         self.forward_u8_ptr(xin.ptr, B, out.data(), fused)
         self.ctx.sync()
         return out.numpy()
@@ -290,7 +341,7 @@ class NativeModel:
         packed, offsets, heights, widths = pack_images(images)
         B = len(heights)
         xin = _up_raw(packed)
-        out = FloatTensor((B, 1000), Device.GPU)
+        out = FloatTensor((B, self.classes), Device.GPU)
         L.check(L.lib().rn_model_forward_images_u8(self.handle, xin.ptr, _u64p(offsets), _u64p(heights), _u64p(widths),
                                                    B, out.data(), L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS),
                 "rn_model_forward_images_u8", self.ctx.handle)
@@ -599,6 +650,7 @@ class Pipeline:
         if input not in ("f32", "u8", "images"):
             raise ValueError(f"input must be 'f32', 'u8' or 'images', not {input!r}")
         self.model, self.batch, self.input = model, batch, input
+        self.classes = model.classes  # the row length of what collect() returns
         h = ctypes.c_void_p()
         mode = L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS
         if input == "images":
@@ -667,8 +719,8 @@ class Pipeline:
         return self.collect_top1()[0]
 
     def collect_top1(self):
-        """(logits [n,1000], class indices [n]) of the oldest batch in flight."""
-        out = np.empty((self.batch, 1000), dtype=np.float32)
+        """(logits [n,classes], class indices [n]) of the oldest batch in flight."""
+        out = np.empty((self.batch, self.classes), dtype=np.float32)
         idx = np.empty(self.batch, dtype=np.uint64)
         n = ctypes.c_uint64()
         L.check(L.lib().rn_pipeline_collect_n(self.handle, out.ctypes.data, idx.ctypes.data, ctypes.byref(n)),

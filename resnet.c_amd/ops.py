@@ -121,6 +121,62 @@ def argmax(logits) -> np.ndarray:
     return raw.view(np.uint64).astype(np.int64)
 
 
+def topk_reference(x, k: int):
+    """The contract of rn_topk_forward in numpy, for rows without NaN: the k largest, descending, equal
+    values (-0.0 == +0.0 among them) in ascending index order -- a stable argsort of -x."""
+    x = np.asarray(x, dtype=np.float32)
+    idx = np.argsort(-x, axis=-1, kind="stable")[..., :k]
+    return np.take_along_axis(x, idx, axis=-1), idx.astype(np.int64)
+
+
+def softmax_reference(x) -> np.ndarray:
+    """float64 softmax of the fp32 rows (what rn_softmax_forward is measured against)."""
+    x = np.asarray(x, dtype=np.float32).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        e = np.exp(x - x.max(axis=-1, keepdims=True))
+    return e / e.sum(axis=-1, keepdims=True)
+
+
+def softmax(x) -> np.ndarray:
+    """rn_softmax_forward on host rows [B, classes]."""
+    x = np.asarray(x, dtype=np.float32)
+    B, C = x.shape
+    dx = _up(x, "nchw")
+    out = FloatTensor((B, C), Device.GPU)
+    _run("rn_softmax_forward", "nchw", dx.data(), out.data(), B, C)
+    return _down(out, (B, C), "nchw")
+
+
+def _topk_call(name: str, x, k: int, want_probs: bool):
+    from .tensor import _DeviceBuffer
+    ctx = get_ctx()
+    x = np.asarray(x, dtype=np.float32)
+    B, C = x.shape
+    dx = _up(x, "nchw")
+    val = FloatTensor((B, k), Device.GPU)
+    idx = _DeviceBuffer(ctx, max(B * k * 8, 16))
+    probs = FloatTensor((B, C), Device.GPU) if want_probs else None
+    if name == "rn_topk_forward":
+        _run(name, "nchw", dx.data(), val.data(), idx.ptr, B, C, k)
+    else:
+        _run(name, "nchw", dx.data(), probs.data() if probs else None, val.data(), idx.ptr, B, C, k)
+    hi = _down_raw(idx, np.uint64, B * k).astype(np.int64).reshape(B, k)
+    return _down(val, (B, k), "nchw"), hi, (_down(probs, (B, C), "nchw") if probs else None)
+
+
+def topk(x, k: int):
+    """rn_topk_forward: (values [B,k], indices [B,k] int64), descending, ties by ascending index."""
+    v, i, _ = _topk_call("rn_topk_forward", x, k, False)
+    return v, i
+
+
+def softmax_topk(x, k: int, return_probs: bool = False):
+    """rn_softmax_topk_forward: (topk_prob [B,k], topk_idx [B,k]) ordered by logit, and with ``return_probs``
+    the full probabilities [B, classes] as a third element, all from one launch."""
+    v, i, p = _topk_call("rn_softmax_topk_forward", x, k, return_probs)
+    return (v, i, p) if return_probs else (v, i)
+
+
 def conv2d_nhwc_fused(x, w, stride=1, pad=0, scale=None, shift=None, residual=None,
                       relu_: bool = False) -> np.ndarray:
     """rn_conv2d_pack_weight + rn_conv2d_nhwc_forward with an epilogue (NCHW host arrays)."""
