@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import bf16_ref as BR
 import resnet_c_amd as R
 from oracle import oracle as O
 from resnet_c_amd import ops
@@ -76,6 +77,8 @@ def test_bf16_every_tile_candidate_matches_oracle_and_each_other(case):
     ctx, lib = R.get_ctx(), L.lib()
     base = ops.conv2d_nhwc_bf16(x, w, s, p, scale, shift, res, True)
     assert np.abs(base - want).max() <= 2 ** -8 * np.abs(want).max() + 1e-5
+    BR.assert_bf16_rounded(base, BR.epilogue64(BR.conv64(ops.bf16_round(x), ops.bf16_round(w), s, p), scale, shift,
+                                               ops.bf16_round(res), True), Cin * k * k, f"{case}")
     plain = ops.conv2d_nhwc_bf16(x, w, s, p)
     try:
         for cand in range(1, lib.rn_conv_tile_candidates() + 1):
@@ -373,6 +376,8 @@ def test_bf16_fused_epilogue():
     want = np.maximum(y * scale[None, :, None, None] + shift[None, :, None, None] + ops.bf16_round(res), 0)
     got = ops.conv2d_nhwc_bf16(x, w, 1, 1, scale, shift, res, True)
     assert np.abs(got - want).max() <= 2 ** -8 * np.abs(want).max() + 1e-5
+    BR.assert_bf16_rounded(got, BR.epilogue64(BR.conv64(ops.bf16_round(x), ops.bf16_round(w), 1, 1), scale, shift,
+                                              ops.bf16_round(res), True), Cin * 9, "fused epilogue")
 
 
 def test_bf16_conv_pair():
@@ -389,6 +394,8 @@ def test_bf16_conv_pair():
     want = O.relu_(O.conv2d(tb, w1b, 1, 0) + O.conv2d(xb, w2b, s2, 0) + shift[None, :, None, None])
     got = ops.conv2d_nhwc_pair(t, w, x2, w2, 1, 0, s2, sc1, sc2, shift, None, True, bf16=True)
     np.testing.assert_allclose(got, ops.bf16_round(want), rtol=2 ** -7, atol=1e-2)
+    BR.assert_bf16_rounded(got, BR.epilogue64(BR.conv64(tb, w1b, 1, 0) + BR.conv64(xb, w2b, s2, 0), None, shift, None, True),
+                           Cin + Cin2, "fused pair")
 
 
 @pytest.mark.parametrize("case", [(2, 3, 224, 224, 4, 3), (2, 3, 9, 10, 4, 2), (1, 3, 6, 7, 4, 1),
