@@ -431,6 +431,17 @@ RN_API int rn_avgpool2d_nhwc_forward_dt(rn_ctx *ctx, int dtype, const void *inp,
                                         uint64_t kernel_size, uint64_t stride, uint64_t padding,
                                         uint64_t h_out, uint64_t w_out, uint64_t B,
                                         uint64_t channels, uint64_t H, uint64_t W);
+/* Global average over any H x W map: inp [B,H,W,channels] -> out [B,channels], both of `dtype` (what
+ * torch's AdaptiveAvgPool2d(1) computes; the reference has no such op, its average pool takes one square
+ * kernel_size).  The head of the model driver at every input size.  fp32 accumulator, sum / (H*W) in fp32,
+ * rounded once to the storage type.  H == W == 7 runs the kernel of rn_avgpool2d_nhwc_forward_dt(k = 7) and
+ * gives its bits.  Every other map: the taps of an output are split over up to 16 lanes and added in an
+ * order that depends on (H, W) alone (written down above global_avgpool_kernel in rn_pool.hip), so an
+ * image's result does not depend on B or on its place in the batch.
+ * RN_ERR_INVALID, nothing launched: a null pointer, inp == out, channels % 4 != 0 (fp32) / % 8 != 0 (bf16),
+ * inp or out off a 16-byte boundary, an unknown dtype.  B, channels, H or W == 0 is RN_OK. */
+RN_API int rn_global_avgpool_nhwc_forward_dt(rn_ctx *ctx, int dtype, const void *inp, void *out, uint64_t B,
+                                             uint64_t channels, uint64_t H, uint64_t W);
 
 /* ---- grouped convolution (torch's `groups`): ResNeXt's conv2 ---------------------------------
  * weight [out_channels][in_channels / groups][k][k]; output channel o belongs to group
@@ -525,25 +536,52 @@ RN_API int rn_model_set_dtype(rn_model *m, int dtype);
 RN_API int rn_model_finalize(rn_model *m);
 /* names of the tensors the loader expects, one per call; returns NULL past the end */
 RN_API const char *rn_model_tensor_key(const rn_model *m, uint64_t index, uint64_t *numel);
-/* input: device NCHW [B,3,224,224]; logits: device [B,classes]. Asynchronous on the stream.
+/* The size of the images every forward entry point of this model reads: [B,3,H,W] floats or [B,H,W,3]
+ * bytes (rn_model_forward, _u8, _outputs, _outputs_u8, rn_model_tune, rn_model_capture, rn_pipeline_create /
+ * _u8).  Default 224 x 224; 32..2048 for each of H and W.  A property of the model, like the class count:
+ * there is no per-call size.  Legal before or after rn_model_finalize (the weights do not depend on it).
+ * RN_ERR_INVALID, nothing changed: a side out of range, a size of which not one image fits the kernels'
+ * tensor range (none within 2048 x 2048), or a captured graph or a pipeline of this model alive (they hold
+ * buffers of the old size).  It waits for the model's queued forwards, frees the activation arenas (the
+ * next forward sizes them anew; rn_model_activation_bytes follows) and drops the tuned tiles.
+ * What follows from the size:
+ *   - the head pools whatever map the last stage leaves (H/32 x W/32, rounded up) with
+ *     rn_global_avgpool_nhwc_forward_dt; at 224 x 224 that is the 7 x 7 launch and every bit of before;
+ *   - the stem route.  The fused stem + max-pool launch (rn_stem_pool_forward_dt) is used where its
+ *     conditions hold: conv output width a multiple of 8 and at most 128 (W a multiple of 16 up to 256, or
+ *     one less), its LDS budget, bf16: an even W; the NCHW-fetching form (fusion 2) also W % 4 == 0.
+ *     Otherwise stem and max-pool run as separate launches, as with rn_model_set_stem_pool_fusion(m, 0).
+ *     The route depends on (H, W, dtype, settings) only, never on B: an image's logits stay independent of
+ *     batch, part and sub-batch, bit for bit;
+ *   - rn_model_max_sub_batch: the largest power of two, at most 512, for which the largest tensor of the
+ *     arenas (per image: the padded input, the stem output, the first stage's output) times it stays below
+ *     the kernels' 2^29 elements: 512 at 224 x 224, 16 at 1024 x 1024;
+ *   - the tuning table's header carries the size in a word of its own that is absent for 224 x 224, whose
+ *     tables keep their format; a model refuses a table measured at another size;
+ *   - rn_model_forward_images_u8 and rn_pipeline_create_images_u8 stay at 224 x 224 (their contract is
+ *     "resize 256, crop 224"): RN_ERR_UNSUPPORTED with rn_last_error's text on a model of another size.
+ *     rn_shard_* creates its own models and stays at 224 x 224. */
+RN_API int rn_model_set_input_size(rn_model *m, uint64_t H, uint64_t W);
+RN_API int rn_model_input_size(const rn_model *m, uint64_t *H, uint64_t *W); /* either pointer may be NULL */
+RN_API uint64_t rn_model_max_sub_batch(const rn_model *m);
+/* input: device NCHW [B,3,H,W] of the model's input size; logits: device [B,classes]. Asynchronous on the stream.
  *
- * Fixed geometry of the model driver (the op entry points above are general; the driver, like
- * the reference's -- main.cu:230 hard-codes {1, 3, 224, 224} -- is not):
- *   - images are 3 x 224 x 224 fp32, NCHW; there is no size argument, so a buffer of another
- *     geometry cannot be expressed: callers that read files check the element count first
- *     (rn_infer does and reports RN_ERR_UNSUPPORTED's text for anything but B*3*224*224 floats);
- *   - bottleneck depths 50 / 101 / 152, basic-block depths 18 / 34; the class count is NOT fixed
- *     (rn_model_set_classes, default 1000), the 224 x 224 image is;
- *   - any B >= 1: the kernels address a tensor with 32-bit byte offsets (2^29 fp32 elements; the
- *     stem output of 669 images is the first to pass it), so a batch runs as sub-batches of at
- *     most 512 images through the same arenas, each as `streams` parts (rn_model_set_streams);
- *     every image's logits are independent of that split, bit for bit;
- *   - arenas: 13.6 MB (fp32) / 6.8 MB (bf16) of activations per image of the largest sub-batch
- *     seen (basic-block networks: 8.5 / 4.2 MB), allocated on first use (RN_ERR_NOMEM when the
- *     device cannot hold them). */
+ * Geometry of the model driver (the reference's -- main.cu:230 hard-codes {1, 3, 224, 224} -- is fixed):
+ *   - images are 3 x H x W fp32, NCHW, H x W = rn_model_input_size (default 224 x 224).  The call has no size
+ *     argument: a buffer of another geometry cannot be told apart, so callers that read files check the
+ *     element count first (rn_infer does: --size H,W, and it refuses anything but B*3*H*W floats);
+ *   - bottleneck depths 50 / 101 / 152, basic-block depths 18 / 34; the class count is not fixed either
+ *     (rn_model_set_classes, default 1000);
+ *   - any B >= 1: the kernels address a tensor with 32-bit byte offsets (2^29 fp32 elements; at 224 x 224
+ *     the stem output of 669 images is the first to pass it), so a batch runs as sub-batches of at most
+ *     rn_model_max_sub_batch images (512 at 224 x 224) through the same arenas, each as `streams` parts
+ *     (rn_model_set_streams); every image's logits are independent of that split, bit for bit;
+ *   - arenas: at 224 x 224 13.6 MB (fp32) / 6.8 MB (bf16) of activations per image of the largest
+ *     sub-batch seen (basic-block networks: 8.5 / 4.2 MB), in proportion to H x W otherwise, allocated on
+ *     first use (RN_ERR_NOMEM when the device cannot hold them). */
 RN_API int rn_model_forward(rn_model *m, const float *input_nchw, uint64_t B, float *logits,
                             int mode);
-/* The same forward from 8-bit RGB crops, [B,224,224,3] on the device: the first launch
+/* The same forward from 8-bit RGB crops, [B,H,W,3] of the model's input size on the device: the first launch
  * (rn_image_u8_to_nhwc_pad_dt with the ImageNet mean (0.485, 0.456, 0.406) and std (0.229, 0.224,
  * 0.225)) replaces the layout launch of the float route and writes the same first tensor, so the
  * logits are those of rn_model_forward on the host-normalised image, bit for bit, for every
@@ -561,7 +599,8 @@ RN_API int rn_model_forward_u8(rn_model *m, const uint8_t *input_nhwc, uint64_t 
  * route; the resize of a sub-batch runs on the model's own stream before the parts fork.  The
  * coefficient tables come from host memory that the call frees, so a stream that is being captured
  * is refused with RN_ERR_UNSUPPORTED.  Refusals of rn_image_u8_resize_crop apply (checked for the
- * whole batch before anything is launched). */
+ * whole batch before anything is launched).  A model whose input size is not 224 x 224:
+ * RN_ERR_UNSUPPORTED. */
 RN_API int rn_model_forward_images_u8(rn_model *m, const uint8_t *packed_dev, const uint64_t *offsets,
                                       const uint64_t *heights, const uint64_t *widths, uint64_t B,
                                       float *logits, int mode);
@@ -574,7 +613,7 @@ typedef struct rn_model_outputs {
     uint64_t *topk_idx;  /* [B, k]: ordered by logit (rn_softmax_topk_forward) */
     uint64_t k;          /* 0 = no top-k; otherwise 1..min(classes, 64) with both topk pointers set */
 } rn_model_outputs;
-/* Exactly the launches of rn_model_forward / rn_model_forward_u8 -- same sub-batches (<= 512 images), streams
+/* Exactly the launches of rn_model_forward / rn_model_forward_u8 -- same sub-batches (<= rn_model_max_sub_batch images), streams
  * and profile records -- and behind each sub-batch, on the model's own stream: the features (fp32 models: a
  * device-to-device copy out of the pooled arena; bf16 models: the bf16 values widened to fp32, exact; op
  * "features" of layer "head"), then at most one rn_softmax_topk_forward (op "softmax_topk"), or
@@ -594,7 +633,7 @@ RN_API int rn_model_tune(rn_model *m, const float *input_nchw, uint64_t B, float
 /* The table that rn_model_tune filled, as 64-bit words (header: architecture, element type, fusion
  * settings, batch, mode, candidate count of the build; then the (tile, launch batch) slots of every
  * layer), and its way into another model of the same architecture / element type / settings on an
- * identical device: the shards of a node take over ONE shard's measurement (rn_shard_tune), a later
+ * identical device (and of the same input size, rn_model_set_input_size): the shards of a node take over ONE shard's measurement (rn_shard_tune), a later
  * process a stored one.  export with words == NULL returns the size in *n_words; import refuses a
  * table measured for anything else (RN_ERR_INVALID, nothing changed).  Tiles change speed only. */
 RN_API int rn_model_export_tuning(const rn_model *m, uint64_t *words, uint64_t cap, uint64_t *n_words);
@@ -772,11 +811,12 @@ RN_API uint64_t rn_graph_node_count(const rn_graph *g);
 typedef struct rn_pipeline rn_pipeline;
 RN_API int rn_pipeline_create(rn_model *m, rn_pipeline **out, uint64_t B, int mode);
 RN_API int rn_pipeline_destroy(rn_pipeline *p);
-/* The pinned staging buffer (B*3*224*224 floats) the next submit will upload from: a decoder
+/* The pinned staging buffer (B*3*H*W floats, the model's input size when the pipeline was created -- it
+ * cannot change while the pipeline lives) the next submit will upload from: a decoder
  * that writes its output there saves the host-side copy.  RN_ERR_INVALID when both slots are
  * busy. */
 RN_API int rn_pipeline_input_buffer(rn_pipeline *p, float **host_staging);
-/* host_input_nchw: B*3*224*224 floats in any host memory (copied into the staging buffer), or
+/* host_input_nchw: B*3*H*W floats in any host memory (copied into the staging buffer), or
  * NULL / the pointer rn_pipeline_input_buffer returned when the staging buffer is already
  * filled. */
 RN_API int rn_pipeline_submit(rn_pipeline *p, const float *host_input_nchw);
@@ -789,20 +829,21 @@ RN_API uint64_t rn_pipeline_in_flight(const rn_pipeline *p);
  * ([n]) and n may each be NULL. */
 RN_API int rn_pipeline_submit_n(rn_pipeline *p, const float *host_input_nchw, uint64_t n);
 RN_API int rn_pipeline_collect_n(rn_pipeline *p, float *host_logits, uint64_t *host_top1, uint64_t *n);
-/* A pipeline for 8-bit RGB input ([n,224,224,3], rn_model_forward_u8): pinned staging and device
- * input buffers of B*150528 bytes, a quarter of the fp32 pipeline's upload and staging copy.
+/* A pipeline for 8-bit RGB input ([n,H,W,3], rn_model_forward_u8): pinned staging and device
+ * input buffers of B*H*W*3 bytes (B*150528 at 224 x 224), a quarter of the fp32 pipeline's upload and staging copy.
  * Collect as above.  A pipeline takes the input format it was created for: the float calls on a
  * byte pipeline, and these on a float pipeline, return RN_ERR_INVALID. */
 RN_API int rn_pipeline_create_u8(rn_model *m, rn_pipeline **out, uint64_t B, int mode);
 RN_API int rn_pipeline_input_buffer_u8(rn_pipeline *p, uint8_t **host_staging);
-/* host_input_nhwc: n*150528 bytes in any host memory, or NULL / the staging pointer; n <= B */
+/* host_input_nhwc: n*H*W*3 bytes in any host memory, or NULL / the staging pointer; n <= B */
 RN_API int rn_pipeline_submit_u8_n(rn_pipeline *p, const uint8_t *host_input_nhwc, uint64_t n);
 /* A pipeline for decoded images of any size (rn_model_forward_images_u8): pinned staging and device
  * input buffers hold the packed batch -- at most max_batch_bytes of pixels -- and behind it the
  * coefficient tables, uploaded together on the copy stream.  host_imgs: n <= B pointers to the images
  * in any host memory (image i: heights[i] x widths[i] x 3 bytes); they are packed back to back into
  * staging.  Collect as above.  A batch of more than max_batch_bytes, or the call on a pipeline of
- * another input format (and the float / byte calls on this one), is RN_ERR_INVALID. */
+ * another input format (and the float / byte calls on this one), is RN_ERR_INVALID.  A model whose
+ * input size is not 224 x 224: RN_ERR_UNSUPPORTED at creation. */
 RN_API int rn_pipeline_create_images_u8(rn_model *m, rn_pipeline **out, uint64_t B, int mode,
                                         uint64_t max_batch_bytes);
 RN_API int rn_pipeline_submit_images_u8_n(rn_pipeline *p, const uint8_t *const *host_imgs,

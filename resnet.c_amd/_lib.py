@@ -147,6 +147,10 @@ SIGNATURES = {
     "rn_model_set_front_parts": (c_int, [c_void_p, c_int]),
     "rn_maxpool2d_nhwc_forward_dt": (c_int, [c_void_p, c_int, fptr, fptr] + [u64] * 9),
     "rn_avgpool2d_nhwc_forward_dt": (c_int, [c_void_p, c_int, fptr, fptr] + [u64] * 9),
+    "rn_global_avgpool_nhwc_forward_dt": (c_int, [c_void_p, c_int, fptr, fptr] + [u64] * 4),
+    "rn_model_set_input_size": (c_int, [c_void_p, u64, u64]),
+    "rn_model_input_size": (c_int, [c_void_p, POINTER(u64), POINTER(u64)]),
+    "rn_model_max_sub_batch": (u64, [c_void_p]),
     "rn_model_create": (c_int, [c_void_p, POINTER(c_void_p), c_int]),
     "rn_model_create_ex": (c_int, [c_void_p, POINTER(c_void_p), c_int, c_int, c_int]),
     "rn_model_set_dtype": (c_int, [c_void_p, c_int]),

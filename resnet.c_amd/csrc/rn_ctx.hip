@@ -289,6 +289,9 @@ int rn_ctx_scratch_slot(rn_ctx *ctx, int slot, uint64_t bytes, void **ptr)
     RN_TRY(rn_bind_device(ctx));
     return rn_scratch(ctx, slot, bytes, ptr);
 }
+/* library-internal: rn_last_error's text from plain C (rn_model.c); returns status */
+int rn_ctx_set_error(rn_ctx *ctx, int status, const char *msg) { return rn_set_error(ctx, status, "%s", msg); }
+
 int rn_ctx_is_capturing(rn_ctx *ctx)
 {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;

@@ -5,8 +5,11 @@
  * B = 1, paths); here the same defaults can be overridden from the command line.
  *
  *   rn_infer [--arch 18|34|50|101|152|resnext50_32x4d|resnext101_32x8d|resnext101_64x4d|wide_resnet50_2|wide_resnet101_2] [--weights DIR] [--input FILE | --u8 FILE | --rgb FILE --hw H,W] [--batch B]
- *            [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,c,...]
+ *            [--size H,W] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,c,...]
  *
+ * --size H,W sets the model's input size (rn_model_set_input_size; default 224,224; single device only):
+ * --input then holds B x 3 x H x W floats and --u8 B x H x W x 3 bytes, and a file of any other length is
+ * refused with the size in the message.
  * --u8 FILE reads B x 150528 raw bytes, the decoder's 8-bit RGB crops ([B,224,224,3]), instead of
  * the preprocessed fp32 file: the device normalises them (rn_model_forward_u8), same lines out.
  * --rgb FILE --hw H,W reads the H x W x 3 raw bytes of ONE decoded image of any size: the device resizes
@@ -35,19 +38,23 @@
     } while (0)
 
 /* the whole file, which must hold exactly `want` bytes; NULL (and a message) otherwise */
+static uint64_t size_h = 224, size_w = 224; /* --size */
+
 static void *read_exact(const char *path, uint64_t want, uint64_t B, int u8)
 {
     void *host = malloc(want);
     FILE *f = fopen(path, "rb");
     if (!host || !f || fread(host, 1, want, f) != want || fgetc(f) != EOF) {
         if (u8)
-            fprintf(stderr, "rn_infer: %s: %s: --u8 takes 224 x 224 x 3 8-bit RGB images only; the file does not "
+            fprintf(stderr, "rn_infer: %s: %s: --u8 takes %llu x %llu x 3 8-bit RGB images only (--size); the file does not "
                             "hold exactly %llu bytes (batch %llu)\n", rn_status_string(RN_ERR_UNSUPPORTED), path,
-                    (unsigned long long)want, (unsigned long long)B);
+                    (unsigned long long)size_h, (unsigned long long)size_w, (unsigned long long)want,
+                    (unsigned long long)B);
         else
-            fprintf(stderr, "rn_infer: %s: %s: the model driver takes 3 x 224 x 224 fp32 images only; the file "
+            fprintf(stderr, "rn_infer: %s: %s: the model driver takes 3 x %llu x %llu fp32 images only (--size); the file "
                             "does not hold exactly %llu floats (batch %llu)\n", rn_status_string(RN_ERR_UNSUPPORTED),
-                    path, (unsigned long long)(want / sizeof(float)), (unsigned long long)B);
+                    path, (unsigned long long)size_h, (unsigned long long)size_w,
+                    (unsigned long long)(want / sizeof(float)), (unsigned long long)B);
         if (f) fclose(f);
         free(host);
         return NULL;
@@ -157,6 +164,12 @@ int main(int argc, char **argv)
             dtype = strcmp(v, "bf16") ? RN_DTYPE_F32 : RN_DTYPE_BF16;
             ++i;
         }
+        else if (!strcmp(a, "--size") && v) {
+            char *q = NULL;
+            size_h = strtoull(v, &q, 10);
+            size_w = (q && *q == ',') ? strtoull(q + 1, NULL, 10) : 0;
+            ++i;
+        }
         else if (!strcmp(a, "--batch") && v) { B = strtoull(v, NULL, 10); ++i; }
         else if (!strcmp(a, "--classes") && v) { classes = strtoull(v, NULL, 10); ++i; }
         else if (!strcmp(a, "--topk") && v) { topk = strtoull(v, NULL, 10); ++i; }
@@ -172,7 +185,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--mode") && v) { mode = strcmp(v, "ops") ? RN_FWD_FUSED : RN_FWD_REFERENCE_OPS; ++i; }
         else {
             fprintf(stderr, "usage: %s [--arch 18|34|50|101|152|resnext50_32x4d|resnext101_32x8d|resnext101_64x4d|wide_resnet50_2|wide_resnet101_2] [--weights DIR] [--input FILE | --u8 FILE | --rgb FILE --hw H,W] "
-                            "[--batch B] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,...] [--classes N] [--topk K]\n",
+                            "[--batch B] [--size H,W] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,...] [--classes N] [--topk K]\n",
                     argv[0]);
             return 2;
         }
@@ -188,11 +201,21 @@ int main(int argc, char **argv)
                 rn_status_string(RN_ERR_UNSUPPORTED));
         return 1;
     }
+    if ((size_h != 224 || size_w != 224) && (ndev > 0 || rgb)) {
+        fprintf(stderr, "rn_infer: %s: --size other than 224,224 runs on one device and not with --rgb (decoded images are "
+                        "cropped to 224 x 224)\n", rn_status_string(RN_ERR_UNSUPPORTED));
+        return 1;
+    }
     if (ndev > 0) return run_sharded(devices, ndev, arch, weights, input, u8, B, mode, dtype);
     CHECK(ctx, rn_ctx_create(&ctx, device, NULL));
     CHECK(ctx, groups_g ? rn_model_create_ex(ctx, &model, arch, groups_g, wpg_g) : rn_model_create(ctx, &model, arch));
     if (classes) CHECK(ctx, rn_model_set_classes(model, classes)); /* before the weights: fc.* take its size */
     classes = rn_model_classes(model);
+    if (rn_model_set_input_size(model, size_h, size_w) != RN_OK) {
+        fprintf(stderr, "rn_infer: %s: --size %llu,%llu: each side must be 32..2048\n", rn_status_string(RN_ERR_INVALID),
+                (unsigned long long)size_h, (unsigned long long)size_w);
+        return 1;
+    }
     CHECK(ctx, rn_model_load_dir(model, weights));
     if (dtype != RN_DTYPE_F32) CHECK(ctx, rn_model_set_dtype(model, dtype));
     CHECK(ctx, rn_model_finalize(model));
@@ -213,18 +236,19 @@ int main(int argc, char **argv)
         CHECK(ctx, rn_memcpy_h2d(ctx, inp_u8, host, want));
         free(host);
     } else if (u8) {
-        void *host = read_exact(input, B * 224 * 224 * 3, B, 1);
+        void *host = read_exact(input, B * size_h * size_w * 3, B, 1);
         if (!host) return 1;
-        CHECK(ctx, rn_malloc(ctx, (void **)&inp_u8, B * 224 * 224 * 3));
-        CHECK(ctx, rn_memcpy_h2d(ctx, inp_u8, host, B * 224 * 224 * 3));
+        CHECK(ctx, rn_malloc(ctx, (void **)&inp_u8, B * size_h * size_w * 3));
+        CHECK(ctx, rn_memcpy_h2d(ctx, inp_u8, host, B * size_h * size_w * 3));
         free(host);
     } else {
         CHECK(ctx, rn_load_f32_file(ctx, input, &inp, &numel));
     }
-    if (!u8 && !rgb && numel != B * 3 * 224 * 224) {
-        fprintf(stderr, "rn_infer: %s: the model driver takes 3 x 224 x 224 fp32 images only; %s holds "
-                        "%llu floats, expected %llu for batch %llu\n", rn_status_string(RN_ERR_UNSUPPORTED), input,
-                (unsigned long long)numel, (unsigned long long)(B * 3 * 224 * 224),
+    if (!u8 && !rgb && numel != B * 3 * size_h * size_w) {
+        fprintf(stderr, "rn_infer: %s: the model driver takes 3 x %llu x %llu fp32 images only (--size); %s holds "
+                        "%llu floats, expected %llu for batch %llu\n", rn_status_string(RN_ERR_UNSUPPORTED),
+                (unsigned long long)size_h, (unsigned long long)size_w, input,
+                (unsigned long long)numel, (unsigned long long)(B * 3 * size_h * size_w),
                 (unsigned long long)B);
         return 1;
     }

@@ -31,10 +31,12 @@
 #include "rn_private.h"
 
 #define RN_MAX_KEY 96
-/* the fixed geometry: 224 x 224 RGB images, a 64-channel stem; the class count is a field of the model */
-#define RN_IMAGE_SIDE 224
-#define RN_IMAGE_NUMEL (3 * RN_IMAGE_SIDE * RN_IMAGE_SIDE)
-#define RN_RESIZE_SIDE 256 /* decoded images: the shorter side before the centre crop */
+/* RGB images of the model's H x W (rn_model_set_input_size; the default below), a 64-channel stem; the size and
+ * the class count are fields of the model */
+#define RN_DEFAULT_SIDE 224
+#define RN_MIN_SIDE 32
+#define RN_MAX_SIDE 2048
+#define RN_RESIZE_SIDE 256 /* decoded images: the shorter side before the centre crop (to RN_DEFAULT_SIDE) */
 #define RN_STEM_WIDTH 64
 #define RN_DEFAULT_CLASSES 1000
 #define RN_MAX_CLASSES 65536
@@ -104,6 +106,11 @@ typedef struct {
     float *x4, *p0, *p1, *dsb, *t1, *t2, *pooled; /* views into the arenas */
 } rn_run;
 
+/* What a pipeline keeps of its model after the model may be gone: freed by whoever leaves last. */
+struct rn_model_share {
+    int pipelines, model_alive;
+};
+
 struct rn_model {
     rn_ctx *ctx;
     int arch;
@@ -115,7 +122,11 @@ struct rn_model {
     int classes_locked; /* a tensor was set, a directory loaded or the model finalized: the count stays */
     float *own_logits;  /* [own_logits_cap, classes]: where rn_model_forward_outputs keeps logits nobody asked for */
     uint64_t own_logits_cap;
-    uint64_t stem_side, pool_side; /* the stem's output (112) and the max-pool's (56), which the first stage keeps */
+    uint64_t H, W;                 /* the input image: 224 x 224 unless rn_model_set_input_size said otherwise */
+    uint64_t stem_h, stem_w;       /* the stem's output (112 x 112 at 224) */
+    uint64_t pool_h, pool_w;       /* the max-pool's (56 x 56), which the first stage keeps */
+    uint64_t max_sub;              /* images per launch batch at this size: see rn_model_forward */
+    struct rn_model_share *share;  /* counts the pipelines whose buffers are sized for H x W */
     /* per-image element counts of the arenas (ensure_acts) */
     uint64_t x4_img, p_img, ds_img, t1_img, t2_img;
     uint64_t s1_img; /* the first stage's output per image (56*56*256, or 56*56*64): slices of a depth-first front */
@@ -224,22 +235,37 @@ static uint64_t mid_width(const rn_model *m, int li)
 /* The spatial sizes and, from them, the arenas per image: x4 the input image, p0 / p1 the block outputs
  * (and the stem output), dsb the downsample branch, t1 / t2 the block-internal tensors (a basic block
  * has one: conv1's output).  Max-pool 3x3 s2 p1 (main.cu:114,192); the first stage has stride 1. */
-static void set_geometry(rn_model *m)
+#define RN_SUB_BATCH_LIMIT 512
+static void set_geometry(rn_model *m, uint64_t H, uint64_t W)
 {
     const rn_conv *stem = &m->convs[0];
-    const uint64_t padded = RN_IMAGE_SIDE + 2 * stem->pad; /* bf16 and exact-K stems keep a zero border */
-    uint64_t s1, s2, stem_img;
-    m->stem_side = rn_conv_output_size(RN_IMAGE_SIDE, stem->k, stem->stride, stem->pad);
-    m->pool_side = rn_conv_output_size(m->stem_side, 3, 2, 1);
-    s1 = m->pool_side * m->pool_side;
-    s2 = rn_conv_output_size(m->pool_side, 1, kStrides[1], 0); /* side of the second stage */
-    stem_img = m->stem_side * m->stem_side * stem->cout;
-    m->x4_img = padded * padded * 4;
+    /* bf16 and exact-K stems keep a zero border */
+    const uint64_t padded = (H + 2 * stem->pad) * (W + 2 * stem->pad);
+    uint64_t s1, s2, stem_img, largest;
+    m->H = H;
+    m->W = W;
+    m->stem_h = rn_conv_output_size(H, stem->k, stem->stride, stem->pad);
+    m->stem_w = rn_conv_output_size(W, stem->k, stem->stride, stem->pad);
+    m->pool_h = rn_conv_output_size(m->stem_h, 3, 2, 1);
+    m->pool_w = rn_conv_output_size(m->stem_w, 3, 2, 1);
+    s1 = m->pool_h * m->pool_w;
+    /* map of the second stage (the 3x3 / 2 / 1 and the 1x1 / 2 / 0 convolutions agree on it) */
+    s2 = rn_conv_output_size(m->pool_h, 1, kStrides[1], 0) * rn_conv_output_size(m->pool_w, 1, kStrides[1], 0);
+    stem_img = m->stem_h * m->stem_w * stem->cout;
+    m->x4_img = padded * 4;
     m->s1_img = s1 * (m->basic ? kBasicWidths[0] : kWidths[0][2]);
     m->p_img = stem_img > m->s1_img ? stem_img : m->s1_img;
-    m->ds_img = m->basic ? s2 * s2 * kBasicWidths[1] : m->s1_img; /* layer2.0's, or layer1.0's of a bottleneck */
+    m->ds_img = m->basic ? s2 * kBasicWidths[1] : m->s1_img; /* layer2.0's, or layer1.0's of a bottleneck */
     m->t1_img = s1 * (m->basic ? kBasicWidths[0] : mid_width(m, 1)); /* layer2.0 conv1 of a bottleneck */
     m->t2_img = m->basic ? 0 : m->t1_img;
+    /* The contraction kernels address a tensor with 32-bit byte offsets and refuse one of 2^29 elements or
+     * more: a launch batch is the largest power of two, at most 512, whose largest arena tensor stays below
+     * that (512 at 224 x 224; 0 = not even one image of this size fits). */
+    largest = m->x4_img > m->p_img ? m->x4_img : m->p_img;
+    if (m->t1_img > largest) largest = m->t1_img;
+    if (m->ds_img > largest) largest = m->ds_img;
+    m->max_sub = RN_SUB_BATCH_LIMIT;
+    while (m->max_sub > 0 && largest * m->max_sub >= (1ull << 29)) m->max_sub /= 2;
 }
 
 static int model_create(rn_ctx *ctx, rn_model **out, int arch, int groups, int width_per_group)
@@ -280,13 +306,15 @@ static int model_create(rn_ctx *ctx, rn_model **out, int arch, int groups, int w
     m->blocks = (rn_block *)calloc((size_t)total_blocks, sizeof(rn_block));
     m->cap_calls = max_convs;
     m->calls = (rn_conv_call *)calloc((size_t)m->cap_calls, sizeof(rn_conv_call));
-    if (!m->params || !m->convs || !m->blocks || !m->calls) {
+    m->share = (struct rn_model_share *)calloc(1, sizeof(struct rn_model_share));
+    if (m->share) m->share->model_alive = 1;
+    if (!m->params || !m->convs || !m->blocks || !m->calls || !m->share) {
         rn_model_destroy(m);
         return RN_ERR_NOMEM;
     }
     /* stem: conv1 7x7 s2 p3 + bn1 (main.cu:111-112) */
     add_conv(m, "conv1", "bn1", 3, RN_STEM_WIDTH, 7, 2, 3);
-    set_geometry(m);
+    set_geometry(m, RN_DEFAULT_SIDE, RN_DEFAULT_SIDE);
     for (li = 0; li < 4; ++li) {
         for (bi = 0; bi < d[li]; ++bi) {
             rn_block *b = &m->blocks[m->n_blocks++];
@@ -379,6 +407,48 @@ static void free_acts(rn_model *m)
     m->act_bytes = 0;
 }
 
+/* The weights do not depend on the image size, the arenas, the tuned tiles and the sub-batch do. */
+int rn_model_set_input_size(rn_model *m, uint64_t H, uint64_t W)
+{
+    rn_model probe;
+    int c;
+    if (!m || H < RN_MIN_SIDE || H > RN_MAX_SIDE || W < RN_MIN_SIDE || W > RN_MAX_SIDE) return RN_ERR_INVALID;
+    /* a captured graph points into the arenas; a pipeline's staging and device buffers hold images of the
+     * size it was created at */
+    if (m->graphs_live > 0 || m->share->pipelines > 0) return RN_ERR_INVALID;
+    probe = *m; /* the geometry of the new size, before anything changes */
+    set_geometry(&probe, H, W);
+    if (probe.max_sub < 1) return RN_ERR_INVALID;
+    if (H == m->H && W == m->W) return RN_OK;
+    if (m->batch_cap > 0) { /* forwards still queued read the arenas */
+        rn_sync(m->ctx);
+        for (c = 0; c < RN_MAX_STREAMS - 1; ++c)
+            if (m->ctxn[c]) rn_sync(m->ctxn[c]);
+        free_acts(m);
+    }
+    set_geometry(m, H, W);
+    for (c = 0; c < m->n_convs; ++c) {
+        m->convs[c].tile[0] = m->convs[c].tile[1] = 0;
+        m->convs[c].tile_B[0] = m->convs[c].tile_B[1] = 0;
+    }
+    for (c = 0; c < m->n_blocks; ++c) {
+        m->blocks[c].pair_tile[0] = m->blocks[c].pair_tile[1] = 0;
+        m->blocks[c].pair_tile_B[0] = m->blocks[c].pair_tile_B[1] = 0;
+    }
+    m->tuned_B = 0;
+    return RN_OK;
+}
+
+int rn_model_input_size(const rn_model *m, uint64_t *H, uint64_t *W)
+{
+    if (!m) return RN_ERR_INVALID;
+    if (H) *H = m->H;
+    if (W) *W = m->W;
+    return RN_OK;
+}
+
+uint64_t rn_model_max_sub_batch(const rn_model *m) { return m ? m->max_sub : 0; }
+
 static void free_prof(rn_model *m)
 {
     uint64_t i;
@@ -400,6 +470,10 @@ int rn_model_destroy(rn_model *m)
      * its extra streams, and rn_graph_destroy unpins those contexts: the graphs go first */
     if (m->graphs_live > 0) return RN_ERR_INVALID;
     if (m->ctx) rn_sync(m->ctx);
+    if (m->share) {
+        m->share->model_alive = 0;
+        if (m->share->pipelines == 0) free(m->share);
+    }
     if (m->params) {
         for (i = 0; i < m->n_params; ++i) rn_free(m->ctx, m->params[i].dev);
     }
@@ -665,6 +739,22 @@ int rn_model_contexts(rn_model *m, rn_ctx **out, int cap)
         if (m->ctxn[k] && n < cap) out[n++] = m->ctxn[k];
     return n;
 }
+/* library-internal: the pipelines of this model (see rn_private.h) */
+void *rn_model_pipeline_attach(rn_model *m)
+{
+    if (!m) return NULL;
+    ++m->share->pipelines;
+    return m->share;
+}
+
+void rn_model_pipeline_detach(void *cell)
+{
+    struct rn_model_share *sh = (struct rn_model_share *)cell;
+    if (!sh) return;
+    --sh->pipelines;
+    if (!sh->model_alive && sh->pipelines == 0) free(sh);
+}
+
 /* library-internal: rn_model_capture / rn_graph_destroy count the graphs that hold this model */
 void rn_model_graph_ref(rn_model *m, int delta)
 {
@@ -1084,10 +1174,15 @@ static int block_forward(rn_model *m, rn_block *b, const float *x, float *y, uin
 
 /* ---- the three parts of a forward: input + stem + pool, a run of blocks, average pool + fc ---- */
 
-/* The form the stem reads its image in (x4).  bf16: [B,230,230,4] with its own 3-pixel zero border,
- * padding 0.  fp32 exact-K: [B,230,230,3] with a physical border.  fp32 otherwise: [B,224,224,4] and the
+/* The form the stem reads its image in (x4).  bf16: [B,H+6,W+6,4] with its own 3-pixel zero border,
+ * padding 0.  fp32 exact-K: [B,H+6,W+6,3] with a physical border.  fp32 otherwise: [B,H,W,4] and the
  * layer's padding.  With from_nchw the fused stem + pool fetches its patches from the caller's NCHW fp32
- * image itself and no layout launch runs (a byte image always goes through x4). */
+ * image itself and no layout launch runs (a byte image always goes through x4).
+ * The route is a function of (H, W, dtype, settings) alone, never of B: where the fused stem + pool launch
+ * does not take the size (rn_stem_pool_applies: a conv output width off a multiple of 8 or above 128, its
+ * LDS budget, an odd padded width in bf16), every launch of the model runs the stem and the max-pool as
+ * separate launches, as with rn_model_set_stem_pool_fusion(m, 0); where only the NCHW-fetching form does
+ * not (W % 4 != 0, W > 256), the padded-image form runs, which gives the same bits. */
 typedef struct {
     uint64_t cpad, border; /* channels 3 or 4; zero border 0 or 3 */
     int exact, fused_pool, from_nchw;
@@ -1100,28 +1195,30 @@ static rn_stem_form stem_form(const rn_model *m, int in_u8, int mode)
     f.exact = !bf16 && m->stem_exact;
     f.cpad = f.exact ? 3 : 4;
     f.border = bf16 || f.exact ? m->convs[0].pad : 0;
-    f.fused_pool = mode == RN_FWD_FUSED && m->stem_pool && (bf16 || f.exact);
-    f.from_nchw = f.fused_pool && m->stem_pool == 2 && !in_u8;
+    f.fused_pool = mode == RN_FWD_FUSED && m->stem_pool && (bf16 || f.exact) &&
+                   rn_stem_pool_applies(m->dtype, m->H + 2 * m->convs[0].pad, m->W + 2 * m->convs[0].pad, 0);
+    f.from_nchw = f.fused_pool && m->stem_pool == 2 && !in_u8 &&
+                  rn_stem_pool_applies(m->dtype, m->H + 2 * m->convs[0].pad, m->W + 2 * m->convs[0].pad, 1);
     return f;
 }
 
 /* The first launch: the caller's image -> the normalised (byte route) NHWC image in x4, the same bits
- * from 8-bit RGB [B,224,224,3] as from the host-normalised fp32 NCHW image. */
+ * from 8-bit RGB [B,H,W,3] as from the host-normalised fp32 NCHW image. */
 static const float kImageMean[3] = {0.485f, 0.456f, 0.406f}, kImageStd[3] = {0.229f, 0.224f, 0.225f};
 
 static int op_input(rn_model *m, const void *input, int in_u8, uint64_t B, const rn_stem_form *f)
 {
-    const double side = (double)(RN_IMAGE_SIDE + 2 * f->border);
-    const double out = (double)elem_size(m) * side * side * (double)f->cpad;
+    const double out = (double)elem_size(m) * (double)((m->H + 2 * f->border) * (m->W + 2 * f->border)) * (double)f->cpad;
+    const double in_numel = (double)(3 * m->H * m->W);
     TRY(prof_begin(m, in_u8 ? (f->cpad == 3 ? "image_u8_to_nhwc3" : "image_u8_to_nhwc4")
                             : (f->cpad == 3 ? "nchw_to_nhwc3" : "nchw_to_nhwc4"),
-                   "input", 0.0, (double)B * ((in_u8 ? 1.0 : 4.0) * RN_IMAGE_NUMEL + out)));
+                   "input", 0.0, (double)B * ((in_u8 ? 1.0 : 4.0) * in_numel + out)));
     if (in_u8)
-        TRY(rn_image_u8_to_nhwc_pad_dt(m->run.ctx, m->dtype, (const uint8_t *)input, m->run.x4, B, RN_IMAGE_SIDE,
-                                       RN_IMAGE_SIDE, f->cpad, f->border, kImageMean, kImageStd));
+        TRY(rn_image_u8_to_nhwc_pad_dt(m->run.ctx, m->dtype, (const uint8_t *)input, m->run.x4, B, m->H, m->W,
+                                       f->cpad, f->border, kImageMean, kImageStd));
     else
-        TRY(rn_nchw_to_nhwc_pad_dt(m->run.ctx, m->dtype, (const float *)input, m->run.x4, B, 3, RN_IMAGE_SIDE,
-                                   RN_IMAGE_SIDE, f->cpad, f->border));
+        TRY(rn_nchw_to_nhwc_pad_dt(m->run.ctx, m->dtype, (const float *)input, m->run.x4, B, 3, m->H, m->W,
+                                   f->cpad, f->border));
     return prof_end(m);
 }
 
@@ -1132,68 +1229,66 @@ static int op_stem_pool(rn_model *m, const rn_conv *stem, const float *input_nch
                         const rn_stem_form *f)
 {
     const double es = (double)elem_size(m);
-    const uint64_t S = RN_IMAGE_SIDE, Sp = S + 2 * f->border, ho = m->stem_side, hp = m->pool_side;
+    const uint64_t Hp = m->H + 2 * f->border, Wp = m->W + 2 * f->border;
     TRY(prof_begin(m, "conv2d+epilogue+maxpool", "conv1+maxpool",
-                   2.0 * (double)(B * ho * ho) * (double)stem->cout * (double)(stem->cin * stem->k * stem->k),
-                   (input_nchw ? 4.0 * (double)(B * S * S * stem->cin)
-                               : es * (double)(B * Sp * Sp) * (double)f->cpad) +
+                   2.0 * (double)(B * m->stem_h * m->stem_w) * (double)stem->cout *
+                       (double)(stem->cin * stem->k * stem->k),
+                   (input_nchw ? 4.0 * (double)(B * m->H * m->W * stem->cin)
+                               : es * (double)(B * Hp * Wp) * (double)f->cpad) +
                        es * ((double)(stem->cout * stem->cin * stem->k * stem->k) +
-                             (double)(B * hp * hp * stem->cout))));
+                             (double)(B * m->pool_h * m->pool_w * stem->cout))));
     if (input_nchw) /* stem_pool == 2: the patch fetch reads the caller's NCHW fp32 image itself */
         TRY(rn_stem_pool_nchw_forward_dt(m->run.ctx, m->dtype, input_nchw, m->run.p0, m->stem_pool_packed,
-                                         stem->scale, stem->shift, 1, B, stem->cin, S, S));
+                                         stem->scale, stem->shift, 1, B, stem->cin, m->H, m->W));
     else
         TRY(rn_stem_pool_forward_dt(m->run.ctx, m->dtype, m->run.x4, m->run.p0, m->stem_pool_packed, stem->scale,
-                                    stem->shift, 1, B, Sp, Sp));
+                                    stem->shift, 1, B, Hp, Wp));
     return prof_end(m);
 }
 
-/* input + stem + max-pool: the caller's images -> p0 [B,pool_side,pool_side,64] */
+/* input + stem + max-pool: the caller's images -> p0 [B,pool_h,pool_w,64] */
 static int run_front(rn_model *m, const void *input, int in_u8, uint64_t B, int mode)
 {
     const rn_conv *stem = &m->convs[0];
     const rn_stem_form f = stem_form(m, in_u8, mode);
-    const uint64_t Sp = RN_IMAGE_SIDE + 2 * f.border, ho = m->stem_side, hp = m->pool_side;
+    const uint64_t Hp = m->H + 2 * f.border, Wp = m->W + 2 * f.border;
+    const uint64_t so = m->stem_h * m->stem_w, po = m->pool_h * m->pool_w;
     rn_epilogue ep;
     if (!f.from_nchw) TRY(op_input(m, input, in_u8, B, &f));
     if (f.fused_pool) return op_stem_pool(m, stem, f.from_nchw ? (const float *)input : NULL, B, &f);
     ep.scale = stem->scale; ep.shift = stem->shift; ep.residual = NULL; ep.relu = 1;
-    TRY(op_conv_at(m, stem, m->run.x4, m->run.p1, B, Sp, Sp, mode == RN_FWD_FUSED ? &ep : NULL,
+    TRY(op_conv_at(m, stem, m->run.x4, m->run.p1, B, Hp, Wp, mode == RN_FWD_FUSED ? &ep : NULL,
                    f.border ? 0 : stem->pad, f.exact));
     if (mode != RN_FWD_FUSED) {
-        TRY(op_bn(m, stem, m->run.p1, B, ho * ho));
-        TRY(op_relu(m, "conv1", m->run.p1, B * ho * ho * stem->cout));
+        TRY(op_bn(m, stem, m->run.p1, B, so));
+        TRY(op_relu(m, "conv1", m->run.p1, B * so * stem->cout));
     }
     /* maxpool 3x3 s2 p1 (main.cu:114,192) */
     TRY(prof_begin(m, "maxpool2d", "maxpool", 0.0,
-                   (double)elem_size(m) * (double)(B * stem->cout * (ho * ho + hp * hp))));
-    TRY(rn_maxpool2d_nhwc_forward_dt(m->run.ctx, m->dtype, m->run.p1, m->run.p0, 3, 2, 1, hp, hp, B, stem->cout, ho,
-                                     ho));
+                   (double)elem_size(m) * (double)(B * stem->cout * (so + po))));
+    TRY(rn_maxpool2d_nhwc_forward_dt(m->run.ctx, m->dtype, m->run.p1, m->run.p0, 3, 2, 1, m->pool_h, m->pool_w, B,
+                                     stem->cout, m->stem_h, m->stem_w));
     return prof_end(m);
 }
 
 /* block i reads ping-pong arena i & 1 and writes the other */
 static float *block_input(const rn_model *m, int i) { return (i & 1) ? m->run.p1 : m->run.p0; }
 
-/* blocks [first, last) on a side x side map; *side becomes that of block last's input */
-static int run_blocks(rn_model *m, int first, int last, uint64_t B, uint64_t *side, int mode)
+/* blocks [first, last) on an *H x *W map, which become those of block last's input */
+static int run_blocks(rn_model *m, int first, int last, uint64_t B, uint64_t *H, uint64_t *W, int mode)
 {
-    uint64_t H = *side, W = *side;
     int bi;
     for (bi = first; bi < last; ++bi)
-        TRY(block_forward(m, &m->blocks[bi], block_input(m, bi), block_input(m, bi + 1), B, &H, &W, mode));
-    *side = H;
+        TRY(block_forward(m, &m->blocks[bi], block_input(m, bi), block_input(m, bi + 1), B, H, W, mode));
     return RN_OK;
 }
 
-/* global average over the side x side map (main.cu:120,213) then fc (main.cu:122,224) */
-static int run_head(rn_model *m, const float *x, uint64_t B, uint64_t side, float *logits)
+/* global average over the H x W map (main.cu:120,213: 7 x 7, where this is that launch) then fc (main.cu:122,224) */
+static int run_head(rn_model *m, const float *x, uint64_t B, uint64_t H, uint64_t W, float *logits)
 {
     const double es = (double)elem_size(m);
-    TRY(prof_begin(m, "avgpool2d", "avgpool", 0.0, es * (double)(B * m->feat * (side * side + 1))));
-    TRY(rn_avgpool2d_nhwc_forward_dt(m->run.ctx, m->dtype, x, m->run.pooled, side, 1, 0,
-                                     rn_conv_output_size(side, side, 1, 0), rn_conv_output_size(side, side, 1, 0), B,
-                                     m->feat, side, side));
+    TRY(prof_begin(m, "avgpool2d", "avgpool", 0.0, es * (double)(B * m->feat * (H * W + 1))));
+    TRY(rn_global_avgpool_nhwc_forward_dt(m->run.ctx, m->dtype, x, m->run.pooled, B, m->feat, H, W));
     TRY(prof_end(m));
     TRY(prof_begin(m, "linear", "fc", 2.0 * (double)B * (double)m->feat * (double)m->classes,
                    es * ((double)(B * m->feat) + (double)m->feat * (double)m->classes) +
@@ -1248,10 +1343,10 @@ static int forward_phase(rn_model *m, const void *input, int in_u8, uint64_t B, 
 {
     const int first = phase == RN_PHASE_BACK ? m->depths[0] : 0;
     const int last = phase == RN_PHASE_FRONT ? m->depths[0] : m->n_blocks;
-    uint64_t side = m->pool_side; /* the first stage keeps it (stride 1): the back starts there too */
+    uint64_t H = m->pool_h, W = m->pool_w; /* the first stage keeps them (stride 1): the back starts there too */
     if (phase != RN_PHASE_BACK) TRY(run_front(m, input, in_u8, B, mode));
-    TRY(run_blocks(m, first, last, B, &side, mode));
-    if (phase != RN_PHASE_FRONT) TRY(run_head(m, block_input(m, last), B, side, logits));
+    TRY(run_blocks(m, first, last, B, &H, &W, mode));
+    if (phase != RN_PHASE_FRONT) TRY(run_head(m, block_input(m, last), B, H, W, logits));
     return RN_OK;
 }
 
@@ -1275,22 +1370,20 @@ static int forward_sub(rn_model *m, rn_ctx *run, uint64_t img_off, uint64_t slic
  * a count the caller set (rn_model_set_streams) is taken down to parts of 64 */
 #define RN_STREAM_MIN_PART(m) ((m)->dtype == RN_DTYPE_F32 && !(m)->streams_set ? 128u : 64u)
 
-#define RN_MAX_SUB_BATCH 512 /* images per launch batch: see rn_model_forward */
-
 /* parts (streams) a launch batch of B images runs as */
 static int parts_of(const rn_model *m, uint64_t B)
 {
     int parts = m->streams;
-    if (B > RN_MAX_SUB_BATCH) B = RN_MAX_SUB_BATCH;
+    if (B > m->max_sub) B = m->max_sub; /* images per launch batch: see rn_model_forward */
     while (parts > 1 && B / (uint64_t)parts < RN_STREAM_MIN_PART(m)) parts /= 2;
     return parts;
 }
 #define RN_FRONT_MIN_SLICE 16
 
 /* image `lo` of the caller's input: fp32 NCHW, or 8-bit RGB on the byte route */
-static const void *input_at(const void *input, int in_u8, uint64_t lo)
+static const void *input_at(const rn_model *m, const void *input, int in_u8, uint64_t lo)
 {
-    return (const char *)input + lo * RN_IMAGE_NUMEL * (in_u8 ? 1 : sizeof(float));
+    return (const char *)input + lo * 3 * m->H * m->W * (in_u8 ? 1 : sizeof(float));
 }
 
 /* B images at image offset img_off on `run`: whole, or depth-first through the front */
@@ -1303,7 +1396,7 @@ static int forward_part(rn_model *m, rn_ctx *run, uint64_t img_off, const void *
     if (fp < 2) return forward_sub(m, run, img_off, 0, input, in_u8, B, logits, mode, RN_PHASE_ALL);
     for (j = 0; j < fp; ++j) {
         const uint64_t hi = B * (uint64_t)(j + 1) / (uint64_t)fp;
-        TRY(forward_sub(m, run, img_off, lo, input_at(input, in_u8, lo), in_u8, hi - lo, logits, mode,
+        TRY(forward_sub(m, run, img_off, lo, input_at(m, input, in_u8, lo), in_u8, hi - lo, logits, mode,
                         RN_PHASE_FRONT));
         lo = hi;
     }
@@ -1335,7 +1428,7 @@ static int forward_chunk(rn_model *m, const void *input, int in_u8, uint64_t B, 
         const uint64_t hi = B * (uint64_t)(i + 1) / (uint64_t)parts;
         rn_ctx *run = i == 0 ? m->ctx : m->ctxn[i - 1];
         if (i > 0) TRY(rn_ctx_wait_event(run, m->ev_fork));
-        TRY(forward_part(m, run, lo, input_at(input, in_u8, lo), in_u8, hi - lo, logits + lo * m->classes,
+        TRY(forward_part(m, run, lo, input_at(m, input, in_u8, lo), in_u8, hi - lo, logits + lo * m->classes,
                          mode));
         if (i > 0) TRY(rn_event_record(run, m->ev_join[i - 1]));
         lo = hi;
@@ -1375,12 +1468,12 @@ static int head_outputs(rn_model *m, const rn_model_outputs *o, uint64_t done, u
 }
 
 /* The reference has no batch limit other than memory (main.cu:168-226).  Here the contraction
- * kernels address every tensor with 32-bit byte offsets (2^29 fp32 elements; the stem output
- * of 669 images is the first to pass it), so a larger batch runs as sub-batches of at most
- * RN_MAX_SUB_BATCH images through the same arenas.  Every image's logits are independent of
- * what else is in its launch (batch invariance, bit for bit), so the split changes nothing.
- * (RN_MAX_SUB_BATCH is defined above, next to the stream split.)
- * in_u8: the input is 8-bit RGB [B,224,224,3], not fp32 NCHW; prof_keep: see forward_chunk (the
+ * kernels address every tensor with 32-bit byte offsets (2^29 fp32 elements; at 224 x 224 the stem
+ * output of 669 images is the first to pass it), so a larger batch runs as sub-batches of at most
+ * m->max_sub images (set_geometry: 512 at 224 x 224, fewer for larger images) through the same arenas.
+ * Every image's logits are independent of what else is in its launch (batch invariance, bit for bit), so
+ * the split changes nothing.
+ * in_u8: the input is 8-bit RGB [B,H,W,3], not fp32 NCHW; prof_keep: see forward_chunk (the
  * first sub-batch only).  outs (rn_model_forward_outputs, NULL otherwise): what to write besides the
  * logits; with logits == NULL those of a sub-batch go to a buffer the model owns. */
 static int forward_outputs(rn_model *m, const void *input, int in_u8, uint64_t B, float *logits,
@@ -1398,7 +1491,7 @@ static int forward_outputs(rn_model *m, const void *input, int in_u8, uint64_t B
             return RN_ERR_INVALID;
     }
     if (!logits) {
-        const uint64_t need = B < RN_MAX_SUB_BATCH ? B : RN_MAX_SUB_BATCH;
+        const uint64_t need = B < m->max_sub ? B : m->max_sub;
         if (need > m->own_logits_cap) { /* grows like the arenas: never under a capture or a live graph */
             if (rn_ctx_is_capturing(m->ctx)) return RN_ERR_UNSUPPORTED;
             if (m->own_logits_cap > 0 && rn_ctx_graphs_live(m->ctx) > 0) return RN_ERR_INVALID;
@@ -1410,9 +1503,9 @@ static int forward_outputs(rn_model *m, const void *input, int in_u8, uint64_t B
         }
     }
     while (done < B) {
-        const uint64_t nb = B - done < RN_MAX_SUB_BATCH ? B - done : RN_MAX_SUB_BATCH;
+        const uint64_t nb = B - done < m->max_sub ? B - done : m->max_sub;
         float *sub = logits ? logits + done * m->classes : m->own_logits;
-        TRY(forward_chunk(m, input_at(input, in_u8, done), in_u8, nb, sub, mode, prof_keep && done == 0));
+        TRY(forward_chunk(m, input_at(m, input, in_u8, done), in_u8, nb, sub, mode, prof_keep && done == 0));
         if (outs) TRY(head_outputs(m, outs, done, nb, sub));
         done += nb;
     }
@@ -1448,6 +1541,16 @@ int rn_model_forward_outputs_u8(rn_model *m, const uint8_t *input_nhwc, uint64_t
     return forward_outputs(m, input_nhwc, 1, B, outs->logits, outs, mode, 0);
 }
 
+/* The decoded-image route resizes to 256 and crops 224 x 224: a model of another size refuses it. */
+static int default_size(const rn_model *m) { return m->H == RN_DEFAULT_SIDE && m->W == RN_DEFAULT_SIDE; }
+
+static int images_need_default(rn_model *m)
+{
+    return rn_ctx_set_error(m->ctx, RN_ERR_UNSUPPORTED,
+                            "decoded images are resized to 256 and cropped to 224 x 224: the model's input size is "
+                            "another (rn_model_set_input_size); crop them yourself and use rn_model_forward_u8");
+}
+
 /* Decoded images whose tables are on the device already (the host pipeline stages them with the batch):
  * one resize launch for the whole batch on the model's stream, then the byte route on the crops.
  * src_bytes: what the launch reads, for the profile record. */
@@ -1458,18 +1561,20 @@ int rn_model_forward_images_table(rn_model *m, const uint8_t *packed_dev, const 
     if (mode != RN_FWD_REFERENCE_OPS && mode != RN_FWD_FUSED) return RN_ERR_INVALID;
     if (!m->finalized) return RN_ERR_INVALID;
     if (m->dtype != RN_DTYPE_F32 && mode != RN_FWD_FUSED) return RN_ERR_UNSUPPORTED;
+    if (!default_size(m)) return images_need_default(m);
     if (B > m->crops_cap) {
         if (m->crops_cap > 0 && rn_ctx_graphs_live(m->ctx) > 0) return RN_ERR_INVALID;
         if (m->crops) TRY(rn_free(m->ctx, m->crops));
         m->crops = NULL;
         m->crops_cap = 0;
-        TRY(rn_malloc(m->ctx, (void **)&m->crops, B * RN_IMAGE_NUMEL));
+        TRY(rn_malloc(m->ctx, (void **)&m->crops, B * 3 * RN_DEFAULT_SIDE * RN_DEFAULT_SIDE));
         m->crops_cap = B;
     }
     run_begin(m, m->ctx, 0, 0, mode);
     m->n_prof = 0;
-    TRY(prof_begin(m, "image_u8_resize_crop", "input", 0.0, src_bytes + (double)B * RN_IMAGE_NUMEL));
-    TRY(rn_image_u8_resize_crop_launch(m->ctx, packed_dev, table_dev, B, m->crops, RN_IMAGE_SIDE));
+    TRY(prof_begin(m, "image_u8_resize_crop", "input", 0.0,
+                   src_bytes + (double)B * 3.0 * RN_DEFAULT_SIDE * RN_DEFAULT_SIDE));
+    TRY(rn_image_u8_resize_crop_launch(m->ctx, packed_dev, table_dev, B, m->crops, RN_DEFAULT_SIDE));
     TRY(prof_end(m));
     return forward_any(m, m->crops, 1, B, logits, mode, 1); /* keeps the resize launch's record */
 }
@@ -1477,19 +1582,20 @@ int rn_model_forward_images_table(rn_model *m, const uint8_t *packed_dev, const 
 int rn_model_forward_images_u8(rn_model *m, const uint8_t *packed_dev, const uint64_t *offsets,
                                const uint64_t *heights, const uint64_t *widths, uint64_t B, float *logits, int mode)
 {
-    const double crop = (double)RN_IMAGE_SIDE / RN_RESIZE_SIDE;
+    const double crop = (double)RN_DEFAULT_SIDE / RN_RESIZE_SIDE;
     uint64_t bytes = 0, i;
     double src_bytes = 0.0;
     void *host, *dev = NULL;
     int st;
     if (!m || !packed_dev || !offsets || !heights || !widths || !logits || B == 0) return RN_ERR_INVALID;
-    if (rn_image_u8_resize_crop_table(offsets, heights, widths, B, RN_RESIZE_SIDE, RN_IMAGE_SIDE, NULL, 0, &bytes) !=
+    if (!default_size(m)) return images_need_default(m);
+    if (rn_image_u8_resize_crop_table(offsets, heights, widths, B, RN_RESIZE_SIDE, RN_DEFAULT_SIDE, NULL, 0, &bytes) !=
         RN_OK)
         return RN_ERR_INVALID;
     if (rn_ctx_is_capturing(m->ctx)) return RN_ERR_UNSUPPORTED; /* the tables come from host memory freed below */
     host = malloc(bytes);
     if (!host) return RN_ERR_NOMEM;
-    st = rn_image_u8_resize_crop_table(offsets, heights, widths, B, RN_RESIZE_SIDE, RN_IMAGE_SIDE, host, bytes, &bytes);
+    st = rn_image_u8_resize_crop_table(offsets, heights, widths, B, RN_RESIZE_SIDE, RN_DEFAULT_SIDE, host, bytes, &bytes);
     if (st == RN_OK) st = rn_ctx_scratch_slot(m->ctx, 5, bytes, &dev);
     if (st == RN_OK) st = rn_ctx_upload_sync(m->ctx, dev, host, bytes);
     free(host);
@@ -1569,7 +1675,7 @@ int rn_model_tune(rn_model *m, const float *input_nchw, uint64_t B, float *logit
     uint64_t Bp;
     int c, st;
     if (!m) return RN_ERR_INVALID;
-    if (B > RN_MAX_SUB_BATCH) B = RN_MAX_SUB_BATCH; /* the launches of a larger batch are sub-batches */
+    if (B > m->max_sub) B = m->max_sub; /* the launches of a larger batch are sub-batches */
     Bp = B;
     {   /* ... and those run as `streams` parts */
         const int parts = parts_of(m, B);
@@ -1595,13 +1701,22 @@ int rn_model_tune(rn_model *m, const float *input_nchw, uint64_t B, float *logit
  * timing every candidate again: the shards of a node (rn_shard_tune tunes ONE shard), or a later
  * process.  Tiles only change speed, never bits, so a stale table costs time, not parity. */
 #define RN_TUNING_MAGIC 0x726e54554e453034ull /* "rnTUNE04" */
-#define RN_TUNING_HEADER 10
+#define RN_TUNING_HEADER 10 /* of a 224 x 224 model; a model of another size appends tuning_size */
 
 /* header word 9: 0 for the plain (1, 64) networks, whose tables keep their format */
 static uint64_t tuning_family(const rn_model *m)
 {
     return m->groups == 1 && m->width_per_group == 64 ? 0 : (uint64_t)m->groups << 32 | (uint64_t)m->width_per_group;
 }
+
+/* header word 10, present only when not 0: 0 for 224 x 224 models, whose tables keep their format.  A table and
+ * a model of different sizes differ in this word or in the table's length. */
+static uint64_t tuning_size(const rn_model *m)
+{
+    return m->H == RN_DEFAULT_SIDE && m->W == RN_DEFAULT_SIDE ? 0 : m->H << 32 | m->W;
+}
+
+static uint64_t tuning_header(const rn_model *m) { return RN_TUNING_HEADER + (tuning_size(m) ? 1 : 0); }
 
 static uint64_t tuning_settings(const rn_model *m)
 {
@@ -1614,7 +1729,7 @@ int rn_model_export_tuning(const rn_model *m, uint64_t *words, uint64_t cap, uin
     uint64_t need, at = 0;
     int c, k;
     if (!m || !n_words) return RN_ERR_INVALID;
-    need = RN_TUNING_HEADER + 4 * ((uint64_t)m->n_convs + (uint64_t)m->n_blocks);
+    need = tuning_header(m) + 4 * ((uint64_t)m->n_convs + (uint64_t)m->n_blocks);
     *n_words = need;
     if (!words) return RN_OK; /* size query */
     if (cap < need || !m->tuned_B) return RN_ERR_INVALID;
@@ -1628,6 +1743,7 @@ int rn_model_export_tuning(const rn_model *m, uint64_t *words, uint64_t cap, uin
     words[at++] = (uint64_t)m->n_blocks;
     words[at++] = (uint64_t)rn_conv_tile_candidates();
     words[at++] = tuning_family(m);
+    if (tuning_size(m)) words[at++] = tuning_size(m);
     for (c = 0; c < m->n_convs; ++c)
         for (k = 0; k < 2; ++k) {
             words[at++] = (uint64_t)m->convs[c].tile[k];
@@ -1643,14 +1759,16 @@ int rn_model_export_tuning(const rn_model *m, uint64_t *words, uint64_t cap, uin
 
 int rn_model_import_tuning(rn_model *m, const uint64_t *words, uint64_t n_words)
 {
-    uint64_t at = RN_TUNING_HEADER;
+    uint64_t at;
     int c, k;
-    if (!m || !words || n_words < RN_TUNING_HEADER) return RN_ERR_INVALID;
+    if (!m || !words || n_words < tuning_header(m)) return RN_ERR_INVALID;
+    at = tuning_header(m);
     if (words[0] != RN_TUNING_MAGIC || words[1] != (uint64_t)m->arch || words[2] != (uint64_t)m->dtype ||
         words[3] != tuning_settings(m) || words[6] != (uint64_t)m->n_convs || words[7] != (uint64_t)m->n_blocks ||
         words[8] != (uint64_t)rn_conv_tile_candidates() || words[9] != tuning_family(m) ||
-        n_words != RN_TUNING_HEADER + 4 * ((uint64_t)m->n_convs + (uint64_t)m->n_blocks))
-        return RN_ERR_INVALID; /* measured for another model, setting or build */
+        (tuning_size(m) && words[RN_TUNING_HEADER] != tuning_size(m)) ||
+        n_words != at + 4 * ((uint64_t)m->n_convs + (uint64_t)m->n_blocks))
+        return RN_ERR_INVALID; /* measured for another model, size, setting or build */
     for (c = 0; c < m->n_convs + m->n_blocks; ++c) /* a candidate this build does not have */
         if (words[at + 4 * (uint64_t)c] > (uint64_t)rn_conv_tile_candidates() ||
             words[at + 4 * (uint64_t)c + 2] > (uint64_t)rn_conv_tile_candidates())

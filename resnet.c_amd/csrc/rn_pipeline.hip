@@ -35,11 +35,12 @@ struct rn_pipeline_slot {
 
 struct rn_pipeline {
     rn_model *model;
+    void *model_cell;  // rn_model_pipeline_attach: the model counts this pipeline (its buffers are sized for the model's input)
     rn_ctx *ctx;
     uint64_t B;
     uint64_t classes;  // the model's class count when the pipeline was created: the row length of d_out / h_out
     int mode;
-    int u8;            // input format: 0 = fp32 NCHW, 1 = 8-bit RGB [B,224,224,3] (rn_pipeline_create_u8),
+    int u8;            // input format: 0 = fp32 NCHW, 1 = 8-bit RGB [B,H,W,3] (rn_pipeline_create_u8),
                        // 2 = decoded 8-bit RGB images of any size (rn_pipeline_create_images_u8)
     size_t img_bytes;  // of one image in that format (formats 0 and 1)
     size_t max_bytes;  // format 2: pixels of one batch; the tables sit at table_off = max_bytes rounded up to 16
@@ -145,6 +146,7 @@ int rn_pipeline_destroy(rn_pipeline *p)
         if (s->done) (void)hipEventDestroy(s->done);
     }
     if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
+    rn_model_pipeline_detach(p->model_cell);
     free(p);
     return RN_OK;
 }
@@ -154,15 +156,22 @@ static int pipeline_create(rn_model *m, rn_pipeline **out, uint64_t B, int mode,
     if (!m || !out || B == 0 || (u8 == 2 && max_batch_bytes == 0)) return RN_ERR_INVALID;
     *out = nullptr;
     rn_ctx *ctx = rn_model_context(m);
+    uint64_t H = 0, W = 0;
+    rn_model_input_size(m, &H, &W);
+    if (u8 == 2 && (H != 224 || W != 224))
+        return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "rn_pipeline_create_images_u8: decoded images are resized to 256 and "
+                            "cropped to 224 x 224; the model's input size is %llu x %llu",
+                            (unsigned long long)H, (unsigned long long)W);
     rn_pipeline *p = (rn_pipeline *)calloc(1, sizeof(rn_pipeline));
     if (!p) return RN_ERR_NOMEM;
     p->model = m;
+    p->model_cell = rn_model_pipeline_attach(m);
     p->ctx = ctx;
     p->B = B;
     p->classes = rn_model_classes(m);
     p->mode = mode;
     p->u8 = u8;
-    p->img_bytes = (size_t)3 * 224 * 224 * (u8 ? sizeof(uint8_t) : sizeof(float));
+    p->img_bytes = (size_t)(3 * H * W) * (u8 ? sizeof(uint8_t) : sizeof(float));  // the model's size now: it stays while this pipeline lives
     {
         const char *ct = getenv("RN_COPY_THREADS");
         const int n = ct ? atoi(ct) : 3;
@@ -262,7 +271,7 @@ static int submit_n(rn_pipeline *p, const void *host_input, uint64_t n, int u8, 
     const size_t in_bytes = (size_t)n * p->img_bytes;
     const int st = [&]() -> int {
         if (host_input && host_input != s->h_in) {
-            // pageable -> pinned -> device in pieces of 16 images (9.6 MB of fp32, 2.4 MB of bytes): the upload of piece i runs on the
+            // pageable -> pinned -> device in pieces of 16 images (at 224 x 224 9.6 MB of fp32, 2.4 MB of bytes): the upload of piece i runs on the
             // copy stream while piece i+1 is being copied, so a batch costs max(copy, upload) instead of their
             // sum before its forward can start.  One core copies a 154 MB fp32 batch in 6-7 ms (23 GB/s), which
             // is longer than its upload (3.8 ms) and than a bf16 forward (3.3 ms): the pieces are copied by

@@ -208,6 +208,82 @@ __global__ __launch_bounds__(kBlock) void avgpool_global_kernel(const void *__re
     }
 }
 
+// Global average over ANY H x W map: [B,H,W,C] -> [B,C], one output pixel per image, T = H * W taps.
+// As in avgpool_global_kernel a lane owns V = 16 bytes of channels and memory parallelism is all the launch
+// has, but T is no template constant and may be large (a 512 x 512 image ends in 16 x 16 = 256 taps): the
+// taps of one output are dealt to S lanes of one block, so that neither a lane's chain of loads is long nor
+// the launch a handful of such chains when B * C / 4 is small.
+//
+// Summation order -- a function of (H, W) only, never of B, the grid or the image's place in the batch:
+//   T = H * W, taps numbered t = h * W + w (memory order);
+//   S = the smallest power of two >= ceil(T / 16), at most 16;  L = ceil(T / S);
+//   slice s = taps [s * L, min(T, (s + 1) * L)), for s = 0 .. ceil(T / L) - 1 (the non-empty slices);
+//   p_s   = ((0 + x[first]) + x[first + 1]) + ...      fp32, ascending t within the slice;
+//   sum   = (p_0 + p_1) + p_2 + ...                    fp32, ascending s;
+//   out   = sum / (float)T                             fp32, then rounded once to the storage type.
+// A slice is read in chunks of kGapChunk taps: every load of a chunk is issued before its first add (the
+// chunking changes no order).  The last chunk of a slice repeats its last tap's load instead of branching
+// and leaves the repeats out of the sum.
+constexpr int kGapChunk = 16;
+
+static void gap_split(uint64_t T, int *S, int *L)
+{
+    int s = 1;
+    while (s < 16 && (uint64_t)s * kGapChunk < T) s *= 2;
+    *S = s;
+    *L = (int)rn_ceil_div(T, (uint64_t)s);
+}
+
+template <typename E, int N>
+__global__ __launch_bounds__(kBlock) void global_avgpool_kernel(const void *__restrict__ inp, void *__restrict__ outp,
+                                                                int CV, int T, int S, int L, float tf, uint64_t total)
+{
+    typedef E V __attribute__((ext_vector_type(N)));
+    __shared__ float part[kBlock * N];  // [S][lanes][N]
+    const V *in = static_cast<const V *>(inp);
+    V *out = static_cast<V *>(outp);
+    const int lanes = kBlock / S;  // outputs (b, 16 bytes of channels) of this block
+    const int s = (int)threadIdx.x / lanes, l = (int)threadIdx.x - s * lanes;
+    const uint64_t o = (uint64_t)blockIdx.x * (uint64_t)lanes + (uint64_t)l;
+    const int t0 = s * L, t1 = min(T, t0 + L);
+    float acc[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) acc[j] = 0.f;
+    if (o < total && t0 < t1) {
+        const uint64_t b = o / (uint64_t)CV, c = o - b * (uint64_t)CV;
+        const V *src = in + b * (uint64_t)T * (uint64_t)CV + c;
+        for (int t = t0; t < t1; t += kGapChunk) {
+            const int n = min(kGapChunk, t1 - t);
+            V v[kGapChunk];
+#pragma unroll
+            for (int i = 0; i < kGapChunk; ++i)
+                v[i] = __builtin_nontemporal_load(src + (uint64_t)(t + min(i, n - 1)) * (uint64_t)CV);
+            __builtin_amdgcn_sched_barrier(0);  // every load of the chunk issued before the first add
+#pragma unroll
+            for (int i = 0; i < kGapChunk; ++i)
+                if (i < n) {
+#pragma unroll
+                    for (int j = 0; j < N; ++j) acc[j] += (float)v[i][j];
+                }
+        }
+    }
+    if (S > 1) {  // uniform over the block
+#pragma unroll
+        for (int j = 0; j < N; ++j) part[threadIdx.x * N + j] = acc[j];
+        __syncthreads();
+        if (s != 0) return;
+        const int used = (T + L - 1) / L;  // non-empty slices
+        for (int q = 1; q < used; ++q)
+#pragma unroll
+            for (int j = 0; j < N; ++j) acc[j] += part[(q * lanes + l) * N + j];
+    }
+    if (o >= total) return;
+    V ov;
+#pragma unroll
+    for (int j = 0; j < N; ++j) ov[j] = (E)(acc[j] / tf);
+    out[o] = ov;
+}
+
 // 3x3 max-pool whose every window holds at least one real pixel (the network's pool after the
 // stem, ops.cu:50-78 with k 3, stride 2, padding 1).  A padded tap is replaced by the nearest
 // pixel inside the image, which is a tap of the same window already, so the maximum -- NaN
@@ -544,6 +620,44 @@ int rn_avgpool2d_forward(rn_ctx *ctx, const float *inp, float *out, uint64_t ker
 {
     return pool_dispatch<false>(ctx, inp, out, kernel_size, stride, padding, h_out, w_out, B,
                                 channels, H, W, "rn_avgpool2d_forward");
+}
+
+int rn_global_avgpool_nhwc_forward_dt(rn_ctx *ctx, int dtype, const void *inp, void *out, uint64_t B,
+                                      uint64_t channels, uint64_t H, uint64_t W)
+{
+    RN_ENTER(ctx);
+    const bool bf = dtype == RN_DTYPE_BF16;
+    RN_REQUIRE(ctx, bf || dtype == RN_DTYPE_F32, "unknown dtype");
+    const uint64_t total = B * channels;
+    if (total == 0 || H == 0 || W == 0) return RN_OK;
+    RN_REQUIRE(ctx, inp && out && inp != out, "null or aliased tensor");
+    RN_REQUIRE(ctx, H < (1u << 15) && W < (1u << 15) && channels < (1u << 30) && B < (1ull << 31), "dimension out of range");
+    const uint64_t N = bf ? 8 : 4, T = H * W;
+    RN_REQUIRE(ctx, channels % N == 0, bf ? "bf16 pooling needs C % 8 == 0" : "fp32 NHWC pooling needs C % 4 == 0");
+    RN_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(inp) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
+               "tensors must be 16-byte aligned");
+    const uint64_t CV = channels / N, totalv = total / N;
+    RN_REQUIRE(ctx, totalv < (1ull << 32) && B * T * CV < (1ull << 40), "tensor too large");
+    if (H == 7 && W == 7) {  // the network's 224 x 224 head: the kernel and the bits of rn_avgpool2d_nhwc_forward_dt
+        if (bf)
+            avgpool_global_kernel<bf16_t, 8, 49><<<rn_stream_grid(totalv, kBlock), kBlock, 0, ctx->stream>>>(
+                inp, out, (int)CV, 7.f, totalv);
+        else
+            avgpool_global_kernel<float, 4, 49><<<rn_stream_grid(totalv, kBlock), kBlock, 0, ctx->stream>>>(
+                inp, out, (int)CV, 7.f, totalv);
+        return rn_after_launch(ctx, "rn_global_avgpool_nhwc_forward_dt");
+    }
+    int S, L;
+    gap_split(T, &S, &L);
+    const uint64_t blocks = rn_ceil_div(totalv, (uint64_t)(kBlock / S));
+    RN_REQUIRE(ctx, blocks < (1ull << 31), "too many blocks");
+    if (bf)
+        global_avgpool_kernel<bf16_t, 8><<<(unsigned)blocks, kBlock, 0, ctx->stream>>>(inp, out, (int)CV, (int)T, S, L,
+                                                                                      (float)T, totalv);
+    else
+        global_avgpool_kernel<float, 4><<<(unsigned)blocks, kBlock, 0, ctx->stream>>>(inp, out, (int)CV, (int)T, S, L,
+                                                                                     (float)T, totalv);
+    return rn_after_launch(ctx, "rn_global_avgpool_nhwc_forward_dt");
 }
 
 }  // extern "C"

@@ -18,6 +18,8 @@ int rn_ctx_graphs_live(const rn_ctx *ctx);
 int rn_ctx_wait_event(rn_ctx *ctx, rn_event *ev);
 int rn_ctx_scratch_slot(rn_ctx *ctx, int slot, uint64_t bytes, void **ptr);
 int rn_ctx_is_capturing(rn_ctx *ctx);
+/* sets the text rn_last_error returns; returns status */
+int rn_ctx_set_error(rn_ctx *ctx, int status, const char *msg);
 /* pageable host memory -> device on the context's stream, over when the call returns */
 int rn_ctx_upload_sync(rn_ctx *ctx, void *dev, const void *host, uint64_t bytes);
 
@@ -28,6 +30,11 @@ int rn_linear_direct_forward(rn_ctx *ctx, const float *inp, float *out, const fl
 /* n bf16 values as fp32 (exact): the pooled features of a bf16 model */
 int rn_widen_bf16_forward(rn_ctx *ctx, const void *src_bf16, float *dst, uint64_t n);
 
+/* ---- rn_stem.hip ---- */
+/* 1 when the fused stem + max-pool launch takes a padded image of Hp x Wp (nchw: the NCHW-fetching form on
+ * an image of Hp - 6 x Wp - 6) of `dtype`: its documented conditions on the geometry alone */
+int rn_stem_pool_applies(int dtype, uint64_t Hp, uint64_t Wp, int nchw);
+
 /* ---- rn_model.c: what the pipeline and the graph capture (rn_pipeline.hip) need of a model ---- */
 /* the model keeps its context private; the pipeline queues on its compute stream */
 rn_ctx *rn_model_context(rn_model *m);
@@ -36,6 +43,11 @@ int rn_model_profiling_enabled(const rn_model *m);
 int rn_model_contexts(rn_model *m, rn_ctx **out, int cap);
 /* rn_model_capture / rn_graph_destroy count the graphs that hold the model */
 void rn_model_graph_ref(rn_model *m, int delta);
+/* rn_pipeline_create* / rn_pipeline_destroy count the pipelines whose buffers are sized for the model's input
+ * (rn_model_set_input_size is refused while one lives).  attach returns the counter's cell, which outlives the
+ * model when the model is destroyed first; detach takes that cell, not the model. */
+void *rn_model_pipeline_attach(rn_model *m);
+void rn_model_pipeline_detach(void *cell);
 /* decoded images whose resize tables are on the device already */
 int rn_model_forward_images_table(rn_model *m, const uint8_t *packed_dev, const void *table_dev, uint64_t B,
                                   double src_bytes, float *logits, int mode);

@@ -41,6 +41,7 @@
 
 #include "rn_conv_params.h"
 #include "rn_lds_dma.h"
+#include "rn_private.h"
 
 using namespace rn_gemm;
 
@@ -648,6 +649,25 @@ int rn_stem_pool_nchw_forward_dt(rn_ctx *ctx, int dtype, const float *inp_nchw, 
     RN_ENTER(ctx);
     return stem_pool_launch(ctx, dtype, inp_nchw, out, packed_weight, scale, shift, relu, B, H + 6, W + 6, true,
                             in_channels, "rn_stem_pool_nchw_forward_dt");
+}
+
+// Library-internal (rn_private.h): 1 when stem_pool_launch takes a padded image of Hp x Wp (nchw: an NCHW
+// image of Hp - 6 x Wp - 6) of `dtype` -- the geometric conditions it checks above, nothing about the
+// pointers or B.  The model driver picks its stem route from this.
+int rn_stem_pool_applies(int dtype, uint64_t Hp, uint64_t Wp, int nchw)
+{
+    if (dtype != RN_DTYPE_F32 && dtype != RN_DTYPE_BF16) return 0;
+    if (Hp < 7 || Wp < 7 || Hp >= (1u << 14) || Wp >= (1u << 14)) return 0;
+    const uint64_t Wo = rn_conv_output_size(Wp, 7, 2, 0), PW = rn_conv_output_size(Wo, 3, 2, 1);
+    if (Wo % 8 != 0 || Wo / 8 > 4 * kMaxTiles) return 0;
+    const bool bf = dtype == RN_DTYPE_BF16;
+    const uint64_t es = bf ? 2 : 4, cs = bf ? 4 : 3;
+    if (nchw && ((Wp - 6) % 4 != 0 || (Wp - 6) / 4 > 64)) return 0;
+    if (!nchw && bf && (Wp * cs * es) % 16 != 0) return 0;
+    uint64_t lrow = Wp * cs * es;
+    if (bf) lrow += (64 + 128 - (lrow & 127)) & 127;
+    const uint64_t patch = 48 + ((kPatchRows * lrow + 15) & ~15ull);
+    return patch <= 48 * 1024 && 2 * patch + kRing * PW * kCout * sizeof(float) <= 160 * 1024;
 }
 
 // the same launch writing the stem tensor as well: stem_out [B,Ho,Wo,64] = relu(bn(conv)) in NHWC, fp32

@@ -210,9 +210,11 @@ def argmax(logits: np.ndarray) -> np.ndarray:
 class NativeModel:
     def __init__(self, arch: str = "resnet50", state: Optional[Dict[str, np.ndarray]] = None,
                  weights_dir: Optional[str] = None, ctx: Optional[Context] = None,
-                 dtype: str = "f32", classes: Optional[int] = None):
+                 dtype: str = "f32", classes: Optional[int] = None,
+                 input_size: Optional[Tuple[int, int]] = None):
         """classes: rows of the classifier; None = state["fc.weight"].shape[0] when a state is given,
-        otherwise the library's 1000."""
+        otherwise the library's 1000.  input_size: (H, W) of the images every forward reads, 32..2048 each;
+        None = the library's 224 x 224 (set_input_size changes it later: the weights do not depend on it)."""
         self.ctx = ctx or get_ctx()
         self.arch = arch
         lib = L.lib()
@@ -243,6 +245,32 @@ class NativeModel:
         L.check(lib.rn_model_set_dtype(h, {"f32": L.RN_DTYPE_F32, "bf16": L.RN_DTYPE_BF16}[dtype]),
                 "rn_model_set_dtype", self.ctx.handle)
         L.check(lib.rn_model_finalize(h), "rn_model_finalize", self.ctx.handle)
+        if input_size is not None:
+            self.set_input_size(*input_size)
+
+    def set_input_size(self, H: int, W: int) -> None:
+        """Images of H x W from the next forward on (rn_model_set_input_size): 32..2048 each.  Refused
+        (RnError, nothing changed) out of range and while a Graph or a Pipeline of this model lives.  Frees
+        the activation arenas and drops the tuned tiles."""
+        L.check(L.lib().rn_model_set_input_size(self.handle, int(H), int(W)),
+                "rn_model_set_input_size: sides 32..2048, no live Graph or Pipeline", self.ctx.handle)
+
+    @property
+    def input_size(self) -> Tuple[int, int]:
+        """(H, W) of the images the forwards read: (224, 224) unless set otherwise."""
+        h, w = ctypes.c_uint64(), ctypes.c_uint64()
+        L.check(L.lib().rn_model_input_size(self.handle, ctypes.byref(h), ctypes.byref(w)), "rn_model_input_size")
+        return int(h.value), int(w.value)
+
+    def max_sub_batch(self) -> int:
+        """Images per launch batch at the model's input size (rn_model_max_sub_batch): 512 at 224 x 224, a
+        smaller power of two for larger images; a larger batch runs as sub-batches, same bits."""
+        return int(L.lib().rn_model_max_sub_batch(self.handle))
+
+    def _check_input(self, x: np.ndarray, u8: bool = False) -> None:
+        H, W = self.input_size
+        want = (H, W, 3) if u8 else (3, H, W)
+        assert x.ndim == 4 and tuple(x.shape[1:]) == want, (x.shape, "the model's input_size is", (H, W))
 
     @property
     def classes(self) -> int:
@@ -257,13 +285,13 @@ class NativeModel:
                         topk: int = 0, fused: bool = True) -> dict:
         """One forward, several outputs (rn_model_forward_outputs): a dict with the requested of
         "logits" [B,classes], "features" [B,features], "probs" [B,classes], "topk_prob" / "topk_idx" [B,topk].
-        x: fp32 NCHW [B,3,224,224], or uint8 NHWC [B,224,224,3] (normalised on the device)."""
+        x: fp32 NCHW [B,3,H,W], or uint8 NHWC [B,H,W,3] (normalised on the device), H x W = input_size."""
         from .ops import _down_raw, _up_raw
         from .tensor import _DeviceBuffer
         x = np.asarray(x)
         u8 = x.dtype == np.uint8
         x = np.ascontiguousarray(x, dtype=np.uint8 if u8 else np.float32)
-        assert x.ndim == 4 and x.shape[1:] == ((224, 224, 3) if u8 else (3, 224, 224)), x.shape
+        self._check_input(x, u8)
         B, C, F, k = x.shape[0], self.classes, self.features, int(topk)
         xin = _up_raw(x)
         bufs = {}
@@ -305,7 +333,8 @@ class NativeModel:
                 "rn_model_forward", self.ctx.handle)
 
     def forward(self, x: np.ndarray, fused: bool = True) -> np.ndarray:
-        """NCHW host array -> logits host array (synchronous convenience)."""
+        """NCHW host array [B,3,H,W] of the model's input_size -> logits host array (synchronous convenience)."""
+        self._check_input(np.asarray(x))
         xin = FloatTensor.from_numpy(x, Device.GPU)
         B = x.shape[0]
         out = FloatTensor((B, self.classes), Device.GPU)
@@ -314,7 +343,7 @@ class NativeModel:
         return out.numpy()
 
     def forward_u8_ptr(self, input_ptr: int, B: int, logits_ptr: int, fused: bool = True) -> None:
-        """Queue one forward from 8-bit RGB [B,224,224,3] on the device (asynchronous): the first
+        """Queue one forward from 8-bit RGB [B,H,W,3] (input_size) on the device (asynchronous): the first
         launch normalises the bytes (rn_model_forward_u8); same logits as forward_ptr on
         preprocess.normalize_u8 of them, bit for bit."""
         L.check(L.lib().rn_model_forward_u8(self.handle, input_ptr, B, logits_ptr,
@@ -322,10 +351,11 @@ class NativeModel:
                 "rn_model_forward_u8", self.ctx.handle)
 
     def forward_u8(self, px: np.ndarray, fused: bool = True) -> np.ndarray:
-        """uint8 RGB host array [B,224,224,3] -> logits host array (synchronous convenience)."""
+        """uint8 RGB host array [B,H,W,3] of the model's input_size -> logits host array (synchronous
+        convenience)."""
         from .ops import _up_raw
         px = np.ascontiguousarray(px, dtype=np.uint8)
-        assert px.ndim == 4 and px.shape[1:] == (224, 224, 3), px.shape
+        self._check_input(px, True)
         B = px.shape[0]
         xin = _up_raw(px)
         out = FloatTensor((B, self.classes), Device.GPU)
@@ -336,7 +366,8 @@ class NativeModel:
     def forward_images(self, images, fused: bool = True) -> np.ndarray:
         """A list of decoded [H,W,3] uint8 RGB arrays of any sizes -> logits host array: the device
         resizes (short side 256) and centre-crops (224) them to PIL's bytes, then runs forward_u8's
-        launches (rn_model_forward_images_u8).  Synchronous convenience."""
+        launches (rn_model_forward_images_u8).  Synchronous convenience.  Only at input_size (224, 224):
+        RnError (RN_ERR_UNSUPPORTED) otherwise."""
         from .ops import _u64p, _up_raw, pack_images
         packed, offsets, heights, widths = pack_images(images)
         B = len(heights)
@@ -609,7 +640,8 @@ class ShardedModel:
 
 
 class Graph:
-    """A captured forward (rn_model_capture): launch() replays it on the context's stream."""
+    """A captured forward (rn_model_capture) of `batch` images of the model's input_size: launch() replays it
+    on the context's stream.  While it lives the model refuses set_input_size."""
 
     def __init__(self, model: NativeModel, input_ptr, batch: int, logits_ptr, fused: bool = True):
         self.model = model
@@ -643,14 +675,17 @@ class Pipeline:
 
     def __init__(self, model: NativeModel, batch: int, fused: bool = True, input: str = "f32",
                  max_batch_bytes: Optional[int] = None):
-        """input: "f32" (NCHW floats, submit), "u8" (RGB bytes [n,224,224,3], submit_u8: a
+        """input: "f32" (NCHW floats, submit), "u8" (RGB bytes [n,H,W,3], submit_u8: a
         quarter of the upload, normalised on the device) or "images" (decoded RGB images of any
-        size, submit_images: resized and cropped on the device; ``max_batch_bytes`` is the room for
-        one batch's pixels, default 1 MB per image)."""
+        size, submit_images: resized and cropped on the device, models of input_size (224, 224) only;
+        ``max_batch_bytes`` is the room for one batch's pixels, default 1 MB per image).  The buffers
+        are sized for the model's input_size at creation; while the pipeline lives the model refuses
+        set_input_size."""
         if input not in ("f32", "u8", "images"):
             raise ValueError(f"input must be 'f32', 'u8' or 'images', not {input!r}")
         self.model, self.batch, self.input = model, batch, input
         self.classes = model.classes  # the row length of what collect() returns
+        self.input_size = model.input_size  # (H, W) of the staging buffers
         h = ctypes.c_void_p()
         mode = L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS
         if input == "images":
@@ -664,38 +699,40 @@ class Pipeline:
         self.handle = h
 
     def input_buffer(self) -> np.ndarray:
-        """The pinned staging buffer of the next slot as a [B,3,224,224] float array (a byte
-        pipeline: [B,224,224,3] uint8): fill it in place, then submit without an argument."""
+        """The pinned staging buffer of the next slot as a [B,3,H,W] float array (a byte
+        pipeline: [B,H,W,3] uint8), H x W the model's input_size: fill it in place, then submit without
+        an argument."""
         ptr = ctypes.c_void_p()
+        H, W = self.input_size
         if self.input == "u8":
             L.check(L.lib().rn_pipeline_input_buffer_u8(self.handle, ctypes.byref(ptr)),
                     "rn_pipeline_input_buffer_u8", self.model.ctx.handle)
-            buf = (ctypes.c_uint8 * (self.batch * 224 * 224 * 3)).from_address(ptr.value)
-            return np.frombuffer(buf, dtype=np.uint8).reshape(self.batch, 224, 224, 3)
+            buf = (ctypes.c_uint8 * (self.batch * H * W * 3)).from_address(ptr.value)
+            return np.frombuffer(buf, dtype=np.uint8).reshape(self.batch, H, W, 3)
         L.check(L.lib().rn_pipeline_input_buffer(self.handle, ctypes.byref(ptr)),
                 "rn_pipeline_input_buffer", self.model.ctx.handle)
-        n = self.batch * 3 * 224 * 224
+        n = self.batch * 3 * H * W
         buf = (ctypes.c_float * n).from_address(ptr.value)
-        return np.frombuffer(buf, dtype=np.float32).reshape(self.batch, 3, 224, 224)
+        return np.frombuffer(buf, dtype=np.float32).reshape(self.batch, 3, H, W)
 
     def submit(self, x: np.ndarray | None = None) -> None:
-        """x: [n,3,224,224] with n <= batch (a ragged last batch), or None when the staging
+        """x: [n,3,H,W] (the model's input_size) with n <= batch (a ragged last batch), or None when the staging
         buffer was filled in place (a whole batch)."""
         ptr, n = None, self.batch
         if x is not None:
             x = np.ascontiguousarray(x, dtype=np.float32)
-            assert x.shape[1:] == (3, 224, 224)
+            assert x.shape[1:] == (3,) + self.input_size, (x.shape, self.input_size)
             ptr, n = x.ctypes.data, x.shape[0]
         L.check(L.lib().rn_pipeline_submit_n(self.handle, ptr, n), "rn_pipeline_submit_n",
                 self.model.ctx.handle)
 
     def submit_u8(self, px: np.ndarray | None = None) -> None:
-        """px: [n,224,224,3] uint8 with n <= batch, or None when the staging buffer was filled in
+        """px: [n,H,W,3] uint8 (the model's input_size) with n <= batch, or None when the staging buffer was filled in
         place (a whole batch).  Only on a pipeline created with input="u8"."""
         ptr, n = None, self.batch
         if px is not None:
             px = np.ascontiguousarray(px, dtype=np.uint8)
-            assert px.shape[1:] == (224, 224, 3)
+            assert px.shape[1:] == self.input_size + (3,), (px.shape, self.input_size)
             ptr, n = px.ctypes.data, px.shape[0]
         L.check(L.lib().rn_pipeline_submit_u8_n(self.handle, ptr, n), "rn_pipeline_submit_u8_n",
                 self.model.ctx.handle)

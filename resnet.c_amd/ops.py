@@ -474,6 +474,26 @@ def pool_nhwc_bf16(x, k, stride=1, pad=0, is_max=True) -> np.ndarray:
     return y.reshape(B, ho, wo, C).transpose(0, 3, 1, 2).copy()
 
 
+def global_avgpool(x, bf16: bool = False) -> np.ndarray:
+    """Mean over the whole H x W map (rn_global_avgpool_nhwc_forward_dt): NCHW fp32 host array [B,C,H,W] in
+    (uploaded as NHWC, rounded to bf16 first when ``bf16``), [B,C] fp32 out (bf16 results widened, exact).
+    C % 4 == 0 (bf16: % 8).  The summation order depends on (H, W) only; 7 x 7 gives the bits of
+    avgpool2d(k=7) on NHWC."""
+    from .tensor import _DeviceBuffer
+    ctx = get_ctx()
+    x = np.asarray(x, dtype=np.float32)
+    B, C, H, W = x.shape
+    nhwc = np.ascontiguousarray(x.transpose(0, 2, 3, 1))
+    dx = _up_raw(to_bf16_bits(nhwc) if bf16 else nhwc)
+    out = _DeviceBuffer(ctx, max(B * C * (2 if bf16 else 4), 16))
+    L.check(L.lib().rn_global_avgpool_nhwc_forward_dt(ctx.handle, L.RN_DTYPE_BF16 if bf16 else L.RN_DTYPE_F32,
+                                                      dx.ptr, out.ptr, B, C, H, W),
+            "rn_global_avgpool_nhwc_forward_dt", ctx.handle)
+    ctx.sync()
+    y = from_bf16_bits(_down_raw(out, np.uint16, B * C)) if bf16 else _down_raw(out, np.float32, B * C)
+    return y.reshape(B, C)
+
+
 def image_u8_to_nhwc_pad(px, cpad: int = 4, border: int = 0, bf16: bool = False, mean=None, std=None,
                          prefill: Optional[int] = None) -> np.ndarray:
     """rn_image_u8_to_nhwc_pad_dt: uint8 RGB [B,H,W,3] -> the normalised, padded first tensor

@@ -240,13 +240,23 @@ def generate_state(arch: str, seed: int = 0) -> Dict[str, np.ndarray]:
     return out
 
 
-def generate_input(batch: int, seed: int = 0, hw: int = 224, name: str = "input") -> np.ndarray:
-    """[batch,3,hw,hw] NCHW fp32, uniform in [-2,2): image i depends on (seed, i) only."""
-    per = 3 * hw * hw
-    out = np.empty((batch, 3, hw, hw), dtype=np.float32)
+def _hw_pair(hw) -> Tuple[int, int]:
+    """hw: one side (square) or (H, W)."""
+    if isinstance(hw, (tuple, list)):
+        h, w = hw
+        return int(h), int(w)
+    return int(hw), int(hw)
+
+
+def generate_input(batch: int, seed: int = 0, hw=224, name: str = "input") -> np.ndarray:
+    """[batch,3,H,W] NCHW fp32, uniform in [-2,2): image i depends on (seed, i) and the size only.
+    hw: one side, or (H, W)."""
+    h, w = _hw_pair(hw)
+    per = 3 * h * w
+    out = np.empty((batch, 3, h, w), dtype=np.float32)
     for i in range(batch):
         u = uniform01(name, per, seed, offset=i * per)
-        out[i] = (-2.0 + 4.0 * u).astype(np.float32).reshape(3, hw, hw)
+        out[i] = (-2.0 + 4.0 * u).astype(np.float32).reshape(3, h, w)
     return out
 
 
@@ -301,22 +311,27 @@ def iter_basic_blocks(arch: str) -> Iterator[Tuple[str, int, int, int, bool]]:
         prev = cout
 
 
-def forward_flops(arch: str, hw: int = 224) -> int:
+def forward_flops(arch: str, hw=224) -> int:
     """Algorithmic FLOPs of one image: 2 x MACs of every convolution (output sizes tracked through
-    the network) and of fc.  8,178,368,512 for resnet50, 3,628,146,688 for resnet18."""
+    the network) and of fc.  8,178,368,512 for resnet50, 3,628,146,688 for resnet18 at 224 x 224.
+    hw: one side (a square image) or (H, W)."""
     def out(n, k, s, p):
         return (n + 2 * p - k) // s + 1
-    total, block_in, last = 0, {}, hw
+
+    def out2(n, k, s, p):
+        return out(n[0], k, s, p), out(n[1], k, s, p)
+    size = _hw_pair(hw)
+    total, block_in, last = 0, {}, size
     for name, cin, cout, k, s, p in conv_specs(arch):
         if name == "conv1":
-            n_in = hw
+            n_in = size
         else:
             pre = name.rsplit(".", 2)[0] if name.endswith("downsample.0") else name.rsplit(".", 1)[0]
             if pre not in block_in:   # first convolution of a block: the previous block's output
-                block_in[pre] = last if len(block_in) else out(last, 3, 2, 1)  # max-pool after the stem
+                block_in[pre] = last if len(block_in) else out2(last, 3, 2, 1)  # max-pool after the stem
             first = name.endswith(("downsample.0", ".conv1"))
             n_in = block_in[pre] if first else last
-        n_out = out(n_in, k, s, p)
-        total += 2 * n_out * n_out * cout * (cin // conv_groups(arch, name)) * k * k
+        n_out = out2(n_in, k, s, p)
+        total += 2 * n_out[0] * n_out[1] * cout * (cin // conv_groups(arch, name)) * k * k
         last = n_out
     return total + 2 * feature_width(arch) * NUM_CLASSES
