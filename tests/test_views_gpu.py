@@ -259,25 +259,11 @@ def _bf16(a):
     return ops.to_bf16_bits(np.ascontiguousarray(np.asarray(a, dtype=np.float32).transpose(0, 2, 3, 1)))
 
 
-def _packed_dt(w, dt):
-    Cout, Cin, k, _ = w.shape
-    n = int(L.lib().rn_conv2d_packed_weight_numel_dt(dt, Cin, Cout, k))
-    vw, vp = V.place(w), V.place_out(n * (2 if dt == L.RN_DTYPE_BF16 else 4))
-    V.must("rn_conv2d_pack_weight_dt", dt, vw.ptr, vp.ptr, Cin, Cout, k)
-    return V.fetch(vp, np.uint16 if dt == L.RN_DTYPE_BF16 else np.float32, "pack_dt")
-
-
 def _conv_bf16(offs):
     B, Cin, Cout, H, W = 2, 64, 64, 6, 6
     x, w = rnd((B, Cin, H, W), 1), rnd((Cout, Cin, 1, 1), 2) / 8
     sc, sh, res = rnd((Cout,), 3), rnd((Cout,), 4), rnd((B, Cout, H, W), 5)
-    vi, vw = V.place(_bf16(x), offs.get("inp", 0)), V.place(_packed_dt(w, L.RN_DTYPE_BF16), offs.get("weight", 0))
-    vsc, vsh = V.place(sc, offs.get("scale", 0)), V.place(sh, offs.get("shift", 0))
-    vr, vo = V.place(_bf16(res), offs.get("residual", 0)), V.place_out(B * Cout * H * W * 2, offs.get("out", 0))
-    ep = L.Epilogue(vsc.ptr, vsh.ptr, vr.ptr, 1)
-    st = V.call("rn_conv2d_nhwc_forward_dt", L.RN_DTYPE_BF16, L.RN_DTYPE_BF16, vi.ptr, vo.ptr, vw.ptr, 1, 1, 0, H, W, B,
-                Cin, Cout, H, W, ctypes.byref(ep))
-    return st, [vo], [vi, vw, vsc, vsh, vr]
+    return V.launch_conv_dt(x, w, 1, 0, sc, sh, res, True, L.RN_DTYPE_BF16, L.RN_DTYPE_BF16, offs)
 
 
 def _conv_exact(offs):
@@ -302,18 +288,7 @@ def _conv_pair(offs):
     t, w = rnd((B, Cin, H, W), 11), rnd((Cout, Cin, 1, 1), 12) / 8
     x2, w2 = rnd((B, Cin2, H, W), 13), rnd((Cout, Cin2, 1, 1), 14) / 6
     sh, res = rnd((Cout,), 15), rnd((B, Cout, H, W), 16)
-    n = int(L.lib().rn_conv2d_packed_pair_weight_numel(Cin, Cout, 1, Cin2))
-    v1, v2, vp = V.place(w), V.place(w2), V.place_out(n * 4)
-    V.must("rn_conv2d_pack_weight_pair_dt", L.RN_DTYPE_F32, v1.ptr, None, v2.ptr, None, vp.ptr, Cin, Cout, 1, Cin2)
-    nhwc = lambda a: np.ascontiguousarray(a.transpose(0, 2, 3, 1))
-    vi, vi2 = V.place(nhwc(t), offs.get("inp", 0)), V.place(nhwc(x2), offs.get("second", 0))
-    vw = V.place(V.fetch(vp, np.float32, "pack_pair"), offs.get("weight", 0))
-    vsh, vr = V.place(sh, offs.get("shift", 0)), V.place(nhwc(res), offs.get("residual", 0))
-    vo = V.place_out(B * Cout * H * W * 4, offs.get("out", 0))
-    ep, second = L.Epilogue(None, vsh.ptr, vr.ptr, 1), L.ConvSecond(vi2.ptr, Cin2, H, W, 1)
-    st = V.call("rn_conv2d_nhwc_pair_forward_dt", L.RN_DTYPE_F32, L.RN_DTYPE_F32, vi.ptr, vo.ptr, vw.ptr, 1, 1, 0, H, W, B,
-                Cin, Cout, H, W, ctypes.byref(second), ctypes.byref(ep))
-    return st, [vo], [vi, vi2, vw, vsh, vr]
+    return V.launch_conv_pair_dt(t, w, x2, w2, 1, 0, 1, None, None, sh, res, True, L.RN_DTYPE_F32, offs)
 
 
 def _pool_bf16(kind):
@@ -334,50 +309,23 @@ def _stem(form):
         x, w = rnd((B, 3, H, W), 18), rnd((64, 3, 7, 7), 19) / 12
         g = np.random.default_rng(20)
         sc, sh = g.random(64, dtype=np.float32) + 0.5, g.standard_normal(64, dtype=np.float32)
-        n = int(L.lib().rn_stem_pool_packed_weight_numel(L.RN_DTYPE_F32))
-        v0, vp = V.place(w), V.place_out(n * 4)
-        V.must("rn_stem_pool_pack_weight_dt", L.RN_DTYPE_F32, v0.ptr, vp.ptr, 3)
-        vw = V.place(V.fetch(vp, np.float32, "stem pack"), offs.get("weight", 0))
-        vsc, vsh = V.place(sc, offs.get("scale", 0)), V.place(sh, offs.get("shift", 0))
-        vo = V.place_out(B * 4 * 4 * 64 * 4, offs.get("out", 0))
-        if form == "y":
-            vi, vy = V.place(x, offs.get("inp", 0)), V.place_out(B * 8 * 8 * 64 * 4, offs.get("y", 0))
-            st = V.call("rn_stem_conv_pool_nchw_forward", vi.ptr, vy.ptr, vo.ptr, vw.ptr, vsc.ptr, vsh.ptr, B, 3, H, W)
-            return st, [vo, vy], [vi, vw, vsc, vsh]
-        if form == "nchw":
-            vi = V.place(x, offs.get("inp", 0))
-            st = V.call("rn_stem_pool_nchw_forward_dt", L.RN_DTYPE_F32, vi.ptr, vo.ptr, vw.ptr, vsc.ptr, vsh.ptr, 1, B, 3, H, W)
-            return st, [vo], [vi, vw, vsc, vsh]
-        vi = V.place(V.pad_reference(x, 3, 3), offs.get("inp", 0))
-        st = V.call("rn_stem_pool_forward_dt", L.RN_DTYPE_F32, vi.ptr, vo.ptr, vw.ptr, vsc.ptr, vsh.ptr, 1, B, H + 6, W + 6)
-        return st, [vo], [vi, vw, vsc, vsh]
+        return V.launch_stem_pool(form, x, w, sc, sh, L.RN_DTYPE_F32, offs)
     return run
 
 
 def _chain(pair, bf16):
     """rn_conv_chain_forward_dt / rn_conv_chain_pair_forward_dt, 64 -> 256 -> 64 channels on 128 rows (the case of
-    test_chain_refuses_misaligned_or_aliased_tensors); any panel contents are valid weights."""
+    test_chain_refuses_misaligned_or_aliased_tensors)."""
     def run(offs):
-        rows, dt = 128, (L.RN_DTYPE_BF16 if bf16 else L.RN_DTYPE_F32)
-        act = (lambda a: ops.to_bf16_bits(a)) if bf16 else (lambda a: a)
-        es = 2 if bf16 else 4
-        t2, x = rnd((rows, 64), 21), rnd((rows, 64 if pair else 256), 22)
-        w3, w1 = rnd((256, 128 if pair else 64), 23) / 8, rnd((64, 256), 24) / 16
+        dt = L.RN_DTYPE_BF16 if bf16 else L.RN_DTYPE_F32
+        t2, x = rnd((2, 64, 8, 8), 21), rnd((2, 64 if pair else 256, 8, 8), 22)
+        w3, w1 = rnd((256, 64, 1, 1), 23) / 8, rnd((64, 256, 1, 1), 24) / 16
         g = np.random.default_rng(25)
         sc3, sh3 = g.random(256, dtype=np.float32) + 0.5, g.standard_normal(256, dtype=np.float32)
         sc1, sh1 = g.random(64, dtype=np.float32) + 0.5, g.standard_normal(64, dtype=np.float32)
-        vt2, vx = V.place(act(t2), offs.get("t2", 0)), V.place(act(x), offs.get("x", 0))
-        vw3, vw1 = V.place(act(w3), offs.get("w3", 0)), V.place(act(w1), offs.get("w1", 0))
-        vsc3, vsh3 = V.place(sc3, offs.get("scale3", 0)), V.place(sh3, offs.get("shift3", 0))
-        vsc1, vsh1 = V.place(sc1, offs.get("scale1", 0)), V.place(sh1, offs.get("shift1", 0))
-        vy, vt1 = V.place_out(rows * 256 * es, offs.get("y", 0)), V.place_out(rows * 64 * es, offs.get("t1", 0))
         if pair:
-            st = V.call("rn_conv_chain_pair_forward_dt", dt, vt2.ptr, vx.ptr, vy.ptr, vw3.ptr, vsh3.ptr, vt1.ptr, vw1.ptr,
-                        vsc1.ptr, vsh1.ptr, rows, 64, 64, 256, 64)
-        else:
-            st = V.call("rn_conv_chain_forward_dt", dt, vt2.ptr, vx.ptr, vy.ptr, vw3.ptr, vsc3.ptr, vsh3.ptr, vt1.ptr,
-                        vw1.ptr, vsc1.ptr, vsh1.ptr, rows, 64, 256, 64)
-        return st, [vy, vt1], [vt2, vx, vw3, vw1, vsc3, vsh3, vsc1, vsh1]
+            return V.launch_chain_dt(t2, x, w3, None, sh3, w1, sc1, sh1, dt, pair_w=rnd((256, 64, 1, 1), 26) / 8, offs=offs)
+        return V.launch_chain_dt(t2, x, w3, sc3, sh3, w1, sc1, sh1, dt, offs=offs)
     return run
 
 
