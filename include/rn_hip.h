@@ -489,6 +489,53 @@ RN_API int rn_conv2d_grouped_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dty
                                              uint64_t out_channels, uint64_t H, uint64_t W,
                                              uint64_t groups, const rn_epilogue *epilogue /* nullable */);
 
+/* ---- dilated convolution (torch's `dilation`, one factor for rows and columns) -----------------
+ * Kernel tap (kh, kw) of output (oh, ow) reads input (oh * stride - padding + kh * dilation,
+ * ow * stride - padding + kw * dilation); a tap outside the image contributes nothing.  The weight,
+ * its packed panels (rn_conv2d_pack_weight_dt for groups == 1, rn_conv2d_grouped_pack_weight_dt for
+ * groups >= 2: dilation does not change a panel), the FLOPs and the summation order of an output
+ * element are those of the undilated convolution of the same shape.
+ * rn_conv_output_size_dilated = (x + 2 * padding - dilation * (kernel_size - 1) - 1) / stride + 1, and 0
+ * where the dilated kernel does not fit the padded extent (or an argument that must be >= 1 is 0).
+ * rn_conv2d_dilated_forward is the reference's conv2d signature plus `dilation` and `groups`: OIHW
+ * weight, tensors in the context layout (NCHW: transposed into scratch, the contraction writes
+ * NCHW); on a deferred context it runs what is recorded and then itself, at once.
+ * rn_conv2d_dilated_nhwc_forward_dt is NHWC in / NHWC out with a packed weight and the fused epilogue.
+ * With dilation == 1 (and for kernel_size == 1, whose one tap no dilation moves) both issue exactly the
+ * launch of rn_conv2d_forward / rn_conv2d_grouped_forward and rn_conv2d_nhwc_forward_dt /
+ * rn_conv2d_grouped_nhwc_forward_dt: the same bits.
+ * Which kernel runs, dilation >= 2:
+ *  - matrix cores, groups == 1: in_channels % 32 == 0 (fp32) or % 64 == 0 (bf16, required), kernel_size
+ *    <= 15, tensors below 2^29 elements, every operand on a 16-byte boundary -- all tile candidates,
+ *    the resident grids, split K, the chunked K sum and the bf16 256-wide tiles, each bit-identical
+ *    to the others wherever the undilated layer's are;
+ *  - matrix cores, groups >= 2: the fp32 super-group kernel under its undilated conditions (kernel_size
+ *    3, in_channels == out_channels, ...); bf16 runs the dense contraction on the dense panel;
+ *  - everything else in fp32 -- in particular the small-Cin (stem) packing, which has no dilated
+ *    form, and an operand off a 16-byte boundary -- runs the direct kernel, one thread per output in
+ *    the reference's summation order; the bf16 small-Cin form is RN_ERR_UNSUPPORTED;
+ *  - never: the strip kernel, the exact-K packing, the NCHW-native kernel, the chained launches.
+ * Alignment rules and non-finite behaviour are those of the undilated entry point of the same form
+ * (a padded or never-reached tap is skipped, not multiplied by zero; the grouped fast path and the
+ * bf16 grouped panel multiply their structural zeros, see above).
+ * RN_ERR_INVALID, nothing launched: dilation == 0 or above RN_CONV_MAX_DILATION, h_out / w_out other
+ * than rn_conv_output_size_dilated of H / W, groups that do not divide both channel counts. */
+#define RN_CONV_MAX_DILATION 1024
+RN_API uint64_t rn_conv_output_size_dilated(uint64_t x, uint64_t kernel_size, uint64_t stride,
+                                            uint64_t padding, uint64_t dilation);
+RN_API int rn_conv2d_dilated_forward(rn_ctx *ctx, const float *inp, float *out, const float *weight,
+                                     uint64_t kernel_size, uint64_t stride, uint64_t padding,
+                                     uint64_t dilation, uint64_t h_out, uint64_t w_out, uint64_t B,
+                                     uint64_t in_channels, uint64_t out_channels, uint64_t H, uint64_t W,
+                                     uint64_t groups);
+RN_API int rn_conv2d_dilated_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const void *inp,
+                                             void *out, const void *packed_weight, uint64_t kernel_size,
+                                             uint64_t stride, uint64_t padding, uint64_t dilation,
+                                             uint64_t h_out, uint64_t w_out, uint64_t B,
+                                             uint64_t in_channels, uint64_t out_channels, uint64_t H,
+                                             uint64_t W, uint64_t groups,
+                                             const rn_epilogue *epilogue /* nullable */);
+
 /* ---- model (main.cu driver) ---------------------------------------------- */
 /* arch: 50, 101 or 152 (bottleneck blocks, counts 3/4/6/3, 3/4/23/3, 3/8/36/3), or 18 or 34
  * (torchvision's basic blocks -- two 3x3 convolutions, expansion 1, final width 512 -- counts
@@ -564,6 +611,32 @@ RN_API const char *rn_model_tensor_key(const rn_model *m, uint64_t index, uint64
 RN_API int rn_model_set_input_size(rn_model *m, uint64_t H, uint64_t W);
 RN_API int rn_model_input_size(const rn_model *m, uint64_t *H, uint64_t *W); /* either pointer may be NULL */
 RN_API uint64_t rn_model_max_sub_batch(const rn_model *m);
+/* torchvision's replace_stride_with_dilation (flags 0 or 1 for layer2, layer3, layer4): a flagged stage keeps
+ * its input's resolution and dilates its 3x3 convolutions instead, so the backbone's output stride becomes 16, 8
+ * or 4 (rn_model_output_stride; 32 undilated) -- the form DeepLab / FCN run these weights in.  The rule is
+ * torchvision's _make_layer: a running dilation starts at 1; for a flagged stage previous = dilation,
+ * dilation *= 2, stride = 1.  Block 0 of a stage runs conv2 at the stage's stride with dilation = padding =
+ * previous and keeps its downsample 1x1 (at the stage's stride: the widths differ); blocks 1.. run conv2 with
+ * dilation = padding = dilation; an unflagged stage uses the current dilation for all its blocks and keeps its
+ * stride.  ResNet-50 with (0,1,1): layer3.0 d1, layer3.1-5 d2, layer4.0 d2, layer4.1-2 d4, final map 28 x 28 at
+ * 224 x 224; with (1,1,1) the largest dilation is 8.  The dilated convolutions are
+ * rn_conv2d_dilated_nhwc_forward_dt on the panels of the undilated model.
+ * A property of the model, like the input size: legal before or after rn_model_finalize (the weights do not
+ * depend on it).  RN_ERR_INVALID, nothing changed: a flag other than 0 or 1, flags of which not one image fits
+ * the kernels' tensor range, or a captured graph or a pipeline of this model alive.  RN_ERR_UNSUPPORTED with
+ * rn_last_error's text: ResNet-18/34 (torchvision raises NotImplementedError for BasicBlock).  It waits for the
+ * model's queued forwards, frees the activation arenas and drops the tuned tiles.
+ * What follows from the flags, as from the size: the arenas (each the maximum over all stages: layer4's output
+ * of a (0,1,1) model at 224 x 224 is 28 * 28 * 2048 elements per image, twice the stem's; those of a (0,0,0)
+ * model are what they were), rn_model_max_sub_batch (256 there) and rn_model_activation_bytes; the map the head
+ * pools; the profile's FLOPs; block 0 of a dilated stage as a fused pair is the two-source launch with
+ * stride2 == 1; every forward entry point, rn_model_tune, rn_model_capture and the pipelines
+ * (rn_model_forward_images_u8 included: its contract is the 224 crop only).  The tuning table's header carries
+ * the flags in a word of its own that is absent for (0,0,0), whose tables keep their format; a model refuses a
+ * table measured under other flags.  rn_shard_* creates its own models and stays undilated. */
+RN_API int rn_model_set_dilation(rn_model *m, int layer2, int layer3, int layer4);
+RN_API int rn_model_dilation(const rn_model *m, int out[3]);
+RN_API int rn_model_output_stride(const rn_model *m); /* 32, 16, 8 or 4 */
 /* input: device NCHW [B,3,H,W] of the model's input size; logits: device [B,classes]. Asynchronous on the stream.
  *
  * Geometry of the model driver (the reference's -- main.cu:230 hard-codes {1, 3, 224, 224} -- is fixed):

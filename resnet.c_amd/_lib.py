@@ -19,6 +19,7 @@ RN_ERR_INVALID, RN_ERR_HIP, RN_ERR_IO, RN_ERR_NOMEM, RN_ERR_UNSUPPORTED = 1, 2, 
 RN_LAYOUT_NCHW, RN_LAYOUT_NHWC = 0, 1
 RN_FWD_REFERENCE_OPS, RN_FWD_FUSED = 0, 1
 RN_DTYPE_F32, RN_DTYPE_BF16 = 0, 1
+RN_CONV_MAX_DILATION = 1024  # the largest dilation of the rn_conv2d_dilated_* entry points
 
 u64 = c_uint64
 fptr = c_void_p  # device pointers travel as plain addresses
@@ -121,6 +122,10 @@ SIGNATURES = {
     "rn_conv2d_grouped_pack_weight_dt": (c_int, [c_void_p, c_int, fptr, fptr, u64, u64, u64, u64]),
     "rn_conv2d_grouped_nhwc_forward_dt": (c_int, [c_void_p, c_int, c_int, fptr, fptr, fptr] + [u64] * 11
                                           + [POINTER(Epilogue)]),
+    "rn_conv_output_size_dilated": (u64, [u64, u64, u64, u64, u64]),
+    "rn_conv2d_dilated_forward": (c_int, [c_void_p, fptr, fptr, fptr] + [u64] * 12),
+    "rn_conv2d_dilated_nhwc_forward_dt": (c_int, [c_void_p, c_int, c_int, fptr, fptr, fptr] + [u64] * 12
+                                          + [POINTER(Epilogue)]),
     "rn_conv2d_packed_weight_numel_exact": (u64, [u64, u64, u64]),
     "rn_conv2d_pack_weight_exact": (c_int, [c_void_p, fptr, fptr, u64, u64, u64]),
     "rn_conv2d_nhwc_exact_forward": (c_int, [c_void_p, fptr, fptr, fptr] + [u64] * 9
@@ -151,6 +156,9 @@ SIGNATURES = {
     "rn_model_set_input_size": (c_int, [c_void_p, u64, u64]),
     "rn_model_input_size": (c_int, [c_void_p, POINTER(u64), POINTER(u64)]),
     "rn_model_max_sub_batch": (u64, [c_void_p]),
+    "rn_model_set_dilation": (c_int, [c_void_p, c_int, c_int, c_int]),
+    "rn_model_dilation": (c_int, [c_void_p, POINTER(c_int)]),
+    "rn_model_output_stride": (c_int, [c_void_p]),
     "rn_model_create": (c_int, [c_void_p, POINTER(c_void_p), c_int]),
     "rn_model_create_ex": (c_int, [c_void_p, POINTER(c_void_p), c_int, c_int, c_int]),
     "rn_model_set_dtype": (c_int, [c_void_p, c_int]),

@@ -135,7 +135,11 @@ struct OutVec<bf16_t> {
 // DUAL: the K loop continues through a second (input, weight-row tail) pair, see GemmParams
 // XK: exact-K small-Cin form (the 7x7x3 stem as K = 147 -> 160 instead of 224), fp32 only
 // CHUNK: chunked K sum with the tail tiles cut into pieces, fp32 only (see GemmParams)
-template <typename T, typename TO, int BM, int BN, bool DUAL = false, bool XK = false, bool CHUNK = false>
+// DIL: GemmParams::dil > 1 -- kernel row kh reads input row ih0 + kh * dil, columns alike; the row masks are
+//      built tap by tap and the tap offset scales.  A flag of the instantiation, not a branch, so that the
+//      row setup of the undilated launches (block life outside the K loop) is what it was
+template <typename T, typename TO, int BM, int BN, bool DUAL = false, bool XK = false, bool CHUNK = false,
+          bool DIL = false>
 __global__ __launch_bounds__(256, (BM * BN <= 64 * 64 ? 4 : BM * BN <= 64 * 128 ? 3 : 2)) void conv_gemm_kernel(const GemmParams p)
 {
     constexpr int CH = Elem<T>::CH, ES = (int)sizeof(T);
@@ -240,7 +244,9 @@ __global__ __launch_bounds__(256, (BM * BN <= 64 * 64 ? 4 : BM * BN <= 64 * 128 
                 const int iwc = iw0 + cc * p.chunk_dw;
                 a_off[j] = (((b * p.H + ih0 + hi) * p.W + iw0) * p.Cs + (XK ? 0 : cc * CH)) * ES;
                 int rm = 0;
-                if (p.tap_rows == 1) {
+                if constexpr (DIL) {  // (tap_rows == 1: the small-Cin forms are never dilated)
+                    rm = tap_mask(ih0, p.KH, p.H, p.dil);
+                } else if (p.tap_rows == 1) {
                     const int rlo = max(0, -ih0), rhi = min(p.KH, p.H - ih0);
                     rm = rhi > rlo ? ((1 << rhi) - 1) & ~((1 << rlo) - 1) : 0;
                 } else {
@@ -251,6 +257,7 @@ __global__ __launch_bounds__(256, (BM * BN <= 64 * 64 ? 4 : BM * BN <= 64 * 128 
                 }
                 const int clo = max(0, -iwc), chi = min(p.KW, p.W - iwc);
                 int cm = chi > clo ? ((1 << chi) - 1) & ~((1 << clo) - 1) : 0;
+                if constexpr (DIL) cm = tap_mask(iwc, p.KW, p.W, p.dil);
                 if (p.chunk_dw && cc >= p.c4_chunks) cm = 0;  // chunk holds only zero-weight slots
                 a_mask[j] = rm | (cm << 16);
                 if constexpr (DUAL)
@@ -320,7 +327,9 @@ __global__ __launch_bounds__(256, (BM * BN <= 64 * 64 ? 4 : BM * BN <= 64 * 128 
             if (first || s_cs == 0) {
                 const unsigned ukh = p.KW == 1 ? tap : (__umulhi(tap, p.mul_kw) >> p.shr_kw);
                 const int s_kh = (int)ukh, s_kw = (int)(tap - ukh * (unsigned)p.KW);
-                const int toff = (s_kh * p.tap_rows * p.W + s_kw) * p.Cs * ES;
+                // (DIL, unsigned: a tap that is never inside the image may wrap; its mask bit is clear)
+                const int toff = DIL ? (int)((unsigned)(s_kh * p.W + s_kw) * (unsigned)(p.dil * p.Cs * ES))
+                                     : (s_kh * p.tap_rows * p.W + s_kw) * p.Cs * ES;
 #pragma unroll
                 for (int j = 0; j < AP; ++j) {
                     const bool ok = ((a_mask[j] >> s_kh) & (a_mask[j] >> (16 + s_kw)) & 1) != 0;
@@ -727,7 +736,7 @@ struct DirectParams {
     const float *shift;
     const float *residual;
     int relu;
-    int k, stride, pad, Ho, Wo, Cin, Cs, Cout, H, W;
+    int k, stride, pad, dil, Ho, Wo, Cin, Cs, Cout, H, W;
     int nhwc;      // activation layout
     int w_packed;  // 0: OIHW, 1: [Cout][kh][kw][Cin], 2: small-Cin panel [Cout][kh][8][4]
     uint64_t total;
@@ -758,10 +767,10 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const DirectParams p)
         float sum = 0.f;
         for (int ic = 0; ic < p.Cin; ++ic) {
             for (int kh = 0; kh < p.k; ++kh) {
-                const int ih = ih0 + kh;
+                const int ih = ih0 + kh * p.dil;
                 if (ih < 0 || ih >= p.H) continue;
                 for (int kw = 0; kw < p.k; ++kw) {
-                    const int iw = iw0 + kw;
+                    const int iw = iw0 + kw * p.dil;
                     if (iw < 0 || iw >= p.W) continue;
                     const uint64_t ii = p.nhwc ? (((b * p.H + ih) * p.W + iw) * p.Cs + ic)
                                                : (((b * p.Cin + ic) * p.H + ih) * p.W + iw);
@@ -830,17 +839,17 @@ void fast_div(unsigned d, unsigned *mul, unsigned *shr) { rn_fast_div(d, mul, sh
 
 // Blocks of one instantiation that fit a CU at once (registers and LDS) on the context's device,
 // asked once per context and instantiation: the answer lives in the context, not in the process.
-template <typename T, typename TO, int BM, int BN, bool DUAL, bool XK, bool CHUNK>
+template <typename T, typename TO, int BM, int BN, bool DUAL, bool XK, bool CHUNK, bool DIL>
 int resident_blocks_per_cu(rn_ctx *ctx)
 {
     constexpr int tile = (BM == 128 ? 0 : 2) + (BN == 128 ? 0 : 1);
     constexpr int types = sizeof(T) == 4 ? 0 : sizeof(TO) == 4 ? 1 : 2;
-    constexpr int id = tile + 4 * ((DUAL ? 1 : 0) + 2 * (XK ? 1 : 0) + 4 * (CHUNK ? 1 : 0)) + 32 * types;
+    constexpr int id = tile + 4 * ((DUAL ? 1 : 0) + 2 * (XK ? 1 : 0) + 4 * (CHUNK ? 1 : 0)) + 32 * types + (DIL ? 128 : 0);
     static_assert(id < (int)(sizeof(ctx->occupancy) / sizeof(ctx->occupancy[0])), "occupancy table");
     if (ctx->occupancy[id] == 0) {
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_gemm_kernel<T, TO, BM, BN, DUAL, XK, CHUNK>, 256,
-                                                         0) != hipSuccess ||
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_gemm_kernel<T, TO, BM, BN, DUAL, XK, CHUNK, DIL>,
+                                                         256, 0) != hipSuccess ||
             nb < 1)
             nb = 1;
         ctx->occupancy[id] = nb;
@@ -848,15 +857,18 @@ int resident_blocks_per_cu(rn_ctx *ctx)
     return ctx->occupancy[id];
 }
 
-template <typename T, typename TO, int BM, int BN, bool DUAL, bool XK, bool CHUNK = false>
+template <typename T, typename TO, int BM, int BN, bool DUAL, bool XK, bool CHUNK = false, bool DIL = false>
 void launch_one(rn_ctx *ctx, GemmParams &p, bool persistent)
 {
+    if constexpr (!DIL && !XK) {  // every form but the exact-K one has a dilated twin
+        if (p.dil != 1) return launch_one<T, TO, BM, BN, DUAL, XK, CHUNK, true>(ctx, p, persistent);
+    }
     unsigned grid = p.grid_items;
     if (persistent) {
-        const unsigned slots = 256u * (unsigned)resident_blocks_per_cu<T, TO, BM, BN, DUAL, XK, CHUNK>(ctx);
+        const unsigned slots = 256u * (unsigned)resident_blocks_per_cu<T, TO, BM, BN, DUAL, XK, CHUNK, DIL>(ctx);
         if (grid > slots) grid = slots;
     }
-    conv_gemm_kernel<T, TO, BM, BN, DUAL, XK, CHUNK><<<dim3(grid), dim3(256), 0, ctx->stream>>>(p);
+    conv_gemm_kernel<T, TO, BM, BN, DUAL, XK, CHUNK, DIL><<<dim3(grid), dim3(256), 0, ctx->stream>>>(p);
 }
 
 template <typename T, typename TO, bool DUAL = false, bool XK = false>
@@ -953,7 +965,7 @@ int launch_gemm(rn_ctx *ctx, int dt_in, int dt_out, const void *inp, void *out, 
                 uint64_t k, uint64_t stride, uint64_t pad, uint64_t h_out, uint64_t w_out,
                 uint64_t B, uint64_t Cin, uint64_t Cout, uint64_t H, uint64_t W,
                 const rn_epilogue *ep, const char *what, const rn_conv_second *second = nullptr,
-                bool exact = false, bool out_nchw = false)
+                bool exact = false, bool out_nchw = false, uint64_t dil = 1)
 {
     const int es = dt_in == RN_DTYPE_BF16 ? 2 : 4;
     const int bke = 128 / es;
@@ -983,6 +995,7 @@ int launch_gemm(rn_ctx *ctx, int dt_in, int dt_out, const void *inp, void *out, 
     p.KW = c4 ? 1 : (int)k;
     p.stride = (int)stride;
     p.pad = (int)pad;
+    p.dil = (int)dil;  // (the small-Cin and exact-K forms are never dilated: their callers pass 1)
     p.cseg = c4 ? 1 : (int)(Cin / bke);
     p.chunk_dw = c4 ? 16 / (4 * es) : 0;  // pixels of a 4-channel image per 16-byte chunk
     p.c4_chunks = c4 ? (int)rn_ceil_div(k, p.chunk_dw) : 0;  // <= 4 in the two-row form (k <= 8)
@@ -1264,7 +1277,7 @@ int launch_gemm(rn_ctx *ctx, int dt_in, int dt_out, const void *inp, void *out, 
 int launch_direct(rn_ctx *ctx, const float *inp, float *out, const float *w, uint64_t k,
                   uint64_t stride, uint64_t pad, uint64_t h_out, uint64_t w_out, uint64_t B,
                   uint64_t Cin, uint64_t Cs, uint64_t Cout, uint64_t H, uint64_t W, int nhwc,
-                  int w_packed, const rn_epilogue *ep, const char *what)
+                  int w_packed, const rn_epilogue *ep, const char *what, uint64_t dil = 1)
 {
     DirectParams p;
     p.in = inp;
@@ -1277,6 +1290,7 @@ int launch_direct(rn_ctx *ctx, const float *inp, float *out, const float *w, uin
     p.k = (int)k;
     p.stride = (int)stride;
     p.pad = (int)pad;
+    p.dil = (int)dil;
     p.Ho = (int)h_out;
     p.Wo = (int)w_out;
     p.Cin = (int)Cin;
@@ -1325,14 +1339,14 @@ bool epilogue_aligned(const rn_epilogue *ep, uintptr_t mask)
                     reinterpret_cast<uintptr_t>(ep->residual)) & mask) == 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rn_conv2d_nhwc_forward(rn_ctx *ctx, const float *inp, float *out, const float *packed_weight,
-                           uint64_t kernel_size, uint64_t stride, uint64_t padding, uint64_t h_out,
-                           uint64_t w_out, uint64_t B, uint64_t in_channels, uint64_t out_channels,
-                           uint64_t H, uint64_t W, const rn_epilogue *epilogue)
+// The bodies of rn_conv2d_nhwc_forward, rn_conv2d_forward and rn_conv2d_nhwc_forward_dt with a dilation: the
+// undilated entry points pass 1, the dilated ones (below) their validated factor -- with 1 they ARE the
+// undilated call.  A dilated call never takes a route that has no dilation: the small-Cin and exact-K
+// packings, the NCHW-native kernel, the strip kernel (rn_conv_strip_eligible) and the recorded list.
+int nhwc_forward(rn_ctx *ctx, const float *inp, float *out, const float *packed_weight,
+                 uint64_t kernel_size, uint64_t stride, uint64_t padding, uint64_t dil, uint64_t h_out,
+                 uint64_t w_out, uint64_t B, uint64_t in_channels, uint64_t out_channels,
+                 uint64_t H, uint64_t W, const rn_epilogue *epilogue)
 {
     RN_ENTER(ctx);
     if (B * out_channels * h_out * w_out == 0) return RN_OK;
@@ -1342,36 +1356,37 @@ int rn_conv2d_nhwc_forward(rn_ctx *ctx, const float *inp, float *out, const floa
     RN_REQUIRE(ctx, epilogue_aligned(epilogue, 3),
                "misaligned scale / shift / residual (fp32 tensors sit on 4-byte boundaries)");
     // any operand off a 16-byte boundary, the epilogue's included: the element-wise kernel
-    if (epilogue_aligned(epilogue, 15) &&
+    // (the small-Cin packing has no dilated form: a dilated call reads its panel through the direct kernel)
+    if (epilogue_aligned(epilogue, 15) && (dil == 1 || in_channels % 32 == 0) &&
         gemm_eligible(inp, out, packed_weight, in_channels, kernel_size,
                       B * H * W * rn_conv2d_input_channels(in_channels),
                       rn_conv2d_packed_weight_numel(in_channels, out_channels, kernel_size),
                       B * h_out * w_out * out_channels)) {
         return launch_gemm(ctx, RN_DTYPE_F32, RN_DTYPE_F32, inp, out, packed_weight, kernel_size,
                            stride, padding, h_out, w_out, B, in_channels, out_channels, H, W,
-                           epilogue, "rn_conv2d_nhwc_forward");
+                           epilogue, "rn_conv2d_nhwc_forward", nullptr, false, false, dil);
     }
     const bool c4 = rn_conv_is_c4(in_channels, kernel_size);
     return launch_direct(ctx, inp, out, packed_weight, kernel_size, stride, padding, h_out, w_out,
                          B, in_channels, rn_conv2d_input_channels(in_channels), out_channels, H, W,
-                         1, c4 ? 2 : 1, epilogue, "rn_conv2d_nhwc_forward(direct)");
+                         1, c4 ? 2 : 1, epilogue, "rn_conv2d_nhwc_forward(direct)", dil);
 }
 
-int rn_conv2d_forward(rn_ctx *ctx, const float *inp, float *out, const float *weight,
-                      uint64_t kernel_size, uint64_t stride, uint64_t padding, uint64_t h_out,
-                      uint64_t w_out, uint64_t B, uint64_t in_channels, uint64_t out_channels,
-                      uint64_t H, uint64_t W)
+int conv2d_forward(rn_ctx *ctx, const float *inp, float *out, const float *weight,
+                   uint64_t kernel_size, uint64_t stride, uint64_t padding, uint64_t dil, uint64_t h_out,
+                   uint64_t w_out, uint64_t B, uint64_t in_channels, uint64_t out_channels,
+                   uint64_t H, uint64_t W)
 {
     if (!ctx) return RN_ERR_INVALID;
     if (B * out_channels * h_out * w_out == 0) return RN_OK;
     RN_TRY(check_conv_args(ctx, inp, out, weight, kernel_size, stride, padding, h_out, w_out, B,
                            in_channels, out_channels, H, W));
     RN_REQUIRE(ctx, in_channels >= 1, "in_channels must be >= 1");
-    if (RN_DEFERS(ctx))  // recorded; runs with the in-place batch-norm / add / ReLU behind it folded in (rn_defer.hip)
+    if (dil == 1 && RN_DEFERS(ctx))  // recorded; runs with the in-place batch-norm / add / ReLU behind it folded in (rn_defer.hip)
         return rn_defer_conv(ctx, inp, out, weight, kernel_size, stride, padding, h_out, w_out, B, in_channels,
                              out_channels, H, W);
     RN_ENTER(ctx);
-    const bool c4 = rn_conv_is_c4(in_channels, kernel_size);
+    const bool c4 = dil == 1 && rn_conv_is_c4(in_channels, kernel_size);
     const bool fast = (in_channels % 32 == 0 || c4) && kernel_size <= 15 &&
                       B * H * W * rn_conv2d_input_channels(in_channels) < (1ull << 29) &&
                       B * h_out * w_out * out_channels < (1ull << 29) &&
@@ -1382,11 +1397,11 @@ int rn_conv2d_forward(rn_ctx *ctx, const float *inp, float *out, const float *we
         return launch_direct(ctx, inp, out, weight, kernel_size, stride, padding, h_out, w_out, B,
                              in_channels, in_channels, out_channels, H, W,
                              ctx->layout == RN_LAYOUT_NHWC, 0, nullptr,
-                             "rn_conv2d_forward(direct)");
+                             "rn_conv2d_forward(direct)", dil);
     }
     // NCHW tensors: NCHW is the MFMA's own layout with the operands swapped (rn_conv_nchw.hip) -- no transpose of
     // the input, the same bits.  1x1: the OIHW weight as it is, no packing either
-    const bool native = ctx->layout == RN_LAYOUT_NCHW && h_out == (H + 2 * padding - kernel_size) / stride + 1 &&
+    const bool native = dil == 1 && ctx->layout == RN_LAYOUT_NCHW && h_out == (H + 2 * padding - kernel_size) / stride + 1 &&
                         w_out == (W + 2 * padding - kernel_size) / stride + 1 &&
                         rn_conv_nchw_eligible(kernel_size, stride, padding, B, in_channels, out_channels, H, W);
     if (native && kernel_size == 1 && padding == 0 && (reinterpret_cast<uintptr_t>(weight) & 15) == 0)
@@ -1406,7 +1421,7 @@ int rn_conv2d_forward(rn_ctx *ctx, const float *inp, float *out, const float *we
     if (!taps && (wide & 15) != 0)
         return launch_direct(ctx, inp, out, weight, kernel_size, stride, padding, h_out, w_out, B, in_channels,
                              in_channels, out_channels, H, W, ctx->layout == RN_LAYOUT_NHWC, 0, nullptr,
-                             "rn_conv2d_forward(direct)");
+                             "rn_conv2d_forward(direct)", dil);
     // K-major panel of the OIHW weight: packed per call into scratch, or -- with the context's
     // weight cache on -- once per (weight buffer, shape) and kept until that buffer is freed or
     // written through the rn_* calls
@@ -1427,7 +1442,7 @@ int rn_conv2d_forward(rn_ctx *ctx, const float *inp, float *out, const float *we
     if (ctx->layout == RN_LAYOUT_NHWC) {
         return launch_gemm(ctx, RN_DTYPE_F32, RN_DTYPE_F32, inp, out, wp, kernel_size, stride,
                            padding, h_out, w_out, B, in_channels, out_channels, H, W, nullptr,
-                           "rn_conv2d_forward(nhwc)");
+                           "rn_conv2d_forward(nhwc)", nullptr, false, false, dil);
     }
     if (taps)
         return rn_conv_nchw_launch(ctx, inp, out, (const float *)wp, kernel_size, stride, padding, B, in_channels,
@@ -1443,21 +1458,20 @@ int rn_conv2d_forward(rn_ctx *ctx, const float *inp, float *out, const float *we
     }
     return launch_gemm(ctx, RN_DTYPE_F32, RN_DTYPE_F32, xin, out, wp, kernel_size, stride, padding,
                        h_out, w_out, B, in_channels, out_channels, H, W, nullptr,
-                       "rn_conv2d_forward(gemm)", nullptr, false, true);
+                       "rn_conv2d_forward(gemm)", nullptr, false, true, dil);
 }
 
-int rn_conv2d_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const void *inp, void *out,
-                              const void *packed_weight, uint64_t kernel_size, uint64_t stride,
-                              uint64_t padding, uint64_t h_out, uint64_t w_out, uint64_t B,
-                              uint64_t in_channels, uint64_t out_channels, uint64_t H, uint64_t W,
-                              const rn_epilogue *epilogue)
+int nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const void *inp, void *out,
+                    const void *packed_weight, uint64_t kernel_size, uint64_t stride,
+                    uint64_t padding, uint64_t dil, uint64_t h_out, uint64_t w_out, uint64_t B,
+                    uint64_t in_channels, uint64_t out_channels, uint64_t H, uint64_t W,
+                    const rn_epilogue *epilogue)
 {
     RN_ENTER(ctx);
     if (dtype == RN_DTYPE_F32) {
         RN_REQUIRE(ctx, out_dtype == RN_DTYPE_F32, "fp32 input implies fp32 output");
-        return rn_conv2d_nhwc_forward(ctx, (const float *)inp, (float *)out,
-                                      (const float *)packed_weight, kernel_size, stride, padding,
-                                      h_out, w_out, B, in_channels, out_channels, H, W, epilogue);
+        return nhwc_forward(ctx, (const float *)inp, (float *)out, (const float *)packed_weight, kernel_size,
+                            stride, padding, dil, h_out, w_out, B, in_channels, out_channels, H, W, epilogue);
     }
     RN_REQUIRE(ctx, dtype == RN_DTYPE_BF16, "unknown dtype");
     if (B * out_channels * h_out * w_out == 0) return RN_OK;
@@ -1467,6 +1481,8 @@ int rn_conv2d_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const void 
                "kernel_size / stride / padding out of range");
     const bool c4 = rn_conv_is_c4(in_channels, kernel_size);
     const uint64_t cs = c4 ? 4 : in_channels;
+    if (c4 && dil != 1)
+        return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "the bf16 small-Cin form has no dilation");
     if (c4) {
         // two 4-channel pixels per 16-byte chunk: the image must carry its own zero border
         RN_REQUIRE(ctx, padding == 0 && stride % 2 == 0 && W % 2 == 0,
@@ -1486,7 +1502,103 @@ int rn_conv2d_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const void 
     RN_REQUIRE(ctx, epilogue_aligned(epilogue, 15), "misaligned scale / shift / residual (16-byte alignment)");
     return launch_gemm(ctx, RN_DTYPE_BF16, out_dtype, inp, out, packed_weight, kernel_size, stride,
                        padding, h_out, w_out, B, in_channels, out_channels, H, W, epilogue,
-                       "rn_conv2d_nhwc_forward_dt");
+                       "rn_conv2d_nhwc_forward_dt", nullptr, false, false, dil);
+}
+
+// what the dilated entry points check before anything is launched; k == 1 has one tap, so its dilation is 1
+int check_dilation(rn_ctx *ctx, uint64_t k, uint64_t stride, uint64_t pad, uint64_t *dil, uint64_t h_out,
+                   uint64_t w_out, uint64_t H, uint64_t W)
+{
+    RN_REQUIRE(ctx, *dil >= 1 && *dil <= RN_CONV_MAX_DILATION, "dilation must be 1..RN_CONV_MAX_DILATION");
+    RN_REQUIRE(ctx, k >= 1 && k < (1u << 12) && stride >= 1 && stride < (1u << 12) && pad < (1u << 12),
+               "kernel_size / stride / padding out of range");
+    RN_REQUIRE(ctx, H < (1ull << 31) && W < (1ull << 31), "dimension too large");
+    RN_REQUIRE(ctx, rn_conv_output_size_dilated(H, k, stride, pad, *dil) == h_out &&
+                        rn_conv_output_size_dilated(W, k, stride, pad, *dil) == w_out,
+               "h_out / w_out are not the dilated convolution's output size");
+    if (k == 1) *dil = 1;
+    return RN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t rn_conv_output_size_dilated(uint64_t x, uint64_t kernel_size, uint64_t stride, uint64_t padding,
+                                     uint64_t dilation)
+{
+    if (kernel_size == 0 || stride == 0 || dilation == 0) return 0;
+    const uint64_t span = dilation * (kernel_size - 1) + 1;  // the dilated kernel's extent
+    if (x + 2 * padding < span) return 0;
+    return (x + 2 * padding - span) / stride + 1;
+}
+
+int rn_conv2d_nhwc_forward(rn_ctx *ctx, const float *inp, float *out, const float *packed_weight,
+                           uint64_t kernel_size, uint64_t stride, uint64_t padding, uint64_t h_out,
+                           uint64_t w_out, uint64_t B, uint64_t in_channels, uint64_t out_channels,
+                           uint64_t H, uint64_t W, const rn_epilogue *epilogue)
+{
+    return nhwc_forward(ctx, inp, out, packed_weight, kernel_size, stride, padding, 1, h_out, w_out, B, in_channels,
+                        out_channels, H, W, epilogue);
+}
+
+int rn_conv2d_forward(rn_ctx *ctx, const float *inp, float *out, const float *weight,
+                      uint64_t kernel_size, uint64_t stride, uint64_t padding, uint64_t h_out,
+                      uint64_t w_out, uint64_t B, uint64_t in_channels, uint64_t out_channels,
+                      uint64_t H, uint64_t W)
+{
+    return conv2d_forward(ctx, inp, out, weight, kernel_size, stride, padding, 1, h_out, w_out, B, in_channels,
+                          out_channels, H, W);
+}
+
+int rn_conv2d_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const void *inp, void *out,
+                              const void *packed_weight, uint64_t kernel_size, uint64_t stride,
+                              uint64_t padding, uint64_t h_out, uint64_t w_out, uint64_t B,
+                              uint64_t in_channels, uint64_t out_channels, uint64_t H, uint64_t W,
+                              const rn_epilogue *epilogue)
+{
+    return nhwc_forward_dt(ctx, dtype, out_dtype, inp, out, packed_weight, kernel_size, stride, padding, 1, h_out,
+                           w_out, B, in_channels, out_channels, H, W, epilogue);
+}
+
+int rn_conv2d_dilated_forward(rn_ctx *ctx, const float *inp, float *out, const float *weight, uint64_t kernel_size,
+                              uint64_t stride, uint64_t padding, uint64_t dilation, uint64_t h_out, uint64_t w_out,
+                              uint64_t B, uint64_t in_channels, uint64_t out_channels, uint64_t H, uint64_t W,
+                              uint64_t groups)
+{
+    if (!ctx) return RN_ERR_INVALID;
+    RN_TRY(check_dilation(ctx, kernel_size, stride, padding, &dilation, h_out, w_out, H, W));
+    if (groups != 1)
+        return rn_conv_group_forward(ctx, inp, out, weight, kernel_size, stride, padding, dilation, h_out, w_out, B,
+                                     in_channels, out_channels, H, W, groups);
+    return conv2d_forward(ctx, inp, out, weight, kernel_size, stride, padding, dilation, h_out, w_out, B, in_channels,
+                          out_channels, H, W);
+}
+
+int rn_conv2d_dilated_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const void *inp, void *out,
+                                      const void *packed_weight, uint64_t kernel_size, uint64_t stride,
+                                      uint64_t padding, uint64_t dilation, uint64_t h_out, uint64_t w_out, uint64_t B,
+                                      uint64_t in_channels, uint64_t out_channels, uint64_t H, uint64_t W,
+                                      uint64_t groups, const rn_epilogue *epilogue)
+{
+    if (!ctx) return RN_ERR_INVALID;
+    RN_TRY(check_dilation(ctx, kernel_size, stride, padding, &dilation, h_out, w_out, H, W));
+    if (groups != 1)
+        return rn_conv_group_nhwc_forward_dt(ctx, dtype, out_dtype, inp, out, packed_weight, kernel_size, stride,
+                                             padding, dilation, h_out, w_out, B, in_channels, out_channels, H, W,
+                                             groups, epilogue);
+    return nhwc_forward_dt(ctx, dtype, out_dtype, inp, out, packed_weight, kernel_size, stride, padding, dilation,
+                           h_out, w_out, B, in_channels, out_channels, H, W, epilogue);
+}
+
+// library-internal (rn_private.h): the dense contraction of a bf16 grouped panel, dilated
+int rn_conv_dense_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const void *inp, void *out,
+                                  const void *packed_weight, uint64_t kernel_size, uint64_t stride, uint64_t padding,
+                                  uint64_t dilation, uint64_t h_out, uint64_t w_out, uint64_t B, uint64_t in_channels,
+                                  uint64_t out_channels, uint64_t H, uint64_t W, const rn_epilogue *epilogue)
+{
+    return nhwc_forward_dt(ctx, dtype, out_dtype, inp, out, packed_weight, kernel_size, stride, padding, dilation,
+                           h_out, w_out, B, in_channels, out_channels, H, W, epilogue);
 }
 
 int rn_conv2d_nhwc_exact_forward(rn_ctx *ctx, const float *inp_padded, float *out,

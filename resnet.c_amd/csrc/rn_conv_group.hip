@@ -35,6 +35,7 @@
 // dense bf16 contraction; the forward is rn_conv2d_nhwc_forward_dt on it (correct for every Cg,
 // wasteful by G; a non-finite input surfaces in every output channel of its pixel neighbourhood).
 #include "rn_conv_params.h"
+#include "rn_private.h"
 
 using rn_gemm::f32x16;
 
@@ -59,6 +60,7 @@ struct GroupParams {
     int sgs;  // super-groups: C / 32
     int out_nchw;
     unsigned mul_hw, shr_hw, mul_w, shr_w;
+    int dil;  // dilation (>= 1): kernel row kh reads input row ih0 + kh * dil, columns alike
 };
 
 // packed index of weight (o, channel cl of the super-group's input slice, tap)
@@ -69,6 +71,8 @@ __host__ __device__ inline uint64_t packed_index(int o, int cl, int tap, int nq)
     return ((((uint64_t)(sg * nq + q) * TAPS + tap) * 16 + s) * 2 + h) * SG + n;
 }
 
+// DIL: p.dil > 1 (a flag of the instantiation: the undilated launches keep their row setup as it was)
+template <bool DIL>
 __global__ __launch_bounds__(256) void conv_group_kernel(const GroupParams p)
 {
     __shared__ __attribute__((aligned(16))) float wl[SLICE];
@@ -94,12 +98,22 @@ __global__ __launch_bounds__(256) void conv_group_kernel(const GroupParams p)
             const int ow = rem - oh * p.Wo;
             const int ih0 = oh * p.stride - p.pad, iw0 = ow * p.stride - p.pad;
             a_off[mt] = ((long long)(b * p.H + ih0) * p.W + iw0) * p.C + cin0 + 4 * h;
+            if constexpr (!DIL) {
 #pragma unroll
-            for (int kh = 0; kh < 3; ++kh)
+                for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
-                for (int kw = 0; kw < 3; ++kw)
-                    if (ih0 + kh >= 0 && ih0 + kh < p.H && iw0 + kw >= 0 && iw0 + kw < p.W)
-                        a_mask[mt] |= 1 << (kh * 3 + kw);
+                    for (int kw = 0; kw < 3; ++kw)
+                        if (ih0 + kh >= 0 && ih0 + kh < p.H && iw0 + kw >= 0 && iw0 + kw < p.W)
+                            a_mask[mt] |= 1 << (kh * 3 + kw);
+            } else {
+#pragma unroll
+                for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+                    for (int kw = 0; kw < 3; ++kw)
+                        if (ih0 + kh * p.dil >= 0 && ih0 + kh * p.dil < p.H && iw0 + kw * p.dil >= 0 &&
+                            iw0 + kw * p.dil < p.W)
+                            a_mask[mt] |= 1 << (kh * 3 + kw);
+            }
         }
     }
 
@@ -122,7 +136,7 @@ __global__ __launch_bounds__(256) void conv_group_kernel(const GroupParams p)
         f32x4 a[2][2][4];  // [buffer][row tile][float4 j]
         auto load_tap = [&](int tap, f32x4 (&dstv)[2][4]) {
             const int kh = tap / 3, kw = tap % 3;
-            const long long toff = (long long)(kh * p.W + kw) * p.C + q * SG;
+            const long long toff = (long long)(kh * p.W + kw) * (DIL ? p.dil : 1) * p.C + q * SG;
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {
                 const bool ok = (a_mask[mt] >> tap) & 1;
@@ -182,7 +196,7 @@ struct GroupDirectParams {
     float *out;
     const float *scale, *shift, *residual;
     int relu;
-    int k, stride, pad, Ho, Wo, Cin, Cout, H, W, groups;
+    int k, stride, pad, dil, Ho, Wo, Cin, Cout, H, W, groups;
     int nhwc;      // activation layout
     int w_packed;  // 0: OIHW [Cout][Cin/G][k][k]; 1: the super-group pack of the fast path
     uint64_t total;
@@ -217,10 +231,10 @@ __global__ __launch_bounds__(256) void conv_group_direct_kernel(const GroupDirec
         float sum = 0.f;
         for (int ic = 0; ic < cg; ++ic) {
             for (int kh = 0; kh < p.k; ++kh) {
-                const int ih = ih0 + kh;
+                const int ih = ih0 + kh * p.dil;
                 if (ih < 0 || ih >= p.H) continue;
                 for (int kw = 0; kw < p.k; ++kw) {
-                    const int iw = iw0 + kw;
+                    const int iw = iw0 + kw * p.dil;
                     if (iw < 0 || iw >= p.W) continue;
                     const uint64_t ii = p.nhwc ? (((b * p.H + ih) * p.W + iw) * p.Cin + c0 + ic)
                                                : (((b * p.Cin + c0 + ic) * p.H + ih) * p.W + iw);
@@ -308,8 +322,8 @@ bool aligned16(const void *a, const void *b, const void *c, const rn_epilogue *e
 }
 
 int check_args(rn_ctx *ctx, const void *inp, const void *out, const void *weight, uint64_t k, uint64_t stride,
-               uint64_t pad, uint64_t h_out, uint64_t w_out, uint64_t B, uint64_t Cin, uint64_t Cout, uint64_t H,
-               uint64_t W, uint64_t groups)
+               uint64_t pad, uint64_t dil, uint64_t h_out, uint64_t w_out, uint64_t B, uint64_t Cin, uint64_t Cout,
+               uint64_t H, uint64_t W, uint64_t groups)
 {
     RN_REQUIRE(ctx, inp && out && weight, "null tensor");
     RN_REQUIRE(ctx, inp != out, "conv2d cannot run in place");
@@ -317,8 +331,9 @@ int check_args(rn_ctx *ctx, const void *inp, const void *out, const void *weight
     RN_REQUIRE(ctx, k < (1u << 12) && stride < (1u << 12) && pad < (1u << 12), "dimension too large");
     RN_REQUIRE(ctx, shape_ok(Cin, Cout, groups), "groups must divide in_channels and out_channels");
     RN_REQUIRE(ctx, groups >= 2, "groups == 1 is rn_conv2d_forward / rn_conv2d_nhwc_forward");
-    RN_REQUIRE(ctx, H + 2 * pad >= k && W + 2 * pad >= k && h_out == (H + 2 * pad - k) / stride + 1 &&
-                        w_out == (W + 2 * pad - k) / stride + 1,
+    const uint64_t span = dil * (k - 1) + 1;  // the (dilated) kernel's extent
+    RN_REQUIRE(ctx, H + 2 * pad >= span && W + 2 * pad >= span && h_out == (H + 2 * pad - span) / stride + 1 &&
+                        w_out == (W + 2 * pad - span) / stride + 1,
                "h_out / w_out do not match the input");
     RN_REQUIRE(ctx, B * H * W * Cin < (1ull << 29) && B * h_out * w_out * Cout < (1ull << 29) &&
                         Cout * (Cin / groups < 32 ? 32 : Cin / groups) * k * k < (1ull << 29),
@@ -327,7 +342,7 @@ int check_args(rn_ctx *ctx, const void *inp, const void *out, const void *weight
 }
 
 int launch_fast(rn_ctx *ctx, const float *inp, float *out, const float *packed, uint64_t stride, uint64_t pad,
-                uint64_t h_out, uint64_t w_out, uint64_t B, uint64_t C, uint64_t H, uint64_t W, uint64_t groups,
+                uint64_t dil, uint64_t h_out, uint64_t w_out, uint64_t B, uint64_t C, uint64_t H, uint64_t W, uint64_t groups,
                 const rn_epilogue *ep, int out_nchw, const char *what)
 {
     GroupParams p;
@@ -346,6 +361,7 @@ int launch_fast(rn_ctx *ctx, const float *inp, float *out, const float *packed, 
     p.Wo = (int)w_out;
     p.stride = (int)stride;
     p.pad = (int)pad;
+    p.dil = (int)dil;
     p.M = (int)(B * h_out * w_out);
     p.HoWo = (int)(h_out * w_out);
     p.kc = (int)(cg > SG ? cg : (uint64_t)SG);
@@ -354,12 +370,15 @@ int launch_fast(rn_ctx *ctx, const float *inp, float *out, const float *packed, 
     rn_fast_div((unsigned)p.HoWo, &p.mul_hw, &p.shr_hw);
     rn_fast_div((unsigned)p.Wo, &p.mul_w, &p.shr_w);
     const uint64_t blocks = rn_ceil_div((uint64_t)p.M, BM) * (uint64_t)p.sgs;
-    conv_group_kernel<<<(unsigned)blocks, 256, 0, ctx->stream>>>(p);
+    if (dil != 1)
+        conv_group_kernel<true><<<(unsigned)blocks, 256, 0, ctx->stream>>>(p);
+    else
+        conv_group_kernel<false><<<(unsigned)blocks, 256, 0, ctx->stream>>>(p);
     return rn_after_launch(ctx, what);
 }
 
 int launch_group_direct(rn_ctx *ctx, const float *inp, float *out, const float *w, uint64_t k, uint64_t stride,
-                        uint64_t pad, uint64_t h_out, uint64_t w_out, uint64_t B, uint64_t Cin, uint64_t Cout,
+                        uint64_t pad, uint64_t dil, uint64_t h_out, uint64_t w_out, uint64_t B, uint64_t Cin, uint64_t Cout,
                         uint64_t H, uint64_t W, uint64_t groups, int nhwc, int w_packed, const rn_epilogue *ep,
                         const char *what)
 {
@@ -374,6 +393,7 @@ int launch_group_direct(rn_ctx *ctx, const float *inp, float *out, const float *
     p.k = (int)k;
     p.stride = (int)stride;
     p.pad = (int)pad;
+    p.dil = (int)dil;
     p.Ho = (int)h_out;
     p.Wo = (int)w_out;
     p.Cin = (int)Cin;
@@ -443,13 +463,25 @@ int rn_conv2d_grouped_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, con
                                       uint64_t in_channels, uint64_t out_channels, uint64_t H, uint64_t W,
                                       uint64_t groups, const rn_epilogue *epilogue)
 {
+    return rn_conv_group_nhwc_forward_dt(ctx, dtype, out_dtype, inp, out, packed_weight, kernel_size, stride, padding,
+                                         1, h_out, w_out, B, in_channels, out_channels, H, W, groups, epilogue);
+}
+
+// library-internal (rn_private.h): the entry point above with a dilation the caller has validated
+int rn_conv_group_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const void *inp, void *out,
+                                  const void *packed_weight, uint64_t kernel_size, uint64_t stride, uint64_t padding,
+                                  uint64_t dilation, uint64_t h_out, uint64_t w_out, uint64_t B, uint64_t in_channels,
+                                  uint64_t out_channels, uint64_t H, uint64_t W, uint64_t groups,
+                                  const rn_epilogue *epilogue)
+{
     RN_ENTER(ctx);
     if (B * out_channels * h_out * w_out == 0) return RN_OK;
-    RN_TRY(check_args(ctx, inp, out, packed_weight, kernel_size, stride, padding, h_out, w_out, B, in_channels,
-                      out_channels, H, W, groups));
+    RN_TRY(check_args(ctx, inp, out, packed_weight, kernel_size, stride, padding, dilation, h_out, w_out, B,
+                      in_channels, out_channels, H, W, groups));
     if (dtype == RN_DTYPE_BF16)  // dense panel with zeros outside the groups: the dense contraction
-        return rn_conv2d_nhwc_forward_dt(ctx, dtype, out_dtype, inp, out, packed_weight, kernel_size, stride, padding,
-                                         h_out, w_out, B, in_channels, out_channels, H, W, epilogue);
+        return rn_conv_dense_nhwc_forward_dt(ctx, dtype, out_dtype, inp, out, packed_weight, kernel_size, stride,
+                                             padding, dilation, h_out, w_out, B, in_channels, out_channels, H, W,
+                                             epilogue);
     RN_REQUIRE(ctx, dtype == RN_DTYPE_F32 && out_dtype == RN_DTYPE_F32, "fp32 input implies fp32 output");
     const rn_epilogue none = {nullptr, nullptr, nullptr, 0};
     const rn_epilogue *ep = epilogue ? epilogue : &none;
@@ -459,10 +491,10 @@ int rn_conv2d_grouped_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, con
                "misaligned tensor (fp32 tensors sit on 4-byte boundaries)");
     const bool fs = fast_shape(in_channels, out_channels, kernel_size, groups);
     if (fs && aligned16(inp, out, packed_weight, epilogue))
-        return launch_fast(ctx, (const float *)inp, (float *)out, (const float *)packed_weight, stride, padding, h_out,
-                           w_out, B, in_channels, H, W, groups, epilogue, 0, "rn_conv2d_grouped_nhwc_forward_dt");
+        return launch_fast(ctx, (const float *)inp, (float *)out, (const float *)packed_weight, stride, padding,
+                           dilation, h_out, w_out, B, in_channels, H, W, groups, epilogue, 0, "rn_conv2d_grouped_nhwc_forward_dt");
     return launch_group_direct(ctx, (const float *)inp, (float *)out, (const float *)packed_weight, kernel_size, stride,
-                               padding, h_out, w_out, B, in_channels, out_channels, H, W, groups, 1, fs ? 1 : 0,
+                               padding, dilation, h_out, w_out, B, in_channels, out_channels, H, W, groups, 1, fs ? 1 : 0,
                                epilogue, "rn_conv2d_grouped_nhwc_forward_dt(direct)");
 }
 
@@ -470,10 +502,20 @@ int rn_conv2d_grouped_forward(rn_ctx *ctx, const float *inp, float *out, const f
                               uint64_t stride, uint64_t padding, uint64_t h_out, uint64_t w_out, uint64_t B,
                               uint64_t in_channels, uint64_t out_channels, uint64_t H, uint64_t W, uint64_t groups)
 {
+    return rn_conv_group_forward(ctx, inp, out, weight, kernel_size, stride, padding, 1, h_out, w_out, B, in_channels,
+                                 out_channels, H, W, groups);
+}
+
+// library-internal (rn_private.h): the entry point above with a dilation the caller has validated
+int rn_conv_group_forward(rn_ctx *ctx, const float *inp, float *out, const float *weight, uint64_t kernel_size,
+                          uint64_t stride, uint64_t padding, uint64_t dilation, uint64_t h_out, uint64_t w_out,
+                          uint64_t B, uint64_t in_channels, uint64_t out_channels, uint64_t H, uint64_t W,
+                          uint64_t groups)
+{
     RN_ENTER(ctx);  // on a deferred context: runs what is recorded, then this call at once
     if (B * out_channels * h_out * w_out == 0) return RN_OK;
-    RN_TRY(check_args(ctx, inp, out, weight, kernel_size, stride, padding, h_out, w_out, B, in_channels, out_channels,
-                      H, W, groups));
+    RN_TRY(check_args(ctx, inp, out, weight, kernel_size, stride, padding, dilation, h_out, w_out, B, in_channels,
+                      out_channels, H, W, groups));
     RN_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(inp) | reinterpret_cast<uintptr_t>(out) |
                       reinterpret_cast<uintptr_t>(weight)) & 3) == 0,
                "misaligned tensor (fp32 tensors sit on 4-byte boundaries)");
@@ -481,7 +523,7 @@ int rn_conv2d_grouped_forward(rn_ctx *ctx, const float *inp, float *out, const f
     // as for the dense entry points: the matrix-core path when every operand sits on a 16-byte boundary
     const bool fast = fast_shape(in_channels, out_channels, kernel_size, groups) && aligned16(inp, out, weight, nullptr);
     if (!fast)  // exact reference order; OIHW weights as given
-        return launch_group_direct(ctx, inp, out, weight, kernel_size, stride, padding, h_out, w_out, B, in_channels,
+        return launch_group_direct(ctx, inp, out, weight, kernel_size, stride, padding, dilation, h_out, w_out, B, in_channels,
                                    out_channels, H, W, groups, nhwc, 0, nullptr, "rn_conv2d_grouped_forward(direct)");
     void *wp = nullptr;
     const uint64_t pn = packed_numel(in_channels, out_channels, kernel_size, groups);
@@ -490,12 +532,12 @@ int rn_conv2d_grouped_forward(rn_ctx *ctx, const float *inp, float *out, const f
                                                                         (int)(in_channels / groups), pn);
     RN_TRY(rn_after_launch(ctx, "rn_conv2d_grouped_forward(pack)"));
     if (nhwc)
-        return launch_fast(ctx, inp, out, (const float *)wp, stride, padding, h_out, w_out, B, in_channels, H, W, groups,
+        return launch_fast(ctx, inp, out, (const float *)wp, stride, padding, dilation, h_out, w_out, B, in_channels, H, W, groups,
                            nullptr, 0, "rn_conv2d_grouped_forward(nhwc)");
     void *xin = nullptr;
     RN_TRY(rn_scratch(ctx, 2, B * H * W * in_channels * sizeof(float), &xin));
     RN_TRY(rn_nchw_to_nhwc(ctx, inp, (float *)xin, B, in_channels, H, W));
-    return launch_fast(ctx, (const float *)xin, out, (const float *)wp, stride, padding, h_out, w_out, B, in_channels, H,
+    return launch_fast(ctx, (const float *)xin, out, (const float *)wp, stride, padding, dilation, h_out, w_out, B, in_channels, H,
                        W, groups, nullptr, 1, "rn_conv2d_grouped_forward");
 }
 

@@ -77,6 +77,9 @@ struct GemmParams {
     int out_nchw;
     // diagnostic only (tools/conv_stamps.py): 16 stamp slots per block, or null
     unsigned long long *stamps;
+    // dilation (>= 1): kernel row kh reads input row ih0 + kh * dil, columns alike.  Above 1 only with
+    // tap_rows == 1, chunk_dw == 0 and kreal == 0 (the small-Cin and exact-K forms have no dilation)
+    int dil;
 };
 
 typedef __bf16 bf16_t;
@@ -93,6 +96,20 @@ template <>
 struct Elem<bf16_t> {
     static constexpr int CH = 8;
 };
+
+#ifdef __HIPCC__
+// Which of K taps x0, x0 + d, x0 + 2d, ... lie inside [0, X): bit t for tap t (the valid ones are a contiguous
+// range of t, as without a dilation, but its ends would take two divisions: the taps are tested one by one)
+__device__ __forceinline__ int tap_mask(int x0, int K, int X, int d)
+{
+    int m = 0;
+    for (int t = 0; t < K; ++t) {
+        const int x = x0 + t * d;
+        if (x >= 0 && x < X) m |= 1 << t;
+    }
+    return m;
+}
+#endif
 
 }  // namespace rn_gemm
 

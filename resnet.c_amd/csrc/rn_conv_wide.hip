@@ -132,8 +132,12 @@ __global__ __launch_bounds__(512, LDS_CAP <= 80 * 1024 ? 4 : 2) void conv_wide_k
             a_off[j] = ((b * p.H + ih0) * p.W + iw0) * p.Cs * 2 + chunk;
             const int rlo = max(0, -ih0), rhi = min(p.KH, p.H - ih0);
             const int clo = max(0, -iw0), chi = min(p.KW, p.W - iw0);
-            const int rm = rhi > rlo ? ((1 << rhi) - 1) & ~((1 << rlo) - 1) : 0;
-            const int cm = chi > clo ? ((1 << chi) - 1) & ~((1 << clo) - 1) : 0;
+            int rm = rhi > rlo ? ((1 << rhi) - 1) & ~((1 << rlo) - 1) : 0;
+            int cm = chi > clo ? ((1 << chi) - 1) & ~((1 << clo) - 1) : 0;
+            if (p.dil != 1) {  // launch-uniform: a dilated launch tests its taps one by one
+                rm = tap_mask(ih0, p.KH, p.H, p.dil);
+                cm = tap_mask(iw0, p.KW, p.W, p.dil);
+            }
             a_mask[j] = rm | (cm << 16);
             if constexpr (DUAL)
                 a_off2[j] = ((b * p.H2 + oh * p.stride2) * p.W2 + ow * p.stride2) * p.Cs2 * 2 + chunk;
@@ -176,7 +180,8 @@ __global__ __launch_bounds__(512, LDS_CAP <= 80 * 1024 ? 4 : 2) void conv_wide_k
             if (s_cs == 0) {
                 const unsigned ukh = p.KW == 1 ? tap : (__umulhi(tap, p.mul_kw) >> p.shr_kw);
                 const int s_kh = (int)ukh, s_kw = (int)(tap - ukh * (unsigned)p.KW);
-                const int toff = (s_kh * p.W + s_kw) * p.Cs * 2;  // tap_rows == 1 (eligibility)
+                // tap_rows == 1 (eligibility); unsigned: a dilated tap outside every image may wrap, masked
+                const int toff = (int)((unsigned)(s_kh * p.W + s_kw) * (unsigned)(p.dil * p.Cs * 2));
 #pragma unroll
                 for (int j = 0; j < PA; ++j) {
                     const bool ok = ((a_mask[j] >> s_kh) & (a_mask[j] >> (16 + s_kw)) & 1) != 0;
@@ -968,7 +973,7 @@ void rn_conv_wide_launch(rn_ctx *ctx, GemmParams &p, int which, bool dual)
 
 bool rn_conv_strip_eligible(const GemmParams &p)
 {
-    const bool common = p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1 && p.chunk_dw == 0 && p.kreal == 0 &&
+    const bool common = p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1 && p.dil == 1 && p.chunk_dw == 0 && p.kreal == 0 &&
                         p.tap_rows == 1 && (reinterpret_cast<uintptr_t>(p.residual) & 15) == 0 &&
                         p.Ho == p.H && p.Wo == p.W &&
                         (uint64_t)(p.M / (p.H * p.W) * (p.H + 1) + 1) * (uint64_t)(p.W + 2) < (1ull << 30);

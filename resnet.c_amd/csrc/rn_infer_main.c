@@ -5,11 +5,13 @@
  * B = 1, paths); here the same defaults can be overridden from the command line.
  *
  *   rn_infer [--arch 18|34|50|101|152|resnext50_32x4d|resnext101_32x8d|resnext101_64x4d|wide_resnet50_2|wide_resnet101_2] [--weights DIR] [--input FILE | --u8 FILE | --rgb FILE --hw H,W] [--batch B]
- *            [--size H,W] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,c,...]
+ *            [--size H,W] [--dilate a,b,c] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,c,...]
  *
  * --size H,W sets the model's input size (rn_model_set_input_size; default 224,224; single device only):
  * --input then holds B x 3 x H x W floats and --u8 B x H x W x 3 bytes, and a file of any other length is
  * refused with the size in the message.
+ * --dilate a,b,c (each 0 or 1) is torchvision's replace_stride_with_dilation for layer2, layer3, layer4
+ * (rn_model_set_dilation; bottleneck networks, single device only): the same weights at output stride 16, 8 or 4.
  * --u8 FILE reads B x 150528 raw bytes, the decoder's 8-bit RGB crops ([B,224,224,3]), instead of
  * the preprocessed fp32 file: the device normalises them (rn_model_forward_u8), same lines out.
  * --rgb FILE --hw H,W reads the H x W x 3 raw bytes of ONE decoded image of any size: the device resizes
@@ -138,6 +140,7 @@ int main(int argc, char **argv)
     float *top_prob_dev = NULL, *top_prob = NULL;
     uint64_t *top_idx_dev = NULL, *top_idx = NULL;
     int rgb = 0;
+    int dilate[3] = {0, 0, 0}; /* --dilate */
     const char *weights = "weights_bin";
     const char *input = "test_bins/ILSVRC2012_val_00004749.bin";
     rn_ctx *ctx = NULL;
@@ -170,6 +173,10 @@ int main(int argc, char **argv)
             size_w = (q && *q == ',') ? strtoull(q + 1, NULL, 10) : 0;
             ++i;
         }
+        else if (!strcmp(a, "--dilate") && v) {
+            if (sscanf(v, "%d,%d,%d", &dilate[0], &dilate[1], &dilate[2]) != 3) dilate[0] = -1; /* refused below */
+            ++i;
+        }
         else if (!strcmp(a, "--batch") && v) { B = strtoull(v, NULL, 10); ++i; }
         else if (!strcmp(a, "--classes") && v) { classes = strtoull(v, NULL, 10); ++i; }
         else if (!strcmp(a, "--topk") && v) { topk = strtoull(v, NULL, 10); ++i; }
@@ -185,7 +192,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--mode") && v) { mode = strcmp(v, "ops") ? RN_FWD_FUSED : RN_FWD_REFERENCE_OPS; ++i; }
         else {
             fprintf(stderr, "usage: %s [--arch 18|34|50|101|152|resnext50_32x4d|resnext101_32x8d|resnext101_64x4d|wide_resnet50_2|wide_resnet101_2] [--weights DIR] [--input FILE | --u8 FILE | --rgb FILE --hw H,W] "
-                            "[--batch B] [--size H,W] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,...] [--classes N] [--topk K]\n",
+                            "[--batch B] [--size H,W] [--dilate a,b,c] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,...] [--classes N] [--topk K]\n",
                     argv[0]);
             return 2;
         }
@@ -206,6 +213,11 @@ int main(int argc, char **argv)
                         "cropped to 224 x 224)\n", rn_status_string(RN_ERR_UNSUPPORTED));
         return 1;
     }
+    if ((dilate[0] || dilate[1] || dilate[2]) && ndev > 0) {
+        fprintf(stderr, "rn_infer: %s: --dilate runs on one device (the shards stay undilated)\n",
+                rn_status_string(RN_ERR_UNSUPPORTED));
+        return 1;
+    }
     if (ndev > 0) return run_sharded(devices, ndev, arch, weights, input, u8, B, mode, dtype);
     CHECK(ctx, rn_ctx_create(&ctx, device, NULL));
     CHECK(ctx, groups_g ? rn_model_create_ex(ctx, &model, arch, groups_g, wpg_g) : rn_model_create(ctx, &model, arch));
@@ -215,6 +227,14 @@ int main(int argc, char **argv)
         fprintf(stderr, "rn_infer: %s: --size %llu,%llu: each side must be 32..2048\n", rn_status_string(RN_ERR_INVALID),
                 (unsigned long long)size_h, (unsigned long long)size_w);
         return 1;
+    }
+    if (dilate[0] || dilate[1] || dilate[2]) {
+        const int st = rn_model_set_dilation(model, dilate[0], dilate[1], dilate[2]);
+        if (st != RN_OK) {
+            fprintf(stderr, "rn_infer: %s: --dilate %d,%d,%d: three flags 0 or 1, on a bottleneck network (%s)\n",
+                    rn_status_string(st), dilate[0], dilate[1], dilate[2], rn_last_error(ctx));
+            return 1;
+        }
     }
     CHECK(ctx, rn_model_load_dir(model, weights));
     if (dtype != RN_DTYPE_F32) CHECK(ctx, rn_model_set_dtype(model, dtype));

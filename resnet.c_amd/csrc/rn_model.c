@@ -53,6 +53,7 @@ typedef struct {
 typedef struct {
     char name[RN_MAX_KEY];
     uint64_t cin, cout, k, stride, pad;
+    uint64_t dil;                  /* dilation: 1 but for conv2 of a dilated stage (rn_model_set_dilation) */
     uint64_t groups;               /* > 1: a grouped convolution (ResNeXt's conv2), weight [cout][cin/groups][k][k] */
     int w, bn_w, bn_b, bn_m, bn_v; /* indices into params */
     void *packed;                  /* K-major panel, model dtype */
@@ -122,6 +123,7 @@ struct rn_model {
     int classes_locked; /* a tensor was set, a directory loaded or the model finalized: the count stays */
     float *own_logits;  /* [own_logits_cap, classes]: where rn_model_forward_outputs keeps logits nobody asked for */
     uint64_t own_logits_cap;
+    int dilate[3];                 /* torchvision's replace_stride_with_dilation: layer2, layer3, layer4 */
     uint64_t H, W;                 /* the input image: 224 x 224 unless rn_model_set_input_size said otherwise */
     uint64_t stem_h, stem_w;       /* the stem's output (112 x 112 at 224) */
     uint64_t pool_h, pool_w;       /* the max-pool's (56 x 56), which the first stage keeps */
@@ -206,6 +208,7 @@ static int add_conv_grouped(rn_model *m, const char *name, const char *bn_name, 
     c->k = k;
     c->stride = stride;
     c->pad = pad;
+    c->dil = 1;
     c->groups = groups;
     snprintf(key, sizeof(key), "%s.weight", name);
     c->w = add_param(m, key, cout * (cin / groups) * k * k);
@@ -232,9 +235,47 @@ static uint64_t mid_width(const rn_model *m, int li)
     return kWidths[li][1] * (uint64_t)m->width_per_group / 64 * (uint64_t)m->groups;
 }
 
+/* a convolution's output side */
+static uint64_t conv_side(const rn_conv *cv, uint64_t x, uint64_t pad)
+{
+    return cv->dil > 1 ? rn_conv_output_size_dilated(x, cv->k, cv->stride, pad, cv->dil)
+                       : rn_conv_output_size(x, cv->k, cv->stride, pad);
+}
+
+/* torchvision's _make_layer with replace_stride_with_dilation, over the blocks of a bottleneck network: a
+ * running dilation starts at 1; a flagged stage doubles it and takes stride 1 instead of 2.  Block 0 of a stage
+ * runs its conv2 at the stage's stride with the dilation (and padding) from BEFORE the stage, its downsample
+ * at the stage's stride; the other blocks run conv2 with the current one.  Weights, panels and folded
+ * constants do not depend on any of it. */
+static void apply_dilation(rn_model *m)
+{
+    uint64_t dilation = 1;
+    int li, bi, at = 0;
+    if (m->basic) return;
+    for (li = 0; li < 4; ++li) {
+        const uint64_t previous = dilation;
+        uint64_t stride = kStrides[li];
+        if (li > 0 && m->dilate[li - 1]) {
+            dilation *= 2;
+            stride = 1;
+        }
+        for (bi = 0; bi < m->depths[li]; ++bi, ++at) {
+            const rn_block *b = &m->blocks[at];
+            rn_conv *c2 = &m->convs[b->conv2];
+            c2->stride = bi == 0 ? stride : 1;
+            c2->dil = c2->pad = bi == 0 ? previous : dilation;
+            if (b->ds >= 0) m->convs[b->ds].stride = stride;
+        }
+    }
+}
+
 /* The spatial sizes and, from them, the arenas per image: x4 the input image, p0 / p1 the block outputs
  * (and the stem output), dsb the downsample branch, t1 / t2 the block-internal tensors (a basic block
- * has one: conv1's output).  Max-pool 3x3 s2 p1 (main.cu:114,192); the first stage has stride 1. */
+ * has one: conv1's output).  Max-pool 3x3 s2 p1 (main.cu:114,192); the first stage has stride 1.
+ * A bottleneck network takes each arena as the maximum over its stages: undilated that is the stem and the
+ * first stage (and layer2.0's conv1), as it always was; a stage that keeps its resolution
+ * (rn_model_set_dilation) carries wider tensors on the same map -- layer4's output of a (0,1,1) model at
+ * 224 x 224 is 28 x 28 x 2048, twice the stem's. */
 #define RN_SUB_BATCH_LIMIT 512
 static void set_geometry(rn_model *m, uint64_t H, uint64_t W)
 {
@@ -249,15 +290,35 @@ static void set_geometry(rn_model *m, uint64_t H, uint64_t W)
     m->pool_h = rn_conv_output_size(m->stem_h, 3, 2, 1);
     m->pool_w = rn_conv_output_size(m->stem_w, 3, 2, 1);
     s1 = m->pool_h * m->pool_w;
-    /* map of the second stage (the 3x3 / 2 / 1 and the 1x1 / 2 / 0 convolutions agree on it) */
-    s2 = rn_conv_output_size(m->pool_h, 1, kStrides[1], 0) * rn_conv_output_size(m->pool_w, 1, kStrides[1], 0);
     stem_img = m->stem_h * m->stem_w * stem->cout;
     m->x4_img = padded * 4;
     m->s1_img = s1 * (m->basic ? kBasicWidths[0] : kWidths[0][2]);
     m->p_img = stem_img > m->s1_img ? stem_img : m->s1_img;
-    m->ds_img = m->basic ? s2 * kBasicWidths[1] : m->s1_img; /* layer2.0's, or layer1.0's of a bottleneck */
-    m->t1_img = s1 * (m->basic ? kBasicWidths[0] : mid_width(m, 1)); /* layer2.0 conv1 of a bottleneck */
-    m->t2_img = m->basic ? 0 : m->t1_img;
+    if (m->basic) {
+        /* map of the second stage (the 3x3 / 2 / 1 and the 1x1 / 2 / 0 convolutions agree on it) */
+        s2 = rn_conv_output_size(m->pool_h, 1, kStrides[1], 0) * rn_conv_output_size(m->pool_w, 1, kStrides[1], 0);
+        m->ds_img = s2 * kBasicWidths[1]; /* layer2.0's */
+        m->t1_img = s1 * kBasicWidths[0];
+        m->t2_img = 0;
+    } else {
+        uint64_t h = m->pool_h, w = m->pool_w;
+        int li;
+        m->ds_img = m->t1_img = 0;
+        for (li = 0; li < 4; ++li) {
+            const uint64_t stride = li > 0 && m->dilate[li - 1] ? 1 : kStrides[li];
+            /* (the strided 3x3 with padding == dilation and the 1x1 / stride / 0 agree on the stage's map) */
+            const uint64_t ho = rn_conv_output_size(h, 1, stride, 0), wo = rn_conv_output_size(w, 1, stride, 0);
+            const uint64_t in = h * w * mid_width(m, li);        /* block 0's conv1 sees the stage's input map */
+            const uint64_t out = ho * wo * kWidths[li][2];       /* block outputs, and block 0's downsample branch */
+            if (out > m->p_img) m->p_img = out;
+            if (out > m->ds_img) m->ds_img = out;
+            if (in > m->t1_img) m->t1_img = in;
+            if (ho * wo * mid_width(m, li) > m->t1_img) m->t1_img = ho * wo * mid_width(m, li);
+            h = ho;
+            w = wo;
+        }
+        m->t2_img = m->t1_img;
+    }
     /* The contraction kernels address a tensor with 32-bit byte offsets and refuse one of 2^29 elements or
      * more: a launch batch is the largest power of two, at most 512, whose largest arena tensor stays below
      * that (512 at 224 x 224; 0 = not even one image of this size fits). */
@@ -437,6 +498,58 @@ int rn_model_set_input_size(rn_model *m, uint64_t H, uint64_t W)
     }
     m->tuned_B = 0;
     return RN_OK;
+}
+
+/* torchvision's replace_stride_with_dilation: like the input size a property of the model that the weights do
+ * not depend on; the arenas, the tuned tiles and the sub-batch do. */
+int rn_model_set_dilation(rn_model *m, int layer2, int layer3, int layer4)
+{
+    rn_model probe;
+    int c;
+    if (!m || (layer2 | layer3 | layer4) < 0 || layer2 > 1 || layer3 > 1 || layer4 > 1) return RN_ERR_INVALID;
+    if (m->basic)
+        return rn_ctx_set_error(m->ctx, RN_ERR_UNSUPPORTED,
+                                "rn_model_set_dilation: replace_stride_with_dilation is defined for bottleneck "
+                                "networks only (torchvision's BasicBlock raises NotImplementedError)");
+    /* a captured graph points into the arenas; a pipeline's device buffers are sized by the model */
+    if (m->graphs_live > 0 || m->share->pipelines > 0) return RN_ERR_INVALID;
+    if (layer2 == m->dilate[0] && layer3 == m->dilate[1] && layer4 == m->dilate[2]) return RN_OK;
+    probe = *m; /* the geometry under the new flags, before anything changes */
+    probe.dilate[0] = layer2; probe.dilate[1] = layer3; probe.dilate[2] = layer4;
+    set_geometry(&probe, m->H, m->W);
+    if (probe.max_sub < 1) return RN_ERR_INVALID;
+    if (m->batch_cap > 0) { /* forwards still queued read the arenas */
+        rn_sync(m->ctx);
+        for (c = 0; c < RN_MAX_STREAMS - 1; ++c)
+            if (m->ctxn[c]) rn_sync(m->ctxn[c]);
+        free_acts(m);
+    }
+    m->dilate[0] = layer2; m->dilate[1] = layer3; m->dilate[2] = layer4;
+    apply_dilation(m);
+    set_geometry(m, m->H, m->W);
+    for (c = 0; c < m->n_convs; ++c) {
+        m->convs[c].tile[0] = m->convs[c].tile[1] = 0;
+        m->convs[c].tile_B[0] = m->convs[c].tile_B[1] = 0;
+    }
+    for (c = 0; c < m->n_blocks; ++c) {
+        m->blocks[c].pair_tile[0] = m->blocks[c].pair_tile[1] = 0;
+        m->blocks[c].pair_tile_B[0] = m->blocks[c].pair_tile_B[1] = 0;
+    }
+    m->tuned_B = 0;
+    return RN_OK;
+}
+
+int rn_model_dilation(const rn_model *m, int out[3])
+{
+    if (!m || !out) return RN_ERR_INVALID;
+    out[0] = m->dilate[0]; out[1] = m->dilate[1]; out[2] = m->dilate[2];
+    return RN_OK;
+}
+
+/* input pixels per pixel of the final map: 32, or 16 / 8 / 4 with one / two / three dilated stages */
+int rn_model_output_stride(const rn_model *m)
+{
+    return m ? 32 >> (m->dilate[0] + m->dilate[1] + m->dilate[2]) : 0;
 }
 
 int rn_model_input_size(const rn_model *m, uint64_t *H, uint64_t *W)
@@ -918,8 +1031,7 @@ static int launch_call(const rn_model *m, rn_ctx *ctx, const rn_conv_call *k)
 {
     const rn_conv *cv = &m->convs[k->conv];
     const rn_epilogue *ep = k->has_ep ? &k->ep : NULL;
-    const uint64_t ho = rn_conv_output_size(k->H, cv->k, cv->stride, k->pad);
-    const uint64_t wo = rn_conv_output_size(k->W, cv->k, cv->stride, k->pad);
+    const uint64_t ho = conv_side(cv, k->H, k->pad), wo = conv_side(cv, k->W, k->pad);
     if (k->pair_block >= 0) {
         const rn_block *pb = &m->blocks[k->pair_block];
         const rn_conv *cd = &m->convs[pb->ds];
@@ -933,6 +1045,10 @@ static int launch_call(const rn_model *m, rn_ctx *ctx, const rn_conv_call *k)
     if (k->exact)
         return rn_conv2d_nhwc_exact_forward(ctx, (const float *)k->x, (float *)k->y, m->stem_packed_exact, cv->k,
                                             cv->stride, ho, wo, k->B, cv->cin, cv->cout, k->H, k->W, ep);
+    if (cv->dil > 1) /* conv2 of a dilated stage, dense or grouped: the same panel, the taps dil apart */
+        return rn_conv2d_dilated_nhwc_forward_dt(ctx, m->dtype, m->dtype, k->x, k->y, cv->packed, cv->k, cv->stride,
+                                                 k->pad, cv->dil, ho, wo, k->B, cv->cin, cv->cout, k->H, k->W,
+                                                 cv->groups, ep);
     if (cv->groups > 1) /* one kernel, no tile candidates: every candidate times the same launch */
         return rn_conv2d_grouped_nhwc_forward_dt(ctx, m->dtype, m->dtype, k->x, k->y, cv->packed, cv->k, cv->stride,
                                                  k->pad, ho, wo, k->B, cv->cin, cv->cout, k->H, k->W, cv->groups, ep);
@@ -964,8 +1080,7 @@ static int op_call(rn_model *m, const rn_conv_call *k, const char *op, const cha
 static int op_conv_at(rn_model *m, const rn_conv *cv, const void *x, void *y, uint64_t B, uint64_t H,
                       uint64_t W, const rn_epilogue *ep, uint64_t pad, int exact)
 {
-    const uint64_t ho = rn_conv_output_size(H, cv->k, cv->stride, pad);
-    const uint64_t wo = rn_conv_output_size(W, cv->k, cv->stride, pad);
+    const uint64_t ho = conv_side(cv, H, pad), wo = conv_side(cv, W, pad);
     /* a grouped convolution counts its algorithmic products: K = k*k*cin/groups per output */
     const double M = (double)(B * ho * wo), K = (double)(cv->cin / cv->groups * cv->k * cv->k);
     const double es = (double)elem_size(m);
@@ -1120,8 +1235,7 @@ static int block_forward(rn_model *m, rn_block *b, const float *x, float *y, uin
     const rn_conv *cd = b->ds >= 0 ? &m->convs[b->ds] : NULL;
     const rn_conv *cs = c2 ? c2 : c1;                          /* where the stride sits */
     const uint64_t h = *H, w = *W;
-    const uint64_t ho = rn_conv_output_size(h, cs->k, cs->stride, cs->pad);
-    const uint64_t wo = rn_conv_output_size(w, cs->k, cs->stride, cs->pad);
+    const uint64_t ho = conv_side(cs, h, cs->pad), wo = conv_side(cs, w, cs->pad);
     const uint64_t h1 = c2 ? h : ho, w1 = c2 ? w : wo;         /* conv1's output */
     float *mid = c2 ? m->run.t2 : m->run.t1;                   /* the tail's input */
     const float *shortcut = x;
@@ -1716,7 +1830,19 @@ static uint64_t tuning_size(const rn_model *m)
     return m->H == RN_DEFAULT_SIDE && m->W == RN_DEFAULT_SIDE ? 0 : m->H << 32 | m->W;
 }
 
-static uint64_t tuning_header(const rn_model *m) { return RN_TUNING_HEADER + (tuning_size(m) ? 1 : 0); }
+/* the header word behind those, present only when not 0: 0 for undilated models, whose tables keep their format.
+ * The tag in its top byte is one no size word has (sides are at most 2048), so a table of a sized model and one of
+ * a dilated model of the same length still differ. */
+static uint64_t tuning_dilation(const rn_model *m)
+{
+    const uint64_t flags = (uint64_t)(m->dilate[0] | m->dilate[1] << 1 | m->dilate[2] << 2);
+    return flags ? 0xD1ull << 56 | flags : 0;
+}
+
+static uint64_t tuning_header(const rn_model *m)
+{
+    return RN_TUNING_HEADER + (tuning_size(m) ? 1 : 0) + (tuning_dilation(m) ? 1 : 0);
+}
 
 static uint64_t tuning_settings(const rn_model *m)
 {
@@ -1744,6 +1870,7 @@ int rn_model_export_tuning(const rn_model *m, uint64_t *words, uint64_t cap, uin
     words[at++] = (uint64_t)rn_conv_tile_candidates();
     words[at++] = tuning_family(m);
     if (tuning_size(m)) words[at++] = tuning_size(m);
+    if (tuning_dilation(m)) words[at++] = tuning_dilation(m);
     for (c = 0; c < m->n_convs; ++c)
         for (k = 0; k < 2; ++k) {
             words[at++] = (uint64_t)m->convs[c].tile[k];
@@ -1767,8 +1894,9 @@ int rn_model_import_tuning(rn_model *m, const uint64_t *words, uint64_t n_words)
         words[3] != tuning_settings(m) || words[6] != (uint64_t)m->n_convs || words[7] != (uint64_t)m->n_blocks ||
         words[8] != (uint64_t)rn_conv_tile_candidates() || words[9] != tuning_family(m) ||
         (tuning_size(m) && words[RN_TUNING_HEADER] != tuning_size(m)) ||
+        (tuning_dilation(m) && words[at - 1] != tuning_dilation(m)) ||
         n_words != at + 4 * ((uint64_t)m->n_convs + (uint64_t)m->n_blocks))
-        return RN_ERR_INVALID; /* measured for another model, size, setting or build */
+        return RN_ERR_INVALID; /* measured for another model, size, dilation, setting or build */
     for (c = 0; c < m->n_convs + m->n_blocks; ++c) /* a candidate this build does not have */
         if (words[at + 4 * (uint64_t)c] > (uint64_t)rn_conv_tile_candidates() ||
             words[at + 4 * (uint64_t)c + 2] > (uint64_t)rn_conv_tile_candidates())

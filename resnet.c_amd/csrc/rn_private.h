@@ -30,6 +30,23 @@ int rn_linear_direct_forward(rn_ctx *ctx, const float *inp, float *out, const fl
 /* n bf16 values as fp32 (exact): the pooled features of a bf16 model */
 int rn_widen_bf16_forward(rn_ctx *ctx, const void *src_bf16, float *dst, uint64_t n);
 
+/* ---- dilated convolution: the public entry points (rn_conv.hip) have checked the dilation and the output size ---- */
+/* rn_conv2d_nhwc_forward_dt with a dilation (rn_conv.hip): the dense contraction, also of a bf16 grouped panel */
+int rn_conv_dense_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const void *inp, void *out,
+                                  const void *packed_weight, uint64_t kernel_size, uint64_t stride, uint64_t padding,
+                                  uint64_t dilation, uint64_t h_out, uint64_t w_out, uint64_t B, uint64_t in_channels,
+                                  uint64_t out_channels, uint64_t H, uint64_t W, const rn_epilogue *epilogue);
+/* rn_conv2d_grouped_forward / rn_conv2d_grouped_nhwc_forward_dt with a dilation (rn_conv_group.hip) */
+int rn_conv_group_forward(rn_ctx *ctx, const float *inp, float *out, const float *weight, uint64_t kernel_size,
+                          uint64_t stride, uint64_t padding, uint64_t dilation, uint64_t h_out, uint64_t w_out,
+                          uint64_t B, uint64_t in_channels, uint64_t out_channels, uint64_t H, uint64_t W,
+                          uint64_t groups);
+int rn_conv_group_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const void *inp, void *out,
+                                  const void *packed_weight, uint64_t kernel_size, uint64_t stride, uint64_t padding,
+                                  uint64_t dilation, uint64_t h_out, uint64_t w_out, uint64_t B, uint64_t in_channels,
+                                  uint64_t out_channels, uint64_t H, uint64_t W, uint64_t groups,
+                                  const rn_epilogue *epilogue);
+
 /* ---- rn_stem.hip ---- */
 /* 1 when the fused stem + max-pool launch takes a padded image of Hp x Wp (nchw: the NCHW-fetching form on
  * an image of Hp - 6 x Wp - 6) of `dtype`: its documented conditions on the geometry alone */

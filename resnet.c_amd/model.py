@@ -211,10 +211,12 @@ class NativeModel:
     def __init__(self, arch: str = "resnet50", state: Optional[Dict[str, np.ndarray]] = None,
                  weights_dir: Optional[str] = None, ctx: Optional[Context] = None,
                  dtype: str = "f32", classes: Optional[int] = None,
-                 input_size: Optional[Tuple[int, int]] = None):
+                 input_size: Optional[Tuple[int, int]] = None,
+                 replace_stride_with_dilation: Optional[Tuple[bool, bool, bool]] = None):
         """classes: rows of the classifier; None = state["fc.weight"].shape[0] when a state is given,
         otherwise the library's 1000.  input_size: (H, W) of the images every forward reads, 32..2048 each;
-        None = the library's 224 x 224 (set_input_size changes it later: the weights do not depend on it)."""
+        None = the library's 224 x 224 (set_input_size changes it later: the weights do not depend on it).
+        replace_stride_with_dilation: torchvision's three flags (layer2, layer3, layer4), see set_dilation."""
         self.ctx = ctx or get_ctx()
         self.arch = arch
         lib = L.lib()
@@ -247,6 +249,28 @@ class NativeModel:
         L.check(lib.rn_model_finalize(h), "rn_model_finalize", self.ctx.handle)
         if input_size is not None:
             self.set_input_size(*input_size)
+        if replace_stride_with_dilation is not None:
+            self.set_dilation(*replace_stride_with_dilation)
+
+    def set_dilation(self, layer2, layer3, layer4) -> None:
+        """torchvision's replace_stride_with_dilation from the next forward on (rn_model_set_dilation): a
+        flagged stage keeps its resolution and dilates its 3x3 convolutions.  Bottleneck networks only
+        (RnError with RN_ERR_UNSUPPORTED on resnet18/34); refused, nothing changed, while a Graph or a Pipeline
+        of this model lives.  Frees the activation arenas and drops the tuned tiles."""
+        L.check(L.lib().rn_model_set_dilation(self.handle, int(bool(layer2)), int(bool(layer3)), int(bool(layer4))),
+                "rn_model_set_dilation: bottleneck networks, no live Graph or Pipeline", self.ctx.handle)
+
+    @property
+    def dilation(self) -> Tuple[bool, bool, bool]:
+        """The three flags (layer2, layer3, layer4): (False, False, False) unless set otherwise."""
+        out = (ctypes.c_int * 3)()
+        L.check(L.lib().rn_model_dilation(self.handle, out), "rn_model_dilation")
+        return tuple(bool(v) for v in out)
+
+    @property
+    def output_stride(self) -> int:
+        """Input pixels per pixel of the final map: 32, or 16 / 8 / 4 with dilated stages."""
+        return int(L.lib().rn_model_output_stride(self.handle))
 
     def set_input_size(self, H: int, W: int) -> None:
         """Images of H x W from the next forward on (rn_model_set_input_size): 32..2048 each.  Refused

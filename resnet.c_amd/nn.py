@@ -39,22 +39,28 @@ def _gpu(*tensors: Tensor) -> None:
 
 class Conv2d:
     def __init__(self, weight: FloatTensor, in_channels: int, out_channels: int, kernel_size: int,
-                 stride: int = 1, padding: int = 0, groups: int = 1):
+                 stride: int = 1, padding: int = 0, groups: int = 1, dilation: int = 1):
         self.weight = weight  # [out_channels, in_channels // groups, k, k]
         self.in_channels, self.out_channels = in_channels, out_channels
         self.kernel_size, self.stride, self.padding = kernel_size, stride, padding
         self.groups = groups
+        self.dilation = dilation
 
     @staticmethod
     def loadWeightToCuda(name: str, in_channels: int, out_channels: int, kernel_size: int,
-                         stride: int = 1, padding: int = 0, groups: int = 1) -> "Conv2d":
+                         stride: int = 1, padding: int = 0, groups: int = 1, dilation: int = 1) -> "Conv2d":
         weight = FloatTensor.loadToCuda(WEIGHTS_DIR + name + ".weight").view(
             Shape((out_channels, in_channels // groups, kernel_size, kernel_size)))
-        return Conv2d(weight, in_channels, out_channels, kernel_size, stride, padding, groups)
+        return Conv2d(weight, in_channels, out_channels, kernel_size, stride, padding, groups, dilation)
 
     def getOutShape(self, x_shape: Shape) -> Shape:
         assert len(x_shape) == 4
         assert x_shape[1] == self.in_channels
+        if self.dilation != 1:
+            side = L.lib().rn_conv_output_size_dilated
+            return Shape((x_shape[0], self.out_channels,
+                          int(side(x_shape[2], self.kernel_size, self.stride, self.padding, self.dilation)),
+                          int(side(x_shape[3], self.kernel_size, self.stride, self.padding, self.dilation))))
         return Shape((x_shape[0], self.out_channels,
                       convOutputSize(x_shape[2], self.kernel_size, self.stride, self.padding),
                       convOutputSize(x_shape[3], self.kernel_size, self.stride, self.padding)))
@@ -64,6 +70,11 @@ class Conv2d:
         B, _c, H, W = x.shape().as_tuple(4)
         _b, _oc, h_out, w_out = out.shape().as_tuple(4)
         out.layout = x.layout
+        if self.dilation != 1:
+            _call("rn_conv2d_dilated_forward", x.layout, x.data(), out.data(), self.weight.data(),
+                  self.kernel_size, self.stride, self.padding, self.dilation, h_out, w_out, B, self.in_channels,
+                  self.out_channels, H, W, self.groups)
+            return
         if self.groups != 1:
             _call("rn_conv2d_grouped_forward", x.layout, x.data(), out.data(), self.weight.data(),
                   self.kernel_size, self.stride, self.padding, h_out, w_out, B, self.in_channels,

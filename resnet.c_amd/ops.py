@@ -690,3 +690,98 @@ def conv2d_grouped_nhwc_bf16(x, w, stride=1, pad=0, groups=1, scale=None, shift=
     ctx.sync()
     y = _down_raw(out, np.float32, n_out) if out_f32 else from_bf16_bits(_down_raw(out, np.uint16, n_out))
     return y.reshape(B, ho, wo, Cout).transpose(0, 3, 1, 2).copy()
+
+
+# ---------------------------------------------------------------------------
+# dilated convolution (torch's ``dilation``, one factor for rows and columns)
+# ---------------------------------------------------------------------------
+def conv_output_size_dilated(x: int, k: int, stride: int, pad: int, dilation: int) -> int:
+    return int(L.lib().rn_conv_output_size_dilated(x, k, stride, pad, dilation))
+
+
+def conv2d_dilated(x, w, stride: int = 1, pad: int = 0, dilation: int = 1, groups: int = 1,
+                   layout: str = "nchw") -> np.ndarray:
+    """rn_conv2d_dilated_forward: w is [Cout, Cin / groups, k, k] (torch's layout)."""
+    B, Cin, H, W = x.shape
+    Cout, _, k, _ = w.shape
+    ho, wo = (conv_output_size_dilated(n, k, stride, pad, dilation) for n in (H, W))
+    dx, dw = _up(x, layout), _up(w, "nchw")
+    out = FloatTensor((B, Cout, ho, wo), Device.GPU)
+    _run("rn_conv2d_dilated_forward", layout, dx.data(), out.data(), dw.data(), k, stride, pad, dilation, ho, wo, B,
+         Cin, Cout, H, W, groups)
+    return _down(out, (B, Cout, ho, wo), layout)
+
+
+def _pack_dt(dtype, dw, Cin, Cout, k, groups):
+    """The panel the dilated NHWC entry point reads: the dense one for groups == 1, the grouped one above."""
+    from .tensor import _DeviceBuffer
+    ctx, lib = get_ctx(), L.lib()
+    es = 2 if dtype == L.RN_DTYPE_BF16 else 4
+    if groups == 1:
+        pn = int(lib.rn_conv2d_packed_weight_numel_dt(dtype, Cin, Cout, k))
+        packed = _DeviceBuffer(ctx, max(pn, 8) * es)
+        L.check(lib.rn_conv2d_pack_weight_dt(ctx.handle, dtype, dw.data(), packed.ptr, Cin, Cout, k),
+                "rn_conv2d_pack_weight_dt", ctx.handle)
+    else:
+        pn = int(lib.rn_conv2d_grouped_packed_weight_numel_dt(dtype, Cin, Cout, k, groups))
+        packed = _DeviceBuffer(ctx, max(pn, 8) * es)
+        L.check(lib.rn_conv2d_grouped_pack_weight_dt(ctx.handle, dtype, dw.data(), packed.ptr, Cin, Cout, k, groups),
+                "rn_conv2d_grouped_pack_weight_dt", ctx.handle)
+    return packed
+
+
+def conv2d_dilated_nhwc(x, w, stride=1, pad=0, dilation=1, groups=1, scale=None, shift=None, residual=None,
+                        relu_: bool = False) -> np.ndarray:
+    """rn_conv2d_pack_weight_dt / rn_conv2d_grouped_pack_weight_dt + rn_conv2d_dilated_nhwc_forward_dt in
+    fp32, with an epilogue (NCHW host arrays; a small-Cin image is padded to its 4 channels)."""
+    ctx, lib = get_ctx(), L.lib()
+    B, Cin, H, W = x.shape
+    Cout, _, k, _ = w.shape
+    ho, wo = (conv_output_size_dilated(n, k, stride, pad, dilation) for n in (H, W))
+    cs = int(lib.rn_conv2d_input_channels(Cin)) if groups == 1 else Cin
+    xp = np.zeros((B, H, W, cs), dtype=np.float32)
+    xp[..., :Cin] = np.asarray(x, dtype=np.float32).transpose(0, 2, 3, 1)
+    dx, dw = FloatTensor.from_numpy(xp, Device.GPU), _up(w, "nchw")
+    packed = _pack_dt(L.RN_DTYPE_F32, dw, Cin, Cout, k, groups)
+    keep = [_up(v, "nchw") if v is not None else None for v in (scale, shift)]
+    dres = _up(residual, "nhwc") if residual is not None else None
+    ep = L.Epilogue(keep[0].data() if keep[0] else None, keep[1].data() if keep[1] else None,
+                    dres.data() if dres else None, int(relu_))
+    out = FloatTensor((B, Cout, ho, wo), Device.GPU)
+    L.check(lib.rn_conv2d_dilated_nhwc_forward_dt(ctx.handle, L.RN_DTYPE_F32, L.RN_DTYPE_F32, dx.data(), out.data(),
+                                                  packed.ptr, k, stride, pad, dilation, ho, wo, B, Cin, Cout, H, W,
+                                                  groups, ctypes.byref(ep)),
+            "rn_conv2d_dilated_nhwc_forward_dt", ctx.handle)
+    ctx.sync()
+    return _down(out, (B, Cout, ho, wo), "nhwc")
+
+
+def conv2d_dilated_nhwc_bf16(x, w, stride=1, pad=0, dilation=1, groups=1, scale=None, shift=None, residual=None,
+                             relu_: bool = False, out_f32: bool = False) -> np.ndarray:
+    """The bf16 form of conv2d_dilated_nhwc (in_channels % 64 == 0).  NCHW fp32 host arrays in (rounded
+    to bf16 on upload), NCHW fp32 host array out."""
+    from .tensor import _DeviceBuffer
+    ctx, lib = get_ctx(), L.lib()
+    B, Cin, H, W = x.shape
+    Cout, _, k, _ = w.shape
+    ho, wo = (conv_output_size_dilated(n, k, stride, pad, dilation) for n in (H, W))
+    dx = _up_raw(to_bf16_bits(np.asarray(x, dtype=np.float32).transpose(0, 2, 3, 1)))
+    dw = _up(w, "nchw")
+    packed = _pack_dt(L.RN_DTYPE_BF16, dw, Cin, Cout, k, groups)
+    keep = [_up(v, "nchw") if v is not None else None for v in (scale, shift)]
+    dres = None
+    if residual is not None:
+        r = np.asarray(residual, dtype=np.float32).transpose(0, 2, 3, 1)
+        dres = _up_raw(r if out_f32 else to_bf16_bits(r))
+    ep = L.Epilogue(keep[0].data() if keep[0] else None, keep[1].data() if keep[1] else None,
+                    dres.ptr if dres else None, int(relu_))
+    n_out = B * Cout * ho * wo
+    out = _DeviceBuffer(ctx, max(n_out, 8) * (4 if out_f32 else 2))
+    L.check(lib.rn_conv2d_dilated_nhwc_forward_dt(ctx.handle, L.RN_DTYPE_BF16,
+                                                  L.RN_DTYPE_F32 if out_f32 else L.RN_DTYPE_BF16, dx.ptr, out.ptr,
+                                                  packed.ptr, k, stride, pad, dilation, ho, wo, B, Cin, Cout, H, W,
+                                                  groups, ctypes.byref(ep)),
+            "rn_conv2d_dilated_nhwc_forward_dt", ctx.handle)
+    ctx.sync()
+    y = _down_raw(out, np.float32, n_out) if out_f32 else from_bf16_bits(_down_raw(out, np.uint16, n_out))
+    return y.reshape(B, ho, wo, Cout).transpose(0, 3, 1, 2).copy()

@@ -98,10 +98,20 @@ def feature_width(arch: str) -> int:
     return BASIC_WIDTHS[-1] if block_kind(arch) == "basic" else STAGE_WIDTHS[-1][2]
 
 
-def conv_specs(arch: str) -> List[Tuple[str, int, int, int, int, int]]:
+def conv_specs(arch: str, replace_stride_with_dilation=(False, False, False)) -> List[Tuple[str, int, int, int, int, int]]:
     """(name, cin, cout, k, stride, pad) for every convolution, in forward order (conv_groups() gives
-    the groups of a ResNeXt's conv2: its weight is [cout, cin // groups, k, k])."""
+    the groups of a ResNeXt's conv2: its weight is [cout, cin // groups, k, k]).  With
+    replace_stride_with_dilation (bottleneck networks) the strides are the dilated network's and a conv2's
+    pad is its dilation (iter_blocks_dilated yields it by name)."""
     out = [("conv1", 3, 64, 7, 2, 3)]
+    if any(replace_stride_with_dilation):
+        for pre, b_in, mid, cout, b_stride, has_ds, dil in iter_blocks_dilated(arch, replace_stride_with_dilation):
+            if has_ds:
+                out.append((f"{pre}.downsample.0", b_in, cout, 1, b_stride, 0))
+            out.append((f"{pre}.conv1", b_in, mid, 1, 1, 0))
+            out.append((f"{pre}.conv2", mid, mid, 3, b_stride, dil))
+            out.append((f"{pre}.conv3", mid, cout, 1, 1, 0))
+        return out
     if block_kind(arch) == "basic":
         for pre, cin, cout, stride, has_ds in iter_basic_blocks(arch):
             if has_ds:
@@ -284,16 +294,39 @@ def load_weights_bin(arch: str, dir_name: str) -> Dict[str, np.ndarray]:
     return state
 
 
-def iter_blocks(arch: str) -> Iterator[Tuple[str, int, int, int, int, bool]]:
+def iter_blocks(arch: str, replace_stride_with_dilation=(False, False, False)
+                ) -> Iterator[Tuple[str, int, int, int, int, bool]]:
     """(prefix, cin, mid, cout, stride, has_downsample) per bottleneck block."""
+    for blk in iter_blocks_dilated(arch, replace_stride_with_dilation):
+        yield blk[:6]
+
+
+def iter_blocks_dilated(arch: str, replace_stride_with_dilation=(False, False, False)
+                        ) -> Iterator[Tuple[str, int, int, int, int, bool, int]]:
+    """(prefix, cin, mid, cout, stride, has_downsample, dilation) per bottleneck block: torchvision's
+    _make_layer.  A running dilation starts at 1; a flagged stage (layer2, layer3, layer4) doubles it and
+    takes stride 1.  Block 0 of a stage runs conv2 at the stage's stride with the dilation from before the
+    stage (and keeps its downsample: the widths differ), blocks 1.. with the current one; conv2's padding
+    is its dilation."""
+    flags = tuple(bool(f) for f in replace_stride_with_dilation)
+    if len(flags) != 3:
+        raise ValueError("replace_stride_with_dilation takes three flags: layer2, layer3, layer4")
+    if any(flags) and block_kind(arch) == "basic":
+        raise NotImplementedError("replace_stride_with_dilation is defined for bottleneck networks only")
+    dilation = 1
     for li, ((cin, mid, cout), stride, n) in enumerate(
         zip(stage_widths(arch), STAGE_STRIDES, depths_of(arch)), start=1
     ):
+        previous = dilation
+        if li > 1 and flags[li - 2]:
+            dilation *= 2
+            stride = 1
         for bi in range(n):
             b_in = cin if bi == 0 else cout
             b_stride = stride if bi == 0 else 1
+            # (torchvision: stride != 1 or inplanes != planes * expansion -- with the stage's stride)
             yield (f"layer{li}.{bi}", b_in, mid, cout, b_stride,
-                   bi == 0 and (b_stride != 1 or b_in != cout))
+                   bi == 0 and (b_stride != 1 or b_in != cout), previous if bi == 0 else dilation)
 
 
 def iter_basic_blocks(arch: str) -> Iterator[Tuple[str, int, int, int, bool]]:
@@ -311,18 +344,20 @@ def iter_basic_blocks(arch: str) -> Iterator[Tuple[str, int, int, int, bool]]:
         prev = cout
 
 
-def forward_flops(arch: str, hw=224) -> int:
+def forward_flops(arch: str, hw=224, replace_stride_with_dilation=(False, False, False)) -> int:
     """Algorithmic FLOPs of one image: 2 x MACs of every convolution (output sizes tracked through
     the network) and of fc.  8,178,368,512 for resnet50, 3,628,146,688 for resnet18 at 224 x 224.
-    hw: one side (a square image) or (H, W)."""
-    def out(n, k, s, p):
-        return (n + 2 * p - k) // s + 1
+    hw: one side (a square image) or (H, W).  replace_stride_with_dilation: the dilated network's (a
+    dilated stage keeps its map, so everything behind it costs four times as much)."""
+    dil = {}
+    if any(replace_stride_with_dilation):
+        dil = {f"{blk[0]}.conv2": blk[6] for blk in iter_blocks_dilated(arch, replace_stride_with_dilation)}
 
-    def out2(n, k, s, p):
-        return out(n[0], k, s, p), out(n[1], k, s, p)
+    def out2(n, k, s, p, d=1):
+        return tuple((x + 2 * p - d * (k - 1) - 1) // s + 1 for x in n)
     size = _hw_pair(hw)
     total, block_in, last = 0, {}, size
-    for name, cin, cout, k, s, p in conv_specs(arch):
+    for name, cin, cout, k, s, p in conv_specs(arch, replace_stride_with_dilation):
         if name == "conv1":
             n_in = size
         else:
@@ -331,7 +366,7 @@ def forward_flops(arch: str, hw=224) -> int:
                 block_in[pre] = last if len(block_in) else out2(last, 3, 2, 1)  # max-pool after the stem
             first = name.endswith(("downsample.0", ".conv1"))
             n_in = block_in[pre] if first else last
-        n_out = out2(n_in, k, s, p)
+        n_out = out2(n_in, k, s, p, dil.get(name, 1))
         total += 2 * n_out[0] * n_out[1] * cout * (cin // conv_groups(arch, name)) * k * k
         last = n_out
     return total + 2 * feature_width(arch) * NUM_CLASSES
