@@ -68,6 +68,10 @@ namespace {
 
 constexpr int ROW_FLOATS = 32;  // LDS row = 128 bytes, addressed as 32 dwords
 
+// Blocks of a BM x BN tile that share a CU: what the kernel is compiled for (__launch_bounds__) and what the XCD
+// tile order counts as resident (choose_tile_order)
+constexpr int tile_blocks_per_cu(int BM, int BN) { return BM * BN <= 64 * 64 ? 4 : BM * BN <= 64 * 128 ? 3 : 2; }
+
 // Diagnostic time stamps (100 MHz wall clock) of a block's phases; off unless a debug
 // buffer was attached to the context.  Nothing else reads that buffer.
 __device__ __forceinline__ void stamp(unsigned long long *buf, int slot)
@@ -140,7 +144,7 @@ struct OutVec<bf16_t> {
 //      row setup of the undilated launches (block life outside the K loop) is what it was
 template <typename T, typename TO, int BM, int BN, bool DUAL = false, bool XK = false, bool CHUNK = false,
           bool DIL = false>
-__global__ __launch_bounds__(256, (BM * BN <= 64 * 64 ? 4 : BM * BN <= 64 * 128 ? 3 : 2)) void conv_gemm_kernel(const GemmParams p)
+__global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_kernel(const GemmParams p)
 {
     constexpr int CH = Elem<T>::CH, ES = (int)sizeof(T);
     constexpr int AP = BM / 32;  // A rows staged per thread
@@ -835,67 +839,266 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const FinishParams p
 
 bool fits_i32(uint64_t v) { return v < (1ull << 31); }
 
-void fast_div(unsigned d, unsigned *mul, unsigned *shr) { rn_fast_div(d, mul, shr); }
-
-// Blocks of one instantiation that fit a CU at once (registers and LDS) on the context's device,
-// asked once per context and instantiation: the answer lives in the context, not in the process.
-template <typename T, typename TO, int BM, int BN, bool DUAL, bool XK, bool CHUNK, bool DIL>
-int resident_blocks_per_cu(rn_ctx *ctx)
+// scale / shift / residual / ReLU of an epilogue (or of none) into a kernel parameter struct of this file
+template <typename P>
+void set_epilogue(P &p, const rn_epilogue *ep)
 {
-    constexpr int tile = (BM == 128 ? 0 : 2) + (BN == 128 ? 0 : 1);
-    constexpr int types = sizeof(T) == 4 ? 0 : sizeof(TO) == 4 ? 1 : 2;
-    constexpr int id = tile + 4 * ((DUAL ? 1 : 0) + 2 * (XK ? 1 : 0) + 4 * (CHUNK ? 1 : 0)) + 32 * types + (DIL ? 128 : 0);
-    static_assert(id < (int)(sizeof(ctx->occupancy) / sizeof(ctx->occupancy[0])), "occupancy table");
-    if (ctx->occupancy[id] == 0) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_gemm_kernel<T, TO, BM, BN, DUAL, XK, CHUNK, DIL>,
-                                                         256, 0) != hipSuccess ||
-            nb < 1)
-            nb = 1;
-        ctx->occupancy[id] = nb;
-    }
-    return ctx->occupancy[id];
+    p.scale = ep ? ep->scale : nullptr;
+    p.shift = ep ? ep->shift : nullptr;
+    p.residual = ep ? static_cast<decltype(p.residual)>(ep->residual) : nullptr;
+    p.relu = ep ? ep->relu : 0;
 }
 
-template <typename T, typename TO, int BM, int BN, bool DUAL, bool XK, bool CHUNK = false, bool DIL = false>
-void launch_one(rn_ctx *ctx, GemmParams &p, bool persistent)
+// One contraction on NHWC data with packed weights, as an entry point describes it to launch_gemm.
+struct Contraction {
+    int dt_in, dt_out;  // element type of activations and weights; of the output and the residual
+    const void *inp;
+    void *out;
+    const void *packed;
+    uint64_t k, stride, pad, dil, h_out, w_out, B, Cin, Cout, H, W;
+    const rn_epilogue *ep;         // or null
+    const rn_conv_second *second;  // fused pair: the second source, or null
+    bool exact;                    // exact-K small-Cin form over a physically padded image
+    bool out_nchw;                 // the output tensor is NCHW (describe() says when the kernel writes it so)
+    const char *what;              // the entry point, for error texts
+};
+
+// ---- describe: the kernel's view of the contraction; the work-division fields are left to split_* ----
+GemmParams describe(const rn_ctx *ctx, const Contraction &d)
 {
-    if constexpr (!DIL && !XK) {  // every form but the exact-K one has a dilated twin
-        if (p.dil != 1) return launch_one<T, TO, BM, BN, DUAL, XK, CHUNK, true>(ctx, p, persistent);
+    const int es = d.dt_in == RN_DTYPE_BF16 ? 2 : 4;
+    const int bke = 128 / es;
+    const uint64_t k = d.k, Cin = d.Cin;
+    GemmParams p{};  // whatever a form does not use is zero: second source, exact-K fields, tile order, scratch
+    // NCHW output: fp32, no residual (it would be NHWC); a 1x1 output image is the same in both
+    p.out_nchw = d.out_nchw && d.dt_out == RN_DTYPE_F32 && !(d.ep && d.ep->residual) && d.h_out * d.w_out > 1;
+    p.in = d.inp, p.w = d.packed, p.out = d.out;
+    set_epilogue(p, d.ep);
+    const bool c4 = !d.exact && rn_conv_is_c4(Cin, k);
+    p.H = (int)d.H, p.W = (int)d.W, p.Cs = c4 ? 4 : (int)Cin;
+    p.Ho = (int)d.h_out, p.Wo = (int)d.w_out, p.Cout = (int)d.Cout;
+    const bool c4pair = c4 && d.dt_in == RN_DTYPE_BF16;  // two kernel rows per K tile
+    p.tap_rows = c4pair ? 2 : 1, p.k_rows = (int)k;
+    p.KH = c4pair ? (int)rn_ceil_div(k, 2) : (int)k;
+    p.KW = c4 ? 1 : (int)k;
+    p.stride = (int)d.stride, p.pad = (int)d.pad;
+    p.dil = (int)d.dil;  // (the small-Cin and exact-K forms are never dilated: their callers pass 1)
+    p.cseg = c4 ? 1 : (int)(Cin / bke);
+    p.chunk_dw = c4 ? 16 / (4 * es) : 0;  // pixels of a 4-channel image per 16-byte chunk
+    p.c4_chunks = c4 ? (int)rn_ceil_div(k, p.chunk_dw) : 0;  // <= 4 in the two-row form (k <= 8)
+    p.M = (int)(d.B * d.h_out * d.w_out);
+    p.nk = p.KH * p.KW * p.cseg;
+    p.nk1 = p.nk;
+    if (const rn_conv_second *s = d.second) {
+        p.in2 = s->inp;
+        p.H2 = (int)s->H, p.W2 = (int)s->W, p.Cs2 = (int)s->in_channels, p.stride2 = (int)s->stride;
+        p.in2_bytes = (int)(d.B * s->H * s->W * s->in_channels * es);
+        p.nk += (int)(s->in_channels / bke);
     }
-    unsigned grid = p.grid_items;
-    if (persistent) {
-        const unsigned slots = 256u * (unsigned)resident_blocks_per_cu<T, TO, BM, BN, DUAL, XK, CHUNK, DIL>(ctx);
-        if (grid > slots) grid = slots;
+    p.Ktot = p.nk * bke;
+    if (d.exact) {
+        p.kreal = (int)(k * k * Cin), p.kc = (int)(k * Cin), p.kskip = (int)((d.W - k) * Cin);
+        p.nk = p.nk1 = (int)rn_ceil_div((uint64_t)p.kreal, 32);
+        p.Ktot = p.nk * 32, p.cseg = 1;
+        rn_fast_div((unsigned)p.kc, &p.mul_kc, &p.shr_kc);
     }
-    conv_gemm_kernel<T, TO, BM, BN, DUAL, XK, CHUNK, DIL><<<dim3(grid), dim3(256), 0, ctx->stream>>>(p);
+    p.HoWo = p.Ho * p.Wo;
+    rn_fast_div((unsigned)p.HoWo, &p.mul_hw, &p.shr_hw);
+    rn_fast_div((unsigned)p.Wo, &p.mul_w, &p.shr_w);
+    rn_fast_div((unsigned)p.cseg, &p.mul_cs, &p.shr_cs);
+    rn_fast_div((unsigned)p.KW, &p.mul_kw, &p.shr_kw);
+    p.stamps = (unsigned long long *)ctx->debug_stamps;
+    p.in_bytes = (int)(d.B * d.H * d.W * (uint64_t)p.Cs * es);
+    p.w_bytes = (int)(d.Cout * (uint64_t)p.Ktot * es);
+    p.out_bytes = (int)(d.B * d.h_out * d.w_out * d.Cout * (uint64_t)(d.dt_out == RN_DTYPE_BF16 ? 2 : 4));
+    return p;
 }
 
-template <typename T, typename TO, bool DUAL = false, bool XK = false>
-void launch_tiles(rn_ctx *ctx, GemmParams &p, int BMsel, int BNsel, bool persistent)
+// ---- choose: which kernel family runs, and on which tile ----
+struct Choice {
+    enum Family { STRIP, WIDE, FOUR_WAVE } family;
+    int which;        // WIDE: the tile of rn_conv_wide.hip
+    int BM, BN;       // WIDE and FOUR_WAVE: the block tile
+    bool persistent;  // FOUR_WAVE: a resident grid walks the tiles (else one block per tile)
+    bool chunked;     // FOUR_WAVE: chunked K sum
+};
+
+// the four-wave tile of conv_gemm_kernel
+Choice choose_four_wave(const rn_ctx *ctx, const Contraction &d, const GemmParams &p)
 {
-    if (BMsel == 128 && BNsel == 128)
-        launch_one<T, TO, 128, 128, DUAL, XK>(ctx, p, persistent);
-    else if (BMsel == 128 && BNsel == 64)
-        launch_one<T, TO, 128, 64, DUAL, XK>(ctx, p, persistent);
-    else if (BMsel == 64 && BNsel == 128)
-        launch_one<T, TO, 64, 128, DUAL, XK>(ctx, p, persistent);
-    else
-        launch_one<T, TO, 64, 64, DUAL, XK>(ctx, p, persistent);
+    // tile choice: the contraction is matrix-core bound, so a launch takes about
+    // ceil(tiles / 256 CUs) rounds of one tile's MFMA time; pick the candidate with the
+    // least (rounds * tile area / relative tile efficiency), i.e. the least padded,
+    // best balanced cover of the 256 CUs.  rn_model_tune measures instead of guessing.
+    static const int cand[4][2] = {{128, 128}, {128, 64}, {64, 128}, {64, 64}};
+    // relative efficiency of a full tile, measured on 3x3 and 1x1 layers at B=256: fp32 is
+    // bound by the matrix pipe and likes many small tiles (occupancy, tails); bf16 is bound by
+    // operand traffic per MFMA and likes large ones
+    static const double eff_f32[4] = {0.84, 0.95, 0.96, 1.00}, eff_bf16[4] = {1.00, 0.92, 0.95, 0.80};
+    const double *cand_eff = d.dt_in == RN_DTYPE_BF16 ? eff_bf16 : eff_f32;
+    Choice c{};
+    c.family = Choice::FOUR_WAVE, c.BM = c.BN = 128;
+    if (ctx->conv_tile >= 1 && ctx->conv_tile <= 8) {
+        // candidates 1-4: one block per tile; 5-8: the same tiles walked by a resident grid
+        c.BM = cand[(ctx->conv_tile - 1) & 3][0], c.BN = cand[(ctx->conv_tile - 1) & 3][1];
+        c.persistent = ctx->conv_tile > 4;
+    } else {
+        double best = 1e300;
+        for (int ci = 0; ci < 4; ++ci) {
+            const uint64_t tm = rn_ceil_div((uint64_t)p.M, cand[ci][0]);
+            const uint64_t tn = rn_ceil_div(d.Cout, cand[ci][1]);
+            const double rounds = (double)rn_ceil_div(tm * tn, 256);
+            const double cost = rounds * cand[ci][0] * cand[ci][1] / cand_eff[ci];
+            if (cost < best * 0.999) {
+                best = cost;
+                c.BM = cand[ci][0], c.BN = cand[ci][1];
+            }
+        }
+        c.persistent = true;
+    }
+    // Chunked K sum: a property of the LAYER (element type, kind, K), never of the batch size or
+    // the tile, so that every launch of the layer adds the same products in the same order.
+    // (bf16 operands with fp32 results: the fc of a bf16 model -- 64 tiles of 32 K steps at B = 256, 30 us as
+    // one block per tile on a quarter of the CUs)
+    const bool chunk_bf16 = d.dt_in == RN_DTYPE_BF16 && d.dt_out == RN_DTYPE_F32;
+    c.chunked = ((d.dt_in == RN_DTYPE_F32 && d.dt_out == RN_DTYPE_F32) || chunk_bf16) && !d.second && !d.exact &&
+                p.nk >= 32 && d.Cout % 4 == 0;  // (nk >= 16 measured: -0.3 % on the fp32 step)
+    // (the 128x128 tile has no registers to spare for a second accumulator; bf16 operands have the one tile)
+    if (c.chunked && c.BM == 128 && c.BN == 128) c.BN = 64;
+    if (c.chunked && chunk_bf16) c.BM = c.BN = 64;
+    return c;
 }
 
-// chunked K sum (fp32, and bf16 operands with an fp32 result: the fc of a bf16 model; the 128x128 tile has
-// no registers to spare for a second accumulator)
-void launch_tiles_chunked(rn_ctx *ctx, GemmParams &p, int BMsel, int BNsel, bool persistent, bool bf16_in)
+Choice choose(const rn_ctx *ctx, const Contraction &d, const GemmParams &p)
 {
-    if (bf16_in)
-        launch_one<bf16_t, float, 64, 64, false, false, true>(ctx, p, persistent);
-    else if (BMsel == 128)
-        launch_one<float, float, 128, 64, false, false, true>(ctx, p, persistent);
-    else if (BNsel == 128)
-        launch_one<float, float, 64, 128, false, false, true>(ctx, p, persistent);
-    else
-        launch_one<float, float, 64, 64, false, false, true>(ctx, p, persistent);
+    // bf16 on 256-wide block tiles (rn_conv_wide.hip): candidates 9.. of the tuner; without a
+    // tuned choice, the K-heavy layers whose tiles fill at least half the chip.  Same k order
+    // per output element as every other candidate, so this too only changes the speed.
+    if (d.dt_in == RN_DTYPE_BF16 && d.dt_out == RN_DTYPE_BF16 && ctx->split_k <= 1) {
+        const int nwide = rn_conv_wide_count();
+        Choice c{};
+        // 3x3 / 64 -> 64 channels: the strip kernel (weights in registers, input ring in LDS);
+        // the candidate after the wide tiles, and the untuned choice where it applies
+        if ((ctx->conv_tile == 9 + nwide || (ctx->conv_tile == 0 && p.M >= 256 * 256)) && d.second == nullptr &&
+            rn_conv_strip_eligible(p)) {
+            c.family = Choice::STRIP;
+            return c;
+        }
+        c.family = Choice::WIDE, c.which = -1;
+        if (ctx->conv_tile > 8 && ctx->conv_tile <= 8 + nwide) {
+            if (rn_conv_wide_eligible(p, ctx->conv_tile - 9)) c.which = ctx->conv_tile - 9;
+        } else if (ctx->conv_tile == 0 && p.nk >= 8 && d.Cout >= 128) {
+            // relative efficiency of a full tile (the 64x64 wave tiles of the 128-wide forms
+            // read twice the LDS bytes per MFMA)
+            static const double eff_wide[6] = {1.00, 0.80, 0.80, 0.50, 0.90, 0.55};
+            double best = 1e300;
+            for (int wi = 0; wi < nwide; ++wi) {
+                int bm, bn;
+                rn_conv_wide_tile(wi, &bm, &bn);
+                if (!rn_conv_wide_eligible(p, wi) || (uint64_t)bn > 2 * d.Cout) continue;
+                const uint64_t tiles = rn_ceil_div((uint64_t)p.M, bm) * rn_ceil_div(d.Cout, bn);
+                if (tiles < 128) continue;
+                const double cost = (double)rn_ceil_div(tiles, 256) * bm * bn / eff_wide[wi];
+                if (cost < best * 0.999) {
+                    best = cost;
+                    c.which = wi;
+                }
+            }
+        }
+        if (c.which >= 0) {
+            rn_conv_wide_tile(c.which, &c.BM, &c.BN);
+            return c;
+        }
+    }
+    return choose_four_wave(ctx, d, p);
+}
+
+// ---- split: how the work is divided among blocks ----
+// One work item per whole tile, every K tile of it, nothing in scratch: what the wide kernels and the plain
+// four-wave launch run, and what the two splits below start from.  False: more tiles than an int holds.
+bool split_whole_tiles(GemmParams &p, int BM, int BN)
+{
+    p.tiles_n = (int)rn_ceil_div((uint64_t)p.Cout, BN);
+    const uint64_t total = rn_ceil_div((uint64_t)p.M, BM) * (uint64_t)p.tiles_n;
+    if (!fits_i32(total)) return false;
+    p.total_tiles = p.total_work = p.grid_items = p.full_tiles = (unsigned)total;
+    p.ksplit = 1, p.kchunk = p.chunk_L = p.nk;
+    return true;
+}
+
+// The pass that adds raw fp32 sums left in scratch (`splits` slices of `slice` elements) and runs the epilogue
+// on the output rows from row0 on.
+FinishParams finish_params(const Contraction &d, const void *partial, int splits, uint64_t row0, uint64_t slice)
+{
+    const uint64_t skip = row0 * d.Cout * (d.dt_out == RN_DTYPE_BF16 ? 2 : 4);  // bytes of output before row0
+    FinishParams f{};
+    set_epilogue(f, d.ep);
+    f.partial = (const float *)partial;
+    f.out = (char *)d.out + skip;
+    if (f.residual) f.residual = (const char *)f.residual + skip;
+    f.splits = splits, f.Cout = (int)d.Cout, f.slice = f.stride = slice;
+    return f;
+}
+
+// Latency mode (rn_ctx_set_split_k): a launch whose tiles cannot fill the chip splits its
+// K loop over several blocks; each writes a raw fp32 partial tile to scratch and a second
+// kernel adds the partials in split order and applies the epilogue.  Deterministic, but
+// the summation order differs from the unsplit launch, so it is opt-in.  No XCD order.
+// fin->splits > 0 when the launch was split.
+int split_k_loop(rn_ctx *ctx, const Contraction &d, GemmParams &p, FinishParams *fin)
+{
+    if (!(ctx->split_k > 1 && p.total_tiles < 512 && p.nk >= 8 && d.Cout % 4 == 0 && !p.out_nchw &&
+          !(d.second && d.dt_in == RN_DTYPE_BF16)))
+        return RN_OK;
+    int S = (int)rn_ceil_div(1024, p.total_tiles);
+    if (S > ctx->split_k) S = ctx->split_k;
+    if (S > p.nk / 4) S = p.nk / 4;  // at least four K tiles per block
+    if (S <= 1) return RN_OK;
+    const int chunk = (int)rn_ceil_div((uint64_t)p.nk, (uint64_t)S);
+    S = (int)rn_ceil_div((uint64_t)p.nk, (uint64_t)chunk);
+    const uint64_t slice = (uint64_t)p.M * d.Cout;
+    void *ws = nullptr;
+    RN_TRY(rn_scratch(ctx, 4, (uint64_t)S * slice * sizeof(float), &ws));
+    *fin = finish_params(d, ws, S, 0, slice);
+    p.out = ws;
+    set_epilogue(p, nullptr);  // the finishing pass runs it
+    p.ksplit = S, p.kchunk = chunk;
+    p.total_work = p.grid_items = p.total_tiles * (unsigned)S;
+    p.split_stride = (long long)(slice * sizeof(float));
+    p.out_bytes = (int)(slice * sizeof(float));
+    return RN_OK;
+}
+
+// Chunked K sum: eight chunks (the last may be shorter; measured: as fast as four at B=256, 11 % less
+// B=1 latency), chunk length even for the two-tile loop trips.  fin->splits > 0 when the tail was cut.
+int split_chunked_tail(rn_ctx *ctx, const Contraction &d, int BM, GemmParams &p, FinishParams *fin)
+{
+    p.chunk_L = 2 * (int)rn_ceil_div((uint64_t)p.nk, 16);  // (even: the fp32 loop takes two K tiles per trip)
+    const int S = (int)rn_ceil_div((uint64_t)p.nk, (uint64_t)p.chunk_L);
+    // tail = the tiles past the last full round of the 256 CUs, in whole rows of M tiles;
+    // cutting them into S pieces pays when the pieces need fewer CU rounds than S
+    // (a launch with at most one round of tiles is all tail: small batches get S times the
+    // blocks, in the same summation order as any other batch size)
+    unsigned tail = p.total_tiles > 256 ? p.total_tiles % 256 : p.total_tiles;
+    tail -= tail % (unsigned)p.tiles_n;
+    // (NCHW output: the finishing kernel writes NHWC, so the tail tiles fold their chunks in
+    // registers like the others -- the same sum)
+    const bool cut = ctx->split_k <= 1 && tail > 0 && !p.out_nchw &&
+                     rn_ceil_div((uint64_t)tail * S, 256) < (uint64_t)S;
+    if (!cut) return RN_OK;
+    // the workspace holds only the tail rows [row0, M) of every chunk slice; the kernel
+    // addresses it like the output, through a base moved back by row0 rows
+    const uint64_t row0 = (uint64_t)((p.total_tiles - tail) / (unsigned)p.tiles_n) * (uint64_t)BM;
+    const uint64_t tail_elems = ((uint64_t)p.M - row0) * d.Cout;
+    void *ws = nullptr;
+    RN_TRY(rn_scratch(ctx, 4, (uint64_t)S * tail_elems * sizeof(float), &ws));
+    *fin = finish_params(d, ws, S, row0, tail_elems);
+    // (integer arithmetic: the moved base lies before the allocation and is never dereferenced)
+    p.ws = reinterpret_cast<void *>(reinterpret_cast<uintptr_t>(ws) - row0 * d.Cout * sizeof(float));
+    p.ws_stride = (long long)(tail_elems * sizeof(float));
+    p.tail_tiles = tail, p.full_tiles = p.total_tiles - tail;
+    p.total_work = p.grid_items = p.full_tiles + tail * (unsigned)S;
+    return RN_OK;
 }
 
 // Which order the tiles are dealt to the XCDs in (GemmParams::xg).  Every XCD has its own 4 MB L2; what an
@@ -915,8 +1118,6 @@ void launch_tiles_chunked(rn_ctx *ctx, GemmParams &p, int BMsel, int BNsel, bool
 // The order changes which block computes a tile, never a bit of the result.
 void choose_tile_order(rn_ctx *ctx, GemmParams &p, unsigned remap_tiles, int BM, int BN)
 {
-    p.xg = 0;
-    p.xrows = 0;
     const unsigned tn = (unsigned)p.tiles_n;
     if (tn < 2 || remap_tiles < 8 * tn) return;  // too few rows of M panels for eight ranges per group
     int groups = ctx->xcd_groups;                // forced (RN_XCD_NGROUPS / rn_ctx_set_xcd_groups): A/B runs
@@ -924,7 +1125,7 @@ void choose_tile_order(rn_ctx *ctx, GemmParams &p, unsigned remap_tiles, int BM,
         const double es = p.w_bytes / ((double)p.Cout * p.Ktot);  // bytes per element
         const double w_slab = (double)BN * p.Ktot * es;           // weight rows of one N tile
         const double a_slab = (double)BM * es * (p.Cs + (p.in2 ? p.Cs2 : 0));    // input rows of one M panel
-        const double R = 32.0 * (BM * BN <= 64 * 64 ? 4 : BM * BN <= 64 * 128 ? 3 : 2);
+        const double R = 32.0 * tile_blocks_per_cu(BM, BN);
         const double A = (double)p.in_bytes + (p.in2 ? (double)p.in2_bytes / (p.stride2 * p.stride2) : 0.0);
         const double Wb = (double)p.w_bytes, MB = 1024.0 * 1024.0;
         const double panels = (double)(remap_tiles / tn);  // M panels of the launch
@@ -959,347 +1160,126 @@ void choose_tile_order(rn_ctx *ctx, GemmParams &p, unsigned remap_tiles, int BM,
     p.xrows = remap_tiles / tn;
 }
 
-// GEMM launch on NHWC data with packed weights.  Caller has checked eligibility.
-// dt_in: element type of activations and weights; dt_out: of the output and the residual.
-int launch_gemm(rn_ctx *ctx, int dt_in, int dt_out, const void *inp, void *out, const void *packed,
-                uint64_t k, uint64_t stride, uint64_t pad, uint64_t h_out, uint64_t w_out,
-                uint64_t B, uint64_t Cin, uint64_t Cout, uint64_t H, uint64_t W,
-                const rn_epilogue *ep, const char *what, const rn_conv_second *second = nullptr,
-                bool exact = false, bool out_nchw = false, uint64_t dil = 1)
+// ---- dispatch: the instantiations of conv_gemm_kernel, each with its launcher ----
+// A resident grid is 256 CUs x the blocks of the instantiation that fit a CU at once (registers and LDS) on the
+// context's device: asked once per context and instantiation, the answer lives in the context (*occupancy).
+template <typename T, typename TO, int BM, int BN, bool DUAL, bool XK, bool CHUNK, bool DIL>
+void launch_one(rn_ctx *ctx, const GemmParams &p, bool persistent, int *occupancy)
 {
-    const int es = dt_in == RN_DTYPE_BF16 ? 2 : 4;
-    const int bke = 128 / es;
-    GemmParams p;
-    p.xg = 0;  // tile order: the logical one unless choose_tile_order says otherwise (tiled launches only)
-    p.xrows = 0;
-    // NCHW output: fp32, no residual (it would be NHWC); a 1x1 output image is the same in both
-    p.out_nchw = out_nchw && dt_out == RN_DTYPE_F32 && !(ep && ep->residual) && h_out * w_out > 1;
-    p.in = inp;
-    p.w = packed;
-    p.out = out;
-    p.scale = ep ? ep->scale : nullptr;
-    p.shift = ep ? ep->shift : nullptr;
-    p.residual = ep ? ep->residual : nullptr;
-    p.relu = ep ? ep->relu : 0;
-    const bool c4 = !exact && rn_conv_is_c4(Cin, k);
-    p.H = (int)H;
-    p.W = (int)W;
-    p.Cs = c4 ? 4 : (int)Cin;
-    p.Ho = (int)h_out;
-    p.Wo = (int)w_out;
-    p.Cout = (int)Cout;
-    const bool c4pair = c4 && dt_in == RN_DTYPE_BF16;  // two kernel rows per K tile
-    p.tap_rows = c4pair ? 2 : 1;
-    p.k_rows = (int)k;
-    p.KH = c4pair ? (int)rn_ceil_div(k, 2) : (int)k;
-    p.KW = c4 ? 1 : (int)k;
-    p.stride = (int)stride;
-    p.pad = (int)pad;
-    p.dil = (int)dil;  // (the small-Cin and exact-K forms are never dilated: their callers pass 1)
-    p.cseg = c4 ? 1 : (int)(Cin / bke);
-    p.chunk_dw = c4 ? 16 / (4 * es) : 0;  // pixels of a 4-channel image per 16-byte chunk
-    p.c4_chunks = c4 ? (int)rn_ceil_div(k, p.chunk_dw) : 0;  // <= 4 in the two-row form (k <= 8)
-    p.M = (int)(B * h_out * w_out);
-    p.nk = p.KH * p.KW * p.cseg;
-    p.nk1 = p.nk;
-    p.in2 = nullptr;
-    p.in2_bytes = p.H2 = p.W2 = p.Cs2 = p.stride2 = 0;
-    if (second) {
-        p.in2 = second->inp;
-        p.H2 = (int)second->H;
-        p.W2 = (int)second->W;
-        p.Cs2 = (int)second->in_channels;
-        p.stride2 = (int)second->stride;
-        p.in2_bytes = (int)(B * second->H * second->W * second->in_channels * es);
-        p.nk += (int)(second->in_channels / bke);
+    unsigned grid = p.grid_items;
+    if (persistent) {
+        if (*occupancy == 0) {
+            int nb = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                    &nb, conv_gemm_kernel<T, TO, BM, BN, DUAL, XK, CHUNK, DIL>, 256, 0) != hipSuccess ||
+                nb < 1)
+                nb = 1;
+            *occupancy = nb;
+        }
+        const unsigned slots = 256u * (unsigned)*occupancy;
+        if (grid > slots) grid = slots;
     }
-    p.Ktot = p.nk * bke;
-    p.kc = p.kskip = p.kreal = 0;
-    p.mul_kc = p.shr_kc = 0;
-    if (exact) {
-        p.kreal = (int)(k * k * Cin);
-        p.kc = (int)(k * Cin);
-        p.kskip = (int)((W - k) * Cin);
-        p.nk = p.nk1 = (int)rn_ceil_div((uint64_t)p.kreal, 32);
-        p.Ktot = p.nk * 32;
-        p.cseg = 1;
-        fast_div((unsigned)p.kc, &p.mul_kc, &p.shr_kc);
-    }
-    p.HoWo = p.Ho * p.Wo;
-    fast_div((unsigned)p.HoWo, &p.mul_hw, &p.shr_hw);
-    fast_div((unsigned)p.Wo, &p.mul_w, &p.shr_w);
-    fast_div((unsigned)p.cseg, &p.mul_cs, &p.shr_cs);
-    fast_div((unsigned)p.KW, &p.mul_kw, &p.shr_kw);
-    p.stamps = (unsigned long long *)ctx->debug_stamps;
-    p.in_bytes = (int)(B * H * W * (uint64_t)p.Cs * es);
-    p.w_bytes = (int)(Cout * (uint64_t)p.Ktot * es);
-    p.out_bytes = (int)(B * h_out * w_out * Cout * (uint64_t)(dt_out == RN_DTYPE_BF16 ? 2 : 4));
+    conv_gemm_kernel<T, TO, BM, BN, DUAL, XK, CHUNK, DIL><<<dim3(grid), dim3(256), 0, ctx->stream>>>(p);
+}
 
-    // bf16 on 256-wide block tiles (rn_conv_wide.hip): candidates 9.. of the tuner; without a
-    // tuned choice, the K-heavy layers whose tiles fill at least half the chip.  Same k order
-    // per output element as every other candidate, so this too only changes the speed.
-    if (dt_in == RN_DTYPE_BF16 && dt_out == RN_DTYPE_BF16 && ctx->split_k <= 1) {
-        const int nwide = rn_conv_wide_count();
-        int which = -1;
-        // 3x3 / 64 -> 64 channels: the strip kernel (weights in registers, input ring in LDS);
-        // the candidate after the wide tiles, and the untuned choice where it applies
-        if ((ctx->conv_tile == 9 + nwide || (ctx->conv_tile == 0 && p.M >= 256 * 256)) && second == nullptr &&
-            rn_conv_strip_eligible(p)) {
-            rn_conv_strip_launch(ctx, p);
-            return rn_after_launch(ctx, what);
-        }
-        if (ctx->conv_tile > 8 && ctx->conv_tile <= 8 + nwide) {
-            if (rn_conv_wide_eligible(p, ctx->conv_tile - 9)) which = ctx->conv_tile - 9;
-        } else if (ctx->conv_tile == 0 && p.nk >= 8 && Cout >= 128) {
-            // relative efficiency of a full tile (the 64x64 wave tiles of the 128-wide forms
-            // read twice the LDS bytes per MFMA)
-            static const double eff_wide[6] = {1.00, 0.80, 0.80, 0.50, 0.90, 0.55};
-            double best = 1e300;
-            for (int wi = 0; wi < nwide; ++wi) {
-                int bm, bn;
-                rn_conv_wide_tile(wi, &bm, &bn);
-                if (!rn_conv_wide_eligible(p, wi) || (uint64_t)bn > 2 * Cout) continue;
-                const uint64_t tiles = rn_ceil_div((uint64_t)p.M, bm) * rn_ceil_div(Cout, bn);
-                if (tiles < 128) continue;
-                const double cost = (double)rn_ceil_div(tiles, 256) * bm * bn / eff_wide[wi];
-                if (cost < best * 0.999) {
-                    best = cost;
-                    which = wi;
-                }
-            }
-        }
-        if (which >= 0) {
-            int bm, bn;
-            rn_conv_wide_tile(which, &bm, &bn);
-            p.tiles_n = (int)rn_ceil_div(Cout, bn);
-            const uint64_t total = rn_ceil_div((uint64_t)p.M, bm) * (uint64_t)p.tiles_n;
-            RN_REQUIRE(ctx, fits_i32(total), "too many tiles");
-            p.total_tiles = (unsigned)total;
-            p.ksplit = 1;
-            p.kchunk = p.nk;
-            p.total_work = p.total_tiles;
-            p.grid_items = p.total_tiles;
-            p.split_stride = 0;
-            p.chunk_L = p.nk;
-            p.full_tiles = p.total_tiles;
-            p.tail_tiles = 0;
-            p.ws = nullptr;
-            p.ws_stride = 0;
-            rn_conv_wide_launch(ctx, p, which, second != nullptr);
-            return rn_after_launch(ctx, what);
-        }
-    }
+struct KernelRow {
+    int dt_in, dt_out, BM, BN;
+    bool dual, xk, chunk, dil;
+    void (*launch)(rn_ctx *, const GemmParams &, bool persistent, int *occupancy);
+};
 
-    // tile choice: the contraction is matrix-core bound, so a launch takes about
-    // ceil(tiles / 256 CUs) rounds of one tile's MFMA time; pick the candidate with the
-    // least (rounds * tile area / relative tile efficiency), i.e. the least padded,
-    // best balanced cover of the 256 CUs.  rn_model_tune measures instead of guessing.
-    static const int cand[4][2] = {{128, 128}, {128, 64}, {64, 128}, {64, 64}};
-    // relative efficiency of a full tile, measured on 3x3 and 1x1 layers at B=256: fp32 is
-    // bound by the matrix pipe and likes many small tiles (occupancy, tails); bf16 is bound by
-    // operand traffic per MFMA and likes large ones
-    static const double eff_f32[4] = {0.84, 0.95, 0.96, 1.00}, eff_bf16[4] = {1.00, 0.92, 0.95, 0.80};
-    const double *cand_eff = dt_in == RN_DTYPE_BF16 ? eff_bf16 : eff_f32;
-    int BMsel = 128, BNsel = 128;
-    bool persistent;
-    if (ctx->conv_tile >= 1 && ctx->conv_tile <= 8) {
-        // candidates 1-4: one block per tile; 5-8: the same tiles walked by a resident grid
-        BMsel = cand[(ctx->conv_tile - 1) & 3][0];
-        BNsel = cand[(ctx->conv_tile - 1) & 3][1];
-        persistent = ctx->conv_tile > 4;
-    } else {
-        double best = 1e300;
-        for (int ci = 0; ci < 4; ++ci) {
-            const uint64_t tm = rn_ceil_div((uint64_t)p.M, cand[ci][0]);
-            const uint64_t tn = rn_ceil_div(Cout, cand[ci][1]);
-            const double rounds = (double)rn_ceil_div(tm * tn, 256);
-            const double cost = rounds * cand[ci][0] * cand[ci][1] / cand_eff[ci];
-            if (cost < best * 0.999) {
-                best = cost;
-                BMsel = cand[ci][0];
-                BNsel = cand[ci][1];
-            }
-        }
-        persistent = true;
-    }
-    // Chunked K sum: a property of the LAYER (element type, kind, K), never of the batch size or
-    // the tile, so that every launch of the layer adds the same products in the same order.
-    // (bf16 operands with fp32 results: the fc of a bf16 model -- 64 tiles of 32 K steps at B = 256, 30 us as
-    // one block per tile on a quarter of the CUs)
-    const bool chunk_bf16 = dt_in == RN_DTYPE_BF16 && dt_out == RN_DTYPE_F32;
-    const bool chunked = ((dt_in == RN_DTYPE_F32 && dt_out == RN_DTYPE_F32) || chunk_bf16) && !second && !exact &&
-                         p.nk >= 32 && Cout % 4 == 0;  // (nk >= 16 measured: -0.3 % on the fp32 step)
-    if (chunked && BMsel == 128 && BNsel == 128) BNsel = 64;
-    if (chunked && chunk_bf16) BMsel = BNsel = 64;
-    const uint64_t tiles_n = rn_ceil_div(Cout, BNsel);
-    const uint64_t tiles_m = rn_ceil_div((uint64_t)p.M, BMsel);
-    p.tiles_n = (int)tiles_n;
-    const uint64_t total = tiles_m * tiles_n;
-    RN_REQUIRE(ctx, fits_i32(total), "too many tiles");
-    p.total_tiles = (unsigned)total;
-    p.ksplit = 1;
-    p.kchunk = p.nk;
-    p.total_work = p.total_tiles;
-    p.split_stride = 0;
-    p.chunk_L = p.nk;
-    p.full_tiles = p.total_tiles;
-    p.tail_tiles = 0;
-    p.ws = nullptr;
-    p.ws_stride = 0;
-    // Latency mode (rn_ctx_set_split_k): a launch whose tiles cannot fill the chip splits its
-    // K loop over several blocks; each writes a raw fp32 partial tile to scratch and a second
-    // kernel adds the partials in split order and applies the epilogue.  Deterministic, but
-    // the summation order differs from the unsplit launch, so it is opt-in.
-    if (ctx->split_k > 1 && total < 512 && p.nk >= 8 && Cout % 4 == 0 && !p.out_nchw &&
-        !(second && dt_in == RN_DTYPE_BF16)) {
-        int S = (int)rn_ceil_div(1024, total);
-        if (S > ctx->split_k) S = ctx->split_k;
-        if (S > p.nk / 4) S = p.nk / 4;  // at least four K tiles per block
-        if (S > 1) {
-            const int chunk = (int)rn_ceil_div((uint64_t)p.nk, (uint64_t)S);
-            S = (int)rn_ceil_div((uint64_t)p.nk, (uint64_t)chunk);
-            const uint64_t slice = (uint64_t)p.M * Cout;
-            void *ws = nullptr;
-            RN_TRY(rn_scratch(ctx, 4, (uint64_t)S * slice * sizeof(float), &ws));
-            GemmParams q = p;
-            q.out = ws;
-            q.scale = q.shift = nullptr;
-            q.residual = nullptr;
-            q.relu = 0;
-            q.ksplit = S;
-            q.kchunk = chunk;
-            q.total_work = p.total_tiles * (unsigned)S;
-            q.split_stride = (long long)(slice * sizeof(float));
-            q.out_bytes = (int)(slice * sizeof(float));
-            q.grid_items = q.total_work;
-            if (exact)
-                launch_tiles<float, float, false, true>(ctx, q, BMsel, BNsel, persistent);
-            else if (second)
-                launch_tiles<float, float, true>(ctx, q, BMsel, BNsel, persistent);
-            else if (dt_in == RN_DTYPE_F32)
-                launch_tiles<float, float>(ctx, q, BMsel, BNsel, persistent);
-            else
-                launch_tiles<bf16_t, float>(ctx, q, BMsel, BNsel, persistent);
-            RN_TRY(rn_after_launch(ctx, what));
-            FinishParams f;
-            f.partial = (const float *)ws;
-            f.out = out;
-            f.scale = p.scale;
-            f.shift = p.shift;
-            f.residual = p.residual;
-            f.relu = p.relu;
-            f.splits = S;
-            f.Cout = (int)Cout;
-            f.slice = slice;
-            f.stride = slice;
-            const unsigned fgrid = rn_stream_grid(slice / 4, 256);
-            if (dt_out == RN_DTYPE_BF16)
-                splitk_finish_kernel<bf16_t><<<fgrid, 256, 0, ctx->stream>>>(f);
-            else
-                splitk_finish_kernel<float><<<fgrid, 256, 0, ctx->stream>>>(f);
-            return rn_after_launch(ctx, what);
-        }
-    }
-    if (chunked) {
-        // eight chunks (the last may be shorter; measured: as fast as four at B=256, 11 % less
-        // B=1 latency), chunk length even for the two-tile loop trips
-        p.chunk_L = 2 * (int)rn_ceil_div((uint64_t)p.nk, 16);  // (even: the fp32 loop takes two K tiles per trip)
-        const int S = (int)rn_ceil_div((uint64_t)p.nk, (uint64_t)p.chunk_L);
-        // tail = the tiles past the last full round of the 256 CUs, in whole rows of M tiles;
-        // cutting them into S pieces pays when the pieces need fewer CU rounds than S
-        // (a launch with at most one round of tiles is all tail: small batches get S times the
-        // blocks, in the same summation order as any other batch size)
-        unsigned tail = total > 256 ? (unsigned)(total % 256) : (unsigned)total;
-        tail -= tail % (unsigned)tiles_n;
-        // (NCHW output: the finishing kernel writes NHWC, so the tail tiles fold their chunks in
-        // registers like the others -- the same sum)
-        const bool cut = ctx->split_k <= 1 && tail > 0 && !p.out_nchw &&
-                         rn_ceil_div((uint64_t)tail * S, 256) < (uint64_t)S;
-        // the workspace holds only the tail rows [row0, M) of every chunk slice; the kernel
-        // addresses it like the output, through a base moved back by row0 rows
-        uint64_t row0 = 0, tail_elems = 0;
-        void *ws_real = nullptr;
-        if (cut) {
-            row0 = (uint64_t)((p.total_tiles - tail) / (unsigned)tiles_n) * (uint64_t)BMsel;
-            tail_elems = ((uint64_t)p.M - row0) * Cout;
-            RN_TRY(rn_scratch(ctx, 4, (uint64_t)S * tail_elems * sizeof(float), &ws_real));
-            // (integer arithmetic: the moved base lies before the allocation and is never dereferenced)
-            p.ws = reinterpret_cast<void *>(reinterpret_cast<uintptr_t>(ws_real) - row0 * Cout * sizeof(float));
-            p.ws_stride = (long long)(tail_elems * sizeof(float));
-            p.tail_tiles = tail;
-            p.full_tiles = p.total_tiles - tail;
-            p.total_work = p.full_tiles + tail * (unsigned)S;
-        }
-        p.grid_items = p.total_work;
-        choose_tile_order(ctx, p, p.full_tiles, BMsel, BNsel);
-        launch_tiles_chunked(ctx, p, BMsel, BNsel, persistent, chunk_bf16);
-        RN_TRY(rn_after_launch(ctx, what));
-        if (cut) {
-            FinishParams f;
-            f.partial = (const float *)ws_real;
-            f.out = (float *)out + row0 * Cout;
-            f.scale = p.scale;
-            f.shift = p.shift;
-            f.residual = p.residual ? (const float *)p.residual + row0 * Cout : nullptr;
-            f.relu = p.relu;
-            f.splits = S;
-            f.Cout = (int)Cout;
-            f.slice = tail_elems;
-            f.stride = tail_elems;
-            splitk_finish_kernel<float><<<rn_stream_grid(f.slice / 4, 256), 256, 0, ctx->stream>>>(f);
-            return rn_after_launch(ctx, what);
-        }
-        return RN_OK;
-    }
+template <typename T>
+constexpr int dtype_of = std::is_same<T, float>::value ? RN_DTYPE_F32 : RN_DTYPE_BF16;
 
-    p.grid_items = p.total_tiles;
-    choose_tile_order(ctx, p, p.total_tiles, BMsel, BNsel);
-    if (exact)
-        launch_tiles<float, float, false, true>(ctx, p, BMsel, BNsel, persistent);
-    else if (second && dt_in == RN_DTYPE_F32 && dt_out == RN_DTYPE_F32)
-        launch_tiles<float, float, true>(ctx, p, BMsel, BNsel, persistent);
-    else if (second && dt_in == RN_DTYPE_BF16 && dt_out == RN_DTYPE_BF16)
-        launch_tiles<bf16_t, bf16_t, true>(ctx, p, BMsel, BNsel, persistent);
-    else if (second)
-        return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "%s: fused pair needs equal in/out dtype", what);
-    else if (dt_in == RN_DTYPE_F32 && dt_out == RN_DTYPE_F32)
-        launch_tiles<float, float>(ctx, p, BMsel, BNsel, persistent);
-    else if (dt_in == RN_DTYPE_BF16 && dt_out == RN_DTYPE_BF16)
-        launch_tiles<bf16_t, bf16_t>(ctx, p, BMsel, BNsel, persistent);
-    else if (dt_in == RN_DTYPE_BF16 && dt_out == RN_DTYPE_F32)
-        launch_tiles<bf16_t, float>(ctx, p, BMsel, BNsel, persistent);
+template <int BM, int BN, typename T, typename TO, bool DUAL = false, bool XK = false, bool CHUNK = false,
+          bool DIL = false>
+constexpr KernelRow row()
+{
+    return {dtype_of<T>, dtype_of<TO>, BM, BN, DUAL, XK, CHUNK, DIL, launch_one<T, TO, BM, BN, DUAL, XK, CHUNK, DIL>};
+}
+#define FOUR_TILES(...) \
+    row<128, 128, __VA_ARGS__>(), row<128, 64, __VA_ARGS__>(), row<64, 128, __VA_ARGS__>(), row<64, 64, __VA_ARGS__>()
+
+// Every instantiation that exists, and no other: a row that is not here is a combination nobody launches (or,
+// for a chunked 128x128 tile, one that does not fit the register file).  A row's place is its slot in
+// rn_ctx::occupancy.  Arguments: <tile,> T, TO, DUAL, XK, CHUNK, DIL; every form but the exact-K one has a
+// dilated twin (a flag of the instantiation: see conv_gemm_kernel).
+constexpr KernelRow kKernels[] = {
+    FOUR_TILES(float, float, false, false, false, false),   FOUR_TILES(float, float, false, false, false, true),
+    FOUR_TILES(float, float, true, false, false, false),    FOUR_TILES(float, float, true, false, false, true),
+    FOUR_TILES(float, float, false, true, false, false),  // exact-K
+    FOUR_TILES(bf16_t, bf16_t, false, false, false, false), FOUR_TILES(bf16_t, bf16_t, false, false, false, true),
+    FOUR_TILES(bf16_t, bf16_t, true, false, false, false),  FOUR_TILES(bf16_t, bf16_t, true, false, false, true),
+    FOUR_TILES(bf16_t, float, false, false, false, false),  FOUR_TILES(bf16_t, float, false, false, false, true),
+    // chunked K sum: fp32, and bf16 operands with an fp32 result (the fc of a bf16 model) on the one tile
+    row<128, 64, float, float, false, false, true, false>(), row<128, 64, float, float, false, false, true, true>(),
+    row<64, 128, float, float, false, false, true, false>(), row<64, 128, float, float, false, false, true, true>(),
+    row<64, 64, float, float, false, false, true, false>(),  row<64, 64, float, float, false, false, true, true>(),
+    row<64, 64, bf16_t, float, false, false, true, false>(), row<64, 64, bf16_t, float, false, false, true, true>(),
+};
+#undef FOUR_TILES
+static_assert(sizeof(kKernels) / sizeof(kKernels[0]) == RN_CONV_GEMM_KERNELS, "one rn_ctx::occupancy slot per row");
+
+// fp32_partials: the first pass of a split K loop -- the fp32-output row of the same family, never chunked
+int dispatch(rn_ctx *ctx, const Contraction &d, const Choice &c, const GemmParams &p, bool fp32_partials)
+{
+    const bool xk = d.exact, dual = d.second && !xk;
+    const int dt_out = fp32_partials ? RN_DTYPE_F32 : d.dt_out;
+    const bool chunk = c.chunked && !fp32_partials, dil = p.dil != 1 && !xk;
+    for (const KernelRow &r : kKernels) {
+        if (r.dt_in != d.dt_in || r.dt_out != dt_out || r.BM != c.BM || r.BN != c.BN || r.dual != dual ||
+            r.xk != xk || r.chunk != chunk || r.dil != dil)
+            continue;
+        r.launch(ctx, p, c.persistent, &ctx->occupancy[&r - kKernels]);
+        return rn_after_launch(ctx, d.what);
+    }
+    if (d.second) return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "%s: fused pair needs equal in/out dtype", d.what);
+    return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "%s: dtype combination %d -> %d", d.what, d.dt_in, d.dt_out);
+}
+
+// GEMM launch on NHWC data with packed weights.  Caller has checked eligibility.
+int launch_gemm(rn_ctx *ctx, const Contraction &d)
+{
+    GemmParams p = describe(ctx, d);
+    const Choice c = choose(ctx, d, p);
+    if (c.family == Choice::STRIP) {
+        rn_conv_strip_launch(ctx, p);
+        return rn_after_launch(ctx, d.what);
+    }
+    RN_REQUIRE(ctx, split_whole_tiles(p, c.BM, c.BN), "too many tiles");
+    if (c.family == Choice::WIDE) {
+        rn_conv_wide_launch(ctx, p, c.which, d.second != nullptr);
+        return rn_after_launch(ctx, d.what);
+    }
+    FinishParams fin{};  // splits > 0: the launch leaves raw sums in scratch for a finishing pass
+    RN_TRY(split_k_loop(ctx, d, p, &fin));
+    const bool k_split = fin.splits > 0;
+    if (!k_split) {
+        if (c.chunked) RN_TRY(split_chunked_tail(ctx, d, c.BM, p, &fin));
+        choose_tile_order(ctx, p, p.full_tiles, c.BM, c.BN);
+    }
+    RN_TRY(dispatch(ctx, d, c, p, k_split));
+    if (fin.splits == 0) return RN_OK;
+    const unsigned fgrid = rn_stream_grid(fin.slice / 4, 256);
+    if (d.dt_out == RN_DTYPE_BF16)
+        splitk_finish_kernel<bf16_t><<<fgrid, 256, 0, ctx->stream>>>(fin);
     else
-        return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "%s: dtype combination %d -> %d", what, dt_in,
-                            dt_out);
-    return rn_after_launch(ctx, what);
+        splitk_finish_kernel<float><<<fgrid, 256, 0, ctx->stream>>>(fin);
+    return rn_after_launch(ctx, d.what);
 }
 
 int launch_direct(rn_ctx *ctx, const float *inp, float *out, const float *w, uint64_t k,
                   uint64_t stride, uint64_t pad, uint64_t h_out, uint64_t w_out, uint64_t B,
                   uint64_t Cin, uint64_t Cs, uint64_t Cout, uint64_t H, uint64_t W, int nhwc,
-                  int w_packed, const rn_epilogue *ep, const char *what, uint64_t dil = 1)
+                  int w_packed, const rn_epilogue *ep, const char *what, uint64_t dil)
 {
     DirectParams p;
-    p.in = inp;
-    p.w = w;
-    p.out = out;
-    p.scale = ep ? ep->scale : nullptr;
-    p.shift = ep ? ep->shift : nullptr;
-    p.residual = ep ? static_cast<const float *>(ep->residual) : nullptr;
-    p.relu = ep ? ep->relu : 0;
-    p.k = (int)k;
-    p.stride = (int)stride;
-    p.pad = (int)pad;
-    p.dil = (int)dil;
-    p.Ho = (int)h_out;
-    p.Wo = (int)w_out;
-    p.Cin = (int)Cin;
-    p.Cs = (int)Cs;
-    p.Cout = (int)Cout;
-    p.H = (int)H;
-    p.W = (int)W;
-    p.nhwc = nhwc;
-    p.w_packed = w_packed;
+    p.in = inp, p.w = w, p.out = out;
+    set_epilogue(p, ep);
+    p.k = (int)k, p.stride = (int)stride, p.pad = (int)pad, p.dil = (int)dil;
+    p.Ho = (int)h_out, p.Wo = (int)w_out, p.H = (int)H, p.W = (int)W;
+    p.Cin = (int)Cin, p.Cs = (int)Cs, p.Cout = (int)Cout;
+    p.nhwc = nhwc, p.w_packed = w_packed;
     p.total = B * Cout * h_out * w_out;
     conv_direct_kernel<<<rn_stream_grid(p.total, 256), 256, 0, ctx->stream>>>(p);
     return rn_after_launch(ctx, what);
@@ -1362,9 +1342,12 @@ int nhwc_forward(rn_ctx *ctx, const float *inp, float *out, const float *packed_
                       B * H * W * rn_conv2d_input_channels(in_channels),
                       rn_conv2d_packed_weight_numel(in_channels, out_channels, kernel_size),
                       B * h_out * w_out * out_channels)) {
-        return launch_gemm(ctx, RN_DTYPE_F32, RN_DTYPE_F32, inp, out, packed_weight, kernel_size,
-                           stride, padding, h_out, w_out, B, in_channels, out_channels, H, W,
-                           epilogue, "rn_conv2d_nhwc_forward", nullptr, false, false, dil);
+        Contraction d{};
+        d.dt_in = d.dt_out = RN_DTYPE_F32, d.inp = inp, d.out = out, d.packed = packed_weight;
+        d.k = kernel_size, d.stride = stride, d.pad = padding, d.dil = dil, d.h_out = h_out, d.w_out = w_out;
+        d.B = B, d.Cin = in_channels, d.Cout = out_channels, d.H = H, d.W = W;
+        d.ep = epilogue, d.what = "rn_conv2d_nhwc_forward";
+        return launch_gemm(ctx, d);
     }
     const bool c4 = rn_conv_is_c4(in_channels, kernel_size);
     return launch_direct(ctx, inp, out, packed_weight, kernel_size, stride, padding, h_out, w_out,
@@ -1439,11 +1422,12 @@ int conv2d_forward(rn_ctx *ctx, const float *inp, float *out, const float *weigh
             return pst;
         }
     }
-    if (ctx->layout == RN_LAYOUT_NHWC) {
-        return launch_gemm(ctx, RN_DTYPE_F32, RN_DTYPE_F32, inp, out, wp, kernel_size, stride,
-                           padding, h_out, w_out, B, in_channels, out_channels, H, W, nullptr,
-                           "rn_conv2d_forward(nhwc)", nullptr, false, false, dil);
-    }
+    Contraction d{};
+    d.dt_in = d.dt_out = RN_DTYPE_F32, d.inp = inp, d.out = out, d.packed = wp;
+    d.k = kernel_size, d.stride = stride, d.pad = padding, d.dil = dil, d.h_out = h_out, d.w_out = w_out;
+    d.B = B, d.Cin = in_channels, d.Cout = out_channels, d.H = H, d.W = W;
+    d.what = "rn_conv2d_forward(nhwc)";
+    if (ctx->layout == RN_LAYOUT_NHWC) return launch_gemm(ctx, d);
     if (taps)
         return rn_conv_nchw_launch(ctx, inp, out, (const float *)wp, kernel_size, stride, padding, B, in_channels,
                                    out_channels, H, W);
@@ -1456,9 +1440,8 @@ int conv2d_forward(rn_ctx *ctx, const float *inp, float *out, const float *weigh
     } else {
         RN_TRY(rn_nchw_to_nhwc(ctx, inp, (float *)xin, B, in_channels, H, W));
     }
-    return launch_gemm(ctx, RN_DTYPE_F32, RN_DTYPE_F32, xin, out, wp, kernel_size, stride, padding,
-                       h_out, w_out, B, in_channels, out_channels, H, W, nullptr,
-                       "rn_conv2d_forward(gemm)", nullptr, false, true, dil);
+    d.inp = xin, d.out_nchw = true, d.what = "rn_conv2d_forward(gemm)";
+    return launch_gemm(ctx, d);
 }
 
 int nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const void *inp, void *out,
@@ -1500,9 +1483,12 @@ int nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const void *inp, void
                       reinterpret_cast<uintptr_t>(packed_weight)) & 15) == 0,
                "bf16 tensors must be 16-byte aligned");
     RN_REQUIRE(ctx, epilogue_aligned(epilogue, 15), "misaligned scale / shift / residual (16-byte alignment)");
-    return launch_gemm(ctx, RN_DTYPE_BF16, out_dtype, inp, out, packed_weight, kernel_size, stride,
-                       padding, h_out, w_out, B, in_channels, out_channels, H, W, epilogue,
-                       "rn_conv2d_nhwc_forward_dt", nullptr, false, false, dil);
+    Contraction d{};
+    d.dt_in = RN_DTYPE_BF16, d.dt_out = out_dtype, d.inp = inp, d.out = out, d.packed = packed_weight;
+    d.k = kernel_size, d.stride = stride, d.pad = padding, d.dil = dil, d.h_out = h_out, d.w_out = w_out;
+    d.B = B, d.Cin = in_channels, d.Cout = out_channels, d.H = H, d.W = W;
+    d.ep = epilogue, d.what = "rn_conv2d_nhwc_forward_dt";
+    return launch_gemm(ctx, d);
 }
 
 // what the dilated entry points check before anything is launched; k == 1 has one tap, so its dilation is 1
@@ -1627,9 +1613,12 @@ int rn_conv2d_nhwc_exact_forward(rn_ctx *ctx, const float *inp_padded, float *ou
                         (reinterpret_cast<uintptr_t>(inp_padded) & 3) == 0,
                "misaligned tensor");
     RN_REQUIRE(ctx, epilogue_aligned(epilogue, 15), "misaligned scale / shift / residual (16-byte alignment)");
-    return launch_gemm(ctx, RN_DTYPE_F32, RN_DTYPE_F32, inp_padded, out, packed_exact_weight,
-                       kernel_size, stride, 0, h_out, w_out, B, in_channels, out_channels, Hp, Wp,
-                       epilogue, "rn_conv2d_nhwc_exact_forward", nullptr, true);
+    Contraction d{};
+    d.dt_in = d.dt_out = RN_DTYPE_F32, d.inp = inp_padded, d.out = out, d.packed = packed_exact_weight;
+    d.k = kernel_size, d.stride = stride, d.pad = 0, d.dil = 1, d.h_out = h_out, d.w_out = w_out;
+    d.B = B, d.Cin = in_channels, d.Cout = out_channels, d.H = Hp, d.W = Wp;
+    d.ep = epilogue, d.exact = true, d.what = "rn_conv2d_nhwc_exact_forward";
+    return launch_gemm(ctx, d);
 }
 
 int rn_conv2d_nhwc_pair_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const void *inp, void *out,
@@ -1672,9 +1661,12 @@ int rn_conv2d_nhwc_pair_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const 
                       reinterpret_cast<uintptr_t>(second->inp)) & 15) == 0,
                "tensors must be 16-byte aligned");
     RN_REQUIRE(ctx, epilogue_aligned(epilogue, 15), "misaligned scale / shift / residual (16-byte alignment)");
-    return launch_gemm(ctx, dtype, out_dtype, inp, out, packed_pair_weight, kernel_size, stride,
-                       padding, h_out, w_out, B, in_channels, out_channels, H, W, epilogue,
-                       "rn_conv2d_nhwc_pair_forward_dt", second);
+    Contraction d{};
+    d.dt_in = dtype, d.dt_out = out_dtype, d.inp = inp, d.out = out, d.packed = packed_pair_weight;
+    d.k = kernel_size, d.stride = stride, d.pad = padding, d.dil = 1, d.h_out = h_out, d.w_out = w_out;
+    d.B = B, d.Cin = in_channels, d.Cout = out_channels, d.H = H, d.W = W;
+    d.ep = epilogue, d.second = second, d.what = "rn_conv2d_nhwc_pair_forward_dt";
+    return launch_gemm(ctx, d);
 }
 
 int rn_linear_forward(rn_ctx *ctx, const float *inp, float *out, const float *weight,
@@ -1695,11 +1687,15 @@ int rn_linear_forward(rn_ctx *ctx, const float *inp, float *out, const float *we
     if (in_features % 32 == 0 && epilogue_aligned(&ep, 15) &&  // (the bias is the epilogue's shift)
         gemm_eligible(inp, out, weight, in_features, 1, B * in_features, out_features * in_features,
                       B * out_features)) {
-        return launch_gemm(ctx, RN_DTYPE_F32, RN_DTYPE_F32, inp, out, weight, 1, 1, 0, 1, 1, B,
-                           in_features, out_features, 1, 1, &ep, "rn_linear_forward");
+        Contraction d{};
+        d.dt_in = d.dt_out = RN_DTYPE_F32, d.inp = inp, d.out = out, d.packed = weight;
+        d.k = d.stride = d.dil = d.h_out = d.w_out = d.H = d.W = 1;  // (pad = 0)
+        d.B = B, d.Cin = in_features, d.Cout = out_features;
+        d.ep = &ep, d.what = "rn_linear_forward";
+        return launch_gemm(ctx, d);
     }
     return launch_direct(ctx, inp, out, weight, 1, 1, 0, 1, 1, B, in_features, in_features,
-                         out_features, 1, 1, 1, 0, &ep, "rn_linear_forward(direct)");
+                         out_features, 1, 1, 1, 0, &ep, "rn_linear_forward(direct)", 1);
 }
 
 // library-internal (rn_private.h): rn_linear_forward through the direct kernel whatever the alignment.  The
@@ -1718,7 +1714,7 @@ int rn_linear_direct_forward(rn_ctx *ctx, const float *inp, float *out, const fl
                "tensor has 2^31 or more elements");
     rn_epilogue ep = {nullptr, bias, nullptr, 0};
     return launch_direct(ctx, inp, out, weight, 1, 1, 0, 1, 1, B, in_features, in_features, out_features, 1, 1, 1, 0,
-                         &ep, "rn_linear_direct_forward");
+                         &ep, "rn_linear_direct_forward", 1);
 }
 
 }  // extern "C"

@@ -14,6 +14,8 @@ struct rn_wcache_entry {
     void *packed;
 };
 
+#define RN_CONV_GEMM_KERNELS 52  // instantiations of conv_gemm_kernel (rn_conv.hip checks the count)
+
 struct rn_ctx {
     int device;
     int cus;  // compute units of the device (256 on MI355X), asked once at creation
@@ -32,9 +34,10 @@ struct rn_ctx {
     // warm up first so the sizes are already settled)
     void *scratch[6];  // 0 batch-norm constants, 1-3 NCHW convolution, 4 split-K partial sums, 5 resize tables
     uint64_t scratch_bytes[6];
-    // resident blocks per CU of each contraction-kernel instantiation on THIS context's device,
-    // asked once per context (0 = not asked yet); no process-wide mutable state
-    int occupancy[256];
+    // resident blocks per CU of each contraction-kernel instantiation on THIS context's device, one per row of
+    // the kernel table of rn_conv.hip, asked once per context (0 = not asked yet); no process-wide mutable state
+    int occupancy[RN_CONV_GEMM_KERNELS];
+    int stem_lds_allowed[5];  // fused-stem kernels that were allowed their dynamic LDS on this device (rn_stem.hip)
     uint64_t launches;  // kernel launches issued through this context (rn_after_launch)
     // packed-weight cache of the NCHW drop-in route (rn_conv2d_forward): OIHW weight pointer +
     // shape -> K-major panel, packed on first use; off unless rn_ctx_set_weight_cache(ctx, 1)

@@ -615,7 +615,7 @@ static int stem_pool_launch(rn_ctx *ctx, int dtype, const void *inp, void *out, 
                              : nchw ? (const void *)stem_pool_kernel<float, true> : (const void *)stem_pool_kernel<float, false>);
     // more than 64 KB of dynamic LDS has to be allowed once per kernel and device (not a stream
     // operation: done on the first call, which a capturing caller makes eagerly anyway)
-    int *allowed = &ctx->occupancy[y ? 252 : 248 + (bf ? 1 : 0) + (nchw ? 2 : 0)];
+    int *allowed = &ctx->stem_lds_allowed[y ? 4 : (bf ? 1 : 0) + (nchw ? 2 : 0)];
     if (lds_bytes > 64 * 1024 && *allowed == 0) {
         RN_HIP_TRY(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         *allowed = 1;

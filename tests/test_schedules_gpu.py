@@ -27,6 +27,7 @@ Schedule (resnet.c_amd/csrc/)                          reached by
   splitk_finish_kernel (out + row0 * Cout)                test_chunked_k_sum[*], test_split_k[*]
   launch_gemm: split_k > 1                                test_split_k[*], test_split_k_pair[*]
   rn_conv_wide_launch, rn_conv_strip_launch               test_wide_tiles_and_strip[*]
+  choose: the wide / strip / 4-wave rules, candidate 0    test_own_choice[*]
   chain_launch (rn_chain.hip)                             test_chain[*]
   stem_pool_launch: seg_len, segs (rn_stem.hip)           test_fused_stem[*]
   GemmParams::out_nchw                                    test_nchw_output_of_the_transposing_route
@@ -454,6 +455,53 @@ def test_wide_tiles_and_strip(name):
         first = got if first is None else first
         fig.same(got, first, what + " (against candidate 4)")
     print(f"\n  test_wide_tiles_and_strip[{name}]: kernel per candidate: {' '.join(ran)}")
+    fig.done()
+
+
+# ---- 6b. the dispatcher's own choice between the wide, strip and 4-wave kernels (bf16 -> bf16, candidate 0) ------
+# choose (rn_conv.hip) with nothing forced.  The smallest shapes at which each rule flips, from its constants:
+#   wide       1x1, Cin = 512 (nk = 8 K tiles of 64), Cout = 256, 4 x 64 x 64 = 16384 rows.  Cost = ceil(tiles / 256) x
+#              tile area / eff_wide: 128x128 256 tiles, 16384 / 0.55 = 29789; 256x64 256 tiles, 16384 / 0.50 = 32768;
+#              256x128 and 128x256 128 tiles, 32768 / 0.80 = 40960; 256x256 (64 tiles) and 224x256 (74) have fewer
+#              than 128 tiles.  So the 128x128 wide tile, one block per tile: grid 256
+#   not-wide   the same with Cin = 448: nk = 7 < 8, no wide tile is considered -- a 4-wave tile
+#   strip      3x3 / 1 / 1, 64 -> 64, 16 x 128 x 32 = 65536 rows = 256 * 256, W + 3 = 35 <= 64: the strip kernel
+#   not-strip  the same with 15 images: 61440 rows < 256 * 256, and Cout < 128 rules the wide tiles out -- a 4-wave tile
+# Which kernel ran is read from the debug stamps as in test_wide_tiles_and_strip.  One launch per case.
+OWN_CASES = {"wide": ((4, 512, 256, 64, 64, 1, 1, 0), "wide", 256), "not-wide": ((4, 448, 256, 64, 64, 1, 1, 0), "tile", None),
+             "strip": ((16, 64, 64, 128, 32, 3, 1, 1), "strip", None), "not-strip": ((15, 64, 64, 128, 32, 3, 1, 1), "tile", None)}
+
+
+@pytest.mark.parametrize("name", sorted(OWN_CASES))
+def test_own_choice(name):
+    from resnet_c_amd.tensor import _DeviceBuffer
+    case, want_kernel, want_grid = OWN_CASES[name]
+    B, Cin, Cout, H, W, k, s, p = case
+    K = Cin * k * k
+    x, w, sc, sh, res = conv_operands(case, 650 + sum(case), BF16)
+    ref = conv_reference(x, w, s, p, sc, sh, res, True, BF16, name)
+    ctx, lib = R.get_ctx(), L.lib()
+    M = int(np.prod(ref.shape)) // Cout
+    nblk = -(-M // 64) * -(-Cout // 64)      # the most blocks any kernel launches here: one per 64 x 64 tile
+    stamps = _DeviceBuffer(ctx, nblk * 16 * 8)
+    L.check(lib.rn_memset(ctx.handle, stamps.ptr, 0, nblk * 128), "memset", ctx.handle)
+    with schedule():
+        try:
+            L.check(lib.rn_ctx_set_debug_stamps(ctx.handle, stamps.ptr), "stamps", ctx.handle)
+            got = V.run_conv_dt(x, w, s, p, sc, sh, res, True, BF16, BF16)
+        finally:
+            lib.rn_ctx_set_debug_stamps(ctx.handle, None)
+    slots = np.zeros(nblk * 16, np.uint64)
+    L.check(lib.rn_memcpy_d2h(ctx.handle, slots.ctypes.data, stamps.ptr, slots.nbytes), "d2h", ctx.handle)
+    wrote = slots.reshape(nblk, 16) != 0
+    kernel = "strip" if wrote[:, 10].any() else "tile" if wrote[:, 7].any() else "wide"
+    grid = int(wrote[:, 0].sum())
+    what = f"own choice {name}: {kernel} kernel, grid {grid}"
+    print(f"\n  test_own_choice[{name}]: {M} rows, K = {K}: {kernel} kernel, grid {grid}")
+    assert kernel == want_kernel and grid > 0, f"{what}; expected the {want_kernel} kernel"
+    assert want_grid is None or grid == want_grid, f"{what}; expected a grid of {want_grid}"
+    fig = Figures(f"test_own_choice[{name}]")
+    fig.values(got, ref, K, True, True, what)
     fig.done()
 
 

@@ -7,7 +7,8 @@
 
 Per kernel of the parent: VGPRs, AGPRs, scratch bytes and occupancy, "same" or "DIFF" against this tree's kernel of
 that name.  An instantiation that gained the trailing DIL = false template flag (conv_gemm_kernel,
-conv_group_kernel) is compared with the parent's kernel without the flag; kernels only this tree has are "new"."""
+conv_group_kernel) is compared with the parent's kernel without the flag where the parent has no kernel of its
+own name; kernels only this tree has are "new"."""
 import re
 import sys
 def parse(path):
@@ -38,16 +39,15 @@ parent_dir, this_dir, files = sys.argv[1], sys.argv[2], sys.argv[3:]
 bad = 0
 for f in files:
     p, t = parse(f"{parent_dir}/{f}.s"), parse(f"{this_dir}/{f}.s")
-    tmap = {}
-    for k, v in t.items():
-        tmap[strip_dil(k)] = v
+    tmap = {strip_dil(k): v for k, v in t.items()}
+    tmap.update(t)      # a parent that has the flag too: name against name
     print(f"== {f}.hip: {len(p)} kernels at the parent, {len(t)} in this tree")
     for k, v in p.items():
         w = tmap.get(k)
         same = w is not None and all(v.get(x) == w.get(x) for x in ("vgpr", "agpr", "scratch", "occupancy"))
         bad += not same
         print(f"{'same ' if same else 'DIFF '} {norm(k)[:78]:78s} vgpr {v.get('vgpr')} agpr {v.get('agpr')} scratch {v.get('scratch')} occupancy {v.get('occupancy')}" + ("" if same else f"  -> {w}"))
-    new = [k for k in t if strip_dil(k) not in p]
+    new = [k for k in t if k not in p and strip_dil(k) not in p]
     for k in new:
         v = t[k]
         print(f"new   {norm(k)[:78]:78s} vgpr {v.get('vgpr')} agpr {v.get('agpr')} scratch {v.get('scratch')} occupancy {v.get('occupancy')}")

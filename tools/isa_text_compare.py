@@ -1,0 +1,60 @@
+#!/usr/bin/env python3
+"""Device code of one build against another's, as text, from hipcc -S dumps (made as for tools/isa_regs_compare.py).
+
+    python tools/isa_text_compare.py PARENT_DIR THIS_DIR rn_conv ...
+
+The compiler's per-build hash (__hip_cuid_*) and the function number in local labels (.LBB<n>_3) are replaced
+and .file / .ident / .loc lines are dropped.  Then each dump is
+cut into one piece per kernel (code, kernel descriptor, register comment block) and the entries of its
+metadata list, and the two builds must hold the same pieces: every instruction, every kernel-argument offset and
+every register count of every kernel.  The order the compiler emitted the kernels in is reported separately: it
+follows the order the host code first names the instantiations in and is no property of any kernel."""
+import re
+import sys
+
+
+def pieces(path):
+    txt = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_X", open(path).read())
+    # local labels carry the number of their function in emission order: .LBB12_3, .Lfunc_end12, .Ltmp7
+    txt = re.sub(r"\.L(BB|func_begin|func_end|tmp|JTI)\d+", r".L\1N", txt)
+    txt = re.sub(r"\bBB\d+_(\d+)", r"BBN_\1", txt)  # (the same labels in loop comments)
+    txt = re.sub(r"[ \t]+;", " ;", txt)  # (the comment column behind a label moves with the label's length)
+    lines = [l for l in txt.splitlines() if not re.match(r"\s*\.(ident|file|loc)\b", l)]
+    out, cur, meta = [], [], False
+    for l in lines:
+        if l.startswith("\t.section\t.AMDGPU.gpr_maximums"):  # the module's trailer, the metadata list behind it
+            meta = True
+            out.append("\n".join(cur))
+            cur = []
+        elif meta and re.match(r"  - \.|amdhsa\.target", l):
+            out.append("\n".join(cur))
+            cur = []
+        elif not meta and "; -- Begin function" in l:
+            # a kernel's piece starts at the section line in front of its .globl line
+            at = max((i for i, c in enumerate(cur) if re.match(r"\t\.(section|text)\b", c)), default=len(cur))
+            out.append("\n".join(cur[:at]))
+            cur = cur[at:]
+        cur.append(l)
+    out.append("\n".join(cur))
+    return out
+
+
+def main():
+    a_dir, b_dir, names = sys.argv[1], sys.argv[2], sys.argv[3:]
+    bad = 0
+    for n in names:
+        a, b = pieces(f"{a_dir}/{n}.s"), pieces(f"{b_dir}/{n}.s")
+        kernels = sum(p.count(".amdhsa_kernel ") for p in a), sum(p.count(".amdhsa_kernel ") for p in b)
+        only_a, only_b = set(a) - set(b), set(b) - set(a)
+        same = sorted(a) == sorted(b)
+        bad += not same
+        print(f"{n}.s: kernels {kernels[0]} / {kernels[1]}, pieces {len(a)} / {len(b)}, "
+              f"differing pieces {len(only_a)} / {len(only_b)}: {'same text' if same else 'DIFFERENT'}; "
+              f"emission order {'same' if a == b else 'differs'}")
+        for p in sorted(only_a | only_b)[:4]:
+            print("   differs:", p.strip().splitlines()[0][:160])
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
