@@ -211,6 +211,28 @@ RN_API int rn_ctx_set_xcd_groups(rn_ctx *ctx, int groups);
  * on planes of 2048 pixels or more, where it measures faster (tools/nchw_bench.py).  Also RN_NCHW_TAPS in the
  * environment at context creation.  Changes the route, no bit. */
 RN_API int rn_ctx_set_nchw_taps(rn_ctx *ctx, int mode);
+/* fp32 k x k convolutions with padding: pixel-major tiles.  An M tile of the contraction is then one output
+ * pixel of a block of images instead of consecutive (b, oh, ow) rows, so the taps that fall into the padding are
+ * the same for the whole tile and their K tiles are not multiplied at all (the row-major schedule multiplies
+ * them as zeros).  No tensor changes its layout.  Eligible: fp32 in and out, kernel_size > 1, padding > 0,
+ * in_channels % 32 == 0, dilation 1, one source, NHWC output, no split K, every output pixel with a tap inside
+ * the image.  mode 0 (default): the library's rule (rn_conv_tap_skip_plan says what it decides); 1: never;
+ * 2: wherever eligible.  Also RN_TAP_SKIP in the environment at context creation.  Only products with a zero
+ * operand are left out: for finite operands the result is bit for bit that of mode 1; a non-finite weight
+ * opposite padding (0 * Inf) no longer reaches the sum, as in the reference, which skips those taps too. */
+RN_API int rn_ctx_set_tap_skip(rn_ctx *ctx, int mode);
+/* Pixel-major launches issued through this context and the K tiles (128 bytes of K per tile row) they left out. */
+RN_API int rn_ctx_tap_skip_stats(const rn_ctx *ctx, uint64_t *launches, uint64_t *k_tiles_skipped);
+/* Pure host arithmetic, no device: the pixel-major plan of one convolution launch on tile candidate `tile`
+ * (1..8 as rn_ctx_set_conv_tile; 0 = the tile the library chooses for the shape).  dtype is that of input and
+ * output.  Returns 1 when the shape is eligible, 0 when not (the outputs are then 0), -1 for bad arguments.
+ * m_tiles: h_out * w_out * ceil(B / BM); k_tiles: K tiles of the launch in the row-major count,
+ * m_tiles * N tiles * (k * k * in_channels / 32); k_tiles_skipped: those a pixel-major launch leaves out;
+ * rule: 1 when mode 0 takes the pixel-major tiles for this launch.  Any output may be NULL. */
+RN_API int rn_conv_tap_skip_plan(int dtype, uint64_t B, uint64_t in_channels, uint64_t out_channels, uint64_t H,
+                                 uint64_t W, uint64_t kernel_size, uint64_t stride, uint64_t padding,
+                                 uint64_t dilation, int tile, uint64_t *m_tiles, uint64_t *k_tiles,
+                                 uint64_t *k_tiles_skipped, int *rule);
 /* Diagnostics: device buffer of 16 x uint64 per block that the contraction kernel fills with
  * wall-clock and shader-clock stamps of its phases (tools/conv_stamps.py); NULL (default) = off. */
 RN_API int rn_ctx_set_debug_stamps(rn_ctx *ctx, void *dev_buffer);

@@ -61,6 +61,9 @@ SIGNATURES = {
     "rn_ctx_set_stem_items": (c_int, [c_void_p, c_int]),
     "rn_ctx_set_xcd_groups": (c_int, [c_void_p, c_int]),
     "rn_ctx_set_nchw_taps": (c_int, [c_void_p, c_int]),
+    "rn_ctx_set_tap_skip": (c_int, [c_void_p, c_int]),
+    "rn_ctx_tap_skip_stats": (c_int, [c_void_p, POINTER(u64), POINTER(u64)]),
+    "rn_conv_tap_skip_plan": (c_int, [c_int] + [u64] * 9 + [c_int] + [POINTER(u64)] * 3 + [POINTER(c_int)]),
     "rn_ctx_set_debug_stamps": (c_int, [c_void_p, c_void_p]),
     "rn_ctx_stream": (c_void_p, [c_void_p]),
     "rn_ctx_device": (c_int, [c_void_p]),

@@ -52,6 +52,14 @@
 // everywhere with bf16 storage.  Algorithmic bytes: es*(M*K_in + N*K + M*N) (+ es*M*N
 // with a residual), flops 2*M*N*K.
 //
+// Pixel-major tiles (PM, fp32 only): the M tile is (output pixel, block of BM images) instead of BM consecutive
+// (b, oh, ow) rows.  All rows of such a tile share (oh, ow), so which taps fall into the padding is a scalar of
+// the tile and the K loop walks only the K tiles of the taps inside the image.  Only products with a zero
+// operand are left out: for finite operands every output is the same fmaf chain with its +0 terms removed,
+// bit for bit the result of the row-major schedule (chunked K sums keep their fold points at the real K
+// positions).  A non-finite weight opposite padding no longer turns 0 * Inf into NaN: there PM behaves like
+// the reference, which skips those taps as well (ops.cu:35-37).  No tensor changes its layout.
+//
 // Shapes the GEMM cannot take (Cin not a multiple of 32 and not the small-Cin stem
 // form, or tensors of 2 GiB and more) run a direct fp32 kernel that keeps the
 // reference's exact summation order ic -> kh -> kw.
@@ -142,8 +150,10 @@ struct OutVec<bf16_t> {
 // DIL: GemmParams::dil > 1 -- kernel row kh reads input row ih0 + kh * dil, columns alike; the row masks are
 //      built tap by tap and the tap offset scales.  A flag of the instantiation, not a branch, so that the
 //      row setup of the undilated launches (block life outside the K loop) is what it was
+// PM: pixel-major M tiles that skip the padding taps (see the head of this file and GemmParams::pm), fp32 in and
+//      out, never with DUAL, XK or DIL
 template <typename T, typename TO, int BM, int BN, bool DUAL = false, bool XK = false, bool CHUNK = false,
-          bool DIL = false>
+          bool DIL = false, bool PM = false>
 __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_kernel(const GemmParams p)
 {
     constexpr int CH = Elem<T>::CH, ES = (int)sizeof(T);
@@ -210,6 +220,21 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
     unsigned vtile = blockIdx.x;
     int m0, n0, kb, ke, ks_idx;
     work_item(vtile, m0, n0, kb, ke, ks_idx);
+    // PM: M tile m0 / BM = image block * HoWo + output pixel (neighbouring pixels of the same images are dealt
+    // together: their taps overlap in L2), and the K walk of the tile setup_rows was last called for -- its first
+    // K tile, the K tiles of one kernel row's run of valid taps, the K tiles between two runs, the valid K tiles
+    [[maybe_unused]] auto pm_tile = [&](int m0_, int &g_, int &pix_) {
+        const int mt = m0_ / BM;
+        g_ = p.HoWo == 1 ? mt : (int)(__umulhi((unsigned)mt, p.mul_hw) >> p.shr_hw);
+        pix_ = mt - g_ * p.HoWo;
+    };
+    [[maybe_unused]] int pm_kt0 = 0, pm_run = 0, pm_gap = 0, pm_nv = 0;
+    [[maybe_unused]] int pm_a0 = 0, pm_left = 0;  // per thread: offset of staged row 0 at tap (0, 0); images from it on
+    // images of the batch, M / HoWo (asked for inside the PM code only: a read of p in the common path moves the
+    // kernel-argument loads of every other instantiation)
+    [[maybe_unused]] auto pm_images = [&]() {
+        return p.HoWo == 1 ? p.M : (int)(__umulhi((unsigned)p.M, p.mul_hw) >> p.shr_hw);
+    };
 
     const int t = threadIdx.x;
     const int c = t & 7;    // 16-byte chunk of the 128-byte row this thread stages
@@ -232,8 +257,28 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
     int a_off[AP], a_mask[AP], b_off[BP];
     int a_off2[DUAL ? AP : 1];  // second source: byte offset of chunk c of the row's pixel
     auto setup_rows = [&](int m0_, int n0_) {
+        if constexpr (PM) {
+            // one pixel for the whole tile: the valid kernel rows and columns are scalars, a row is an image
+            // (no division), and a row's mask only says whether the image exists
+            int g, pix;
+            pm_tile(m0_, g, pix);
+            const int oh = p.Wo == 1 ? pix : (int)(__umulhi((unsigned)pix, p.mul_w) >> p.shr_w);
+            const int ow = pix - oh * p.Wo;
+            const int ih0 = oh * p.stride - p.pad, iw0 = ow * p.stride - p.pad;
+            const int hlo = max(0, -ih0), hhi = min(p.KH, p.H - ih0);
+            const int wlo = max(0, -iw0), whi = min(p.KW, p.W - iw0);
+            pm_run = (whi - wlo) * p.cseg;
+            pm_gap = (p.KW - (whi - wlo)) * p.cseg;
+            pm_kt0 = (hlo * p.KW + wlo) * p.cseg;
+            pm_nv = (hhi - hlo) * pm_run;  // > 0: the host launches PM only where every pixel has a valid tap
+            // staged row j is image g * BM + r0 + 32 j: one offset and one count of the images that exist per
+            // thread, the step from j to j + 1 is a scalar
+            const int b0 = g * BM + r0;
+            pm_left = pm_images() - b0;
+            pm_a0 = pm_left > 0 ? (((b0 * p.H + ih0) * p.W + iw0) * p.Cs + c * CH) * ES : 0;
+        }
 #pragma unroll
-        for (int j = 0; j < AP; ++j) {
+        for (int j = 0; j < (PM ? 0 : AP); ++j) {
             const int m = m0_ + r0 + 32 * j;
             if (m < p.M) {
                 const int b = p.HoWo == 1 ? m : (int)(__umulhi((unsigned)m, p.mul_hw) >> p.shr_hw);
@@ -279,6 +324,7 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
         }
     };
     setup_rows(m0, n0);
+    if constexpr (PM) kb = pm_kt0;
 
     u32x4 ra[AP], rb[BP];
     int a_cur[AP];  // byte offset of the current tap's first segment, or kOob
@@ -334,8 +380,14 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
                 // (DIL, unsigned: a tap that is never inside the image may wrap; its mask bit is clear)
                 const int toff = DIL ? (int)((unsigned)(s_kh * p.W + s_kw) * (unsigned)(p.dil * p.Cs * ES))
                                      : (s_kh * p.tap_rows * p.W + s_kw) * p.Cs * ES;
+                if constexpr (PM) {  // every tap the walk reaches is inside the image: a row only has to exist
+                    const unsigned img32 = 32u * (unsigned)(p.H * p.W * p.Cs * ES);
 #pragma unroll
-                for (int j = 0; j < AP; ++j) {
+                    for (int j = 0; j < AP; ++j)
+                        a_cur[j] = 32 * j < pm_left ? pm_a0 + (int)((unsigned)toff + (unsigned)j * img32) : kOob;
+                }
+#pragma unroll
+                for (int j = 0; j < (PM ? 0 : AP); ++j) {
                     const bool ok = ((a_mask[j] >> s_kh) & (a_mask[j] >> (16 + s_kw)) & 1) != 0;
                     a_cur[j] = ok ? a_off[j] + toff : kOob;
                 }
@@ -472,6 +524,15 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
     // by then).
     constexpr bool EARLY_RES = !CHUNK && PASSES * (int)sizeof(T) <= 16;
 
+    // PM: output row (index into [0, M)) of row `row` of the current tile -- the row's image at the tile's
+    // pixel -- and whether the tile has that row
+    [[maybe_unused]] auto pm_row = [&](int row, int &m_) {
+        int g, pix;
+        pm_tile(m0, g, pix);
+        const int b = g * BM + row;
+        m_ = (int)((unsigned)b * (unsigned)p.HoWo) + pix;
+        return b < pm_images();
+    };
     // residual rows and the channel constants of the CURRENT tile (m0, n0)
     auto prefetch_epilogue = [&]() {
         const int n = n0 + cv * EPT;
@@ -483,8 +544,15 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
         }
 #pragma unroll
         for (int ps = 0; ps < PASSES; ++ps) {
-            const int m = m0 + rr + ps * RPP;
-            const int off = (col_ok && m < p.M) ? (m * p.Cout + n) * (int)sizeof(TO) : kOob;
+            int off;
+            if constexpr (PM) {
+                int m;
+                const bool row_ok = pm_row(rr + ps * RPP, m);
+                off = (col_ok && row_ok) ? (m * p.Cout + n) * (int)sizeof(TO) : kOob;
+            } else {
+                const int m = m0 + rr + ps * RPP;
+                off = (col_ok && m < p.M) ? (m * p.Cout + n) * (int)sizeof(TO) : kOob;
+            }
             resv[ps] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_r, off, 0, 0);
         }
     };
@@ -511,7 +579,64 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
         const unsigned vnext = vtile + gridDim.x;
         const bool has_next = vnext < p.total_work;
         int m0n = 0, n0n = 0, kbn = 0, ken = 0, ksn = 0;
-        if constexpr (sizeof(T) == 4) {
+        if constexpr (PM) {
+            // pixel-major tile: the K tiles of the taps inside the image in K order -- kt runs through one
+            // kernel row's valid taps and jumps to the next row's.  The fp32 loop below with a scalar walk in
+            // place of kt + 1: two K tiles per trip on compile-time LDS buffers, no vector ALU work between
+            // the MFMAs; a pair may straddle two taps (Cin = 32: one K tile per tap).
+            int kt = kb, run = pm_run, left = pm_nv;  // left: K tiles still to multiply, the staged one included
+            const int run_len = pm_run, gap = pm_gap;
+            auto advance = [&]() {
+                ++kt;
+                if (--run == 0) kt += gap, run = run_len;
+            };
+            // CHUNK: the fold points stay at the real K positions (multiples of chunk_L); every fold point up to
+            // K tile k is taken before k is multiplied, so a chunk whose tiles were all skipped folds +0 -- what
+            // its zero products summed to.  A fold point may fall between the two tiles of a trip.
+            [[maybe_unused]] int fold_at = p.chunk_L;
+            [[maybe_unused]] bool folded = false;
+            auto fold_before = [&](int k) {
+                if constexpr (CHUNK) {
+                    while (k >= fold_at) {  // uniform
+                        fold_acc(folded);
+                        folded = true;
+                        fold_at += p.chunk_L;
+                    }
+                }
+            };
+            while (left > 2) {
+                fold_before(kt);
+                advance();
+                load_tile(kt, ra, rb, std::false_type{});
+                compute_tile(Buf0{});
+                store_tile(Buf1{}, ra, rb);
+                __syncthreads();
+                fold_before(kt);
+                advance();
+                load_tile(kt, ra, rb, std::false_type{});
+                compute_tile(Buf1{});
+                store_tile(Buf0{}, ra, rb);
+                __syncthreads();
+                left -= 2;
+            }
+            fold_before(kt);
+            if (left == 2) {  // two tiles left: one in buffer 0, the other still to fetch
+                advance();
+                load_tile(kt, ra, rb, std::false_type{});
+                compute_tile(Buf0{});
+                store_tile(Buf1{}, ra, rb);
+                __syncthreads();
+                fold_before(kt);
+                compute_tile(Buf1{});
+            } else {  // one tile left, in buffer 0
+                compute_tile(Buf0{});
+            }
+            fold_before(p.nk - 1);  // the chunks behind the last valid tap
+            if constexpr (CHUNK) {
+                if (folded) finish_acc();
+            }
+            __syncthreads();
+        } else if constexpr (sizeof(T) == 4) {
             // fp32 (MFMA-bound): two K tiles per trip so that the LDS buffer of every access is
             // a compile-time offset -- no vector ALU work at all between the MFMAs.  Inside the
             // loop both loads are unconditional (no phi copies of the staging registers); the
@@ -583,6 +708,7 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
         if (has_next) {
             work_item(vnext, m0n, n0n, kbn, ken, ksn);
             setup_rows(m0n, n0n);
+            if constexpr (PM) kbn = pm_kt0;
             load_tile(kbn, ra, rb, std::true_type{});
         }
 
@@ -685,7 +811,14 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
                     v[j] = RELU ? fmaxf(y[0], 0.f) : y[0];
                     v[j + 1] = RELU ? fmaxf(y[1], 0.f) : y[1];
                 }
-                const int off = (col_ok && m < p.M) ? (m * p.Cout + n) * (int)sizeof(TO) : kOob;
+                int off;
+                if constexpr (PM) {
+                    int mp;
+                    const bool row_ok = pm_row(row, mp);
+                    off = (col_ok && row_ok) ? (mp * p.Cout + n) * (int)sizeof(TO) : kOob;
+                } else {
+                    off = (col_ok && m < p.M) ? (m * p.Cout + n) * (int)sizeof(TO) : kOob;
+                }
                 __builtin_amdgcn_raw_buffer_store_b128(OutVec<TO>::pack(v), rsrc_o, off, 0, 0);
             }
         };
@@ -701,8 +834,12 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
         // ragged channel count (Cout % EPT != 0): element-wise, rare
         for (int ps = 0; ps < PASSES; ++ps) {
             const int row = rr + ps * RPP;
-            const int m = m0 + row;
-            if (m >= p.M) continue;
+            int m = m0 + row;
+            if constexpr (PM) {
+                if (!pm_row(row, m)) continue;
+            } else {
+                if (m >= p.M) continue;
+            }
             for (int j = 0; j < EPT; ++j) {
                 if (n + j >= p.Cout) break;
                 const size_t o = (size_t)m * p.Cout + n + j;
@@ -921,10 +1058,11 @@ struct Choice {
     int BM, BN;       // WIDE and FOUR_WAVE: the block tile
     bool persistent;  // FOUR_WAVE: a resident grid walks the tiles (else one block per tile)
     bool chunked;     // FOUR_WAVE: chunked K sum
+    bool pm;          // FOUR_WAVE: pixel-major M tiles that skip the padding taps (plan_tap_skip)
 };
 
 // the four-wave tile of conv_gemm_kernel
-Choice choose_four_wave(const rn_ctx *ctx, const Contraction &d, const GemmParams &p)
+Choice choose_four_wave(int conv_tile, const Contraction &d, const GemmParams &p)
 {
     // tile choice: the contraction is matrix-core bound, so a launch takes about
     // ceil(tiles / 256 CUs) rounds of one tile's MFMA time; pick the candidate with the
@@ -938,10 +1076,10 @@ Choice choose_four_wave(const rn_ctx *ctx, const Contraction &d, const GemmParam
     const double *cand_eff = d.dt_in == RN_DTYPE_BF16 ? eff_bf16 : eff_f32;
     Choice c{};
     c.family = Choice::FOUR_WAVE, c.BM = c.BN = 128;
-    if (ctx->conv_tile >= 1 && ctx->conv_tile <= 8) {
+    if (conv_tile >= 1 && conv_tile <= 8) {
         // candidates 1-4: one block per tile; 5-8: the same tiles walked by a resident grid
-        c.BM = cand[(ctx->conv_tile - 1) & 3][0], c.BN = cand[(ctx->conv_tile - 1) & 3][1];
-        c.persistent = ctx->conv_tile > 4;
+        c.BM = cand[(conv_tile - 1) & 3][0], c.BN = cand[(conv_tile - 1) & 3][1];
+        c.persistent = conv_tile > 4;
     } else {
         double best = 1e300;
         for (int ci = 0; ci < 4; ++ci) {
@@ -1010,7 +1148,57 @@ Choice choose(const rn_ctx *ctx, const Contraction &d, const GemmParams &p)
             return c;
         }
     }
-    return choose_four_wave(ctx, d, p);
+    return choose_four_wave(ctx->conv_tile, d, p);
+}
+
+// ---- pixel-major tiles: where they apply, what they leave out, and when mode 0 takes them ----
+struct TapSkipPlan {
+    bool eligible;
+    bool rule;                               // mode 0 takes the pixel-major tiles
+    uint64_t m_tiles, k_tiles, k_skipped;    // of the launch on BM x BN tiles (k_tiles: the row-major count)
+};
+
+// The rule of mode 0, from profiles/tap_skip/layers_off_against_on.txt (ResNet-50 fp32, B = 256, the pixel-major
+// launch against the row-major one, layer by layer, three alternations).  Every stride-1 3x3 layer gains 0.009 -
+// 0.015 ms of 0.42 - 0.48 (2 - 3.5 %, beyond the off runs' spread of 0 - 0.007) from 2.4 % of padded K tiles up,
+// so x = kTapSkipMinShare = 0.02.  Of the three stride-2 layers the one on a 28x28 output gains as much and the
+// two on 14x14 and 7x7 outputs lose 0.017 and 0.032 ms: they skip only the top row and the left column, and with
+// few pixels their tiles (uncut tail included) no longer balance over the resident grid; a strided launch is
+// taken from kTapSkipMinStridedPixels = 784 output pixels on.  Masked rows are multiplied like any other, so
+// ceil(B / BM) * BM - B wasted rows cost their share of the launch: with 2 - 3.5 % to gain,
+// y = kTapSkipMaxWaste = 0.02 (B = 256 and its two halves of 128 waste nothing on either tile height).
+constexpr double kTapSkipMinShare = 0.02, kTapSkipMaxWaste = 0.02;
+constexpr uint64_t kTapSkipMinStridedPixels = 784;
+
+// Pure host arithmetic.  The taps of output row oh that are inside the image are kernel rows
+// [max(0, -ih0), min(k, H - ih0)) with ih0 = oh * stride - pad, columns alike, so the valid taps of a pixel are
+// rows(oh) * cols(ow) and their sum over the map is sum(rows) * sum(cols).
+TapSkipPlan plan_tap_skip(const Contraction &d, const GemmParams &p, int BM, int BN, bool split_k)
+{
+    TapSkipPlan t{};
+    if (d.dt_in != RN_DTYPE_F32 || d.dt_out != RN_DTYPE_F32 || d.k <= 1 || d.pad == 0 || d.Cin % 32 != 0 ||
+        d.dil != 1 || d.second || d.exact || p.out_nchw || split_k)
+        return t;
+    uint64_t sum[2] = {0, 0};
+    const uint64_t n_out[2] = {d.h_out, d.w_out}, n_in[2] = {d.H, d.W};
+    for (int ax = 0; ax < 2; ++ax)
+        for (uint64_t o = 0; o < n_out[ax]; ++o) {
+            const int64_t x0 = (int64_t)(o * d.stride) - (int64_t)d.pad;
+            const int64_t lo = x0 < 0 ? -x0 : 0, hi = (int64_t)n_in[ax] - x0 < (int64_t)d.k ? (int64_t)n_in[ax] - x0 : (int64_t)d.k;
+            if (hi <= lo) return t;  // a pixel without a tap inside the image: the K walk needs one
+            sum[ax] += (uint64_t)(hi - lo);
+        }
+    const uint64_t blocks = rn_ceil_div(d.B, (uint64_t)BM), tiles_n = rn_ceil_div(d.Cout, (uint64_t)BN);
+    const uint64_t pixels = d.h_out * d.w_out, cseg = d.Cin / 32;
+    t.eligible = true;
+    t.m_tiles = pixels * blocks;
+    t.k_tiles = t.m_tiles * tiles_n * (d.k * d.k * cseg);
+    t.k_skipped = blocks * tiles_n * cseg * (pixels * d.k * d.k - sum[0] * sum[1]);
+    const double share = (double)t.k_skipped / (double)t.k_tiles;
+    const double waste = 1.0 - (double)d.B / (double)(blocks * (uint64_t)BM);
+    t.rule = share >= kTapSkipMinShare && waste <= kTapSkipMaxWaste &&
+             (d.stride == 1 || pixels >= kTapSkipMinStridedPixels);
+    return t;
 }
 
 // ---- split: how the work is divided among blocks ----
@@ -1023,6 +1211,20 @@ bool split_whole_tiles(GemmParams &p, int BM, int BN)
     if (!fits_i32(total)) return false;
     p.total_tiles = p.total_work = p.grid_items = p.full_tiles = (unsigned)total;
     p.ksplit = 1, p.kchunk = p.chunk_L = p.nk;
+    return true;
+}
+
+// Pixel-major: one work item per (output pixel, block of BM images, N tile), every valid K tile of it.  The
+// chunked form folds all its chunks in registers (the tail is never cut into pieces: the workspace is addressed
+// by contiguous rows), which is the same sum.
+bool split_pixel_major(GemmParams &p, const Contraction &d, int BM, int BN)
+{
+    p.tiles_n = (int)rn_ceil_div((uint64_t)p.Cout, BN);
+    const uint64_t total = (uint64_t)p.HoWo * rn_ceil_div(d.B, (uint64_t)BM) * (uint64_t)p.tiles_n;
+    if (!fits_i32(total * (uint64_t)BM / (uint64_t)p.tiles_n)) return false;  // (the kernel's m0 = M tile * BM)
+    if (!fits_i32(total)) return false;
+    p.total_tiles = p.total_work = p.grid_items = p.full_tiles = (unsigned)total;
+    p.ksplit = 1, p.kchunk = p.nk;
     return true;
 }
 
@@ -1163,7 +1365,7 @@ void choose_tile_order(rn_ctx *ctx, GemmParams &p, unsigned remap_tiles, int BM,
 // ---- dispatch: the instantiations of conv_gemm_kernel, each with its launcher ----
 // A resident grid is 256 CUs x the blocks of the instantiation that fit a CU at once (registers and LDS) on the
 // context's device: asked once per context and instantiation, the answer lives in the context (*occupancy).
-template <typename T, typename TO, int BM, int BN, bool DUAL, bool XK, bool CHUNK, bool DIL>
+template <typename T, typename TO, int BM, int BN, bool DUAL, bool XK, bool CHUNK, bool DIL, bool PM>
 void launch_one(rn_ctx *ctx, const GemmParams &p, bool persistent, int *occupancy)
 {
     unsigned grid = p.grid_items;
@@ -1171,7 +1373,7 @@ void launch_one(rn_ctx *ctx, const GemmParams &p, bool persistent, int *occupanc
         if (*occupancy == 0) {
             int nb = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                    &nb, conv_gemm_kernel<T, TO, BM, BN, DUAL, XK, CHUNK, DIL>, 256, 0) != hipSuccess ||
+                    &nb, conv_gemm_kernel<T, TO, BM, BN, DUAL, XK, CHUNK, DIL, PM>, 256, 0) != hipSuccess ||
                 nb < 1)
                 nb = 1;
             *occupancy = nb;
@@ -1179,12 +1381,12 @@ void launch_one(rn_ctx *ctx, const GemmParams &p, bool persistent, int *occupanc
         const unsigned slots = 256u * (unsigned)*occupancy;
         if (grid > slots) grid = slots;
     }
-    conv_gemm_kernel<T, TO, BM, BN, DUAL, XK, CHUNK, DIL><<<dim3(grid), dim3(256), 0, ctx->stream>>>(p);
+    conv_gemm_kernel<T, TO, BM, BN, DUAL, XK, CHUNK, DIL, PM><<<dim3(grid), dim3(256), 0, ctx->stream>>>(p);
 }
 
 struct KernelRow {
     int dt_in, dt_out, BM, BN;
-    bool dual, xk, chunk, dil;
+    bool dual, xk, chunk, dil, pm;
     void (*launch)(rn_ctx *, const GemmParams &, bool persistent, int *occupancy);
 };
 
@@ -1192,18 +1394,20 @@ template <typename T>
 constexpr int dtype_of = std::is_same<T, float>::value ? RN_DTYPE_F32 : RN_DTYPE_BF16;
 
 template <int BM, int BN, typename T, typename TO, bool DUAL = false, bool XK = false, bool CHUNK = false,
-          bool DIL = false>
+          bool DIL = false, bool PM = false>
 constexpr KernelRow row()
 {
-    return {dtype_of<T>, dtype_of<TO>, BM, BN, DUAL, XK, CHUNK, DIL, launch_one<T, TO, BM, BN, DUAL, XK, CHUNK, DIL>};
+    return {dtype_of<T>, dtype_of<TO>, BM, BN, DUAL, XK, CHUNK, DIL, PM,
+            launch_one<T, TO, BM, BN, DUAL, XK, CHUNK, DIL, PM>};
 }
 #define FOUR_TILES(...) \
     row<128, 128, __VA_ARGS__>(), row<128, 64, __VA_ARGS__>(), row<64, 128, __VA_ARGS__>(), row<64, 64, __VA_ARGS__>()
 
 // Every instantiation that exists, and no other: a row that is not here is a combination nobody launches (or,
 // for a chunked 128x128 tile, one that does not fit the register file).  A row's place is its slot in
-// rn_ctx::occupancy.  Arguments: <tile,> T, TO, DUAL, XK, CHUNK, DIL; every form but the exact-K one has a
-// dilated twin (a flag of the instantiation: see conv_gemm_kernel).
+// rn_ctx::occupancy.  Arguments: <tile,> T, TO, DUAL, XK, CHUNK, DIL, PM; every form but the exact-K one has a
+// dilated twin (a flag of the instantiation: see conv_gemm_kernel); the plain and the chunked fp32 forms have a
+// pixel-major twin.
 constexpr KernelRow kKernels[] = {
     FOUR_TILES(float, float, false, false, false, false),   FOUR_TILES(float, float, false, false, false, true),
     FOUR_TILES(float, float, true, false, false, false),    FOUR_TILES(float, float, true, false, false, true),
@@ -1216,6 +1420,11 @@ constexpr KernelRow kKernels[] = {
     row<64, 128, float, float, false, false, true, false>(), row<64, 128, float, float, false, false, true, true>(),
     row<64, 64, float, float, false, false, true, false>(),  row<64, 64, float, float, false, false, true, true>(),
     row<64, 64, bf16_t, float, false, false, true, false>(), row<64, 64, bf16_t, float, false, false, true, true>(),
+    // pixel-major tiles that skip the padding taps: fp32, plain and chunked
+    FOUR_TILES(float, float, false, false, false, false, true),
+    row<128, 64, float, float, false, false, true, false, true>(),
+    row<64, 128, float, float, false, false, true, false, true>(),
+    row<64, 64, float, float, false, false, true, false, true>(),
 };
 #undef FOUR_TILES
 static_assert(sizeof(kKernels) / sizeof(kKernels[0]) == RN_CONV_GEMM_KERNELS, "one rn_ctx::occupancy slot per row");
@@ -1228,7 +1437,7 @@ int dispatch(rn_ctx *ctx, const Contraction &d, const Choice &c, const GemmParam
     const bool chunk = c.chunked && !fp32_partials, dil = p.dil != 1 && !xk;
     for (const KernelRow &r : kKernels) {
         if (r.dt_in != d.dt_in || r.dt_out != dt_out || r.BM != c.BM || r.BN != c.BN || r.dual != dual ||
-            r.xk != xk || r.chunk != chunk || r.dil != dil)
+            r.xk != xk || r.chunk != chunk || r.dil != dil || r.pm != c.pm)
             continue;
         r.launch(ctx, p, c.persistent, &ctx->occupancy[&r - kKernels]);
         return rn_after_launch(ctx, d.what);
@@ -1245,6 +1454,20 @@ int launch_gemm(rn_ctx *ctx, const Contraction &d)
     if (c.family == Choice::STRIP) {
         rn_conv_strip_launch(ctx, p);
         return rn_after_launch(ctx, d.what);
+    }
+    if (c.family == Choice::FOUR_WAVE && ctx->tap_skip != 1) {
+        const TapSkipPlan t = plan_tap_skip(d, p, c.BM, c.BN, ctx->split_k > 1);
+        if (t.eligible && (ctx->tap_skip == 2 || t.rule)) {
+            Choice cp = c;
+            cp.pm = true;
+            RN_REQUIRE(ctx, split_pixel_major(p, d, c.BM, c.BN), "too many tiles");
+            if (c.chunked) p.chunk_L = 2 * (int)rn_ceil_div((uint64_t)p.nk, 16);  // the fold points of split_chunked_tail
+            else p.chunk_L = p.nk;
+            choose_tile_order(ctx, p, p.full_tiles, c.BM, c.BN);
+            RN_TRY(dispatch(ctx, d, cp, p, false));
+            ctx->tap_skip_launches += 1, ctx->tap_skip_k_tiles += t.k_skipped;
+            return RN_OK;
+        }
     }
     RN_REQUIRE(ctx, split_whole_tiles(p, c.BM, c.BN), "too many tiles");
     if (c.family == Choice::WIDE) {
@@ -1517,6 +1740,40 @@ uint64_t rn_conv_output_size_dilated(uint64_t x, uint64_t kernel_size, uint64_t 
     const uint64_t span = dilation * (kernel_size - 1) + 1;  // the dilated kernel's extent
     if (x + 2 * padding < span) return 0;
     return (x + 2 * padding - span) / stride + 1;
+}
+
+int rn_conv_tap_skip_plan(int dtype, uint64_t B, uint64_t in_channels, uint64_t out_channels, uint64_t H, uint64_t W,
+                          uint64_t kernel_size, uint64_t stride, uint64_t padding, uint64_t dilation, int tile,
+                          uint64_t *m_tiles, uint64_t *k_tiles, uint64_t *k_tiles_skipped, int *rule)
+{
+    if (m_tiles) *m_tiles = 0;
+    if (k_tiles) *k_tiles = 0;
+    if (k_tiles_skipped) *k_tiles_skipped = 0;
+    if (rule) *rule = 0;
+    if ((dtype != RN_DTYPE_F32 && dtype != RN_DTYPE_BF16) || tile < 0 || tile > 8 || B == 0 || in_channels == 0 ||
+        out_channels == 0 || kernel_size == 0 || kernel_size > 15 || stride == 0 || dilation == 0)
+        return -1;
+    const uint64_t h_out = rn_conv_output_size_dilated(H, kernel_size, stride, padding, dilation);
+    const uint64_t w_out = rn_conv_output_size_dilated(W, kernel_size, stride, padding, dilation);
+    if (h_out == 0 || w_out == 0) return -1;
+    if (dtype != RN_DTYPE_F32 || in_channels % 32 != 0 ||
+        !gemm_eligible(nullptr, nullptr, nullptr, in_channels, kernel_size, B * H * W * in_channels,
+                       out_channels * kernel_size * kernel_size * in_channels, B * h_out * w_out * out_channels))
+        return 0;  // (bf16, or a shape the fp32 contraction does not take at all)
+    Contraction d{};
+    d.dt_in = d.dt_out = dtype;
+    d.k = kernel_size, d.stride = stride, d.pad = padding, d.dil = kernel_size == 1 ? 1 : dilation;
+    d.h_out = h_out, d.w_out = w_out, d.B = B, d.Cin = in_channels, d.Cout = out_channels, d.H = H, d.W = W;
+    rn_ctx none{};  // describe() reads the debug stamps of a context: none
+    const GemmParams p = describe(&none, d);
+    const Choice c = choose_four_wave(tile, d, p);
+    const TapSkipPlan t = plan_tap_skip(d, p, c.BM, c.BN, false);
+    if (!t.eligible) return 0;
+    if (m_tiles) *m_tiles = t.m_tiles;
+    if (k_tiles) *k_tiles = t.k_tiles;
+    if (k_tiles_skipped) *k_tiles_skipped = t.k_skipped;
+    if (rule) *rule = t.rule ? 1 : 0;
+    return 1;
 }
 
 int rn_conv2d_nhwc_forward(rn_ctx *ctx, const float *inp, float *out, const float *packed_weight,

@@ -35,6 +35,9 @@ struct GemmParams {
     int nk;         // K tiles
     int tiles_n;
     unsigned total_tiles;  // the grid may be smaller: blocks then walk tiles grid-stride
+    // pixel-major launches (PM kernels only, fp32): M tile t = (image block g = t / HoWo, output pixel t % HoWo),
+    // its row r is image g * BM + r at that pixel (output row b * HoWo + pixel as ever), masked when b >= B =
+    // M / HoWo; the K loop walks only the K tiles of the taps that are inside the image at that pixel
     // tile order (rn_conv.hip, conv_gemm_kernel): the tiles the remap covers are dealt to the 8 XCDs as
     // contiguous ranges of an ORDER; xg = 0: the order is the logical one (M panel major, the N tiles of a
     // panel adjacent: an XCD reads its A panels once and streams the whole weight panel);  xg > 0: the order

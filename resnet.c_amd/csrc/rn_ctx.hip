@@ -215,6 +215,10 @@ int rn_ctx_create(rn_ctx **out, int device, void *hip_stream)
         const int v = atoi(nt);
         if (v >= 0 && v <= 2) ctx->nchw_taps = v;
     }
+    if (const char *ts = getenv("RN_TAP_SKIP")) {  // A/B runs of the pixel-major tiles (tools/layer_report.py)
+        const int v = atoi(ts);
+        if (v >= 0 && v <= 2) ctx->tap_skip = v;
+    }
     if (hip_stream) {
         ctx->stream = (hipStream_t)hip_stream;
         ctx->own_stream = false;
@@ -283,6 +287,7 @@ int rn_conv_tile_candidates(void) { return 8 + rn_conv_wide_count() + 1; }  // +
 
 // library-internal, declared in rn_private.h (rn_model.c is plain C and sees the context only through functions)
 int rn_ctx_graphs_live(const rn_ctx *ctx) { return ctx ? ctx->graphs_live : 0; }
+int rn_ctx_tap_skip_mode(const rn_ctx *ctx) { return ctx ? ctx->tap_skip : 0; }
 int rn_ctx_scratch_slot(rn_ctx *ctx, int slot, uint64_t bytes, void **ptr)
 {
     if (!ctx || !ptr) return RN_ERR_INVALID;
@@ -332,6 +337,23 @@ int rn_ctx_set_nchw_taps(rn_ctx *ctx, int mode)
     if (!ctx) return RN_ERR_INVALID;
     if (mode < 0 || mode > 2) return rn_set_error(ctx, RN_ERR_INVALID, "nchw taps mode %d: 0 (never), 1 (large planes) or 2 (always)", mode);
     ctx->nchw_taps = mode;
+    return RN_OK;
+}
+
+int rn_ctx_set_tap_skip(rn_ctx *ctx, int mode)
+{
+    if (!ctx) return RN_ERR_INVALID;
+    if (mode < 0 || mode > 2)
+        return rn_set_error(ctx, RN_ERR_INVALID, "tap skip mode %d: 0 (the library's rule), 1 (never) or 2 (wherever eligible)", mode);
+    ctx->tap_skip = mode;
+    return RN_OK;
+}
+
+int rn_ctx_tap_skip_stats(const rn_ctx *ctx, uint64_t *launches, uint64_t *k_tiles_skipped)
+{
+    if (!ctx) return RN_ERR_INVALID;
+    if (launches) *launches = ctx->tap_skip_launches;
+    if (k_tiles_skipped) *k_tiles_skipped = ctx->tap_skip_k_tiles;
     return RN_OK;
 }
 

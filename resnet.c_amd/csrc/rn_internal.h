@@ -14,7 +14,7 @@ struct rn_wcache_entry {
     void *packed;
 };
 
-#define RN_CONV_GEMM_KERNELS 52  // instantiations of conv_gemm_kernel (rn_conv.hip checks the count)
+#define RN_CONV_GEMM_KERNELS 59  // instantiations of conv_gemm_kernel (rn_conv.hip checks the count)
 
 struct rn_ctx {
     int device;
@@ -29,6 +29,8 @@ struct rn_ctx {
     int stem_items; // fused stem: items (four stem rows) a block walks; 0 = chosen per launch
     int nchw_taps;  // k x k convolutions on NCHW tensors without the input transpose: 0 never, 1 large planes, 2 always
     int xcd_groups; // N-tile groups the contraction's tiles are dealt to the XCDs in; 0 = chosen per launch
+    int tap_skip;   // pixel-major tiles that skip the padding taps (fp32 k x k): 0 = the library's rule, 1 never, 2 wherever eligible
+    uint64_t tap_skip_launches, tap_skip_k_tiles;  // pixel-major launches issued, and the K tiles they left out
     void *debug_stamps;  // diagnostic phase stamps of the contraction kernel, normally null
     // scratch grown on demand (never inside a graph capture; callers that capture
     // warm up first so the sizes are already settled)

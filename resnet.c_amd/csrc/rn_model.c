@@ -1541,7 +1541,10 @@ static int forward_chunk(rn_model *m, const void *input, int in_u8, uint64_t B, 
     for (i = 0; i < parts; ++i) {
         const uint64_t hi = B * (uint64_t)(i + 1) / (uint64_t)parts;
         rn_ctx *run = i == 0 ? m->ctx : m->ctxn[i - 1];
-        if (i > 0) TRY(rn_ctx_wait_event(run, m->ev_fork));
+        if (i > 0) {
+            TRY(rn_ctx_set_tap_skip(run, rn_ctx_tap_skip_mode(m->ctx))); /* the caller's choice holds on every stream */
+            TRY(rn_ctx_wait_event(run, m->ev_fork));
+        }
         TRY(forward_part(m, run, lo, input_at(m, input, in_u8, lo), in_u8, hi - lo, logits + lo * m->classes,
                          mode));
         if (i > 0) TRY(rn_event_record(run, m->ev_join[i - 1]));

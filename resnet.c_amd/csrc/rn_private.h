@@ -14,6 +14,8 @@ extern "C" {
 
 /* ---- rn_ctx.hip: rn_model.c is plain C and sees the context only through functions ---- */
 int rn_ctx_graphs_live(const rn_ctx *ctx);
+/* rn_ctx_set_tap_skip's mode of a context (the model gives it to the contexts of its other streams) */
+int rn_ctx_tap_skip_mode(const rn_ctx *ctx);
 /* everything queued on ctx's stream after this call waits for the event (the stream, not the host) */
 int rn_ctx_wait_event(rn_ctx *ctx, rn_event *ev);
 int rn_ctx_scratch_slot(rn_ctx *ctx, int slot, uint64_t bytes, void **ptr);

@@ -96,6 +96,19 @@ class Context:
         the route, never a bit."""
         L.check(L.lib().rn_ctx_set_nchw_taps(self.handle, int(mode)), "rn_ctx_set_nchw_taps", self.handle)
 
+    def set_tap_skip(self, mode: int) -> None:
+        """fp32 k x k convolutions with padding on pixel-major tiles that skip the padding taps: 0 = the library's
+        rule, 1 = never, 2 = wherever eligible (rn_ctx_set_tap_skip).  Changes the schedule, never a bit of a finite
+        result."""
+        L.check(L.lib().rn_ctx_set_tap_skip(self.handle, int(mode)), "rn_ctx_set_tap_skip", self.handle)
+
+    def tap_skip_stats(self) -> dict:
+        """Pixel-major launches issued through this context and the K tiles they left out."""
+        import ctypes
+        n, k = ctypes.c_uint64(), ctypes.c_uint64()
+        L.check(L.lib().rn_ctx_tap_skip_stats(self.handle, ctypes.byref(n), ctypes.byref(k)), "rn_ctx_tap_skip_stats")
+        return {"launches": int(n.value), "k_tiles_skipped": int(k.value)}
+
     def set_weight_cache(self, on: bool) -> None:
         """rn_conv2d_forward (OIHW weights) packs each weight buffer once instead of per call."""
         L.check(L.lib().rn_ctx_set_weight_cache(self.handle, int(on)), "rn_ctx_set_weight_cache")

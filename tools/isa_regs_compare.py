@@ -34,6 +34,9 @@ def strip_dil(k):
     # this tree's undilated instantiation of a kernel that gained the DIL flag -> the parent's name
     k2 = re.sub(r"(conv_gemm_kernelI.*?Lb[01]ELb[01]ELb[01]E)Lb0E(EEvN7rn_gemm)", r"\1\2", k)
     k2 = k2.replace("conv_group_kernelILb0EEEvNS_11GroupParamsE", "conv_group_kernelENS_11GroupParamsE")
+    # ... or the trailing PM = false flag (the parent then has four flags)
+    if k2 == k:
+        k2 = re.sub(r"(conv_gemm_kernelI.*?(?:Lb[01]E){4})Lb0E(EEvN7rn_gemm)", r"\1\2", k)
     return k2
 parent_dir, this_dir, files = sys.argv[1], sys.argv[2], sys.argv[3:]
 bad = 0
