@@ -61,7 +61,9 @@
  * cores, the price of a slice nobody has measured on network-sized layers -- as soon as ONE of
  * them is off a 16-byte boundary: a parameter arena that packs scale / shift vectors back to back
  * wants channel counts that are multiples of 4.  rn_nchw_to_nhwc_pad_dt(BF16) takes a dst on any
- * 2-byte boundary.
+ * 2-byte boundary.  rn_nhwc_to_nchw_dt takes a dst on any 4-byte boundary in both element types and keeps
+ * its 16-byte stores there (only its src decides between the fast and the element-wise form); so do the
+ * stage maps of rn_model_forward_maps, which are its dst.
  * The grouped convolution (rn_conv2d_grouped_forward, rn_conv2d_grouped_nhwc_forward_dt in fp32) follows the
  * same rule: matrix cores with every operand on a 16-byte boundary, the direct kernel in the reference's
  * summation order otherwise; its bf16 form is rn_conv2d_nhwc_forward_dt(BF16) and refuses like it.
@@ -327,6 +329,17 @@ RN_API int rn_nchw_to_nhwc(rn_ctx *ctx, const float *src, float *dst, uint64_t B
                            uint64_t H, uint64_t W);
 RN_API int rn_nhwc_to_nchw(rn_ctx *ctx, const float *src, float *dst, uint64_t B, uint64_t C,
                            uint64_t H, uint64_t W);
+/* NHWC [B,H,W,C] of `dtype` (RN_DTYPE_F32 or RN_DTYPE_BF16) -> NCHW [B,C,H,W] fp32; bf16 is widened exactly (its
+ * bits shifted left by 16).  The form a model hands its stage maps out in (rn_model_forward_maps).  Any C, H, W
+ * >= 1 (each, and H * W, below 2^31) and any B (more than 65535 images run as several launches); offsets are 64-bit
+ * per image, so a dst of more than 2^31 bytes is legal.  dst_nchw on any 4-byte boundary, src_nhwc aligned to its
+ * element (RN_ERR_INVALID otherwise, rn_last_error names the operand); asynchronous on the context's stream.
+ * Fast form -- C % 4 == 0 (bf16: % 8) and src_nhwc on a 16-byte boundary, what a model's tensors always meet:
+ * 16-byte loads along C, a padded LDS tile, 16-byte stores along H * W wherever four consecutive outputs share an
+ * aligned 16 bytes of dst, whatever H * W and dst's address are (a 7 x 7 map: a block's 32 or 64 channels are one
+ * contiguous span of dst with a scalar head and tail).  Any other shape: one element per thread, the same bits. */
+RN_API int rn_nhwc_to_nchw_dt(rn_ctx *ctx, int dtype, const void *src_nhwc, float *dst_nchw, uint64_t B,
+                              uint64_t C, uint64_t H, uint64_t W);
 /* channels of the engine-side input image for a convolution: in_channels, or 4 when
  * in_channels < 4 (the 3-channel stem reads a [B,H,W,4] zero-padded image). */
 RN_API uint64_t rn_conv2d_input_channels(uint64_t in_channels);
@@ -721,6 +734,32 @@ RN_API int rn_model_forward_outputs(rn_model *m, const float *input_nchw, uint64
                                     const rn_model_outputs *outs, int mode);
 RN_API int rn_model_forward_outputs_u8(rn_model *m, const uint8_t *input_nhwc, uint64_t B,
                                        const rn_model_outputs *outs, int mode);
+/* The feature maps behind layer1..layer4 from one forward, each [B, C, H, W] fp32 in the caller's device buffer
+ * (torchvision's IntermediateLayerGetter; the backbone form DeepLab / FCN / FPN read).  NULL = not wanted. */
+typedef struct rn_model_maps { float *layer[4]; } rn_model_maps;   /* layer1..layer4; NULL = not wanted */
+/* C, H, W of the map behind stage 1..4 for the model's architecture, input size and dilation flags (ResNet-50 at
+ * 224 x 224: 256 x 56 x 56 .. 2048 x 7 x 7; with (0,1,1) layer3 and layer4 at 28 x 28; ResNet-18: 64 .. 512
+ * channels).  Legal before rn_model_finalize; any of the pointers may be NULL; stage outside 1..4: RN_ERR_INVALID. */
+RN_API int rn_model_stage_shape(const rn_model *m, int stage /* 1..4 */, uint64_t *C, uint64_t *H, uint64_t *W);
+/* Exactly the launches of rn_model_forward_outputs -- same sub-batches, parts, front slices and profile records,
+ * the same bits in every head output -- plus one rn_nhwc_to_nchw_dt per wanted stage and launch batch (op
+ * "stage_map", layer "layer1".."layer4" in the profile; bf16 models: the stored values widened exactly).  The
+ * export is queued right behind the last block of its stage on the stream that block ran on, where the stage's
+ * output still sits in its ping-pong arena (two blocks later it is overwritten); the parts' streams are joined
+ * before the call's work on the model's stream ends, as for the logits.  outs may be NULL (or name nothing): the
+ * logits then go to the buffer the model owns, as with outs->logits == NULL.  Both forward modes, every
+ * architecture, input size and dilation.  No new arenas: rn_model_activation_bytes, rn_model_max_sub_batch and the
+ * tuning table are what they were.  The request lives for this call only: no later forward, tune, capture or
+ * pipeline submit exports anything.
+ * Refused, nothing launched, nothing changed: maps == NULL, or all four stages NULL and nothing wanted in outs
+ * (RN_ERR_INVALID, "nothing to write"); a stage pointer off a 4-byte boundary (RN_ERR_INVALID, rn_last_error names
+ * the stage); a model that is not finalized, a bad mode, a bad top-k request (RN_ERR_INVALID); a bf16 model with
+ * RN_FWD_REFERENCE_OPS (RN_ERR_UNSUPPORTED).  rn_model_capture, the pipelines and rn_shard_* carry no maps, and a
+ * backbone-only forward still runs the head. */
+RN_API int rn_model_forward_maps(rn_model *m, const float *input_nchw, uint64_t B, const rn_model_outputs *outs,
+                                 const rn_model_maps *maps, int mode);
+RN_API int rn_model_forward_maps_u8(rn_model *m, const uint8_t *input_nhwc, uint64_t B, const rn_model_outputs *outs,
+                                    const rn_model_maps *maps, int mode);
 /* Run one forward, then time every tile candidate of every convolution at batch B on the
  * device (events on the context's stream, on the buffers that forward used) and remember the fastest per layer for
  * that batch size.  Results do not change (candidates are bit-identical), only speed. */

@@ -36,6 +36,11 @@ class ModelOutputs(ctypes.Structure):
                 ("topk_idx", c_void_p), ("k", c_uint64)]
 
 
+class ModelMaps(ctypes.Structure):
+    """rn_model_maps: device pointers of the [B,C,H,W] fp32 maps behind layer1..layer4; NULL = not wanted."""
+    _fields_ = [("layer", c_void_p * 4)]
+
+
 class Epilogue(ctypes.Structure):
     _fields_ = [("scale", c_void_p), ("shift", c_void_p), ("residual", c_void_p),
                 ("relu", c_int)]
@@ -99,6 +104,7 @@ SIGNATURES = {
     "rn_softmax_topk_forward": (c_int, [c_void_p, fptr, fptr, fptr, c_void_p, u64, u64, u64]),
     "rn_nchw_to_nhwc": (c_int, [c_void_p, fptr, fptr] + [u64] * 4),
     "rn_nhwc_to_nchw": (c_int, [c_void_p, fptr, fptr] + [u64] * 4),
+    "rn_nhwc_to_nchw_dt": (c_int, [c_void_p, c_int, fptr, fptr] + [u64] * 4),
     "rn_conv2d_input_channels": (u64, [u64]),
     "rn_nchw_to_nhwc_pad": (c_int, [c_void_p, fptr, fptr] + [u64] * 5),
     "rn_conv2d_packed_weight_numel": (u64, [u64, u64, u64]),
@@ -170,6 +176,9 @@ SIGNATURES = {
     "rn_model_features": (u64, [c_void_p]),
     "rn_model_forward_outputs": (c_int, [c_void_p, fptr, u64, POINTER(ModelOutputs), c_int]),
     "rn_model_forward_outputs_u8": (c_int, [c_void_p, c_void_p, u64, POINTER(ModelOutputs), c_int]),
+    "rn_model_stage_shape": (c_int, [c_void_p, c_int, POINTER(u64), POINTER(u64), POINTER(u64)]),
+    "rn_model_forward_maps": (c_int, [c_void_p, fptr, u64, POINTER(ModelOutputs), POINTER(ModelMaps), c_int]),
+    "rn_model_forward_maps_u8": (c_int, [c_void_p, c_void_p, u64, POINTER(ModelOutputs), POINTER(ModelMaps), c_int]),
     "rn_model_destroy": (c_int, [c_void_p]),
     "rn_model_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, u64]),
     "rn_model_load_dir": (c_int, [c_void_p, c_char_p]),

@@ -5,13 +5,16 @@
  * B = 1, paths); here the same defaults can be overridden from the command line.
  *
  *   rn_infer [--arch 18|34|50|101|152|resnext50_32x4d|resnext101_32x8d|resnext101_64x4d|wide_resnet50_2|wide_resnet101_2] [--weights DIR] [--input FILE | --u8 FILE | --rgb FILE --hw H,W] [--batch B]
- *            [--size H,W] [--dilate a,b,c] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,c,...]
+ *            [--size H,W] [--dilate a,b,c] [--maps PREFIX] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,c,...]
  *
  * --size H,W sets the model's input size (rn_model_set_input_size; default 224,224; single device only):
  * --input then holds B x 3 x H x W floats and --u8 B x H x W x 3 bytes, and a file of any other length is
  * refused with the size in the message.
  * --dilate a,b,c (each 0 or 1) is torchvision's replace_stride_with_dilation for layer2, layer3, layer4
  * (rn_model_set_dilation; bottleneck networks, single device only): the same weights at output stride 16, 8 or 4.
+ * --maps PREFIX also writes the feature maps behind layer1..layer4 of the batch it ran, from the same forward
+ * (rn_model_forward_maps): PREFIX.layer1.bin .. PREFIX.layer4.bin, each [B,C,H,W] fp32 (rn_save_f32_file; the
+ * shapes are rn_model_stage_shape's).  Single device, not with --rgb; the lines printed are unchanged.
  * --u8 FILE reads B x 150528 raw bytes, the decoder's 8-bit RGB crops ([B,224,224,3]), instead of
  * the preprocessed fp32 file: the device normalises them (rn_model_forward_u8), same lines out.
  * --rgb FILE --hw H,W reads the H x W x 3 raw bytes of ONE decoded image of any size: the device resizes
@@ -143,6 +146,8 @@ int main(int argc, char **argv)
     int dilate[3] = {0, 0, 0}; /* --dilate */
     const char *weights = "weights_bin";
     const char *input = "test_bins/ILSVRC2012_val_00004749.bin";
+    const char *maps_prefix = NULL; /* --maps */
+    rn_model_maps maps = {{NULL, NULL, NULL, NULL}};
     rn_ctx *ctx = NULL;
     rn_model *model = NULL;
     float *inp = NULL, *logits = NULL;
@@ -177,6 +182,7 @@ int main(int argc, char **argv)
             if (sscanf(v, "%d,%d,%d", &dilate[0], &dilate[1], &dilate[2]) != 3) dilate[0] = -1; /* refused below */
             ++i;
         }
+        else if (!strcmp(a, "--maps") && v) { maps_prefix = v; ++i; }
         else if (!strcmp(a, "--batch") && v) { B = strtoull(v, NULL, 10); ++i; }
         else if (!strcmp(a, "--classes") && v) { classes = strtoull(v, NULL, 10); ++i; }
         else if (!strcmp(a, "--topk") && v) { topk = strtoull(v, NULL, 10); ++i; }
@@ -192,7 +198,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--mode") && v) { mode = strcmp(v, "ops") ? RN_FWD_FUSED : RN_FWD_REFERENCE_OPS; ++i; }
         else {
             fprintf(stderr, "usage: %s [--arch 18|34|50|101|152|resnext50_32x4d|resnext101_32x8d|resnext101_64x4d|wide_resnet50_2|wide_resnet101_2] [--weights DIR] [--input FILE | --u8 FILE | --rgb FILE --hw H,W] "
-                            "[--batch B] [--size H,W] [--dilate a,b,c] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,...] [--classes N] [--topk K]\n",
+                            "[--batch B] [--size H,W] [--dilate a,b,c] [--maps PREFIX] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,...] [--classes N] [--topk K]\n",
                     argv[0]);
             return 2;
         }
@@ -216,6 +222,10 @@ int main(int argc, char **argv)
     if ((dilate[0] || dilate[1] || dilate[2]) && ndev > 0) {
         fprintf(stderr, "rn_infer: %s: --dilate runs on one device (the shards stay undilated)\n",
                 rn_status_string(RN_ERR_UNSUPPORTED));
+        return 1;
+    }
+    if (maps_prefix && (ndev > 0 || rgb)) {
+        fprintf(stderr, "rn_infer: %s: --maps runs on one device and not with --rgb\n", rn_status_string(RN_ERR_UNSUPPORTED));
         return 1;
     }
     if (ndev > 0) return run_sharded(devices, ndev, arch, weights, input, u8, B, mode, dtype);
@@ -277,6 +287,27 @@ int main(int argc, char **argv)
     if (rgb) {
         const uint64_t zero = 0;
         CHECK(ctx, rn_model_forward_images_u8(model, inp_u8, &zero, &rgb_h, &rgb_w, 1, logits, mode));
+    } else if (maps_prefix) { /* the same forward, and the four stage maps out of it */
+        rn_model_outputs outs;
+        int s;
+        memset(&outs, 0, sizeof(outs));
+        outs.logits = logits;
+        for (s = 0; s < 4; ++s) {
+            uint64_t C = 0, H = 0, W = 0;
+            CHECK(ctx, rn_model_stage_shape(model, s + 1, &C, &H, &W));
+            CHECK(ctx, rn_malloc(ctx, (void **)&maps.layer[s], B * C * H * W * sizeof(float)));
+        }
+        if (u8)
+            CHECK(ctx, rn_model_forward_maps_u8(model, inp_u8, B, &outs, &maps, mode));
+        else
+            CHECK(ctx, rn_model_forward_maps(model, inp, B, &outs, &maps, mode));
+        for (s = 0; s < 4; ++s) {
+            uint64_t C = 0, H = 0, W = 0;
+            char path[1024];
+            CHECK(ctx, rn_model_stage_shape(model, s + 1, &C, &H, &W));
+            snprintf(path, sizeof(path), "%s.layer%d.bin", maps_prefix, s + 1);
+            CHECK(ctx, rn_save_f32_file(ctx, path, maps.layer[s], B * C * H * W));
+        }
     } else if (u8)
         CHECK(ctx, rn_model_forward_u8(model, inp_u8, B, logits, mode));
     else
@@ -312,6 +343,7 @@ int main(int argc, char **argv)
     rn_free(ctx, logits);
     rn_free(ctx, inp);
     rn_free(ctx, inp_u8);
+    for (i = 0; i < 4; ++i) rn_free(ctx, maps.layer[i]);
     rn_model_destroy(model);
     rn_ctx_destroy(ctx);
     return 0;

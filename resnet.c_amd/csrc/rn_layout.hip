@@ -288,6 +288,123 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc4_border_bf16_kernel(
     dst[b * n2 + i] = __builtin_bit_cast(uint4, v);
 }
 
+// ---- NHWC (fp32 or bf16) -> NCHW fp32: the stage maps a model hands out (rn_nhwc_to_nchw_dt) -------------
+// One block: kMapPix pixels x CT channels of one image, CT = 8 lanes of 16 bytes along C (32 fp32 / 64 bf16
+// channels: 128 bytes of every pixel row).  Load: 16 bytes per lane along C into an LDS tile; store: along HW,
+// 16 bytes per lane wherever four consecutive floats of dst sit in one 16-byte-aligned quad, whatever H*W and
+// the address of dst are.  An image's [C][HW] output is one contiguous run, so
+//   WHOLE (H*W <= kMapWhole): the block takes all pixels, its CT x HW outputs are ONE span of dst: aligned quads
+//     across the channel boundaries, scalar stores only for the span's head and tail (7 x 7: 392 quads and at most
+//     6 scalars; 14 x 14: 25 KB written as one run);
+//   otherwise: one span of up to kMapPix floats per channel, each with its own scalar head and tail (none where
+//     H*W % 4 == 0 and dst is 16-byte aligned).
+// LDS element (pixel p, channel c) at (p >> 2) * P + (p & 3) * R + c with R = CT + 1 and P = 3 R + CT (odd):
+// the dword writes of a loaded 16 bytes (lanes: 8 channel chunks x 4 pixels of a group) and the dword reads
+// behind a stored quad (lanes: consecutive groups of one channel) both spread over the 32 banks (bf16 writes:
+// two lanes per bank).  The tile is dynamic LDS, sized by the pixels the block takes: at most kMapWhole / 4 groups of
+// P floats, 29 KB (fp32) or 58 KB (bf16), 8.4 / 16.6 KB for a 64-pixel chunk.
+constexpr int kMapPix = 64;
+constexpr int kMapWhole = 224;
+
+__device__ inline void map_unpack(const uint4 v, float (&f)[4])
+{
+    f[0] = __uint_as_float(v.x), f[1] = __uint_as_float(v.y), f[2] = __uint_as_float(v.z), f[3] = __uint_as_float(v.w);
+}
+
+__device__ inline void map_unpack(const uint4 v, float (&f)[8])  // bf16 widened exactly: bits << 16
+{
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        f[2 * i] = __uint_as_float(w[i] << 16);
+        f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+    }
+}
+
+template <typename T, bool WHOLE, int PASSES>  // PASSES * 32 pixels at most: 2 (a chunk, a small map) or 7
+__global__ __launch_bounds__(256) void nhwc_to_nchw_map_kernel(const T *__restrict__ src, float *__restrict__ dst,
+                                                               uint32_t C, uint32_t HW, uint32_t mul_n, uint32_t shr_n)
+{
+    constexpr int V = 16 / sizeof(T), CT = 8 * V, R = CT + 1, P = 3 * R + CT;
+    constexpr uint32_t QS = kMapPix / 4 + 1;  // quads a channel's span of kMapPix floats can touch
+    extern __shared__ float tile[];  // ((pixels of the block + 3) / 4) * P floats
+    constexpr uint32_t kCap = 32 * PASSES;
+    const uint64_t img = blockIdx.z;
+    const uint32_t p0 = blockIdx.x * kMapPix, c0 = blockIdx.y * CT;
+    const uint32_t n = HW - p0 < kCap ? HW - p0 : kCap;
+    const uint32_t nc = C - c0 < (uint32_t)CT ? C - c0 : (uint32_t)CT;
+    {
+        const uint32_t cl = (threadIdx.x & 7) * V, pr = threadIdx.x >> 3;
+        const bool ok = cl < nc;  // C % V == 0: a chunk is inside or outside as a whole
+        const T *s = src + (img * HW + p0) * C + c0 + (ok ? cl : 0);
+        // every load of the thread is issued before the first LDS write: rows past the tile re-read its last row
+        // (always inside the tensor) and are dropped
+        uint4 v[PASSES];
+#pragma unroll
+        for (int i = 0; i < PASSES; ++i) {
+            const uint32_t lp = pr + 32 * i;
+            v[i] = *reinterpret_cast<const uint4 *>(s + (uint64_t)(lp < n ? lp : n - 1) * C);
+        }
+#pragma unroll
+        for (int i = 0; i < PASSES; ++i) {
+            const uint32_t lp = pr + 32 * i;
+            if (lp < n && ok) {
+                float f[V];
+                map_unpack(v[i], f);
+                float *t = &tile[(lp >> 2) * P + (lp & 3) * R + cl];
+#pragma unroll
+                for (int e = 0; e < V; ++e) t[e] = f[e];
+            }
+        }
+    }
+    __syncthreads();
+    float *out = dst + img * C * HW + (uint64_t)c0 * HW + p0;  // (channel c0, pixel p0) of the image
+    const uint32_t items = WHOLE ? (nc * n + 3) / 4 + 1 : nc * QS;
+    for (uint32_t w = threadIdx.x; w < items; w += 256) {
+        const uint32_t span = WHOLE ? 0 : w / QS, q = WHOLE ? w : w - span * QS;
+        const uint32_t len = WHOLE ? nc * n : n;
+        float *run = out + (uint64_t)span * HW;
+        const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(run) >> 2) & 3;  // floats behind the aligned quad
+        const uint32_t t0 = 4 * q - sh;  // wraps below 0: those elements are outside the span
+        float v[4];
+        bool in[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const uint32_t t = t0 + e;
+            in[e] = t < len;
+            uint32_t lc = span, lp = t;
+            if (WHOLE) {
+                lc = n == 1 ? t : __umulhi(t, mul_n) >> shr_n;
+                lp = t - lc * n;
+            }
+            v[e] = in[e] ? tile[(lp >> 2) * P + (lp & 3) * R + lc] : 0.f;
+        }
+        if (in[0] && in[3]) {  // the whole quad is inside: run + t0 is 16-byte aligned by construction
+            *reinterpret_cast<float4 *>(run + t0) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (in[e]) run[(uint32_t)(t0 + e)] = v[e];
+        }
+    }
+}
+
+// any other shape or alignment: one output element per thread and step, merely correct
+template <typename T>
+__global__ __launch_bounds__(256) void nhwc_to_nchw_elem_kernel(const T *__restrict__ src, float *__restrict__ dst,
+                                                                uint64_t C, uint64_t HW, uint64_t total)
+{
+    const uint64_t gstride = (uint64_t)gridDim.x * 256;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += gstride) {
+        const uint64_t p = i % HW, r = i / HW, c = r % C, b = r / C;
+        const uint64_t at = (b * HW + p) * C + c;
+        if (sizeof(T) == 2)
+            dst[i] = __uint_as_float((uint32_t)reinterpret_cast<const uint16_t *>(src)[at] << 16);
+        else
+            dst[i] = reinterpret_cast<const float *>(src)[at];
+    }
+}
+
 void magic_div(uint32_t d, uint32_t *mul, uint32_t *shr)
 {
     uint32_t lg = 0;
@@ -295,6 +412,30 @@ void magic_div(uint32_t d, uint32_t *mul, uint32_t *shr)
     const uint32_t p = 31 + lg;
     *mul = (uint32_t)(((1ull << p) + d - 1) / d);
     *shr = p - 32;
+}
+
+template <typename T>
+void map_launch(rn_ctx *ctx, const T *src, float *dst, uint64_t B, uint64_t C, uint64_t HW)
+{
+    constexpr uint64_t CT = 8 * (16 / sizeof(T));
+    const bool whole = HW <= (uint64_t)kMapWhole;
+    const uint64_t pix = whole ? HW : (HW < (uint64_t)kMapPix ? HW : (uint64_t)kMapPix);
+    const size_t lds = (size_t)((pix + 3) / 4) * (3 * (CT + 1) + CT) * sizeof(float);
+    uint32_t mul = 0, shr = 0;
+    if (whole && HW > 1) magic_div((uint32_t)HW, &mul, &shr);
+    // gridDim.z is limited to 65535: walk the batch in slabs
+    for (uint64_t b0 = 0; b0 < B; b0 += 65535) {
+        const uint64_t nb = (B - b0) < 65535 ? (B - b0) : 65535;
+        dim3 grid(whole ? 1u : (unsigned)rn_ceil_div(HW, kMapPix), (unsigned)rn_ceil_div(C, CT), (unsigned)nb);
+        const T *s = src + b0 * C * HW;
+        float *d = dst + b0 * C * HW;
+        if (whole && HW <= (uint64_t)kMapPix)
+            nhwc_to_nchw_map_kernel<T, true, kMapPix / 32><<<grid, 256, lds, ctx->stream>>>(s, d, (uint32_t)C, (uint32_t)HW, mul, shr);
+        else if (whole)
+            nhwc_to_nchw_map_kernel<T, true, kMapWhole / 32><<<grid, 256, lds, ctx->stream>>>(s, d, (uint32_t)C, (uint32_t)HW, mul, shr);
+        else
+            nhwc_to_nchw_map_kernel<T, false, kMapPix / 32><<<grid, 256, lds, ctx->stream>>>(s, d, (uint32_t)C, (uint32_t)HW, mul, shr);
+    }
 }
 
 }  // namespace
@@ -512,6 +653,37 @@ int rn_nhwc_to_nchw(rn_ctx *ctx, const float *src, float *dst, uint64_t B, uint6
 {
     RN_ENTER(ctx);
     return transpose_launch(ctx, src, dst, B, H * W, C, "rn_nhwc_to_nchw");
+}
+
+int rn_nhwc_to_nchw_dt(rn_ctx *ctx, int dtype, const void *src_nhwc, float *dst_nchw, uint64_t B, uint64_t C,
+                       uint64_t H, uint64_t W)
+{
+    RN_ENTER(ctx);
+    RN_REQUIRE(ctx, dtype == RN_DTYPE_F32 || dtype == RN_DTYPE_BF16, "unknown dtype");
+    RN_REQUIRE(ctx, H < (1ull << 31) && W < (1ull << 31) && H * W < (1ull << 31) && C < (1ull << 31),
+               "dimension too large");
+    const uint64_t HW = H * W, es = dtype == RN_DTYPE_BF16 ? 2 : 4;
+    if (B * C * HW == 0) return RN_OK;
+    const uintptr_t sa = reinterpret_cast<uintptr_t>(src_nhwc), da = reinterpret_cast<uintptr_t>(dst_nchw);
+    RN_REQUIRE(ctx, src_nhwc && dst_nchw && src_nhwc != (const void *)dst_nchw, "null or aliased tensor");
+    RN_REQUIRE(ctx, (da & 3) == 0, "dst_nchw must be 4-byte aligned");
+    RN_REQUIRE(ctx, (sa & (es - 1)) == 0, "src_nhwc must be aligned to its element");
+    const uint64_t V = 16 / es;
+    if (C % V == 0 && (sa & 15) == 0 && rn_ceil_div(C, 8 * V) <= 65535) {
+        if (dtype == RN_DTYPE_BF16)
+            map_launch(ctx, (const bf16_t *)src_nhwc, dst_nchw, B, C, HW);
+        else
+            map_launch(ctx, (const float *)src_nhwc, dst_nchw, B, C, HW);
+    } else {
+        const uint64_t total = B * C * HW;
+        if (dtype == RN_DTYPE_BF16)
+            nhwc_to_nchw_elem_kernel<bf16_t><<<rn_stream_grid(total, 256), 256, 0, ctx->stream>>>(
+                (const bf16_t *)src_nhwc, dst_nchw, C, HW, total);
+        else
+            nhwc_to_nchw_elem_kernel<float><<<rn_stream_grid(total, 256), 256, 0, ctx->stream>>>(
+                (const float *)src_nhwc, dst_nchw, C, HW, total);
+    }
+    return rn_after_launch(ctx, "rn_nhwc_to_nchw_dt");
 }
 
 int rn_nchw_to_nhwc_pad(rn_ctx *ctx, const float *src, float *dst, uint64_t B, uint64_t C,

@@ -105,6 +105,7 @@ typedef struct {
     int mode;
     int t1_ready; /* the previous block's chained launch has produced this block's conv1 output */
     float *x4, *p0, *p1, *dsb, *t1, *t2, *pooled; /* views into the arenas */
+    uint64_t img0; /* the caller's index of this launch's first image: sub-batch + part + front slice (stage maps) */
 } rn_run;
 
 /* What a pipeline keeps of its model after the model may be gone: freed by whoever leaves last. */
@@ -170,6 +171,10 @@ struct rn_model {
      * network then runs on the whole batch.  1 = off. */
     int front_parts;
     rn_run run;
+    /* rn_model_forward_maps: the stage maps wanted by the call that is running (NULL in every other forward), and
+     * the caller's index of the first image of the sub-batch being queued */
+    const rn_model_maps *maps;
+    uint64_t maps_done;
     /* tile tuning: calls of the last forward, and the batch size the tiles were tuned for */
     rn_conv_call *calls;
     int n_calls, cap_calls, recording;
@@ -561,6 +566,25 @@ int rn_model_input_size(const rn_model *m, uint64_t *H, uint64_t *W)
 }
 
 uint64_t rn_model_max_sub_batch(const rn_model *m) { return m ? m->max_sub : 0; }
+
+/* the map behind stage 1..4: the stage's stride (1 where it is dilated) on the map before it, as set_geometry */
+int rn_model_stage_shape(const rn_model *m, int stage, uint64_t *C, uint64_t *H, uint64_t *W)
+{
+    uint64_t h, w;
+    int li;
+    if (!m || stage < 1 || stage > 4) return RN_ERR_INVALID;
+    h = m->pool_h;
+    w = m->pool_w;
+    for (li = 0; li < stage; ++li) {
+        const uint64_t stride = li > 0 && m->dilate[li - 1] ? 1 : kStrides[li];
+        h = rn_conv_output_size(h, 1, stride, 0);
+        w = rn_conv_output_size(w, 1, stride, 0);
+    }
+    if (C) *C = m->basic ? kBasicWidths[stage - 1] : kWidths[stage - 1][2];
+    if (H) *H = h;
+    if (W) *W = w;
+    return RN_OK;
+}
 
 static void free_prof(rn_model *m)
 {
@@ -1388,12 +1412,29 @@ static int run_front(rn_model *m, const void *input, int in_u8, uint64_t B, int 
 /* block i reads ping-pong arena i & 1 and writes the other */
 static float *block_input(const rn_model *m, int i) { return (i & 1) ? m->run.p1 : m->run.p0; }
 
-/* blocks [first, last) on an *H x *W map, which become those of block last's input */
+/* rn_model_forward_maps: stage li + 1's output x [B,H,W,C] of this launch -> the caller's NCHW fp32 map, from the
+ * caller's image run.img0 on.  Queued right behind the stage's last block on that block's stream: two blocks
+ * later the same stream overwrites the arena x lives in. */
+static int op_stage_map(rn_model *m, int li, const float *x, uint64_t B, uint64_t H, uint64_t W)
+{
+    const uint64_t C = m->basic ? kBasicWidths[li] : kWidths[li][2];
+    char layer[RN_MAX_KEY];
+    snprintf(layer, sizeof(layer), "layer%d", li + 1);
+    TRY(prof_begin(m, "stage_map", layer, 0.0, (double)(B * C * H * W) * (double)(elem_size(m) + 4)));
+    TRY(rn_nhwc_to_nchw_dt(m->run.ctx, m->dtype, x, m->maps->layer[li] + m->run.img0 * C * H * W, B, C, H, W));
+    return prof_end(m);
+}
+
+/* blocks [first, last) on an *H x *W map, which become those of block last's input; behind the last block of a
+ * stage the export of its map, when the running call wants it */
 static int run_blocks(rn_model *m, int first, int last, uint64_t B, uint64_t *H, uint64_t *W, int mode)
 {
-    int bi;
-    for (bi = first; bi < last; ++bi)
+    int bi, li = 0, end = m->depths[0]; /* block `end` is the first of stage li + 1 */
+    for (bi = first; bi < last; ++bi) {
         TRY(block_forward(m, &m->blocks[bi], block_input(m, bi), block_input(m, bi + 1), B, H, W, mode));
+        while (bi >= end) end += m->depths[++li];
+        if (m->maps && bi + 1 == end && m->maps->layer[li]) TRY(op_stage_map(m, li, block_input(m, bi + 1), B, *H, *W));
+    }
     return RN_OK;
 }
 
@@ -1439,6 +1480,7 @@ static void run_begin(rn_model *m, rn_ctx *ctx, uint64_t img_off, uint64_t slice
     r->ctx = ctx;
     r->mode = mode;
     r->t1_ready = 0;
+    r->img0 = m->maps_done + img_off;
     r->x4 = (float *)((char *)m->x4 + img_off * m->x4_img * es);
     r->p0 = (float *)((char *)m->p0 + p_off * es);
     r->p1 = (float *)((char *)m->p1 + p_off * es);
@@ -1603,7 +1645,7 @@ static int forward_outputs(rn_model *m, const void *input, int in_u8, uint64_t B
     /* bf16 storage exists only with the fused epilogues (no standalone bf16 bn/relu/add) */
     if (m->dtype != RN_DTYPE_F32 && mode != RN_FWD_FUSED) return RN_ERR_UNSUPPORTED;
     if (outs) {
-        if (!logits && !outs->features && !outs->probs && outs->k == 0) return RN_ERR_INVALID;
+        if (!logits && !outs->features && !outs->probs && outs->k == 0 && !m->maps) return RN_ERR_INVALID;
         if (outs->k > 0 && (!outs->topk_prob || !outs->topk_idx || outs->k > 64 || outs->k > m->classes))
             return RN_ERR_INVALID;
     }
@@ -1622,6 +1664,7 @@ static int forward_outputs(rn_model *m, const void *input, int in_u8, uint64_t B
     while (done < B) {
         const uint64_t nb = B - done < m->max_sub ? B - done : m->max_sub;
         float *sub = logits ? logits + done * m->classes : m->own_logits;
+        m->maps_done = done;
         TRY(forward_chunk(m, input_at(m, input, in_u8, done), in_u8, nb, sub, mode, prof_keep && done == 0));
         if (outs) TRY(head_outputs(m, outs, done, nb, sub));
         done += nb;
@@ -1656,6 +1699,48 @@ int rn_model_forward_outputs_u8(rn_model *m, const uint8_t *input_nhwc, uint64_t
 {
     if (!outs) return RN_ERR_INVALID;
     return forward_outputs(m, input_nhwc, 1, B, outs->logits, outs, mode, 0);
+}
+
+/* rn_model_forward_maps(_u8): the request is state of this call alone -- set once every refusal that belongs to the
+ * maps has passed, cleared on every way out -- so that no other forward, tuning pass, capture or pipeline submit
+ * ever exports (run_blocks asks m->maps). */
+static int forward_maps(rn_model *m, const void *input, int in_u8, uint64_t B, const rn_model_outputs *outs,
+                        const rn_model_maps *maps, int mode)
+{
+    rn_model_outputs none;
+    int li, wanted = 0, st;
+    if (!m) return RN_ERR_INVALID;
+    if (!maps) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_maps: maps is NULL");
+    for (li = 0; li < 4; ++li) {
+        if (!maps->layer[li]) continue;
+        wanted = 1;
+        if ((uintptr_t)maps->layer[li] & 3) {
+            char msg[96];
+            snprintf(msg, sizeof(msg), "rn_model_forward_maps: the map of layer%d must be 4-byte aligned", li + 1);
+            return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, msg);
+        }
+    }
+    if (!wanted && !(outs && (outs->logits || outs->features || outs->probs || outs->k)))
+        return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_maps: nothing to write");
+    memset(&none, 0, sizeof(none));
+    if (!outs) outs = &none;
+    m->maps = wanted ? maps : NULL;
+    st = forward_outputs(m, input, in_u8, B, outs->logits, outs, mode, 0);
+    m->maps = NULL;
+    m->maps_done = 0;
+    return st;
+}
+
+int rn_model_forward_maps(rn_model *m, const float *input_nchw, uint64_t B, const rn_model_outputs *outs,
+                          const rn_model_maps *maps, int mode)
+{
+    return forward_maps(m, input_nchw, 0, B, outs, maps, mode);
+}
+
+int rn_model_forward_maps_u8(rn_model *m, const uint8_t *input_nhwc, uint64_t B, const rn_model_outputs *outs,
+                             const rn_model_maps *maps, int mode)
+{
+    return forward_maps(m, input_nhwc, 1, B, outs, maps, mode);
 }
 
 /* The decoded-image route resizes to 256 and crops 224 x 224: a model of another size refuses it. */

@@ -341,6 +341,74 @@ class NativeModel:
                 out[name] = _down_raw(b, np.float32, int(np.prod(shapes[name]))).reshape(shapes[name])
         return out
 
+    STAGES = ("layer1", "layer2", "layer3", "layer4")
+
+    @property
+    def stage_shapes(self) -> Dict[str, Tuple[int, int, int]]:
+        """"layerN" -> (C, H, W) of the map behind that stage (rn_model_stage_shape): follows the architecture,
+        input_size and dilation.  ResNet-50 at 224 x 224: (256, 56, 56) .. (2048, 7, 7)."""
+        out = {}
+        for i, name in enumerate(self.STAGES):
+            c, h, w = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+            L.check(L.lib().rn_model_stage_shape(self.handle, i + 1, ctypes.byref(c), ctypes.byref(h), ctypes.byref(w)),
+                    "rn_model_stage_shape")
+            out[name] = (int(c.value), int(h.value), int(w.value))
+        return out
+
+    def forward_maps(self, x: np.ndarray, stages=STAGES, *, logits: bool = False, features: bool = False,
+                     probs: bool = False, topk: int = 0, fused: bool = True) -> dict:
+        """One forward, the feature maps behind the named stages (rn_model_forward_maps; torchvision's
+        IntermediateLayerGetter): a dict "layerN" -> [B,C,H,W] fp32 (stage_shapes) in the order of `stages`, then
+        the head outputs asked for, as forward_outputs returns them.  bf16 models: the stored values, widened
+        exactly.  x: fp32 NCHW [B,3,H,W], or uint8 NHWC [B,H,W,3] (normalised on the device).  An unknown or
+        repeated stage name raises ValueError."""
+        from .ops import _down_raw, _up_raw
+        from .tensor import _DeviceBuffer
+        stages = tuple(stages)
+        for s in stages:
+            if s not in self.STAGES:
+                raise ValueError(f"unknown stage {s!r}: one of {self.STAGES}")
+        if len(set(stages)) != len(stages):
+            raise ValueError(f"repeated stage in {stages}")
+        x = np.asarray(x)
+        u8 = x.dtype == np.uint8
+        x = np.ascontiguousarray(x, dtype=np.uint8 if u8 else np.float32)
+        self._check_input(x, u8)
+        B, C, F, k = x.shape[0], self.classes, self.features, int(topk)
+        xin = _up_raw(x)
+        shapes = {name: (B,) + chw for name, chw in self.stage_shapes.items()}
+        mbufs = {s: _DeviceBuffer(self.ctx, max(int(np.prod(shapes[s])) * 4, 16)) for s in stages}
+        maps = L.ModelMaps()
+        for s in stages:
+            maps.layer[self.STAGES.index(s)] = mbufs[s].ptr
+        bufs = {}
+
+        def buf(name, want, nbytes):
+            if want:
+                bufs[name] = _DeviceBuffer(self.ctx, max(nbytes, 16))
+            return bufs[name].ptr if want else None
+
+        o = L.ModelOutputs(buf("logits", logits, B * C * 4), buf("features", features, B * F * 4),
+                           buf("probs", probs, B * C * 4), buf("topk_prob", k > 0, B * k * 4),
+                           buf("topk_idx", k > 0, B * k * 8), k)
+        fn = L.lib().rn_model_forward_maps_u8 if u8 else L.lib().rn_model_forward_maps
+        L.check(fn(self.handle, xin.ptr, B, ctypes.byref(o), ctypes.byref(maps),
+                   L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS), "rn_model_forward_maps", self.ctx.handle)
+        self.ctx.sync()
+        shapes.update({"logits": (B, C), "features": (B, F), "probs": (B, C), "topk_prob": (B, k), "topk_idx": (B, k)})
+        out = {s: _down_raw(mbufs[s], np.float32, int(np.prod(shapes[s]))).reshape(shapes[s]) for s in stages}
+        for name, b in bufs.items():
+            if name == "topk_idx":
+                out[name] = _down_raw(b, np.uint64, B * k).astype(np.int64).reshape(B, k)
+            else:
+                out[name] = _down_raw(b, np.float32, int(np.prod(shapes[name]))).reshape(shapes[name])
+        return out
+
+    def forward_maps_u8(self, px: np.ndarray, stages=STAGES, **kw) -> dict:
+        """forward_maps from 8-bit RGB [B,H,W,3] (rn_model_forward_maps_u8): the same maps as forward_maps on
+        preprocess.normalize_u8 of the bytes, bit for bit."""
+        return self.forward_maps(np.ascontiguousarray(px, dtype=np.uint8), stages, **kw)
+
     def tensor_keys(self) -> List[Tuple[str, int]]:
         out, i, n = [], 0, ctypes.c_uint64()
         while True:

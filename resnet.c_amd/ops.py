@@ -494,6 +494,26 @@ def global_avgpool(x, bf16: bool = False) -> np.ndarray:
     return y.reshape(B, C)
 
 
+def nhwc_to_nchw_dt(x, bf16: bool = False) -> np.ndarray:
+    """rn_nhwc_to_nchw_dt: NHWC host array [B,H,W,C] in -- fp32, or uint16 bf16 bit patterns (``bf16``; an fp32
+    array is rounded to bf16 first) -- NCHW fp32 [B,C,H,W] out, bf16 widened exactly.  Any C, H, W; the fast
+    form where C % 4 == 0 (bf16: % 8)."""
+    from .tensor import _DeviceBuffer
+    ctx = get_ctx()
+    x = np.asarray(x)
+    if bf16:
+        x = x if x.dtype == np.uint16 else to_bf16_bits(x).reshape(x.shape)
+    else:
+        x = x.astype(np.float32, copy=False)
+    B, H, W, C = x.shape
+    dx = _up_raw(x)
+    out = _DeviceBuffer(ctx, max(x.size * 4, 16))
+    L.check(L.lib().rn_nhwc_to_nchw_dt(ctx.handle, L.RN_DTYPE_BF16 if bf16 else L.RN_DTYPE_F32, dx.ptr, out.ptr,
+                                       B, C, H, W), "rn_nhwc_to_nchw_dt", ctx.handle)
+    ctx.sync()
+    return _down_raw(out, np.float32, x.size).reshape(B, C, H, W)
+
+
 def image_u8_to_nhwc_pad(px, cpad: int = 4, border: int = 0, bf16: bool = False, mean=None, std=None,
                          prefill: Optional[int] = None) -> np.ndarray:
     """rn_image_u8_to_nhwc_pad_dt: uint8 RGB [B,H,W,3] -> the normalised, padded first tensor
