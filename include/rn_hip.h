@@ -760,6 +760,85 @@ RN_API int rn_model_forward_maps(rn_model *m, const float *input_nchw, uint64_t 
                                  const rn_model_maps *maps, int mode);
 RN_API int rn_model_forward_maps_u8(rn_model *m, const uint8_t *input_nhwc, uint64_t B, const rn_model_outputs *outs,
                                     const rn_model_maps *maps, int mode);
+/* ---- semantic segmentation: per-pixel scores upsampled to the image, and the label map ----------------------
+ * Bilinear upsample of NHWC class scores [B, h, w, src_channels] fp32 to H x W, as NCHW scores [B, classes, H, W]
+ * and / or as the label map [B, H, W] (one byte per pixel: the argmax over the classes), in ONE launch.  With
+ * scores_nchw == NULL no score is written anywhere: the running maximum lives in registers and the launch moves
+ * one byte per output pixel instead of 4 * classes.  Only channels 0 .. classes-1 of a source pixel are read;
+ * src_channels >= classes is the pixel's pitch (the padded channel count a 1x1 convolution wrote).
+ * The arithmetic is torch.nn.functional.interpolate(mode="bilinear", align_corners=False) with every operation
+ * rounded to fp32 on its own, no product fused into an add.  Per axis n_in -> n_out, output index o:
+ *     scale = (float)n_in / (float)n_out                       (one fp32 division, on the host)
+ *     src   = max(fl(fl(scale * fl((float)o + 0.5f)) - 0.5f), 0.0f)
+ *     i0    = min((int)src, n_in - 1);  i1 = min(i0 + 1, n_in - 1)
+ *     l1    = fl(src - (float)i0);      l0 = fl(1.0f - l1)
+ * and with row weights (a0, a1), column weights (b0, b1):
+ *     top = fl(fl(b0 * v[y0][x0]) + fl(b1 * v[y0][x1]));  bot = the same on row y1
+ *     out = fl(fl(a0 * top) + fl(a1 * bot))
+ * (segmentation.upsample_bilinear_ref restates it in numpy; the kernel matches it bit for bit).  The label is the
+ * lowest channel index that holds the maximum: channel 0 to start with, replaced only where v > best, which is
+ * numpy.argmax on finite data.  A NaN score never replaces the best (and a NaN in channel 0 is never replaced).
+ * Any ratio: enlarging is the purpose, H == h && W == w (the source's bits) and shrinking are correct as well.
+ * classes 1..256 (a label fits a byte), src_channels <= 256 and a multiple of 4, h, w, H, W >= 1, h * w and H * W
+ * below 2^31; offsets are 64-bit per image.  src_nhwc on a 16-byte boundary, scores_nchw on any 4-byte boundary,
+ * labels anywhere: 16-byte score stores and 4-byte label stores are used wherever four consecutive outputs share
+ * an aligned unit of the destination, whatever W and the addresses are.  Asynchronous on the context's stream;
+ * allocates and uploads nothing, every parameter is a kernel argument (capturable).  B == 0: RN_OK, nothing
+ * launched.  RN_ERR_INVALID, nothing launched, rn_last_error names the operand: ctx or src_nhwc NULL, both outputs
+ * NULL, classes outside 1..256, src_channels < classes or no multiple of 4, a zero size, a misaligned src_nhwc or
+ * scores_nchw. */
+RN_API int rn_upsample_bilinear_forward(rn_ctx *ctx, const float *src_nhwc, uint64_t B, uint64_t h, uint64_t w,
+                                        uint64_t classes, uint64_t src_channels, uint64_t H, uint64_t W,
+                                        float *scores_nchw /* [B,classes,H,W] or NULL */,
+                                        uint8_t *labels /* [B,H,W] or NULL */);
+/* torchvision's FCNHead on any NHWC map, no model needed: Conv3x3(in, mid, padding 1, no bias) + BatchNorm + ReLU
+ * (+ Dropout, the identity at inference) + Conv1x1(mid, classes) with bias, then the upsample above.  No convolution
+ * code of its own: rn_batchnorm2d_fold, rn_conv2d_pack_weight_dt and two rn_conv2d_nhwc_forward_dt launches (the
+ * 3x3 with the folded scale / shift and ReLU in its epilogue; the 1x1 with shift = bias and fp32 output whatever
+ * the storage type, its out_channels rounded up to a multiple of 4 with zero rows so that every coarse pixel
+ * starts on a 16-byte boundary: the src_channels of the upsample).  in_channels is a multiple of 64, classes
+ * 1..256; mid_channels is a multiple of 64 where it comes from a backbone (layer4 of a bottleneck network: 2048 ->
+ * 512; of a basic-block network: 512 -> 128) and may be any count 1..8192: the head rounds it up to a multiple of 64
+ * inside (the bf16 contraction's K granule) with channels of zero weights, scale 0 and shift 0, which hold
+ * ReLU(0) = 0 and add exact zeros to the 1x1 convolution's sums (FCNHead(128, 21) runs 128 -> 32 as 128 -> 64).
+ * Tensors (rn_seg_head_set_tensor, fp32 host data, torchvision's keys and shapes): classifier.0.weight
+ * [mid,in,3,3]; classifier.1.weight / .bias / .running_mean / .running_var [mid]; classifier.4.weight
+ * [classes,mid,1,1]; classifier.4.bias [classes].  rn_seg_head_set_dtype (before finalize) chooses the storage
+ * type of the input map, the mid tensor and the weight panels.  rn_seg_head_finalize folds and packs; it needs
+ * every tensor.
+ * rn_seg_head_forward: x_nhwc [B,h,w,in_channels] of the storage type (16-byte aligned) -> scores_nchw
+ * [B,classes,H,W] and / or labels [B,H,W] (either may be NULL, not both): three launches on the context's stream.
+ * The head owns its two scratch tensors (the mid tensor [B,h,w,mid] and the coarse scores [B,h,w,classes padded]
+ * fp32); they grow on first use like the logits buffer a model owns: RN_ERR_UNSUPPORTED on a stream that is being
+ * captured, RN_ERR_INVALID while a captured graph of the context lives. */
+typedef struct rn_seg_head rn_seg_head;
+RN_API int rn_seg_head_create(rn_ctx *ctx, rn_seg_head **out, uint64_t in_channels, uint64_t mid_channels,
+                              uint64_t classes);
+RN_API int rn_seg_head_set_dtype(rn_seg_head *hd, int dtype);
+RN_API int rn_seg_head_set_tensor(rn_seg_head *hd, const char *key, const float *host_data, uint64_t numel);
+RN_API int rn_seg_head_finalize(rn_seg_head *hd);
+RN_API int rn_seg_head_destroy(rn_seg_head *hd);
+RN_API int rn_seg_head_forward(rn_seg_head *hd, const void *x_nhwc, uint64_t B, uint64_t h, uint64_t w, uint64_t H,
+                               uint64_t W, float *scores_nchw, uint8_t *labels);
+/* The label map (and / or the scores) of B images from one forward: exactly the launches and bits of
+ * rn_model_forward_outputs -- same sub-batches, parts, front slices, profile records, the classification head
+ * included -- plus the head's three launches per launch batch (ops "seg_conv1", "seg_conv2", "seg_upsample" of
+ * layer "segmentation" in the profile), queued right behind the last block of layer4 on that block's stream, where
+ * the map still sits in its ping-pong arena (as rn_model_forward_maps exports it).  The outputs are at the model's
+ * input size: labels [B,H,W] bytes, scores [B,classes,H,W] fp32 (4-byte aligned), device pointers, either may be
+ * NULL.  Every part of a launch batch uses its own slice of the head's scratch, which is sized for one sub-batch
+ * (it grows with the refusals of rn_seg_head_forward) and is reused by the next sub-batch behind the join of the
+ * parts' streams, like the arenas.  A head that also runs on its own (rn_seg_head_forward) on another stream is
+ * the caller's to order.  outs may be NULL, as in rn_model_forward_maps.  The request lives for this call only.
+ * RN_ERR_INVALID with a text in rn_last_error of the model's context, nothing launched: seg == NULL, a seg that
+ * names nothing, misaligned scores, a model or a head that is not finalized, a head whose in_channels is not
+ * rn_model_features or whose storage type (dtype) is not the model's.  rn_model_capture, the pipelines and
+ * rn_shard_* carry no segmentation. */
+typedef struct rn_seg_outputs { uint8_t *labels; float *scores; } rn_seg_outputs;
+RN_API int rn_model_forward_segment(rn_model *m, rn_seg_head *hd, const float *input_nchw, uint64_t B,
+                                    const rn_model_outputs *outs /* nullable */, const rn_seg_outputs *seg, int mode);
+RN_API int rn_model_forward_segment_u8(rn_model *m, rn_seg_head *hd, const uint8_t *input_nhwc, uint64_t B,
+                                       const rn_model_outputs *outs, const rn_seg_outputs *seg, int mode);
 /* Run one forward, then time every tile candidate of every convolution at batch B on the
  * device (events on the context's stream, on the buffers that forward used) and remember the fastest per layer for
  * that batch size.  Results do not change (candidates are bit-identical), only speed. */

@@ -41,6 +41,11 @@ class ModelMaps(ctypes.Structure):
     _fields_ = [("layer", c_void_p * 4)]
 
 
+class SegOutputs(ctypes.Structure):
+    """rn_seg_outputs: device pointers of the label map [B,H,W] (bytes) and the scores [B,classes,H,W] fp32."""
+    _fields_ = [("labels", c_void_p), ("scores", c_void_p)]
+
+
 class Epilogue(ctypes.Structure):
     _fields_ = [("scale", c_void_p), ("shift", c_void_p), ("residual", c_void_p),
                 ("relu", c_int)]
@@ -179,6 +184,17 @@ SIGNATURES = {
     "rn_model_stage_shape": (c_int, [c_void_p, c_int, POINTER(u64), POINTER(u64), POINTER(u64)]),
     "rn_model_forward_maps": (c_int, [c_void_p, fptr, u64, POINTER(ModelOutputs), POINTER(ModelMaps), c_int]),
     "rn_model_forward_maps_u8": (c_int, [c_void_p, c_void_p, u64, POINTER(ModelOutputs), POINTER(ModelMaps), c_int]),
+    "rn_upsample_bilinear_forward": (c_int, [c_void_p, fptr] + [u64] * 7 + [fptr, c_void_p]),
+    "rn_seg_head_create": (c_int, [c_void_p, POINTER(c_void_p), u64, u64, u64]),
+    "rn_seg_head_set_dtype": (c_int, [c_void_p, c_int]),
+    "rn_seg_head_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, u64]),
+    "rn_seg_head_finalize": (c_int, [c_void_p]),
+    "rn_seg_head_destroy": (c_int, [c_void_p]),
+    "rn_seg_head_forward": (c_int, [c_void_p, c_void_p] + [u64] * 5 + [fptr, c_void_p]),
+    "rn_model_forward_segment": (c_int, [c_void_p, c_void_p, fptr, u64, POINTER(ModelOutputs), POINTER(SegOutputs),
+                                         c_int]),
+    "rn_model_forward_segment_u8": (c_int, [c_void_p, c_void_p, c_void_p, u64, POINTER(ModelOutputs),
+                                            POINTER(SegOutputs), c_int]),
     "rn_model_destroy": (c_int, [c_void_p]),
     "rn_model_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, u64]),
     "rn_model_load_dir": (c_int, [c_void_p, c_char_p]),

@@ -5,7 +5,7 @@
  * B = 1, paths); here the same defaults can be overridden from the command line.
  *
  *   rn_infer [--arch 18|34|50|101|152|resnext50_32x4d|resnext101_32x8d|resnext101_64x4d|wide_resnet50_2|wide_resnet101_2] [--weights DIR] [--input FILE | --u8 FILE | --rgb FILE --hw H,W] [--batch B]
- *            [--size H,W] [--dilate a,b,c] [--maps PREFIX] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,c,...]
+ *            [--size H,W] [--dilate a,b,c] [--maps PREFIX] [--segment HEAD_DIR --labels FILE] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,c,...]
  *
  * --size H,W sets the model's input size (rn_model_set_input_size; default 224,224; single device only):
  * --input then holds B x 3 x H x W floats and --u8 B x H x W x 3 bytes, and a file of any other length is
@@ -15,6 +15,12 @@
  * --maps PREFIX also writes the feature maps behind layer1..layer4 of the batch it ran, from the same forward
  * (rn_model_forward_maps): PREFIX.layer1.bin .. PREFIX.layer4.bin, each [B,C,H,W] fp32 (rn_save_f32_file; the
  * shapes are rn_model_stage_shape's).  Single device, not with --rgb; the lines printed are unchanged.
+ * --segment HEAD_DIR --labels FILE also writes the label map of the batch it ran, from the same forward
+ * (rn_model_forward_segment): HEAD_DIR/<key> holds the seven fp32 tensors of torchvision's FCNHead
+ * (classifier.0.weight .. classifier.4.bias; in_channels is the model's feature width, mid_channels a quarter of
+ * it, the class count is the length of classifier.4.bias), FILE receives B x H x W label bytes at the model's
+ * input size.  Works with --size, --dilate, --dtype and --u8; single device, not with --rgb or --maps; the lines
+ * printed are unchanged.
  * --u8 FILE reads B x 150528 raw bytes, the decoder's 8-bit RGB crops ([B,224,224,3]), instead of
  * the preprocessed fp32 file: the device normalises them (rn_model_forward_u8), same lines out.
  * --rgb FILE --hw H,W reads the H x W x 3 raw bytes of ONE decoded image of any size: the device resizes
@@ -65,6 +71,27 @@ static void *read_exact(const char *path, uint64_t want, uint64_t B, int u8)
         return NULL;
     }
     fclose(f);
+    return host;
+}
+
+/* HEAD_DIR/key: raw fp32, the weights_bin format; the malloc'd values and their count, NULL when unreadable */
+static float *read_f32(const char *dir, const char *key, uint64_t *numel)
+{
+    char path[1024];
+    FILE *f;
+    long bytes;
+    float *host = NULL;
+    snprintf(path, sizeof(path), "%s/%s", dir, key);
+    f = fopen(path, "rb");
+    if (f && fseek(f, 0, SEEK_END) == 0 && (bytes = ftell(f)) > 0 && bytes % 4 == 0 && fseek(f, 0, SEEK_SET) == 0 &&
+        (host = (float *)malloc((size_t)bytes)) != NULL && fread(host, 1, (size_t)bytes, f) == (size_t)bytes) {
+        *numel = (uint64_t)bytes / 4;
+    } else {
+        fprintf(stderr, "rn_infer: %s: %s: cannot read fp32 values\n", rn_status_string(RN_ERR_IO), path);
+        free(host);
+        host = NULL;
+    }
+    if (f) fclose(f);
     return host;
 }
 
@@ -147,6 +174,9 @@ int main(int argc, char **argv)
     const char *weights = "weights_bin";
     const char *input = "test_bins/ILSVRC2012_val_00004749.bin";
     const char *maps_prefix = NULL; /* --maps */
+    const char *seg_dir = NULL, *labels_path = NULL; /* --segment, --labels */
+    rn_seg_head *head = NULL;
+    uint8_t *labels_dev = NULL;
     rn_model_maps maps = {{NULL, NULL, NULL, NULL}};
     rn_ctx *ctx = NULL;
     rn_model *model = NULL;
@@ -183,6 +213,8 @@ int main(int argc, char **argv)
             ++i;
         }
         else if (!strcmp(a, "--maps") && v) { maps_prefix = v; ++i; }
+        else if (!strcmp(a, "--segment") && v) { seg_dir = v; ++i; }
+        else if (!strcmp(a, "--labels") && v) { labels_path = v; ++i; }
         else if (!strcmp(a, "--batch") && v) { B = strtoull(v, NULL, 10); ++i; }
         else if (!strcmp(a, "--classes") && v) { classes = strtoull(v, NULL, 10); ++i; }
         else if (!strcmp(a, "--topk") && v) { topk = strtoull(v, NULL, 10); ++i; }
@@ -198,7 +230,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--mode") && v) { mode = strcmp(v, "ops") ? RN_FWD_FUSED : RN_FWD_REFERENCE_OPS; ++i; }
         else {
             fprintf(stderr, "usage: %s [--arch 18|34|50|101|152|resnext50_32x4d|resnext101_32x8d|resnext101_64x4d|wide_resnet50_2|wide_resnet101_2] [--weights DIR] [--input FILE | --u8 FILE | --rgb FILE --hw H,W] "
-                            "[--batch B] [--size H,W] [--dilate a,b,c] [--maps PREFIX] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,...] [--classes N] [--topk K]\n",
+                            "[--batch B] [--size H,W] [--dilate a,b,c] [--maps PREFIX] [--segment HEAD_DIR --labels FILE] [--mode fused|ops] [--dtype f32|bf16] [--device N | --devices a,b,...] [--classes N] [--topk K]\n",
                     argv[0]);
             return 2;
         }
@@ -226,6 +258,11 @@ int main(int argc, char **argv)
     }
     if (maps_prefix && (ndev > 0 || rgb)) {
         fprintf(stderr, "rn_infer: %s: --maps runs on one device and not with --rgb\n", rn_status_string(RN_ERR_UNSUPPORTED));
+        return 1;
+    }
+    if ((seg_dir != NULL) != (labels_path != NULL) || (seg_dir && (ndev > 0 || rgb || maps_prefix))) {
+        fprintf(stderr, "rn_infer: %s: --segment HEAD_DIR and --labels FILE go together, on one device and not with --rgb "
+                        "or --maps\n", rn_status_string(RN_ERR_UNSUPPORTED));
         return 1;
     }
     if (ndev > 0) return run_sharded(devices, ndev, arch, weights, input, u8, B, mode, dtype);
@@ -308,6 +345,46 @@ int main(int argc, char **argv)
             snprintf(path, sizeof(path), "%s.layer%d.bin", maps_prefix, s + 1);
             CHECK(ctx, rn_save_f32_file(ctx, path, maps.layer[s], B * C * H * W));
         }
+    } else if (seg_dir) { /* the same forward, and the label map out of it */
+        static const char *const keys[7] = {"classifier.0.weight", "classifier.1.weight", "classifier.1.bias",
+                                            "classifier.1.running_mean", "classifier.1.running_var",
+                                            "classifier.4.weight", "classifier.4.bias"};
+        const uint64_t feat = rn_model_features(model), pixels = B * size_h * size_w;
+        uint64_t n = 0;
+        rn_model_outputs outs;
+        rn_seg_outputs seg;
+        uint8_t *host_labels = (uint8_t *)malloc(pixels);
+        FILE *f;
+        int k;
+        float *t = read_f32(seg_dir, keys[6], &n); /* the bias first: its length is the class count */
+        if (!t || !host_labels) return 1;
+        CHECK(ctx, rn_seg_head_create(ctx, &head, feat, feat / 4, n));
+        CHECK(ctx, rn_seg_head_set_dtype(head, dtype));
+        CHECK(ctx, rn_seg_head_set_tensor(head, keys[6], t, n));
+        free(t);
+        for (k = 0; k < 6; ++k) {
+            if (!(t = read_f32(seg_dir, keys[k], &n))) return 1;
+            CHECK(ctx, rn_seg_head_set_tensor(head, keys[k], t, n));
+            free(t);
+        }
+        CHECK(ctx, rn_seg_head_finalize(head));
+        CHECK(ctx, rn_malloc(ctx, (void **)&labels_dev, pixels));
+        memset(&outs, 0, sizeof(outs));
+        outs.logits = logits;
+        seg.labels = labels_dev;
+        seg.scores = NULL;
+        if (u8)
+            CHECK(ctx, rn_model_forward_segment_u8(model, head, inp_u8, B, &outs, &seg, mode));
+        else
+            CHECK(ctx, rn_model_forward_segment(model, head, inp, B, &outs, &seg, mode));
+        CHECK(ctx, rn_memcpy_d2h(ctx, host_labels, labels_dev, pixels));
+        f = fopen(labels_path, "wb");
+        if (!f || fwrite(host_labels, 1, pixels, f) != pixels || fclose(f) != 0) {
+            fprintf(stderr, "rn_infer: %s: %s: cannot write %llu label bytes\n", rn_status_string(RN_ERR_IO), labels_path,
+                    (unsigned long long)pixels);
+            return 1;
+        }
+        free(host_labels);
     } else if (u8)
         CHECK(ctx, rn_model_forward_u8(model, inp_u8, B, logits, mode));
     else
@@ -344,6 +421,8 @@ int main(int argc, char **argv)
     rn_free(ctx, inp);
     rn_free(ctx, inp_u8);
     for (i = 0; i < 4; ++i) rn_free(ctx, maps.layer[i]);
+    rn_free(ctx, labels_dev);
+    rn_seg_head_destroy(head);
     rn_model_destroy(model);
     rn_ctx_destroy(ctx);
     return 0;

@@ -106,6 +106,7 @@ typedef struct {
     int t1_ready; /* the previous block's chained launch has produced this block's conv1 output */
     float *x4, *p0, *p1, *dsb, *t1, *t2, *pooled; /* views into the arenas */
     uint64_t img0; /* the caller's index of this launch's first image: sub-batch + part + front slice (stage maps) */
+    uint64_t sub0; /* the same image's index inside its sub-batch: its slice of a segmentation head's scratch */
 } rn_run;
 
 /* What a pipeline keeps of its model after the model may be gone: freed by whoever leaves last. */
@@ -175,6 +176,9 @@ struct rn_model {
      * the caller's index of the first image of the sub-batch being queued */
     const rn_model_maps *maps;
     uint64_t maps_done;
+    /* rn_model_forward_segment: the head and the buffers of the call that is running (NULL in every other forward) */
+    rn_seg_head *seg_head;
+    const rn_seg_outputs *seg;
     /* tile tuning: calls of the last forward, and the batch size the tiles were tuned for */
     rn_conv_call *calls;
     int n_calls, cap_calls, recording;
@@ -1425,8 +1429,39 @@ static int op_stage_map(rn_model *m, int li, const float *x, uint64_t B, uint64_
     return prof_end(m);
 }
 
+/* rn_model_forward_segment: the head on layer4's output x [B,h,w,C] of this launch, into the caller's buffers from
+ * image run.img0 on.  Queued behind the last block on that block's stream, like op_stage_map and for its reason.
+ * The launch's images use the slice of the head's scratch that starts at their index in the sub-batch: the parts
+ * of a launch batch run side by side on their streams, and forward_chunk joins those streams before the next
+ * sub-batch reuses the scratch, as it does for the arenas. */
+static int op_segment(rn_model *m, const float *x, uint64_t B, uint64_t h, uint64_t w)
+{
+    static const char *const ops[3] = {"seg_conv1", "seg_conv2", "seg_upsample"};
+    const uint64_t HW = m->H * m->W, es = elem_size(m);
+    uint64_t d[4]; /* in, mid, classes, padded classes */
+    double flops[3], bytes[3];
+    float *scores;
+    uint8_t *labels;
+    int step;
+    rn_seg_head_dims(m->seg_head, d);
+    scores = m->seg->scores ? m->seg->scores + m->run.img0 * d[2] * HW : NULL;
+    labels = m->seg->labels ? m->seg->labels + m->run.img0 * HW : NULL;
+    flops[0] = 2.0 * (double)(B * h * w) * 9.0 * (double)d[0] * (double)d[1];
+    bytes[0] = (double)es * ((double)(B * h * w) * (double)(d[0] + d[1]) + 9.0 * (double)d[0] * (double)d[1]);
+    flops[1] = 2.0 * (double)(B * h * w) * (double)d[1] * (double)d[3];
+    bytes[1] = (double)(B * h * w) * ((double)es * (double)d[1] + 4.0 * (double)d[3]) + (double)es * (double)(d[1] * d[3]);
+    flops[2] = 0.0;
+    bytes[2] = 4.0 * (double)(B * h * w * d[3]) + (double)(B * HW) * ((scores ? 4.0 * (double)d[2] : 0.0) + (labels ? 1.0 : 0.0));
+    for (step = 0; step < 3; ++step) {
+        TRY(prof_begin(m, ops[step], "segmentation", flops[step], bytes[step]));
+        TRY(rn_seg_head_step(m->seg_head, m->run.ctx, step, x, m->run.sub0 * h * w, B, h, w, m->H, m->W, scores, labels));
+        TRY(prof_end(m));
+    }
+    return RN_OK;
+}
+
 /* blocks [first, last) on an *H x *W map, which become those of block last's input; behind the last block of a
- * stage the export of its map, when the running call wants it */
+ * stage the export of its map, when the running call wants it; behind the last block of all the segmentation head */
 static int run_blocks(rn_model *m, int first, int last, uint64_t B, uint64_t *H, uint64_t *W, int mode)
 {
     int bi, li = 0, end = m->depths[0]; /* block `end` is the first of stage li + 1 */
@@ -1434,6 +1469,7 @@ static int run_blocks(rn_model *m, int first, int last, uint64_t B, uint64_t *H,
         TRY(block_forward(m, &m->blocks[bi], block_input(m, bi), block_input(m, bi + 1), B, H, W, mode));
         while (bi >= end) end += m->depths[++li];
         if (m->maps && bi + 1 == end && m->maps->layer[li]) TRY(op_stage_map(m, li, block_input(m, bi + 1), B, *H, *W));
+        if (m->seg_head && bi + 1 == m->n_blocks) TRY(op_segment(m, block_input(m, bi + 1), B, *H, *W));
     }
     return RN_OK;
 }
@@ -1481,6 +1517,7 @@ static void run_begin(rn_model *m, rn_ctx *ctx, uint64_t img_off, uint64_t slice
     r->mode = mode;
     r->t1_ready = 0;
     r->img0 = m->maps_done + img_off;
+    r->sub0 = img_off;
     r->x4 = (float *)((char *)m->x4 + img_off * m->x4_img * es);
     r->p0 = (float *)((char *)m->p0 + p_off * es);
     r->p1 = (float *)((char *)m->p1 + p_off * es);
@@ -1645,7 +1682,7 @@ static int forward_outputs(rn_model *m, const void *input, int in_u8, uint64_t B
     /* bf16 storage exists only with the fused epilogues (no standalone bf16 bn/relu/add) */
     if (m->dtype != RN_DTYPE_F32 && mode != RN_FWD_FUSED) return RN_ERR_UNSUPPORTED;
     if (outs) {
-        if (!logits && !outs->features && !outs->probs && outs->k == 0 && !m->maps) return RN_ERR_INVALID;
+        if (!logits && !outs->features && !outs->probs && outs->k == 0 && !m->maps && !m->seg_head) return RN_ERR_INVALID;
         if (outs->k > 0 && (!outs->topk_prob || !outs->topk_idx || outs->k > 64 || outs->k > m->classes))
             return RN_ERR_INVALID;
     }
@@ -1741,6 +1778,54 @@ int rn_model_forward_maps_u8(rn_model *m, const uint8_t *input_nhwc, uint64_t B,
                              const rn_model_maps *maps, int mode)
 {
     return forward_maps(m, input_nhwc, 1, B, outs, maps, mode);
+}
+
+/* rn_model_forward_segment(_u8): like the maps, the request is state of this call alone -- set once every refusal
+ * has passed, cleared on every way out (run_blocks asks m->seg_head). */
+static int forward_segment(rn_model *m, rn_seg_head *hd, const void *input, int in_u8, uint64_t B,
+                           const rn_model_outputs *outs, const rn_seg_outputs *seg, int mode)
+{
+    rn_model_outputs none;
+    const char *why = NULL;
+    uint64_t h = 0, w = 0;
+    int st;
+    if (!m) return RN_ERR_INVALID;
+    if (!seg) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_segment: seg is NULL");
+    if (!seg->labels && !seg->scores)
+        return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_segment: seg names nothing (labels and scores are NULL)");
+    if ((uintptr_t)seg->scores & 3)
+        return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_segment: seg->scores must be 4-byte aligned");
+    if (!m->finalized) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_segment: the model is not finalized");
+    if (!rn_seg_head_matches(hd, m->feat, m->dtype, &why)) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "rn_model_forward_segment: %s", why);
+        return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, msg);
+    }
+    if (!input || B == 0 || (mode != RN_FWD_REFERENCE_OPS && mode != RN_FWD_FUSED)) return RN_ERR_INVALID;
+    if (m->dtype != RN_DTYPE_F32 && mode != RN_FWD_FUSED) return RN_ERR_UNSUPPORTED;
+    TRY(rn_model_stage_shape(m, 4, NULL, &h, &w));
+    TRY(rn_seg_head_reserve(hd, (B < m->max_sub ? B : m->max_sub) * h * w));
+    memset(&none, 0, sizeof(none));
+    if (!outs) outs = &none;
+    m->seg_head = hd;
+    m->seg = seg;
+    st = forward_outputs(m, input, in_u8, B, outs->logits, outs, mode, 0);
+    m->seg_head = NULL;
+    m->seg = NULL;
+    m->maps_done = 0;
+    return st;
+}
+
+int rn_model_forward_segment(rn_model *m, rn_seg_head *hd, const float *input_nchw, uint64_t B,
+                             const rn_model_outputs *outs, const rn_seg_outputs *seg, int mode)
+{
+    return forward_segment(m, hd, input_nchw, 0, B, outs, seg, mode);
+}
+
+int rn_model_forward_segment_u8(rn_model *m, rn_seg_head *hd, const uint8_t *input_nhwc, uint64_t B,
+                                const rn_model_outputs *outs, const rn_seg_outputs *seg, int mode)
+{
+    return forward_segment(m, hd, input_nhwc, 1, B, outs, seg, mode);
 }
 
 /* The decoded-image route resizes to 256 and crops 224 x 224: a model of another size refuses it. */

@@ -49,6 +49,18 @@ int rn_conv_group_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const v
                                   uint64_t out_channels, uint64_t H, uint64_t W, uint64_t groups,
                                   const rn_epilogue *epilogue);
 
+/* ---- rn_seg.hip: the segmentation head as the model driver queues it ---- */
+/* 1 when the head is finalized and reads maps of in_channels channels of `dtype`; *why: what is wrong otherwise */
+int rn_seg_head_matches(const rn_seg_head *hd, uint64_t in_channels, int dtype, const char **why);
+/* in_channels, mid_channels, classes, and classes rounded up to a multiple of 4 (the coarse scores' pixel pitch) */
+void rn_seg_head_dims(const rn_seg_head *hd, uint64_t dims[4]);
+/* the head's two scratch tensors for `pixels` coarse pixels (images x h x w); grows like the model's logits buffer */
+int rn_seg_head_reserve(rn_seg_head *hd, uint64_t pixels);
+/* launch `step` (0: the 3x3, 1: the 1x1, 2: the upsample) for B images on ctx; their scratch starts pix0 coarse
+ * pixels into the head's tensors */
+int rn_seg_head_step(rn_seg_head *hd, rn_ctx *ctx, int step, const void *x_nhwc, uint64_t pix0, uint64_t B, uint64_t h,
+                     uint64_t w, uint64_t H, uint64_t W, float *scores_nchw, uint8_t *labels);
+
 /* ---- rn_stem.hip ---- */
 /* 1 when the fused stem + max-pool launch takes a padded image of Hp x Wp (nchw: the NCHW-fetching form on
  * an image of Hp - 6 x Wp - 6) of `dtype`: its documented conditions on the geometry alone */

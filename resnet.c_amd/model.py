@@ -409,6 +409,53 @@ class NativeModel:
         preprocess.normalize_u8 of the bytes, bit for bit."""
         return self.forward_maps(np.ascontiguousarray(px, dtype=np.uint8), stages, **kw)
 
+    def forward_segment(self, x: np.ndarray, head, labels: bool = True, scores: bool = False, *, logits: bool = False,
+                        features: bool = False, probs: bool = False, topk: int = 0, fused: bool = True) -> dict:
+        """One forward with a segmentation head behind layer4 (rn_model_forward_segment): a dict with "labels"
+        [B,H,W] uint8 and / or "scores" [B,classes,H,W] fp32 at the model's input_size, then the head outputs
+        asked for, as forward_outputs returns them.  head: a segmentation.FCNHead of this model's feature width
+        and dtype, on this model's context.  x: fp32 NCHW [B,3,H,W], or uint8 NHWC [B,H,W,3]."""
+        from .ops import _down_raw, _up_raw
+        from .tensor import _DeviceBuffer
+        x = np.asarray(x)
+        u8 = x.dtype == np.uint8
+        x = np.ascontiguousarray(x, dtype=np.uint8 if u8 else np.float32)
+        self._check_input(x, u8)
+        (H, W), K = self.input_size, head.classes
+        B, C, F, k = x.shape[0], self.classes, self.features, int(topk)
+        xin = _up_raw(x)
+        bufs = {}
+
+        def buf(name, want, nbytes):
+            if want:
+                bufs[name] = _DeviceBuffer(self.ctx, max(nbytes, 16))
+            return bufs[name].ptr if want else None
+
+        seg = L.SegOutputs(buf("labels", labels, B * H * W), buf("scores", scores, B * K * H * W * 4))
+        o = L.ModelOutputs(buf("logits", logits, B * C * 4), buf("features", features, B * F * 4),
+                           buf("probs", probs, B * C * 4), buf("topk_prob", k > 0, B * k * 4),
+                           buf("topk_idx", k > 0, B * k * 8), k)
+        fn = L.lib().rn_model_forward_segment_u8 if u8 else L.lib().rn_model_forward_segment
+        L.check(fn(self.handle, head.handle, xin.ptr, B, ctypes.byref(o), ctypes.byref(seg),
+                   L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS), "rn_model_forward_segment", self.ctx.handle)
+        self.ctx.sync()
+        shapes = {"scores": (B, K, H, W), "logits": (B, C), "features": (B, F), "probs": (B, C), "topk_prob": (B, k),
+                  "topk_idx": (B, k)}
+        out = {}
+        for name, b in bufs.items():
+            if name == "labels":
+                out[name] = _down_raw(b, np.uint8, B * H * W).reshape(B, H, W)
+            elif name == "topk_idx":
+                out[name] = _down_raw(b, np.uint64, B * k).astype(np.int64).reshape(B, k)
+            else:
+                out[name] = _down_raw(b, np.float32, int(np.prod(shapes[name]))).reshape(shapes[name])
+        return out
+
+    def forward_segment_u8(self, px: np.ndarray, head, **kw) -> dict:
+        """forward_segment from 8-bit RGB [B,H,W,3] (rn_model_forward_segment_u8): the same scores and labels as
+        forward_segment on preprocess.normalize_u8 of the bytes, bit for bit."""
+        return self.forward_segment(np.ascontiguousarray(px, dtype=np.uint8), head, **kw)
+
     def tensor_keys(self) -> List[Tuple[str, int]]:
         out, i, n = [], 0, ctypes.c_uint64()
         while True:

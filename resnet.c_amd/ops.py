@@ -805,3 +805,25 @@ def conv2d_dilated_nhwc_bf16(x, w, stride=1, pad=0, dilation=1, groups=1, scale=
     ctx.sync()
     y = _down_raw(out, np.float32, n_out) if out_f32 else from_bf16_bits(_down_raw(out, np.uint16, n_out))
     return y.reshape(B, ho, wo, Cout).transpose(0, 3, 1, 2).copy()
+
+
+def upsample_bilinear(x_nhwc, size, classes: Optional[int] = None, scores: bool = True, labels: bool = False):
+    """rn_upsample_bilinear_forward: NHWC scores [B,h,w,C] fp32 (C % 4 == 0, C <= 256) -> (scores [B,classes,H,W]
+    fp32 or None, labels [B,H,W] uint8 or None) at size = (H, W), one launch; only channels 0 .. classes-1 are read
+    (classes = None: all).  Bit for bit segmentation.upsample_bilinear_ref; with scores=False the launch writes
+    the label bytes only."""
+    from .tensor import _DeviceBuffer
+    ctx = get_ctx()
+    x = np.ascontiguousarray(x_nhwc, dtype=np.float32)
+    B, h, w, C = x.shape
+    classes = C if classes is None else int(classes)
+    H, W = int(size[0]), int(size[1])
+    dx = _up_raw(x)
+    ds = _DeviceBuffer(ctx, max(B * classes * H * W * 4, 16)) if scores else None
+    dl = _DeviceBuffer(ctx, max(B * H * W, 16)) if labels else None
+    L.check(L.lib().rn_upsample_bilinear_forward(ctx.handle, dx.ptr, B, h, w, classes, C, H, W, ds.ptr if ds else None,
+                                                 dl.ptr if dl else None), "rn_upsample_bilinear_forward", ctx.handle)
+    ctx.sync()
+    s = _down_raw(ds, np.float32, B * classes * H * W).reshape(B, classes, H, W) if scores else None
+    lb = _down_raw(dl, np.uint8, B * H * W).reshape(B, H, W) if labels else None
+    return s, lb
