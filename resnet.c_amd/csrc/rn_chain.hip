@@ -45,17 +45,7 @@ struct ChainParams {
     int t2_bytes, x_bytes, y_bytes, t1_bytes;
 };
 
-typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
 typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
-
-// four fp32 -> two dwords of bf16 (round to nearest even)
-__device__ __forceinline__ void pack4(const float (&v)[4], unsigned (&d)[2])
-{
-    bf16x2 a, b;
-    a[0] = (bf16_t)v[0], a[1] = (bf16_t)v[1], b[0] = (bf16_t)v[2], b[1] = (bf16_t)v[3];
-    d[0] = __builtin_bit_cast(unsigned, a);
-    d[1] = __builtin_bit_cast(unsigned, b);
-}
 
 // Geometry per mid-channel count MID (block channels C = 4 MID):
 //   MID  64: 8 waves, 64 rows per step; a wave owns 32 of the 256 channels of the first product
@@ -96,12 +86,7 @@ __global__ __launch_bounds__(64 * Geo<MID>::WAVES) void chain_kernel(const Chain
 
     // this block's steps: a contiguous range, the remainder to the first blocks
     int nst, s0;
-    {
-        const unsigned total = gridDim.x, v = blockIdx.x;
-        const unsigned base = (unsigned)p.nsteps / total, rem = (unsigned)p.nsteps % total;
-        nst = (int)(base + (v < rem ? 1u : 0u));
-        s0 = (int)(v * base + min(v, rem));
-    }
+    dealt_range((unsigned)p.nsteps, gridDim.x, blockIdx.x, &nst, &s0);
 
     // weights.  First product: wave w owns channel fragments CF1*w .. CF1*w + CF1-1.  Second: wave w
     // owns rows 32(w % PF) .. +31 of the step and channel fragment w / PF (waves past PF*N1F: none)
@@ -123,7 +108,7 @@ __global__ __launch_bounds__(64 * Geo<MID>::WAVES) void chain_kernel(const Chain
     }
     for (int i = t; i < C; i += THREADS) {
         ssl[i] = p.sc3 ? p.sc3[i] : 1.f;
-        ssl[C + i] = p.sh3 ? p.sh3[i] : -0.f;  // -0.0 keeps a -0.0 sum
+        ssl[C + i] = p.sh3 ? p.sh3[i] : -0.f;
     }
     for (int i = t; i < N1; i += THREADS) {
         ssl[2 * C + i] = p.sc1 ? p.sc1[i] : 1.f;
@@ -132,8 +117,8 @@ __global__ __launch_bounds__(64 * Geo<MID>::WAVES) void chain_kernel(const Chain
 
     const i32x4 srd_t2 = make_srd(p.t2, p.t2_bytes);
     const i32x4 srd_x = make_srd(p.x, p.x_bytes);
-    const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_t1 = __builtin_amdgcn_make_buffer_rsrc(p.t1, 0, p.t1_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_y = make_rsrc(p.y, p.y_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_t1 = make_rsrc(p.t1, p.t1_bytes);
     const unsigned lds_base = (unsigned)(uintptr_t)((lds_void *)lds);
 
     // the DMA pieces (1 KiB each) of step s into buffer `buf`.  t2: K tile kt, rows 8i .. 8i+7 in
@@ -147,14 +132,14 @@ __global__ __launch_bounds__(64 * Geo<MID>::WAVES) void chain_kernel(const Chain
         for (int j = 0; j < T2P / G::WAVES; ++j) {
             const int q = G::WAVES * j + wave, kt = q / (ROWS / 8), r = 8 * (q % (ROWS / 8)) + (lane >> 3);
             const int pc = lane & 7, m = m0 + r;
-            dma16((live && m < p.M) ? m * (MID * 2) + kt * 128 + ((pc ^ ((r >> 1) & 7)) << 4) : kOob, srd_t2, 0,
+            dma16((live && m < p.M) ? m * (MID * 2) + kt * 128 + (RN_SWZ(pc, r) << 4) : kOob, srd_t2, 0,
                   lds_base + (unsigned)(G::oT2 + buf * G::T2B + q * 1024));
         }
         if constexpr (DUAL) {  // the second input's rows, in the same operand image as t2
 #pragma unroll
             for (int j = 0; j < T2P / G::WAVES; ++j) {
                 const int q = G::WAVES * j + wave, r = 8 * q + (lane >> 3), pc = lane & 7, m = m0 + r;
-                dma16((live && m < p.M) ? m * 128 + ((pc ^ ((r >> 1) & 7)) << 4) : kOob, srd_x, 0,
+                dma16((live && m < p.M) ? m * 128 + (RN_SWZ(pc, r) << 4) : kOob, srd_x, 0,
                       lds_base + (unsigned)(G::oX + buf * G::XB + q * 1024));
             }
         } else {
@@ -198,7 +183,7 @@ __global__ __launch_bounds__(64 * Geo<MID>::WAVES) void chain_kernel(const Chain
                 const int kk = second ? ks - MID / 16 : ks;
                 const char *src = second ? lds + G::oX + buf * G::XB : lds + G::oT2 + buf * G::T2B;
                 const i32x4 px = *reinterpret_cast<const i32x4 *>(
-                    src + (kk >> 2) * (ROWS * 128) + r * 128 + (((2 * (kk & 3) + lh) ^ ((r >> 1) & 7)) << 4));
+                    src + (kk >> 2) * (ROWS * 128) + r * 128 + (RN_SWZ(2 * (kk & 3) + lh, r) << 4));
 #pragma unroll
                 for (int f = 0; f < CF1; ++f)
                     acc[pf][f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w3r[f][ks]),
@@ -220,19 +205,15 @@ __global__ __launch_bounds__(64 * Geo<MID>::WAVES) void chain_kernel(const Chain
                     const int c4 = 32 * cf + 8 * j + 4 * lh;
                     const float4 sc = *reinterpret_cast<const float4 *>(ssl + c4);
                     const float4 sh = *reinterpret_cast<const float4 *>(ssl + C + c4);
-                    float v[4] = {fmaf(acc[pf][f][4 * j], sc.x, sh.x), fmaf(acc[pf][f][4 * j + 1], sc.y, sh.y),
-                                  fmaf(acc[pf][f][4 * j + 2], sc.z, sh.z), fmaf(acc[pf][f][4 * j + 3], sc.w, sh.w)};
+                    float4 v = affine4(acc[pf][f], j, sc, sh);
                     if constexpr (!DUAL) {
                         const int chunk = 4 * cf + j;  // 16-byte chunk of the residual row
                         const bf16x4 rv = *reinterpret_cast<const bf16x4 *>(
                             lds + G::oX + buf * G::XB + r * (C * 2) +
                             (((chunk & ~15) | ((chunk & 15) ^ (r & 15))) << 4) + 8 * lh);
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) v[k] = v[k] + (float)rv[k];
+                        v.x = v.x + (float)rv[0], v.y = v.y + (float)rv[1], v.z = v.z + (float)rv[2], v.w = v.w + (float)rv[3];
                     }
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] = fmaxf(v[k], 0.f);
-                    pack4(v, d[j]);
+                    pack_bf16x4(relu4(v), d[j]);
                 }
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
@@ -241,7 +222,7 @@ __global__ __launch_bounds__(64 * Geo<MID>::WAVES) void chain_kernel(const Chain
                     // channels 32cf + 16h + 8lh + {0..7}: chunk 4cf + 2h + lh of the C-channel row
                     const int cy = 4 * cf + 2 * h + lh;
                     *reinterpret_cast<i32x4 *>(lds + G::oY + (cy >> 3) * (ROWS * 128) + r * 128 +
-                                               (((cy & 7) ^ ((r >> 1) & 7)) << 4)) =
+                                               (RN_SWZ(cy & 7, r) << 4)) =
                         i32x4{(int)x0[0], (int)x1[0], (int)x0[1], (int)x1[1]};
                 }
             }
@@ -252,7 +233,7 @@ __global__ __launch_bounds__(64 * Geo<MID>::WAVES) void chain_kernel(const Chain
         for (int i = 0; i < ROWS * (C / 8) / THREADS; ++i) {
             const int g = t + i * THREADS, r = g / (C / 8), c = g % (C / 8), m = m0 + r;
             const i32x4 v = *reinterpret_cast<const i32x4 *>(lds + G::oY + (c >> 3) * (ROWS * 128) + r * 128 +
-                                                             (((c & 7) ^ ((r >> 1) & 7)) << 4));
+                                                             (RN_SWZ(c & 7, r) << 4));
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc_y,
                                                    m < p.M ? m * (C * 2) + (c << 4) : kOob, 0, 0);
         }
@@ -266,7 +247,7 @@ __global__ __launch_bounds__(64 * Geo<MID>::WAVES) void chain_kernel(const Chain
 #pragma unroll
             for (int s2 = 0; s2 < K1S; ++s2) {
                 const i32x4 px = *reinterpret_cast<const i32x4 *>(
-                    lds + G::oY + (s2 >> 2) * (ROWS * 128) + r * 128 + (((2 * (s2 & 3) + lh) ^ ((r >> 1) & 7)) << 4));
+                    lds + G::oY + (s2 >> 2) * (ROWS * 128) + r * 128 + (RN_SWZ(2 * (s2 & 3) + lh, r) << 4));
                 a2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w1r[s2]),
                                                              __builtin_bit_cast(bf16x8, px), a2, 0, 0, 0);
             }
@@ -276,9 +257,7 @@ __global__ __launch_bounds__(64 * Geo<MID>::WAVES) void chain_kernel(const Chain
                 const int c4 = 32 * cf2 + 8 * j + 4 * lh;
                 const float4 sc = *reinterpret_cast<const float4 *>(ssl + 2 * C + c4);
                 const float4 sh = *reinterpret_cast<const float4 *>(ssl + 2 * C + 256 + c4);
-                float v[4] = {fmaxf(fmaf(a2[4 * j], sc.x, sh.x), 0.f), fmaxf(fmaf(a2[4 * j + 1], sc.y, sh.y), 0.f),
-                              fmaxf(fmaf(a2[4 * j + 2], sc.z, sh.z), 0.f), fmaxf(fmaf(a2[4 * j + 3], sc.w, sh.w), 0.f)};
-                pack4(v, d[j]);
+                pack_bf16x4(affine4_relu(a2, j, sc, sh), d[j]);
             }
             const int m = m0 + r;
 #pragma unroll
@@ -323,12 +302,7 @@ __global__ __launch_bounds__(512) void chain32_kernel(const ChainParams p)
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int li = lane & 31, lh = lane >> 5;
     int nst, s0;
-    {
-        const unsigned total = gridDim.x, v = blockIdx.x;
-        const unsigned base = (unsigned)p.nsteps / total, rem = (unsigned)p.nsteps % total;
-        nst = (int)(base + (v < rem ? 1u : 0u));
-        s0 = (int)(v * base + min(v, rem));
-    }
+    dealt_range((unsigned)p.nsteps, gridDim.x, blockIdx.x, &nst, &s0);
     const int pf2 = wave & 1, cf2 = wave >> 1;
     const bool has2 = cf2 < N1F;  // wave-uniform
     u32x4 w3r[2][4], w1r[8][4];
@@ -354,8 +328,8 @@ __global__ __launch_bounds__(512) void chain32_kernel(const ChainParams p)
     }
     const i32x4 srd_t2 = make_srd(p.t2, p.t2_bytes);
     const i32x4 srd_x = make_srd(p.x, p.x_bytes);
-    const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_t1 = __builtin_amdgcn_make_buffer_rsrc(p.t1, 0, p.t1_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_y = make_rsrc(p.y, p.y_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_t1 = make_rsrc(p.t1, p.t1_bytes);
     const unsigned lds_base = (unsigned)(uintptr_t)((lds_void *)lds);
     const int prow = lane >> 3, pc = lane & 7;
 
@@ -365,7 +339,7 @@ __global__ __launch_bounds__(512) void chain32_kernel(const ChainParams p)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int q = 8 * j + wave, r = 8 * (q & 7) + prow, m = m0 + r;
-            dma16((s < nst && m < p.M) ? m * 256 + (q >> 3) * 128 + ((pc ^ ((r >> 1) & 7)) << 4) : kOob, srd_t2, 0,
+            dma16((s < nst && m < p.M) ? m * 256 + (q >> 3) * 128 + (RN_SWZ(pc, r) << 4) : kOob, srd_t2, 0,
                   lds_base + (unsigned)(k32T2 + q * 1024));
         }
     };
@@ -374,7 +348,7 @@ __global__ __launch_bounds__(512) void chain32_kernel(const ChainParams p)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int q = 8 * j + wave, r = 8 * (q & 7) + prow, m = m0 + r;
-            dma16((s < nst && m < p.M) ? m * 1024 + (q >> 3) * 128 + ((pc ^ ((r >> 1) & 7)) << 4) : kOob, srd_x, 0,
+            dma16((s < nst && m < p.M) ? m * 1024 + (q >> 3) * 128 + (RN_SWZ(pc, r) << 4) : kOob, srd_x, 0,
                   lds_base + (unsigned)(k32XY + buf * k32XYB + q * 1024));
         }
     };
@@ -404,7 +378,7 @@ __global__ __launch_bounds__(512) void chain32_kernel(const ChainParams p)
                 for (int ks = 0; ks < 4; ++ks) {
                     const int r = 32 * pf + li;
                     const u32x4 px = *reinterpret_cast<const u32x4 *>(
-                        lds + k32T2 + kt * 8192 + r * 128 + (((2 * ks + lh) ^ ((r >> 1) & 7)) << 4));
+                        lds + k32T2 + kt * 8192 + r * 128 + (RN_SWZ(2 * ks + lh, r) << 4));
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
                         acc[pf] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(w3r[kt][ks][j]),
@@ -420,14 +394,9 @@ __global__ __launch_bounds__(512) void chain32_kernel(const ChainParams p)
                 const int c4 = 32 * wave + 8 * g + 4 * lh;
                 const float4 sc = *reinterpret_cast<const float4 *>(ssl + c4);
                 const float4 sh = *reinterpret_cast<const float4 *>(ssl + 256 + c4);
-                float4 *slot = reinterpret_cast<float4 *>(xy + wave * 8192 + r * 128 + (((2 * g + lh) ^ ((r >> 1) & 7)) << 4));
+                float4 *slot = reinterpret_cast<float4 *>(xy + wave * 8192 + r * 128 + (RN_SWZ(2 * g + lh, r) << 4));
                 const float4 rv = *slot;
-                float4 o;
-                o.x = fmaxf(fmaf(acc[pf][4 * g], sc.x, sh.x) + rv.x, 0.f);
-                o.y = fmaxf(fmaf(acc[pf][4 * g + 1], sc.y, sh.y) + rv.y, 0.f);
-                o.z = fmaxf(fmaf(acc[pf][4 * g + 2], sc.z, sh.z) + rv.z, 0.f);
-                o.w = fmaxf(fmaf(acc[pf][4 * g + 3], sc.w, sh.w) + rv.w, 0.f);
-                *slot = o;
+                *slot = affine4_add_relu(acc[pf], g, sc, sh, rv);
             }
         }
         __syncthreads();
@@ -446,7 +415,7 @@ __global__ __launch_bounds__(512) void chain32_kernel(const ChainParams p)
                     for (int i = i0; i < i0 + 4; ++i) {
                         const int g = tt + i * (kSplit ? 256 : 512), r = g >> 6, c = g & 63, m = m0 + r;
                         const u32x4 v = *reinterpret_cast<const u32x4 *>(xy + (c >> 3) * 8192 + r * 128 +
-                                                                         (((c & 7) ^ ((r >> 1) & 7)) << 4));
+                                                                         (RN_SWZ(c & 7, r) << 4));
                         __builtin_amdgcn_raw_buffer_store_b128(v, rsrc_y, m < p.M ? m * 1024 + (c << 4) : kOob, 0, 0);
                     }
                 }
@@ -464,7 +433,7 @@ __global__ __launch_bounds__(512) void chain32_kernel(const ChainParams p)
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) {
                     const u32x4 px = *reinterpret_cast<const u32x4 *>(
-                        xy + kt * 8192 + r * 128 + (((2 * ks + lh) ^ ((r >> 1) & 7)) << 4));
+                        xy + kt * 8192 + r * 128 + (RN_SWZ(2 * ks + lh, r) << 4));
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
                         a2 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(w1r[kt][ks][j]), __uint_as_float(px[j]),
@@ -476,11 +445,7 @@ __global__ __launch_bounds__(512) void chain32_kernel(const ChainParams p)
                 const int c4 = 32 * cf2 + 8 * g + 4 * lh;
                 const float4 sc = *reinterpret_cast<const float4 *>(ssl + 512 + c4);
                 const float4 sh = *reinterpret_cast<const float4 *>(ssl + 640 + c4);
-                u32x4 o;
-                o[0] = __float_as_uint(fmaxf(fmaf(a2[4 * g], sc.x, sh.x), 0.f));
-                o[1] = __float_as_uint(fmaxf(fmaf(a2[4 * g + 1], sc.y, sh.y), 0.f));
-                o[2] = __float_as_uint(fmaxf(fmaf(a2[4 * g + 2], sc.z, sh.z), 0.f));
-                o[3] = __float_as_uint(fmaxf(fmaf(a2[4 * g + 3], sc.w, sh.w), 0.f));
+                const u32x4 o = __builtin_bit_cast(u32x4, affine4_relu(a2, g, sc, sh));
                 __builtin_amdgcn_raw_buffer_store_b128(o, rsrc_t1, m < p.M ? (m * N1 + c4) * 4 : kOob, 0, 0);
             }
         }
@@ -502,12 +467,7 @@ __global__ __launch_bounds__(512) void chain32_pair_kernel(const ChainParams p)
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int li = lane & 31, lh = lane >> 5;
     int nst, s0;
-    {
-        const unsigned total = gridDim.x, v = blockIdx.x;
-        const unsigned base = (unsigned)p.nsteps / total, rem = (unsigned)p.nsteps % total;
-        nst = (int)(base + (v < rem ? 1u : 0u));
-        s0 = (int)(v * base + min(v, rem));
-    }
+    dealt_range((unsigned)p.nsteps, gridDim.x, blockIdx.x, &nst, &s0);
     const int pf2 = wave & 1, cf2 = wave >> 1;
     const bool has2 = cf2 < 2;  // 64 channels of conv1: four fragments, waves 0-3
     u32x4 w3r[4][4];            // K tiles 0-1: conv3's rows of the panel, 2-3: the downsample's
@@ -521,8 +481,8 @@ __global__ __launch_bounds__(512) void chain32_pair_kernel(const ChainParams p)
     const i32x4 srd_t2 = make_srd(p.t2, p.t2_bytes);
     const i32x4 srd_x = make_srd(p.x, p.x_bytes);
     const i32x4 srd_w1 = make_srd(p.w1, 64 * 256 * 4);
-    const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_t1 = __builtin_amdgcn_make_buffer_rsrc(p.t1, 0, p.t1_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_y = make_rsrc(p.y, p.y_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_t1 = make_rsrc(p.t1, p.t1_bytes);
     const unsigned lds_base = (unsigned)(uintptr_t)((lds_void *)lds);
     const int prow = lane >> 3, pc = lane & 7;
 
@@ -530,7 +490,7 @@ __global__ __launch_bounds__(512) void chain32_pair_kernel(const ChainParams p)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int q = 8 * j + wave, r = 8 * (q & 7) + prow;
-        dma16(r * 1024 + (q >> 3) * 128 + ((pc ^ ((r >> 1) & 7)) << 4), srd_w1, 0,
+        dma16(r * 1024 + (q >> 3) * 128 + (RN_SWZ(pc, r) << 4), srd_w1, 0,
               lds_base + (unsigned)(kP32W1 + q * 1024));
     }
     auto fetch_in = [&](int s) {  // both 64-channel inputs of step s (one buffer each)
@@ -538,7 +498,7 @@ __global__ __launch_bounds__(512) void chain32_pair_kernel(const ChainParams p)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int q = 8 * j + wave, r = 8 * (q & 7) + prow, m = m0 + r;
-            const int off = (s < nst && m < p.M) ? m * 256 + (q >> 3) * 128 + ((pc ^ ((r >> 1) & 7)) << 4) : kOob;
+            const int off = (s < nst && m < p.M) ? m * 256 + (q >> 3) * 128 + (RN_SWZ(pc, r) << 4) : kOob;
             dma16(off, srd_t2, 0, lds_base + (unsigned)(kP32T2 + q * 1024));
             dma16(off, srd_x, 0, lds_base + (unsigned)(kP32X2 + q * 1024));
         }
@@ -562,7 +522,7 @@ __global__ __launch_bounds__(512) void chain32_pair_kernel(const ChainParams p)
                 for (int ks = 0; ks < 4; ++ks) {
                     const int r = 32 * pf + li;
                     const u32x4 px = *reinterpret_cast<const u32x4 *>(
-                        lds + (kt < 2 ? kP32T2 : kP32X2) + (kt & 1) * 8192 + r * 128 + (((2 * ks + lh) ^ ((r >> 1) & 7)) << 4));
+                        lds + (kt < 2 ? kP32T2 : kP32X2) + (kt & 1) * 8192 + r * 128 + (RN_SWZ(2 * ks + lh, r) << 4));
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
                         acc[pf] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(w3r[kt][ks][j]),
@@ -575,12 +535,9 @@ __global__ __launch_bounds__(512) void chain32_pair_kernel(const ChainParams p)
             for (int g = 0; g < 4; ++g) {
                 const int c4 = 32 * wave + 8 * g + 4 * lh;
                 const float4 sh = p.sh3 ? *reinterpret_cast<const float4 *>(p.sh3 + c4) : make_float4(-0.f, -0.f, -0.f, -0.f);
-                float4 o;  // the pair's epilogue: scale folded into the panel, shift, no residual, ReLU
-                o.x = fmaxf(fmaf(acc[pf][4 * g], 1.f, sh.x), 0.f);
-                o.y = fmaxf(fmaf(acc[pf][4 * g + 1], 1.f, sh.y), 0.f);
-                o.z = fmaxf(fmaf(acc[pf][4 * g + 2], 1.f, sh.z), 0.f);
-                o.w = fmaxf(fmaf(acc[pf][4 * g + 3], 1.f, sh.w), 0.f);
-                *reinterpret_cast<float4 *>(lds + kP32Y + wave * 8192 + r * 128 + (((2 * g + lh) ^ ((r >> 1) & 7)) << 4)) = o;
+                // the pair's epilogue: scale folded into the panel, shift, no residual, ReLU
+                const float4 o = affine4_relu(acc[pf], g, make_float4(1.f, 1.f, 1.f, 1.f), sh);
+                *reinterpret_cast<float4 *>(lds + kP32Y + wave * 8192 + r * 128 + (RN_SWZ(2 * g + lh, r) << 4)) = o;
             }
         }
         __syncthreads();
@@ -593,7 +550,7 @@ __global__ __launch_bounds__(512) void chain32_pair_kernel(const ChainParams p)
                 for (int i = i0; i < i0 + 4; ++i) {
                     const int g = t - 256 + i * 256, r = g >> 6, c = g & 63, m = m0 + r;
                     const u32x4 v = *reinterpret_cast<const u32x4 *>(lds + kP32Y + (c >> 3) * 8192 + r * 128 +
-                                                                     (((c & 7) ^ ((r >> 1) & 7)) << 4));
+                                                                     (RN_SWZ(c & 7, r) << 4));
                     __builtin_amdgcn_raw_buffer_store_b128(v, rsrc_y, m < p.M ? m * 1024 + (c << 4) : kOob, 0, 0);
                 }
             }
@@ -609,9 +566,9 @@ __global__ __launch_bounds__(512) void chain32_pair_kernel(const ChainParams p)
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) {
                     const u32x4 px = *reinterpret_cast<const u32x4 *>(
-                        lds + kP32Y + kt * 8192 + r * 128 + (((2 * ks + lh) ^ ((r >> 1) & 7)) << 4));
+                        lds + kP32Y + kt * 8192 + r * 128 + (RN_SWZ(2 * ks + lh, r) << 4));
                     const u32x4 wv = *reinterpret_cast<const u32x4 *>(
-                        lds + kP32W1 + kt * 8192 + wr * 128 + (((2 * ks + lh) ^ ((wr >> 1) & 7)) << 4));
+                        lds + kP32W1 + kt * 8192 + wr * 128 + (RN_SWZ(2 * ks + lh, wr) << 4));
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
                         a2 = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(wv[j]), __uint_as_float(px[j]), a2, 0, 0, 0);
@@ -622,11 +579,7 @@ __global__ __launch_bounds__(512) void chain32_pair_kernel(const ChainParams p)
                 const int c4 = 32 * cf2 + 8 * g + 4 * lh;
                 const float4 sc = p.sc1 ? *reinterpret_cast<const float4 *>(p.sc1 + c4) : make_float4(1.f, 1.f, 1.f, 1.f);
                 const float4 sh = p.sh1 ? *reinterpret_cast<const float4 *>(p.sh1 + c4) : make_float4(-0.f, -0.f, -0.f, -0.f);
-                u32x4 o;
-                o[0] = __float_as_uint(fmaxf(fmaf(a2[4 * g], sc.x, sh.x), 0.f));
-                o[1] = __float_as_uint(fmaxf(fmaf(a2[4 * g + 1], sc.y, sh.y), 0.f));
-                o[2] = __float_as_uint(fmaxf(fmaf(a2[4 * g + 2], sc.z, sh.z), 0.f));
-                o[3] = __float_as_uint(fmaxf(fmaf(a2[4 * g + 3], sc.w, sh.w), 0.f));
+                const u32x4 o = __builtin_bit_cast(u32x4, affine4_relu(a2, g, sc, sh));
                 __builtin_amdgcn_raw_buffer_store_b128(o, rsrc_t1, m < p.M ? (m * 64 + c4) * 4 : kOob, 0, 0);
             }
         }

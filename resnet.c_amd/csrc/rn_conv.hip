@@ -80,69 +80,6 @@ constexpr int ROW_FLOATS = 32;  // LDS row = 128 bytes, addressed as 32 dwords
 // tile order counts as resident (choose_tile_order)
 constexpr int tile_blocks_per_cu(int BM, int BN) { return BM * BN <= 64 * 64 ? 4 : BM * BN <= 64 * 128 ? 3 : 2; }
 
-// Diagnostic time stamps (100 MHz wall clock) of a block's phases; off unless a debug
-// buffer was attached to the context.  Nothing else reads that buffer.
-__device__ __forceinline__ void stamp(unsigned long long *buf, int slot)
-{
-    if (buf && threadIdx.x == 0) buf[(size_t)blockIdx.x * 16 + slot] = wall_clock64();
-}
-// ... and of the shader clock (s_memtime), to read the clock the chip holds inside the K loop
-__device__ __forceinline__ void stamp_cycles(unsigned long long *buf, int slot)
-{
-    if (buf && threadIdx.x == 0) buf[(size_t)blockIdx.x * 16 + slot] = __builtin_amdgcn_s_memtime();
-}
-
-// EPT consecutive output elements of one row: load (residual) / store as one 16-byte access
-template <typename TO>
-struct OutVec;
-template <>
-struct OutVec<float> {
-    static constexpr int EPT = 4;
-    static __device__ __forceinline__ void unpack(const u32x4 &x, float (&v)[4])
-    {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = __uint_as_float(x[j]);
-    }
-    static __device__ __forceinline__ u32x4 pack(const float (&v)[4])
-    {
-        return u32x4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]),
-                     __float_as_uint(v[3])};
-    }
-    static __device__ __forceinline__ float load1(const void *base, size_t idx)
-    {
-        return static_cast<const float *>(base)[idx];
-    }
-    static __device__ __forceinline__ void store1(void *base, size_t idx, float v)
-    {
-        static_cast<float *>(base)[idx] = v;
-    }
-};
-template <>
-struct OutVec<bf16_t> {
-    static constexpr int EPT = 8;
-    static __device__ __forceinline__ void unpack(const u32x4 &r, float (&v)[8])
-    {
-        const bf16x8 x = __builtin_bit_cast(bf16x8, r);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (float)x[j];
-    }
-    static __device__ __forceinline__ u32x4 pack(const float (&v)[8])
-    {
-        bf16x8 x;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = (bf16_t)v[j];  // round to nearest even
-        return __builtin_bit_cast(u32x4, x);
-    }
-    static __device__ __forceinline__ float load1(const void *base, size_t idx)
-    {
-        return (float)static_cast<const bf16_t *>(base)[idx];
-    }
-    static __device__ __forceinline__ void store1(void *base, size_t idx, float v)
-    {
-        static_cast<bf16_t *>(base)[idx] = (bf16_t)v;
-    }
-};
-
 // T: element type of activations and weights; TO: element type of the output (and residual)
 // DUAL: the K loop continues through a second (input, weight-row tail) pair, see GemmParams
 // XK: exact-K small-Cin form (the 7x7x3 stem as K = 147 -> 160 instead of 224), fp32 only
@@ -164,8 +101,8 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
     constexpr int STAGE = (BM + BN) * ROW_FLOATS;
     __shared__ __attribute__((aligned(16))) float lds[2 * STAGE];
 
-    // XCD-aware tile order (bijective for any tile count): virtual block v of total_tiles
-    // gets the v-th tile of its XCD's contiguous range, N tiles of one M panel adjacent.
+    // XCD-aware tile order (xcd_deal): virtual block v of total_tiles gets the v-th tile of its
+    // XCD's contiguous range, N tiles of one M panel adjacent.
     // A block walks v = blockIdx.x, + gridDim.x, ... (persistent when the grid is smaller
     // than the tile count: the next tile's operands are fetched during this tile's epilogue).
     __builtin_amdgcn_s_setprio(3);
@@ -176,8 +113,7 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
         m0_ = (int)(logical / (unsigned)p.tiles_n) * BM;
     };
     auto tile_origin = [&](unsigned v, int &m0_, int &n0_) {
-        const unsigned q = total_tiles >> 3, r = total_tiles & 7, xcd = v & 7;
-        unsigned pos = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (v >> 3);
+        unsigned pos = xcd_deal(total_tiles, v);
         if (p.xg > 0) {
             // position in the (N group, M panel, N tile of the group) order -> logical tile; the tiles past
             // the last whole row of M panels keep their place at the end (a bijection for any tile count)
@@ -225,7 +161,7 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
     // K tile, the K tiles of one kernel row's run of valid taps, the K tiles between two runs, the valid K tiles
     [[maybe_unused]] auto pm_tile = [&](int m0_, int &g_, int &pix_) {
         const int mt = m0_ / BM;
-        g_ = p.HoWo == 1 ? mt : (int)(__umulhi((unsigned)mt, p.mul_hw) >> p.shr_hw);
+        g_ = (int)fast_div((unsigned)mt, p.HoWo, p.mul_hw, p.shr_hw);
         pix_ = mt - g_ * p.HoWo;
     };
     [[maybe_unused]] int pm_kt0 = 0, pm_run = 0, pm_gap = 0, pm_nv = 0;
@@ -233,7 +169,7 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
     // images of the batch, M / HoWo (asked for inside the PM code only: a read of p in the common path moves the
     // kernel-argument loads of every other instantiation)
     [[maybe_unused]] auto pm_images = [&]() {
-        return p.HoWo == 1 ? p.M : (int)(__umulhi((unsigned)p.M, p.mul_hw) >> p.shr_hw);
+        return (int)fast_div((unsigned)p.M, p.HoWo, p.mul_hw, p.shr_hw);
     };
 
     const int t = threadIdx.x;
@@ -243,13 +179,9 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
     // Operands are fetched with buffer loads: the descriptor's range check turns an
     // out-of-range offset into zeros, so a padded tap (or a row past M / Cout) costs
     // one select on the offset instead of a branch around the load.
-    const __amdgpu_buffer_rsrc_t rsrc_a =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.in), 0, p.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_b =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w), 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_a2 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<void *>(DUAL ? p.in2 : p.in), 0, DUAL ? p.in2_bytes : 0, 0x00020000);
-    constexpr int kOob = (int)0x80000000;  // >= num_records for every tensor we accept
+    const __amdgpu_buffer_rsrc_t rsrc_a = make_rsrc(p.in, p.in_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_b = make_rsrc(p.w, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_a2 = make_rsrc(DUAL ? p.in2 : p.in, DUAL ? p.in2_bytes : 0);
 
     // per staged A row: byte offset of tap (0,0) chunk c, and which taps are in bounds:
     // bit kh of the low half = row ih0+kh inside [0,H), bit kw of the high half = column;
@@ -262,7 +194,7 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
             // (no division), and a row's mask only says whether the image exists
             int g, pix;
             pm_tile(m0_, g, pix);
-            const int oh = p.Wo == 1 ? pix : (int)(__umulhi((unsigned)pix, p.mul_w) >> p.shr_w);
+            const int oh = (int)fast_div((unsigned)pix, p.Wo, p.mul_w, p.shr_w);
             const int ow = pix - oh * p.Wo;
             const int ih0 = oh * p.stride - p.pad, iw0 = ow * p.stride - p.pad;
             const int hlo = max(0, -ih0), hhi = min(p.KH, p.H - ih0);
@@ -281,10 +213,7 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
         for (int j = 0; j < (PM ? 0 : AP); ++j) {
             const int m = m0_ + r0 + 32 * j;
             if (m < p.M) {
-                const int b = p.HoWo == 1 ? m : (int)(__umulhi((unsigned)m, p.mul_hw) >> p.shr_hw);
-                const int rem = m - b * p.HoWo;
-                const int oh = p.Wo == 1 ? rem : (int)(__umulhi((unsigned)rem, p.mul_w) >> p.shr_w);
-                const int ow = rem - oh * p.Wo;
+                const auto [b, oh, ow] = row_of(m, p);
                 const int ih0 = oh * p.stride - p.pad;
                 const int iw0 = ow * p.stride - p.pad;
                 // small-Cin forms: this thread's chunk is pixel(s) cc*chunk_dw.. of kernel row
@@ -372,11 +301,11 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
                 for (int j = 0; j < AP; ++j) a_cur[j] = a_off2[DUAL ? j : 0];
             }
         } else {
-            const unsigned tap = p.cseg == 1 ? s_kt : (__umulhi(s_kt, p.mul_cs) >> p.shr_cs);
-            s_cs = (int)(s_kt - tap * (unsigned)p.cseg);
+            const TapSeg ts = tap_of(s_kt, p);
+            s_cs = ts.seg;
             if (first || s_cs == 0) {
-                const unsigned ukh = p.KW == 1 ? tap : (__umulhi(tap, p.mul_kw) >> p.shr_kw);
-                const int s_kh = (int)ukh, s_kw = (int)(tap - ukh * (unsigned)p.KW);
+                const TapRowCol rc = tap_row_col(ts.tap, p);
+                const int s_kh = rc.kh, s_kw = rc.kw;
                 // (DIL, unsigned: a tap that is never inside the image may wrap; its mask bit is clear)
                 const int toff = DIL ? (int)((unsigned)(s_kh * p.W + s_kw) * (unsigned)(p.dil * p.Cs * ES))
                                      : (s_kh * p.tap_rows * p.W + s_kw) * p.Cs * ES;
@@ -404,8 +333,8 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
     };
 
     // LDS addresses are per-thread constants plus compile-time offsets (buffer, row block):
-    // (row >> 1) & 7 of rows r0 + 32j is that of r0, so one base serves every staged row
-    float *const stage_base = lds + r0 * ROW_FLOATS + (c ^ ((r0 >> 1) & 7)) * 4;
+    // the swizzle of rows r0 + 32j is that of r0, so one base serves every staged row
+    float *const stage_base = lds + r0 * ROW_FLOATS + RN_SWZ(c, r0) * 4;
     auto store_tile = [&](auto buf_c, const u32x4 (&xa)[AP], const u32x4 (&xb)[BP]) {
         const int buf = buf_c;  // compile-time (Buf0 / Buf1) or a run-time 0 / 1
 #pragma unroll
@@ -421,7 +350,6 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
     const int lane = t & 63, wave = t >> 6;
     const int wr = wave >> 1, wc = wave & 1;
     const int li = lane & 31, lh = lane >> 5;
-    const int sw = (li >> 1) & 7;  // swizzle term of this lane's fragment rows
 
     f32x16 acc[MI][NI];
     // CHUNK: running total of the finished chunks; fold_acc moves the chunk sum into it (the
@@ -458,7 +386,7 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
     const float *frag_a[4], *frag_b[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-        const int pc = ((2 * ks + lh) ^ sw) * 4;
+        const int pc = RN_SWZ(2 * ks + lh, li) * 4;  // (the swizzle of this lane's fragment rows is that of li)
         frag_a[ks] = lds + (wr * (BM / 2) + li) * ROW_FLOATS + pc;
         frag_b[ks] = lds + BM * ROW_FLOATS + (wc * (BN / 2) + li) * ROW_FLOATS + pc;
     }
@@ -510,12 +438,9 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
     // of every use, which serialised the 8-16 row stores of a tile (stamps: 7-9 us).
     const bool has_scale = p.scale != nullptr, has_shift = p.shift != nullptr;
     const bool has_res = p.residual != nullptr;
-    const __amdgpu_buffer_rsrc_t rsrc_r = __builtin_amdgcn_make_buffer_rsrc(
-        has_res ? const_cast<void *>(p.residual) : p.out, 0, has_res ? p.out_bytes : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_sc = __builtin_amdgcn_make_buffer_rsrc(
-        has_scale ? (void *)const_cast<float *>(p.scale) : p.out, 0, has_scale ? p.Cout * 4 : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_sh = __builtin_amdgcn_make_buffer_rsrc(
-        has_shift ? (void *)const_cast<float *>(p.shift) : p.out, 0, has_shift ? p.Cout * 4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_r = make_rsrc(has_res ? p.residual : p.out, has_res ? p.out_bytes : 0);
+    const __amdgpu_buffer_rsrc_t rsrc_sc = make_rsrc(has_scale ? (const void *)p.scale : p.out, has_scale ? p.Cout * 4 : 0);
+    const __amdgpu_buffer_rsrc_t rsrc_sh = make_rsrc(has_shift ? (const void *)p.shift : p.out, has_shift ? p.Cout * 4 : 0);
     u32x4 resv[PASSES], scv[EPT / 4], shv[EPT / 4];
     // Fetching the residual tile before the K loop hides its latency completely, but its
     // registers stay live across the loop; with 16 passes (fp32 128x128: 64 VGPRs) that
@@ -713,9 +638,7 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
         }
 
         // epilogue.  The accumulators go through LDS (free after the K loop) so that global
-        // traffic is row-contiguous 16-byte accesses: C/D map of the 32x32 MFMA is
-        // col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5); a ds_write_b32 of one register
-        // puts 32 consecutive columns of two rows, conflict-free.
+        // traffic is row-contiguous 16-byte accesses (RN_STAGE_ACC).
         if (vtile == blockIdx.x) {
             stamp_cycles(p.stamps, 9);
             stamp(p.stamps, 2);  // K loop done
@@ -724,11 +647,8 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < NI; ++ni) {
-            float *dst = Cs + (wr * (BM / 2) + mi * 32 + 4 * lh) * BN + wc * (BN / 2) + ni * 32 + li;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) dst[((e & 3) + 8 * (e >> 2)) * BN] = acc[mi][ni][e];
-        }
+        for (int ni = 0; ni < NI; ++ni)
+            RN_STAGE_ACC(Cs + (wr * (BM / 2) + mi * 32 + 4 * lh) * BN + wc * (BN / 2) + ni * 32 + li, acc[mi][ni], BN)
     if constexpr (!EARLY_RES) prefetch_epilogue();
     if (vtile == blockIdx.x) stamp(p.stamps, 5);  // accumulators written to LDS (issued)
     __syncthreads();
@@ -738,8 +658,7 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
     const bool raw = CHUNK && ks_idx >= 0;  // a piece: plain chunk sum, no epilogue
     void *const out_base = raw ? static_cast<char *>(p.ws) + (long long)ks_idx * p.ws_stride
                                : static_cast<char *>(p.out) + (long long)ks_idx * p.split_stride;
-    const __amdgpu_buffer_rsrc_t rsrc_o =
-        __builtin_amdgcn_make_buffer_rsrc(out_base, 0, p.out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_o = make_rsrc(out_base, p.out_bytes);
     if (sizeof(TO) == 4 && p.out_nchw && !raw) {
         // NCHW output (drop-in route): lanes along the channels -- conflict-free column reads of
         // the staged tile -- and four consecutive pixels of one channel per 16-byte store.  The
@@ -775,16 +694,14 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
             }
         }
     } else if (vec) {
-        // straight-line: 16-byte LDS read, channel affine, residual, ReLU, 16-byte store per pass.
-        // The two launch-uniform switches (residual, ReLU) pick one of four copies of the loop:
-        // as per-element selects they cost as many vector instructions as the arithmetic itself.
+        // straight-line: 16-byte LDS read, channel affine, residual, ReLU, 16-byte store per pass
+        // (RN_EPILOGUE_ROW), in one of four copies of the loop (RN_WITH_RES_RELU)
         float sc[EPT], sh[EPT];
 #pragma unroll
         for (int j4 = 0; j4 < EPT / 4; ++j4)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 sc[4 * j4 + j] = (has_scale && !raw) ? __uint_as_float(scv[j4][j]) : 1.f;
-                // -0.0 as the neutral addend keeps a -0.0 convolution result bit-exact
                 sh[4 * j4 + j] = (has_shift && !raw) ? __uint_as_float(shv[j4][j]) : -0.f;
             }
         const bool col_ok = n < p.Cout;
@@ -794,23 +711,7 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
             for (int ps = 0; ps < PASSES; ++ps) {
                 const int row = rr + ps * RPP;
                 const int m = m0 + row;
-                float v[EPT], res[EPT];
-                if constexpr (RES) OutVec<TO>::unpack(resv[ps], res);
-#pragma unroll
-                for (int j4 = 0; j4 < EPT / 4; ++j4) {
-                    const float4 x = *reinterpret_cast<const float4 *>(Cs + row * BN + cv * EPT + 4 * j4);
-                    v[4 * j4] = x.x, v[4 * j4 + 1] = x.y, v[4 * j4 + 2] = x.z, v[4 * j4 + 3] = x.w;
-                }
-                // two outputs per instruction: v_pk_fma_f32 / v_pk_add_f32 (the same IEEE results)
-                typedef float f32x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-                for (int j = 0; j < EPT; j += 2) {
-                    f32x2 y = __builtin_elementwise_fma(f32x2{v[j], v[j + 1]}, f32x2{sc[j], sc[j + 1]},
-                                                        f32x2{sh[j], sh[j + 1]});
-                    if constexpr (RES) y = y + f32x2{res[j], res[j + 1]};
-                    v[j] = RELU ? fmaxf(y[0], 0.f) : y[0];
-                    v[j + 1] = RELU ? fmaxf(y[1], 0.f) : y[1];
-                }
+                RN_EPILOGUE_ROW(TO, RES, RELU, Cs + row * BN + cv * EPT, resv[ps], sc, sh, v)
                 int off;
                 if constexpr (PM) {
                     int mp;
@@ -823,13 +724,7 @@ __global__ __launch_bounds__(256, tile_blocks_per_cu(BM, BN)) void conv_gemm_ker
             }
         };
         const bool do_res = has_res && !raw, do_relu = p.relu && !raw;
-        if (do_res) {
-            if (do_relu) rows_out(std::true_type{}, std::true_type{});
-            else rows_out(std::true_type{}, std::false_type{});
-        } else {
-            if (do_relu) rows_out(std::false_type{}, std::true_type{});
-            else rows_out(std::false_type{}, std::false_type{});
-        }
+        RN_WITH_RES_RELU(do_res, do_relu, rows_out(with_res, with_relu))
     } else if (n < p.Cout) {
         // ragged channel count (Cout % EPT != 0): element-wise, rare
         for (int ps = 0; ps < PASSES; ++ps) {

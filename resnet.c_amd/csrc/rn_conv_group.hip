@@ -92,10 +92,7 @@ __global__ __launch_bounds__(256) void conv_group_kernel(const GroupParams p)
         a_off[mt] = 0;
         a_mask[mt] = 0;
         if (m < p.M) {
-            const int b = p.HoWo == 1 ? m : (int)(__umulhi((unsigned)m, p.mul_hw) >> p.shr_hw);
-            const int rem = m - b * p.HoWo;
-            const int oh = p.Wo == 1 ? rem : (int)(__umulhi((unsigned)rem, p.mul_w) >> p.shr_w);
-            const int ow = rem - oh * p.Wo;
+            const auto [b, oh, ow] = rn_gemm::row_of(m, p);
             const int ih0 = oh * p.stride - p.pad, iw0 = ow * p.stride - p.pad;
             a_off[mt] = ((long long)(b * p.H + ih0) * p.W + iw0) * p.C + cin0 + 4 * h;
             if constexpr (!DIL) {

@@ -79,28 +79,19 @@ __global__ __launch_bounds__(256, 2) void conv_nchw_kernel(const NchwParams p)
     constexpr int WT = BM * 32, XT = 32 * BN;  // floats of one staged tile
     constexpr int WP = BM / 32, XP = BN / 32;  // 16-byte pieces per thread and K tile
     __shared__ __attribute__((aligned(16))) float lds[2 * (WT + XT)];
-    constexpr int kOob = (int)0x80000000;
 
     // XCD-aware tile order: each XCD takes a contiguous range of tiles, the output-channel tiles of
     // one pixel tile adjacent (they re-read the same X panel from that XCD's L2)
-    unsigned m0, q0;
-    {
-        const unsigned v = blockIdx.x, tt = p.total_tiles;
-        const unsigned q = tt >> 3, r = tt & 7, xcd = v & 7;
-        const unsigned logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (v >> 3);
-        m0 = (logical % p.tiles_m) * BM;
-        q0 = (logical / p.tiles_m) * BN;
-    }
+    const unsigned logical = xcd_deal(p.total_tiles, blockIdx.x);
+    const unsigned m0 = (logical % p.tiles_m) * BM, q0 = (logical / p.tiles_m) * BN;
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int li = lane & 31, lh = lane >> 5;
 
-    const __amdgpu_buffer_rsrc_t rsrc_w =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.w), 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_x =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.in), 0, p.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_o = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, p.out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_w = make_rsrc(p.w, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_x = make_rsrc(p.in, p.in_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_o = make_rsrc(p.out, p.out_bytes);
 
     // staging: W piece j = row (t >> 3) + 32 j, chunk t & 7; X piece j = channel (t / (BN/4)) + (1024/BN) j
     // ... of the K tile, pixels 4 (t % (BN/4)) ..
@@ -121,10 +112,10 @@ __global__ __launch_bounds__(256, 2) void conv_nchw_kernel(const NchwParams p)
     bool g_ok = false;
     {
         const unsigned q = q0 + (GATHER ? (unsigned)xq : 4u * (unsigned)xq);
-        const unsigned b = p.HW == 1 ? q : __umulhi(q, p.mul_hw) >> p.shr_hw;  // (rn_fast_div leaves d = 1 to the kernel)
+        const unsigned b = fast_div(q, p.HW, p.mul_hw, p.shr_hw);
         const unsigned pp = q - b * (unsigned)p.HW;
         if constexpr (GATHER) {  // output pixel -> input pixel of tap (0, 0)
-            const unsigned oh = p.Wo == 1 ? pp : __umulhi(pp, p.mul_wo) >> p.shr_wo, ow = pp - oh * (unsigned)p.Wo;
+            const unsigned oh = fast_div(pp, p.Wo, p.mul_wo, p.shr_wo), ow = pp - oh * (unsigned)p.Wo;
             g_ih0 = (int)oh * p.stride - p.pad;
             g_iw0 = (int)ow * p.stride - p.pad;
             g_ok = q < p.Q;
@@ -167,7 +158,7 @@ __global__ __launch_bounds__(256, 2) void conv_nchw_kernel(const NchwParams p)
 #pragma unroll
         for (int j = 0; j < WP; ++j) {
             const int row = wr0 + 32 * j;
-            *reinterpret_cast<u32x4 *>(wl + row * 32 + ((wc ^ ((row >> 1) & 7)) << 2)) = rw[j];
+            *reinterpret_cast<u32x4 *>(wl + row * 32 + (RN_SWZ(wc, row) << 2)) = rw[j];
         }
         if constexpr (GATHER) {
 #pragma unroll
@@ -185,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void conv_nchw_kernel(const NchwParams p)
         for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f, tot[mi][ni][e] = 0.f;
-    const int sw = (li >> 1) & 7;
+    const int sw = RN_SWZ(0, li);  // swizzle term of this lane's fragment rows: chunk c lies in chunk c ^ sw
     auto compute_tile = [&](int buf) {
         const float *wl = lds + buf * (WT + XT), *xl = wl + WT;
 #pragma unroll
@@ -254,7 +245,7 @@ __global__ __launch_bounds__(256, 2) void conv_nchw_kernel(const NchwParams p)
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni) {
         const unsigned q = q0 + (unsigned)(wn * 64 + ni * 32 + li);
-        const unsigned b = p.HW == 1 ? q : __umulhi(q, p.mul_hw) >> p.shr_hw, pp = q - b * (unsigned)p.HW;
+        const unsigned b = fast_div(q, p.HW, p.mul_hw, p.shr_hw), pp = q - b * (unsigned)p.HW;
         const unsigned obase = b * (unsigned)p.Cout * (unsigned)p.HW + pp;
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)

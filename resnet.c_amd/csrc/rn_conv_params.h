@@ -1,6 +1,8 @@
-// Parameters and small types shared by the contraction kernels (rn_conv.hip: the 4-wave
-// kernels for fp32 and bf16; rn_conv_wide.hip: the 8-wave LDS-DMA kernels for bf16 -- 256-wide
-// tiles and the strip kernel).
+// Parameters and small types shared by the contraction kernels: rn_conv.hip (the 4-wave kernels for
+// fp32 and bf16), rn_conv_wide.hip (the 8-wave LDS-DMA kernels for bf16 -- 256-wide tiles and the strip
+// kernels), rn_chain.hip (conv3 + conv1 chains), rn_conv_group.hip (grouped 3x3), rn_conv_nchw.hip (fp32
+// on NCHW tensors) and rn_stem.hip (the fused stem).  The device-side helpers they share are in rn_tile.h,
+// included below.
 #ifndef RN_CONV_PARAMS_H
 #define RN_CONV_PARAMS_H
 
@@ -116,6 +118,9 @@ __device__ __forceinline__ int tap_mask(int x0, int K, int X, int d)
 
 }  // namespace rn_gemm
 
+#include "rn_tile.h"
+
+// Host side of the kernels' fast_div (rn_tile.h):
 // n / d == umulhi(n, mul) >> shr for 0 <= n < 2^31, d >= 1 (round-up magic number)
 inline void rn_fast_div(unsigned d, unsigned *mul, unsigned *shr)
 {

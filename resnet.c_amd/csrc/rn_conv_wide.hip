@@ -42,26 +42,6 @@ namespace {
 
 using namespace rn_dma;
 
-template <typename TO>
-struct Out;
-template <>
-struct Out<bf16_t> {
-    static constexpr int EPT = 8;
-    static __device__ __forceinline__ void unpack(const i32x4 &r, float (&v)[8])
-    {
-        const bf16x8 x = __builtin_bit_cast(bf16x8, r);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (float)x[j];
-    }
-    static __device__ __forceinline__ i32x4 pack(const float (&v)[8])
-    {
-        bf16x8 x;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = (bf16_t)v[j];  // round to nearest even
-        return __builtin_bit_cast(i32x4, x);
-    }
-};
-
 // BM x BN block tile, WM x WN waves (WM * WN == 8), DUAL as in conv_gemm_kernel.
 // LDS_CAP: the block's LDS budget.  All of the CU's 160 KB for the 256-wide tiles (one block per CU);
 // 80 KB for the 128x128 tile, so that TWO blocks share a CU (four waves per SIMD, 128 registers each)
@@ -91,16 +71,10 @@ __global__ __launch_bounds__(512, LDS_CAP <= 80 * 1024 ? 4 : 2) void conv_wide_k
     __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
 
     stamp(p.stamps, 0);
-    // XCD-aware tile order, as conv_gemm_kernel: each XCD walks a contiguous range of tiles with
-    // the N tiles of one M panel adjacent
-    int m0, n0;
-    {
-        const unsigned total = p.total_tiles, v = blockIdx.x;
-        const unsigned q = total >> 3, r = total & 7, xcd = v & 7;
-        const unsigned logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (v >> 3);
-        n0 = (int)(logical % (unsigned)p.tiles_n) * BN;
-        m0 = (int)(logical / (unsigned)p.tiles_n) * BM;
-    }
+    // XCD-aware tile order, as conv_gemm_kernel: the N tiles of one M panel adjacent
+    const unsigned logical = xcd_deal(p.total_tiles, blockIdx.x);
+    const int n0 = (int)(logical % (unsigned)p.tiles_n) * BN;
+    const int m0 = (int)(logical / (unsigned)p.tiles_n) * BM;
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wave / WN, wn = wave % WN;
@@ -113,7 +87,7 @@ __global__ __launch_bounds__(512, LDS_CAP <= 80 * 1024 ? 4 : 2) void conv_wide_k
 
     // DMA geometry: piece q = 8*j + wave of an operand tile covers tile rows 8q .. 8q+7; lane l
     // fills (row 8q + l/8, physical chunk l%8) and therefore fetches logical chunk
-    // (l%8) ^ ((row>>1)&7).  Per piece and lane: byte offset of tap (0,0) of the row, and which
+    // RN_SWZ(l%8, row).  Per piece and lane: byte offset of tap (0,0) of the row, and which
     // taps are inside the image (bit kh of the low half, bit kw of the high half).
     const int prow = lane >> 3, pc = lane & 7;
     int a_off[PA], a_mask[PA], a_cur[PA], b_off[PB];
@@ -121,13 +95,10 @@ __global__ __launch_bounds__(512, LDS_CAP <= 80 * 1024 ? 4 : 2) void conv_wide_k
 #pragma unroll
     for (int j = 0; j < PA; ++j) {
         const int r = 8 * (8 * j + wave) + prow;
-        const int chunk = (pc ^ ((r >> 1) & 7)) * 16;
+        const int chunk = RN_SWZ(pc, r) * 16;
         const int m = m0 + r;
         if (r < BM && m < p.M) {
-            const int b = p.HoWo == 1 ? m : (int)(__umulhi((unsigned)m, p.mul_hw) >> p.shr_hw);
-            const int rem = m - b * p.HoWo;
-            const int oh = p.Wo == 1 ? rem : (int)(__umulhi((unsigned)rem, p.mul_w) >> p.shr_w);
-            const int ow = rem - oh * p.Wo;
+            const auto [b, oh, ow] = row_of(m, p);
             const int ih0 = oh * p.stride - p.pad, iw0 = ow * p.stride - p.pad;
             a_off[j] = ((b * p.H + ih0) * p.W + iw0) * p.Cs * 2 + chunk;
             const int rlo = max(0, -ih0), rhi = min(p.KH, p.H - ih0);
@@ -152,7 +123,7 @@ __global__ __launch_bounds__(512, LDS_CAP <= 80 * 1024 ? 4 : 2) void conv_wide_k
     for (int j = 0; j < PB; ++j) {
         const int r = 8 * (8 * j + wave) + prow;
         const int n = n0 + r;
-        b_off[j] = n < p.Cout ? n * p.Ktot * 2 + (pc ^ ((r >> 1) & 7)) * 16 : kOob;
+        b_off[j] = n < p.Cout ? n * p.Ktot * 2 + RN_SWZ(pc, r) * 16 : kOob;
     }
 
     // K tile kt of A into ring slot `slot`.  The K position (tap, 128-byte segment) is scalar
@@ -175,11 +146,11 @@ __global__ __launch_bounds__(512, LDS_CAP <= 80 * 1024 ? 4 : 2) void conv_wide_k
                 for (int j = 0; j < PA; ++j) a_cur[j] = a_off2[DUAL ? j : 0];
             }
         } else {
-            const unsigned tap = p.cseg == 1 ? s_kt : (__umulhi(s_kt, p.mul_cs) >> p.shr_cs);
-            s_cs = (int)(s_kt - tap * (unsigned)p.cseg);
+            const TapSeg ts = tap_of(s_kt, p);
+            s_cs = ts.seg;
             if (s_cs == 0) {
-                const unsigned ukh = p.KW == 1 ? tap : (__umulhi(tap, p.mul_kw) >> p.shr_kw);
-                const int s_kh = (int)ukh, s_kw = (int)(tap - ukh * (unsigned)p.KW);
+                const TapRowCol rc = tap_row_col(ts.tap, p);
+                const int s_kh = rc.kh, s_kw = rc.kw;
                 // tap_rows == 1 (eligibility); unsigned: a dilated tap outside every image may wrap, masked
                 const int toff = (int)((unsigned)(s_kh * p.W + s_kw) * (unsigned)(p.dil * p.Cs * 2));
 #pragma unroll
@@ -230,11 +201,10 @@ __global__ __launch_bounds__(512, LDS_CAP <= 80 * 1024 ? 4 : 2) void conv_wide_k
             for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;
 
     // fragment reads: lane (li, lh) reads chunk 2*ks+lh of its rows -> k = 16ks + 8lh + {0..7},
-    // the operand map of the 32x32x16 MFMA; (row>>1)&7 of rows base+32i+li is that of li
-    const int sw = (li >> 1) & 7;
+    // the operand map of the 32x32x16 MFMA; the swizzle of rows base+32i+li is that of li
     int frag_co[4];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) frag_co[ks] = ((2 * ks + lh) ^ sw) * 16;
+    for (int ks = 0; ks < 4; ++ks) frag_co[ks] = RN_SWZ(2 * ks + lh, li) * 16;
     const int a_thr = (wm * TM + li) * 128, b_thr = SA * A_SLOT + (wn * TN + li) * 128;
     // One K step: fragment reads and MFMAs of tile (sa, sb), and between the MFMA groups of its
     // four k-steps the step's DMA pieces -- piece(i) issues the i-th.  Issued as one block after
@@ -269,7 +239,7 @@ __global__ __launch_bounds__(512, LDS_CAP <= 80 * 1024 ? 4 : 2) void conv_wide_k
     };
     using AllPieces = std::integral_constant<int, PA + PB>;
 
-    constexpr int EPT = Out<TO>::EPT;
+    constexpr int EPT = OutVec<TO>::EPT;
     constexpr int CV = BN / EPT, RPP = 512 / CV, STEPS = EROWS / RPP;
     static_assert(STEPS >= 1 && EROWS % RPP == 0, "epilogue geometry");
     const int cv = t % CV, rr = t / CV;
@@ -277,24 +247,21 @@ __global__ __launch_bounds__(512, LDS_CAP <= 80 * 1024 ? 4 : 2) void conv_wide_k
     const bool col_ok = n < p.Cout;  // Cout % 8 == 0 (eligibility): then n + 8 <= Cout
     const bool has_scale = p.scale != nullptr, has_shift = p.shift != nullptr;
     const bool has_res = p.residual != nullptr;
-    const __amdgpu_buffer_rsrc_t rsrc_r = __builtin_amdgcn_make_buffer_rsrc(
-        has_res ? const_cast<void *>(p.residual) : p.out, 0, has_res ? p.out_bytes : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_sc = __builtin_amdgcn_make_buffer_rsrc(
-        has_scale ? (void *)const_cast<float *>(p.scale) : p.out, 0, has_scale ? p.Cout * 4 : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_sh = __builtin_amdgcn_make_buffer_rsrc(
-        has_shift ? (void *)const_cast<float *>(p.shift) : p.out, 0, has_shift ? p.Cout * 4 : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_o = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, p.out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_r = make_rsrc(has_res ? p.residual : p.out, has_res ? p.out_bytes : 0);
+    const __amdgpu_buffer_rsrc_t rsrc_sc = make_rsrc(has_scale ? (const void *)p.scale : p.out, has_scale ? p.Cout * 4 : 0);
+    const __amdgpu_buffer_rsrc_t rsrc_sh = make_rsrc(has_shift ? (const void *)p.shift : p.out, has_shift ? p.Cout * 4 : 0);
+    const __amdgpu_buffer_rsrc_t rsrc_o = make_rsrc(p.out, p.out_bytes);
     // residual rows of a pass.  (Asking for the first pass's earlier -- during the last K tile, or
     // before the K loop -- was measured on the K = 256 layers: the wait only moves, into the K
     // loop's closing vmcnt(0) or into the first operand tiles' (+2.5 us there); those launches
     // run at the memory system's pace, 3.9 TB/s.)
-    i32x4 resv[STEPS];
+    u32x4 resv[STEPS];
     auto load_res = [&](int row0) {
 #pragma unroll
         for (int s = 0; s < STEPS; ++s) {
             const int m = m0 + row0 + rr + s * RPP;
             const int off = (col_ok && m < p.M && row0 + rr + s * RPP < BM) ? (m * p.Cout + n) * (int)sizeof(TO) : kOob;
-            resv[s] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_r, off, 0, 0));
+            resv[s] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_r, off, 0, 0);
         }
     };
 
@@ -345,9 +312,7 @@ __global__ __launch_bounds__(512, LDS_CAP <= 80 * 1024 ? 4 : 2) void conv_wide_k
     stamp(p.stamps, 2);
 
     // ---- epilogue ----------------------------------------------------------------------------
-    // C/D map of the 32x32 MFMA: col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5); one
-    // ds_write_b32 per register puts 32 consecutive columns of two rows, conflict-free.  Then
-    // 16 bytes of one output row per thread and step: channel affine, residual, ReLU, store.
+    // accumulators -> LDS (stage_acc), then 16 bytes of one output row per thread and step (epilogue_row)
     float sc[EPT], sh[EPT];
 #pragma unroll
     for (int j4 = 0; j4 < EPT / 4; ++j4) {
@@ -358,7 +323,7 @@ __global__ __launch_bounds__(512, LDS_CAP <= 80 * 1024 ? 4 : 2) void conv_wide_k
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             sc[4 * j4 + j] = has_scale ? __int_as_float(s4[j]) : 1.f;
-            sh[4 * j4 + j] = has_shift ? __int_as_float(h4[j]) : -0.f;  // -0.0 keeps a -0.0 sum
+            sh[4 * j4 + j] = has_shift ? __int_as_float(h4[j]) : -0.f;
         }
     }
     float *const Cs = reinterpret_cast<float *>(lds);  // [EROWS][BN] fp32
@@ -374,48 +339,23 @@ __global__ __launch_bounds__(512, LDS_CAP <= 80 * 1024 ? 4 : 2) void conv_wide_k
             const int fr = wm * TM + mi * 32 - row0;  // fragment's first row in this pass: wave-uniform
             if (fr < 0 || fr >= EROWS) continue;
 #pragma unroll
-            for (int ni = 0; ni < NI; ++ni) {
-                float *dst = Cs + (fr + 4 * lh) * BN + wn * TN + ni * 32 + li;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) dst[((e & 3) + 8 * (e >> 2)) * BN] = acc[mi][ni][e];
-            }
+            for (int ni = 0; ni < NI; ++ni)
+                RN_STAGE_ACC(Cs + (fr + 4 * lh) * BN + wn * TN + ni * 32 + li, acc[mi][ni], BN)
         }
         __syncthreads();
 #pragma unroll
         for (int s = 0; s < STEPS; ++s) {
             const int row = rr + s * RPP;
             const int m = m0 + row0 + row;
-            float v[EPT], res[EPT];
-            if constexpr (RES) Out<TO>::unpack(resv[s], res);
-#pragma unroll
-            for (int j4 = 0; j4 < EPT / 4; ++j4) {
-                const float4 x = *reinterpret_cast<const float4 *>(Cs + row * BN + cv * EPT + 4 * j4);
-                v[4 * j4] = x.x, v[4 * j4 + 1] = x.y, v[4 * j4 + 2] = x.z, v[4 * j4 + 3] = x.w;
-            }
-            // two outputs per instruction: v_pk_fma_f32 / v_pk_add_f32 (the same IEEE results)
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-            for (int j = 0; j < EPT; j += 2) {
-                f32x2 y = __builtin_elementwise_fma(f32x2{v[j], v[j + 1]}, f32x2{sc[j], sc[j + 1]},
-                                                    f32x2{sh[j], sh[j + 1]});
-                if constexpr (RES) y = y + f32x2{res[j], res[j + 1]};
-                v[j] = RELU ? fmaxf(y[0], 0.f) : y[0];
-                v[j + 1] = RELU ? fmaxf(y[1], 0.f) : y[1];
-            }
+            RN_EPILOGUE_ROW(TO, RES, RELU, Cs + row * BN + cv * EPT, resv[s], sc, sh, v)
             const int off = (col_ok && m < p.M && row0 + row < BM) ? (m * p.Cout + n) * (int)sizeof(TO) : kOob;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, Out<TO>::pack(v)), rsrc_o, off, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(OutVec<TO>::pack(v), rsrc_o, off, 0, 0);
         }
     };
 #pragma unroll
     for (int pass = 0; pass < CPASS; ++pass) {
         const int row0 = pass * EROWS;  // first tile row of this pass
-        if (has_res) {
-            if (p.relu) read_back(row0, std::true_type{}, std::true_type{});
-            else read_back(row0, std::true_type{}, std::false_type{});
-        } else {
-            if (p.relu) read_back(row0, std::false_type{}, std::true_type{});
-            else read_back(row0, std::false_type{}, std::false_type{});
-        }
+        RN_WITH_RES_RELU(has_res, p.relu, read_back(row0, with_res, with_relu))
         if (pass + 1 < CPASS) __syncthreads();
     }
     if (p.stamps) {
@@ -490,12 +430,45 @@ struct StripParams {
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // v[c] += the c-th of four bf16 values packed low half first (the widening is exact, the sum one fp32 add)
-__device__ __forceinline__ void add_bf16x4(float (&v)[4], const u32x2 r)
+__device__ __forceinline__ void add_bf16x4(float4 &v, const u32x2 r)
 {
-    v[0] += __uint_as_float(r[0] << 16);
-    v[1] += __uint_as_float(r[0] & 0xffff0000u);
-    v[2] += __uint_as_float(r[1] << 16);
-    v[3] += __uint_as_float(r[1] & 0xffff0000u);
+    v.x += __uint_as_float(r[0] << 16);
+    v.y += __uint_as_float(r[0] & 0xffff0000u);
+    v.z += __uint_as_float(r[1] << 16);
+    v.w += __uint_as_float(r[1] & 0xffff0000u);
+}
+
+// padded position u -> pixel index of the NHWC tensor, or -1 for a padding position
+__device__ __forceinline__ int pixel_of(const StripParams &p, int u)
+{
+    if (u < 0 || u >= p.U) return -1;
+    const unsigned R = __umulhi((unsigned)u, p.mul_wp) >> p.shr_wp;
+    const int cc = u - (int)R * p.Wp;
+    const unsigned b = __umulhi(R, p.mul_hq) >> p.shr_hq;
+    const int rr = (int)R - (int)b * p.Hq;
+    if (cc < 1 || cc > p.W || rr < 1) return -1;
+    return ((int)b * p.H + rr - 1) * p.W + cc - 1;
+}
+
+// store q = 2i + h of a step's results: the h-th 16 bytes of fragment i's pixel (32 bytes per lane)
+template <int N>
+__device__ __forceinline__ void store_piece(const i32x4 (&pend)[N][2], const int (&pend_off)[N],
+                                            __amdgpu_buffer_rsrc_t rsrc_o, int q)
+{
+    const int i = q >> 1, h = q & 1;
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pend[i][h]), rsrc_o,
+                                           pend_off[i] == kOob ? kOob : pend_off[i] + 32 * h, 0, 0);
+}
+
+// channels 4j .. 4j+3 of an accumulator's pixel: affine (+ residual in fp32) + ReLU, one rounding to bf16
+template <bool RES>
+__device__ __forceinline__ void finish4(const f32x16 &acc, int j, const float4 sc, const float4 sh, const u32x2 res,
+                                        int relu, unsigned (&d)[2])
+{
+    float4 v = affine4(acc, j, sc, sh);
+    if constexpr (RES) add_bf16x4(v, res);
+    d[0] = pack_bf16x2(relu ? fmaxf(v.x, 0.f) : v.x, relu ? fmaxf(v.y, 0.f) : v.y);
+    d[1] = pack_bf16x2(relu ? fmaxf(v.z, 0.f) : v.z, relu ? fmaxf(v.w, 0.f) : v.w);
 }
 
 constexpr int kRing = 640;       // positions in the LDS ring (5 x 128: 256-position steps wrap every 5)
@@ -517,24 +490,19 @@ __global__ __launch_bounds__(512, 2) void conv_strip_kernel(const StripParams p)
     // this block's steps: XCD-aware order (neighbouring ranges, which share their halo rows,
     // on one XCD's L2), remainder steps to the first blocks
     int nst, ub;
-    {
-        const unsigned total = gridDim.x, v = blockIdx.x;
-        const unsigned q = total >> 3, r = total & 7, xcd = v & 7;
-        const unsigned logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (v >> 3);
-        const unsigned base = (unsigned)p.nsteps / total, rem = (unsigned)p.nsteps % total;
-        nst = (int)(base + (logical < rem ? 1u : 0u));
-        ub = (int)(logical * base + min(logical, rem)) * 256;
+    {  // (first padded position: first step x positions per step)
+        dealt_range((unsigned)p.nsteps, gridDim.x, xcd_deal(gridDim.x, blockIdx.x), &nst, &ub);
+        ub *= 256;
     }
 
     if (t < 64) {
         ssl[t] = p.scale ? p.scale[t] : 1.f;
-        ssl[64 + t] = p.shift ? p.shift[t] : -0.f;  // -0.0 keeps a -0.0 sum
+        ssl[64 + t] = p.shift ? p.shift[t] : -0.f;
     }
 
     const i32x4 srd_in = make_srd(p.in, p.in_bytes);
-    const __amdgpu_buffer_rsrc_t rsrc_o = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, p.out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_r =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.residual), 0, RES ? p.out_bytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_o = make_rsrc(p.out, p.out_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_r = make_rsrc(p.residual, RES ? p.out_bytes : 0);
     const unsigned lds_base = (unsigned)(uintptr_t)((lds_void *)lds);
 
     // Weights: 72 KB, the same for every block.  Fetched coalesced (1-KiB DMA pieces) and picked
@@ -556,21 +524,11 @@ __global__ __launch_bounds__(512, 2) void conv_strip_kernel(const StripParams p)
         }
     }
 
-    // padded position u -> pixel index of the NHWC tensor, or -1 for a padding position
-    auto pixel_of = [&](int u) -> int {
-        if (u < 0 || u >= p.U) return -1;
-        const unsigned R = __umulhi((unsigned)u, p.mul_wp) >> p.shr_wp;
-        const int cc = u - (int)R * p.Wp;
-        const unsigned b = __umulhi(R, p.mul_hq) >> p.shr_hq;
-        const int rr = (int)R - (int)b * p.Hq;
-        if (cc < 1 || cc > p.W || rr < 1) return -1;
-        return ((int)b * p.H + rr - 1) * p.W + cc - 1;
-    };
     // source offset of this lane's 16 bytes of a DMA piece: ring position `slot` holds padded
-    // position u, physical chunk pc holds logical chunk pc ^ ((slot>>1)&7)
+    // position u, physical chunk pc holds logical chunk RN_SWZ(pc, slot)
     auto src_off = [&](int u, int slot) -> int {
-        const int g = pixel_of(u);
-        return g < 0 ? kOob : g * 128 + ((pc ^ ((slot >> 1) & 7)) << 4);
+        const int g = pixel_of(p, u);
+        return g < 0 ? kOob : g * 128 + (RN_SWZ(pc, slot) << 4);
     };
 
     // ring positions 0 .. 383 = padded positions ub - 64 .. ub + 319: all of step 0's
@@ -594,12 +552,6 @@ __global__ __launch_bounds__(512, 2) void conv_strip_kernel(const StripParams p)
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int h = 0; h < 2; ++h) pend[i][h] = i32x4{0, 0, 0, 0};
-    // the four 16-byte stores of a step's results: store q = 2i + h
-    auto store_piece = [&](int q) {
-        const int i = q >> 1, h = q & 1;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pend[i][h]), rsrc_o,
-                                               pend_off[i] == kOob ? kOob : pend_off[i] + 32 * h, 0, 0);
-    };
 
     // diagnostic stamps of step 4 (top, own memory landed, barrier passed, taps done, results packed)
     // and of step 5's end, kept in registers and written when the block is done: a stamp stored
@@ -648,7 +600,7 @@ __global__ __launch_bounds__(512, 2) void conv_strip_kernel(const StripParams p)
                 sb = sb >= kRing ? sb - kRing : sb;
                 const unsigned r0 = (unsigned)(sb + li);
                 const unsigned r = min(r0, r0 - (unsigned)kRing);  // wraps at most once
-                y[tap][i] = (int)((r << 7) | (((unsigned)lh ^ ((r >> 1) & 7u)) << 4));
+                y[tap][i] = (int)((r << 7) | (RN_SWZ((unsigned)lh, r) << 4));
             }
             return *reinterpret_cast<const i32x4 *>(lds + (y[tap][i] ^ (ks << 5)));
         };
@@ -670,7 +622,7 @@ __global__ __launch_bounds__(512, 2) void conv_strip_kernel(const StripParams p)
                 if (n < 32)
                     dma16(nxt_off[n >> 3], srd_in, 0, (unsigned)__builtin_amdgcn_readfirstlane((int)nxt_dst[n >> 3]));
                 else if (n < 64)
-                    store_piece((n >> 3) - 4);
+                    store_piece(pend, pend_off, rsrc_o, (n >> 3) - 4);
             }
         }
         if (s == 4) tk[3] = wall_clock64();
@@ -680,7 +632,7 @@ __global__ __launch_bounds__(512, 2) void conv_strip_kernel(const StripParams p)
         // so that each lane owns channels 32nf + 16h + 8lh + {0..7}: two 16-byte stores per fragment.
         int gpx[2];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) gpx[i] = pixel_of(ub + 256 * s + 64 * mq + 32 * i + li);
+        for (int i = 0; i < 2; ++i) gpx[i] = pixel_of(p, ub + 256 * s + 64 * mq + 32 * i + li);
         u32x2 rres[2][4];
         if constexpr (RES) {
 #pragma unroll
@@ -697,17 +649,7 @@ __global__ __launch_bounds__(512, 2) void conv_strip_kernel(const StripParams p)
             for (int j = 0; j < 4; ++j) {
                 const float4 sc = *reinterpret_cast<const float4 *>(ssl + 32 * nf + 8 * j + 4 * lh);
                 const float4 sh = *reinterpret_cast<const float4 *>(ssl + 64 + 32 * nf + 8 * j + 4 * lh);
-                float v[4] = {fmaf(acc[i][4 * j], sc.x, sh.x), fmaf(acc[i][4 * j + 1], sc.y, sh.y),
-                              fmaf(acc[i][4 * j + 2], sc.z, sh.z), fmaf(acc[i][4 * j + 3], sc.w, sh.w)};
-                if constexpr (RES) add_bf16x4(v, rres[i][j]);
-                typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    bf16x2 o;
-                    o[0] = (bf16_t)(p.relu ? fmaxf(v[2 * c], 0.f) : v[2 * c]);
-                    o[1] = (bf16_t)(p.relu ? fmaxf(v[2 * c + 1], 0.f) : v[2 * c + 1]);
-                    d[j][c] = __builtin_bit_cast(unsigned, o);
-                }
+                finish4<RES>(acc[i], j, sc, sh, rres[i][j], p.relu, d[j]);
             }
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -724,7 +666,7 @@ __global__ __launch_bounds__(512, 2) void conv_strip_kernel(const StripParams p)
     }
     stamp(p.stamps, 10);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) store_piece(q);
+    for (int q = 0; q < 4; ++q) store_piece(pend, pend_off, rsrc_o, q);
     if (p.stamps) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         stamp(p.stamps, 11);
@@ -754,18 +696,13 @@ __global__ __launch_bounds__(256) void conv_strip128_kernel(const StripParams p)
     const int prow = lane >> 3, pc = lane & 7;
     stamp(p.stamps, 0);
     int nst, ub;
-    {
-        const unsigned total = gridDim.x, v = blockIdx.x;
-        const unsigned q = total >> 3, r = total & 7, xcd = v & 7;
-        const unsigned logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (v >> 3);
-        const unsigned base = (unsigned)p.nsteps / total, rem = (unsigned)p.nsteps % total;
-        nst = (int)(base + (logical < rem ? 1u : 0u));
-        ub = (int)(logical * base + min(logical, rem)) * 128;
+    {  // (first padded position: first step x positions per step)
+        dealt_range((unsigned)p.nsteps, gridDim.x, xcd_deal(gridDim.x, blockIdx.x), &nst, &ub);
+        ub *= 128;
     }
     const i32x4 srd_in = make_srd(p.in, p.in_bytes);
-    const __amdgpu_buffer_rsrc_t rsrc_o = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, p.out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_r =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.residual), 0, RES ? p.out_bytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_o = make_rsrc(p.out, p.out_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_r = make_rsrc(p.residual, RES ? p.out_bytes : 0);
     const unsigned lds_base = (unsigned)(uintptr_t)((lds_void *)lds);
 
     // weights: two rounds of 64 output channels; LDS rows of 145 chunks (144 + 1: 145r mod 16 differs
@@ -801,19 +738,10 @@ __global__ __launch_bounds__(256) void conv_strip128_kernel(const StripParams p)
         sh[j] = p.shift ? *reinterpret_cast<const float4 *>(p.shift + c4) : make_float4(-0.f, -0.f, -0.f, -0.f);
     }
 
-    auto pixel_of = [&](int u) -> int {
-        if (u < 0 || u >= p.U) return -1;
-        const unsigned R = __umulhi((unsigned)u, p.mul_wp) >> p.shr_wp;
-        const int cc = u - (int)R * p.Wp;
-        const unsigned b = __umulhi(R, p.mul_hq) >> p.shr_hq;
-        const int rr = (int)R - (int)b * p.Hq;
-        if (cc < 1 || cc > p.W || rr < 1) return -1;
-        return ((int)b * p.H + rr - 1) * p.W + cc - 1;
-    };
     // piece of 8 ring positions starting at ring position slot0, channel segment seg
     auto src_off = [&](int u, int slot, int seg) -> int {
-        const int g = pixel_of(u);
-        return g < 0 ? kOob : g * 256 + seg * 128 + ((pc ^ ((slot >> 1) & 7)) << 4);
+        const int g = pixel_of(p, u);
+        return g < 0 ? kOob : g * 256 + seg * 128 + (RN_SWZ(pc, slot) << 4);
     };
     // ring positions 0 .. 191 = padded positions ub - 32 .. ub + 159: all of step 0's; 48 pieces
 #pragma unroll 1
@@ -827,11 +755,6 @@ __global__ __launch_bounds__(256) void conv_strip128_kernel(const StripParams p)
     int pend_off[4] = {kOob, kOob, kOob, kOob};
 #pragma unroll
     for (int i = 0; i < 4; ++i) pend[i][0] = pend[i][1] = i32x4{0, 0, 0, 0};
-    auto store_piece = [&](int q) {
-        const int i = q >> 1, h = q & 1;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pend[i][h]), rsrc_o,
-                                               pend_off[i] == kOob ? kOob : pend_off[i] + 32 * h, 0, 0);
-    };
 
     int relbase = 0;  // (128 * s) mod 320
     for (int s = 0; s < nst; ++s) {
@@ -870,7 +793,7 @@ __global__ __launch_bounds__(256) void conv_strip128_kernel(const StripParams p)
                 sb = sb >= kRing2 ? sb - kRing2 : sb;
                 const unsigned r0 = (unsigned)(sb + li);
                 const unsigned r = min(r0, r0 - (unsigned)kRing2);
-                y[tap][i] = (int)((r << 7) | (((unsigned)lh ^ ((r >> 1) & 7u)) << 4));
+                y[tap][i] = (int)((r << 7) | (RN_SWZ((unsigned)lh, r) << 4));
             }
             return *reinterpret_cast<const i32x4 *>(lds + seg * kSeg2 + (y[tap][i] ^ (ks << 5)));
         };
@@ -889,14 +812,14 @@ __global__ __launch_bounds__(256) void conv_strip128_kernel(const StripParams p)
                 if (k < 8)
                     dma16(nxt_off[k], srd_in, 0, (unsigned)__builtin_amdgcn_readfirstlane((int)nxt_dst[k]));
                 else if (k < 16)
-                    store_piece(k - 8);
+                    store_piece(pend, pend_off, rsrc_o, k - 8);
             }
         }
 
         if (s == 0) stamp(p.stamps, 3);
         int gpx[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) gpx[i] = pixel_of(ub + 128 * s + 32 * i + li);
+        for (int i = 0; i < 4; ++i) gpx[i] = pixel_of(p, ub + 128 * s + 32 * i + li);
         u32x2 rres[4][4];
         if constexpr (RES) {
 #pragma unroll
@@ -910,19 +833,7 @@ __global__ __launch_bounds__(256) void conv_strip128_kernel(const StripParams p)
         for (int i = 0; i < 4; ++i) {
             unsigned d[4][2];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float v[4] = {fmaf(acc[i][4 * j], sc[j].x, sh[j].x), fmaf(acc[i][4 * j + 1], sc[j].y, sh[j].y),
-                              fmaf(acc[i][4 * j + 2], sc[j].z, sh[j].z), fmaf(acc[i][4 * j + 3], sc[j].w, sh[j].w)};
-                if constexpr (RES) add_bf16x4(v, rres[i][j]);
-                typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    bf16x2 o;
-                    o[0] = (bf16_t)(p.relu ? fmaxf(v[2 * c], 0.f) : v[2 * c]);
-                    o[1] = (bf16_t)(p.relu ? fmaxf(v[2 * c + 1], 0.f) : v[2 * c + 1]);
-                    d[j][c] = __builtin_bit_cast(unsigned, o);
-                }
-            }
+            for (int j = 0; j < 4; ++j) finish4<RES>(acc[i], j, sc[j], sh[j], rres[i][j], p.relu, d[j]);
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const auto x0 = __builtin_amdgcn_permlane32_swap(d[2 * h][0], d[2 * h + 1][0], false, false);
@@ -936,7 +847,7 @@ __global__ __launch_bounds__(256) void conv_strip128_kernel(const StripParams p)
     }
     stamp(p.stamps, 10);
 #pragma unroll
-    for (int q = 0; q < 8; ++q) store_piece(q);
+    for (int q = 0; q < 8; ++q) store_piece(pend, pend_off, rsrc_o, q);
 }
 
 }  // namespace

@@ -1,18 +1,18 @@
-// LDS-DMA helpers shared by the 8-wave bf16 kernels (rn_conv_wide.hip, rn_chain.hip): buffer
-// descriptor, the buffer_load ... lds wave instruction, the counted wait + barrier, stamps.
+// LDS-DMA helpers shared by the kernels that fetch operands that way (rn_conv_wide.hip, rn_chain.hip,
+// rn_stem.hip): buffer descriptor, the buffer_load ... lds wave instruction, the counted wait + barrier.
 #ifndef RN_LDS_DMA_H
 #define RN_LDS_DMA_H
 
-#include "rn_internal.h"
+#include "rn_conv_params.h"
 
 namespace rn_dma {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void;
 
-constexpr int kOob = (int)0x80000000;  // >= num_records of every tensor we accept
+using rn_gemm::kOob;
 
-// buffer descriptor in four SGPRs for the inline-asm DMA (raw buffer, no swizzle, 32-bit offsets)
+// buffer descriptor in four SGPRs for the inline-asm DMA (what make_rsrc builds for the buffer builtins)
 __device__ __forceinline__ i32x4 make_srd(const void *ptr, int bytes)
 {
     const unsigned long long a = (unsigned long long)ptr;
@@ -20,7 +20,7 @@ __device__ __forceinline__ i32x4 make_srd(const void *ptr, int bytes)
     r[0] = (int)(unsigned)a;
     r[1] = (int)((unsigned)(a >> 32) & 0xffffu);
     r[2] = bytes;
-    r[3] = 0x00020000;
+    r[3] = rn_gemm::kRawBuffer;
     return r;
 }
 
@@ -49,16 +49,6 @@ __device__ __forceinline__ void wait_and_barrier()
 {
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
     __builtin_amdgcn_sched_barrier(0);
-}
-
-__device__ __forceinline__ void stamp(unsigned long long *buf, int slot)
-{
-    if (buf && threadIdx.x == 0) buf[(size_t)blockIdx.x * 16 + slot] = wall_clock64();
-}
-
-__device__ __forceinline__ void stamp_cycles(unsigned long long *buf, int slot)
-{
-    if (buf && threadIdx.x == 0) buf[(size_t)blockIdx.x * 16 + slot] = __builtin_amdgcn_s_memtime();
 }
 
 }  // namespace rn_dma

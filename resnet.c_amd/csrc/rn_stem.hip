@@ -147,9 +147,9 @@ __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const StemParams p)
     const float sc = p.scale ? p.scale[n] : 1.f;
     const float sh = p.shift ? p.shift[n] : 0.f;
     // WRITE_Y: this image of the stem tensor (Ho x Wo x 64 fp32: below 2^31 bytes, checked by the launcher)
-    [[maybe_unused]] const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(
-        WRITE_Y ? static_cast<char *>(p.y) + (size_t)b * p.Ho * p.Wo * kCout * 4 : nullptr, 0,
-        WRITE_Y ? p.Ho * p.Wo * kCout * 4 : 0, 0x00020000);
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t rsrc_y =
+        make_rsrc(WRITE_Y ? static_cast<char *>(p.y) + (size_t)b * p.Ho * p.Wo * kCout * 4 : nullptr,
+                  WRITE_Y ? p.Ho * p.Wo * kCout * 4 : 0);
 
     for (int i = t; i < kRing * ring_row; i += 512) ring[i] = 0u;
     if constexpr (NCHW_IN) {  // the patches' border pixels and pad channel are zero and stay zero

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Device code of one build against another's, as text, from hipcc -S dumps (made as for tools/isa_regs_compare.py).
 
-    python tools/isa_text_compare.py PARENT_DIR THIS_DIR rn_conv ...
+    python tools/isa_text_compare.py [--mnemonics] PARENT_DIR THIS_DIR rn_conv ...
 
 The compiler's per-build hash (__hip_cuid_*) and the function number in local labels (.LBB<n>_3) are replaced
 and .file / .ident / .loc lines are dropped.  Then each dump is
@@ -10,9 +10,17 @@ metadata list, and the two builds must hold the same pieces: every instruction, 
 every register count of every kernel; the pixel-major instantiations of conv_gemm_kernel (a fifth template
 flag, true) exist in this tree only and are counted apart, and an instantiation whose fifth flag is false is compared
 under its four-flag name.  The order the compiler emitted the kernels in is reported separately: it
-follows the order the host code first names the instantiations in and is no property of any kernel."""
+follows the order the host code first names the instantiations in and is no property of any kernel.
+
+--mnemonics: the same cut into kernels, but of a kernel's code only the first token of every instruction line --
+the opcode without its operands -- is compared, in order: the two builds must hold the same kernels and every
+kernel the same sequence of mnemonics (same length, same order).  What the full text holds against a build and this
+mode does not: which register the allocator picked, an immediate, a label's number."""
 import re
 import sys
+
+
+FIVE_FLAGS = r"conv_gemm_kernelI\w+?Li\d+ELi\d+E(?:Lb[01]E){5}EEvN7rn_gemm"
 
 
 def pieces(path, parent_names=False):
@@ -45,11 +53,56 @@ def pieces(path, parent_names=False):
     return out
 
 
+def has_five_flags(path):
+    return re.search(FIVE_FLAGS, open(path).read()) is not None
+
+
+def mnemonics(path, parent_names=False):
+    """kernel name -> the mnemonics of its code, from the symbol's label to its s_endpgm / .Lfunc_end"""
+    out = {}
+    for p in pieces(path, parent_names):
+        m = re.search(r"^(\S+):\s*; @\1\n(.*?)^\.Lfunc_endN:", p, re.S | re.M)
+        if not m or ".amdhsa_kernel " + m.group(1) not in p:
+            continue
+        seq = []
+        for l in m.group(2).splitlines():
+            l = l.split(";")[0].strip()
+            if l and not l.startswith(".") and not l.endswith(":"):  # no directive, no label
+                seq.append(l.split()[0])
+        out[m.group(1)] = seq
+    return out
+
+
+def main_mnemonics(a_dir, b_dir, names):
+    bad = 0
+    for n in names:
+        a, b = mnemonics(f"{a_dir}/{n}.s"), mnemonics(f"{b_dir}/{n}.s", parent_names=not has_five_flags(f"{a_dir}/{n}.s"))
+        missing, new = sorted(set(a) - set(b)), sorted(set(b) - set(a))
+        differ = [k for k in a if k in b and a[k] != b[k]]
+        same = not missing and not new and not differ
+        bad += not same
+        print(f"{n}.s: kernels {len(a)} / {len(b)}, missing {len(missing)}, new {len(new)}, mnemonics "
+              f"{sum(map(len, a.values()))} / {sum(map(len, b.values()))}, kernels whose sequence differs {len(differ)}: "
+              f"{'same mnemonics' if same else 'DIFFERENT'}")
+        for k in missing:
+            print("   missing:", k[:150])
+        for k in new:
+            print("   new:", k[:150])
+        for k in differ:
+            at = next((i for i, (x, y) in enumerate(zip(a[k], b[k])) if x != y), min(len(a[k]), len(b[k])))
+            print(f"   differs: {k[:120]}: {len(a[k])} / {len(b[k])} instructions, first difference at {at}: "
+                  f"{' '.join(a[k][at:at + 3])} / {' '.join(b[k][at:at + 3])}")
+    return 1 if bad else 0
+
+
 def main():
+    if sys.argv[1] == "--mnemonics":
+        return main_mnemonics(sys.argv[2], sys.argv[3], sys.argv[4:])
     a_dir, b_dir, names = sys.argv[1], sys.argv[2], sys.argv[3:]
     bad = 0
     for n in names:
-        a, b = pieces(f"{a_dir}/{n}.s"), pieces(f"{b_dir}/{n}.s", parent_names=True)
+        # (a parent that has the fifth flag itself is compared name against name)
+        a, b = pieces(f"{a_dir}/{n}.s"), pieces(f"{b_dir}/{n}.s", parent_names=not has_five_flags(f"{a_dir}/{n}.s"))
         kernels = sum(p.count(".amdhsa_kernel ") for p in a), sum(p.count(".amdhsa_kernel ") for p in b)
         only_a, only_b = set(a) - set(b), set(b) - set(a)
         # kernels only this tree has (the pixel-major instantiations) are reported, not held against it
