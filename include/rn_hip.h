@@ -820,10 +820,60 @@ RN_API int rn_seg_head_finalize(rn_seg_head *hd);
 RN_API int rn_seg_head_destroy(rn_seg_head *hd);
 RN_API int rn_seg_head_forward(rn_seg_head *hd, const void *x_nhwc, uint64_t B, uint64_t h, uint64_t w, uint64_t H,
                                uint64_t W, float *scores_nchw, uint8_t *labels);
+/* Channel concat with a per-image broadcast source, ONE launch: dst [B, pixels, sum(channels) + per_image_channels]
+ * = the n_src (1..8) sources srcs[i] [B, pixels, channels[i]] in order, then per_image [B, per_image_channels]
+ * repeated at every pixel of its image (NULL with per_image_channels == 0: no broadcast).  All of `dtype` (fp32 or
+ * bf16).  A copy in 16-byte units: bit for bit numpy.concatenate, NaN payloads and signed zeros included.  Every
+ * channel count times the element size is a multiple of 16 bytes and every pointer 16-byte aligned, so every source
+ * starts on a 16-byte boundary inside a destination pixel.  B * pixels below 2^31; offsets are 64-bit (B * pixels *
+ * channels may pass 2^31).  Asynchronous on the context's stream, every parameter a kernel argument (capturable).
+ * B == 0 or pixels == 0: RN_OK, nothing launched.  RN_ERR_INVALID, nothing launched: ctx, srcs, channels, dst or a
+ * source NULL, per_image NULL with channels or channels without per_image, n_src 0 or above 8, a channel count of 0
+ * or no multiple of 16 bytes, a pointer off a 16-byte boundary, dst overlapping a source or per_image, an unknown
+ * dtype. */
+RN_API int rn_concat_channels_forward_dt(rn_ctx *ctx, int dtype, uint64_t n_src, const void *const *srcs,
+                                         const uint64_t *channels, const void *per_image /* nullable */,
+                                         uint64_t per_image_channels, void *dst, uint64_t B, uint64_t pixels);
+/* torchvision's DeepLabHead(in_channels, classes) in eval mode as a second kind of rn_seg_head: every function above
+ * but rn_seg_head_create takes either kind, and so do rn_model_forward_segment(_u8).  With a = aspp_channels
+ * (torchvision: 256) and the n = n_rates rates (torchvision: 12, 24, 36):
+ *   branch 0      Conv1x1(in, a) + BatchNorm + ReLU
+ *   branch i      Conv3x3(in, a, padding = dilation = rates[i-1]) + BatchNorm + ReLU, i = 1..n
+ *   pooled        global average over h x w, Conv1x1(in, a) + BatchNorm + ReLU on the [B,1,1,in] result, then the same
+ *                 value at every pixel (torchvision upsamples the 1x1 map bilinearly: a constant map; here a copy)
+ *   concat        branch 0, branches 1..n, pooled: (n + 2) a channels
+ *   project       Conv1x1((n + 2) a, a) + BatchNorm + ReLU (+ Dropout, the identity)
+ *   head          Conv3x3(a, a, padding 1) + BatchNorm + ReLU, Conv1x1(a, classes) with bias, the upsample above
+ * in_channels a multiple of 64 (at most 8192), aspp_channels a multiple of 64 (at most 1024), classes 1..256, n_rates
+ * 1..4, every rate 1..RN_CONV_MAX_DILATION; RN_ERR_INVALID otherwise.  Tensors (rn_seg_head_set_tensor; an unknown
+ * key or a wrong element count is refused with the key in the message): classifier.0.convs.i.0.weight and
+ * classifier.0.convs.i.1.{weight,bias,running_mean,running_var} for i = 0..n; the pooled branch
+ * classifier.0.convs.(n+1).1.weight and classifier.0.convs.(n+1).2.{...} (index 0 of that Sequential is the pool);
+ * classifier.0.project.0.weight, classifier.0.project.1.{...}; classifier.1.weight, classifier.2.{...};
+ * classifier.4.weight, classifier.4.bias.  rn_seg_head_finalize folds every batch-norm (rn_batchnorm2d_fold), packs
+ * every weight (rn_conv2d_pack_weight_dt), pads classes to a multiple of 4 like the FCN kind and packs the centre
+ * tap weight[:, :, 1, 1] of every dilated branch as a 1x1 panel.
+ * A forward is n + 8 launches on public entry points, the folded scale / shift and ReLU in the epilogues: branch 0;
+ * branches 1..n (rn_conv2d_dilated_nhwc_forward_dt); the pool (rn_global_avgpool_nhwc_forward_dt); the pooled 1x1
+ * (h = w = 1, M = B); the concat above; project; the 3x3; the classifier (fp32 output, shift = bias); the upsample.
+ * Scratch, owned and grown like the FCN kind's: per coarse pixel (n + 1) a for the branches, (n + 2) a for the
+ * concat and the padded classes in fp32, per image in + a for the pooled vectors; the projected tensor and the 3x3's
+ * output live in two branch tensors, which are dead behind the concat.
+ * Centre-tap plan: a dilated branch with rate >= h and rate >= w has one tap inside the image for every output
+ * pixel, the centre; such a forward runs that branch as the 1x1 contraction on the centre panel -- a ninth of the
+ * FLOPs, the same bits.  Decided per forward from h and w.  It is taken only where both routes round the sum at the
+ * same places: every bf16 head; an fp32 head only with in_channels == 64 (from 128 on the fp32 3x3 folds its K sum
+ * in chunks that cut the centre tap's range elsewhere than the 1x1 does).  rn_seg_head_set_center_tap(hd, 0 | 1),
+ * default 1, switches the plan (A/B runs); RN_ERR_INVALID on an FCN head. */
+RN_API int rn_seg_head_create_deeplab(rn_ctx *ctx, rn_seg_head **out, uint64_t in_channels, uint64_t aspp_channels,
+                                      uint64_t classes, uint64_t n_rates, const uint64_t *rates);
+RN_API int rn_seg_head_set_center_tap(rn_seg_head *hd, int on);
 /* The label map (and / or the scores) of B images from one forward: exactly the launches and bits of
  * rn_model_forward_outputs -- same sub-batches, parts, front slices, profile records, the classification head
- * included -- plus the head's three launches per launch batch (ops "seg_conv1", "seg_conv2", "seg_upsample" of
- * layer "segmentation" in the profile), queued right behind the last block of layer4 on that block's stream, where
+ * included -- plus the head's launches per launch batch (an FCN head: ops "seg_conv1", "seg_conv2", "seg_upsample"
+ * of layer "segmentation" in the profile; a DeepLab head: "aspp_conv0", "aspp_conv1" .. "aspp_convN" with the FLOPs
+ * of the route that runs, "aspp_pool", "aspp_pool_conv", "aspp_concat", "aspp_project", then those three), queued
+ * right behind the last block of layer4 on that block's stream, where
  * the map still sits in its ping-pong arena (as rn_model_forward_maps exports it).  The outputs are at the model's
  * input size: labels [B,H,W] bytes, scores [B,classes,H,W] fp32 (4-byte aligned), device pointers, either may be
  * NULL.  Every part of a launch batch uses its own slice of the head's scratch, which is sized for one sub-batch

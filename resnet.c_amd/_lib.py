@@ -186,6 +186,10 @@ SIGNATURES = {
     "rn_model_forward_maps_u8": (c_int, [c_void_p, c_void_p, u64, POINTER(ModelOutputs), POINTER(ModelMaps), c_int]),
     "rn_upsample_bilinear_forward": (c_int, [c_void_p, fptr] + [u64] * 7 + [fptr, c_void_p]),
     "rn_seg_head_create": (c_int, [c_void_p, POINTER(c_void_p), u64, u64, u64]),
+    "rn_concat_channels_forward_dt": (c_int, [c_void_p, c_int, u64, POINTER(c_void_p), POINTER(u64), c_void_p, u64,
+                                              c_void_p, u64, u64]),
+    "rn_seg_head_create_deeplab": (c_int, [c_void_p, POINTER(c_void_p), u64, u64, u64, u64, POINTER(u64)]),
+    "rn_seg_head_set_center_tap": (c_int, [c_void_p, c_int]),
     "rn_seg_head_set_dtype": (c_int, [c_void_p, c_int]),
     "rn_seg_head_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, u64]),
     "rn_seg_head_finalize": (c_int, [c_void_p]),

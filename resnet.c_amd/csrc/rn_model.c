@@ -1436,25 +1436,22 @@ static int op_stage_map(rn_model *m, int li, const float *x, uint64_t B, uint64_
  * sub-batch reuses the scratch, as it does for the arenas. */
 static int op_segment(rn_model *m, const float *x, uint64_t B, uint64_t h, uint64_t w)
 {
-    static const char *const ops[3] = {"seg_conv1", "seg_conv2", "seg_upsample"};
-    const uint64_t HW = m->H * m->W, es = elem_size(m);
+    const uint64_t HW = m->H * m->W;
     uint64_t d[4]; /* in, mid, classes, padded classes */
-    double flops[3], bytes[3];
     float *scores;
     uint8_t *labels;
-    int step;
+    int step, steps;
     rn_seg_head_dims(m->seg_head, d);
     scores = m->seg->scores ? m->seg->scores + m->run.img0 * d[2] * HW : NULL;
     labels = m->seg->labels ? m->seg->labels + m->run.img0 * HW : NULL;
-    flops[0] = 2.0 * (double)(B * h * w) * 9.0 * (double)d[0] * (double)d[1];
-    bytes[0] = (double)es * ((double)(B * h * w) * (double)(d[0] + d[1]) + 9.0 * (double)d[0] * (double)d[1]);
-    flops[1] = 2.0 * (double)(B * h * w) * (double)d[1] * (double)d[3];
-    bytes[1] = (double)(B * h * w) * ((double)es * (double)d[1] + 4.0 * (double)d[3]) + (double)es * (double)(d[1] * d[3]);
-    flops[2] = 0.0;
-    bytes[2] = 4.0 * (double)(B * h * w * d[3]) + (double)(B * HW) * ((scores ? 4.0 * (double)d[2] : 0.0) + (labels ? 1.0 : 0.0));
-    for (step = 0; step < 3; ++step) {
-        TRY(prof_begin(m, ops[step], "segmentation", flops[step], bytes[step]));
-        TRY(rn_seg_head_step(m->seg_head, m->run.ctx, step, x, m->run.sub0 * h * w, B, h, w, m->H, m->W, scores, labels));
+    /* the head says what it launches: three steps (FCN) or rates + 8 (DeepLab), with their names, FLOPs and bytes */
+    steps = rn_seg_head_plan(m->seg_head, B, h, w, m->H, m->W, scores != NULL, labels != NULL, -1, NULL, NULL, NULL);
+    for (step = 0; step < steps; ++step) {
+        const char *op = NULL;
+        double flops = 0.0, bytes = 0.0;
+        rn_seg_head_plan(m->seg_head, B, h, w, m->H, m->W, scores != NULL, labels != NULL, step, &op, &flops, &bytes);
+        TRY(prof_begin(m, op, "segmentation", flops, bytes));
+        TRY(rn_seg_head_step(m->seg_head, m->run.ctx, step, x, m->run.sub0, B, h, w, m->H, m->W, scores, labels));
         TRY(prof_end(m));
     }
     return RN_OK;
@@ -1804,7 +1801,7 @@ static int forward_segment(rn_model *m, rn_seg_head *hd, const void *input, int 
     if (!input || B == 0 || (mode != RN_FWD_REFERENCE_OPS && mode != RN_FWD_FUSED)) return RN_ERR_INVALID;
     if (m->dtype != RN_DTYPE_F32 && mode != RN_FWD_FUSED) return RN_ERR_UNSUPPORTED;
     TRY(rn_model_stage_shape(m, 4, NULL, &h, &w));
-    TRY(rn_seg_head_reserve(hd, (B < m->max_sub ? B : m->max_sub) * h * w));
+    TRY(rn_seg_head_reserve(hd, B < m->max_sub ? B : m->max_sub, h * w));
     memset(&none, 0, sizeof(none));
     if (!outs) outs = &none;
     m->seg_head = hd;

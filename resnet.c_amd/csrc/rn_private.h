@@ -52,13 +52,20 @@ int rn_conv_group_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const v
 /* ---- rn_seg.hip: the segmentation head as the model driver queues it ---- */
 /* 1 when the head is finalized and reads maps of in_channels channels of `dtype`; *why: what is wrong otherwise */
 int rn_seg_head_matches(const rn_seg_head *hd, uint64_t in_channels, int dtype, const char **why);
-/* in_channels, mid_channels, classes, and classes rounded up to a multiple of 4 (the coarse scores' pixel pitch) */
+/* in_channels, mid_channels (a DeepLab head: its ASPP width), classes, and classes rounded up to a multiple of 4 (the
+ * coarse scores' pixel pitch) */
 void rn_seg_head_dims(const rn_seg_head *hd, uint64_t dims[4]);
-/* the head's two scratch tensors for `pixels` coarse pixels (images x h x w); grows like the model's logits buffer */
-int rn_seg_head_reserve(rn_seg_head *hd, uint64_t pixels);
-/* launch `step` (0: the 3x3, 1: the 1x1, 2: the upsample) for B images on ctx; their scratch starts pix0 coarse
- * pixels into the head's tensors */
-int rn_seg_head_step(rn_seg_head *hd, rn_ctx *ctx, int step, const void *x_nhwc, uint64_t pix0, uint64_t B, uint64_t h,
+/* The one source of what a forward of the head launches: returns the number of launches of a forward of B images on
+ * an h x w map to H x W (FCN: 3; DeepLab: rates + 8) and, for step 0 .. that - 1, the launch's profile name, FLOPs
+ * and bytes (name, flops, bytes: any may be NULL; another step only counts).  A DeepLab branch reports the route
+ * that runs at this h x w: a ninth of the FLOPs where the centre-tap plan applies. */
+int rn_seg_head_plan(const rn_seg_head *hd, uint64_t B, uint64_t h, uint64_t w, uint64_t H, uint64_t W, int want_scores,
+                     int want_labels, int step, const char **name, double *flops, double *bytes);
+/* the head's scratch for `images` images of `pixels` coarse pixels (h x w) each; grows like the model's logits buffer */
+int rn_seg_head_reserve(rn_seg_head *hd, uint64_t images, uint64_t pixels);
+/* launch `step` of rn_seg_head_plan for B images of an h x w map on ctx; their scratch starts img0 images into the
+ * head's tensors (img0 * h * w coarse pixels into the per-pixel ones, img0 rows into a DeepLab head's pooled vectors) */
+int rn_seg_head_step(rn_seg_head *hd, rn_ctx *ctx, int step, const void *x_nhwc, uint64_t img0, uint64_t B, uint64_t h,
                      uint64_t w, uint64_t H, uint64_t W, float *scores_nchw, uint8_t *labels);
 
 /* ---- rn_stem.hip ---- */

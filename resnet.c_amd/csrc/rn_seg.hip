@@ -1,9 +1,12 @@
 // Semantic segmentation: the bilinear upsample of per-pixel class scores with an optional fused argmax
-// (rn_upsample_bilinear_forward) and torchvision's FCNHead as an object over the library's own convolutions
-// (rn_seg_head_*).  The reference classifies whole images only; nothing here has a counterpart in it.
+// (rn_upsample_bilinear_forward), the channel concat with a per-image broadcast source
+// (rn_concat_channels_forward_dt), and torchvision's FCNHead and DeepLabHead as the two kinds of one object over the
+// library's own convolutions (rn_seg_head_*).  The reference classifies whole images only; nothing here has a
+// counterpart in it.
 #include <stdlib.h>
 #include <string.h>
 
+#include "rn_conv_params.h"
 #include "rn_internal.h"
 #include "rn_private.h"
 
@@ -206,6 +209,53 @@ uint64_t seg_span(float scale, uint64_t t, uint64_t n_in)
     return s < n_in ? s : n_in;
 }
 
+// ---- the channel concat -----------------------------------------------------------------------------------
+// A copy, bound by HBM: one thread moves one 16-byte chunk per trip, consecutive threads consecutive chunks of
+// the destination, so a wave stores 1 KiB in a row and loads runs of a source's pixel (the 256 fp32 channels of
+// an ASPP branch are one such KiB).  256 threads, no LDS, a dozen registers: every CU holds its eight blocks,
+// and the grid is at most the 2048 blocks that fill the chip (rn_stream_grid); a thread then strides on.  A
+// chunk is (pixel, chunk k of the destination pixel); the stride is a fixed (pixels, chunks) pair, so a trip adds
+// it with one carry: no division in the loop but the image of a broadcast chunk, and 64-bit offsets only where an
+// address is formed (B * pixels * channels passes 2^31; B * pixels and the chunks of a pixel do not).
+struct concat_args {
+    const uint4 *src[8];
+    const uint4 *per_image;
+    uint4 *dst;
+    uint32_t end[8];  // chunk of a destination pixel where source i ends (sources past n_src: where the last ends)
+    uint32_t cpp, pc;  // chunks of a destination pixel, of them the broadcast's (the last ones)
+    uint32_t pixels, total_pix;
+    uint32_t mul_cpp, shr_cpp, mul_px, shr_px;
+    uint32_t step_pix, step_k;  // the grid's threads as (pixels, chunks)
+};
+
+__global__ __launch_bounds__(256) void concat_channels_kernel(const concat_args p)
+{
+    const uint32_t gid = blockIdx.x * 256 + threadIdx.x;  // < 2^19
+    uint32_t pix = rn_gemm::fast_div(gid, (int)p.cpp, p.mul_cpp, p.shr_cpp), k = gid - pix * p.cpp;
+    while (pix < p.total_pix) {
+        const uint4 *from = nullptr;
+        uint32_t lo = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (k >= lo && k < p.end[j]) from = p.src[j] + ((uint64_t)pix * (p.end[j] - lo) + (k - lo));
+            lo = p.end[j];
+        }
+        if (!from) {  // the broadcast: image pix / pixels
+            const uint32_t b = rn_gemm::fast_div(pix, (int)p.pixels, p.mul_px, p.shr_px);
+            from = p.per_image + ((uint64_t)b * p.pc + (k - lo));
+        }
+        p.dst[(uint64_t)pix * p.cpp + k] = *from;
+        pix += p.step_pix, k += p.step_k;
+        if (k >= p.cpp) k -= p.cpp, ++pix;
+    }
+}
+
+bool seg_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
+{
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + b_bytes && y < x + a_bytes;
+}
+
 }  // namespace
 
 struct rn_seg_head {
@@ -223,6 +273,43 @@ struct rn_seg_head {
     void *mid_t;       // [cap, h, w, mid] of the storage type
     float *coarse;     // [cap, h, w, cpad] fp32
     uint64_t cap_pix;  // pixels (images x h x w) the two scratch tensors hold
+    struct seg_deeplab *dl;  // NULL: the FCN kind, everything above; else the DeepLab kind, which uses of the above
+                             // ctx, cin, classes, cpad, dtype, finalized, coarse and cap_pix
+};
+
+// The DeepLab kind: torchvision's DeepLabHead(in, classes) = ASPP(in, rates, a) + Conv3x3(a, a) + BN + ReLU +
+// Conv1x1(a, classes).  n + 4 convolutions with a batch-norm ("units": 0 the 1x1 branch, 1..n the dilated 3x3
+// branches, n + 1 the pooled branch's 1x1, n + 2 the projection, n + 3 the 3x3) and the classifier.
+constexpr int kDlMaxRates = 4, kDlMaxUnits = kDlMaxRates + 4, kDlMaxTensors = 5 * kDlMaxUnits + 2;
+
+struct seg_tensor {
+    char key[64];
+    uint64_t numel, padded;  // elements of the state dict's tensor, and of its device copy (classifier rows: cpad)
+    float *raw;
+    int is_set;
+};
+
+struct seg_unit {
+    uint64_t cin, k, dilation;
+    void *packed;
+    void *center;       // dilated branches: the centre tap weight[:, :, 1, 1] packed as a 1x1 panel
+    float *raw_center;  // its fp32 [a, cin] source until finalize
+    float *scale, *shift;
+};
+
+struct seg_deeplab {
+    uint64_t a, n, rates[kDlMaxRates];
+    int center_tap;  // rn_seg_head_set_center_tap
+    int n_units, n_tensors;
+    seg_unit unit[kDlMaxUnits];
+    seg_tensor tensor[kDlMaxTensors];  // unit u: 5u + {weight, bn weight, bn bias, running_mean, running_var}; then
+                                       // the classifier's weight and bias
+    void *packed_cls;
+    // scratch: per coarse pixel the n + 1 branch tensors [cap_pix, a] each, the concat [cap_pix, (n + 2) a]; per image
+    // the pooled map [cap_img, cin] and the pooled branch [cap_img, a].  The projected tensor and the 3x3's output
+    // live in branch 0's and branch 1's tensors, which are dead behind the concat.
+    void *branch[kDlMaxRates + 1], *cat, *pool_in, *pool_out;
+    uint64_t cap_img;
 };
 
 namespace {
@@ -239,6 +326,164 @@ uint64_t seg_key_numel(const rn_seg_head *hd, int i)
 }
 
 uint64_t seg_elem(const rn_seg_head *hd) { return hd->dtype == RN_DTYPE_BF16 ? 2 : 4; }
+
+// ---- the DeepLab kind ----
+const char *const kDlBranchOps[kDlMaxRates + 1] = {"aspp_conv0", "aspp_conv1", "aspp_conv2", "aspp_conv3", "aspp_conv4"};
+
+// Whether dilated branch u of a forward on an h x w map runs as the 1x1 contraction on its centre tap.  With
+// rate >= h and rate >= w every other tap of every output pixel lies outside the image, so the 3x3 sums the centre
+// tap's products in channel order among zeros, and so does the 1x1 -- the same bits as long as both routes round
+// that sum at the same places.  bf16 tensors: every candidate of both adds one K tile after the other into one
+// accumulator; the plan holds for every width.  fp32 tensors: a contraction of 32 or more K tiles (K >= 1024)
+// folds its sum in eight chunks whose ends are multiples of 2 * ceil(K tiles / 16) (choose_four_wave and
+// split_chunked_tail of rn_conv.hip).  The 3x3 has nine times the K tiles of the 1x1, so from in_channels = 128 on
+// its chunk ends cut the centre tap's range elsewhere than the 1x1 does (in = 128: tiles 16..19 of 36 fold at 18, the
+// 1x1's four tiles not at all; in = 2048: tiles 256..319 of 576 fold once, at 288, the 1x1's 64 tiles at every
+// eighth): the same products, added in another association.  Only in = 64 (18 and 2 tiles, neither chunked) keeps
+// the bits in fp32, and only there does an fp32 head take the plan ("DeepLabV3 head").
+bool dl_center_route(const rn_seg_head *hd, int u, uint64_t h, uint64_t w)
+{
+    const seg_deeplab *dl = hd->dl;
+    if (!dl->center_tap || u < 1 || (uint64_t)u > dl->n) return false;
+    if (dl->unit[u].dilation < h || dl->unit[u].dilation < w) return false;
+    return hd->dtype == RN_DTYPE_BF16 || 9 * hd->cin / 32 < 32;
+}
+
+void dl_free(rn_ctx *ctx, void **p)
+{
+    if (*p) rn_free(ctx, *p);
+    *p = NULL;
+}
+
+void dl_free_scratch(rn_seg_head *hd)
+{
+    seg_deeplab *dl = hd->dl;
+    for (uint64_t i = 0; i <= dl->n; ++i) dl_free(hd->ctx, &dl->branch[i]);
+    dl_free(hd->ctx, &dl->cat), dl_free(hd->ctx, &dl->pool_in), dl_free(hd->ctx, &dl->pool_out);
+    dl_free(hd->ctx, (void **)&hd->coarse);
+    hd->cap_pix = dl->cap_img = 0;
+}
+
+int dl_set_tensor(rn_seg_head *hd, const char *key, const float *host_data, uint64_t numel)
+{
+    rn_ctx *ctx = hd->ctx;
+    seg_deeplab *dl = hd->dl;
+    int i = 0;
+    while (i < dl->n_tensors && strcmp(key, dl->tensor[i].key) != 0) ++i;
+    if (i == dl->n_tensors) return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head_set_tensor: unknown key '%s'", key);
+    seg_tensor *t = &dl->tensor[i];
+    if (numel != t->numel)
+        return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head_set_tensor: %s has %llu elements, not %llu", key,
+                            (unsigned long long)t->numel, (unsigned long long)numel);
+    // only the classifier is padded (classes -> cpad rows of zeros: its weight and its bias)
+    float *padded = (float *)calloc(t->padded, sizeof(float));
+    if (!padded) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_seg_head_set_tensor: out of host memory");
+    memcpy(padded, host_data, numel * sizeof(float));
+    int st = t->raw ? RN_OK : rn_malloc(ctx, (void **)&t->raw, t->padded * sizeof(float));
+    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, t->raw, padded, t->padded * sizeof(float));
+    free(padded);
+    RN_TRY(st);
+    const int u = i / 5;
+    if (i % 5 == 0 && u >= 1 && (uint64_t)u <= dl->n) {  // a dilated branch's weight [a, in, 3, 3]: its centre tap too
+        seg_unit *un = &dl->unit[u];
+        const uint64_t rows = dl->a * un->cin;
+        float *center = (float *)malloc(rows * sizeof(float));
+        if (!center) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_seg_head_set_tensor: out of host memory");
+        for (uint64_t r = 0; r < rows; ++r) center[r] = host_data[r * 9 + 4];
+        st = un->raw_center ? RN_OK : rn_malloc(ctx, (void **)&un->raw_center, rows * sizeof(float));
+        if (st == RN_OK) st = rn_ctx_upload_sync(ctx, un->raw_center, center, rows * sizeof(float));
+        free(center);
+        RN_TRY(st);
+    }
+    t->is_set = 1;
+    return RN_OK;
+}
+
+int dl_finalize(rn_seg_head *hd)
+{
+    rn_ctx *ctx = hd->ctx;
+    seg_deeplab *dl = hd->dl;
+    for (int i = 0; i < dl->n_tensors; ++i)
+        if (!dl->tensor[i].is_set)
+            return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head_finalize: %s is not set", dl->tensor[i].key);
+    const uint64_t es = seg_elem(hd);
+    for (int u = 0; u < dl->n_units; ++u) {
+        seg_unit *un = &dl->unit[u];
+        seg_tensor *t = &dl->tensor[5 * u];
+        RN_TRY(rn_malloc(ctx, (void **)&un->scale, dl->a * sizeof(float)));
+        RN_TRY(rn_malloc(ctx, (void **)&un->shift, dl->a * sizeof(float)));
+        RN_TRY(rn_malloc(ctx, &un->packed, rn_conv2d_packed_weight_numel_dt(hd->dtype, un->cin, dl->a, un->k) * es));
+        RN_TRY(rn_batchnorm2d_fold(ctx, t[1].raw, t[2].raw, t[3].raw, t[4].raw, un->scale, un->shift, dl->a));
+        RN_TRY(rn_conv2d_pack_weight_dt(ctx, hd->dtype, t[0].raw, un->packed, un->cin, dl->a, un->k));
+        if (un->raw_center) {
+            RN_TRY(rn_malloc(ctx, &un->center, rn_conv2d_packed_weight_numel_dt(hd->dtype, un->cin, dl->a, 1) * es));
+            RN_TRY(rn_conv2d_pack_weight_dt(ctx, hd->dtype, un->raw_center, un->center, un->cin, dl->a, 1));
+        }
+    }
+    seg_tensor *cls = &dl->tensor[5 * dl->n_units];
+    RN_TRY(rn_malloc(ctx, &dl->packed_cls, rn_conv2d_packed_weight_numel_dt(hd->dtype, dl->a, hd->cpad, 1) * es));
+    RN_TRY(rn_conv2d_pack_weight_dt(ctx, hd->dtype, cls->raw, dl->packed_cls, dl->a, hd->cpad, 1));
+    RN_TRY(rn_sync(ctx));
+    for (int i = 0; i < dl->n_tensors - 1; ++i) dl_free(ctx, (void **)&dl->tensor[i].raw);  // the bias stays: a shift
+    for (int u = 0; u < dl->n_units; ++u) dl_free(ctx, (void **)&dl->unit[u].raw_center);
+    hd->finalized = 1;
+    return RN_OK;
+}
+
+// launch `step` of a DeepLab forward (the order of rn_hip.h): B images whose scratch starts img0 images into the
+// head's tensors
+int dl_step(rn_seg_head *hd, rn_ctx *ctx, int step, const void *x, uint64_t img0, uint64_t B, uint64_t h, uint64_t w,
+            uint64_t H, uint64_t W, float *scores_nchw, uint8_t *labels)
+{
+    seg_deeplab *dl = hd->dl;
+    const uint64_t es = seg_elem(hd), n = dl->n, a = dl->a, pix0 = img0 * h * w;
+    const int dt = hd->dtype;
+    void *br[kDlMaxRates + 1];
+    for (uint64_t i = 0; i <= n; ++i) br[i] = (char *)dl->branch[i] + pix0 * a * es;
+    void *cat = (char *)dl->cat + pix0 * (n + 2) * a * es;
+    void *pool_in = (char *)dl->pool_in + img0 * hd->cin * es, *pool_out = (char *)dl->pool_out + img0 * a * es;
+    void *proj = br[0], *mid = br[1];
+    float *coarse = hd->coarse + pix0 * hd->cpad;
+    rn_epilogue ep;
+    ep.residual = NULL;
+    if (pix0 + B * h * w > hd->cap_pix || img0 + B > dl->cap_img)
+        return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head: scratch not reserved");
+    const uint64_t s = (uint64_t)step;
+    if (s <= n) {  // the branches
+        const seg_unit *un = &dl->unit[s];
+        ep.scale = un->scale, ep.shift = un->shift, ep.relu = 1;
+        if (s == 0 || dl_center_route(hd, (int)s, h, w))
+            return rn_conv2d_nhwc_forward_dt(ctx, dt, dt, x, br[s], s == 0 ? un->packed : un->center, 1, 1, 0, h, w, B,
+                                             hd->cin, a, h, w, &ep);
+        return rn_conv2d_dilated_nhwc_forward_dt(ctx, dt, dt, x, br[s], un->packed, 3, 1, un->dilation, un->dilation, h,
+                                                 w, B, hd->cin, a, h, w, 1, &ep);
+    }
+    if (s == n + 1) return rn_global_avgpool_nhwc_forward_dt(ctx, dt, x, pool_in, B, hd->cin, h, w);
+    if (s == n + 2) {  // the pooled branch: B "pixels"
+        const seg_unit *un = &dl->unit[n + 1];
+        ep.scale = un->scale, ep.shift = un->shift, ep.relu = 1;
+        return rn_conv2d_nhwc_forward_dt(ctx, dt, dt, pool_in, pool_out, un->packed, 1, 1, 0, 1, 1, B, hd->cin, a, 1, 1,
+                                         &ep);
+    }
+    if (s == n + 3) {
+        uint64_t ch[kDlMaxRates + 1];
+        for (uint64_t i = 0; i <= n; ++i) ch[i] = a;
+        return rn_concat_channels_forward_dt(ctx, dt, n + 1, br, ch, pool_out, a, cat, B, h * w);
+    }
+    if (s == n + 4 || s == n + 5) {
+        const seg_unit *un = &dl->unit[s - 2];
+        const uint64_t k = un->k;
+        ep.scale = un->scale, ep.shift = un->shift, ep.relu = 1;
+        return rn_conv2d_nhwc_forward_dt(ctx, dt, dt, s == n + 4 ? cat : proj, s == n + 4 ? proj : mid, un->packed, k, 1,
+                                         k / 2, h, w, B, un->cin, a, h, w, &ep);
+    }
+    if (s == n + 6) {
+        ep.scale = NULL, ep.shift = dl->tensor[dl->n_tensors - 1].raw, ep.relu = 0;
+        return rn_conv2d_nhwc_forward_dt(ctx, dt, RN_DTYPE_F32, mid, coarse, dl->packed_cls, 1, 1, 0, h, w, B, a, hd->cpad,
+                                         h, w, &ep);
+    }
+    return rn_upsample_bilinear_forward(ctx, coarse, B, h, w, hd->classes, hd->cpad, H, W, scores_nchw, labels);
+}
 
 }  // namespace
 
@@ -287,6 +532,53 @@ int rn_upsample_bilinear_forward(rn_ctx *ctx, const float *src_nhwc, uint64_t B,
     return rn_after_launch(ctx, "rn_upsample_bilinear_forward");
 }
 
+int rn_concat_channels_forward_dt(rn_ctx *ctx, int dtype, uint64_t n_src, const void *const *srcs,
+                                  const uint64_t *channels, const void *per_image, uint64_t per_image_channels, void *dst,
+                                  uint64_t B, uint64_t pixels)
+{
+    RN_ENTER(ctx);
+    RN_REQUIRE(ctx, dtype == RN_DTYPE_F32 || dtype == RN_DTYPE_BF16, "unknown dtype");
+    RN_REQUIRE(ctx, n_src >= 1 && n_src <= 8, "n_src must be 1..8");
+    RN_REQUIRE(ctx, srcs && channels && dst, "srcs, channels or dst is NULL");
+    RN_REQUIRE(ctx, (per_image != NULL) == (per_image_channels != 0),
+               "per_image and per_image_channels: a pointer with channels, or NULL with 0");
+    RN_REQUIRE(ctx, B < (1ull << 31) && pixels < (1ull << 31) && B * pixels < (1ull << 31), "B * pixels must be below 2^31");
+    const uint64_t es = dtype == RN_DTYPE_BF16 ? 2 : 4, per = 16 / es;  // elements of a 16-byte chunk
+    concat_args p{};
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n_src; ++i) {
+        RN_REQUIRE(ctx, srcs[i], "a source is NULL");
+        RN_REQUIRE(ctx, channels[i] >= 1 && channels[i] < (1ull << 31), "a channel count is 0 (or 2^31 and above)");
+        RN_REQUIRE(ctx, channels[i] % per == 0, "a source's channels are no multiple of 16 bytes");
+        RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(srcs[i]) & 15) == 0, "a source is off a 16-byte boundary");
+        total += channels[i];
+        p.src[i] = (const uint4 *)srcs[i];
+        p.end[i] = (uint32_t)(total / per);
+    }
+    RN_REQUIRE(ctx, per_image_channels % per == 0 && per_image_channels < (1ull << 31),
+               "per_image_channels is no multiple of 16 bytes");
+    RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(per_image) & 15) == 0, "per_image is off a 16-byte boundary");
+    RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(dst) & 15) == 0, "dst is off a 16-byte boundary");
+    total += per_image_channels;
+    RN_REQUIRE(ctx, total / per < (1ull << 31), "a destination pixel must be below 2^31 chunks of 16 bytes");
+    if (B == 0 || pixels == 0) return RN_OK;
+    const uint64_t npix = B * pixels, dst_bytes = npix * total * es;
+    for (uint64_t i = 0; i < n_src; ++i)
+        RN_REQUIRE(ctx, !seg_overlap(dst, dst_bytes, srcs[i], npix * channels[i] * es), "dst overlaps a source");
+    RN_REQUIRE(ctx, !per_image || !seg_overlap(dst, dst_bytes, per_image, B * per_image_channels * es),
+               "dst overlaps per_image");
+    for (uint64_t i = n_src; i < 8; ++i) p.end[i] = p.end[n_src - 1];
+    p.per_image = (const uint4 *)per_image, p.dst = (uint4 *)dst;
+    p.cpp = (uint32_t)(total / per), p.pc = (uint32_t)(per_image_channels / per);
+    p.pixels = (uint32_t)pixels, p.total_pix = (uint32_t)npix;
+    rn_fast_div(p.cpp, &p.mul_cpp, &p.shr_cpp);
+    rn_fast_div(p.pixels, &p.mul_px, &p.shr_px);
+    const unsigned grid = rn_stream_grid(npix * p.cpp, 256);
+    p.step_pix = (uint32_t)((uint64_t)grid * 256 / p.cpp), p.step_k = (uint32_t)((uint64_t)grid * 256 % p.cpp);
+    concat_channels_kernel<<<grid, 256, 0, ctx->stream>>>(p);
+    return rn_after_launch(ctx, "rn_concat_channels_forward_dt");
+}
+
 // ---- the head ---------------------------------------------------------------------------------------------
 
 int rn_seg_head_create(rn_ctx *ctx, rn_seg_head **out, uint64_t in_channels, uint64_t mid_channels, uint64_t classes)
@@ -308,6 +600,76 @@ int rn_seg_head_create(rn_ctx *ctx, rn_seg_head **out, uint64_t in_channels, uin
     return RN_OK;
 }
 
+int rn_seg_head_create_deeplab(rn_ctx *ctx, rn_seg_head **out, uint64_t in_channels, uint64_t aspp_channels,
+                               uint64_t classes, uint64_t n_rates, const uint64_t *rates)
+{
+    static const char *const bn[4] = {"weight", "bias", "running_mean", "running_var"};
+    RN_ENTER(ctx);
+    RN_REQUIRE(ctx, out, "out is NULL");
+    *out = NULL;
+    RN_REQUIRE(ctx, in_channels >= 64 && in_channels % 64 == 0 && in_channels <= 8192,
+               "in_channels must be a multiple of 64 (at most 8192)");
+    RN_REQUIRE(ctx, aspp_channels >= 64 && aspp_channels % 64 == 0 && aspp_channels <= 1024,
+               "aspp_channels must be a multiple of 64 (at most 1024)");
+    RN_REQUIRE(ctx, classes >= 1 && classes <= 256, "classes must be 1..256");
+    RN_REQUIRE(ctx, n_rates >= 1 && n_rates <= (uint64_t)kDlMaxRates && rates, "n_rates must be 1..4 (and rates not NULL)");
+    for (uint64_t i = 0; i < n_rates; ++i)
+        RN_REQUIRE(ctx, rates[i] >= 1 && rates[i] <= RN_CONV_MAX_DILATION, "a rate must be 1..RN_CONV_MAX_DILATION");
+    rn_seg_head *hd = (rn_seg_head *)calloc(1, sizeof(*hd));
+    seg_deeplab *dl = (seg_deeplab *)calloc(1, sizeof(*dl));
+    if (!hd || !dl) {
+        free(hd), free(dl);
+        return rn_set_error(ctx, RN_ERR_NOMEM, "rn_seg_head_create_deeplab: out of host memory");
+    }
+    hd->ctx = ctx, hd->dl = dl;
+    hd->cin = in_channels, hd->classes = classes, hd->cpad = (classes + 3) / 4 * 4;
+    hd->mid = hd->midp = aspp_channels;
+    hd->dtype = RN_DTYPE_F32;
+    const uint64_t n = n_rates, a = aspp_channels;
+    dl->a = a, dl->n = n, dl->center_tap = 1;
+    dl->n_units = (int)n + 4, dl->n_tensors = 5 * dl->n_units + 2;
+    for (int u = 0; u < dl->n_units; ++u) {
+        seg_unit *un = &dl->unit[u];
+        seg_tensor *t = &dl->tensor[5 * u];
+        char conv[48], norm[48];
+        const uint64_t v = (uint64_t)u;
+        un->cin = v <= n + 1 ? in_channels : v == n + 2 ? (n + 2) * a : a;
+        un->k = (v >= 1 && v <= n) || v == n + 3 ? 3 : 1;
+        un->dilation = v >= 1 && v <= n ? rates[v - 1] : 1;
+        if (v >= 1 && v <= n) dl->rates[v - 1] = rates[v - 1];
+        // the pooled branch's Sequential starts with the pool: its convolution is .1, its batch-norm .2
+        if (v <= n + 1) {
+            snprintf(conv, sizeof(conv), "classifier.0.convs.%d.%d", u, v <= n ? 0 : 1);
+            snprintf(norm, sizeof(norm), "classifier.0.convs.%d.%d", u, v <= n ? 1 : 2);
+        } else {
+            snprintf(conv, sizeof(conv), "%s", v == n + 2 ? "classifier.0.project.0" : "classifier.1");
+            snprintf(norm, sizeof(norm), "%s", v == n + 2 ? "classifier.0.project.1" : "classifier.2");
+        }
+        snprintf(t[0].key, sizeof(t[0].key), "%s.weight", conv);
+        t[0].numel = t[0].padded = a * un->cin * un->k * un->k;
+        for (int j = 0; j < 4; ++j) {
+            snprintf(t[1 + j].key, sizeof(t[1 + j].key), "%s.%s", norm, bn[j]);
+            t[1 + j].numel = t[1 + j].padded = a;
+        }
+    }
+    seg_tensor *cls = &dl->tensor[5 * dl->n_units];
+    snprintf(cls[0].key, sizeof(cls[0].key), "classifier.4.weight");
+    snprintf(cls[1].key, sizeof(cls[1].key), "classifier.4.bias");
+    cls[0].numel = classes * a, cls[0].padded = hd->cpad * a;
+    cls[1].numel = classes, cls[1].padded = hd->cpad;
+    *out = hd;
+    return RN_OK;
+}
+
+int rn_seg_head_set_center_tap(rn_seg_head *hd, int on)
+{
+    if (!hd) return RN_ERR_INVALID;
+    RN_REQUIRE(hd->ctx, hd->dl, "not a DeepLab head");
+    RN_REQUIRE(hd->ctx, on == 0 || on == 1, "on must be 0 or 1");
+    hd->dl->center_tap = on;
+    return RN_OK;
+}
+
 int rn_seg_head_set_dtype(rn_seg_head *hd, int dtype)
 {
     if (!hd) return RN_ERR_INVALID;
@@ -324,6 +686,7 @@ int rn_seg_head_set_tensor(rn_seg_head *hd, const char *key, const float *host_d
     RN_ENTER(ctx);
     RN_REQUIRE(ctx, key && host_data, "key or host_data is NULL");
     RN_REQUIRE(ctx, !hd->finalized, "the head is finalized");
+    if (hd->dl) return dl_set_tensor(hd, key, host_data, numel);
     int i = 0;
     while (i < 7 && strcmp(key, kSegKeys[i]) != 0) ++i;
     if (i == 7) return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head_set_tensor: unknown key '%s'", key);
@@ -353,6 +716,7 @@ int rn_seg_head_finalize(rn_seg_head *hd)
     rn_ctx *ctx = hd->ctx;
     RN_ENTER(ctx);
     if (hd->finalized) return RN_OK;
+    if (hd->dl) return dl_finalize(hd);
     for (int i = 0; i < 7; ++i)
         if (!hd->is_set[i]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head_finalize: %s is not set", kSegKeys[i]);
     const uint64_t es = seg_elem(hd);
@@ -378,6 +742,20 @@ int rn_seg_head_destroy(rn_seg_head *hd)
     rn_ctx *ctx = hd->ctx;
     RN_ENTER(ctx);
     RN_TRY(rn_sync(ctx));
+    if (hd->dl) {
+        seg_deeplab *dl = hd->dl;
+        dl_free_scratch(hd);
+        for (int i = 0; i < dl->n_tensors; ++i) dl_free(ctx, (void **)&dl->tensor[i].raw);
+        for (int u = 0; u < dl->n_units; ++u) {
+            seg_unit *un = &dl->unit[u];
+            dl_free(ctx, &un->packed), dl_free(ctx, &un->center), dl_free(ctx, (void **)&un->raw_center);
+            dl_free(ctx, (void **)&un->scale), dl_free(ctx, (void **)&un->shift);
+        }
+        dl_free(ctx, &dl->packed_cls);
+        free(dl);
+        free(hd);
+        return RN_OK;
+    }
     void *bufs[6] = {hd->packed1, hd->packed2, hd->scale, hd->shift, hd->mid_t, hd->coarse};
     for (int i = 0; i < 7; ++i)
         if (hd->raw[i]) rn_free(ctx, hd->raw[i]);
@@ -404,33 +782,87 @@ void rn_seg_head_dims(const rn_seg_head *hd, uint64_t dims[4])
     dims[0] = hd->cin, dims[1] = hd->midp, dims[2] = hd->classes, dims[3] = hd->cpad;
 }
 
-// the two scratch tensors for `pixels` coarse pixels (images x h x w); they grow like the model's logits buffer:
-// never on a stream that is being captured, never while a captured graph of the context may hold them
-int rn_seg_head_reserve(rn_seg_head *hd, uint64_t pixels)
+// launch `step` of a forward of B images on an h x w map to H x W: its profile name, FLOPs and bytes; returns the
+// number of launches (3 for the FCN kind, n + 8 for the DeepLab kind); step outside 0 .. that - 1 only counts
+int rn_seg_head_plan(const rn_seg_head *hd, uint64_t B, uint64_t h, uint64_t w, uint64_t H, uint64_t W, int want_scores,
+                     int want_labels, int step, const char **name, double *flops, double *bytes)
+{
+    const double es = (double)seg_elem(hd), P = (double)(B * h * w), cin = (double)hd->cin, cpad = (double)hd->cpad;
+    const double up = 4.0 * P * cpad +
+                      (double)(B * H * W) * ((want_scores ? 4.0 * (double)hd->classes : 0.0) + (want_labels ? 1.0 : 0.0));
+    const int count = hd->dl ? (int)hd->dl->n + 8 : 3;
+    const char *nm = NULL;
+    double f = 0.0, by = 0.0;
+    if (step < 0 || step >= count) return count;
+    if (!hd->dl) {
+        const double mid = (double)hd->midp;
+        if (step == 0) nm = "seg_conv1", f = 2.0 * P * 9.0 * cin * mid, by = es * (P * (cin + mid) + 9.0 * cin * mid);
+        else if (step == 1) nm = "seg_conv2", f = 2.0 * P * mid * cpad, by = P * (es * mid + 4.0 * cpad) + es * (mid * cpad);
+        else nm = "seg_upsample", by = up;
+    } else {
+        const uint64_t n = hd->dl->n, s = (uint64_t)step;
+        const double a = (double)hd->dl->a, cat = (double)(n + 2) * a;
+        if (s <= n) {  // the FLOPs of the route that runs
+            const double taps = s == 0 || dl_center_route(hd, step, h, w) ? 1.0 : 9.0;
+            nm = kDlBranchOps[s], f = 2.0 * P * taps * cin * a, by = es * (P * (cin + a) + taps * cin * a);
+        } else if (s == n + 1) nm = "aspp_pool", by = es * (double)B * cin * (double)(h * w + 1);
+        else if (s == n + 2) nm = "aspp_pool_conv", f = 2.0 * (double)B * cin * a, by = es * ((double)B * (cin + a) + cin * a);
+        else if (s == n + 3) nm = "aspp_concat", by = es * (2.0 * P * cat - P * a + (double)B * a);
+        else if (s == n + 4) nm = "aspp_project", f = 2.0 * P * cat * a, by = es * (P * (cat + a) + cat * a);
+        else if (s == n + 5) nm = "seg_conv1", f = 2.0 * P * 9.0 * a * a, by = es * (P * 2.0 * a + 9.0 * a * a);
+        else if (s == n + 6) nm = "seg_conv2", f = 2.0 * P * a * cpad, by = P * (es * a + 4.0 * cpad) + es * (a * cpad);
+        else nm = "seg_upsample", by = up;
+    }
+    if (name) *name = nm;
+    if (flops) *flops = f;
+    if (bytes) *bytes = by;
+    return count;
+}
+
+// the scratch for `images` images of `pixels` coarse pixels (h x w) each; it grows like the model's logits buffer:
+// never on a stream that is being captured, never while a captured graph of the context may hold it
+int rn_seg_head_reserve(rn_seg_head *hd, uint64_t images, uint64_t pixels)
 {
     rn_ctx *ctx = hd->ctx;
-    if (pixels <= hd->cap_pix) return RN_OK;
+    seg_deeplab *dl = hd->dl;
+    uint64_t pix = images * pixels;
+    if (pix <= hd->cap_pix && (!dl || images <= dl->cap_img)) return RN_OK;
     if (rn_ctx_is_capturing(ctx))
         return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "rn_seg_head: the scratch cannot grow on a stream that is being captured");
     if (hd->cap_pix > 0 && ctx->graphs_live > 0)
         return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head: the scratch cannot grow while a captured graph lives");
     RN_TRY(rn_sync(ctx));
+    if (dl) {
+        const uint64_t es = seg_elem(hd);
+        if (pix < hd->cap_pix) pix = hd->cap_pix;
+        if (images < dl->cap_img) images = dl->cap_img;
+        dl_free_scratch(hd);
+        for (uint64_t i = 0; i <= dl->n; ++i) RN_TRY(rn_malloc(ctx, &dl->branch[i], pix * dl->a * es));
+        RN_TRY(rn_malloc(ctx, &dl->cat, pix * (dl->n + 2) * dl->a * es));
+        RN_TRY(rn_malloc(ctx, &dl->pool_in, images * hd->cin * es));
+        RN_TRY(rn_malloc(ctx, &dl->pool_out, images * dl->a * es));
+        RN_TRY(rn_malloc(ctx, (void **)&hd->coarse, pix * hd->cpad * sizeof(float)));
+        hd->cap_pix = pix, dl->cap_img = images;
+        return RN_OK;
+    }
     if (hd->mid_t) RN_TRY(rn_free(ctx, hd->mid_t));
     hd->mid_t = NULL;
     if (hd->coarse) RN_TRY(rn_free(ctx, hd->coarse));
     hd->coarse = NULL;
     hd->cap_pix = 0;
-    RN_TRY(rn_malloc(ctx, &hd->mid_t, pixels * hd->midp * seg_elem(hd)));
-    RN_TRY(rn_malloc(ctx, (void **)&hd->coarse, pixels * hd->cpad * sizeof(float)));
-    hd->cap_pix = pixels;
+    RN_TRY(rn_malloc(ctx, &hd->mid_t, pix * hd->midp * seg_elem(hd)));
+    RN_TRY(rn_malloc(ctx, (void **)&hd->coarse, pix * hd->cpad * sizeof(float)));
+    hd->cap_pix = pix;
     return RN_OK;
 }
 
-// one of the head's three launches on `ctx` (the head's own context, or the context of the model's stream the
-// images run on): B images whose scratch starts `pix0` coarse pixels into the head's two tensors
-int rn_seg_head_step(rn_seg_head *hd, rn_ctx *ctx, int step, const void *x_nhwc, uint64_t pix0, uint64_t B, uint64_t h,
+// one of the head's launches on `ctx` (the head's own context, or the context of the model's stream the images
+// run on): B images whose scratch starts `img0` images (img0 * h * w coarse pixels) into the head's tensors
+int rn_seg_head_step(rn_seg_head *hd, rn_ctx *ctx, int step, const void *x_nhwc, uint64_t img0, uint64_t B, uint64_t h,
                      uint64_t w, uint64_t H, uint64_t W, float *scores_nchw, uint8_t *labels)
 {
+    if (hd->dl) return dl_step(hd, ctx, step, x_nhwc, img0, B, h, w, H, W, scores_nchw, labels);
+    const uint64_t pix0 = img0 * h * w;
     void *mid = (char *)hd->mid_t + pix0 * hd->midp * seg_elem(hd);
     float *coarse = hd->coarse + pix0 * hd->cpad;
     rn_epilogue ep;
@@ -462,13 +894,15 @@ int rn_seg_head_forward(rn_seg_head *hd, const void *x_nhwc, uint64_t B, uint64_
     RN_REQUIRE(ctx, h < (1ull << 31) && w < (1ull << 31) && B * h * w < (1ull << 31), "B * h * w must be below 2^31");
     if (B == 0) return RN_OK;
     const int saved_layout = ctx->layout;
-    RN_TRY(rn_seg_head_reserve(hd, B * h * w));
+    RN_TRY(rn_seg_head_reserve(hd, B, h * w));
     ctx->layout = RN_LAYOUT_NHWC;
     int st = RN_OK;
-    for (int step = 0; step < 3 && st == RN_OK; ++step)
+    const int steps = rn_seg_head_plan(hd, B, h, w, H, W, scores_nchw != NULL, labels != NULL, -1, NULL, NULL, NULL);
+    for (int step = 0; step < steps && st == RN_OK; ++step)
         st = rn_seg_head_step(hd, ctx, step, x_nhwc, 0, B, h, w, H, W, scores_nchw, labels);
     ctx->layout = saved_layout;
     return st;
 }
 
 }  // extern "C"
+

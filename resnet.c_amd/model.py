@@ -413,8 +413,8 @@ class NativeModel:
                         features: bool = False, probs: bool = False, topk: int = 0, fused: bool = True) -> dict:
         """One forward with a segmentation head behind layer4 (rn_model_forward_segment): a dict with "labels"
         [B,H,W] uint8 and / or "scores" [B,classes,H,W] fp32 at the model's input_size, then the head outputs
-        asked for, as forward_outputs returns them.  head: a segmentation.FCNHead of this model's feature width
-        and dtype, on this model's context.  x: fp32 NCHW [B,3,H,W], or uint8 NHWC [B,H,W,3]."""
+        asked for, as forward_outputs returns them.  head: a segmentation.FCNHead or segmentation.DeepLabHead of this
+        model's feature width and dtype, on this model's context.  x: fp32 NCHW [B,3,H,W], or uint8 NHWC [B,H,W,3]."""
         from .ops import _down_raw, _up_raw
         from .tensor import _DeviceBuffer
         x = np.asarray(x)

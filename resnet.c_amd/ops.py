@@ -827,3 +827,50 @@ def upsample_bilinear(x_nhwc, size, classes: Optional[int] = None, scores: bool 
     s = _down_raw(ds, np.float32, B * classes * H * W).reshape(B, classes, H, W) if scores else None
     lb = _down_raw(dl, np.uint8, B * H * W).reshape(B, H, W) if labels else None
     return s, lb
+
+
+def concat_channels_ref(srcs, per_image=None) -> np.ndarray:
+    """The contract of rn_concat_channels_forward_dt in numpy: sources [B, pixels, C_i] (any one dtype) joined along
+    the channels, then per_image [B, C_p] repeated at every pixel of its image.  A copy: no value is touched."""
+    parts = [np.asarray(s) for s in srcs]
+    if per_image is not None:
+        p = np.asarray(per_image)
+        B, pixels = parts[0].shape[:2]
+        parts.append(np.broadcast_to(p[:, None, :], (B, pixels, p.shape[1])))
+    return np.ascontiguousarray(np.concatenate(parts, axis=2))
+
+
+def _concat_channels(dtype, np_dtype, srcs, per_image):
+    from .tensor import _DeviceBuffer
+    ctx, lib = get_ctx(), L.lib()
+    srcs = [np.ascontiguousarray(s, dtype=np_dtype) for s in srcs]
+    B, pixels = srcs[0].shape[:2]
+    assert all(s.ndim == 3 and s.shape[:2] == (B, pixels) for s in srcs), [s.shape for s in srcs]
+    ch = [int(s.shape[2]) for s in srcs]
+    cp = 0
+    dp = None
+    if per_image is not None:
+        per_image = np.ascontiguousarray(per_image, dtype=np_dtype)
+        assert per_image.shape[0] == B and per_image.ndim == 2, per_image.shape
+        cp, dp = int(per_image.shape[1]), _up_raw(per_image)
+    bufs = [_up_raw(s) for s in srcs]
+    total = sum(ch) + cp
+    es = np.dtype(np_dtype).itemsize
+    out = _DeviceBuffer(ctx, max(B * pixels * total * es, 16))
+    ptrs = (ctypes.c_void_p * len(bufs))(*[b.ptr for b in bufs])
+    chans = (ctypes.c_uint64 * len(ch))(*ch)
+    L.check(lib.rn_concat_channels_forward_dt(ctx.handle, dtype, len(bufs), ptrs, chans, dp.ptr if dp else None, cp,
+                                              out.ptr, B, pixels), "rn_concat_channels_forward_dt", ctx.handle)
+    ctx.sync()
+    return _down_raw(out, np_dtype, B * pixels * total).reshape(B, pixels, total)
+
+
+def concat_channels(srcs, per_image=None) -> np.ndarray:
+    """rn_concat_channels_forward_dt in fp32: host arrays [B, pixels, C_i] (C_i % 4 == 0) and per_image [B, C_p] or
+    None -> [B, pixels, sum C_i + C_p], one launch; bit for bit concat_channels_ref."""
+    return _concat_channels(L.RN_DTYPE_F32, np.float32, srcs, per_image)
+
+
+def concat_channels_bf16(srcs, per_image=None) -> np.ndarray:
+    """The bf16 form of concat_channels: uint16 bit patterns in (to_bf16_bits of fp32 data) and out, C_i % 8 == 0."""
+    return _concat_channels(L.RN_DTYPE_BF16, np.uint16, srcs, per_image)

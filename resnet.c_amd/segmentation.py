@@ -3,7 +3,9 @@
 Pure-numpy / torch-on-CPU restatements of what the device computes (``upsample_bilinear_ref``, ``fcn_head_ref``),
 seeded head weights (``generate_fcn_head_state``), the split of a torchvision ``fcn_resnet*`` state dict
 (``split_state``), and ``FCNHead``, the Python face of ``rn_seg_head_*``.  ``NativeModel.forward_segment`` runs a
-head right behind layer4 of a forward; ``ops.upsample_bilinear`` is the upsample launch alone.
+head right behind layer4 of a forward; ``ops.upsample_bilinear`` is the upsample launch alone.  The second half of
+the file is the same for torchvision's DeepLabHead (``deeplab_head_shapes``, ``generate_deeplab_head_state``,
+``deeplab_head_ref``, ``DeepLabHead``), the other kind of the same device object.
 """
 from __future__ import annotations
 
@@ -93,8 +95,9 @@ def generate_fcn_head_state(in_channels: int, classes: int, seed: int = 0) -> Di
 
 
 def split_state(state) -> Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]:
-    """A torchvision fcn_resnet* state dict -> (backbone_state, head_state): "backbone." is stripped (the keys
-    NativeModel reads), "classifier." is kept (the keys FCNHead reads), "aux_classifier." is dropped, and so are
+    """A torchvision fcn_resnet* or deeplabv3_resnet* state dict -> (backbone_state, head_state): "backbone." is
+    stripped (the keys NativeModel reads), "classifier." is kept (the keys FCNHead or DeepLabHead reads),
+    "aux_classifier." is dropped, and so are
     the batch-norms' num_batches_tracked.  A segmentation backbone has no fc: when fc.* is absent a zero classifier
     of 4 rows is supplied, so that NativeModel finalizes (its logits are then zeros)."""
     backbone, head = {}, {}
@@ -110,7 +113,8 @@ def split_state(state) -> Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]:
         else:
             raise ValueError(f"{key!r}: not a key of a torchvision fcn_resnet* state dict")
     if "fc.weight" not in backbone:
-        feat = int(head["classifier.0.weight"].shape[1])
+        first = "classifier.0.weight" if "classifier.0.weight" in head else "classifier.0.convs.0.0.weight"
+        feat = int(head[first].shape[1])
         backbone["fc.weight"] = np.zeros((4, feat), dtype=np.float32)
         backbone["fc.bias"] = np.zeros((4,), dtype=np.float32)
     return backbone, head
@@ -197,3 +201,128 @@ class FCNHead:
             self.close()
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------------------
+# DeepLabV3: torchvision's DeepLabHead (ASPP + Conv3x3 + Conv1x1) as the second kind of rn_seg_head
+# ---------------------------------------------------------------------------
+DEEPLAB_RATES = (12, 24, 36)
+_BN = ("weight", "bias", "running_mean", "running_var")
+
+
+def deeplab_head_shapes(in_channels: int, classes: int, aspp_channels: int = 256,
+                        rates=DEEPLAB_RATES) -> Dict[str, Tuple[int, ...]]:
+    """Key -> shape of torchvision's DeepLabHead(in_channels, classes) with ASPP(in_channels, rates, aspp_channels),
+    in the order of its state dict (num_batches_tracked left out).  convs.0 is the 1x1 branch, convs.1..n the
+    dilated 3x3 branches, convs.(n+1) the pooled branch, whose Sequential starts with the pool: its convolution is
+    .1 and its batch-norm .2."""
+    a, n = int(aspp_channels), len(rates)
+    out: Dict[str, Tuple[int, ...]] = {}
+
+    def unit(conv: str, norm: str, cin: int, k: int):
+        out[f"{conv}.weight"] = (a, cin, k, k)
+        for name in _BN:
+            out[f"{norm}.{name}"] = (a,)
+
+    unit("classifier.0.convs.0.0", "classifier.0.convs.0.1", in_channels, 1)
+    for i in range(1, n + 1):
+        unit(f"classifier.0.convs.{i}.0", f"classifier.0.convs.{i}.1", in_channels, 3)
+    unit(f"classifier.0.convs.{n + 1}.1", f"classifier.0.convs.{n + 1}.2", in_channels, 1)
+    unit("classifier.0.project.0", "classifier.0.project.1", (n + 2) * a, 1)
+    unit("classifier.1", "classifier.2", a, 3)
+    out["classifier.4.weight"] = (int(classes), a, 1, 1)
+    out["classifier.4.bias"] = (int(classes),)
+    return out
+
+
+def generate_deeplab_head_state(in_channels: int, classes: int, aspp_channels: int = 256, rates=DEEPLAB_RATES,
+                                seed: int = 0) -> Dict[str, np.ndarray]:
+    """Seeded tensors of DeepLabHead under torchvision's keys: the draws of generate_fcn_head_state (convolutions
+    He-uniform over their fan-in, batch-norms as there, the classifier's bias in +-0.02), every key with a name of
+    its own in the generator."""
+    out = {}
+    tag = f"deeplab{in_channels}x{aspp_channels}x{classes}r{'_'.join(str(int(r)) for r in rates)}"
+    for key, shape in deeplab_head_shapes(in_channels, classes, aspp_channels, rates).items():
+        name = f"{tag}.{key}"
+        if key == "classifier.4.bias":
+            out[key] = weights._uniform(name, shape, -0.02, 0.02, seed)
+        elif len(shape) == 4:
+            bound = float(np.sqrt(6.0 / (shape[1] * shape[2] * shape[3])))
+            out[key] = weights._uniform(name, shape, -bound, bound, seed)
+        elif key.endswith("running_var") or key.endswith(".weight"):
+            out[key] = weights._uniform(name, shape, 0.5, 1.5, seed)
+        else:
+            out[key] = weights._uniform(name, shape, -0.1, 0.1, seed)
+    return out
+
+
+def deeplab_head_ref(x_nchw_f64, state, size, rates=DEEPLAB_RATES, round_fn=None) -> np.ndarray:
+    """DeepLabHead + interpolate in torch on the CPU, float64: x [B,in,h,w] -> scores [B,classes,H,W] float64.  The
+    pooled branch is broadcast (what bilinear interpolation from a 1x1 map gives).  round_fn (bf16 heads): applied
+    to the map, every convolution weight and every tensor the device stores in its element type -- the branch
+    outputs, the pooled mean, the pooled branch, the projected tensor and the 3x3's output; the batch-norm constants
+    and the bias stay as they are."""
+    import torch
+    import torch.nn.functional as F
+
+    rd = (lambda a: np.asarray(round_fn(np.asarray(a, dtype=np.float32)), dtype=np.float64)) if round_fn else (lambda a: a)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))  # noqa: E731
+    n = len(rates)
+
+    def unit(y, conv, norm, **kw):
+        """convolution + batch-norm + ReLU, stored"""
+        y = F.conv2d(y, t(rd(state[f"{conv}.weight"])), **kw)
+        y = F.batch_norm(y, t(state[f"{norm}.running_mean"]), t(state[f"{norm}.running_var"]), t(state[f"{norm}.weight"]),
+                         t(state[f"{norm}.bias"]), training=False, eps=1e-5)
+        y = torch.relu(y)
+        return t(rd(y.numpy())) if round_fn else y
+
+    with torch.no_grad():
+        x = t(rd(x_nchw_f64))
+        outs = [unit(x, "classifier.0.convs.0.0", "classifier.0.convs.0.1")]
+        for i, r in enumerate(rates, start=1):
+            outs.append(unit(x, f"classifier.0.convs.{i}.0", f"classifier.0.convs.{i}.1", padding=int(r), dilation=int(r)))
+        pooled = x.mean(dim=(2, 3), keepdim=True)
+        if round_fn:
+            pooled = t(rd(pooled.numpy()))
+        pooled = unit(pooled, f"classifier.0.convs.{n + 1}.1", f"classifier.0.convs.{n + 1}.2")
+        outs.append(pooled.expand(-1, -1, x.shape[2], x.shape[3]))
+        y = unit(torch.cat(outs, dim=1), "classifier.0.project.0", "classifier.0.project.1")
+        y = unit(y, "classifier.1", "classifier.2", padding=1)
+        y = F.conv2d(y, t(rd(state["classifier.4.weight"])), t(state["classifier.4.bias"]))
+        y = F.interpolate(y, size=(int(size[0]), int(size[1])), mode="bilinear", align_corners=False)
+    return y.numpy()
+
+
+class DeepLabHead(FCNHead):
+    """rn_seg_head_create_deeplab: DeepLabHead(in_channels, classes) with ASPP(in_channels, rates, aspp_channels) on
+    the device; state holds torchvision's tensors (deeplab_head_shapes).  forward, close and the attributes are
+    FCNHead's (mid_channels is the ASPP width); dtype "f32" or "bf16" as there.  center_tap(on) switches the
+    centre-tap plan (default on): a dilated branch whose rate is at least the map's height and width runs as the 1x1
+    contraction on its centre tap -- the same bits, a ninth of the FLOPs (every bf16 head; an fp32 head only at
+    in_channels == 64, see include/rn_hip.h)."""
+
+    def __init__(self, in_channels: int, classes: int, state: Dict[str, np.ndarray], aspp_channels: int = 256,
+                 rates=DEEPLAB_RATES, dtype: str = "f32", ctx=None):
+        from .tensor import get_ctx
+        self.ctx = ctx or get_ctx()
+        self.in_channels, self.mid_channels, self.classes, self.dtype = int(in_channels), int(aspp_channels), int(classes), dtype
+        self.aspp_channels, self.rates = int(aspp_channels), tuple(int(r) for r in rates)
+        lib = L.lib()
+        h = ctypes.c_void_p()
+        rates_c = (ctypes.c_uint64 * len(self.rates))(*self.rates)
+        L.check(lib.rn_seg_head_create_deeplab(self.ctx.handle, ctypes.byref(h), self.in_channels, self.aspp_channels,
+                                               self.classes, len(self.rates), rates_c),
+                "rn_seg_head_create_deeplab", self.ctx.handle)
+        self.handle = h
+        L.check(lib.rn_seg_head_set_dtype(h, {"f32": L.RN_DTYPE_F32, "bf16": L.RN_DTYPE_BF16}[dtype]),
+                "rn_seg_head_set_dtype", self.ctx.handle)
+        for key, shape in deeplab_head_shapes(self.in_channels, self.classes, self.aspp_channels, self.rates).items():
+            arr = np.ascontiguousarray(state[key], dtype=np.float32)
+            assert arr.size == int(np.prod(shape)), (key, arr.shape, shape)
+            L.check(lib.rn_seg_head_set_tensor(h, key.encode(), arr.ctypes.data, arr.size),
+                    f"rn_seg_head_set_tensor({key})", self.ctx.handle)
+        L.check(lib.rn_seg_head_finalize(h), "rn_seg_head_finalize", self.ctx.handle)
+
+    def center_tap(self, on: bool) -> None:
+        L.check(L.lib().rn_seg_head_set_center_tap(self.handle, int(bool(on))), "rn_seg_head_set_center_tap", self.ctx.handle)

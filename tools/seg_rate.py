@@ -2,6 +2,12 @@
 """What the label map costs: rn_upsample_bilinear_forward alone, and ResNet-50 (0,1,1) with a 21-class FCN head.
 
     python tools/seg_rate.py [--rounds 5] [--reps 10] [--seconds 0.3] [--skip-model] [--skip-kernel]
+                             [--head fcn|deeplabv3] [--dilate a,b,c] [--steps-profile]
+
+--head deeplabv3 runs (c) with torchvision's DeepLabHead (ASPP 256, rates 12, 24, 36) instead of the FCN head;
+--dilate sets the backbone's replace_stride_with_dilation (default 0,1,1); --steps-profile adds one line per launch
+of the head from the model's profile records (a DeepLab head: once with the centre-tap plan, once without).  With
+none of the three the output is what it always was.
 
 (a) The upsample launch alone, coarse scores [B,h,w,24] (21 classes) at output stride 8 to 224 x 224 (B = 64) and
 512 x 512 (B = 16), in its three forms: labels only, scores only, both.  Bytes actually moved = the source once +
@@ -97,11 +103,29 @@ def kernel(lib, ctx, events, B, h, w, H, W, rounds, reps):
                       "fused_over_unfused": round(times["labels"] / (times["scores"] + min(t)), 4)}), flush=True)
 
 
-def model(dtype, B, side, seconds, rounds):
+def steps_profile(m, head, x_host, tag):
+    """one line per launch of the head: the profile records of layer "segmentation" of one labels-only forward"""
+    m.forward_segment(x_host, head)
+    m.set_profiling(True)
+    try:
+        m.forward_segment(x_host, head)
+        recs = [r for r in m.profile() if r["layer"] == "segmentation"]
+    finally:
+        m.set_profiling(False)
+    for r in recs:
+        print(json.dumps(dict(tag, op=r["op"], ms=round(r["ms"], 4), gflop=round(r["flops"] / 1e9, 3),
+                              tflops=round(r["flops"] / r["ms"] / 1e9, 1) if r["ms"] > 0 else None)), flush=True)
+    print(json.dumps(dict(tag, op="head total", ms=round(sum(r["ms"] for r in recs), 4))), flush=True)
+
+
+def model(dtype, B, side, seconds, rounds, head_kind="fcn", flags=(0, 1, 1), profile=False):
     arch = "resnet50"
     m = R.NativeModel(arch, state=R.weights.generate_state(arch, 0), dtype=dtype, input_size=(side, side),
-                      replace_stride_with_dilation=(0, 1, 1))
-    head = S.FCNHead(m.features, CLASSES, S.generate_fcn_head_state(m.features, CLASSES, 0), dtype=dtype)
+                      replace_stride_with_dilation=tuple(flags))
+    if head_kind == "fcn":
+        head = S.FCNHead(m.features, CLASSES, S.generate_fcn_head_state(m.features, CLASSES, 0), dtype=dtype)
+    else:
+        head = S.DeepLabHead(m.features, CLASSES, S.generate_deeplab_head_state(m.features, CLASSES, seed=0), dtype=dtype)
     lib, ctx = L.lib(), m.ctx
     try:
         x = R.FloatTensor.from_numpy(R.weights.generate_input(B, 0, hw=side), R.Device.GPU)
@@ -140,11 +164,23 @@ def model(dtype, B, side, seconds, rounds):
         base = min(ms["forward_maps(layer4) + download of the map"])
         for k in runs:
             best = min(ms[k])
-            print(json.dumps({"arch": arch, "dilation": [0, 1, 1], "dtype": dtype, "batch": B, "size": side, "run": k,
+            extra = {} if head_kind == "fcn" else {"head": head_kind}
+            print(json.dumps({"arch": arch, **extra, "dilation": list(flags), "dtype": dtype, "batch": B, "size": side, "run": k,
                               "steps": steps, "rounds": rounds, "ms_per_batch": round(best, 3),
                               "spread_ms": round(max(ms[k]) - best, 3), "images_per_s": round(B / best * 1e3, 1),
                               "downloaded_mb": round((hmap.nbytes if run_maps is runs[k] else hlab.nbytes) / 1e6, 2),
                               "against_maps": round(best / base, 4)}), flush=True)
+        if profile:
+            tag = {"head": head_kind, "dilation": list(flags), "dtype": dtype, "batch": B, "size": side,
+                   "map": list(m.stage_shapes["layer4"][1:])}
+            xh = R.weights.generate_input(B, 0, hw=side)
+            if head_kind == "fcn":
+                steps_profile(m, head, xh, tag)
+            else:
+                for on in (True, False):
+                    head.center_tap(on)
+                    steps_profile(m, head, xh, dict(tag, center_tap=on))
+                head.center_tap(True)
     finally:
         head.close()
         m.close()
@@ -157,6 +193,10 @@ def main():
     ap.add_argument("--seconds", type=float, default=0.3)
     ap.add_argument("--skip-model", action="store_true")
     ap.add_argument("--skip-kernel", action="store_true")
+    ap.add_argument("--head", choices=("fcn", "deeplabv3"), default="fcn")
+    ap.add_argument("--dilate", default="0,1,1")
+    ap.add_argument("--steps-profile", action="store_true")
+    ap.add_argument("--sizes", default="", help="B,side[;B,side...] in place of 32,224;8,512")
     a = ap.parse_args()
     lib, ctx = L.lib(), R.get_ctx()
     if not a.skip_kernel:
@@ -166,8 +206,9 @@ def main():
             kernel(lib, ctx, (e0, e1), *shape, a.rounds, a.reps)
     if not a.skip_model:
         for dtype in ("f32", "bf16"):
-            for B, side in MODEL_SHAPES:
-                model(dtype, B, side, a.seconds, a.rounds)
+            shapes = [tuple(int(v) for v in t.split(",")) for t in a.sizes.split(";")] if a.sizes else MODEL_SHAPES
+            for B, side in shapes:
+                model(dtype, B, side, a.seconds, a.rounds, a.head, tuple(int(v) for v in a.dilate.split(",")), a.steps_profile)
 
 
 if __name__ == "__main__":
