@@ -889,6 +889,89 @@ RN_API int rn_model_forward_segment(rn_model *m, rn_seg_head *hd, const float *i
                                     const rn_model_outputs *outs /* nullable */, const rn_seg_outputs *seg, int mode);
 RN_API int rn_model_forward_segment_u8(rn_model *m, rn_seg_head *hd, const uint8_t *input_nhwc, uint64_t B,
                                        const rn_model_outputs *outs, const rn_seg_outputs *seg, int mode);
+/* ---- feature pyramid: torchvision's FeaturePyramidNetwork on the stage maps ------------------------------------
+ * The top-down step as ONE launch: dst[b,y,x,c] = lat[b,y,x,c] + top[b, iy(y), ix(x), c], all NHWC of `dtype` (fp32
+ * or bf16), top [B,h,w,C], lat and dst [B,H,W,C].  lat_nhwc == NULL: the plain nearest upsample
+ * (torch.nn.functional.interpolate(mode="nearest", size=(H, W))).  The source index is torch's size= form, per axis
+ * n_in -> n_out, output index o:
+ *     scale = (float)n_in / (float)n_out                       (one fp32 division, on the host)
+ *     i(o)  = min((int)floorf(fl((float)o * scale)), n_in - 1)
+ * the product rounded to fp32 on its own, no double precision and no integer shortcut anywhere
+ * (ops.upsample_nearest_add_ref restates it in numpy).  Any ratio: 2x, equal sizes (a dilated backbone), odd sizes
+ * (7 -> 13 -> 25 -> 50), shrinking.  Arithmetic: fp32 tensors, one fp32 add per element -- bit for bit
+ * lat + F.interpolate(top); bf16 tensors, both operands widened, added in fp32 and rounded once to bf16 (nearest
+ * even, the rounding of the contraction epilogues); lat == NULL: a copy, NaN payloads and signed zeros kept.
+ * Every lane moves 16 bytes along C, so C * element size is a multiple of 16 bytes and every pointer 16-byte
+ * aligned; B * H * W and B * h * w below 2^31 (C below 2^31); offsets are 64-bit.  dst may be lat itself (every
+ * element is read and written by the same thread); it must not overlap top and must not overlap lat partly.
+ * Asynchronous on the context's stream; allocates and uploads nothing, every parameter is a kernel argument
+ * (capturable).  B == 0: RN_OK, nothing launched.  RN_ERR_INVALID, nothing launched, rn_last_error names the
+ * operand: ctx, top_nhwc or dst_nhwc NULL, a zero size, a bad channel count, a misaligned pointer, a forbidden
+ * overlap, an unknown dtype. */
+RN_API int rn_upsample_nearest_add_forward_dt(rn_ctx *ctx, int dtype, const void *top_nhwc /* [B,h,w,C] */, uint64_t B,
+                                              uint64_t h, uint64_t w, uint64_t C,
+                                              const void *lat_nhwc /* [B,H,W,C] or NULL */,
+                                              void *dst_nhwc /* [B,H,W,C]; may be lat_nhwc */, uint64_t H, uint64_t W);
+/* torchvision's FeaturePyramidNetwork(in_channels_list, out_channels, extra_blocks=LastLevelMaxPool() or None) in
+ * eval mode with norm_layer=None, on any NHWC maps, no model needed.  n_levels 1..4, level 0 the finest; every
+ * in_channels a multiple of 64 (at most 8192), out_channels (a) a multiple of 64 (at most 1024); extra 0 = no extra
+ * block, 1 = the pool; RN_ERR_INVALID otherwise.  No convolution code of its own.
+ * Tensors (rn_fpn_set_tensor, fp32 host data, torchvision's keys and shapes; an unknown key or a wrong element count
+ * is refused with the key in the message): inner_blocks.i.0.weight [a,in_i,1,1], inner_blocks.i.0.bias [a],
+ * layer_blocks.i.0.weight [a,a,3,3], layer_blocks.i.0.bias [a]; the older spelling without the ".0" (inner_blocks.i.weight)
+ * names the same tensors.  rn_fpn_set_dtype (before finalize) chooses the storage type of the input maps, the
+ * lateral tensors and the weight panels.  rn_fpn_finalize packs every weight (rn_conv2d_pack_weight_dt); a bias is
+ * its convolution's shift, with no scale and no ReLU; it needs every tensor.
+ * rn_fpn_level_shape: C, H, W of output `level` when the level's input map is h_in x w_in; level == n_levels is the
+ * pooled output (h_in, w_in of the coarsest level; RN_ERR_INVALID without the pool).
+ * rn_fpn_forward: x_nhwc[i] [B,h[i],w[i],in_i] of the storage type (16-byte aligned) -> out_nchw[i] [B,a,h[i],w[i]]
+ * fp32 (4-byte aligned), and with the pool out_nchw[n_levels] [B,a,(h-1)/2+1,(w-1)/2+1] of the coarsest level; NULL
+ * = not wanted (not all of them).  Every launch is on a public entry point, on the context's stream:
+ *   1. n lateral 1x1 contractions into the neck's scratch, storage type;
+ *   2. n - 1 rn_upsample_nearest_add_forward_dt, coarsest first, each in place on the next finer lateral;
+ *   3. a 3x3 contraction (padding 1) per wanted level, fp32 output whatever the storage type;
+ *   4. with the pool wanted, rn_maxpool2d_nhwc_forward_dt(k = 1, stride 2, padding 0) on the coarsest 3x3 output;
+ *   5. one rn_nhwc_to_nchw_dt per wanted output.
+ * A level that is not wanted still runs its lateral and its top-down step (finer levels need them) and skips its 3x3
+ * and its export; the coarsest 3x3 also runs when only the pool is wanted.  The neck owns its scratch (per level the
+ * lateral tensor and the fp32 output, and the pooled tensor); it grows on first use like a segmentation head's:
+ * RN_ERR_UNSUPPORTED on a stream that is being captured, RN_ERR_INVALID while a captured graph of the context lives. */
+typedef struct rn_fpn rn_fpn;
+RN_API int rn_fpn_create(rn_ctx *ctx, rn_fpn **out, uint64_t n_levels, const uint64_t *in_channels,
+                         uint64_t out_channels, int extra /* 0 none, 1 pool */);
+RN_API int rn_fpn_set_dtype(rn_fpn *fpn, int dtype);
+RN_API int rn_fpn_set_tensor(rn_fpn *fpn, const char *key, const float *host_data, uint64_t numel);
+RN_API int rn_fpn_finalize(rn_fpn *fpn);
+RN_API int rn_fpn_destroy(rn_fpn *fpn);
+RN_API int rn_fpn_level_shape(const rn_fpn *fpn, int level, uint64_t h_in, uint64_t w_in, uint64_t *C, uint64_t *H,
+                              uint64_t *W);
+RN_API int rn_fpn_forward(rn_fpn *fpn, const void *const *x_nhwc, uint64_t B, const uint64_t *h, const uint64_t *w,
+                          float *const *out_nchw);
+/* The pyramid of B images from one forward (torchvision's resnet_fpn_backbone): exactly the launches and bits of
+ * rn_model_forward_outputs -- same sub-batches, parts, front slices, profile records, the classification head
+ * included -- plus the neck's.  stages: the n_levels stages (each 1..4, ascending) whose maps are the neck's levels
+ * 0 .. n_levels-1.  fpn_out->level[i]: device buffer [B,a,H_i,W_i] fp32 of level i ("0".."3" of torchvision's dict),
+ * level[n_levels] the pooled one ("pool"); NULL = not wanted.  The lateral 1x1 of a stage is queued right behind that
+ * stage's last block on that block's stream and reads the stage's output in place, where it still sits in its
+ * ping-pong arena, so no stage map is ever copied and no arena is added; the rest of the neck is queued behind
+ * layer4's last block, where a segmentation head is.  Profile ops of layer "fpn": "fpn_inner<i>" (behind stage i's
+ * blocks), then "fpn_topdown<i>" for i = n-1 .. 1 (level i added into level i-1), "fpn_layer<i>", "fpn_pool",
+ * "fpn_export<i>" and "fpn_export_pool", with FLOPs and bytes as the segmentation steps have them.  Every part of a
+ * launch batch uses its own slice of the neck's scratch, which is sized for one sub-batch and reused by the next
+ * behind the join of the parts' streams.  outs may be NULL, as in rn_model_forward_maps.  The request lives for this
+ * call only.  Every architecture, both storage types, any input size and dilation, and the byte route.
+ * Refused with a text in rn_last_error of the model's context, nothing launched: a NULL or unfinalized neck or model;
+ * a neck whose dtype is not the model's or whose context is on another device; stages NULL, not ascending, outside 1..4; an in_channels that is not the
+ * stage's C (rn_model_stage_shape); fpn_out NULL or nothing wanted in it; an output off a 4-byte boundary
+ * (RN_ERR_INVALID); a bf16 model with RN_FWD_REFERENCE_OPS (RN_ERR_UNSUPPORTED).  rn_model_capture, the pipelines and
+ * rn_shard_* carry no pyramid. */
+typedef struct rn_fpn_outputs { float *level[5]; } rn_fpn_outputs;   /* levels 0..n-1, then the pool; NULL = not wanted */
+RN_API int rn_model_forward_fpn(rn_model *m, rn_fpn *fpn, const float *input_nchw, uint64_t B,
+                                const rn_model_outputs *outs /* nullable */, const int *stages,
+                                const rn_fpn_outputs *fpn_out, int mode);
+RN_API int rn_model_forward_fpn_u8(rn_model *m, rn_fpn *fpn, const uint8_t *input_nhwc, uint64_t B,
+                                   const rn_model_outputs *outs, const int *stages, const rn_fpn_outputs *fpn_out,
+                                   int mode);
 /* Run one forward, then time every tile candidate of every convolution at batch B on the
  * device (events on the context's stream, on the buffers that forward used) and remember the fastest per layer for
  * that batch size.  Results do not change (candidates are bit-identical), only speed. */

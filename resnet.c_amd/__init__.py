@@ -8,7 +8,7 @@ cheap; the shared library is loaded on first use and its absence is a hard
 error -- there is no CPU fallback.
 """
 from . import weights, preprocess  # noqa: F401  (pure-numpy helpers)
-from . import _lib, tensor, nn, ops, model, segmentation  # noqa: F401
+from . import _lib, tensor, nn, ops, model, segmentation, fpn  # noqa: F401
 from ._lib import RnError  # noqa: F401
 from .tensor import Device, Shape, Tensor, FloatTensor, Context, get_ctx, set_device  # noqa: F401
 from .nn import (Conv2d, BatchNorm2d, Pool2d, Linear, reluForward, addForward,  # noqa: F401

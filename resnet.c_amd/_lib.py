@@ -46,6 +46,11 @@ class SegOutputs(ctypes.Structure):
     _fields_ = [("labels", c_void_p), ("scores", c_void_p)]
 
 
+class FpnOutputs(ctypes.Structure):
+    """rn_fpn_outputs: device pointers of the [B,a,H,W] fp32 levels 0..n-1, then the pooled one; NULL = not wanted."""
+    _fields_ = [("level", c_void_p * 5)]
+
+
 class Epilogue(ctypes.Structure):
     _fields_ = [("scale", c_void_p), ("shift", c_void_p), ("residual", c_void_p),
                 ("relu", c_int)]
@@ -199,6 +204,18 @@ SIGNATURES = {
                                          c_int]),
     "rn_model_forward_segment_u8": (c_int, [c_void_p, c_void_p, c_void_p, u64, POINTER(ModelOutputs),
                                             POINTER(SegOutputs), c_int]),
+    "rn_upsample_nearest_add_forward_dt": (c_int, [c_void_p, c_int, c_void_p] + [u64] * 4 + [c_void_p, c_void_p, u64, u64]),
+    "rn_fpn_create": (c_int, [c_void_p, POINTER(c_void_p), u64, POINTER(u64), u64, c_int]),
+    "rn_fpn_set_dtype": (c_int, [c_void_p, c_int]),
+    "rn_fpn_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, u64]),
+    "rn_fpn_finalize": (c_int, [c_void_p]),
+    "rn_fpn_destroy": (c_int, [c_void_p]),
+    "rn_fpn_level_shape": (c_int, [c_void_p, c_int, u64, u64, POINTER(u64), POINTER(u64), POINTER(u64)]),
+    "rn_fpn_forward": (c_int, [c_void_p, POINTER(c_void_p), u64, POINTER(u64), POINTER(u64), POINTER(c_void_p)]),
+    "rn_model_forward_fpn": (c_int, [c_void_p, c_void_p, fptr, u64, POINTER(ModelOutputs), POINTER(c_int),
+                                     POINTER(FpnOutputs), c_int]),
+    "rn_model_forward_fpn_u8": (c_int, [c_void_p, c_void_p, c_void_p, u64, POINTER(ModelOutputs), POINTER(c_int),
+                                        POINTER(FpnOutputs), c_int]),
     "rn_model_destroy": (c_int, [c_void_p]),
     "rn_model_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, u64]),
     "rn_model_load_dir": (c_int, [c_void_p, c_char_p]),

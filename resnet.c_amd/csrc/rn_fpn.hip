@@ -1,0 +1,465 @@
+// Feature pyramid: the top-down step of torchvision's FeaturePyramidNetwork as one launch
+// (rn_upsample_nearest_add_forward_dt: dst = lat + nearest_upsample(top), or the plain nearest upsample), and the
+// neck itself as an object over the library's own contractions, max-pool and export (rn_fpn_*).  The reference
+// classifies whole images only; nothing here has a counterpart in it.
+#include <stdlib.h>
+#include <string.h>
+
+#include "rn_conv_params.h"
+#include "rn_internal.h"
+#include "rn_private.h"
+
+using rn_gemm::bf16_t;
+using rn_gemm::u32x4;
+
+namespace {
+
+// ---- the top-down kernel ----------------------------------------------------------------------------------
+// Bound by HBM: dst and lat stream once, top is read H / h times, the repeats from cache (at 2x the two output
+// rows of a source row are adjacent in the grid's walk, the two columns adjacent lanes' runs).  A "chunk" is 16
+// bytes along C; a pixel is cpp chunks.  A block takes `span` consecutive pixels of one output row (span * cpp is
+// about kNaChunks, so short pixels are grouped and a long pixel is one block's loop): consecutive lanes hold
+// consecutive chunks, a wave stores 1 KiB in a row and loads runs of cpp chunks of top.  The source row is computed
+// once per output row (a scalar), the source column per chunk: one fp32 multiply, no table.  Four chunks per thread
+// are loaded before the first is stored.  Both grid dimensions stride: rows of all images in y, spans of a row in
+// x.  256 threads, no LDS.  Every chunk is read (lat, top) and written (dst) by the same thread, the reads of a trip
+// before its writes: dst == lat is safe by construction.  Offsets are 64-bit from the image on; inside a block's
+// span they are 32-bit (span * cpp < 2^31 by the host's choice of span).
+constexpr uint32_t kNaBlock = 256, kNaUnroll = 4, kNaChunks = kNaBlock * kNaUnroll;
+
+struct nearest_args {
+    const uint4 *top, *lat;
+    uint4 *dst;
+    uint32_t h, w, H, W, rows;  // rows = B * H
+    uint32_t cpp, span, spans;  // chunks of a pixel; pixels of a block's run; runs of a row
+    uint32_t mul_cpp, shr_cpp;
+    float scale_h, scale_w;
+};
+
+// the contract's source index of output o
+__device__ __forceinline__ uint32_t nearest_index(uint32_t o, float scale, uint32_t n_in)
+{
+    const uint32_t i = (uint32_t)floorf(__fmul_rn((float)o, scale));  // the product rounded on its own; never negative
+    return i < n_in - 1 ? i : n_in - 1;
+}
+
+template <typename T>
+__device__ __forceinline__ uint4 add_chunk(const uint4 a, const uint4 b)
+{
+    constexpr int EPT = rn_gemm::OutVec<T>::EPT;
+    const u32x4 ua{a.x, a.y, a.z, a.w}, ub{b.x, b.y, b.z, b.w};
+    float va[EPT], vb[EPT];
+    rn_gemm::OutVec<T>::unpack(ua, va);
+    rn_gemm::OutVec<T>::unpack(ub, vb);
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) va[j] = va[j] + vb[j];  // fp32, then one rounding to the storage type
+    const u32x4 r = rn_gemm::OutVec<T>::pack(va);
+    return make_uint4(r[0], r[1], r[2], r[3]);
+}
+
+template <typename T, bool ADD>
+__global__ __launch_bounds__(kNaBlock) void upsample_nearest_add_kernel(const nearest_args p)
+{
+    for (uint32_t row = blockIdx.y; row < p.rows; row += gridDim.y) {
+        const uint32_t b = row / p.H, y = row - b * p.H;  // uniform: once per row
+        const uint32_t iy = nearest_index(y, p.scale_h, p.h);
+        const uint4 *top_row = p.top + ((uint64_t)b * p.h + iy) * p.w * p.cpp;
+        const uint64_t out_row = (uint64_t)row * p.W * p.cpp;
+        for (uint32_t s = blockIdx.x; s < p.spans; s += gridDim.x) {
+            const uint32_t x0 = s * p.span;
+            const uint32_t px = p.W - x0 < p.span ? p.W - x0 : p.span, n = px * p.cpp;
+            const uint64_t base = out_row + (uint64_t)x0 * p.cpp;
+            for (uint32_t j0 = threadIdx.x; j0 < n; j0 += kNaChunks) {
+                uint4 t[kNaUnroll], l[kNaUnroll];
+#pragma unroll
+                for (uint32_t u = 0; u < kNaUnroll; ++u) {
+                    const uint32_t j = j0 + u * kNaBlock;
+                    if (j < n) {
+                        const uint32_t dx = rn_gemm::fast_div(j, (int)p.cpp, p.mul_cpp, p.shr_cpp), k = j - dx * p.cpp;
+                        const uint32_t ix = nearest_index(x0 + dx, p.scale_w, p.w);
+                        t[u] = top_row[(uint64_t)ix * p.cpp + k];
+                        if (ADD) l[u] = p.lat[base + j];
+                    }
+                }
+#pragma unroll
+                for (uint32_t u = 0; u < kNaUnroll; ++u) {
+                    const uint32_t j = j0 + u * kNaBlock;
+                    if (j < n) p.dst[base + j] = ADD ? add_chunk<T>(l[u], t[u]) : t[u];
+                }
+            }
+        }
+    }
+}
+
+bool fpn_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
+{
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + b_bytes && y < x + a_bytes;
+}
+
+constexpr int kFpnMaxLevels = 4;
+
+}  // namespace
+
+// torchvision's FeaturePyramidNetwork(in_channels_list, a, extra_blocks=LastLevelMaxPool() or None), norm_layer=None
+struct rn_fpn {
+    rn_ctx *ctx;
+    int n, extra, dtype, finalized;
+    uint64_t cin[kFpnMaxLevels], a;
+    // per level: 0 the lateral's weight [a,in,1,1], 1 its bias [a], 2 the 3x3's weight [a,a,3,3], 3 its bias [a]; fp32
+    // on the device.  The biases stay (the epilogues' shifts), the weights go once they are packed.
+    float *raw[kFpnMaxLevels][4];
+    int is_set[kFpnMaxLevels][4];
+    void *packed_inner[kFpnMaxLevels], *packed_layer[kFpnMaxLevels];
+    // scratch, per level: the lateral / merged tensor [cap, h, w, a] of the storage type and the 3x3's output
+    // [cap, h, w, a] fp32; the pooled coarsest output [cap, hp, wp, a] fp32
+    void *inner[kFpnMaxLevels];
+    float *outb[kFpnMaxLevels], *poolb;
+    uint64_t cap_pix[kFpnMaxLevels], cap_pool;
+};
+
+namespace {
+
+uint64_t fpn_elem(const rn_fpn *f) { return f->dtype == RN_DTYPE_BF16 ? 2 : 4; }
+
+uint64_t fpn_key_numel(const rn_fpn *f, int level, int which)
+{
+    return which == 0 ? f->a * f->cin[level] : which == 2 ? f->a * f->a * 9 : f->a;
+}
+
+void fpn_free(rn_ctx *ctx, void **p)
+{
+    if (*p) rn_free(ctx, *p);
+    *p = NULL;
+}
+
+void fpn_free_scratch(rn_fpn *f)
+{
+    for (int i = 0; i < f->n; ++i) {
+        fpn_free(f->ctx, &f->inner[i]), fpn_free(f->ctx, (void **)&f->outb[i]);
+        f->cap_pix[i] = 0;
+    }
+    fpn_free(f->ctx, (void **)&f->poolb);
+    f->cap_pool = 0;
+}
+
+// "inner_blocks.2.0.weight", "inner_blocks.2.weight" (the older spelling), "layer_blocks.0.0.bias" ... -> level and
+// tensor (0..3); false: not a key of this neck
+bool fpn_parse_key(const rn_fpn *f, const char *key, int *level, int *which)
+{
+    int base;
+    if (strncmp(key, "inner_blocks.", 13) == 0) base = 0;
+    else if (strncmp(key, "layer_blocks.", 13) == 0) base = 2;
+    else return false;
+    const char *s = key + 13;
+    if (*s < '0' || *s >= '0' + f->n || s[1] != '.') return false;
+    *level = *s - '0';
+    s += 2;
+    if (strncmp(s, "0.", 2) == 0) s += 2;
+    if (strcmp(s, "weight") == 0) *which = base;
+    else if (strcmp(s, "bias") == 0) *which = base + 1;
+    else return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rn_upsample_nearest_add_forward_dt(rn_ctx *ctx, int dtype, const void *top_nhwc, uint64_t B, uint64_t h, uint64_t w,
+                                       uint64_t C, const void *lat_nhwc, void *dst_nhwc, uint64_t H, uint64_t W)
+{
+    RN_ENTER(ctx);
+    RN_REQUIRE(ctx, dtype == RN_DTYPE_F32 || dtype == RN_DTYPE_BF16, "unknown dtype");
+    RN_REQUIRE(ctx, top_nhwc, "top_nhwc is NULL");
+    RN_REQUIRE(ctx, dst_nhwc, "dst_nhwc is NULL");
+    RN_REQUIRE(ctx, h >= 1 && w >= 1 && H >= 1 && W >= 1, "h, w, H, W must be >= 1");
+    const uint64_t es = dtype == RN_DTYPE_BF16 ? 2 : 4, per = 16 / es;  // elements of a 16-byte chunk
+    RN_REQUIRE(ctx, C >= 1 && C < (1ull << 31) && C % per == 0, "C must be a multiple of 16 bytes (and below 2^31)");
+    RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(top_nhwc) & 15) == 0, "top_nhwc is off a 16-byte boundary");
+    RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(lat_nhwc) & 15) == 0, "lat_nhwc is off a 16-byte boundary");
+    RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(dst_nhwc) & 15) == 0, "dst_nhwc is off a 16-byte boundary");
+    RN_REQUIRE(ctx, h < (1ull << 31) && w < (1ull << 31) && H < (1ull << 31) && W < (1ull << 31) && B < (1ull << 31) &&
+                        h * w < (1ull << 31) && H * W < (1ull << 31) && B * h * w < (1ull << 31) &&
+                        B * H * W < (1ull << 31),
+               "B * h * w and B * H * W must be below 2^31");
+    if (B == 0) return RN_OK;
+    const uint64_t top_bytes = B * h * w * C * es, dst_bytes = B * H * W * C * es;
+    RN_REQUIRE(ctx, !fpn_overlap(dst_nhwc, dst_bytes, top_nhwc, top_bytes), "dst_nhwc overlaps top_nhwc");
+    RN_REQUIRE(ctx, !lat_nhwc || lat_nhwc == dst_nhwc || !fpn_overlap(dst_nhwc, dst_bytes, lat_nhwc, dst_bytes),
+               "dst_nhwc overlaps lat_nhwc partly (it may be lat_nhwc itself)");
+    nearest_args p;
+    p.top = (const uint4 *)top_nhwc, p.lat = (const uint4 *)lat_nhwc, p.dst = (uint4 *)dst_nhwc;
+    p.h = (uint32_t)h, p.w = (uint32_t)w, p.H = (uint32_t)H, p.W = (uint32_t)W, p.rows = (uint32_t)(B * H);
+    p.cpp = (uint32_t)(C / per);
+    p.span = p.cpp >= kNaChunks ? 1 : kNaChunks / p.cpp;
+    p.spans = (uint32_t)rn_ceil_div(W, p.span);
+    rn_fast_div(p.cpp, &p.mul_cpp, &p.shr_cpp);
+    p.scale_h = (float)h / (float)H, p.scale_w = (float)w / (float)W;
+    // at most about 4096 blocks, eight a CU and some to balance; the rest is the kernel's two strides
+    const uint32_t gx = p.spans < 2048 ? p.spans : 2048, per_x = 4096 / gx;
+    const dim3 grid(gx, p.rows < per_x ? p.rows : per_x);
+    if (dtype == RN_DTYPE_BF16) {
+        if (lat_nhwc) upsample_nearest_add_kernel<bf16_t, true><<<grid, kNaBlock, 0, ctx->stream>>>(p);
+        else upsample_nearest_add_kernel<bf16_t, false><<<grid, kNaBlock, 0, ctx->stream>>>(p);
+    } else {
+        if (lat_nhwc) upsample_nearest_add_kernel<float, true><<<grid, kNaBlock, 0, ctx->stream>>>(p);
+        else upsample_nearest_add_kernel<float, false><<<grid, kNaBlock, 0, ctx->stream>>>(p);
+    }
+    return rn_after_launch(ctx, "rn_upsample_nearest_add_forward_dt");
+}
+
+// ---- the neck -----------------------------------------------------------------------------------------------
+
+int rn_fpn_create(rn_ctx *ctx, rn_fpn **out, uint64_t n_levels, const uint64_t *in_channels, uint64_t out_channels,
+                  int extra)
+{
+    RN_ENTER(ctx);
+    RN_REQUIRE(ctx, out, "out is NULL");
+    *out = NULL;
+    RN_REQUIRE(ctx, n_levels >= 1 && n_levels <= (uint64_t)kFpnMaxLevels && in_channels,
+               "n_levels must be 1..4 (and in_channels not NULL)");
+    for (uint64_t i = 0; i < n_levels; ++i)
+        RN_REQUIRE(ctx, in_channels[i] >= 64 && in_channels[i] % 64 == 0 && in_channels[i] <= 8192,
+                   "every in_channels must be a multiple of 64 (at most 8192)");
+    RN_REQUIRE(ctx, out_channels >= 64 && out_channels % 64 == 0 && out_channels <= 1024,
+               "out_channels must be a multiple of 64 (at most 1024)");
+    RN_REQUIRE(ctx, extra == 0 || extra == 1, "extra must be 0 (none) or 1 (LastLevelMaxPool)");
+    rn_fpn *f = (rn_fpn *)calloc(1, sizeof(*f));
+    if (!f) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_fpn_create: out of host memory");
+    f->ctx = ctx, f->n = (int)n_levels, f->extra = extra, f->a = out_channels, f->dtype = RN_DTYPE_F32;
+    for (uint64_t i = 0; i < n_levels; ++i) f->cin[i] = in_channels[i];
+    *out = f;
+    return RN_OK;
+}
+
+int rn_fpn_set_dtype(rn_fpn *f, int dtype)
+{
+    if (!f) return RN_ERR_INVALID;
+    RN_REQUIRE(f->ctx, !f->finalized, "the neck is finalized");
+    RN_REQUIRE(f->ctx, dtype == RN_DTYPE_F32 || dtype == RN_DTYPE_BF16, "unknown dtype");
+    f->dtype = dtype;
+    return RN_OK;
+}
+
+int rn_fpn_set_tensor(rn_fpn *f, const char *key, const float *host_data, uint64_t numel)
+{
+    if (!f) return RN_ERR_INVALID;
+    rn_ctx *ctx = f->ctx;
+    RN_ENTER(ctx);
+    RN_REQUIRE(ctx, key && host_data, "key or host_data is NULL");
+    RN_REQUIRE(ctx, !f->finalized, "the neck is finalized");
+    int level = 0, which = 0;
+    if (!fpn_parse_key(f, key, &level, &which))
+        return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn_set_tensor: unknown key '%s'", key);
+    const uint64_t want = fpn_key_numel(f, level, which);
+    if (numel != want)
+        return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn_set_tensor: %s has %llu elements, not %llu", key,
+                            (unsigned long long)want, (unsigned long long)numel);
+    float **raw = &f->raw[level][which];
+    if (!*raw) RN_TRY(rn_malloc(ctx, (void **)raw, want * sizeof(float)));
+    RN_TRY(rn_ctx_upload_sync(ctx, *raw, host_data, want * sizeof(float)));
+    f->is_set[level][which] = 1;
+    return RN_OK;
+}
+
+int rn_fpn_finalize(rn_fpn *f)
+{
+    static const char *const names[4] = {"inner_blocks.%d.0.weight", "inner_blocks.%d.0.bias", "layer_blocks.%d.0.weight",
+                                         "layer_blocks.%d.0.bias"};
+    if (!f) return RN_ERR_INVALID;
+    rn_ctx *ctx = f->ctx;
+    RN_ENTER(ctx);
+    if (f->finalized) return RN_OK;
+    for (int i = 0; i < f->n; ++i)
+        for (int t = 0; t < 4; ++t)
+            if (!f->is_set[i][t]) {
+                char key[48];
+                snprintf(key, sizeof(key), names[t], i);
+                return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn_finalize: %s is not set", key);
+            }
+    const uint64_t es = fpn_elem(f);
+    for (int i = 0; i < f->n; ++i) {
+        RN_TRY(rn_malloc(ctx, &f->packed_inner[i], rn_conv2d_packed_weight_numel_dt(f->dtype, f->cin[i], f->a, 1) * es));
+        RN_TRY(rn_malloc(ctx, &f->packed_layer[i], rn_conv2d_packed_weight_numel_dt(f->dtype, f->a, f->a, 3) * es));
+        RN_TRY(rn_conv2d_pack_weight_dt(ctx, f->dtype, f->raw[i][0], f->packed_inner[i], f->cin[i], f->a, 1));
+        RN_TRY(rn_conv2d_pack_weight_dt(ctx, f->dtype, f->raw[i][2], f->packed_layer[i], f->a, f->a, 3));
+    }
+    RN_TRY(rn_sync(ctx));
+    for (int i = 0; i < f->n; ++i) fpn_free(ctx, (void **)&f->raw[i][0]), fpn_free(ctx, (void **)&f->raw[i][2]);
+    f->finalized = 1;
+    return RN_OK;
+}
+
+int rn_fpn_destroy(rn_fpn *f)
+{
+    if (!f) return RN_OK;
+    rn_ctx *ctx = f->ctx;
+    RN_ENTER(ctx);
+    RN_TRY(rn_sync(ctx));
+    fpn_free_scratch(f);
+    for (int i = 0; i < f->n; ++i) {
+        for (int t = 0; t < 4; ++t) fpn_free(ctx, (void **)&f->raw[i][t]);
+        fpn_free(ctx, &f->packed_inner[i]), fpn_free(ctx, &f->packed_layer[i]);
+    }
+    free(f);
+    return RN_OK;
+}
+
+int rn_fpn_level_shape(const rn_fpn *f, int level, uint64_t h_in, uint64_t w_in, uint64_t *C, uint64_t *H, uint64_t *W)
+{
+    if (!f) return RN_ERR_INVALID;
+    if (level < 0 || level > f->n || (level == f->n && !f->extra) || h_in == 0 || w_in == 0) return RN_ERR_INVALID;
+    const int pool = level == f->n;  // LastLevelMaxPool: kernel 1, stride 2, no padding, on the coarsest output
+    if (C) *C = f->a;
+    if (H) *H = pool ? (h_in - 1) / 2 + 1 : h_in;
+    if (W) *W = pool ? (w_in - 1) / 2 + 1 : w_in;
+    return RN_OK;
+}
+
+// ---- library-internal (rn_private.h): what the model driver asks of a neck and queues of it ----
+
+int rn_fpn_matches(const rn_fpn *f, const rn_ctx *ctx, int dtype, const char **why)
+{
+    const char *w = NULL;
+    if (!f) w = "the neck is NULL";
+    else if (!f->finalized) w = "the neck is not finalized";
+    else if (f->ctx->device != ctx->device) w = "the neck's context is on another device than the model's";
+    else if (f->dtype != dtype) w = "the neck's storage type (dtype) is not the model's";
+    if (why) *why = w;
+    return w == NULL;
+}
+
+void rn_fpn_dims(const rn_fpn *f, int *n_levels, int *extra, uint64_t *out_channels, uint64_t in_channels[4])
+{
+    if (n_levels) *n_levels = f->n;
+    if (extra) *extra = f->extra;
+    if (out_channels) *out_channels = f->a;
+    if (in_channels)
+        for (int i = 0; i < f->n; ++i) in_channels[i] = f->cin[i];
+}
+
+int rn_fpn_reserve(rn_fpn *f, uint64_t images, const uint64_t *h, const uint64_t *w)
+{
+    rn_ctx *ctx = f->ctx;
+    const int last = f->n - 1;
+    const uint64_t pool_pix = f->extra ? images * ((h[last] - 1) / 2 + 1) * ((w[last] - 1) / 2 + 1) : 0;
+    bool fits = pool_pix <= f->cap_pool;
+    for (int i = 0; i < f->n; ++i) fits = fits && images * h[i] * w[i] <= f->cap_pix[i];
+    if (fits) return RN_OK;
+    const bool had = f->cap_pix[0] > 0;
+    if (rn_ctx_is_capturing(ctx))
+        return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "rn_fpn: the scratch cannot grow on a stream that is being captured");
+    if (had && ctx->graphs_live > 0)
+        return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn: the scratch cannot grow while a captured graph lives");
+    RN_TRY(rn_sync(ctx));
+    uint64_t pix[kFpnMaxLevels], pool = pool_pix > f->cap_pool ? pool_pix : f->cap_pool;
+    for (int i = 0; i < f->n; ++i) pix[i] = images * h[i] * w[i] > f->cap_pix[i] ? images * h[i] * w[i] : f->cap_pix[i];
+    fpn_free_scratch(f);
+    for (int i = 0; i < f->n; ++i) {
+        RN_TRY(rn_malloc(ctx, &f->inner[i], pix[i] * f->a * fpn_elem(f)));
+        RN_TRY(rn_malloc(ctx, (void **)&f->outb[i], pix[i] * f->a * sizeof(float)));
+        f->cap_pix[i] = pix[i];
+    }
+    if (pool) RN_TRY(rn_malloc(ctx, (void **)&f->poolb, pool * f->a * sizeof(float)));
+    f->cap_pool = pool;
+    return RN_OK;
+}
+
+void rn_fpn_cost(const rn_fpn *f, int kind, int level, uint64_t B, const uint64_t *h, const uint64_t *w, double *flops,
+                 double *bytes)
+{
+    const double es = (double)fpn_elem(f), a = (double)f->a;
+    const int l = level < f->n ? level : f->n - 1;
+    const double P = (double)(B * h[l] * w[l]), cin = (double)f->cin[l];
+    const double Pp = (double)(B * ((h[l] - 1) / 2 + 1) * ((w[l] - 1) / 2 + 1));
+    double fl = 0.0, by = 0.0;
+    switch (kind) {
+    case RN_FPN_INNER: fl = 2.0 * P * cin * a, by = es * (P * (cin + a) + cin * a); break;
+    case RN_FPN_TOPDOWN:  // level: the coarser one; the finer one is read and written
+        by = es * a * (P + 2.0 * (double)(B * h[l - 1] * w[l - 1]));
+        break;
+    case RN_FPN_LAYER: fl = 2.0 * P * 9.0 * a * a, by = P * a * (es + 4.0) + es * 9.0 * a * a; break;
+    case RN_FPN_POOL: by = 4.0 * a * (P + Pp); break;
+    default: by = 8.0 * a * (level == f->n ? Pp : P); break;  // the export
+    }
+    if (flops) *flops = fl;
+    if (bytes) *bytes = by;
+}
+
+int rn_fpn_step(rn_fpn *f, rn_ctx *ctx, int kind, int level, const void *x_nhwc, uint64_t img0, uint64_t B,
+                const uint64_t *h, const uint64_t *w, float *dst_nchw)
+{
+    const int dt = f->dtype, last = f->n - 1;
+    const uint64_t es = fpn_elem(f), a = f->a;
+    const uint64_t hp = (h[last] - 1) / 2 + 1, wp = (w[last] - 1) / 2 + 1;
+    for (int i = 0; i < f->n; ++i)
+        if ((img0 + B) * h[i] * w[i] > f->cap_pix[i]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn: scratch not reserved");
+    if (f->extra && (img0 + B) * hp * wp > f->cap_pool) return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn: scratch not reserved");
+    const int l = level < f->n ? level : last;
+    void *inner = (char *)f->inner[l] + img0 * h[l] * w[l] * a * es;
+    float *outb = f->outb[l] + img0 * h[l] * w[l] * a;
+    float *poolb = f->extra ? f->poolb + img0 * hp * wp * a : NULL;
+    rn_epilogue ep;
+    ep.scale = NULL, ep.residual = NULL, ep.relu = 0;
+    switch (kind) {
+    case RN_FPN_INNER:
+        ep.shift = f->raw[l][1];
+        return rn_conv2d_nhwc_forward_dt(ctx, dt, dt, x_nhwc, inner, f->packed_inner[l], 1, 1, 0, h[l], w[l], B, f->cin[l], a,
+                                         h[l], w[l], &ep);
+    case RN_FPN_TOPDOWN: {  // level (the coarser) -> level - 1, in place on the finer lateral
+        void *fine = (char *)f->inner[l - 1] + img0 * h[l - 1] * w[l - 1] * a * es;
+        return rn_upsample_nearest_add_forward_dt(ctx, dt, inner, B, h[l], w[l], a, fine, fine, h[l - 1], w[l - 1]);
+    }
+    case RN_FPN_LAYER:
+        ep.shift = f->raw[l][3];
+        return rn_conv2d_nhwc_forward_dt(ctx, dt, RN_DTYPE_F32, inner, outb, f->packed_layer[l], 3, 1, 1, h[l], w[l], B, a, a,
+                                         h[l], w[l], &ep);
+    case RN_FPN_POOL:
+        return rn_maxpool2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, outb, poolb, 1, 2, 0, hp, wp, B, a, h[l], w[l]);
+    default:
+        if (level == f->n) return rn_nhwc_to_nchw_dt(ctx, RN_DTYPE_F32, poolb, dst_nchw, B, a, hp, wp);
+        return rn_nhwc_to_nchw_dt(ctx, RN_DTYPE_F32, outb, dst_nchw, B, a, h[l], w[l]);
+    }
+}
+
+int rn_fpn_forward(rn_fpn *f, const void *const *x_nhwc, uint64_t B, const uint64_t *h, const uint64_t *w,
+                   float *const *out_nchw)
+{
+    if (!f) return RN_ERR_INVALID;
+    rn_ctx *ctx = f->ctx;
+    RN_ENTER(ctx);
+    RN_REQUIRE(ctx, f->finalized, "the neck is not finalized");
+    RN_REQUIRE(ctx, x_nhwc && h && w && out_nchw, "x_nhwc, h, w or out_nchw is NULL");
+    const int n = f->n, n_out = n + f->extra;
+    bool wanted = false;
+    for (int i = 0; i < n; ++i) {
+        RN_REQUIRE(ctx, x_nhwc[i], "a level's map is NULL");
+        RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(x_nhwc[i]) & 15) == 0, "a level's map is off a 16-byte boundary");
+        RN_REQUIRE(ctx, h[i] >= 1 && w[i] >= 1, "h and w must be >= 1");
+        RN_REQUIRE(ctx, h[i] < (1ull << 31) && w[i] < (1ull << 31) && B < (1ull << 31) && B * h[i] * w[i] < (1ull << 31),
+                   "B * h * w must be below 2^31");
+    }
+    for (int i = 0; i < n_out; ++i) {
+        RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(out_nchw[i]) & 3) == 0, "an output is off a 4-byte boundary");
+        wanted = wanted || out_nchw[i];
+    }
+    RN_REQUIRE(ctx, wanted, "nothing wanted (every output is NULL)");
+    if (B == 0) return RN_OK;
+    RN_TRY(rn_fpn_reserve(f, B, h, w));
+    const int saved_layout = ctx->layout;
+    ctx->layout = RN_LAYOUT_NHWC;
+    const bool pool = f->extra && out_nchw[n];
+    int st = RN_OK;
+    for (int i = 0; i < n && st == RN_OK; ++i) st = rn_fpn_step(f, ctx, RN_FPN_INNER, i, x_nhwc[i], 0, B, h, w, NULL);
+    for (int i = n - 1; i >= 1 && st == RN_OK; --i) st = rn_fpn_step(f, ctx, RN_FPN_TOPDOWN, i, NULL, 0, B, h, w, NULL);
+    for (int i = 0; i < n && st == RN_OK; ++i)
+        if (out_nchw[i] || (pool && i == n - 1)) st = rn_fpn_step(f, ctx, RN_FPN_LAYER, i, NULL, 0, B, h, w, NULL);
+    if (pool && st == RN_OK) st = rn_fpn_step(f, ctx, RN_FPN_POOL, n - 1, NULL, 0, B, h, w, NULL);
+    for (int i = 0; i < n_out && st == RN_OK; ++i)
+        if (out_nchw[i]) st = rn_fpn_step(f, ctx, RN_FPN_EXPORT, i, NULL, 0, B, h, w, out_nchw[i]);
+    ctx->layout = saved_layout;
+    return st;
+}
+
+}  // extern "C"

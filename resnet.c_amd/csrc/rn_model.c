@@ -179,6 +179,12 @@ struct rn_model {
     /* rn_model_forward_segment: the head and the buffers of the call that is running (NULL in every other forward) */
     rn_seg_head *seg_head;
     const rn_seg_outputs *seg;
+    /* rn_model_forward_fpn: the neck, the buffers and the levels of the call that is running (fpn NULL in every other
+     * forward): level j reads stage fpn_stage[j] (1..4), an fpn_h[j] x fpn_w[j] map */
+    rn_fpn *fpn;
+    const rn_fpn_outputs *fpn_out;
+    int fpn_n, fpn_extra, fpn_stage[4];
+    uint64_t fpn_a, fpn_h[4], fpn_w[4];
     /* tile tuning: calls of the last forward, and the batch size the tiles were tuned for */
     rn_conv_call *calls;
     int n_calls, cap_calls, recording;
@@ -1457,8 +1463,59 @@ static int op_segment(rn_model *m, const float *x, uint64_t B, uint64_t h, uint6
     return RN_OK;
 }
 
+/* the profile names of the neck's launches (a record keeps the pointer, so they are literals) */
+static const char *const kFpnInnerOps[4] = {"fpn_inner0", "fpn_inner1", "fpn_inner2", "fpn_inner3"};
+static const char *const kFpnTopdownOps[4] = {NULL, "fpn_topdown1", "fpn_topdown2", "fpn_topdown3"};
+static const char *const kFpnLayerOps[4] = {"fpn_layer0", "fpn_layer1", "fpn_layer2", "fpn_layer3"};
+static const char *const kFpnExportOps[4] = {"fpn_export0", "fpn_export1", "fpn_export2", "fpn_export3"};
+
+/* one launch of the neck of rn_model_forward_fpn with its profile record: the images of this launch use the slice
+ * of the neck's scratch that starts at their index in the sub-batch, for op_segment's reason */
+static int op_fpn(rn_model *m, int kind, int level, const char *op, const void *x, uint64_t B, float *dst)
+{
+    double flops = 0.0, bytes = 0.0;
+    rn_fpn_cost(m->fpn, kind, level, B, m->fpn_h, m->fpn_w, &flops, &bytes);
+    TRY(prof_begin(m, op, "fpn", flops, bytes));
+    TRY(rn_fpn_step(m->fpn, m->run.ctx, kind, level, x, m->run.sub0, B, m->fpn_h, m->fpn_w, dst));
+    return prof_end(m);
+}
+
+/* rn_model_forward_fpn: the lateral 1x1 of the level that reads stage li + 1, on the stage's output x in place.
+ * Queued right behind the stage's last block on that block's stream, like op_stage_map and for its reason. */
+static int op_fpn_lateral(rn_model *m, int li, const float *x, uint64_t B)
+{
+    int j;
+    for (j = 0; j < m->fpn_n; ++j)
+        if (m->fpn_stage[j] == li + 1) TRY(op_fpn(m, RN_FPN_INNER, j, kFpnInnerOps[j], x, B, NULL));
+    return RN_OK;
+}
+
+/* rn_model_forward_fpn: what follows the laterals, behind the last block of all (where op_segment sits): the
+ * top-down steps coarsest first, the 3x3 of every wanted level (the coarsest one's also for the pool), the pool, the
+ * exports into the caller's buffers from image run.img0 on */
+static int op_fpn_rest(rn_model *m, uint64_t B)
+{
+    const int n = m->fpn_n;
+    float *const *out = m->fpn_out->level;
+    const int pool = m->fpn_extra && out[n];
+    int j;
+    for (j = n - 1; j >= 1; --j) TRY(op_fpn(m, RN_FPN_TOPDOWN, j, kFpnTopdownOps[j], NULL, B, NULL));
+    for (j = 0; j < n; ++j)
+        if (out[j] || (pool && j == n - 1)) TRY(op_fpn(m, RN_FPN_LAYER, j, kFpnLayerOps[j], NULL, B, NULL));
+    if (pool) TRY(op_fpn(m, RN_FPN_POOL, n - 1, "fpn_pool", NULL, B, NULL));
+    for (j = 0; j <= n; ++j) {
+        uint64_t H, W;
+        if (j == n ? !pool : !out[j]) continue;
+        TRY(rn_fpn_level_shape(m->fpn, j, m->fpn_h[j < n ? j : n - 1], m->fpn_w[j < n ? j : n - 1], NULL, &H, &W));
+        TRY(op_fpn(m, RN_FPN_EXPORT, j, j < n ? kFpnExportOps[j] : "fpn_export_pool", NULL, B,
+                   out[j] + m->run.img0 * m->fpn_a * H * W));
+    }
+    return RN_OK;
+}
+
 /* blocks [first, last) on an *H x *W map, which become those of block last's input; behind the last block of a
- * stage the export of its map, when the running call wants it; behind the last block of all the segmentation head */
+ * stage the export of its map or the neck's lateral on it, when the running call wants either; behind the last block
+ * of all the segmentation head or the rest of the neck */
 static int run_blocks(rn_model *m, int first, int last, uint64_t B, uint64_t *H, uint64_t *W, int mode)
 {
     int bi, li = 0, end = m->depths[0]; /* block `end` is the first of stage li + 1 */
@@ -1467,6 +1524,8 @@ static int run_blocks(rn_model *m, int first, int last, uint64_t B, uint64_t *H,
         while (bi >= end) end += m->depths[++li];
         if (m->maps && bi + 1 == end && m->maps->layer[li]) TRY(op_stage_map(m, li, block_input(m, bi + 1), B, *H, *W));
         if (m->seg_head && bi + 1 == m->n_blocks) TRY(op_segment(m, block_input(m, bi + 1), B, *H, *W));
+        if (m->fpn && bi + 1 == end) TRY(op_fpn_lateral(m, li, block_input(m, bi + 1), B));
+        if (m->fpn && bi + 1 == m->n_blocks) TRY(op_fpn_rest(m, B));
     }
     return RN_OK;
 }
@@ -1679,7 +1738,7 @@ static int forward_outputs(rn_model *m, const void *input, int in_u8, uint64_t B
     /* bf16 storage exists only with the fused epilogues (no standalone bf16 bn/relu/add) */
     if (m->dtype != RN_DTYPE_F32 && mode != RN_FWD_FUSED) return RN_ERR_UNSUPPORTED;
     if (outs) {
-        if (!logits && !outs->features && !outs->probs && outs->k == 0 && !m->maps && !m->seg_head) return RN_ERR_INVALID;
+        if (!logits && !outs->features && !outs->probs && outs->k == 0 && !m->maps && !m->seg_head && !m->fpn) return RN_ERR_INVALID;
         if (outs->k > 0 && (!outs->topk_prob || !outs->topk_idx || outs->k > 64 || outs->k > m->classes))
             return RN_ERR_INVALID;
     }
@@ -1823,6 +1882,75 @@ int rn_model_forward_segment_u8(rn_model *m, rn_seg_head *hd, const uint8_t *inp
                                 const rn_model_outputs *outs, const rn_seg_outputs *seg, int mode)
 {
     return forward_segment(m, hd, input_nhwc, 1, B, outs, seg, mode);
+}
+
+/* rn_model_forward_fpn(_u8): like the maps, the request is state of this call alone -- set once every refusal has
+ * passed, cleared on every way out (run_blocks asks m->fpn). */
+static int forward_fpn(rn_model *m, rn_fpn *fpn, const void *input, int in_u8, uint64_t B, const rn_model_outputs *outs,
+                       const int *stages, const rn_fpn_outputs *fo, int mode)
+{
+    rn_model_outputs none;
+    const char *why = NULL;
+    char msg[200];
+    uint64_t cin[4], a = 0, h[4], w[4];
+    int n = 0, extra = 0, j, wanted = 0, st;
+    if (!m) return RN_ERR_INVALID;
+    if (!m->finalized) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_fpn: the model is not finalized");
+    if (!rn_fpn_matches(fpn, m->ctx, m->dtype, &why)) {
+        snprintf(msg, sizeof(msg), "rn_model_forward_fpn: %s", why);
+        return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, msg);
+    }
+    if (!stages) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_fpn: stages is NULL");
+    if (!fo) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_fpn: fpn_out is NULL");
+    rn_fpn_dims(fpn, &n, &extra, &a, cin);
+    for (j = 0; j < n; ++j)
+        if (stages[j] < 1 || stages[j] > 4 || (j > 0 && stages[j] <= stages[j - 1]))
+            return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_fpn: stages must be ascending, each 1..4");
+    for (j = 0; j < n; ++j) {
+        uint64_t C = 0;
+        TRY(rn_model_stage_shape(m, stages[j], &C, &h[j], &w[j]));
+        if (C != cin[j]) {
+            snprintf(msg, sizeof(msg), "rn_model_forward_fpn: in_channels of level %d is %llu, layer%d has %llu channels", j,
+                     (unsigned long long)cin[j], stages[j], (unsigned long long)C);
+            return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, msg);
+        }
+    }
+    for (j = 0; j < n + extra; ++j) {
+        if (!fo->level[j]) continue;
+        wanted = 1;
+        if ((uintptr_t)fo->level[j] & 3) {
+            snprintf(msg, sizeof(msg), "rn_model_forward_fpn: fpn_out->level[%d] must be 4-byte aligned", j);
+            return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, msg);
+        }
+    }
+    if (!wanted) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_fpn: nothing wanted (every level is NULL)");
+    if (!input || B == 0 || (mode != RN_FWD_REFERENCE_OPS && mode != RN_FWD_FUSED)) return RN_ERR_INVALID;
+    if (m->dtype != RN_DTYPE_F32 && mode != RN_FWD_FUSED)
+        return rn_ctx_set_error(m->ctx, RN_ERR_UNSUPPORTED, "rn_model_forward_fpn: a bf16 model runs RN_FWD_FUSED only");
+    TRY(rn_fpn_reserve(fpn, B < m->max_sub ? B : m->max_sub, h, w));
+    memset(&none, 0, sizeof(none));
+    if (!outs) outs = &none;
+    m->fpn = fpn;
+    m->fpn_out = fo;
+    m->fpn_n = n, m->fpn_extra = extra, m->fpn_a = a;
+    for (j = 0; j < n; ++j) m->fpn_stage[j] = stages[j], m->fpn_h[j] = h[j], m->fpn_w[j] = w[j];
+    st = forward_outputs(m, input, in_u8, B, outs->logits, outs, mode, 0);
+    m->fpn = NULL;
+    m->fpn_out = NULL;
+    m->maps_done = 0;
+    return st;
+}
+
+int rn_model_forward_fpn(rn_model *m, rn_fpn *fpn, const float *input_nchw, uint64_t B, const rn_model_outputs *outs,
+                         const int *stages, const rn_fpn_outputs *fpn_out, int mode)
+{
+    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, mode);
+}
+
+int rn_model_forward_fpn_u8(rn_model *m, rn_fpn *fpn, const uint8_t *input_nhwc, uint64_t B, const rn_model_outputs *outs,
+                            const int *stages, const rn_fpn_outputs *fpn_out, int mode)
+{
+    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, mode);
 }
 
 /* The decoded-image route resizes to 256 and crops 224 x 224: a model of another size refuses it. */

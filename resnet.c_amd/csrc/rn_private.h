@@ -68,6 +68,26 @@ int rn_seg_head_reserve(rn_seg_head *hd, uint64_t images, uint64_t pixels);
 int rn_seg_head_step(rn_seg_head *hd, rn_ctx *ctx, int step, const void *x_nhwc, uint64_t img0, uint64_t B, uint64_t h,
                      uint64_t w, uint64_t H, uint64_t W, float *scores_nchw, uint8_t *labels);
 
+/* ---- rn_fpn.hip: the feature pyramid neck as the model driver queues it ---- */
+/* the launches of a neck's forward: the lateral 1x1 of a level, the top-down step from a level into the next finer
+ * one (in place on that one's lateral), the 3x3 of a level (fp32 output), the max-pool of the coarsest 3x3 output,
+ * the NCHW export of a level's output (level == n_levels: the pooled one) */
+enum { RN_FPN_INNER = 0, RN_FPN_TOPDOWN = 1, RN_FPN_LAYER = 2, RN_FPN_POOL = 3, RN_FPN_EXPORT = 4 };
+/* 1 when the neck is finalized, stores `dtype` and lives on the device of ctx (its weights and scratch are read by
+ * launches on the model's streams); *why: what is wrong otherwise */
+int rn_fpn_matches(const rn_fpn *fpn, const rn_ctx *ctx, int dtype, const char **why);
+/* levels, extra (0 none, 1 pool), out_channels, in_channels of every level; any pointer may be NULL */
+void rn_fpn_dims(const rn_fpn *fpn, int *n_levels, int *extra, uint64_t *out_channels, uint64_t in_channels[4]);
+/* the neck's scratch for `images` images whose level i is an h[i] x w[i] map; grows like the model's logits buffer */
+int rn_fpn_reserve(rn_fpn *fpn, uint64_t images, const uint64_t *h, const uint64_t *w);
+/* FLOPs and bytes of one launch of `kind` at `level` for B images (the profile's figures) */
+void rn_fpn_cost(const rn_fpn *fpn, int kind, int level, uint64_t B, const uint64_t *h, const uint64_t *w, double *flops,
+                 double *bytes);
+/* one launch of `kind` at `level` on ctx for B images whose scratch starts img0 images into the neck's tensors.
+ * x_nhwc: the level's map (RN_FPN_INNER only); dst_nchw: where the B images' output goes (RN_FPN_EXPORT only) */
+int rn_fpn_step(rn_fpn *fpn, rn_ctx *ctx, int kind, int level, const void *x_nhwc, uint64_t img0, uint64_t B,
+                const uint64_t *h, const uint64_t *w, float *dst_nchw);
+
 /* ---- rn_stem.hip ---- */
 /* 1 when the fused stem + max-pool launch takes a padded image of Hp x Wp (nchw: the NCHW-fetching form on
  * an image of Hp - 6 x Wp - 6) of `dtype`: its documented conditions on the geometry alone */

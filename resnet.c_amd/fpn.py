@@ -1,0 +1,202 @@
+"""Feature pyramid on top of the backbone: torchvision's FeaturePyramidNetwork (the neck of resnet_fpn_backbone).
+
+Key shapes (``fpn_shapes``), seeded weights (``generate_fpn_state``), the split of a torchvision detection state dict
+(``split_state``), the float64 restatement of what the device computes (``fpn_ref``) and ``FeaturePyramidNetwork``,
+the Python face of ``rn_fpn_*``.  ``NativeModel.forward_fpn`` runs a neck inside a forward: every lateral 1x1 right
+behind its stage, the rest behind layer4.  ``ops.upsample_nearest_add`` is the top-down launch alone.
+"""
+from __future__ import annotations
+
+import ctypes
+import re
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib as L
+from . import weights
+
+EXTRA = {None: 0, "none": 0, "pool": 1}
+
+
+def fpn_shapes(in_channels_list: Sequence[int], out_channels: int) -> Dict[str, Tuple[int, ...]]:
+    """Key -> shape of torchvision's FeaturePyramidNetwork(in_channels_list, out_channels) with norm_layer=None, in
+    the order of its state dict: every lateral 1x1 (inner_blocks), then every 3x3 (layer_blocks)."""
+    a = int(out_channels)
+    out: Dict[str, Tuple[int, ...]] = {}
+    for i, c in enumerate(in_channels_list):
+        out[f"inner_blocks.{i}.0.weight"] = (a, int(c), 1, 1)
+        out[f"inner_blocks.{i}.0.bias"] = (a,)
+    for i, _ in enumerate(in_channels_list):
+        out[f"layer_blocks.{i}.0.weight"] = (a, a, 3, 3)
+        out[f"layer_blocks.{i}.0.bias"] = (a,)
+    return out
+
+
+def generate_fpn_state(in_channels_list: Sequence[int], out_channels: int, seed: int = 0) -> Dict[str, np.ndarray]:
+    """Seeded tensors of the neck under torchvision's keys, from the generator of weights.py: every convolution
+    He-uniform over its fan-in, every bias uniform in +-0.1, every key with a name of its own in the generator."""
+    tag = f"fpn{'_'.join(str(int(c)) for c in in_channels_list)}x{int(out_channels)}"
+    out = {}
+    for key, shape in fpn_shapes(in_channels_list, out_channels).items():
+        if len(shape) == 4:
+            bound = float(np.sqrt(6.0 / (shape[1] * shape[2] * shape[3])))
+            out[key] = weights._uniform(f"{tag}.{key}", shape, -bound, bound, seed)
+        else:
+            out[key] = weights._uniform(f"{tag}.{key}", shape, -0.1, 0.1, seed)
+    return out
+
+
+_KEY = re.compile(r"^(inner_blocks|layer_blocks)\.(\d+)\.(?:0\.)?(weight|bias)$")
+
+
+def split_state(state) -> Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]:
+    """A state dict that holds a torchvision FPN -> (backbone_state, fpn_state).  The neck's keys may carry the prefix
+    "fpn." or "backbone.fpn." and either spelling, "inner_blocks.0.0.weight" (Conv2dNormActivation) or the older
+    "inner_blocks.0.weight"; they come back as fpn_shapes spells them.  "backbone.body." / "body." keys come back
+    without the prefix (the keys NativeModel reads); everything else (rpn.*, roi_heads.*, num_batches_tracked) is
+    dropped.  A key that starts like a neck's and is not one raises ValueError."""
+    backbone, neck = {}, {}
+    for key, value in state.items():
+        if key.endswith("num_batches_tracked"):
+            continue
+        arr = value.detach().cpu().numpy() if hasattr(value, "detach") else np.asarray(value)
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+        k = key
+        for prefix in ("backbone.fpn.", "fpn."):
+            if k.startswith(prefix):
+                k = k[len(prefix):]
+                break
+        if k.startswith(("inner_blocks.", "layer_blocks.")):
+            m = _KEY.match(k)
+            if not m:
+                raise ValueError(f"{key!r}: not a key of torchvision's FeaturePyramidNetwork")
+            neck[f"{m.group(1)}.{int(m.group(2))}.0.{m.group(3)}"] = arr
+            continue
+        for prefix in ("backbone.body.", "body."):
+            if key.startswith(prefix):
+                backbone[key[len(prefix):]] = arr
+                break
+    return backbone, neck
+
+
+def fpn_ref(maps_nchw_f64, state, extra="pool", round_fn=None) -> Dict[str, np.ndarray]:
+    """The neck in torch on the CPU, float64: maps [B,in_i,h_i,w_i], finest first -> {"0": [B,a,h_0,w_0], ..., "pool"}
+    float64.  The top-down step gathers with ops.nearest_index, the index contract of
+    rn_upsample_nearest_add_forward_dt.  round_fn (bf16 necks): applied to the maps, every convolution weight and
+    every tensor the device stores in its element type -- the laterals and the merged tensors; the biases and the
+    3x3 outputs (fp32 on the device) stay as they are."""
+    import torch
+    import torch.nn.functional as F
+
+    from .ops import nearest_index
+    rd = (lambda a: np.asarray(round_fn(np.asarray(a, dtype=np.float32)), dtype=np.float64)) if round_fn else (lambda a: a)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))  # noqa: E731
+    n = len(maps_nchw_f64)
+    out: Dict[str, np.ndarray] = {}
+    with torch.no_grad():
+        inner = []
+        for i, x in enumerate(maps_nchw_f64):
+            y = F.conv2d(t(rd(x)), t(rd(state[f"inner_blocks.{i}.0.weight"])), t(state[f"inner_blocks.{i}.0.bias"]))
+            inner.append(rd(y.numpy()))
+        for i in range(n - 2, -1, -1):
+            H, W = inner[i].shape[2:]
+            iy, ix = nearest_index(inner[i + 1].shape[2], H), nearest_index(inner[i + 1].shape[3], W)
+            inner[i] = rd(inner[i] + inner[i + 1][:, :, iy][:, :, :, ix])
+        for i in range(n):
+            y = F.conv2d(t(inner[i]), t(rd(state[f"layer_blocks.{i}.0.weight"])), t(state[f"layer_blocks.{i}.0.bias"]),
+                         padding=1)
+            out[str(i)] = y.numpy()
+    if EXTRA[extra]:
+        out["pool"] = np.ascontiguousarray(out[str(n - 1)][:, :, ::2, ::2])
+    return out
+
+
+class FeaturePyramidNetwork:
+    """rn_fpn_*: FeaturePyramidNetwork(in_channels_list, out_channels, extra_blocks=LastLevelMaxPool()) on the device
+    (extra=None: no extra block); state holds torchvision's tensors (fpn_shapes; split_state normalises the keys).
+    dtype "f32" or "bf16": storage of the input maps, the lateral tensors and the weight panels; the outputs are fp32
+    either way."""
+
+    def __init__(self, in_channels_list: Sequence[int], out_channels: int, state: Dict[str, np.ndarray],
+                 extra: Optional[str] = "pool", dtype: str = "f32", ctx=None):
+        from .tensor import get_ctx
+        self.ctx = ctx or get_ctx()
+        self.in_channels_list = tuple(int(c) for c in in_channels_list)
+        self.out_channels, self.extra, self.dtype = int(out_channels), EXTRA[extra], dtype
+        self.handle = None
+        lib = L.lib()
+        h = ctypes.c_void_p()
+        cin = (ctypes.c_uint64 * max(len(self.in_channels_list), 1))(*self.in_channels_list)
+        L.check(lib.rn_fpn_create(self.ctx.handle, ctypes.byref(h), len(self.in_channels_list), cin, self.out_channels,
+                                  self.extra), "rn_fpn_create", self.ctx.handle)
+        self.handle = h
+        L.check(lib.rn_fpn_set_dtype(h, {"f32": L.RN_DTYPE_F32, "bf16": L.RN_DTYPE_BF16}[dtype]), "rn_fpn_set_dtype",
+                self.ctx.handle)
+        for key, shape in fpn_shapes(self.in_channels_list, self.out_channels).items():
+            arr = np.ascontiguousarray(state[key], dtype=np.float32)
+            assert arr.size == int(np.prod(shape)), (key, arr.shape, shape)
+            L.check(lib.rn_fpn_set_tensor(h, key.encode(), arr.ctypes.data, arr.size), f"rn_fpn_set_tensor({key})",
+                    self.ctx.handle)
+        L.check(lib.rn_fpn_finalize(h), "rn_fpn_finalize", self.ctx.handle)
+
+    @property
+    def names(self) -> Tuple[str, ...]:
+        """torchvision's output names: "0" .. "n-1", then "pool" with the extra block."""
+        return tuple(str(i) for i in range(len(self.in_channels_list))) + (("pool",) if self.extra else ())
+
+    def level_shape(self, name: str, h_in: int, w_in: int) -> Tuple[int, int, int]:
+        """(C, H, W) of output `name` when its level's map (for "pool": the coarsest level's) is h_in x w_in."""
+        c, h, w = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        L.check(L.lib().rn_fpn_level_shape(self.handle, self.names.index(name), int(h_in), int(w_in), ctypes.byref(c),
+                                           ctypes.byref(h), ctypes.byref(w)), "rn_fpn_level_shape", self.ctx.handle)
+        return int(c.value), int(h.value), int(w.value)
+
+    def forward(self, maps_nhwc, levels=None) -> Dict[str, np.ndarray]:
+        """maps_nhwc: one host array [B,h_i,w_i,in_i] fp32 per level, finest first (a bf16 neck rounds them on upload;
+        uint16 bf16 bit patterns are taken as they are) -> {"0": [B,a,h_0,w_0] fp32, ..., "pool": ...}, the names in
+        `levels` only (default: all).  Synchronous convenience."""
+        from .ops import _down_raw, _up_raw, to_bf16_bits
+        from .tensor import _DeviceBuffer
+        n = len(self.in_channels_list)
+        assert len(maps_nhwc) == n, (len(maps_nhwc), n)
+        levels = self.names if levels is None else tuple(levels)
+        for name in levels:
+            if name not in self.names:
+                raise ValueError(f"unknown level {name!r}: one of {self.names}")
+        xs = []
+        for x, c in zip(maps_nhwc, self.in_channels_list):
+            x = np.asarray(x)
+            if self.dtype == "bf16":
+                x = x if x.dtype == np.uint16 else to_bf16_bits(x).reshape(x.shape)
+            else:
+                x = np.ascontiguousarray(x, dtype=np.float32)
+            assert x.ndim == 4 and x.shape[3] == c and x.shape[0] == np.shape(maps_nhwc[0])[0], (x.shape, c)
+            xs.append(x)
+        B = xs[0].shape[0]
+        hs, ws = [x.shape[1] for x in xs], [x.shape[2] for x in xs]
+        dx = [_up_raw(x) for x in xs]
+        shapes, bufs = {}, {}
+        for i, name in enumerate(self.names):
+            j = min(i, n - 1)
+            shapes[name] = (B,) + self.level_shape(name, hs[j], ws[j])
+            if name in levels:
+                bufs[name] = _DeviceBuffer(self.ctx, max(int(np.prod(shapes[name])) * 4, 16))
+        xp = (ctypes.c_void_p * n)(*[d.ptr for d in dx])
+        op = (ctypes.c_void_p * len(self.names))(*[bufs[name].ptr if name in bufs else None for name in self.names])
+        L.check(L.lib().rn_fpn_forward(self.handle, xp, B, (ctypes.c_uint64 * n)(*hs), (ctypes.c_uint64 * n)(*ws), op),
+                "rn_fpn_forward", self.ctx.handle)
+        self.ctx.sync()
+        return {name: _down_raw(bufs[name], np.float32, int(np.prod(shapes[name]))).reshape(shapes[name])
+                for name in self.names if name in bufs}
+
+    def close(self) -> None:
+        if self.handle:
+            L.lib().rn_fpn_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -456,6 +456,75 @@ class NativeModel:
         forward_segment on preprocess.normalize_u8 of the bytes, bit for bit."""
         return self.forward_segment(np.ascontiguousarray(px, dtype=np.uint8), head, **kw)
 
+    def forward_fpn(self, x: np.ndarray, neck, stages=STAGES, levels=None, *, logits: bool = False,
+                    features: bool = False, probs: bool = False, topk: int = 0, fused: bool = True) -> dict:
+        """One forward with a feature pyramid neck (rn_model_forward_fpn; torchvision's resnet_fpn_backbone): an
+        ordered dict "0", "1", .. (one per stage in `stages`, finest first), then "pool" when the neck has the extra
+        block -> [B,a,H,W] fp32; then the head outputs asked for, as forward_outputs returns them.  neck: an
+        fpn.FeaturePyramidNetwork of this model's dtype on this model's context whose in_channels_list is the
+        channels of `stages`.  levels: the names wanted (default: all).  x: fp32 NCHW [B,3,H,W], or uint8 NHWC
+        [B,H,W,3].  An unknown, repeated or descending stage, a stage count that is not the neck's, or an unknown
+        level raises ValueError."""
+        from .ops import _down_raw, _up_raw
+        from .tensor import _DeviceBuffer
+        stages = tuple(stages)
+        for s in stages:
+            if s not in self.STAGES:
+                raise ValueError(f"unknown stage {s!r}: one of {self.STAGES}")
+        idx = [self.STAGES.index(s) + 1 for s in stages]
+        if any(b <= a for a, b in zip(idx, idx[1:])):
+            raise ValueError(f"stages must ascend without repeats: {stages}")
+        if len(stages) != len(neck.in_channels_list):
+            raise ValueError(f"{len(stages)} stages for a neck of {len(neck.in_channels_list)} levels")
+        names = neck.names
+        levels = names if levels is None else tuple(levels)
+        for name in levels:
+            if name not in names:
+                raise ValueError(f"unknown level {name!r}: one of {names}")
+        x = np.asarray(x)
+        u8 = x.dtype == np.uint8
+        x = np.ascontiguousarray(x, dtype=np.uint8 if u8 else np.float32)
+        self._check_input(x, u8)
+        B, C, F, k = x.shape[0], self.classes, self.features, int(topk)
+        xin = _up_raw(x)
+        stage_shapes = self.stage_shapes
+        shapes, lbufs = {}, {}
+        fo = L.FpnOutputs()
+        for i, name in enumerate(names):
+            _, h, w = stage_shapes[stages[min(i, len(stages) - 1)]]
+            shapes[name] = (B,) + neck.level_shape(name, h, w)
+            if name in levels:
+                lbufs[name] = _DeviceBuffer(self.ctx, max(int(np.prod(shapes[name])) * 4, 16))
+                fo.level[i] = lbufs[name].ptr
+        bufs = {}
+
+        def buf(name, want, nbytes):
+            if want:
+                bufs[name] = _DeviceBuffer(self.ctx, max(nbytes, 16))
+            return bufs[name].ptr if want else None
+
+        o = L.ModelOutputs(buf("logits", logits, B * C * 4), buf("features", features, B * F * 4),
+                           buf("probs", probs, B * C * 4), buf("topk_prob", k > 0, B * k * 4),
+                           buf("topk_idx", k > 0, B * k * 8), k)
+        fn = L.lib().rn_model_forward_fpn_u8 if u8 else L.lib().rn_model_forward_fpn
+        L.check(fn(self.handle, neck.handle, xin.ptr, B, ctypes.byref(o), (ctypes.c_int * len(idx))(*idx), ctypes.byref(fo),
+                   L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS), "rn_model_forward_fpn", self.ctx.handle)
+        self.ctx.sync()
+        shapes.update({"logits": (B, C), "features": (B, F), "probs": (B, C), "topk_prob": (B, k), "topk_idx": (B, k)})
+        out = {name: _down_raw(lbufs[name], np.float32, int(np.prod(shapes[name]))).reshape(shapes[name])
+               for name in names if name in lbufs}
+        for name, b in bufs.items():
+            if name == "topk_idx":
+                out[name] = _down_raw(b, np.uint64, B * k).astype(np.int64).reshape(B, k)
+            else:
+                out[name] = _down_raw(b, np.float32, int(np.prod(shapes[name]))).reshape(shapes[name])
+        return out
+
+    def forward_fpn_u8(self, px: np.ndarray, neck, stages=STAGES, levels=None, **kw) -> dict:
+        """forward_fpn from 8-bit RGB [B,H,W,3] (rn_model_forward_fpn_u8): the same pyramid as forward_fpn on
+        preprocess.normalize_u8 of the bytes, bit for bit."""
+        return self.forward_fpn(np.ascontiguousarray(px, dtype=np.uint8), neck, stages, levels, **kw)
+
     def tensor_keys(self) -> List[Tuple[str, int]]:
         out, i, n = [], 0, ctypes.c_uint64()
         while True:

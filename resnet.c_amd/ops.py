@@ -874,3 +874,66 @@ def concat_channels(srcs, per_image=None) -> np.ndarray:
 def concat_channels_bf16(srcs, per_image=None) -> np.ndarray:
     """The bf16 form of concat_channels: uint16 bit patterns in (to_bf16_bits of fp32 data) and out, C_i % 8 == 0."""
     return _concat_channels(L.RN_DTYPE_BF16, np.uint16, srcs, per_image)
+
+
+def nearest_index(n_in: int, n_out: int) -> np.ndarray:
+    """The source index of every output index along one axis, as rn_upsample_nearest_add_forward_dt computes it
+    (torch's size= form): scale = fp32(n_in) / fp32(n_out), i(o) = min(int(floor(fp32(fp32(o) * scale))), n_in - 1),
+    the product rounded to fp32 on its own."""
+    scale = np.float32(n_in) / np.float32(n_out)
+    o = np.arange(n_out, dtype=np.float32)
+    prod = (o * scale).astype(np.float32)
+    return np.minimum(np.floor(prod).astype(np.int64), n_in - 1)
+
+
+def upsample_nearest_add_ref(top, lat=None, size=None) -> np.ndarray:
+    """The contract of rn_upsample_nearest_add_forward_dt in numpy: top [B,h,w,C] and lat [B,H,W,C] or None, NHWC;
+    size = (H, W) (default: lat's).  fp32 arrays: lat + top[:, iy][:, :, ix], one fp32 add.  uint16 arrays (bf16 bit
+    patterns): widened, added in fp32, rounded once to the nearest even bf16.  lat = None: the gathered copy of top,
+    every bit kept."""
+    top = np.asarray(top)
+    if size is None:
+        size = np.asarray(lat).shape[1:3]
+    H, W = int(size[0]), int(size[1])
+    iy, ix = nearest_index(top.shape[1], H), nearest_index(top.shape[2], W)
+    up = top[:, iy][:, :, ix]
+    if lat is None:
+        return np.ascontiguousarray(up)
+    lat = np.asarray(lat)
+    assert lat.dtype == top.dtype and lat.shape == up.shape, (lat.shape, up.shape, lat.dtype, top.dtype)
+    if top.dtype == np.uint16:
+        with np.errstate(invalid="ignore"):
+            return to_bf16_bits(from_bf16_bits(lat) + from_bf16_bits(up)).reshape(up.shape)
+    assert top.dtype == np.float32, top.dtype
+    with np.errstate(invalid="ignore"):
+        return lat + up
+
+
+def _upsample_nearest_add(dtype, np_dtype, top, lat, size):
+    from .tensor import _DeviceBuffer
+    ctx = get_ctx()
+    top = np.ascontiguousarray(top, dtype=np_dtype)
+    B, h, w, C = top.shape
+    if lat is not None:
+        lat = np.ascontiguousarray(lat, dtype=np_dtype)
+        size = lat.shape[1:3] if size is None else size
+        assert lat.shape == (B, int(size[0]), int(size[1]), C), (lat.shape, top.shape, size)
+    H, W = int(size[0]), int(size[1])
+    dt, dl = _up_raw(top), (_up_raw(lat) if lat is not None else None)
+    n = B * H * W * C
+    out = _DeviceBuffer(ctx, max(n * np.dtype(np_dtype).itemsize, 16))
+    L.check(L.lib().rn_upsample_nearest_add_forward_dt(ctx.handle, dtype, dt.ptr, B, h, w, C, dl.ptr if dl else None,
+                                                       out.ptr, H, W), "rn_upsample_nearest_add_forward_dt", ctx.handle)
+    ctx.sync()
+    return _down_raw(out, np_dtype, n).reshape(B, H, W, C)
+
+
+def upsample_nearest_add(top, lat=None, size=None) -> np.ndarray:
+    """rn_upsample_nearest_add_forward_dt in fp32: host arrays top [B,h,w,C] and lat [B,H,W,C] or None (then size =
+    (H, W)), C % 4 == 0 -> lat + nearest_upsample(top) [B,H,W,C], one launch; bit for bit upsample_nearest_add_ref."""
+    return _upsample_nearest_add(L.RN_DTYPE_F32, np.float32, top, lat, size)
+
+
+def upsample_nearest_add_bf16(top, lat=None, size=None) -> np.ndarray:
+    """The bf16 form of upsample_nearest_add: uint16 bit patterns in (to_bf16_bits of fp32 data) and out, C % 8 == 0."""
+    return _upsample_nearest_add(L.RN_DTYPE_BF16, np.uint16, top, lat, size)
