@@ -608,7 +608,7 @@ int chain_launch(rn_ctx *ctx, const char *what, int dtype, const void *t2, const
     const bool s2 = mid_channels == 128 && channels == 512 && next_mid == 128 && !dual && dtype == RN_DTYPE_BF16;
     RN_REQUIRE(ctx, s1 || s2, "shapes: 64 -> 256 -> 64 | 128 channels, or (bf16) 128 -> 512 -> 128");
     RN_REQUIRE(ctx, !(dual && dtype == RN_DTYPE_F32 && next_mid != 64), "fp32 pair chain: next_mid 64");
-    const uint64_t es = dtype == RN_DTYPE_BF16 ? 2 : 4;
+    const uint64_t es = rn_elem_size(dtype);
     RN_REQUIRE(ctx, rows * channels * es < (1ull << 31), "tensor too large");
     if (dtype == RN_DTYPE_F32) {
         ChainParams q;

@@ -942,7 +942,7 @@ GemmParams describe(const rn_ctx *ctx, const Contraction &d)
     p.stamps = (unsigned long long *)ctx->debug_stamps;
     p.in_bytes = (int)(d.B * d.H * d.W * (uint64_t)p.Cs * es);
     p.w_bytes = (int)(d.Cout * (uint64_t)p.Ktot * es);
-    p.out_bytes = (int)(d.B * d.h_out * d.w_out * d.Cout * (uint64_t)(d.dt_out == RN_DTYPE_BF16 ? 2 : 4));
+    p.out_bytes = (int)(d.B * d.h_out * d.w_out * d.Cout * rn_elem_size(d.dt_out));
     return p;
 }
 
@@ -1127,7 +1127,7 @@ bool split_pixel_major(GemmParams &p, const Contraction &d, int BM, int BN)
 // on the output rows from row0 on.
 FinishParams finish_params(const Contraction &d, const void *partial, int splits, uint64_t row0, uint64_t slice)
 {
-    const uint64_t skip = row0 * d.Cout * (d.dt_out == RN_DTYPE_BF16 ? 2 : 4);  // bytes of output before row0
+    const uint64_t skip = row0 * d.Cout * rn_elem_size(d.dt_out);  // bytes of output before row0
     FinishParams f{};
     set_epilogue(f, d.ep);
     f.partial = (const float *)partial;

@@ -91,12 +91,6 @@ __global__ __launch_bounds__(kNaBlock) void upsample_nearest_add_kernel(const ne
     }
 }
 
-bool fpn_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
-{
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + b_bytes && y < x + a_bytes;
-}
-
 constexpr int kFpnMaxLevels = 4;
 
 }  // namespace
@@ -120,26 +114,18 @@ struct rn_fpn {
 
 namespace {
 
-uint64_t fpn_elem(const rn_fpn *f) { return f->dtype == RN_DTYPE_BF16 ? 2 : 4; }
-
 uint64_t fpn_key_numel(const rn_fpn *f, int level, int which)
 {
     return which == 0 ? f->a * f->cin[level] : which == 2 ? f->a * f->a * 9 : f->a;
 }
 
-void fpn_free(rn_ctx *ctx, void **p)
-{
-    if (*p) rn_free(ctx, *p);
-    *p = NULL;
-}
-
 void fpn_free_scratch(rn_fpn *f)
 {
     for (int i = 0; i < f->n; ++i) {
-        fpn_free(f->ctx, &f->inner[i]), fpn_free(f->ctx, (void **)&f->outb[i]);
+        rn_free_null(f->ctx, &f->inner[i]), rn_free_null(f->ctx, (void **)&f->outb[i]);
         f->cap_pix[i] = 0;
     }
-    fpn_free(f->ctx, (void **)&f->poolb);
+    rn_free_null(f->ctx, (void **)&f->poolb);
     f->cap_pool = 0;
 }
 
@@ -174,7 +160,7 @@ int rn_upsample_nearest_add_forward_dt(rn_ctx *ctx, int dtype, const void *top_n
     RN_REQUIRE(ctx, top_nhwc, "top_nhwc is NULL");
     RN_REQUIRE(ctx, dst_nhwc, "dst_nhwc is NULL");
     RN_REQUIRE(ctx, h >= 1 && w >= 1 && H >= 1 && W >= 1, "h, w, H, W must be >= 1");
-    const uint64_t es = dtype == RN_DTYPE_BF16 ? 2 : 4, per = 16 / es;  // elements of a 16-byte chunk
+    const uint64_t es = rn_elem_size(dtype), per = 16 / es;  // elements of a 16-byte chunk
     RN_REQUIRE(ctx, C >= 1 && C < (1ull << 31) && C % per == 0, "C must be a multiple of 16 bytes (and below 2^31)");
     RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(top_nhwc) & 15) == 0, "top_nhwc is off a 16-byte boundary");
     RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(lat_nhwc) & 15) == 0, "lat_nhwc is off a 16-byte boundary");
@@ -185,8 +171,8 @@ int rn_upsample_nearest_add_forward_dt(rn_ctx *ctx, int dtype, const void *top_n
                "B * h * w and B * H * W must be below 2^31");
     if (B == 0) return RN_OK;
     const uint64_t top_bytes = B * h * w * C * es, dst_bytes = B * H * W * C * es;
-    RN_REQUIRE(ctx, !fpn_overlap(dst_nhwc, dst_bytes, top_nhwc, top_bytes), "dst_nhwc overlaps top_nhwc");
-    RN_REQUIRE(ctx, !lat_nhwc || lat_nhwc == dst_nhwc || !fpn_overlap(dst_nhwc, dst_bytes, lat_nhwc, dst_bytes),
+    RN_REQUIRE(ctx, !rn_overlap(dst_nhwc, dst_bytes, top_nhwc, top_bytes), "dst_nhwc overlaps top_nhwc");
+    RN_REQUIRE(ctx, !lat_nhwc || lat_nhwc == dst_nhwc || !rn_overlap(dst_nhwc, dst_bytes, lat_nhwc, dst_bytes),
                "dst_nhwc overlaps lat_nhwc partly (it may be lat_nhwc itself)");
     nearest_args p;
     p.top = (const uint4 *)top_nhwc, p.lat = (const uint4 *)lat_nhwc, p.dst = (uint4 *)dst_nhwc;
@@ -278,7 +264,7 @@ int rn_fpn_finalize(rn_fpn *f)
                 snprintf(key, sizeof(key), names[t], i);
                 return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn_finalize: %s is not set", key);
             }
-    const uint64_t es = fpn_elem(f);
+    const uint64_t es = rn_elem_size(f->dtype);
     for (int i = 0; i < f->n; ++i) {
         RN_TRY(rn_malloc(ctx, &f->packed_inner[i], rn_conv2d_packed_weight_numel_dt(f->dtype, f->cin[i], f->a, 1) * es));
         RN_TRY(rn_malloc(ctx, &f->packed_layer[i], rn_conv2d_packed_weight_numel_dt(f->dtype, f->a, f->a, 3) * es));
@@ -286,7 +272,7 @@ int rn_fpn_finalize(rn_fpn *f)
         RN_TRY(rn_conv2d_pack_weight_dt(ctx, f->dtype, f->raw[i][2], f->packed_layer[i], f->a, f->a, 3));
     }
     RN_TRY(rn_sync(ctx));
-    for (int i = 0; i < f->n; ++i) fpn_free(ctx, (void **)&f->raw[i][0]), fpn_free(ctx, (void **)&f->raw[i][2]);
+    for (int i = 0; i < f->n; ++i) rn_free_null(ctx, (void **)&f->raw[i][0]), rn_free_null(ctx, (void **)&f->raw[i][2]);
     f->finalized = 1;
     return RN_OK;
 }
@@ -299,8 +285,8 @@ int rn_fpn_destroy(rn_fpn *f)
     RN_TRY(rn_sync(ctx));
     fpn_free_scratch(f);
     for (int i = 0; i < f->n; ++i) {
-        for (int t = 0; t < 4; ++t) fpn_free(ctx, (void **)&f->raw[i][t]);
-        fpn_free(ctx, &f->packed_inner[i]), fpn_free(ctx, &f->packed_layer[i]);
+        for (int t = 0; t < 4; ++t) rn_free_null(ctx, (void **)&f->raw[i][t]);
+        rn_free_null(ctx, &f->packed_inner[i]), rn_free_null(ctx, &f->packed_layer[i]);
     }
     free(f);
     return RN_OK;
@@ -357,7 +343,7 @@ int rn_fpn_reserve(rn_fpn *f, uint64_t images, const uint64_t *h, const uint64_t
     for (int i = 0; i < f->n; ++i) pix[i] = images * h[i] * w[i] > f->cap_pix[i] ? images * h[i] * w[i] : f->cap_pix[i];
     fpn_free_scratch(f);
     for (int i = 0; i < f->n; ++i) {
-        RN_TRY(rn_malloc(ctx, &f->inner[i], pix[i] * f->a * fpn_elem(f)));
+        RN_TRY(rn_malloc(ctx, &f->inner[i], pix[i] * f->a * rn_elem_size(f->dtype)));
         RN_TRY(rn_malloc(ctx, (void **)&f->outb[i], pix[i] * f->a * sizeof(float)));
         f->cap_pix[i] = pix[i];
     }
@@ -369,7 +355,7 @@ int rn_fpn_reserve(rn_fpn *f, uint64_t images, const uint64_t *h, const uint64_t
 void rn_fpn_cost(const rn_fpn *f, int kind, int level, uint64_t B, const uint64_t *h, const uint64_t *w, double *flops,
                  double *bytes)
 {
-    const double es = (double)fpn_elem(f), a = (double)f->a;
+    const double es = (double)rn_elem_size(f->dtype), a = (double)f->a;
     const int l = level < f->n ? level : f->n - 1;
     const double P = (double)(B * h[l] * w[l]), cin = (double)f->cin[l];
     const double Pp = (double)(B * ((h[l] - 1) / 2 + 1) * ((w[l] - 1) / 2 + 1));
@@ -391,7 +377,7 @@ int rn_fpn_step(rn_fpn *f, rn_ctx *ctx, int kind, int level, const void *x_nhwc,
                 const uint64_t *h, const uint64_t *w, float *dst_nchw)
 {
     const int dt = f->dtype, last = f->n - 1;
-    const uint64_t es = fpn_elem(f), a = f->a;
+    const uint64_t es = rn_elem_size(f->dtype), a = f->a;
     const uint64_t hp = (h[last] - 1) / 2 + 1, wp = (w[last] - 1) / 2 + 1;
     for (int i = 0; i < f->n; ++i)
         if ((img0 + B) * h[i] * w[i] > f->cap_pix[i]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn: scratch not reserved");

@@ -128,6 +128,23 @@ int rn_defer_linear(rn_ctx *ctx, const float *inp, float *out, const float *w, c
 
 static inline uint64_t rn_ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 
+// bytes of an element of a storage type (RN_DTYPE_*)
+static inline uint64_t rn_elem_size(int dtype) { return dtype == RN_DTYPE_BF16 ? 2 : 4; }
+
+// whether the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte
+static inline bool rn_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
+{
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + b_bytes && y < x + a_bytes;
+}
+
+// rn_free of *p unless it is NULL, which it is afterwards
+static inline void rn_free_null(rn_ctx *ctx, void **p)
+{
+    if (*p) rn_free(ctx, *p);
+    *p = NULL;
+}
+
 // grid for a grid-stride bandwidth kernel: enough blocks to fill 256 CUs x 8, no more
 static inline unsigned rn_stream_grid(uint64_t work_items, unsigned block)
 {

@@ -662,7 +662,7 @@ int rn_nhwc_to_nchw_dt(rn_ctx *ctx, int dtype, const void *src_nhwc, float *dst_
     RN_REQUIRE(ctx, dtype == RN_DTYPE_F32 || dtype == RN_DTYPE_BF16, "unknown dtype");
     RN_REQUIRE(ctx, H < (1ull << 31) && W < (1ull << 31) && H * W < (1ull << 31) && C < (1ull << 31),
                "dimension too large");
-    const uint64_t HW = H * W, es = dtype == RN_DTYPE_BF16 ? 2 : 4;
+    const uint64_t HW = H * W, es = rn_elem_size(dtype);
     if (B * C * HW == 0) return RN_OK;
     const uintptr_t sa = reinterpret_cast<uintptr_t>(src_nhwc), da = reinterpret_cast<uintptr_t>(dst_nchw);
     RN_REQUIRE(ctx, src_nhwc && dst_nchw && src_nhwc != (const void *)dst_nchw, "null or aliased tensor");

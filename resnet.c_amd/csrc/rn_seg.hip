@@ -1,8 +1,8 @@
 // Semantic segmentation: the bilinear upsample of per-pixel class scores with an optional fused argmax
 // (rn_upsample_bilinear_forward), the channel concat with a per-image broadcast source
-// (rn_concat_channels_forward_dt), and torchvision's FCNHead and DeepLabHead as the two kinds of one object over the
-// library's own convolutions (rn_seg_head_*).  The reference classifies whole images only; nothing here has a
-// counterpart in it.
+// (rn_concat_channels_forward_dt), and torchvision's FCNHead and DeepLabHead as one object (rn_seg_head_*): a table
+// of convolution units and a list of launches over the library's own convolutions, which the two create functions
+// fill differently.  The reference classifies whole images only; nothing here has a counterpart in it.
 #include <stdlib.h>
 #include <string.h>
 
@@ -250,87 +250,150 @@ __global__ __launch_bounds__(256) void concat_channels_kernel(const concat_args 
     }
 }
 
-bool seg_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
-{
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + b_bytes && y < x + a_bytes;
-}
-
 }  // namespace
 
-struct rn_seg_head {
-    rn_ctx *ctx;
-    uint64_t cin, mid, classes;
-    // what the two convolutions run with: mid rounded up to a multiple of 64 (the bf16 contraction's K granule; the
-    // added channels have zero weights, scale 0 and shift 0, so they hold ReLU(0) = 0 and meet zero columns of the
-    // 1x1 panel: exact zeros added to every sum) and classes rounded up to a multiple of 4 (16-byte coarse pixels)
-    uint64_t midp, cpad;
-    int dtype, finalized;
-    float *raw[7];     // the state dict's tensors on the device, fp32, padded to midp / cpad
-    int is_set[7];
-    void *packed1, *packed2;
-    float *scale, *shift;
-    void *mid_t;       // [cap, h, w, mid] of the storage type
-    float *coarse;     // [cap, h, w, cpad] fp32
-    uint64_t cap_pix;  // pixels (images x h x w) the two scratch tensors hold
-    struct seg_deeplab *dl;  // NULL: the FCN kind, everything above; else the DeepLab kind, which uses of the above
-                             // ctx, cin, classes, cpad, dtype, finalized, coarse and cap_pix
-};
+// ---- the head's tables --------------------------------------------------------------------------------------
+// A head is a table of convolution "units", the state dict's tensors they are made of, a list of scratch tensors
+// and the list of a forward's launches.  Its create function fills the four; nothing else knows a kind of head.
+//   FCNHead(in, classes): Conv3x3(in, mid) + BN + ReLU, Conv1x1(mid, classes).  2 units, 3 launches.
+//   DeepLabHead(in, classes) = ASPP(in, rates, a) + Conv3x3(a, a) + BN + ReLU + Conv1x1(a, classes).  n + 5 units
+//   (the 1x1 branch, the n dilated 3x3 branches, the pooled branch's 1x1, the projection, the 3x3, the
+//   classifier), n + 8 launches.
+constexpr int kSegMaxRates = 4, kSegMaxUnits = kSegMaxRates + 5, kSegMaxTensors = 5 * (kSegMaxUnits - 1) + 2;
+constexpr int kSegMaxBufs = kSegMaxRates + 5, kSegMaxSteps = kSegMaxRates + 8;
 
-// The DeepLab kind: torchvision's DeepLabHead(in, classes) = ASPP(in, rates, a) + Conv3x3(a, a) + BN + ReLU +
-// Conv1x1(a, classes).  n + 4 convolutions with a batch-norm ("units": 0 the 1x1 branch, 1..n the dilated 3x3
-// branches, n + 1 the pooled branch's 1x1, n + 2 the projection, n + 3 the 3x3) and the classifier.
-constexpr int kDlMaxRates = 4, kDlMaxUnits = kDlMaxRates + 4, kDlMaxTensors = 5 * kDlMaxUnits + 2;
-
+// a tensor of the state dict, `rows` rows of `len` values, and its fp32 copy on the device, `prows` rows of `pitch`:
+// padded on the host, every added element `fill`
 struct seg_tensor {
     char key[64];
-    uint64_t numel, padded;  // elements of the state dict's tensor, and of its device copy (classifier rows: cpad)
+    uint64_t rows, len, prows, pitch;
+    float fill;
     float *raw;
     int is_set;
 };
 
+// A k x k convolution of cin -> cout channels, both as they run (padded).  bn: a batch-norm folded into scale and
+// shift and a ReLU follow, the output is of the storage type; tensors first .. first + 4 are the weight and the
+// batch-norm's weight, bias, running_mean and running_var.  Otherwise (the classifier) it carries a bias, which is
+// its shift, has no ReLU and an fp32 output; tensors first and first + 1.
 struct seg_unit {
-    uint64_t cin, k, dilation;
+    uint64_t cin, cout, k;
+    uint64_t dilation;  // 0: a plain convolution, padding k / 2; else a dilated 3x3 branch of ASPP, padding = dilation
+    int bn, first;
     void *packed;
-    void *center;       // dilated branches: the centre tap weight[:, :, 1, 1] packed as a 1x1 panel
-    float *raw_center;  // its fp32 [a, cin] source until finalize
     float *scale, *shift;
+    void *center;       // dilated branches: the centre tap weight[:, :, 1, 1] packed as a 1x1 panel
+    float *raw_center;  // its fp32 [cout, cin] source until finalize
 };
 
-struct seg_deeplab {
-    uint64_t a, n, rates[kDlMaxRates];
+struct seg_buf {  // a scratch tensor: [cap_img, channels] or [cap_pix, channels], fp32 or of the storage type
+    int per_image, f32;
+    uint64_t channels;
+    void *ptr;
+};
+
+// A launch of a forward.  src, dst: scratch tensors; src -1 is the input map.  SEG_CONV: unit u (on a per-image src:
+// B "pixels").  SEG_POOL: the global average of src.  SEG_CONCAT: scratch tensors 0 .. u - 1 side by side, then the
+// per-image src at every pixel of its image.  SEG_UPSAMPLE: src to the caller's scores and labels.
+enum { SEG_CONV, SEG_POOL, SEG_CONCAT, SEG_UPSAMPLE };
+
+struct seg_step {
+    int kind, u, src, dst;
+    const char *name;  // of its profile record
+};
+
+struct rn_seg_head {
+    rn_ctx *ctx;
+    uint64_t cin, classes;
+    uint64_t midp, cpad;  // the classifier's channels as it runs (seg_add_unit)
+    int dtype, finalized;
     int center_tap;  // rn_seg_head_set_center_tap
-    int n_units, n_tensors;
-    seg_unit unit[kDlMaxUnits];
-    seg_tensor tensor[kDlMaxTensors];  // unit u: 5u + {weight, bn weight, bn bias, running_mean, running_var}; then
-                                       // the classifier's weight and bias
-    void *packed_cls;
-    // scratch: per coarse pixel the n + 1 branch tensors [cap_pix, a] each, the concat [cap_pix, (n + 2) a]; per image
-    // the pooled map [cap_img, cin] and the pooled branch [cap_img, a].  The projected tensor and the 3x3's output
-    // live in branch 0's and branch 1's tensors, which are dead behind the concat.
-    void *branch[kDlMaxRates + 1], *cat, *pool_in, *pool_out;
-    uint64_t cap_img;
+    int n_units, n_tensors, n_bufs, n_steps;
+    seg_unit unit[kSegMaxUnits];
+    seg_tensor tensor[kSegMaxTensors];
+    seg_buf buf[kSegMaxBufs];
+    seg_step step[kSegMaxSteps];
+    uint64_t cap_pix, cap_img;  // coarse pixels (images x h x w) and images the scratch tensors hold
 };
 
 namespace {
 
-const char *const kSegKeys[7] = {"classifier.0.weight",       "classifier.1.weight",      "classifier.1.bias",
-                                 "classifier.1.running_mean", "classifier.1.running_var", "classifier.4.weight",
-                                 "classifier.4.bias"};
-
-uint64_t seg_key_numel(const rn_seg_head *hd, int i)
+void seg_add_tensor(rn_seg_head *hd, const char *module, const char *name, uint64_t rows, uint64_t len, uint64_t prows,
+                    uint64_t pitch, float fill)
 {
-    if (i == 0) return hd->mid * hd->cin * 9;
-    if (i <= 4) return hd->mid;
-    return i == 5 ? hd->classes * hd->mid : hd->classes;
+    seg_tensor *t = &hd->tensor[hd->n_tensors++];
+    snprintf(t->key, sizeof(t->key), "%s.%s", module, name);
+    t->rows = rows, t->len = len, t->prows = prows, t->pitch = pitch, t->fill = fill;
 }
 
-uint64_t seg_elem(const rn_seg_head *hd) { return hd->dtype == RN_DTYPE_BF16 ? 2 : 4; }
+// The unit `conv` (+ batch-norm `norm`, or NULL: + bias) of the state dict: cin -> cout channels there.  It runs
+// with cin rounded up to a multiple of 64 (the bf16 contraction's K granule; only a 1x1 is ever given such a cin)
+// and cout to one of 64 with a batch-norm (the next unit's cin) or of 4 without (16-byte coarse pixels).  The
+// added rows and columns of the weight are zero, and so is the bias; an added channel of the batch-norm has
+// variance 1 and zeros otherwise (scale = 0 / sqrt(1 + eps) = 0, shift = 0), so it holds ReLU(0) = 0 and meets
+// zero columns of the next panel: exact zeros added to every sum.  Returns the unit's index.
+int seg_add_unit(rn_seg_head *hd, const char *conv, const char *norm, uint64_t cin, uint64_t cout, uint64_t k,
+                 uint64_t dilation)
+{
+    static const char *const bn[4] = {"weight", "bias", "running_mean", "running_var"};
+    seg_unit *un = &hd->unit[hd->n_units];
+    un->cin = (cin + 63) / 64 * 64, un->cout = norm ? (cout + 63) / 64 * 64 : (cout + 3) / 4 * 4;
+    un->k = k, un->dilation = dilation, un->bn = norm != NULL, un->first = hd->n_tensors;
+    seg_add_tensor(hd, conv, "weight", cout, cin * k * k, un->cout, un->cin * k * k, 0.0f);
+    if (!norm) seg_add_tensor(hd, conv, "bias", 1, cout, 1, un->cout, 0.0f);
+    for (int j = 0; norm && j < 4; ++j) seg_add_tensor(hd, norm, bn[j], 1, cout, 1, un->cout, j == 3 ? 1.0f : 0.0f);
+    return hd->n_units++;
+}
 
-// ---- the DeepLab kind ----
-const char *const kDlBranchOps[kDlMaxRates + 1] = {"aspp_conv0", "aspp_conv1", "aspp_conv2", "aspp_conv3", "aspp_conv4"};
+int seg_add_buf(rn_seg_head *hd, int per_image, uint64_t channels, int f32)
+{
+    seg_buf *b = &hd->buf[hd->n_bufs];
+    b->per_image = per_image, b->channels = channels, b->f32 = f32;
+    return hd->n_bufs++;
+}
 
-// Whether dilated branch u of a forward on an h x w map runs as the 1x1 contraction on its centre tap.  With
+void seg_add_step(rn_seg_head *hd, int kind, int u, int src, int dst, const char *name)
+{
+    seg_step *s = &hd->step[hd->n_steps++];
+    s->kind = kind, s->u = u, s->src = src, s->dst = dst, s->name = name;
+}
+
+int seg_new(rn_ctx *ctx, rn_seg_head **out, uint64_t in_channels, uint64_t classes, const char *who)
+{
+    rn_seg_head *hd = (rn_seg_head *)calloc(1, sizeof(*hd));
+    if (!hd) return rn_set_error(ctx, RN_ERR_NOMEM, "%s: out of host memory", who);
+    hd->ctx = ctx, hd->cin = in_channels, hd->classes = classes, hd->dtype = RN_DTYPE_F32, hd->center_tap = 1;
+    *out = hd;
+    return RN_OK;
+}
+
+// what every head ends with: the classifier on scratch tensor `from` (mid channels in the state dict), the upsample
+void seg_add_classifier(rn_seg_head *hd, int from, uint64_t mid)
+{
+    const int u = seg_add_unit(hd, "classifier.4", NULL, mid, hd->classes, 1, 0);
+    hd->midp = hd->unit[u].cin, hd->cpad = hd->unit[u].cout;
+    const int coarse = seg_add_buf(hd, 0, hd->cpad, 1);
+    seg_add_step(hd, SEG_CONV, u, from, coarse, "seg_conv2");
+    seg_add_step(hd, SEG_UPSAMPLE, 0, coarse, -1, "seg_upsample");
+}
+
+// `rows` rows of `len` values, `stride` apart in src, to the device as prows rows of pitch (*dev: allocated at the
+// first call); every element added is `fill`
+int seg_upload(rn_ctx *ctx, float **dev, const float *src, uint64_t rows, uint64_t len, uint64_t stride, uint64_t prows,
+               uint64_t pitch, float fill)
+{
+    const uint64_t n = prows * pitch;
+    float *padded = (float *)malloc(n * sizeof(float));
+    if (!padded) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_seg_head_set_tensor: out of host memory");
+    for (uint64_t i = 0; i < n; ++i) padded[i] = fill;
+    for (uint64_t r = 0; r < rows; ++r) memcpy(padded + r * pitch, src + r * stride, len * sizeof(float));
+    int st = *dev ? RN_OK : rn_malloc(ctx, (void **)dev, n * sizeof(float));
+    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, *dev, padded, n * sizeof(float));
+    free(padded);
+    return st;
+}
+
+// Whether dilated branch `un` of a forward on an h x w map runs as the 1x1 contraction on its centre tap.  With
 // rate >= h and rate >= w every other tap of every output pixel lies outside the image, so the 3x3 sums the centre
 // tap's products in channel order among zeros, and so does the 1x1 -- the same bits as long as both routes round
 // that sum at the same places.  bf16 tensors: every candidate of both adds one K tile after the other into one
@@ -341,148 +404,33 @@ const char *const kDlBranchOps[kDlMaxRates + 1] = {"aspp_conv0", "aspp_conv1", "
 // 1x1's four tiles not at all; in = 2048: tiles 256..319 of 576 fold once, at 288, the 1x1's 64 tiles at every
 // eighth): the same products, added in another association.  Only in = 64 (18 and 2 tiles, neither chunked) keeps
 // the bits in fp32, and only there does an fp32 head take the plan ("DeepLabV3 head").
-bool dl_center_route(const rn_seg_head *hd, int u, uint64_t h, uint64_t w)
+bool dl_center_route(const rn_seg_head *hd, const seg_unit *un, uint64_t h, uint64_t w)
 {
-    const seg_deeplab *dl = hd->dl;
-    if (!dl->center_tap || u < 1 || (uint64_t)u > dl->n) return false;
-    if (dl->unit[u].dilation < h || dl->unit[u].dilation < w) return false;
+    if (!hd->center_tap || !un->dilation) return false;
+    if (un->dilation < h || un->dilation < w) return false;
     return hd->dtype == RN_DTYPE_BF16 || 9 * hd->cin / 32 < 32;
 }
 
-void dl_free(rn_ctx *ctx, void **p)
+// whether every scratch tensor holds `pix` coarse pixels or `images` images, whichever it is made of
+bool seg_fits(const rn_seg_head *hd, uint64_t pix, uint64_t images)
 {
-    if (*p) rn_free(ctx, *p);
-    *p = NULL;
+    for (int i = 0; i < hd->n_bufs; ++i)
+        if (hd->buf[i].per_image ? images > hd->cap_img : pix > hd->cap_pix) return false;
+    return true;
 }
 
-void dl_free_scratch(rn_seg_head *hd)
+void seg_free_scratch(rn_seg_head *hd)
 {
-    seg_deeplab *dl = hd->dl;
-    for (uint64_t i = 0; i <= dl->n; ++i) dl_free(hd->ctx, &dl->branch[i]);
-    dl_free(hd->ctx, &dl->cat), dl_free(hd->ctx, &dl->pool_in), dl_free(hd->ctx, &dl->pool_out);
-    dl_free(hd->ctx, (void **)&hd->coarse);
-    hd->cap_pix = dl->cap_img = 0;
+    for (int i = 0; i < hd->n_bufs; ++i) rn_free_null(hd->ctx, &hd->buf[i].ptr);
+    hd->cap_pix = hd->cap_img = 0;
 }
 
-int dl_set_tensor(rn_seg_head *hd, const char *key, const float *host_data, uint64_t numel)
+// where the B images of a launch whose scratch starts img0 images (pix0 coarse pixels) in begin in scratch tensor i
+void *seg_at(const rn_seg_head *hd, int i, uint64_t img0, uint64_t pix0)
 {
-    rn_ctx *ctx = hd->ctx;
-    seg_deeplab *dl = hd->dl;
-    int i = 0;
-    while (i < dl->n_tensors && strcmp(key, dl->tensor[i].key) != 0) ++i;
-    if (i == dl->n_tensors) return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head_set_tensor: unknown key '%s'", key);
-    seg_tensor *t = &dl->tensor[i];
-    if (numel != t->numel)
-        return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head_set_tensor: %s has %llu elements, not %llu", key,
-                            (unsigned long long)t->numel, (unsigned long long)numel);
-    // only the classifier is padded (classes -> cpad rows of zeros: its weight and its bias)
-    float *padded = (float *)calloc(t->padded, sizeof(float));
-    if (!padded) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_seg_head_set_tensor: out of host memory");
-    memcpy(padded, host_data, numel * sizeof(float));
-    int st = t->raw ? RN_OK : rn_malloc(ctx, (void **)&t->raw, t->padded * sizeof(float));
-    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, t->raw, padded, t->padded * sizeof(float));
-    free(padded);
-    RN_TRY(st);
-    const int u = i / 5;
-    if (i % 5 == 0 && u >= 1 && (uint64_t)u <= dl->n) {  // a dilated branch's weight [a, in, 3, 3]: its centre tap too
-        seg_unit *un = &dl->unit[u];
-        const uint64_t rows = dl->a * un->cin;
-        float *center = (float *)malloc(rows * sizeof(float));
-        if (!center) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_seg_head_set_tensor: out of host memory");
-        for (uint64_t r = 0; r < rows; ++r) center[r] = host_data[r * 9 + 4];
-        st = un->raw_center ? RN_OK : rn_malloc(ctx, (void **)&un->raw_center, rows * sizeof(float));
-        if (st == RN_OK) st = rn_ctx_upload_sync(ctx, un->raw_center, center, rows * sizeof(float));
-        free(center);
-        RN_TRY(st);
-    }
-    t->is_set = 1;
-    return RN_OK;
-}
-
-int dl_finalize(rn_seg_head *hd)
-{
-    rn_ctx *ctx = hd->ctx;
-    seg_deeplab *dl = hd->dl;
-    for (int i = 0; i < dl->n_tensors; ++i)
-        if (!dl->tensor[i].is_set)
-            return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head_finalize: %s is not set", dl->tensor[i].key);
-    const uint64_t es = seg_elem(hd);
-    for (int u = 0; u < dl->n_units; ++u) {
-        seg_unit *un = &dl->unit[u];
-        seg_tensor *t = &dl->tensor[5 * u];
-        RN_TRY(rn_malloc(ctx, (void **)&un->scale, dl->a * sizeof(float)));
-        RN_TRY(rn_malloc(ctx, (void **)&un->shift, dl->a * sizeof(float)));
-        RN_TRY(rn_malloc(ctx, &un->packed, rn_conv2d_packed_weight_numel_dt(hd->dtype, un->cin, dl->a, un->k) * es));
-        RN_TRY(rn_batchnorm2d_fold(ctx, t[1].raw, t[2].raw, t[3].raw, t[4].raw, un->scale, un->shift, dl->a));
-        RN_TRY(rn_conv2d_pack_weight_dt(ctx, hd->dtype, t[0].raw, un->packed, un->cin, dl->a, un->k));
-        if (un->raw_center) {
-            RN_TRY(rn_malloc(ctx, &un->center, rn_conv2d_packed_weight_numel_dt(hd->dtype, un->cin, dl->a, 1) * es));
-            RN_TRY(rn_conv2d_pack_weight_dt(ctx, hd->dtype, un->raw_center, un->center, un->cin, dl->a, 1));
-        }
-    }
-    seg_tensor *cls = &dl->tensor[5 * dl->n_units];
-    RN_TRY(rn_malloc(ctx, &dl->packed_cls, rn_conv2d_packed_weight_numel_dt(hd->dtype, dl->a, hd->cpad, 1) * es));
-    RN_TRY(rn_conv2d_pack_weight_dt(ctx, hd->dtype, cls->raw, dl->packed_cls, dl->a, hd->cpad, 1));
-    RN_TRY(rn_sync(ctx));
-    for (int i = 0; i < dl->n_tensors - 1; ++i) dl_free(ctx, (void **)&dl->tensor[i].raw);  // the bias stays: a shift
-    for (int u = 0; u < dl->n_units; ++u) dl_free(ctx, (void **)&dl->unit[u].raw_center);
-    hd->finalized = 1;
-    return RN_OK;
-}
-
-// launch `step` of a DeepLab forward (the order of rn_hip.h): B images whose scratch starts img0 images into the
-// head's tensors
-int dl_step(rn_seg_head *hd, rn_ctx *ctx, int step, const void *x, uint64_t img0, uint64_t B, uint64_t h, uint64_t w,
-            uint64_t H, uint64_t W, float *scores_nchw, uint8_t *labels)
-{
-    seg_deeplab *dl = hd->dl;
-    const uint64_t es = seg_elem(hd), n = dl->n, a = dl->a, pix0 = img0 * h * w;
-    const int dt = hd->dtype;
-    void *br[kDlMaxRates + 1];
-    for (uint64_t i = 0; i <= n; ++i) br[i] = (char *)dl->branch[i] + pix0 * a * es;
-    void *cat = (char *)dl->cat + pix0 * (n + 2) * a * es;
-    void *pool_in = (char *)dl->pool_in + img0 * hd->cin * es, *pool_out = (char *)dl->pool_out + img0 * a * es;
-    void *proj = br[0], *mid = br[1];
-    float *coarse = hd->coarse + pix0 * hd->cpad;
-    rn_epilogue ep;
-    ep.residual = NULL;
-    if (pix0 + B * h * w > hd->cap_pix || img0 + B > dl->cap_img)
-        return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head: scratch not reserved");
-    const uint64_t s = (uint64_t)step;
-    if (s <= n) {  // the branches
-        const seg_unit *un = &dl->unit[s];
-        ep.scale = un->scale, ep.shift = un->shift, ep.relu = 1;
-        if (s == 0 || dl_center_route(hd, (int)s, h, w))
-            return rn_conv2d_nhwc_forward_dt(ctx, dt, dt, x, br[s], s == 0 ? un->packed : un->center, 1, 1, 0, h, w, B,
-                                             hd->cin, a, h, w, &ep);
-        return rn_conv2d_dilated_nhwc_forward_dt(ctx, dt, dt, x, br[s], un->packed, 3, 1, un->dilation, un->dilation, h,
-                                                 w, B, hd->cin, a, h, w, 1, &ep);
-    }
-    if (s == n + 1) return rn_global_avgpool_nhwc_forward_dt(ctx, dt, x, pool_in, B, hd->cin, h, w);
-    if (s == n + 2) {  // the pooled branch: B "pixels"
-        const seg_unit *un = &dl->unit[n + 1];
-        ep.scale = un->scale, ep.shift = un->shift, ep.relu = 1;
-        return rn_conv2d_nhwc_forward_dt(ctx, dt, dt, pool_in, pool_out, un->packed, 1, 1, 0, 1, 1, B, hd->cin, a, 1, 1,
-                                         &ep);
-    }
-    if (s == n + 3) {
-        uint64_t ch[kDlMaxRates + 1];
-        for (uint64_t i = 0; i <= n; ++i) ch[i] = a;
-        return rn_concat_channels_forward_dt(ctx, dt, n + 1, br, ch, pool_out, a, cat, B, h * w);
-    }
-    if (s == n + 4 || s == n + 5) {
-        const seg_unit *un = &dl->unit[s - 2];
-        const uint64_t k = un->k;
-        ep.scale = un->scale, ep.shift = un->shift, ep.relu = 1;
-        return rn_conv2d_nhwc_forward_dt(ctx, dt, dt, s == n + 4 ? cat : proj, s == n + 4 ? proj : mid, un->packed, k, 1,
-                                         k / 2, h, w, B, un->cin, a, h, w, &ep);
-    }
-    if (s == n + 6) {
-        ep.scale = NULL, ep.shift = dl->tensor[dl->n_tensors - 1].raw, ep.relu = 0;
-        return rn_conv2d_nhwc_forward_dt(ctx, dt, RN_DTYPE_F32, mid, coarse, dl->packed_cls, 1, 1, 0, h, w, B, a, hd->cpad,
-                                         h, w, &ep);
-    }
-    return rn_upsample_bilinear_forward(ctx, coarse, B, h, w, hd->classes, hd->cpad, H, W, scores_nchw, labels);
+    const seg_buf *b = &hd->buf[i];
+    const uint64_t es = b->f32 ? 4 : rn_elem_size(hd->dtype);
+    return (char *)b->ptr + (b->per_image ? img0 : pix0) * b->channels * es;
 }
 
 }  // namespace
@@ -543,7 +491,7 @@ int rn_concat_channels_forward_dt(rn_ctx *ctx, int dtype, uint64_t n_src, const 
     RN_REQUIRE(ctx, (per_image != NULL) == (per_image_channels != 0),
                "per_image and per_image_channels: a pointer with channels, or NULL with 0");
     RN_REQUIRE(ctx, B < (1ull << 31) && pixels < (1ull << 31) && B * pixels < (1ull << 31), "B * pixels must be below 2^31");
-    const uint64_t es = dtype == RN_DTYPE_BF16 ? 2 : 4, per = 16 / es;  // elements of a 16-byte chunk
+    const uint64_t es = rn_elem_size(dtype), per = 16 / es;  // elements of a 16-byte chunk
     concat_args p{};
     uint64_t total = 0;
     for (uint64_t i = 0; i < n_src; ++i) {
@@ -564,8 +512,8 @@ int rn_concat_channels_forward_dt(rn_ctx *ctx, int dtype, uint64_t n_src, const 
     if (B == 0 || pixels == 0) return RN_OK;
     const uint64_t npix = B * pixels, dst_bytes = npix * total * es;
     for (uint64_t i = 0; i < n_src; ++i)
-        RN_REQUIRE(ctx, !seg_overlap(dst, dst_bytes, srcs[i], npix * channels[i] * es), "dst overlaps a source");
-    RN_REQUIRE(ctx, !per_image || !seg_overlap(dst, dst_bytes, per_image, B * per_image_channels * es),
+        RN_REQUIRE(ctx, !rn_overlap(dst, dst_bytes, srcs[i], npix * channels[i] * es), "dst overlaps a source");
+    RN_REQUIRE(ctx, !per_image || !rn_overlap(dst, dst_bytes, per_image, B * per_image_channels * es),
                "dst overlaps per_image");
     for (uint64_t i = n_src; i < 8; ++i) p.end[i] = p.end[n_src - 1];
     p.per_image = (const uint4 *)per_image, p.dst = (uint4 *)dst;
@@ -590,20 +538,20 @@ int rn_seg_head_create(rn_ctx *ctx, rn_seg_head **out, uint64_t in_channels, uin
                "in_channels must be a multiple of 64 (at most 8192)");
     RN_REQUIRE(ctx, mid_channels >= 1 && mid_channels <= 8192, "mid_channels must be 1..8192");
     RN_REQUIRE(ctx, classes >= 1 && classes <= 256, "classes must be 1..256");
-    rn_seg_head *hd = (rn_seg_head *)calloc(1, sizeof(*hd));
-    if (!hd) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_seg_head_create: out of host memory");
-    hd->ctx = ctx;
-    hd->cin = in_channels, hd->mid = mid_channels, hd->classes = classes;
-    hd->midp = (mid_channels + 63) / 64 * 64, hd->cpad = (classes + 3) / 4 * 4;
-    hd->dtype = RN_DTYPE_F32;
-    *out = hd;
+    RN_TRY(seg_new(ctx, out, in_channels, classes, __func__));
+    rn_seg_head *hd = *out;
+    const int u = seg_add_unit(hd, "classifier.0", "classifier.1", in_channels, mid_channels, 3, 0);
+    const int mid = seg_add_buf(hd, 0, hd->unit[u].cout, 0);
+    seg_add_step(hd, SEG_CONV, u, -1, mid, "seg_conv1");
+    seg_add_classifier(hd, mid, mid_channels);
     return RN_OK;
 }
 
 int rn_seg_head_create_deeplab(rn_ctx *ctx, rn_seg_head **out, uint64_t in_channels, uint64_t aspp_channels,
                                uint64_t classes, uint64_t n_rates, const uint64_t *rates)
 {
-    static const char *const bn[4] = {"weight", "bias", "running_mean", "running_var"};
+    static const char *const branch_ops[kSegMaxRates + 1] = {"aspp_conv0", "aspp_conv1", "aspp_conv2", "aspp_conv3",
+                                                             "aspp_conv4"};
     RN_ENTER(ctx);
     RN_REQUIRE(ctx, out, "out is NULL");
     *out = NULL;
@@ -612,61 +560,48 @@ int rn_seg_head_create_deeplab(rn_ctx *ctx, rn_seg_head **out, uint64_t in_chann
     RN_REQUIRE(ctx, aspp_channels >= 64 && aspp_channels % 64 == 0 && aspp_channels <= 1024,
                "aspp_channels must be a multiple of 64 (at most 1024)");
     RN_REQUIRE(ctx, classes >= 1 && classes <= 256, "classes must be 1..256");
-    RN_REQUIRE(ctx, n_rates >= 1 && n_rates <= (uint64_t)kDlMaxRates && rates, "n_rates must be 1..4 (and rates not NULL)");
+    RN_REQUIRE(ctx, n_rates >= 1 && n_rates <= (uint64_t)kSegMaxRates && rates, "n_rates must be 1..4 (and rates not NULL)");
     for (uint64_t i = 0; i < n_rates; ++i)
         RN_REQUIRE(ctx, rates[i] >= 1 && rates[i] <= RN_CONV_MAX_DILATION, "a rate must be 1..RN_CONV_MAX_DILATION");
-    rn_seg_head *hd = (rn_seg_head *)calloc(1, sizeof(*hd));
-    seg_deeplab *dl = (seg_deeplab *)calloc(1, sizeof(*dl));
-    if (!hd || !dl) {
-        free(hd), free(dl);
-        return rn_set_error(ctx, RN_ERR_NOMEM, "rn_seg_head_create_deeplab: out of host memory");
-    }
-    hd->ctx = ctx, hd->dl = dl;
-    hd->cin = in_channels, hd->classes = classes, hd->cpad = (classes + 3) / 4 * 4;
-    hd->mid = hd->midp = aspp_channels;
-    hd->dtype = RN_DTYPE_F32;
-    const uint64_t n = n_rates, a = aspp_channels;
-    dl->a = a, dl->n = n, dl->center_tap = 1;
-    dl->n_units = (int)n + 4, dl->n_tensors = 5 * dl->n_units + 2;
-    for (int u = 0; u < dl->n_units; ++u) {
-        seg_unit *un = &dl->unit[u];
-        seg_tensor *t = &dl->tensor[5 * u];
+    RN_TRY(seg_new(ctx, out, in_channels, classes, __func__));
+    rn_seg_head *hd = *out;
+    const int n = (int)n_rates;
+    const uint64_t a = aspp_channels;
+    // scratch: per coarse pixel the n + 1 branch tensors (0 .. n: what the concat reads) and the concat; per image
+    // the pooled map and the pooled branch.  The projected tensor and the 3x3's output live in branch 0's and branch
+    // 1's tensors, which are dead behind the concat.
+    for (int i = 0; i <= n; ++i) seg_add_buf(hd, 0, a, 0);
+    const int cat = seg_add_buf(hd, 0, (n_rates + 2) * a, 0);
+    const int pool_in = seg_add_buf(hd, 1, in_channels, 0), pool_out = seg_add_buf(hd, 1, a, 0);
+    for (int i = 0; i <= n; ++i) {  // convs.0 is the 1x1 branch, convs.1 .. n the dilated ones
         char conv[48], norm[48];
-        const uint64_t v = (uint64_t)u;
-        un->cin = v <= n + 1 ? in_channels : v == n + 2 ? (n + 2) * a : a;
-        un->k = (v >= 1 && v <= n) || v == n + 3 ? 3 : 1;
-        un->dilation = v >= 1 && v <= n ? rates[v - 1] : 1;
-        if (v >= 1 && v <= n) dl->rates[v - 1] = rates[v - 1];
-        // the pooled branch's Sequential starts with the pool: its convolution is .1, its batch-norm .2
-        if (v <= n + 1) {
-            snprintf(conv, sizeof(conv), "classifier.0.convs.%d.%d", u, v <= n ? 0 : 1);
-            snprintf(norm, sizeof(norm), "classifier.0.convs.%d.%d", u, v <= n ? 1 : 2);
-        } else {
-            snprintf(conv, sizeof(conv), "%s", v == n + 2 ? "classifier.0.project.0" : "classifier.1");
-            snprintf(norm, sizeof(norm), "%s", v == n + 2 ? "classifier.0.project.1" : "classifier.2");
-        }
-        snprintf(t[0].key, sizeof(t[0].key), "%s.weight", conv);
-        t[0].numel = t[0].padded = a * un->cin * un->k * un->k;
-        for (int j = 0; j < 4; ++j) {
-            snprintf(t[1 + j].key, sizeof(t[1 + j].key), "%s.%s", norm, bn[j]);
-            t[1 + j].numel = t[1 + j].padded = a;
-        }
+        snprintf(conv, sizeof(conv), "classifier.0.convs.%d.0", i);
+        snprintf(norm, sizeof(norm), "classifier.0.convs.%d.1", i);
+        const int u = seg_add_unit(hd, conv, norm, in_channels, a, i ? 3 : 1, i ? rates[i - 1] : 0);
+        seg_add_step(hd, SEG_CONV, u, -1, i, branch_ops[i]);
     }
-    seg_tensor *cls = &dl->tensor[5 * dl->n_units];
-    snprintf(cls[0].key, sizeof(cls[0].key), "classifier.4.weight");
-    snprintf(cls[1].key, sizeof(cls[1].key), "classifier.4.bias");
-    cls[0].numel = classes * a, cls[0].padded = hd->cpad * a;
-    cls[1].numel = classes, cls[1].padded = hd->cpad;
-    *out = hd;
+    // the pooled branch's Sequential starts with the pool: its convolution is .1, its batch-norm .2
+    char conv[48], norm[48];
+    snprintf(conv, sizeof(conv), "classifier.0.convs.%d.1", n + 1);
+    snprintf(norm, sizeof(norm), "classifier.0.convs.%d.2", n + 1);
+    seg_add_step(hd, SEG_POOL, 0, -1, pool_in, "aspp_pool");
+    seg_add_step(hd, SEG_CONV, seg_add_unit(hd, conv, norm, in_channels, a, 1, 0), pool_in, pool_out, "aspp_pool_conv");
+    seg_add_step(hd, SEG_CONCAT, n + 1, pool_out, cat, "aspp_concat");
+    const int project = seg_add_unit(hd, "classifier.0.project.0", "classifier.0.project.1", (n_rates + 2) * a, a, 1, 0);
+    seg_add_step(hd, SEG_CONV, project, cat, 0, "aspp_project");
+    seg_add_step(hd, SEG_CONV, seg_add_unit(hd, "classifier.1", "classifier.2", a, a, 3, 0), 0, 1, "seg_conv1");
+    seg_add_classifier(hd, 1, a);
     return RN_OK;
 }
 
 int rn_seg_head_set_center_tap(rn_seg_head *hd, int on)
 {
     if (!hd) return RN_ERR_INVALID;
-    RN_REQUIRE(hd->ctx, hd->dl, "not a DeepLab head");
+    int dilated = 0;
+    for (int u = 0; u < hd->n_units; ++u) dilated |= hd->unit[u].dilation != 0;
+    RN_REQUIRE(hd->ctx, dilated, "not a DeepLab head");
     RN_REQUIRE(hd->ctx, on == 0 || on == 1, "on must be 0 or 1");
-    hd->dl->center_tap = on;
+    hd->center_tap = on;
     return RN_OK;
 }
 
@@ -686,27 +621,20 @@ int rn_seg_head_set_tensor(rn_seg_head *hd, const char *key, const float *host_d
     RN_ENTER(ctx);
     RN_REQUIRE(ctx, key && host_data, "key or host_data is NULL");
     RN_REQUIRE(ctx, !hd->finalized, "the head is finalized");
-    if (hd->dl) return dl_set_tensor(hd, key, host_data, numel);
     int i = 0;
-    while (i < 7 && strcmp(key, kSegKeys[i]) != 0) ++i;
-    if (i == 7) return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head_set_tensor: unknown key '%s'", key);
-    if (numel != seg_key_numel(hd, i))
+    while (i < hd->n_tensors && strcmp(key, hd->tensor[i].key) != 0) ++i;
+    if (i == hd->n_tensors) return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head_set_tensor: unknown key '%s'", key);
+    seg_tensor *t = &hd->tensor[i];
+    if (numel != t->rows * t->len)
         return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head_set_tensor: %s has %llu elements, not %llu", key,
-                            (unsigned long long)seg_key_numel(hd, i), (unsigned long long)numel);
-    // padded on the host: rows of `len` values become rows of `pitch`, `rows` rows become `prows`; everything added
-    // is zero but the running variance of an added mid channel (1: scale = 0 / sqrt(1 + eps) = 0, shift = 0)
-    const uint64_t rows = i == 0 ? hd->mid : i <= 4 ? 1 : hd->classes, prows = i == 0 ? hd->midp : i <= 4 ? 1 : hd->cpad;
-    const uint64_t len = i == 0 ? hd->cin * 9 : i <= 5 ? hd->mid : 1, pitch = i == 0 ? len : i <= 5 ? hd->midp : 1;
-    float *padded = (float *)calloc(prows * pitch, sizeof(float));
-    if (!padded) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_seg_head_set_tensor: out of host memory");
-    for (uint64_t r = 0; r < rows; ++r) memcpy(padded + r * pitch, host_data + r * len, len * sizeof(float));
-    if (i == 4)
-        for (uint64_t c = hd->mid; c < hd->midp; ++c) padded[c] = 1.0f;
-    int st = hd->raw[i] ? RN_OK : rn_malloc(ctx, (void **)&hd->raw[i], prows * pitch * sizeof(float));
-    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, hd->raw[i], padded, prows * pitch * sizeof(float));
-    free(padded);
-    RN_TRY(st);
-    hd->is_set[i] = 1;
+                            (unsigned long long)(t->rows * t->len), (unsigned long long)numel);
+    RN_TRY(seg_upload(ctx, &t->raw, host_data, t->rows, t->len, t->len, t->prows, t->pitch, t->fill));
+    for (int u = 0; u < hd->n_units; ++u) {  // a dilated branch's weight [cout, cin, 3, 3]: its centre tap too
+        seg_unit *un = &hd->unit[u];
+        const uint64_t taps = un->cout * un->cin;  // a branch is never padded
+        if (un->dilation && un->first == i) RN_TRY(seg_upload(ctx, &un->raw_center, host_data + 4, taps, 1, 9, taps, 1, 0.0f));
+    }
+    t->is_set = 1;
     return RN_OK;
 }
 
@@ -716,22 +644,34 @@ int rn_seg_head_finalize(rn_seg_head *hd)
     rn_ctx *ctx = hd->ctx;
     RN_ENTER(ctx);
     if (hd->finalized) return RN_OK;
-    if (hd->dl) return dl_finalize(hd);
-    for (int i = 0; i < 7; ++i)
-        if (!hd->is_set[i]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head_finalize: %s is not set", kSegKeys[i]);
-    const uint64_t es = seg_elem(hd);
-    RN_TRY(rn_malloc(ctx, (void **)&hd->scale, hd->midp * sizeof(float)));
-    RN_TRY(rn_malloc(ctx, (void **)&hd->shift, hd->midp * sizeof(float)));
-    RN_TRY(rn_malloc(ctx, &hd->packed1, rn_conv2d_packed_weight_numel_dt(hd->dtype, hd->cin, hd->midp, 3) * es));
-    RN_TRY(rn_malloc(ctx, &hd->packed2, rn_conv2d_packed_weight_numel_dt(hd->dtype, hd->midp, hd->cpad, 1) * es));
-    RN_TRY(rn_batchnorm2d_fold(ctx, hd->raw[1], hd->raw[2], hd->raw[3], hd->raw[4], hd->scale, hd->shift, hd->midp));
-    RN_TRY(rn_conv2d_pack_weight_dt(ctx, hd->dtype, hd->raw[0], hd->packed1, hd->cin, hd->midp, 3));
-    RN_TRY(rn_conv2d_pack_weight_dt(ctx, hd->dtype, hd->raw[5], hd->packed2, hd->midp, hd->cpad, 1));
-    RN_TRY(rn_sync(ctx));
-    for (int i = 0; i < 6; ++i) {  // the bias (raw[6]) stays: it is the 1x1 convolution's shift
-        RN_TRY(rn_free(ctx, hd->raw[i]));
-        hd->raw[i] = NULL;
+    for (int i = 0; i < hd->n_tensors; ++i)
+        if (!hd->tensor[i].is_set)
+            return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head_finalize: %s is not set", hd->tensor[i].key);
+    const int dt = hd->dtype;
+    const uint64_t es = rn_elem_size(dt);
+    for (int u = 0; u < hd->n_units; ++u) {
+        seg_unit *un = &hd->unit[u];
+        seg_tensor *t = &hd->tensor[un->first];
+        if (un->bn) {
+            RN_TRY(rn_malloc(ctx, (void **)&un->scale, un->cout * sizeof(float)));
+            RN_TRY(rn_malloc(ctx, (void **)&un->shift, un->cout * sizeof(float)));
+            RN_TRY(rn_batchnorm2d_fold(ctx, t[1].raw, t[2].raw, t[3].raw, t[4].raw, un->scale, un->shift, un->cout));
+        }
+        RN_TRY(rn_malloc(ctx, &un->packed, rn_conv2d_packed_weight_numel_dt(dt, un->cin, un->cout, un->k) * es));
+        RN_TRY(rn_conv2d_pack_weight_dt(ctx, dt, t[0].raw, un->packed, un->cin, un->cout, un->k));
+        if (un->raw_center) {
+            RN_TRY(rn_malloc(ctx, &un->center, rn_conv2d_packed_weight_numel_dt(dt, un->cin, un->cout, 1) * es));
+            RN_TRY(rn_conv2d_pack_weight_dt(ctx, dt, un->raw_center, un->center, un->cin, un->cout, 1));
+        }
     }
+    RN_TRY(rn_sync(ctx));
+    for (int u = 0; u < hd->n_units; ++u) {
+        seg_unit *un = &hd->unit[u];
+        float **bias = &hd->tensor[un->first + 1].raw;
+        if (!un->bn) un->shift = *bias, *bias = NULL;  // the bias stays: the unit's shift
+        rn_free_null(ctx, (void **)&un->raw_center);
+    }
+    for (int i = 0; i < hd->n_tensors; ++i) rn_free_null(ctx, (void **)&hd->tensor[i].raw);
     hd->finalized = 1;
     return RN_OK;
 }
@@ -742,25 +682,13 @@ int rn_seg_head_destroy(rn_seg_head *hd)
     rn_ctx *ctx = hd->ctx;
     RN_ENTER(ctx);
     RN_TRY(rn_sync(ctx));
-    if (hd->dl) {
-        seg_deeplab *dl = hd->dl;
-        dl_free_scratch(hd);
-        for (int i = 0; i < dl->n_tensors; ++i) dl_free(ctx, (void **)&dl->tensor[i].raw);
-        for (int u = 0; u < dl->n_units; ++u) {
-            seg_unit *un = &dl->unit[u];
-            dl_free(ctx, &un->packed), dl_free(ctx, &un->center), dl_free(ctx, (void **)&un->raw_center);
-            dl_free(ctx, (void **)&un->scale), dl_free(ctx, (void **)&un->shift);
-        }
-        dl_free(ctx, &dl->packed_cls);
-        free(dl);
-        free(hd);
-        return RN_OK;
+    seg_free_scratch(hd);
+    for (int i = 0; i < hd->n_tensors; ++i) rn_free_null(ctx, (void **)&hd->tensor[i].raw);
+    for (int u = 0; u < hd->n_units; ++u) {
+        seg_unit *un = &hd->unit[u];
+        rn_free_null(ctx, &un->packed), rn_free_null(ctx, &un->center), rn_free_null(ctx, (void **)&un->raw_center);
+        rn_free_null(ctx, (void **)&un->scale), rn_free_null(ctx, (void **)&un->shift);
     }
-    void *bufs[6] = {hd->packed1, hd->packed2, hd->scale, hd->shift, hd->mid_t, hd->coarse};
-    for (int i = 0; i < 7; ++i)
-        if (hd->raw[i]) rn_free(ctx, hd->raw[i]);
-    for (int i = 0; i < 6; ++i)
-        if (bufs[i]) rn_free(ctx, bufs[i]);
     free(hd);
     return RN_OK;
 }
@@ -783,76 +711,62 @@ void rn_seg_head_dims(const rn_seg_head *hd, uint64_t dims[4])
 }
 
 // launch `step` of a forward of B images on an h x w map to H x W: its profile name, FLOPs and bytes; returns the
-// number of launches (3 for the FCN kind, n + 8 for the DeepLab kind); step outside 0 .. that - 1 only counts
+// number of launches; step outside 0 .. that - 1 only counts.  Every count is an integer far below 2^53, so the
+// doubles are exact whatever the order of their products.
 int rn_seg_head_plan(const rn_seg_head *hd, uint64_t B, uint64_t h, uint64_t w, uint64_t H, uint64_t W, int want_scores,
                      int want_labels, int step, const char **name, double *flops, double *bytes)
 {
-    const double es = (double)seg_elem(hd), P = (double)(B * h * w), cin = (double)hd->cin, cpad = (double)hd->cpad;
-    const double up = 4.0 * P * cpad +
-                      (double)(B * H * W) * ((want_scores ? 4.0 * (double)hd->classes : 0.0) + (want_labels ? 1.0 : 0.0));
-    const int count = hd->dl ? (int)hd->dl->n + 8 : 3;
-    const char *nm = NULL;
+    if (step < 0 || step >= hd->n_steps) return hd->n_steps;
+    const seg_step *s = &hd->step[step];
+    const double es = (double)rn_elem_size(hd->dtype), nb = (double)B, P = (double)(B * h * w);
     double f = 0.0, by = 0.0;
-    if (step < 0 || step >= count) return count;
-    if (!hd->dl) {
-        const double mid = (double)hd->midp;
-        if (step == 0) nm = "seg_conv1", f = 2.0 * P * 9.0 * cin * mid, by = es * (P * (cin + mid) + 9.0 * cin * mid);
-        else if (step == 1) nm = "seg_conv2", f = 2.0 * P * mid * cpad, by = P * (es * mid + 4.0 * cpad) + es * (mid * cpad);
-        else nm = "seg_upsample", by = up;
-    } else {
-        const uint64_t n = hd->dl->n, s = (uint64_t)step;
-        const double a = (double)hd->dl->a, cat = (double)(n + 2) * a;
-        if (s <= n) {  // the FLOPs of the route that runs
-            const double taps = s == 0 || dl_center_route(hd, step, h, w) ? 1.0 : 9.0;
-            nm = kDlBranchOps[s], f = 2.0 * P * taps * cin * a, by = es * (P * (cin + a) + taps * cin * a);
-        } else if (s == n + 1) nm = "aspp_pool", by = es * (double)B * cin * (double)(h * w + 1);
-        else if (s == n + 2) nm = "aspp_pool_conv", f = 2.0 * (double)B * cin * a, by = es * ((double)B * (cin + a) + cin * a);
-        else if (s == n + 3) nm = "aspp_concat", by = es * (2.0 * P * cat - P * a + (double)B * a);
-        else if (s == n + 4) nm = "aspp_project", f = 2.0 * P * cat * a, by = es * (P * (cat + a) + cat * a);
-        else if (s == n + 5) nm = "seg_conv1", f = 2.0 * P * 9.0 * a * a, by = es * (P * 2.0 * a + 9.0 * a * a);
-        else if (s == n + 6) nm = "seg_conv2", f = 2.0 * P * a * cpad, by = P * (es * a + 4.0 * cpad) + es * (a * cpad);
-        else nm = "seg_upsample", by = up;
+    switch (s->kind) {
+    case SEG_CONV: {  // the FLOPs of the route that runs
+        const seg_unit *un = &hd->unit[s->u];
+        const double M = s->src >= 0 && hd->buf[s->src].per_image ? nb : P, cin = (double)un->cin, cout = (double)un->cout;
+        const double taps = dl_center_route(hd, un, h, w) ? 1.0 : (double)(un->k * un->k);
+        f = 2.0 * M * taps * cin * cout, by = M * (es * cin + (un->bn ? es : 4.0) * cout) + es * taps * cin * cout;
+        break;
     }
-    if (name) *name = nm;
+    case SEG_POOL: by = es * nb * (double)hd->buf[s->dst].channels * (double)(h * w + 1); break;
+    case SEG_CONCAT: {
+        const double cat = (double)hd->buf[s->dst].channels, a = (double)hd->buf[s->src].channels;
+        by = es * (2.0 * P * cat - P * a + nb * a);
+        break;
+    }
+    default:
+        by = 4.0 * P * (double)hd->cpad +
+             (double)(B * H * W) * ((want_scores ? 4.0 * (double)hd->classes : 0.0) + (want_labels ? 1.0 : 0.0));
+        break;
+    }
+    if (name) *name = s->name;
     if (flops) *flops = f;
     if (bytes) *bytes = by;
-    return count;
+    return hd->n_steps;
 }
 
-// the scratch for `images` images of `pixels` coarse pixels (h x w) each; it grows like the model's logits buffer:
-// never on a stream that is being captured, never while a captured graph of the context may hold it
+// the scratch for `images` images of `pixels` coarse pixels (h x w) each; it never shrinks and grows like the
+// model's logits buffer: never on a stream that is being captured, never while a captured graph of the context may
+// hold it
 int rn_seg_head_reserve(rn_seg_head *hd, uint64_t images, uint64_t pixels)
 {
     rn_ctx *ctx = hd->ctx;
-    seg_deeplab *dl = hd->dl;
     uint64_t pix = images * pixels;
-    if (pix <= hd->cap_pix && (!dl || images <= dl->cap_img)) return RN_OK;
+    if (seg_fits(hd, pix, images)) return RN_OK;
     if (rn_ctx_is_capturing(ctx))
         return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "rn_seg_head: the scratch cannot grow on a stream that is being captured");
     if (hd->cap_pix > 0 && ctx->graphs_live > 0)
         return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head: the scratch cannot grow while a captured graph lives");
     RN_TRY(rn_sync(ctx));
-    if (dl) {
-        const uint64_t es = seg_elem(hd);
-        if (pix < hd->cap_pix) pix = hd->cap_pix;
-        if (images < dl->cap_img) images = dl->cap_img;
-        dl_free_scratch(hd);
-        for (uint64_t i = 0; i <= dl->n; ++i) RN_TRY(rn_malloc(ctx, &dl->branch[i], pix * dl->a * es));
-        RN_TRY(rn_malloc(ctx, &dl->cat, pix * (dl->n + 2) * dl->a * es));
-        RN_TRY(rn_malloc(ctx, &dl->pool_in, images * hd->cin * es));
-        RN_TRY(rn_malloc(ctx, &dl->pool_out, images * dl->a * es));
-        RN_TRY(rn_malloc(ctx, (void **)&hd->coarse, pix * hd->cpad * sizeof(float)));
-        hd->cap_pix = pix, dl->cap_img = images;
-        return RN_OK;
+    if (pix < hd->cap_pix) pix = hd->cap_pix;
+    if (images < hd->cap_img) images = hd->cap_img;
+    seg_free_scratch(hd);
+    for (int i = 0; i < hd->n_bufs; ++i) {
+        seg_buf *b = &hd->buf[i];
+        const uint64_t es = b->f32 ? 4 : rn_elem_size(hd->dtype);
+        RN_TRY(rn_malloc(ctx, &b->ptr, (b->per_image ? images : pix) * b->channels * es));
     }
-    if (hd->mid_t) RN_TRY(rn_free(ctx, hd->mid_t));
-    hd->mid_t = NULL;
-    if (hd->coarse) RN_TRY(rn_free(ctx, hd->coarse));
-    hd->coarse = NULL;
-    hd->cap_pix = 0;
-    RN_TRY(rn_malloc(ctx, &hd->mid_t, pix * hd->midp * seg_elem(hd)));
-    RN_TRY(rn_malloc(ctx, (void **)&hd->coarse, pix * hd->cpad * sizeof(float)));
-    hd->cap_pix = pix;
+    hd->cap_pix = pix, hd->cap_img = images;
     return RN_OK;
 }
 
@@ -861,24 +775,38 @@ int rn_seg_head_reserve(rn_seg_head *hd, uint64_t images, uint64_t pixels)
 int rn_seg_head_step(rn_seg_head *hd, rn_ctx *ctx, int step, const void *x_nhwc, uint64_t img0, uint64_t B, uint64_t h,
                      uint64_t w, uint64_t H, uint64_t W, float *scores_nchw, uint8_t *labels)
 {
-    if (hd->dl) return dl_step(hd, ctx, step, x_nhwc, img0, B, h, w, H, W, scores_nchw, labels);
     const uint64_t pix0 = img0 * h * w;
-    void *mid = (char *)hd->mid_t + pix0 * hd->midp * seg_elem(hd);
-    float *coarse = hd->coarse + pix0 * hd->cpad;
-    rn_epilogue ep;
-    ep.residual = NULL;
-    if (pix0 + B * h * w > hd->cap_pix) return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head: scratch not reserved");
-    if (step == 0) {
-        ep.scale = hd->scale, ep.shift = hd->shift, ep.relu = 1;
-        return rn_conv2d_nhwc_forward_dt(ctx, hd->dtype, hd->dtype, x_nhwc, mid, hd->packed1, 3, 1, 1, h, w, B, hd->cin,
-                                         hd->midp, h, w, &ep);
+    const int dt = hd->dtype;
+    RN_REQUIRE(ctx, step >= 0 && step < hd->n_steps, "no such step");
+    if (!seg_fits(hd, pix0 + B * h * w, img0 + B)) return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head: scratch not reserved");
+    const seg_step *s = &hd->step[step];
+    const bool per_image = s->src >= 0 && hd->buf[s->src].per_image;
+    const void *src = s->src < 0 ? x_nhwc : seg_at(hd, s->src, img0, pix0);
+    void *dst = s->dst < 0 ? NULL : seg_at(hd, s->dst, img0, pix0);
+    switch (s->kind) {
+    case SEG_CONV: {
+        const seg_unit *un = &hd->unit[s->u];
+        const uint64_t uh = per_image ? 1 : h, uw = per_image ? 1 : w;
+        rn_epilogue ep;
+        ep.scale = un->scale, ep.shift = un->shift, ep.residual = NULL, ep.relu = un->bn;
+        if (un->dilation && !dl_center_route(hd, un, h, w))
+            return rn_conv2d_dilated_nhwc_forward_dt(ctx, dt, dt, src, dst, un->packed, 3, 1, un->dilation, un->dilation, h,
+                                                     w, B, un->cin, un->cout, h, w, 1, &ep);
+        const uint64_t k = un->dilation ? 1 : un->k;  // a dilated branch gets here on its centre tap
+        return rn_conv2d_nhwc_forward_dt(ctx, dt, un->bn ? dt : RN_DTYPE_F32, src, dst, un->dilation ? un->center : un->packed,
+                                         k, 1, k / 2, uh, uw, B, un->cin, un->cout, uh, uw, &ep);
     }
-    if (step == 1) {
-        ep.scale = NULL, ep.shift = hd->raw[6], ep.relu = 0;
-        return rn_conv2d_nhwc_forward_dt(ctx, hd->dtype, RN_DTYPE_F32, mid, coarse, hd->packed2, 1, 1, 0, h, w, B,
-                                         hd->midp, hd->cpad, h, w, &ep);
+    case SEG_POOL: return rn_global_avgpool_nhwc_forward_dt(ctx, dt, src, dst, B, hd->buf[s->dst].channels, h, w);
+    case SEG_CONCAT: {
+        const void *srcs[kSegMaxRates + 1];
+        uint64_t ch[kSegMaxRates + 1];
+        for (int i = 0; i < s->u; ++i) srcs[i] = seg_at(hd, i, img0, pix0), ch[i] = hd->buf[i].channels;
+        return rn_concat_channels_forward_dt(ctx, dt, (uint64_t)s->u, srcs, ch, src, hd->buf[s->src].channels, dst, B, h * w);
     }
-    return rn_upsample_bilinear_forward(ctx, coarse, B, h, w, hd->classes, hd->cpad, H, W, scores_nchw, labels);
+    default:
+        return rn_upsample_bilinear_forward(ctx, (const float *)src, B, h, w, hd->classes, hd->cpad, H, W, scores_nchw,
+                                            labels);
+    }
 }
 
 int rn_seg_head_forward(rn_seg_head *hd, const void *x_nhwc, uint64_t B, uint64_t h, uint64_t w, uint64_t H, uint64_t W,
@@ -897,8 +825,7 @@ int rn_seg_head_forward(rn_seg_head *hd, const void *x_nhwc, uint64_t B, uint64_
     RN_TRY(rn_seg_head_reserve(hd, B, h * w));
     ctx->layout = RN_LAYOUT_NHWC;
     int st = RN_OK;
-    const int steps = rn_seg_head_plan(hd, B, h, w, H, W, scores_nchw != NULL, labels != NULL, -1, NULL, NULL, NULL);
-    for (int step = 0; step < steps && st == RN_OK; ++step)
+    for (int step = 0; step < hd->n_steps && st == RN_OK; ++step)
         st = rn_seg_head_step(hd, ctx, step, x_nhwc, 0, B, h, w, H, W, scores_nchw, labels);
     ctx->layout = saved_layout;
     return st;

@@ -5,7 +5,7 @@ seeded head weights (``generate_fcn_head_state``), the split of a torchvision ``
 (``split_state``), and ``FCNHead``, the Python face of ``rn_seg_head_*``.  ``NativeModel.forward_segment`` runs a
 head right behind layer4 of a forward; ``ops.upsample_bilinear`` is the upsample launch alone.  The second half of
 the file is the same for torchvision's DeepLabHead (``deeplab_head_shapes``, ``generate_deeplab_head_state``,
-``deeplab_head_ref``, ``DeepLabHead``), the other kind of the same device object.
+``deeplab_head_ref``, ``DeepLabHead``), the same device object with a longer table of convolutions.
 """
 from __future__ import annotations
 
@@ -73,15 +73,12 @@ def upsample_bilinear_ref(x_nhwc, size, classes: Optional[int] = None):
 # ---------------------------------------------------------------------------
 # weights
 # ---------------------------------------------------------------------------
-def generate_fcn_head_state(in_channels: int, classes: int, seed: int = 0) -> Dict[str, np.ndarray]:
-    """Seeded tensors of FCNHead(in_channels, classes) under torchvision's keys, from the generator of weights.py:
-    both convolutions He-uniform over their fan-in, the batch-norm as weights.generate_tensor draws one.  The
-    classifier's bias is uniform in +-0.02: two orders below the spread the He-scaled 1x1 convolution gives the
-    scores of an O(1) mid tensor, so that the bias never decides a label (ADVICE.md: a bias-dominated fixture makes
-    every top-1 assert vacuous)."""
+def _draw_head_state(tag: str, shapes: Dict[str, Tuple[int, ...]], seed: int) -> Dict[str, np.ndarray]:
+    """The draws of generate_fcn_head_state for every key of shapes; `{tag}.{key}` is the tensor's name in the
+    generator."""
     out = {}
-    for key, shape in head_shapes(in_channels, classes).items():
-        name = f"fcn{in_channels}x{classes}.{key}"
+    for key, shape in shapes.items():
+        name = f"{tag}.{key}"
         if key == "classifier.4.bias":
             out[key] = weights._uniform(name, shape, -0.02, 0.02, seed)
         elif len(shape) == 4:
@@ -92,6 +89,16 @@ def generate_fcn_head_state(in_channels: int, classes: int, seed: int = 0) -> Di
         else:
             out[key] = weights._uniform(name, shape, -0.1, 0.1, seed)
     return out
+
+
+def generate_fcn_head_state(in_channels: int, classes: int, seed: int = 0,
+                            mid_channels: Optional[int] = None) -> Dict[str, np.ndarray]:
+    """Seeded tensors of FCNHead(in_channels, classes) under torchvision's keys, from the generator of weights.py:
+    both convolutions He-uniform over their fan-in, the batch-norm as weights.generate_tensor draws one.  The
+    classifier's bias is uniform in +-0.02: two orders below the spread the He-scaled 1x1 convolution gives the
+    scores of an O(1) mid tensor, so that the bias never decides a label (ADVICE.md: a bias-dominated fixture makes
+    every top-1 assert vacuous)."""
+    return _draw_head_state(f"fcn{in_channels}x{classes}", head_shapes(in_channels, classes, mid_channels), seed)
 
 
 def split_state(state) -> Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]:
@@ -147,20 +154,30 @@ def fcn_head_ref(x_nchw_f64, state, size, round_fn=None) -> np.ndarray:
 class FCNHead:
     """rn_seg_head_*: FCNHead(in_channels, classes) with mid = in_channels // 4 on the device; state holds
     torchvision's seven tensors (HEAD_KEYS).  dtype "f32" or "bf16": storage of the input map, the mid tensor and
-    the weight panels; the coarse scores and the outputs are fp32 either way."""
+    the weight panels; the coarse scores and the outputs are fp32 either way.  mid_channels: another width than
+    torchvision's in_channels // 4."""
 
-    def __init__(self, in_channels: int, classes: int, state: Dict[str, np.ndarray], dtype: str = "f32", ctx=None):
+    def __init__(self, in_channels: int, classes: int, state: Dict[str, np.ndarray], dtype: str = "f32", ctx=None,
+                 mid_channels: Optional[int] = None):
+        mid = int(in_channels) // 4 if mid_channels is None else int(mid_channels)
+        self._build(in_channels, mid, classes, dtype, ctx, state, head_shapes(in_channels, classes, mid),
+                    "rn_seg_head_create", mid, int(classes))
+
+    def _build(self, in_channels, mid_channels, classes, dtype, ctx, state, shapes, create, *create_args):
+        """the head of either kind: `create`(ctx, &handle, in_channels, *create_args), its dtype, the tensors of shapes
+        from state, finalize"""
         from .tensor import get_ctx
+        self.handle = None                                   # close() is safe whatever fails below
         self.ctx = ctx or get_ctx()
-        self.in_channels, self.mid_channels, self.classes, self.dtype = int(in_channels), int(in_channels) // 4, int(classes), dtype
+        self.in_channels, self.mid_channels, self.classes, self.dtype = int(in_channels), int(mid_channels), int(classes), dtype
         lib = L.lib()
         h = ctypes.c_void_p()
-        L.check(lib.rn_seg_head_create(self.ctx.handle, ctypes.byref(h), self.in_channels, self.mid_channels, self.classes),
-                "rn_seg_head_create", self.ctx.handle)
+        L.check(getattr(lib, create)(self.ctx.handle, ctypes.byref(h), self.in_channels, *create_args), create,
+                self.ctx.handle)
         self.handle = h
         L.check(lib.rn_seg_head_set_dtype(h, {"f32": L.RN_DTYPE_F32, "bf16": L.RN_DTYPE_BF16}[dtype]),
                 "rn_seg_head_set_dtype", self.ctx.handle)
-        for key, shape in head_shapes(self.in_channels, self.classes).items():
+        for key, shape in shapes.items():
             arr = np.ascontiguousarray(state[key], dtype=np.float32)
             assert arr.size == int(np.prod(shape)), (key, arr.shape, shape)
             L.check(lib.rn_seg_head_set_tensor(h, key.encode(), arr.ctypes.data, arr.size),
@@ -204,7 +221,7 @@ class FCNHead:
 
 
 # ---------------------------------------------------------------------------
-# DeepLabV3: torchvision's DeepLabHead (ASPP + Conv3x3 + Conv1x1) as the second kind of rn_seg_head
+# DeepLabV3: torchvision's DeepLabHead (ASPP + Conv3x3 + Conv1x1), an rn_seg_head from rn_seg_head_create_deeplab
 # ---------------------------------------------------------------------------
 DEEPLAB_RATES = (12, 24, 36)
 _BN = ("weight", "bias", "running_mean", "running_var")
@@ -240,20 +257,8 @@ def generate_deeplab_head_state(in_channels: int, classes: int, aspp_channels: i
     """Seeded tensors of DeepLabHead under torchvision's keys: the draws of generate_fcn_head_state (convolutions
     He-uniform over their fan-in, batch-norms as there, the classifier's bias in +-0.02), every key with a name of
     its own in the generator."""
-    out = {}
     tag = f"deeplab{in_channels}x{aspp_channels}x{classes}r{'_'.join(str(int(r)) for r in rates)}"
-    for key, shape in deeplab_head_shapes(in_channels, classes, aspp_channels, rates).items():
-        name = f"{tag}.{key}"
-        if key == "classifier.4.bias":
-            out[key] = weights._uniform(name, shape, -0.02, 0.02, seed)
-        elif len(shape) == 4:
-            bound = float(np.sqrt(6.0 / (shape[1] * shape[2] * shape[3])))
-            out[key] = weights._uniform(name, shape, -bound, bound, seed)
-        elif key.endswith("running_var") or key.endswith(".weight"):
-            out[key] = weights._uniform(name, shape, 0.5, 1.5, seed)
-        else:
-            out[key] = weights._uniform(name, shape, -0.1, 0.1, seed)
-    return out
+    return _draw_head_state(tag, deeplab_head_shapes(in_channels, classes, aspp_channels, rates), seed)
 
 
 def deeplab_head_ref(x_nchw_f64, state, size, rates=DEEPLAB_RATES, round_fn=None) -> np.ndarray:
@@ -304,25 +309,11 @@ class DeepLabHead(FCNHead):
 
     def __init__(self, in_channels: int, classes: int, state: Dict[str, np.ndarray], aspp_channels: int = 256,
                  rates=DEEPLAB_RATES, dtype: str = "f32", ctx=None):
-        from .tensor import get_ctx
-        self.ctx = ctx or get_ctx()
-        self.in_channels, self.mid_channels, self.classes, self.dtype = int(in_channels), int(aspp_channels), int(classes), dtype
         self.aspp_channels, self.rates = int(aspp_channels), tuple(int(r) for r in rates)
-        lib = L.lib()
-        h = ctypes.c_void_p()
         rates_c = (ctypes.c_uint64 * len(self.rates))(*self.rates)
-        L.check(lib.rn_seg_head_create_deeplab(self.ctx.handle, ctypes.byref(h), self.in_channels, self.aspp_channels,
-                                               self.classes, len(self.rates), rates_c),
-                "rn_seg_head_create_deeplab", self.ctx.handle)
-        self.handle = h
-        L.check(lib.rn_seg_head_set_dtype(h, {"f32": L.RN_DTYPE_F32, "bf16": L.RN_DTYPE_BF16}[dtype]),
-                "rn_seg_head_set_dtype", self.ctx.handle)
-        for key, shape in deeplab_head_shapes(self.in_channels, self.classes, self.aspp_channels, self.rates).items():
-            arr = np.ascontiguousarray(state[key], dtype=np.float32)
-            assert arr.size == int(np.prod(shape)), (key, arr.shape, shape)
-            L.check(lib.rn_seg_head_set_tensor(h, key.encode(), arr.ctypes.data, arr.size),
-                    f"rn_seg_head_set_tensor({key})", self.ctx.handle)
-        L.check(lib.rn_seg_head_finalize(h), "rn_seg_head_finalize", self.ctx.handle)
+        self._build(in_channels, self.aspp_channels, classes, dtype, ctx, state,
+                    deeplab_head_shapes(in_channels, classes, self.aspp_channels, self.rates),
+                    "rn_seg_head_create_deeplab", self.aspp_channels, int(classes), len(self.rates), rates_c)
 
     def center_tap(self, on: bool) -> None:
         L.check(L.lib().rn_seg_head_set_center_tap(self.handle, int(bool(on))), "rn_seg_head_set_center_tap", self.ctx.handle)

@@ -199,6 +199,105 @@ def test_head_refusals():
 
 
 # =====================================================================================================================
+# 4b. the head's bookkeeping: padding in its general form, scratch growth, a tensor set twice
+# =====================================================================================================================
+PAD_SEED = 2   # the float64 reference labels of this seed hold all three classes, fp32 and bf16 (17, 14 and 32 pixels)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_head_padding_in_general(dtype):
+    """FCNHead(64, 3, mid_channels=20): mid 20 -> 64 and classes 3 -> 4, neither count a multiple of 4.  The bounds of
+    test_head_alone; the added channels must add exact zeros and the added class must never be a label"""
+    cin, classes, mid, size = 64, 3, 20, (7, 9)
+    x = np.random.default_rng(20).standard_normal((1, 3, 5, cin), dtype=np.float32)
+    st = S.generate_fcn_head_state(cin, classes, seed=PAD_SEED, mid_channels=mid)
+    ref = S.fcn_head_ref(x.transpose(0, 3, 1, 2).astype(np.float64), st, size,
+                         round_fn=ops.bf16_round if dtype == "bf16" else None)
+    assert len(np.unique(ref.argmax(axis=1))) >= 2
+    head = S.FCNHead(cin, classes, st, dtype=dtype, mid_channels=mid)
+    try:
+        assert head.mid_channels == mid
+        scores, labels = head.forward(x, size, scores=True, labels=True)
+    finally:
+        head.close()
+    tol = tol_f32(ref, 9 * cin) if dtype == "f32" else tol_bf16(ref)
+    err = float(np.abs(scores - ref).max())
+    print(f"\n  FCNHead({cin}, {classes}, mid {mid}) {dtype}: max|gpu - fp64| = {err:.3e}, bound {tol:.3e}")
+    assert scores.shape == ref.shape and err <= tol
+    assert np.array_equal(labels, scores.argmax(axis=1))
+    assert len(np.unique(labels)) >= 2
+
+
+def small_head(kind, dtype="f32", rates=(1, 2)):
+    """(constructor of a 64-channel, 5-class head of either kind, its state, its shapes, the C create call and its
+    arguments behind in_channels)"""
+    if kind == "fcn":
+        st = S.generate_fcn_head_state(64, 5, seed=3)
+        return (lambda: S.FCNHead(64, 5, st, dtype=dtype)), st, S.head_shapes(64, 5), "rn_seg_head_create", (16, 5)
+    st = S.generate_deeplab_head_state(64, 5, 64, rates, seed=3)
+    rates_c = (ctypes.c_uint64 * len(rates))(*rates)
+    return ((lambda: S.DeepLabHead(64, 5, st, aspp_channels=64, rates=rates, dtype=dtype)), st,
+            S.deeplab_head_shapes(64, 5, 64, rates), "rn_seg_head_create_deeplab", (64, 5, len(rates), rates_c))
+
+
+@pytest.mark.parametrize("kind", ["fcn", "deeplab"])
+def test_scratch_growth_keeps_the_bits(kind):
+    """one head on (1, 2, 2), then (2, 4, 3), then (1, 2, 2) again -- its scratch grows in pixels and in images, then
+    is larger than needed: every result is, bit for bit, that of a fresh head on the same input"""
+    make = small_head(kind)[0]
+    head = make()
+    try:
+        for i, bhw in enumerate(((1, 2, 2), (2, 4, 3), (1, 2, 2))):
+            x = np.random.default_rng(40 + i).standard_normal(bhw + (64,), dtype=np.float32)
+            size = (2 * bhw[1] + 1, 3 * bhw[2])
+            fresh = make()
+            try:
+                want_s, want_l = fresh.forward(x, size, scores=True, labels=True)
+            finally:
+                fresh.close()
+            got_s, got_l = head.forward(x, size, scores=True, labels=True)
+            assert np.array_equal(bits(got_s), bits(want_s)) and np.array_equal(got_l, want_l), (kind, i, bhw)
+    finally:
+        head.close()
+
+
+@pytest.mark.parametrize("kind,dtype,twice", [
+    ("fcn", "f32", ("classifier.0.weight", "classifier.1.running_var")),
+    ("deeplab", "bf16", ("classifier.0.convs.1.0.weight",))], ids=["fcn", "deeplab"])
+def test_tensor_set_twice(kind, dtype, twice):
+    """garbage under a key, then the right values, before finalize: the bits of a head that was set once.  DeepLab:
+    bf16 on a 2 x 2 map with rates (2, 3), where both dilated branches run on their centre tap, so a centre-tap copy
+    of the garbage would show"""
+    make, st, shapes, create, args = small_head(kind, dtype, rates=(2, 3))
+    x = np.random.default_rng(50).standard_normal((1, 2, 2, 64), dtype=np.float32)
+    size = (5, 6)
+    once = make()
+    try:
+        want_s, want_l = once.forward(x, size, scores=True, labels=True)
+    finally:
+        once.close()
+    lib, ctx = L.lib(), R.get_ctx()
+    h = ctypes.c_void_p()
+    assert getattr(lib, create)(ctx.handle, ctypes.byref(h), 64, *args) == L.RN_OK
+    try:
+        assert lib.rn_seg_head_set_dtype(h, {"f32": L.RN_DTYPE_F32, "bf16": L.RN_DTYPE_BF16}[dtype]) == L.RN_OK
+        for key in shapes:
+            right = np.ascontiguousarray(st[key], dtype=np.float32)
+            for data in ([np.full(right.size, 1e3, np.float32)] if key in twice else []) + [right]:
+                assert lib.rn_seg_head_set_tensor(h, key.encode(), data.ctypes.data, data.size) == L.RN_OK, key
+        assert lib.rn_seg_head_finalize(h) == L.RN_OK
+        vi = V.place(ops.to_bf16_bits(x).reshape(x.shape) if dtype == "bf16" else x)
+        vs, vl = V.place_out(5 * size[0] * size[1] * 4), V.place_out(size[0] * size[1])
+        assert lib.rn_seg_head_forward(h, vi.ptr, 1, 2, 2, size[0], size[1], vs.ptr, vl.ptr) == L.RN_OK
+        ctx.sync()
+        got_s = V.fetch(vs, np.float32, kind, written=True).reshape(want_s.shape)
+        got_l = V.fetch(vl, np.uint8, kind, written=True).reshape(want_l.shape)
+    finally:
+        lib.rn_seg_head_destroy(h)
+    assert np.array_equal(bits(got_s), bits(want_s)) and np.array_equal(got_l, want_l)
+
+
+# =====================================================================================================================
 # 5. the model
 # =====================================================================================================================
 SIZE, FLAGS, CLASSES, MB = (64, 64), (0, 1, 1), 21, 3
