@@ -972,6 +972,77 @@ RN_API int rn_model_forward_fpn(rn_model *m, rn_fpn *fpn, const float *input_nch
 RN_API int rn_model_forward_fpn_u8(rn_model *m, rn_fpn *fpn, const uint8_t *input_nhwc, uint64_t B,
                                    const rn_model_outputs *outs, const int *stages, const rn_fpn_outputs *fpn_out,
                                    int mode);
+/* ---- RoIAlign over the pyramid: torchvision's MultiScaleRoIAlign as ONE launch ---------------------------------
+ * rn_roi_align_forward_dt pools K regions from n_levels NHWC maps (1..4, finest first; x_nhwc[i] [B,h[i],w[i],C] of
+ * `dtype`, 16-byte aligned, C * element size a multiple of 16 bytes, scales[i] its spatial scale) into
+ * out [K,C,PH,PW] fp32 (torchvision's layout, 4-byte aligned); every RoI picks its level inside the kernel.
+ * rois_dev: device [K,5] fp32 (image index, x1, y1, x2, y2) in input-image pixels, torchvision's format.
+ * levels_out: the chosen level of every RoI, int32 [K], or NULL.  PH, PW 1..32; sampling_ratio 1..4 (<= 0, the
+ * adaptive grid, is RN_ERR_UNSUPPORTED); aligned 0 or 1.
+ * The arithmetic is a contract, torchvision's roi_align in its own order; every operation fp32 and rounded on its
+ * own, none fused (ops.roi_align_ref restates it in numpy).  With S = sampling_ratio, h x w the level's map:
+ *   extent:  off = aligned ? 0.5 : 0;  x1s = x1 * scale - off, likewise y1s, x2s, y2s;  rw = x2s - x1s, rh = y2s - y1s,
+ *            each replaced by 1 where it is < 1 and not aligned;  bin_h = rh / PH, bin_w = rw / PW.
+ *   sample:  y = y1s + ph * bin_h + (iy + 0.5) * bin_h / S (the product before the quotient), x likewise.
+ *            It contributes only if y >= -1 && y <= h && x >= -1 && x <= w (a NaN coordinate contributes nothing).
+ *            Then y = max(y, 0), yl = (int)y; if yl >= h - 1: yl = yh = h - 1, y = yl; else yh = yl + 1; x likewise;
+ *            ly = y - yl, hy = 1 - ly, lx, hx likewise;
+ *            val = hy*hx*v1 + hy*lx*v2 + ly*hx*v3 + ly*lx*v4, added left to right (v1 = (yl,xl), v2 = (yl,xh),
+ *            v3 = (yh,xl), v4 = (yh,xh)); a bf16 value is widened exactly.
+ *   bin:     the samples summed with iy outer and ix inner, the sum divided by S * S.
+ * The index clamps are unconditional: no RoI content (NaN, +-Inf, 1e30) indexes outside its map.  A RoI whose image
+ * index is not an integer in [0, B) gets a row of zeros and level -1.
+ * Level: area = (x2 - x1) * (y2 - y1) in fp32, image pixels; level = the number of j with area >= thr[j], thr the
+ * n_levels - 1 thresholds of rn_roi_level_thresholds (host only): k_min = round(-log2(scales[0])),
+ * thr[j] = (canonical_scale * 2^(k_min + 1 + j - canonical_level - 1e-6))^2 in double, rounded up to fp32 -- the
+ * boundaries of torchvision's LevelMapper floor(k0 + log2(sqrt(area) / s0) + 1e-6) clamped to the levels (defaults
+ * s0 = 224, k0 = 4), with no logarithm on the device.
+ * One block takes one RoI and a slab of channels; the slab's outputs are one contiguous run of `out`, stored by
+ * rn_nhwc_to_nchw_dt's rule.  Offsets are 64-bit; B * h * w, C, B and K below 2^31.  Asynchronous on the context's
+ * stream; allocates and uploads nothing (capturable).  K == 0 or B == 0: RN_OK, nothing launched.  RN_ERR_INVALID,
+ * nothing launched, rn_last_error names the operand: a NULL pointer, a misaligned pointer, a bad C, a parameter out
+ * of range, a size at or above 2^31, a scale that is not positive and finite, out or levels_out overlapping an input
+ * or each other. */
+RN_API int rn_roi_level_thresholds(uint64_t n_levels, const float *scales, double canonical_scale, int canonical_level,
+                                   float *thr_out /* n_levels - 1 */);
+RN_API int rn_roi_align_forward_dt(rn_ctx *ctx, int dtype, uint64_t n_levels, const void *const *x_nhwc, const uint64_t *h,
+                                   const uint64_t *w, const float *scales, const float *thr, uint64_t B, uint64_t C,
+                                   const float *rois_dev, uint64_t K, uint64_t PH, uint64_t PW, int sampling_ratio,
+                                   int aligned, float *out, int32_t *levels_out /* nullable */);
+/* A pooler behind a neck: the RoIs (device, [K,5]), the size of the input image they are given in, the neck's levels
+ * the pooler reads (ascending, 0 .. n_levels - 1 of the neck; the pooled extra level is none of them), the pooler's
+ * parameters and the outputs: pooled [K,a,PH,PW] fp32 and, optionally, levels_out int32 [K] (indices into `level`).
+ * The scale of a level is torchvision's, 2^round(log2(h_level / image_h)), computed on the host (the height's, as
+ * torchvision returns it).  The kernel reads the fp32 3x3 outputs in the neck's scratch in place, so the neck runs the
+ * 3x3 of every level the pooler reads, exported or not.
+ * rn_fpn_forward_rois: rn_fpn_forward plus the pooler, queued last; out_nchw may be NULL (no level exported).
+ * rn_model_forward_rois(_u8): rn_model_forward_fpn(_u8)'s launches plus the pooler, queued behind the neck's last
+ * launch of every part with the profile op "roi_align" of layer "fpn"; fpn_out may be NULL.  Every part of a launch
+ * batch pools the RoIs of its own images from its own slice of the scratch; every row of `pooled` is written exactly
+ * once per forward (rows of an invalid image index by the part that holds image 0).  The pooler follows the neck:
+ * dtype, input size, dilation, every architecture, the byte route.  Refused like rn_model_forward_fpn, and: a level
+ * that is not the neck's, rois_dev or pooled NULL with K > 0, a parameter out of range, pooled, levels_out or
+ * rois_dev sharing a byte with each other, an exported level or a head output of the call (RN_ERR_INVALID),
+ * sampling_ratio <= 0 (RN_ERR_UNSUPPORTED).  rn_model_capture, the pipelines and rn_shard_* carry no pooler. */
+typedef struct rn_roi_pool {
+    const float *rois_dev;
+    uint64_t K, image_h, image_w;
+    int n_levels, level[4];
+    uint64_t PH, PW;
+    int sampling_ratio, aligned;
+    double canonical_scale; /* 224 */
+    int canonical_level;    /* 4 */
+    float *pooled;
+    int32_t *levels_out; /* nullable */
+} rn_roi_pool;
+RN_API int rn_fpn_forward_rois(rn_fpn *fpn, const void *const *x_nhwc, uint64_t B, const uint64_t *h, const uint64_t *w,
+                               float *const *out_nchw /* nullable */, const rn_roi_pool *rois);
+RN_API int rn_model_forward_rois(rn_model *m, rn_fpn *fpn, const float *input_nchw, uint64_t B,
+                                 const rn_model_outputs *outs /* nullable */, const int *stages,
+                                 const rn_fpn_outputs *fpn_out /* nullable */, const rn_roi_pool *rois, int mode);
+RN_API int rn_model_forward_rois_u8(rn_model *m, rn_fpn *fpn, const uint8_t *input_nhwc, uint64_t B,
+                                    const rn_model_outputs *outs, const int *stages, const rn_fpn_outputs *fpn_out,
+                                    const rn_roi_pool *rois, int mode);
 /* Run one forward, then time every tile candidate of every convolution at batch B on the
  * device (events on the context's stream, on the buffers that forward used) and remember the fastest per layer for
  * that batch size.  Results do not change (candidates are bit-identical), only speed. */

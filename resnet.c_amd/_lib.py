@@ -51,6 +51,15 @@ class FpnOutputs(ctypes.Structure):
     _fields_ = [("level", c_void_p * 5)]
 
 
+class RoiPool(ctypes.Structure):
+    """rn_roi_pool: the RoIs (device [K,5]), the image size, the neck's levels the pooler reads, its parameters and
+    the outputs pooled [K,a,PH,PW] fp32 and levels_out int32 [K] (or NULL)."""
+    _fields_ = [("rois_dev", c_void_p), ("K", c_uint64), ("image_h", c_uint64), ("image_w", c_uint64),
+                ("n_levels", c_int), ("level", c_int * 4), ("PH", c_uint64), ("PW", c_uint64),
+                ("sampling_ratio", c_int), ("aligned", c_int), ("canonical_scale", c_double),
+                ("canonical_level", c_int), ("pooled", c_void_p), ("levels_out", c_void_p)]
+
+
 class Epilogue(ctypes.Structure):
     _fields_ = [("scale", c_void_p), ("shift", c_void_p), ("residual", c_void_p),
                 ("relu", c_int)]
@@ -216,6 +225,15 @@ SIGNATURES = {
                                      POINTER(FpnOutputs), c_int]),
     "rn_model_forward_fpn_u8": (c_int, [c_void_p, c_void_p, c_void_p, u64, POINTER(ModelOutputs), POINTER(c_int),
                                         POINTER(FpnOutputs), c_int]),
+    "rn_roi_level_thresholds": (c_int, [u64, POINTER(c_float), c_double, c_int, POINTER(c_float)]),
+    "rn_roi_align_forward_dt": (c_int, [c_void_p, c_int, u64, POINTER(c_void_p), POINTER(u64), POINTER(u64), POINTER(c_float),
+                                        POINTER(c_float), u64, u64, c_void_p, u64, u64, u64, c_int, c_int, c_void_p, c_void_p]),
+    "rn_fpn_forward_rois": (c_int, [c_void_p, POINTER(c_void_p), u64, POINTER(u64), POINTER(u64), POINTER(c_void_p),
+                                    POINTER(RoiPool)]),
+    "rn_model_forward_rois": (c_int, [c_void_p, c_void_p, fptr, u64, POINTER(ModelOutputs), POINTER(c_int),
+                                      POINTER(FpnOutputs), POINTER(RoiPool), c_int]),
+    "rn_model_forward_rois_u8": (c_int, [c_void_p, c_void_p, c_void_p, u64, POINTER(ModelOutputs), POINTER(c_int),
+                                         POINTER(FpnOutputs), POINTER(RoiPool), c_int]),
     "rn_model_destroy": (c_int, [c_void_p]),
     "rn_model_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, u64]),
     "rn_model_load_dir": (c_int, [c_void_p, c_char_p]),

@@ -2,6 +2,7 @@
 // (rn_upsample_nearest_add_forward_dt: dst = lat + nearest_upsample(top), or the plain nearest upsample), and the
 // neck itself as an object over the library's own contractions, max-pool and export (rn_fpn_*).  The reference
 // classifies whole images only; nothing here has a counterpart in it.
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -409,28 +410,120 @@ int rn_fpn_step(rn_fpn *f, rn_ctx *ctx, int kind, int level, const void *x_nhwc,
     }
 }
 
-int rn_fpn_forward(rn_fpn *f, const void *const *x_nhwc, uint64_t B, const uint64_t *h, const uint64_t *w,
-                   float *const *out_nchw)
+// ---- the pooler behind the neck (rn_roi.hip's kernel on the 3x3 outputs, in place) ----
+
+int rn_fpn_roi_check(const rn_fpn *f, rn_ctx *ctx, const rn_roi_pool *rp, const uint64_t *h, const uint64_t *w,
+                     float scales[4], float thr[3])
 {
+    RN_REQUIRE(ctx, rp, "the pooler's request is NULL");
+    RN_REQUIRE(ctx, rp->n_levels >= 1 && rp->n_levels <= f->n, "the pooler reads 1 .. n_levels of the neck's levels");
+    for (int i = 0; i < rp->n_levels; ++i)
+        RN_REQUIRE(ctx, rp->level[i] >= 0 && rp->level[i] < f->n && (i == 0 || rp->level[i] > rp->level[i - 1]),
+                   "the pooler's levels must be the neck's (0 .. n_levels - 1, the pool is none), ascending");
+    RN_REQUIRE(ctx, rp->image_h >= 1 && rp->image_w >= 1, "image_h and image_w must be >= 1");
+    RN_REQUIRE(ctx, rp->PH >= 1 && rp->PH <= 32 && rp->PW >= 1 && rp->PW <= 32, "PH and PW must be 1..32");
+    if (rp->sampling_ratio <= 0)
+        return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "%s: sampling_ratio <= 0 (adaptive grids) is not carried", __func__);
+    RN_REQUIRE(ctx, rp->sampling_ratio <= 4, "sampling_ratio must be 1..4");
+    RN_REQUIRE(ctx, rp->aligned == 0 || rp->aligned == 1, "aligned must be 0 or 1");
+    RN_REQUIRE(ctx, rp->canonical_scale > 0.0, "canonical_scale must be positive");
+    RN_REQUIRE(ctx, rp->K < (1ull << 31), "K must be below 2^31");
+    RN_REQUIRE(ctx, rp->K == 0 || rp->rois_dev, "rois_dev is NULL (K > 0)");
+    RN_REQUIRE(ctx, rp->K == 0 || rp->pooled, "pooled is NULL (K > 0)");
+    RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(rp->rois_dev) & 3) == 0 && (reinterpret_cast<uintptr_t>(rp->pooled) & 3) == 0 &&
+                        (reinterpret_cast<uintptr_t>(rp->levels_out) & 3) == 0,
+               "rois_dev, pooled or levels_out is off a 4-byte boundary");
+    const uint64_t out_bytes = rp->K * f->a * rp->PH * rp->PW * sizeof(float);
+    RN_REQUIRE(ctx, rp->K == 0 || !rn_overlap(rp->pooled, out_bytes, rp->rois_dev, rp->K * 5 * sizeof(float)),
+               "pooled overlaps rois_dev");
+    RN_REQUIRE(ctx, rp->K == 0 || !rp->levels_out ||
+                        (!rn_overlap(rp->levels_out, rp->K * 4, rp->pooled, out_bytes) &&
+                         !rn_overlap(rp->levels_out, rp->K * 4, rp->rois_dev, rp->K * 5 * sizeof(float))),
+               "levels_out overlaps pooled or rois_dev");
+    // torchvision's infer_scale: the power of two nearest the level's height over the image's (it returns the first of
+    // the two axes' scales)
+    (void)w;
+    for (int i = 0; i < rp->n_levels; ++i)
+        scales[i] = (float)exp2(rint(log2((double)h[rp->level[i]] / (double)rp->image_h)));
+    if (rn_roi_level_thresholds((uint64_t)rp->n_levels, scales, rp->canonical_scale, rp->canonical_level, thr) != RN_OK)
+        return rn_set_error(ctx, RN_ERR_INVALID, "%s: the level thresholds cannot be formed", __func__);
+    return RN_OK;
+}
+
+int rn_fpn_roi_step(rn_fpn *f, rn_ctx *ctx, const rn_roi_pool *rp, const float *scales, const float *thr,
+                    uint64_t sub0, uint64_t img0, uint64_t B, uint64_t images, const uint64_t *h, const uint64_t *w)
+{
+    const void *maps[kFpnMaxLevels];
+    uint64_t hs[kFpnMaxLevels], ws[kFpnMaxLevels];
+    if (rp->K == 0) return RN_OK;
+    for (int i = 0; i < rp->n_levels; ++i) {
+        const int l = rp->level[i];
+        if ((sub0 + B) * h[l] * w[l] > f->cap_pix[l]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn: scratch not reserved");
+        maps[i] = f->outb[l] + sub0 * h[l] * w[l] * f->a, hs[i] = h[l], ws[i] = w[l];
+    }
+    return rn_roi_align_window(ctx, RN_DTYPE_F32, (uint64_t)rp->n_levels, maps, hs, ws, scales, thr, images, img0, B,
+                               img0 == 0, f->a, rp->rois_dev, rp->K, rp->PH, rp->PW, rp->sampling_ratio, rp->aligned,
+                               rp->pooled, rp->levels_out);
+}
+
+int rn_fpn_roi_clear_of(const rn_fpn *f, rn_ctx *ctx, const rn_roi_pool *rp, const void *other, uint64_t other_bytes)
+{
+    if (!rp || rp->K == 0 || !other || other_bytes == 0) return RN_OK;
+    const uint64_t out_bytes = rp->K * f->a * rp->PH * rp->PW * sizeof(float);
+    RN_REQUIRE(ctx, !rn_overlap(rp->pooled, out_bytes, other, other_bytes), "pooled overlaps another output of the call");
+    RN_REQUIRE(ctx, !rp->levels_out || !rn_overlap(rp->levels_out, rp->K * 4, other, other_bytes),
+               "levels_out overlaps another output of the call");
+    RN_REQUIRE(ctx, !rn_overlap(rp->rois_dev, rp->K * 5 * sizeof(float), other, other_bytes),
+               "rois_dev overlaps an output of the call");
+    return RN_OK;
+}
+
+namespace {
+
+// a refusal of fpn_forward names the entry point that was called
+#define FPN_REQUIRE(cond, msg)                                                       \
+    do {                                                                             \
+        if (!(cond)) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s", fn, (msg)); \
+    } while (0)
+
+// rn_fpn_forward (fn names it; rp NULL, out_nchw needed) and rn_fpn_forward_rois (rp needed, out_nchw may be NULL)
+int fpn_forward(const char *fn, bool with_rois, rn_fpn *f, const void *const *x_nhwc, uint64_t B, const uint64_t *h,
+                const uint64_t *w, float *const *out_nchw, const rn_roi_pool *rp)
+{
+    static float *const none[kFpnMaxLevels + 1] = {NULL, NULL, NULL, NULL, NULL};
     if (!f) return RN_ERR_INVALID;
     rn_ctx *ctx = f->ctx;
     RN_ENTER(ctx);
-    RN_REQUIRE(ctx, f->finalized, "the neck is not finalized");
-    RN_REQUIRE(ctx, x_nhwc && h && w && out_nchw, "x_nhwc, h, w or out_nchw is NULL");
+    FPN_REQUIRE(f->finalized, "the neck is not finalized");
+    FPN_REQUIRE(x_nhwc && h && w && (out_nchw || with_rois), "x_nhwc, h, w or out_nchw is NULL");
+    FPN_REQUIRE(rp || !with_rois, "rois is NULL");
+    if (!out_nchw) out_nchw = none;
     const int n = f->n, n_out = n + f->extra;
-    bool wanted = false;
+    bool wanted = rp != NULL;
     for (int i = 0; i < n; ++i) {
-        RN_REQUIRE(ctx, x_nhwc[i], "a level's map is NULL");
-        RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(x_nhwc[i]) & 15) == 0, "a level's map is off a 16-byte boundary");
-        RN_REQUIRE(ctx, h[i] >= 1 && w[i] >= 1, "h and w must be >= 1");
-        RN_REQUIRE(ctx, h[i] < (1ull << 31) && w[i] < (1ull << 31) && B < (1ull << 31) && B * h[i] * w[i] < (1ull << 31),
-                   "B * h * w must be below 2^31");
+        FPN_REQUIRE(x_nhwc[i], "a level's map is NULL");
+        FPN_REQUIRE((reinterpret_cast<uintptr_t>(x_nhwc[i]) & 15) == 0, "a level's map is off a 16-byte boundary");
+        FPN_REQUIRE(h[i] >= 1 && w[i] >= 1, "h and w must be >= 1");
+        FPN_REQUIRE(h[i] < (1ull << 31) && w[i] < (1ull << 31) && B < (1ull << 31) && B * h[i] * w[i] < (1ull << 31),
+                    "B * h * w must be below 2^31");
     }
     for (int i = 0; i < n_out; ++i) {
-        RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(out_nchw[i]) & 3) == 0, "an output is off a 4-byte boundary");
+        FPN_REQUIRE((reinterpret_cast<uintptr_t>(out_nchw[i]) & 3) == 0, "an output is off a 4-byte boundary");
         wanted = wanted || out_nchw[i];
     }
-    RN_REQUIRE(ctx, wanted, "nothing wanted (every output is NULL)");
+    FPN_REQUIRE(wanted, "nothing wanted (every output is NULL)");
+    float scales[kFpnMaxLevels], thr[kFpnMaxLevels - 1];
+    bool reads[kFpnMaxLevels] = {false, false, false, false};
+    if (rp) {
+        RN_TRY(rn_fpn_roi_check(f, ctx, rp, h, w, scales, thr));
+        for (int i = 0; i < rp->n_levels; ++i) reads[rp->level[i]] = rp->K > 0;
+        for (int i = 0; i < n_out; ++i) {  // the pooler's buffers against every exported level
+            uint64_t H = 0, W = 0;
+            const int l = i < n ? i : n - 1;
+            RN_TRY(rn_fpn_level_shape(f, i, h[l], w[l], NULL, &H, &W));
+            RN_TRY(rn_fpn_roi_clear_of(f, ctx, rp, out_nchw[i], B * f->a * H * W * sizeof(float)));
+        }
+    }
     if (B == 0) return RN_OK;
     RN_TRY(rn_fpn_reserve(f, B, h, w));
     const int saved_layout = ctx->layout;
@@ -440,12 +533,29 @@ int rn_fpn_forward(rn_fpn *f, const void *const *x_nhwc, uint64_t B, const uint6
     for (int i = 0; i < n && st == RN_OK; ++i) st = rn_fpn_step(f, ctx, RN_FPN_INNER, i, x_nhwc[i], 0, B, h, w, NULL);
     for (int i = n - 1; i >= 1 && st == RN_OK; --i) st = rn_fpn_step(f, ctx, RN_FPN_TOPDOWN, i, NULL, 0, B, h, w, NULL);
     for (int i = 0; i < n && st == RN_OK; ++i)
-        if (out_nchw[i] || (pool && i == n - 1)) st = rn_fpn_step(f, ctx, RN_FPN_LAYER, i, NULL, 0, B, h, w, NULL);
+        if (out_nchw[i] || (pool && i == n - 1) || reads[i]) st = rn_fpn_step(f, ctx, RN_FPN_LAYER, i, NULL, 0, B, h, w, NULL);
     if (pool && st == RN_OK) st = rn_fpn_step(f, ctx, RN_FPN_POOL, n - 1, NULL, 0, B, h, w, NULL);
     for (int i = 0; i < n_out && st == RN_OK; ++i)
         if (out_nchw[i]) st = rn_fpn_step(f, ctx, RN_FPN_EXPORT, i, NULL, 0, B, h, w, out_nchw[i]);
+    if (rp && st == RN_OK) st = rn_fpn_roi_step(f, ctx, rp, scales, thr, 0, 0, B, B, h, w);
     ctx->layout = saved_layout;
     return st;
+}
+
+#undef FPN_REQUIRE
+
+}  // namespace
+
+int rn_fpn_forward(rn_fpn *f, const void *const *x_nhwc, uint64_t B, const uint64_t *h, const uint64_t *w,
+                   float *const *out_nchw)
+{
+    return fpn_forward(__func__, false, f, x_nhwc, B, h, w, out_nchw, NULL);
+}
+
+int rn_fpn_forward_rois(rn_fpn *f, const void *const *x_nhwc, uint64_t B, const uint64_t *h, const uint64_t *w,
+                        float *const *out_nchw, const rn_roi_pool *rois)
+{
+    return fpn_forward(__func__, true, f, x_nhwc, B, h, w, out_nchw, rois);
 }
 
 }  // extern "C"

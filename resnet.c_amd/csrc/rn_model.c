@@ -185,6 +185,11 @@ struct rn_model {
     const rn_fpn_outputs *fpn_out;
     int fpn_n, fpn_extra, fpn_stage[4];
     uint64_t fpn_a, fpn_h[4], fpn_w[4];
+    /* rn_model_forward_rois: the pooler behind that neck (NULL in every other forward), its levels' scales and
+     * thresholds, the images of the whole call */
+    const rn_roi_pool *roi;
+    float roi_scales[4], roi_thr[3];
+    uint64_t roi_images;
     /* tile tuning: calls of the last forward, and the batch size the tiles were tuned for */
     rn_conv_call *calls;
     int n_calls, cap_calls, recording;
@@ -1498,10 +1503,12 @@ static int op_fpn_rest(rn_model *m, uint64_t B)
     const int n = m->fpn_n;
     float *const *out = m->fpn_out->level;
     const int pool = m->fpn_extra && out[n];
-    int j;
+    int j, reads[4] = {0, 0, 0, 0};
+    if (m->roi && m->roi->K > 0)
+        for (j = 0; j < m->roi->n_levels; ++j) reads[m->roi->level[j]] = 1;
     for (j = n - 1; j >= 1; --j) TRY(op_fpn(m, RN_FPN_TOPDOWN, j, kFpnTopdownOps[j], NULL, B, NULL));
     for (j = 0; j < n; ++j)
-        if (out[j] || (pool && j == n - 1)) TRY(op_fpn(m, RN_FPN_LAYER, j, kFpnLayerOps[j], NULL, B, NULL));
+        if (out[j] || (pool && j == n - 1) || reads[j]) TRY(op_fpn(m, RN_FPN_LAYER, j, kFpnLayerOps[j], NULL, B, NULL));
     if (pool) TRY(op_fpn(m, RN_FPN_POOL, n - 1, "fpn_pool", NULL, B, NULL));
     for (j = 0; j <= n; ++j) {
         uint64_t H, W;
@@ -1509,6 +1516,17 @@ static int op_fpn_rest(rn_model *m, uint64_t B)
         TRY(rn_fpn_level_shape(m->fpn, j, m->fpn_h[j < n ? j : n - 1], m->fpn_w[j < n ? j : n - 1], NULL, &H, &W));
         TRY(op_fpn(m, RN_FPN_EXPORT, j, j < n ? kFpnExportOps[j] : "fpn_export_pool", NULL, B,
                    out[j] + m->run.img0 * m->fpn_a * H * W));
+    }
+    if (m->roi && m->roi->K > 0) {
+        /* bytes: the outputs only.  What the RoIs gather is several times that (profiles/roi_align) but depends on every
+         * box's size against its level, which the host does not look at: the record's GB/s is the OUTPUT rate */
+        const double outs = (double)(m->roi->K * m->fpn_a * m->roi->PH * m->roi->PW);
+        const double share = (double)B / (double)m->roi_images; /* the RoIs are taken as spread evenly over the images */
+        const double taps = 4.0 * (double)(m->roi->sampling_ratio * m->roi->sampling_ratio);
+        TRY(prof_begin(m, "roi_align", "fpn", share * outs * 2.0 * taps, share * outs * 4.0));
+        TRY(rn_fpn_roi_step(m->fpn, m->run.ctx, m->roi, m->roi_scales, m->roi_thr, m->run.sub0, m->run.img0, B,
+                            m->roi_images, m->fpn_h, m->fpn_w));
+        TRY(prof_end(m));
     }
     return RN_OK;
 }
@@ -1887,8 +1905,9 @@ int rn_model_forward_segment_u8(rn_model *m, rn_seg_head *hd, const uint8_t *inp
 /* rn_model_forward_fpn(_u8): like the maps, the request is state of this call alone -- set once every refusal has
  * passed, cleared on every way out (run_blocks asks m->fpn). */
 static int forward_fpn(rn_model *m, rn_fpn *fpn, const void *input, int in_u8, uint64_t B, const rn_model_outputs *outs,
-                       const int *stages, const rn_fpn_outputs *fo, int mode)
+                       const int *stages, const rn_fpn_outputs *fo, const rn_roi_pool *roi, int mode)
 {
+    static const rn_fpn_outputs no_levels = {{NULL, NULL, NULL, NULL, NULL}};
     rn_model_outputs none;
     const char *why = NULL;
     char msg[200];
@@ -1901,6 +1920,7 @@ static int forward_fpn(rn_model *m, rn_fpn *fpn, const void *input, int in_u8, u
         return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, msg);
     }
     if (!stages) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_fpn: stages is NULL");
+    if (!fo && roi) fo = &no_levels;
     if (!fo) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_fpn: fpn_out is NULL");
     rn_fpn_dims(fpn, &n, &extra, &a, cin);
     for (j = 0; j < n; ++j)
@@ -1923,7 +1943,23 @@ static int forward_fpn(rn_model *m, rn_fpn *fpn, const void *input, int in_u8, u
             return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, msg);
         }
     }
-    if (!wanted) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_fpn: nothing wanted (every level is NULL)");
+    if (!wanted && !roi)
+        return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_fpn: nothing wanted (every level is NULL)");
+    if (roi) {
+        TRY(rn_fpn_roi_check(fpn, m->ctx, roi, h, w, m->roi_scales, m->roi_thr));
+        for (j = 0; j < n + extra; ++j) { /* the pooler's buffers against every other output of the call */
+            uint64_t LH = 0, LW = 0;
+            TRY(rn_fpn_level_shape(fpn, j, h[j < n ? j : n - 1], w[j < n ? j : n - 1], NULL, &LH, &LW));
+            TRY(rn_fpn_roi_clear_of(fpn, m->ctx, roi, fo->level[j], B * a * LH * LW * sizeof(float)));
+        }
+        if (outs) {
+            TRY(rn_fpn_roi_clear_of(fpn, m->ctx, roi, outs->logits, B * m->classes * sizeof(float)));
+            TRY(rn_fpn_roi_clear_of(fpn, m->ctx, roi, outs->features, B * m->feat * sizeof(float)));
+            TRY(rn_fpn_roi_clear_of(fpn, m->ctx, roi, outs->probs, B * m->classes * sizeof(float)));
+            TRY(rn_fpn_roi_clear_of(fpn, m->ctx, roi, outs->topk_prob, B * outs->k * sizeof(float)));
+            TRY(rn_fpn_roi_clear_of(fpn, m->ctx, roi, outs->topk_idx, B * outs->k * sizeof(uint64_t)));
+        }
+    }
     if (!input || B == 0 || (mode != RN_FWD_REFERENCE_OPS && mode != RN_FWD_FUSED)) return RN_ERR_INVALID;
     if (m->dtype != RN_DTYPE_F32 && mode != RN_FWD_FUSED)
         return rn_ctx_set_error(m->ctx, RN_ERR_UNSUPPORTED, "rn_model_forward_fpn: a bf16 model runs RN_FWD_FUSED only");
@@ -1932,11 +1968,14 @@ static int forward_fpn(rn_model *m, rn_fpn *fpn, const void *input, int in_u8, u
     if (!outs) outs = &none;
     m->fpn = fpn;
     m->fpn_out = fo;
+    m->roi = roi;
+    m->roi_images = B;
     m->fpn_n = n, m->fpn_extra = extra, m->fpn_a = a;
     for (j = 0; j < n; ++j) m->fpn_stage[j] = stages[j], m->fpn_h[j] = h[j], m->fpn_w[j] = w[j];
     st = forward_outputs(m, input, in_u8, B, outs->logits, outs, mode, 0);
     m->fpn = NULL;
     m->fpn_out = NULL;
+    m->roi = NULL;
     m->maps_done = 0;
     return st;
 }
@@ -1944,13 +1983,27 @@ static int forward_fpn(rn_model *m, rn_fpn *fpn, const void *input, int in_u8, u
 int rn_model_forward_fpn(rn_model *m, rn_fpn *fpn, const float *input_nchw, uint64_t B, const rn_model_outputs *outs,
                          const int *stages, const rn_fpn_outputs *fpn_out, int mode)
 {
-    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, mode);
+    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, NULL, mode);
 }
 
 int rn_model_forward_fpn_u8(rn_model *m, rn_fpn *fpn, const uint8_t *input_nhwc, uint64_t B, const rn_model_outputs *outs,
                             const int *stages, const rn_fpn_outputs *fpn_out, int mode)
 {
-    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, mode);
+    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, NULL, mode);
+}
+
+int rn_model_forward_rois(rn_model *m, rn_fpn *fpn, const float *input_nchw, uint64_t B, const rn_model_outputs *outs,
+                          const int *stages, const rn_fpn_outputs *fpn_out, const rn_roi_pool *rois, int mode)
+{
+    if (m && !rois) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_rois: rois is NULL");
+    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, rois, mode);
+}
+
+int rn_model_forward_rois_u8(rn_model *m, rn_fpn *fpn, const uint8_t *input_nhwc, uint64_t B, const rn_model_outputs *outs,
+                             const int *stages, const rn_fpn_outputs *fpn_out, const rn_roi_pool *rois, int mode)
+{
+    if (m && !rois) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_rois: rois is NULL");
+    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, rois, mode);
 }
 
 /* The decoded-image route resizes to 256 and crops 224 x 224: a model of another size refuses it. */

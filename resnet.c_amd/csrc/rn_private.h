@@ -88,6 +88,28 @@ void rn_fpn_cost(const rn_fpn *fpn, int kind, int level, uint64_t B, const uint6
 int rn_fpn_step(rn_fpn *fpn, rn_ctx *ctx, int kind, int level, const void *x_nhwc, uint64_t img0, uint64_t B,
                 const uint64_t *h, const uint64_t *w, float *dst_nchw);
 
+/* ---- rn_roi.hip / rn_fpn.hip: the pooler behind a neck ---- */
+/* rn_roi_align_forward_dt's launch, no checks, for a window of the batch: the maps start at image img_lo and hold
+ * img_cnt images; image indices 0 .. images - 1 are valid.  The launch writes the rows of the RoIs whose image is in
+ * its window and, with write_invalid, the rows of zeros of the RoIs whose index is invalid; every other row it leaves
+ * to the launch of another window. */
+int rn_roi_align_window(rn_ctx *ctx, int dtype, uint64_t n_levels, const void *const *x_nhwc, const uint64_t *h,
+                        const uint64_t *w, const float *scales, const float *thr, uint64_t images, uint64_t img_lo,
+                        uint64_t img_cnt, int write_invalid, uint64_t C, const float *rois_dev, uint64_t K, uint64_t PH,
+                        uint64_t PW, int sampling_ratio, int aligned, float *out, int32_t *levels_out);
+/* a pooler's request against a neck whose level i is an h[i] x w[i] map: every refusal of rn_fpn_forward_rois that
+ * concerns the pooler (text in ctx); scales and thr: the pooler's levels' scales (torchvision's infer_scale) and the
+ * thresholds between them */
+int rn_fpn_roi_check(const rn_fpn *fpn, rn_ctx *ctx, const rn_roi_pool *rp, const uint64_t *h, const uint64_t *w,
+                     float scales[4], float thr[3]);
+/* RN_ERR_INVALID with a text in ctx when the pooler's pooled, levels_out or rois_dev shares a byte with [other,
+ * other + other_bytes), another output of the same call (an exported level, a head output); NULL or 0 bytes: RN_OK */
+int rn_fpn_roi_clear_of(const rn_fpn *fpn, rn_ctx *ctx, const rn_roi_pool *rp, const void *other, uint64_t other_bytes);
+/* the pooler's launch on ctx for the B images from the caller's image img0 on, whose 3x3 outputs start sub0 images
+ * into the neck's scratch; images: the batch of the whole forward.  The launch of img0 == 0 writes the invalid rows. */
+int rn_fpn_roi_step(rn_fpn *fpn, rn_ctx *ctx, const rn_roi_pool *rp, const float *scales, const float *thr,
+                    uint64_t sub0, uint64_t img0, uint64_t B, uint64_t images, const uint64_t *h, const uint64_t *w);
+
 /* ---- rn_stem.hip ---- */
 /* 1 when the fused stem + max-pool launch takes a padded image of Hp x Wp (nchw: the NCHW-fetching form on
  * an image of Hp - 6 x Wp - 6) of `dtype`: its documented conditions on the geometry alone */

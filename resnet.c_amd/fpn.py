@@ -3,7 +3,9 @@
 Key shapes (``fpn_shapes``), seeded weights (``generate_fpn_state``), the split of a torchvision detection state dict
 (``split_state``), the float64 restatement of what the device computes (``fpn_ref``) and ``FeaturePyramidNetwork``,
 the Python face of ``rn_fpn_*``.  ``NativeModel.forward_fpn`` runs a neck inside a forward: every lateral 1x1 right
-behind its stage, the rest behind layer4.  ``ops.upsample_nearest_add`` is the top-down launch alone.
+behind its stage, the rest behind layer4.  ``ops.upsample_nearest_add`` is the top-down launch alone.  With RoIs and a
+``roi.MultiScaleRoIAlign`` both forwards also pool the regions from the neck's own fp32 outputs (``rn_fpn_forward_rois``,
+``rn_model_forward_rois``).
 """
 from __future__ import annotations
 
@@ -152,10 +154,15 @@ class FeaturePyramidNetwork:
                                            ctypes.byref(h), ctypes.byref(w)), "rn_fpn_level_shape", self.ctx.handle)
         return int(c.value), int(h.value), int(w.value)
 
-    def forward(self, maps_nhwc, levels=None) -> Dict[str, np.ndarray]:
+    def forward(self, maps_nhwc, levels=None, *, rois=None, pooler=None, image_size=None, roi_levels: bool = False,
+                validate: bool = True) -> Dict[str, np.ndarray]:
         """maps_nhwc: one host array [B,h_i,w_i,in_i] fp32 per level, finest first (a bf16 neck rounds them on upload;
         uint16 bf16 bit patterns are taken as they are) -> {"0": [B,a,h_0,w_0] fp32, ..., "pool": ...}, the names in
-        `levels` only (default: all).  Synchronous convenience."""
+        `levels` only (default: all).  With rois ([K,5] fp32: image index, x1, y1, x2, y2 in pixels of the input image),
+        a pooler (roi.MultiScaleRoIAlign) and image_size (H, W): rn_fpn_forward_rois, which adds "pooled" [K,a,PH,PW]
+        fp32 and, with roi_levels, "roi_levels" int32 [K]; levels may then be empty.  A RoI whose image index is no
+        integer in [0, B) raises ValueError (validate=False hands it to the device, which answers zeros and level -1).
+        Synchronous convenience."""
         from .ops import _down_raw, _up_raw, to_bf16_bits
         from .tensor import _DeviceBuffer
         n = len(self.in_channels_list)
@@ -164,6 +171,8 @@ class FeaturePyramidNetwork:
         for name in levels:
             if name not in self.names:
                 raise ValueError(f"unknown level {name!r}: one of {self.names}")
+        if (rois is None) != (pooler is None) or (rois is not None and image_size is None):
+            raise ValueError("rois, pooler and image_size go together")
         xs = []
         for x, c in zip(maps_nhwc, self.in_channels_list):
             x = np.asarray(x)
@@ -184,11 +193,26 @@ class FeaturePyramidNetwork:
                 bufs[name] = _DeviceBuffer(self.ctx, max(int(np.prod(shapes[name])) * 4, 16))
         xp = (ctypes.c_void_p * n)(*[d.ptr for d in dx])
         op = (ctypes.c_void_p * len(self.names))(*[bufs[name].ptr if name in bufs else None for name in self.names])
-        L.check(L.lib().rn_fpn_forward(self.handle, xp, B, (ctypes.c_uint64 * n)(*hs), (ctypes.c_uint64 * n)(*ws), op),
-                "rn_fpn_forward", self.ctx.handle)
+        hp, wp = (ctypes.c_uint64 * n)(*hs), (ctypes.c_uint64 * n)(*ws)
+        if rois is None:
+            L.check(L.lib().rn_fpn_forward(self.handle, xp, B, hp, wp, op), "rn_fpn_forward", self.ctx.handle)
+        else:
+            from . import roi as R
+            drois, K = R.upload_rois(rois, B, validate)
+            PH, PW = pooler.output_size
+            pooled = _DeviceBuffer(self.ctx, max(K * self.out_channels * PH * PW * 4, 16))
+            lv = _DeviceBuffer(self.ctx, max(K * 4, 16)) if roi_levels else None
+            req = pooler.request(self.names, drois.ptr, K, image_size, pooled.ptr, lv.ptr if lv else None)
+            L.check(L.lib().rn_fpn_forward_rois(self.handle, xp, B, hp, wp, op, ctypes.byref(req)), "rn_fpn_forward_rois",
+                    self.ctx.handle)
         self.ctx.sync()
-        return {name: _down_raw(bufs[name], np.float32, int(np.prod(shapes[name]))).reshape(shapes[name])
-                for name in self.names if name in bufs}
+        out = {name: _down_raw(bufs[name], np.float32, int(np.prod(shapes[name]))).reshape(shapes[name])
+               for name in self.names if name in bufs}
+        if rois is not None:
+            out["pooled"] = _down_raw(pooled, np.float32, K * self.out_channels * PH * PW).reshape(K, self.out_channels, PH, PW)
+            if roi_levels:
+                out["roi_levels"] = _down_raw(lv, np.int32, K)
+        return out
 
     def close(self) -> None:
         if self.handle:

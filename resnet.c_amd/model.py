@@ -457,14 +457,20 @@ class NativeModel:
         return self.forward_segment(np.ascontiguousarray(px, dtype=np.uint8), head, **kw)
 
     def forward_fpn(self, x: np.ndarray, neck, stages=STAGES, levels=None, *, logits: bool = False,
-                    features: bool = False, probs: bool = False, topk: int = 0, fused: bool = True) -> dict:
+                    features: bool = False, probs: bool = False, topk: int = 0, fused: bool = True, rois=None,
+                    pooler=None, roi_levels: bool = False, validate: bool = True) -> dict:
         """One forward with a feature pyramid neck (rn_model_forward_fpn; torchvision's resnet_fpn_backbone): an
         ordered dict "0", "1", .. (one per stage in `stages`, finest first), then "pool" when the neck has the extra
         block -> [B,a,H,W] fp32; then the head outputs asked for, as forward_outputs returns them.  neck: an
         fpn.FeaturePyramidNetwork of this model's dtype on this model's context whose in_channels_list is the
         channels of `stages`.  levels: the names wanted (default: all).  x: fp32 NCHW [B,3,H,W], or uint8 NHWC
         [B,H,W,3].  An unknown, repeated or descending stage, a stage count that is not the neck's, or an unknown
-        level raises ValueError."""
+        level raises ValueError.
+        With rois ([K,5] fp32: image index, x1, y1, x2, y2 in pixels of the model's input) and a pooler
+        (roi.MultiScaleRoIAlign): rn_model_forward_rois, the same launches plus the pooler's behind the neck, which
+        adds "pooled" [K,a,PH,PW] fp32 and, with roi_levels, "roi_levels" int32 [K]; levels may then be empty.  A RoI
+        whose image index is no integer in [0, B) raises ValueError (validate=False hands it to the device: zeros
+        and level -1)."""
         from .ops import _down_raw, _up_raw
         from .tensor import _DeviceBuffer
         stages = tuple(stages)
@@ -506,9 +512,24 @@ class NativeModel:
         o = L.ModelOutputs(buf("logits", logits, B * C * 4), buf("features", features, B * F * 4),
                            buf("probs", probs, B * C * 4), buf("topk_prob", k > 0, B * k * 4),
                            buf("topk_idx", k > 0, B * k * 8), k)
-        fn = L.lib().rn_model_forward_fpn_u8 if u8 else L.lib().rn_model_forward_fpn
-        L.check(fn(self.handle, neck.handle, xin.ptr, B, ctypes.byref(o), (ctypes.c_int * len(idx))(*idx), ctypes.byref(fo),
-                   L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS), "rn_model_forward_fpn", self.ctx.handle)
+        if (rois is None) != (pooler is None):
+            raise ValueError("rois and pooler go together")
+        mode = L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS
+        stage_arr = (ctypes.c_int * len(idx))(*idx)
+        if rois is None:
+            fn = L.lib().rn_model_forward_fpn_u8 if u8 else L.lib().rn_model_forward_fpn
+            L.check(fn(self.handle, neck.handle, xin.ptr, B, ctypes.byref(o), stage_arr, ctypes.byref(fo), mode),
+                    "rn_model_forward_fpn", self.ctx.handle)
+        else:
+            from . import roi as R
+            drois, K = R.upload_rois(rois, B, validate)
+            PH, PW = pooler.output_size
+            pooled = _DeviceBuffer(self.ctx, max(K * neck.out_channels * PH * PW * 4, 16))
+            lv = _DeviceBuffer(self.ctx, max(K * 4, 16)) if roi_levels else None
+            req = pooler.request(names, drois.ptr, K, self.input_size, pooled.ptr, lv.ptr if lv else None)
+            fn = L.lib().rn_model_forward_rois_u8 if u8 else L.lib().rn_model_forward_rois
+            L.check(fn(self.handle, neck.handle, xin.ptr, B, ctypes.byref(o), stage_arr, ctypes.byref(fo), ctypes.byref(req),
+                       mode), "rn_model_forward_rois", self.ctx.handle)
         self.ctx.sync()
         shapes.update({"logits": (B, C), "features": (B, F), "probs": (B, C), "topk_prob": (B, k), "topk_idx": (B, k)})
         out = {name: _down_raw(lbufs[name], np.float32, int(np.prod(shapes[name]))).reshape(shapes[name])
@@ -518,6 +539,10 @@ class NativeModel:
                 out[name] = _down_raw(b, np.uint64, B * k).astype(np.int64).reshape(B, k)
             else:
                 out[name] = _down_raw(b, np.float32, int(np.prod(shapes[name]))).reshape(shapes[name])
+        if rois is not None:
+            out["pooled"] = _down_raw(pooled, np.float32, K * neck.out_channels * PH * PW).reshape(K, neck.out_channels, PH, PW)
+            if roi_levels:
+                out["roi_levels"] = _down_raw(lv, np.int32, K)
         return out
 
     def forward_fpn_u8(self, px: np.ndarray, neck, stages=STAGES, levels=None, **kw) -> dict:

@@ -937,3 +937,162 @@ def upsample_nearest_add(top, lat=None, size=None) -> np.ndarray:
 def upsample_nearest_add_bf16(top, lat=None, size=None) -> np.ndarray:
     """The bf16 form of upsample_nearest_add: uint16 bit patterns in (to_bf16_bits of fp32 data) and out, C % 8 == 0."""
     return _upsample_nearest_add(L.RN_DTYPE_BF16, np.uint16, top, lat, size)
+
+
+# ---------------------------------------------------------------------------
+# RoIAlign over a pyramid (rn_roi_align_forward_dt)
+# ---------------------------------------------------------------------------
+def roi_level_thresholds(scales, canonical_scale: float = 224.0, canonical_level: int = 4) -> np.ndarray:
+    """rn_roi_level_thresholds (host only): the len(scales) - 1 fp32 area thresholds between the levels of
+    torchvision's LevelMapper, thr[j] = (s0 * 2^(k_min + 1 + j - k0 - 1e-6))^2 in double, rounded up to fp32."""
+    sc = np.ascontiguousarray(scales, dtype=np.float32).reshape(-1)
+    thr = np.zeros(max(sc.size - 1, 1), dtype=np.float32)
+    st = L.lib().rn_roi_level_thresholds(sc.size, sc.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), float(canonical_scale),
+                                         int(canonical_level), thr.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+    if st != L.RN_OK:
+        raise ValueError(f"rn_roi_level_thresholds: 1..4 positive finite scales and a positive canonical scale, not {sc}")
+    return thr[:sc.size - 1]
+
+
+def roi_levels_ref(rois, thresholds, images: Optional[int] = None) -> np.ndarray:
+    """The level of every RoI as the kernel chooses it: area = (x2 - x1) * (y2 - y1) in fp32, level = the number of j
+    with area >= thresholds[j]; int32 [K].  images: a RoI whose image index is no integer in [0, images) gets -1."""
+    r = np.ascontiguousarray(rois, dtype=np.float32).reshape(-1, 5)
+    thr = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        area = (r[:, 3] - r[:, 1]) * (r[:, 4] - r[:, 2])
+        lv = (area[:, None] >= thr[None, :]).sum(axis=1).astype(np.int32)
+    if images is not None:
+        lv[~roi_image_valid(r, images)] = -1
+    return lv
+
+
+def roi_image_valid(rois, images: int) -> np.ndarray:
+    """Which RoIs name an image: the index is an integer in [0, images)."""
+    b = np.ascontiguousarray(rois, dtype=np.float32).reshape(-1, 5)[:, 0]
+    with np.errstate(invalid="ignore"):
+        return (b >= 0) & (b < np.float32(2147483648.0)) & (b == np.trunc(b)) & (b.astype(np.float64) < images)
+
+
+def _roi_axis(c, ok, n, ft):
+    """the contract's "One sample" along one axis on an array of coordinates: (low index, high index, l, h)"""
+    c = np.where(ok, c, ft(0))
+    c = np.where(c > 0, c, ft(0))
+    lo = c.astype(np.int64)
+    top = lo >= n - 1
+    lo = np.where(top, n - 1, lo)
+    hi = np.where(top, n - 1, lo + 1)
+    c = np.where(top, lo.astype(ft), c)
+    lw = (c - lo.astype(ft)).astype(ft)
+    return lo, hi, lw, (ft(1) - lw).astype(ft)
+
+
+def _roi_align_host(maps_nhwc, rois, scales, output_size, sampling_ratio, aligned, levels, ft):
+    """The contract of rn_roi_align_forward_dt in numpy, every operation in the float type ft and rounded on its own,
+    vectorised over the channels and the sample grid of a RoI.  maps_nhwc: [B,h,w,C] arrays of ft; levels: the level
+    of every RoI (-1: a row of zeros) -> [K,C,PH,PW] of ft."""
+    PH, PW = (int(output_size), int(output_size)) if np.ndim(output_size) == 0 else (int(output_size[0]), int(output_size[1]))
+    S = int(sampling_ratio)
+    rois = np.asarray(rois).reshape(-1, 5)
+    K, C = rois.shape[0], maps_nhwc[0].shape[3]
+    out = np.zeros((K, C, PH, PW), dtype=ft)
+    off = ft(0.5) if aligned else ft(0)
+    grid = lambda n: ((np.arange(n, dtype=ft)[:, None], (np.arange(S, dtype=ft) + ft(0.5))[None, :]))  # noqa: E731
+    (ph, sy), (pw, sx) = grid(PH), grid(PW)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for r in range(K):
+            lv = int(levels[r])
+            if lv < 0:
+                continue
+            m = maps_nhwc[lv]
+            h, w = m.shape[1], m.shape[2]
+            scale = ft(scales[lv])
+            b, x1, y1, x2, y2 = (ft(v) for v in rois[r])
+            x1s, y1s, x2s, y2s = x1 * scale - off, y1 * scale - off, x2 * scale - off, y2 * scale - off
+            rw, rh = ft(x2s - x1s), ft(y2s - y1s)
+            if not aligned:
+                rw, rh = (ft(1) if rw < 1 else rw), (ft(1) if rh < 1 else rh)
+            bin_h, bin_w = ft(rh / ft(PH)), ft(rw / ft(PW))
+            y = ((y1s + ph * bin_h) + (sy * bin_h) / ft(S)).astype(ft).reshape(-1)      # [PH*S]
+            x = ((x1s + pw * bin_w) + (sx * bin_w) / ft(S)).astype(ft).reshape(-1)      # [PW*S]
+            oky, okx = (y >= -1) & (y <= h), (x >= -1) & (x <= w)
+            ok = oky[:, None] & okx[None, :]
+            yl, yh, ly, hy = _roi_axis(y, oky, h, ft)
+            xl, xh, lx, hx = _roi_axis(x, okx, w, ft)
+            img = m[int(b)]
+            v1, v2 = img[yl][:, xl], img[yl][:, xh]
+            v3, v4 = img[yh][:, xl], img[yh][:, xh]
+            w1, w2 = (hy[:, None] * hx[None, :])[..., None], (hy[:, None] * lx[None, :])[..., None]
+            w3, w4 = (ly[:, None] * hx[None, :])[..., None], (ly[:, None] * lx[None, :])[..., None]
+            val = (w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4).reshape(PH, S, PW, S, C)
+            okg = ok.reshape(PH, S, PW, S)
+            acc = np.zeros((PH, PW, C), dtype=ft)
+            for iy in range(S):
+                for ix in range(S):
+                    acc = np.where(okg[:, iy, :, ix, None], acc + val[:, iy, :, ix], acc)
+            out[r] = (acc / ft(S * S)).transpose(2, 0, 1)
+    return out
+
+
+def roi_align_ref(maps_nhwc, rois, scales, output_size, sampling_ratio: int = 2, aligned: bool = False,
+                  thresholds=None, return_levels: bool = False):
+    """The contract of rn_roi_align_forward_dt in numpy fp32 (include/rn_hip.h states it): maps_nhwc one [B,h,w,C]
+    array per level, finest first, fp32 or uint16 bf16 bit patterns (widened exactly); rois [K,5] fp32 (image index,
+    x1, y1, x2, y2) -> [K,C,PH,PW] fp32, and with return_levels the int32 level of every RoI.  A RoI whose image index
+    is no integer in [0, B): zeros, level -1."""
+    maps = [np.asarray(m) for m in maps_nhwc]
+    maps = [from_bf16_bits(m).reshape(m.shape) if m.dtype == np.uint16 else np.ascontiguousarray(m, dtype=np.float32) for m in maps]
+    rois = np.ascontiguousarray(rois, dtype=np.float32).reshape(-1, 5)
+    if thresholds is None:
+        thresholds = roi_level_thresholds(scales)
+    levels = roi_levels_ref(rois, thresholds, images=maps[0].shape[0])
+    out = _roi_align_host(maps, rois, np.asarray(scales, dtype=np.float32), output_size, sampling_ratio, aligned, levels,
+                          np.float32)
+    return (out, levels) if return_levels else out
+
+
+def _roi_align(dtype, np_dtype, maps_nhwc, rois, scales, output_size, sampling_ratio, aligned, thresholds, return_levels):
+    from .tensor import _DeviceBuffer
+    ctx = get_ctx()
+    maps = [np.ascontiguousarray(m, dtype=np_dtype) for m in maps_nhwc]
+    n, (B, C) = len(maps), (maps[0].shape[0], maps[0].shape[3])
+    assert all(m.ndim == 4 and m.shape[0] == B and m.shape[3] == C for m in maps), [m.shape for m in maps]
+    rois = np.ascontiguousarray(rois, dtype=np.float32).reshape(-1, 5)
+    K = rois.shape[0]
+    if not roi_image_valid(rois, B).all():
+        raise ValueError(f"a RoI's image index is no integer in [0, {B})")
+    PH, PW = (int(output_size), int(output_size)) if np.ndim(output_size) == 0 else (int(output_size[0]), int(output_size[1]))
+    sc = np.ascontiguousarray(scales, dtype=np.float32).reshape(-1)
+    assert sc.size == n, (sc.size, n)
+    thr = roi_level_thresholds(sc) if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float32).reshape(-1)
+    assert thr.size == n - 1, (thr.size, n)
+    thr = np.concatenate([thr, np.zeros(1, np.float32)])       # never an empty array behind the pointer
+    dm, dr = [_up_raw(m) for m in maps], _up_raw(rois)
+    out = _DeviceBuffer(ctx, max(K * C * PH * PW * 4, 16))
+    lv = _DeviceBuffer(ctx, max(K * 4, 16)) if return_levels else None
+    fp = ctypes.POINTER(ctypes.c_float)
+    L.check(L.lib().rn_roi_align_forward_dt(
+        ctx.handle, dtype, n, (ctypes.c_void_p * n)(*[d.ptr for d in dm]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in maps]),
+        (ctypes.c_uint64 * n)(*[m.shape[2] for m in maps]), sc.ctypes.data_as(fp), thr.ctypes.data_as(fp), B, C, dr.ptr, K,
+        PH, PW, int(sampling_ratio), int(bool(aligned)), out.ptr, lv.ptr if lv else None), "rn_roi_align_forward_dt", ctx.handle)
+    ctx.sync()
+    pooled = _down_raw(out, np.float32, K * C * PH * PW).reshape(K, C, PH, PW)
+    return (pooled, _down_raw(lv, np.int32, K)) if return_levels else pooled
+
+
+def roi_align(maps_nhwc, rois, scales, output_size, sampling_ratio: int = 2, aligned: bool = False, thresholds=None,
+              return_levels: bool = False):
+    """rn_roi_align_forward_dt in fp32, one launch: host arrays maps_nhwc (one [B,h,w,C] per level, finest first,
+    C % 4 == 0), rois [K,5] (image index, x1, y1, x2, y2), scales per level -> [K,C,PH,PW] fp32, bit for bit
+    roi_align_ref; thresholds default to roi_level_thresholds(scales); return_levels: (pooled, int32 [K]).  A RoI
+    whose image index is no integer in [0, B) raises ValueError."""
+    return _roi_align(L.RN_DTYPE_F32, np.float32, maps_nhwc, rois, scales, output_size, sampling_ratio, aligned, thresholds,
+                      return_levels)
+
+
+def roi_align_bf16(maps_nhwc, rois, scales, output_size, sampling_ratio: int = 2, aligned: bool = False, thresholds=None,
+                   return_levels: bool = False):
+    """The bf16 form of roi_align: the maps are uint16 bit patterns (to_bf16_bits of fp32 data), C % 8 == 0; the
+    output is fp32."""
+    return _roi_align(L.RN_DTYPE_BF16, np.uint16, maps_nhwc, rois, scales, output_size, sampling_ratio, aligned, thresholds,
+                      return_levels)
