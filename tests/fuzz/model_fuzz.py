@@ -4,7 +4,8 @@ every switch that only reschedules the same arithmetic (streams, depth-first fro
 graph capture and replay, the host pipeline; NOT pair fusion or stem fusion, which fold the batch-norm
 scales into the weights / use another K padding and so round differently).  None of them may change a bit: every image's logits must
 equal the ones a plain forward of the whole pool gave at the start (batch invariance), whatever ran
-before -- arenas resized, scratch regrown, tiles tuned at another batch size.
+before -- arenas resized, scratch regrown, tiles tuned at another batch size.  Everything that changes the
+arithmetic key (input size, dilation) and every other forward kind: tests/fuzz/state_fuzz.py.
 
     python tests/fuzz/model_fuzz.py [--seconds 60] [--seed 0] [--dtype f32|bf16] [--arch resnet50]"""
 import argparse

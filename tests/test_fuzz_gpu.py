@@ -1,7 +1,8 @@
-"""Short runs of the randomised parity programs (tests/fuzz/conv_fuzz.py, ops_fuzz.py, model_fuzz.py) with
-fixed seeds: every convolution entry point over random shapes / layouts / storage types / tile
+"""Short runs of the randomised parity programs (tests/fuzz/conv_fuzz.py, ops_fuzz.py, model_fuzz.py, state_fuzz.py)
+with fixed seeds: every convolution entry point over random shapes / layouts / storage types / tile
 candidates against the CPU oracle, the element-wise / pooling / batch-norm / linear entry points, and
-the model driver's state machine (no switch that only reschedules the arithmetic may change a bit).
+the model driver's state machine (no switch that only reschedules the arithmetic may change a bit; no property
+switch, forward kind, held object or refusal may leave anything behind for the next call).
 The long runs (minutes, other seeds) are started by hand; these keep the paths exercised in every run
 of the suite.  Each tool exits non-zero with the failing case in its assertion message."""
 import os
@@ -13,6 +14,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "fuzz"))
+from state_fuzz import COMMITTED, PHRASE  # noqa: E402
 
 
 def run_tool(name, *args):
@@ -50,3 +53,13 @@ def test_view_fuzz_short():
     (tests/views.py)."""
     out = run_tool("view_fuzz.py", "--seconds", "8", "--seed", "105")
     assert "all guards clean" in out
+
+
+@pytest.mark.parametrize("arch,dtype,seed,steps", COMMITTED, ids=lambda v: str(v))
+def test_state_fuzz_short(arch, dtype, seed, steps):
+    """One model, one head of each kind, one neck and one pooler through property switches, every forward kind, held
+    graphs and pipelines and the documented refusals: every output bit for bit what a never-reconfigured model gives,
+    that model within the float64 bounds of the features' own tests.  The step counts give the coverage the tool
+    asserts; tests/test_state_fuzz_host.py checks that on the CPU."""
+    out = run_tool("state_fuzz.py", "--steps", str(steps), "--seed", str(seed), "--arch", arch, "--dtype", dtype)
+    assert PHRASE in out
