@@ -1043,6 +1043,129 @@ RN_API int rn_model_forward_rois(rn_model *m, rn_fpn *fpn, const float *input_nc
 RN_API int rn_model_forward_rois_u8(rn_model *m, rn_fpn *fpn, const uint8_t *input_nhwc, uint64_t B,
                                     const rn_model_outputs *outs, const int *stages, const rn_fpn_outputs *fpn_out,
                                     const rn_roi_pool *rois, int mode);
+/* ---- RPN proposals behind the head: top-k, box decode, NMS and the merge over the levels (rn_rpn.hip) ----------
+ * torchvision's RegionProposalNetwork in eval mode behind RPNHead (AnchorGenerator, BoxCoder.decode,
+ * filter_proposals), as three launches: rn_rpn_select_decode_forward (one) and rn_rpn_nms_merge_forward (two: the IoU
+ * mask, then the scan and the merge).  The arithmetic is a contract; every fp32 operation is rounded on its own and
+ * none is fused (rpn.py restates it in numpy).  min(a, b) is a > b ? b : a and max(a, b) is a < b ? b : a: a NaN in
+ * `a` stays.  L = 1..5 levels, finest first; A = 1..12 anchors per position, the same on every level; the image is
+ * H x W, a level h x w.
+ *   Anchors:  per level, sizes s_j and ratios r_i; hr = sqrtf(r), wr = 1 / hr; base anchor (i, j), at index
+ *             i * n_sizes + j, is rint((-wr*s, -hr*s, wr*s, hr*s) / 2), half to even, formed on the host in fp32:
+ *             base_anchors is that table, [L, A, 4].  Strides sh = H / h, sw = W / w, INTEGER division.  Anchor
+ *             n = (y*w + x)*A + a is base[a] + (x*sw, y*sh, x*sw, y*sh).
+ *   Head:     per level NHWC fp32 [B, h, w, P], P = 5A rounded up to a multiple of 4; channel a is the objectness
+ *             logit of anchor a, channel A + 4a + c is delta c of anchor a (torchvision's permute_and_flatten order).
+ *   Select:   per (image, level) the min(pre_nms_top_n, h*w*A) first anchors in rn_topk_forward's order: (v_i, i)
+ *             precedes (v_j, j) when v_i > v_j, or v_i == v_j and i < j; -0 == +0 and a NaN ranks as -inf.
+ *   Decode:   weights wx, wy, ww, wh (the RPN's: 1, 1, 1, 1), clip = (float)log(1000.0 / 16.0):
+ *             wa = ax2 - ax1; cx = ax1 + 0.5f*wa; dx = d0 / wx; dw = min(d2 / ww, clip); pcx = dx*wa + cx;
+ *             pw = expf(dw)*wa; x1 = pcx - 0.5f*pw; x2 = pcx + 0.5f*pw; y likewise (ha, cy, d1 / wy, d3 / wh);
+ *             then x = min(max(x, 0), W), y = min(max(y, 0), H).  expf is the device's: the one operation that is not
+ *             bit-defined against numpy.
+ *   Valid:    (x2 - x1 >= min_size) && (y2 - y1 >= min_size) && (logit >= logit_thresh); a NaN anywhere fails.
+ *             logit_thresh is logit(score_thresh) formed by the caller (score_thresh 0: -INFINITY).  Scores are
+ *             logits end to end.
+ *   NMS:      per segment, on candidates in their given order; an invalid candidate neither survives nor suppresses;
+ *             candidate i survives if no surviving j < i has inter / (area_i + area_j - inter) > nms_thresh, with
+ *             inter = max(min(x2i,x2j) - max(x1i,x1j), 0) * max(min(y2i,y2j) - max(y1i,y1j), 0) and
+ *             area = (x2 - x1) * (y2 - y1); 0/0 is a NaN and does not suppress.  (torchvision's nms on the unshifted
+ *             boxes of a level, _batched_nms_vanilla; not the coordinate-offset form of batched_nms.)
+ *   Merge:    per image the survivors of all levels in the order of (logit, position), position = level *
+ *             pre_nms_top_n + rank, the same order as Select; the first post_nms_top_n are the proposals.
+ * rn_rpn_candidates, per (image, level, rank) [B, L, pre_nms_top_n]: index int32 (the anchor n), logit, box [.., 4],
+ * valid (bytes 0 / 1) and count [B, L] int32 (min(pre_nms_top_n, h*w*A)); ranks at or past count hold index -1,
+ * logit -inf, box 0, valid 0.  rn_rpn_select_decode_forward writes those that are not NULL (not all may be), every
+ * row on every call.
+ * rn_rpn_proposals: boxes [B, post, 4], logits [B, post], levels [B, post] int32, count [B] int32, rois [B*post, 5]
+ * in the pooler's format (image index, x1, y1, x2, y2), cand_keep [B, L, pre] bytes (the candidates NMS left); any
+ * may be NULL, not all.  Rows at or past an image's count hold boxes 0, logit -inf, level -1 and RoI image index -1
+ * (the pooler answers such a row with zeros and level -1).  Every row is written on every call.
+ * rn_nms_forward: S segments of n <= 4096 boxes [S, n, 4], already in score order, valid [S, n] bytes or NULL (all
+ * valid) -> keep [S, n] bytes, keep_count [S] int32 or NULL.  Two launches: mask and scan.
+ * rn_box_decode_forward: Decode on its own, anchors [N, 4] + deltas [N, 4] -> boxes [N, 4], one launch; image_h and
+ * image_w are the clip's H and W (INFINITY: no upper clip).  A second-stage box head uses weights (10, 10, 5, 5).
+ * The IoU mask (one 64-bit word per candidate row and block of 64 columns, upper triangle only, vector stores) lives
+ * in a scratch of the context that grows on demand: never during a capture, not while a captured graph lives.  No
+ * floating-point atomics and no atomics on global memory anywhere.  All asynchronous on the context's stream; the
+ * launch counts do not depend on B or S.  B, S or N == 0: RN_OK, nothing launched.  RN_ERR_INVALID, nothing launched,
+ * rn_last_error names the operand: a NULL operand, an operand of 4-byte elements off a 4-byte boundary, an output
+ * sharing a byte with another operand, a parameter out of range (pre_nms_top_n, post_nms_top_n 1..4096; h*w*A below
+ * 2^31; B, B*L and S at most 65535; a NaN threshold). */
+typedef struct rn_rpn_candidates {
+    int32_t *index;
+    float *logit;
+    float *box;
+    uint8_t *valid;
+    int32_t *count;
+} rn_rpn_candidates;
+typedef struct rn_rpn_proposals {
+    float *boxes;
+    float *logits;
+    int32_t *levels;
+    int32_t *count;
+    float *rois;
+    uint8_t *cand_keep;
+} rn_rpn_proposals;
+RN_API int rn_rpn_select_decode_forward(rn_ctx *ctx, uint64_t L, const float *const *head_nhwc, uint64_t B,
+                                        const uint64_t *h, const uint64_t *w, uint64_t A,
+                                        const float *base_anchors /* host, [L, A, 4] */, uint64_t image_h,
+                                        uint64_t image_w, uint64_t pre_nms_top_n, float min_size, float logit_thresh,
+                                        const rn_rpn_candidates *cand);
+RN_API int rn_rpn_nms_merge_forward(rn_ctx *ctx, const rn_rpn_candidates *cand, uint64_t B, uint64_t L,
+                                    uint64_t pre_nms_top_n, uint64_t post_nms_top_n, float nms_thresh,
+                                    const rn_rpn_proposals *out);
+RN_API int rn_nms_forward(rn_ctx *ctx, const float *boxes, const uint8_t *valid /* nullable */, uint64_t S, uint64_t n,
+                          float iou_threshold, uint8_t *keep, int32_t *keep_count /* nullable */);
+RN_API int rn_box_decode_forward(rn_ctx *ctx, const float *anchors, const float *deltas, uint64_t N, float wx, float wy,
+                                 float ww, float wh, float image_h, float image_w, float *boxes);
+/* The RPN as an object, modelled on rn_fpn: torchvision's RPNHead (3x3 C -> C with ReLU, then cls_logits and bbox_pred as
+ * ONE 1x1 C -> P panel, zero rows up to P, the biases as the epilogues' shifts: exact) in front of the three launches.
+ * rn_rpn_create(ctx, &rpn, in_channels (a multiple of 64), L, A, base_anchors [L, A, 4] host); rn_rpn_set_tensor takes
+ * "head.conv.0.0.weight|bias" (older spelling "head.conv.weight|bias"), "head.cls_logits.weight|bias",
+ * "head.bbox_pred.weight|bias" (host fp32); rn_rpn_finalize packs the two panels.  rn_rpn_forward runs the stage on
+ * caller-given fp32 NHWC levels x_nhwc[l] [B, h[l], w[l], in_channels] (16-byte aligned) of an image_h x image_w image:
+ * 2 L + 3 launches whatever B (two contractions per level, select + decode, mask, scan + merge).  The request: the
+ * parameters, the proposals' outputs (any may be NULL, not all) and the optional pre-NMS candidates (all may be NULL).
+ * The object's scratch (head outputs, candidates, mask) grows on demand: never during a capture, not while a captured
+ * graph lives.  Refused (RN_ERR_INVALID, nothing launched, rn_last_error names the operand): as the stand-alone ops,
+ * and an output sharing a byte with a level's map.
+ * rn_fpn_forward_proposals: rn_fpn_forward plus the stage on the neck's fp32 3x3 outputs and pooled level, read in
+ * place (so the 3x3 of every level runs, exported or not); the rpn's L is the neck's levels plus its pool.  Queued after
+ * the exports and before the pooler.  rois (nullable): a pooler as in rn_fpn_forward_rois; when rois->rois_dev ==
+ * req->out.rois and rois->K == B * post_nms_top_n the pooler pools the proposals of the same call -- the only case in
+ * which rois_dev may be an output of the call; the padding rows give zeros and level -1. */
+typedef struct rn_rpn rn_rpn;
+typedef struct rn_rpn_request {
+    uint64_t pre_nms_top_n, post_nms_top_n;
+    float nms_thresh, logit_thresh, min_size;
+    rn_rpn_proposals out;
+    rn_rpn_candidates cand; /* optional */
+} rn_rpn_request;
+RN_API int rn_rpn_create(rn_ctx *ctx, rn_rpn **out, uint64_t in_channels, uint64_t L, uint64_t A, const float *base_anchors);
+RN_API int rn_rpn_set_tensor(rn_rpn *rpn, const char *key, const float *host_data, uint64_t numel);
+RN_API int rn_rpn_finalize(rn_rpn *rpn);
+RN_API int rn_rpn_destroy(rn_rpn *rpn);
+RN_API int rn_rpn_forward(rn_rpn *rpn, const float *const *x_nhwc, uint64_t B, const uint64_t *h, const uint64_t *w,
+                          uint64_t image_h, uint64_t image_w, const rn_rpn_request *req);
+RN_API int rn_fpn_forward_proposals(rn_fpn *fpn, rn_rpn *rpn, const void *const *x_nhwc, uint64_t B, const uint64_t *h,
+                                    const uint64_t *w, float *const *out_nchw /* nullable */, uint64_t image_h,
+                                    uint64_t image_w, const rn_rpn_request *req, const rn_roi_pool *rois /* nullable */);
+/* rn_model_forward_proposals(_u8): rn_model_forward_rois(_u8)'s arguments plus the rpn and its request; the pooler is
+ * nullable.  The image size is the model's input size.  Every part of a launch batch runs the stage on its own images
+ * from its own slice of the neck's and the rpn's scratch and writes its own rows, after the exports and before the
+ * pooler (one profile record "rpn_stage" of layer "rpn").  With the chain (rois->rois_dev == req->out.rois and K == B *
+ * post_nms_top_n) the pooler of a part takes exactly its own images' rows of the RoIs, pooled and levels_out, padding
+ * rows included, so no part reads a row another part has yet to write.  Refused like rn_model_forward_rois, and: an rpn
+ * that is not the neck's, a request out of range, an output of the request sharing a byte with another output of the
+ * call. */
+RN_API int rn_model_forward_proposals(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, const float *input_nchw, uint64_t B,
+                                      const rn_model_outputs *outs /* nullable */, const int *stages,
+                                      const rn_fpn_outputs *fpn_out /* nullable */, const rn_rpn_request *req,
+                                      const rn_roi_pool *rois /* nullable */, int mode);
+RN_API int rn_model_forward_proposals_u8(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, const uint8_t *input_nhwc, uint64_t B,
+                                         const rn_model_outputs *outs, const int *stages, const rn_fpn_outputs *fpn_out,
+                                         const rn_rpn_request *req, const rn_roi_pool *rois, int mode);
 /* Run one forward, then time every tile candidate of every convolution at batch B on the
  * device (events on the context's stream, on the buffers that forward used) and remember the fastest per layer for
  * that batch size.  Results do not change (candidates are bit-identical), only speed. */

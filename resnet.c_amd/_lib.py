@@ -60,6 +60,25 @@ class RoiPool(ctypes.Structure):
                 ("canonical_level", c_int), ("pooled", c_void_p), ("levels_out", c_void_p)]
 
 
+class RpnCandidates(ctypes.Structure):
+    """rn_rpn_candidates: device pointers per (image, level, rank): index int32, logit, box [..,4], valid bytes, and
+    count int32 [B,L]; any may be NULL where the entry point says so."""
+    _fields_ = [("index", c_void_p), ("logit", c_void_p), ("box", c_void_p), ("valid", c_void_p), ("count", c_void_p)]
+
+
+class RpnProposals(ctypes.Structure):
+    """rn_rpn_proposals: device pointers of boxes [B,post,4], logits, levels int32, count int32 [B], rois [B*post,5]
+    and cand_keep bytes [B,L,pre]; any may be NULL, not all."""
+    _fields_ = [("boxes", c_void_p), ("logits", c_void_p), ("levels", c_void_p), ("count", c_void_p),
+                ("rois", c_void_p), ("cand_keep", c_void_p)]
+
+
+class RpnRequest(ctypes.Structure):
+    """rn_rpn_request: the parameters, the proposals' outputs and the optional pre-NMS candidates"""
+    _fields_ = [("pre_nms_top_n", c_uint64), ("post_nms_top_n", c_uint64), ("nms_thresh", c_float), ("logit_thresh", c_float),
+                ("min_size", c_float), ("out", RpnProposals), ("cand", RpnCandidates)]
+
+
 class Epilogue(ctypes.Structure):
     _fields_ = [("scale", c_void_p), ("shift", c_void_p), ("residual", c_void_p),
                 ("relu", c_int)]
@@ -234,6 +253,23 @@ SIGNATURES = {
                                       POINTER(FpnOutputs), POINTER(RoiPool), c_int]),
     "rn_model_forward_rois_u8": (c_int, [c_void_p, c_void_p, c_void_p, u64, POINTER(ModelOutputs), POINTER(c_int),
                                          POINTER(FpnOutputs), POINTER(RoiPool), c_int]),
+    "rn_rpn_select_decode_forward": (c_int, [c_void_p, u64, POINTER(c_void_p), u64, POINTER(u64), POINTER(u64), u64,
+                                             POINTER(c_float), u64, u64, u64, c_float, c_float, POINTER(RpnCandidates)]),
+    "rn_rpn_nms_merge_forward": (c_int, [c_void_p, POINTER(RpnCandidates), u64, u64, u64, u64, c_float,
+                                         POINTER(RpnProposals)]),
+    "rn_nms_forward": (c_int, [c_void_p, c_void_p, c_void_p, u64, u64, c_float, c_void_p, c_void_p]),
+    "rn_box_decode_forward": (c_int, [c_void_p, fptr, fptr, u64] + [c_float] * 6 + [fptr]),
+    "rn_rpn_create": (c_int, [c_void_p, POINTER(c_void_p), u64, u64, u64, POINTER(c_float)]),
+    "rn_rpn_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, u64]),
+    "rn_rpn_finalize": (c_int, [c_void_p]),
+    "rn_rpn_destroy": (c_int, [c_void_p]),
+    "rn_rpn_forward": (c_int, [c_void_p, POINTER(c_void_p), u64, POINTER(u64), POINTER(u64), u64, u64, POINTER(RpnRequest)]),
+    "rn_fpn_forward_proposals": (c_int, [c_void_p, c_void_p, POINTER(c_void_p), u64, POINTER(u64), POINTER(u64),
+                                         POINTER(c_void_p), u64, u64, POINTER(RpnRequest), POINTER(RoiPool)]),
+    "rn_model_forward_proposals": (c_int, [c_void_p, c_void_p, c_void_p, fptr, u64, POINTER(ModelOutputs), POINTER(c_int),
+                                           POINTER(FpnOutputs), POINTER(RpnRequest), POINTER(RoiPool), c_int]),
+    "rn_model_forward_proposals_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, u64, POINTER(ModelOutputs), POINTER(c_int),
+                                              POINTER(FpnOutputs), POINTER(RpnRequest), POINTER(RoiPool), c_int]),
     "rn_model_destroy": (c_int, [c_void_p]),
     "rn_model_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, u64]),
     "rn_model_load_dir": (c_int, [c_void_p, c_char_p]),

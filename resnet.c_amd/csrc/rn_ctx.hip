@@ -39,7 +39,7 @@ int rn_after_launch(rn_ctx *ctx, const char *what)
 
 int rn_scratch(rn_ctx *ctx, int slot, uint64_t bytes, void **ptr)
 {
-    if (slot < 0 || slot >= 6) return rn_set_error(ctx, RN_ERR_INVALID, "bad scratch slot");
+    if (slot < 0 || slot >= 7) return rn_set_error(ctx, RN_ERR_INVALID, "bad scratch slot");
     if (ctx->scratch_bytes[slot] < bytes) {
         if (ctx->graphs_live > 0)
             return rn_set_error(ctx, RN_ERR_INVALID,
@@ -240,7 +240,7 @@ int rn_ctx_destroy(rn_ctx *ctx)
     (void)rn_defer_flush(ctx);  // recorded ops run (their outputs may be read through other contexts later)
     (void)hipStreamSynchronize(ctx->stream);
     rn_defer_destroy(ctx);
-    for (int i = 0; i < 6; ++i) {
+    for (int i = 0; i < 7; ++i) {
         if (ctx->scratch[i]) (void)hipFree(ctx->scratch[i]);
     }
     for (int i = 0; i < ctx->wcache_n; ++i) (void)hipFree(ctx->wcache[i].packed);

@@ -466,6 +466,42 @@ int rn_fpn_roi_step(rn_fpn *f, rn_ctx *ctx, const rn_roi_pool *rp, const float *
                                rp->pooled, rp->levels_out);
 }
 
+// the chain: the pooler of a part on that part's own proposals, rows row0 .. row0 + rows of rois_dev / pooled /
+// levels_out, every one of which it writes (the padding rows as zeros and level -1)
+int rn_fpn_roi_step_rows(rn_fpn *f, rn_ctx *ctx, const rn_roi_pool *rp, const float *scales, const float *thr, uint64_t sub0,
+                         uint64_t img0, uint64_t B, uint64_t images, const uint64_t *h, const uint64_t *w, uint64_t row0,
+                         uint64_t rows)
+{
+    const void *maps[kFpnMaxLevels];
+    uint64_t hs[kFpnMaxLevels], ws[kFpnMaxLevels];
+    if (rows == 0) return RN_OK;
+    for (int i = 0; i < rp->n_levels; ++i) {
+        const int l = rp->level[i];
+        if ((sub0 + B) * h[l] * w[l] > f->cap_pix[l]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn: scratch not reserved");
+        maps[i] = f->outb[l] + sub0 * h[l] * w[l] * f->a, hs[i] = h[l], ws[i] = w[l];
+    }
+    return rn_roi_align_window(ctx, RN_DTYPE_F32, (uint64_t)rp->n_levels, maps, hs, ws, scales, thr, images, img0, B, 1, f->a,
+                               rp->rois_dev + row0 * 5, rows, rp->PH, rp->PW, rp->sampling_ratio, rp->aligned,
+                               rp->pooled + row0 * f->a * rp->PH * rp->PW, rp->levels_out ? rp->levels_out + row0 : NULL);
+}
+
+// the rpn's stage on the neck's 3x3 outputs and pooled level of B images, read in place sub0 images into the scratch
+int rn_fpn_rpn_step(rn_fpn *f, rn_rpn *rpn, rn_ctx *ctx, uint64_t sub0, uint64_t img0, uint64_t B, const uint64_t *h,
+                    const uint64_t *w, uint64_t image_h, uint64_t image_w, const rn_rpn_request *req)
+{
+    const float *lv[kFpnMaxLevels + 1];
+    uint64_t hl[kFpnMaxLevels + 1], wl[kFpnMaxLevels + 1];
+    const int n = f->n, n_out = n + f->extra;
+    for (int i = 0; i < n_out; ++i) {
+        const int l = i < n ? i : n - 1;
+        RN_TRY(rn_fpn_level_shape(f, i, h[l], w[l], NULL, &hl[i], &wl[i]));
+        if (i < n ? (sub0 + B) * hl[i] * wl[i] > f->cap_pix[i] : (sub0 + B) * hl[i] * wl[i] > f->cap_pool)
+            return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn: scratch not reserved");
+        lv[i] = (i < n ? f->outb[i] : f->poolb) + sub0 * hl[i] * wl[i] * f->a;
+    }
+    return rn_rpn_step(rpn, ctx, lv, sub0, img0, B, hl, wl, image_h, image_w, req);
+}
+
 int rn_fpn_roi_clear_of(const rn_fpn *f, rn_ctx *ctx, const rn_roi_pool *rp, const void *other, uint64_t other_bytes)
 {
     if (!rp || rp->K == 0 || !other || other_bytes == 0) return RN_OK;
@@ -486,20 +522,22 @@ namespace {
         if (!(cond)) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s", fn, (msg)); \
     } while (0)
 
-// rn_fpn_forward (fn names it; rp NULL, out_nchw needed) and rn_fpn_forward_rois (rp needed, out_nchw may be NULL)
+// rn_fpn_forward (fn names it; rp NULL, out_nchw needed), rn_fpn_forward_rois (rp needed, out_nchw may be NULL) and
+// rn_fpn_forward_proposals (rpn and req needed, rp and out_nchw may be NULL)
 int fpn_forward(const char *fn, bool with_rois, rn_fpn *f, const void *const *x_nhwc, uint64_t B, const uint64_t *h,
-                const uint64_t *w, float *const *out_nchw, const rn_roi_pool *rp)
+                const uint64_t *w, float *const *out_nchw, const rn_roi_pool *rp, rn_rpn *rpn = NULL,
+                const rn_rpn_request *req = NULL, uint64_t image_h = 0, uint64_t image_w = 0)
 {
     static float *const none[kFpnMaxLevels + 1] = {NULL, NULL, NULL, NULL, NULL};
     if (!f) return RN_ERR_INVALID;
     rn_ctx *ctx = f->ctx;
     RN_ENTER(ctx);
     FPN_REQUIRE(f->finalized, "the neck is not finalized");
-    FPN_REQUIRE(x_nhwc && h && w && (out_nchw || with_rois), "x_nhwc, h, w or out_nchw is NULL");
+    FPN_REQUIRE(x_nhwc && h && w && (out_nchw || with_rois || rpn), "x_nhwc, h, w or out_nchw is NULL");
     FPN_REQUIRE(rp || !with_rois, "rois is NULL");
     if (!out_nchw) out_nchw = none;
     const int n = f->n, n_out = n + f->extra;
-    bool wanted = rp != NULL;
+    bool wanted = rp != NULL || rpn != NULL;
     for (int i = 0; i < n; ++i) {
         FPN_REQUIRE(x_nhwc[i], "a level's map is NULL");
         FPN_REQUIRE((reinterpret_cast<uintptr_t>(x_nhwc[i]) & 15) == 0, "a level's map is off a 16-byte boundary");
@@ -524,11 +562,32 @@ int fpn_forward(const char *fn, bool with_rois, rn_fpn *f, const void *const *x_
             RN_TRY(rn_fpn_roi_clear_of(f, ctx, rp, out_nchw[i], B * f->a * H * W * sizeof(float)));
         }
     }
+    // the rpn behind the neck reads every level's 3x3 output and the pooled level in place
+    uint64_t hl[kFpnMaxLevels + 1], wl[kFpnMaxLevels + 1];
+    if (rpn) {
+        const char *why = NULL;
+        if (!rn_rpn_matches(rpn, ctx, f->a, (uint64_t)n_out, &why)) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s", fn, why);
+        for (int i = 0; i < n_out; ++i) RN_TRY(rn_fpn_level_shape(f, i, h[i < n ? i : n - 1], w[i < n ? i : n - 1], NULL, &hl[i], &wl[i]));
+        RN_TRY(rn_rpn_check(rpn, ctx, req, B, hl, wl, image_h, image_w));
+        for (int i = 0; i < n; ++i) {
+            reads[i] = true;
+            RN_TRY(rn_rpn_clear_of(rpn, ctx, req, B, x_nhwc[i], B * h[i] * w[i] * f->cin[i] * rn_elem_size(f->dtype)));
+        }
+        for (int i = 0; i < n_out; ++i) RN_TRY(rn_rpn_clear_of(rpn, ctx, req, B, out_nchw[i], B * f->a * hl[i] * wl[i] * sizeof(float)));
+        if (rp && rp->K > 0) {
+            // the chain: the pooler may read the RoIs this call writes, and only those
+            const bool chain = rp->rois_dev == req->out.rois && rp->K == B * req->post_nms_top_n;
+            if (!chain) RN_TRY(rn_rpn_clear_of(rpn, ctx, req, B, rp->rois_dev, rp->K * 5 * sizeof(float)));
+            RN_TRY(rn_rpn_clear_of(rpn, ctx, req, B, rp->pooled, rp->K * f->a * rp->PH * rp->PW * sizeof(float)));
+            RN_TRY(rn_rpn_clear_of(rpn, ctx, req, B, rp->levels_out, rp->K * 4));
+        }
+    }
     if (B == 0) return RN_OK;
     RN_TRY(rn_fpn_reserve(f, B, h, w));
+    if (rpn) RN_TRY(rn_rpn_reserve(rpn, B, hl, wl, req->pre_nms_top_n));
     const int saved_layout = ctx->layout;
     ctx->layout = RN_LAYOUT_NHWC;
-    const bool pool = f->extra && out_nchw[n];
+    const bool pool = f->extra && (out_nchw[n] || rpn);
     int st = RN_OK;
     for (int i = 0; i < n && st == RN_OK; ++i) st = rn_fpn_step(f, ctx, RN_FPN_INNER, i, x_nhwc[i], 0, B, h, w, NULL);
     for (int i = n - 1; i >= 1 && st == RN_OK; --i) st = rn_fpn_step(f, ctx, RN_FPN_TOPDOWN, i, NULL, 0, B, h, w, NULL);
@@ -537,6 +596,7 @@ int fpn_forward(const char *fn, bool with_rois, rn_fpn *f, const void *const *x_
     if (pool && st == RN_OK) st = rn_fpn_step(f, ctx, RN_FPN_POOL, n - 1, NULL, 0, B, h, w, NULL);
     for (int i = 0; i < n_out && st == RN_OK; ++i)
         if (out_nchw[i]) st = rn_fpn_step(f, ctx, RN_FPN_EXPORT, i, NULL, 0, B, h, w, out_nchw[i]);
+    if (rpn && st == RN_OK) st = rn_fpn_rpn_step(f, rpn, ctx, 0, 0, B, h, w, image_h, image_w, req);
     if (rp && st == RN_OK) st = rn_fpn_roi_step(f, ctx, rp, scales, thr, 0, 0, B, B, h, w);
     ctx->layout = saved_layout;
     return st;
@@ -556,6 +616,15 @@ int rn_fpn_forward_rois(rn_fpn *f, const void *const *x_nhwc, uint64_t B, const 
                         float *const *out_nchw, const rn_roi_pool *rois)
 {
     return fpn_forward(__func__, true, f, x_nhwc, B, h, w, out_nchw, rois);
+}
+
+int rn_fpn_forward_proposals(rn_fpn *f, rn_rpn *rpn, const void *const *x_nhwc, uint64_t B, const uint64_t *h, const uint64_t *w,
+                             float *const *out_nchw, uint64_t image_h, uint64_t image_w, const rn_rpn_request *req,
+                             const rn_roi_pool *rois)
+{
+    if (f && !rpn) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: rpn is NULL", __func__);
+    if (f && !req) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: req is NULL", __func__);
+    return fpn_forward(__func__, false, f, x_nhwc, B, h, w, out_nchw, rois, rpn, req, image_h, image_w);
 }
 
 }  // extern "C"

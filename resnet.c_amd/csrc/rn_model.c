@@ -188,6 +188,11 @@ struct rn_model {
     /* rn_model_forward_rois: the pooler behind that neck (NULL in every other forward), its levels' scales and
      * thresholds, the images of the whole call */
     const rn_roi_pool *roi;
+    /* rn_model_forward_proposals: the rpn behind that neck and its request (NULL in every other forward); roi_chain:
+     * the pooler pools the proposals of the same call, every part its own rows */
+    rn_rpn *rpn;
+    const rn_rpn_request *rpn_req;
+    int roi_chain;
     float roi_scales[4], roi_thr[3];
     uint64_t roi_images;
     /* tile tuning: calls of the last forward, and the batch size the tiles were tuned for */
@@ -1502,22 +1507,36 @@ static int op_fpn_rest(rn_model *m, uint64_t B)
 {
     const int n = m->fpn_n;
     float *const *out = m->fpn_out->level;
-    const int pool = m->fpn_extra && out[n];
+    const int pool = m->fpn_extra && (out[n] || m->rpn);
     int j, reads[4] = {0, 0, 0, 0};
     if (m->roi && m->roi->K > 0)
         for (j = 0; j < m->roi->n_levels; ++j) reads[m->roi->level[j]] = 1;
+    if (m->rpn)
+        for (j = 0; j < n; ++j) reads[j] = 1;
     for (j = n - 1; j >= 1; --j) TRY(op_fpn(m, RN_FPN_TOPDOWN, j, kFpnTopdownOps[j], NULL, B, NULL));
     for (j = 0; j < n; ++j)
         if (out[j] || (pool && j == n - 1) || reads[j]) TRY(op_fpn(m, RN_FPN_LAYER, j, kFpnLayerOps[j], NULL, B, NULL));
     if (pool) TRY(op_fpn(m, RN_FPN_POOL, n - 1, "fpn_pool", NULL, B, NULL));
     for (j = 0; j <= n; ++j) {
         uint64_t H, W;
-        if (j == n ? !pool : !out[j]) continue;
+        if (j == n ? !(pool && out[n]) : !out[j]) continue;
         TRY(rn_fpn_level_shape(m->fpn, j, m->fpn_h[j < n ? j : n - 1], m->fpn_w[j < n ? j : n - 1], NULL, &H, &W));
         TRY(op_fpn(m, RN_FPN_EXPORT, j, j < n ? kFpnExportOps[j] : "fpn_export_pool", NULL, B,
                    out[j] + m->run.img0 * m->fpn_a * H * W));
     }
-    if (m->roi && m->roi->K > 0) {
+    if (m->rpn) { /* after the exports, before the pooler: 2 L + 3 launches under one record */
+        const double rows = (double)(B * (uint64_t)(n + m->fpn_extra) * m->rpn_req->pre_nms_top_n);
+        TRY(prof_begin(m, "rpn_stage", "rpn", 0.0, rows * 25.0));
+        TRY(rn_fpn_rpn_step(m->fpn, m->rpn, m->run.ctx, m->run.sub0, m->run.img0, B, m->fpn_h, m->fpn_w, m->H, m->W, m->rpn_req));
+        TRY(prof_end(m));
+    }
+    if (m->roi && m->roi_chain) {
+        const uint64_t post = m->rpn_req->post_nms_top_n;
+        TRY(prof_begin(m, "roi_align", "fpn", 0.0, (double)(B * post * m->fpn_a * m->roi->PH * m->roi->PW) * 4.0));
+        TRY(rn_fpn_roi_step_rows(m->fpn, m->run.ctx, m->roi, m->roi_scales, m->roi_thr, m->run.sub0, m->run.img0, B,
+                                 m->roi_images, m->fpn_h, m->fpn_w, m->run.img0 * post, B * post));
+        TRY(prof_end(m));
+    } else if (m->roi && m->roi->K > 0) {
         /* bytes: the outputs only.  What the RoIs gather is several times that (profiles/roi_align) but depends on every
          * box's size against its level, which the host does not look at: the record's GB/s is the OUTPUT rate */
         const double outs = (double)(m->roi->K * m->fpn_a * m->roi->PH * m->roi->PW);
@@ -1905,8 +1924,11 @@ int rn_model_forward_segment_u8(rn_model *m, rn_seg_head *hd, const uint8_t *inp
 /* rn_model_forward_fpn(_u8): like the maps, the request is state of this call alone -- set once every refusal has
  * passed, cleared on every way out (run_blocks asks m->fpn). */
 static int forward_fpn(rn_model *m, rn_fpn *fpn, const void *input, int in_u8, uint64_t B, const rn_model_outputs *outs,
-                       const int *stages, const rn_fpn_outputs *fo, const rn_roi_pool *roi, int mode)
+                       const int *stages, const rn_fpn_outputs *fo, const rn_roi_pool *roi, int mode, rn_rpn *rpn,
+                       const rn_rpn_request *req)
 {
+    uint64_t hl[5], wl[5];
+    int chain = 0;
     static const rn_fpn_outputs no_levels = {{NULL, NULL, NULL, NULL, NULL}};
     rn_model_outputs none;
     const char *why = NULL;
@@ -1920,7 +1942,7 @@ static int forward_fpn(rn_model *m, rn_fpn *fpn, const void *input, int in_u8, u
         return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, msg);
     }
     if (!stages) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_fpn: stages is NULL");
-    if (!fo && roi) fo = &no_levels;
+    if (!fo && (roi || rpn)) fo = &no_levels;
     if (!fo) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_fpn: fpn_out is NULL");
     rn_fpn_dims(fpn, &n, &extra, &a, cin);
     for (j = 0; j < n; ++j)
@@ -1943,7 +1965,7 @@ static int forward_fpn(rn_model *m, rn_fpn *fpn, const void *input, int in_u8, u
             return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, msg);
         }
     }
-    if (!wanted && !roi)
+    if (!wanted && !roi && !rpn)
         return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_fpn: nothing wanted (every level is NULL)");
     if (roi) {
         TRY(rn_fpn_roi_check(fpn, m->ctx, roi, h, w, m->roi_scales, m->roi_thr));
@@ -1960,22 +1982,48 @@ static int forward_fpn(rn_model *m, rn_fpn *fpn, const void *input, int in_u8, u
             TRY(rn_fpn_roi_clear_of(fpn, m->ctx, roi, outs->topk_idx, B * outs->k * sizeof(uint64_t)));
         }
     }
+    if (rpn) { /* the rpn's request against the neck, the image (the model's input size) and every other output */
+        if (!rn_rpn_matches(rpn, m->ctx, a, (uint64_t)(n + extra), &why)) {
+            snprintf(msg, sizeof(msg), "rn_model_forward_proposals: %s", why);
+            return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, msg);
+        }
+        for (j = 0; j < n + extra; ++j)
+            TRY(rn_fpn_level_shape(fpn, j, h[j < n ? j : n - 1], w[j < n ? j : n - 1], NULL, &hl[j], &wl[j]));
+        TRY(rn_rpn_check(rpn, m->ctx, req, B, hl, wl, m->H, m->W));
+        for (j = 0; j < n + extra; ++j) TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, fo->level[j], B * a * hl[j] * wl[j] * sizeof(float)));
+        if (outs) {
+            TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, outs->logits, B * m->classes * sizeof(float)));
+            TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, outs->features, B * m->feat * sizeof(float)));
+            TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, outs->probs, B * m->classes * sizeof(float)));
+            TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, outs->topk_prob, B * outs->k * sizeof(float)));
+            TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, outs->topk_idx, B * outs->k * sizeof(uint64_t)));
+        }
+        if (roi && roi->K > 0) {
+            chain = roi->rois_dev == req->out.rois && roi->K == B * req->post_nms_top_n;
+            if (!chain) TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, roi->rois_dev, roi->K * 5 * sizeof(float)));
+            TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, roi->pooled, roi->K * a * roi->PH * roi->PW * sizeof(float)));
+            TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, roi->levels_out, roi->K * 4));
+        }
+    }
     if (!input || B == 0 || (mode != RN_FWD_REFERENCE_OPS && mode != RN_FWD_FUSED)) return RN_ERR_INVALID;
     if (m->dtype != RN_DTYPE_F32 && mode != RN_FWD_FUSED)
         return rn_ctx_set_error(m->ctx, RN_ERR_UNSUPPORTED, "rn_model_forward_fpn: a bf16 model runs RN_FWD_FUSED only");
     TRY(rn_fpn_reserve(fpn, B < m->max_sub ? B : m->max_sub, h, w));
+    if (rpn) TRY(rn_rpn_reserve(rpn, B < m->max_sub ? B : m->max_sub, hl, wl, req->pre_nms_top_n));
     memset(&none, 0, sizeof(none));
     if (!outs) outs = &none;
     m->fpn = fpn;
     m->fpn_out = fo;
     m->roi = roi;
     m->roi_images = B;
+    m->rpn = rpn, m->rpn_req = req, m->roi_chain = chain;
     m->fpn_n = n, m->fpn_extra = extra, m->fpn_a = a;
     for (j = 0; j < n; ++j) m->fpn_stage[j] = stages[j], m->fpn_h[j] = h[j], m->fpn_w[j] = w[j];
     st = forward_outputs(m, input, in_u8, B, outs->logits, outs, mode, 0);
     m->fpn = NULL;
     m->fpn_out = NULL;
     m->roi = NULL;
+    m->rpn = NULL, m->rpn_req = NULL, m->roi_chain = 0;
     m->maps_done = 0;
     return st;
 }
@@ -1983,27 +2031,43 @@ static int forward_fpn(rn_model *m, rn_fpn *fpn, const void *input, int in_u8, u
 int rn_model_forward_fpn(rn_model *m, rn_fpn *fpn, const float *input_nchw, uint64_t B, const rn_model_outputs *outs,
                          const int *stages, const rn_fpn_outputs *fpn_out, int mode)
 {
-    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, NULL, mode);
+    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, NULL, mode, NULL, NULL);
 }
 
 int rn_model_forward_fpn_u8(rn_model *m, rn_fpn *fpn, const uint8_t *input_nhwc, uint64_t B, const rn_model_outputs *outs,
                             const int *stages, const rn_fpn_outputs *fpn_out, int mode)
 {
-    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, NULL, mode);
+    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, NULL, mode, NULL, NULL);
 }
 
 int rn_model_forward_rois(rn_model *m, rn_fpn *fpn, const float *input_nchw, uint64_t B, const rn_model_outputs *outs,
                           const int *stages, const rn_fpn_outputs *fpn_out, const rn_roi_pool *rois, int mode)
 {
     if (m && !rois) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_rois: rois is NULL");
-    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, rois, mode);
+    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, rois, mode, NULL, NULL);
 }
 
 int rn_model_forward_rois_u8(rn_model *m, rn_fpn *fpn, const uint8_t *input_nhwc, uint64_t B, const rn_model_outputs *outs,
                              const int *stages, const rn_fpn_outputs *fpn_out, const rn_roi_pool *rois, int mode)
 {
     if (m && !rois) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_rois: rois is NULL");
-    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, rois, mode);
+    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, rois, mode, NULL, NULL);
+}
+
+int rn_model_forward_proposals(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, const float *input_nchw, uint64_t B,
+                               const rn_model_outputs *outs, const int *stages, const rn_fpn_outputs *fpn_out,
+                               const rn_rpn_request *req, const rn_roi_pool *rois, int mode)
+{
+    if (m && (!rpn || !req)) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_proposals: rpn or req is NULL");
+    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, rois, mode, rpn, req);
+}
+
+int rn_model_forward_proposals_u8(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, const uint8_t *input_nhwc, uint64_t B,
+                                  const rn_model_outputs *outs, const int *stages, const rn_fpn_outputs *fpn_out,
+                                  const rn_rpn_request *req, const rn_roi_pool *rois, int mode)
+{
+    if (m && (!rpn || !req)) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_proposals: rpn or req is NULL");
+    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, rois, mode, rpn, req);
 }
 
 /* The decoded-image route resizes to 256 and crops 224 x 224: a model of another size refuses it. */

@@ -110,6 +110,31 @@ int rn_fpn_roi_clear_of(const rn_fpn *fpn, rn_ctx *ctx, const rn_roi_pool *rp, c
 int rn_fpn_roi_step(rn_fpn *fpn, rn_ctx *ctx, const rn_roi_pool *rp, const float *scales, const float *thr,
                     uint64_t sub0, uint64_t img0, uint64_t B, uint64_t images, const uint64_t *h, const uint64_t *w);
 
+/* ---- rn_rpn.hip: the RPN behind a neck, mirroring rn_fpn_roi_* ---- */
+/* 1 when the rpn is finalized, lives on ctx's device, reads in_channels channels and n_levels levels; *why otherwise */
+int rn_rpn_matches(const rn_rpn *rpn, const rn_ctx *ctx, uint64_t in_channels, uint64_t n_levels, const char **why);
+/* the object's scratch for `images` images whose level l is h[l] x w[l], and pre candidates per (image, level) */
+int rn_rpn_reserve(rn_rpn *rpn, uint64_t images, const uint64_t *h, const uint64_t *w, uint64_t pre);
+/* every refusal that concerns the request alone, for a forward of `images` images (text in ctx) */
+int rn_rpn_check(const rn_rpn *rpn, rn_ctx *ctx, const rn_rpn_request *req, uint64_t images, const uint64_t *h,
+                 const uint64_t *w, uint64_t image_h, uint64_t image_w);
+/* RN_ERR_INVALID when an output of the request shares a byte with [other, other + other_bytes) */
+int rn_rpn_clear_of(const rn_rpn *rpn, rn_ctx *ctx, const rn_rpn_request *req, uint64_t images, const void *other,
+                    uint64_t other_bytes);
+/* the stage's 2 L + 3 launches on ctx for the B images from the caller's image img0 on, whose scratch starts sub0
+ * images into the object's tensors; x: the L fp32 NHWC levels of these B images */
+int rn_rpn_step(rn_rpn *rpn, rn_ctx *ctx, const float *const *x, uint64_t sub0, uint64_t img0, uint64_t B,
+                const uint64_t *h, const uint64_t *w, uint64_t image_h, uint64_t image_w, const rn_rpn_request *req);
+
+/* rn_fpn.hip: the rpn's stage on the neck's 3x3 outputs and pooled level of B images, read in place sub0 images into the
+ * neck's scratch (h, w: the neck's input levels) */
+int rn_fpn_rpn_step(rn_fpn *fpn, rn_rpn *rpn, rn_ctx *ctx, uint64_t sub0, uint64_t img0, uint64_t B, const uint64_t *h,
+                    const uint64_t *w, uint64_t image_h, uint64_t image_w, const rn_rpn_request *req);
+/* the chain: rn_fpn_roi_step on rows row0 .. row0 + rows of rois_dev, pooled and levels_out alone, all of them written */
+int rn_fpn_roi_step_rows(rn_fpn *fpn, rn_ctx *ctx, const rn_roi_pool *rp, const float *scales, const float *thr,
+                         uint64_t sub0, uint64_t img0, uint64_t B, uint64_t images, const uint64_t *h, const uint64_t *w,
+                         uint64_t row0, uint64_t rows);
+
 /* ---- rn_stem.hip ---- */
 /* 1 when the fused stem + max-pool launch takes a padded image of Hp x Wp (nchw: the NCHW-fetching form on
  * an image of Hp - 6 x Wp - 6) of `dtype`: its documented conditions on the geometry alone */

@@ -1,0 +1,901 @@
+// The launches between the neck and the pooler of a two-stage detector: torchvision's RegionProposalNetwork in eval
+// mode behind its head.  Three kernels and the ops around them:
+//   select + decode (rn_rpn_select_decode_forward): per (image, level) the pre_nms_top_n best anchors by logit, in
+//     rank order, decoded against their anchors, clipped to the image and marked valid or not;
+//   IoU mask + scan (rn_nms_forward): greedy NMS of segments of boxes that are already in score order;
+//   IoU mask + scan and merge (rn_rpn_nms_merge_forward): NMS per (image, level), then the post_nms_top_n best
+//     survivors of an image over all its levels;
+//   rn_box_decode_forward: BoxCoder.decode on its own, the same device function.
+// The reference classifies whole images only; nothing here has a counterpart in it.
+//
+// Order.  A selection orders 64-bit keys that are unique by construction: a monotone image of the logit in the high
+// word (NaN as -inf, -0 as +0), the complement of the index in the low word -- so "greater key" IS rn_topk_forward's
+// "(v_i, i) precedes (v_j, j)".  rpn_select_sort finds the k-th key exactly with an MSB-first radix select (8 passes
+// of 8 bits, a 256-bin histogram in LDS), gathers the k keys at or above it into LDS and sorts them with a bitonic
+// network.  The gather's order (it goes through an LDS counter) never reaches an output: the sort removes it.
+// Atomics: integer adds in LDS only.  No floating-point atomics, no atomics on global memory.
+#include <math.h>
+#include <string.h>
+
+#include "rn_conv_params.h"
+#include "rn_internal.h"
+#include "rn_private.h"
+
+// The arithmetic of the decode, the validity rule and the IoU is a contract, operation by operation (rn_hip.h): no
+// product of this file is fused into an add.
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr uint32_t kRpnBlock = 1024;  // select + decode and merge: one block per segment / image
+constexpr uint32_t kRpnMaxK = 4096;   // keys a selection holds in LDS (32 KiB)
+constexpr int kRpnMaxLevels = 5;
+constexpr int kRpnMaxAnchors = 12;
+constexpr int kNmsScratchSlot = 6;    // the context's scratch slot of the IoU mask
+
+struct sel_smem {
+    uint64_t keys[kRpnMaxK];
+    uint32_t hist[256];
+    uint64_t prefix;
+    uint32_t remaining, fill;
+};
+
+// the contract's min and max: a NaN first operand stays (torch.clamp's and numpy's rule)
+__device__ __forceinline__ float rpn_min(float a, float b) { return a > b ? b : a; }
+__device__ __forceinline__ float rpn_max(float a, float b) { return a < b ? b : a; }
+
+__device__ __forceinline__ uint32_t rpn_mono(float v)
+{
+    uint32_t u = __float_as_uint(v);
+    if (v != v) u = 0xFF800000u;   // a NaN ranks as -inf
+    if (u == 0x80000000u) u = 0u;  // -0 == +0
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // never 0: -inf is 0x007FFFFF
+}
+
+__device__ __forceinline__ uint64_t rpn_key(float v, uint32_t index) { return ((uint64_t)rpn_mono(v) << 32) | (uint32_t)~index; }
+
+// Block-wide.  key_at(i), i < n, gives element i's key; keys are unique except for 0, which marks an absent element.
+// want: 1 <= want <= min(number of nonzero keys, kRpnMaxK).  Afterwards s.keys[0 .. want) are the `want` greatest
+// keys, descending.
+template <typename KeyAt>
+__device__ void rpn_select_sort(sel_smem &s, uint32_t n, uint32_t want, KeyAt key_at)
+{
+    const uint32_t tid = threadIdx.x, nt = blockDim.x;
+    uint64_t kth = 0;  // want == n: every key is taken
+    if (want < n) {
+        uint64_t prefix = 0;
+        uint32_t rem = want;
+        for (int pass = 7; pass >= 0; --pass) {
+            const int shift = pass * 8;
+            if (tid < 256) s.hist[tid] = 0;
+            __syncthreads();
+            for (uint32_t i = tid; i < n; i += nt) {
+                const uint64_t key = key_at(i);
+                if (pass == 7 || (key >> (shift + 8)) == prefix) atomicAdd(&s.hist[(uint32_t)(key >> shift) & 255u], 1u);
+            }
+            __syncthreads();
+            if (tid < 64) {  // wave 0: the digit whose bin holds the rem-th key from the top
+                uint32_t c[4], tot = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) c[j] = s.hist[4 * tid + j], tot += c[j];
+                uint32_t incl = tot;  // keys in this lane's bins and all higher ones
+                for (uint32_t off = 1; off < 64; off <<= 1) {
+                    const uint32_t v = __shfl_down(incl, off, 64);
+                    if (tid + off < 64) incl += v;
+                }
+                uint32_t above = incl - tot;
+                if (above < rem && rem <= incl) {  // exactly one lane
+                    int d = 0;
+                    bool found = false;
+#pragma unroll
+                    for (int j = 3; j >= 0; --j) {
+                        if (found) continue;
+                        if (rem <= above + c[j]) d = j, found = true;
+                        else above += c[j];
+                    }
+                    s.prefix = (prefix << 8) | (uint64_t)(4 * tid + d);
+                    s.remaining = rem - above;
+                }
+            }
+            __syncthreads();
+            prefix = s.prefix, rem = s.remaining;
+        }
+        kth = prefix;
+    }
+    if (tid == 0) s.fill = 0;
+    __syncthreads();
+    for (uint32_t i = tid; i < n; i += nt) {
+        const uint64_t key = key_at(i);
+        if (key != 0 && key >= kth) {
+            const uint32_t slot = atomicAdd(&s.fill, 1u);
+            if (slot < kRpnMaxK) s.keys[slot] = key;
+        }
+    }
+    __syncthreads();
+    uint32_t P = 2;
+    while (P < want) P <<= 1;  // at most kRpnMaxK
+    for (uint32_t i = want + tid; i < P; i += nt) s.keys[i] = 0;
+    __syncthreads();
+    for (uint32_t size = 2; size <= P; size <<= 1) {
+        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+            for (uint32_t t = tid; t < P / 2; t += nt) {
+                const uint32_t lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+                const bool desc = (lo & size) == 0;
+                const uint64_t a = s.keys[lo], b = s.keys[hi];
+                if ((a < b) == desc) s.keys[lo] = b, s.keys[hi] = a;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// ---- BoxCoder.decode_single + clip_boxes_to_image, the contract's "Decode" ----------------------------------
+struct decode_consts {
+    float wx, wy, ww, wh, clip, img_w, img_h;
+};
+
+__device__ __forceinline__ void rpn_decode(const float a[4], const float d[4], const decode_consts &k, float out[4])
+{
+    const float wa = a[2] - a[0], ha = a[3] - a[1];
+    const float cx = a[0] + 0.5f * wa, cy = a[1] + 0.5f * ha;
+    const float dx = d[0] / k.wx, dy = d[1] / k.wy;
+    const float dw = rpn_min(d[2] / k.ww, k.clip), dh = rpn_min(d[3] / k.wh, k.clip);
+    const float pcx = dx * wa + cx, pcy = dy * ha + cy;
+    const float pw = expf(dw) * wa, ph = expf(dh) * ha;
+    const float hw = 0.5f * pw, hh = 0.5f * ph;
+    out[0] = rpn_min(rpn_max(pcx - hw, 0.0f), k.img_w);
+    out[1] = rpn_min(rpn_max(pcy - hh, 0.0f), k.img_h);
+    out[2] = rpn_min(rpn_max(pcx + hw, 0.0f), k.img_w);
+    out[3] = rpn_min(rpn_max(pcy + hh, 0.0f), k.img_h);
+}
+
+__global__ __launch_bounds__(256) void box_decode_kernel(const float *anchors, const float *deltas, float *boxes, uint64_t N,
+                                                         const decode_consts k)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += stride) {
+        float a[4], d[4], o[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) a[c] = anchors[4 * i + c], d[c] = deltas[4 * i + c];
+        rpn_decode(a, d, k, o);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) boxes[4 * i + c] = o[c];
+    }
+}
+
+// ---- select + decode ----------------------------------------------------------------------------------------
+struct select_args {
+    const float *head[kRpnMaxLevels];  // [B,h,w,P]
+    uint32_t h[kRpnMaxLevels], w[kRpnMaxLevels], sh[kRpnMaxLevels], sw[kRpnMaxLevels];
+    float base[kRpnMaxLevels][kRpnMaxAnchors][4];
+    uint32_t L, A, P, pre, mul_a, shr_a;
+    decode_consts dc;
+    float min_size, logit_thresh;
+    int32_t *cand_index;
+    float *cand_logit, *cand_box;
+    uint8_t *cand_valid;
+    int32_t *cand_count;
+};
+
+__global__ __launch_bounds__(kRpnBlock) void rpn_select_decode_kernel(const select_args p)
+{
+    __shared__ sel_smem s;
+    const uint32_t l = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const float *head = p.head[0];
+    uint32_t h = p.h[0], w = p.w[0], sh = p.sh[0], sw = p.sw[0];
+#pragma unroll
+    for (int j = 1; j < kRpnMaxLevels; ++j)
+        if (l == (uint32_t)j) head = p.head[j], h = p.h[j], w = p.w[j], sh = p.sh[j], sw = p.sw[j];
+    const uint32_t n = h * w * p.A, want = n < p.pre ? n : p.pre;
+    const float *img = head + (uint64_t)b * h * w * p.P;
+    const int A = (int)p.A;
+    const uint32_t P = p.P, mul_a = p.mul_a, shr_a = p.shr_a;
+    rpn_select_sort(s, n, want, [=](uint32_t i) {
+        const uint32_t pos = rn_gemm::fast_div(i, A, mul_a, shr_a);
+        return rpn_key(img[(uint64_t)pos * P + (i - pos * (uint32_t)A)], i);
+    });
+    const uint64_t seg = ((uint64_t)b * p.L + l) * p.pre;
+    for (uint32_t r = tid; r < p.pre; r += kRpnBlock) {
+        int32_t index = -1;
+        float logit = -INFINITY, box[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        bool valid = false;
+        if (r < want) {
+            const uint32_t i = ~(uint32_t)s.keys[r];
+            const uint32_t pos = rn_gemm::fast_div(i, A, mul_a, shr_a), a = i - pos * (uint32_t)A;
+            const uint32_t y = pos / w, x = pos - y * w;
+            const float *px = img + (uint64_t)pos * P;
+            index = (int32_t)i;
+            logit = px[a];
+            float d[4], an[4];
+            const float fx = (float)(x * sw), fy = (float)(y * sh);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                d[c] = px[p.A + 4 * a + c];
+                an[c] = p.base[l][a][c] + ((c & 1) ? fy : fx);
+            }
+            rpn_decode(an, d, p.dc, box);
+            valid = (box[2] - box[0] >= p.min_size) && (box[3] - box[1] >= p.min_size) && (logit >= p.logit_thresh);
+        }
+        if (p.cand_index) p.cand_index[seg + r] = index;
+        if (p.cand_logit) p.cand_logit[seg + r] = logit;
+        if (p.cand_valid) p.cand_valid[seg + r] = valid ? 1 : 0;
+        if (p.cand_box) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) p.cand_box[(seg + r) * 4 + c] = box[c];
+        }
+    }
+    if (tid == 0 && p.cand_count) p.cand_count[(uint64_t)b * p.L + l] = (int32_t)want;
+}
+
+// ---- IoU mask -----------------------------------------------------------------------------------------------
+// One wave: rows r0 .. r0 + 63 of a segment against columns c0 .. c0 + 63, c0 >= r0 (the upper triangle); lane j
+// forms row r0 + j's 64-bit word: bit q set when column c0 + q comes after the row, is inside the segment and
+// overlaps the row by more than the threshold.  Words are stored with vector stores; words[seg][row][nw].
+struct mask_args {
+    const float *boxes;     // [S, n, 4]
+    const int32_t *count;   // [S] rows of a segment that can be valid, or NULL: n
+    uint64_t *words;
+    uint32_t n, nw;
+    float thresh;
+};
+
+__global__ __launch_bounds__(64) void nms_mask_kernel(const mask_args p)
+{
+    __shared__ float cb[64][4];
+    const uint32_t cbk = blockIdx.x, rbk = blockIdx.y, sgm = blockIdx.z, lane = threadIdx.x;
+    if (cbk < rbk) return;
+    uint32_t cnt = p.n;
+    if (p.count) {
+        const int32_t c = p.count[sgm];
+        cnt = c < 0 ? 0u : ((uint32_t)c < p.n ? (uint32_t)c : p.n);
+    }
+    if (rbk * 64 >= cnt || cbk * 64 >= cnt) return;  // uniform: the scan reads no word of these rows or columns
+    const float *seg = p.boxes + (uint64_t)sgm * p.n * 4;
+    const uint32_t col = cbk * 64 + lane, row = rbk * 64 + lane;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) cb[lane][c] = col < cnt ? seg[(uint64_t)col * 4 + c] : 0.0f;
+    __syncthreads();
+    if (row >= cnt) return;
+    const float x1 = seg[(uint64_t)row * 4], y1 = seg[(uint64_t)row * 4 + 1], x2 = seg[(uint64_t)row * 4 + 2],
+                y2 = seg[(uint64_t)row * 4 + 3];
+    const float area = (x2 - x1) * (y2 - y1);
+    uint64_t word = 0;
+    for (uint32_t q = 0; q < 64; ++q) {
+        const uint32_t c = cbk * 64 + q;
+        const float u1 = cb[q][0], v1 = cb[q][1], u2 = cb[q][2], v2 = cb[q][3];
+        const float area_c = (u2 - u1) * (v2 - v1);
+        const float iw = (x2 < u2 ? x2 : u2) - (x1 > u1 ? x1 : u1), ih = (y2 < v2 ? y2 : v2) - (y1 > v1 ? y1 : v1);
+        const float inter = (iw > 0.0f ? iw : 0.0f) * (ih > 0.0f ? ih : 0.0f);
+        const float iou = inter / (area + area_c - inter);
+        if (c > row && c < cnt && iou > p.thresh) word |= 1ull << q;
+    }
+    p.words[((uint64_t)sgm * p.n + row) * p.nw + cbk] = word;
+}
+
+// ---- the scan: one wave walks a segment's mask rows ---------------------------------------------------------
+// Lane v holds word v of the removed set (n <= 4096: 64 words).  Invalid candidates and rows at or past cnt start
+// removed: they neither survive nor suppress.  Per block of 64 rows: the block's own word is resolved in registers
+// from the 64 diagonal words (one load), then the rows that survived OR their words into the later lanes.
+// Returns this lane's word of the KEPT set.
+__device__ uint64_t nms_scan_wave(const uint64_t *words, const uint8_t *valid, uint32_t cnt, uint32_t nw, uint32_t lane)
+{
+    const uint32_t nb = (cnt + 63) / 64;
+    uint64_t removed = ~0ull;
+    for (uint32_t c = 0; c < nb; ++c) {
+        const uint32_t i = c * 64 + lane;
+        const bool ok = i < cnt && (!valid || valid[i] != 0);
+        const uint64_t bal = __ballot(ok);
+        if (lane == c) removed = ~bal;
+    }
+    for (uint32_t rb = 0; rb < nb; ++rb) {
+        const uint32_t row = rb * 64 + lane;
+        const uint64_t *rows = words + (uint64_t)rb * 64 * nw;
+        const uint64_t diag = row < cnt ? rows[(uint64_t)lane * nw + rb] : 0ull;
+        uint64_t cur = __shfl(removed, (int)rb, 64);
+#pragma unroll 1
+        for (int j = 0; j < 64; ++j) {
+            const uint64_t dj = __shfl(diag, j, 64);
+            if (!((cur >> j) & 1ull)) cur |= dj;
+        }
+        if (lane == rb) removed = cur;
+        const uint64_t kept = ~cur;  // rows of this block that survive (rows at or past cnt were removed at the start)
+        const bool mine = lane > rb && lane < nb;
+#pragma unroll 1
+        for (int j0 = 0; j0 < 64; j0 += 8) {
+            if (((kept >> j0) & 0xFFull) == 0) continue;  // uniform
+            uint64_t v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                v[u] = (mine && ((kept >> (j0 + u)) & 1ull)) ? rows[(uint64_t)(j0 + u) * nw + lane] : 0ull;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) removed |= v[u];
+        }
+    }
+    return lane < nb ? ~removed : 0ull;
+}
+
+struct scan_args {
+    const uint64_t *words;
+    const uint8_t *valid;  // [S, n] or NULL
+    uint8_t *keep;         // [S, n]
+    int32_t *keep_count;   // [S] or NULL
+    uint32_t n, nw;
+};
+
+__global__ __launch_bounds__(64) void nms_scan_kernel(const scan_args p)
+{
+    const uint32_t sgm = blockIdx.x, lane = threadIdx.x;
+    const uint64_t kept = nms_scan_wave(p.words + (uint64_t)sgm * p.n * p.nw, p.valid ? p.valid + (uint64_t)sgm * p.n : nullptr,
+                                        p.n, p.nw, lane);
+    for (uint32_t c = 0; c < p.nw; ++c) {
+        const uint64_t wd = __shfl(kept, (int)c, 64);
+        const uint32_t i = c * 64 + lane;
+        if (i < p.n) p.keep[(uint64_t)sgm * p.n + i] = (uint8_t)((wd >> lane) & 1ull);
+    }
+    uint32_t total = (uint32_t)__popcll(kept);
+    for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off, 64);
+    if (lane == 0 && p.keep_count) p.keep_count[sgm] = (int32_t)total;
+}
+
+// ---- scan + merge: one block per image ----------------------------------------------------------------------
+struct merge_args {
+    const uint64_t *words;      // [B * L segments][pre][nw]
+    const float *cand_logit, *cand_box;
+    const uint8_t *cand_valid;
+    const int32_t *cand_count;  // [B, L]
+    uint32_t L, pre, post, nw, mul_pre, shr_pre;
+    uint32_t img0;              // the image index of this launch's first image (the RoI rows' first column)
+    float *boxes, *logits, *rois;
+    int32_t *levels, *count;
+    uint8_t *cand_keep;         // [B, L, pre] or NULL
+};
+
+__global__ __launch_bounds__(kRpnBlock) void rpn_merge_kernel(const merge_args p)
+{
+    __shared__ sel_smem s;
+    __shared__ uint64_t skeep[kRpnMaxLevels][64];
+    __shared__ uint32_t skept[kRpnMaxLevels];
+    const uint32_t b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (wave < p.L) {
+        const uint64_t sgm = (uint64_t)b * p.L + wave;
+        const int32_t c = p.cand_count[sgm];
+        const uint32_t cnt = c < 0 ? 0u : ((uint32_t)c < p.pre ? (uint32_t)c : p.pre);
+        const uint64_t kept = nms_scan_wave(p.words + sgm * p.pre * p.nw, p.cand_valid + sgm * p.pre, cnt, p.nw, lane);
+        skeep[wave][lane] = kept;
+        uint32_t total = (uint32_t)__popcll(kept);
+        for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off, 64);
+        if (lane == 0) skept[wave] = total;
+    }
+    __syncthreads();
+    uint32_t survivors = 0;
+    for (uint32_t l = 0; l < p.L; ++l) survivors += skept[l];
+    const uint32_t want = survivors < p.post ? survivors : p.post;
+    const uint32_t n = p.L * p.pre;
+    const float *logit = p.cand_logit + (uint64_t)b * n;
+    const int pre = (int)p.pre;
+    const uint32_t mul_pre = p.mul_pre, shr_pre = p.shr_pre;
+    if (p.cand_keep) {
+        for (uint32_t i = tid; i < n; i += kRpnBlock) {
+            const uint32_t l = rn_gemm::fast_div(i, pre, mul_pre, shr_pre), r = i - l * (uint32_t)pre;
+            p.cand_keep[(uint64_t)b * n + i] = (uint8_t)((skeep[l][r >> 6] >> (r & 63)) & 1ull);
+        }
+    }
+    if (want > 0) {  // uniform
+        rpn_select_sort(s, n, want, [=](uint32_t i) -> uint64_t {
+            const uint32_t l = rn_gemm::fast_div(i, pre, mul_pre, shr_pre), r = i - l * (uint32_t)pre;
+            if (!((skeep[l][r >> 6] >> (r & 63)) & 1ull)) return 0ull;
+            return rpn_key(logit[i], i);
+        });
+    }
+    for (uint32_t r = tid; r < p.post; r += kRpnBlock) {
+        float box[4] = {0.0f, 0.0f, 0.0f, 0.0f}, lg = -INFINITY, image = -1.0f;
+        int32_t level = -1;
+        if (r < want) {
+            const uint32_t i = ~(uint32_t)s.keys[r];
+            level = (int32_t)rn_gemm::fast_div(i, pre, mul_pre, shr_pre);
+            lg = logit[i];
+            image = (float)(p.img0 + b);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) box[c] = p.cand_box[((uint64_t)b * n + i) * 4 + c];
+        }
+        const uint64_t o = (uint64_t)b * p.post + r;
+        if (p.logits) p.logits[o] = lg;
+        if (p.levels) p.levels[o] = level;
+        if (p.boxes) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) p.boxes[o * 4 + c] = box[c];
+        }
+        if (p.rois) {
+            p.rois[o * 5] = image;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) p.rois[o * 5 + 1 + c] = box[c];
+        }
+    }
+    if (tid == 0 && p.count) p.count[b] = (int32_t)want;
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------
+struct operand {
+    const void *ptr;
+    uint64_t bytes;
+    const char *name;
+    bool output;
+    bool bytes_only;  // an array of bytes: any boundary
+};
+
+// every operand on a 4-byte boundary (arrays of bytes: any) and no output sharing a byte with another operand
+int check_operands(rn_ctx *ctx, const char *fn, const operand *ops, int n_ops)
+{
+    for (int i = 0; i < n_ops; ++i) {
+        if (!ops[i].ptr) continue;
+        if (!ops[i].bytes_only && (reinterpret_cast<uintptr_t>(ops[i].ptr) & 3) != 0)
+            return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s is off a 4-byte boundary", fn, ops[i].name);
+    }
+    for (int i = 0; i < n_ops; ++i) {
+        if (!ops[i].ptr || !ops[i].output) continue;
+        for (int j = 0; j < n_ops; ++j) {
+            if (j == i || !ops[j].ptr || (ops[j].output && j < i)) continue;
+            if (rn_overlap(ops[i].ptr, ops[i].bytes, ops[j].ptr, ops[j].bytes))
+                return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s overlaps %s", fn, ops[i].name, ops[j].name);
+        }
+    }
+    return RN_OK;
+}
+
+int mask_launch(rn_ctx *ctx, const float *boxes, const int32_t *count, uint64_t *words, uint64_t S, uint64_t n, float thresh,
+                const char *what)
+{
+    mask_args p;
+    memset(&p, 0, sizeof(p));
+    p.boxes = boxes, p.count = count, p.words = words, p.n = (uint32_t)n, p.nw = (uint32_t)rn_ceil_div(n, 64), p.thresh = thresh;
+    const dim3 grid(p.nw, p.nw, (unsigned)S);
+    nms_mask_kernel<<<grid, 64, 0, ctx->stream>>>(p);
+    return rn_after_launch(ctx, what);
+}
+
+// the select + decode launch, no checks
+int select_launch(rn_ctx *ctx, uint64_t L, const float *const *head_nhwc, uint64_t B, const uint64_t *h, const uint64_t *w,
+                  uint64_t A, const float *base_anchors, uint64_t image_h, uint64_t image_w, uint64_t pre, float min_size,
+                  float logit_thresh, const rn_rpn_candidates *cand, const char *what)
+{
+    select_args p;
+    memset(&p, 0, sizeof(p));
+    for (uint64_t l = 0; l < L; ++l) {
+        p.head[l] = head_nhwc[l], p.h[l] = (uint32_t)h[l], p.w[l] = (uint32_t)w[l];
+        p.sh[l] = (uint32_t)(image_h / h[l]), p.sw[l] = (uint32_t)(image_w / w[l]);
+        for (uint64_t a = 0; a < A; ++a)
+            for (int c = 0; c < 4; ++c) p.base[l][a][c] = base_anchors[(l * A + a) * 4 + c];
+    }
+    p.L = (uint32_t)L, p.A = (uint32_t)A, p.P = (uint32_t)((5 * A + 3) & ~(uint64_t)3), p.pre = (uint32_t)pre;
+    rn_fast_div((unsigned)A, &p.mul_a, &p.shr_a);
+    p.dc = {1.0f, 1.0f, 1.0f, 1.0f, (float)log(1000.0 / 16.0), (float)image_w, (float)image_h};
+    p.min_size = min_size, p.logit_thresh = logit_thresh;
+    p.cand_index = cand->index, p.cand_logit = cand->logit, p.cand_box = cand->box, p.cand_valid = cand->valid;
+    p.cand_count = cand->count;
+    rpn_select_decode_kernel<<<dim3((unsigned)L, (unsigned)B), kRpnBlock, 0, ctx->stream>>>(p);
+    return rn_after_launch(ctx, what);
+}
+
+// the scan + merge launch, no checks; img0: the image index of the launch's first image
+int merge_launch(rn_ctx *ctx, const uint64_t *words, const rn_rpn_candidates *cand, uint64_t B, uint64_t L, uint64_t pre,
+                 uint64_t post, uint64_t img0, const rn_rpn_proposals *out, const char *what)
+{
+    merge_args p;
+    memset(&p, 0, sizeof(p));
+    p.words = words, p.cand_logit = cand->logit, p.cand_box = cand->box, p.cand_valid = cand->valid, p.cand_count = cand->count;
+    p.L = (uint32_t)L, p.pre = (uint32_t)pre, p.post = (uint32_t)post, p.nw = (uint32_t)rn_ceil_div(pre, 64);
+    p.img0 = (uint32_t)img0;
+    rn_fast_div((unsigned)pre, &p.mul_pre, &p.shr_pre);
+    p.boxes = out->boxes, p.logits = out->logits, p.rois = out->rois, p.levels = out->levels, p.count = out->count;
+    p.cand_keep = out->cand_keep;
+    rpn_merge_kernel<<<(unsigned)B, kRpnBlock, 0, ctx->stream>>>(p);
+    return rn_after_launch(ctx, what);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rn_box_decode_forward(rn_ctx *ctx, const float *anchors, const float *deltas, uint64_t N, float wx, float wy, float ww,
+                          float wh, float image_h, float image_w, float *boxes)
+{
+    RN_ENTER(ctx);
+    RN_REQUIRE(ctx, wx > 0.0f && wy > 0.0f && ww > 0.0f && wh > 0.0f && isfinite(wx) && isfinite(wy) && isfinite(ww) && isfinite(wh),
+               "the weights must be positive and finite");
+    RN_REQUIRE(ctx, image_h > 0.0f && image_w > 0.0f, "image_h and image_w must be positive (INFINITY: no upper clip)");
+    RN_REQUIRE(ctx, N < (1ull << 31), "N must be below 2^31");
+    if (N == 0) return RN_OK;
+    RN_REQUIRE(ctx, anchors, "anchors is NULL");
+    RN_REQUIRE(ctx, deltas, "deltas is NULL");
+    RN_REQUIRE(ctx, boxes, "boxes is NULL");
+    const operand ops[] = {{anchors, N * 16, "anchors", false, false}, {deltas, N * 16, "deltas", false, false}, {boxes, N * 16, "boxes", true, false}};
+    RN_TRY(check_operands(ctx, __func__, ops, 3));
+    const decode_consts k = {wx, wy, ww, wh, (float)log(1000.0 / 16.0), image_w, image_h};
+    box_decode_kernel<<<rn_stream_grid(N, 256), 256, 0, ctx->stream>>>(anchors, deltas, boxes, N, k);
+    return rn_after_launch(ctx, "rn_box_decode_forward");
+}
+
+int rn_rpn_select_decode_forward(rn_ctx *ctx, uint64_t L, const float *const *head_nhwc, uint64_t B, const uint64_t *h,
+                                 const uint64_t *w, uint64_t A, const float *base_anchors, uint64_t image_h, uint64_t image_w,
+                                 uint64_t pre_nms_top_n, float min_size, float logit_thresh, const rn_rpn_candidates *cand)
+{
+    RN_ENTER(ctx);
+    RN_REQUIRE(ctx, L >= 1 && L <= (uint64_t)kRpnMaxLevels, "L must be 1..5");
+    RN_REQUIRE(ctx, A >= 1 && A <= (uint64_t)kRpnMaxAnchors, "A must be 1..12");
+    RN_REQUIRE(ctx, head_nhwc && h && w && base_anchors, "head_nhwc, h, w or base_anchors is NULL");
+    RN_REQUIRE(ctx, cand, "cand is NULL");
+    RN_REQUIRE(ctx, cand->index || cand->logit || cand->box || cand->valid || cand->count, "every output of cand is NULL");
+    RN_REQUIRE(ctx, pre_nms_top_n >= 1 && pre_nms_top_n <= kRpnMaxK, "pre_nms_top_n must be 1..4096");
+    RN_REQUIRE(ctx, image_h >= 1 && image_w >= 1 && image_h < (1ull << 24) && image_w < (1ull << 24),
+               "image_h and image_w must be 1 .. 2^24 - 1");
+    RN_REQUIRE(ctx, B <= 65535, "B must be at most 65535");
+    RN_REQUIRE(ctx, !(min_size != min_size) && !(logit_thresh != logit_thresh), "min_size or logit_thresh is a NaN");
+    const uint64_t P = (5 * A + 3) & ~(uint64_t)3;
+    for (uint64_t l = 0; l < L; ++l) {
+        RN_REQUIRE(ctx, h[l] >= 1 && w[l] >= 1 && h[l] <= image_h && w[l] <= image_w, "h and w must be 1 .. the image's");
+        RN_REQUIRE(ctx, h[l] * w[l] * A < (1ull << 31), "h * w * A must be below 2^31");
+    }
+    if (B == 0) return RN_OK;
+    const uint64_t rows = B * L * pre_nms_top_n;
+    operand ops[kRpnMaxLevels + 5];
+    int n_ops = 0;
+    for (uint64_t l = 0; l < L; ++l) {
+        RN_REQUIRE(ctx, head_nhwc[l], "a level's head output is NULL");
+        ops[n_ops++] = {head_nhwc[l], B * h[l] * w[l] * P * 4, "a level's head output", false, false};
+    }
+    ops[n_ops++] = {cand->index, rows * 4, "cand.index", true, false};
+    ops[n_ops++] = {cand->logit, rows * 4, "cand.logit", true, false};
+    ops[n_ops++] = {cand->box, rows * 16, "cand.box", true, false};
+    ops[n_ops++] = {cand->valid, rows, "cand.valid", true, true};
+    ops[n_ops++] = {cand->count, B * L * 4, "cand.count", true, false};
+    RN_TRY(check_operands(ctx, __func__, ops, n_ops));
+    return select_launch(ctx, L, head_nhwc, B, h, w, A, base_anchors, image_h, image_w, pre_nms_top_n, min_size, logit_thresh,
+                         cand, "rn_rpn_select_decode_forward");
+}
+
+int rn_nms_forward(rn_ctx *ctx, const float *boxes, const uint8_t *valid, uint64_t S, uint64_t n, float iou_threshold,
+                   uint8_t *keep, int32_t *keep_count)
+{
+    RN_ENTER(ctx);
+    RN_REQUIRE(ctx, n <= kRpnMaxK, "n must be at most 4096");
+    RN_REQUIRE(ctx, S <= 65535, "S must be at most 65535");
+    RN_REQUIRE(ctx, !(iou_threshold != iou_threshold), "iou_threshold is a NaN");
+    if (S == 0 || n == 0) return RN_OK;
+    RN_REQUIRE(ctx, boxes, "boxes is NULL");
+    RN_REQUIRE(ctx, keep, "keep is NULL");
+    const operand ops[] = {{boxes, S * n * 16, "boxes", false, false},
+                           {valid, S * n, "valid", false, true},
+                           {keep, S * n, "keep", true, true},
+                           {keep_count, S * 4, "keep_count", true, false}};
+    RN_TRY(check_operands(ctx, __func__, ops, 4));
+    const uint64_t nw = rn_ceil_div(n, 64);
+    void *words = nullptr;
+    RN_TRY(rn_scratch(ctx, kNmsScratchSlot, S * n * nw * 8, &words));
+    RN_TRY(mask_launch(ctx, boxes, nullptr, (uint64_t *)words, S, n, iou_threshold, "rn_nms_forward (mask)"));
+    scan_args p;
+    memset(&p, 0, sizeof(p));
+    p.words = (const uint64_t *)words, p.valid = valid, p.keep = keep, p.keep_count = keep_count;
+    p.n = (uint32_t)n, p.nw = (uint32_t)nw;
+    nms_scan_kernel<<<(unsigned)S, 64, 0, ctx->stream>>>(p);
+    return rn_after_launch(ctx, "rn_nms_forward (scan)");
+}
+
+int rn_rpn_nms_merge_forward(rn_ctx *ctx, const rn_rpn_candidates *cand, uint64_t B, uint64_t L, uint64_t pre_nms_top_n,
+                             uint64_t post_nms_top_n, float nms_thresh, const rn_rpn_proposals *out)
+{
+    RN_ENTER(ctx);
+    RN_REQUIRE(ctx, L >= 1 && L <= (uint64_t)kRpnMaxLevels, "L must be 1..5");
+    RN_REQUIRE(ctx, pre_nms_top_n >= 1 && pre_nms_top_n <= kRpnMaxK, "pre_nms_top_n must be 1..4096");
+    RN_REQUIRE(ctx, post_nms_top_n >= 1 && post_nms_top_n <= kRpnMaxK, "post_nms_top_n must be 1..4096");
+    RN_REQUIRE(ctx, !(nms_thresh != nms_thresh), "nms_thresh is a NaN");
+    RN_REQUIRE(ctx, B <= 65535 / L, "B * L must be at most 65535");
+    RN_REQUIRE(ctx, cand, "cand is NULL");
+    RN_REQUIRE(ctx, out, "out is NULL");
+    RN_REQUIRE(ctx, out->boxes || out->logits || out->levels || out->count || out->rois || out->cand_keep,
+               "every output of out is NULL");
+    if (B == 0) return RN_OK;
+    RN_REQUIRE(ctx, cand->logit && cand->box && cand->valid && cand->count, "cand.logit, cand.box, cand.valid or cand.count is NULL");
+    const uint64_t rows = B * L * pre_nms_top_n, prop = B * post_nms_top_n;
+    const operand ops[] = {{cand->logit, rows * 4, "cand.logit", false, false},   {cand->box, rows * 16, "cand.box", false, false},
+                           {cand->valid, rows, "cand.valid", false, true},       {cand->count, B * L * 4, "cand.count", false, false},
+                           {out->boxes, prop * 16, "out.boxes", true, false},     {out->logits, prop * 4, "out.logits", true, false},
+                           {out->levels, prop * 4, "out.levels", true, false},    {out->count, B * 4, "out.count", true, false},
+                           {out->rois, prop * 20, "out.rois", true, false},       {out->cand_keep, rows, "out.cand_keep", true, true}};
+    RN_TRY(check_operands(ctx, __func__, ops, 10));
+    void *words = nullptr;
+    RN_TRY(rn_scratch(ctx, kNmsScratchSlot, rows * rn_ceil_div(pre_nms_top_n, 64) * 8, &words));
+    RN_TRY(mask_launch(ctx, cand->box, cand->count, (uint64_t *)words, B * L, pre_nms_top_n, nms_thresh,
+                       "rn_rpn_nms_merge_forward (mask)"));
+    return merge_launch(ctx, (const uint64_t *)words, cand, B, L, pre_nms_top_n, post_nms_top_n, 0, out,
+                        "rn_rpn_nms_merge_forward (merge)");
+}
+
+// ---- the object: RPNHead's two contractions per level in front of the three launches ---------------------------
+// host copies of the state dict's six tensors until rn_rpn_finalize packs them: 0 conv weight [C,C,3,3], 1 conv bias
+// [C], 2 cls_logits weight [A,C], 3 its bias [A], 4 bbox_pred weight [4A,C], 5 its bias [4A]
+struct rn_rpn {
+    rn_ctx *ctx;
+    uint64_t C, L, A, P;
+    int finalized;
+    float base[kRpnMaxLevels * kRpnMaxAnchors * 4];
+    float *host[6];
+    void *packed_conv, *packed_pred;  // the 3x3 C -> C panel; ONE 1x1 C -> P panel: cls_logits, bbox_pred, zero rows
+    float *conv_bias, *pred_bias;     // the epilogues' shifts (pred_bias: P values, zeros behind 5A)
+    // scratch for cap_img images: per level the 3x3's output [.,h,w,C] and the head output [.,h,w,P]; the candidates
+    // per (image, level, rank) and the IoU mask
+    float *t[kRpnMaxLevels], *head[kRpnMaxLevels];
+    uint64_t cap_pix[kRpnMaxLevels];
+    float *c_logit, *c_box;
+    uint8_t *c_valid;
+    int32_t *c_count;
+    uint64_t *words;
+    uint64_t cap_img, cap_pre;
+};
+
+static uint64_t rpn_key_numel(const rn_rpn *r, int which)
+{
+    const uint64_t n[6] = {r->C * r->C * 9, r->C, r->A * r->C, r->A, 4 * r->A * r->C, 4 * r->A};
+    return n[which];
+}
+
+static void rpn_free_scratch(rn_rpn *r)
+{
+    for (uint64_t l = 0; l < r->L; ++l) {
+        rn_free_null(r->ctx, (void **)&r->t[l]), rn_free_null(r->ctx, (void **)&r->head[l]);
+        r->cap_pix[l] = 0;
+    }
+    rn_free_null(r->ctx, (void **)&r->c_logit), rn_free_null(r->ctx, (void **)&r->c_box);
+    rn_free_null(r->ctx, (void **)&r->c_valid), rn_free_null(r->ctx, (void **)&r->c_count);
+    rn_free_null(r->ctx, (void **)&r->words);
+    r->cap_img = r->cap_pre = 0;
+}
+
+int rn_rpn_create(rn_ctx *ctx, rn_rpn **out, uint64_t in_channels, uint64_t L, uint64_t A, const float *base_anchors)
+{
+    RN_ENTER(ctx);
+    RN_REQUIRE(ctx, out, "out is NULL");
+    *out = NULL;
+    RN_REQUIRE(ctx, in_channels >= 64 && in_channels % 64 == 0 && in_channels <= 1024,
+               "in_channels must be a multiple of 64 (at most 1024)");
+    RN_REQUIRE(ctx, L >= 1 && L <= (uint64_t)kRpnMaxLevels, "L must be 1..5");
+    RN_REQUIRE(ctx, A >= 1 && A <= (uint64_t)kRpnMaxAnchors, "A must be 1..12");
+    RN_REQUIRE(ctx, base_anchors, "base_anchors is NULL");
+    for (uint64_t i = 0; i < L * A * 4; ++i) RN_REQUIRE(ctx, isfinite(base_anchors[i]), "a base anchor is not finite");
+    rn_rpn *r = (rn_rpn *)calloc(1, sizeof(*r));
+    if (!r) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_rpn_create: out of host memory");
+    r->ctx = ctx, r->C = in_channels, r->L = L, r->A = A, r->P = (5 * A + 3) & ~(uint64_t)3;
+    memcpy(r->base, base_anchors, L * A * 4 * sizeof(float));
+    *out = r;
+    return RN_OK;
+}
+
+int rn_rpn_set_tensor(rn_rpn *r, const char *key, const float *host_data, uint64_t numel)
+{
+    static const char *const names[8] = {"head.conv.0.0.weight", "head.conv.0.0.bias", "head.cls_logits.weight",
+                                         "head.cls_logits.bias", "head.bbox_pred.weight", "head.bbox_pred.bias",
+                                         "head.conv.weight",     "head.conv.bias"};
+    if (!r) return RN_ERR_INVALID;
+    rn_ctx *ctx = r->ctx;
+    RN_REQUIRE(ctx, key && host_data, "key or host_data is NULL");
+    RN_REQUIRE(ctx, !r->finalized, "the rpn is finalized");
+    int which = -1;
+    for (int i = 0; i < 8; ++i)
+        if (strcmp(key, names[i]) == 0) which = i < 6 ? i : i - 6;
+    if (which < 0) return rn_set_error(ctx, RN_ERR_INVALID, "rn_rpn_set_tensor: unknown key '%s'", key);
+    const uint64_t want = rpn_key_numel(r, which);
+    if (numel != want)
+        return rn_set_error(ctx, RN_ERR_INVALID, "rn_rpn_set_tensor: %s has %llu elements, not %llu", key,
+                            (unsigned long long)want, (unsigned long long)numel);
+    if (!r->host[which]) r->host[which] = (float *)malloc(want * sizeof(float));
+    if (!r->host[which]) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_rpn_set_tensor: out of host memory");
+    memcpy(r->host[which], host_data, want * sizeof(float));
+    return RN_OK;
+}
+
+int rn_rpn_finalize(rn_rpn *r)
+{
+    static const char *const names[6] = {"head.conv.0.0.weight", "head.conv.0.0.bias", "head.cls_logits.weight",
+                                         "head.cls_logits.bias", "head.bbox_pred.weight", "head.bbox_pred.bias"};
+    if (!r) return RN_ERR_INVALID;
+    rn_ctx *ctx = r->ctx;
+    RN_ENTER(ctx);
+    if (r->finalized) return RN_OK;
+    for (int i = 0; i < 6; ++i)
+        if (!r->host[i]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_rpn_finalize: %s is not set", names[i]);
+    const uint64_t C = r->C, A = r->A, P = r->P;
+    // cls_logits and bbox_pred side by side, zero rows up to P; the bias likewise (seg_add_unit's padding rule: exact)
+    float *w = (float *)calloc(P * C + P, sizeof(float));
+    if (!w) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_rpn_finalize: out of host memory");
+    memcpy(w, r->host[2], A * C * sizeof(float)), memcpy(w + A * C, r->host[4], 4 * A * C * sizeof(float));
+    memcpy(w + P * C, r->host[3], A * sizeof(float)), memcpy(w + P * C + A, r->host[5], 4 * A * sizeof(float));
+    float *raw_conv = NULL, *raw_pred = NULL;
+    int st = rn_malloc(ctx, (void **)&raw_conv, C * C * 9 * sizeof(float));
+    if (st == RN_OK) st = rn_malloc(ctx, (void **)&raw_pred, P * C * sizeof(float));
+    if (st == RN_OK) st = rn_malloc(ctx, (void **)&r->conv_bias, C * sizeof(float));
+    if (st == RN_OK) st = rn_malloc(ctx, (void **)&r->pred_bias, P * sizeof(float));
+    if (st == RN_OK) st = rn_malloc(ctx, &r->packed_conv, rn_conv2d_packed_weight_numel_dt(RN_DTYPE_F32, C, C, 3) * sizeof(float));
+    if (st == RN_OK) st = rn_malloc(ctx, &r->packed_pred, rn_conv2d_packed_weight_numel_dt(RN_DTYPE_F32, C, P, 1) * sizeof(float));
+    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, raw_conv, r->host[0], C * C * 9 * sizeof(float));
+    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, raw_pred, w, P * C * sizeof(float));
+    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, r->conv_bias, r->host[1], C * sizeof(float));
+    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, r->pred_bias, w + P * C, P * sizeof(float));
+    if (st == RN_OK) st = rn_conv2d_pack_weight_dt(ctx, RN_DTYPE_F32, raw_conv, r->packed_conv, C, C, 3);
+    if (st == RN_OK) st = rn_conv2d_pack_weight_dt(ctx, RN_DTYPE_F32, raw_pred, r->packed_pred, C, P, 1);
+    if (st == RN_OK) st = rn_sync(ctx);
+    free(w);
+    rn_free_null(ctx, (void **)&raw_conv), rn_free_null(ctx, (void **)&raw_pred);
+    if (st != RN_OK) return st;
+    for (int i = 0; i < 6; ++i) free(r->host[i]), r->host[i] = NULL;
+    r->finalized = 1;
+    return RN_OK;
+}
+
+int rn_rpn_destroy(rn_rpn *r)
+{
+    if (!r) return RN_OK;
+    rn_ctx *ctx = r->ctx;
+    RN_ENTER(ctx);
+    RN_TRY(rn_sync(ctx));
+    rpn_free_scratch(r);
+    for (int i = 0; i < 6; ++i) free(r->host[i]);
+    rn_free_null(ctx, &r->packed_conv), rn_free_null(ctx, &r->packed_pred);
+    rn_free_null(ctx, (void **)&r->conv_bias), rn_free_null(ctx, (void **)&r->pred_bias);
+    free(r);
+    return RN_OK;
+}
+
+// ---- library-internal (rn_private.h) ----
+
+int rn_rpn_matches(const rn_rpn *r, const rn_ctx *ctx, uint64_t in_channels, uint64_t n_levels, const char **why)
+{
+    const char *w = NULL;
+    if (!r) w = "the rpn is NULL";
+    else if (!r->finalized) w = "the rpn is not finalized";
+    else if (r->ctx->device != ctx->device) w = "the rpn's context is on another device";
+    else if (r->C != in_channels) w = "the rpn's in_channels is not the neck's out_channels";
+    else if (r->L != n_levels) w = "the rpn's level count is not the neck's (its levels and, when it has one, the pool)";
+    if (why) *why = w;
+    return w == NULL;
+}
+
+int rn_rpn_reserve(rn_rpn *r, uint64_t images, const uint64_t *h, const uint64_t *w, uint64_t pre)
+{
+    rn_ctx *ctx = r->ctx;
+    bool fits = images <= r->cap_img && pre <= r->cap_pre;
+    for (uint64_t l = 0; l < r->L; ++l) fits = fits && images * h[l] * w[l] <= r->cap_pix[l];
+    if (fits) return RN_OK;
+    const bool had = r->cap_img > 0;
+    if (rn_ctx_is_capturing(ctx))
+        return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "rn_rpn: the scratch cannot grow on a stream that is being captured");
+    if (had && ctx->graphs_live > 0)
+        return rn_set_error(ctx, RN_ERR_INVALID, "rn_rpn: the scratch cannot grow while a captured graph lives");
+    RN_TRY(rn_sync(ctx));
+    uint64_t pix[kRpnMaxLevels];
+    for (uint64_t l = 0; l < r->L; ++l) pix[l] = images * h[l] * w[l] > r->cap_pix[l] ? images * h[l] * w[l] : r->cap_pix[l];
+    const uint64_t img = images > r->cap_img ? images : r->cap_img, kp = pre > r->cap_pre ? pre : r->cap_pre;
+    rpn_free_scratch(r);
+    for (uint64_t l = 0; l < r->L; ++l) {
+        RN_TRY(rn_malloc(ctx, (void **)&r->t[l], pix[l] * r->C * sizeof(float)));
+        RN_TRY(rn_malloc(ctx, (void **)&r->head[l], pix[l] * r->P * sizeof(float)));
+        r->cap_pix[l] = pix[l];
+    }
+    const uint64_t rows = img * r->L * kp;
+    RN_TRY(rn_malloc(ctx, (void **)&r->c_logit, rows * 4));
+    RN_TRY(rn_malloc(ctx, (void **)&r->c_box, rows * 16));
+    RN_TRY(rn_malloc(ctx, (void **)&r->c_valid, rows));
+    RN_TRY(rn_malloc(ctx, (void **)&r->c_count, img * r->L * 4));
+    RN_TRY(rn_malloc(ctx, (void **)&r->words, rows * rn_ceil_div(kp, 64) * 8));
+    r->cap_img = img, r->cap_pre = kp;
+    return RN_OK;
+}
+
+// every refusal that concerns the request alone, for `images` images (text in ctx)
+int rn_rpn_check(const rn_rpn *r, rn_ctx *ctx, const rn_rpn_request *q, uint64_t images, const uint64_t *h, const uint64_t *w,
+                 uint64_t image_h, uint64_t image_w)
+{
+    RN_REQUIRE(ctx, q, "the rpn's request is NULL");
+    RN_REQUIRE(ctx, q->pre_nms_top_n >= 1 && q->pre_nms_top_n <= kRpnMaxK, "pre_nms_top_n must be 1..4096");
+    RN_REQUIRE(ctx, q->post_nms_top_n >= 1 && q->post_nms_top_n <= kRpnMaxK, "post_nms_top_n must be 1..4096");
+    RN_REQUIRE(ctx, !(q->nms_thresh != q->nms_thresh) && !(q->logit_thresh != q->logit_thresh) && !(q->min_size != q->min_size),
+               "nms_thresh, logit_thresh or min_size is a NaN");
+    RN_REQUIRE(ctx, image_h >= 1 && image_w >= 1 && image_h < (1ull << 24) && image_w < (1ull << 24),
+               "image_h and image_w must be 1 .. 2^24 - 1");
+    RN_REQUIRE(ctx, images <= 65535 / r->L, "B * L must be at most 65535");
+    for (uint64_t l = 0; l < r->L; ++l) {
+        RN_REQUIRE(ctx, h[l] >= 1 && w[l] >= 1 && h[l] <= image_h && w[l] <= image_w, "h and w must be 1 .. the image's");
+        RN_REQUIRE(ctx, h[l] * w[l] * r->A < (1ull << 31), "h * w * A must be below 2^31");
+    }
+    const rn_rpn_proposals *o = &q->out;
+    RN_REQUIRE(ctx, o->boxes || o->logits || o->levels || o->count || o->rois || o->cand_keep, "every output of the request is NULL");
+    const uint64_t rows = images * r->L * q->pre_nms_top_n, prop = images * q->post_nms_top_n;
+    const operand ops[] = {{o->boxes, prop * 16, "out.boxes", true, false},   {o->logits, prop * 4, "out.logits", true, false},
+                           {o->levels, prop * 4, "out.levels", true, false},  {o->count, images * 4, "out.count", true, false},
+                           {o->rois, prop * 20, "out.rois", true, false},     {o->cand_keep, rows, "out.cand_keep", true, true},
+                           {q->cand.index, rows * 4, "cand.index", true, false}, {q->cand.logit, rows * 4, "cand.logit", true, false},
+                           {q->cand.box, rows * 16, "cand.box", true, false}, {q->cand.valid, rows, "cand.valid", true, true},
+                           {q->cand.count, images * r->L * 4, "cand.count", true, false}};
+    return check_operands(ctx, "rn_rpn request", ops, 11);
+}
+
+// RN_ERR_INVALID when an output of the request shares a byte with [other, other + other_bytes)
+int rn_rpn_clear_of(const rn_rpn *r, rn_ctx *ctx, const rn_rpn_request *q, uint64_t images, const void *other,
+                    uint64_t other_bytes)
+{
+    if (!q || !other || other_bytes == 0) return RN_OK;
+    const uint64_t rows = images * r->L * q->pre_nms_top_n, prop = images * q->post_nms_top_n;
+    const void *ptr[11] = {q->out.boxes, q->out.logits, q->out.levels, q->out.count, q->out.rois, q->out.cand_keep,
+                           q->cand.index, q->cand.logit, q->cand.box,  q->cand.valid, q->cand.count};
+    const uint64_t bytes[11] = {prop * 16, prop * 4, prop * 4, images * 4, prop * 20, rows, rows * 4, rows * 4, rows * 16, rows,
+                                images * r->L * 4};
+    for (int i = 0; i < 11; ++i)
+        RN_REQUIRE(ctx, !ptr[i] || !rn_overlap(ptr[i], bytes[i], other, other_bytes),
+                   "an output of the rpn's request overlaps another operand of the call");
+    return RN_OK;
+}
+
+// The stage's 2L + 3 launches on ctx for the B images from the caller's image img0 on, whose scratch starts sub0
+// images into the object's tensors: per level the 3x3 with ReLU and the 1x1 panel, then select + decode, the IoU mask,
+// scan + merge.  x: the L fp32 NHWC levels of these B images.
+int rn_rpn_step(rn_rpn *r, rn_ctx *ctx, const float *const *x, uint64_t sub0, uint64_t img0, uint64_t B, const uint64_t *h,
+                const uint64_t *w, uint64_t image_h, uint64_t image_w, const rn_rpn_request *q)
+{
+    const uint64_t L = r->L, C = r->C, P = r->P, pre = q->pre_nms_top_n, post = q->post_nms_top_n;
+    if (sub0 + B > r->cap_img || pre > r->cap_pre) return rn_set_error(ctx, RN_ERR_INVALID, "rn_rpn: scratch not reserved");
+    const float *heads[kRpnMaxLevels];
+    rn_epilogue ep;
+    ep.scale = NULL, ep.residual = NULL;
+    for (uint64_t l = 0; l < L; ++l) {
+        if ((sub0 + B) * h[l] * w[l] > r->cap_pix[l]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_rpn: scratch not reserved");
+        float *t = r->t[l] + sub0 * h[l] * w[l] * C, *hd = r->head[l] + sub0 * h[l] * w[l] * P;
+        ep.shift = r->conv_bias, ep.relu = 1;
+        RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, x[l], t, r->packed_conv, 3, 1, 1, h[l], w[l], B, C, C,
+                                         h[l], w[l], &ep));
+        ep.shift = r->pred_bias, ep.relu = 0;
+        RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, t, hd, r->packed_pred, 1, 1, 0, h[l], w[l], B, C, P,
+                                         h[l], w[l], &ep));
+        heads[l] = hd;
+    }
+    // the candidates: the caller's rows of these images where it asked for them, the scratch's otherwise
+    const uint64_t urow = img0 * L * pre, srow = sub0 * L * pre;
+    rn_rpn_candidates c;
+    c.index = q->cand.index ? q->cand.index + urow : NULL;
+    c.logit = q->cand.logit ? q->cand.logit + urow : r->c_logit + srow;
+    c.box = q->cand.box ? q->cand.box + urow * 4 : r->c_box + srow * 4;
+    c.valid = q->cand.valid ? q->cand.valid + urow : r->c_valid + srow;
+    c.count = q->cand.count ? q->cand.count + img0 * L : r->c_count + sub0 * L;
+    RN_TRY(select_launch(ctx, L, heads, B, h, w, r->A, r->base, image_h, image_w, pre, q->min_size, q->logit_thresh, &c,
+                         "rn_rpn (select + decode)"));
+    uint64_t *words = r->words + srow * rn_ceil_div(pre, 64);
+    RN_TRY(mask_launch(ctx, c.box, c.count, words, B * L, pre, q->nms_thresh, "rn_rpn (mask)"));
+    rn_rpn_proposals o;
+    const uint64_t orow = img0 * post;
+    o.boxes = q->out.boxes ? q->out.boxes + orow * 4 : NULL, o.logits = q->out.logits ? q->out.logits + orow : NULL;
+    o.levels = q->out.levels ? q->out.levels + orow : NULL, o.count = q->out.count ? q->out.count + img0 : NULL;
+    o.rois = q->out.rois ? q->out.rois + orow * 5 : NULL, o.cand_keep = q->out.cand_keep ? q->out.cand_keep + urow : NULL;
+    return merge_launch(ctx, words, &c, B, L, pre, post, img0, &o, "rn_rpn (scan + merge)");
+}
+
+int rn_rpn_forward(rn_rpn *r, const float *const *x_nhwc, uint64_t B, const uint64_t *h, const uint64_t *w, uint64_t image_h,
+                   uint64_t image_w, const rn_rpn_request *req)
+{
+    if (!r) return RN_ERR_INVALID;
+    rn_ctx *ctx = r->ctx;
+    RN_ENTER(ctx);
+    RN_REQUIRE(ctx, r->finalized, "the rpn is not finalized");
+    RN_REQUIRE(ctx, x_nhwc && h && w, "x_nhwc, h or w is NULL");
+    RN_TRY(rn_rpn_check(r, ctx, req, B, h, w, image_h, image_w));
+    for (uint64_t l = 0; l < r->L; ++l) {
+        RN_REQUIRE(ctx, x_nhwc[l], "a level's map is NULL");
+        RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(x_nhwc[l]) & 15) == 0, "a level's map is off a 16-byte boundary");
+        RN_TRY(rn_rpn_clear_of(r, ctx, req, B, x_nhwc[l], B * h[l] * w[l] * r->C * sizeof(float)));
+    }
+    if (B == 0) return RN_OK;
+    RN_TRY(rn_rpn_reserve(r, B, h, w, req->pre_nms_top_n));
+    const int saved_layout = ctx->layout;
+    ctx->layout = RN_LAYOUT_NHWC;
+    const int st = rn_rpn_step(r, ctx, x_nhwc, 0, 0, B, h, w, image_h, image_w, req);
+    ctx->layout = saved_layout;
+    return st;
+}
+
+}  // extern "C"

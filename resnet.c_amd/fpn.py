@@ -155,14 +155,17 @@ class FeaturePyramidNetwork:
         return int(c.value), int(h.value), int(w.value)
 
     def forward(self, maps_nhwc, levels=None, *, rois=None, pooler=None, image_size=None, roi_levels: bool = False,
-                validate: bool = True) -> Dict[str, np.ndarray]:
+                validate: bool = True, rpn=None, candidates: bool = False) -> Dict[str, np.ndarray]:
         """maps_nhwc: one host array [B,h_i,w_i,in_i] fp32 per level, finest first (a bf16 neck rounds them on upload;
         uint16 bf16 bit patterns are taken as they are) -> {"0": [B,a,h_0,w_0] fp32, ..., "pool": ...}, the names in
         `levels` only (default: all).  With rois ([K,5] fp32: image index, x1, y1, x2, y2 in pixels of the input image),
         a pooler (roi.MultiScaleRoIAlign) and image_size (H, W): rn_fpn_forward_rois, which adds "pooled" [K,a,PH,PW]
         fp32 and, with roi_levels, "roi_levels" int32 [K]; levels may then be empty.  A RoI whose image index is no
         integer in [0, B) raises ValueError (validate=False hands it to the device, which answers zeros and level -1).
-        Synchronous convenience."""
+        With rpn (rpn.RegionProposalNetwork over all of the neck's outputs) and image_size: rn_fpn_forward_proposals,
+        which adds per image "proposals", "scores", "proposal_levels" (and "cand" with candidates=True); with a pooler
+        and no rois the pooler takes the proposals of the same call on the device: "pooled" is [B*post,a,PH,PW] and
+        "rois" [B*post,5] comes with it.  Synchronous convenience."""
         from .ops import _down_raw, _up_raw, to_bf16_bits
         from .tensor import _DeviceBuffer
         n = len(self.in_channels_list)
@@ -171,8 +174,10 @@ class FeaturePyramidNetwork:
         for name in levels:
             if name not in self.names:
                 raise ValueError(f"unknown level {name!r}: one of {self.names}")
-        if (rois is None) != (pooler is None) or (rois is not None and image_size is None):
+        if rpn is None and ((rois is None) != (pooler is None) or (rois is not None and image_size is None)):
             raise ValueError("rois, pooler and image_size go together")
+        if rpn is not None and (image_size is None or (rois is not None and pooler is None)):
+            raise ValueError("rpn needs image_size (and rois a pooler)")
         xs = []
         for x, c in zip(maps_nhwc, self.in_channels_list):
             x = np.asarray(x)
@@ -194,7 +199,24 @@ class FeaturePyramidNetwork:
         xp = (ctypes.c_void_p * n)(*[d.ptr for d in dx])
         op = (ctypes.c_void_p * len(self.names))(*[bufs[name].ptr if name in bufs else None for name in self.names])
         hp, wp = (ctypes.c_uint64 * n)(*hs), (ctypes.c_uint64 * n)(*ws)
-        if rois is None:
+        if rpn is not None:
+            from . import roi as R
+            spec, rbufs = rpn.buffers(B, candidates)
+            rreq, req = rpn.request(rbufs), None
+            if pooler is not None:
+                if rois is None:
+                    drois, K = rbufs["rois"], B * rpn.post
+                else:
+                    drois, K = R.upload_rois(rois, B, validate)
+                PH, PW = pooler.output_size
+                pooled = _DeviceBuffer(self.ctx, max(K * self.out_channels * PH * PW * 4, 16))
+                lv = _DeviceBuffer(self.ctx, max(K * 4, 16)) if roi_levels else None
+                req = pooler.request(self.names, drois.ptr, K, image_size, pooled.ptr, lv.ptr if lv else None)
+            L.check(L.lib().rn_fpn_forward_proposals(self.handle, rpn.handle, xp, B, hp, wp, op, int(image_size[0]),
+                                                     int(image_size[1]), ctypes.byref(rreq),
+                                                     ctypes.byref(req) if req is not None else None),
+                    "rn_fpn_forward_proposals", self.ctx.handle)
+        elif rois is None:
             L.check(L.lib().rn_fpn_forward(self.handle, xp, B, hp, wp, op), "rn_fpn_forward", self.ctx.handle)
         else:
             from . import roi as R
@@ -208,7 +230,11 @@ class FeaturePyramidNetwork:
         self.ctx.sync()
         out = {name: _down_raw(bufs[name], np.float32, int(np.prod(shapes[name]))).reshape(shapes[name])
                for name in self.names if name in bufs}
-        if rois is not None:
+        if rpn is not None:
+            got = rpn.collect(spec, rbufs)
+            out.update({k: got[k] for k in ("proposals", "scores", "proposal_levels", "cand") if k in got})
+            out["rois"], out["proposal_count"], out["proposal_logits"] = got["raw"]["rois"], got["raw"]["count"], got["raw"]["logits"]
+        if pooler is not None:
             out["pooled"] = _down_raw(pooled, np.float32, K * self.out_channels * PH * PW).reshape(K, self.out_channels, PH, PW)
             if roi_levels:
                 out["roi_levels"] = _down_raw(lv, np.int32, K)

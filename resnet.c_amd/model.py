@@ -458,7 +458,7 @@ class NativeModel:
 
     def forward_fpn(self, x: np.ndarray, neck, stages=STAGES, levels=None, *, logits: bool = False,
                     features: bool = False, probs: bool = False, topk: int = 0, fused: bool = True, rois=None,
-                    pooler=None, roi_levels: bool = False, validate: bool = True) -> dict:
+                    pooler=None, roi_levels: bool = False, validate: bool = True, rpn=None, candidates: bool = False) -> dict:
         """One forward with a feature pyramid neck (rn_model_forward_fpn; torchvision's resnet_fpn_backbone): an
         ordered dict "0", "1", .. (one per stage in `stages`, finest first), then "pool" when the neck has the extra
         block -> [B,a,H,W] fp32; then the head outputs asked for, as forward_outputs returns them.  neck: an
@@ -470,7 +470,11 @@ class NativeModel:
         (roi.MultiScaleRoIAlign): rn_model_forward_rois, the same launches plus the pooler's behind the neck, which
         adds "pooled" [K,a,PH,PW] fp32 and, with roi_levels, "roi_levels" int32 [K]; levels may then be empty.  A RoI
         whose image index is no integer in [0, B) raises ValueError (validate=False hands it to the device: zeros
-        and level -1)."""
+        and level -1).
+        With rpn (rpn.RegionProposalNetwork over all of the neck's outputs): rn_model_forward_proposals, which adds per
+        image "proposals" ([count_i, 4]), "scores" and "proposal_levels" (and "cand" with candidates=True); with a
+        pooler and no rois the pooler takes the proposals of the same forward on the device: "pooled" is
+        [B*post,a,PH,PW] and "rois" [B*post,5] is returned with it."""
         from .ops import _down_raw, _up_raw
         from .tensor import _DeviceBuffer
         stages = tuple(stages)
@@ -512,11 +516,27 @@ class NativeModel:
         o = L.ModelOutputs(buf("logits", logits, B * C * 4), buf("features", features, B * F * 4),
                            buf("probs", probs, B * C * 4), buf("topk_prob", k > 0, B * k * 4),
                            buf("topk_idx", k > 0, B * k * 8), k)
-        if (rois is None) != (pooler is None):
+        if rpn is None and (rois is None) != (pooler is None):
             raise ValueError("rois and pooler go together")
+        if rpn is not None and rois is not None and pooler is None:
+            raise ValueError("rois need a pooler")
         mode = L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS
         stage_arr = (ctypes.c_int * len(idx))(*idx)
-        if rois is None:
+        if rpn is not None:
+            from . import roi as R
+            rspec, rbufs = rpn.buffers(B, candidates)
+            rreq, req = rpn.request(rbufs), None
+            if pooler is not None:
+                drois, K = (rbufs["rois"], B * rpn.post) if rois is None else R.upload_rois(rois, B, validate)
+                PH, PW = pooler.output_size
+                pooled = _DeviceBuffer(self.ctx, max(K * neck.out_channels * PH * PW * 4, 16))
+                lv = _DeviceBuffer(self.ctx, max(K * 4, 16)) if roi_levels else None
+                req = pooler.request(names, drois.ptr, K, self.input_size, pooled.ptr, lv.ptr if lv else None)
+            fn = L.lib().rn_model_forward_proposals_u8 if u8 else L.lib().rn_model_forward_proposals
+            L.check(fn(self.handle, neck.handle, rpn.handle, xin.ptr, B, ctypes.byref(o), stage_arr, ctypes.byref(fo),
+                       ctypes.byref(rreq), ctypes.byref(req) if req is not None else None, mode),
+                    "rn_model_forward_proposals", self.ctx.handle)
+        elif rois is None:
             fn = L.lib().rn_model_forward_fpn_u8 if u8 else L.lib().rn_model_forward_fpn
             L.check(fn(self.handle, neck.handle, xin.ptr, B, ctypes.byref(o), stage_arr, ctypes.byref(fo), mode),
                     "rn_model_forward_fpn", self.ctx.handle)
@@ -539,7 +559,11 @@ class NativeModel:
                 out[name] = _down_raw(b, np.uint64, B * k).astype(np.int64).reshape(B, k)
             else:
                 out[name] = _down_raw(b, np.float32, int(np.prod(shapes[name]))).reshape(shapes[name])
-        if rois is not None:
+        if rpn is not None:
+            got = rpn.collect(rspec, rbufs)
+            out.update({key: got[key] for key in ("proposals", "scores", "proposal_levels", "cand") if key in got})
+            out["rois"], out["proposal_count"], out["proposal_logits"] = got["raw"]["rois"], got["raw"]["count"], got["raw"]["logits"]
+        if pooler is not None:
             out["pooled"] = _down_raw(pooled, np.float32, K * neck.out_channels * PH * PW).reshape(K, neck.out_channels, PH, PW)
             if roi_levels:
                 out["roi_levels"] = _down_raw(lv, np.int32, K)

@@ -1096,3 +1096,128 @@ def roi_align_bf16(maps_nhwc, rois, scales, output_size, sampling_ratio: int = 2
     output is fp32."""
     return _roi_align(L.RN_DTYPE_BF16, np.uint16, maps_nhwc, rois, scales, output_size, sampling_ratio, aligned, thresholds,
                       return_levels)
+
+
+# ---------------------------------------------------------------------------
+# RPN proposals behind the head (rn_rpn.hip); the contract in numpy is rpn.py's
+# ---------------------------------------------------------------------------
+def box_decode_ref(anchors, deltas, weights=(1.0, 1.0, 1.0, 1.0), image_size=(np.inf, np.inf)) -> np.ndarray:
+    from . import rpn
+    return rpn.decode_ref(anchors, deltas, weights, image_size)
+
+
+def nms_ref(boxes, iou_threshold: float, valid=None) -> np.ndarray:
+    from . import rpn
+    return rpn.nms_ref(boxes, iou_threshold, valid)
+
+
+def nms_segments_ref(boxes, iou_threshold: float, valid=None) -> np.ndarray:
+    boxes = np.asarray(boxes, dtype=np.float32)
+    return np.stack([nms_ref(boxes[s], iou_threshold, None if valid is None else valid[s]) for s in range(boxes.shape[0])])
+
+
+def box_decode(anchors, deltas, weights=(1.0, 1.0, 1.0, 1.0), image_size=(np.inf, np.inf)) -> np.ndarray:
+    """rn_box_decode_forward, one launch: anchors [N,4] + deltas [N,4] -> boxes [N,4] fp32, BoxCoder.decode_single
+    with `weights` then the clip to image_size (H, W); box_decode_ref up to the device's expf."""
+    from .tensor import _DeviceBuffer
+    ctx = get_ctx()
+    a = np.ascontiguousarray(anchors, dtype=np.float32).reshape(-1, 4)
+    d = np.ascontiguousarray(deltas, dtype=np.float32).reshape(-1, 4)
+    assert a.shape == d.shape, (a.shape, d.shape)
+    N = a.shape[0]
+    da, dd, out = _up_raw(a), _up_raw(d), _DeviceBuffer(ctx, max(N * 16, 16))
+    L.check(L.lib().rn_box_decode_forward(ctx.handle, da.ptr, dd.ptr, N, *[float(v) for v in weights], float(image_size[0]),
+                                          float(image_size[1]), out.ptr), "rn_box_decode_forward", ctx.handle)
+    ctx.sync()
+    return _down_raw(out, np.float32, N * 4).reshape(N, 4)
+
+
+def nms_segments(boxes, iou_threshold: float, valid=None, return_count: bool = False):
+    """rn_nms_forward, two launches: S segments of n <= 4096 boxes [S,n,4], each already in score order, valid [S,n]
+    or None -> keep, bool [S,n], bit for bit nms_segments_ref (and the kept count of every segment)."""
+    from .tensor import _DeviceBuffer
+    ctx = get_ctx()
+    b = np.ascontiguousarray(boxes, dtype=np.float32)
+    assert b.ndim == 3 and b.shape[2] == 4, b.shape
+    S, n = b.shape[:2]
+    db = _up_raw(b)
+    dv = _up_raw(np.ascontiguousarray(valid).astype(np.uint8).reshape(S, n)) if valid is not None else None
+    keep, cnt = _DeviceBuffer(ctx, max(S * n, 16)), _DeviceBuffer(ctx, max(S * 4, 16))
+    L.check(L.lib().rn_nms_forward(ctx.handle, db.ptr, dv.ptr if dv else None, S, n, float(iou_threshold), keep.ptr, cnt.ptr),
+            "rn_nms_forward", ctx.handle)
+    ctx.sync()
+    k = _down_raw(keep, np.uint8, S * n).reshape(S, n).astype(bool)
+    return (k, _down_raw(cnt, np.int32, S)) if return_count else k
+
+
+def nms(boxes, scores, iou_threshold: float) -> np.ndarray:
+    """torchvision.ops.nms: the indices of the boxes greedy NMS keeps, in descending score (ties: the lower index
+    first; the host sorts, the device suppresses).  n <= 4096."""
+    from . import rpn
+    b = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 4)
+    order = rpn.select_ref(scores, b.shape[0])
+    if order.size == 0:
+        return order
+    return order[nms_segments(b[order][None], iou_threshold)[0]]
+
+
+def _cand_buffers(ctx, B, n_levels, pre):
+    from .tensor import _DeviceBuffer
+    rows = B * n_levels * pre
+    spec = (("index", np.int32, rows, (B, n_levels, pre)), ("logit", np.float32, rows, (B, n_levels, pre)),
+            ("box", np.float32, rows * 4, (B, n_levels, pre, 4)), ("valid", np.uint8, rows, (B, n_levels, pre)),
+            ("count", np.int32, B * n_levels, (B, n_levels)))
+    bufs = {k: _DeviceBuffer(ctx, max(n * np.dtype(t).itemsize, 16)) for k, t, n, _ in spec}
+    return spec, bufs, L.RpnCandidates(*[bufs[k].ptr for k, *_ in spec])
+
+
+def _select_decode_launch(ctx, heads, base, image_size, pre, min_size, logit_thresh):
+    heads = [np.ascontiguousarray(hd, dtype=np.float32) for hd in heads]
+    base = np.ascontiguousarray(base, dtype=np.float32)
+    n_levels, A = base.shape[:2]
+    B = heads[0].shape[0]
+    P = (5 * A + 3) // 4 * 4
+    assert len(heads) == n_levels and all(hd.ndim == 4 and hd.shape[0] == B and hd.shape[3] == P for hd in heads), \
+        [hd.shape for hd in heads]
+    dh = [_up_raw(hd) for hd in heads]
+    spec, bufs, cand = _cand_buffers(ctx, B, n_levels, int(pre))
+    L.check(L.lib().rn_rpn_select_decode_forward(
+        ctx.handle, n_levels, (ctypes.c_void_p * n_levels)(*[d.ptr for d in dh]), B,
+        (ctypes.c_uint64 * n_levels)(*[hd.shape[1] for hd in heads]), (ctypes.c_uint64 * n_levels)(*[hd.shape[2] for hd in heads]),
+        A, base.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), int(image_size[0]), int(image_size[1]), int(pre),
+        float(min_size), float(logit_thresh), ctypes.byref(cand)), "rn_rpn_select_decode_forward", ctx.handle)
+    return dh, spec, bufs, cand
+
+
+def rpn_select_decode(heads, base_anchors, image_size, pre_nms_top_n: int, min_size: float = 1e-3,
+                      logit_thresh: float = -np.inf) -> dict:
+    """rn_rpn_select_decode_forward, one launch: heads one host [B,h,w,P] per level, base_anchors [L,A,4] -> the
+    candidates per (image, level, rank): "index" int32, "logit", "box", "valid" (bytes) and "count" [B,L]; index,
+    logit and count bit for bit rpn.select_decode_ref's, box within test_rpn_host.decode_bound of rpn.decode_f64."""
+    ctx = get_ctx()
+    _dh, spec, bufs, _cand = _select_decode_launch(ctx, heads, base_anchors, image_size, pre_nms_top_n, min_size, logit_thresh)
+    ctx.sync()
+    return {k: _down_raw(bufs[k], t, n).reshape(shape) for k, t, n, shape in spec}
+
+
+def rpn_proposals(heads, base_anchors, image_size, pre_nms_top_n: int, post_nms_top_n: int, nms_thresh: float,
+                  min_size: float = 1e-3, logit_thresh: float = -np.inf):
+    """rn_rpn_select_decode_forward and rn_rpn_nms_merge_forward, three launches, nothing leaving the device in
+    between: (candidates as rpn_select_decode returns them, proposals): "boxes" [B,post,4], "logits", "levels" int32,
+    "count" [B], "rois" [B*post,5], "cand_keep" [B,L,pre]; the proposals bit for bit rpn.nms_merge_ref of the
+    candidates."""
+    from .tensor import _DeviceBuffer
+    ctx = get_ctx()
+    pre, post = int(pre_nms_top_n), int(post_nms_top_n)
+    _dh, spec, bufs, cand = _select_decode_launch(ctx, heads, base_anchors, image_size, pre, min_size, logit_thresh)
+    B, n_levels = spec[0][3][0], spec[0][3][1]
+    ospec = (("boxes", np.float32, B * post * 4, (B, post, 4)), ("logits", np.float32, B * post, (B, post)),
+             ("levels", np.int32, B * post, (B, post)), ("count", np.int32, B, (B,)),
+             ("rois", np.float32, B * post * 5, (B * post, 5)), ("cand_keep", np.uint8, B * n_levels * pre, (B, n_levels, pre)))
+    obufs = {k: _DeviceBuffer(ctx, max(n * np.dtype(t).itemsize, 16)) for k, t, n, _ in ospec}
+    out = L.RpnProposals(*[obufs[k].ptr for k, *_ in ospec])
+    L.check(L.lib().rn_rpn_nms_merge_forward(ctx.handle, ctypes.byref(cand), B, n_levels, pre, post, float(nms_thresh),
+                                             ctypes.byref(out)), "rn_rpn_nms_merge_forward", ctx.handle)
+    ctx.sync()
+    return ({k: _down_raw(bufs[k], t, n).reshape(shape) for k, t, n, shape in spec},
+            {k: _down_raw(obufs[k], t, n).reshape(shape) for k, t, n, shape in ospec})
