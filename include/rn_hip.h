@@ -1166,6 +1166,104 @@ RN_API int rn_model_forward_proposals(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, con
 RN_API int rn_model_forward_proposals_u8(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, const uint8_t *input_nhwc, uint64_t B,
                                          const rn_model_outputs *outs, const int *stages, const rn_fpn_outputs *fpn_out,
                                          const rn_rpn_request *req, const rn_roi_pool *rois, int mode);
+/* ---- The box head behind the pooler: FC layers, class scores, per-class NMS, the merge (rn_detect.hip) ----------------
+ * torchvision's TwoMLPHead, FastRCNNPredictor and RoIHeads.postprocess_detections in eval mode.  The post-processing
+ * is rn_detect_postprocess_forward: THREE launches whatever B, R and C (score + decode; per-class sort + NMS; merge).
+ * The arithmetic is a contract, restated in numpy in detection.py; every fp32 operation is rounded on its own and none
+ * is fused; min and max are the RPN section's.  B images; R = 1..4096 RoIs per image; K = B*R rows, image b owns rows
+ * b*R .. b*R + R - 1 (rn_rpn_proposals.rois with R = post_nms_top_n); C = 2..1024 classes, background 0 included;
+ * D = detections_per_img = 1..1024.
+ *   Head:     [K, P] fp32, P = 5C rounded up to a multiple of 4; column c is the logit of class c, column C + 4c + j
+ *             delta j of class c (torchvision's bbox_pred row 4c + j).
+ *   Score:    p[k][c] is rn_softmax_forward's probability of the C logits of row k, bit for bit: the launch has that
+ *             kernel's block shape and shares its statistics' code (one max, one summation order, one division).
+ *   Decode:   for c >= 1 the RPN section's Decode of RoI k's box (x1, y1, x2, y2) with class c's deltas and the
+ *             request's weights (torchvision: 10, 10, 5, 5); the clip constant and the clamp to W, H are unchanged;
+ *             expf stays the one operation that is not bit-defined.
+ *   Valid:    the row is real (its RoI image index equals b; the RPN's padding rows carry -1) && p > score_thresh
+ *             (STRICT, as torchvision) && x2 - x1 >= min_size && y2 - y1 >= min_size (torchvision: 1e-2); a NaN
+ *             anywhere fails.  Class 0 is never valid.
+ *   NMS:      per (image, class c >= 1) the valid candidates in the order (p descending, r ascending), -0 == +0, and
+ *             on them the NMS of the RPN section.  This is torchvision's nms on the unshifted boxes of a class
+ *             (_batched_nms_vanilla); it is NOT the coordinate-offset form batched_nms takes below 4000 boxes, whose
+ *             shifted coordinates round differently.
+ *   Merge:    per image the survivors of all classes in the order (p descending, f ascending), f = r*(C-1) + (c-1)
+ *             (torchvision's flattened index after it drops the background column); the first D are the detections.
+ * rn_detections: boxes [B,D,4], scores [B,D], labels [B,D] int32, roi [B,D] int32 (the row r a detection came from),
+ * count [B] int32; any may be NULL, not all five.  Rows at or past count hold box 0, score 0, label -1, roi -1.
+ * Optional intermediates, row-major by RoI: probs [K,C], class_boxes [K,C,4], valid [K,C] bytes, keep [K,C] bytes (the
+ * candidates NMS left); column 0 is written as box 0, valid 0, keep 0.  Every row of every output that is not NULL is
+ * written on every call.
+ * Scratch is O(B*C*R) -- 12 bytes per (RoI, class), the class boxes where the caller does not take them, a count per
+ * (image, class); there is no IoU mask -- in the context's scratch, which grows on demand: never during a capture, not
+ * while a captured graph lives.  No floating-point atomics and no atomics on global memory.  Asynchronous on the
+ * context's stream.  B == 0: RN_OK, nothing launched.  RN_ERR_INVALID, nothing launched, rn_last_error names the
+ * operand: a NULL operand, an operand of 4-byte elements off a 4-byte boundary, an output sharing a byte with another
+ * operand, a parameter out of range (R, C, D as above; B at most 65535; B*R below 2^31; image_h, image_w 1 .. 2^24 - 1;
+ * weights positive and finite), a NaN threshold. */
+typedef struct rn_detections {
+    float *boxes;
+    float *scores;
+    int32_t *labels;
+    int32_t *roi;
+    int32_t *count;
+    float *probs;       /* optional intermediates from here on */
+    float *class_boxes;
+    uint8_t *valid;
+    uint8_t *keep;
+} rn_detections;
+typedef struct rn_detect_request {
+    float score_thresh, nms_thresh, min_size;
+    uint64_t detections_per_img;
+    float weights[4]; /* wx, wy, ww, wh */
+    rn_detections out;
+} rn_detect_request;
+RN_API int rn_detect_postprocess_forward(rn_ctx *ctx, const float *head /* [K,P] */, const float *rois /* [K,5] */,
+                                         uint64_t B, uint64_t R, uint64_t C, uint64_t image_h, uint64_t image_w,
+                                         const rn_detect_request *req);
+/* The box head as an object, modelled on rn_rpn: rn_box_head_create(ctx, &bh, in_features = a*PH*PW, representation
+ * (both multiples of 64), classes); rn_box_head_set_tensor takes "box_head.fc6.weight|bias", "box_head.fc7.weight|bias",
+ * "box_predictor.cls_score.weight|bias", "box_predictor.bbox_pred.weight|bias" (host fp32, torch.nn.Linear's [out, in]);
+ * rn_box_head_finalize packs three 1x1 panels: fc6, fc7 and ONE panel of cls_score with bbox_pred and zero rows up to P;
+ * the biases are the epilogues' shifts and ReLU sits on fc6 and fc7: exact.  rn_box_head_forward runs three contractions
+ * and the three launches above on pooled [K, a, PH, PW] fp32 (16-byte aligned), which already is the row-major
+ * [K, in_features] matrix in torchvision's flatten(1) order: read in place, no transpose, no copy.  fp32 only.  A contraction is one
+ * launch, or two where its plan finishes a chunked K sum in a second pass (few rows under a long K), so a forward is 6 to
+ * 9 launches: the count depends on the contraction's plan for (K rows, in_features, representation), never on B, R or C
+ * behind the head.
+ * head_out (nullable): the head output [K, P], copied out of the object's scratch.  The scratch (the FC outputs, the head
+ * output, the stage's) grows on demand: never during a capture, not while a captured graph lives.  Refused as the
+ * stand-alone op, and: an output sharing a byte with pooled, rois or head_out. */
+typedef struct rn_box_head rn_box_head;
+RN_API int rn_box_head_create(rn_ctx *ctx, rn_box_head **out, uint64_t in_features, uint64_t representation,
+                              uint64_t classes);
+RN_API int rn_box_head_set_tensor(rn_box_head *bh, const char *key, const float *host_data, uint64_t numel);
+RN_API int rn_box_head_finalize(rn_box_head *bh);
+RN_API int rn_box_head_destroy(rn_box_head *bh);
+RN_API int rn_box_head_forward(rn_box_head *bh, const float *pooled, const float *rois, uint64_t B, uint64_t R,
+                               uint64_t image_h, uint64_t image_w, const rn_detect_request *req,
+                               float *head_out /* nullable */);
+/* The box head behind the neck and inside a forward.  rn_fpn_forward_detections: rn_fpn_forward_proposals plus the box
+ * head and its request; rn_model_forward_detections(_u8): rn_model_forward_proposals(_u8)'s arguments plus them.  Both
+ * require the chained pooler (rois->rois_dev == req->out.rois and rois->K == B * post_nms_top_n) and a pooled on a
+ * 16-byte boundary; R is post_nms_top_n and the image the neck call's image_h x image_w resp. the model's input size.
+ * Each part of a launch batch runs the head on exactly its own rows of pooled and of the RoIs, behind its own pooler
+ * launch, from its own slice of the box head's scratch, and writes its own [b] rows (one profile record "box_stage" of
+ * layer "roi_heads").  Refused like the proposals' calls, and: a box head whose in_features is not a * PH * PW, a
+ * request out of range, an output of the request sharing a byte with any other output of the call (the rpn's, the
+ * pooler's, an exported level, a head output).  Every other forward kind issues exactly the launches it issued. */
+RN_API int rn_fpn_forward_detections(rn_fpn *fpn, rn_rpn *rpn, rn_box_head *bh, const void *const *x_nhwc, uint64_t B,
+                                     const uint64_t *h, const uint64_t *w, float *const *out_nchw /* nullable */,
+                                     uint64_t image_h, uint64_t image_w, const rn_rpn_request *req,
+                                     const rn_roi_pool *rois, const rn_detect_request *det_req);
+RN_API int rn_model_forward_detections(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, rn_box_head *bh, const float *input_nchw,
+                                       uint64_t B, const rn_model_outputs *outs /* nullable */, const int *stages,
+                                       const rn_fpn_outputs *fpn_out /* nullable */, const rn_rpn_request *req,
+                                       const rn_roi_pool *rois, const rn_detect_request *det_req, int mode);
+RN_API int rn_model_forward_detections_u8(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, rn_box_head *bh, const uint8_t *input_nhwc,
+                                          uint64_t B, const rn_model_outputs *outs, const int *stages,
+                                          const rn_fpn_outputs *fpn_out, const rn_rpn_request *req,
+                                          const rn_roi_pool *rois, const rn_detect_request *det_req, int mode);
 /* Run one forward, then time every tile candidate of every convolution at batch B on the
  * device (events on the context's stream, on the buffers that forward used) and remember the fastest per layer for
  * that batch size.  Results do not change (candidates are bit-identical), only speed. */

@@ -79,6 +79,19 @@ class RpnRequest(ctypes.Structure):
                 ("min_size", c_float), ("out", RpnProposals), ("cand", RpnCandidates)]
 
 
+class Detections(ctypes.Structure):
+    """rn_detections: device pointers of boxes [B,D,4], scores [B,D], labels and roi int32 [B,D], count int32 [B] (any may
+    be NULL, not all five) and the optional intermediates probs [K,C], class_boxes [K,C,4], valid and keep bytes [K,C]."""
+    _fields_ = [("boxes", c_void_p), ("scores", c_void_p), ("labels", c_void_p), ("roi", c_void_p), ("count", c_void_p),
+                ("probs", c_void_p), ("class_boxes", c_void_p), ("valid", c_void_p), ("keep", c_void_p)]
+
+
+class DetectRequest(ctypes.Structure):
+    """rn_detect_request: the thresholds, detections_per_img, the decode's weights and the outputs"""
+    _fields_ = [("score_thresh", c_float), ("nms_thresh", c_float), ("min_size", c_float), ("detections_per_img", c_uint64),
+                ("weights", c_float * 4), ("out", Detections)]
+
+
 class Epilogue(ctypes.Structure):
     _fields_ = [("scale", c_void_p), ("shift", c_void_p), ("residual", c_void_p),
                 ("relu", c_int)]
@@ -270,6 +283,21 @@ SIGNATURES = {
                                            POINTER(FpnOutputs), POINTER(RpnRequest), POINTER(RoiPool), c_int]),
     "rn_model_forward_proposals_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, u64, POINTER(ModelOutputs), POINTER(c_int),
                                               POINTER(FpnOutputs), POINTER(RpnRequest), POINTER(RoiPool), c_int]),
+    "rn_detect_postprocess_forward": (c_int, [c_void_p, fptr, fptr, u64, u64, u64, u64, u64, POINTER(DetectRequest)]),
+    "rn_box_head_create": (c_int, [c_void_p, POINTER(c_void_p), u64, u64, u64]),
+    "rn_box_head_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, u64]),
+    "rn_box_head_finalize": (c_int, [c_void_p]),
+    "rn_box_head_destroy": (c_int, [c_void_p]),
+    "rn_box_head_forward": (c_int, [c_void_p, fptr, fptr, u64, u64, u64, u64, POINTER(DetectRequest), fptr]),
+    "rn_fpn_forward_detections": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_void_p), u64, POINTER(u64), POINTER(u64),
+                                          POINTER(c_void_p), u64, u64, POINTER(RpnRequest), POINTER(RoiPool),
+                                          POINTER(DetectRequest)]),
+    "rn_model_forward_detections": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, fptr, u64, POINTER(ModelOutputs),
+                                            POINTER(c_int), POINTER(FpnOutputs), POINTER(RpnRequest), POINTER(RoiPool),
+                                            POINTER(DetectRequest), c_int]),
+    "rn_model_forward_detections_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, u64, POINTER(ModelOutputs),
+                                               POINTER(c_int), POINTER(FpnOutputs), POINTER(RpnRequest), POINTER(RoiPool),
+                                               POINTER(DetectRequest), c_int]),
     "rn_model_destroy": (c_int, [c_void_p]),
     "rn_model_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, u64]),
     "rn_model_load_dir": (c_int, [c_void_p, c_char_p]),

@@ -523,10 +523,12 @@ namespace {
     } while (0)
 
 // rn_fpn_forward (fn names it; rp NULL, out_nchw needed), rn_fpn_forward_rois (rp needed, out_nchw may be NULL) and
-// rn_fpn_forward_proposals (rpn and req needed, rp and out_nchw may be NULL)
+// rn_fpn_forward_proposals (rpn and req needed, rp and out_nchw may be NULL); rn_fpn_forward_detections: those plus the
+// box head and its request behind the chained pooler
 int fpn_forward(const char *fn, bool with_rois, rn_fpn *f, const void *const *x_nhwc, uint64_t B, const uint64_t *h,
                 const uint64_t *w, float *const *out_nchw, const rn_roi_pool *rp, rn_rpn *rpn = NULL,
-                const rn_rpn_request *req = NULL, uint64_t image_h = 0, uint64_t image_w = 0)
+                const rn_rpn_request *req = NULL, uint64_t image_h = 0, uint64_t image_w = 0, rn_box_head *bh = NULL,
+                const rn_detect_request *dreq = NULL)
 {
     static float *const none[kFpnMaxLevels + 1] = {NULL, NULL, NULL, NULL, NULL};
     if (!f) return RN_ERR_INVALID;
@@ -582,9 +584,17 @@ int fpn_forward(const char *fn, bool with_rois, rn_fpn *f, const void *const *x_
             RN_TRY(rn_rpn_clear_of(rpn, ctx, req, B, rp->levels_out, rp->K * 4));
         }
     }
+    if (bh) {  // the box head behind the chained pooler: its outputs against the maps and every exported level as well
+        RN_TRY(rn_box_head_chain_check(bh, ctx, fn, dreq, B, rpn, req, rp, f->a, image_h, image_w));
+        const uint64_t R = req->post_nms_top_n;
+        for (int i = 0; i < n; ++i)
+            RN_TRY(rn_box_head_clear_of(bh, ctx, dreq, B, R, x_nhwc[i], B * h[i] * w[i] * f->cin[i] * rn_elem_size(f->dtype)));
+        for (int i = 0; i < n_out; ++i) RN_TRY(rn_box_head_clear_of(bh, ctx, dreq, B, R, out_nchw[i], B * f->a * hl[i] * wl[i] * sizeof(float)));
+    }
     if (B == 0) return RN_OK;
     RN_TRY(rn_fpn_reserve(f, B, h, w));
     if (rpn) RN_TRY(rn_rpn_reserve(rpn, B, hl, wl, req->pre_nms_top_n));
+    if (bh) RN_TRY(rn_box_head_reserve(bh, B, req->post_nms_top_n));
     const int saved_layout = ctx->layout;
     ctx->layout = RN_LAYOUT_NHWC;
     const bool pool = f->extra && (out_nchw[n] || rpn);
@@ -598,6 +608,7 @@ int fpn_forward(const char *fn, bool with_rois, rn_fpn *f, const void *const *x_
         if (out_nchw[i]) st = rn_fpn_step(f, ctx, RN_FPN_EXPORT, i, NULL, 0, B, h, w, out_nchw[i]);
     if (rpn && st == RN_OK) st = rn_fpn_rpn_step(f, rpn, ctx, 0, 0, B, h, w, image_h, image_w, req);
     if (rp && st == RN_OK) st = rn_fpn_roi_step(f, ctx, rp, scales, thr, 0, 0, B, B, h, w);
+    if (bh && st == RN_OK) st = rn_box_head_step(bh, ctx, rp->pooled, rp->rois_dev, 0, 0, B, req->post_nms_top_n, image_h, image_w, dreq);
     ctx->layout = saved_layout;
     return st;
 }
@@ -625,6 +636,15 @@ int rn_fpn_forward_proposals(rn_fpn *f, rn_rpn *rpn, const void *const *x_nhwc, 
     if (f && !rpn) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: rpn is NULL", __func__);
     if (f && !req) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: req is NULL", __func__);
     return fpn_forward(__func__, false, f, x_nhwc, B, h, w, out_nchw, rois, rpn, req, image_h, image_w);
+}
+
+int rn_fpn_forward_detections(rn_fpn *f, rn_rpn *rpn, rn_box_head *bh, const void *const *x_nhwc, uint64_t B, const uint64_t *h,
+                              const uint64_t *w, float *const *out_nchw, uint64_t image_h, uint64_t image_w,
+                              const rn_rpn_request *req, const rn_roi_pool *rois, const rn_detect_request *det_req)
+{
+    if (f && (!rpn || !req)) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: rpn or req is NULL", __func__);
+    if (f && (!bh || !det_req)) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: the box head or its request is NULL", __func__);
+    return fpn_forward(__func__, false, f, x_nhwc, B, h, w, out_nchw, rois, rpn, req, image_h, image_w, bh, det_req);
 }
 
 }  // extern "C"

@@ -14,18 +14,15 @@
 //     so round j simply takes the first element that comes AFTER round j-1's winner: nothing is
 //     struck out, nothing is stored per element;
 //   - loads and stores are dwords: any 4-byte boundary, the same bits.  No atomics, no scratch.
+// The statistics of the softmax (RN_HEAD_SOFTMAX_STATS) and head_prob live in rn_box_dev.h: the box head's class scores
+// (rn_detect.hip) are these bits because they are this code.
+#include "rn_box_dev.h"
 #include "rn_internal.h"
 #include "rn_private.h"
 
 namespace {
 
-constexpr int kHeadBlock = 256;
-constexpr int kHeadWaves = kHeadBlock / 64;
-constexpr uint32_t kHeadLdsRow = 4096;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
-
-// the one expression of a probability
-__device__ __forceinline__ float head_prob(float x, float mx, float sum) { return expf(x - mx) / sum; }
 
 // NaN ranks as -inf (argmax_kernel's rule)
 __device__ __forceinline__ float head_rank(float v) { return v != v ? -INFINITY : v; }
@@ -56,21 +53,7 @@ __global__ __launch_bounds__(kHeadBlock) void head_kernel(const float *x, float 
         mx = fmaxf(mx, v);
     }
     float sum = 0.f;
-    if (soft) {
-        for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-        if (lane == 0) red_v[wave] = mx;
-        __syncthreads();
-        mx = red_v[0];
-        for (int w = 1; w < kHeadWaves; ++w) mx = fmaxf(mx, red_v[w]);
-        __syncthreads();
-        // pass 2: the sum, in the one order described above
-        for (uint32_t i = tid; i < classes; i += kHeadBlock) sum += expf((in_lds ? srow[i] : row[i]) - mx);
-        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
-        if (lane == 0) red_v[wave] = sum;
-        __syncthreads();
-        sum = red_v[0];
-        for (int w = 1; w < kHeadWaves; ++w) sum += red_v[w];
-    }
+    if (soft) RN_HEAD_SOFTMAX_STATS(row, classes, in_lds, srow, red_v, tid, lane, wave, mx, sum);
     __syncthreads();  // srow is complete; red_v is free again
 
     // top-k: round j takes the first element after (pv, pi) in the order

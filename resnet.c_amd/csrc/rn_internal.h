@@ -34,7 +34,7 @@ struct rn_ctx {
     void *debug_stamps;  // diagnostic phase stamps of the contraction kernel, normally null
     // scratch grown on demand (never inside a graph capture; callers that capture
     // warm up first so the sizes are already settled)
-    void *scratch[7];  // 0 batch-norm constants, 1-3 NCHW convolution, 4 split-K partial sums, 5 resize tables, 6 NMS mask
+    void *scratch[7];  // 0 batch-norm constants, 1-3 NCHW convolution, 4 split-K partial sums, 5 resize tables, 6 NMS mask / detection stage
     uint64_t scratch_bytes[7];
     // resident blocks per CU of each contraction-kernel instantiation on THIS context's device, one per row of
     // the kernel table of rn_conv.hip, asked once per context (0 = not asked yet); no process-wide mutable state

@@ -193,6 +193,9 @@ struct rn_model {
     rn_rpn *rpn;
     const rn_rpn_request *rpn_req;
     int roi_chain;
+    /* rn_model_forward_detections: the box head behind the chained pooler and its request (NULL in every other forward) */
+    rn_box_head *box_head;
+    const rn_detect_request *det_req;
     float roi_scales[4], roi_thr[3];
     uint64_t roi_images;
     /* tile tuning: calls of the last forward, and the batch size the tiles were tuned for */
@@ -1536,6 +1539,13 @@ static int op_fpn_rest(rn_model *m, uint64_t B)
         TRY(rn_fpn_roi_step_rows(m->fpn, m->run.ctx, m->roi, m->roi_scales, m->roi_thr, m->run.sub0, m->run.img0, B,
                                  m->roi_images, m->fpn_h, m->fpn_w, m->run.img0 * post, B * post));
         TRY(prof_end(m));
+        if (m->box_head) { /* this part's own rows, behind its own pooler launch: three contractions and three launches */
+            const uint64_t feat = m->fpn_a * m->roi->PH * m->roi->PW, row0 = m->run.img0 * post;
+            TRY(prof_begin(m, "box_stage", "roi_heads", 0.0, (double)(B * post * feat) * 4.0));
+            TRY(rn_box_head_step(m->box_head, m->run.ctx, m->roi->pooled + row0 * feat, m->roi->rois_dev + row0 * 5, m->run.sub0,
+                                 m->run.img0, B, post, m->H, m->W, m->det_req));
+            TRY(prof_end(m));
+        }
     } else if (m->roi && m->roi->K > 0) {
         /* bytes: the outputs only.  What the RoIs gather is several times that (profiles/roi_align) but depends on every
          * box's size against its level, which the host does not look at: the record's GB/s is the OUTPUT rate */
@@ -1925,7 +1935,7 @@ int rn_model_forward_segment_u8(rn_model *m, rn_seg_head *hd, const uint8_t *inp
  * passed, cleared on every way out (run_blocks asks m->fpn). */
 static int forward_fpn(rn_model *m, rn_fpn *fpn, const void *input, int in_u8, uint64_t B, const rn_model_outputs *outs,
                        const int *stages, const rn_fpn_outputs *fo, const rn_roi_pool *roi, int mode, rn_rpn *rpn,
-                       const rn_rpn_request *req)
+                       const rn_rpn_request *req, rn_box_head *bh, const rn_detect_request *dreq)
 {
     uint64_t hl[5], wl[5];
     int chain = 0;
@@ -2005,11 +2015,24 @@ static int forward_fpn(rn_model *m, rn_fpn *fpn, const void *input, int in_u8, u
             TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, roi->levels_out, roi->K * 4));
         }
     }
+    if (bh) { /* the box head behind the chained pooler: its request against every other output of the call */
+        const uint64_t R = req ? req->post_nms_top_n : 0;
+        TRY(rn_box_head_chain_check(bh, m->ctx, "rn_model_forward_detections", dreq, B, rpn, req, roi, a, m->H, m->W));
+        for (j = 0; j < n + extra; ++j) TRY(rn_box_head_clear_of(bh, m->ctx, dreq, B, R, fo->level[j], B * a * hl[j] * wl[j] * sizeof(float)));
+        if (outs) {
+            TRY(rn_box_head_clear_of(bh, m->ctx, dreq, B, R, outs->logits, B * m->classes * sizeof(float)));
+            TRY(rn_box_head_clear_of(bh, m->ctx, dreq, B, R, outs->features, B * m->feat * sizeof(float)));
+            TRY(rn_box_head_clear_of(bh, m->ctx, dreq, B, R, outs->probs, B * m->classes * sizeof(float)));
+            TRY(rn_box_head_clear_of(bh, m->ctx, dreq, B, R, outs->topk_prob, B * outs->k * sizeof(float)));
+            TRY(rn_box_head_clear_of(bh, m->ctx, dreq, B, R, outs->topk_idx, B * outs->k * sizeof(uint64_t)));
+        }
+    }
     if (!input || B == 0 || (mode != RN_FWD_REFERENCE_OPS && mode != RN_FWD_FUSED)) return RN_ERR_INVALID;
     if (m->dtype != RN_DTYPE_F32 && mode != RN_FWD_FUSED)
         return rn_ctx_set_error(m->ctx, RN_ERR_UNSUPPORTED, "rn_model_forward_fpn: a bf16 model runs RN_FWD_FUSED only");
     TRY(rn_fpn_reserve(fpn, B < m->max_sub ? B : m->max_sub, h, w));
     if (rpn) TRY(rn_rpn_reserve(rpn, B < m->max_sub ? B : m->max_sub, hl, wl, req->pre_nms_top_n));
+    if (bh) TRY(rn_box_head_reserve(bh, B < m->max_sub ? B : m->max_sub, req->post_nms_top_n));
     memset(&none, 0, sizeof(none));
     if (!outs) outs = &none;
     m->fpn = fpn;
@@ -2017,6 +2040,7 @@ static int forward_fpn(rn_model *m, rn_fpn *fpn, const void *input, int in_u8, u
     m->roi = roi;
     m->roi_images = B;
     m->rpn = rpn, m->rpn_req = req, m->roi_chain = chain;
+    m->box_head = bh, m->det_req = dreq;
     m->fpn_n = n, m->fpn_extra = extra, m->fpn_a = a;
     for (j = 0; j < n; ++j) m->fpn_stage[j] = stages[j], m->fpn_h[j] = h[j], m->fpn_w[j] = w[j];
     st = forward_outputs(m, input, in_u8, B, outs->logits, outs, mode, 0);
@@ -2024,6 +2048,7 @@ static int forward_fpn(rn_model *m, rn_fpn *fpn, const void *input, int in_u8, u
     m->fpn_out = NULL;
     m->roi = NULL;
     m->rpn = NULL, m->rpn_req = NULL, m->roi_chain = 0;
+    m->box_head = NULL, m->det_req = NULL;
     m->maps_done = 0;
     return st;
 }
@@ -2031,27 +2056,27 @@ static int forward_fpn(rn_model *m, rn_fpn *fpn, const void *input, int in_u8, u
 int rn_model_forward_fpn(rn_model *m, rn_fpn *fpn, const float *input_nchw, uint64_t B, const rn_model_outputs *outs,
                          const int *stages, const rn_fpn_outputs *fpn_out, int mode)
 {
-    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, NULL, mode, NULL, NULL);
+    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, NULL, mode, NULL, NULL, NULL, NULL);
 }
 
 int rn_model_forward_fpn_u8(rn_model *m, rn_fpn *fpn, const uint8_t *input_nhwc, uint64_t B, const rn_model_outputs *outs,
                             const int *stages, const rn_fpn_outputs *fpn_out, int mode)
 {
-    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, NULL, mode, NULL, NULL);
+    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, NULL, mode, NULL, NULL, NULL, NULL);
 }
 
 int rn_model_forward_rois(rn_model *m, rn_fpn *fpn, const float *input_nchw, uint64_t B, const rn_model_outputs *outs,
                           const int *stages, const rn_fpn_outputs *fpn_out, const rn_roi_pool *rois, int mode)
 {
     if (m && !rois) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_rois: rois is NULL");
-    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, rois, mode, NULL, NULL);
+    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, rois, mode, NULL, NULL, NULL, NULL);
 }
 
 int rn_model_forward_rois_u8(rn_model *m, rn_fpn *fpn, const uint8_t *input_nhwc, uint64_t B, const rn_model_outputs *outs,
                              const int *stages, const rn_fpn_outputs *fpn_out, const rn_roi_pool *rois, int mode)
 {
     if (m && !rois) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_rois: rois is NULL");
-    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, rois, mode, NULL, NULL);
+    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, rois, mode, NULL, NULL, NULL, NULL);
 }
 
 int rn_model_forward_proposals(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, const float *input_nchw, uint64_t B,
@@ -2059,7 +2084,7 @@ int rn_model_forward_proposals(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, const floa
                                const rn_rpn_request *req, const rn_roi_pool *rois, int mode)
 {
     if (m && (!rpn || !req)) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_proposals: rpn or req is NULL");
-    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, rois, mode, rpn, req);
+    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, rois, mode, rpn, req, NULL, NULL);
 }
 
 int rn_model_forward_proposals_u8(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, const uint8_t *input_nhwc, uint64_t B,
@@ -2067,7 +2092,27 @@ int rn_model_forward_proposals_u8(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, const u
                                   const rn_rpn_request *req, const rn_roi_pool *rois, int mode)
 {
     if (m && (!rpn || !req)) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_proposals: rpn or req is NULL");
-    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, rois, mode, rpn, req);
+    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, rois, mode, rpn, req, NULL, NULL);
+}
+
+int rn_model_forward_detections(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, rn_box_head *bh, const float *input_nchw, uint64_t B,
+                                const rn_model_outputs *outs, const int *stages, const rn_fpn_outputs *fpn_out,
+                                const rn_rpn_request *req, const rn_roi_pool *rois, const rn_detect_request *det_req, int mode)
+{
+    if (m && (!rpn || !req)) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_detections: rpn or req is NULL");
+    if (m && (!bh || !det_req))
+        return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_detections: the box head or its request is NULL");
+    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, rois, mode, rpn, req, bh, det_req);
+}
+
+int rn_model_forward_detections_u8(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, rn_box_head *bh, const uint8_t *input_nhwc, uint64_t B,
+                                   const rn_model_outputs *outs, const int *stages, const rn_fpn_outputs *fpn_out,
+                                   const rn_rpn_request *req, const rn_roi_pool *rois, const rn_detect_request *det_req, int mode)
+{
+    if (m && (!rpn || !req)) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_detections: rpn or req is NULL");
+    if (m && (!bh || !det_req))
+        return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_detections: the box head or its request is NULL");
+    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, rois, mode, rpn, req, bh, det_req);
 }
 
 /* The decoded-image route resizes to 256 and crops 224 x 224: a model of another size refuses it. */

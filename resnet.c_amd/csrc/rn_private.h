@@ -135,6 +135,28 @@ int rn_fpn_roi_step_rows(rn_fpn *fpn, rn_ctx *ctx, const rn_roi_pool *rp, const 
                          uint64_t sub0, uint64_t img0, uint64_t B, uint64_t images, const uint64_t *h, const uint64_t *w,
                          uint64_t row0, uint64_t rows);
 
+/* ---- rn_detect.hip: the box head behind the pooler, mirroring rn_rpn_* ---- */
+/* 1 when the box head is finalized, lives on ctx's device and reads in_features values per RoI; *why otherwise */
+int rn_box_head_matches(const rn_box_head *bh, const rn_ctx *ctx, uint64_t in_features, const char **why);
+/* the object's scratch for `images` images of R RoIs each */
+int rn_box_head_reserve(rn_box_head *bh, uint64_t images, uint64_t R);
+/* every refusal that concerns the request alone, for a forward of `images` images of R RoIs (text in ctx) */
+int rn_box_head_check(const rn_box_head *bh, rn_ctx *ctx, const rn_detect_request *req, uint64_t images, uint64_t R,
+                      uint64_t image_h, uint64_t image_w);
+/* RN_ERR_INVALID when an output of the request shares a byte with [other, other + other_bytes) */
+int rn_box_head_clear_of(const rn_box_head *bh, rn_ctx *ctx, const rn_detect_request *req, uint64_t images, uint64_t R,
+                         const void *other, uint64_t other_bytes);
+/* every refusal of a forward that runs the box head behind the rpn and the pooler of the same call (fn names the entry
+ * point): the chained pooler, pooled on a 16-byte boundary, a head that reads a * PH * PW values, the request, and its
+ * outputs against pooled, the RoIs, levels_out and every output of the rpn's request */
+int rn_box_head_chain_check(const rn_box_head *bh, rn_ctx *ctx, const char *fn, const rn_detect_request *req, uint64_t B,
+                            const rn_rpn *rpn, const rn_rpn_request *rpn_req, const rn_roi_pool *rois, uint64_t a,
+                            uint64_t image_h, uint64_t image_w);
+/* the stage's launches (three contractions of one or two launches each, then three) on ctx for the B images from the caller's image img0 on, whose scratch starts sub0 images
+ * into the object's tensors; pooled [B*R, in_features] and rois [B*R, 5]: the rows of these B images */
+int rn_box_head_step(rn_box_head *bh, rn_ctx *ctx, const float *pooled, const float *rois, uint64_t sub0, uint64_t img0,
+                     uint64_t B, uint64_t R, uint64_t image_h, uint64_t image_w, const rn_detect_request *req);
+
 /* ---- rn_stem.hip ---- */
 /* 1 when the fused stem + max-pool launch takes a padded image of Hp x Wp (nchw: the NCHW-fetching form on
  * an image of Hp - 6 x Wp - 6) of `dtype`: its documented conditions on the geometry alone */

@@ -8,7 +8,7 @@
 //   rn_box_decode_forward: BoxCoder.decode on its own, the same device function.
 // The reference classifies whole images only; nothing here has a counterpart in it.
 //
-// Order.  A selection orders 64-bit keys that are unique by construction: a monotone image of the logit in the high
+// Order (the code: rn_box_dev.h, shared with rn_detect.hip).  A selection orders 64-bit keys that are unique by construction: a monotone image of the logit in the high
 // word (NaN as -inf, -0 as +0), the complement of the index in the low word -- so "greater key" IS rn_topk_forward's
 // "(v_i, i) precedes (v_j, j)".  rpn_select_sort finds the k-th key exactly with an MSB-first radix select (8 passes
 // of 8 bits, a 256-bin histogram in LDS), gathers the k keys at or above it into LDS and sorts them with a bitonic
@@ -17,6 +17,7 @@
 #include <math.h>
 #include <string.h>
 
+#include "rn_box_dev.h"
 #include "rn_conv_params.h"
 #include "rn_internal.h"
 #include "rn_private.h"
@@ -27,127 +28,9 @@
 
 namespace {
 
-constexpr uint32_t kRpnBlock = 1024;  // select + decode and merge: one block per segment / image
-constexpr uint32_t kRpnMaxK = 4096;   // keys a selection holds in LDS (32 KiB)
 constexpr int kRpnMaxLevels = 5;
 constexpr int kRpnMaxAnchors = 12;
 constexpr int kNmsScratchSlot = 6;    // the context's scratch slot of the IoU mask
-
-struct sel_smem {
-    uint64_t keys[kRpnMaxK];
-    uint32_t hist[256];
-    uint64_t prefix;
-    uint32_t remaining, fill;
-};
-
-// the contract's min and max: a NaN first operand stays (torch.clamp's and numpy's rule)
-__device__ __forceinline__ float rpn_min(float a, float b) { return a > b ? b : a; }
-__device__ __forceinline__ float rpn_max(float a, float b) { return a < b ? b : a; }
-
-__device__ __forceinline__ uint32_t rpn_mono(float v)
-{
-    uint32_t u = __float_as_uint(v);
-    if (v != v) u = 0xFF800000u;   // a NaN ranks as -inf
-    if (u == 0x80000000u) u = 0u;  // -0 == +0
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // never 0: -inf is 0x007FFFFF
-}
-
-__device__ __forceinline__ uint64_t rpn_key(float v, uint32_t index) { return ((uint64_t)rpn_mono(v) << 32) | (uint32_t)~index; }
-
-// Block-wide.  key_at(i), i < n, gives element i's key; keys are unique except for 0, which marks an absent element.
-// want: 1 <= want <= min(number of nonzero keys, kRpnMaxK).  Afterwards s.keys[0 .. want) are the `want` greatest
-// keys, descending.
-template <typename KeyAt>
-__device__ void rpn_select_sort(sel_smem &s, uint32_t n, uint32_t want, KeyAt key_at)
-{
-    const uint32_t tid = threadIdx.x, nt = blockDim.x;
-    uint64_t kth = 0;  // want == n: every key is taken
-    if (want < n) {
-        uint64_t prefix = 0;
-        uint32_t rem = want;
-        for (int pass = 7; pass >= 0; --pass) {
-            const int shift = pass * 8;
-            if (tid < 256) s.hist[tid] = 0;
-            __syncthreads();
-            for (uint32_t i = tid; i < n; i += nt) {
-                const uint64_t key = key_at(i);
-                if (pass == 7 || (key >> (shift + 8)) == prefix) atomicAdd(&s.hist[(uint32_t)(key >> shift) & 255u], 1u);
-            }
-            __syncthreads();
-            if (tid < 64) {  // wave 0: the digit whose bin holds the rem-th key from the top
-                uint32_t c[4], tot = 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) c[j] = s.hist[4 * tid + j], tot += c[j];
-                uint32_t incl = tot;  // keys in this lane's bins and all higher ones
-                for (uint32_t off = 1; off < 64; off <<= 1) {
-                    const uint32_t v = __shfl_down(incl, off, 64);
-                    if (tid + off < 64) incl += v;
-                }
-                uint32_t above = incl - tot;
-                if (above < rem && rem <= incl) {  // exactly one lane
-                    int d = 0;
-                    bool found = false;
-#pragma unroll
-                    for (int j = 3; j >= 0; --j) {
-                        if (found) continue;
-                        if (rem <= above + c[j]) d = j, found = true;
-                        else above += c[j];
-                    }
-                    s.prefix = (prefix << 8) | (uint64_t)(4 * tid + d);
-                    s.remaining = rem - above;
-                }
-            }
-            __syncthreads();
-            prefix = s.prefix, rem = s.remaining;
-        }
-        kth = prefix;
-    }
-    if (tid == 0) s.fill = 0;
-    __syncthreads();
-    for (uint32_t i = tid; i < n; i += nt) {
-        const uint64_t key = key_at(i);
-        if (key != 0 && key >= kth) {
-            const uint32_t slot = atomicAdd(&s.fill, 1u);
-            if (slot < kRpnMaxK) s.keys[slot] = key;
-        }
-    }
-    __syncthreads();
-    uint32_t P = 2;
-    while (P < want) P <<= 1;  // at most kRpnMaxK
-    for (uint32_t i = want + tid; i < P; i += nt) s.keys[i] = 0;
-    __syncthreads();
-    for (uint32_t size = 2; size <= P; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (uint32_t t = tid; t < P / 2; t += nt) {
-                const uint32_t lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-                const bool desc = (lo & size) == 0;
-                const uint64_t a = s.keys[lo], b = s.keys[hi];
-                if ((a < b) == desc) s.keys[lo] = b, s.keys[hi] = a;
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// ---- BoxCoder.decode_single + clip_boxes_to_image, the contract's "Decode" ----------------------------------
-struct decode_consts {
-    float wx, wy, ww, wh, clip, img_w, img_h;
-};
-
-__device__ __forceinline__ void rpn_decode(const float a[4], const float d[4], const decode_consts &k, float out[4])
-{
-    const float wa = a[2] - a[0], ha = a[3] - a[1];
-    const float cx = a[0] + 0.5f * wa, cy = a[1] + 0.5f * ha;
-    const float dx = d[0] / k.wx, dy = d[1] / k.wy;
-    const float dw = rpn_min(d[2] / k.ww, k.clip), dh = rpn_min(d[3] / k.wh, k.clip);
-    const float pcx = dx * wa + cx, pcy = dy * ha + cy;
-    const float pw = expf(dw) * wa, ph = expf(dh) * ha;
-    const float hw = 0.5f * pw, hh = 0.5f * ph;
-    out[0] = rpn_min(rpn_max(pcx - hw, 0.0f), k.img_w);
-    out[1] = rpn_min(rpn_max(pcy - hh, 0.0f), k.img_h);
-    out[2] = rpn_min(rpn_max(pcx + hw, 0.0f), k.img_w);
-    out[3] = rpn_min(rpn_max(pcy + hh, 0.0f), k.img_h);
-}
 
 __global__ __launch_bounds__(256) void box_decode_kernel(const float *anchors, const float *deltas, float *boxes, uint64_t N,
                                                          const decode_consts k)
@@ -262,11 +145,7 @@ __global__ __launch_bounds__(64) void nms_mask_kernel(const mask_args p)
     uint64_t word = 0;
     for (uint32_t q = 0; q < 64; ++q) {
         const uint32_t c = cbk * 64 + q;
-        const float u1 = cb[q][0], v1 = cb[q][1], u2 = cb[q][2], v2 = cb[q][3];
-        const float area_c = (u2 - u1) * (v2 - v1);
-        const float iw = (x2 < u2 ? x2 : u2) - (x1 > u1 ? x1 : u1), ih = (y2 < v2 ? y2 : v2) - (y1 > v1 ? y1 : v1);
-        const float inter = (iw > 0.0f ? iw : 0.0f) * (ih > 0.0f ? ih : 0.0f);
-        const float iou = inter / (area + area_c - inter);
+        const float iou = rpn_iou(x1, y1, x2, y2, area, cb[q][0], cb[q][1], cb[q][2], cb[q][3]);
         if (c > row && c < cnt && iou > p.thresh) word |= 1ull << q;
     }
     p.words[((uint64_t)sgm * p.n + row) * p.nw + cbk] = word;

@@ -155,7 +155,8 @@ class FeaturePyramidNetwork:
         return int(c.value), int(h.value), int(w.value)
 
     def forward(self, maps_nhwc, levels=None, *, rois=None, pooler=None, image_size=None, roi_levels: bool = False,
-                validate: bool = True, rpn=None, candidates: bool = False) -> Dict[str, np.ndarray]:
+                validate: bool = True, rpn=None, candidates: bool = False, box_head=None,
+                detect_intermediates: bool = False) -> Dict[str, np.ndarray]:
         """maps_nhwc: one host array [B,h_i,w_i,in_i] fp32 per level, finest first (a bf16 neck rounds them on upload;
         uint16 bf16 bit patterns are taken as they are) -> {"0": [B,a,h_0,w_0] fp32, ..., "pool": ...}, the names in
         `levels` only (default: all).  With rois ([K,5] fp32: image index, x1, y1, x2, y2 in pixels of the input image),
@@ -165,7 +166,9 @@ class FeaturePyramidNetwork:
         With rpn (rpn.RegionProposalNetwork over all of the neck's outputs) and image_size: rn_fpn_forward_proposals,
         which adds per image "proposals", "scores", "proposal_levels" (and "cand" with candidates=True); with a pooler
         and no rois the pooler takes the proposals of the same call on the device: "pooled" is [B*post,a,PH,PW] and
-        "rois" [B*post,5] comes with it.  Synchronous convenience."""
+        "rois" [B*post,5] comes with it.  With box_head (detection.BoxHead) behind that rpn and pooler (no rois):
+        rn_fpn_forward_detections, which adds "boxes", "scores" (the proposals' go to "proposal_scores"), "labels",
+        "detections" and "detection_rois" (and the intermediates with detect_intermediates).  Synchronous convenience."""
         from .ops import _down_raw, _up_raw, to_bf16_bits
         from .tensor import _DeviceBuffer
         n = len(self.in_channels_list)
@@ -212,10 +215,22 @@ class FeaturePyramidNetwork:
                 pooled = _DeviceBuffer(self.ctx, max(K * self.out_channels * PH * PW * 4, 16))
                 lv = _DeviceBuffer(self.ctx, max(K * 4, 16)) if roi_levels else None
                 req = pooler.request(self.names, drois.ptr, K, image_size, pooled.ptr, lv.ptr if lv else None)
-            L.check(L.lib().rn_fpn_forward_proposals(self.handle, rpn.handle, xp, B, hp, wp, op, int(image_size[0]),
-                                                     int(image_size[1]), ctypes.byref(rreq),
-                                                     ctypes.byref(req) if req is not None else None),
-                    "rn_fpn_forward_proposals", self.ctx.handle)
+            if box_head is not None:
+                if pooler is None or rois is not None:
+                    raise ValueError("box_head needs a pooler that takes the proposals of the same call (no rois)")
+                dspec, dbufs = box_head.buffers(B, rpn.post, detect_intermediates)
+                dreq = box_head.request(dbufs)
+                L.check(L.lib().rn_fpn_forward_detections(self.handle, rpn.handle, box_head.handle, xp, B, hp, wp, op,
+                                                          int(image_size[0]), int(image_size[1]), ctypes.byref(rreq),
+                                                          ctypes.byref(req), ctypes.byref(dreq)),
+                        "rn_fpn_forward_detections", self.ctx.handle)
+            else:
+                L.check(L.lib().rn_fpn_forward_proposals(self.handle, rpn.handle, xp, B, hp, wp, op, int(image_size[0]),
+                                                         int(image_size[1]), ctypes.byref(rreq),
+                                                         ctypes.byref(req) if req is not None else None),
+                        "rn_fpn_forward_proposals", self.ctx.handle)
+        elif box_head is not None:
+            raise ValueError("box_head needs an rpn and a pooler")
         elif rois is None:
             L.check(L.lib().rn_fpn_forward(self.handle, xp, B, hp, wp, op), "rn_fpn_forward", self.ctx.handle)
         else:
@@ -238,6 +253,9 @@ class FeaturePyramidNetwork:
             out["pooled"] = _down_raw(pooled, np.float32, K * self.out_channels * PH * PW).reshape(K, self.out_channels, PH, PW)
             if roi_levels:
                 out["roi_levels"] = _down_raw(lv, np.int32, K)
+        if box_head is not None:
+            out["proposal_scores"] = out.pop("scores")
+            out.update(box_head.collect(dspec, dbufs))
         return out
 
     def close(self) -> None:

@@ -458,7 +458,8 @@ class NativeModel:
 
     def forward_fpn(self, x: np.ndarray, neck, stages=STAGES, levels=None, *, logits: bool = False,
                     features: bool = False, probs: bool = False, topk: int = 0, fused: bool = True, rois=None,
-                    pooler=None, roi_levels: bool = False, validate: bool = True, rpn=None, candidates: bool = False) -> dict:
+                    pooler=None, roi_levels: bool = False, validate: bool = True, rpn=None, candidates: bool = False,
+                    box_head=None, detect_intermediates: bool = False) -> dict:
         """One forward with a feature pyramid neck (rn_model_forward_fpn; torchvision's resnet_fpn_backbone): an
         ordered dict "0", "1", .. (one per stage in `stages`, finest first), then "pool" when the neck has the extra
         block -> [B,a,H,W] fp32; then the head outputs asked for, as forward_outputs returns them.  neck: an
@@ -474,7 +475,11 @@ class NativeModel:
         With rpn (rpn.RegionProposalNetwork over all of the neck's outputs): rn_model_forward_proposals, which adds per
         image "proposals" ([count_i, 4]), "scores" and "proposal_levels" (and "cand" with candidates=True); with a
         pooler and no rois the pooler takes the proposals of the same forward on the device: "pooled" is
-        [B*post,a,PH,PW] and "rois" [B*post,5] is returned with it."""
+        [B*post,a,PH,PW] and "rois" [B*post,5] is returned with it.
+        With box_head (detection.BoxHead) behind that rpn and pooler (no rois): rn_model_forward_detections, which adds
+        "boxes" [B,D,4], "scores" [B,D] (in place of the proposals' scores, which stay under "proposal_scores"), "labels",
+        "detections" (the counts [B]) and "detection_rois" (the proposal row of every detection), padded as the device
+        wrote them; with detect_intermediates also "probs", "class_boxes", "valid" and "keep"."""
         from .ops import _down_raw, _up_raw
         from .tensor import _DeviceBuffer
         stages = tuple(stages)
@@ -532,10 +537,22 @@ class NativeModel:
                 pooled = _DeviceBuffer(self.ctx, max(K * neck.out_channels * PH * PW * 4, 16))
                 lv = _DeviceBuffer(self.ctx, max(K * 4, 16)) if roi_levels else None
                 req = pooler.request(names, drois.ptr, K, self.input_size, pooled.ptr, lv.ptr if lv else None)
-            fn = L.lib().rn_model_forward_proposals_u8 if u8 else L.lib().rn_model_forward_proposals
-            L.check(fn(self.handle, neck.handle, rpn.handle, xin.ptr, B, ctypes.byref(o), stage_arr, ctypes.byref(fo),
-                       ctypes.byref(rreq), ctypes.byref(req) if req is not None else None, mode),
-                    "rn_model_forward_proposals", self.ctx.handle)
+            if box_head is not None:
+                if pooler is None or rois is not None:
+                    raise ValueError("box_head needs a pooler that takes the proposals of the same forward (no rois)")
+                dspec, dbufs = box_head.buffers(B, rpn.post, detect_intermediates)
+                dreq = box_head.request(dbufs)
+                fn = L.lib().rn_model_forward_detections_u8 if u8 else L.lib().rn_model_forward_detections
+                L.check(fn(self.handle, neck.handle, rpn.handle, box_head.handle, xin.ptr, B, ctypes.byref(o), stage_arr,
+                           ctypes.byref(fo), ctypes.byref(rreq), ctypes.byref(req), ctypes.byref(dreq), mode),
+                        "rn_model_forward_detections", self.ctx.handle)
+            else:
+                fn = L.lib().rn_model_forward_proposals_u8 if u8 else L.lib().rn_model_forward_proposals
+                L.check(fn(self.handle, neck.handle, rpn.handle, xin.ptr, B, ctypes.byref(o), stage_arr, ctypes.byref(fo),
+                           ctypes.byref(rreq), ctypes.byref(req) if req is not None else None, mode),
+                        "rn_model_forward_proposals", self.ctx.handle)
+        elif box_head is not None:
+            raise ValueError("box_head needs an rpn and a pooler")
         elif rois is None:
             fn = L.lib().rn_model_forward_fpn_u8 if u8 else L.lib().rn_model_forward_fpn
             L.check(fn(self.handle, neck.handle, xin.ptr, B, ctypes.byref(o), stage_arr, ctypes.byref(fo), mode),
@@ -567,6 +584,9 @@ class NativeModel:
             out["pooled"] = _down_raw(pooled, np.float32, K * neck.out_channels * PH * PW).reshape(K, neck.out_channels, PH, PW)
             if roi_levels:
                 out["roi_levels"] = _down_raw(lv, np.int32, K)
+        if box_head is not None:
+            out["proposal_scores"] = out.pop("scores")
+            out.update(box_head.collect(dspec, dbufs))
         return out
 
     def forward_fpn_u8(self, px: np.ndarray, neck, stages=STAGES, levels=None, **kw) -> dict:

@@ -1221,3 +1221,30 @@ def rpn_proposals(heads, base_anchors, image_size, pre_nms_top_n: int, post_nms_
     ctx.sync()
     return ({k: _down_raw(bufs[k], t, n).reshape(shape) for k, t, n, shape in spec},
             {k: _down_raw(obufs[k], t, n).reshape(shape) for k, t, n, shape in ospec})
+
+
+# ---------------------------------------------------------------------------
+# The box head's post-processing (rn_detect.hip); the contract in numpy is detection.py's
+# ---------------------------------------------------------------------------
+def detect_postprocess(head, rois, B: int, C: int, image_size, score_thresh: float = 0.05, nms_thresh: float = 0.5,
+                       detections_per_img: int = 100, weights=(10.0, 10.0, 5.0, 5.0), min_size: float = 1e-2,
+                       intermediates: bool = False) -> dict:
+    """rn_detect_postprocess_forward, three launches: head [K,P] and rois [K,5] host arrays of B images (K = B*R) ->
+    "boxes" [B,D,4], "scores", "labels", "roi" int32 [B,D], "count" [B]; with intermediates also "probs" [K,C],
+    "class_boxes" [K,C,4], "valid" and "keep" [K,C].  Bit for bit detection.postprocess_ref on the device's own
+    probabilities and class boxes."""
+    from . import detection
+    from .tensor import _DeviceBuffer
+    ctx = get_ctx()
+    h = np.ascontiguousarray(head, dtype=np.float32)
+    r = np.ascontiguousarray(rois, dtype=np.float32).reshape(-1, 5)
+    K = h.shape[0]
+    assert h.shape == (K, detection.head_pitch(C)) and r.shape[0] == K and B > 0 and K % B == 0, (h.shape, r.shape, B, C)
+    dh, dr = _up_raw(h), _up_raw(r)
+    spec = detection.output_spec(B, K // B, C, int(detections_per_img), intermediates)
+    bufs = {k: _DeviceBuffer(ctx, max(int(np.prod(sh)) * np.dtype(t).itemsize, 16)) for k, (t, sh) in spec.items()}
+    req = detection.make_request(bufs, score_thresh, nms_thresh, min_size, detections_per_img, weights)
+    L.check(L.lib().rn_detect_postprocess_forward(ctx.handle, dh.ptr, dr.ptr, B, K // B, C, int(image_size[0]), int(image_size[1]),
+                                                  ctypes.byref(req)), "rn_detect_postprocess_forward", ctx.handle)
+    ctx.sync()
+    return {k: _down_raw(bufs[k], t, int(np.prod(sh))).reshape(sh) for k, (t, sh) in spec.items()}
