@@ -286,33 +286,6 @@ det_scratch det_carve(void *base, uint64_t cap, uint64_t sub0, uint64_t R, uint6
     return d;
 }
 
-struct operand {
-    const void *ptr;
-    uint64_t bytes;
-    const char *name;
-    bool output;
-    bool bytes_only;  // an array of bytes: any boundary
-};
-
-// every operand on a 4-byte boundary (arrays of bytes: any) and no output sharing a byte with another operand
-int check_operands(rn_ctx *ctx, const char *fn, const operand *ops, int n_ops)
-{
-    for (int i = 0; i < n_ops; ++i) {
-        if (!ops[i].ptr) continue;
-        if (!ops[i].bytes_only && (reinterpret_cast<uintptr_t>(ops[i].ptr) & 3) != 0)
-            return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s is off a 4-byte boundary", fn, ops[i].name);
-    }
-    for (int i = 0; i < n_ops; ++i) {
-        if (!ops[i].ptr || !ops[i].output) continue;
-        for (int j = 0; j < n_ops; ++j) {
-            if (j == i || !ops[j].ptr || (ops[j].output && j < i)) continue;
-            if (rn_overlap(ops[i].ptr, ops[i].bytes, ops[j].ptr, ops[j].bytes))
-                return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s overlaps %s", fn, ops[i].name, ops[j].name);
-        }
-    }
-    return RN_OK;
-}
-
 constexpr int kDetOutputs = 9;
 
 // the request's outputs for `images` images as operands
@@ -590,44 +563,12 @@ int rn_box_head_check(const rn_box_head *h, rn_ctx *ctx, const rn_detect_request
     return check_operands(ctx, "rn_box_head request", ops, kDetOutputs);
 }
 
-// RN_ERR_INVALID when an output of the request shares a byte with [other, other + other_bytes)
-int rn_box_head_clear_of(const rn_box_head *h, rn_ctx *ctx, const rn_detect_request *q, uint64_t images, uint64_t R,
-                         const void *other, uint64_t other_bytes)
+int rn_box_head_operands(const rn_box_head *h, const rn_detect_request *q, uint64_t images, uint64_t R,
+                         rn_operand ops[RN_BOX_HEAD_OPERANDS])
 {
-    if (!q || !other || other_bytes == 0) return RN_OK;
-    operand ops[kDetOutputs];
+    static_assert(RN_BOX_HEAD_OPERANDS == kDetOutputs, "the box head's operands are its request's outputs");
     det_outputs(&q->out, images, R, h->C, q->detections_per_img, ops);
-    for (int i = 0; i < kDetOutputs; ++i)
-        RN_REQUIRE(ctx, !ops[i].ptr || !rn_overlap(ops[i].ptr, ops[i].bytes, other, other_bytes),
-                   "an output of the box head's request overlaps another operand of the call");
-    return RN_OK;
-}
-
-// Every refusal of a forward that runs the box head behind the rpn and the pooler of the same call (text in ctx,
-// fn names the entry point): the chained pooler (rp->rois_dev == rq->out.rois, K == B * post_nms_top_n), a pooled on a
-// 16-byte boundary, a head that reads a * PH * PW values, the request, and its outputs against pooled, the RoIs,
-// levels_out and every output of the rpn's request.
-int rn_box_head_chain_check(const rn_box_head *h, rn_ctx *ctx, const char *fn, const rn_detect_request *q, uint64_t B,
-                            const rn_rpn *rpn, const rn_rpn_request *rq, const rn_roi_pool *rp, uint64_t a, uint64_t image_h,
-                            uint64_t image_w)
-{
-    const char *why = NULL;
-    if (!rpn || !rq) why = "the box head needs the rpn and its request";
-    else if (!rp || rp->K == 0) why = "the box head needs the pooler";
-    else if (rp->rois_dev != rq->out.rois || rp->K != B * rq->post_nms_top_n)
-        why = "the box head needs the chained pooler (rois_dev == req->out.rois, K == B * post_nms_top_n)";
-    else if ((reinterpret_cast<uintptr_t>(rp->pooled) & 15) != 0) why = "pooled is off a 16-byte boundary";
-    else rn_box_head_matches(h, ctx, a * rp->PH * rp->PW, &why);
-    if (why) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s", fn, why);
-    const uint64_t R = rq->post_nms_top_n;
-    RN_TRY(rn_box_head_check(h, ctx, q, B, R, image_h, image_w));
-    RN_TRY(rn_box_head_clear_of(h, ctx, q, B, R, rp->pooled, rp->K * h->F * sizeof(float)));
-    RN_TRY(rn_box_head_clear_of(h, ctx, q, B, R, rp->rois_dev, rp->K * 20));
-    RN_TRY(rn_box_head_clear_of(h, ctx, q, B, R, rp->levels_out, rp->K * 4));
-    operand ops[kDetOutputs];
-    det_outputs(&q->out, B, R, h->C, q->detections_per_img, ops);
-    for (int i = 0; i < kDetOutputs; ++i) RN_TRY(rn_rpn_clear_of(rpn, ctx, rq, B, ops[i].ptr, ops[i].bytes));
-    return RN_OK;
+    return kDetOutputs;
 }
 
 // The stage's launches (6 to 9: a contraction is one launch, or two where its plan finishes a chunked K sum in a second
@@ -668,11 +609,14 @@ int rn_box_head_forward(rn_box_head *h, const float *pooled, const float *rois, 
     RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(rois) & 3) == 0, "rois is off a 4-byte boundary");
     RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(head_out) & 3) == 0, "head_out is off a 4-byte boundary");
     const uint64_t K = B * R;
-    RN_TRY(rn_box_head_clear_of(h, ctx, req, B, R, pooled, K * h->F * sizeof(float)));
-    RN_TRY(rn_box_head_clear_of(h, ctx, req, B, R, rois, K * 20));
-    RN_TRY(rn_box_head_clear_of(h, ctx, req, B, R, head_out, K * h->P * sizeof(float)));
-    RN_REQUIRE(ctx, !head_out || (!rn_overlap(head_out, K * h->P * 4, pooled, K * h->F * 4) && !rn_overlap(head_out, K * h->P * 4, rois, K * 20)),
-               "head_out overlaps pooled or rois");
+    operand outs[kDetOutputs];
+    const operand own[3] = {{head_out, K * h->P * sizeof(float), "head_out", true, false},
+                            {pooled, K * h->F * sizeof(float), "pooled", false, false},
+                            {rois, K * 20, "rois", false, false}};
+    rn_box_head_operands(h, req, B, R, outs);
+    const rn_operand_group groups[2] = {{own, 3}, {outs, kDetOutputs}};
+    RN_TRY(check_operand_groups(ctx, __func__, groups, 2));
+    RN_TRY(check_operands(ctx, __func__, own, 3));  // head_out against pooled and rois
     RN_TRY(rn_box_head_reserve(h, B, R));
     const int saved_layout = ctx->layout;
     ctx->layout = RN_LAYOUT_NHWC;

@@ -412,10 +412,30 @@ int rn_fpn_step(rn_fpn *f, rn_ctx *ctx, int kind, int level, const void *x_nhwc,
 
 // ---- the pooler behind the neck (rn_roi.hip's kernel on the 3x3 outputs, in place) ----
 
-int rn_fpn_roi_check(const rn_fpn *f, rn_ctx *ctx, const rn_roi_pool *rp, const uint64_t *h, const uint64_t *w,
-                     float scales[4], float thr[3])
+// ---- one forward of the neck and what runs behind it (rn_private.h: rn_neck_call) ----
+
+namespace {
+
+// what follows the exports, after the kinds of rn_fpn_step
+enum { NECK_RPN = RN_FPN_EXPORT + 1, NECK_ROI, NECK_BOX };
+
+constexpr int kRoiOperands = 3;
+
+// the pooler's buffers as operands: pooled and levels_out are written, rois_dev is read
+void roi_operands(const rn_neck_call *c, operand ops[kRoiOperands])
 {
-    RN_REQUIRE(ctx, rp, "the pooler's request is NULL");
+    const rn_roi_pool *rp = c->roi;
+    ops[0] = {rp->pooled, rp->K * c->a * rp->PH * rp->PW * sizeof(float), "pooled", true, false};
+    ops[1] = {rp->levels_out, rp->K * 4, "levels_out", true, false};
+    ops[2] = {rp->rois_dev, rp->K * 5 * sizeof(float), "rois_dev", false, false};
+}
+
+// the pooler's request against the neck whose level i is an h[i] x w[i] map: every refusal that concerns the pooler
+// alone; fills the levels' scales (torchvision's infer_scale) and the thresholds between them
+int rn_fpn_roi_check(rn_neck_call *c, rn_ctx *ctx)
+{
+    const rn_fpn *f = c->fpn;
+    const rn_roi_pool *rp = c->roi;
     RN_REQUIRE(ctx, rp->n_levels >= 1 && rp->n_levels <= f->n, "the pooler reads 1 .. n_levels of the neck's levels");
     for (int i = 0; i < rp->n_levels; ++i)
         RN_REQUIRE(ctx, rp->level[i] >= 0 && rp->level[i] < f->n && (i == 0 || rp->level[i] > rp->level[i - 1]),
@@ -430,88 +450,212 @@ int rn_fpn_roi_check(const rn_fpn *f, rn_ctx *ctx, const rn_roi_pool *rp, const 
     RN_REQUIRE(ctx, rp->K < (1ull << 31), "K must be below 2^31");
     RN_REQUIRE(ctx, rp->K == 0 || rp->rois_dev, "rois_dev is NULL (K > 0)");
     RN_REQUIRE(ctx, rp->K == 0 || rp->pooled, "pooled is NULL (K > 0)");
-    RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(rp->rois_dev) & 3) == 0 && (reinterpret_cast<uintptr_t>(rp->pooled) & 3) == 0 &&
-                        (reinterpret_cast<uintptr_t>(rp->levels_out) & 3) == 0,
-               "rois_dev, pooled or levels_out is off a 4-byte boundary");
-    const uint64_t out_bytes = rp->K * f->a * rp->PH * rp->PW * sizeof(float);
-    RN_REQUIRE(ctx, rp->K == 0 || !rn_overlap(rp->pooled, out_bytes, rp->rois_dev, rp->K * 5 * sizeof(float)),
-               "pooled overlaps rois_dev");
-    RN_REQUIRE(ctx, rp->K == 0 || !rp->levels_out ||
-                        (!rn_overlap(rp->levels_out, rp->K * 4, rp->pooled, out_bytes) &&
-                         !rn_overlap(rp->levels_out, rp->K * 4, rp->rois_dev, rp->K * 5 * sizeof(float))),
-               "levels_out overlaps pooled or rois_dev");
-    // torchvision's infer_scale: the power of two nearest the level's height over the image's (it returns the first of
-    // the two axes' scales)
-    (void)w;
+    operand ops[kRoiOperands];
+    roi_operands(c, ops);
+    RN_TRY(check_operands(ctx, __func__, ops, kRoiOperands));
+    // the power of two nearest the level's height over the image's (infer_scale returns the first of the two axes' scales)
     for (int i = 0; i < rp->n_levels; ++i)
-        scales[i] = (float)exp2(rint(log2((double)h[rp->level[i]] / (double)rp->image_h)));
-    if (rn_roi_level_thresholds((uint64_t)rp->n_levels, scales, rp->canonical_scale, rp->canonical_level, thr) != RN_OK)
+        c->scales[i] = (float)exp2(rint(log2((double)c->h[rp->level[i]] / (double)rp->image_h)));
+    if (rn_roi_level_thresholds((uint64_t)rp->n_levels, c->scales, rp->canonical_scale, rp->canonical_level, c->thr) != RN_OK)
         return rn_set_error(ctx, RN_ERR_INVALID, "%s: the level thresholds cannot be formed", __func__);
     return RN_OK;
 }
 
-int rn_fpn_roi_step(rn_fpn *f, rn_ctx *ctx, const rn_roi_pool *rp, const float *scales, const float *thr,
-                    uint64_t sub0, uint64_t img0, uint64_t B, uint64_t images, const uint64_t *h, const uint64_t *w)
+// The pooler's launch on ctx for the B images from the caller's image img0 on, whose 3x3 outputs start sub0 images
+// into the neck's scratch, on rows row0 .. row0 + rows of rois_dev, pooled and levels_out.  A window of the whole
+// call's rows leaves the rows of other images to their parts' launches and writes the invalid rows (zeros, level -1)
+// where write_invalid; the chain gives a part its own rows, every one of which it writes.
+int neck_roi_step(const rn_neck_call *c, rn_ctx *ctx, uint64_t sub0, uint64_t img0, uint64_t B, uint64_t row0, uint64_t rows,
+                  int write_invalid)
 {
-    const void *maps[kFpnMaxLevels];
-    uint64_t hs[kFpnMaxLevels], ws[kFpnMaxLevels];
-    if (rp->K == 0) return RN_OK;
-    for (int i = 0; i < rp->n_levels; ++i) {
-        const int l = rp->level[i];
-        if ((sub0 + B) * h[l] * w[l] > f->cap_pix[l]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn: scratch not reserved");
-        maps[i] = f->outb[l] + sub0 * h[l] * w[l] * f->a, hs[i] = h[l], ws[i] = w[l];
-    }
-    return rn_roi_align_window(ctx, RN_DTYPE_F32, (uint64_t)rp->n_levels, maps, hs, ws, scales, thr, images, img0, B,
-                               img0 == 0, f->a, rp->rois_dev, rp->K, rp->PH, rp->PW, rp->sampling_ratio, rp->aligned,
-                               rp->pooled, rp->levels_out);
-}
-
-// the chain: the pooler of a part on that part's own proposals, rows row0 .. row0 + rows of rois_dev / pooled /
-// levels_out, every one of which it writes (the padding rows as zeros and level -1)
-int rn_fpn_roi_step_rows(rn_fpn *f, rn_ctx *ctx, const rn_roi_pool *rp, const float *scales, const float *thr, uint64_t sub0,
-                         uint64_t img0, uint64_t B, uint64_t images, const uint64_t *h, const uint64_t *w, uint64_t row0,
-                         uint64_t rows)
-{
+    const rn_fpn *f = c->fpn;
+    const rn_roi_pool *rp = c->roi;
     const void *maps[kFpnMaxLevels];
     uint64_t hs[kFpnMaxLevels], ws[kFpnMaxLevels];
     if (rows == 0) return RN_OK;
     for (int i = 0; i < rp->n_levels; ++i) {
         const int l = rp->level[i];
-        if ((sub0 + B) * h[l] * w[l] > f->cap_pix[l]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn: scratch not reserved");
-        maps[i] = f->outb[l] + sub0 * h[l] * w[l] * f->a, hs[i] = h[l], ws[i] = w[l];
+        if ((sub0 + B) * c->h[l] * c->w[l] > f->cap_pix[l]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn: scratch not reserved");
+        maps[i] = f->outb[l] + sub0 * c->h[l] * c->w[l] * f->a, hs[i] = c->h[l], ws[i] = c->w[l];
     }
-    return rn_roi_align_window(ctx, RN_DTYPE_F32, (uint64_t)rp->n_levels, maps, hs, ws, scales, thr, images, img0, B, 1, f->a,
-                               rp->rois_dev + row0 * 5, rows, rp->PH, rp->PW, rp->sampling_ratio, rp->aligned,
-                               rp->pooled + row0 * f->a * rp->PH * rp->PW, rp->levels_out ? rp->levels_out + row0 : NULL);
+    return rn_roi_align_window(ctx, RN_DTYPE_F32, (uint64_t)rp->n_levels, maps, hs, ws, c->scales, c->thr, c->images, img0, B,
+                               write_invalid, f->a, rp->rois_dev + row0 * 5, rows, rp->PH, rp->PW, rp->sampling_ratio,
+                               rp->aligned, rp->pooled + row0 * f->a * rp->PH * rp->PW,
+                               rp->levels_out ? rp->levels_out + row0 : NULL);
 }
 
 // the rpn's stage on the neck's 3x3 outputs and pooled level of B images, read in place sub0 images into the scratch
-int rn_fpn_rpn_step(rn_fpn *f, rn_rpn *rpn, rn_ctx *ctx, uint64_t sub0, uint64_t img0, uint64_t B, const uint64_t *h,
-                    const uint64_t *w, uint64_t image_h, uint64_t image_w, const rn_rpn_request *req)
+int neck_rpn_step(const rn_neck_call *c, rn_ctx *ctx, uint64_t sub0, uint64_t img0, uint64_t B)
 {
+    const rn_fpn *f = c->fpn;
     const float *lv[kFpnMaxLevels + 1];
-    uint64_t hl[kFpnMaxLevels + 1], wl[kFpnMaxLevels + 1];
-    const int n = f->n, n_out = n + f->extra;
-    for (int i = 0; i < n_out; ++i) {
-        const int l = i < n ? i : n - 1;
-        RN_TRY(rn_fpn_level_shape(f, i, h[l], w[l], NULL, &hl[i], &wl[i]));
-        if (i < n ? (sub0 + B) * hl[i] * wl[i] > f->cap_pix[i] : (sub0 + B) * hl[i] * wl[i] > f->cap_pool)
+    for (int i = 0; i < c->n + c->extra; ++i) {
+        if ((sub0 + B) * c->hl[i] * c->wl[i] > (i < c->n ? f->cap_pix[i] : f->cap_pool))
             return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn: scratch not reserved");
-        lv[i] = (i < n ? f->outb[i] : f->poolb) + sub0 * hl[i] * wl[i] * f->a;
+        lv[i] = (i < c->n ? f->outb[i] : f->poolb) + sub0 * c->hl[i] * c->wl[i] * f->a;
     }
-    return rn_rpn_step(rpn, ctx, lv, sub0, img0, B, hl, wl, image_h, image_w, req);
+    return rn_rpn_step(c->rpn, ctx, lv, sub0, img0, B, c->hl, c->wl, c->image_h, c->image_w, c->rpn_req);
 }
 
-int rn_fpn_roi_clear_of(const rn_fpn *f, rn_ctx *ctx, const rn_roi_pool *rp, const void *other, uint64_t other_bytes)
+// step `step` of what follows the laterals: its kind and level (untouched when there is no such step); returns how
+// many steps there are.  The order of a forward is this function and nothing else.
+int neck_step_at(const rn_neck_call *c, int step, int *kind, int *level)
 {
-    if (!rp || rp->K == 0 || !other || other_bytes == 0) return RN_OK;
-    const uint64_t out_bytes = rp->K * f->a * rp->PH * rp->PW * sizeof(float);
-    RN_REQUIRE(ctx, !rn_overlap(rp->pooled, out_bytes, other, other_bytes), "pooled overlaps another output of the call");
-    RN_REQUIRE(ctx, !rp->levels_out || !rn_overlap(rp->levels_out, rp->K * 4, other, other_bytes),
-               "levels_out overlaps another output of the call");
-    RN_REQUIRE(ctx, !rn_overlap(rp->rois_dev, rp->K * 5 * sizeof(float), other, other_bytes),
-               "rois_dev overlaps an output of the call");
+    int at = 0;
+    const auto put = [&](int k, int l) {
+        if (at++ == step) *kind = k, *level = l;
+    };
+    for (int j = c->n - 1; j >= 1; --j) put(RN_FPN_TOPDOWN, j);
+    for (int j = 0; j < c->n; ++j)
+        if (c->layer_runs[j]) put(RN_FPN_LAYER, j);
+    if (c->pool) put(RN_FPN_POOL, c->n - 1);
+    for (int j = 0; j < c->n + c->extra; ++j)
+        if (c->out[j]) put(RN_FPN_EXPORT, j);
+    if (c->rpn) put(NECK_RPN, 0);
+    if (c->roi && c->roi->K > 0) put(NECK_ROI, 0);
+    if (c->box_head) put(NECK_BOX, 0);
+    return at;
+}
+
+}  // namespace
+
+const char *rn_fpn_op_name(const rn_fpn *f, int kind, int level)
+{
+    static const char *const names[4][kFpnMaxLevels] = {{"fpn_inner0", "fpn_inner1", "fpn_inner2", "fpn_inner3"},
+                                                        {NULL, "fpn_topdown1", "fpn_topdown2", "fpn_topdown3"},
+                                                        {"fpn_layer0", "fpn_layer1", "fpn_layer2", "fpn_layer3"},
+                                                        {"fpn_export0", "fpn_export1", "fpn_export2", "fpn_export3"}};
+    if (kind == RN_FPN_POOL) return "fpn_pool";
+    if (kind == RN_FPN_EXPORT) return level == f->n ? "fpn_export_pool" : names[3][level];
+    return names[kind][level];
+}
+
+int rn_neck_check(rn_neck_call *c, rn_ctx *ctx, const char *fn, const rn_operand *others, int n_others)
+{
+    static const char *const level_names[kFpnMaxLevels + 1] = {"level[0]", "level[1]", "level[2]", "level[3]", "level[4]"};
+    const rn_fpn *f = c->fpn;
+    const rn_roi_pool *rp = c->roi;
+    const uint64_t B = c->images;
+    const char *why = NULL;
+    if (!rn_fpn_matches(f, ctx, f ? f->dtype : 0, &why)) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s", fn, why);
+    c->n = f->n, c->extra = f->extra, c->a = f->a;
+    const int n = f->n, n_out = n + f->extra;
+    bool wanted = rp != NULL || c->rpn != NULL;
+    for (int i = 0; i < n_out; ++i) {
+        const int l = i < n ? i : n - 1;
+        RN_TRY(rn_fpn_level_shape(f, i, c->h[l], c->w[l], NULL, &c->hl[i], &c->wl[i]));
+        if ((reinterpret_cast<uintptr_t>(c->out[i]) & 3) != 0)
+            return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s of the outputs must be 4-byte aligned (it is off a 4-byte boundary)",
+                                fn, level_names[i]);
+        wanted = wanted || c->out[i];
+    }
+    if (!wanted) return rn_set_error(ctx, RN_ERR_INVALID, "%s: nothing wanted (every output level is NULL)", fn);
+    if (rp) RN_TRY(rn_fpn_roi_check(c, ctx));
+    if (c->rpn) {  // the rpn behind the neck reads every level's 3x3 output and the pooled level in place
+        if (!rn_rpn_matches(c->rpn, ctx, f->a, (uint64_t)n_out, &why)) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s", fn, why);
+        RN_TRY(rn_rpn_check(c->rpn, ctx, c->rpn_req, B, c->hl, c->wl, c->image_h, c->image_w));
+    }
+    // the chain: the pooler may read the RoIs this call writes, and only those
+    c->chain = c->rpn && rp && rp->K > 0 && rp->rois_dev == c->rpn_req->out.rois && rp->K == B * c->rpn_req->post_nms_top_n;
+    if (c->box_head) {  // behind the chained pooler, on its rows
+        if (!c->rpn || !c->rpn_req) why = "the box head needs the rpn and its request";
+        else if (!rp || rp->K == 0) why = "the box head needs the pooler";
+        else if (!c->chain) why = "the box head needs the chained pooler (rois_dev == req->out.rois, K == B * post_nms_top_n)";
+        else if ((reinterpret_cast<uintptr_t>(rp->pooled) & 15) != 0) why = "pooled is off a 16-byte boundary";
+        else rn_box_head_matches(c->box_head, ctx, f->a * rp->PH * rp->PW, &why);
+        if (why) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s", fn, why);
+        RN_TRY(rn_box_head_check(c->box_head, ctx, c->det_req, B, c->rpn_req->post_nms_top_n, c->image_h, c->image_w));
+    }
+    c->pool = f->extra && (c->out[n] || c->rpn);
+    for (int i = 0; i < n; ++i) c->layer_runs[i] = c->out[i] || (c->pool && i == n - 1) || c->rpn;
+    if (rp && rp->K > 0)
+        for (int i = 0; i < rp->n_levels; ++i) c->layer_runs[rp->level[i]] = 1;
+    // the operand matrix: every group against every group before it
+    operand levels[kFpnMaxLevels + 1], roi[kRoiOperands], rpn[RN_RPN_OPERANDS], box[RN_BOX_HEAD_OPERANDS];
+    for (int i = 0; i < n_out; ++i) levels[i] = {c->out[i], B * f->a * c->hl[i] * c->wl[i] * sizeof(float), level_names[i], true, false};
+    if (rp) roi_operands(c, roi);
+    if (c->rpn) rn_rpn_operands(c->rpn, c->rpn_req, B, rpn);
+    if (c->box_head) rn_box_head_operands(c->box_head, c->det_req, B, c->rpn_req->post_nms_top_n, box);
+    if (c->chain) roi[2].ptr = NULL;  // the one exception: rois_dev IS the rpn's out.rois, which stands for it below
+    const rn_operand_group groups[5] = {{others, n_others},
+                                        {levels, n_out},
+                                        {roi, rp ? kRoiOperands : 0},
+                                        {rpn, c->rpn ? RN_RPN_OPERANDS : 0},
+                                        {box, c->box_head ? RN_BOX_HEAD_OPERANDS : 0}};
+    return check_operand_groups(ctx, fn, groups, 5);
+}
+
+int rn_neck_reserve(const rn_neck_call *c, uint64_t images_at_once)
+{
+    RN_TRY(rn_fpn_reserve(c->fpn, images_at_once, c->h, c->w));
+    if (c->rpn) RN_TRY(rn_rpn_reserve(c->rpn, images_at_once, c->hl, c->wl, c->rpn_req->pre_nms_top_n));
+    if (c->box_head) RN_TRY(rn_box_head_reserve(c->box_head, images_at_once, c->rpn_req->post_nms_top_n));
     return RN_OK;
+}
+
+int rn_neck_plan(const rn_neck_call *c, uint64_t B, int step, const char **op, const char **layer, double *flops, double *bytes)
+{
+    int kind = -1, level = 0;
+    const int steps = neck_step_at(c, step, &kind, &level);
+    if (kind < 0) return steps;
+    const rn_roi_pool *rp = c->roi;
+    const uint64_t post = c->rpn ? c->rpn_req->post_nms_top_n : 0;
+    const char *name = NULL, *lay = "fpn";
+    double fl = 0.0, by = 0.0;
+    switch (kind) {
+    case NECK_RPN:  // 2 L + 3 launches under one record
+        name = "rpn_stage", lay = "rpn";
+        by = (double)(B * (uint64_t)(c->n + c->extra) * c->rpn_req->pre_nms_top_n) * 25.0;
+        break;
+    case NECK_ROI:
+        // bytes: the outputs only.  What the RoIs gather is several times that (profiles/roi_align) but depends on every
+        // box's size against its level, which the host does not look at: the record's GB/s is the OUTPUT rate
+        name = "roi_align";
+        if (c->chain) {
+            by = (double)(B * post * c->a * rp->PH * rp->PW) * 4.0;
+        } else {
+            const double outs = (double)(rp->K * c->a * rp->PH * rp->PW);
+            const double share = (double)B / (double)c->images;  // the RoIs are taken as spread evenly over the images
+            const double taps = 4.0 * (double)(rp->sampling_ratio * rp->sampling_ratio);
+            fl = share * outs * 2.0 * taps, by = share * outs * 4.0;
+        }
+        break;
+    case NECK_BOX:  // three contractions and three launches under one record
+        name = "box_stage", lay = "roi_heads";
+        by = (double)(B * post * (c->a * rp->PH * rp->PW)) * 4.0;
+        break;
+    default:
+        name = rn_fpn_op_name(c->fpn, kind, level);
+        rn_fpn_cost(c->fpn, kind, level, B, c->h, c->w, &fl, &by);
+    }
+    if (op) *op = name;
+    if (layer) *layer = lay;
+    if (flops) *flops = fl;
+    if (bytes) *bytes = by;
+    return steps;
+}
+
+int rn_neck_step(const rn_neck_call *c, rn_ctx *ctx, int step, uint64_t sub0, uint64_t img0, uint64_t B)
+{
+    int kind = -1, level = 0;
+    neck_step_at(c, step, &kind, &level);
+    const rn_roi_pool *rp = c->roi;
+    const uint64_t post = c->rpn ? c->rpn_req->post_nms_top_n : 0;
+    switch (kind) {
+    case -1: return rn_set_error(ctx, RN_ERR_INVALID, "rn_neck_step: no such step");
+    case NECK_RPN: return neck_rpn_step(c, ctx, sub0, img0, B);
+    case NECK_ROI:
+        if (c->chain) return neck_roi_step(c, ctx, sub0, img0, B, img0 * post, B * post, 1);  // this part's own proposals
+        return neck_roi_step(c, ctx, sub0, img0, B, 0, rp->K, img0 == 0);
+    case NECK_BOX: {  // this part's own rows, behind its own pooler launch
+        const uint64_t feat = c->a * rp->PH * rp->PW, row0 = img0 * post;
+        return rn_box_head_step(c->box_head, ctx, rp->pooled + row0 * feat, rp->rois_dev + row0 * 5, sub0, img0, B, post,
+                                c->image_h, c->image_w, c->det_req);
+    }
+    case RN_FPN_EXPORT:  // into the caller's buffer from image img0 on
+        return rn_fpn_step(c->fpn, ctx, kind, level, NULL, sub0, B, c->h, c->w, c->out[level] + img0 * c->a * c->hl[level] * c->wl[level]);
+    default: return rn_fpn_step(c->fpn, ctx, kind, level, NULL, sub0, B, c->h, c->w, NULL);
+    }
 }
 
 namespace {
@@ -522,93 +666,39 @@ namespace {
         if (!(cond)) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s", fn, (msg)); \
     } while (0)
 
-// rn_fpn_forward (fn names it; rp NULL, out_nchw needed), rn_fpn_forward_rois (rp needed, out_nchw may be NULL) and
-// rn_fpn_forward_proposals (rpn and req needed, rp and out_nchw may be NULL); rn_fpn_forward_detections: those plus the
-// box head and its request behind the chained pooler
-int fpn_forward(const char *fn, bool with_rois, rn_fpn *f, const void *const *x_nhwc, uint64_t B, const uint64_t *h,
-                const uint64_t *w, float *const *out_nchw, const rn_roi_pool *rp, rn_rpn *rpn = NULL,
-                const rn_rpn_request *req = NULL, uint64_t image_h = 0, uint64_t image_w = 0, rn_box_head *bh = NULL,
-                const rn_detect_request *dreq = NULL)
+// the stand-alone family (fn names the entry point): its own refusals -- the maps, their boundary, the 2^31 limit --
+// then the shared check, the reserve, the laterals and the steps
+int fpn_forward(const char *fn, rn_neck_call *c, const void *const *x_nhwc, const uint64_t *h, const uint64_t *w)
 {
     static float *const none[kFpnMaxLevels + 1] = {NULL, NULL, NULL, NULL, NULL};
+    static const char *const map_names[kFpnMaxLevels] = {"x_nhwc[0]", "x_nhwc[1]", "x_nhwc[2]", "x_nhwc[3]"};
+    rn_fpn *f = c->fpn;
     if (!f) return RN_ERR_INVALID;
     rn_ctx *ctx = f->ctx;
     RN_ENTER(ctx);
     FPN_REQUIRE(f->finalized, "the neck is not finalized");
-    FPN_REQUIRE(x_nhwc && h && w && (out_nchw || with_rois || rpn), "x_nhwc, h, w or out_nchw is NULL");
-    FPN_REQUIRE(rp || !with_rois, "rois is NULL");
-    if (!out_nchw) out_nchw = none;
-    const int n = f->n, n_out = n + f->extra;
-    bool wanted = rp != NULL || rpn != NULL;
-    for (int i = 0; i < n; ++i) {
+    FPN_REQUIRE(x_nhwc && h && w && (c->out || c->roi || c->rpn), "x_nhwc, h, w or out_nchw is NULL");
+    if (!c->out) c->out = none;
+    const uint64_t B = c->images;
+    operand maps[kFpnMaxLevels];
+    for (int i = 0; i < f->n; ++i) {
         FPN_REQUIRE(x_nhwc[i], "a level's map is NULL");
         FPN_REQUIRE((reinterpret_cast<uintptr_t>(x_nhwc[i]) & 15) == 0, "a level's map is off a 16-byte boundary");
         FPN_REQUIRE(h[i] >= 1 && w[i] >= 1, "h and w must be >= 1");
         FPN_REQUIRE(h[i] < (1ull << 31) && w[i] < (1ull << 31) && B < (1ull << 31) && B * h[i] * w[i] < (1ull << 31),
                     "B * h * w must be below 2^31");
+        c->h[i] = h[i], c->w[i] = w[i];
+        maps[i] = {x_nhwc[i], B * h[i] * w[i] * f->cin[i] * rn_elem_size(f->dtype), map_names[i], false, false};
     }
-    for (int i = 0; i < n_out; ++i) {
-        FPN_REQUIRE((reinterpret_cast<uintptr_t>(out_nchw[i]) & 3) == 0, "an output is off a 4-byte boundary");
-        wanted = wanted || out_nchw[i];
-    }
-    FPN_REQUIRE(wanted, "nothing wanted (every output is NULL)");
-    float scales[kFpnMaxLevels], thr[kFpnMaxLevels - 1];
-    bool reads[kFpnMaxLevels] = {false, false, false, false};
-    if (rp) {
-        RN_TRY(rn_fpn_roi_check(f, ctx, rp, h, w, scales, thr));
-        for (int i = 0; i < rp->n_levels; ++i) reads[rp->level[i]] = rp->K > 0;
-        for (int i = 0; i < n_out; ++i) {  // the pooler's buffers against every exported level
-            uint64_t H = 0, W = 0;
-            const int l = i < n ? i : n - 1;
-            RN_TRY(rn_fpn_level_shape(f, i, h[l], w[l], NULL, &H, &W));
-            RN_TRY(rn_fpn_roi_clear_of(f, ctx, rp, out_nchw[i], B * f->a * H * W * sizeof(float)));
-        }
-    }
-    // the rpn behind the neck reads every level's 3x3 output and the pooled level in place
-    uint64_t hl[kFpnMaxLevels + 1], wl[kFpnMaxLevels + 1];
-    if (rpn) {
-        const char *why = NULL;
-        if (!rn_rpn_matches(rpn, ctx, f->a, (uint64_t)n_out, &why)) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s", fn, why);
-        for (int i = 0; i < n_out; ++i) RN_TRY(rn_fpn_level_shape(f, i, h[i < n ? i : n - 1], w[i < n ? i : n - 1], NULL, &hl[i], &wl[i]));
-        RN_TRY(rn_rpn_check(rpn, ctx, req, B, hl, wl, image_h, image_w));
-        for (int i = 0; i < n; ++i) {
-            reads[i] = true;
-            RN_TRY(rn_rpn_clear_of(rpn, ctx, req, B, x_nhwc[i], B * h[i] * w[i] * f->cin[i] * rn_elem_size(f->dtype)));
-        }
-        for (int i = 0; i < n_out; ++i) RN_TRY(rn_rpn_clear_of(rpn, ctx, req, B, out_nchw[i], B * f->a * hl[i] * wl[i] * sizeof(float)));
-        if (rp && rp->K > 0) {
-            // the chain: the pooler may read the RoIs this call writes, and only those
-            const bool chain = rp->rois_dev == req->out.rois && rp->K == B * req->post_nms_top_n;
-            if (!chain) RN_TRY(rn_rpn_clear_of(rpn, ctx, req, B, rp->rois_dev, rp->K * 5 * sizeof(float)));
-            RN_TRY(rn_rpn_clear_of(rpn, ctx, req, B, rp->pooled, rp->K * f->a * rp->PH * rp->PW * sizeof(float)));
-            RN_TRY(rn_rpn_clear_of(rpn, ctx, req, B, rp->levels_out, rp->K * 4));
-        }
-    }
-    if (bh) {  // the box head behind the chained pooler: its outputs against the maps and every exported level as well
-        RN_TRY(rn_box_head_chain_check(bh, ctx, fn, dreq, B, rpn, req, rp, f->a, image_h, image_w));
-        const uint64_t R = req->post_nms_top_n;
-        for (int i = 0; i < n; ++i)
-            RN_TRY(rn_box_head_clear_of(bh, ctx, dreq, B, R, x_nhwc[i], B * h[i] * w[i] * f->cin[i] * rn_elem_size(f->dtype)));
-        for (int i = 0; i < n_out; ++i) RN_TRY(rn_box_head_clear_of(bh, ctx, dreq, B, R, out_nchw[i], B * f->a * hl[i] * wl[i] * sizeof(float)));
-    }
+    RN_TRY(rn_neck_check(c, ctx, fn, maps, f->n));
     if (B == 0) return RN_OK;
-    RN_TRY(rn_fpn_reserve(f, B, h, w));
-    if (rpn) RN_TRY(rn_rpn_reserve(rpn, B, hl, wl, req->pre_nms_top_n));
-    if (bh) RN_TRY(rn_box_head_reserve(bh, B, req->post_nms_top_n));
+    RN_TRY(rn_neck_reserve(c, B));
     const int saved_layout = ctx->layout;
     ctx->layout = RN_LAYOUT_NHWC;
-    const bool pool = f->extra && (out_nchw[n] || rpn);
+    const int steps = rn_neck_plan(c, B, -1, NULL, NULL, NULL, NULL);
     int st = RN_OK;
-    for (int i = 0; i < n && st == RN_OK; ++i) st = rn_fpn_step(f, ctx, RN_FPN_INNER, i, x_nhwc[i], 0, B, h, w, NULL);
-    for (int i = n - 1; i >= 1 && st == RN_OK; --i) st = rn_fpn_step(f, ctx, RN_FPN_TOPDOWN, i, NULL, 0, B, h, w, NULL);
-    for (int i = 0; i < n && st == RN_OK; ++i)
-        if (out_nchw[i] || (pool && i == n - 1) || reads[i]) st = rn_fpn_step(f, ctx, RN_FPN_LAYER, i, NULL, 0, B, h, w, NULL);
-    if (pool && st == RN_OK) st = rn_fpn_step(f, ctx, RN_FPN_POOL, n - 1, NULL, 0, B, h, w, NULL);
-    for (int i = 0; i < n_out && st == RN_OK; ++i)
-        if (out_nchw[i]) st = rn_fpn_step(f, ctx, RN_FPN_EXPORT, i, NULL, 0, B, h, w, out_nchw[i]);
-    if (rpn && st == RN_OK) st = rn_fpn_rpn_step(f, rpn, ctx, 0, 0, B, h, w, image_h, image_w, req);
-    if (rp && st == RN_OK) st = rn_fpn_roi_step(f, ctx, rp, scales, thr, 0, 0, B, B, h, w);
-    if (bh && st == RN_OK) st = rn_box_head_step(bh, ctx, rp->pooled, rp->rois_dev, 0, 0, B, req->post_nms_top_n, image_h, image_w, dreq);
+    for (int i = 0; i < f->n && st == RN_OK; ++i) st = rn_fpn_step(f, ctx, RN_FPN_INNER, i, x_nhwc[i], 0, B, h, w, NULL);
+    for (int s = 0; s < steps && st == RN_OK; ++s) st = rn_neck_step(c, ctx, s, 0, 0, B);
     ctx->layout = saved_layout;
     return st;
 }
@@ -620,31 +710,41 @@ int fpn_forward(const char *fn, bool with_rois, rn_fpn *f, const void *const *x_
 int rn_fpn_forward(rn_fpn *f, const void *const *x_nhwc, uint64_t B, const uint64_t *h, const uint64_t *w,
                    float *const *out_nchw)
 {
-    return fpn_forward(__func__, false, f, x_nhwc, B, h, w, out_nchw, NULL);
+    rn_neck_call c = {};
+    c.fpn = f, c.out = out_nchw, c.images = B;
+    return fpn_forward(__func__, &c, x_nhwc, h, w);
 }
 
 int rn_fpn_forward_rois(rn_fpn *f, const void *const *x_nhwc, uint64_t B, const uint64_t *h, const uint64_t *w,
                         float *const *out_nchw, const rn_roi_pool *rois)
 {
-    return fpn_forward(__func__, true, f, x_nhwc, B, h, w, out_nchw, rois);
+    rn_neck_call c = {};
+    c.fpn = f, c.out = out_nchw, c.images = B, c.roi = rois;
+    if (f && !rois) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: rois is NULL", __func__);
+    return fpn_forward(__func__, &c, x_nhwc, h, w);
 }
 
 int rn_fpn_forward_proposals(rn_fpn *f, rn_rpn *rpn, const void *const *x_nhwc, uint64_t B, const uint64_t *h, const uint64_t *w,
                              float *const *out_nchw, uint64_t image_h, uint64_t image_w, const rn_rpn_request *req,
                              const rn_roi_pool *rois)
 {
+    rn_neck_call c = {};
+    c.fpn = f, c.out = out_nchw, c.images = B, c.roi = rois, c.rpn = rpn, c.rpn_req = req, c.image_h = image_h, c.image_w = image_w;
     if (f && !rpn) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: rpn is NULL", __func__);
     if (f && !req) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: req is NULL", __func__);
-    return fpn_forward(__func__, false, f, x_nhwc, B, h, w, out_nchw, rois, rpn, req, image_h, image_w);
+    return fpn_forward(__func__, &c, x_nhwc, h, w);
 }
 
 int rn_fpn_forward_detections(rn_fpn *f, rn_rpn *rpn, rn_box_head *bh, const void *const *x_nhwc, uint64_t B, const uint64_t *h,
                               const uint64_t *w, float *const *out_nchw, uint64_t image_h, uint64_t image_w,
                               const rn_rpn_request *req, const rn_roi_pool *rois, const rn_detect_request *det_req)
 {
+    rn_neck_call c = {};
+    c.fpn = f, c.out = out_nchw, c.images = B, c.roi = rois, c.rpn = rpn, c.rpn_req = req, c.image_h = image_h, c.image_w = image_w;
+    c.box_head = bh, c.det_req = det_req;
     if (f && (!rpn || !req)) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: rpn or req is NULL", __func__);
     if (f && (!bh || !det_req)) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: the box head or its request is NULL", __func__);
-    return fpn_forward(__func__, false, f, x_nhwc, B, h, w, out_nchw, rois, rpn, req, image_h, image_w, bh, det_req);
+    return fpn_forward(__func__, &c, x_nhwc, h, w);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 #include <stdio.h>
 
 #include "rn_hip.h"
+#include "rn_operands.h"
 
 struct rn_wcache_entry {
     const void *key;  // the caller's OIHW weight buffer
@@ -136,6 +137,29 @@ static inline bool rn_overlap(const void *a, uint64_t a_bytes, const void *b, ui
 {
     const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
     return x < y + b_bytes && y < x + a_bytes;
+}
+
+// the buffers of one call or request as a list (rn_operands.h): {ptr, bytes, name, output, bytes_only}
+typedef rn_operand operand;
+
+// every operand on a 4-byte boundary (arrays of bytes: any) and no output sharing a byte with another operand
+static inline int check_operands(rn_ctx *ctx, const char *fn, const operand *ops, int n_ops)
+{
+    int with = 0;
+    const int off = rn_operands_misaligned(ops, n_ops);
+    if (off >= 0) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s is off a 4-byte boundary", fn, ops[off].name);
+    const int out = rn_operands_clash(ops, n_ops, &with);
+    if (out >= 0) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s overlaps %s", fn, ops[out].name, ops[with].name);
+    return RN_OK;
+}
+
+// no output of a group sharing a byte with an operand of another group (rn_operands.h: rn_operand_groups_clash)
+static inline int check_operand_groups(rn_ctx *ctx, const char *fn, const rn_operand_group *groups, int n_groups)
+{
+    const operand *a = NULL, *b = NULL;
+    if (!rn_operand_groups_clash(groups, n_groups, &a, &b)) return RN_OK;
+    return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s overlaps %s, another %s of the call", fn, a->name, b->name,
+                        b->output ? "output" : "operand");
 }
 
 // rn_free of *p unless it is NULL, which it is afterwards

@@ -179,25 +179,10 @@ struct rn_model {
     /* rn_model_forward_segment: the head and the buffers of the call that is running (NULL in every other forward) */
     rn_seg_head *seg_head;
     const rn_seg_outputs *seg;
-    /* rn_model_forward_fpn: the neck, the buffers and the levels of the call that is running (fpn NULL in every other
-     * forward): level j reads stage fpn_stage[j] (1..4), an fpn_h[j] x fpn_w[j] map */
-    rn_fpn *fpn;
-    const rn_fpn_outputs *fpn_out;
-    int fpn_n, fpn_extra, fpn_stage[4];
-    uint64_t fpn_a, fpn_h[4], fpn_w[4];
-    /* rn_model_forward_rois: the pooler behind that neck (NULL in every other forward), its levels' scales and
-     * thresholds, the images of the whole call */
-    const rn_roi_pool *roi;
-    /* rn_model_forward_proposals: the rpn behind that neck and its request (NULL in every other forward); roi_chain:
-     * the pooler pools the proposals of the same call, every part its own rows */
-    rn_rpn *rpn;
-    const rn_rpn_request *rpn_req;
-    int roi_chain;
-    /* rn_model_forward_detections: the box head behind the chained pooler and its request (NULL in every other forward) */
-    rn_box_head *box_head;
-    const rn_detect_request *det_req;
-    float roi_scales[4], roi_thr[3];
-    uint64_t roi_images;
+    /* rn_model_forward_fpn and what runs behind its neck (rois, proposals, detections): the call that is running, on
+     * forward_fpn's stack (NULL in every other forward); its level j reads stage fpn_stage[j] (1..4) */
+    const rn_neck_call *neck;
+    int fpn_stage[4];
     /* tile tuning: calls of the last forward, and the batch size the tiles were tuned for */
     rn_conv_call *calls;
     int n_calls, cap_calls, recording;
@@ -1476,85 +1461,37 @@ static int op_segment(rn_model *m, const float *x, uint64_t B, uint64_t h, uint6
     return RN_OK;
 }
 
-/* the profile names of the neck's launches (a record keeps the pointer, so they are literals) */
-static const char *const kFpnInnerOps[4] = {"fpn_inner0", "fpn_inner1", "fpn_inner2", "fpn_inner3"};
-static const char *const kFpnTopdownOps[4] = {NULL, "fpn_topdown1", "fpn_topdown2", "fpn_topdown3"};
-static const char *const kFpnLayerOps[4] = {"fpn_layer0", "fpn_layer1", "fpn_layer2", "fpn_layer3"};
-static const char *const kFpnExportOps[4] = {"fpn_export0", "fpn_export1", "fpn_export2", "fpn_export3"};
-
-/* one launch of the neck of rn_model_forward_fpn with its profile record: the images of this launch use the slice
- * of the neck's scratch that starts at their index in the sub-batch, for op_segment's reason */
-static int op_fpn(rn_model *m, int kind, int level, const char *op, const void *x, uint64_t B, float *dst)
-{
-    double flops = 0.0, bytes = 0.0;
-    rn_fpn_cost(m->fpn, kind, level, B, m->fpn_h, m->fpn_w, &flops, &bytes);
-    TRY(prof_begin(m, op, "fpn", flops, bytes));
-    TRY(rn_fpn_step(m->fpn, m->run.ctx, kind, level, x, m->run.sub0, B, m->fpn_h, m->fpn_w, dst));
-    return prof_end(m);
-}
-
 /* rn_model_forward_fpn: the lateral 1x1 of the level that reads stage li + 1, on the stage's output x in place.
- * Queued right behind the stage's last block on that block's stream, like op_stage_map and for its reason. */
+ * Queued right behind the stage's last block on that block's stream, like op_stage_map and for its reason.  The
+ * images of this launch use the slice of the neck's scratch that starts at their index in the sub-batch, for
+ * op_segment's reason. */
 static int op_fpn_lateral(rn_model *m, int li, const float *x, uint64_t B)
 {
+    const rn_neck_call *c = m->neck;
     int j;
-    for (j = 0; j < m->fpn_n; ++j)
-        if (m->fpn_stage[j] == li + 1) TRY(op_fpn(m, RN_FPN_INNER, j, kFpnInnerOps[j], x, B, NULL));
+    for (j = 0; j < c->n; ++j) {
+        double flops = 0.0, bytes = 0.0;
+        if (m->fpn_stage[j] != li + 1) continue;
+        rn_fpn_cost(c->fpn, RN_FPN_INNER, j, B, c->h, c->w, &flops, &bytes);
+        TRY(prof_begin(m, rn_fpn_op_name(c->fpn, RN_FPN_INNER, j), "fpn", flops, bytes));
+        TRY(rn_fpn_step(c->fpn, m->run.ctx, RN_FPN_INNER, j, x, m->run.sub0, B, c->h, c->w, NULL));
+        TRY(prof_end(m));
+    }
     return RN_OK;
 }
 
-/* rn_model_forward_fpn: what follows the laterals, behind the last block of all (where op_segment sits): the
- * top-down steps coarsest first, the 3x3 of every wanted level (the coarsest one's also for the pool), the pool, the
- * exports into the caller's buffers from image run.img0 on */
+/* rn_model_forward_fpn: what follows the laterals, behind the last block of all (where op_segment sits): the steps
+ * of rn_neck_plan for this part's images, each under its own profile record */
 static int op_fpn_rest(rn_model *m, uint64_t B)
 {
-    const int n = m->fpn_n;
-    float *const *out = m->fpn_out->level;
-    const int pool = m->fpn_extra && (out[n] || m->rpn);
-    int j, reads[4] = {0, 0, 0, 0};
-    if (m->roi && m->roi->K > 0)
-        for (j = 0; j < m->roi->n_levels; ++j) reads[m->roi->level[j]] = 1;
-    if (m->rpn)
-        for (j = 0; j < n; ++j) reads[j] = 1;
-    for (j = n - 1; j >= 1; --j) TRY(op_fpn(m, RN_FPN_TOPDOWN, j, kFpnTopdownOps[j], NULL, B, NULL));
-    for (j = 0; j < n; ++j)
-        if (out[j] || (pool && j == n - 1) || reads[j]) TRY(op_fpn(m, RN_FPN_LAYER, j, kFpnLayerOps[j], NULL, B, NULL));
-    if (pool) TRY(op_fpn(m, RN_FPN_POOL, n - 1, "fpn_pool", NULL, B, NULL));
-    for (j = 0; j <= n; ++j) {
-        uint64_t H, W;
-        if (j == n ? !(pool && out[n]) : !out[j]) continue;
-        TRY(rn_fpn_level_shape(m->fpn, j, m->fpn_h[j < n ? j : n - 1], m->fpn_w[j < n ? j : n - 1], NULL, &H, &W));
-        TRY(op_fpn(m, RN_FPN_EXPORT, j, j < n ? kFpnExportOps[j] : "fpn_export_pool", NULL, B,
-                   out[j] + m->run.img0 * m->fpn_a * H * W));
-    }
-    if (m->rpn) { /* after the exports, before the pooler: 2 L + 3 launches under one record */
-        const double rows = (double)(B * (uint64_t)(n + m->fpn_extra) * m->rpn_req->pre_nms_top_n);
-        TRY(prof_begin(m, "rpn_stage", "rpn", 0.0, rows * 25.0));
-        TRY(rn_fpn_rpn_step(m->fpn, m->rpn, m->run.ctx, m->run.sub0, m->run.img0, B, m->fpn_h, m->fpn_w, m->H, m->W, m->rpn_req));
-        TRY(prof_end(m));
-    }
-    if (m->roi && m->roi_chain) {
-        const uint64_t post = m->rpn_req->post_nms_top_n;
-        TRY(prof_begin(m, "roi_align", "fpn", 0.0, (double)(B * post * m->fpn_a * m->roi->PH * m->roi->PW) * 4.0));
-        TRY(rn_fpn_roi_step_rows(m->fpn, m->run.ctx, m->roi, m->roi_scales, m->roi_thr, m->run.sub0, m->run.img0, B,
-                                 m->roi_images, m->fpn_h, m->fpn_w, m->run.img0 * post, B * post));
-        TRY(prof_end(m));
-        if (m->box_head) { /* this part's own rows, behind its own pooler launch: three contractions and three launches */
-            const uint64_t feat = m->fpn_a * m->roi->PH * m->roi->PW, row0 = m->run.img0 * post;
-            TRY(prof_begin(m, "box_stage", "roi_heads", 0.0, (double)(B * post * feat) * 4.0));
-            TRY(rn_box_head_step(m->box_head, m->run.ctx, m->roi->pooled + row0 * feat, m->roi->rois_dev + row0 * 5, m->run.sub0,
-                                 m->run.img0, B, post, m->H, m->W, m->det_req));
-            TRY(prof_end(m));
-        }
-    } else if (m->roi && m->roi->K > 0) {
-        /* bytes: the outputs only.  What the RoIs gather is several times that (profiles/roi_align) but depends on every
-         * box's size against its level, which the host does not look at: the record's GB/s is the OUTPUT rate */
-        const double outs = (double)(m->roi->K * m->fpn_a * m->roi->PH * m->roi->PW);
-        const double share = (double)B / (double)m->roi_images; /* the RoIs are taken as spread evenly over the images */
-        const double taps = 4.0 * (double)(m->roi->sampling_ratio * m->roi->sampling_ratio);
-        TRY(prof_begin(m, "roi_align", "fpn", share * outs * 2.0 * taps, share * outs * 4.0));
-        TRY(rn_fpn_roi_step(m->fpn, m->run.ctx, m->roi, m->roi_scales, m->roi_thr, m->run.sub0, m->run.img0, B,
-                            m->roi_images, m->fpn_h, m->fpn_w));
+    const int steps = rn_neck_plan(m->neck, B, -1, NULL, NULL, NULL, NULL);
+    int step;
+    for (step = 0; step < steps; ++step) {
+        const char *op = NULL, *layer = NULL;
+        double flops = 0.0, bytes = 0.0;
+        rn_neck_plan(m->neck, B, step, &op, &layer, &flops, &bytes);
+        TRY(prof_begin(m, op, layer, flops, bytes));
+        TRY(rn_neck_step(m->neck, m->run.ctx, step, m->run.sub0, m->run.img0, B));
         TRY(prof_end(m));
     }
     return RN_OK;
@@ -1571,8 +1508,8 @@ static int run_blocks(rn_model *m, int first, int last, uint64_t B, uint64_t *H,
         while (bi >= end) end += m->depths[++li];
         if (m->maps && bi + 1 == end && m->maps->layer[li]) TRY(op_stage_map(m, li, block_input(m, bi + 1), B, *H, *W));
         if (m->seg_head && bi + 1 == m->n_blocks) TRY(op_segment(m, block_input(m, bi + 1), B, *H, *W));
-        if (m->fpn && bi + 1 == end) TRY(op_fpn_lateral(m, li, block_input(m, bi + 1), B));
-        if (m->fpn && bi + 1 == m->n_blocks) TRY(op_fpn_rest(m, B));
+        if (m->neck && bi + 1 == end) TRY(op_fpn_lateral(m, li, block_input(m, bi + 1), B));
+        if (m->neck && bi + 1 == m->n_blocks) TRY(op_fpn_rest(m, B));
     }
     return RN_OK;
 }
@@ -1785,7 +1722,7 @@ static int forward_outputs(rn_model *m, const void *input, int in_u8, uint64_t B
     /* bf16 storage exists only with the fused epilogues (no standalone bf16 bn/relu/add) */
     if (m->dtype != RN_DTYPE_F32 && mode != RN_FWD_FUSED) return RN_ERR_UNSUPPORTED;
     if (outs) {
-        if (!logits && !outs->features && !outs->probs && outs->k == 0 && !m->maps && !m->seg_head && !m->fpn) return RN_ERR_INVALID;
+        if (!logits && !outs->features && !outs->probs && outs->k == 0 && !m->maps && !m->seg_head && !m->neck) return RN_ERR_INVALID;
         if (outs->k > 0 && (!outs->topk_prob || !outs->topk_idx || outs->k > 64 || outs->k > m->classes))
             return RN_ERR_INVALID;
     }
@@ -1931,189 +1868,144 @@ int rn_model_forward_segment_u8(rn_model *m, rn_seg_head *hd, const uint8_t *inp
     return forward_segment(m, hd, input_nhwc, 1, B, outs, seg, mode);
 }
 
-/* rn_model_forward_fpn(_u8): like the maps, the request is state of this call alone -- set once every refusal has
- * passed, cleared on every way out (run_blocks asks m->fpn). */
-static int forward_fpn(rn_model *m, rn_fpn *fpn, const void *input, int in_u8, uint64_t B, const rn_model_outputs *outs,
-                       const int *stages, const rn_fpn_outputs *fo, const rn_roi_pool *roi, int mode, rn_rpn *rpn,
-                       const rn_rpn_request *req, rn_box_head *bh, const rn_detect_request *dreq)
+/* rn_model_forward_fpn and the entry points that run more behind its neck (fn names the one that was called; c holds
+ * what it was given).  The model's own refusals -- the stages and their channel counts -- then the neck call's check
+ * against the head outputs, then the reserve.  Like the maps, the call is state of this forward alone: set once every
+ * refusal has passed, cleared on every way out (run_blocks asks m->neck). */
+static int forward_fpn(rn_model *m, const char *fn, rn_neck_call *c, const void *input, int in_u8, uint64_t B,
+                       const rn_model_outputs *outs, const int *stages, const rn_fpn_outputs *fo, int mode)
 {
-    uint64_t hl[5], wl[5];
-    int chain = 0;
     static const rn_fpn_outputs no_levels = {{NULL, NULL, NULL, NULL, NULL}};
     rn_model_outputs none;
     const char *why = NULL;
     char msg[200];
-    uint64_t cin[4], a = 0, h[4], w[4];
-    int n = 0, extra = 0, j, wanted = 0, st;
+    uint64_t cin[4];
+    int n = 0, j, st;
     if (!m) return RN_ERR_INVALID;
     if (!m->finalized) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_fpn: the model is not finalized");
-    if (!rn_fpn_matches(fpn, m->ctx, m->dtype, &why)) {
+    if (!rn_fpn_matches(c->fpn, m->ctx, m->dtype, &why)) {
         snprintf(msg, sizeof(msg), "rn_model_forward_fpn: %s", why);
         return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, msg);
     }
     if (!stages) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_fpn: stages is NULL");
-    if (!fo && (roi || rpn)) fo = &no_levels;
+    if (!fo && (c->roi || c->rpn)) fo = &no_levels;
     if (!fo) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_fpn: fpn_out is NULL");
-    rn_fpn_dims(fpn, &n, &extra, &a, cin);
+    rn_fpn_dims(c->fpn, &n, NULL, NULL, cin);
     for (j = 0; j < n; ++j)
         if (stages[j] < 1 || stages[j] > 4 || (j > 0 && stages[j] <= stages[j - 1]))
             return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_fpn: stages must be ascending, each 1..4");
     for (j = 0; j < n; ++j) {
         uint64_t C = 0;
-        TRY(rn_model_stage_shape(m, stages[j], &C, &h[j], &w[j]));
+        TRY(rn_model_stage_shape(m, stages[j], &C, &c->h[j], &c->w[j]));
         if (C != cin[j]) {
             snprintf(msg, sizeof(msg), "rn_model_forward_fpn: in_channels of level %d is %llu, layer%d has %llu channels", j,
                      (unsigned long long)cin[j], stages[j], (unsigned long long)C);
             return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, msg);
         }
     }
-    for (j = 0; j < n + extra; ++j) {
-        if (!fo->level[j]) continue;
-        wanted = 1;
-        if ((uintptr_t)fo->level[j] & 3) {
-            snprintf(msg, sizeof(msg), "rn_model_forward_fpn: fpn_out->level[%d] must be 4-byte aligned", j);
-            return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, msg);
-        }
-    }
-    if (!wanted && !roi && !rpn)
-        return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_fpn: nothing wanted (every level is NULL)");
-    if (roi) {
-        TRY(rn_fpn_roi_check(fpn, m->ctx, roi, h, w, m->roi_scales, m->roi_thr));
-        for (j = 0; j < n + extra; ++j) { /* the pooler's buffers against every other output of the call */
-            uint64_t LH = 0, LW = 0;
-            TRY(rn_fpn_level_shape(fpn, j, h[j < n ? j : n - 1], w[j < n ? j : n - 1], NULL, &LH, &LW));
-            TRY(rn_fpn_roi_clear_of(fpn, m->ctx, roi, fo->level[j], B * a * LH * LW * sizeof(float)));
-        }
-        if (outs) {
-            TRY(rn_fpn_roi_clear_of(fpn, m->ctx, roi, outs->logits, B * m->classes * sizeof(float)));
-            TRY(rn_fpn_roi_clear_of(fpn, m->ctx, roi, outs->features, B * m->feat * sizeof(float)));
-            TRY(rn_fpn_roi_clear_of(fpn, m->ctx, roi, outs->probs, B * m->classes * sizeof(float)));
-            TRY(rn_fpn_roi_clear_of(fpn, m->ctx, roi, outs->topk_prob, B * outs->k * sizeof(float)));
-            TRY(rn_fpn_roi_clear_of(fpn, m->ctx, roi, outs->topk_idx, B * outs->k * sizeof(uint64_t)));
-        }
-    }
-    if (rpn) { /* the rpn's request against the neck, the image (the model's input size) and every other output */
-        if (!rn_rpn_matches(rpn, m->ctx, a, (uint64_t)(n + extra), &why)) {
-            snprintf(msg, sizeof(msg), "rn_model_forward_proposals: %s", why);
-            return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, msg);
-        }
-        for (j = 0; j < n + extra; ++j)
-            TRY(rn_fpn_level_shape(fpn, j, h[j < n ? j : n - 1], w[j < n ? j : n - 1], NULL, &hl[j], &wl[j]));
-        TRY(rn_rpn_check(rpn, m->ctx, req, B, hl, wl, m->H, m->W));
-        for (j = 0; j < n + extra; ++j) TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, fo->level[j], B * a * hl[j] * wl[j] * sizeof(float)));
-        if (outs) {
-            TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, outs->logits, B * m->classes * sizeof(float)));
-            TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, outs->features, B * m->feat * sizeof(float)));
-            TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, outs->probs, B * m->classes * sizeof(float)));
-            TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, outs->topk_prob, B * outs->k * sizeof(float)));
-            TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, outs->topk_idx, B * outs->k * sizeof(uint64_t)));
-        }
-        if (roi && roi->K > 0) {
-            chain = roi->rois_dev == req->out.rois && roi->K == B * req->post_nms_top_n;
-            if (!chain) TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, roi->rois_dev, roi->K * 5 * sizeof(float)));
-            TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, roi->pooled, roi->K * a * roi->PH * roi->PW * sizeof(float)));
-            TRY(rn_rpn_clear_of(rpn, m->ctx, req, B, roi->levels_out, roi->K * 4));
-        }
-    }
-    if (bh) { /* the box head behind the chained pooler: its request against every other output of the call */
-        const uint64_t R = req ? req->post_nms_top_n : 0;
-        TRY(rn_box_head_chain_check(bh, m->ctx, "rn_model_forward_detections", dreq, B, rpn, req, roi, a, m->H, m->W));
-        for (j = 0; j < n + extra; ++j) TRY(rn_box_head_clear_of(bh, m->ctx, dreq, B, R, fo->level[j], B * a * hl[j] * wl[j] * sizeof(float)));
-        if (outs) {
-            TRY(rn_box_head_clear_of(bh, m->ctx, dreq, B, R, outs->logits, B * m->classes * sizeof(float)));
-            TRY(rn_box_head_clear_of(bh, m->ctx, dreq, B, R, outs->features, B * m->feat * sizeof(float)));
-            TRY(rn_box_head_clear_of(bh, m->ctx, dreq, B, R, outs->probs, B * m->classes * sizeof(float)));
-            TRY(rn_box_head_clear_of(bh, m->ctx, dreq, B, R, outs->topk_prob, B * outs->k * sizeof(float)));
-            TRY(rn_box_head_clear_of(bh, m->ctx, dreq, B, R, outs->topk_idx, B * outs->k * sizeof(uint64_t)));
-        }
+    memset(&none, 0, sizeof(none));
+    if (!outs) outs = &none;
+    c->out = fo->level, c->image_h = m->H, c->image_w = m->W, c->images = B;
+    {
+        const rn_operand heads[5] = {{outs->logits, B * m->classes * sizeof(float), "logits", 1, 0},
+                                     {outs->features, B * m->feat * sizeof(float), "features", 1, 0},
+                                     {outs->probs, B * m->classes * sizeof(float), "probs", 1, 0},
+                                     {outs->topk_prob, B * outs->k * sizeof(float), "topk_prob", 1, 0},
+                                     {outs->topk_idx, B * outs->k * sizeof(uint64_t), "topk_idx", 1, 0}};
+        TRY(rn_neck_check(c, m->ctx, fn, heads, 5));
     }
     if (!input || B == 0 || (mode != RN_FWD_REFERENCE_OPS && mode != RN_FWD_FUSED)) return RN_ERR_INVALID;
     if (m->dtype != RN_DTYPE_F32 && mode != RN_FWD_FUSED)
         return rn_ctx_set_error(m->ctx, RN_ERR_UNSUPPORTED, "rn_model_forward_fpn: a bf16 model runs RN_FWD_FUSED only");
-    TRY(rn_fpn_reserve(fpn, B < m->max_sub ? B : m->max_sub, h, w));
-    if (rpn) TRY(rn_rpn_reserve(rpn, B < m->max_sub ? B : m->max_sub, hl, wl, req->pre_nms_top_n));
-    if (bh) TRY(rn_box_head_reserve(bh, B < m->max_sub ? B : m->max_sub, req->post_nms_top_n));
-    memset(&none, 0, sizeof(none));
-    if (!outs) outs = &none;
-    m->fpn = fpn;
-    m->fpn_out = fo;
-    m->roi = roi;
-    m->roi_images = B;
-    m->rpn = rpn, m->rpn_req = req, m->roi_chain = chain;
-    m->box_head = bh, m->det_req = dreq;
-    m->fpn_n = n, m->fpn_extra = extra, m->fpn_a = a;
-    for (j = 0; j < n; ++j) m->fpn_stage[j] = stages[j], m->fpn_h[j] = h[j], m->fpn_w[j] = w[j];
+    TRY(rn_neck_reserve(c, B < m->max_sub ? B : m->max_sub));
+    for (j = 0; j < n; ++j) m->fpn_stage[j] = stages[j];
+    m->neck = c;
     st = forward_outputs(m, input, in_u8, B, outs->logits, outs, mode, 0);
-    m->fpn = NULL;
-    m->fpn_out = NULL;
-    m->roi = NULL;
-    m->rpn = NULL, m->rpn_req = NULL, m->roi_chain = 0;
-    m->box_head = NULL, m->det_req = NULL;
+    m->neck = NULL;
     m->maps_done = 0;
     return st;
+}
+
+/* what an entry point of the forward_fpn family was given, the rest zero */
+static rn_neck_call neck_call(rn_fpn *fpn, const rn_roi_pool *rois, rn_rpn *rpn, const rn_rpn_request *req, rn_box_head *bh,
+                              const rn_detect_request *det_req)
+{
+    rn_neck_call c;
+    memset(&c, 0, sizeof(c));
+    c.fpn = fpn, c.roi = rois, c.rpn = rpn, c.rpn_req = req, c.box_head = bh, c.det_req = det_req;
+    return c;
 }
 
 int rn_model_forward_fpn(rn_model *m, rn_fpn *fpn, const float *input_nchw, uint64_t B, const rn_model_outputs *outs,
                          const int *stages, const rn_fpn_outputs *fpn_out, int mode)
 {
-    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, NULL, mode, NULL, NULL, NULL, NULL);
+    rn_neck_call c = neck_call(fpn, NULL, NULL, NULL, NULL, NULL);
+    return forward_fpn(m, __func__, &c, input_nchw, 0, B, outs, stages, fpn_out, mode);
 }
 
 int rn_model_forward_fpn_u8(rn_model *m, rn_fpn *fpn, const uint8_t *input_nhwc, uint64_t B, const rn_model_outputs *outs,
                             const int *stages, const rn_fpn_outputs *fpn_out, int mode)
 {
-    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, NULL, mode, NULL, NULL, NULL, NULL);
+    rn_neck_call c = neck_call(fpn, NULL, NULL, NULL, NULL, NULL);
+    return forward_fpn(m, "rn_model_forward_fpn", &c, input_nhwc, 1, B, outs, stages, fpn_out, mode);
 }
 
 int rn_model_forward_rois(rn_model *m, rn_fpn *fpn, const float *input_nchw, uint64_t B, const rn_model_outputs *outs,
                           const int *stages, const rn_fpn_outputs *fpn_out, const rn_roi_pool *rois, int mode)
 {
+    rn_neck_call c = neck_call(fpn, rois, NULL, NULL, NULL, NULL);
     if (m && !rois) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_rois: rois is NULL");
-    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, rois, mode, NULL, NULL, NULL, NULL);
+    return forward_fpn(m, __func__, &c, input_nchw, 0, B, outs, stages, fpn_out, mode);
 }
 
 int rn_model_forward_rois_u8(rn_model *m, rn_fpn *fpn, const uint8_t *input_nhwc, uint64_t B, const rn_model_outputs *outs,
                              const int *stages, const rn_fpn_outputs *fpn_out, const rn_roi_pool *rois, int mode)
 {
+    rn_neck_call c = neck_call(fpn, rois, NULL, NULL, NULL, NULL);
     if (m && !rois) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_rois: rois is NULL");
-    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, rois, mode, NULL, NULL, NULL, NULL);
+    return forward_fpn(m, "rn_model_forward_rois", &c, input_nhwc, 1, B, outs, stages, fpn_out, mode);
 }
 
 int rn_model_forward_proposals(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, const float *input_nchw, uint64_t B,
                                const rn_model_outputs *outs, const int *stages, const rn_fpn_outputs *fpn_out,
                                const rn_rpn_request *req, const rn_roi_pool *rois, int mode)
 {
+    rn_neck_call c = neck_call(fpn, rois, rpn, req, NULL, NULL);
     if (m && (!rpn || !req)) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_proposals: rpn or req is NULL");
-    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, rois, mode, rpn, req, NULL, NULL);
+    return forward_fpn(m, __func__, &c, input_nchw, 0, B, outs, stages, fpn_out, mode);
 }
 
 int rn_model_forward_proposals_u8(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, const uint8_t *input_nhwc, uint64_t B,
                                   const rn_model_outputs *outs, const int *stages, const rn_fpn_outputs *fpn_out,
                                   const rn_rpn_request *req, const rn_roi_pool *rois, int mode)
 {
+    rn_neck_call c = neck_call(fpn, rois, rpn, req, NULL, NULL);
     if (m && (!rpn || !req)) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_proposals: rpn or req is NULL");
-    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, rois, mode, rpn, req, NULL, NULL);
+    return forward_fpn(m, "rn_model_forward_proposals", &c, input_nhwc, 1, B, outs, stages, fpn_out, mode);
 }
 
 int rn_model_forward_detections(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, rn_box_head *bh, const float *input_nchw, uint64_t B,
                                 const rn_model_outputs *outs, const int *stages, const rn_fpn_outputs *fpn_out,
                                 const rn_rpn_request *req, const rn_roi_pool *rois, const rn_detect_request *det_req, int mode)
 {
+    rn_neck_call c = neck_call(fpn, rois, rpn, req, bh, det_req);
     if (m && (!rpn || !req)) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_detections: rpn or req is NULL");
     if (m && (!bh || !det_req))
         return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_detections: the box head or its request is NULL");
-    return forward_fpn(m, fpn, input_nchw, 0, B, outs, stages, fpn_out, rois, mode, rpn, req, bh, det_req);
+    return forward_fpn(m, __func__, &c, input_nchw, 0, B, outs, stages, fpn_out, mode);
 }
 
 int rn_model_forward_detections_u8(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, rn_box_head *bh, const uint8_t *input_nhwc, uint64_t B,
                                    const rn_model_outputs *outs, const int *stages, const rn_fpn_outputs *fpn_out,
                                    const rn_rpn_request *req, const rn_roi_pool *rois, const rn_detect_request *det_req, int mode)
 {
+    rn_neck_call c = neck_call(fpn, rois, rpn, req, bh, det_req);
     if (m && (!rpn || !req)) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_detections: rpn or req is NULL");
     if (m && (!bh || !det_req))
         return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_detections: the box head or its request is NULL");
-    return forward_fpn(m, fpn, input_nhwc, 1, B, outs, stages, fpn_out, rois, mode, rpn, req, bh, det_req);
+    return forward_fpn(m, "rn_model_forward_detections", &c, input_nhwc, 1, B, outs, stages, fpn_out, mode);
 }
+
 
 /* The decoded-image route resizes to 256 and crops 224 x 224: a model of another size refuses it. */
 static int default_size(const rn_model *m) { return m->H == RN_DEFAULT_SIDE && m->W == RN_DEFAULT_SIDE; }

@@ -7,6 +7,7 @@
 #define RN_PRIVATE_H
 
 #include "rn_hip.h"
+#include "rn_operands.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -97,18 +98,6 @@ int rn_roi_align_window(rn_ctx *ctx, int dtype, uint64_t n_levels, const void *c
                         const uint64_t *w, const float *scales, const float *thr, uint64_t images, uint64_t img_lo,
                         uint64_t img_cnt, int write_invalid, uint64_t C, const float *rois_dev, uint64_t K, uint64_t PH,
                         uint64_t PW, int sampling_ratio, int aligned, float *out, int32_t *levels_out);
-/* a pooler's request against a neck whose level i is an h[i] x w[i] map: every refusal of rn_fpn_forward_rois that
- * concerns the pooler (text in ctx); scales and thr: the pooler's levels' scales (torchvision's infer_scale) and the
- * thresholds between them */
-int rn_fpn_roi_check(const rn_fpn *fpn, rn_ctx *ctx, const rn_roi_pool *rp, const uint64_t *h, const uint64_t *w,
-                     float scales[4], float thr[3]);
-/* RN_ERR_INVALID with a text in ctx when the pooler's pooled, levels_out or rois_dev shares a byte with [other,
- * other + other_bytes), another output of the same call (an exported level, a head output); NULL or 0 bytes: RN_OK */
-int rn_fpn_roi_clear_of(const rn_fpn *fpn, rn_ctx *ctx, const rn_roi_pool *rp, const void *other, uint64_t other_bytes);
-/* the pooler's launch on ctx for the B images from the caller's image img0 on, whose 3x3 outputs start sub0 images
- * into the neck's scratch; images: the batch of the whole forward.  The launch of img0 == 0 writes the invalid rows. */
-int rn_fpn_roi_step(rn_fpn *fpn, rn_ctx *ctx, const rn_roi_pool *rp, const float *scales, const float *thr,
-                    uint64_t sub0, uint64_t img0, uint64_t B, uint64_t images, const uint64_t *h, const uint64_t *w);
 
 /* ---- rn_rpn.hip: the RPN behind a neck, mirroring rn_fpn_roi_* ---- */
 /* 1 when the rpn is finalized, lives on ctx's device, reads in_channels channels and n_levels levels; *why otherwise */
@@ -118,22 +107,13 @@ int rn_rpn_reserve(rn_rpn *rpn, uint64_t images, const uint64_t *h, const uint64
 /* every refusal that concerns the request alone, for a forward of `images` images (text in ctx) */
 int rn_rpn_check(const rn_rpn *rpn, rn_ctx *ctx, const rn_rpn_request *req, uint64_t images, const uint64_t *h,
                  const uint64_t *w, uint64_t image_h, uint64_t image_w);
-/* RN_ERR_INVALID when an output of the request shares a byte with [other, other + other_bytes) */
-int rn_rpn_clear_of(const rn_rpn *rpn, rn_ctx *ctx, const rn_rpn_request *req, uint64_t images, const void *other,
-                    uint64_t other_bytes);
+/* the request's 11 buffers for `images` images as operands, all of them outputs; returns 11 */
+enum { RN_RPN_OPERANDS = 11 };
+int rn_rpn_operands(const rn_rpn *rpn, const rn_rpn_request *req, uint64_t images, rn_operand ops[RN_RPN_OPERANDS]);
 /* the stage's 2 L + 3 launches on ctx for the B images from the caller's image img0 on, whose scratch starts sub0
  * images into the object's tensors; x: the L fp32 NHWC levels of these B images */
 int rn_rpn_step(rn_rpn *rpn, rn_ctx *ctx, const float *const *x, uint64_t sub0, uint64_t img0, uint64_t B,
                 const uint64_t *h, const uint64_t *w, uint64_t image_h, uint64_t image_w, const rn_rpn_request *req);
-
-/* rn_fpn.hip: the rpn's stage on the neck's 3x3 outputs and pooled level of B images, read in place sub0 images into the
- * neck's scratch (h, w: the neck's input levels) */
-int rn_fpn_rpn_step(rn_fpn *fpn, rn_rpn *rpn, rn_ctx *ctx, uint64_t sub0, uint64_t img0, uint64_t B, const uint64_t *h,
-                    const uint64_t *w, uint64_t image_h, uint64_t image_w, const rn_rpn_request *req);
-/* the chain: rn_fpn_roi_step on rows row0 .. row0 + rows of rois_dev, pooled and levels_out alone, all of them written */
-int rn_fpn_roi_step_rows(rn_fpn *fpn, rn_ctx *ctx, const rn_roi_pool *rp, const float *scales, const float *thr,
-                         uint64_t sub0, uint64_t img0, uint64_t B, uint64_t images, const uint64_t *h, const uint64_t *w,
-                         uint64_t row0, uint64_t rows);
 
 /* ---- rn_detect.hip: the box head behind the pooler, mirroring rn_rpn_* ---- */
 /* 1 when the box head is finalized, lives on ctx's device and reads in_features values per RoI; *why otherwise */
@@ -143,19 +123,57 @@ int rn_box_head_reserve(rn_box_head *bh, uint64_t images, uint64_t R);
 /* every refusal that concerns the request alone, for a forward of `images` images of R RoIs (text in ctx) */
 int rn_box_head_check(const rn_box_head *bh, rn_ctx *ctx, const rn_detect_request *req, uint64_t images, uint64_t R,
                       uint64_t image_h, uint64_t image_w);
-/* RN_ERR_INVALID when an output of the request shares a byte with [other, other + other_bytes) */
-int rn_box_head_clear_of(const rn_box_head *bh, rn_ctx *ctx, const rn_detect_request *req, uint64_t images, uint64_t R,
-                         const void *other, uint64_t other_bytes);
-/* every refusal of a forward that runs the box head behind the rpn and the pooler of the same call (fn names the entry
- * point): the chained pooler, pooled on a 16-byte boundary, a head that reads a * PH * PW values, the request, and its
- * outputs against pooled, the RoIs, levels_out and every output of the rpn's request */
-int rn_box_head_chain_check(const rn_box_head *bh, rn_ctx *ctx, const char *fn, const rn_detect_request *req, uint64_t B,
-                            const rn_rpn *rpn, const rn_rpn_request *rpn_req, const rn_roi_pool *rois, uint64_t a,
-                            uint64_t image_h, uint64_t image_w);
+/* the request's 9 outputs for `images` images of R RoIs as operands; returns 9 */
+enum { RN_BOX_HEAD_OPERANDS = 9 };
+int rn_box_head_operands(const rn_box_head *bh, const rn_detect_request *req, uint64_t images, uint64_t R,
+                         rn_operand ops[RN_BOX_HEAD_OPERANDS]);
 /* the stage's launches (three contractions of one or two launches each, then three) on ctx for the B images from the caller's image img0 on, whose scratch starts sub0 images
  * into the object's tensors; pooled [B*R, in_features] and rois [B*R, 5]: the rows of these B images */
 int rn_box_head_step(rn_box_head *bh, rn_ctx *ctx, const float *pooled, const float *rois, uint64_t sub0, uint64_t img0,
                      uint64_t B, uint64_t R, uint64_t image_h, uint64_t image_w, const rn_detect_request *req);
+
+/* ---- rn_fpn.hip: one forward of a neck and what runs behind it, for both entry families ---- */
+/* The description of a call.  It lives on the stack of the entry point that runs it (rn_fpn_forward*, the model's
+ * forward_fpn); rn_neck_check fills the second half once and everything after it only reads. */
+typedef struct rn_neck_call {
+    /* what the caller gave */
+    rn_fpn *fpn;
+    float *const *out;              /* n + extra NCHW outputs; NULL: that level is not exported */
+    const rn_roi_pool *roi;         /* the pooler behind the neck, or NULL */
+    rn_rpn *rpn;                    /* the rpn behind the neck and its request, or NULL */
+    const rn_rpn_request *rpn_req;
+    rn_box_head *box_head;          /* the box head behind the chained pooler and its request, or NULL */
+    const rn_detect_request *det_req;
+    uint64_t image_h, image_w;      /* the image the rpn and the box head clip to */
+    uint64_t h[4], w[4];            /* the input levels' maps */
+    uint64_t images;                /* the batch of the whole call */
+    /* what rn_neck_check derives */
+    int n, extra;
+    uint64_t a, hl[5], wl[5];       /* out_channels; the output levels' maps (the pooled one last) */
+    int chain;                      /* the pooler pools the proposals this call writes, every part its own rows */
+    int pool;                       /* the max-pool runs */
+    int layer_runs[4];              /* the 3x3 of the level runs: exported, pooled from, or read by the pooler / the rpn */
+    float scales[4], thr[3];        /* the pooler's levels' scales and the thresholds between them */
+} rn_neck_call;
+/* Every refusal the two families share, in one order: the neck, the outputs' alignment, nothing wanted, the pooler's
+ * request, the rpn and its request, the box head's conditions and request, then the operand matrix: no output of the
+ * exported levels, the pooler, the rpn, the box head or `others` (the family's own operands: the model's head outputs,
+ * the stand-alone family's input maps) may share a byte with an operand of another of these groups -- but for the
+ * chained pooler's rois_dev, which IS the rpn's out.rois.  Text in ctx, under the name fn; nothing is launched. */
+int rn_neck_check(rn_neck_call *call, rn_ctx *ctx, const char *fn, const rn_operand *others, int n_others);
+/* the scratch of the neck, the rpn and the box head for parts of at most images_at_once images */
+int rn_neck_reserve(const rn_neck_call *call, uint64_t images_at_once);
+/* The one source of what follows the laterals for a part of B images: returns the number of steps and, for step
+ * 0 .. that - 1, its profile name, layer, FLOPs and bytes (any may be NULL; another step only counts).  In order:
+ * the top-down steps coarsest first, the 3x3 of every level that runs, the pool, the exports, the rpn's stage, the
+ * pooler (the whole call's window, or in the chain the part's own rows), the box head's stage. */
+int rn_neck_plan(const rn_neck_call *call, uint64_t B, int step, const char **op, const char **layer, double *flops,
+                 double *bytes);
+/* launch `step` of rn_neck_plan on ctx for the B images from the caller's image img0 on, whose scratch starts sub0
+ * images into the objects' tensors */
+int rn_neck_step(const rn_neck_call *call, rn_ctx *ctx, int step, uint64_t sub0, uint64_t img0, uint64_t B);
+/* the profile name of a neck's launch (a record keeps the pointer: literals) */
+const char *rn_fpn_op_name(const rn_fpn *fpn, int kind, int level);
 
 /* ---- rn_stem.hip ---- */
 /* 1 when the fused stem + max-pool launch takes a padded image of Hp x Wp (nchw: the NCHW-fetching form on

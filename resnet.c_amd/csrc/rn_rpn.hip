@@ -294,33 +294,6 @@ __global__ __launch_bounds__(kRpnBlock) void rpn_merge_kernel(const merge_args p
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------
-struct operand {
-    const void *ptr;
-    uint64_t bytes;
-    const char *name;
-    bool output;
-    bool bytes_only;  // an array of bytes: any boundary
-};
-
-// every operand on a 4-byte boundary (arrays of bytes: any) and no output sharing a byte with another operand
-int check_operands(rn_ctx *ctx, const char *fn, const operand *ops, int n_ops)
-{
-    for (int i = 0; i < n_ops; ++i) {
-        if (!ops[i].ptr) continue;
-        if (!ops[i].bytes_only && (reinterpret_cast<uintptr_t>(ops[i].ptr) & 3) != 0)
-            return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s is off a 4-byte boundary", fn, ops[i].name);
-    }
-    for (int i = 0; i < n_ops; ++i) {
-        if (!ops[i].ptr || !ops[i].output) continue;
-        for (int j = 0; j < n_ops; ++j) {
-            if (j == i || !ops[j].ptr || (ops[j].output && j < i)) continue;
-            if (rn_overlap(ops[i].ptr, ops[i].bytes, ops[j].ptr, ops[j].bytes))
-                return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s overlaps %s", fn, ops[i].name, ops[j].name);
-        }
-    }
-    return RN_OK;
-}
-
 int mask_launch(rn_ctx *ctx, const float *boxes, const int32_t *count, uint64_t *words, uint64_t S, uint64_t n, float thresh,
                 const char *what)
 {
@@ -686,30 +659,23 @@ int rn_rpn_check(const rn_rpn *r, rn_ctx *ctx, const rn_rpn_request *q, uint64_t
     }
     const rn_rpn_proposals *o = &q->out;
     RN_REQUIRE(ctx, o->boxes || o->logits || o->levels || o->count || o->rois || o->cand_keep, "every output of the request is NULL");
-    const uint64_t rows = images * r->L * q->pre_nms_top_n, prop = images * q->post_nms_top_n;
-    const operand ops[] = {{o->boxes, prop * 16, "out.boxes", true, false},   {o->logits, prop * 4, "out.logits", true, false},
-                           {o->levels, prop * 4, "out.levels", true, false},  {o->count, images * 4, "out.count", true, false},
-                           {o->rois, prop * 20, "out.rois", true, false},     {o->cand_keep, rows, "out.cand_keep", true, true},
-                           {q->cand.index, rows * 4, "cand.index", true, false}, {q->cand.logit, rows * 4, "cand.logit", true, false},
-                           {q->cand.box, rows * 16, "cand.box", true, false}, {q->cand.valid, rows, "cand.valid", true, true},
-                           {q->cand.count, images * r->L * 4, "cand.count", true, false}};
-    return check_operands(ctx, "rn_rpn request", ops, 11);
+    operand ops[RN_RPN_OPERANDS];
+    return check_operands(ctx, "rn_rpn request", ops, rn_rpn_operands(r, q, images, ops));
 }
 
-// RN_ERR_INVALID when an output of the request shares a byte with [other, other + other_bytes)
-int rn_rpn_clear_of(const rn_rpn *r, rn_ctx *ctx, const rn_rpn_request *q, uint64_t images, const void *other,
-                    uint64_t other_bytes)
+int rn_rpn_operands(const rn_rpn *r, const rn_rpn_request *q, uint64_t images, rn_operand ops[RN_RPN_OPERANDS])
 {
-    if (!q || !other || other_bytes == 0) return RN_OK;
+    const rn_rpn_proposals *o = &q->out;
     const uint64_t rows = images * r->L * q->pre_nms_top_n, prop = images * q->post_nms_top_n;
-    const void *ptr[11] = {q->out.boxes, q->out.logits, q->out.levels, q->out.count, q->out.rois, q->out.cand_keep,
-                           q->cand.index, q->cand.logit, q->cand.box,  q->cand.valid, q->cand.count};
-    const uint64_t bytes[11] = {prop * 16, prop * 4, prop * 4, images * 4, prop * 20, rows, rows * 4, rows * 4, rows * 16, rows,
-                                images * r->L * 4};
-    for (int i = 0; i < 11; ++i)
-        RN_REQUIRE(ctx, !ptr[i] || !rn_overlap(ptr[i], bytes[i], other, other_bytes),
-                   "an output of the rpn's request overlaps another operand of the call");
-    return RN_OK;
+    const operand all[RN_RPN_OPERANDS] = {
+        {o->boxes, prop * 16, "out.boxes", true, false},      {o->logits, prop * 4, "out.logits", true, false},
+        {o->levels, prop * 4, "out.levels", true, false},     {o->count, images * 4, "out.count", true, false},
+        {o->rois, prop * 20, "out.rois", true, false},        {o->cand_keep, rows, "out.cand_keep", true, true},
+        {q->cand.index, rows * 4, "cand.index", true, false}, {q->cand.logit, rows * 4, "cand.logit", true, false},
+        {q->cand.box, rows * 16, "cand.box", true, false},    {q->cand.valid, rows, "cand.valid", true, true},
+        {q->cand.count, images * r->L * 4, "cand.count", true, false}};
+    memcpy(ops, all, sizeof(all));
+    return RN_RPN_OPERANDS;
 }
 
 // The stage's 2L + 3 launches on ctx for the B images from the caller's image img0 on, whose scratch starts sub0
@@ -763,11 +729,14 @@ int rn_rpn_forward(rn_rpn *r, const float *const *x_nhwc, uint64_t B, const uint
     RN_REQUIRE(ctx, r->finalized, "the rpn is not finalized");
     RN_REQUIRE(ctx, x_nhwc && h && w, "x_nhwc, h or w is NULL");
     RN_TRY(rn_rpn_check(r, ctx, req, B, h, w, image_h, image_w));
+    operand outs[RN_RPN_OPERANDS], maps[kRpnMaxLevels];
     for (uint64_t l = 0; l < r->L; ++l) {
         RN_REQUIRE(ctx, x_nhwc[l], "a level's map is NULL");
         RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(x_nhwc[l]) & 15) == 0, "a level's map is off a 16-byte boundary");
-        RN_TRY(rn_rpn_clear_of(r, ctx, req, B, x_nhwc[l], B * h[l] * w[l] * r->C * sizeof(float)));
+        maps[l] = {x_nhwc[l], B * h[l] * w[l] * r->C * sizeof(float), "a level's map", false, false};
     }
+    const rn_operand_group groups[2] = {{maps, (int)r->L}, {outs, rn_rpn_operands(r, req, B, outs)}};
+    RN_TRY(check_operand_groups(ctx, __func__, groups, 2));
     if (B == 0) return RN_OK;
     RN_TRY(rn_rpn_reserve(r, B, h, w, req->pre_nms_top_n));
     const int saved_layout = ctx->layout;

@@ -114,6 +114,74 @@ def fpn_ref(maps_nchw_f64, state, extra="pool", round_fn=None) -> Dict[str, np.n
     return out
 
 
+class NeckTail:
+    """What runs behind a neck in one forward -- the pooler, the rpn, the box head -- for both
+    ``FeaturePyramidNetwork.forward`` and ``NativeModel.forward_fpn``.  Creating one raises the ValueErrors of a bad
+    combination and touches no device; ``build`` makes the device buffers and the ctypes requests; ``entry`` names the
+    entry point of the family that applies ("fpn", "rois", "proposals" or "detections") and ``requests`` what that one
+    takes behind the levels; ``collect`` adds the results to the forward's dict once the context is synchronised."""
+
+    def __init__(self, ctx, names, out_channels, B, image_size, rois, pooler, roi_levels, validate, rpn, candidates,
+                 box_head, detect_intermediates):
+        if rpn is None and ((rois is None) != (pooler is None) or (rois is not None and image_size is None)):
+            raise ValueError("rois, pooler and image_size go together")
+        if rpn is not None and (image_size is None or (rois is not None and pooler is None)):
+            raise ValueError("rpn needs image_size (and rois a pooler)")
+        if box_head is not None and rpn is None:
+            raise ValueError("box_head needs an rpn and a pooler")
+        if box_head is not None and (pooler is None or rois is not None):
+            raise ValueError("box_head needs a pooler that takes the proposals of the same call (no rois)")
+        self.ctx, self.names, self.a, self.B, self.image_size = ctx, names, int(out_channels), int(B), image_size
+        self.rois, self.pooler, self.roi_levels, self.validate = rois, pooler, roi_levels, validate
+        self.rpn, self.candidates, self.box_head, self.detect_intermediates = rpn, candidates, box_head, detect_intermediates
+        self.entry = ("detections" if box_head is not None else "proposals" if rpn is not None else
+                      "rois" if pooler is not None else "fpn")
+        self.req = self.rreq = self.dreq = None
+
+    def build(self) -> None:
+        from . import roi as R
+        from .tensor import _DeviceBuffer
+        if self.rpn is not None:
+            self.rspec, self.rbufs = self.rpn.buffers(self.B, self.candidates)
+            self.rreq = self.rpn.request(self.rbufs)
+        if self.pooler is not None:
+            if self.rois is None:  # the chain: the proposals of the same call, on the device
+                self.drois, self.K = self.rbufs["rois"], self.B * self.rpn.post
+            else:
+                self.drois, self.K = R.upload_rois(self.rois, self.B, self.validate)
+            PH, PW = self.pooler.output_size
+            self.pooled = _DeviceBuffer(self.ctx, max(self.K * self.a * PH * PW * 4, 16))
+            self.lv = _DeviceBuffer(self.ctx, max(self.K * 4, 16)) if self.roi_levels else None
+            self.req = self.pooler.request(self.names, self.drois.ptr, self.K, self.image_size, self.pooled.ptr,
+                                           self.lv.ptr if self.lv else None)
+        if self.box_head is not None:
+            self.dspec, self.dbufs = self.box_head.buffers(self.B, self.rpn.post, self.detect_intermediates)
+            self.dreq = self.box_head.request(self.dbufs)
+
+    @property
+    def requests(self) -> tuple:
+        """The arguments of ``entry`` behind the levels, in the C order: req, rois, det_req."""
+        ref = lambda r: ctypes.byref(r) if r is not None else None  # noqa: E731
+        return {"fpn": (), "rois": (ref(self.req),), "proposals": (ref(self.rreq), ref(self.req)),
+                "detections": (ref(self.rreq), ref(self.req), ref(self.dreq))}[self.entry]
+
+    def collect(self, out: dict) -> dict:
+        from .ops import _down_raw
+        if self.rpn is not None:
+            got = self.rpn.collect(self.rspec, self.rbufs)
+            out.update({k: got[k] for k in ("proposals", "scores", "proposal_levels", "cand") if k in got})
+            out["rois"], out["proposal_count"], out["proposal_logits"] = got["raw"]["rois"], got["raw"]["count"], got["raw"]["logits"]
+        if self.pooler is not None:
+            PH, PW = self.pooler.output_size
+            out["pooled"] = _down_raw(self.pooled, np.float32, self.K * self.a * PH * PW).reshape(self.K, self.a, PH, PW)
+            if self.roi_levels:
+                out["roi_levels"] = _down_raw(self.lv, np.int32, self.K)
+        if self.box_head is not None:
+            out["proposal_scores"] = out.pop("scores")
+            out.update(self.box_head.collect(self.dspec, self.dbufs))
+        return out
+
+
 class FeaturePyramidNetwork:
     """rn_fpn_*: FeaturePyramidNetwork(in_channels_list, out_channels, extra_blocks=LastLevelMaxPool()) on the device
     (extra=None: no extra block); state holds torchvision's tensors (fpn_shapes; split_state normalises the keys).
@@ -177,10 +245,8 @@ class FeaturePyramidNetwork:
         for name in levels:
             if name not in self.names:
                 raise ValueError(f"unknown level {name!r}: one of {self.names}")
-        if rpn is None and ((rois is None) != (pooler is None) or (rois is not None and image_size is None)):
-            raise ValueError("rois, pooler and image_size go together")
-        if rpn is not None and (image_size is None or (rois is not None and pooler is None)):
-            raise ValueError("rpn needs image_size (and rois a pooler)")
+        tail = NeckTail(self.ctx, self.names, self.out_channels, np.shape(maps_nhwc[0])[0], image_size, rois, pooler,
+                        roi_levels, validate, rpn, candidates, box_head, detect_intermediates)
         xs = []
         for x, c in zip(maps_nhwc, self.in_channels_list):
             x = np.asarray(x)
@@ -202,61 +268,21 @@ class FeaturePyramidNetwork:
         xp = (ctypes.c_void_p * n)(*[d.ptr for d in dx])
         op = (ctypes.c_void_p * len(self.names))(*[bufs[name].ptr if name in bufs else None for name in self.names])
         hp, wp = (ctypes.c_uint64 * n)(*hs), (ctypes.c_uint64 * n)(*ws)
-        if rpn is not None:
-            from . import roi as R
-            spec, rbufs = rpn.buffers(B, candidates)
-            rreq, req = rpn.request(rbufs), None
-            if pooler is not None:
-                if rois is None:
-                    drois, K = rbufs["rois"], B * rpn.post
-                else:
-                    drois, K = R.upload_rois(rois, B, validate)
-                PH, PW = pooler.output_size
-                pooled = _DeviceBuffer(self.ctx, max(K * self.out_channels * PH * PW * 4, 16))
-                lv = _DeviceBuffer(self.ctx, max(K * 4, 16)) if roi_levels else None
-                req = pooler.request(self.names, drois.ptr, K, image_size, pooled.ptr, lv.ptr if lv else None)
-            if box_head is not None:
-                if pooler is None or rois is not None:
-                    raise ValueError("box_head needs a pooler that takes the proposals of the same call (no rois)")
-                dspec, dbufs = box_head.buffers(B, rpn.post, detect_intermediates)
-                dreq = box_head.request(dbufs)
-                L.check(L.lib().rn_fpn_forward_detections(self.handle, rpn.handle, box_head.handle, xp, B, hp, wp, op,
-                                                          int(image_size[0]), int(image_size[1]), ctypes.byref(rreq),
-                                                          ctypes.byref(req), ctypes.byref(dreq)),
-                        "rn_fpn_forward_detections", self.ctx.handle)
-            else:
-                L.check(L.lib().rn_fpn_forward_proposals(self.handle, rpn.handle, xp, B, hp, wp, op, int(image_size[0]),
-                                                         int(image_size[1]), ctypes.byref(rreq),
-                                                         ctypes.byref(req) if req is not None else None),
-                        "rn_fpn_forward_proposals", self.ctx.handle)
-        elif box_head is not None:
-            raise ValueError("box_head needs an rpn and a pooler")
-        elif rois is None:
-            L.check(L.lib().rn_fpn_forward(self.handle, xp, B, hp, wp, op), "rn_fpn_forward", self.ctx.handle)
+        tail.build()
+        lib, size = L.lib(), tuple(int(s) for s in image_size) if image_size is not None else ()
+        if tail.entry == "detections":
+            st = lib.rn_fpn_forward_detections(self.handle, rpn.handle, box_head.handle, xp, B, hp, wp, op, *size, *tail.requests)
+        elif tail.entry == "proposals":
+            st = lib.rn_fpn_forward_proposals(self.handle, rpn.handle, xp, B, hp, wp, op, *size, *tail.requests)
+        elif tail.entry == "rois":
+            st = lib.rn_fpn_forward_rois(self.handle, xp, B, hp, wp, op, *tail.requests)
         else:
-            from . import roi as R
-            drois, K = R.upload_rois(rois, B, validate)
-            PH, PW = pooler.output_size
-            pooled = _DeviceBuffer(self.ctx, max(K * self.out_channels * PH * PW * 4, 16))
-            lv = _DeviceBuffer(self.ctx, max(K * 4, 16)) if roi_levels else None
-            req = pooler.request(self.names, drois.ptr, K, image_size, pooled.ptr, lv.ptr if lv else None)
-            L.check(L.lib().rn_fpn_forward_rois(self.handle, xp, B, hp, wp, op, ctypes.byref(req)), "rn_fpn_forward_rois",
-                    self.ctx.handle)
+            st = lib.rn_fpn_forward(self.handle, xp, B, hp, wp, op)
+        L.check(st, "rn_fpn_forward" + {"fpn": ""}.get(tail.entry, "_" + tail.entry), self.ctx.handle)
         self.ctx.sync()
         out = {name: _down_raw(bufs[name], np.float32, int(np.prod(shapes[name]))).reshape(shapes[name])
                for name in self.names if name in bufs}
-        if rpn is not None:
-            got = rpn.collect(spec, rbufs)
-            out.update({k: got[k] for k in ("proposals", "scores", "proposal_levels", "cand") if k in got})
-            out["rois"], out["proposal_count"], out["proposal_logits"] = got["raw"]["rois"], got["raw"]["count"], got["raw"]["logits"]
-        if pooler is not None:
-            out["pooled"] = _down_raw(pooled, np.float32, K * self.out_channels * PH * PW).reshape(K, self.out_channels, PH, PW)
-            if roi_levels:
-                out["roi_levels"] = _down_raw(lv, np.int32, K)
-        if box_head is not None:
-            out["proposal_scores"] = out.pop("scores")
-            out.update(box_head.collect(dspec, dbufs))
-        return out
+        return tail.collect(out)
 
     def close(self) -> None:
         if self.handle:

@@ -480,6 +480,7 @@ class NativeModel:
         "boxes" [B,D,4], "scores" [B,D] (in place of the proposals' scores, which stay under "proposal_scores"), "labels",
         "detections" (the counts [B]) and "detection_rois" (the proposal row of every detection), padded as the device
         wrote them; with detect_intermediates also "probs", "class_boxes", "valid" and "keep"."""
+        from .fpn import NeckTail
         from .ops import _down_raw, _up_raw
         from .tensor import _DeviceBuffer
         stages = tuple(stages)
@@ -497,6 +498,8 @@ class NativeModel:
             if name not in names:
                 raise ValueError(f"unknown level {name!r}: one of {names}")
         x = np.asarray(x)
+        tail = NeckTail(self.ctx, names, neck.out_channels, x.shape[0], self.input_size, rois, pooler, roi_levels, validate,
+                        rpn, candidates, box_head, detect_intermediates)
         u8 = x.dtype == np.uint8
         x = np.ascontiguousarray(x, dtype=np.uint8 if u8 else np.float32)
         self._check_input(x, u8)
@@ -521,52 +524,14 @@ class NativeModel:
         o = L.ModelOutputs(buf("logits", logits, B * C * 4), buf("features", features, B * F * 4),
                            buf("probs", probs, B * C * 4), buf("topk_prob", k > 0, B * k * 4),
                            buf("topk_idx", k > 0, B * k * 8), k)
-        if rpn is None and (rois is None) != (pooler is None):
-            raise ValueError("rois and pooler go together")
-        if rpn is not None and rois is not None and pooler is None:
-            raise ValueError("rois need a pooler")
+        tail.build()
         mode = L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS
         stage_arr = (ctypes.c_int * len(idx))(*idx)
-        if rpn is not None:
-            from . import roi as R
-            rspec, rbufs = rpn.buffers(B, candidates)
-            rreq, req = rpn.request(rbufs), None
-            if pooler is not None:
-                drois, K = (rbufs["rois"], B * rpn.post) if rois is None else R.upload_rois(rois, B, validate)
-                PH, PW = pooler.output_size
-                pooled = _DeviceBuffer(self.ctx, max(K * neck.out_channels * PH * PW * 4, 16))
-                lv = _DeviceBuffer(self.ctx, max(K * 4, 16)) if roi_levels else None
-                req = pooler.request(names, drois.ptr, K, self.input_size, pooled.ptr, lv.ptr if lv else None)
-            if box_head is not None:
-                if pooler is None or rois is not None:
-                    raise ValueError("box_head needs a pooler that takes the proposals of the same forward (no rois)")
-                dspec, dbufs = box_head.buffers(B, rpn.post, detect_intermediates)
-                dreq = box_head.request(dbufs)
-                fn = L.lib().rn_model_forward_detections_u8 if u8 else L.lib().rn_model_forward_detections
-                L.check(fn(self.handle, neck.handle, rpn.handle, box_head.handle, xin.ptr, B, ctypes.byref(o), stage_arr,
-                           ctypes.byref(fo), ctypes.byref(rreq), ctypes.byref(req), ctypes.byref(dreq), mode),
-                        "rn_model_forward_detections", self.ctx.handle)
-            else:
-                fn = L.lib().rn_model_forward_proposals_u8 if u8 else L.lib().rn_model_forward_proposals
-                L.check(fn(self.handle, neck.handle, rpn.handle, xin.ptr, B, ctypes.byref(o), stage_arr, ctypes.byref(fo),
-                           ctypes.byref(rreq), ctypes.byref(req) if req is not None else None, mode),
-                        "rn_model_forward_proposals", self.ctx.handle)
-        elif box_head is not None:
-            raise ValueError("box_head needs an rpn and a pooler")
-        elif rois is None:
-            fn = L.lib().rn_model_forward_fpn_u8 if u8 else L.lib().rn_model_forward_fpn
-            L.check(fn(self.handle, neck.handle, xin.ptr, B, ctypes.byref(o), stage_arr, ctypes.byref(fo), mode),
-                    "rn_model_forward_fpn", self.ctx.handle)
-        else:
-            from . import roi as R
-            drois, K = R.upload_rois(rois, B, validate)
-            PH, PW = pooler.output_size
-            pooled = _DeviceBuffer(self.ctx, max(K * neck.out_channels * PH * PW * 4, 16))
-            lv = _DeviceBuffer(self.ctx, max(K * 4, 16)) if roi_levels else None
-            req = pooler.request(names, drois.ptr, K, self.input_size, pooled.ptr, lv.ptr if lv else None)
-            fn = L.lib().rn_model_forward_rois_u8 if u8 else L.lib().rn_model_forward_rois
-            L.check(fn(self.handle, neck.handle, xin.ptr, B, ctypes.byref(o), stage_arr, ctypes.byref(fo), ctypes.byref(req),
-                       mode), "rn_model_forward_rois", self.ctx.handle)
+        objs = {"fpn": (), "rois": (), "proposals": (rpn,), "detections": (rpn, box_head)}[tail.entry]
+        name = "rn_model_forward_" + tail.entry
+        fn = getattr(L.lib(), name + ("_u8" if u8 else ""))
+        L.check(fn(self.handle, neck.handle, *[obj.handle for obj in objs], xin.ptr, B, ctypes.byref(o), stage_arr,
+                   ctypes.byref(fo), *tail.requests, mode), name, self.ctx.handle)
         self.ctx.sync()
         shapes.update({"logits": (B, C), "features": (B, F), "probs": (B, C), "topk_prob": (B, k), "topk_idx": (B, k)})
         out = {name: _down_raw(lbufs[name], np.float32, int(np.prod(shapes[name]))).reshape(shapes[name])
@@ -576,18 +541,7 @@ class NativeModel:
                 out[name] = _down_raw(b, np.uint64, B * k).astype(np.int64).reshape(B, k)
             else:
                 out[name] = _down_raw(b, np.float32, int(np.prod(shapes[name]))).reshape(shapes[name])
-        if rpn is not None:
-            got = rpn.collect(rspec, rbufs)
-            out.update({key: got[key] for key in ("proposals", "scores", "proposal_levels", "cand") if key in got})
-            out["rois"], out["proposal_count"], out["proposal_logits"] = got["raw"]["rois"], got["raw"]["count"], got["raw"]["logits"]
-        if pooler is not None:
-            out["pooled"] = _down_raw(pooled, np.float32, K * neck.out_channels * PH * PW).reshape(K, neck.out_channels, PH, PW)
-            if roi_levels:
-                out["roi_levels"] = _down_raw(lv, np.int32, K)
-        if box_head is not None:
-            out["proposal_scores"] = out.pop("scores")
-            out.update(box_head.collect(dspec, dbufs))
-        return out
+        return tail.collect(out)
 
     def forward_fpn_u8(self, px: np.ndarray, neck, stages=STAGES, levels=None, **kw) -> dict:
         """forward_fpn from 8-bit RGB [B,H,W,3] (rn_model_forward_fpn_u8): the same pyramid as forward_fpn on
