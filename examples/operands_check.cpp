@@ -75,6 +75,40 @@ int main()
         roi[0].bytes = 0;  // a pooler of no RoIs is in nobody's way, wherever its pointers are
         EXPECT(!rn_operand_groups_clash(g, 4, &a, &b));
     }
+    // the sixth group: a mask head's request behind a box head's, its pasted outputs the largest buffers of the call
+    {
+        const rn_operand maps[] = {{p, 64, "x[0]", 0, 0}};
+        const rn_operand levels[] = {{nullptr, 64, "level[0]", 1, 0}};
+        const rn_operand roi[] = {{p + 64, 64, "pooled", 1, 0}, {nullptr, 8, "levels_out", 1, 0}, {nullptr, 40, "rois_dev", 0, 0}};
+        const rn_operand rpn[] = {{p + 128, 32, "out.boxes", 1, 0}, {p + 160, 40, "out.rois", 1, 0}};
+        rn_operand box[] = {{p + 256, 64, "out.boxes", 1, 0}, {p + 320, 16, "out.labels", 1, 0}, {nullptr, 16, "out.scores", 1, 0}};
+        rn_operand mask[] = {{p + 512, 80, "mask.rois", 1, 0}, {nullptr, 256, "mask.pooled", 1, 0}, {p + 768, 256, "mask.probs", 1, 0},
+                             {p + 1024, 1024, "mask.masks", 1, 0}, {p + 2048, 256, "mask.bits", 1, 1}};
+        const rn_operand_group g[6] = {{maps, 1}, {levels, 1}, {roi, 3}, {rpn, 2}, {box, 3}, {mask, 5}};
+        const rn_operand *a = nullptr, *b = nullptr;
+        EXPECT(rn_operands_misaligned(mask, 5) == -1 && rn_operands_clash(mask, 5, &with) == -1);
+        EXPECT(!rn_operand_groups_clash(g, 6, &a, &b));
+        mask[4].ptr = p + 2047;  // the bytes one byte into the fp32 masks: the stage's own list answers
+        EXPECT(rn_operands_clash(mask, 5, &with) == 3 && with == 4);
+        mask[4].ptr = p + 2049;  // arrays of bytes sit anywhere
+        EXPECT(rn_operands_misaligned(mask, 5) == -1 && rn_operands_clash(mask, 5, &with) == -1);
+        mask[3].ptr = p + 1026;
+        EXPECT(rn_operands_misaligned(mask, 5) == 3);
+        mask[3].ptr = p + 1024;
+        mask[2].ptr = box[0].ptr;  // the probabilities on the detections the stage reads
+        EXPECT(rn_operand_groups_clash(g, 6, &a, &b) && a == &mask[2] && b == &box[0]);
+        mask[2].ptr = p + 768;
+        mask[0].ptr = p + 335;  // the RoI rows over the last byte of the labels
+        EXPECT(rn_operand_groups_clash(g, 6, &a, &b) && a == &mask[0] && b == &box[1]);
+        mask[0].ptr = p + 336;  // adjacent
+        EXPECT(!rn_operand_groups_clash(g, 6, &a, &b));
+        mask[3].ptr = p;  // the pasted masks over an input map of the family
+        EXPECT(rn_operand_groups_clash(g, 6, &a, &b) && a == &mask[3] && b == &maps[0]);
+        mask[3].ptr = nullptr;  // not wanted: in nobody's way
+        EXPECT(!rn_operand_groups_clash(g, 6, &a, &b));
+        box[2].ptr = p + 800;  // an output of the box head inside the probabilities
+        EXPECT(rn_operand_groups_clash(g, 6, &a, &b) && a == &mask[2] && b == &box[2]);
+    }
     std::free(mem);
     std::printf(failures ? "%d expectations failed\n" : "operands_check: every expectation holds\n", failures);
     return failures ? 1 : 0;

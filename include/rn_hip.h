@@ -1264,6 +1264,132 @@ RN_API int rn_model_forward_detections_u8(rn_model *m, rn_fpn *fpn, rn_rpn *rpn,
                                           uint64_t B, const rn_model_outputs *outs, const int *stages,
                                           const rn_fpn_outputs *fpn_out, const rn_rpn_request *req,
                                           const rn_roi_pool *rois, const rn_detect_request *det_req, int mode);
+/* ---- The mask head behind the box head: convs, deconv, class select and paste (rn_mask.hip; the pooler form: rn_roi.hip) --
+ * torchvision's mask branch of RoIHeads in eval mode: mask_roi_pool on the DETECTED boxes, MaskRCNNHeads (3x3
+ * convolutions with bias and ReLU), MaskRCNNPredictor (conv5_mask, a ConvTranspose2d(., Cr, 2, 2) with ReLU, then the 1x1
+ * mask_fcn_logits), maskrcnn_inference (the sigmoid of the channel of each detection's own label) and
+ * paste_masks_in_image.  fp32 only, like the box head.  Every entry point is asynchronous on the context's stream and
+ * allocates nothing outside scratch that grows on demand; none of its kernels uses an atomic.  No content of a label or
+ * a box indexes outside a buffer: the index clamps are unconditional.  Refusals: RN_ERR_INVALID, nothing launched,
+ * rn_last_error names the operand; no output may share a byte with another operand; K, B or D == 0: RN_OK, nothing
+ * launched.
+ *
+ * rn_roi_align_nhwc_forward_dt: rn_roi_align_forward_dt with the output as [K, PH, PW, C], the layout the convolutions
+ * read.  Every argument, every refusal and every value are that function's: element (k, ph, pw, c) holds, bit for bit,
+ * its (k, c, ph, pw), the rows of zeros and the level -1 of an invalid image index included.  out_nhwc sits on a 16-byte
+ * boundary: a thread stores the 4 (bf16 maps: 8) channels it summed with 16-byte stores, no LDS transposition.
+ *
+ * rn_detection_rois_forward: boxes [B,D,4] fp32 and labels [B,D] int32 (device) -> rois [B*D,5]: row (b, d) is
+ * (b, x1, y1, x2, y2) where labels[b][d] >= 1 and (-1, 0, 0, 0, 0) otherwise -- the padding rows of rn_detections carry
+ * label -1, and the pooler answers an image index of -1 with zeros.  One launch, 16-byte stores wherever four
+ * consecutive outputs share an aligned 16 bytes.  B * D * 5 below 2^31.
+ *
+ * rn_mask_predict_forward: t [K, M, M, 4*Cr] fp32 on a 16-byte boundary, the deconvolution's output after bias and ReLU
+ * with channel (dy*2 + dx)*Cr + c holding output pixel (2y + dy, 2x + dx), channel c; labels [K] int32; weight [C, Cr]
+ * (16-byte aligned) and bias [C] fp32 on the device, mask_fcn_logits in torchvision's layout -> probs [K, 2M, 2M] fp32:
+ *     probs[k][2y+dy][2x+dx] = 1 / (1 + expf(-(bias[l] + sum_c weight[l][c] * t[k][y][x][(dy*2+dx)*Cr + c]))), l = labels[k]
+ * and a row whose label is outside [1, C) is all zeros.  Only the label's row of the 1x1 is computed; no [K, C, 2M, 2M]
+ * tensor exists.  Cr a multiple of 64 up to 1024, M 1..32, C 2..1024.  The sum is not bit-defined against numpy and
+ * neither is expf, but the order is fixed: with j = c / 4, lane li = j % 16 adds its products to 0 in ascending c, and
+ * the sixteen partial sums fold by the butterfly 8, 4, 2, 1 (lane li takes li ^ 8, then ^ 4, ^ 2, ^ 1).  It depends on
+ * Cr alone -- not on K, the row's position or a launch's window -- so a row computed inside a model's forward carries
+ * the bits of the stand-alone run.
+ *
+ * rn_paste_masks_forward: paste_masks_in_image with padding 1.  probs [K, Mo, Mo] fp32 (Mo 1..64), boxes [K, 4] fp32,
+ * labels [K] int32 or NULL (all valid), the image H x W (each below 2^24, H * W below 2^31 - 8192), threshold ->
+ * masks [K, H, W] fp32 (4-byte aligned) and / or bits [K, H, W] bytes (anywhere) holding mask > threshold; either may be
+ * NULL, not both.  Every byte is written exactly once, with 16-byte (bits: 4-byte) stores wherever four consecutive
+ * outputs share an aligned unit, whatever W and the addresses are (rn_upsample_bilinear_forward's rule; scalars remain
+ * where a wave's last lane has no neighbour and at a plane's ends).  The arithmetic is torchvision's, every fp32
+ * operation rounded on its own (mask.paste_masks_ref restates it in numpy; the kernel matches it bit for bit):
+ *     s  = (float)((double)(Mo + 2) / (double)Mo)                                   (host)
+ *     wh = ((x2 - x1) * 0.5f) * s;  hh likewise;  xc = (x2 + x1) * 0.5f;  yc likewise
+ *     bx0 = (int)(xc - wh), by0 = (int)(yc - hh), bx1 = (int)(xc + wh), by1 = (int)(yc + hh)    truncation toward zero,
+ *                                                                    each clamped to +-2^30 before the conversion
+ *     w = max(bx1 - bx0 + 1, 1);  h = max(by1 - by0 + 1, 1)
+ *     pixel (y, x) with max(bx0,0) <= x < min(bx1+1, W) and max(by0,0) <= y < min(by1+1, H):
+ *         the bilinear value (align_corners = False) of the zero-padded (Mo+2) x (Mo+2) map resized to h x w at
+ *         (y - by0, x - bx0), by the per-axis rule and the sum order of rn_upsample_bilinear_forward's contract, with
+ *         scale = (float)(Mo+2) / (float)w  resp.  / (float)h   (one fp32 division, here on the device)
+ *     every other pixel: 0
+ * A row is all zeros when its label is below 1 (where labels is given), when its box has a non-finite coordinate, or
+ * when one of the four expanded coordinates xc -+ wh, yc -+ hh is not finite (the expansion of a box near FLT_MAX).
+ * One block holds one detection's padded map in LDS and 8192 consecutive outputs of its plane; a block none of whose
+ * rows meets the box reads nothing.
+ *
+ * The object.  rn_mask_head_create(ctx, &mh, in_channels, n_layers (1..8), layer_channels[], dim_reduced, classes,
+ * resolution M (1..32)); channel counts are multiples of 64 (dim_reduced at most 1024).  rn_mask_head_set_tensor takes
+ * host fp32 in both spellings of torchvision, with or without the "roi_heads." prefix: mask_head.{i}.0.weight|bias and
+ * mask_head.mask_fcn{i+1}.weight|bias ([c_i, c_{i-1}, 3, 3], [c_i]), mask_predictor.conv5_mask.weight|bias
+ * ([c_last, Cr, 2, 2], [Cr]), mask_predictor.mask_fcn_logits.weight|bias ([C, Cr, 1, 1], [C]).  rn_mask_head_finalize
+ * needs every tensor; it packs each 3x3 through rn_conv2d_pack_weight_dt (the bias is the epilogue's shift, ReLU on) and
+ * the transposed convolution as ONE 1x1 panel of 4*Cr output channels, row (dy*2+dx)*Cr + co = W[:, co, dy, dx], the
+ * shift the bias four times, ReLU on: exact, because kernel 2 at stride 2 overlaps nothing.  norm_layer and dilation of
+ * MaskRCNNHeads are not carried.
+ * rn_mask_head_forward: pooled_nhwc [K, M, M, in_channels] fp32 (16-byte aligned), labels [K], boxes [K, 4] (NULL: no
+ * paste, masks and bits of the request must be NULL), the image size and the request -> n_layers + 1 contractions
+ * (rn_conv2d_nhwc_forward_dt: one launch each, or two where the plan finishes a chunked K sum in a second pass), the
+ * predict launch, the paste launch where masks or bits is wanted.  Of the request it reads threshold, probs [K, 2M, 2M],
+ * masks and bits [K, H, W] (any may be NULL, not all three); the pooler's parameters, rois and pooled are the route's.
+ * The scratch -- two ping-pong maps, the [K, M, M, 4*Cr] tensor and the probabilities of a forward that does not export
+ * them -- grows on demand under the box head's rules. */
+typedef struct rn_mask_request {
+    int n_levels, level[4];            /* the mask pooler's levels of the neck, as rn_roi_pool's */
+    int sampling_ratio, aligned;
+    double canonical_scale;            /* 224 */
+    int canonical_level;               /* 4 */
+    float threshold;                   /* bits = mask > threshold; torchvision: 0.5 */
+    float *rois;                       /* [B*D, 5] or NULL */
+    float *pooled;                     /* [B*D, M, M, a] or NULL */
+    float *probs;                      /* [B, D, 2M, 2M] or NULL */
+    float *masks;                      /* [B, D, H, W] or NULL */
+    uint8_t *bits;                     /* [B, D, H, W] or NULL */
+} rn_mask_request;
+typedef struct rn_mask_head rn_mask_head;
+RN_API int rn_roi_align_nhwc_forward_dt(rn_ctx *ctx, int dtype, uint64_t n_levels, const void *const *x_nhwc,
+                                        const uint64_t *h, const uint64_t *w, const float *scales, const float *thr,
+                                        uint64_t B, uint64_t C, const float *rois_dev, uint64_t K, uint64_t PH, uint64_t PW,
+                                        int sampling_ratio, int aligned, float *out_nhwc, int32_t *levels_out /* nullable */);
+RN_API int rn_detection_rois_forward(rn_ctx *ctx, const float *boxes, const int32_t *labels, uint64_t B, uint64_t D,
+                                     float *rois);
+RN_API int rn_mask_predict_forward(rn_ctx *ctx, const float *t, const int32_t *labels, const float *weight,
+                                   const float *bias, uint64_t K, uint64_t M, uint64_t Cr, uint64_t C, float *probs);
+RN_API int rn_paste_masks_forward(rn_ctx *ctx, const float *probs, const float *boxes, const int32_t *labels /* nullable */,
+                                  uint64_t K, uint64_t Mo, uint64_t H, uint64_t W, float threshold,
+                                  float *masks /* nullable */, uint8_t *bits /* nullable */);
+RN_API int rn_mask_head_create(rn_ctx *ctx, rn_mask_head **out, uint64_t in_channels, uint64_t n_layers,
+                               const uint64_t *layer_channels, uint64_t dim_reduced, uint64_t classes, uint64_t resolution);
+RN_API int rn_mask_head_set_tensor(rn_mask_head *mh, const char *key, const float *host_data, uint64_t numel);
+RN_API int rn_mask_head_finalize(rn_mask_head *mh);
+RN_API int rn_mask_head_destroy(rn_mask_head *mh);
+RN_API int rn_mask_head_forward(rn_mask_head *mh, const float *pooled_nhwc, const int32_t *labels,
+                                const float *boxes /* nullable */, uint64_t K, uint64_t image_h, uint64_t image_w,
+                                const rn_mask_request *req);
+/* The mask head behind the neck and inside a forward.  rn_fpn_forward_masks: rn_fpn_forward_detections plus the mask head
+ * and its request; rn_model_forward_masks(_u8): rn_model_forward_detections(_u8)'s arguments plus them.  One more step
+ * behind the box head's ("mask_stage" of layer "roi_heads" in the profile, one record per part).  A part of a launch
+ * batch forms the RoIs of its own D = detections_per_img detection rows per image (rn_detection_rois_forward's rule),
+ * pools them NHWC (M x M, the request's levels, sampling_ratio, aligned and canonical pair; the scales torchvision's, as
+ * the pooler's are formed) from its own slice of the neck's scratch, runs the head and writes its own [b] rows of
+ * rois [B*D, 5], pooled [B*D, M, M, a], probs [B, D, 2M, 2M], masks and bits [B, D, H, W] (H x W: the call's image);
+ * every row of every non-NULL output is written once per forward, and the values are those of the stand-alone entry
+ * points on the same rows, bit for bit.  Refused like the detections' calls, and: a mask head without a box head, a
+ * detect request whose boxes or labels is NULL, a mask head whose in_channels is not the neck's out_channels, a request
+ * out of range or with probs, masks and bits all NULL, a pooled off a 16-byte boundary, an output of the request sharing
+ * a byte with any other output of the call.  Every other forward kind issues exactly the launches it issued. */
+RN_API int rn_fpn_forward_masks(rn_fpn *fpn, rn_rpn *rpn, rn_box_head *bh, rn_mask_head *mh, const void *const *x_nhwc,
+                                uint64_t B, const uint64_t *h, const uint64_t *w, float *const *out_nchw /* nullable */,
+                                uint64_t image_h, uint64_t image_w, const rn_rpn_request *req, const rn_roi_pool *rois,
+                                const rn_detect_request *det_req, const rn_mask_request *mask_req);
+RN_API int rn_model_forward_masks(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, rn_box_head *bh, rn_mask_head *mh,
+                                  const float *input_nchw, uint64_t B, const rn_model_outputs *outs /* nullable */,
+                                  const int *stages, const rn_fpn_outputs *fpn_out /* nullable */, const rn_rpn_request *req,
+                                  const rn_roi_pool *rois, const rn_detect_request *det_req, const rn_mask_request *mask_req,
+                                  int mode);
+RN_API int rn_model_forward_masks_u8(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, rn_box_head *bh, rn_mask_head *mh,
+                                     const uint8_t *input_nhwc, uint64_t B, const rn_model_outputs *outs, const int *stages,
+                                     const rn_fpn_outputs *fpn_out, const rn_rpn_request *req, const rn_roi_pool *rois,
+                                     const rn_detect_request *det_req, const rn_mask_request *mask_req, int mode);
 /* Run one forward, then time every tile candidate of every convolution at batch B on the
  * device (events on the context's stream, on the buffers that forward used) and remember the fastest per layer for
  * that batch size.  Results do not change (candidates are bit-identical), only speed. */

@@ -92,6 +92,15 @@ class DetectRequest(ctypes.Structure):
                 ("weights", c_float * 4), ("out", Detections)]
 
 
+class MaskRequest(ctypes.Structure):
+    """rn_mask_request: the mask pooler's levels and parameters, the threshold and the outputs rois [B*D,5], pooled
+    [B*D,M,M,a], probs [B,D,2M,2M], masks [B,D,H,W] fp32 and bits [B,D,H,W] bytes (any may be NULL, not all of the last
+    three)"""
+    _fields_ = [("n_levels", c_int), ("level", c_int * 4), ("sampling_ratio", c_int), ("aligned", c_int),
+                ("canonical_scale", c_double), ("canonical_level", c_int), ("threshold", c_float), ("rois", c_void_p),
+                ("pooled", c_void_p), ("probs", c_void_p), ("masks", c_void_p), ("bits", c_void_p)]
+
+
 class Epilogue(ctypes.Structure):
     _fields_ = [("scale", c_void_p), ("shift", c_void_p), ("residual", c_void_p),
                 ("relu", c_int)]
@@ -298,6 +307,26 @@ SIGNATURES = {
     "rn_model_forward_detections_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, u64, POINTER(ModelOutputs),
                                                POINTER(c_int), POINTER(FpnOutputs), POINTER(RpnRequest), POINTER(RoiPool),
                                                POINTER(DetectRequest), c_int]),
+    "rn_roi_align_nhwc_forward_dt": (c_int, [c_void_p, c_int, u64, POINTER(c_void_p), POINTER(u64), POINTER(u64), POINTER(c_float),
+                                             POINTER(c_float), u64, u64, c_void_p, u64, u64, u64, c_int, c_int, c_void_p,
+                                             c_void_p]),
+    "rn_detection_rois_forward": (c_int, [c_void_p, fptr, fptr, u64, u64, fptr]),
+    "rn_mask_predict_forward": (c_int, [c_void_p, fptr, fptr, fptr, fptr, u64, u64, u64, u64, fptr]),
+    "rn_paste_masks_forward": (c_int, [c_void_p, fptr, fptr, fptr, u64, u64, u64, u64, c_float, fptr, fptr]),
+    "rn_mask_head_create": (c_int, [c_void_p, POINTER(c_void_p), u64, u64, POINTER(u64), u64, u64, u64]),
+    "rn_mask_head_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, u64]),
+    "rn_mask_head_finalize": (c_int, [c_void_p]),
+    "rn_mask_head_destroy": (c_int, [c_void_p]),
+    "rn_mask_head_forward": (c_int, [c_void_p, fptr, fptr, fptr, u64, u64, u64, POINTER(MaskRequest)]),
+    "rn_fpn_forward_masks": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), u64, POINTER(u64), POINTER(u64),
+                                     POINTER(c_void_p), u64, u64, POINTER(RpnRequest), POINTER(RoiPool),
+                                     POINTER(DetectRequest), POINTER(MaskRequest)]),
+    "rn_model_forward_masks": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, fptr, u64, POINTER(ModelOutputs),
+                                       POINTER(c_int), POINTER(FpnOutputs), POINTER(RpnRequest), POINTER(RoiPool),
+                                       POINTER(DetectRequest), POINTER(MaskRequest), c_int]),
+    "rn_model_forward_masks_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, u64, POINTER(ModelOutputs),
+                                          POINTER(c_int), POINTER(FpnOutputs), POINTER(RpnRequest), POINTER(RoiPool),
+                                          POINTER(DetectRequest), POINTER(MaskRequest), c_int]),
     "rn_model_destroy": (c_int, [c_void_p]),
     "rn_model_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, u64]),
     "rn_model_load_dir": (c_int, [c_void_p, c_char_p]),

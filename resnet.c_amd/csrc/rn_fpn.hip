@@ -417,7 +417,7 @@ int rn_fpn_step(rn_fpn *f, rn_ctx *ctx, int kind, int level, const void *x_nhwc,
 namespace {
 
 // what follows the exports, after the kinds of rn_fpn_step
-enum { NECK_RPN = RN_FPN_EXPORT + 1, NECK_ROI, NECK_BOX };
+enum { NECK_RPN = RN_FPN_EXPORT + 1, NECK_ROI, NECK_BOX, NECK_MASK };
 
 constexpr int kRoiOperands = 3;
 
@@ -459,6 +459,49 @@ int rn_fpn_roi_check(rn_neck_call *c, rn_ctx *ctx)
     if (rn_roi_level_thresholds((uint64_t)rp->n_levels, c->scales, rp->canonical_scale, rp->canonical_level, c->thr) != RN_OK)
         return rn_set_error(ctx, RN_ERR_INVALID, "%s: the level thresholds cannot be formed", __func__);
     return RN_OK;
+}
+
+// the mask request's pooler against the neck: every refusal that concerns it alone; fills the mask pooler's scales
+// (formed as rn_fpn_roi_check forms the pooler's) and thresholds
+int neck_mask_pool_check(rn_neck_call *c, rn_ctx *ctx, const char *fn)
+{
+    const rn_fpn *f = c->fpn;
+    const rn_mask_request *q = c->mask_req;
+    const char *why = NULL;
+    if (q->n_levels < 1 || q->n_levels > f->n) why = "the mask pooler reads 1 .. n_levels of the neck's levels";
+    for (int i = 0; i < q->n_levels && !why; ++i)
+        if (q->level[i] < 0 || q->level[i] >= f->n || (i > 0 && q->level[i] <= q->level[i - 1]))
+            why = "the mask pooler's levels must be the neck's (0 .. n_levels - 1, the pool is none), ascending";
+    if (!why && q->sampling_ratio <= 0)
+        return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "%s: the mask pooler's sampling_ratio <= 0 (adaptive grids) is not carried", fn);
+    if (!why && q->sampling_ratio > 4) why = "the mask pooler's sampling_ratio must be 1..4";
+    if (!why && q->aligned != 0 && q->aligned != 1) why = "the mask pooler's aligned must be 0 or 1";
+    if (!why && !(q->canonical_scale > 0.0)) why = "the mask pooler's canonical_scale must be positive";
+    if (!why && (reinterpret_cast<uintptr_t>(q->pooled) & 15) != 0) why = "mask.pooled is off a 16-byte boundary";
+    if (why) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s", fn, why);
+    for (int i = 0; i < q->n_levels; ++i)
+        c->mask_scales[i] = (float)exp2(rint(log2((double)c->h[q->level[i]] / (double)c->image_h)));
+    if (rn_roi_level_thresholds((uint64_t)q->n_levels, c->mask_scales, q->canonical_scale, q->canonical_level, c->mask_thr) != RN_OK)
+        return rn_set_error(ctx, RN_ERR_INVALID, "%s: the mask pooler's level thresholds cannot be formed", fn);
+    return RN_OK;
+}
+
+// the mask head's stage on the 3x3 outputs of B images, read in place sub0 images into the neck's scratch, on these
+// images' own detection rows
+int neck_mask_step(const rn_neck_call *c, rn_ctx *ctx, uint64_t sub0, uint64_t img0, uint64_t B)
+{
+    const rn_fpn *f = c->fpn;
+    const rn_mask_request *q = c->mask_req;
+    const void *maps[kFpnMaxLevels];
+    uint64_t hs[kFpnMaxLevels], ws[kFpnMaxLevels];
+    for (int i = 0; i < q->n_levels; ++i) {
+        const int l = q->level[i];
+        if ((sub0 + B) * c->h[l] * c->w[l] > f->cap_pix[l]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn: scratch not reserved");
+        maps[i] = f->outb[l] + sub0 * c->h[l] * c->w[l] * f->a, hs[i] = c->h[l], ws[i] = c->w[l];
+    }
+    return rn_mask_head_stage(c->mask_head, ctx, (uint64_t)q->n_levels, maps, hs, ws, c->mask_scales, c->mask_thr, c->images, sub0,
+                              img0, B, c->det_req->detections_per_img, c->det_req->out.boxes, c->det_req->out.labels, c->image_h,
+                              c->image_w, q);
 }
 
 // The pooler's launch on ctx for the B images from the caller's image img0 on, whose 3x3 outputs start sub0 images
@@ -514,6 +557,7 @@ int neck_step_at(const rn_neck_call *c, int step, int *kind, int *level)
     if (c->rpn) put(NECK_RPN, 0);
     if (c->roi && c->roi->K > 0) put(NECK_ROI, 0);
     if (c->box_head) put(NECK_BOX, 0);
+    if (c->mask_head) put(NECK_MASK, 0);
     return at;
 }
 
@@ -566,23 +610,37 @@ int rn_neck_check(rn_neck_call *c, rn_ctx *ctx, const char *fn, const rn_operand
         if (why) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s", fn, why);
         RN_TRY(rn_box_head_check(c->box_head, ctx, c->det_req, B, c->rpn_req->post_nms_top_n, c->image_h, c->image_w));
     }
+    if (c->mask_head) {  // behind the box head, on the detections it writes
+        if (!c->box_head || !c->det_req) why = "the mask head needs the box head and its request";
+        else if (!c->det_req->out.boxes || !c->det_req->out.labels) why = "the mask head needs boxes and labels of the detect request";
+        else if (!c->mask_req) why = "the mask request is NULL";
+        else rn_mask_head_matches(c->mask_head, ctx, f->a, &why);
+        if (why) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s", fn, why);
+        RN_TRY(rn_mask_head_check(c->mask_head, ctx, fn, c->mask_req, B * c->det_req->detections_per_img, 1, c->image_h, c->image_w));
+        RN_TRY(neck_mask_pool_check(c, ctx, fn));
+    }
     c->pool = f->extra && (c->out[n] || c->rpn);
     for (int i = 0; i < n; ++i) c->layer_runs[i] = c->out[i] || (c->pool && i == n - 1) || c->rpn;
     if (rp && rp->K > 0)
         for (int i = 0; i < rp->n_levels; ++i) c->layer_runs[rp->level[i]] = 1;
     // the operand matrix: every group against every group before it
-    operand levels[kFpnMaxLevels + 1], roi[kRoiOperands], rpn[RN_RPN_OPERANDS], box[RN_BOX_HEAD_OPERANDS];
+    operand levels[kFpnMaxLevels + 1], roi[kRoiOperands], rpn[RN_RPN_OPERANDS], box[RN_BOX_HEAD_OPERANDS], mask[RN_MASK_HEAD_OPERANDS];
     for (int i = 0; i < n_out; ++i) levels[i] = {c->out[i], B * f->a * c->hl[i] * c->wl[i] * sizeof(float), level_names[i], true, false};
     if (rp) roi_operands(c, roi);
     if (c->rpn) rn_rpn_operands(c->rpn, c->rpn_req, B, rpn);
     if (c->box_head) rn_box_head_operands(c->box_head, c->det_req, B, c->rpn_req->post_nms_top_n, box);
+    if (c->mask_head) {
+        rn_mask_head_operands(c->mask_head, c->mask_req, B * c->det_req->detections_per_img, c->image_h, c->image_w, mask);
+        RN_TRY(check_operands(ctx, fn, mask, RN_MASK_HEAD_OPERANDS));
+    }
     if (c->chain) roi[2].ptr = NULL;  // the one exception: rois_dev IS the rpn's out.rois, which stands for it below
-    const rn_operand_group groups[5] = {{others, n_others},
+    const rn_operand_group groups[6] = {{others, n_others},
                                         {levels, n_out},
                                         {roi, rp ? kRoiOperands : 0},
                                         {rpn, c->rpn ? RN_RPN_OPERANDS : 0},
-                                        {box, c->box_head ? RN_BOX_HEAD_OPERANDS : 0}};
-    return check_operand_groups(ctx, fn, groups, 5);
+                                        {box, c->box_head ? RN_BOX_HEAD_OPERANDS : 0},
+                                        {mask, c->mask_head ? RN_MASK_HEAD_OPERANDS : 0}};
+    return check_operand_groups(ctx, fn, groups, 6);
 }
 
 int rn_neck_reserve(const rn_neck_call *c, uint64_t images_at_once)
@@ -590,6 +648,7 @@ int rn_neck_reserve(const rn_neck_call *c, uint64_t images_at_once)
     RN_TRY(rn_fpn_reserve(c->fpn, images_at_once, c->h, c->w));
     if (c->rpn) RN_TRY(rn_rpn_reserve(c->rpn, images_at_once, c->hl, c->wl, c->rpn_req->pre_nms_top_n));
     if (c->box_head) RN_TRY(rn_box_head_reserve(c->box_head, images_at_once, c->rpn_req->post_nms_top_n));
+    if (c->mask_head) RN_TRY(rn_mask_head_reserve(c->mask_head, images_at_once * c->det_req->detections_per_img, 1));
     return RN_OK;
 }
 
@@ -624,6 +683,12 @@ int rn_neck_plan(const rn_neck_call *c, uint64_t B, int step, const char **op, c
         name = "box_stage", lay = "roi_heads";
         by = (double)(B * post * (c->a * rp->PH * rp->PW)) * 4.0;
         break;
+    case NECK_MASK: {  // the RoI former, the pooler, the contractions, the predict and the paste under one record
+        const uint64_t M = rn_mask_head_resolution(c->mask_head);
+        name = "mask_stage", lay = "roi_heads";
+        by = (double)(B * c->det_req->detections_per_img * M * M * c->a) * 4.0;
+        break;
+    }
     default:
         name = rn_fpn_op_name(c->fpn, kind, level);
         rn_fpn_cost(c->fpn, kind, level, B, c->h, c->w, &fl, &by);
@@ -652,6 +717,7 @@ int rn_neck_step(const rn_neck_call *c, rn_ctx *ctx, int step, uint64_t sub0, ui
         return rn_box_head_step(c->box_head, ctx, rp->pooled + row0 * feat, rp->rois_dev + row0 * 5, sub0, img0, B, post,
                                 c->image_h, c->image_w, c->det_req);
     }
+    case NECK_MASK: return neck_mask_step(c, ctx, sub0, img0, B);
     case RN_FPN_EXPORT:  // into the caller's buffer from image img0 on
         return rn_fpn_step(c->fpn, ctx, kind, level, NULL, sub0, B, c->h, c->w, c->out[level] + img0 * c->a * c->hl[level] * c->wl[level]);
     default: return rn_fpn_step(c->fpn, ctx, kind, level, NULL, sub0, B, c->h, c->w, NULL);
@@ -744,6 +810,19 @@ int rn_fpn_forward_detections(rn_fpn *f, rn_rpn *rpn, rn_box_head *bh, const voi
     c.box_head = bh, c.det_req = det_req;
     if (f && (!rpn || !req)) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: rpn or req is NULL", __func__);
     if (f && (!bh || !det_req)) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: the box head or its request is NULL", __func__);
+    return fpn_forward(__func__, &c, x_nhwc, h, w);
+}
+
+int rn_fpn_forward_masks(rn_fpn *f, rn_rpn *rpn, rn_box_head *bh, rn_mask_head *mh, const void *const *x_nhwc, uint64_t B,
+                         const uint64_t *h, const uint64_t *w, float *const *out_nchw, uint64_t image_h, uint64_t image_w,
+                         const rn_rpn_request *req, const rn_roi_pool *rois, const rn_detect_request *det_req,
+                         const rn_mask_request *mask_req)
+{
+    rn_neck_call c = {};
+    c.fpn = f, c.out = out_nchw, c.images = B, c.roi = rois, c.rpn = rpn, c.rpn_req = req, c.image_h = image_h, c.image_w = image_w;
+    c.box_head = bh, c.det_req = det_req, c.mask_head = mh, c.mask_req = mask_req;
+    if (f && (!rpn || !req)) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: rpn or req is NULL", __func__);
+    if (f && !mh) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: the mask head is NULL", __func__);
     return fpn_forward(__func__, &c, x_nhwc, h, w);
 }
 

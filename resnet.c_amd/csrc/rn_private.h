@@ -98,6 +98,16 @@ int rn_roi_align_window(rn_ctx *ctx, int dtype, uint64_t n_levels, const void *c
                         const uint64_t *w, const float *scales, const float *thr, uint64_t images, uint64_t img_lo,
                         uint64_t img_cnt, int write_invalid, uint64_t C, const float *rois_dev, uint64_t K, uint64_t PH,
                         uint64_t PW, int sampling_ratio, int aligned, float *out, int32_t *levels_out);
+/* the same window of rn_roi_align_nhwc_forward_dt: out [K, PH, PW, C] on a 16-byte boundary */
+int rn_roi_align_nhwc_window(rn_ctx *ctx, int dtype, uint64_t n_levels, const void *const *x_nhwc, const uint64_t *h,
+                             const uint64_t *w, const float *scales, const float *thr, uint64_t images, uint64_t img_lo,
+                             uint64_t img_cnt, int write_invalid, uint64_t C, const float *rois_dev, uint64_t K, uint64_t PH,
+                             uint64_t PW, int sampling_ratio, int aligned, float *out, int32_t *levels_out);
+
+/* ---- rn_mask.hip: the windows the parts of a forward use, no checks ---- */
+/* rn_detection_rois_forward for the B images from image img0 on; boxes, labels and rois point at these images' rows */
+int rn_detection_rois_window(rn_ctx *ctx, const float *boxes, const int32_t *labels, uint64_t img0, uint64_t B, uint64_t D,
+                             float *rois);
 
 /* ---- rn_rpn.hip: the RPN behind a neck, mirroring rn_fpn_roi_* ---- */
 /* 1 when the rpn is finalized, lives on ctx's device, reads in_channels channels and n_levels levels; *why otherwise */
@@ -132,6 +142,30 @@ int rn_box_head_operands(const rn_box_head *bh, const rn_detect_request *req, ui
 int rn_box_head_step(rn_box_head *bh, rn_ctx *ctx, const float *pooled, const float *rois, uint64_t sub0, uint64_t img0,
                      uint64_t B, uint64_t R, uint64_t image_h, uint64_t image_w, const rn_detect_request *req);
 
+/* ---- rn_mask.hip: the mask head behind the box head, mirroring rn_box_head_* ---- */
+/* 1 when the mask head is finalized, lives on ctx's device and reads in_channels channels per pooled pixel; *why otherwise */
+int rn_mask_head_matches(const rn_mask_head *mh, const rn_ctx *ctx, uint64_t in_channels, const char **why);
+/* M: the side of the pooled map the head reads */
+uint64_t rn_mask_head_resolution(const rn_mask_head *mh);
+/* the object's scratch for `rows` detections; with_pool: the RoI rows and the pooled features of a stage behind a neck too */
+int rn_mask_head_reserve(rn_mask_head *mh, uint64_t rows, int with_pool);
+/* every refusal that concerns the request's outputs and the shapes alone, for `rows` detections (text in ctx, under fn);
+ * paste_possible: the caller has the boxes a paste needs */
+int rn_mask_head_check(const rn_mask_head *mh, rn_ctx *ctx, const char *fn, const rn_mask_request *req, uint64_t rows,
+                       int paste_possible, uint64_t image_h, uint64_t image_w);
+/* the request's 5 outputs for `rows` detections as operands; returns 5 */
+enum { RN_MASK_HEAD_OPERANDS = 5 };
+int rn_mask_head_operands(const rn_mask_head *mh, const rn_mask_request *req, uint64_t rows, uint64_t image_h, uint64_t image_w,
+                          rn_operand ops[RN_MASK_HEAD_OPERANDS]);
+/* The stage's launches on ctx for the B images from the caller's image img0 on (D detections each), whose scratch starts
+ * sub0 images into the object's tensors: the RoI former on these images' detection rows, the NHWC pooler on maps[i]
+ * (level i of image img0, h[i] x w[i], fp32), then n_layers + 1 contractions of one or two launches, the predict launch
+ * and the paste where wanted.  boxes [images*D, 4], labels [images*D] and the request's outputs: the whole call's. */
+int rn_mask_head_stage(rn_mask_head *mh, rn_ctx *ctx, uint64_t n_levels, const void *const *maps, const uint64_t *h,
+                       const uint64_t *w, const float *scales, const float *thr, uint64_t images, uint64_t sub0, uint64_t img0,
+                       uint64_t B, uint64_t D, const float *boxes, const int32_t *labels, uint64_t image_h, uint64_t image_w,
+                       const rn_mask_request *req);
+
 /* ---- rn_fpn.hip: one forward of a neck and what runs behind it, for both entry families ---- */
 /* The description of a call.  It lives on the stack of the entry point that runs it (rn_fpn_forward*, the model's
  * forward_fpn); rn_neck_check fills the second half once and everything after it only reads. */
@@ -144,6 +178,8 @@ typedef struct rn_neck_call {
     const rn_rpn_request *rpn_req;
     rn_box_head *box_head;          /* the box head behind the chained pooler and its request, or NULL */
     const rn_detect_request *det_req;
+    rn_mask_head *mask_head;        /* the mask head behind the box head and its request, or NULL */
+    const rn_mask_request *mask_req;
     uint64_t image_h, image_w;      /* the image the rpn and the box head clip to */
     uint64_t h[4], w[4];            /* the input levels' maps */
     uint64_t images;                /* the batch of the whole call */
@@ -154,19 +190,20 @@ typedef struct rn_neck_call {
     int pool;                       /* the max-pool runs */
     int layer_runs[4];              /* the 3x3 of the level runs: exported, pooled from, or read by the pooler / the rpn */
     float scales[4], thr[3];        /* the pooler's levels' scales and the thresholds between them */
+    float mask_scales[4], mask_thr[3]; /* the mask pooler's */
 } rn_neck_call;
 /* Every refusal the two families share, in one order: the neck, the outputs' alignment, nothing wanted, the pooler's
- * request, the rpn and its request, the box head's conditions and request, then the operand matrix: no output of the
- * exported levels, the pooler, the rpn, the box head or `others` (the family's own operands: the model's head outputs,
+ * request, the rpn and its request, the box head's conditions and request, the mask head's, then the operand matrix: no
+ * output of the exported levels, the pooler, the rpn, the box head, the mask head or `others` (the family's own operands: the model's head outputs,
  * the stand-alone family's input maps) may share a byte with an operand of another of these groups -- but for the
  * chained pooler's rois_dev, which IS the rpn's out.rois.  Text in ctx, under the name fn; nothing is launched. */
 int rn_neck_check(rn_neck_call *call, rn_ctx *ctx, const char *fn, const rn_operand *others, int n_others);
-/* the scratch of the neck, the rpn and the box head for parts of at most images_at_once images */
+/* the scratch of the neck, the rpn, the box head and the mask head for parts of at most images_at_once images */
 int rn_neck_reserve(const rn_neck_call *call, uint64_t images_at_once);
 /* The one source of what follows the laterals for a part of B images: returns the number of steps and, for step
  * 0 .. that - 1, its profile name, layer, FLOPs and bytes (any may be NULL; another step only counts).  In order:
  * the top-down steps coarsest first, the 3x3 of every level that runs, the pool, the exports, the rpn's stage, the
- * pooler (the whole call's window, or in the chain the part's own rows), the box head's stage. */
+ * pooler (the whole call's window, or in the chain the part's own rows), the box head's stage, the mask head's stage. */
 int rn_neck_plan(const rn_neck_call *call, uint64_t B, int step, const char **op, const char **layer, double *flops,
                  double *bytes);
 /* launch `step` of rn_neck_plan on ctx for the B images from the caller's image img0 on, whose scratch starts sub0

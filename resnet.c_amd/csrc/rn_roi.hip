@@ -75,7 +75,9 @@ __device__ __forceinline__ void roi_axis(float c, uint32_t n, uint32_t *lo, uint
     *hw = 1.0f - *l;
 }
 
-template <typename T, int S>
+// NHWC: the store layout [K, PH, PW, C] of rn_roi_align_nhwc_forward_dt.  An item's V values are 16 (bf16 maps: 32)
+// consecutive bytes of that layout, so the thread stores its acc[] itself: no tile, no barrier, the same values.
+template <typename T, int S, bool NHWC>
 __global__ __launch_bounds__(kRoiBlock) void roi_align_kernel(const roi_args p)
 {
     constexpr int V = 16 / sizeof(T), UY = S <= 2 ? S : 1;  // the sample rows unrolled: a row's loads are in flight together
@@ -196,12 +198,21 @@ __global__ __launch_bounds__(kRoiBlock) void roi_align_kernel(const roi_args p)
                     }
                 }
             }
+            if (NHWC) {
+                float4 *dst = reinterpret_cast<float4 *>(p.out + ((uint64_t)r * p.bins + b) * p.C + c0 + k * V);
+#pragma unroll
+                for (int e = 0; e < V; e += 4)
+                    dst[e / 4] = make_float4(acc[e] / (float)(S * S), acc[e + 1] / (float)(S * S), acc[e + 2] / (float)(S * S),
+                                             acc[e + 3] / (float)(S * S));
+                continue;
+            }
 #pragma unroll
             for (int e = 0; e < V; ++e) {
                 const uint32_t u = (k * V + e) * p.bins + b + sh;
                 tile[(u >> 2) + (u & 3) * p.Q] = acc[e] / (float)(S * S);
             }
         }
+        if (NHWC) continue;  // nothing of the block is shared: the next RoI may start
         __syncthreads();
         const uint32_t quads = (len + sh + 3) >> 2;
         for (uint32_t q = threadIdx.x; q < quads; q += kRoiBlock) {
@@ -225,16 +236,110 @@ __global__ __launch_bounds__(kRoiBlock) void roi_align_kernel(const roi_args p)
     }
 }
 
-template <typename T>
+template <typename T, bool NHWC>
 void roi_launch_s(int S, dim3 grid, size_t lds, hipStream_t stream, const roi_args &p)
 {
     switch (S) {
-    case 1: roi_align_kernel<T, 1><<<grid, kRoiBlock, lds, stream>>>(p); break;
-    case 2: roi_align_kernel<T, 2><<<grid, kRoiBlock, lds, stream>>>(p); break;
-    case 3: roi_align_kernel<T, 3><<<grid, kRoiBlock, lds, stream>>>(p); break;
-    default: roi_align_kernel<T, 4><<<grid, kRoiBlock, lds, stream>>>(p); break;
+    case 1: roi_align_kernel<T, 1, NHWC><<<grid, kRoiBlock, lds, stream>>>(p); break;
+    case 2: roi_align_kernel<T, 2, NHWC><<<grid, kRoiBlock, lds, stream>>>(p); break;
+    case 3: roi_align_kernel<T, 3, NHWC><<<grid, kRoiBlock, lds, stream>>>(p); break;
+    default: roi_align_kernel<T, 4, NHWC><<<grid, kRoiBlock, lds, stream>>>(p); break;
     }
 }
+
+// the launch of either form, no checks
+int roi_window(rn_ctx *ctx, bool nhwc, int dtype, uint64_t n_levels, const void *const *x_nhwc, const uint64_t *h,
+               const uint64_t *w, const float *scales, const float *thr, uint64_t images, uint64_t img_lo, uint64_t img_cnt,
+               int write_invalid, uint64_t C, const float *rois_dev, uint64_t K, uint64_t PH, uint64_t PW, int sampling_ratio,
+               int aligned, float *out, int32_t *levels_out)
+{
+    const uint64_t V = 16 / rn_elem_size(dtype), bins = PH * PW, cpp = C / V;
+    roi_args p;
+    memset(&p, 0, sizeof(p));
+    for (uint64_t i = 0; i < n_levels; ++i) {
+        p.map[i] = (const uint4 *)x_nhwc[i], p.h[i] = (uint32_t)h[i], p.w[i] = (uint32_t)w[i], p.scale[i] = scales[i];
+        if (i + 1 < n_levels) p.thr[i] = thr[i];
+    }
+    p.rois = rois_dev, p.out = out, p.levels = levels_out;
+    p.n = (uint32_t)n_levels, p.K = (uint32_t)K, p.C = (uint32_t)C, p.cpp = (uint32_t)cpp;
+    p.images = (uint32_t)images, p.img_lo = (uint32_t)img_lo, p.img_cnt = (uint32_t)img_cnt;
+    p.write_invalid = write_invalid ? 1u : 0u;
+    p.PH = (uint32_t)PH, p.PW = (uint32_t)PW, p.bins = (uint32_t)bins;
+    rn_fast_div(p.PW, &p.mul_pw, &p.shr_pw);
+    // the slab: the most chunks (a power of two, at most 64 channels of fp32 / bf16 lanes' worth) whose outputs fit
+    uint32_t sl = 1, lg = 0;
+    while (sl * 2 * V <= 64 && sl < cpp && (uint64_t)sl * 2 * V * bins * sizeof(float) <= kRoiLdsCap) sl *= 2, ++lg;
+    p.sl = sl, p.sl_log2 = lg;
+    uint32_t Q = (uint32_t)((sl * V * bins + 6) / 4 + 1);
+    Q += (8 + 32 - Q % 32) % 32;  // Q = 8 (mod 32)
+    p.Q = Q;
+    p.aligned = aligned ? 1u : 0u;
+    const size_t lds = nhwc ? 0 : (size_t)Q * 4 * sizeof(float);  // the NHWC form has no tile
+    const dim3 grid((unsigned)rn_ceil_div(cpp, sl), (unsigned)(K < 65535 ? K : 65535));
+    if (nhwc) {
+        if (dtype == RN_DTYPE_BF16) roi_launch_s<bf16_t, true>(sampling_ratio, grid, lds, ctx->stream, p);
+        else roi_launch_s<float, true>(sampling_ratio, grid, lds, ctx->stream, p);
+        return rn_after_launch(ctx, "rn_roi_align_nhwc_forward_dt");
+    }
+    if (dtype == RN_DTYPE_BF16) roi_launch_s<bf16_t, false>(sampling_ratio, grid, lds, ctx->stream, p);
+    else roi_launch_s<float, false>(sampling_ratio, grid, lds, ctx->stream, p);
+    return rn_after_launch(ctx, "rn_roi_align_forward_dt");
+}
+
+#define ROI_REQUIRE(cond, msg)                                                            \
+    do {                                                                                  \
+        if (!(cond)) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s", fn, (msg));       \
+    } while (0)
+// both public forms: every check, then the launch.  fn: the entry point's name in a refusal
+int roi_forward(rn_ctx *ctx, const char *fn, bool nhwc, int dtype, uint64_t n_levels, const void *const *x_nhwc,
+                const uint64_t *h, const uint64_t *w, const float *scales, const float *thr, uint64_t B, uint64_t C,
+                const float *rois_dev, uint64_t K, uint64_t PH, uint64_t PW, int sampling_ratio, int aligned, float *out,
+                int32_t *levels_out)
+{
+    RN_ENTER(ctx);
+    ROI_REQUIRE(dtype == RN_DTYPE_F32 || dtype == RN_DTYPE_BF16, "unknown dtype");
+    ROI_REQUIRE(n_levels >= 1 && n_levels <= (uint64_t)kRoiMaxLevels, "n_levels must be 1..4");
+    ROI_REQUIRE(x_nhwc && h && w && scales, "x_nhwc, h, w or scales is NULL");
+    ROI_REQUIRE(n_levels == 1 || thr, "thr is NULL (n_levels - 1 thresholds)");
+    ROI_REQUIRE(PH >= 1 && PH <= 32 && PW >= 1 && PW <= 32, "PH and PW must be 1..32");
+    if (sampling_ratio <= 0)
+        return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "%s: sampling_ratio <= 0 (adaptive grids) is not carried", fn);
+    ROI_REQUIRE(sampling_ratio <= 4, "sampling_ratio must be 1..4");
+    ROI_REQUIRE(aligned == 0 || aligned == 1, "aligned must be 0 or 1");
+    const uint64_t es = rn_elem_size(dtype), per = 16 / es;
+    ROI_REQUIRE(C >= 1 && C < (1ull << 31) && C % per == 0, "C must be a multiple of 16 bytes (and below 2^31)");
+    ROI_REQUIRE(B < (1ull << 31) && K < (1ull << 31), "B and K must be below 2^31");
+    for (uint64_t i = 0; i < n_levels; ++i) {
+        ROI_REQUIRE(h[i] >= 1 && w[i] >= 1, "h and w must be >= 1");
+        ROI_REQUIRE(h[i] < (1ull << 31) && w[i] < (1ull << 31) && h[i] * w[i] < (1ull << 31) &&
+                            B * h[i] * w[i] < (1ull << 31),
+                   "B * h * w must be below 2^31");
+        ROI_REQUIRE(scales[i] > 0.0f && isfinite(scales[i]), "every scale must be positive and finite");
+    }
+    if (K == 0 || B == 0) return RN_OK;
+    ROI_REQUIRE(rois_dev, "rois_dev is NULL");
+    ROI_REQUIRE(out, "out is NULL");
+    ROI_REQUIRE((reinterpret_cast<uintptr_t>(rois_dev) & 3) == 0, "rois_dev is off a 4-byte boundary");
+    if (nhwc) ROI_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, "out is off a 16-byte boundary");
+    ROI_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "out is off a 4-byte boundary");
+    ROI_REQUIRE((reinterpret_cast<uintptr_t>(levels_out) & 3) == 0, "levels_out is off a 4-byte boundary");
+    const uint64_t out_bytes = K * C * PH * PW * sizeof(float);
+    for (uint64_t i = 0; i < n_levels; ++i) {
+        ROI_REQUIRE(x_nhwc[i], "a level's map is NULL");
+        ROI_REQUIRE((reinterpret_cast<uintptr_t>(x_nhwc[i]) & 15) == 0, "a level's map is off a 16-byte boundary");
+        ROI_REQUIRE(!rn_overlap(out, out_bytes, x_nhwc[i], B * h[i] * w[i] * C * es), "out overlaps a level's map");
+        ROI_REQUIRE(!levels_out || !rn_overlap(levels_out, K * 4, x_nhwc[i], B * h[i] * w[i] * C * es),
+                   "levels_out overlaps a level's map");
+    }
+    ROI_REQUIRE(!rn_overlap(out, out_bytes, rois_dev, K * 5 * sizeof(float)), "out overlaps rois_dev");
+    ROI_REQUIRE(!levels_out || !rn_overlap(levels_out, K * 4, rois_dev, K * 5 * sizeof(float)),
+               "levels_out overlaps rois_dev");
+    ROI_REQUIRE(!levels_out || !rn_overlap(levels_out, K * 4, out, out_bytes), "levels_out overlaps out");
+    return roi_window(ctx, nhwc, dtype, n_levels, x_nhwc, h, w, scales, thr, B, 0, B, 1, C, rois_dev, K, PH, PW, sampling_ratio,
+                      aligned, out, levels_out);
+}
+#undef ROI_REQUIRE
+
 
 }  // namespace
 
@@ -263,32 +368,17 @@ int rn_roi_align_window(rn_ctx *ctx, int dtype, uint64_t n_levels, const void *c
                         uint64_t img_cnt, int write_invalid, uint64_t C, const float *rois_dev, uint64_t K, uint64_t PH,
                         uint64_t PW, int sampling_ratio, int aligned, float *out, int32_t *levels_out)
 {
-    const uint64_t V = 16 / rn_elem_size(dtype), bins = PH * PW, cpp = C / V;
-    roi_args p;
-    memset(&p, 0, sizeof(p));
-    for (uint64_t i = 0; i < n_levels; ++i) {
-        p.map[i] = (const uint4 *)x_nhwc[i], p.h[i] = (uint32_t)h[i], p.w[i] = (uint32_t)w[i], p.scale[i] = scales[i];
-        if (i + 1 < n_levels) p.thr[i] = thr[i];
-    }
-    p.rois = rois_dev, p.out = out, p.levels = levels_out;
-    p.n = (uint32_t)n_levels, p.K = (uint32_t)K, p.C = (uint32_t)C, p.cpp = (uint32_t)cpp;
-    p.images = (uint32_t)images, p.img_lo = (uint32_t)img_lo, p.img_cnt = (uint32_t)img_cnt;
-    p.write_invalid = write_invalid ? 1u : 0u;
-    p.PH = (uint32_t)PH, p.PW = (uint32_t)PW, p.bins = (uint32_t)bins;
-    rn_fast_div(p.PW, &p.mul_pw, &p.shr_pw);
-    // the slab: the most chunks (a power of two, at most 64 channels of fp32 / bf16 lanes' worth) whose outputs fit
-    uint32_t sl = 1, lg = 0;
-    while (sl * 2 * V <= 64 && sl < cpp && (uint64_t)sl * 2 * V * bins * sizeof(float) <= kRoiLdsCap) sl *= 2, ++lg;
-    p.sl = sl, p.sl_log2 = lg;
-    uint32_t Q = (uint32_t)((sl * V * bins + 6) / 4 + 1);
-    Q += (8 + 32 - Q % 32) % 32;  // Q = 8 (mod 32)
-    p.Q = Q;
-    p.aligned = aligned ? 1u : 0u;
-    const size_t lds = (size_t)Q * 4 * sizeof(float);
-    const dim3 grid((unsigned)rn_ceil_div(cpp, sl), (unsigned)(K < 65535 ? K : 65535));
-    if (dtype == RN_DTYPE_BF16) roi_launch_s<bf16_t>(sampling_ratio, grid, lds, ctx->stream, p);
-    else roi_launch_s<float>(sampling_ratio, grid, lds, ctx->stream, p);
-    return rn_after_launch(ctx, "rn_roi_align_forward_dt");
+    return roi_window(ctx, false, dtype, n_levels, x_nhwc, h, w, scales, thr, images, img_lo, img_cnt, write_invalid, C,
+                      rois_dev, K, PH, PW, sampling_ratio, aligned, out, levels_out);
+}
+
+int rn_roi_align_nhwc_window(rn_ctx *ctx, int dtype, uint64_t n_levels, const void *const *x_nhwc, const uint64_t *h,
+                             const uint64_t *w, const float *scales, const float *thr, uint64_t images, uint64_t img_lo,
+                             uint64_t img_cnt, int write_invalid, uint64_t C, const float *rois_dev, uint64_t K, uint64_t PH,
+                             uint64_t PW, int sampling_ratio, int aligned, float *out, int32_t *levels_out)
+{
+    return roi_window(ctx, true, dtype, n_levels, x_nhwc, h, w, scales, thr, images, img_lo, img_cnt, write_invalid, C,
+                      rois_dev, K, PH, PW, sampling_ratio, aligned, out, levels_out);
 }
 
 int rn_roi_align_forward_dt(rn_ctx *ctx, int dtype, uint64_t n_levels, const void *const *x_nhwc, const uint64_t *h,
@@ -296,46 +386,17 @@ int rn_roi_align_forward_dt(rn_ctx *ctx, int dtype, uint64_t n_levels, const voi
                             const float *rois_dev, uint64_t K, uint64_t PH, uint64_t PW, int sampling_ratio, int aligned,
                             float *out, int32_t *levels_out)
 {
-    RN_ENTER(ctx);
-    RN_REQUIRE(ctx, dtype == RN_DTYPE_F32 || dtype == RN_DTYPE_BF16, "unknown dtype");
-    RN_REQUIRE(ctx, n_levels >= 1 && n_levels <= (uint64_t)kRoiMaxLevels, "n_levels must be 1..4");
-    RN_REQUIRE(ctx, x_nhwc && h && w && scales, "x_nhwc, h, w or scales is NULL");
-    RN_REQUIRE(ctx, n_levels == 1 || thr, "thr is NULL (n_levels - 1 thresholds)");
-    RN_REQUIRE(ctx, PH >= 1 && PH <= 32 && PW >= 1 && PW <= 32, "PH and PW must be 1..32");
-    if (sampling_ratio <= 0)
-        return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "%s: sampling_ratio <= 0 (adaptive grids) is not carried", __func__);
-    RN_REQUIRE(ctx, sampling_ratio <= 4, "sampling_ratio must be 1..4");
-    RN_REQUIRE(ctx, aligned == 0 || aligned == 1, "aligned must be 0 or 1");
-    const uint64_t es = rn_elem_size(dtype), per = 16 / es;
-    RN_REQUIRE(ctx, C >= 1 && C < (1ull << 31) && C % per == 0, "C must be a multiple of 16 bytes (and below 2^31)");
-    RN_REQUIRE(ctx, B < (1ull << 31) && K < (1ull << 31), "B and K must be below 2^31");
-    for (uint64_t i = 0; i < n_levels; ++i) {
-        RN_REQUIRE(ctx, h[i] >= 1 && w[i] >= 1, "h and w must be >= 1");
-        RN_REQUIRE(ctx, h[i] < (1ull << 31) && w[i] < (1ull << 31) && h[i] * w[i] < (1ull << 31) &&
-                            B * h[i] * w[i] < (1ull << 31),
-                   "B * h * w must be below 2^31");
-        RN_REQUIRE(ctx, scales[i] > 0.0f && isfinite(scales[i]), "every scale must be positive and finite");
-    }
-    if (K == 0 || B == 0) return RN_OK;
-    RN_REQUIRE(ctx, rois_dev, "rois_dev is NULL");
-    RN_REQUIRE(ctx, out, "out is NULL");
-    RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(rois_dev) & 3) == 0, "rois_dev is off a 4-byte boundary");
-    RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(out) & 3) == 0, "out is off a 4-byte boundary");
-    RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(levels_out) & 3) == 0, "levels_out is off a 4-byte boundary");
-    const uint64_t out_bytes = K * C * PH * PW * sizeof(float);
-    for (uint64_t i = 0; i < n_levels; ++i) {
-        RN_REQUIRE(ctx, x_nhwc[i], "a level's map is NULL");
-        RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(x_nhwc[i]) & 15) == 0, "a level's map is off a 16-byte boundary");
-        RN_REQUIRE(ctx, !rn_overlap(out, out_bytes, x_nhwc[i], B * h[i] * w[i] * C * es), "out overlaps a level's map");
-        RN_REQUIRE(ctx, !levels_out || !rn_overlap(levels_out, K * 4, x_nhwc[i], B * h[i] * w[i] * C * es),
-                   "levels_out overlaps a level's map");
-    }
-    RN_REQUIRE(ctx, !rn_overlap(out, out_bytes, rois_dev, K * 5 * sizeof(float)), "out overlaps rois_dev");
-    RN_REQUIRE(ctx, !levels_out || !rn_overlap(levels_out, K * 4, rois_dev, K * 5 * sizeof(float)),
-               "levels_out overlaps rois_dev");
-    RN_REQUIRE(ctx, !levels_out || !rn_overlap(levels_out, K * 4, out, out_bytes), "levels_out overlaps out");
-    return rn_roi_align_window(ctx, dtype, n_levels, x_nhwc, h, w, scales, thr, B, 0, B, 1, C, rois_dev, K, PH, PW,
-                               sampling_ratio, aligned, out, levels_out);
+    return roi_forward(ctx, __func__, false, dtype, n_levels, x_nhwc, h, w, scales, thr, B, C, rois_dev, K, PH, PW,
+                       sampling_ratio, aligned, out, levels_out);
+}
+
+int rn_roi_align_nhwc_forward_dt(rn_ctx *ctx, int dtype, uint64_t n_levels, const void *const *x_nhwc, const uint64_t *h,
+                                 const uint64_t *w, const float *scales, const float *thr, uint64_t B, uint64_t C,
+                                 const float *rois_dev, uint64_t K, uint64_t PH, uint64_t PW, int sampling_ratio, int aligned,
+                                 float *out_nhwc, int32_t *levels_out)
+{
+    return roi_forward(ctx, __func__, true, dtype, n_levels, x_nhwc, h, w, scales, thr, B, C, rois_dev, K, PH, PW,
+                       sampling_ratio, aligned, out_nhwc, levels_out);
 }
 
 }  // extern "C"

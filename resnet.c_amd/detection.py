@@ -148,12 +148,18 @@ def split_state(state) -> tuple:
 
 def split_detector_state(state) -> dict:
     """A whole fasterrcnn_resnet50_fpn state dict taken apart through the existing split_state's: "backbone" (the keys
-    NativeModel reads) and "neck" (fpn.split_state), "rpn" (rpn.split_state) and "box_head" (split_state above)"""
-    from . import fpn
+    NativeModel reads) and "neck" (fpn.split_state), "rpn" (rpn.split_state) and "box_head" (split_state above); a
+    maskrcnn_resnet50_fpn state also gives "mask_head" (mask.split_state) -- an entry that exists only when the state
+    holds such keys"""
+    from . import fpn, mask
     backbone, neck = fpn.split_state(state)
     head, _ = rpn.split_state(state)
     box, _ = split_state(state)
-    return {"backbone": backbone, "neck": neck, "rpn": head, "box_head": box}
+    out = {"backbone": backbone, "neck": neck, "rpn": head, "box_head": box}
+    mine, _ = mask.split_state(state)
+    if mine:
+        out["mask_head"] = mine
+    return out
 
 
 def generate_box_head_state(in_features: int, representation: int, classes: int, seed: int = 0, std=None) -> dict:

@@ -459,7 +459,8 @@ class NativeModel:
     def forward_fpn(self, x: np.ndarray, neck, stages=STAGES, levels=None, *, logits: bool = False,
                     features: bool = False, probs: bool = False, topk: int = 0, fused: bool = True, rois=None,
                     pooler=None, roi_levels: bool = False, validate: bool = True, rpn=None, candidates: bool = False,
-                    box_head=None, detect_intermediates: bool = False) -> dict:
+                    box_head=None, detect_intermediates: bool = False, mask_head=None, masks=("probs",),
+                    mask_pooled: bool = False) -> dict:
         """One forward with a feature pyramid neck (rn_model_forward_fpn; torchvision's resnet_fpn_backbone): an
         ordered dict "0", "1", .. (one per stage in `stages`, finest first), then "pool" when the neck has the extra
         block -> [B,a,H,W] fp32; then the head outputs asked for, as forward_outputs returns them.  neck: an
@@ -479,7 +480,10 @@ class NativeModel:
         With box_head (detection.BoxHead) behind that rpn and pooler (no rois): rn_model_forward_detections, which adds
         "boxes" [B,D,4], "scores" [B,D] (in place of the proposals' scores, which stay under "proposal_scores"), "labels",
         "detections" (the counts [B]) and "detection_rois" (the proposal row of every detection), padded as the device
-        wrote them; with detect_intermediates also "probs", "class_boxes", "valid" and "keep"."""
+        wrote them; with detect_intermediates also "probs", "class_boxes", "valid" and "keep".
+        With mask_head (mask.MaskHead) behind that box head: rn_model_forward_masks, which adds "mask_rois" [B*D,5] and,
+        as `masks` names them ("probs", "image", "bits"), "mask_probs" [B,D,2M,2M], "masks" [B,D,H,W] fp32 and
+        "mask_bits" [B,D,H,W] uint8 at the model's input size (and "mask_pooled" [B*D,M,M,a] with mask_pooled)."""
         from .fpn import NeckTail
         from .ops import _down_raw, _up_raw
         from .tensor import _DeviceBuffer
@@ -499,7 +503,7 @@ class NativeModel:
                 raise ValueError(f"unknown level {name!r}: one of {names}")
         x = np.asarray(x)
         tail = NeckTail(self.ctx, names, neck.out_channels, x.shape[0], self.input_size, rois, pooler, roi_levels, validate,
-                        rpn, candidates, box_head, detect_intermediates)
+                        rpn, candidates, box_head, detect_intermediates, mask_head, masks, mask_pooled)
         u8 = x.dtype == np.uint8
         x = np.ascontiguousarray(x, dtype=np.uint8 if u8 else np.float32)
         self._check_input(x, u8)
@@ -527,7 +531,8 @@ class NativeModel:
         tail.build()
         mode = L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS
         stage_arr = (ctypes.c_int * len(idx))(*idx)
-        objs = {"fpn": (), "rois": (), "proposals": (rpn,), "detections": (rpn, box_head)}[tail.entry]
+        objs = {"fpn": (), "rois": (), "proposals": (rpn,), "detections": (rpn, box_head),
+                "masks": (rpn, box_head, mask_head)}[tail.entry]
         name = "rn_model_forward_" + tail.entry
         fn = getattr(L.lib(), name + ("_u8" if u8 else ""))
         L.check(fn(self.handle, neck.handle, *[obj.handle for obj in objs], xin.ptr, B, ctypes.byref(o), stage_arr,

@@ -1051,7 +1051,8 @@ def roi_align_ref(maps_nhwc, rois, scales, output_size, sampling_ratio: int = 2,
     return (out, levels) if return_levels else out
 
 
-def _roi_align(dtype, np_dtype, maps_nhwc, rois, scales, output_size, sampling_ratio, aligned, thresholds, return_levels):
+def _roi_align(dtype, np_dtype, maps_nhwc, rois, scales, output_size, sampling_ratio, aligned, thresholds, return_levels,
+               nhwc: bool = False, validate: bool = True):
     from .tensor import _DeviceBuffer
     ctx = get_ctx()
     maps = [np.ascontiguousarray(m, dtype=np_dtype) for m in maps_nhwc]
@@ -1059,7 +1060,7 @@ def _roi_align(dtype, np_dtype, maps_nhwc, rois, scales, output_size, sampling_r
     assert all(m.ndim == 4 and m.shape[0] == B and m.shape[3] == C for m in maps), [m.shape for m in maps]
     rois = np.ascontiguousarray(rois, dtype=np.float32).reshape(-1, 5)
     K = rois.shape[0]
-    if not roi_image_valid(rois, B).all():
+    if validate and not roi_image_valid(rois, B).all():
         raise ValueError(f"a RoI's image index is no integer in [0, {B})")
     PH, PW = (int(output_size), int(output_size)) if np.ndim(output_size) == 0 else (int(output_size[0]), int(output_size[1]))
     sc = np.ascontiguousarray(scales, dtype=np.float32).reshape(-1)
@@ -1071,12 +1072,13 @@ def _roi_align(dtype, np_dtype, maps_nhwc, rois, scales, output_size, sampling_r
     out = _DeviceBuffer(ctx, max(K * C * PH * PW * 4, 16))
     lv = _DeviceBuffer(ctx, max(K * 4, 16)) if return_levels else None
     fp = ctypes.POINTER(ctypes.c_float)
-    L.check(L.lib().rn_roi_align_forward_dt(
+    name = "rn_roi_align_nhwc_forward_dt" if nhwc else "rn_roi_align_forward_dt"
+    L.check(getattr(L.lib(), name)(
         ctx.handle, dtype, n, (ctypes.c_void_p * n)(*[d.ptr for d in dm]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in maps]),
         (ctypes.c_uint64 * n)(*[m.shape[2] for m in maps]), sc.ctypes.data_as(fp), thr.ctypes.data_as(fp), B, C, dr.ptr, K,
-        PH, PW, int(sampling_ratio), int(bool(aligned)), out.ptr, lv.ptr if lv else None), "rn_roi_align_forward_dt", ctx.handle)
+        PH, PW, int(sampling_ratio), int(bool(aligned)), out.ptr, lv.ptr if lv else None), name, ctx.handle)
     ctx.sync()
-    pooled = _down_raw(out, np.float32, K * C * PH * PW).reshape(K, C, PH, PW)
+    pooled = _down_raw(out, np.float32, K * C * PH * PW).reshape((K, PH, PW, C) if nhwc else (K, C, PH, PW))
     return (pooled, _down_raw(lv, np.int32, K)) if return_levels else pooled
 
 
@@ -1096,6 +1098,15 @@ def roi_align_bf16(maps_nhwc, rois, scales, output_size, sampling_ratio: int = 2
     output is fp32."""
     return _roi_align(L.RN_DTYPE_BF16, np.uint16, maps_nhwc, rois, scales, output_size, sampling_ratio, aligned, thresholds,
                       return_levels)
+
+
+def roi_align_nhwc(maps_nhwc, rois, scales, output_size, sampling_ratio: int = 2, aligned: bool = False, thresholds=None,
+                   return_levels: bool = False, bf16: bool = False, validate: bool = True):
+    """rn_roi_align_nhwc_forward_dt, one launch: roi_align's arguments (bf16: roi_align_bf16's) -> [K,PH,PW,C] fp32, bit
+    for bit the transpose of what roi_align returns.  validate=False hands a RoI whose image index is no integer in
+    [0, B) -- the rows detection_rois forms of padding detections -- to the device, which answers zeros and level -1."""
+    return _roi_align(L.RN_DTYPE_BF16 if bf16 else L.RN_DTYPE_F32, np.uint16 if bf16 else np.float32, maps_nhwc, rois, scales,
+                      output_size, sampling_ratio, aligned, thresholds, return_levels, nhwc=True, validate=validate)
 
 
 # ---------------------------------------------------------------------------
@@ -1248,3 +1259,61 @@ def detect_postprocess(head, rois, B: int, C: int, image_size, score_thresh: flo
                                                   ctypes.byref(req)), "rn_detect_postprocess_forward", ctx.handle)
     ctx.sync()
     return {k: _down_raw(bufs[k], t, int(np.prod(sh))).reshape(sh) for k, (t, sh) in spec.items()}
+
+
+# ---------------------------------------------------------------------------
+# The mask head's launches (rn_mask.hip); the contracts in numpy are mask.py's
+# ---------------------------------------------------------------------------
+def detection_rois(boxes, labels) -> np.ndarray:
+    """rn_detection_rois_forward, one launch: boxes [B,D,4] fp32 and labels [B,D] int32 -> rois [B*D,5], bit for bit
+    mask.detection_rois_ref."""
+    from .tensor import _DeviceBuffer
+    ctx = get_ctx()
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    B, D = lab.shape
+    bx = np.ascontiguousarray(boxes, dtype=np.float32).reshape(B, D, 4)
+    db, dl, out = _up_raw(bx), _up_raw(lab), _DeviceBuffer(ctx, max(B * D * 20, 16))
+    L.check(L.lib().rn_detection_rois_forward(ctx.handle, db.ptr, dl.ptr, B, D, out.ptr), "rn_detection_rois_forward", ctx.handle)
+    ctx.sync()
+    return _down_raw(out, np.float32, B * D * 5).reshape(B * D, 5)
+
+
+def mask_predict(t, labels, weight, bias) -> np.ndarray:
+    """rn_mask_predict_forward, one launch: t [K,M,M,4*Cr] fp32 (channel (dy*2+dx)*Cr + c), labels [K] int32, weight
+    [C,Cr(,1,1)] and bias [C] -> probs [K,2M,2M] fp32: the sigmoid of the label's row of the 1x1, rows of a label outside
+    [1, C) zeros; within the bound of tests/test_mask_gpu.py of mask.predict_ref."""
+    from .tensor import _DeviceBuffer
+    ctx = get_ctx()
+    t = np.ascontiguousarray(t, dtype=np.float32)
+    K, M, _, c4 = t.shape
+    w = np.ascontiguousarray(weight, dtype=np.float32).reshape(np.shape(weight)[0], -1)
+    b = np.ascontiguousarray(bias, dtype=np.float32).reshape(-1)
+    lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+    assert t.shape[2] == M and c4 == 4 * w.shape[1] and b.size == w.shape[0] and lab.size == K, (t.shape, w.shape, b.shape, lab.shape)
+    dt, dl, dw, db = _up_raw(t), _up_raw(lab), _up_raw(w), _up_raw(b)
+    out = _DeviceBuffer(ctx, max(K * 4 * M * M * 4, 16))
+    L.check(L.lib().rn_mask_predict_forward(ctx.handle, dt.ptr, dl.ptr, dw.ptr, db.ptr, K, M, w.shape[1], w.shape[0], out.ptr),
+            "rn_mask_predict_forward", ctx.handle)
+    ctx.sync()
+    return _down_raw(out, np.float32, K * 4 * M * M).reshape(K, 2 * M, 2 * M)
+
+
+def paste_masks(probs, boxes, image_size, labels=None, threshold: float = 0.5, masks: bool = True, bits: bool = False):
+    """rn_paste_masks_forward, one launch: probs [K,Mo,Mo] fp32, boxes [K,4], labels [K] int32 or None -> (masks
+    [K,H,W] fp32 or None, bits [K,H,W] uint8 or None) at image_size = (H, W); masks bit for bit mask.paste_masks_ref,
+    bits == masks > threshold."""
+    from .tensor import _DeviceBuffer
+    ctx = get_ctx()
+    p = np.ascontiguousarray(probs, dtype=np.float32)
+    K, Mo = p.shape[0], p.shape[1]
+    H, W = int(image_size[0]), int(image_size[1])
+    bx = np.ascontiguousarray(boxes, dtype=np.float32).reshape(K, 4)
+    dp, db = _up_raw(p), _up_raw(bx)
+    dl = _up_raw(np.ascontiguousarray(labels, dtype=np.int32).reshape(K)) if labels is not None else None
+    dm = _DeviceBuffer(ctx, max(K * H * W * 4, 16)) if masks else None
+    dbits = _DeviceBuffer(ctx, max(K * H * W, 16)) if bits else None
+    L.check(L.lib().rn_paste_masks_forward(ctx.handle, dp.ptr, db.ptr, dl.ptr if dl else None, K, Mo, H, W, float(threshold),
+                                           dm.ptr if dm else None, dbits.ptr if dbits else None), "rn_paste_masks_forward", ctx.handle)
+    ctx.sync()
+    return (_down_raw(dm, np.float32, K * H * W).reshape(K, H, W) if masks else None,
+            _down_raw(dbits, np.uint8, K * H * W).reshape(K, H, W) if bits else None)
