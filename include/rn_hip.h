@@ -1332,7 +1332,7 @@ RN_API int rn_model_forward_detections_u8(rn_model *m, rn_fpn *fpn, rn_rpn *rpn,
  * predict launch, the paste launch where masks or bits is wanted.  Of the request it reads threshold, probs [K, 2M, 2M],
  * masks and bits [K, H, W] (any may be NULL, not all three); the pooler's parameters, rois and pooled are the route's.
  * The scratch -- two ping-pong maps, the [K, M, M, 4*Cr] tensor and the probabilities of a forward that does not export
- * them -- grows on demand under the box head's rules. */
+ * them -- grows on demand, never on a stream that is being captured and never while a captured graph of the context lives. */
 typedef struct rn_mask_request {
     int n_levels, level[4];            /* the mask pooler's levels of the neck, as rn_roi_pool's */
     int sampling_ratio, aligned;

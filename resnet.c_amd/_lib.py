@@ -440,6 +440,35 @@ def source_digest() -> str:
     return h.hexdigest()[:16]
 
 
+def set_tensors(handle, prefix: str, ctx, shapes, state) -> None:
+    """What every object behind the backbone does with its state dict: `prefix`_set_tensor for each key of the ordered
+    {key: shape} `shapes` (state[key] as contiguous fp32, of that many elements), then `prefix`_finalize."""
+    import numpy as np
+    for key, shape in shapes.items():
+        arr = np.ascontiguousarray(state[key], dtype=np.float32)
+        assert arr.size == int(np.prod(shape)), (key, arr.shape, shape)
+        check(getattr(lib(), prefix + "_set_tensor")(handle, key.encode(), arr.ctypes.data, arr.size),
+              f"{prefix}_set_tensor({key})", ctx.handle)
+    check(getattr(lib(), prefix + "_finalize")(handle), prefix + "_finalize", ctx.handle)
+
+
+class Handle:
+    """close() and __del__ of an object that owns the C handle self.handle; DESTROY names its destroy function."""
+    DESTROY = ""
+    handle = None
+
+    def close(self) -> None:
+        if self.handle:
+            getattr(lib(), self.DESTROY)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def check(status: int, where: str, ctx=None) -> None:
     if status != RN_OK:
         detail = ""

@@ -398,36 +398,27 @@ int rn_detect_postprocess_forward(rn_ctx *ctx, const float *head, const float *r
 }
 
 // ---- the object: TwoMLPHead and FastRCNNPredictor in front of the three launches --------------------------------
-// host copies of the state dict's eight tensors until rn_box_head_finalize packs them
 struct rn_box_head {
     rn_ctx *ctx;
     uint64_t F, M, C, P;  // in_features, representation, classes, the head output's pitch
     int finalized;
-    float *host[8];
-    void *packed[3];   // fc6 F -> M, fc7 M -> M, ONE panel M -> P: cls_score, bbox_pred, zero rows
-    float *bias[3];    // the epilogues' shifts (the last: P values, zeros behind 5C)
-    // scratch for cap_img images of cap_r RoIs: fc6's and fc7's outputs [., M], the head output [., P], the stage's
+    rn_params params;       // the state dict's eight tensors: fc6, fc7, cls_score, bbox_pred, weight then bias
+    rn_stage_unit unit[3];  // fc6 F -> M, fc7 M -> M, ONE panel M -> P: cls_score, bbox_pred, zero rows
+    // scratch for cap[0] images of cap[1] RoIs: fc6's and fc7's outputs [., M], the head output [., P], the stage's
     float *t6, *t7, *head;
     void *det;
-    uint64_t cap_img, cap_r;
+    uint64_t cap[2];
 };
+enum { kBoxImg, kBoxR, kBoxScratch = 4 };
 
-static const char *const kBoxHeadKeys[8] = {"box_head.fc6.weight",           "box_head.fc6.bias",
-                                            "box_head.fc7.weight",           "box_head.fc7.bias",
-                                            "box_predictor.cls_score.weight", "box_predictor.cls_score.bias",
-                                            "box_predictor.bbox_pred.weight", "box_predictor.bbox_pred.bias"};
-
-static uint64_t box_head_numel(const rn_box_head *h, int which)
+// the scratch tensors for `img` images of `R` RoIs; returns how many
+static int box_head_scratch(rn_box_head *h, uint64_t img, uint64_t R, rn_scratch_item *list)
 {
-    const uint64_t n[8] = {h->M * h->F, h->M, h->M * h->M, h->M, h->C * h->M, h->C, 4 * h->C * h->M, 4 * h->C};
-    return n[which];
-}
-
-static void box_head_free_scratch(rn_box_head *h)
-{
-    rn_free_null(h->ctx, (void **)&h->t6), rn_free_null(h->ctx, (void **)&h->t7), rn_free_null(h->ctx, (void **)&h->head);
-    rn_free_null(h->ctx, &h->det);
-    h->cap_img = h->cap_r = 0;
+    list[0] = {(void **)&h->t6, img * R * h->M * sizeof(float)};
+    list[1] = {(void **)&h->t7, img * R * h->M * sizeof(float)};
+    list[2] = {(void **)&h->head, img * R * h->P * sizeof(float)};
+    list[3] = {&h->det, det_scratch_bytes(img, R, h->C)};
+    return kBoxScratch;
 }
 
 int rn_box_head_create(rn_ctx *ctx, rn_box_head **out, uint64_t in_features, uint64_t representation, uint64_t classes)
@@ -443,6 +434,16 @@ int rn_box_head_create(rn_ctx *ctx, rn_box_head **out, uint64_t in_features, uin
     rn_box_head *h = (rn_box_head *)calloc(1, sizeof(*h));
     if (!h) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_box_head_create: out of host memory");
     h->ctx = ctx, h->F = in_features, h->M = representation, h->C = classes, h->P = head_pitch(classes);
+    static const char *const layer[4] = {"box_head.fc6", "box_head.fc7", "box_predictor.cls_score", "box_predictor.bbox_pred"};
+    const uint64_t rows[4] = {h->M, h->M, h->C, 4 * h->C};
+    for (int i = 0; i < 4; ++i) {
+        char key[RN_PARAM_KEY];
+        const uint64_t len = i == 0 ? h->F : h->M;
+        snprintf(key, sizeof(key), "%s.weight", layer[i]);
+        rn_params_add(&h->params, key, NULL, rows[i], len, rows[i], len, 0.0f);
+        snprintf(key, sizeof(key), "%s.bias", layer[i]);
+        rn_params_add(&h->params, key, NULL, 1, rows[i], 1, rows[i], 0.0f);
+    }
     *out = h;
     return RN_OK;
 }
@@ -450,37 +451,7 @@ int rn_box_head_create(rn_ctx *ctx, rn_box_head **out, uint64_t in_features, uin
 int rn_box_head_set_tensor(rn_box_head *h, const char *key, const float *host_data, uint64_t numel)
 {
     if (!h) return RN_ERR_INVALID;
-    rn_ctx *ctx = h->ctx;
-    RN_REQUIRE(ctx, key && host_data, "key or host_data is NULL");
-    RN_REQUIRE(ctx, !h->finalized, "the box head is finalized");
-    int which = -1;
-    for (int i = 0; i < 8; ++i)
-        if (strcmp(key, kBoxHeadKeys[i]) == 0) which = i;
-    if (which < 0) return rn_set_error(ctx, RN_ERR_INVALID, "rn_box_head_set_tensor: unknown key '%s'", key);
-    const uint64_t want = box_head_numel(h, which);
-    if (numel != want)
-        return rn_set_error(ctx, RN_ERR_INVALID, "rn_box_head_set_tensor: %s has %llu elements, not %llu", key,
-                            (unsigned long long)numel, (unsigned long long)want);
-    if (!h->host[which]) h->host[which] = (float *)malloc(want * sizeof(float));
-    if (!h->host[which]) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_box_head_set_tensor: out of host memory");
-    memcpy(h->host[which], host_data, want * sizeof(float));
-    return RN_OK;
-}
-
-// one Linear as a packed 1x1 panel and its shift; w [cout, cin] and b [cout] on the host
-static int box_head_pack(rn_box_head *h, int slot, const float *w, const float *b, uint64_t cin, uint64_t cout)
-{
-    rn_ctx *ctx = h->ctx;
-    float *raw = NULL;
-    int st = rn_malloc(ctx, (void **)&raw, cout * cin * sizeof(float));
-    if (st == RN_OK) st = rn_malloc(ctx, (void **)&h->bias[slot], cout * sizeof(float));
-    if (st == RN_OK) st = rn_malloc(ctx, &h->packed[slot], rn_conv2d_packed_weight_numel_dt(RN_DTYPE_F32, cin, cout, 1) * sizeof(float));
-    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, raw, w, cout * cin * sizeof(float));
-    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, h->bias[slot], b, cout * sizeof(float));
-    if (st == RN_OK) st = rn_conv2d_pack_weight_dt(ctx, RN_DTYPE_F32, raw, h->packed[slot], cin, cout, 1);
-    if (st == RN_OK) st = rn_sync(ctx);
-    rn_free_null(ctx, (void **)&raw);
-    return st;
+    return rn_stage_set_tensor(h->ctx, __func__, "the box head", h->finalized, &h->params, key, host_data, numel);
 }
 
 int rn_box_head_finalize(rn_box_head *h)
@@ -489,20 +460,17 @@ int rn_box_head_finalize(rn_box_head *h)
     rn_ctx *ctx = h->ctx;
     RN_ENTER(ctx);
     if (h->finalized) return RN_OK;
-    for (int i = 0; i < 8; ++i)
-        if (!h->host[i]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_box_head_finalize: %s is not set", kBoxHeadKeys[i]);
+    RN_TRY(rn_stage_all_set(ctx, __func__, &h->params));
     const uint64_t M = h->M, C = h->C, P = h->P;
-    // cls_score and bbox_pred side by side, zero rows up to P; the bias likewise (rn_rpn_finalize's rule: exact)
-    float *w = (float *)calloc(P * M + P, sizeof(float));
+    const rn_params_entry *p = h->params.p;
+    float *w = rn_stage_side_by_side(p[4].host, p[5].host, C, p[6].host, p[7].host, 4 * C, M, P);
     if (!w) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_box_head_finalize: out of host memory");
-    memcpy(w, h->host[4], C * M * sizeof(float)), memcpy(w + C * M, h->host[6], 4 * C * M * sizeof(float));
-    memcpy(w + P * M, h->host[5], C * sizeof(float)), memcpy(w + P * M + C, h->host[7], 4 * C * sizeof(float));
-    int st = box_head_pack(h, 0, h->host[0], h->host[1], h->F, M);
-    if (st == RN_OK) st = box_head_pack(h, 1, h->host[2], h->host[3], M, M);
-    if (st == RN_OK) st = box_head_pack(h, 2, w, w + P * M, M, P);
+    int st = rn_stage_pack(ctx, RN_DTYPE_F32, p[0].host, h->F, M, 1, p[1].host, NULL, &h->unit[0]);
+    if (st == RN_OK) st = rn_stage_pack(ctx, RN_DTYPE_F32, p[2].host, M, M, 1, p[3].host, NULL, &h->unit[1]);
+    if (st == RN_OK) st = rn_stage_pack(ctx, RN_DTYPE_F32, w, M, P, 1, w + P * M, NULL, &h->unit[2]);
     free(w);
     if (st != RN_OK) return st;
-    for (int i = 0; i < 8; ++i) free(h->host[i]), h->host[i] = NULL;
+    rn_params_free(&h->params);
     h->finalized = 1;
     return RN_OK;
 }
@@ -513,9 +481,10 @@ int rn_box_head_destroy(rn_box_head *h)
     rn_ctx *ctx = h->ctx;
     RN_ENTER(ctx);
     RN_TRY(rn_sync(ctx));
-    box_head_free_scratch(h);
-    for (int i = 0; i < 8; ++i) free(h->host[i]);
-    for (int i = 0; i < 3; ++i) rn_free_null(ctx, &h->packed[i]), rn_free_null(ctx, (void **)&h->bias[i]);
+    rn_scratch_item list[kBoxScratch];
+    rn_stage_free_list(ctx, list, box_head_scratch(h, 0, 0, list));
+    rn_params_free(&h->params);
+    for (int i = 0; i < 3; ++i) rn_stage_unit_free(ctx, &h->unit[i]);
     free(h);
     return RN_OK;
 }
@@ -535,22 +504,10 @@ int rn_box_head_matches(const rn_box_head *h, const rn_ctx *ctx, uint64_t in_fea
 
 int rn_box_head_reserve(rn_box_head *h, uint64_t images, uint64_t R)
 {
-    rn_ctx *ctx = h->ctx;
-    if (images <= h->cap_img && R <= h->cap_r) return RN_OK;
-    const bool had = h->cap_img > 0;
-    if (rn_ctx_is_capturing(ctx))
-        return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "rn_box_head: the scratch cannot grow on a stream that is being captured");
-    if (had && ctx->graphs_live > 0)
-        return rn_set_error(ctx, RN_ERR_INVALID, "rn_box_head: the scratch cannot grow while a captured graph lives");
-    RN_TRY(rn_sync(ctx));
-    const uint64_t img = images > h->cap_img ? images : h->cap_img, rr = R > h->cap_r ? R : h->cap_r;
-    box_head_free_scratch(h);
-    RN_TRY(rn_malloc(ctx, (void **)&h->t6, img * rr * h->M * sizeof(float)));
-    RN_TRY(rn_malloc(ctx, (void **)&h->t7, img * rr * h->M * sizeof(float)));
-    RN_TRY(rn_malloc(ctx, (void **)&h->head, img * rr * h->P * sizeof(float)));
-    RN_TRY(rn_malloc(ctx, &h->det, det_scratch_bytes(img, rr, h->C)));
-    h->cap_img = img, h->cap_r = rr;
-    return RN_OK;
+    if (images <= h->cap[kBoxImg] && R <= h->cap[kBoxR]) return RN_OK;
+    const uint64_t want[2] = {images > h->cap[kBoxImg] ? images : h->cap[kBoxImg], R > h->cap[kBoxR] ? R : h->cap[kBoxR]};
+    rn_scratch_item list[kBoxScratch];
+    return rn_stage_grow(h->ctx, "rn_box_head", list, box_head_scratch(h, want[kBoxImg], want[kBoxR], list), h->cap, want, 2);
 }
 
 // every refusal that concerns the request alone, for a forward of `images` images of R RoIs (text in ctx)
@@ -578,19 +535,19 @@ int rn_box_head_operands(const rn_box_head *h, const rn_detect_request *q, uint6
 int rn_box_head_step(rn_box_head *h, rn_ctx *ctx, const float *pooled, const float *rois, uint64_t sub0, uint64_t img0,
                      uint64_t B, uint64_t R, uint64_t image_h, uint64_t image_w, const rn_detect_request *q)
 {
-    if (sub0 + B > h->cap_img || R > h->cap_r) return rn_set_error(ctx, RN_ERR_INVALID, "rn_box_head: scratch not reserved");
+    if (sub0 + B > h->cap[kBoxImg] || R > h->cap[kBoxR]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_box_head: scratch not reserved");
     const uint64_t K = B * R, row0 = sub0 * R;
     float *t6 = h->t6 + row0 * h->M, *t7 = h->t7 + row0 * h->M, *head = h->head + row0 * h->P;
     rn_epilogue ep;
     ep.scale = NULL, ep.residual = NULL;
-    ep.shift = h->bias[0], ep.relu = 1;
-    RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, pooled, t6, h->packed[0], 1, 1, 0, 1, 1, K, h->F, h->M, 1, 1, &ep));
-    ep.shift = h->bias[1];
-    RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, t6, t7, h->packed[1], 1, 1, 0, 1, 1, K, h->M, h->M, 1, 1, &ep));
-    ep.shift = h->bias[2], ep.relu = 0;
-    RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, t7, head, h->packed[2], 1, 1, 0, 1, 1, K, h->M, h->P, 1, 1, &ep));
+    ep.shift = h->unit[0].shift, ep.relu = 1;
+    RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, pooled, t6, h->unit[0].packed, 1, 1, 0, 1, 1, K, h->F, h->M, 1, 1, &ep));
+    ep.shift = h->unit[1].shift;
+    RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, t6, t7, h->unit[1].packed, 1, 1, 0, 1, 1, K, h->M, h->M, 1, 1, &ep));
+    ep.shift = h->unit[2].shift, ep.relu = 0;
+    RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, t7, head, h->unit[2].packed, 1, 1, 0, 1, 1, K, h->M, h->P, 1, 1, &ep));
     const rn_detections out = det_rows(&q->out, img0, R, h->C, q->detections_per_img);
-    return det_launch(ctx, head, rois, B, R, h->C, img0, image_h, image_w, q, &out, det_carve(h->det, h->cap_img, sub0, h->cap_r, h->C),
+    return det_launch(ctx, head, rois, B, R, h->C, img0, image_h, image_w, q, &out, det_carve(h->det, h->cap[kBoxImg], sub0, h->cap[kBoxR], h->C),
                       "rn_box_head");
 }
 

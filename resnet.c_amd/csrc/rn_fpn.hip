@@ -92,7 +92,7 @@ __global__ __launch_bounds__(kNaBlock) void upsample_nearest_add_kernel(const ne
     }
 }
 
-constexpr int kFpnMaxLevels = 4;
+constexpr int kFpnMaxLevels = 4, kFpnPool = kFpnMaxLevels, kFpnScratch = 2 * kFpnMaxLevels + 1;
 
 }  // namespace
 
@@ -101,52 +101,28 @@ struct rn_fpn {
     rn_ctx *ctx;
     int n, extra, dtype, finalized;
     uint64_t cin[kFpnMaxLevels], a;
-    // per level: 0 the lateral's weight [a,in,1,1], 1 its bias [a], 2 the 3x3's weight [a,a,3,3], 3 its bias [a]; fp32
-    // on the device.  The biases stay (the epilogues' shifts), the weights go once they are packed.
-    float *raw[kFpnMaxLevels][4];
-    int is_set[kFpnMaxLevels][4];
-    void *packed_inner[kFpnMaxLevels], *packed_layer[kFpnMaxLevels];
+    // entries 4 l .. 4 l + 3, level l: the lateral's weight [a,in,1,1] and bias [a], the 3x3's weight [a,a,3,3] and bias [a]
+    rn_params params;
+    rn_stage_unit lateral[kFpnMaxLevels], layer[kFpnMaxLevels];  // the biases are the epilogues' shifts
     // scratch, per level: the lateral / merged tensor [cap, h, w, a] of the storage type and the 3x3's output
     // [cap, h, w, a] fp32; the pooled coarsest output [cap, hp, wp, a] fp32
     void *inner[kFpnMaxLevels];
     float *outb[kFpnMaxLevels], *poolb;
-    uint64_t cap_pix[kFpnMaxLevels], cap_pool;
+    uint64_t cap_pix[kFpnMaxLevels + 1];  // pixels a level's tensors hold; the last: the pooled output's (kFpnPool)
 };
 
 namespace {
 
-uint64_t fpn_key_numel(const rn_fpn *f, int level, int which)
+// the scratch tensors for pix[l] pixels of level l and pix[kFpnPool] of the pooled output; returns how many
+int fpn_scratch(rn_fpn *f, const uint64_t *pix, rn_scratch_item *list)
 {
-    return which == 0 ? f->a * f->cin[level] : which == 2 ? f->a * f->a * 9 : f->a;
-}
-
-void fpn_free_scratch(rn_fpn *f)
-{
+    int n = 0;
     for (int i = 0; i < f->n; ++i) {
-        rn_free_null(f->ctx, &f->inner[i]), rn_free_null(f->ctx, (void **)&f->outb[i]);
-        f->cap_pix[i] = 0;
+        list[n++] = {&f->inner[i], pix[i] * f->a * rn_elem_size(f->dtype)};
+        list[n++] = {(void **)&f->outb[i], pix[i] * f->a * sizeof(float)};
     }
-    rn_free_null(f->ctx, (void **)&f->poolb);
-    f->cap_pool = 0;
-}
-
-// "inner_blocks.2.0.weight", "inner_blocks.2.weight" (the older spelling), "layer_blocks.0.0.bias" ... -> level and
-// tensor (0..3); false: not a key of this neck
-bool fpn_parse_key(const rn_fpn *f, const char *key, int *level, int *which)
-{
-    int base;
-    if (strncmp(key, "inner_blocks.", 13) == 0) base = 0;
-    else if (strncmp(key, "layer_blocks.", 13) == 0) base = 2;
-    else return false;
-    const char *s = key + 13;
-    if (*s < '0' || *s >= '0' + f->n || s[1] != '.') return false;
-    *level = *s - '0';
-    s += 2;
-    if (strncmp(s, "0.", 2) == 0) s += 2;
-    if (strcmp(s, "weight") == 0) *which = base;
-    else if (strcmp(s, "bias") == 0) *which = base + 1;
-    else return false;
-    return true;
+    list[n++] = {(void **)&f->poolb, pix[kFpnPool] * f->a * sizeof(float)};
+    return n;
 }
 
 }  // namespace
@@ -215,7 +191,17 @@ int rn_fpn_create(rn_ctx *ctx, rn_fpn **out, uint64_t n_levels, const uint64_t *
     rn_fpn *f = (rn_fpn *)calloc(1, sizeof(*f));
     if (!f) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_fpn_create: out of host memory");
     f->ctx = ctx, f->n = (int)n_levels, f->extra = extra, f->a = out_channels, f->dtype = RN_DTYPE_F32;
-    for (uint64_t i = 0; i < n_levels; ++i) f->cin[i] = in_channels[i];
+    for (uint64_t i = 0; i < n_levels; ++i) {  // "inner_blocks.2.0.weight", or "inner_blocks.2.weight": the older spelling
+        static const char *const block[2] = {"inner_blocks", "layer_blocks"}, *const part[2] = {"weight", "bias"};
+        f->cin[i] = in_channels[i];
+        for (int t = 0; t < 4; ++t) {
+            char key[RN_PARAM_KEY], alt[RN_PARAM_KEY];
+            snprintf(key, sizeof(key), "%s.%d.0.%s", block[t / 2], (int)i, part[t % 2]);
+            snprintf(alt, sizeof(alt), "%s.%d.%s", block[t / 2], (int)i, part[t % 2]);
+            const uint64_t rows = t % 2 ? 1 : f->a, len = t == 0 ? f->cin[i] : t == 2 ? f->a * 9 : f->a;
+            rn_params_add(&f->params, key, alt, rows, len, rows, len, 0.0f);
+        }
+    }
     *out = f;
     return RN_OK;
 }
@@ -232,48 +218,22 @@ int rn_fpn_set_dtype(rn_fpn *f, int dtype)
 int rn_fpn_set_tensor(rn_fpn *f, const char *key, const float *host_data, uint64_t numel)
 {
     if (!f) return RN_ERR_INVALID;
-    rn_ctx *ctx = f->ctx;
-    RN_ENTER(ctx);
-    RN_REQUIRE(ctx, key && host_data, "key or host_data is NULL");
-    RN_REQUIRE(ctx, !f->finalized, "the neck is finalized");
-    int level = 0, which = 0;
-    if (!fpn_parse_key(f, key, &level, &which))
-        return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn_set_tensor: unknown key '%s'", key);
-    const uint64_t want = fpn_key_numel(f, level, which);
-    if (numel != want)
-        return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn_set_tensor: %s has %llu elements, not %llu", key,
-                            (unsigned long long)want, (unsigned long long)numel);
-    float **raw = &f->raw[level][which];
-    if (!*raw) RN_TRY(rn_malloc(ctx, (void **)raw, want * sizeof(float)));
-    RN_TRY(rn_ctx_upload_sync(ctx, *raw, host_data, want * sizeof(float)));
-    f->is_set[level][which] = 1;
-    return RN_OK;
+    return rn_stage_set_tensor(f->ctx, __func__, "the neck", f->finalized, &f->params, key, host_data, numel);
 }
 
 int rn_fpn_finalize(rn_fpn *f)
 {
-    static const char *const names[4] = {"inner_blocks.%d.0.weight", "inner_blocks.%d.0.bias", "layer_blocks.%d.0.weight",
-                                         "layer_blocks.%d.0.bias"};
     if (!f) return RN_ERR_INVALID;
     rn_ctx *ctx = f->ctx;
     RN_ENTER(ctx);
     if (f->finalized) return RN_OK;
-    for (int i = 0; i < f->n; ++i)
-        for (int t = 0; t < 4; ++t)
-            if (!f->is_set[i][t]) {
-                char key[48];
-                snprintf(key, sizeof(key), names[t], i);
-                return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn_finalize: %s is not set", key);
-            }
-    const uint64_t es = rn_elem_size(f->dtype);
+    RN_TRY(rn_stage_all_set(ctx, __func__, &f->params));
     for (int i = 0; i < f->n; ++i) {
-        RN_TRY(rn_malloc(ctx, &f->packed_inner[i], rn_conv2d_packed_weight_numel_dt(f->dtype, f->cin[i], f->a, 1) * es));
-        RN_TRY(rn_malloc(ctx, &f->packed_layer[i], rn_conv2d_packed_weight_numel_dt(f->dtype, f->a, f->a, 3) * es));
-        RN_TRY(rn_conv2d_pack_weight_dt(ctx, f->dtype, f->raw[i][0], f->packed_inner[i], f->cin[i], f->a, 1));
-        RN_TRY(rn_conv2d_pack_weight_dt(ctx, f->dtype, f->raw[i][2], f->packed_layer[i], f->a, f->a, 3));
+        const rn_params_entry *p = &f->params.p[4 * i];
+        RN_TRY(rn_stage_pack(ctx, f->dtype, p[0].host, f->cin[i], f->a, 1, p[1].host, NULL, &f->lateral[i]));
+        RN_TRY(rn_stage_pack(ctx, f->dtype, p[2].host, f->a, f->a, 3, p[3].host, NULL, &f->layer[i]));
     }
-    RN_TRY(rn_sync(ctx));
-    for (int i = 0; i < f->n; ++i) rn_free_null(ctx, (void **)&f->raw[i][0]), rn_free_null(ctx, (void **)&f->raw[i][2]);
+    rn_params_free(&f->params);
     f->finalized = 1;
     return RN_OK;
 }
@@ -284,11 +244,10 @@ int rn_fpn_destroy(rn_fpn *f)
     rn_ctx *ctx = f->ctx;
     RN_ENTER(ctx);
     RN_TRY(rn_sync(ctx));
-    fpn_free_scratch(f);
-    for (int i = 0; i < f->n; ++i) {
-        for (int t = 0; t < 4; ++t) rn_free_null(ctx, (void **)&f->raw[i][t]);
-        rn_free_null(ctx, &f->packed_inner[i]), rn_free_null(ctx, &f->packed_layer[i]);
-    }
+    rn_scratch_item list[kFpnScratch];
+    rn_stage_free_list(ctx, list, fpn_scratch(f, f->cap_pix, list));
+    rn_params_free(&f->params);
+    for (int i = 0; i < f->n; ++i) rn_stage_unit_free(ctx, &f->lateral[i]), rn_stage_unit_free(ctx, &f->layer[i]);
     free(f);
     return RN_OK;
 }
@@ -328,29 +287,18 @@ void rn_fpn_dims(const rn_fpn *f, int *n_levels, int *extra, uint64_t *out_chann
 
 int rn_fpn_reserve(rn_fpn *f, uint64_t images, const uint64_t *h, const uint64_t *w)
 {
-    rn_ctx *ctx = f->ctx;
     const int last = f->n - 1;
-    const uint64_t pool_pix = f->extra ? images * ((h[last] - 1) / 2 + 1) * ((w[last] - 1) / 2 + 1) : 0;
-    bool fits = pool_pix <= f->cap_pool;
-    for (int i = 0; i < f->n; ++i) fits = fits && images * h[i] * w[i] <= f->cap_pix[i];
-    if (fits) return RN_OK;
-    const bool had = f->cap_pix[0] > 0;
-    if (rn_ctx_is_capturing(ctx))
-        return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "rn_fpn: the scratch cannot grow on a stream that is being captured");
-    if (had && ctx->graphs_live > 0)
-        return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn: the scratch cannot grow while a captured graph lives");
-    RN_TRY(rn_sync(ctx));
-    uint64_t pix[kFpnMaxLevels], pool = pool_pix > f->cap_pool ? pool_pix : f->cap_pool;
-    for (int i = 0; i < f->n; ++i) pix[i] = images * h[i] * w[i] > f->cap_pix[i] ? images * h[i] * w[i] : f->cap_pix[i];
-    fpn_free_scratch(f);
-    for (int i = 0; i < f->n; ++i) {
-        RN_TRY(rn_malloc(ctx, &f->inner[i], pix[i] * f->a * rn_elem_size(f->dtype)));
-        RN_TRY(rn_malloc(ctx, (void **)&f->outb[i], pix[i] * f->a * sizeof(float)));
-        f->cap_pix[i] = pix[i];
+    uint64_t want[kFpnMaxLevels + 1] = {};
+    want[kFpnPool] = f->extra ? images * ((h[last] - 1) / 2 + 1) * ((w[last] - 1) / 2 + 1) : 0;
+    for (int i = 0; i < f->n; ++i) want[i] = images * h[i] * w[i];
+    bool fits = true;
+    for (int i = 0; i <= kFpnPool; ++i) {
+        fits = fits && want[i] <= f->cap_pix[i];
+        if (want[i] < f->cap_pix[i]) want[i] = f->cap_pix[i];
     }
-    if (pool) RN_TRY(rn_malloc(ctx, (void **)&f->poolb, pool * f->a * sizeof(float)));
-    f->cap_pool = pool;
-    return RN_OK;
+    if (fits) return RN_OK;
+    rn_scratch_item list[kFpnScratch];
+    return rn_stage_grow(f->ctx, "rn_fpn", list, fpn_scratch(f, want, list), f->cap_pix, want, kFpnMaxLevels + 1);
 }
 
 void rn_fpn_cost(const rn_fpn *f, int kind, int level, uint64_t B, const uint64_t *h, const uint64_t *w, double *flops,
@@ -382,7 +330,7 @@ int rn_fpn_step(rn_fpn *f, rn_ctx *ctx, int kind, int level, const void *x_nhwc,
     const uint64_t hp = (h[last] - 1) / 2 + 1, wp = (w[last] - 1) / 2 + 1;
     for (int i = 0; i < f->n; ++i)
         if ((img0 + B) * h[i] * w[i] > f->cap_pix[i]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn: scratch not reserved");
-    if (f->extra && (img0 + B) * hp * wp > f->cap_pool) return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn: scratch not reserved");
+    if (f->extra && (img0 + B) * hp * wp > f->cap_pix[kFpnPool]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn: scratch not reserved");
     const int l = level < f->n ? level : last;
     void *inner = (char *)f->inner[l] + img0 * h[l] * w[l] * a * es;
     float *outb = f->outb[l] + img0 * h[l] * w[l] * a;
@@ -391,16 +339,16 @@ int rn_fpn_step(rn_fpn *f, rn_ctx *ctx, int kind, int level, const void *x_nhwc,
     ep.scale = NULL, ep.residual = NULL, ep.relu = 0;
     switch (kind) {
     case RN_FPN_INNER:
-        ep.shift = f->raw[l][1];
-        return rn_conv2d_nhwc_forward_dt(ctx, dt, dt, x_nhwc, inner, f->packed_inner[l], 1, 1, 0, h[l], w[l], B, f->cin[l], a,
+        ep.shift = f->lateral[l].shift;
+        return rn_conv2d_nhwc_forward_dt(ctx, dt, dt, x_nhwc, inner, f->lateral[l].packed, 1, 1, 0, h[l], w[l], B, f->cin[l], a,
                                          h[l], w[l], &ep);
     case RN_FPN_TOPDOWN: {  // level (the coarser) -> level - 1, in place on the finer lateral
         void *fine = (char *)f->inner[l - 1] + img0 * h[l - 1] * w[l - 1] * a * es;
         return rn_upsample_nearest_add_forward_dt(ctx, dt, inner, B, h[l], w[l], a, fine, fine, h[l - 1], w[l - 1]);
     }
     case RN_FPN_LAYER:
-        ep.shift = f->raw[l][3];
-        return rn_conv2d_nhwc_forward_dt(ctx, dt, RN_DTYPE_F32, inner, outb, f->packed_layer[l], 3, 1, 1, h[l], w[l], B, a, a,
+        ep.shift = f->layer[l].shift;
+        return rn_conv2d_nhwc_forward_dt(ctx, dt, RN_DTYPE_F32, inner, outb, f->layer[l].packed, 3, 1, 1, h[l], w[l], B, a, a,
                                          h[l], w[l], &ep);
     case RN_FPN_POOL:
         return rn_maxpool2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, outb, poolb, 1, 2, 0, hp, wp, B, a, h[l], w[l]);
@@ -533,7 +481,7 @@ int neck_rpn_step(const rn_neck_call *c, rn_ctx *ctx, uint64_t sub0, uint64_t im
     const rn_fpn *f = c->fpn;
     const float *lv[kFpnMaxLevels + 1];
     for (int i = 0; i < c->n + c->extra; ++i) {
-        if ((sub0 + B) * c->hl[i] * c->wl[i] > (i < c->n ? f->cap_pix[i] : f->cap_pool))
+        if ((sub0 + B) * c->hl[i] * c->wl[i] > (i < c->n ? f->cap_pix[i] : f->cap_pix[kFpnPool]))
             return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn: scratch not reserved");
         lv[i] = (i < c->n ? f->outb[i] : f->poolb) + sub0 * c->hl[i] * c->wl[i] * f->a;
     }

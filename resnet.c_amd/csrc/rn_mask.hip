@@ -410,61 +410,34 @@ int rn_paste_masks_forward(rn_ctx *ctx, const float *probs, const float *boxes, 
 }
 
 // ---- the object: MaskRCNNHeads and MaskRCNNPredictor in front of the predict and paste launches ------------------
-enum { kMaskMaxLayers = 8, kMaskTensors = 2 * kMaskMaxLayers + 4 };
+enum { kMaskMaxLayers = 8, kMaskRows = 0, kMaskPool = 1, kMaskScratch = 6 };
 
 struct rn_mask_head {
     rn_ctx *ctx;
     uint64_t Cin, n_layers, ch[kMaskMaxLayers], Cr, C, M;
     int finalized;
-    float *host[kMaskTensors];          // layer i: 2i, 2i + 1; conv5_mask: 2n, 2n + 1; mask_fcn_logits: 2n + 2, 2n + 3
-    void *packed[kMaskMaxLayers + 1];   // the 3x3 panels, then the transposed convolution as ONE 1x1 panel Clast -> 4 Cr
-    float *bias[kMaskMaxLayers + 1];    // the epilogues' shifts (the last: conv5_mask's bias four times)
+    rn_params params;                   // layer i: 2i, 2i + 1; conv5_mask: 2n, 2n + 1; mask_fcn_logits: 2n + 2, 2n + 3
+    rn_stage_unit unit[kMaskMaxLayers + 1];  // the 3x3 layers, then the transposed convolution as ONE 1x1 panel Clast -> 4 Cr
+                                        // (its shift: conv5_mask's bias four times)
     float *lw, *lb;                     // mask_fcn_logits on the device, torchvision's layout
     // scratch for cap rows: two ping-pong maps [., M, M, widest], the deconvolution's output [., M, M, 4 Cr] and the
     // probabilities [., 2M, 2M] of a forward that does not export them
     float *ping, *pong, *t, *probs;
     float *rois, *pooled;               // behind a neck: the RoI rows [., 5] and the pooled features [., M, M, Cin] of cap_pool rows
-    uint64_t cap, cap_pool, widest;
+    uint64_t cap[2], widest;            // cap: rows (kMaskRows), of them with RoI rows and pooled features (kMaskPool)
 };
 
-static uint64_t mask_head_numel(const rn_mask_head *h, uint64_t which)
+// the scratch tensors for `rows` detections, `pool` of them behind a neck; returns how many
+static int mask_head_scratch(rn_mask_head *h, uint64_t rows, uint64_t pool, rn_scratch_item *list)
 {
-    const uint64_t n = h->n_layers;
-    if (which < 2 * n) {
-        const uint64_t i = which / 2, cin = i == 0 ? h->Cin : h->ch[i - 1];
-        return which % 2 == 0 ? h->ch[i] * cin * 9 : h->ch[i];
-    }
-    const uint64_t last = h->ch[n - 1];
-    const uint64_t tail[4] = {last * h->Cr * 4, h->Cr, h->C * h->Cr, h->C};
-    return tail[which - 2 * n];
-}
-
-// the slot of a state-dict key (either spelling, with or without "roi_heads."), or -1
-static int mask_head_slot(const rn_mask_head *h, const char *key)
-{
-    if (strncmp(key, "roi_heads.", 10) == 0) key += 10;
-    const int n = (int)h->n_layers;
-    static const char *const tail[4] = {"mask_predictor.conv5_mask.weight", "mask_predictor.conv5_mask.bias",
-                                        "mask_predictor.mask_fcn_logits.weight", "mask_predictor.mask_fcn_logits.bias"};
-    for (int i = 0; i < 4; ++i)
-        if (strcmp(key, tail[i]) == 0) return 2 * n + i;
-    char name[64];
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < 2; ++j) {
-            snprintf(name, sizeof(name), "mask_head.%d.0.%s", i, j ? "bias" : "weight");
-            if (strcmp(key, name) == 0) return 2 * i + j;
-            snprintf(name, sizeof(name), "mask_head.mask_fcn%d.%s", i + 1, j ? "bias" : "weight");
-            if (strcmp(key, name) == 0) return 2 * i + j;
-        }
-    return -1;
-}
-
-static void mask_head_free_scratch(rn_mask_head *h)
-{
-    rn_free_null(h->ctx, (void **)&h->ping), rn_free_null(h->ctx, (void **)&h->pong);
-    rn_free_null(h->ctx, (void **)&h->t), rn_free_null(h->ctx, (void **)&h->probs);
-    rn_free_null(h->ctx, (void **)&h->rois), rn_free_null(h->ctx, (void **)&h->pooled);
-    h->cap = h->cap_pool = 0;
+    const uint64_t px = rows * h->M * h->M;
+    list[0] = {(void **)&h->ping, px * h->widest * sizeof(float)};
+    list[1] = {(void **)&h->pong, px * h->widest * sizeof(float)};
+    list[2] = {(void **)&h->t, px * 4 * h->Cr * sizeof(float)};
+    list[3] = {(void **)&h->probs, px * 4 * sizeof(float)};
+    list[4] = {(void **)&h->rois, pool * 5 * sizeof(float)};
+    list[5] = {(void **)&h->pooled, pool * h->M * h->M * h->Cin * sizeof(float)};
+    return kMaskScratch;
 }
 
 int rn_mask_head_create(rn_ctx *ctx, rn_mask_head **out, uint64_t in_channels, uint64_t n_layers, const uint64_t *layer_channels,
@@ -491,6 +464,21 @@ int rn_mask_head_create(rn_ctx *ctx, rn_mask_head **out, uint64_t in_channels, u
         h->ch[i] = layer_channels[i];
         if (h->ch[i] > h->widest) h->widest = h->ch[i];
     }
+    // either spelling of a layer ("mask_head.0.0.weight", "mask_head.mask_fcn1.weight"), with or without "roi_heads."
+    h->params.prefix = "roi_heads.";
+    for (uint64_t i = 0; i < n_layers; ++i)
+        for (int j = 0; j < 2; ++j) {
+            char key[RN_PARAM_KEY], alt[RN_PARAM_KEY];
+            snprintf(key, sizeof(key), "mask_head.%d.0.%s", (int)i, j ? "bias" : "weight");
+            snprintf(alt, sizeof(alt), "mask_head.mask_fcn%d.%s", (int)i + 1, j ? "bias" : "weight");
+            const uint64_t rows = j ? 1 : h->ch[i], len = j ? h->ch[i] : (i == 0 ? h->Cin : h->ch[i - 1]) * 9;
+            rn_params_add(&h->params, key, alt, rows, len, rows, len, 0.0f);
+        }
+    const uint64_t last = h->ch[n_layers - 1], Cr = dim_reduced;
+    rn_params_add(&h->params, "mask_predictor.conv5_mask.weight", NULL, last, Cr * 4, last, Cr * 4, 0.0f);
+    rn_params_add(&h->params, "mask_predictor.conv5_mask.bias", NULL, 1, Cr, 1, Cr, 0.0f);
+    rn_params_add(&h->params, "mask_predictor.mask_fcn_logits.weight", NULL, classes, Cr, classes, Cr, 0.0f);
+    rn_params_add(&h->params, "mask_predictor.mask_fcn_logits.bias", NULL, 1, classes, 1, classes, 0.0f);
     *out = h;
     return RN_OK;
 }
@@ -498,36 +486,7 @@ int rn_mask_head_create(rn_ctx *ctx, rn_mask_head **out, uint64_t in_channels, u
 int rn_mask_head_set_tensor(rn_mask_head *h, const char *key, const float *host_data, uint64_t numel)
 {
     if (!h) return RN_ERR_INVALID;
-    rn_ctx *ctx = h->ctx;
-    RN_REQUIRE(ctx, key && host_data, "key or host_data is NULL");
-    RN_REQUIRE(ctx, !h->finalized, "the mask head is finalized");
-    const int which = mask_head_slot(h, key);
-    if (which < 0) return rn_set_error(ctx, RN_ERR_INVALID, "rn_mask_head_set_tensor: unknown key '%s'", key);
-    const uint64_t want = mask_head_numel(h, (uint64_t)which);
-    if (numel != want)
-        return rn_set_error(ctx, RN_ERR_INVALID, "rn_mask_head_set_tensor: %s has %llu elements, not %llu", key,
-                            (unsigned long long)numel, (unsigned long long)want);
-    if (!h->host[which]) h->host[which] = (float *)malloc(want * sizeof(float));
-    if (!h->host[which]) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_mask_head_set_tensor: out of host memory");
-    memcpy(h->host[which], host_data, want * sizeof(float));
-    return RN_OK;
-}
-
-// one convolution as a packed panel and its shift; w OIHW [cout, cin, k, k] and b [cout] on the host
-static int mask_head_pack(rn_mask_head *h, uint64_t slot, const float *w, const float *b, uint64_t cin, uint64_t cout, uint64_t k)
-{
-    rn_ctx *ctx = h->ctx;
-    float *raw = NULL;
-    const uint64_t n = cout * cin * k * k;
-    int st = rn_malloc(ctx, (void **)&raw, n * sizeof(float));
-    if (st == RN_OK) st = rn_malloc(ctx, (void **)&h->bias[slot], cout * sizeof(float));
-    if (st == RN_OK) st = rn_malloc(ctx, &h->packed[slot], rn_conv2d_packed_weight_numel_dt(RN_DTYPE_F32, cin, cout, k) * sizeof(float));
-    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, raw, w, n * sizeof(float));
-    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, h->bias[slot], b, cout * sizeof(float));
-    if (st == RN_OK) st = rn_conv2d_pack_weight_dt(ctx, RN_DTYPE_F32, raw, h->packed[slot], cin, cout, k);
-    if (st == RN_OK) st = rn_sync(ctx);
-    rn_free_null(ctx, (void **)&raw);
-    return st;
+    return rn_stage_set_tensor(h->ctx, __func__, "the mask head", h->finalized, &h->params, key, host_data, numel);
 }
 
 int rn_mask_head_finalize(rn_mask_head *h)
@@ -536,31 +495,30 @@ int rn_mask_head_finalize(rn_mask_head *h)
     rn_ctx *ctx = h->ctx;
     RN_ENTER(ctx);
     if (h->finalized) return RN_OK;
+    RN_TRY(rn_stage_all_set(ctx, __func__, &h->params));
     const uint64_t n = h->n_layers, Cr = h->Cr, last = h->ch[n - 1];
-    for (uint64_t i = 0; i < 2 * n + 4; ++i)
-        if (!h->host[i]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_mask_head_finalize: tensor %llu of the mask head is not set (layers first, weight then bias; conv5_mask; mask_fcn_logits)", (unsigned long long)i);
-    int st = RN_OK;
-    for (uint64_t i = 0; i < n && st == RN_OK; ++i)
-        st = mask_head_pack(h, i, h->host[2 * i], h->host[2 * i + 1], i == 0 ? h->Cin : h->ch[i - 1], h->ch[i], 3);
-    if (st != RN_OK) return st;
+    const rn_params_entry *p = h->params.p;
+    for (uint64_t i = 0; i < n; ++i)
+        RN_TRY(rn_stage_pack(ctx, RN_DTYPE_F32, p[2 * i].host, i == 0 ? h->Cin : h->ch[i - 1], h->ch[i], 3, p[2 * i + 1].host, NULL,
+                             &h->unit[i]));
     // ConvTranspose2d(last, Cr, 2, 2), weight [last, Cr, 2, 2]: output (2y + dy, 2x + dx) reads input (y, x) alone, so
     // it is the 1x1 convolution whose row (dy * 2 + dx) * Cr + co is W[:, co, dy, dx]; the bias four times
     float *w = (float *)malloc((4 * Cr * last + 4 * Cr) * sizeof(float));
     if (!w) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_mask_head_finalize: out of host memory");
-    const float *dw = h->host[2 * n], *db = h->host[2 * n + 1];
+    const float *dw = p[2 * n].host, *db = p[2 * n + 1].host;
     for (uint64_t q = 0; q < 4; ++q)
         for (uint64_t co = 0; co < Cr; ++co) {
             for (uint64_t ci = 0; ci < last; ++ci) w[(q * Cr + co) * last + ci] = dw[(ci * Cr + co) * 4 + q];
             w[4 * Cr * last + q * Cr + co] = db[co];
         }
-    st = mask_head_pack(h, n, w, w + 4 * Cr * last, last, 4 * Cr, 1);
+    int st = rn_stage_pack(ctx, RN_DTYPE_F32, w, last, 4 * Cr, 1, w + 4 * Cr * last, NULL, &h->unit[n]);
     free(w);
-    if (st == RN_OK) st = rn_malloc(ctx, (void **)&h->lw, h->C * Cr * sizeof(float));
-    if (st == RN_OK) st = rn_malloc(ctx, (void **)&h->lb, h->C * sizeof(float));
-    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, h->lw, h->host[2 * n + 2], h->C * Cr * sizeof(float));
-    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, h->lb, h->host[2 * n + 3], h->C * sizeof(float));
+    if (st == RN_OK && !h->lw) st = rn_malloc(ctx, (void **)&h->lw, h->C * Cr * sizeof(float));
+    if (st == RN_OK && !h->lb) st = rn_malloc(ctx, (void **)&h->lb, h->C * sizeof(float));
+    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, h->lw, p[2 * n + 2].host, h->C * Cr * sizeof(float));
+    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, h->lb, p[2 * n + 3].host, h->C * sizeof(float));
     if (st != RN_OK) return st;
-    for (int i = 0; i < kMaskTensors; ++i) free(h->host[i]), h->host[i] = NULL;
+    rn_params_free(&h->params);
     h->finalized = 1;
     return RN_OK;
 }
@@ -571,9 +529,10 @@ int rn_mask_head_destroy(rn_mask_head *h)
     rn_ctx *ctx = h->ctx;
     RN_ENTER(ctx);
     RN_TRY(rn_sync(ctx));
-    mask_head_free_scratch(h);
-    for (int i = 0; i < kMaskTensors; ++i) free(h->host[i]);
-    for (int i = 0; i <= kMaskMaxLayers; ++i) rn_free_null(ctx, &h->packed[i]), rn_free_null(ctx, (void **)&h->bias[i]);
+    rn_scratch_item list[kMaskScratch];
+    rn_stage_free_list(ctx, list, mask_head_scratch(h, 0, 0, list));
+    rn_params_free(&h->params);
+    for (int i = 0; i <= kMaskMaxLayers; ++i) rn_stage_unit_free(ctx, &h->unit[i]);
     rn_free_null(ctx, (void **)&h->lw), rn_free_null(ctx, (void **)&h->lb);
     free(h);
     return RN_OK;
@@ -594,32 +553,15 @@ int rn_mask_head_matches(const rn_mask_head *h, const rn_ctx *ctx, uint64_t in_c
 
 uint64_t rn_mask_head_resolution(const rn_mask_head *h) { return h->M; }
 
-// the object's scratch for `rows` detections, under the box head's rules; with_pool: the RoI rows and the pooled
-// features of a forward behind a neck as well
+// the object's scratch for `rows` detections (rn_stage_grow's rule); with_pool: the RoI rows and the pooled features of a
+// forward behind a neck as well
 int rn_mask_head_reserve(rn_mask_head *h, uint64_t rows, int with_pool)
 {
-    rn_ctx *ctx = h->ctx;
-    if (rows <= h->cap && (!with_pool || rows <= h->cap_pool)) return RN_OK;
-    if (rn_ctx_is_capturing(ctx))
-        return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "rn_mask_head: the scratch cannot grow on a stream that is being captured");
-    if (h->cap > 0 && ctx->graphs_live > 0)
-        return rn_set_error(ctx, RN_ERR_INVALID, "rn_mask_head: the scratch cannot grow while a captured graph lives");
-    RN_TRY(rn_sync(ctx));
-    const uint64_t cap = rows > h->cap ? rows : h->cap;
-    const uint64_t cap_pool = with_pool && rows > h->cap_pool ? rows : h->cap_pool;
-    mask_head_free_scratch(h);
-    const uint64_t px = cap * h->M * h->M;
-    RN_TRY(rn_malloc(ctx, (void **)&h->ping, px * h->widest * sizeof(float)));
-    RN_TRY(rn_malloc(ctx, (void **)&h->pong, px * h->widest * sizeof(float)));
-    RN_TRY(rn_malloc(ctx, (void **)&h->t, px * 4 * h->Cr * sizeof(float)));
-    RN_TRY(rn_malloc(ctx, (void **)&h->probs, px * 4 * sizeof(float)));
-    h->cap = cap;
-    if (cap_pool) {
-        RN_TRY(rn_malloc(ctx, (void **)&h->rois, cap_pool * 5 * sizeof(float)));
-        RN_TRY(rn_malloc(ctx, (void **)&h->pooled, cap_pool * h->M * h->M * h->Cin * sizeof(float)));
-    }
-    h->cap_pool = cap_pool;
-    return RN_OK;
+    if (rows <= h->cap[kMaskRows] && (!with_pool || rows <= h->cap[kMaskPool])) return RN_OK;
+    const uint64_t want[2] = {rows > h->cap[kMaskRows] ? rows : h->cap[kMaskRows],
+                              with_pool && rows > h->cap[kMaskPool] ? rows : h->cap[kMaskPool]};
+    rn_scratch_item list[kMaskScratch];
+    return rn_stage_grow(h->ctx, "rn_mask_head", list, mask_head_scratch(h, want[kMaskRows], want[kMaskPool], list), h->cap, want, 2);
 }
 
 // every refusal that concerns the request and the shapes alone, for `rows` detections
@@ -654,7 +596,7 @@ int rn_mask_head_step(rn_mask_head *h, rn_ctx *ctx, const float *pooled_nhwc, co
                       uint64_t sub0, uint64_t K, uint64_t image_h, uint64_t image_w, float threshold, float *probs_out,
                       float *masks, uint8_t *bits)
 {
-    if (sub0 + K > h->cap) return rn_set_error(ctx, RN_ERR_INVALID, "rn_mask_head: scratch not reserved");
+    if (sub0 + K > h->cap[kMaskRows]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_mask_head: scratch not reserved");
     const uint64_t M = h->M, px0 = sub0 * M * M;
     float *ping = h->ping + px0 * h->widest, *pong = h->pong + px0 * h->widest, *t = h->t + px0 * 4 * h->Cr;
     rn_epilogue ep;
@@ -663,12 +605,12 @@ int rn_mask_head_step(rn_mask_head *h, rn_ctx *ctx, const float *pooled_nhwc, co
     uint64_t cin = h->Cin;
     for (uint64_t i = 0; i < h->n_layers; ++i) {
         float *y = i % 2 == 0 ? ping : pong;
-        ep.shift = h->bias[i];
-        RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, x, y, h->packed[i], 3, 1, 1, M, M, K, cin, h->ch[i], M, M, &ep));
+        ep.shift = h->unit[i].shift;
+        RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, x, y, h->unit[i].packed, 3, 1, 1, M, M, K, cin, h->ch[i], M, M, &ep));
         x = y, cin = h->ch[i];
     }
-    ep.shift = h->bias[h->n_layers];
-    RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, x, t, h->packed[h->n_layers], 1, 1, 0, M, M, K, cin, 4 * h->Cr, M, M, &ep));
+    ep.shift = h->unit[h->n_layers].shift;
+    RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, x, t, h->unit[h->n_layers].packed, 1, 1, 0, M, M, K, cin, 4 * h->Cr, M, M, &ep));
     float *probs = probs_out ? probs_out : h->probs + px0 * 4;
     RN_TRY(predict_launch(ctx, t, labels, h->lw, h->lb, K, M, h->Cr, h->C, probs, "rn_mask_head (predict)"));
     if (!masks && !bits) return RN_OK;
@@ -684,7 +626,7 @@ int rn_mask_head_stage(rn_mask_head *h, rn_ctx *ctx, uint64_t n_levels, const vo
                        const rn_mask_request *q)
 {
     const uint64_t M = h->M, K = B * D, row0 = img0 * D, srow0 = sub0 * D, feat = M * M * h->Cin;
-    if ((!q->rois || !q->pooled) && srow0 + K > h->cap_pool) return rn_set_error(ctx, RN_ERR_INVALID, "rn_mask_head: scratch not reserved");
+    if ((!q->rois || !q->pooled) && srow0 + K > h->cap[kMaskPool]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_mask_head: scratch not reserved");
     float *rois = q->rois ? q->rois + row0 * 5 : h->rois + srow0 * 5;
     float *pooled = q->pooled ? q->pooled + row0 * feat : h->pooled + srow0 * feat;
     const uint64_t plane = image_h * image_w;

@@ -8,6 +8,7 @@
 
 #include "rn_hip.h"
 #include "rn_operands.h"
+#include "rn_params.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -50,6 +51,45 @@ int rn_conv_group_nhwc_forward_dt(rn_ctx *ctx, int dtype, int out_dtype, const v
                                   uint64_t out_channels, uint64_t H, uint64_t W, uint64_t groups,
                                   const rn_epilogue *epilogue);
 
+/* ---- rn_stage.hip: what every object behind the backbone (neck, rpn, box head, mask head, segmentation head) is made
+ * of.  An object declares its parameters (rn_params.h) at create time, its convolution units and its scratch tensors;
+ * set_tensor, the "is not set" walk, the pack, the growth guard and the frees are here, once. ---- */
+/* the whole of a *_set_tensor behind its NULL-object check, under the name fn; `what`: "the neck", "the rpn", ...
+ * Keeps a host copy; nothing touches the device before finalize. */
+int rn_stage_set_tensor(rn_ctx *ctx, const char *fn, const char *what, int finalized, rn_params *t, const char *key,
+                        const float *host_data, uint64_t numel);
+/* RN_OK, or the refusal "<fn>: <key> is not set" for the first entry that is not */
+int rn_stage_all_set(rn_ctx *ctx, const char *fn, const rn_params *t);
+/* a convolution on the device: its packed panel, the epilogue's scale (a folded batch-norm; else NULL) and shift (that
+ * batch-norm's, or the bias), and a second panel where the object has one (a dilated branch's centre tap) */
+typedef struct rn_stage_unit {
+    void *packed;
+    float *scale, *shift;
+    void *center;
+} rn_stage_unit;
+/* Fills u->packed (and shift, scale) from host tensors: w [cout, cin, k, k] as it is stored, and either bias [cout], or
+ * bn: a batch-norm's weight, bias, running_mean, running_var [cout] each, or neither (no shift).  Over when it returns;
+ * what u held before is freed, and on failure u holds nothing. */
+int rn_stage_pack(rn_ctx *ctx, int dtype, const float *w, uint64_t cin, uint64_t cout, uint64_t k, const float *bias,
+                  const float *const *bn, rn_stage_unit *u);
+void rn_stage_unit_free(rn_ctx *ctx, rn_stage_unit *u);
+/* Two linear layers of `len` inputs as ONE panel of P rows: wa [ra, len] above wb [rb, len], zero rows up to P, and
+ * behind the panel the P biases likewise (ba, bb, zeros).  The added rows are exact zeros in every sum.  malloc'd
+ * (P * len + P values), or NULL. */
+float *rn_stage_side_by_side(const float *wa, const float *ba, uint64_t ra, const float *wb, const float *bb, uint64_t rb,
+                             uint64_t len, uint64_t P);
+/* a scratch tensor of an object: where its pointer lives and the bytes the capacities asked for need (0: none) */
+typedef struct rn_scratch_item {
+    void **ptr;
+    uint64_t bytes;
+} rn_scratch_item;
+/* The one growth rule, like the model's logits buffer: never on a stream that is being captured (RN_ERR_UNSUPPORTED),
+ * never while a captured graph of the context may hold what the object had (any of caps > 0: RN_ERR_INVALID).  Then
+ * sync, free the list, allocate the list, caps = want.  A failed allocation leaves caps at 0. */
+int rn_stage_grow(rn_ctx *ctx, const char *who, const rn_scratch_item *list, int n, uint64_t *caps, const uint64_t *want,
+                  int n_caps);
+void rn_stage_free_list(rn_ctx *ctx, const rn_scratch_item *list, int n);
+
 /* ---- rn_seg.hip: the segmentation head as the model driver queues it ---- */
 /* 1 when the head is finalized and reads maps of in_channels channels of `dtype`; *why: what is wrong otherwise */
 int rn_seg_head_matches(const rn_seg_head *hd, uint64_t in_channels, int dtype, const char **why);
@@ -62,7 +102,7 @@ void rn_seg_head_dims(const rn_seg_head *hd, uint64_t dims[4]);
  * that runs at this h x w: a ninth of the FLOPs where the centre-tap plan applies. */
 int rn_seg_head_plan(const rn_seg_head *hd, uint64_t B, uint64_t h, uint64_t w, uint64_t H, uint64_t W, int want_scores,
                      int want_labels, int step, const char **name, double *flops, double *bytes);
-/* the head's scratch for `images` images of `pixels` coarse pixels (h x w) each; grows like the model's logits buffer */
+/* the head's scratch for `images` images of `pixels` coarse pixels (h x w) each; grows under rn_stage_grow's rule */
 int rn_seg_head_reserve(rn_seg_head *hd, uint64_t images, uint64_t pixels);
 /* launch `step` of rn_seg_head_plan for B images of an h x w map on ctx; their scratch starts img0 images into the
  * head's tensors (img0 * h * w coarse pixels into the per-pixel ones, img0 rows into a DeepLab head's pooled vectors) */
@@ -79,7 +119,7 @@ enum { RN_FPN_INNER = 0, RN_FPN_TOPDOWN = 1, RN_FPN_LAYER = 2, RN_FPN_POOL = 3, 
 int rn_fpn_matches(const rn_fpn *fpn, const rn_ctx *ctx, int dtype, const char **why);
 /* levels, extra (0 none, 1 pool), out_channels, in_channels of every level; any pointer may be NULL */
 void rn_fpn_dims(const rn_fpn *fpn, int *n_levels, int *extra, uint64_t *out_channels, uint64_t in_channels[4]);
-/* the neck's scratch for `images` images whose level i is an h[i] x w[i] map; grows like the model's logits buffer */
+/* the neck's scratch for `images` images whose level i is an h[i] x w[i] map; grows under rn_stage_grow's rule */
 int rn_fpn_reserve(rn_fpn *fpn, uint64_t images, const uint64_t *h, const uint64_t *w);
 /* FLOPs and bytes of one launch of `kind` at `level` for B images (the profile's figures) */
 void rn_fpn_cost(const rn_fpn *fpn, int kind, int level, uint64_t B, const uint64_t *h, const uint64_t *w, double *flops,
@@ -109,7 +149,7 @@ int rn_roi_align_nhwc_window(rn_ctx *ctx, int dtype, uint64_t n_levels, const vo
 int rn_detection_rois_window(rn_ctx *ctx, const float *boxes, const int32_t *labels, uint64_t img0, uint64_t B, uint64_t D,
                              float *rois);
 
-/* ---- rn_rpn.hip: the RPN behind a neck, mirroring rn_fpn_roi_* ---- */
+/* ---- rn_rpn.hip: the RPN behind a neck (its parameters, units and scratch: rn_stage.hip) ---- */
 /* 1 when the rpn is finalized, lives on ctx's device, reads in_channels channels and n_levels levels; *why otherwise */
 int rn_rpn_matches(const rn_rpn *rpn, const rn_ctx *ctx, uint64_t in_channels, uint64_t n_levels, const char **why);
 /* the object's scratch for `images` images whose level l is h[l] x w[l], and pre candidates per (image, level) */
@@ -125,7 +165,7 @@ int rn_rpn_operands(const rn_rpn *rpn, const rn_rpn_request *req, uint64_t image
 int rn_rpn_step(rn_rpn *rpn, rn_ctx *ctx, const float *const *x, uint64_t sub0, uint64_t img0, uint64_t B,
                 const uint64_t *h, const uint64_t *w, uint64_t image_h, uint64_t image_w, const rn_rpn_request *req);
 
-/* ---- rn_detect.hip: the box head behind the pooler, mirroring rn_rpn_* ---- */
+/* ---- rn_detect.hip: the box head behind the pooler (its parameters, units and scratch: rn_stage.hip) ---- */
 /* 1 when the box head is finalized, lives on ctx's device and reads in_features values per RoI; *why otherwise */
 int rn_box_head_matches(const rn_box_head *bh, const rn_ctx *ctx, uint64_t in_features, const char **why);
 /* the object's scratch for `images` images of R RoIs each */
@@ -142,7 +182,7 @@ int rn_box_head_operands(const rn_box_head *bh, const rn_detect_request *req, ui
 int rn_box_head_step(rn_box_head *bh, rn_ctx *ctx, const float *pooled, const float *rois, uint64_t sub0, uint64_t img0,
                      uint64_t B, uint64_t R, uint64_t image_h, uint64_t image_w, const rn_detect_request *req);
 
-/* ---- rn_mask.hip: the mask head behind the box head, mirroring rn_box_head_* ---- */
+/* ---- rn_mask.hip: the mask head behind the box head (its parameters, units and scratch: rn_stage.hip) ---- */
 /* 1 when the mask head is finalized, lives on ctx's device and reads in_channels channels per pooled pixel; *why otherwise */
 int rn_mask_head_matches(const rn_mask_head *mh, const rn_ctx *ctx, uint64_t in_channels, const char **why);
 /* M: the side of the pooled map the head reads */

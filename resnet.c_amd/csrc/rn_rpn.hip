@@ -463,43 +463,41 @@ int rn_rpn_nms_merge_forward(rn_ctx *ctx, const rn_rpn_candidates *cand, uint64_
 }
 
 // ---- the object: RPNHead's two contractions per level in front of the three launches ---------------------------
-// host copies of the state dict's six tensors until rn_rpn_finalize packs them: 0 conv weight [C,C,3,3], 1 conv bias
-// [C], 2 cls_logits weight [A,C], 3 its bias [A], 4 bbox_pred weight [4A,C], 5 its bias [4A]
+// the state dict's six tensors (params): 0 conv weight [C,C,3,3], 1 conv bias [C], 2 cls_logits weight [A,C], 3 its
+// bias [A], 4 bbox_pred weight [4A,C], 5 its bias [4A]
 struct rn_rpn {
     rn_ctx *ctx;
     uint64_t C, L, A, P;
     int finalized;
     float base[kRpnMaxLevels * kRpnMaxAnchors * 4];
-    float *host[6];
-    void *packed_conv, *packed_pred;  // the 3x3 C -> C panel; ONE 1x1 C -> P panel: cls_logits, bbox_pred, zero rows
-    float *conv_bias, *pred_bias;     // the epilogues' shifts (pred_bias: P values, zeros behind 5A)
+    rn_params params;
+    rn_stage_unit conv, pred;  // the 3x3 C -> C; ONE 1x1 C -> P panel: cls_logits, bbox_pred, zero rows (rn_stage_side_by_side)
     // scratch for cap_img images: per level the 3x3's output [.,h,w,C] and the head output [.,h,w,P]; the candidates
     // per (image, level, rank) and the IoU mask
     float *t[kRpnMaxLevels], *head[kRpnMaxLevels];
-    uint64_t cap_pix[kRpnMaxLevels];
     float *c_logit, *c_box;
     uint8_t *c_valid;
     int32_t *c_count;
     uint64_t *words;
-    uint64_t cap_img, cap_pre;
+    uint64_t cap[kRpnMaxLevels + 2];  // images, candidates per (image, level), then the pixels of every level
 };
+enum { kRpnImg, kRpnPre, kRpnPix, kRpnScratch = 2 * kRpnMaxLevels + 5 };
 
-static uint64_t rpn_key_numel(const rn_rpn *r, int which)
+// the scratch tensors for the capacities `cap`; returns how many
+static int rpn_scratch(rn_rpn *r, const uint64_t *cap, rn_scratch_item *list)
 {
-    const uint64_t n[6] = {r->C * r->C * 9, r->C, r->A * r->C, r->A, 4 * r->A * r->C, 4 * r->A};
-    return n[which];
-}
-
-static void rpn_free_scratch(rn_rpn *r)
-{
+    int n = 0;
     for (uint64_t l = 0; l < r->L; ++l) {
-        rn_free_null(r->ctx, (void **)&r->t[l]), rn_free_null(r->ctx, (void **)&r->head[l]);
-        r->cap_pix[l] = 0;
+        list[n++] = {(void **)&r->t[l], cap[kRpnPix + l] * r->C * sizeof(float)};
+        list[n++] = {(void **)&r->head[l], cap[kRpnPix + l] * r->P * sizeof(float)};
     }
-    rn_free_null(r->ctx, (void **)&r->c_logit), rn_free_null(r->ctx, (void **)&r->c_box);
-    rn_free_null(r->ctx, (void **)&r->c_valid), rn_free_null(r->ctx, (void **)&r->c_count);
-    rn_free_null(r->ctx, (void **)&r->words);
-    r->cap_img = r->cap_pre = 0;
+    const uint64_t rows = cap[kRpnImg] * r->L * cap[kRpnPre];
+    list[n++] = {(void **)&r->c_logit, rows * 4};
+    list[n++] = {(void **)&r->c_box, rows * 16};
+    list[n++] = {(void **)&r->c_valid, rows};
+    list[n++] = {(void **)&r->c_count, cap[kRpnImg] * r->L * 4};
+    list[n++] = {(void **)&r->words, rows * rn_ceil_div(cap[kRpnPre], 64) * 8};
+    return n;
 }
 
 int rn_rpn_create(rn_ctx *ctx, rn_rpn **out, uint64_t in_channels, uint64_t L, uint64_t A, const float *base_anchors)
@@ -517,67 +515,39 @@ int rn_rpn_create(rn_ctx *ctx, rn_rpn **out, uint64_t in_channels, uint64_t L, u
     if (!r) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_rpn_create: out of host memory");
     r->ctx = ctx, r->C = in_channels, r->L = L, r->A = A, r->P = (5 * A + 3) & ~(uint64_t)3;
     memcpy(r->base, base_anchors, L * A * 4 * sizeof(float));
+    const uint64_t C = in_channels;
+    rn_params_add(&r->params, "head.conv.0.0.weight", "head.conv.weight", C, C * 9, C, C * 9, 0.0f);
+    rn_params_add(&r->params, "head.conv.0.0.bias", "head.conv.bias", 1, C, 1, C, 0.0f);
+    rn_params_add(&r->params, "head.cls_logits.weight", NULL, A, C, A, C, 0.0f);
+    rn_params_add(&r->params, "head.cls_logits.bias", NULL, 1, A, 1, A, 0.0f);
+    rn_params_add(&r->params, "head.bbox_pred.weight", NULL, 4 * A, C, 4 * A, C, 0.0f);
+    rn_params_add(&r->params, "head.bbox_pred.bias", NULL, 1, 4 * A, 1, 4 * A, 0.0f);
     *out = r;
     return RN_OK;
 }
 
 int rn_rpn_set_tensor(rn_rpn *r, const char *key, const float *host_data, uint64_t numel)
 {
-    static const char *const names[8] = {"head.conv.0.0.weight", "head.conv.0.0.bias", "head.cls_logits.weight",
-                                         "head.cls_logits.bias", "head.bbox_pred.weight", "head.bbox_pred.bias",
-                                         "head.conv.weight",     "head.conv.bias"};
     if (!r) return RN_ERR_INVALID;
-    rn_ctx *ctx = r->ctx;
-    RN_REQUIRE(ctx, key && host_data, "key or host_data is NULL");
-    RN_REQUIRE(ctx, !r->finalized, "the rpn is finalized");
-    int which = -1;
-    for (int i = 0; i < 8; ++i)
-        if (strcmp(key, names[i]) == 0) which = i < 6 ? i : i - 6;
-    if (which < 0) return rn_set_error(ctx, RN_ERR_INVALID, "rn_rpn_set_tensor: unknown key '%s'", key);
-    const uint64_t want = rpn_key_numel(r, which);
-    if (numel != want)
-        return rn_set_error(ctx, RN_ERR_INVALID, "rn_rpn_set_tensor: %s has %llu elements, not %llu", key,
-                            (unsigned long long)want, (unsigned long long)numel);
-    if (!r->host[which]) r->host[which] = (float *)malloc(want * sizeof(float));
-    if (!r->host[which]) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_rpn_set_tensor: out of host memory");
-    memcpy(r->host[which], host_data, want * sizeof(float));
-    return RN_OK;
+    return rn_stage_set_tensor(r->ctx, __func__, "the rpn", r->finalized, &r->params, key, host_data, numel);
 }
 
 int rn_rpn_finalize(rn_rpn *r)
 {
-    static const char *const names[6] = {"head.conv.0.0.weight", "head.conv.0.0.bias", "head.cls_logits.weight",
-                                         "head.cls_logits.bias", "head.bbox_pred.weight", "head.bbox_pred.bias"};
     if (!r) return RN_ERR_INVALID;
     rn_ctx *ctx = r->ctx;
     RN_ENTER(ctx);
     if (r->finalized) return RN_OK;
-    for (int i = 0; i < 6; ++i)
-        if (!r->host[i]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_rpn_finalize: %s is not set", names[i]);
+    RN_TRY(rn_stage_all_set(ctx, __func__, &r->params));
     const uint64_t C = r->C, A = r->A, P = r->P;
-    // cls_logits and bbox_pred side by side, zero rows up to P; the bias likewise (seg_add_unit's padding rule: exact)
-    float *w = (float *)calloc(P * C + P, sizeof(float));
+    const rn_params_entry *p = r->params.p;
+    float *w = rn_stage_side_by_side(p[2].host, p[3].host, A, p[4].host, p[5].host, 4 * A, C, P);
     if (!w) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_rpn_finalize: out of host memory");
-    memcpy(w, r->host[2], A * C * sizeof(float)), memcpy(w + A * C, r->host[4], 4 * A * C * sizeof(float));
-    memcpy(w + P * C, r->host[3], A * sizeof(float)), memcpy(w + P * C + A, r->host[5], 4 * A * sizeof(float));
-    float *raw_conv = NULL, *raw_pred = NULL;
-    int st = rn_malloc(ctx, (void **)&raw_conv, C * C * 9 * sizeof(float));
-    if (st == RN_OK) st = rn_malloc(ctx, (void **)&raw_pred, P * C * sizeof(float));
-    if (st == RN_OK) st = rn_malloc(ctx, (void **)&r->conv_bias, C * sizeof(float));
-    if (st == RN_OK) st = rn_malloc(ctx, (void **)&r->pred_bias, P * sizeof(float));
-    if (st == RN_OK) st = rn_malloc(ctx, &r->packed_conv, rn_conv2d_packed_weight_numel_dt(RN_DTYPE_F32, C, C, 3) * sizeof(float));
-    if (st == RN_OK) st = rn_malloc(ctx, &r->packed_pred, rn_conv2d_packed_weight_numel_dt(RN_DTYPE_F32, C, P, 1) * sizeof(float));
-    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, raw_conv, r->host[0], C * C * 9 * sizeof(float));
-    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, raw_pred, w, P * C * sizeof(float));
-    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, r->conv_bias, r->host[1], C * sizeof(float));
-    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, r->pred_bias, w + P * C, P * sizeof(float));
-    if (st == RN_OK) st = rn_conv2d_pack_weight_dt(ctx, RN_DTYPE_F32, raw_conv, r->packed_conv, C, C, 3);
-    if (st == RN_OK) st = rn_conv2d_pack_weight_dt(ctx, RN_DTYPE_F32, raw_pred, r->packed_pred, C, P, 1);
-    if (st == RN_OK) st = rn_sync(ctx);
+    int st = rn_stage_pack(ctx, RN_DTYPE_F32, p[0].host, C, C, 3, p[1].host, NULL, &r->conv);
+    if (st == RN_OK) st = rn_stage_pack(ctx, RN_DTYPE_F32, w, C, P, 1, w + P * C, NULL, &r->pred);
     free(w);
-    rn_free_null(ctx, (void **)&raw_conv), rn_free_null(ctx, (void **)&raw_pred);
     if (st != RN_OK) return st;
-    for (int i = 0; i < 6; ++i) free(r->host[i]), r->host[i] = NULL;
+    rn_params_free(&r->params);
     r->finalized = 1;
     return RN_OK;
 }
@@ -588,10 +558,10 @@ int rn_rpn_destroy(rn_rpn *r)
     rn_ctx *ctx = r->ctx;
     RN_ENTER(ctx);
     RN_TRY(rn_sync(ctx));
-    rpn_free_scratch(r);
-    for (int i = 0; i < 6; ++i) free(r->host[i]);
-    rn_free_null(ctx, &r->packed_conv), rn_free_null(ctx, &r->packed_pred);
-    rn_free_null(ctx, (void **)&r->conv_bias), rn_free_null(ctx, (void **)&r->pred_bias);
+    rn_scratch_item list[kRpnScratch];
+    rn_stage_free_list(ctx, list, rpn_scratch(r, r->cap, list));
+    rn_params_free(&r->params);
+    rn_stage_unit_free(ctx, &r->conv), rn_stage_unit_free(ctx, &r->pred);
     free(r);
     return RN_OK;
 }
@@ -612,33 +582,17 @@ int rn_rpn_matches(const rn_rpn *r, const rn_ctx *ctx, uint64_t in_channels, uin
 
 int rn_rpn_reserve(rn_rpn *r, uint64_t images, const uint64_t *h, const uint64_t *w, uint64_t pre)
 {
-    rn_ctx *ctx = r->ctx;
-    bool fits = images <= r->cap_img && pre <= r->cap_pre;
-    for (uint64_t l = 0; l < r->L; ++l) fits = fits && images * h[l] * w[l] <= r->cap_pix[l];
-    if (fits) return RN_OK;
-    const bool had = r->cap_img > 0;
-    if (rn_ctx_is_capturing(ctx))
-        return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "rn_rpn: the scratch cannot grow on a stream that is being captured");
-    if (had && ctx->graphs_live > 0)
-        return rn_set_error(ctx, RN_ERR_INVALID, "rn_rpn: the scratch cannot grow while a captured graph lives");
-    RN_TRY(rn_sync(ctx));
-    uint64_t pix[kRpnMaxLevels];
-    for (uint64_t l = 0; l < r->L; ++l) pix[l] = images * h[l] * w[l] > r->cap_pix[l] ? images * h[l] * w[l] : r->cap_pix[l];
-    const uint64_t img = images > r->cap_img ? images : r->cap_img, kp = pre > r->cap_pre ? pre : r->cap_pre;
-    rpn_free_scratch(r);
-    for (uint64_t l = 0; l < r->L; ++l) {
-        RN_TRY(rn_malloc(ctx, (void **)&r->t[l], pix[l] * r->C * sizeof(float)));
-        RN_TRY(rn_malloc(ctx, (void **)&r->head[l], pix[l] * r->P * sizeof(float)));
-        r->cap_pix[l] = pix[l];
+    uint64_t want[kRpnMaxLevels + 2] = {};
+    want[kRpnImg] = images, want[kRpnPre] = pre;
+    for (uint64_t l = 0; l < r->L; ++l) want[kRpnPix + l] = images * h[l] * w[l];
+    bool fits = true;
+    for (int i = 0; i < kRpnMaxLevels + 2; ++i) {
+        fits = fits && want[i] <= r->cap[i];
+        if (want[i] < r->cap[i]) want[i] = r->cap[i];
     }
-    const uint64_t rows = img * r->L * kp;
-    RN_TRY(rn_malloc(ctx, (void **)&r->c_logit, rows * 4));
-    RN_TRY(rn_malloc(ctx, (void **)&r->c_box, rows * 16));
-    RN_TRY(rn_malloc(ctx, (void **)&r->c_valid, rows));
-    RN_TRY(rn_malloc(ctx, (void **)&r->c_count, img * r->L * 4));
-    RN_TRY(rn_malloc(ctx, (void **)&r->words, rows * rn_ceil_div(kp, 64) * 8));
-    r->cap_img = img, r->cap_pre = kp;
-    return RN_OK;
+    if (fits) return RN_OK;
+    rn_scratch_item list[kRpnScratch];
+    return rn_stage_grow(r->ctx, "rn_rpn", list, rpn_scratch(r, want, list), r->cap, want, kRpnMaxLevels + 2);
 }
 
 // every refusal that concerns the request alone, for `images` images (text in ctx)
@@ -685,18 +639,18 @@ int rn_rpn_step(rn_rpn *r, rn_ctx *ctx, const float *const *x, uint64_t sub0, ui
                 const uint64_t *w, uint64_t image_h, uint64_t image_w, const rn_rpn_request *q)
 {
     const uint64_t L = r->L, C = r->C, P = r->P, pre = q->pre_nms_top_n, post = q->post_nms_top_n;
-    if (sub0 + B > r->cap_img || pre > r->cap_pre) return rn_set_error(ctx, RN_ERR_INVALID, "rn_rpn: scratch not reserved");
+    if (sub0 + B > r->cap[kRpnImg] || pre > r->cap[kRpnPre]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_rpn: scratch not reserved");
     const float *heads[kRpnMaxLevels];
     rn_epilogue ep;
     ep.scale = NULL, ep.residual = NULL;
     for (uint64_t l = 0; l < L; ++l) {
-        if ((sub0 + B) * h[l] * w[l] > r->cap_pix[l]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_rpn: scratch not reserved");
+        if ((sub0 + B) * h[l] * w[l] > r->cap[kRpnPix + l]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_rpn: scratch not reserved");
         float *t = r->t[l] + sub0 * h[l] * w[l] * C, *hd = r->head[l] + sub0 * h[l] * w[l] * P;
-        ep.shift = r->conv_bias, ep.relu = 1;
-        RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, x[l], t, r->packed_conv, 3, 1, 1, h[l], w[l], B, C, C,
+        ep.shift = r->conv.shift, ep.relu = 1;
+        RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, x[l], t, r->conv.packed, 3, 1, 1, h[l], w[l], B, C, C,
                                          h[l], w[l], &ep));
-        ep.shift = r->pred_bias, ep.relu = 0;
-        RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, t, hd, r->packed_pred, 1, 1, 0, h[l], w[l], B, C, P,
+        ep.shift = r->pred.shift, ep.relu = 0;
+        RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, t, hd, r->pred.packed, 1, 1, 0, h[l], w[l], B, C, P,
                                          h[l], w[l], &ep));
         heads[l] = hd;
     }

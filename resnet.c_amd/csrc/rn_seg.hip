@@ -259,31 +259,18 @@ __global__ __launch_bounds__(256) void concat_channels_kernel(const concat_args 
 //   DeepLabHead(in, classes) = ASPP(in, rates, a) + Conv3x3(a, a) + BN + ReLU + Conv1x1(a, classes).  n + 5 units
 //   (the 1x1 branch, the n dilated 3x3 branches, the pooled branch's 1x1, the projection, the 3x3, the
 //   classifier), n + 8 launches.
-constexpr int kSegMaxRates = 4, kSegMaxUnits = kSegMaxRates + 5, kSegMaxTensors = 5 * (kSegMaxUnits - 1) + 2;
+constexpr int kSegMaxRates = 4, kSegMaxUnits = kSegMaxRates + 5;
 constexpr int kSegMaxBufs = kSegMaxRates + 5, kSegMaxSteps = kSegMaxRates + 8;
 
-// a tensor of the state dict, `rows` rows of `len` values, and its fp32 copy on the device, `prows` rows of `pitch`:
-// padded on the host, every added element `fill`
-struct seg_tensor {
-    char key[64];
-    uint64_t rows, len, prows, pitch;
-    float fill;
-    float *raw;
-    int is_set;
-};
-
 // A k x k convolution of cin -> cout channels, both as they run (padded).  bn: a batch-norm folded into scale and
-// shift and a ReLU follow, the output is of the storage type; tensors first .. first + 4 are the weight and the
+// shift and a ReLU follow, the output is of the storage type; parameters first .. first + 4 are the weight and the
 // batch-norm's weight, bias, running_mean and running_var.  Otherwise (the classifier) it carries a bias, which is
-// its shift, has no ReLU and an fp32 output; tensors first and first + 1.
+// its shift, has no ReLU and an fp32 output; parameters first and first + 1.
 struct seg_unit {
     uint64_t cin, cout, k;
     uint64_t dilation;  // 0: a plain convolution, padding k / 2; else a dilated 3x3 branch of ASPP, padding = dilation
     int bn, first;
-    void *packed;
-    float *scale, *shift;
-    void *center;       // dilated branches: the centre tap weight[:, :, 1, 1] packed as a 1x1 panel
-    float *raw_center;  // its fp32 [cout, cin] source until finalize
+    rn_stage_unit dev;  // center: a dilated branch's centre tap weight[:, :, 1, 1] packed as a 1x1 panel
 };
 
 struct seg_buf {  // a scratch tensor: [cap_img, channels] or [cap_pix, channels], fp32 or of the storage type
@@ -308,22 +295,24 @@ struct rn_seg_head {
     uint64_t midp, cpad;  // the classifier's channels as it runs (seg_add_unit)
     int dtype, finalized;
     int center_tap;  // rn_seg_head_set_center_tap
-    int n_units, n_tensors, n_bufs, n_steps;
+    int n_units, n_bufs, n_steps;
     seg_unit unit[kSegMaxUnits];
-    seg_tensor tensor[kSegMaxTensors];
+    rn_params params;  // 5 per unit with a batch-norm, 2 of the classifier: at most 5 * (kSegMaxUnits - 1) + 2
     seg_buf buf[kSegMaxBufs];
     seg_step step[kSegMaxSteps];
-    uint64_t cap_pix, cap_img;  // coarse pixels (images x h x w) and images the scratch tensors hold
+    uint64_t cap[2];  // coarse pixels (images x h x w) and images the scratch tensors hold
 };
+enum { kSegPix, kSegImg };
+static_assert(5 * (kSegMaxUnits - 1) + 2 <= RN_PARAMS_MAX, "the parameter table holds a DeepLab head of kSegMaxRates rates");
 
 namespace {
 
 void seg_add_tensor(rn_seg_head *hd, const char *module, const char *name, uint64_t rows, uint64_t len, uint64_t prows,
                     uint64_t pitch, float fill)
 {
-    seg_tensor *t = &hd->tensor[hd->n_tensors++];
-    snprintf(t->key, sizeof(t->key), "%s.%s", module, name);
-    t->rows = rows, t->len = len, t->prows = prows, t->pitch = pitch, t->fill = fill;
+    char key[RN_PARAM_KEY];
+    snprintf(key, sizeof(key), "%s.%s", module, name);
+    rn_params_add(&hd->params, key, NULL, rows, len, prows, pitch, fill);
 }
 
 // The unit `conv` (+ batch-norm `norm`, or NULL: + bias) of the state dict: cin -> cout channels there.  It runs
@@ -338,7 +327,7 @@ int seg_add_unit(rn_seg_head *hd, const char *conv, const char *norm, uint64_t c
     static const char *const bn[4] = {"weight", "bias", "running_mean", "running_var"};
     seg_unit *un = &hd->unit[hd->n_units];
     un->cin = (cin + 63) / 64 * 64, un->cout = norm ? (cout + 63) / 64 * 64 : (cout + 3) / 4 * 4;
-    un->k = k, un->dilation = dilation, un->bn = norm != NULL, un->first = hd->n_tensors;
+    un->k = k, un->dilation = dilation, un->bn = norm != NULL, un->first = hd->params.n;
     seg_add_tensor(hd, conv, "weight", cout, cin * k * k, un->cout, un->cin * k * k, 0.0f);
     if (!norm) seg_add_tensor(hd, conv, "bias", 1, cout, 1, un->cout, 0.0f);
     for (int j = 0; norm && j < 4; ++j) seg_add_tensor(hd, norm, bn[j], 1, cout, 1, un->cout, j == 3 ? 1.0f : 0.0f);
@@ -377,22 +366,6 @@ void seg_add_classifier(rn_seg_head *hd, int from, uint64_t mid)
     seg_add_step(hd, SEG_UPSAMPLE, 0, coarse, -1, "seg_upsample");
 }
 
-// `rows` rows of `len` values, `stride` apart in src, to the device as prows rows of pitch (*dev: allocated at the
-// first call); every element added is `fill`
-int seg_upload(rn_ctx *ctx, float **dev, const float *src, uint64_t rows, uint64_t len, uint64_t stride, uint64_t prows,
-               uint64_t pitch, float fill)
-{
-    const uint64_t n = prows * pitch;
-    float *padded = (float *)malloc(n * sizeof(float));
-    if (!padded) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_seg_head_set_tensor: out of host memory");
-    for (uint64_t i = 0; i < n; ++i) padded[i] = fill;
-    for (uint64_t r = 0; r < rows; ++r) memcpy(padded + r * pitch, src + r * stride, len * sizeof(float));
-    int st = *dev ? RN_OK : rn_malloc(ctx, (void **)dev, n * sizeof(float));
-    if (st == RN_OK) st = rn_ctx_upload_sync(ctx, *dev, padded, n * sizeof(float));
-    free(padded);
-    return st;
-}
-
 // Whether dilated branch `un` of a forward on an h x w map runs as the 1x1 contraction on its centre tap.  With
 // rate >= h and rate >= w every other tap of every output pixel lies outside the image, so the 3x3 sums the centre
 // tap's products in channel order among zeros, and so does the 1x1 -- the same bits as long as both routes round
@@ -415,14 +388,18 @@ bool dl_center_route(const rn_seg_head *hd, const seg_unit *un, uint64_t h, uint
 bool seg_fits(const rn_seg_head *hd, uint64_t pix, uint64_t images)
 {
     for (int i = 0; i < hd->n_bufs; ++i)
-        if (hd->buf[i].per_image ? images > hd->cap_img : pix > hd->cap_pix) return false;
+        if (hd->buf[i].per_image ? images > hd->cap[kSegImg] : pix > hd->cap[kSegPix]) return false;
     return true;
 }
 
-void seg_free_scratch(rn_seg_head *hd)
+// the scratch tensors for `pix` coarse pixels and `images` images; returns how many
+int seg_scratch(rn_seg_head *hd, uint64_t pix, uint64_t images, rn_scratch_item *list)
 {
-    for (int i = 0; i < hd->n_bufs; ++i) rn_free_null(hd->ctx, &hd->buf[i].ptr);
-    hd->cap_pix = hd->cap_img = 0;
+    for (int i = 0; i < hd->n_bufs; ++i) {
+        seg_buf *b = &hd->buf[i];
+        list[i] = {&b->ptr, (b->per_image ? images : pix) * b->channels * (b->f32 ? 4 : rn_elem_size(hd->dtype))};
+    }
+    return hd->n_bufs;
 }
 
 // where the B images of a launch whose scratch starts img0 images (pix0 coarse pixels) in begin in scratch tensor i
@@ -617,25 +594,31 @@ int rn_seg_head_set_dtype(rn_seg_head *hd, int dtype)
 int rn_seg_head_set_tensor(rn_seg_head *hd, const char *key, const float *host_data, uint64_t numel)
 {
     if (!hd) return RN_ERR_INVALID;
-    rn_ctx *ctx = hd->ctx;
-    RN_ENTER(ctx);
-    RN_REQUIRE(ctx, key && host_data, "key or host_data is NULL");
-    RN_REQUIRE(ctx, !hd->finalized, "the head is finalized");
-    int i = 0;
-    while (i < hd->n_tensors && strcmp(key, hd->tensor[i].key) != 0) ++i;
-    if (i == hd->n_tensors) return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head_set_tensor: unknown key '%s'", key);
-    seg_tensor *t = &hd->tensor[i];
-    if (numel != t->rows * t->len)
-        return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head_set_tensor: %s has %llu elements, not %llu", key,
-                            (unsigned long long)(t->rows * t->len), (unsigned long long)numel);
-    RN_TRY(seg_upload(ctx, &t->raw, host_data, t->rows, t->len, t->len, t->prows, t->pitch, t->fill));
-    for (int u = 0; u < hd->n_units; ++u) {  // a dilated branch's weight [cout, cin, 3, 3]: its centre tap too
-        seg_unit *un = &hd->unit[u];
-        const uint64_t taps = un->cout * un->cin;  // a branch is never padded
-        if (un->dilation && un->first == i) RN_TRY(seg_upload(ctx, &un->raw_center, host_data + 4, taps, 1, 9, taps, 1, 0.0f));
+    return rn_stage_set_tensor(hd->ctx, __func__, "the head", hd->finalized, &hd->params, key, host_data, numel);
+}
+
+// unit `un` on the device: its parameters as they are stored (seg_add_unit's padding), packed; a dilated branch's
+// centre tap, cut from the weight [cout, cin, 3, 3] (a branch is never padded), as a second panel
+static int seg_pack_unit(rn_seg_head *hd, seg_unit *un)
+{
+    const rn_params *t = &hd->params;
+    const rn_params_entry *e = &t->p[un->first];
+    const uint64_t n = e->prows * e->pitch, taps = un->cout * un->cin;
+    float *buf = (float *)malloc((n + 4 * un->cout + (un->dilation ? taps : 0)) * sizeof(float));
+    if (!buf) return rn_set_error(hd->ctx, RN_ERR_NOMEM, "rn_seg_head_finalize: out of host memory");
+    float *vec = buf + n, *tap = vec + 4 * un->cout;
+    const float *bn[4];
+    rn_params_write(t, un->first, buf);
+    for (int j = 0; j < (un->bn ? 4 : 1); ++j) rn_params_write(t, un->first + 1 + j, vec + j * un->cout), bn[j] = vec + j * un->cout;
+    int st = rn_stage_pack(hd->ctx, hd->dtype, buf, un->cin, un->cout, un->k, un->bn ? NULL : vec, un->bn ? bn : NULL, &un->dev);
+    if (st == RN_OK && un->dilation) {
+        rn_stage_unit c = {};
+        for (uint64_t i = 0; i < taps; ++i) tap[i] = e->host[i * 9 + 4];
+        st = rn_stage_pack(hd->ctx, hd->dtype, tap, un->cin, un->cout, 1, NULL, NULL, &c);
+        un->dev.center = c.packed;
     }
-    t->is_set = 1;
-    return RN_OK;
+    free(buf);
+    return st;
 }
 
 int rn_seg_head_finalize(rn_seg_head *hd)
@@ -644,34 +627,9 @@ int rn_seg_head_finalize(rn_seg_head *hd)
     rn_ctx *ctx = hd->ctx;
     RN_ENTER(ctx);
     if (hd->finalized) return RN_OK;
-    for (int i = 0; i < hd->n_tensors; ++i)
-        if (!hd->tensor[i].is_set)
-            return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head_finalize: %s is not set", hd->tensor[i].key);
-    const int dt = hd->dtype;
-    const uint64_t es = rn_elem_size(dt);
-    for (int u = 0; u < hd->n_units; ++u) {
-        seg_unit *un = &hd->unit[u];
-        seg_tensor *t = &hd->tensor[un->first];
-        if (un->bn) {
-            RN_TRY(rn_malloc(ctx, (void **)&un->scale, un->cout * sizeof(float)));
-            RN_TRY(rn_malloc(ctx, (void **)&un->shift, un->cout * sizeof(float)));
-            RN_TRY(rn_batchnorm2d_fold(ctx, t[1].raw, t[2].raw, t[3].raw, t[4].raw, un->scale, un->shift, un->cout));
-        }
-        RN_TRY(rn_malloc(ctx, &un->packed, rn_conv2d_packed_weight_numel_dt(dt, un->cin, un->cout, un->k) * es));
-        RN_TRY(rn_conv2d_pack_weight_dt(ctx, dt, t[0].raw, un->packed, un->cin, un->cout, un->k));
-        if (un->raw_center) {
-            RN_TRY(rn_malloc(ctx, &un->center, rn_conv2d_packed_weight_numel_dt(dt, un->cin, un->cout, 1) * es));
-            RN_TRY(rn_conv2d_pack_weight_dt(ctx, dt, un->raw_center, un->center, un->cin, un->cout, 1));
-        }
-    }
-    RN_TRY(rn_sync(ctx));
-    for (int u = 0; u < hd->n_units; ++u) {
-        seg_unit *un = &hd->unit[u];
-        float **bias = &hd->tensor[un->first + 1].raw;
-        if (!un->bn) un->shift = *bias, *bias = NULL;  // the bias stays: the unit's shift
-        rn_free_null(ctx, (void **)&un->raw_center);
-    }
-    for (int i = 0; i < hd->n_tensors; ++i) rn_free_null(ctx, (void **)&hd->tensor[i].raw);
+    RN_TRY(rn_stage_all_set(ctx, __func__, &hd->params));
+    for (int u = 0; u < hd->n_units; ++u) RN_TRY(seg_pack_unit(hd, &hd->unit[u]));
+    rn_params_free(&hd->params);
     hd->finalized = 1;
     return RN_OK;
 }
@@ -682,13 +640,10 @@ int rn_seg_head_destroy(rn_seg_head *hd)
     rn_ctx *ctx = hd->ctx;
     RN_ENTER(ctx);
     RN_TRY(rn_sync(ctx));
-    seg_free_scratch(hd);
-    for (int i = 0; i < hd->n_tensors; ++i) rn_free_null(ctx, (void **)&hd->tensor[i].raw);
-    for (int u = 0; u < hd->n_units; ++u) {
-        seg_unit *un = &hd->unit[u];
-        rn_free_null(ctx, &un->packed), rn_free_null(ctx, &un->center), rn_free_null(ctx, (void **)&un->raw_center);
-        rn_free_null(ctx, (void **)&un->scale), rn_free_null(ctx, (void **)&un->shift);
-    }
+    rn_scratch_item list[kSegMaxBufs];
+    rn_stage_free_list(ctx, list, seg_scratch(hd, 0, 0, list));
+    rn_params_free(&hd->params);
+    for (int u = 0; u < hd->n_units; ++u) rn_stage_unit_free(ctx, &hd->unit[u].dev);
     free(hd);
     return RN_OK;
 }
@@ -745,29 +700,14 @@ int rn_seg_head_plan(const rn_seg_head *hd, uint64_t B, uint64_t h, uint64_t w, 
     return hd->n_steps;
 }
 
-// the scratch for `images` images of `pixels` coarse pixels (h x w) each; it never shrinks and grows like the
-// model's logits buffer: never on a stream that is being captured, never while a captured graph of the context may
-// hold it
+// the scratch for `images` images of `pixels` coarse pixels (h x w) each; it never shrinks (rn_stage_grow's rule)
 int rn_seg_head_reserve(rn_seg_head *hd, uint64_t images, uint64_t pixels)
 {
-    rn_ctx *ctx = hd->ctx;
-    uint64_t pix = images * pixels;
+    const uint64_t pix = images * pixels;
     if (seg_fits(hd, pix, images)) return RN_OK;
-    if (rn_ctx_is_capturing(ctx))
-        return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "rn_seg_head: the scratch cannot grow on a stream that is being captured");
-    if (hd->cap_pix > 0 && ctx->graphs_live > 0)
-        return rn_set_error(ctx, RN_ERR_INVALID, "rn_seg_head: the scratch cannot grow while a captured graph lives");
-    RN_TRY(rn_sync(ctx));
-    if (pix < hd->cap_pix) pix = hd->cap_pix;
-    if (images < hd->cap_img) images = hd->cap_img;
-    seg_free_scratch(hd);
-    for (int i = 0; i < hd->n_bufs; ++i) {
-        seg_buf *b = &hd->buf[i];
-        const uint64_t es = b->f32 ? 4 : rn_elem_size(hd->dtype);
-        RN_TRY(rn_malloc(ctx, &b->ptr, (b->per_image ? images : pix) * b->channels * es));
-    }
-    hd->cap_pix = pix, hd->cap_img = images;
-    return RN_OK;
+    const uint64_t want[2] = {pix > hd->cap[kSegPix] ? pix : hd->cap[kSegPix], images > hd->cap[kSegImg] ? images : hd->cap[kSegImg]};
+    rn_scratch_item list[kSegMaxBufs];
+    return rn_stage_grow(hd->ctx, "rn_seg_head", list, seg_scratch(hd, want[kSegPix], want[kSegImg], list), hd->cap, want, 2);
 }
 
 // one of the head's launches on `ctx` (the head's own context, or the context of the model's stream the images
@@ -788,12 +728,12 @@ int rn_seg_head_step(rn_seg_head *hd, rn_ctx *ctx, int step, const void *x_nhwc,
         const seg_unit *un = &hd->unit[s->u];
         const uint64_t uh = per_image ? 1 : h, uw = per_image ? 1 : w;
         rn_epilogue ep;
-        ep.scale = un->scale, ep.shift = un->shift, ep.residual = NULL, ep.relu = un->bn;
+        ep.scale = un->dev.scale, ep.shift = un->dev.shift, ep.residual = NULL, ep.relu = un->bn;
         if (un->dilation && !dl_center_route(hd, un, h, w))
-            return rn_conv2d_dilated_nhwc_forward_dt(ctx, dt, dt, src, dst, un->packed, 3, 1, un->dilation, un->dilation, h,
+            return rn_conv2d_dilated_nhwc_forward_dt(ctx, dt, dt, src, dst, un->dev.packed, 3, 1, un->dilation, un->dilation, h,
                                                      w, B, un->cin, un->cout, h, w, 1, &ep);
         const uint64_t k = un->dilation ? 1 : un->k;  // a dilated branch gets here on its centre tap
-        return rn_conv2d_nhwc_forward_dt(ctx, dt, un->bn ? dt : RN_DTYPE_F32, src, dst, un->dilation ? un->center : un->packed,
+        return rn_conv2d_nhwc_forward_dt(ctx, dt, un->bn ? dt : RN_DTYPE_F32, src, dst, un->dilation ? un->dev.center : un->dev.packed,
                                          k, 1, k / 2, uh, uw, B, un->cin, un->cout, uh, uw, &ep);
     }
     case SEG_POOL: return rn_global_avgpool_nhwc_forward_dt(ctx, dt, src, dst, B, hd->buf[s->dst].channels, h, w);

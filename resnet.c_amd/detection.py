@@ -14,6 +14,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import rpn
+from ._lib import Handle
 
 F = np.float32
 BOX_WEIGHTS = (10.0, 10.0, 5.0, 5.0)   # torchvision's bbox_reg_weights of the box head
@@ -209,10 +210,11 @@ def make_request(bufs, score_thresh, nms_thresh, min_size, detections_per_img, w
                                                          "valid", "keep")]))
 
 
-class BoxHead:
+class BoxHead(Handle):
     """rn_box_head_*: TwoMLPHead (fc6, fc7 with ReLU) and FastRCNNPredictor as three contractions, then the three
     launches of the post-processing.  in_channels and resolution are the pooler's a and (PH, PW); state holds the eight
     tensors (split_state normalises the keys)."""
+    DESTROY = "rn_box_head_destroy"
 
     def __init__(self, in_channels: int, resolution, representation: int, classes: int, state, score_thresh: float = 0.05,
                  nms_thresh: float = 0.5, detections_per_img: int = 100, bbox_reg_weights=BOX_WEIGHTS, min_size: float = MIN_SIZE,
@@ -233,12 +235,7 @@ class BoxHead:
                 "rn_box_head_create", self.ctx.handle)
         self.handle = h
         mine, _ = split_state(state)
-        for key, shape in head_shapes(self.in_features, self.representation, self.classes).items():
-            arr = np.ascontiguousarray(mine[key], dtype=F)
-            assert arr.size == int(np.prod(shape)), (key, arr.shape, shape)
-            L.check(L.lib().rn_box_head_set_tensor(h, key.encode(), arr.ctypes.data, arr.size), f"rn_box_head_set_tensor({key})",
-                    self.ctx.handle)
-        L.check(L.lib().rn_box_head_finalize(h), "rn_box_head_finalize", self.ctx.handle)
+        L.set_tensors(h, "rn_box_head", self.ctx, head_shapes(self.in_features, self.representation, self.classes), mine)
 
     def buffers(self, B: int, R: int, intermediates: bool = False):
         """device buffers of a forward of B images of R RoIs: (spec, buffers)"""
@@ -286,15 +283,3 @@ class BoxHead:
         if head:
             out["head"] = _down_raw(head, F, K * self.pitch).reshape(K, self.pitch)
         return out
-
-    def close(self) -> None:
-        if self.handle:
-            from . import _lib as L
-            L.lib().rn_box_head_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -192,11 +192,12 @@ class NeckTail:
         return out
 
 
-class FeaturePyramidNetwork:
+class FeaturePyramidNetwork(L.Handle):
     """rn_fpn_*: FeaturePyramidNetwork(in_channels_list, out_channels, extra_blocks=LastLevelMaxPool()) on the device
     (extra=None: no extra block); state holds torchvision's tensors (fpn_shapes; split_state normalises the keys).
     dtype "f32" or "bf16": storage of the input maps, the lateral tensors and the weight panels; the outputs are fp32
     either way."""
+    DESTROY = "rn_fpn_destroy"
 
     def __init__(self, in_channels_list: Sequence[int], out_channels: int, state: Dict[str, np.ndarray],
                  extra: Optional[str] = "pool", dtype: str = "f32", ctx=None):
@@ -213,12 +214,7 @@ class FeaturePyramidNetwork:
         self.handle = h
         L.check(lib.rn_fpn_set_dtype(h, {"f32": L.RN_DTYPE_F32, "bf16": L.RN_DTYPE_BF16}[dtype]), "rn_fpn_set_dtype",
                 self.ctx.handle)
-        for key, shape in fpn_shapes(self.in_channels_list, self.out_channels).items():
-            arr = np.ascontiguousarray(state[key], dtype=np.float32)
-            assert arr.size == int(np.prod(shape)), (key, arr.shape, shape)
-            L.check(lib.rn_fpn_set_tensor(h, key.encode(), arr.ctypes.data, arr.size), f"rn_fpn_set_tensor({key})",
-                    self.ctx.handle)
-        L.check(lib.rn_fpn_finalize(h), "rn_fpn_finalize", self.ctx.handle)
+        L.set_tensors(h, "rn_fpn", self.ctx, fpn_shapes(self.in_channels_list, self.out_channels), state)
 
     @property
     def names(self) -> Tuple[str, ...]:
@@ -300,14 +296,3 @@ class FeaturePyramidNetwork:
         out = {name: _down_raw(bufs[name], np.float32, int(np.prod(shapes[name]))).reshape(shapes[name])
                for name in self.names if name in bufs}
         return tail.collect(out)
-
-    def close(self) -> None:
-        if self.handle:
-            L.lib().rn_fpn_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -13,6 +13,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._lib import Handle
+
 F = np.float32
 PREDICTOR_KEYS = ("mask_predictor.conv5_mask.weight", "mask_predictor.conv5_mask.bias",
                   "mask_predictor.mask_fcn_logits.weight", "mask_predictor.mask_fcn_logits.bias")
@@ -254,11 +256,12 @@ def output_spec(B: int, D: int, M: int, a: int, image_size, masks=("probs",), ro
     return spec
 
 
-class MaskHead:
+class MaskHead(Handle):
     """rn_mask_head_*: MaskRCNNHeads (3x3 convolutions with bias and ReLU), MaskRCNNPredictor's transposed convolution as
     one 1x1 panel, then the class-selected predict launch and the paste.  state holds the head's tensors in either
     spelling (split_state normalises the keys).  featmap_names, sampling_ratio: the mask pooler of a forward behind a
     neck."""
+    DESTROY = "rn_mask_head_destroy"
 
     def __init__(self, in_channels: int, layers=(256,) * 4, dim_reduced: int = 256, classes: int = 91, state=None,
                  resolution: int = 14, featmap_names=("0", "1", "2", "3"), sampling_ratio: int = 2, threshold: float = 0.5,
@@ -280,12 +283,7 @@ class MaskHead:
                                             self.dim_reduced, self.classes, self.resolution), "rn_mask_head_create", self.ctx.handle)
         self.handle = h
         mine, _ = split_state(state)
-        for key, shape in head_shapes(self.in_channels, self.layers, self.dim_reduced, self.classes).items():
-            arr = np.ascontiguousarray(mine[key], dtype=F)
-            assert arr.size == int(np.prod(shape)), (key, arr.shape, shape)
-            L.check(L.lib().rn_mask_head_set_tensor(h, key.encode(), arr.ctypes.data, arr.size),
-                    f"rn_mask_head_set_tensor({key})", self.ctx.handle)
-        L.check(L.lib().rn_mask_head_finalize(h), "rn_mask_head_finalize", self.ctx.handle)
+        L.set_tensors(h, "rn_mask_head", self.ctx, head_shapes(self.in_channels, self.layers, self.dim_reduced, self.classes), mine)
 
     def buffers(self, B: int, D: int, image_size, masks=("probs",), rois: bool = False, pooled: bool = False):
         """device buffers of a forward of B images of D detections: (spec, buffers)"""
@@ -333,15 +331,3 @@ class MaskHead:
                                              ctypes.byref(req)), "rn_mask_head_forward", self.ctx.handle)
         self.ctx.sync()
         return self.collect(spec, bufs)
-
-    def close(self) -> None:
-        if self.handle:
-            from . import _lib as L
-            L.lib().rn_mask_head_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -12,6 +12,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._lib import Handle
+
 F = np.float32
 BBOX_XFORM_CLIP = F(np.log(1000.0 / 16.0))   # (float)log(1000.0 / 16.0)
 
@@ -333,10 +335,11 @@ def filter_proposals(heads, anchor_generator, image_size, pre_nms_top_n: int = 1
     return res
 
 
-class RegionProposalNetwork:
+class RegionProposalNetwork(Handle):
     """rn_rpn_*: torchvision's RegionProposalNetwork in eval mode on the device: RPNHead's two contractions per level,
     then select + decode, the IoU mask and scan + merge -- 2 L + 3 launches.  state holds the head's tensors
     (split_state normalises the keys); the anchor generator has one entry per level the network reads."""
+    DESTROY = "rn_rpn_destroy"
 
     def __init__(self, in_channels: int, anchor_generator: AnchorGenerator, state, pre_nms_top_n: int = 1000,
                  post_nms_top_n: int = 1000, nms_thresh: float = 0.7, score_thresh: float = 0.0, min_size: float = 1e-3,
@@ -357,12 +360,7 @@ class RegionProposalNetwork:
                                       self.base.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), "rn_rpn_create", self.ctx.handle)
         self.handle = h
         mine, _ = split_state(state)
-        for key, shape in head_shapes(self.in_channels, self.A).items():
-            arr = np.ascontiguousarray(mine[key], dtype=F)
-            assert arr.size == int(np.prod(shape)), (key, arr.shape, shape)
-            L.check(L.lib().rn_rpn_set_tensor(h, key.encode(), arr.ctypes.data, arr.size), f"rn_rpn_set_tensor({key})",
-                    self.ctx.handle)
-        L.check(L.lib().rn_rpn_finalize(h), "rn_rpn_finalize", self.ctx.handle)
+        L.set_tensors(h, "rn_rpn", self.ctx, head_shapes(self.in_channels, self.A), mine)
 
     def buffers(self, B: int, candidates: bool = False):
         """device buffers of a forward of B images: (spec, buffers) with spec name -> (dtype, shape)"""
@@ -420,15 +418,3 @@ class RegionProposalNetwork:
                                        ctypes.byref(req)), "rn_rpn_forward", self.ctx.handle)
         self.ctx.sync()
         return self.collect(spec, bufs)
-
-    def close(self) -> None:
-        if self.handle:
-            from . import _lib as L
-            L.lib().rn_rpn_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -151,11 +151,12 @@ def fcn_head_ref(x_nchw_f64, state, size, round_fn=None) -> np.ndarray:
 # ---------------------------------------------------------------------------
 # the device head
 # ---------------------------------------------------------------------------
-class FCNHead:
+class FCNHead(L.Handle):
     """rn_seg_head_*: FCNHead(in_channels, classes) with mid = in_channels // 4 on the device; state holds
     torchvision's seven tensors (HEAD_KEYS).  dtype "f32" or "bf16": storage of the input map, the mid tensor and
     the weight panels; the coarse scores and the outputs are fp32 either way.  mid_channels: another width than
     torchvision's in_channels // 4."""
+    DESTROY = "rn_seg_head_destroy"
 
     def __init__(self, in_channels: int, classes: int, state: Dict[str, np.ndarray], dtype: str = "f32", ctx=None,
                  mid_channels: Optional[int] = None):
@@ -177,12 +178,7 @@ class FCNHead:
         self.handle = h
         L.check(lib.rn_seg_head_set_dtype(h, {"f32": L.RN_DTYPE_F32, "bf16": L.RN_DTYPE_BF16}[dtype]),
                 "rn_seg_head_set_dtype", self.ctx.handle)
-        for key, shape in shapes.items():
-            arr = np.ascontiguousarray(state[key], dtype=np.float32)
-            assert arr.size == int(np.prod(shape)), (key, arr.shape, shape)
-            L.check(lib.rn_seg_head_set_tensor(h, key.encode(), arr.ctypes.data, arr.size),
-                    f"rn_seg_head_set_tensor({key})", self.ctx.handle)
-        L.check(lib.rn_seg_head_finalize(h), "rn_seg_head_finalize", self.ctx.handle)
+        L.set_tensors(h, "rn_seg_head", self.ctx, shapes, state)
 
     def forward(self, x_nhwc, size, scores: bool = True, labels: bool = False):
         """x_nhwc: host array [B,h,w,in_channels] fp32 (a bf16 head rounds it on upload; uint16 bf16 bit patterns
@@ -207,17 +203,6 @@ class FCNHead:
         s = _down_raw(ds, np.float32, B * self.classes * H * W).reshape(B, self.classes, H, W) if scores else None
         lb = _down_raw(dl, np.uint8, B * H * W).reshape(B, H, W) if labels else None
         return s, lb
-
-    def close(self) -> None:
-        if self.handle:
-            L.lib().rn_seg_head_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---------------------------------------------------------------------------

@@ -199,7 +199,8 @@ def test_head_refusals():
 
 
 # =====================================================================================================================
-# 4b. the head's bookkeeping: padding in its general form, scratch growth, a tensor set twice
+# 4b. the head's bookkeeping: padding in its general form (scratch growth and a tensor set twice: every kind of object
+#     shares that code, test_stage_objects_gpu.py)
 # =====================================================================================================================
 PAD_SEED = 2   # the float64 reference labels of this seed hold all three classes, fp32 and bf16 (17, 14 and 32 pixels)
 
@@ -238,63 +239,6 @@ def small_head(kind, dtype="f32", rates=(1, 2)):
     rates_c = (ctypes.c_uint64 * len(rates))(*rates)
     return ((lambda: S.DeepLabHead(64, 5, st, aspp_channels=64, rates=rates, dtype=dtype)), st,
             S.deeplab_head_shapes(64, 5, 64, rates), "rn_seg_head_create_deeplab", (64, 5, len(rates), rates_c))
-
-
-@pytest.mark.parametrize("kind", ["fcn", "deeplab"])
-def test_scratch_growth_keeps_the_bits(kind):
-    """one head on (1, 2, 2), then (2, 4, 3), then (1, 2, 2) again -- its scratch grows in pixels and in images, then
-    is larger than needed: every result is, bit for bit, that of a fresh head on the same input"""
-    make = small_head(kind)[0]
-    head = make()
-    try:
-        for i, bhw in enumerate(((1, 2, 2), (2, 4, 3), (1, 2, 2))):
-            x = np.random.default_rng(40 + i).standard_normal(bhw + (64,), dtype=np.float32)
-            size = (2 * bhw[1] + 1, 3 * bhw[2])
-            fresh = make()
-            try:
-                want_s, want_l = fresh.forward(x, size, scores=True, labels=True)
-            finally:
-                fresh.close()
-            got_s, got_l = head.forward(x, size, scores=True, labels=True)
-            assert np.array_equal(bits(got_s), bits(want_s)) and np.array_equal(got_l, want_l), (kind, i, bhw)
-    finally:
-        head.close()
-
-
-@pytest.mark.parametrize("kind,dtype,twice", [
-    ("fcn", "f32", ("classifier.0.weight", "classifier.1.running_var")),
-    ("deeplab", "bf16", ("classifier.0.convs.1.0.weight",))], ids=["fcn", "deeplab"])
-def test_tensor_set_twice(kind, dtype, twice):
-    """garbage under a key, then the right values, before finalize: the bits of a head that was set once.  DeepLab:
-    bf16 on a 2 x 2 map with rates (2, 3), where both dilated branches run on their centre tap, so a centre-tap copy
-    of the garbage would show"""
-    make, st, shapes, create, args = small_head(kind, dtype, rates=(2, 3))
-    x = np.random.default_rng(50).standard_normal((1, 2, 2, 64), dtype=np.float32)
-    size = (5, 6)
-    once = make()
-    try:
-        want_s, want_l = once.forward(x, size, scores=True, labels=True)
-    finally:
-        once.close()
-    lib, ctx = L.lib(), R.get_ctx()
-    h = ctypes.c_void_p()
-    assert getattr(lib, create)(ctx.handle, ctypes.byref(h), 64, *args) == L.RN_OK
-    try:
-        assert lib.rn_seg_head_set_dtype(h, {"f32": L.RN_DTYPE_F32, "bf16": L.RN_DTYPE_BF16}[dtype]) == L.RN_OK
-        for key in shapes:
-            right = np.ascontiguousarray(st[key], dtype=np.float32)
-            for data in ([np.full(right.size, 1e3, np.float32)] if key in twice else []) + [right]:
-                assert lib.rn_seg_head_set_tensor(h, key.encode(), data.ctypes.data, data.size) == L.RN_OK, key
-        assert lib.rn_seg_head_finalize(h) == L.RN_OK
-        vi = V.place(ops.to_bf16_bits(x).reshape(x.shape) if dtype == "bf16" else x)
-        vs, vl = V.place_out(5 * size[0] * size[1] * 4), V.place_out(size[0] * size[1])
-        assert lib.rn_seg_head_forward(h, vi.ptr, 1, 2, 2, size[0], size[1], vs.ptr, vl.ptr) == L.RN_OK
-        ctx.sync()
-        got_s = V.fetch(vs, np.float32, kind, written=True).reshape(want_s.shape)
-        got_l = V.fetch(vl, np.uint8, kind, written=True).reshape(want_l.shape)
-    finally:
-        lib.rn_seg_head_destroy(h)
-    assert np.array_equal(bits(got_s), bits(want_s)) and np.array_equal(got_l, want_l)
 
 
 # =====================================================================================================================

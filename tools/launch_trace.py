@@ -5,6 +5,7 @@ comparison of two such traces.
     rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 tools/launch_trace.py        (once per library:
                                                                                                RN_HIP_LIB selects it)
     python tools/launch_trace.py --compare PARENT_DIR THIS_DIR > launch_trace_parent_against_this.txt
+    python tools/launch_trace.py --compare-counts PARENT_DIR THIS_DIR       (the same lines as often, in any order)
 
 The run: every convolution shape of ResNet-50 at 224 x 224 (the stem in its small-Cin and exact-K forms, the 1x1
 and 3x3 layers, the downsample layers alone and fused into conv3 as a pair) at B = 256 and B = 1, fp32 and bf16,
@@ -106,5 +107,22 @@ def compare(a_dir, b_dir):
     return 1 if ndiff else 0
 
 
+def compare_counts(a_dir, b_dir):
+    """the same (kernel name, grid, workgroup) lines the same number of times, whatever their order: for two builds that
+    issue the same launches but queue a model's uploads and packs at another moment"""
+    from collections import Counter
+    a, b = Counter(trace(a_dir)), Counter(trace(b_dir))
+    wrong = sorted(k for k in set(a) | set(b) if a[k] != b[k])
+    print(f"launches of the parent's library: {sum(a.values())}; of this one: {sum(b.values())}")
+    print(f"distinct (name, grid, workgroup) lines: {len(a)} / {len(b)}; kernels: {len(set(l.split(' grid ')[0] for l in a))} / "
+          f"{len(set(l.split(' grid ')[0] for l in b))}")
+    print(f"lines whose count differs: {len(wrong)}")
+    for k in wrong[:10]:
+        print(f"  parent {a[k]}, this {b[k]}: {k}")
+    return 1 if wrong else 0
+
+
 if __name__ == "__main__":
-    sys.exit(compare(sys.argv[2], sys.argv[3]) if len(sys.argv) > 1 and sys.argv[1] == "--compare" else run())
+    if len(sys.argv) > 1 and sys.argv[1] in ("--compare", "--compare-counts"):
+        sys.exit((compare if sys.argv[1] == "--compare" else compare_counts)(sys.argv[2], sys.argv[3]))
+    sys.exit(run())
