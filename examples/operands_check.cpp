@@ -109,6 +109,48 @@ int main()
         box[2].ptr = p + 800;  // an output of the box head inside the probabilities
         EXPECT(rn_operand_groups_clash(g, 6, &a, &b) && a == &mask[2] && b == &box[2]);
     }
+    // the seventh group: a keypoint head's request behind the mask head's (or without one: an empty sixth group)
+    {
+        const rn_operand maps[] = {{p, 64, "x[0]", 0, 0}};
+        const rn_operand levels[] = {{nullptr, 64, "level[0]", 1, 0}};
+        const rn_operand roi[] = {{p + 64, 64, "pooled", 1, 0}, {nullptr, 8, "levels_out", 1, 0}, {nullptr, 40, "rois_dev", 0, 0}};
+        const rn_operand rpn[] = {{p + 128, 32, "out.boxes", 1, 0}, {p + 160, 40, "out.rois", 1, 0}};
+        const rn_operand box[] = {{p + 256, 64, "out.boxes", 1, 0}, {p + 320, 16, "out.labels", 1, 0}, {nullptr, 16, "out.scores", 1, 0}};
+        rn_operand mask[] = {{p + 512, 80, "mask.rois", 1, 0}, {nullptr, 256, "mask.pooled", 1, 0}, {p + 768, 256, "mask.probs", 1, 0},
+                             {p + 1024, 1024, "mask.masks", 1, 0}, {p + 2048, 256, "mask.bits", 1, 1}};
+        rn_operand kp[] = {{p + 2304, 80, "keypoint.rois", 1, 0}, {nullptr, 256, "keypoint.pooled", 1, 0},
+                           {p + 2560, 768, "keypoint.heat", 1, 0}, {p + 3328, 144, "keypoint.keypoints", 1, 0},
+                           {p + 3472, 48, "keypoint.scores", 1, 0}};
+        rn_operand_group g[7] = {{maps, 1}, {levels, 1}, {roi, 3}, {rpn, 2}, {box, 3}, {mask, 5}, {kp, 5}};
+        const rn_operand *a = nullptr, *b = nullptr;
+        EXPECT(rn_operands_misaligned(kp, 5) == -1 && rn_operands_clash(kp, 5, &with) == -1);
+        EXPECT(!rn_operand_groups_clash(g, 7, &a, &b));
+        kp[4].ptr = p + 3468;  // the scores over the last keypoint: the stage's own list answers
+        EXPECT(rn_operands_clash(kp, 5, &with) == 3 && with == 4);
+        kp[4].ptr = p + 3474;
+        EXPECT(rn_operands_misaligned(kp, 5) == 4);
+        kp[4].ptr = p + 3472;
+        kp[2].ptr = p + 2300;  // the heat maps over the last byte of the mask's bits
+        EXPECT(rn_operand_groups_clash(g, 7, &a, &b) && a == &kp[2] && b == &mask[4]);
+        kp[2].ptr = p + 2560;
+        kp[3].ptr = box[0].ptr;  // the keypoints on the detections the stage reads
+        EXPECT(rn_operand_groups_clash(g, 7, &a, &b) && a == &kp[3] && b == &box[0]);
+        kp[3].ptr = p + 3328;
+        kp[0].ptr = p + 335;  // the RoI rows over the last byte of the labels
+        EXPECT(rn_operand_groups_clash(g, 7, &a, &b) && a == &kp[0] && b == &box[1]);
+        kp[0].ptr = mask[0].ptr;  // the two heads' RoI rows are two outputs: they may not be one buffer
+        EXPECT(rn_operand_groups_clash(g, 7, &a, &b) && a == &kp[0] && b == &mask[0]);
+        g[5].n = 0;  // no mask head: its request is in nobody's way
+        EXPECT(!rn_operand_groups_clash(g, 7, &a, &b));
+        g[5].n = 5;
+        kp[0].ptr = p + 2304;
+        kp[2].ptr = nullptr;  // not wanted: in nobody's way
+        mask[3].ptr = p + 2600;
+        mask[3].bytes = 64;
+        EXPECT(!rn_operand_groups_clash(g, 7, &a, &b));
+        kp[3].ptr = p;  // the keypoints over an input map of the family
+        EXPECT(rn_operand_groups_clash(g, 7, &a, &b) && a == &kp[3] && b == &maps[0]);
+    }
     std::free(mem);
     std::printf(failures ? "%d expectations failed\n" : "operands_check: every expectation holds\n", failures);
     return failures ? 1 : 0;

@@ -1390,6 +1390,114 @@ RN_API int rn_model_forward_masks_u8(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, rn_b
                                      const uint8_t *input_nhwc, uint64_t B, const rn_model_outputs *outs, const int *stages,
                                      const rn_fpn_outputs *fpn_out, const rn_rpn_request *req, const rn_roi_pool *rois,
                                      const rn_detect_request *det_req, const rn_mask_request *mask_req, int mode);
+
+/* ---- The keypoint head behind the box head: convs, 4x4 deconv, bicubic argmax (rn_keypoint.hip) -------------------------
+ * torchvision's keypoint branch of RoIHeads in eval mode: keypoint_roi_pool on the DETECTED boxes, KeypointRCNNHeads (3x3
+ * convolutions with bias and ReLU), KeypointRCNNPredictor (kps_score_lowres, a ConvTranspose2d(., Kp, 4, 2, 1), then
+ * interpolate(scale_factor=2, mode="bilinear", align_corners=False)), keypointrcnn_inference / heatmaps_to_keypoints.  fp32
+ * only, like the box and mask heads.  Every entry point is asynchronous on the context's stream, allocates and uploads
+ * nothing at forward time (the object's scratch aside), uses no atomics, and refuses with RN_ERR_INVALID -- nothing
+ * launched, rn_last_error names the operand -- a NULL operand, an operand off its boundary, an output sharing a byte with
+ * another operand, a size out of range; K == 0 is RN_OK with nothing launched.
+ *
+ * The transposed convolution is ONE 1x1 panel of 16*Kp channels: with W [Cin, Kp, 4, 4] in torch's layout, the panel's row
+ * k*16 + ky*4 + kx is W[:, k, ky, kx], no shift, no ReLU, and its output t [K, M, M, 16*Kp] holds the products only (the
+ * 16 taps of one keypoint: 64 contiguous bytes of a pixel).  Kernel 4 at stride 2 overlaps: the overlap-add is the predict
+ * launch's.
+ *
+ * rn_keypoint_predict_forward: t (16-byte aligned), bias [Kp], boxes [K, 4], labels [K] int32 or NULL (all valid), M 1..16,
+ * Kp 1..256, max_h and max_w 1..8192 -> heat [K, Kp, S, S] (S = 4M) and / or keypoints [K, Kp, 3] with scores [K, Kp].
+ * One launch, one block per (detection, keypoint), which reads its 16 columns of t once and forms both maps in LDS; with
+ * heat == NULL no heat map reaches memory.  Not all three outputs may be NULL; keypoints and scores come together; boxes
+ * and labels are read only where keypoints is given.
+ * rn_heatmaps_to_keypoints_forward: the same search (the same device code, the same bits) on a caller's heat
+ * [K, Kp, S, S], S 1..64.
+ *
+ * The arithmetic is a contract; every fp32 operation is rounded on its own, no product fused into an add
+ * (keypoint.heatmaps_ref and keypoint.heatmaps_to_keypoints_ref restate it in numpy; the kernel matches them bit for bit):
+ *   low[oy][ox] (2M x 2M) starts at bias[k] and adds the valid taps t[iy][ix][k*16 + ky*4 + kx], 2 iy = oy + 1 - ky and
+ *     2 ix = ox + 1 - kx, in ascending ky, then ascending kx: at most 2 x 2 of them.
+ *   heat is low resized 2M -> 4M by rn_upsample_bilinear_forward's per-axis rule and sum order (the scale is 0.5).
+ *   w = max(x2 - x1, 1.0f), h likewise; Wr = (int)ceilf(w), Hr = (int)ceilf(h).  A row is OUT when a box coordinate is not
+ *     finite, when Wr > max_w or Hr > max_h, or when its label is below 1 (where labels is given); it answers (0, 0, 0)
+ *     and score 0 for every keypoint.  Nothing a box holds decides how long a launch runs beyond max_h x max_w.
+ *   The bicubic resize S -> n_out per axis, output index o:
+ *     scale = (float)S / (float)n_out                          (one fp32 division, on the device)
+ *     src = fl(fl(scale * fl((float)o + 0.5f)) - 0.5f)          NOT clamped at 0: torch's cubic rule
+ *     i = floorf(src), tt = fl(src - i); the taps i-1 .. i+2, each clamped to [0, S-1]
+ *     with A = -0.75: c0 = ((A*x - 5A)*x + 8A)*x - 4A at x = tt + 1;  c1 = ((A+2)*x - (A+3))*x*x + 1 at x = tt;
+ *                     c2: c1's form at x = 1 - tt;  c3: c0's form at x = 2 - tt
+ *     a row value is ((c0*v0 + c1*v1) + c2*v2) + c3*v3 over the columns; the output is the same expression over the four
+ *     row values (the kernel computes a row value once per (source row, output column): the same operations).
+ *   The argmax over the Hr x Wr values: the lowest flat index y*Wr + x that holds the maximum -- index 0 to start with,
+ *     replaced only where v > best, so a NaN never replaces (torch's argmax would pick it: the one stated deviation) and
+ *     a NaN at index 0 stays.  The result does not depend on the block's thread count.
+ *   x = fl(fl(fl((float)x_int + 0.5f) * fl(w / (float)Wr)) + x1), y likewise; keypoints[k][j] = (x, y, 1.0f),
+ *     scores[k][j] = best.
+ *
+ * The object.  rn_keypoint_head_create(ctx, &kh, in_channels, n_layers (1..8), layer_channels[], keypoints Kp, resolution
+ * M (1..16)); channel counts are multiples of 64.  rn_keypoint_head_set_tensor takes host fp32, keys with or without the
+ * "roi_heads." prefix: keypoint_head.{0,2,4,..}.weight|bias ([c_i, c_{i-1}, 3, 3], [c_i]) and
+ * keypoint_predictor.kps_score_lowres.weight|bias ([c_last, Kp, 4, 4], [Kp]).  rn_keypoint_head_forward: pooled_nhwc
+ * [K, M, M, in_channels] fp32 (16-byte aligned), labels [K] or NULL, boxes [K, 4] (NULL: the request wants heat only),
+ * the image size (max_h, max_w) and the request -> n_layers + 1 contractions (one launch each, or two where the plan
+ * finishes a chunked K sum in a second pass) and ONE predict launch.  Of the request it reads heat, keypoints and scores;
+ * the pooler's parameters, rois and pooled are the route's.  The scratch -- two ping-pong maps and t -- grows on demand,
+ * never on a stream that is being captured and never while a captured graph of the context lives. */
+typedef struct rn_keypoint_request {
+    int n_levels, level[4];            /* the keypoint pooler's levels of the neck, as rn_roi_pool's */
+    int sampling_ratio, aligned;
+    double canonical_scale;            /* 224 */
+    int canonical_level;               /* 4 */
+    float *rois;                       /* [B*D, 5] or NULL */
+    float *pooled;                     /* [B*D, M, M, a] or NULL */
+    float *heat;                       /* [B, D, Kp, 4M, 4M] or NULL */
+    float *keypoints;                  /* [B, D, Kp, 3] or NULL */
+    float *scores;                     /* [B, D, Kp] or NULL */
+} rn_keypoint_request;
+typedef struct rn_keypoint_head rn_keypoint_head;
+RN_API int rn_keypoint_predict_forward(rn_ctx *ctx, const float *t, const float *bias, const float *boxes,
+                                       const int32_t *labels /* nullable */, uint64_t K, uint64_t M, uint64_t Kp, uint64_t max_h,
+                                       uint64_t max_w, float *heat /* nullable */, float *keypoints /* nullable */,
+                                       float *scores /* nullable */);
+RN_API int rn_heatmaps_to_keypoints_forward(rn_ctx *ctx, const float *heat, const float *boxes, const int32_t *labels /* nullable */,
+                                            uint64_t K, uint64_t Kp, uint64_t S, uint64_t max_h, uint64_t max_w, float *keypoints,
+                                            float *scores);
+RN_API int rn_keypoint_head_create(rn_ctx *ctx, rn_keypoint_head **out, uint64_t in_channels, uint64_t n_layers,
+                                   const uint64_t *layer_channels, uint64_t keypoints, uint64_t resolution);
+RN_API int rn_keypoint_head_set_tensor(rn_keypoint_head *kh, const char *key, const float *host_data, uint64_t numel);
+RN_API int rn_keypoint_head_finalize(rn_keypoint_head *kh);
+RN_API int rn_keypoint_head_destroy(rn_keypoint_head *kh);
+RN_API int rn_keypoint_head_forward(rn_keypoint_head *kh, const float *pooled_nhwc, const int32_t *labels /* nullable */,
+                                    const float *boxes /* nullable */, uint64_t K, uint64_t image_h, uint64_t image_w,
+                                    const rn_keypoint_request *req);
+/* The keypoint head behind the neck and inside a forward: rn_fpn_forward_masks' / rn_model_forward_masks(_u8)'s arguments
+ * plus the keypoint head and its request; the mask head and its request may be NULL (torchvision allows both heads at
+ * once).  One more step behind the mask head's ("keypoint_stage" of layer "roi_heads" in the profile, one record per
+ * part).  A part of a launch batch forms the RoIs of its own detection rows, pools them NHWC from its own slice of the
+ * neck's scratch, runs the head and writes its own rows of rois [B*D, 5], pooled [B*D, M, M, a], heat [B, D, Kp, 4M, 4M],
+ * keypoints [B, D, Kp, 3] and scores [B, D, Kp] once; max_h x max_w is the call's image; the values are those of the
+ * stand-alone entry points on the same rows, bit for bit.  Refused like the masks' calls, and: a keypoint head without a
+ * box head, a detect request whose boxes or labels is NULL, a keypoint head whose in_channels is not the neck's
+ * out_channels, a request that wants nothing, an image over 8192 a side, an output of the request sharing a byte with any
+ * other output of the call.  Every other forward kind issues exactly the launches it issued. */
+RN_API int rn_fpn_forward_keypoints(rn_fpn *fpn, rn_rpn *rpn, rn_box_head *bh, rn_mask_head *mh /* nullable */,
+                                    rn_keypoint_head *kh, const void *const *x_nhwc, uint64_t B, const uint64_t *h,
+                                    const uint64_t *w, float *const *out_nchw /* nullable */, uint64_t image_h, uint64_t image_w,
+                                    const rn_rpn_request *req, const rn_roi_pool *rois, const rn_detect_request *det_req,
+                                    const rn_mask_request *mask_req /* nullable */, const rn_keypoint_request *kp_req);
+RN_API int rn_model_forward_keypoints(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, rn_box_head *bh, rn_mask_head *mh /* nullable */,
+                                      rn_keypoint_head *kh, const float *input_nchw, uint64_t B,
+                                      const rn_model_outputs *outs /* nullable */, const int *stages,
+                                      const rn_fpn_outputs *fpn_out /* nullable */, const rn_rpn_request *req,
+                                      const rn_roi_pool *rois, const rn_detect_request *det_req,
+                                      const rn_mask_request *mask_req /* nullable */, const rn_keypoint_request *kp_req, int mode);
+RN_API int rn_model_forward_keypoints_u8(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, rn_box_head *bh, rn_mask_head *mh /* nullable */,
+                                         rn_keypoint_head *kh, const uint8_t *input_nhwc, uint64_t B,
+                                         const rn_model_outputs *outs, const int *stages, const rn_fpn_outputs *fpn_out,
+                                         const rn_rpn_request *req, const rn_roi_pool *rois, const rn_detect_request *det_req,
+                                         const rn_mask_request *mask_req /* nullable */, const rn_keypoint_request *kp_req,
+                                         int mode);
 /* Run one forward, then time every tile candidate of every convolution at batch B on the
  * device (events on the context's stream, on the buffers that forward used) and remember the fastest per layer for
  * that batch size.  Results do not change (candidates are bit-identical), only speed. */

@@ -8,7 +8,7 @@ cheap; the shared library is loaded on first use and its absence is a hard
 error -- there is no CPU fallback.
 """
 from . import weights, preprocess  # noqa: F401  (pure-numpy helpers)
-from . import _lib, tensor, nn, ops, model, segmentation, fpn, roi, rpn, detection, mask  # noqa: F401
+from . import _lib, tensor, nn, ops, model, segmentation, fpn, roi, rpn, detection, mask, keypoint  # noqa: F401
 from ._lib import RnError  # noqa: F401
 from .tensor import Device, Shape, Tensor, FloatTensor, Context, get_ctx, set_device  # noqa: F401
 from .nn import (Conv2d, BatchNorm2d, Pool2d, Linear, reluForward, addForward,  # noqa: F401
@@ -19,5 +19,6 @@ from .roi import MultiScaleRoIAlign, boxes_to_rois, infer_scales, roi_align_f64 
 from .rpn import AnchorGenerator, RegionProposalNetwork  # noqa: F401
 from .detection import BoxHead  # noqa: F401
 from .mask import MaskHead  # noqa: F401
+from .keypoint import KeypointHead  # noqa: F401
 
 __version__ = "0.1.0"

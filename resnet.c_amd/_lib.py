@@ -101,6 +101,15 @@ class MaskRequest(ctypes.Structure):
                 ("pooled", c_void_p), ("probs", c_void_p), ("masks", c_void_p), ("bits", c_void_p)]
 
 
+class KeypointRequest(ctypes.Structure):
+    """rn_keypoint_request: the keypoint pooler's levels and parameters and the outputs rois [B*D,5], pooled [B*D,M,M,a],
+    heat [B,D,Kp,4M,4M], keypoints [B,D,Kp,3] and scores [B,D,Kp] (any may be NULL, not all of the last three; keypoints
+    and scores come together)"""
+    _fields_ = [("n_levels", c_int), ("level", c_int * 4), ("sampling_ratio", c_int), ("aligned", c_int),
+                ("canonical_scale", c_double), ("canonical_level", c_int), ("rois", c_void_p), ("pooled", c_void_p),
+                ("heat", c_void_p), ("keypoints", c_void_p), ("scores", c_void_p)]
+
+
 class Epilogue(ctypes.Structure):
     _fields_ = [("scale", c_void_p), ("shift", c_void_p), ("residual", c_void_p),
                 ("relu", c_int)]
@@ -327,6 +336,24 @@ SIGNATURES = {
     "rn_model_forward_masks_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, u64, POINTER(ModelOutputs),
                                           POINTER(c_int), POINTER(FpnOutputs), POINTER(RpnRequest), POINTER(RoiPool),
                                           POINTER(DetectRequest), POINTER(MaskRequest), c_int]),
+    "rn_keypoint_predict_forward": (c_int, [c_void_p, fptr, fptr, fptr, fptr, u64, u64, u64, u64, u64, fptr, fptr, fptr]),
+    "rn_heatmaps_to_keypoints_forward": (c_int, [c_void_p, fptr, fptr, fptr, u64, u64, u64, u64, u64, fptr, fptr]),
+    "rn_keypoint_head_create": (c_int, [c_void_p, POINTER(c_void_p), u64, u64, POINTER(u64), u64, u64]),
+    "rn_keypoint_head_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, u64]),
+    "rn_keypoint_head_finalize": (c_int, [c_void_p]),
+    "rn_keypoint_head_destroy": (c_int, [c_void_p]),
+    "rn_keypoint_head_forward": (c_int, [c_void_p, fptr, fptr, fptr, u64, u64, u64, POINTER(KeypointRequest)]),
+    "rn_fpn_forward_keypoints": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), u64, POINTER(u64),
+                                         POINTER(u64), POINTER(c_void_p), u64, u64, POINTER(RpnRequest), POINTER(RoiPool),
+                                         POINTER(DetectRequest), POINTER(MaskRequest), POINTER(KeypointRequest)]),
+    "rn_model_forward_keypoints": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, fptr, u64,
+                                           POINTER(ModelOutputs), POINTER(c_int), POINTER(FpnOutputs), POINTER(RpnRequest),
+                                           POINTER(RoiPool), POINTER(DetectRequest), POINTER(MaskRequest),
+                                           POINTER(KeypointRequest), c_int]),
+    "rn_model_forward_keypoints_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, u64,
+                                              POINTER(ModelOutputs), POINTER(c_int), POINTER(FpnOutputs), POINTER(RpnRequest),
+                                              POINTER(RoiPool), POINTER(DetectRequest), POINTER(MaskRequest),
+                                              POINTER(KeypointRequest), c_int]),
     "rn_model_destroy": (c_int, [c_void_p]),
     "rn_model_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, u64]),
     "rn_model_load_dir": (c_int, [c_void_p, c_char_p]),

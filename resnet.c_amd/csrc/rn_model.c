@@ -2030,6 +2030,32 @@ int rn_model_forward_masks_u8(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, rn_box_head
     return forward_fpn(m, "rn_model_forward_masks", &c, input_nhwc, 1, B, outs, stages, fpn_out, mode);
 }
 
+int rn_model_forward_keypoints(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, rn_box_head *bh, rn_mask_head *mh, rn_keypoint_head *kh,
+                               const float *input_nchw, uint64_t B, const rn_model_outputs *outs, const int *stages,
+                               const rn_fpn_outputs *fpn_out, const rn_rpn_request *req, const rn_roi_pool *rois,
+                               const rn_detect_request *det_req, const rn_mask_request *mask_req, const rn_keypoint_request *kp_req,
+                               int mode)
+{
+    rn_neck_call c = neck_call(fpn, rois, rpn, req, bh, det_req);
+    c.mask_head = mh, c.mask_req = mask_req, c.kp_head = kh, c.kp_req = kp_req;
+    if (m && (!rpn || !req)) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_keypoints: rpn or req is NULL");
+    if (m && !kh) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_keypoints: the keypoint head is NULL");
+    return forward_fpn(m, __func__, &c, input_nchw, 0, B, outs, stages, fpn_out, mode);
+}
+
+int rn_model_forward_keypoints_u8(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, rn_box_head *bh, rn_mask_head *mh, rn_keypoint_head *kh,
+                                  const uint8_t *input_nhwc, uint64_t B, const rn_model_outputs *outs, const int *stages,
+                                  const rn_fpn_outputs *fpn_out, const rn_rpn_request *req, const rn_roi_pool *rois,
+                                  const rn_detect_request *det_req, const rn_mask_request *mask_req,
+                                  const rn_keypoint_request *kp_req, int mode)
+{
+    rn_neck_call c = neck_call(fpn, rois, rpn, req, bh, det_req);
+    c.mask_head = mh, c.mask_req = mask_req, c.kp_head = kh, c.kp_req = kp_req;
+    if (m && (!rpn || !req)) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_keypoints: rpn or req is NULL");
+    if (m && !kh) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_keypoints: the keypoint head is NULL");
+    return forward_fpn(m, "rn_model_forward_keypoints", &c, input_nhwc, 1, B, outs, stages, fpn_out, mode);
+}
+
 /* The decoded-image route resizes to 256 and crops 224 x 224: a model of another size refuses it. */
 static int default_size(const rn_model *m) { return m->H == RN_DEFAULT_SIDE && m->W == RN_DEFAULT_SIDE; }
 

@@ -206,6 +206,30 @@ int rn_mask_head_stage(rn_mask_head *mh, rn_ctx *ctx, uint64_t n_levels, const v
                        uint64_t B, uint64_t D, const float *boxes, const int32_t *labels, uint64_t image_h, uint64_t image_w,
                        const rn_mask_request *req);
 
+/* ---- rn_keypoint.hip: the keypoint head behind the box head (its parameters, units and scratch: rn_stage.hip) ---- */
+/* 1 when the keypoint head is finalized, lives on ctx's device and reads in_channels channels per pooled pixel; *why otherwise */
+int rn_keypoint_head_matches(const rn_keypoint_head *kh, const rn_ctx *ctx, uint64_t in_channels, const char **why);
+/* M: the side of the pooled map the head reads */
+uint64_t rn_keypoint_head_resolution(const rn_keypoint_head *kh);
+/* the object's scratch for `rows` detections; with_pool: the RoI rows and the pooled features of a stage behind a neck too */
+int rn_keypoint_head_reserve(rn_keypoint_head *kh, uint64_t rows, int with_pool);
+/* every refusal that concerns the request's outputs and the shapes alone, for `rows` detections (text in ctx, under fn);
+ * boxes_given: the caller has the boxes the search needs */
+int rn_keypoint_head_check(const rn_keypoint_head *kh, rn_ctx *ctx, const char *fn, const rn_keypoint_request *req, uint64_t rows,
+                           int boxes_given, uint64_t image_h, uint64_t image_w);
+/* the request's 5 outputs for `rows` detections as operands; returns 5 */
+enum { RN_KEYPOINT_HEAD_OPERANDS = 5 };
+int rn_keypoint_head_operands(const rn_keypoint_head *kh, const rn_keypoint_request *req, uint64_t rows,
+                              rn_operand ops[RN_KEYPOINT_HEAD_OPERANDS]);
+/* The stage's launches on ctx for the B images from the caller's image img0 on (D detections each), whose scratch starts
+ * sub0 images into the object's tensors: the RoI former on these images' detection rows, the NHWC pooler on maps[i]
+ * (level i of image img0, h[i] x w[i], fp32), then n_layers + 1 contractions of one or two launches and the predict
+ * launch.  boxes [images*D, 4], labels [images*D] and the request's outputs: the whole call's. */
+int rn_keypoint_head_stage(rn_keypoint_head *kh, rn_ctx *ctx, uint64_t n_levels, const void *const *maps, const uint64_t *h,
+                           const uint64_t *w, const float *scales, const float *thr, uint64_t images, uint64_t sub0, uint64_t img0,
+                           uint64_t B, uint64_t D, const float *boxes, const int32_t *labels, uint64_t image_h, uint64_t image_w,
+                           const rn_keypoint_request *req);
+
 /* ---- rn_fpn.hip: one forward of a neck and what runs behind it, for both entry families ---- */
 /* The description of a call.  It lives on the stack of the entry point that runs it (rn_fpn_forward*, the model's
  * forward_fpn); rn_neck_check fills the second half once and everything after it only reads. */
@@ -220,6 +244,8 @@ typedef struct rn_neck_call {
     const rn_detect_request *det_req;
     rn_mask_head *mask_head;        /* the mask head behind the box head and its request, or NULL */
     const rn_mask_request *mask_req;
+    rn_keypoint_head *kp_head;      /* the keypoint head behind the box head and its request, or NULL */
+    const rn_keypoint_request *kp_req;
     uint64_t image_h, image_w;      /* the image the rpn and the box head clip to */
     uint64_t h[4], w[4];            /* the input levels' maps */
     uint64_t images;                /* the batch of the whole call */
@@ -231,19 +257,20 @@ typedef struct rn_neck_call {
     int layer_runs[4];              /* the 3x3 of the level runs: exported, pooled from, or read by the pooler / the rpn */
     float scales[4], thr[3];        /* the pooler's levels' scales and the thresholds between them */
     float mask_scales[4], mask_thr[3]; /* the mask pooler's */
+    float kp_scales[4], kp_thr[3];     /* the keypoint pooler's */
 } rn_neck_call;
 /* Every refusal the two families share, in one order: the neck, the outputs' alignment, nothing wanted, the pooler's
- * request, the rpn and its request, the box head's conditions and request, the mask head's, then the operand matrix: no
- * output of the exported levels, the pooler, the rpn, the box head, the mask head or `others` (the family's own operands: the model's head outputs,
+ * request, the rpn and its request, the box head's conditions and request, the mask head's, the keypoint head's, then the operand matrix: no
+ * output of the exported levels, the pooler, the rpn, the box head, the mask head, the keypoint head or `others` (the family's own operands: the model's head outputs,
  * the stand-alone family's input maps) may share a byte with an operand of another of these groups -- but for the
  * chained pooler's rois_dev, which IS the rpn's out.rois.  Text in ctx, under the name fn; nothing is launched. */
 int rn_neck_check(rn_neck_call *call, rn_ctx *ctx, const char *fn, const rn_operand *others, int n_others);
-/* the scratch of the neck, the rpn, the box head and the mask head for parts of at most images_at_once images */
+/* the scratch of the neck, the rpn, the box head, the mask head and the keypoint head for parts of at most images_at_once images */
 int rn_neck_reserve(const rn_neck_call *call, uint64_t images_at_once);
 /* The one source of what follows the laterals for a part of B images: returns the number of steps and, for step
  * 0 .. that - 1, its profile name, layer, FLOPs and bytes (any may be NULL; another step only counts).  In order:
  * the top-down steps coarsest first, the 3x3 of every level that runs, the pool, the exports, the rpn's stage, the
- * pooler (the whole call's window, or in the chain the part's own rows), the box head's stage, the mask head's stage. */
+ * pooler (the whole call's window, or in the chain the part's own rows), the box head's stage, the mask head's stage, the keypoint head's stage. */
 int rn_neck_plan(const rn_neck_call *call, uint64_t B, int step, const char **op, const char **layer, double *flops,
                  double *bytes);
 /* launch `step` of rn_neck_plan on ctx for the B images from the caller's image img0 on, whose scratch starts sub0

@@ -151,8 +151,8 @@ def split_detector_state(state) -> dict:
     """A whole fasterrcnn_resnet50_fpn state dict taken apart through the existing split_state's: "backbone" (the keys
     NativeModel reads) and "neck" (fpn.split_state), "rpn" (rpn.split_state) and "box_head" (split_state above); a
     maskrcnn_resnet50_fpn state also gives "mask_head" (mask.split_state) -- an entry that exists only when the state
-    holds such keys"""
-    from . import fpn, mask
+    holds such keys; a keypointrcnn_resnet50_fpn state gives "keypoint_head" (keypoint.split_state) likewise"""
+    from . import fpn, keypoint, mask
     backbone, neck = fpn.split_state(state)
     head, _ = rpn.split_state(state)
     box, _ = split_state(state)
@@ -160,6 +160,9 @@ def split_detector_state(state) -> dict:
     mine, _ = mask.split_state(state)
     if mine:
         out["mask_head"] = mine
+    mine, _ = keypoint.split_state(state)
+    if mine:
+        out["keypoint_head"] = mine
     return out
 
 

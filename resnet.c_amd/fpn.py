@@ -115,14 +115,16 @@ def fpn_ref(maps_nchw_f64, state, extra="pool", round_fn=None) -> Dict[str, np.n
 
 
 class NeckTail:
-    """What runs behind a neck in one forward -- the pooler, the rpn, the box head, the mask head -- for both
-    ``FeaturePyramidNetwork.forward`` and ``NativeModel.forward_fpn``.  Creating one raises the ValueErrors of a bad
-    combination and touches no device; ``build`` makes the device buffers and the ctypes requests; ``entry`` names the
-    entry point of the family that applies ("fpn", "rois", "proposals", "detections" or "masks") and ``requests`` what that one
-    takes behind the levels; ``collect`` adds the results to the forward's dict once the context is synchronised."""
+    """What runs behind a neck in one forward -- the pooler, the rpn, the box head, the mask head, the keypoint head --
+    for both ``FeaturePyramidNetwork.forward`` and ``NativeModel.forward_fpn``.  Creating one raises the ValueErrors of
+    a bad combination and touches no device; ``build`` makes the device buffers and the ctypes requests; ``entry`` names
+    the entry point of the family that applies ("fpn", "rois", "proposals", "detections", "masks" or "keypoints") and
+    ``requests`` what that one takes behind the levels; ``collect`` adds the results to the forward's dict once the
+    context is synchronised."""
 
     def __init__(self, ctx, names, out_channels, B, image_size, rois, pooler, roi_levels, validate, rpn, candidates,
-                 box_head, detect_intermediates, mask_head=None, masks=("probs",), mask_pooled=False):
+                 box_head, detect_intermediates, mask_head=None, masks=("probs",), mask_pooled=False, keypoint_head=None,
+                 keypoints=("keypoints",)):
         if rpn is None and ((rois is None) != (pooler is None) or (rois is not None and image_size is None)):
             raise ValueError("rois, pooler and image_size go together")
         if rpn is not None and (image_size is None or (rois is not None and pooler is None)):
@@ -133,13 +135,17 @@ class NeckTail:
             raise ValueError("box_head needs a pooler that takes the proposals of the same call (no rois)")
         if mask_head is not None and box_head is None:
             raise ValueError("mask_head needs a box_head (and its rpn and pooler)")
+        if keypoint_head is not None and box_head is None:
+            raise ValueError("keypoint_head needs a box_head (and its rpn and pooler)")
         self.mask_head, self.masks, self.mask_pooled = mask_head, tuple(masks), bool(mask_pooled)
+        self.keypoint_head, self.keypoints = keypoint_head, tuple(keypoints)
         self.ctx, self.names, self.a, self.B, self.image_size = ctx, names, int(out_channels), int(B), image_size
         self.rois, self.pooler, self.roi_levels, self.validate = rois, pooler, roi_levels, validate
         self.rpn, self.candidates, self.box_head, self.detect_intermediates = rpn, candidates, box_head, detect_intermediates
-        self.entry = ("masks" if mask_head is not None else "detections" if box_head is not None else "proposals" if rpn is not None else
+        self.entry = ("keypoints" if keypoint_head is not None else "masks" if mask_head is not None else
+                      "detections" if box_head is not None else "proposals" if rpn is not None else
                       "rois" if pooler is not None else "fpn")
-        self.req = self.rreq = self.dreq = self.mreq = None
+        self.req = self.rreq = self.dreq = self.mreq = self.kreq = None
 
     def build(self) -> None:
         from . import roi as R
@@ -164,14 +170,18 @@ class NeckTail:
             self.mspec, self.mbufs = self.mask_head.buffers(self.B, self.box_head.detections_per_img, self.image_size, self.masks,
                                                             rois=True, pooled=self.mask_pooled)
             self.mreq = self.mask_head.request(self.mbufs, self.names)
+        if self.keypoint_head is not None:
+            self.kspec, self.kbufs = self.keypoint_head.buffers(self.B, self.box_head.detections_per_img, self.keypoints)
+            self.kreq = self.keypoint_head.request(self.kbufs, self.names)
 
     @property
     def requests(self) -> tuple:
-        """The arguments of ``entry`` behind the levels, in the C order: req, rois, det_req, mask_req."""
+        """The arguments of ``entry`` behind the levels, in the C order: req, rois, det_req, mask_req, kp_req."""
         ref = lambda r: ctypes.byref(r) if r is not None else None  # noqa: E731
         return {"fpn": (), "rois": (ref(self.req),), "proposals": (ref(self.rreq), ref(self.req)),
                 "detections": (ref(self.rreq), ref(self.req), ref(self.dreq)),
-                "masks": (ref(self.rreq), ref(self.req), ref(self.dreq), ref(self.mreq))}[self.entry]
+                "masks": (ref(self.rreq), ref(self.req), ref(self.dreq), ref(self.mreq)),
+                "keypoints": (ref(self.rreq), ref(self.req), ref(self.dreq), ref(self.mreq), ref(self.kreq))}[self.entry]
 
     def collect(self, out: dict) -> dict:
         from .ops import _down_raw
@@ -189,6 +199,8 @@ class NeckTail:
             out.update(self.box_head.collect(self.dspec, self.dbufs))
         if self.mask_head is not None:
             out.update(self.mask_head.collect(self.mspec, self.mbufs))
+        if self.keypoint_head is not None:
+            out.update(self.keypoint_head.collect(self.kspec, self.kbufs))
         return out
 
 
@@ -231,7 +243,7 @@ class FeaturePyramidNetwork(L.Handle):
     def forward(self, maps_nhwc, levels=None, *, rois=None, pooler=None, image_size=None, roi_levels: bool = False,
                 validate: bool = True, rpn=None, candidates: bool = False, box_head=None,
                 detect_intermediates: bool = False, mask_head=None, masks=("probs",),
-                mask_pooled: bool = False) -> Dict[str, np.ndarray]:
+                mask_pooled: bool = False, keypoint_head=None, keypoints=("keypoints",)) -> Dict[str, np.ndarray]:
         """maps_nhwc: one host array [B,h_i,w_i,in_i] fp32 per level, finest first (a bf16 neck rounds them on upload;
         uint16 bf16 bit patterns are taken as they are) -> {"0": [B,a,h_0,w_0] fp32, ..., "pool": ...}, the names in
         `levels` only (default: all).  With rois ([K,5] fp32: image index, x1, y1, x2, y2 in pixels of the input image),
@@ -246,7 +258,10 @@ class FeaturePyramidNetwork(L.Handle):
         "detections" and "detection_rois" (and the intermediates with detect_intermediates).  With mask_head
         (mask.MaskHead) behind that box head: rn_fpn_forward_masks, which adds "mask_rois" [B*D,5] and, as `masks` names
         them ("probs", "image", "bits"), "mask_probs" [B,D,2M,2M], "masks" [B,D,H,W] fp32 and "mask_bits" [B,D,H,W] uint8
-        (and "mask_pooled" [B*D,M,M,a] with mask_pooled).  Synchronous convenience."""
+        (and "mask_pooled" [B*D,M,M,a] with mask_pooled).  With keypoint_head (keypoint.KeypointHead) behind that box
+        head, with or without a mask head: rn_fpn_forward_keypoints, which adds, as `keypoints` names them ("keypoints",
+        "heatmaps", "rois", "pooled"), "keypoints" [B,D,Kp,3] with "keypoints_scores" [B,D,Kp], "keypoint_heatmaps"
+        [B,D,Kp,4M,4M], "keypoint_rois" [B*D,5] and "keypoint_pooled" [B*D,M,M,a].  Synchronous convenience."""
         from .ops import _down_raw, _up_raw, to_bf16_bits
         from .tensor import _DeviceBuffer
         n = len(self.in_channels_list)
@@ -256,7 +271,8 @@ class FeaturePyramidNetwork(L.Handle):
             if name not in self.names:
                 raise ValueError(f"unknown level {name!r}: one of {self.names}")
         tail = NeckTail(self.ctx, self.names, self.out_channels, np.shape(maps_nhwc[0])[0], image_size, rois, pooler,
-                        roi_levels, validate, rpn, candidates, box_head, detect_intermediates, mask_head, masks, mask_pooled)
+                        roi_levels, validate, rpn, candidates, box_head, detect_intermediates, mask_head, masks, mask_pooled,
+                        keypoint_head, keypoints)
         xs = []
         for x, c in zip(maps_nhwc, self.in_channels_list):
             x = np.asarray(x)
@@ -280,7 +296,10 @@ class FeaturePyramidNetwork(L.Handle):
         hp, wp = (ctypes.c_uint64 * n)(*hs), (ctypes.c_uint64 * n)(*ws)
         tail.build()
         lib, size = L.lib(), tuple(int(s) for s in image_size) if image_size is not None else ()
-        if tail.entry == "masks":
+        if tail.entry == "keypoints":
+            st = lib.rn_fpn_forward_keypoints(self.handle, rpn.handle, box_head.handle, mask_head.handle if mask_head else None,
+                                              keypoint_head.handle, xp, B, hp, wp, op, *size, *tail.requests)
+        elif tail.entry == "masks":
             st = lib.rn_fpn_forward_masks(self.handle, rpn.handle, box_head.handle, mask_head.handle, xp, B, hp, wp, op, *size,
                                           *tail.requests)
         elif tail.entry == "detections":

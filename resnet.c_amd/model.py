@@ -460,7 +460,7 @@ class NativeModel:
                     features: bool = False, probs: bool = False, topk: int = 0, fused: bool = True, rois=None,
                     pooler=None, roi_levels: bool = False, validate: bool = True, rpn=None, candidates: bool = False,
                     box_head=None, detect_intermediates: bool = False, mask_head=None, masks=("probs",),
-                    mask_pooled: bool = False) -> dict:
+                    mask_pooled: bool = False, keypoint_head=None, keypoints=("keypoints",)) -> dict:
         """One forward with a feature pyramid neck (rn_model_forward_fpn; torchvision's resnet_fpn_backbone): an
         ordered dict "0", "1", .. (one per stage in `stages`, finest first), then "pool" when the neck has the extra
         block -> [B,a,H,W] fp32; then the head outputs asked for, as forward_outputs returns them.  neck: an
@@ -483,7 +483,11 @@ class NativeModel:
         wrote them; with detect_intermediates also "probs", "class_boxes", "valid" and "keep".
         With mask_head (mask.MaskHead) behind that box head: rn_model_forward_masks, which adds "mask_rois" [B*D,5] and,
         as `masks` names them ("probs", "image", "bits"), "mask_probs" [B,D,2M,2M], "masks" [B,D,H,W] fp32 and
-        "mask_bits" [B,D,H,W] uint8 at the model's input size (and "mask_pooled" [B*D,M,M,a] with mask_pooled)."""
+        "mask_bits" [B,D,H,W] uint8 at the model's input size (and "mask_pooled" [B*D,M,M,a] with mask_pooled).
+        With keypoint_head (keypoint.KeypointHead) behind that box head, with or without a mask head:
+        rn_model_forward_keypoints, which adds, as `keypoints` names them ("keypoints", "heatmaps", "rois", "pooled"),
+        "keypoints" [B,D,Kp,3] with "keypoints_scores" [B,D,Kp], "keypoint_heatmaps" [B,D,Kp,4M,4M], "keypoint_rois"
+        [B*D,5] and "keypoint_pooled" [B*D,M,M,a]."""
         from .fpn import NeckTail
         from .ops import _down_raw, _up_raw
         from .tensor import _DeviceBuffer
@@ -503,7 +507,7 @@ class NativeModel:
                 raise ValueError(f"unknown level {name!r}: one of {names}")
         x = np.asarray(x)
         tail = NeckTail(self.ctx, names, neck.out_channels, x.shape[0], self.input_size, rois, pooler, roi_levels, validate,
-                        rpn, candidates, box_head, detect_intermediates, mask_head, masks, mask_pooled)
+                        rpn, candidates, box_head, detect_intermediates, mask_head, masks, mask_pooled, keypoint_head, keypoints)
         u8 = x.dtype == np.uint8
         x = np.ascontiguousarray(x, dtype=np.uint8 if u8 else np.float32)
         self._check_input(x, u8)
@@ -532,10 +536,10 @@ class NativeModel:
         mode = L.RN_FWD_FUSED if fused else L.RN_FWD_REFERENCE_OPS
         stage_arr = (ctypes.c_int * len(idx))(*idx)
         objs = {"fpn": (), "rois": (), "proposals": (rpn,), "detections": (rpn, box_head),
-                "masks": (rpn, box_head, mask_head)}[tail.entry]
+                "masks": (rpn, box_head, mask_head), "keypoints": (rpn, box_head, mask_head, keypoint_head)}[tail.entry]
         name = "rn_model_forward_" + tail.entry
         fn = getattr(L.lib(), name + ("_u8" if u8 else ""))
-        L.check(fn(self.handle, neck.handle, *[obj.handle for obj in objs], xin.ptr, B, ctypes.byref(o), stage_arr,
+        L.check(fn(self.handle, neck.handle, *[obj.handle if obj is not None else None for obj in objs], xin.ptr, B, ctypes.byref(o), stage_arr,
                    ctypes.byref(fo), *tail.requests, mode), name, self.ctx.handle)
         self.ctx.sync()
         shapes.update({"logits": (B, C), "features": (B, F), "probs": (B, C), "topk_prob": (B, k), "topk_idx": (B, k)})

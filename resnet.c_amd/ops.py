@@ -1317,3 +1317,53 @@ def paste_masks(probs, boxes, image_size, labels=None, threshold: float = 0.5, m
     ctx.sync()
     return (_down_raw(dm, np.float32, K * H * W).reshape(K, H, W) if masks else None,
             _down_raw(dbits, np.uint8, K * H * W).reshape(K, H, W) if bits else None)
+
+
+# ---------------------------------------------------------------------------
+# The keypoint head's launch (rn_keypoint.hip); the contracts in numpy are keypoint.py's
+# ---------------------------------------------------------------------------
+def keypoint_predict(t, bias, boxes=None, image_size=None, labels=None, heat: bool = True, keypoints: bool = True):
+    """rn_keypoint_predict_forward, one launch: the panel's output t [K,M,M,16*Kp] fp32 and bias [Kp] -> (heat
+    [K,Kp,4M,4M] or None, keypoints [K,Kp,3] or None, scores [K,Kp] or None); keypoints need boxes [K,4] and image_size =
+    (max_h, max_w); labels [K] int32 or None.  heat bit for bit keypoint.heatmaps_ref, keypoints and scores bit for bit
+    keypoint.heatmaps_to_keypoints_ref on it."""
+    from .tensor import _DeviceBuffer
+    ctx = get_ctx()
+    t = np.ascontiguousarray(t, dtype=np.float32)
+    K, M, _, c16 = t.shape
+    b = np.ascontiguousarray(bias, dtype=np.float32).reshape(-1)
+    Kp = b.size
+    assert t.shape[2] == M and c16 == 16 * Kp, (t.shape, b.shape)
+    S = 4 * M
+    dt, dbias = _up_raw(t), _up_raw(b)
+    dbox = _up_raw(np.ascontiguousarray(boxes, dtype=np.float32).reshape(K, 4)) if boxes is not None else None
+    dl = _up_raw(np.ascontiguousarray(labels, dtype=np.int32).reshape(K)) if labels is not None else None
+    size = image_size if image_size is not None else (1, 1)
+    dh = _DeviceBuffer(ctx, max(K * Kp * S * S * 4, 16)) if heat else None
+    dk = _DeviceBuffer(ctx, max(K * Kp * 12, 16)) if keypoints else None
+    ds = _DeviceBuffer(ctx, max(K * Kp * 4, 16)) if keypoints else None
+    L.check(L.lib().rn_keypoint_predict_forward(ctx.handle, dt.ptr, dbias.ptr, dbox.ptr if dbox else None, dl.ptr if dl else None,
+                                                K, M, Kp, int(size[0]), int(size[1]), dh.ptr if dh else None,
+                                                dk.ptr if dk else None, ds.ptr if ds else None),
+            "rn_keypoint_predict_forward", ctx.handle)
+    ctx.sync()
+    return (_down_raw(dh, np.float32, K * Kp * S * S).reshape(K, Kp, S, S) if heat else None,
+            _down_raw(dk, np.float32, K * Kp * 3).reshape(K, Kp, 3) if keypoints else None,
+            _down_raw(ds, np.float32, K * Kp).reshape(K, Kp) if keypoints else None)
+
+
+def heatmaps_to_keypoints(heat, boxes, image_size, labels=None):
+    """rn_heatmaps_to_keypoints_forward, one launch: heat [K,Kp,S,S] fp32, boxes [K,4], image_size = (max_h, max_w),
+    labels [K] int32 or None -> (keypoints [K,Kp,3], scores [K,Kp]), bit for bit keypoint.heatmaps_to_keypoints_ref."""
+    from .tensor import _DeviceBuffer
+    ctx = get_ctx()
+    x = np.ascontiguousarray(heat, dtype=np.float32)
+    K, Kp, S, _ = x.shape
+    dh, dbox = _up_raw(x), _up_raw(np.ascontiguousarray(boxes, dtype=np.float32).reshape(K, 4))
+    dl = _up_raw(np.ascontiguousarray(labels, dtype=np.int32).reshape(K)) if labels is not None else None
+    dk, ds = _DeviceBuffer(ctx, max(K * Kp * 12, 16)), _DeviceBuffer(ctx, max(K * Kp * 4, 16))
+    L.check(L.lib().rn_heatmaps_to_keypoints_forward(ctx.handle, dh.ptr, dbox.ptr, dl.ptr if dl else None, K, Kp, S,
+                                                     int(image_size[0]), int(image_size[1]), dk.ptr, ds.ptr),
+            "rn_heatmaps_to_keypoints_forward", ctx.handle)
+    ctx.sync()
+    return _down_raw(dk, np.float32, K * Kp * 3).reshape(K, Kp, 3), _down_raw(ds, np.float32, K * Kp).reshape(K, Kp)
