@@ -364,8 +364,10 @@ int rn_fpn_step(rn_fpn *f, rn_ctx *ctx, int kind, int level, const void *x_nhwc,
 
 namespace {
 
-// what follows the exports, after the kinds of rn_fpn_step
+// what follows the exports, after the kinds of rn_fpn_step.  The RoI heads' kinds are NECK_MASK + the head's slot in
+// rn_neck_call (rn_private.h: RN_NECK_*_SLOT): a further head adds its kind here and its slot there, in the same order
 enum { NECK_RPN = RN_FPN_EXPORT + 1, NECK_ROI, NECK_BOX, NECK_MASK, NECK_KEYPOINT };
+static_assert(NECK_MASK + RN_NECK_KEYPOINT_SLOT == NECK_KEYPOINT, "a RoI head's step kind is NECK_MASK + its slot");
 
 constexpr int kRoiOperands = 3;
 
@@ -409,68 +411,45 @@ int rn_fpn_roi_check(rn_neck_call *c, rn_ctx *ctx)
     return RN_OK;
 }
 
-// the pooler of a head's request (who: "mask", "keypoint") against the neck: every refusal that concerns it alone; fills
-// that pooler's scales (formed as rn_fpn_roi_check forms the pooler's) and thresholds
-int neck_head_pool_check(const rn_neck_call *c, rn_ctx *ctx, const char *fn, const char *who, int n_levels, const int *level,
-                         int sampling_ratio, int aligned, double canonical_scale, int canonical_level, const float *pooled,
-                         float *scales, float *thr)
+// the pooler of a RoI head's request against the neck: every refusal that concerns it alone; fills the slot's scales (formed
+// as rn_fpn_roi_check forms the pooler's) and thresholds
+int neck_head_pool_check(const rn_neck_call *c, rn_ctx *ctx, const char *fn, rn_roi_head *s)
 {
     const rn_fpn *f = c->fpn;
+    const rn_roi_pool_view *v = &s->pool;
     const char *why = NULL;
-    if (n_levels < 1 || n_levels > f->n) why = "pooler reads 1 .. n_levels of the neck's levels";
-    for (int i = 0; i < n_levels && !why; ++i)
-        if (level[i] < 0 || level[i] >= f->n || (i > 0 && level[i] <= level[i - 1]))
+    if (v->n_levels < 1 || v->n_levels > f->n) why = "pooler reads 1 .. n_levels of the neck's levels";
+    for (int i = 0; i < v->n_levels && !why; ++i)
+        if (v->level[i] < 0 || v->level[i] >= f->n || (i > 0 && v->level[i] <= v->level[i - 1]))
             why = "pooler's levels must be the neck's (0 .. n_levels - 1, the pool is none), ascending";
-    if (!why && sampling_ratio <= 0)
-        return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "%s: the %s pooler's sampling_ratio <= 0 (adaptive grids) is not carried", fn, who);
-    if (!why && sampling_ratio > 4) why = "pooler's sampling_ratio must be 1..4";
-    if (!why && aligned != 0 && aligned != 1) why = "pooler's aligned must be 0 or 1";
-    if (!why && !(canonical_scale > 0.0)) why = "pooler's canonical_scale must be positive";
-    if (why) return rn_set_error(ctx, RN_ERR_INVALID, "%s: the %s %s", fn, who, why);
-    if ((reinterpret_cast<uintptr_t>(pooled) & 15) != 0)
-        return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s.pooled is off a 16-byte boundary", fn, who);
-    for (int i = 0; i < n_levels; ++i) scales[i] = (float)exp2(rint(log2((double)c->h[level[i]] / (double)c->image_h)));
-    if (rn_roi_level_thresholds((uint64_t)n_levels, scales, canonical_scale, canonical_level, thr) != RN_OK)
-        return rn_set_error(ctx, RN_ERR_INVALID, "%s: the %s pooler's level thresholds cannot be formed", fn, who);
+    if (!why && v->sampling_ratio <= 0)
+        return rn_set_error(ctx, RN_ERR_UNSUPPORTED, "%s: the %s pooler's sampling_ratio <= 0 (adaptive grids) is not carried", fn, s->who);
+    if (!why && v->sampling_ratio > 4) why = "pooler's sampling_ratio must be 1..4";
+    if (!why && v->aligned != 0 && v->aligned != 1) why = "pooler's aligned must be 0 or 1";
+    if (!why && !(v->canonical_scale > 0.0)) why = "pooler's canonical_scale must be positive";
+    if (why) return rn_set_error(ctx, RN_ERR_INVALID, "%s: the %s %s", fn, s->who, why);
+    if ((reinterpret_cast<uintptr_t>(v->pooled) & 15) != 0)
+        return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s.pooled is off a 16-byte boundary", fn, s->who);
+    for (int i = 0; i < v->n_levels; ++i) s->scales[i] = (float)exp2(rint(log2((double)c->h[v->level[i]] / (double)c->image_h)));
+    if (rn_roi_level_thresholds((uint64_t)v->n_levels, s->scales, v->canonical_scale, v->canonical_level, s->thr) != RN_OK)
+        return rn_set_error(ctx, RN_ERR_INVALID, "%s: the %s pooler's level thresholds cannot be formed", fn, s->who);
     return RN_OK;
 }
 
-// level i of a head's pooler for B images read in place sub0 images into the neck's scratch
-int neck_head_maps(const rn_neck_call *c, rn_ctx *ctx, int n_levels, const int *level, uint64_t sub0, uint64_t B, const void **maps,
-                   uint64_t *hs, uint64_t *ws)
+// a RoI head's stage on the 3x3 outputs of B images, read in place sub0 images into the neck's scratch (level i of the
+// head's pooler), on these images' own detection rows
+int neck_head_step(const rn_neck_call *c, rn_ctx *ctx, const rn_roi_head *s, uint64_t sub0, uint64_t img0, uint64_t B)
 {
     const rn_fpn *f = c->fpn;
-    for (int i = 0; i < n_levels; ++i) {
-        const int l = level[i];
+    const void *maps[kFpnMaxLevels];
+    uint64_t hs[kFpnMaxLevels], ws[kFpnMaxLevels];
+    for (int i = 0; i < s->pool.n_levels; ++i) {
+        const int l = s->pool.level[i];
         if ((sub0 + B) * c->h[l] * c->w[l] > f->cap_pix[l]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_fpn: scratch not reserved");
         maps[i] = f->outb[l] + sub0 * c->h[l] * c->w[l] * f->a, hs[i] = c->h[l], ws[i] = c->w[l];
     }
-    return RN_OK;
-}
-
-// the mask head's stage on the 3x3 outputs of B images, read in place sub0 images into the neck's scratch, on these
-// images' own detection rows
-int neck_mask_step(const rn_neck_call *c, rn_ctx *ctx, uint64_t sub0, uint64_t img0, uint64_t B)
-{
-    const rn_mask_request *q = c->mask_req;
-    const void *maps[kFpnMaxLevels];
-    uint64_t hs[kFpnMaxLevels], ws[kFpnMaxLevels];
-    RN_TRY(neck_head_maps(c, ctx, q->n_levels, q->level, sub0, B, maps, hs, ws));
-    return rn_mask_head_stage(c->mask_head, ctx, (uint64_t)q->n_levels, maps, hs, ws, c->mask_scales, c->mask_thr, c->images, sub0,
-                              img0, B, c->det_req->detections_per_img, c->det_req->out.boxes, c->det_req->out.labels, c->image_h,
-                              c->image_w, q);
-}
-
-// the keypoint head's stage, likewise
-int neck_keypoint_step(const rn_neck_call *c, rn_ctx *ctx, uint64_t sub0, uint64_t img0, uint64_t B)
-{
-    const rn_keypoint_request *q = c->kp_req;
-    const void *maps[kFpnMaxLevels];
-    uint64_t hs[kFpnMaxLevels], ws[kFpnMaxLevels];
-    RN_TRY(neck_head_maps(c, ctx, q->n_levels, q->level, sub0, B, maps, hs, ws));
-    return rn_keypoint_head_stage(c->kp_head, ctx, (uint64_t)q->n_levels, maps, hs, ws, c->kp_scales, c->kp_thr, c->images, sub0,
-                                  img0, B, c->det_req->detections_per_img, c->det_req->out.boxes, c->det_req->out.labels,
-                                  c->image_h, c->image_w, q);
+    return rn_roi_head_stage(s, ctx, maps, hs, ws, c->images, sub0, img0, B, c->det_req->detections_per_img, c->det_req->out.boxes,
+                             c->det_req->out.labels, c->image_h, c->image_w);
 }
 
 // The pooler's launch on ctx for the B images from the caller's image img0 on, whose 3x3 outputs start sub0 images
@@ -526,8 +505,8 @@ int neck_step_at(const rn_neck_call *c, int step, int *kind, int *level)
     if (c->rpn) put(NECK_RPN, 0);
     if (c->roi && c->roi->K > 0) put(NECK_ROI, 0);
     if (c->box_head) put(NECK_BOX, 0);
-    if (c->mask_head) put(NECK_MASK, 0);
-    if (c->kp_head) put(NECK_KEYPOINT, 0);
+    for (int i = 0; i < RN_NECK_HEADS; ++i)
+        if (c->head[i].tower) put(NECK_MASK + i, 0);
     return at;
 }
 
@@ -580,56 +559,42 @@ int rn_neck_check(rn_neck_call *c, rn_ctx *ctx, const char *fn, const rn_operand
         if (why) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s", fn, why);
         RN_TRY(rn_box_head_check(c->box_head, ctx, c->det_req, B, c->rpn_req->post_nms_top_n, c->image_h, c->image_w));
     }
-    if (c->mask_head) {  // behind the box head, on the detections it writes
-        if (!c->box_head || !c->det_req) why = "the mask head needs the box head and its request";
-        else if (!c->det_req->out.boxes || !c->det_req->out.labels) why = "the mask head needs boxes and labels of the detect request";
-        else if (!c->mask_req) why = "the mask request is NULL";
-        else rn_mask_head_matches(c->mask_head, ctx, f->a, &why);
-        if (why) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s", fn, why);
-        RN_TRY(rn_mask_head_check(c->mask_head, ctx, fn, c->mask_req, B * c->det_req->detections_per_img, 1, c->image_h, c->image_w));
-        const rn_mask_request *q = c->mask_req;
-        RN_TRY(neck_head_pool_check(c, ctx, fn, "mask", q->n_levels, q->level, q->sampling_ratio, q->aligned, q->canonical_scale,
-                                    q->canonical_level, q->pooled, c->mask_scales, c->mask_thr));
-    }
-    if (c->kp_head) {  // behind the box head, on the detections it writes
-        const rn_keypoint_request *q = c->kp_req;
-        if (!c->box_head || !c->det_req) why = "the keypoint head needs the box head and its request";
-        else if (!c->det_req->out.boxes || !c->det_req->out.labels) why = "the keypoint head needs boxes and labels of the detect request";
-        else if (!q) why = "the keypoint request is NULL";
-        else rn_keypoint_head_matches(c->kp_head, ctx, f->a, &why);
-        if (why) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s", fn, why);
-        RN_TRY(rn_keypoint_head_check(c->kp_head, ctx, fn, q, B * c->det_req->detections_per_img, 1, c->image_h, c->image_w));
-        RN_TRY(neck_head_pool_check(c, ctx, fn, "keypoint", q->n_levels, q->level, q->sampling_ratio, q->aligned, q->canonical_scale,
-                                    q->canonical_level, q->pooled, c->kp_scales, c->kp_thr));
+    for (int i = 0; i < RN_NECK_HEADS; ++i) {  // behind the box head, on the detections it writes
+        rn_roi_head *s = &c->head[i];
+        if (!s->tower) continue;
+        if (!c->box_head || !c->det_req) why = "head needs the box head and its request";
+        else if (!c->det_req->out.boxes || !c->det_req->out.labels) why = "head needs boxes and labels of the detect request";
+        else if (!s->req) why = "request is NULL";
+        else rn_roi_tower_matches(s->tower, ctx, f->a, &why);
+        if (why) return rn_set_error(ctx, RN_ERR_INVALID, "%s: the %s %s", fn, s->who, why);
+        RN_TRY(s->check(s, ctx, fn, B * c->det_req->detections_per_img, 1, c->image_h, c->image_w));
+        RN_TRY(neck_head_pool_check(c, ctx, fn, s));
     }
     c->pool = f->extra && (c->out[n] || c->rpn);
     for (int i = 0; i < n; ++i) c->layer_runs[i] = c->out[i] || (c->pool && i == n - 1) || c->rpn;
     if (rp && rp->K > 0)
         for (int i = 0; i < rp->n_levels; ++i) c->layer_runs[rp->level[i]] = 1;
     // the operand matrix: every group against every group before it
-    operand levels[kFpnMaxLevels + 1], roi[kRoiOperands], rpn[RN_RPN_OPERANDS], box[RN_BOX_HEAD_OPERANDS], mask[RN_MASK_HEAD_OPERANDS];
-    operand kp[RN_KEYPOINT_HEAD_OPERANDS];
+    operand levels[kFpnMaxLevels + 1], roi[kRoiOperands], rpn[RN_RPN_OPERANDS], box[RN_BOX_HEAD_OPERANDS];
+    operand head[RN_NECK_HEADS][RN_ROI_HEAD_OPERANDS];
     for (int i = 0; i < n_out; ++i) levels[i] = {c->out[i], B * f->a * c->hl[i] * c->wl[i] * sizeof(float), level_names[i], true, false};
     if (rp) roi_operands(c, roi);
     if (c->rpn) rn_rpn_operands(c->rpn, c->rpn_req, B, rpn);
     if (c->box_head) rn_box_head_operands(c->box_head, c->det_req, B, c->rpn_req->post_nms_top_n, box);
-    if (c->mask_head) {
-        rn_mask_head_operands(c->mask_head, c->mask_req, B * c->det_req->detections_per_img, c->image_h, c->image_w, mask);
-        RN_TRY(check_operands(ctx, fn, mask, RN_MASK_HEAD_OPERANDS));
-    }
-    if (c->kp_head) {
-        rn_keypoint_head_operands(c->kp_head, c->kp_req, B * c->det_req->detections_per_img, kp);
-        RN_TRY(check_operands(ctx, fn, kp, RN_KEYPOINT_HEAD_OPERANDS));
+    for (int i = 0; i < RN_NECK_HEADS; ++i) {
+        const rn_roi_head *s = &c->head[i];
+        if (!s->tower) continue;
+        s->operands(s, B * c->det_req->detections_per_img, c->image_h, c->image_w, head[i]);
+        RN_TRY(check_operands(ctx, fn, head[i], RN_ROI_HEAD_OPERANDS));
     }
     if (c->chain) roi[2].ptr = NULL;  // the one exception: rois_dev IS the rpn's out.rois, which stands for it below
-    const rn_operand_group groups[7] = {{others, n_others},
+    rn_operand_group groups[5 + RN_NECK_HEADS] = {{others, n_others},
                                         {levels, n_out},
                                         {roi, rp ? kRoiOperands : 0},
                                         {rpn, c->rpn ? RN_RPN_OPERANDS : 0},
-                                        {box, c->box_head ? RN_BOX_HEAD_OPERANDS : 0},
-                                        {mask, c->mask_head ? RN_MASK_HEAD_OPERANDS : 0},
-                                        {kp, c->kp_head ? RN_KEYPOINT_HEAD_OPERANDS : 0}};
-    return check_operand_groups(ctx, fn, groups, 7);
+                                        {box, c->box_head ? RN_BOX_HEAD_OPERANDS : 0}};
+    for (int i = 0; i < RN_NECK_HEADS; ++i) groups[5 + i] = {head[i], c->head[i].tower ? RN_ROI_HEAD_OPERANDS : 0};
+    return check_operand_groups(ctx, fn, groups, 5 + RN_NECK_HEADS);
 }
 
 int rn_neck_reserve(const rn_neck_call *c, uint64_t images_at_once)
@@ -637,8 +602,8 @@ int rn_neck_reserve(const rn_neck_call *c, uint64_t images_at_once)
     RN_TRY(rn_fpn_reserve(c->fpn, images_at_once, c->h, c->w));
     if (c->rpn) RN_TRY(rn_rpn_reserve(c->rpn, images_at_once, c->hl, c->wl, c->rpn_req->pre_nms_top_n));
     if (c->box_head) RN_TRY(rn_box_head_reserve(c->box_head, images_at_once, c->rpn_req->post_nms_top_n));
-    if (c->mask_head) RN_TRY(rn_mask_head_reserve(c->mask_head, images_at_once * c->det_req->detections_per_img, 1));
-    if (c->kp_head) RN_TRY(rn_keypoint_head_reserve(c->kp_head, images_at_once * c->det_req->detections_per_img, 1));
+    for (int i = 0; i < RN_NECK_HEADS; ++i)
+        if (c->head[i].tower) RN_TRY(rn_roi_tower_reserve(c->head[i].tower, images_at_once * c->det_req->detections_per_img, 1));
     return RN_OK;
 }
 
@@ -673,16 +638,11 @@ int rn_neck_plan(const rn_neck_call *c, uint64_t B, int step, const char **op, c
         name = "box_stage", lay = "roi_heads";
         by = (double)(B * post * (c->a * rp->PH * rp->PW)) * 4.0;
         break;
-    case NECK_MASK: {  // the RoI former, the pooler, the contractions, the predict and the paste under one record
-        const uint64_t M = rn_mask_head_resolution(c->mask_head);
-        name = "mask_stage", lay = "roi_heads";
-        by = (double)(B * c->det_req->detections_per_img * M * M * c->a) * 4.0;
-        break;
-    }
-    case NECK_KEYPOINT: {  // the RoI former, the pooler, the contractions and the predict launch under one record
-        const uint64_t M = rn_keypoint_head_resolution(c->kp_head);
-        name = "keypoint_stage", lay = "roi_heads";
-        by = (double)(B * c->det_req->detections_per_img * M * M * c->a) * 4.0;
+    case NECK_MASK:      // the RoI former, the pooler, the contractions and the head's own launches (the mask head's predict
+    case NECK_KEYPOINT: {  // and paste, the keypoint head's predict) under one record
+        const rn_roi_head *s = &c->head[kind - NECK_MASK];
+        name = s->stage, lay = "roi_heads";
+        by = (double)(B * c->det_req->detections_per_img * s->tower->M * s->tower->M * c->a) * 4.0;
         break;
     }
     default:
@@ -713,8 +673,8 @@ int rn_neck_step(const rn_neck_call *c, rn_ctx *ctx, int step, uint64_t sub0, ui
         return rn_box_head_step(c->box_head, ctx, rp->pooled + row0 * feat, rp->rois_dev + row0 * 5, sub0, img0, B, post,
                                 c->image_h, c->image_w, c->det_req);
     }
-    case NECK_MASK: return neck_mask_step(c, ctx, sub0, img0, B);
-    case NECK_KEYPOINT: return neck_keypoint_step(c, ctx, sub0, img0, B);
+    case NECK_MASK:
+    case NECK_KEYPOINT: return neck_head_step(c, ctx, &c->head[kind - NECK_MASK], sub0, img0, B);
     case RN_FPN_EXPORT:  // into the caller's buffer from image img0 on
         return rn_fpn_step(c->fpn, ctx, kind, level, NULL, sub0, B, c->h, c->w, c->out[level] + img0 * c->a * c->hl[level] * c->wl[level]);
     default: return rn_fpn_step(c->fpn, ctx, kind, level, NULL, sub0, B, c->h, c->w, NULL);
@@ -817,7 +777,8 @@ int rn_fpn_forward_masks(rn_fpn *f, rn_rpn *rpn, rn_box_head *bh, rn_mask_head *
 {
     rn_neck_call c = {};
     c.fpn = f, c.out = out_nchw, c.images = B, c.roi = rois, c.rpn = rpn, c.rpn_req = req, c.image_h = image_h, c.image_w = image_w;
-    c.box_head = bh, c.det_req = det_req, c.mask_head = mh, c.mask_req = mask_req;
+    c.box_head = bh, c.det_req = det_req;
+    rn_mask_head_slot(mh, mask_req, &c.head[RN_NECK_MASK_SLOT]);
     if (f && (!rpn || !req)) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: rpn or req is NULL", __func__);
     if (f && !mh) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: the mask head is NULL", __func__);
     return fpn_forward(__func__, &c, x_nhwc, h, w);
@@ -830,7 +791,8 @@ int rn_fpn_forward_keypoints(rn_fpn *f, rn_rpn *rpn, rn_box_head *bh, rn_mask_he
 {
     rn_neck_call c = {};
     c.fpn = f, c.out = out_nchw, c.images = B, c.roi = rois, c.rpn = rpn, c.rpn_req = req, c.image_h = image_h, c.image_w = image_w;
-    c.box_head = bh, c.det_req = det_req, c.mask_head = mh, c.mask_req = mask_req, c.kp_head = kh, c.kp_req = kp_req;
+    c.box_head = bh, c.det_req = det_req;
+    rn_mask_head_slot(mh, mask_req, &c.head[RN_NECK_MASK_SLOT]), rn_keypoint_head_slot(kh, kp_req, &c.head[RN_NECK_KEYPOINT_SLOT]);
     if (f && (!rpn || !req)) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: rpn or req is NULL", __func__);
     if (f && !kh) return rn_set_error(f->ctx, RN_ERR_INVALID, "%s: the keypoint head is NULL", __func__);
     return fpn_forward(__func__, &c, x_nhwc, h, w);

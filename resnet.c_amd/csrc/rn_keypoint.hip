@@ -281,32 +281,19 @@ int rn_heatmaps_to_keypoints_forward(rn_ctx *ctx, const float *heat, const float
     return keypoint_launch(ctx, NULL, NULL, heat, boxes, labels, K, 0, Kp, S, max_h, max_w, NULL, keypoints, scores, __func__);
 }
 
-// ---- the object: KeypointRCNNHeads and kps_score_lowres in front of the predict launch ----------------------------
-enum { kKpMaxLayers = 8, kKpRows = 0, kKpPool = 1, kKpScratch = 5 };
-
+// ---- the object: KeypointRCNNHeads (the RoI tower of rn_stage.hip) and kps_score_lowres in front of the predict launch ----
 struct rn_keypoint_head {
-    rn_ctx *ctx;
-    uint64_t Cin, n_layers, ch[kKpMaxLayers], Kp, M;
-    int finalized;
-    rn_params params;                      // layer i: 2i, 2i + 1; kps_score_lowres: 2n, 2n + 1
-    rn_stage_unit unit[kKpMaxLayers + 1];  // the 3x3 layers, then the transposed convolution as ONE 1x1 panel Clast -> 16 Kp, no shift
-    float *bias;                           // kps_score_lowres.bias on the device
-    // scratch for cap rows: two ping-pong maps [., M, M, widest] and the panel's output [., M, M, 16 Kp]
-    float *ping, *pong, *t;
-    float *rois, *pooled;  // behind a neck: the RoI rows [., 5] and the pooled features [., M, M, Cin] of cap_pool rows
-    uint64_t cap[2], widest;
+    rn_roi_tower tower;  // its panel: the transposed convolution as ONE 1x1 Clast -> 16 Kp, no shift, no ReLU; no extra tensor;
+                         // its table behind the layers: kps_score_lowres: 2n, 2n + 1
+    uint64_t Kp;
+    float *bias;         // kps_score_lowres.bias on the device
 };
 
-// the scratch tensors for `rows` detections, `pool` of them behind a neck; returns how many
-static int keypoint_head_scratch(rn_keypoint_head *h, uint64_t rows, uint64_t pool, rn_scratch_item *list)
+// torchvision's Sequential of (conv, ReLU) pairs: layer i is "keypoint_head.{2i}"
+static void keypoint_layer_key(int i, const char *leaf, char key[RN_PARAM_KEY], char alt[RN_PARAM_KEY])
 {
-    const uint64_t px = rows * h->M * h->M;
-    list[0] = {(void **)&h->ping, px * h->widest * sizeof(float)};
-    list[1] = {(void **)&h->pong, px * h->widest * sizeof(float)};
-    list[2] = {(void **)&h->t, px * 16 * h->Kp * sizeof(float)};
-    list[3] = {(void **)&h->rois, pool * 5 * sizeof(float)};
-    list[4] = {(void **)&h->pooled, pool * h->M * h->M * h->Cin * sizeof(float)};
-    return kKpScratch;
+    snprintf(key, RN_PARAM_KEY, "keypoint_head.%d.%s", 2 * i, leaf);
+    alt[0] = 0;
 }
 
 int rn_keypoint_head_create(rn_ctx *ctx, rn_keypoint_head **out, uint64_t in_channels, uint64_t n_layers, const uint64_t *layer_channels,
@@ -315,34 +302,17 @@ int rn_keypoint_head_create(rn_ctx *ctx, rn_keypoint_head **out, uint64_t in_cha
     RN_ENTER(ctx);
     RN_REQUIRE(ctx, out, "out is NULL");
     *out = NULL;
-    RN_REQUIRE(ctx, in_channels >= 64 && in_channels % 64 == 0 && in_channels <= 8192, "in_channels must be a multiple of 64 (at most 8192)");
-    RN_REQUIRE(ctx, n_layers >= 1 && n_layers <= kKpMaxLayers, "n_layers must be 1..8");
-    RN_REQUIRE(ctx, layer_channels, "layer_channels is NULL");
-    for (uint64_t i = 0; i < n_layers; ++i)
-        RN_REQUIRE(ctx, layer_channels[i] >= 64 && layer_channels[i] % 64 == 0 && layer_channels[i] <= 8192,
-                   "every layer's channels must be a multiple of 64 (at most 8192)");
-    RN_REQUIRE(ctx, keypoints >= 1 && keypoints <= kKpMaxKp, "keypoints must be 1..256");
-    RN_REQUIRE(ctx, resolution >= 1 && resolution <= kKpMaxM, "resolution must be 1..16");
+    RN_TRY(rn_roi_tower_check(ctx, __func__, in_channels, n_layers, layer_channels,
+                              keypoints >= 1 && keypoints <= kKpMaxKp ? NULL : "keypoints must be 1..256", resolution, kKpMaxM));
     rn_keypoint_head *h = (rn_keypoint_head *)calloc(1, sizeof(*h));
     if (!h) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_keypoint_head_create: out of host memory");
-    h->ctx = ctx, h->Cin = in_channels, h->n_layers = n_layers, h->Kp = keypoints, h->M = resolution;
-    h->widest = in_channels;
-    for (uint64_t i = 0; i < n_layers; ++i) {
-        h->ch[i] = layer_channels[i];
-        if (h->ch[i] > h->widest) h->widest = h->ch[i];
-    }
-    // torchvision's Sequential of (conv, ReLU) pairs: layer i is "keypoint_head.{2i}"; with or without "roi_heads."
-    h->params.prefix = "roi_heads.";
-    for (uint64_t i = 0; i < n_layers; ++i)
-        for (int j = 0; j < 2; ++j) {
-            char key[RN_PARAM_KEY];
-            snprintf(key, sizeof(key), "keypoint_head.%d.%s", (int)(2 * i), j ? "bias" : "weight");
-            const uint64_t rows = j ? 1 : h->ch[i], len = j ? h->ch[i] : (i == 0 ? h->Cin : h->ch[i - 1]) * 9;
-            rn_params_add(&h->params, key, NULL, rows, len, rows, len, 0.0f);
-        }
-    const uint64_t last = h->ch[n_layers - 1];
-    rn_params_add(&h->params, "keypoint_predictor.kps_score_lowres.weight", NULL, last, keypoints * 16, last, keypoints * 16, 0.0f);
-    rn_params_add(&h->params, "keypoint_predictor.kps_score_lowres.bias", NULL, 1, keypoints, 1, keypoints, 0.0f);
+    h->Kp = keypoints;
+    rn_roi_tower *t = &h->tower;
+    t->name = "rn_keypoint_head", t->what = "the keypoint head", t->panel = 16 * keypoints, t->panel_relu = 0, t->extra_floats = 0;
+    rn_roi_tower_init(t, ctx, in_channels, n_layers, layer_channels, resolution, keypoint_layer_key);
+    const uint64_t last = t->ch[n_layers - 1];
+    rn_params_add(&t->params, "keypoint_predictor.kps_score_lowres.weight", NULL, last, keypoints * 16, last, keypoints * 16, 0.0f);
+    rn_params_add(&t->params, "keypoint_predictor.kps_score_lowres.bias", NULL, 1, keypoints, 1, keypoints, 0.0f);
     *out = h;
     return RN_OK;
 }
@@ -350,21 +320,20 @@ int rn_keypoint_head_create(rn_ctx *ctx, rn_keypoint_head **out, uint64_t in_cha
 int rn_keypoint_head_set_tensor(rn_keypoint_head *h, const char *key, const float *host_data, uint64_t numel)
 {
     if (!h) return RN_ERR_INVALID;
-    return rn_stage_set_tensor(h->ctx, __func__, "the keypoint head", h->finalized, &h->params, key, host_data, numel);
+    rn_roi_tower *t = &h->tower;
+    return rn_stage_set_tensor(t->ctx, __func__, t->what, t->finalized, &t->params, key, host_data, numel);
 }
 
 int rn_keypoint_head_finalize(rn_keypoint_head *h)
 {
     if (!h) return RN_ERR_INVALID;
-    rn_ctx *ctx = h->ctx;
+    rn_roi_tower *t = &h->tower;
+    rn_ctx *ctx = t->ctx;
     RN_ENTER(ctx);
-    if (h->finalized) return RN_OK;
-    RN_TRY(rn_stage_all_set(ctx, __func__, &h->params));
-    const uint64_t n = h->n_layers, Kp = h->Kp, last = h->ch[n - 1];
-    const rn_params_entry *p = h->params.p;
-    for (uint64_t i = 0; i < n; ++i)
-        RN_TRY(rn_stage_pack(ctx, RN_DTYPE_F32, p[2 * i].host, i == 0 ? h->Cin : h->ch[i - 1], h->ch[i], 3, p[2 * i + 1].host, NULL,
-                             &h->unit[i]));
+    if (t->finalized) return RN_OK;
+    RN_TRY(rn_roi_tower_pack_layers(t, __func__));
+    const uint64_t n = t->n_layers, Kp = h->Kp, last = t->ch[n - 1];
+    const rn_params_entry *p = t->params.p;
     // ConvTranspose2d(last, Kp, 4, 2, 1), weight [last, Kp, 4, 4]: the 1x1 convolution whose row k * 16 + ky * 4 + kx is
     // W[:, k, ky, kx] holds every product; output (oy, ox) adds the taps with 2 iy = oy + 1 - ky, 2 ix = ox + 1 - kx
     float *w = (float *)malloc(16 * Kp * last * sizeof(float));
@@ -372,150 +341,97 @@ int rn_keypoint_head_finalize(rn_keypoint_head *h)
     const float *dw = p[2 * n].host;
     for (uint64_t r = 0; r < 16 * Kp; ++r)
         for (uint64_t ci = 0; ci < last; ++ci) w[r * last + ci] = dw[ci * 16 * Kp + r];
-    int st = rn_stage_pack(ctx, RN_DTYPE_F32, w, last, 16 * Kp, 1, NULL, NULL, &h->unit[n]);
+    int st = rn_roi_tower_pack_panel(t, w, NULL);
     free(w);
     if (st == RN_OK && !h->bias) st = rn_malloc(ctx, (void **)&h->bias, Kp * sizeof(float));
     if (st == RN_OK) st = rn_ctx_upload_sync(ctx, h->bias, p[2 * n + 1].host, Kp * sizeof(float));
     if (st != RN_OK) return st;
-    rn_params_free(&h->params);
-    h->finalized = 1;
+    rn_params_free(&t->params);
+    t->finalized = 1;
     return RN_OK;
 }
 
 int rn_keypoint_head_destroy(rn_keypoint_head *h)
 {
     if (!h) return RN_OK;
-    rn_ctx *ctx = h->ctx;
+    rn_ctx *ctx = h->tower.ctx;
     RN_ENTER(ctx);
     RN_TRY(rn_sync(ctx));
-    rn_scratch_item list[kKpScratch];
-    rn_stage_free_list(ctx, list, keypoint_head_scratch(h, 0, 0, list));
-    rn_params_free(&h->params);
-    for (int i = 0; i <= kKpMaxLayers; ++i) rn_stage_unit_free(ctx, &h->unit[i]);
+    rn_roi_tower_free(&h->tower);
     rn_free_null(ctx, (void **)&h->bias);
     free(h);
     return RN_OK;
 }
 
-// ---- library-internal (rn_private.h) ----
+// ---- what differs from another RoI head (rn_private.h: rn_roi_head) ----
 
-int rn_keypoint_head_matches(const rn_keypoint_head *h, const rn_ctx *ctx, uint64_t in_channels, const char **why)
+// every refusal that concerns the request and the shapes alone, for `rows` detections
+static int keypoint_head_check(const rn_roi_head *s, rn_ctx *ctx, const char *fn, uint64_t rows, int boxes_given, uint64_t image_h,
+                               uint64_t image_w)
 {
-    const char *w = NULL;
-    if (!h) w = "the keypoint head is NULL";
-    else if (!h->finalized) w = "the keypoint head is not finalized";
-    else if (h->ctx->device != ctx->device) w = "the keypoint head's context is on another device";
-    else if (h->Cin != in_channels) w = "the keypoint head's in_channels is not the neck's out_channels";
-    if (why) *why = w;
-    return w == NULL;
-}
-
-uint64_t rn_keypoint_head_resolution(const rn_keypoint_head *h) { return h->M; }
-
-int rn_keypoint_head_reserve(rn_keypoint_head *h, uint64_t rows, int with_pool)
-{
-    if (rows <= h->cap[kKpRows] && (!with_pool || rows <= h->cap[kKpPool])) return RN_OK;
-    const uint64_t want[2] = {rows > h->cap[kKpRows] ? rows : h->cap[kKpRows],
-                              with_pool && rows > h->cap[kKpPool] ? rows : h->cap[kKpPool]};
-    rn_scratch_item list[kKpScratch];
-    return rn_stage_grow(h->ctx, "rn_keypoint_head", list, keypoint_head_scratch(h, want[kKpRows], want[kKpPool], list), h->cap, want, 2);
-}
-
-int rn_keypoint_head_check(const rn_keypoint_head *h, rn_ctx *ctx, const char *fn, const rn_keypoint_request *q, uint64_t rows,
-                           int boxes_given, uint64_t image_h, uint64_t image_w)
-{
+    const rn_keypoint_request *q = (const rn_keypoint_request *)s->req;
     if (!q) return rn_set_error(ctx, RN_ERR_INVALID, "%s: the keypoint request is NULL", fn);
     const char *why = NULL;
     if (!q->heat && !q->keypoints && !q->scores) why = "heat, keypoints and scores of the keypoint request are all NULL";
     else if ((q->keypoints != NULL) != (q->scores != NULL)) why = "keypoints and scores of the keypoint request come together";
     else if (q->keypoints && !boxes_given) why = "boxes is NULL and the keypoint request wants keypoints";
     if (why) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s", fn, why);
-    return keypoint_check(ctx, fn, rows, h->Kp, image_h, image_w);
+    return keypoint_check(ctx, fn, rows, ((const rn_keypoint_head *)s->head)->Kp, image_h, image_w);
 }
 
-int rn_keypoint_head_operands(const rn_keypoint_head *h, const rn_keypoint_request *q, uint64_t rows,
-                              rn_operand ops[RN_KEYPOINT_HEAD_OPERANDS])
+static int keypoint_head_operands(const rn_roi_head *s, uint64_t rows, uint64_t, uint64_t, rn_operand ops[RN_ROI_HEAD_OPERANDS])
 {
-    const uint64_t M = h->M;
+    const rn_keypoint_request *q = (const rn_keypoint_request *)s->req;
+    const uint64_t M = s->tower->M, Kp = ((const rn_keypoint_head *)s->head)->Kp;
     ops[0] = {q->rois, rows * 20, "keypoint.rois", true, false};
-    ops[1] = {q->pooled, rows * M * M * h->Cin * 4, "keypoint.pooled", true, false};
-    ops[2] = {q->heat, rows * h->Kp * 16 * M * M * 4, "keypoint.heat", true, false};
-    ops[3] = {q->keypoints, rows * h->Kp * 12, "keypoint.keypoints", true, false};
-    ops[4] = {q->scores, rows * h->Kp * 4, "keypoint.scores", true, false};
-    return RN_KEYPOINT_HEAD_OPERANDS;
+    ops[1] = {q->pooled, rows * M * M * s->tower->Cin * 4, "keypoint.pooled", true, false};
+    ops[2] = {q->heat, rows * Kp * 16 * M * M * 4, "keypoint.heat", true, false};
+    ops[3] = {q->keypoints, rows * Kp * 12, "keypoint.keypoints", true, false};
+    ops[4] = {q->scores, rows * Kp * 4, "keypoint.scores", true, false};
+    return RN_ROI_HEAD_OPERANDS;
 }
 
-// The head's launches on ctx for K detections whose scratch starts sub0 rows into the object's tensors: n_layers + 1
-// contractions and the predict launch.  ctx->layout is NHWC.
-int rn_keypoint_head_step(rn_keypoint_head *h, rn_ctx *ctx, const float *pooled_nhwc, const int32_t *labels, const float *boxes,
-                          uint64_t sub0, uint64_t K, uint64_t image_h, uint64_t image_w, float *heat, float *keypoints, float *scores)
+// the predict launch
+static int keypoint_head_behind(const rn_roi_head *s, rn_ctx *ctx, const float *t, float *, const int32_t *labels, const float *boxes,
+                                uint64_t row0, uint64_t K, uint64_t image_h, uint64_t image_w)
 {
-    if (sub0 + K > h->cap[kKpRows]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_keypoint_head: scratch not reserved");
-    const uint64_t M = h->M, px0 = sub0 * M * M;
-    float *ping = h->ping + px0 * h->widest, *pong = h->pong + px0 * h->widest, *t = h->t + px0 * 16 * h->Kp;
-    rn_epilogue ep;
-    ep.scale = NULL, ep.residual = NULL, ep.relu = 1;
-    const float *x = pooled_nhwc;
-    uint64_t cin = h->Cin;
-    for (uint64_t i = 0; i < h->n_layers; ++i) {
-        float *y = i % 2 == 0 ? ping : pong;
-        ep.shift = h->unit[i].shift;
-        RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, x, y, h->unit[i].packed, 3, 1, 1, M, M, K, cin, h->ch[i], M, M, &ep));
-        x = y, cin = h->ch[i];
-    }
-    ep.shift = NULL, ep.relu = 0;
-    RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, x, t, h->unit[h->n_layers].packed, 1, 1, 0, M, M, K, cin, 16 * h->Kp, M, M, &ep));
-    return keypoint_launch(ctx, t, h->bias, NULL, boxes, labels, K, M, h->Kp, 4 * M, image_h, image_w, heat, keypoints, scores,
-                           "rn_keypoint_head (predict)");
+    const rn_keypoint_head *h = (const rn_keypoint_head *)s->head;
+    const rn_keypoint_request *q = (const rn_keypoint_request *)s->req;
+    const uint64_t M = s->tower->M, Kp = h->Kp;
+    return keypoint_launch(ctx, t, h->bias, NULL, boxes, labels, K, M, Kp, 4 * M, image_h, image_w,
+                           q->heat ? q->heat + row0 * Kp * 16 * M * M : NULL, q->keypoints ? q->keypoints + row0 * Kp * 3 : NULL,
+                           q->scores ? q->scores + row0 * Kp : NULL, "rn_keypoint_head (predict)");
 }
 
-// The stage behind a neck for the B images from the caller's image img0 on (D detections each), whose scratch starts
-// sub0 images into the object's tensors: the RoIs of these images' detection rows, the NHWC pooler on these images'
-// maps (maps[i]: level i of image img0), the head.  boxes, labels and the request's outputs: the whole call's.
-int rn_keypoint_head_stage(rn_keypoint_head *h, rn_ctx *ctx, uint64_t n_levels, const void *const *maps, const uint64_t *hs,
-                           const uint64_t *ws, const float *scales, const float *thr, uint64_t images, uint64_t sub0, uint64_t img0,
-                           uint64_t B, uint64_t D, const float *boxes, const int32_t *labels, uint64_t image_h, uint64_t image_w,
-                           const rn_keypoint_request *q)
+void rn_keypoint_head_slot(rn_keypoint_head *h, const rn_keypoint_request *q, rn_roi_head *s)
 {
-    const uint64_t M = h->M, K = B * D, row0 = img0 * D, srow0 = sub0 * D, feat = M * M * h->Cin, Kp = h->Kp;
-    if ((!q->rois || !q->pooled) && srow0 + K > h->cap[kKpPool]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_keypoint_head: scratch not reserved");
-    float *rois = q->rois ? q->rois + row0 * 5 : h->rois + srow0 * 5;
-    float *pooled = q->pooled ? q->pooled + row0 * feat : h->pooled + srow0 * feat;
-    RN_TRY(rn_detection_rois_window(ctx, boxes + row0 * 4, labels + row0, img0, B, D, rois));
-    RN_TRY(rn_roi_align_nhwc_window(ctx, RN_DTYPE_F32, n_levels, maps, hs, ws, scales, thr, images, img0, B, 1, h->Cin, rois, K, M,
-                                    M, q->sampling_ratio, q->aligned, pooled, NULL));
-    return rn_keypoint_head_step(h, ctx, pooled, labels + row0, boxes + row0 * 4, srow0, K, image_h, image_w,
-                                 q->heat ? q->heat + row0 * Kp * 16 * M * M : NULL, q->keypoints ? q->keypoints + row0 * Kp * 3 : NULL,
-                                 q->scores ? q->scores + row0 * Kp : NULL);
+    *s = {};
+    if (!h) return;
+    s->who = "keypoint", s->stage = "keypoint_stage", s->tower = &h->tower, s->head = h, s->req = q;
+    s->check = keypoint_head_check, s->operands = keypoint_head_operands, s->behind = keypoint_head_behind;
+    if (q) s->pool = {q->n_levels, q->level, q->sampling_ratio, q->aligned, q->canonical_scale, q->canonical_level, q->rois, q->pooled};
 }
 
 int rn_keypoint_head_forward(rn_keypoint_head *h, const float *pooled_nhwc, const int32_t *labels, const float *boxes, uint64_t K,
                              uint64_t image_h, uint64_t image_w, const rn_keypoint_request *req)
 {
     if (!h) return RN_ERR_INVALID;
-    rn_ctx *ctx = h->ctx;
+    rn_ctx *ctx = h->tower.ctx;
     RN_ENTER(ctx);
-    RN_REQUIRE(ctx, h->finalized, "the keypoint head is not finalized");
-    RN_TRY(rn_keypoint_head_check(h, ctx, __func__, req, K, boxes != NULL, image_h, image_w));
-    RN_REQUIRE(ctx, K * h->M * h->M < (1ull << 31), "K * M * M must be below 2^31");
+    RN_REQUIRE(ctx, h->tower.finalized, "the keypoint head is not finalized");
+    rn_roi_head s;
+    rn_keypoint_head_slot(h, req, &s);
+    RN_TRY(keypoint_head_check(&s, ctx, __func__, K, boxes != NULL, image_h, image_w));
+    const uint64_t M = h->tower.M;
+    RN_REQUIRE(ctx, K * M * M < (1ull << 31), "K * M * M must be below 2^31");
     if (K == 0) return RN_OK;
-    RN_REQUIRE(ctx, pooled_nhwc, "pooled_nhwc is NULL");
-    RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(pooled_nhwc) & 15) == 0, "pooled_nhwc is off a 16-byte boundary");
-    const uint64_t M = h->M;
-    operand ops[RN_KEYPOINT_HEAD_OPERANDS + 3];
-    rn_keypoint_head_operands(h, req, K, ops);
+    operand ops[RN_ROI_HEAD_OPERANDS + 3];
+    keypoint_head_operands(&s, K, image_h, image_w, ops);
     ops[0].ptr = ops[1].ptr = NULL;  // the request's rois and pooled are the route's: nothing here writes them
-    ops[5] = {pooled_nhwc, K * M * M * h->Cin * 4, "pooled_nhwc", false, false};
+    ops[5] = {pooled_nhwc, K * M * M * h->tower.Cin * 4, "pooled_nhwc", false, false};
     ops[6] = {req->keypoints ? labels : NULL, K * 4, "labels", false, false};
     ops[7] = {req->keypoints ? boxes : NULL, K * 16, "boxes", false, false};
-    RN_TRY(check_operands(ctx, __func__, ops, RN_KEYPOINT_HEAD_OPERANDS + 3));
-    RN_TRY(rn_keypoint_head_reserve(h, K, 0));
-    const int saved_layout = ctx->layout;
-    ctx->layout = RN_LAYOUT_NHWC;
-    const int st = rn_keypoint_head_step(h, ctx, pooled_nhwc, labels, boxes, 0, K, image_h, image_w, req->heat, req->keypoints,
-                                         req->scores);
-    ctx->layout = saved_layout;
-    return st;
+    return rn_roi_head_forward(&s, __func__, pooled_nhwc, NULL, ops, RN_ROI_HEAD_OPERANDS + 3, labels, boxes, K, image_h, image_w);
 }
 
 }  // extern "C"

@@ -409,35 +409,21 @@ int rn_paste_masks_forward(rn_ctx *ctx, const float *probs, const float *boxes, 
     return paste_launch(ctx, probs, boxes, labels, K, Mo, H, W, threshold, masks, bits, __func__);
 }
 
-// ---- the object: MaskRCNNHeads and MaskRCNNPredictor in front of the predict and paste launches ------------------
-enum { kMaskMaxLayers = 8, kMaskRows = 0, kMaskPool = 1, kMaskScratch = 6 };
-
+// ---- the object: MaskRCNNHeads (the RoI tower of rn_stage.hip) and MaskRCNNPredictor in front of the predict and paste
+// launches ----
 struct rn_mask_head {
-    rn_ctx *ctx;
-    uint64_t Cin, n_layers, ch[kMaskMaxLayers], Cr, C, M;
-    int finalized;
-    rn_params params;                   // layer i: 2i, 2i + 1; conv5_mask: 2n, 2n + 1; mask_fcn_logits: 2n + 2, 2n + 3
-    rn_stage_unit unit[kMaskMaxLayers + 1];  // the 3x3 layers, then the transposed convolution as ONE 1x1 panel Clast -> 4 Cr
-                                        // (its shift: conv5_mask's bias four times)
-    float *lw, *lb;                     // mask_fcn_logits on the device, torchvision's layout
-    // scratch for cap rows: two ping-pong maps [., M, M, widest], the deconvolution's output [., M, M, 4 Cr] and the
-    // probabilities [., 2M, 2M] of a forward that does not export them
-    float *ping, *pong, *t, *probs;
-    float *rois, *pooled;               // behind a neck: the RoI rows [., 5] and the pooled features [., M, M, Cin] of cap_pool rows
-    uint64_t cap[2], widest;            // cap: rows (kMaskRows), of them with RoI rows and pooled features (kMaskPool)
+    rn_roi_tower tower;  // its panel: the transposed convolution as ONE 1x1 Clast -> 4 Cr (its shift: conv5_mask's bias four
+                         // times), ReLU; its extra tensor: the probabilities [., 2M, 2M] of a forward that does not export them;
+                         // its table behind the layers: conv5_mask: 2n, 2n + 1; mask_fcn_logits: 2n + 2, 2n + 3
+    uint64_t Cr, C;
+    float *lw, *lb;      // mask_fcn_logits on the device, torchvision's layout
 };
 
-// the scratch tensors for `rows` detections, `pool` of them behind a neck; returns how many
-static int mask_head_scratch(rn_mask_head *h, uint64_t rows, uint64_t pool, rn_scratch_item *list)
+// either spelling of a layer ("mask_head.0.0.weight", "mask_head.mask_fcn1.weight")
+static void mask_layer_key(int i, const char *leaf, char key[RN_PARAM_KEY], char alt[RN_PARAM_KEY])
 {
-    const uint64_t px = rows * h->M * h->M;
-    list[0] = {(void **)&h->ping, px * h->widest * sizeof(float)};
-    list[1] = {(void **)&h->pong, px * h->widest * sizeof(float)};
-    list[2] = {(void **)&h->t, px * 4 * h->Cr * sizeof(float)};
-    list[3] = {(void **)&h->probs, px * 4 * sizeof(float)};
-    list[4] = {(void **)&h->rois, pool * 5 * sizeof(float)};
-    list[5] = {(void **)&h->pooled, pool * h->M * h->M * h->Cin * sizeof(float)};
-    return kMaskScratch;
+    snprintf(key, RN_PARAM_KEY, "mask_head.%d.0.%s", i, leaf);
+    snprintf(alt, RN_PARAM_KEY, "mask_head.mask_fcn%d.%s", i + 1, leaf);
 }
 
 int rn_mask_head_create(rn_ctx *ctx, rn_mask_head **out, uint64_t in_channels, uint64_t n_layers, const uint64_t *layer_channels,
@@ -446,39 +432,22 @@ int rn_mask_head_create(rn_ctx *ctx, rn_mask_head **out, uint64_t in_channels, u
     RN_ENTER(ctx);
     RN_REQUIRE(ctx, out, "out is NULL");
     *out = NULL;
-    RN_REQUIRE(ctx, in_channels >= 64 && in_channels % 64 == 0 && in_channels <= 8192, "in_channels must be a multiple of 64 (at most 8192)");
-    RN_REQUIRE(ctx, n_layers >= 1 && n_layers <= kMaskMaxLayers, "n_layers must be 1..8");
-    RN_REQUIRE(ctx, layer_channels, "layer_channels is NULL");
-    for (uint64_t i = 0; i < n_layers; ++i)
-        RN_REQUIRE(ctx, layer_channels[i] >= 64 && layer_channels[i] % 64 == 0 && layer_channels[i] <= 8192,
-                   "every layer's channels must be a multiple of 64 (at most 8192)");
-    RN_REQUIRE(ctx, dim_reduced >= 64 && dim_reduced % 64 == 0 && dim_reduced <= kMaskMaxCr,
-               "dim_reduced must be a multiple of 64 up to 1024");
-    RN_REQUIRE(ctx, classes >= 2 && classes <= kMaskMaxC, "classes must be 2..1024");
-    RN_REQUIRE(ctx, resolution >= 1 && resolution <= kMaskMaxM, "resolution must be 1..32");
+    const char *own = NULL;
+    if (dim_reduced < 64 || dim_reduced % 64 != 0 || dim_reduced > kMaskMaxCr) own = "dim_reduced must be a multiple of 64 up to 1024";
+    else if (classes < 2 || classes > kMaskMaxC) own = "classes must be 2..1024";
+    RN_TRY(rn_roi_tower_check(ctx, __func__, in_channels, n_layers, layer_channels, own, resolution, kMaskMaxM));
     rn_mask_head *h = (rn_mask_head *)calloc(1, sizeof(*h));
     if (!h) return rn_set_error(ctx, RN_ERR_NOMEM, "rn_mask_head_create: out of host memory");
-    h->ctx = ctx, h->Cin = in_channels, h->n_layers = n_layers, h->Cr = dim_reduced, h->C = classes, h->M = resolution;
-    h->widest = in_channels;
-    for (uint64_t i = 0; i < n_layers; ++i) {
-        h->ch[i] = layer_channels[i];
-        if (h->ch[i] > h->widest) h->widest = h->ch[i];
-    }
-    // either spelling of a layer ("mask_head.0.0.weight", "mask_head.mask_fcn1.weight"), with or without "roi_heads."
-    h->params.prefix = "roi_heads.";
-    for (uint64_t i = 0; i < n_layers; ++i)
-        for (int j = 0; j < 2; ++j) {
-            char key[RN_PARAM_KEY], alt[RN_PARAM_KEY];
-            snprintf(key, sizeof(key), "mask_head.%d.0.%s", (int)i, j ? "bias" : "weight");
-            snprintf(alt, sizeof(alt), "mask_head.mask_fcn%d.%s", (int)i + 1, j ? "bias" : "weight");
-            const uint64_t rows = j ? 1 : h->ch[i], len = j ? h->ch[i] : (i == 0 ? h->Cin : h->ch[i - 1]) * 9;
-            rn_params_add(&h->params, key, alt, rows, len, rows, len, 0.0f);
-        }
-    const uint64_t last = h->ch[n_layers - 1], Cr = dim_reduced;
-    rn_params_add(&h->params, "mask_predictor.conv5_mask.weight", NULL, last, Cr * 4, last, Cr * 4, 0.0f);
-    rn_params_add(&h->params, "mask_predictor.conv5_mask.bias", NULL, 1, Cr, 1, Cr, 0.0f);
-    rn_params_add(&h->params, "mask_predictor.mask_fcn_logits.weight", NULL, classes, Cr, classes, Cr, 0.0f);
-    rn_params_add(&h->params, "mask_predictor.mask_fcn_logits.bias", NULL, 1, classes, 1, classes, 0.0f);
+    const uint64_t Cr = h->Cr = dim_reduced;
+    h->C = classes;
+    rn_roi_tower *t = &h->tower;
+    t->name = "rn_mask_head", t->what = "the mask head", t->panel = 4 * Cr, t->panel_relu = 1, t->extra_floats = 4;
+    rn_roi_tower_init(t, ctx, in_channels, n_layers, layer_channels, resolution, mask_layer_key);
+    const uint64_t last = t->ch[n_layers - 1];
+    rn_params_add(&t->params, "mask_predictor.conv5_mask.weight", NULL, last, Cr * 4, last, Cr * 4, 0.0f);
+    rn_params_add(&t->params, "mask_predictor.conv5_mask.bias", NULL, 1, Cr, 1, Cr, 0.0f);
+    rn_params_add(&t->params, "mask_predictor.mask_fcn_logits.weight", NULL, classes, Cr, classes, Cr, 0.0f);
+    rn_params_add(&t->params, "mask_predictor.mask_fcn_logits.bias", NULL, 1, classes, 1, classes, 0.0f);
     *out = h;
     return RN_OK;
 }
@@ -486,21 +455,20 @@ int rn_mask_head_create(rn_ctx *ctx, rn_mask_head **out, uint64_t in_channels, u
 int rn_mask_head_set_tensor(rn_mask_head *h, const char *key, const float *host_data, uint64_t numel)
 {
     if (!h) return RN_ERR_INVALID;
-    return rn_stage_set_tensor(h->ctx, __func__, "the mask head", h->finalized, &h->params, key, host_data, numel);
+    rn_roi_tower *t = &h->tower;
+    return rn_stage_set_tensor(t->ctx, __func__, t->what, t->finalized, &t->params, key, host_data, numel);
 }
 
 int rn_mask_head_finalize(rn_mask_head *h)
 {
     if (!h) return RN_ERR_INVALID;
-    rn_ctx *ctx = h->ctx;
+    rn_roi_tower *t = &h->tower;
+    rn_ctx *ctx = t->ctx;
     RN_ENTER(ctx);
-    if (h->finalized) return RN_OK;
-    RN_TRY(rn_stage_all_set(ctx, __func__, &h->params));
-    const uint64_t n = h->n_layers, Cr = h->Cr, last = h->ch[n - 1];
-    const rn_params_entry *p = h->params.p;
-    for (uint64_t i = 0; i < n; ++i)
-        RN_TRY(rn_stage_pack(ctx, RN_DTYPE_F32, p[2 * i].host, i == 0 ? h->Cin : h->ch[i - 1], h->ch[i], 3, p[2 * i + 1].host, NULL,
-                             &h->unit[i]));
+    if (t->finalized) return RN_OK;
+    RN_TRY(rn_roi_tower_pack_layers(t, __func__));
+    const uint64_t n = t->n_layers, Cr = h->Cr, last = t->ch[n - 1];
+    const rn_params_entry *p = t->params.p;
     // ConvTranspose2d(last, Cr, 2, 2), weight [last, Cr, 2, 2]: output (2y + dy, 2x + dx) reads input (y, x) alone, so
     // it is the 1x1 convolution whose row (dy * 2 + dx) * Cr + co is W[:, co, dy, dx]; the bias four times
     float *w = (float *)malloc((4 * Cr * last + 4 * Cr) * sizeof(float));
@@ -511,160 +479,102 @@ int rn_mask_head_finalize(rn_mask_head *h)
             for (uint64_t ci = 0; ci < last; ++ci) w[(q * Cr + co) * last + ci] = dw[(ci * Cr + co) * 4 + q];
             w[4 * Cr * last + q * Cr + co] = db[co];
         }
-    int st = rn_stage_pack(ctx, RN_DTYPE_F32, w, last, 4 * Cr, 1, w + 4 * Cr * last, NULL, &h->unit[n]);
+    int st = rn_roi_tower_pack_panel(t, w, w + 4 * Cr * last);
     free(w);
     if (st == RN_OK && !h->lw) st = rn_malloc(ctx, (void **)&h->lw, h->C * Cr * sizeof(float));
     if (st == RN_OK && !h->lb) st = rn_malloc(ctx, (void **)&h->lb, h->C * sizeof(float));
     if (st == RN_OK) st = rn_ctx_upload_sync(ctx, h->lw, p[2 * n + 2].host, h->C * Cr * sizeof(float));
     if (st == RN_OK) st = rn_ctx_upload_sync(ctx, h->lb, p[2 * n + 3].host, h->C * sizeof(float));
     if (st != RN_OK) return st;
-    rn_params_free(&h->params);
-    h->finalized = 1;
+    rn_params_free(&t->params);
+    t->finalized = 1;
     return RN_OK;
 }
 
 int rn_mask_head_destroy(rn_mask_head *h)
 {
     if (!h) return RN_OK;
-    rn_ctx *ctx = h->ctx;
+    rn_ctx *ctx = h->tower.ctx;
     RN_ENTER(ctx);
     RN_TRY(rn_sync(ctx));
-    rn_scratch_item list[kMaskScratch];
-    rn_stage_free_list(ctx, list, mask_head_scratch(h, 0, 0, list));
-    rn_params_free(&h->params);
-    for (int i = 0; i <= kMaskMaxLayers; ++i) rn_stage_unit_free(ctx, &h->unit[i]);
+    rn_roi_tower_free(&h->tower);
     rn_free_null(ctx, (void **)&h->lw), rn_free_null(ctx, (void **)&h->lb);
     free(h);
     return RN_OK;
 }
 
-// ---- library-internal (rn_private.h) ----
+// ---- what differs from another RoI head (rn_private.h: rn_roi_head) ----
 
-int rn_mask_head_matches(const rn_mask_head *h, const rn_ctx *ctx, uint64_t in_channels, const char **why)
+// every refusal that concerns the request and the shapes alone, for `rows` detections; boxes_given: a paste is possible
+static int mask_head_check(const rn_roi_head *s, rn_ctx *ctx, const char *fn, uint64_t rows, int boxes_given, uint64_t image_h,
+                           uint64_t image_w)
 {
-    const char *w = NULL;
-    if (!h) w = "the mask head is NULL";
-    else if (!h->finalized) w = "the mask head is not finalized";
-    else if (h->ctx->device != ctx->device) w = "the mask head's context is on another device";
-    else if (h->Cin != in_channels) w = "the mask head's in_channels is not the neck's out_channels";
-    if (why) *why = w;
-    return w == NULL;
-}
-
-uint64_t rn_mask_head_resolution(const rn_mask_head *h) { return h->M; }
-
-// the object's scratch for `rows` detections (rn_stage_grow's rule); with_pool: the RoI rows and the pooled features of a
-// forward behind a neck as well
-int rn_mask_head_reserve(rn_mask_head *h, uint64_t rows, int with_pool)
-{
-    if (rows <= h->cap[kMaskRows] && (!with_pool || rows <= h->cap[kMaskPool])) return RN_OK;
-    const uint64_t want[2] = {rows > h->cap[kMaskRows] ? rows : h->cap[kMaskRows],
-                              with_pool && rows > h->cap[kMaskPool] ? rows : h->cap[kMaskPool]};
-    rn_scratch_item list[kMaskScratch];
-    return rn_stage_grow(h->ctx, "rn_mask_head", list, mask_head_scratch(h, want[kMaskRows], want[kMaskPool], list), h->cap, want, 2);
-}
-
-// every refusal that concerns the request and the shapes alone, for `rows` detections
-int rn_mask_head_check(const rn_mask_head *h, rn_ctx *ctx, const char *fn, const rn_mask_request *q, uint64_t rows,
-                       int paste_possible, uint64_t image_h, uint64_t image_w)
-{
+    const rn_mask_request *q = (const rn_mask_request *)s->req;
+    const uint64_t M = s->tower->M;
     if (!q) return rn_set_error(ctx, RN_ERR_INVALID, "%s: the mask request is NULL", fn);
     const char *why = NULL;
     if (!q->probs && !q->masks && !q->bits) why = "probs, masks and bits of the mask request are all NULL";
-    else if ((q->masks || q->bits) && !paste_possible) why = "boxes is NULL and the mask request wants pasted masks";
-    else if (rows >= (1ull << 31) || rows * h->M * h->M >= (1ull << 31)) why = "K * M * M must be below 2^31";
+    else if ((q->masks || q->bits) && !boxes_given) why = "boxes is NULL and the mask request wants pasted masks";
+    else if (rows >= (1ull << 31) || rows * M * M >= (1ull << 31)) why = "K * M * M must be below 2^31";
     if (why) return rn_set_error(ctx, RN_ERR_INVALID, "%s: %s", fn, why);
-    if (q->masks || q->bits) RN_TRY(paste_check(ctx, fn, rows, 2 * h->M, image_h, image_w, q->threshold));
+    if (q->masks || q->bits) RN_TRY(paste_check(ctx, fn, rows, 2 * M, image_h, image_w, q->threshold));
     return RN_OK;
 }
 
-int rn_mask_head_operands(const rn_mask_head *h, const rn_mask_request *q, uint64_t rows, uint64_t image_h, uint64_t image_w,
-                          rn_operand ops[RN_MASK_HEAD_OPERANDS])
+static int mask_head_operands(const rn_roi_head *s, uint64_t rows, uint64_t image_h, uint64_t image_w, rn_operand ops[RN_ROI_HEAD_OPERANDS])
 {
-    const uint64_t M = h->M, plane = (q->masks || q->bits) ? image_h * image_w : 0;
+    const rn_mask_request *q = (const rn_mask_request *)s->req;
+    const uint64_t M = s->tower->M, plane = (q->masks || q->bits) ? image_h * image_w : 0;
     ops[0] = {q->rois, rows * 20, "mask.rois", true, false};
-    ops[1] = {q->pooled, rows * M * M * h->Cin * 4, "mask.pooled", true, false};
+    ops[1] = {q->pooled, rows * M * M * s->tower->Cin * 4, "mask.pooled", true, false};
     ops[2] = {q->probs, rows * 4 * M * M * 4, "mask.probs", true, false};
     ops[3] = {q->masks, rows * plane * 4, "mask.masks", true, false};
     ops[4] = {q->bits, rows * plane, "mask.bits", true, true};
-    return RN_MASK_HEAD_OPERANDS;
+    return RN_ROI_HEAD_OPERANDS;
 }
 
-// The head's launches on ctx for K detections whose scratch starts sub0 rows into the object's tensors: n_layers + 1
-// contractions, the predict launch, the paste where masks or bits is given.  ctx->layout is NHWC.
-int rn_mask_head_step(rn_mask_head *h, rn_ctx *ctx, const float *pooled_nhwc, const int32_t *labels, const float *boxes,
-                      uint64_t sub0, uint64_t K, uint64_t image_h, uint64_t image_w, float threshold, float *probs_out,
-                      float *masks, uint8_t *bits)
+// the predict launch, and the paste where masks or bits is given
+static int mask_head_behind(const rn_roi_head *s, rn_ctx *ctx, const float *t, float *extra, const int32_t *labels, const float *boxes,
+                            uint64_t row0, uint64_t K, uint64_t image_h, uint64_t image_w)
 {
-    if (sub0 + K > h->cap[kMaskRows]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_mask_head: scratch not reserved");
-    const uint64_t M = h->M, px0 = sub0 * M * M;
-    float *ping = h->ping + px0 * h->widest, *pong = h->pong + px0 * h->widest, *t = h->t + px0 * 4 * h->Cr;
-    rn_epilogue ep;
-    ep.scale = NULL, ep.residual = NULL, ep.relu = 1;
-    const float *x = pooled_nhwc;
-    uint64_t cin = h->Cin;
-    for (uint64_t i = 0; i < h->n_layers; ++i) {
-        float *y = i % 2 == 0 ? ping : pong;
-        ep.shift = h->unit[i].shift;
-        RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, x, y, h->unit[i].packed, 3, 1, 1, M, M, K, cin, h->ch[i], M, M, &ep));
-        x = y, cin = h->ch[i];
-    }
-    ep.shift = h->unit[h->n_layers].shift;
-    RN_TRY(rn_conv2d_nhwc_forward_dt(ctx, RN_DTYPE_F32, RN_DTYPE_F32, x, t, h->unit[h->n_layers].packed, 1, 1, 0, M, M, K, cin, 4 * h->Cr, M, M, &ep));
-    float *probs = probs_out ? probs_out : h->probs + px0 * 4;
+    const rn_mask_head *h = (const rn_mask_head *)s->head;
+    const rn_mask_request *q = (const rn_mask_request *)s->req;
+    const uint64_t M = s->tower->M, plane = image_h * image_w;
+    float *probs = q->probs ? q->probs + row0 * 4 * M * M : extra;
     RN_TRY(predict_launch(ctx, t, labels, h->lw, h->lb, K, M, h->Cr, h->C, probs, "rn_mask_head (predict)"));
-    if (!masks && !bits) return RN_OK;
-    return paste_launch(ctx, probs, boxes, labels, K, 2 * M, image_h, image_w, threshold, masks, bits, "rn_mask_head (paste)");
+    if (!q->masks && !q->bits) return RN_OK;
+    return paste_launch(ctx, probs, boxes, labels, K, 2 * M, image_h, image_w, q->threshold, q->masks ? q->masks + row0 * plane : NULL,
+                        q->bits ? q->bits + row0 * plane : NULL, "rn_mask_head (paste)");
 }
 
-// The stage behind a neck for the B images from the caller's image img0 on (D detections each), whose scratch starts
-// sub0 images into the object's tensors: the RoIs of these images' detection rows, the NHWC pooler on these images'
-// maps (maps[i]: level i of image img0), the head.  boxes, labels and the request's outputs: the whole call's.
-int rn_mask_head_stage(rn_mask_head *h, rn_ctx *ctx, uint64_t n_levels, const void *const *maps, const uint64_t *hs,
-                       const uint64_t *ws, const float *scales, const float *thr, uint64_t images, uint64_t sub0, uint64_t img0,
-                       uint64_t B, uint64_t D, const float *boxes, const int32_t *labels, uint64_t image_h, uint64_t image_w,
-                       const rn_mask_request *q)
+void rn_mask_head_slot(rn_mask_head *h, const rn_mask_request *q, rn_roi_head *s)
 {
-    const uint64_t M = h->M, K = B * D, row0 = img0 * D, srow0 = sub0 * D, feat = M * M * h->Cin;
-    if ((!q->rois || !q->pooled) && srow0 + K > h->cap[kMaskPool]) return rn_set_error(ctx, RN_ERR_INVALID, "rn_mask_head: scratch not reserved");
-    float *rois = q->rois ? q->rois + row0 * 5 : h->rois + srow0 * 5;
-    float *pooled = q->pooled ? q->pooled + row0 * feat : h->pooled + srow0 * feat;
-    const uint64_t plane = image_h * image_w;
-    RN_TRY(rn_detection_rois_window(ctx, boxes + row0 * 4, labels + row0, img0, B, D, rois));
-    RN_TRY(rn_roi_align_nhwc_window(ctx, RN_DTYPE_F32, n_levels, maps, hs, ws, scales, thr, images, img0, B, 1, h->Cin, rois, K, M,
-                                    M, q->sampling_ratio, q->aligned, pooled, NULL));
-    return rn_mask_head_step(h, ctx, pooled, labels + row0, boxes + row0 * 4, srow0, K, image_h, image_w, q->threshold,
-                             q->probs ? q->probs + row0 * 4 * M * M : NULL, q->masks ? q->masks + row0 * plane : NULL,
-                             q->bits ? q->bits + row0 * plane : NULL);
+    *s = {};
+    if (!h) return;
+    s->who = "mask", s->stage = "mask_stage", s->tower = &h->tower, s->head = h, s->req = q;
+    s->check = mask_head_check, s->operands = mask_head_operands, s->behind = mask_head_behind;
+    if (q) s->pool = {q->n_levels, q->level, q->sampling_ratio, q->aligned, q->canonical_scale, q->canonical_level, q->rois, q->pooled};
 }
 
 int rn_mask_head_forward(rn_mask_head *h, const float *pooled_nhwc, const int32_t *labels, const float *boxes, uint64_t K,
                          uint64_t image_h, uint64_t image_w, const rn_mask_request *req)
 {
     if (!h) return RN_ERR_INVALID;
-    rn_ctx *ctx = h->ctx;
+    rn_ctx *ctx = h->tower.ctx;
     RN_ENTER(ctx);
-    RN_REQUIRE(ctx, h->finalized, "the mask head is not finalized");
-    RN_TRY(rn_mask_head_check(h, ctx, __func__, req, K, boxes != NULL, image_h, image_w));
+    RN_REQUIRE(ctx, h->tower.finalized, "the mask head is not finalized");
+    rn_roi_head s;
+    rn_mask_head_slot(h, req, &s);
+    RN_TRY(mask_head_check(&s, ctx, __func__, K, boxes != NULL, image_h, image_w));
     if (K == 0) return RN_OK;
-    RN_REQUIRE(ctx, pooled_nhwc, "pooled_nhwc is NULL");
-    RN_REQUIRE(ctx, labels, "labels is NULL");
-    RN_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(pooled_nhwc) & 15) == 0, "pooled_nhwc is off a 16-byte boundary");
-    const uint64_t M = h->M;
-    operand ops[RN_MASK_HEAD_OPERANDS + 3];
-    rn_mask_head_operands(h, req, K, image_h, image_w, ops);
+    operand ops[RN_ROI_HEAD_OPERANDS + 3];
+    mask_head_operands(&s, K, image_h, image_w, ops);
     ops[0].ptr = ops[1].ptr = NULL;  // the request's rois and pooled are the route's: nothing here writes them
-    ops[5] = {pooled_nhwc, K * M * M * h->Cin * 4, "pooled_nhwc", false, false};
+    ops[5] = {pooled_nhwc, K * h->tower.M * h->tower.M * h->tower.Cin * 4, "pooled_nhwc", false, false};
     ops[6] = {labels, K * 4, "labels", false, false};
     ops[7] = {boxes, K * 16, "boxes", false, false};
-    RN_TRY(check_operands(ctx, __func__, ops, RN_MASK_HEAD_OPERANDS + 3));
-    RN_TRY(rn_mask_head_reserve(h, K, 0));
-    const int saved_layout = ctx->layout;
-    ctx->layout = RN_LAYOUT_NHWC;
-    const int st = rn_mask_head_step(h, ctx, pooled_nhwc, labels, boxes, 0, K, image_h, image_w, req->threshold, req->probs,
-                                     req->masks, req->bits);
-    ctx->layout = saved_layout;
-    return st;
+    return rn_roi_head_forward(&s, __func__, pooled_nhwc, labels ? NULL : "labels is NULL", ops, RN_ROI_HEAD_OPERANDS + 3, labels, boxes,
+                               K, image_h, image_w);
 }
 
 }  // extern "C"

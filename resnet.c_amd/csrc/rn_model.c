@@ -2012,7 +2012,7 @@ int rn_model_forward_masks(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, rn_box_head *b
                            const rn_mask_request *mask_req, int mode)
 {
     rn_neck_call c = neck_call(fpn, rois, rpn, req, bh, det_req);
-    c.mask_head = mh, c.mask_req = mask_req;
+    rn_mask_head_slot(mh, mask_req, &c.head[RN_NECK_MASK_SLOT]);
     if (m && (!rpn || !req)) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_masks: rpn or req is NULL");
     if (m && !mh) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_masks: the mask head is NULL");
     return forward_fpn(m, __func__, &c, input_nchw, 0, B, outs, stages, fpn_out, mode);
@@ -2024,7 +2024,7 @@ int rn_model_forward_masks_u8(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, rn_box_head
                               const rn_mask_request *mask_req, int mode)
 {
     rn_neck_call c = neck_call(fpn, rois, rpn, req, bh, det_req);
-    c.mask_head = mh, c.mask_req = mask_req;
+    rn_mask_head_slot(mh, mask_req, &c.head[RN_NECK_MASK_SLOT]);
     if (m && (!rpn || !req)) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_masks: rpn or req is NULL");
     if (m && !mh) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_masks: the mask head is NULL");
     return forward_fpn(m, "rn_model_forward_masks", &c, input_nhwc, 1, B, outs, stages, fpn_out, mode);
@@ -2037,7 +2037,7 @@ int rn_model_forward_keypoints(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, rn_box_hea
                                int mode)
 {
     rn_neck_call c = neck_call(fpn, rois, rpn, req, bh, det_req);
-    c.mask_head = mh, c.mask_req = mask_req, c.kp_head = kh, c.kp_req = kp_req;
+    rn_mask_head_slot(mh, mask_req, &c.head[RN_NECK_MASK_SLOT]), rn_keypoint_head_slot(kh, kp_req, &c.head[RN_NECK_KEYPOINT_SLOT]);
     if (m && (!rpn || !req)) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_keypoints: rpn or req is NULL");
     if (m && !kh) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_keypoints: the keypoint head is NULL");
     return forward_fpn(m, __func__, &c, input_nchw, 0, B, outs, stages, fpn_out, mode);
@@ -2050,7 +2050,7 @@ int rn_model_forward_keypoints_u8(rn_model *m, rn_fpn *fpn, rn_rpn *rpn, rn_box_
                                   const rn_keypoint_request *kp_req, int mode)
 {
     rn_neck_call c = neck_call(fpn, rois, rpn, req, bh, det_req);
-    c.mask_head = mh, c.mask_req = mask_req, c.kp_head = kh, c.kp_req = kp_req;
+    rn_mask_head_slot(mh, mask_req, &c.head[RN_NECK_MASK_SLOT]), rn_keypoint_head_slot(kh, kp_req, &c.head[RN_NECK_KEYPOINT_SLOT]);
     if (m && (!rpn || !req)) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_keypoints: rpn or req is NULL");
     if (m && !kh) return rn_ctx_set_error(m->ctx, RN_ERR_INVALID, "rn_model_forward_keypoints: the keypoint head is NULL");
     return forward_fpn(m, "rn_model_forward_keypoints", &c, input_nhwc, 1, B, outs, stages, fpn_out, mode);

@@ -182,57 +182,102 @@ int rn_box_head_operands(const rn_box_head *bh, const rn_detect_request *req, ui
 int rn_box_head_step(rn_box_head *bh, rn_ctx *ctx, const float *pooled, const float *rois, uint64_t sub0, uint64_t img0,
                      uint64_t B, uint64_t R, uint64_t image_h, uint64_t image_w, const rn_detect_request *req);
 
-/* ---- rn_mask.hip: the mask head behind the box head (its parameters, units and scratch: rn_stage.hip) ---- */
-/* 1 when the mask head is finalized, lives on ctx's device and reads in_channels channels per pooled pixel; *why otherwise */
-int rn_mask_head_matches(const rn_mask_head *mh, const rn_ctx *ctx, uint64_t in_channels, const char **why);
-/* M: the side of the pooled map the head reads */
-uint64_t rn_mask_head_resolution(const rn_mask_head *mh);
-/* the object's scratch for `rows` detections; with_pool: the RoI rows and the pooled features of a stage behind a neck too */
-int rn_mask_head_reserve(rn_mask_head *mh, uint64_t rows, int with_pool);
-/* every refusal that concerns the request's outputs and the shapes alone, for `rows` detections (text in ctx, under fn);
- * paste_possible: the caller has the boxes a paste needs */
-int rn_mask_head_check(const rn_mask_head *mh, rn_ctx *ctx, const char *fn, const rn_mask_request *req, uint64_t rows,
-                       int paste_possible, uint64_t image_h, uint64_t image_w);
-/* the request's 5 outputs for `rows` detections as operands; returns 5 */
-enum { RN_MASK_HEAD_OPERANDS = 5 };
-int rn_mask_head_operands(const rn_mask_head *mh, const rn_mask_request *req, uint64_t rows, uint64_t image_h, uint64_t image_w,
-                          rn_operand ops[RN_MASK_HEAD_OPERANDS]);
-/* The stage's launches on ctx for the B images from the caller's image img0 on (D detections each), whose scratch starts
- * sub0 images into the object's tensors: the RoI former on these images' detection rows, the NHWC pooler on maps[i]
- * (level i of image img0, h[i] x w[i], fp32), then n_layers + 1 contractions of one or two launches, the predict launch
- * and the paste where wanted.  boxes [images*D, 4], labels [images*D] and the request's outputs: the whole call's. */
-int rn_mask_head_stage(rn_mask_head *mh, rn_ctx *ctx, uint64_t n_levels, const void *const *maps, const uint64_t *h,
-                       const uint64_t *w, const float *scales, const float *thr, uint64_t images, uint64_t sub0, uint64_t img0,
-                       uint64_t B, uint64_t D, const float *boxes, const int32_t *labels, uint64_t image_h, uint64_t image_w,
-                       const rn_mask_request *req);
+/* ---- rn_stage.hip: the RoI tower under the mask head and the keypoint head.  Pooled [K, M, M, Cin] through n_layers
+ * 3x3 convolutions with bias and ReLU over two ping-pong maps, then ONE 1x1 panel that stands for the head's transposed
+ * convolution; behind a neck the RoI former and the NHWC pooler in front.  A head embeds one tower, sets what differs
+ * (name .. extra_floats) at create time and keeps only its predictor. ---- */
+enum { RN_TOWER_MAX_LAYERS = 8, RN_TOWER_ROWS = 0, RN_TOWER_POOL = 1, RN_TOWER_SCRATCH = 6 };
+typedef struct rn_roi_tower {
+    rn_ctx *ctx;
+    const char *name, *what;            /* the words of its messages: "rn_mask_head", "the mask head" */
+    uint64_t Cin, n_layers, ch[RN_TOWER_MAX_LAYERS], M, widest;
+    uint64_t panel;                     /* the panel's output channels */
+    int panel_relu;                     /* the panel's epilogue has ReLU (its shift: whatever the head packed) */
+    uint64_t extra_floats;              /* one further scratch tensor of so many floats per pooled pixel, or 0 */
+    int finalized;
+    rn_params params;                   /* layer i: 2i, 2i + 1; the head's predictor entries behind them, from 2n on */
+    rn_stage_unit unit[RN_TOWER_MAX_LAYERS + 1]; /* the 3x3 layers, then the panel Clast -> panel */
+    /* scratch for cap rows: two ping-pong maps [., M, M, widest], the panel's output [., M, M, panel], the extra tensor */
+    float *ping, *pong, *t, *extra;
+    float *rois, *pooled;               /* behind a neck: the RoI rows [., 5] and the pooled features [., M, M, Cin] of cap_pool rows */
+    uint64_t cap[2];                    /* rows (RN_TOWER_ROWS), of them with RoI rows and pooled features (RN_TOWER_POOL) */
+} rn_roi_tower;
+/* the spelling of layer i's tensor `leaf` ("weight", "bias"); alt: another spelling, or "" */
+typedef void (*rn_roi_tower_key)(int layer, const char *leaf, char key[RN_PARAM_KEY], char alt[RN_PARAM_KEY]);
+/* The refusals of a head's create under the name fn, in their order: in_channels, n_layers, layer_channels, then `own`
+ * (the head's own refusal, or NULL: it always stood here), then resolution against the head's limit. */
+int rn_roi_tower_check(rn_ctx *ctx, const char *fn, uint64_t in_channels, uint64_t n_layers, const uint64_t *layer_channels,
+                       const char *own, uint64_t resolution, uint64_t max_resolution);
+/* a zeroed tower whose name .. extra_floats the head has set: the shapes, ch and widest, the prefix "roi_heads." and the
+ * 2 n_layers layer entries of the parameter table (the head adds its predictor's behind them) */
+void rn_roi_tower_init(rn_roi_tower *t, rn_ctx *ctx, uint64_t in_channels, uint64_t n_layers, const uint64_t *layer_channels,
+                       uint64_t resolution, rn_roi_tower_key key);
+/* the front of a finalize under the name fn: "is not set", then the n_layers packs */
+int rn_roi_tower_pack_layers(rn_roi_tower *t, const char *fn);
+/* the head's reordered transposed convolution as the panel: w [panel, Clast], shift [panel] or NULL */
+int rn_roi_tower_pack_panel(rn_roi_tower *t, const float *w, const float *shift);
+/* the scratch, the host copies and the units; the context is idle */
+void rn_roi_tower_free(rn_roi_tower *t);
+/* 1 when the tower is finalized, lives on ctx's device and reads in_channels channels per pooled pixel; *why: what is
+ * wrong otherwise, to stand behind "the mask" / "the keypoint" ("head is not finalized") */
+int rn_roi_tower_matches(const rn_roi_tower *t, const rn_ctx *ctx, uint64_t in_channels, const char **why);
+/* the scratch for `rows` detections (rn_stage_grow's rule); with_pool: the RoI rows and the pooled features of a stage
+ * behind a neck as well */
+int rn_roi_tower_reserve(rn_roi_tower *t, uint64_t rows, int with_pool);
 
-/* ---- rn_keypoint.hip: the keypoint head behind the box head (its parameters, units and scratch: rn_stage.hip) ---- */
-/* 1 when the keypoint head is finalized, lives on ctx's device and reads in_channels channels per pooled pixel; *why otherwise */
-int rn_keypoint_head_matches(const rn_keypoint_head *kh, const rn_ctx *ctx, uint64_t in_channels, const char **why);
-/* M: the side of the pooled map the head reads */
-uint64_t rn_keypoint_head_resolution(const rn_keypoint_head *kh);
-/* the object's scratch for `rows` detections; with_pool: the RoI rows and the pooled features of a stage behind a neck too */
-int rn_keypoint_head_reserve(rn_keypoint_head *kh, uint64_t rows, int with_pool);
-/* every refusal that concerns the request's outputs and the shapes alone, for `rows` detections (text in ctx, under fn);
- * boxes_given: the caller has the boxes the search needs */
-int rn_keypoint_head_check(const rn_keypoint_head *kh, rn_ctx *ctx, const char *fn, const rn_keypoint_request *req, uint64_t rows,
-                           int boxes_given, uint64_t image_h, uint64_t image_w);
-/* the request's 5 outputs for `rows` detections as operands; returns 5 */
-enum { RN_KEYPOINT_HEAD_OPERANDS = 5 };
-int rn_keypoint_head_operands(const rn_keypoint_head *kh, const rn_keypoint_request *req, uint64_t rows,
-                              rn_operand ops[RN_KEYPOINT_HEAD_OPERANDS]);
-/* The stage's launches on ctx for the B images from the caller's image img0 on (D detections each), whose scratch starts
- * sub0 images into the object's tensors: the RoI former on these images' detection rows, the NHWC pooler on maps[i]
- * (level i of image img0, h[i] x w[i], fp32), then n_layers + 1 contractions of one or two launches and the predict
- * launch.  boxes [images*D, 4], labels [images*D] and the request's outputs: the whole call's. */
-int rn_keypoint_head_stage(rn_keypoint_head *kh, rn_ctx *ctx, uint64_t n_levels, const void *const *maps, const uint64_t *h,
-                           const uint64_t *w, const float *scales, const float *thr, uint64_t images, uint64_t sub0, uint64_t img0,
-                           uint64_t B, uint64_t D, const float *boxes, const int32_t *labels, uint64_t image_h, uint64_t image_w,
-                           const rn_keypoint_request *req);
+/* the pooler's fields of a head's request (the public request structs hold them in different places) */
+typedef struct rn_roi_pool_view {
+    int n_levels;
+    const int *level;
+    int sampling_ratio, aligned;
+    double canonical_scale;
+    int canonical_level;
+    float *rois, *pooled;               /* the request's outputs [rows, 5] and [rows, M, M, Cin], or NULL */
+} rn_roi_pool_view;
+/* A RoI head as the neck call and the tower's two forwards see it: the tower, the pooler's view, and the three things
+ * that differ between heads.  rn_mask_head_slot / rn_keypoint_head_slot fill it (tower NULL: no such head). */
+enum { RN_ROI_HEAD_OPERANDS = 5 };
+typedef struct rn_roi_head {
+    const char *who, *stage;            /* "mask", "keypoint" in the refusals; the stage's profile name ("mask_stage") */
+    rn_roi_tower *tower;
+    const void *head, *req;             /* the head's own: what the three functions read */
+    rn_roi_pool_view pool;
+    /* every refusal that concerns the request's outputs and the shapes alone, for `rows` detections (text in ctx, under
+     * fn); boxes_given: the caller has the boxes a paste or a search needs */
+    int (*check)(const struct rn_roi_head *s, rn_ctx *ctx, const char *fn, uint64_t rows, int boxes_given, uint64_t image_h,
+                 uint64_t image_w);
+    /* the request's 5 outputs for `rows` detections as operands, rois and pooled first; returns 5 */
+    int (*operands)(const struct rn_roi_head *s, uint64_t rows, uint64_t image_h, uint64_t image_w, rn_operand ops[RN_ROI_HEAD_OPERANDS]);
+    /* the launches behind the tower for K detections from row row0 of the request's outputs on: t and extra are the
+     * panel's output and the extra tensor of these rows; labels and boxes point at these rows */
+    int (*behind)(const struct rn_roi_head *s, rn_ctx *ctx, const float *t, float *extra, const int32_t *labels, const float *boxes,
+                  uint64_t row0, uint64_t K, uint64_t image_h, uint64_t image_w);
+    float scales[4], thr[3];            /* rn_neck_check: the pooler's levels' scales and the thresholds between them */
+} rn_roi_head;
+void rn_mask_head_slot(rn_mask_head *mh, const rn_mask_request *req, rn_roi_head *s);
+void rn_keypoint_head_slot(rn_keypoint_head *kh, const rn_keypoint_request *req, rn_roi_head *s);
+/* The head's launches on ctx for K detections whose scratch starts sub0 rows into the tower's tensors: n_layers + 1
+ * contractions of one or two launches, then the head's own.  ctx->layout is NHWC. */
+int rn_roi_head_step(const rn_roi_head *s, rn_ctx *ctx, const float *pooled_nhwc, const int32_t *labels, const float *boxes,
+                     uint64_t sub0, uint64_t row0, uint64_t K, uint64_t image_h, uint64_t image_w);
+/* The stage behind a neck for the B images from the caller's image img0 on (D detections each), whose scratch starts
+ * sub0 images into the tower's tensors: the RoI former on these images' detection rows, the NHWC pooler on maps[i]
+ * (level i of image img0, h[i] x w[i], fp32), then rn_roi_head_step.  boxes [images*D, 4], labels [images*D] and the
+ * request's outputs: the whole call's. */
+int rn_roi_head_stage(const rn_roi_head *s, rn_ctx *ctx, const void *const *maps, const uint64_t *h, const uint64_t *w,
+                      uint64_t images, uint64_t sub0, uint64_t img0, uint64_t B, uint64_t D, const float *boxes,
+                      const int32_t *labels, uint64_t image_h, uint64_t image_w);
+/* The frame of a stand-alone *_forward under the name fn, behind the head's own request check: pooled_nhwc's NULL
+ * refusal, `own` (the head's refusal that stands here, or NULL), its alignment, the operand list, the reserve, and the
+ * step with ctx->layout NHWC around it. */
+int rn_roi_head_forward(const rn_roi_head *s, const char *fn, const float *pooled_nhwc, const char *own, const rn_operand *ops,
+                        int n_ops, const int32_t *labels, const float *boxes, uint64_t K, uint64_t image_h, uint64_t image_w);
 
 /* ---- rn_fpn.hip: one forward of a neck and what runs behind it, for both entry families ---- */
 /* The description of a call.  It lives on the stack of the entry point that runs it (rn_fpn_forward*, the model's
- * forward_fpn); rn_neck_check fills the second half once and everything after it only reads. */
+ * forward_fpn); rn_neck_check fills the second half (and the heads' scales and thresholds) once and everything after
+ * it only reads. */
+enum { RN_NECK_MASK_SLOT = 0, RN_NECK_KEYPOINT_SLOT = 1, RN_NECK_HEADS = 2 };
 typedef struct rn_neck_call {
     /* what the caller gave */
     rn_fpn *fpn;
@@ -242,10 +287,7 @@ typedef struct rn_neck_call {
     const rn_rpn_request *rpn_req;
     rn_box_head *box_head;          /* the box head behind the chained pooler and its request, or NULL */
     const rn_detect_request *det_req;
-    rn_mask_head *mask_head;        /* the mask head behind the box head and its request, or NULL */
-    const rn_mask_request *mask_req;
-    rn_keypoint_head *kp_head;      /* the keypoint head behind the box head and its request, or NULL */
-    const rn_keypoint_request *kp_req;
+    rn_roi_head head[RN_NECK_HEADS]; /* the RoI heads behind the box head and their requests (tower NULL: none) */
     uint64_t image_h, image_w;      /* the image the rpn and the box head clip to */
     uint64_t h[4], w[4];            /* the input levels' maps */
     uint64_t images;                /* the batch of the whole call */
@@ -256,8 +298,6 @@ typedef struct rn_neck_call {
     int pool;                       /* the max-pool runs */
     int layer_runs[4];              /* the 3x3 of the level runs: exported, pooled from, or read by the pooler / the rpn */
     float scales[4], thr[3];        /* the pooler's levels' scales and the thresholds between them */
-    float mask_scales[4], mask_thr[3]; /* the mask pooler's */
-    float kp_scales[4], kp_thr[3];     /* the keypoint pooler's */
 } rn_neck_call;
 /* Every refusal the two families share, in one order: the neck, the outputs' alignment, nothing wanted, the pooler's
  * request, the rpn and its request, the box head's conditions and request, the mask head's, the keypoint head's, then the operand matrix: no

@@ -13,17 +13,21 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import Handle
+from . import roi
 
 F = np.float32
 PREDICTOR_KEYS = ("keypoint_predictor.kps_score_lowres.weight", "keypoint_predictor.kps_score_lowres.bias")
 
 
 # ---- the head's state ------------------------------------------------------------------------------------------
+def _stem(i: int) -> str:
+    return f"keypoint_head.{2 * i}."
+
+
 def layer_keys(n_layers: int) -> tuple:
     """(weight key, bias key) of every 3x3 layer: KeypointRCNNHeads is a Sequential of (conv, ReLU) pairs, so layer i
     is "keypoint_head.{2i}." """
-    return tuple((f"keypoint_head.{2 * i}.weight", f"keypoint_head.{2 * i}.bias") for i in range(int(n_layers)))
+    return tuple((_stem(i) + "weight", _stem(i) + "bias") for i in range(int(n_layers)))
 
 
 def head_shapes(in_channels: int, layers, keypoints: int) -> dict:
@@ -48,24 +52,12 @@ def _normal_key(key: str):
 
 def split_state(state) -> tuple:
     """(the keypoint head's tensors without the "roi_heads." prefix, the rest): takes both spellings"""
-    mine, rest = {}, {}
-    for k, v in (state or {}).items():
-        key = _normal_key(k)
-        if key is None:
-            rest[k] = v
-        else:
-            mine[key] = v
-    return mine, rest
+    return roi.split_state(state or {}, _normal_key)
 
 
 def layers_of(state) -> tuple:
     """the layers' channel counts a state holds, from its 3x3 weights in order"""
-    mine, _ = split_state(state)
-    out, i = [], 0
-    while f"keypoint_head.{2 * i}.weight" in mine:
-        out.append(int(np.shape(mine[f"keypoint_head.{2 * i}.weight"])[0]))
-        i += 1
-    return tuple(out)
+    return roi.layer_widths(split_state(state)[0], _stem)
 
 
 def generate_keypoint_head_state(in_channels: int, layers=(512,) * 8, keypoints: int = 17, seed: int = 0, prefix: str = "") -> dict:
@@ -239,17 +231,10 @@ def heatmaps_to_keypoints_ref(heat, boxes, max_size, labels=None):
 def keypoint_head_ref(pooled_nchw, state, layers: bool = False):
     """KeypointRCNNHeads and KeypointRCNNPredictor in float64 on pooled [K, a, M, M]: heat [K, Kp, 4M, 4M].  layers=True:
     the list of every layer's output instead (the 3x3s as NCHW, then the heat maps)"""
-    from .mask import _conv3x3_f64
     st, _ = split_state(state)
-    x = np.asarray(pooled_nchw, dtype=np.float64)
-    outs, i = [], 0
-    while f"keypoint_head.{2 * i}.weight" in st:
-        x = np.maximum(_conv3x3_f64(x, np.asarray(st[f"keypoint_head.{2 * i}.weight"], dtype=np.float64),
-                                    np.asarray(st[f"keypoint_head.{2 * i}.bias"], dtype=np.float64)), 0.0)
-        outs.append(x)
-        i += 1
+    outs = roi.tower_f64(pooled_nchw, st, _stem)
     rows = deconv_panel(np.asarray(st[PREDICTOR_KEYS[0]], dtype=np.float64))
-    t = np.einsum("kchw,oc->khwo", x, rows, optimize=True)
+    t = np.einsum("kchw,oc->khwo", outs[-1], rows, optimize=True)
     outs.append(heatmaps_ref(t, np.asarray(st[PREDICTOR_KEYS[1]], dtype=np.float64), np.float64))
     return outs if layers else outs[-1]
 
@@ -280,60 +265,30 @@ def output_spec(B: int, D: int, M: int, a: int, Kp: int, keypoints=("keypoints",
     return spec
 
 
-class KeypointHead(Handle):
+class KeypointHead(roi.RoIHead):
     """rn_keypoint_head_*: KeypointRCNNHeads (3x3 convolutions with bias and ReLU), kps_score_lowres as one 1x1 panel of
     16 * Kp channels, then ONE predict launch: overlap-add, 2x bilinear, bicubic resize into the box and argmax.  state
     holds the head's tensors with or without the "roi_heads." prefix.  featmap_names, sampling_ratio: the keypoint pooler
     of a forward behind a neck."""
-    DESTROY = "rn_keypoint_head_destroy"
+    NAME, DESTROY = "rn_keypoint_head", "rn_keypoint_head_destroy"
 
     def __init__(self, in_channels: int, layers=(512,) * 8, keypoints: int = 17, state=None, resolution: int = 14,
                  featmap_names=("0", "1", "2", "3"), sampling_ratio: int = 2, ctx=None):
-        import ctypes
-        from . import _lib as L
-        from . import roi
-        from .tensor import get_ctx
-        self.ctx = ctx or get_ctx()
-        self.in_channels, self.layers = int(in_channels), tuple(int(c) for c in layers)
-        self.keypoints, self.resolution = int(keypoints), int(resolution)
-        self.pooler = roi.MultiScaleRoIAlign(featmap_names, self.resolution, sampling_ratio)
-        self.handle = None
-        self.poison = False   # buffers() fills every output with 0xA5 bytes first (tests: a row never written shows)
-        h = ctypes.c_void_p()
-        ch = (ctypes.c_uint64 * max(len(self.layers), 1))(*self.layers)
-        L.check(L.lib().rn_keypoint_head_create(self.ctx.handle, ctypes.byref(h), self.in_channels, len(self.layers), ch,
-                                                self.keypoints, self.resolution), "rn_keypoint_head_create", self.ctx.handle)
-        self.handle = h
-        mine, _ = split_state(state)
-        L.set_tensors(h, "rn_keypoint_head", self.ctx, head_shapes(self.in_channels, self.layers, self.keypoints), mine)
+        self.keypoints = int(keypoints)
+        super().__init__(in_channels, layers, (self.keypoints,), resolution, featmap_names, sampling_ratio, head_shapes,
+                         split_state(state)[0], ctx)
 
     def buffers(self, B: int, D: int, keypoints=("keypoints",)):
         """device buffers of a forward of B images of D detections: (spec, buffers)"""
-        from . import _lib as L
-        from .tensor import _DeviceBuffer
-        spec = output_spec(B, D, self.resolution, self.in_channels, self.keypoints, keypoints)
-        bufs = {k: _DeviceBuffer(self.ctx, max(int(np.prod(sh)) * np.dtype(t).itemsize, 16)) for k, (t, sh) in spec.items()}
-        if self.poison:
-            for k, (t, sh) in spec.items():
-                L.check(L.lib().rn_memset(self.ctx.handle, bufs[k].ptr, 0xA5, int(np.prod(sh)) * np.dtype(t).itemsize), "rn_memset",
-                        self.ctx.handle)
-        return spec, bufs
+        return self.alloc(output_spec(B, D, self.resolution, self.in_channels, self.keypoints, keypoints))
 
     def request(self, bufs, names=None):
         """the rn_keypoint_request over a mapping name -> object with .ptr (missing names are NULL); names: the level
         names of the neck the pooler reads (None: a stand-alone forward, which has no pooler)"""
-        import ctypes
         from . import _lib as L
         p = lambda k: bufs[k].ptr if k in bufs else None  # noqa: E731
-        idx = self.pooler.level_indices(names) if names is not None else ()
-        return L.KeypointRequest(len(idx), (ctypes.c_int * 4)(*(idx + (0,) * (4 - len(idx)))), self.pooler.sampling_ratio,
-                                 int(self.pooler.aligned), self.pooler.canonical_scale, self.pooler.canonical_level,
-                                 p("keypoint_rois"), p("keypoint_pooled"), p("keypoint_heatmaps"), p("keypoints"),
-                                 p("keypoints_scores"))
-
-    def collect(self, spec, bufs) -> dict:
-        from .ops import _down_raw
-        return {k: _down_raw(bufs[k], t, int(np.prod(sh))).reshape(sh) for k, (t, sh) in spec.items()}
+        return L.KeypointRequest(*self.pool_fields(names), p("keypoint_rois"), p("keypoint_pooled"), p("keypoint_heatmaps"),
+                                 p("keypoints"), p("keypoints_scores"))
 
     def __call__(self, pooled_nhwc, labels=None, boxes=None, image_size=None, keypoints=("keypoints",)) -> dict:
         """pooled_nhwc [K,M,M,a], labels [K] (or None: all valid) and boxes [K,4] host arrays: the stand-alone run.

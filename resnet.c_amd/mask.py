@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import Handle
+from . import roi
 
 F = np.float32
 PREDICTOR_KEYS = ("mask_predictor.conv5_mask.weight", "mask_predictor.conv5_mask.bias",
@@ -21,10 +21,14 @@ PREDICTOR_KEYS = ("mask_predictor.conv5_mask.weight", "mask_predictor.conv5_mask
 
 
 # ---- the head's state ------------------------------------------------------------------------------------------
+def _stem(i: int) -> str:
+    return f"mask_head.{i}.0."
+
+
 def layer_keys(n_layers: int, old: bool = False) -> tuple:
     """(weight key, bias key) of every 3x3 layer: torchvision's spelling since 0.13 ("mask_head.{i}.0.") or the one
     before it ("mask_head.mask_fcn{i+1}.")"""
-    stem = (lambda i: f"mask_head.mask_fcn{i + 1}.") if old else (lambda i: f"mask_head.{i}.0.")
+    stem = (lambda i: f"mask_head.mask_fcn{i + 1}.") if old else _stem
     return tuple((stem(i) + "weight", stem(i) + "bias") for i in range(int(n_layers)))
 
 
@@ -52,24 +56,12 @@ def _normal_key(key: str):
 def split_state(state) -> tuple:
     """(the mask head's tensors under the new spelling's keys, the rest): takes both spellings, with or without the
     "roi_heads." prefix"""
-    mine, rest = {}, {}
-    for k, v in state.items():
-        key = _normal_key(k)
-        if key is None:
-            rest[k] = v
-        else:
-            mine[key] = v
-    return mine, rest
+    return roi.split_state(state, _normal_key)
 
 
 def layers_of(state) -> tuple:
     """the layers' channel counts a state holds, from its 3x3 weights in order"""
-    mine, _ = split_state(state)
-    out, i = [], 0
-    while f"mask_head.{i}.0.weight" in mine:
-        out.append(int(np.shape(mine[f"mask_head.{i}.0.weight"])[0]))
-        i += 1
-    return tuple(out)
+    return roi.layer_widths(split_state(state)[0], _stem)
 
 
 def generate_mask_head_state(in_channels: int, layers=(256,) * 4, dim_reduced: int = 256, classes: int = 91, seed: int = 0,
@@ -92,16 +84,6 @@ def generate_mask_head_state(in_channels: int, layers=(256,) * 4, dim_reduced: i
 
 
 # ---- float64 references ----------------------------------------------------------------------------------------
-def _conv3x3_f64(x, w, b):
-    """x [K,C,H,W], w [O,C,3,3], b [O]: padding 1, float64"""
-    K, C, H, W = x.shape
-    xp = np.zeros((K, C, H + 2, W + 2))
-    xp[:, :, 1:-1, 1:-1] = x
-    cols = np.stack([xp[:, :, dy:dy + H, dx:dx + W] for dy in range(3) for dx in range(3)], axis=2)  # [K,C,9,H,W]
-    y = np.einsum("kcthw,oct->kohw", cols, w.reshape(w.shape[0], C, 9), optimize=True)
-    return y + b[None, :, None, None]
-
-
 def deconv_panel(weight, bias):
     """ConvTranspose2d(Cin, Cr, 2, 2) as ONE 1x1 panel: (rows [4*Cr, Cin], shift [4*Cr]) with row (dy*2+dx)*Cr + co =
     W[:, co, dy, dx] and the bias four times -- exact, kernel 2 at stride 2 overlaps nothing"""
@@ -130,15 +112,9 @@ def mask_head_ref(pooled_nchw, state, layers: bool = False):
     """MaskRCNNHeads and conv5_mask with its ReLU in float64 on pooled [K,a,M,M]: [K,Cr,2M,2M], what mask_fcn_logits
     reads.  layers=True: the list of every layer's output instead (the 3x3s, then the transposed convolution)"""
     st, _ = split_state(state)
-    x = np.asarray(pooled_nchw, dtype=np.float64)
-    outs, i = [], 0
-    while f"mask_head.{i}.0.weight" in st:
-        x = np.maximum(_conv3x3_f64(x, np.asarray(st[f"mask_head.{i}.0.weight"], dtype=np.float64),
-                                    np.asarray(st[f"mask_head.{i}.0.bias"], dtype=np.float64)), 0.0)
-        outs.append(x)
-        i += 1
+    outs = roi.tower_f64(pooled_nchw, st, _stem)
     rows, shift = deconv_panel(np.asarray(st[PREDICTOR_KEYS[0]], dtype=np.float64), np.asarray(st[PREDICTOR_KEYS[1]], dtype=np.float64))
-    t = np.maximum(np.einsum("kchw,oc->khwo", x, rows, optimize=True) + shift, 0.0)
+    t = np.maximum(np.einsum("kchw,oc->khwo", outs[-1], rows, optimize=True) + shift, 0.0)
     outs.append(panel_to_nchw(t))
     return outs if layers else outs[-1]
 
@@ -256,61 +232,31 @@ def output_spec(B: int, D: int, M: int, a: int, image_size, masks=("probs",), ro
     return spec
 
 
-class MaskHead(Handle):
+class MaskHead(roi.RoIHead):
     """rn_mask_head_*: MaskRCNNHeads (3x3 convolutions with bias and ReLU), MaskRCNNPredictor's transposed convolution as
     one 1x1 panel, then the class-selected predict launch and the paste.  state holds the head's tensors in either
     spelling (split_state normalises the keys).  featmap_names, sampling_ratio: the mask pooler of a forward behind a
     neck."""
-    DESTROY = "rn_mask_head_destroy"
+    NAME, DESTROY = "rn_mask_head", "rn_mask_head_destroy"
 
     def __init__(self, in_channels: int, layers=(256,) * 4, dim_reduced: int = 256, classes: int = 91, state=None,
                  resolution: int = 14, featmap_names=("0", "1", "2", "3"), sampling_ratio: int = 2, threshold: float = 0.5,
                  ctx=None):
-        import ctypes
-        from . import _lib as L
-        from . import roi
-        from .tensor import get_ctx
-        self.ctx = ctx or get_ctx()
-        self.in_channels, self.layers = int(in_channels), tuple(int(c) for c in layers)
-        self.dim_reduced, self.classes, self.resolution = int(dim_reduced), int(classes), int(resolution)
-        self.threshold = float(threshold)
-        self.pooler = roi.MultiScaleRoIAlign(featmap_names, self.resolution, sampling_ratio)
-        self.handle = None
-        self.poison = False   # buffers() fills every output with 0xA5 bytes first (tests: a row never written shows)
-        h = ctypes.c_void_p()
-        ch = (ctypes.c_uint64 * max(len(self.layers), 1))(*self.layers)
-        L.check(L.lib().rn_mask_head_create(self.ctx.handle, ctypes.byref(h), self.in_channels, len(self.layers), ch,
-                                            self.dim_reduced, self.classes, self.resolution), "rn_mask_head_create", self.ctx.handle)
-        self.handle = h
-        mine, _ = split_state(state)
-        L.set_tensors(h, "rn_mask_head", self.ctx, head_shapes(self.in_channels, self.layers, self.dim_reduced, self.classes), mine)
+        self.dim_reduced, self.classes, self.threshold = int(dim_reduced), int(classes), float(threshold)
+        super().__init__(in_channels, layers, (self.dim_reduced, self.classes), resolution, featmap_names, sampling_ratio,
+                         head_shapes, split_state(state)[0], ctx)
 
     def buffers(self, B: int, D: int, image_size, masks=("probs",), rois: bool = False, pooled: bool = False):
         """device buffers of a forward of B images of D detections: (spec, buffers)"""
-        from . import _lib as L
-        from .tensor import _DeviceBuffer
-        spec = output_spec(B, D, self.resolution, self.in_channels, image_size, masks, rois, pooled)
-        bufs = {k: _DeviceBuffer(self.ctx, max(int(np.prod(sh)) * np.dtype(t).itemsize, 16)) for k, (t, sh) in spec.items()}
-        if self.poison:
-            for k, (t, sh) in spec.items():
-                L.check(L.lib().rn_memset(self.ctx.handle, bufs[k].ptr, 0xA5, int(np.prod(sh)) * np.dtype(t).itemsize), "rn_memset",
-                        self.ctx.handle)
-        return spec, bufs
+        return self.alloc(output_spec(B, D, self.resolution, self.in_channels, image_size, masks, rois, pooled))
 
     def request(self, bufs, names=None):
         """the rn_mask_request over a mapping name -> object with .ptr (missing names are NULL); names: the level names
         of the neck the pooler reads (None: a stand-alone forward, which has no pooler)"""
-        import ctypes
         from . import _lib as L
         p = lambda k: bufs[k].ptr if k in bufs else None  # noqa: E731
-        idx = self.pooler.level_indices(names) if names is not None else ()
-        return L.MaskRequest(len(idx), (ctypes.c_int * 4)(*(idx + (0,) * (4 - len(idx)))), self.pooler.sampling_ratio,
-                             int(self.pooler.aligned), self.pooler.canonical_scale, self.pooler.canonical_level,
-                             self.threshold, p("mask_rois"), p("mask_pooled"), p("mask_probs"), p("masks"), p("mask_bits"))
-
-    def collect(self, spec, bufs) -> dict:
-        from .ops import _down_raw
-        return {k: _down_raw(bufs[k], t, int(np.prod(sh))).reshape(sh) for k, (t, sh) in spec.items()}
+        return L.MaskRequest(*self.pool_fields(names), self.threshold, p("mask_rois"), p("mask_pooled"), p("mask_probs"), p("masks"),
+                             p("mask_bits"))
 
     def __call__(self, pooled_nhwc, labels, boxes=None, image_size=None, masks=("probs",)) -> dict:
         """pooled_nhwc [K,M,M,a], labels [K] and boxes [K,4] host arrays: the stand-alone run.  Returns "mask_probs"

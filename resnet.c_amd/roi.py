@@ -106,3 +106,88 @@ def upload_rois(rois, images: int, validate: bool = True):
     if validate and not ops.roi_image_valid(rois, images).all():
         raise ValueError(f"a RoI's image index is no integer in [0, {images})")
     return ops._up_raw(rois), rois.shape[0]
+
+
+# ---- what the RoI heads behind the box head share (mask.py, keypoint.py): the tower of 3x3 layers --------------------
+def split_state(state, normal_key) -> tuple:
+    """(the tensors whose key normal_key knows, under the key it returns; the rest, for which it returns None)"""
+    mine, rest = {}, {}
+    for k, v in state.items():
+        key = normal_key(k)
+        if key is None:
+            rest[k] = v
+        else:
+            mine[key] = v
+    return mine, rest
+
+
+def layer_widths(mine, stem) -> tuple:
+    """the layers' channel counts a head's state holds, from its 3x3 weights stem(i) + "weight" in order"""
+    out = []
+    while stem(len(out)) + "weight" in mine:
+        out.append(int(np.shape(mine[stem(len(out)) + "weight"])[0]))
+    return tuple(out)
+
+
+def conv3x3_f64(x, w, b):
+    """x [K,C,H,W], w [O,C,3,3], b [O]: padding 1, float64"""
+    K, C, H, W = x.shape
+    xp = np.zeros((K, C, H + 2, W + 2))
+    xp[:, :, 1:-1, 1:-1] = x
+    cols = np.stack([xp[:, :, dy:dy + H, dx:dx + W] for dy in range(3) for dx in range(3)], axis=2)  # [K,C,9,H,W]
+    y = np.einsum("kcthw,oct->kohw", cols, w.reshape(w.shape[0], C, 9), optimize=True)
+    return y + b[None, :, None, None]
+
+
+def tower_f64(pooled_nchw, mine, stem) -> list:
+    """every 3x3 layer's output (convolution, bias, ReLU) in float64 on pooled [K,a,M,M], for as many layers stem(i) as
+    the state holds; the last one is what the head's transposed convolution reads"""
+    x, outs = np.asarray(pooled_nchw, dtype=np.float64), []
+    while stem(len(outs)) + "weight" in mine:
+        w, b = (np.asarray(mine[stem(len(outs)) + leaf], dtype=np.float64) for leaf in ("weight", "bias"))
+        x = np.maximum(conv3x3_f64(x, w, b), 0.0)
+        outs.append(x)
+    return outs
+
+
+class RoIHead(L.Handle):
+    """What MaskHead and KeypointHead are both: an object of the C library (NAME: "rn_mask_head") that reads pooled
+    [K, M, M, in_channels] through `layers` 3x3 convolutions, with the pooler of a forward behind a neck."""
+    NAME = ""
+
+    def __init__(self, in_channels: int, layers, own, resolution: int, featmap_names, sampling_ratio: int, shapes, mine, ctx=None):
+        """own: the head's own arguments of NAME_create, between layer_channels and resolution; shapes: key -> shape of
+        every tensor (own already in it); mine: the tensors"""
+        from .tensor import get_ctx
+        self.ctx = ctx or get_ctx()
+        self.in_channels, self.layers, self.resolution = int(in_channels), tuple(int(c) for c in layers), int(resolution)
+        self.pooler = MultiScaleRoIAlign(featmap_names, self.resolution, sampling_ratio)
+        self.handle = None
+        self.poison = False   # alloc() fills every output with 0xA5 bytes first (tests: a row never written shows)
+        h = ctypes.c_void_p()
+        ch = (ctypes.c_uint64 * max(len(self.layers), 1))(*self.layers)
+        create = self.NAME + "_create"
+        L.check(getattr(L.lib(), create)(self.ctx.handle, ctypes.byref(h), self.in_channels, len(self.layers), ch, *own,
+                                         self.resolution), create, self.ctx.handle)
+        self.handle = h
+        L.set_tensors(h, self.NAME, self.ctx, shapes(self.in_channels, self.layers, *own), mine)
+
+    def alloc(self, spec):
+        """device buffers of an output_spec: (spec, buffers)"""
+        from .tensor import _DeviceBuffer
+        bufs = {k: _DeviceBuffer(self.ctx, max(int(np.prod(sh)) * np.dtype(t).itemsize, 16)) for k, (t, sh) in spec.items()}
+        if self.poison:
+            for k, (t, sh) in spec.items():
+                L.check(L.lib().rn_memset(self.ctx.handle, bufs[k].ptr, 0xA5, int(np.prod(sh)) * np.dtype(t).itemsize), "rn_memset",
+                        self.ctx.handle)
+        return spec, bufs
+
+    def pool_fields(self, names) -> tuple:
+        """the pooler's six fields in front of a head's request; names: the level names of the neck the pooler reads
+        (None: a stand-alone forward, which has no pooler)"""
+        idx = self.pooler.level_indices(names) if names is not None else ()
+        return (len(idx), (ctypes.c_int * 4)(*(idx + (0,) * (4 - len(idx)))), self.pooler.sampling_ratio, int(self.pooler.aligned),
+                self.pooler.canonical_scale, self.pooler.canonical_level)
+
+    def collect(self, spec, bufs) -> dict:
+        return {k: ops._down_raw(bufs[k], t, int(np.prod(sh))).reshape(sh) for k, (t, sh) in spec.items()}

@@ -1,8 +1,9 @@
-"""What the five objects behind the backbone share (csrc/rn_stage.hip), on every kind of object: the neck, the RPN, the
-box head, the mask head and the segmentation head (FCN and DeepLab).  A tensor set twice, scratch growth, the two
+"""What the six objects behind the backbone share (csrc/rn_stage.hip), on every kind of object: the neck, the RPN, the
+box head, the mask head, the keypoint head and the segmentation head (FCN and DeepLab).  A tensor set twice, scratch growth, the two
 messages that name a key, and the growth guard while a captured graph lives.  Everything is compared bit for bit: an
 object that went through the bookkeeping against a fresh one on the same input, every output between guard bands
-(tests/views.py) taken as raw bytes.  Shapes are the smallest each object accepts."""
+(tests/views.py) taken as raw bytes.  Shapes are the smallest each object accepts.  Last, the two RoI heads in one call
+with two different poolers: each head's outputs are those of the call with that head alone."""
 import ctypes
 import re
 
@@ -14,6 +15,7 @@ import views as V
 from resnet_c_amd import _lib as L
 from resnet_c_amd import detection as D
 from resnet_c_amd import fpn as P
+from resnet_c_amd import keypoint as KP
 from resnet_c_amd import mask as MK
 from resnet_c_amd import ops
 from resnet_c_amd import roi as RO
@@ -109,6 +111,26 @@ class BoxHead:
         return finish(st, outs)
 
 
+def small_tail():
+    """this file's neck, an rpn over its three levels and its box head: what a RoI head runs behind"""
+    net = RP.RegionProposalNetwork(64, RP.AnchorGenerator(sizes=((8,), (16,), (32,)), aspect_ratios=(1.0,)),
+                                   RP.generate_rpn_state(64, 1, seed=6, std=0.05), pre_nms_top_n=4, post_nms_top_n=3)
+    return Neck().make(), net, BoxHead().make()
+
+
+def behind(tail, seed, levels=(), **heads):
+    """2 images of 2 detections each through the tail (maps of 4x4 and 2x2) and the RoI heads given"""
+    neck, net, bh = tail
+    g = np.random.default_rng(seed)
+    maps = [g.standard_normal((2, 4, 4, 64), dtype=F), g.standard_normal((2, 2, 2, 128), dtype=F)]
+    return neck.forward(maps, levels=levels, image_size=IMAGE, rpn=net, pooler=RO.MultiScaleRoIAlign(["0", "1"], 1, 2), box_head=bh,
+                        **heads)
+
+
+MASK_KEYS = ("mask_rois", "mask_pooled", "mask_probs", "masks", "mask_bits")
+KEYPOINT_KEYS = ("keypoint_rois", "keypoint_pooled", "keypoint_heatmaps", "keypoints", "keypoints_scores")
+
+
 class MaskHead:
     """Cin = 64, one layer of 64, Cr = 64, C = 2, M = 2; larger: rows, then rows with the RoI rows and pooled features of a
     forward behind a neck (rn_fpn_forward_masks: step "pool")"""
@@ -135,22 +157,40 @@ class MaskHead:
 
     def behind_a_neck(self, obj):
         """2 images of 2 detections each through a neck, an rpn and a box head of this test's: 4 rows with pool"""
-        if self.tail is None:
-            neck = Neck().make()
-            net = RP.RegionProposalNetwork(64, RP.AnchorGenerator(sizes=((8,), (16,), (32,)), aspect_ratios=(1.0,)),
-                                           RP.generate_rpn_state(64, 1, seed=6, std=0.05), pre_nms_top_n=4, post_nms_top_n=3)
-            self.tail = (neck, net, BoxHead().make())
-        neck, net, bh = self.tail
-        g = np.random.default_rng(139)
-        maps = [g.standard_normal((2, 4, 4, 64), dtype=F), g.standard_normal((2, 2, 2, 128), dtype=F)]
-        out = neck.forward(maps, levels=(), image_size=IMAGE, rpn=net, pooler=RO.MultiScaleRoIAlign(["0", "1"], 1, 2), box_head=bh,
-                           mask_head=obj, masks=("probs", "image", "bits"), mask_pooled=True)
-        return {k: np.ascontiguousarray(out[k]).view(np.uint8) for k in ("mask_rois", "mask_pooled", "mask_probs", "masks", "mask_bits")}
+        self.tail = self.tail or small_tail()
+        out = behind(self.tail, 139, mask_head=obj, masks=("probs", "image", "bits"), mask_pooled=True)
+        return {k: np.ascontiguousarray(out[k]).view(np.uint8) for k in MASK_KEYS}
 
     def close(self):
         for o in self.tail or ():
             o.close()
         self.tail = None
+
+
+class KeypointHead(MaskHead):
+    """Cin = 64, one layer of 64, Kp = 2, M = 2; larger: rows, then rows with the RoI rows and pooled features of a forward
+    behind a neck (rn_fpn_forward_keypoints: step "pool")"""
+    prefix, twice = "rn_keypoint_head", ("keypoint_head.0.weight", "keypoint_predictor.kps_score_lowres.bias")
+
+    def make(self):
+        return KP.KeypointHead(64, (64,), 2, KP.generate_keypoint_head_state(64, (64,), 2, seed=5), resolution=2,
+                               featmap_names=("0", "1"))
+
+    def call(self, obj, step):
+        K = self.steps[step]
+        g = np.random.default_rng(140 + step)
+        lo = g.uniform(0, 12, (K, 2)).astype(F)
+        x = V.place(np.maximum(g.standard_normal((K, 2, 2, 64), dtype=F), 0))
+        lab, box = V.place(np.ones(K, np.int32)), V.place(np.concatenate([lo, lo + g.uniform(4, 16, (K, 2)).astype(F)], axis=1))
+        outs = out_views(KP.output_spec(1, K, 2, 64, 2, ("keypoints", "heatmaps")))
+        req = obj.request(outs)
+        st = L.lib().rn_keypoint_head_forward(obj.handle, x.ptr, lab.ptr, box.ptr, K, *IMAGE, ctypes.byref(req))
+        return finish(st, outs)
+
+    def behind_a_neck(self, obj):
+        self.tail = self.tail or small_tail()
+        out = behind(self.tail, 149, keypoint_head=obj, keypoints=KP.KEYPOINT_OUTPUTS)
+        return {k: np.ascontiguousarray(out[k]).view(np.uint8) for k in KEYPOINT_KEYS}
 
 
 class SegHead:
@@ -177,7 +217,7 @@ class SegHead:
 
 # the DeepLab case of the set-twice test: bf16 on a 2 x 2 map with rates (2, 3), where both dilated branches run on their
 # centre tap, so a centre-tap copy of the garbage would show
-KINDS = {"neck": Neck, "rpn": Rpn, "box_head": BoxHead, "mask_head": MaskHead,
+KINDS = {"neck": Neck, "rpn": Rpn, "box_head": BoxHead, "mask_head": MaskHead, "keypoint_head": KeypointHead,
          "fcn": lambda: SegHead("fcn", "f32", (1, 2), ("classifier.0.weight", "classifier.1.running_var")),
          "deeplab": lambda: SegHead("deeplab", "bf16", (2, 3), ("classifier.0.convs.1.0.weight", "classifier.0.convs.2.1.bias"))}
 
@@ -328,3 +368,39 @@ def test_growth_is_refused_while_a_graph_lives(kind, held):
     finally:
         g.close()
         obj.close()
+
+
+TWO_HEADS_SEED = 139   # at least one of the four detections has a label >= 1 (asserted below)
+
+
+def test_two_heads_with_two_poolers_in_one_call():
+    """A mask head on levels ("0", "1") at resolution 2, two samples, and a keypoint head on level ("1",) at resolution 1,
+    one sample, in ONE forward: every output of either head holds the bytes of the same call with that head alone, each
+    head's pooled features are ops.roi_align_nhwc on the exported levels with that head's own scales and thresholds, and
+    no output keeps its poison.  A slot that read the other's scales, thresholds, resolution or scratch shows here."""
+    tail = small_tail()
+    mh = MaskHead().make()
+    kh = KP.KeypointHead(64, (64,), 2, KP.generate_keypoint_head_state(64, (64,), 2, seed=5), resolution=1, featmap_names=("1",),
+                         sampling_ratio=1)
+    mh.poison = kh.poison = True
+    mask_kw = dict(mask_head=mh, masks=("probs", "image", "bits"), mask_pooled=True)
+    kp_kw = dict(keypoint_head=kh, keypoints=KP.KEYPOINT_OUTPUTS)
+    try:
+        both = behind(tail, TWO_HEADS_SEED, ("0", "1"), **mask_kw, **kp_kw)
+        alone = {MASK_KEYS: behind(tail, TWO_HEADS_SEED, ("0", "1"), **mask_kw),
+                 KEYPOINT_KEYS: behind(tail, TWO_HEADS_SEED, ("0", "1"), **kp_kw)}
+    finally:
+        for o in (mh, kh) + tail:
+            o.close()
+    print("labels", both["labels"].tolist(), "detections", both["detections"].tolist())
+    assert (both["labels"] >= 1).any(), "the comparison would be of zeros"
+    for (keys, one), head in zip(alone.items(), (mh, kh)):
+        for k in keys:
+            raw = np.ascontiguousarray(both[k]).view(np.uint8)
+            V.check_written(raw, both[k].dtype.itemsize, k)
+            assert np.array_equal(raw, np.ascontiguousarray(one[k]).view(np.uint8)), k
+        maps = [np.ascontiguousarray(both[n].transpose(0, 2, 3, 1)) for n in head.pooler.featmap_names]
+        scales = RO.infer_scales([m.shape[1:3] for m in maps], IMAGE)
+        want = ops.roi_align_nhwc(maps, both[keys[0]], scales, head.resolution, head.pooler.sampling_ratio, False,
+                                  head.pooler.thresholds(scales), validate=False)
+        assert np.array_equal(both[keys[1]].view(np.uint8), np.ascontiguousarray(want).view(np.uint8)), keys[1]

@@ -5,9 +5,10 @@
     python tools/stage_objects_bits.py OUT_DIR                 (once per library: writes one .npy per output)
     python tools/stage_objects_bits.py --compare PARENT_DIR THIS_DIR
 
-The run, at a 64 x 64 input, 2 images: ResNet-18 with a neck, an RPN, a pooler, a box head and a mask head in one
-forward_fpn(..., masks=("probs", "bits")), every level exported; a dilated ResNet-50 with a DeepLab head in one
-forward_segment(scores and labels).  The comparison: the same files, the same shapes and types, the same bytes."""
+The run, at a 64 x 64 input, 2 images: ResNet-18 with a neck, an RPN, a pooler, a box head, a mask head and a keypoint
+head in one forward_fpn(..., masks=("probs", "bits"), keypoints=("keypoints", "heatmaps", "rois", "pooled")), every
+level exported; a dilated ResNet-50 with a DeepLab head in one forward_segment(scores and labels).  The comparison:
+the same files, the same shapes and types, the same bytes."""
 import os
 import sys
 
@@ -34,6 +35,7 @@ def run(out_dir):
     import resnet_c_amd as R
     from resnet_c_amd import detection as D
     from resnet_c_amd import fpn as P
+    from resnet_c_amd import keypoint as KP
     from resnet_c_amd import mask as MK
     from resnet_c_amd import roi as RO
     from resnet_c_amd import rpn as RP
@@ -49,10 +51,11 @@ def run(out_dir):
                                    RP.generate_rpn_state(a, 3, seed=3), 100, 60, 0.7)
     bh = D.BoxHead(a, res, 64, C, D.generate_box_head_state(a * res * res, 64, C, seed=6), detections_per_img=Dn)
     mh = MK.MaskHead(a, (64,), 64, C, MK.generate_mask_head_state(a, (64,), 64, C, seed=8), resolution=2)
+    kh = KP.KeypointHead(a, (64,), 3, KP.generate_keypoint_head_state(a, (64,), 3, seed=9), resolution=2)
     got = m.forward_fpn(x, neck, rpn=net, pooler=RO.MultiScaleRoIAlign(["0", "1", "2", "3"], res, 2), box_head=bh, mask_head=mh,
-                        masks=("probs", "bits"))
+                        masks=("probs", "bits"), keypoint_head=kh, keypoints=("keypoints", "heatmaps", "rois", "pooled"))
     outs = flat(got, "fpn.")
-    for o in (mh, bh, net, neck, m):
+    for o in (kh, mh, bh, net, neck, m):
         o.close()
     rates = (2, 12)
     d = R.NativeModel("resnet50", state=W.generate_state("resnet50", seed=2), input_size=SIZE, replace_stride_with_dilation=(0, 1, 1))
