@@ -127,6 +127,12 @@ enum {
 
 /* ---- context ----------------------------------------------------------- */
 RN_API int rn_ctx_create(rn_ctx **out, int device, void *hip_stream /* NULL: own stream */);
+/* On a context with deferred state (rn_ctx_set_deferred, below) destroy runs what is recorded and gives
+ * every caller buffer that the route holds as NHWC its NCHW content back, then waits for the stream.
+ * So memory that was handed to a deferred context must still be allocated when the context is
+ * destroyed: free it through that context first (rn_free takes the buffer out of the route's books), or
+ * rn_observe it (it is NCHW then and destroy leaves it alone) -- a buffer freed behind the context's back
+ * would be written after its free. */
 RN_API int rn_ctx_destroy(rn_ctx *ctx);
 RN_API int rn_ctx_set_layout(rn_ctx *ctx, int layout);
 RN_API int rn_ctx_get_layout(const rn_ctx *ctx);
@@ -156,8 +162,20 @@ RN_API int rn_ctx_set_sync_each_op(rn_ctx *ctx, int on);
  * neither group names a buffer the other writes (checked; otherwise the call order is kept).
  * Contract for the caller: device memory it handed to the seven ops is read and written by other
  * means (own kernels, hipMemcpy) only after rn_observe(ctx, ptr) -- the C++ veneer's Tensor::data()
- * does that; weights and batch-norm parameters are cached in packed / folded form per buffer and the
- * cache follows writes made through rn_* calls only (like rn_ctx_set_weight_cache).
+ * does that.  rn_sync, rn_flush and rn_event_record RUN the list but leave the buffers NHWC (and
+ * tagged): another stream or another context that reads such a buffer must see rn_observe(ctx, ptr)
+ * first, however the two are ordered otherwise.  rn_ctx_destroy, rn_ctx_set_deferred(ctx, 0) and a
+ * change of rn_ctx_set_layout give every buffer its NCHW content back.  Such memory is freed through
+ * this context (rn_free) or observed first, and is still allocated when the context is destroyed (see
+ * rn_ctx_destroy).  Weights and batch-norm parameters are cached in packed / folded form per buffer, by
+ * pointer.  The caches follow writes made by: the seven recorded ops (an rn_add_forward or
+ * rn_relu_forward whose output is a parameter buffer: the ops behind it in the list use the new
+ * content, the ones in front of it the old); rn_memcpy_h2d, rn_memcpy_d2d and rn_memset; rn_free.
+ * Switching the route off forgets them, so the seven ops may write parameters while they run
+ * literally.  Any other writer -- an entry point outside the seven, the caller's own kernels, a
+ * hipMemcpy -- is the caller's promise not to change a parameter buffer the route has seen (with
+ * rn_ctx_set_weight_cache(ctx, 1) the packed panels are that cache's as well and keep its rule while
+ * the route is off).
  * Numerics: the folded batch-norm is one fp32 fmaf per element instead of ops.cu:150's double
  * expression (<= 2e-5 on ResNet logits; the same epilogue as RN_FWD_FUSED).  on = 0 (default): every
  * call launches at once on NCHW tensors, the parity baseline; switching off runs what is recorded and

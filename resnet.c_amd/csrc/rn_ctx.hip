@@ -237,7 +237,9 @@ int rn_ctx_destroy(rn_ctx *ctx)
 {
     if (!ctx) return RN_OK;
     (void)hipSetDevice(ctx->device);
-    (void)rn_defer_flush(ctx);  // recorded ops run (their outputs may be read through other contexts later)
+    // recorded ops run and every buffer the route left NHWC gets its NCHW content back: the tags die with the
+    // context, and the outputs may be read through other contexts later
+    (void)rn_defer_barrier(ctx);
     (void)hipStreamSynchronize(ctx->stream);
     rn_defer_destroy(ctx);
     for (int i = 0; i < 7; ++i) {

@@ -244,6 +244,40 @@ int exact_for(rn_ctx *ctx, const Op &c, const float **packed, bool stem = false)
     return RN_OK;
 }
 
+// Forget every fold and every exact-K / stem panel whose SOURCE (the batch-norm parameter buffers, the OIHW weight)
+// overlaps [ptr, ptr + bytes), which has been or is about to be written.  A launch already queued may still read
+// the device block of a dropped entry, so a hit synchronises the stream before the block is freed (hits are
+// parameter updates: rare, and never part of a forward).  No hit: pointer comparisons only, no device call.
+void drop_cached(rn_ctx *ctx, const void *ptr, uint64_t bytes)
+{
+    rn_defer_state *ds = ctx->ds;
+    bool synced = false;
+    for (size_t i = 0; i < ds->folds.size();) {
+        const Fold &f = ds->folds[i];
+        const uint64_t cb = f.C * sizeof(float);
+        if (overlaps(ptr, bytes, f.w, cb) || overlaps(ptr, bytes, f.b, cb) || overlaps(ptr, bytes, f.m, cb) ||
+            overlaps(ptr, bytes, f.v, cb)) {
+            if (!synced) (void)hipStreamSynchronize(ctx->stream), synced = true;
+            (void)hipFree(f.scale);
+            ds->folds[i] = ds->folds.back();
+            ds->folds.pop_back();
+        } else {
+            ++i;
+        }
+    }
+    for (size_t i = 0; i < ds->exact.size();) {
+        const ExactPack &e = ds->exact[i];
+        if (overlaps(ptr, bytes, e.w, e.cin * e.cout * e.k * e.k * sizeof(float))) {
+            if (!synced) (void)hipStreamSynchronize(ctx->stream), synced = true;
+            (void)hipFree(e.packed);
+            ds->exact[i] = ds->exact.back();
+            ds->exact.pop_back();
+        } else {
+            ++i;
+        }
+    }
+}
+
 bool is_tagged_as(rn_defer_state *ds, const void *ptr, uint64_t B, uint64_t C, uint64_t H, uint64_t W)
 {
     const Tag *t = find_tag(ds, ptr);
@@ -615,6 +649,7 @@ int run_list(rn_ctx *ctx)
     while (st == RN_OK && i < ds->ops.size()) {
         st = settle_op(ctx, ds->ops[i]);
         if (st != RN_OK) break;
+        const size_t first = i;
         if (ds->ops[i].kind == K_CONV) {
             size_t next = i + 1;
             st = run_conv(ctx, i, &next);
@@ -623,6 +658,18 @@ int run_list(rn_ctx *ctx)
             const Op o = ds->ops[i];
             st = run_literal(ctx, o);
             ++i;
+        }
+        // A recorded op may write a batch-norm parameter or a weight (an add or a ReLU into it): whatever was
+        // folded or packed from a buffer this group wrote is stale for the groups BEHIND it in the list, and
+        // still right for the ones in front, which have been issued.  Hence here, in list order.
+        Range r[7];
+        for (size_t a = first; a < i && a < ds->ops.size(); ++a) {
+            const int nr = op_ranges(ds->ops[a], r);
+            for (int x = 0; x < nr; ++x) {
+                if (!r[x].write || !r[x].ptr) continue;
+                drop_cached(ctx, r[x].ptr, r[x].bytes);
+                if (ctx->wcache_n) rn_wcache_drop(ctx, r[x].ptr, r[x].bytes);  // (synchronises on a hit, too)
+            }
         }
     }
     ds->ops.clear();
@@ -692,31 +739,7 @@ int rn_defer_before_write(rn_ctx *ctx, const void *ptr, uint64_t bytes, int whol
         }
         i = 0;
     }
-    bool synced = false;
-    for (size_t i = 0; i < ds->folds.size();) {
-        const Fold &f = ds->folds[i];
-        const uint64_t cb = f.C * sizeof(float);
-        if (overlaps(ptr, bytes, f.w, cb) || overlaps(ptr, bytes, f.b, cb) || overlaps(ptr, bytes, f.m, cb) ||
-            overlaps(ptr, bytes, f.v, cb)) {
-            if (!synced) (void)hipStreamSynchronize(ctx->stream), synced = true;
-            (void)hipFree(f.scale);
-            ds->folds[i] = ds->folds.back();
-            ds->folds.pop_back();
-        } else {
-            ++i;
-        }
-    }
-    for (size_t i = 0; i < ds->exact.size();) {
-        const ExactPack &e = ds->exact[i];
-        if (overlaps(ptr, bytes, e.w, e.cin * e.cout * e.k * e.k * sizeof(float))) {
-            if (!synced) (void)hipStreamSynchronize(ctx->stream), synced = true;
-            (void)hipFree(e.packed);
-            ds->exact[i] = ds->exact.back();
-            ds->exact.pop_back();
-        } else {
-            ++i;
-        }
-    }
+    drop_cached(ctx, ptr, bytes);
     return RN_OK;
 }
 
@@ -817,7 +840,17 @@ int rn_ctx_set_deferred(rn_ctx *ctx, int on)
 {
     if (!ctx) return RN_ERR_INVALID;
     RN_TRY(rn_bind_device(ctx));
-    if (!on && ctx->defer) RN_TRY(rn_defer_barrier(ctx));  // everything runs, every buffer back to NCHW
+    if (!on && ctx->defer) {
+        RN_TRY(rn_defer_barrier(ctx));  // everything runs, every buffer back to NCHW
+        // While the ops run literally nothing compares their outputs with the cached sources: the folds, the
+        // exact-K / stem panels and the panels packed_for put into a weight cache that is otherwise off go now,
+        // and are made again from the buffers' content when the route is switched back on.  (With the weight
+        // cache on, its panels are the literal route's as well and stay under that cache's own rule.)
+        if (ctx->ds) {
+            drop_cached(ctx, nullptr, ~(uint64_t)0);
+            if (!ctx->wcache_on && ctx->wcache_n) rn_wcache_drop(ctx, nullptr, ~(uint64_t)0);
+        }
+    }
     ctx->defer = on ? 1 : 0;
     return RN_OK;
 }

@@ -9,10 +9,15 @@ of device tensors -- in place and out of place, chains that fold (conv -> bn -> 
 chains that do not (another order, another buffer, a shape without an NHWC contraction), residuals that are
 NHWC-tagged outputs of earlier convolutions or plain NCHW tensors -- interleaved with the things that observe
 or disturb recorded work: whole and partial reads, rn_observe, rn_flush, writes into operands, frees, parameter
-updates.  After every read and at the end, every live tensor must hold what the literal run holds: bit for bit
+updates from the host -- and with what tries the state a deferred context keeps: a recorded add or ReLU whose OUTPUT
+is a weight or a batch-norm parameter of the program (devparam), the route switched off for one literal op and on
+again (toggle), the deferred context destroyed with work pending and buffers tagged, and the rest of the program on a
+fresh one (reopen).  The deferred run therefore owns its context; tensors live on the shared one and outlive it.
+After every read and at the end, every live tensor must hold what the literal run holds: bit for bit
 where no batch-norm was folded into a convolution, within the fused epilogue's rounding otherwise (the literal
 route applies ops.cu:150's double expression, the fused one a folded fp32 fmaf)."""
 import argparse
+import collections
 import os
 import sys
 import time
@@ -26,6 +31,22 @@ from resnet_c_amd import _lib as L
 
 def call(ctx, name, *args):
     L.check(getattr(L.lib(), name)(ctx.handle, *args), name, ctx.handle)
+
+
+def read(ctx, t):
+    """the whole tensor through ctx (FloatTensor.numpy reads through the shared context, which knows no tags)"""
+    host = np.empty(tuple(t.shape()), dtype=np.float32)
+    call(ctx, "rn_memcpy_d2h", host.ctypes.data, t.data(), host.nbytes)
+    return host
+
+
+def free_through(ctx, t):
+    """rn_free through the context that may have recorded ops on the buffer or hold it as NHWC"""
+    ptr, t._storage.ptr = t._storage.ptr, 0   # (the finaliser finds nothing left to free)
+    call(ctx, "rn_free", ptr)
+
+
+NEW_KINDS = ("devparam", "toggle", "reopen")
 
 
 class Program:
@@ -71,7 +92,7 @@ class Program:
         for _ in range(n_ops):
             kind = str(g.choice(["conv", "conv", "conv", "bn", "relu", "add", "maxpool", "avgpool", "observe", "read",
                                  "partial", "flush", "rewrite", "free", "newbn", "slice_relu", "slice_conv", "view_conv",
-                                 "view_bn", "boundary"]))
+                                 "view_bn", "boundary", "devparam", "devparam", "toggle", "reopen"]))
             src = int(g.choice(live))
             Bs, C, Hs, Ws = self.shapes[src]
             if kind == "conv":
@@ -198,6 +219,22 @@ class Program:
             elif kind == "free" and src != 0 and len(live) > 2:
                 live.remove(src)
                 self.steps.append(("free", src))
+            elif kind == "devparam":
+                st = self._devparam()
+                if st:
+                    self.steps.append(st)
+            elif kind == "toggle":
+                # deferred off, ONE op run literally, deferred on: an element-wise op on the tensors, or a write into
+                # a parameter that the route has folded or packed
+                inner = self._devparam() if g.random() < 0.5 else None
+                if inner is None:
+                    dst = src if g.random() < 0.7 else self._new_like(src, live)
+                    nxt = max(nxt, dst + 1)
+                    same = [i for i in live if self.shapes[i] == self.shapes[src]]
+                    inner = ("relu", src, dst) if g.random() < 0.5 else ("add", src, int(g.choice(same)), dst)
+                self.steps.append(("toggle", inner))
+            elif kind == "reopen":
+                self.steps.append(("reopen",))
             elif kind == "newbn":
                 bns = [st for st in self.steps if st[0] == "bn"]
                 if bns:
@@ -213,6 +250,25 @@ class Program:
         live.append(dst)
         return dst
 
+    def _devparam(self):
+        """("devparam", target parameter set, index in it, operand, op): rn_add_forward(p, q, p) or rn_relu_forward(q, p)
+        with p a weight or a batch-norm buffer some earlier step of the program uses; None when there is none yet"""
+        g = self.g
+        at = {"conv": 3, "view_conv": 3, "slice_conv": 3, "bn": 3, "view_bn": 2}
+        sets = [st[at[st[0]]] for st in self.steps if st[0] in at]
+        if not sets:
+            return None
+        pi = int(g.choice(sets))
+        j = int(g.integers(0, len(self.params[pi])))
+        p = self.params[pi][j]
+        if len(self.params[pi]) == 4 and j == 3:   # a variance stays positive under either op
+            q = g.random(p.shape, dtype=np.float32) + 0.5
+        else:
+            q = (g.standard_normal(p.shape, dtype=np.float32) * max(float(p.std()), 0.05)).astype(np.float32)
+        qi = len(self.params)
+        self.params[qi] = [q.astype(np.float32)]
+        return ("devparam", pi, j, qi, str(g.choice(["add", "relu"])))
+
     def _bn(self, src, dst):
         C = self.shapes[src][1]
         g = self.g
@@ -221,18 +277,43 @@ class Program:
         self.steps.append(("bn", src, dst, len(self.params)))
         self.params[len(self.params)] = pr
 
-    def run(self, ctx):
-        """Execute on ctx; returns (reads in program order, final contents of the live tensors)."""
+    def run(self, deferred):
+        """Execute literally on the shared context, or on a deferred context of the program's own (a reopen step
+        destroys it and goes on with a fresh one); returns (reads in program order, final contents of the live tensors,
+        deferred counters summed over the contexts, how often each of NEW_KINDS ran)."""
+        ctx = R.Context() if deferred else R.get_ctx()
+        ctx.set_deferred(deferred)
         T = {0: R.FloatTensor.from_numpy(self.host[0], R.Device.GPU)}
         P = {}
         reads = []
+        stats = collections.Counter()
+        ran = collections.Counter()
+        try:
+            self._steps(ctx, deferred, T, P, reads, stats, ran)
+            ctx = self._ctx
+            final = {i: read(ctx, self._tensor(ctx, T, i)) for i in self.live_end}
+            if deferred:
+                ctx.set_deferred(False)   # the barrier: nothing pending, nothing tagged afterwards
+                s = ctx.deferred_stats()
+                assert s["pending_ops"] == 0 and s["nhwc_buffers"] == 0, s
+                stats.update(s)
+        finally:
+            if deferred:                  # before T and P go: destroy rewrites the buffers it holds as NHWC
+                self._ctx.close()
+        return reads, final, stats, ran
+
+    def _tensor(self, ctx, T, i):
+        if i not in T:
+            T[i] = R.FloatTensor(self.shapes[i], R.Device.GPU)
+            # a defined starting content (literal and deferred runs must agree on bytes never written)
+            call(ctx, "rn_memset", T[i].data(), 0, int(np.prod(self.shapes[i])) * 4)
+        return T[i]
+
+    def _steps(self, ctx, deferred, T, P, reads, stats, ran):
+        self._ctx = ctx
 
         def tensor(i):
-            if i not in T:
-                T[i] = R.FloatTensor(self.shapes[i], R.Device.GPU)
-                # a defined starting content (literal and deferred runs must agree on bytes never written)
-                call(ctx, "rn_memset", T[i].data(), 0, int(np.prod(self.shapes[i])) * 4)
-            return T[i]
+            return self._tensor(ctx, T, i)
 
         def param(i):
             if i not in P:
@@ -241,7 +322,30 @@ class Program:
 
         for st in self.steps:
             kind = st[0]
-            if kind == "conv":
+            if kind in NEW_KINDS:
+                ran[kind] += 1
+            toggled = kind == "toggle"
+            if toggled:
+                ctx.set_deferred(False)   # the op inside runs literally; the route is switched back on behind it
+                st = st[1]
+                kind = st[0]
+            if kind == "reopen":
+                if deferred:
+                    s = ctx.deferred_stats()
+                    stats.update(s)
+                    stats["unseen_ops"] += s["pending_ops"]   # destroy runs them: launches no counter shows any more
+                    ctx.close()           # ops pending, buffers tagged: all of it must be in the tensors afterwards
+                    ctx = self._ctx = R.Context()
+                    ctx.set_deferred(True)
+            elif kind == "devparam":
+                _, pi, j, qi, op = st
+                p, q = param(pi)[j], param(qi)[0]
+                n = int(self.params[qi][0].size)
+                if op == "add":
+                    call(ctx, "rn_add_forward", p.data(), q.data(), p.data(), n)
+                else:
+                    call(ctx, "rn_relu_forward", q.data(), p.data(), n)
+            elif kind == "conv":
                 _, src, dst, pi, k, s, p = st
                 Bs, C, Hs, Ws = self.shapes[src]
                 _, Cout, ho, wo = self.shapes[dst]
@@ -290,7 +394,7 @@ class Program:
             elif kind == "flush":
                 ctx.flush()
             elif kind == "read":
-                reads.append((st[1], tensor(st[1]).numpy()))
+                reads.append((st[1], read(ctx, tensor(st[1]))))
             elif kind == "partial":
                 n = int(np.prod(self.shapes[st[1]]))
                 lo = n // 3
@@ -303,12 +407,13 @@ class Program:
                 a = self.params[st[2]][0]
                 call(ctx, "rn_memcpy_h2d", tensor(st[1]).data(), a.ctypes.data, a.nbytes)
             elif kind == "free":
-                T.pop(st[1], None)   # FloatTensor.__del__ -> rn_free
+                if st[1] in T:
+                    free_through(ctx, T.pop(st[1]))
             elif kind == "newbn":
                 a = self.params[st[2]][0]
                 call(ctx, "rn_memcpy_h2d", param(st[1])[0].data(), a.ctypes.data, a.nbytes)
-        final = {i: tensor(i).numpy() for i in self.live_end}
-        return reads, final
+            if toggled:
+                ctx.set_deferred(deferred)
 
 
 def close(a, b, exact):
@@ -324,23 +429,18 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
     g = np.random.default_rng(a.seed)
-    ctx = R.get_ctx()
     t0 = time.time()
     n = fused = 0
+    ran = collections.Counter()
     while time.time() - t0 < a.seconds:
         prog = Program(g)
-        ctx.set_deferred(False)
-        want_reads, want_final = prog.run(ctx)
-        ctx.set_deferred(True)
-        s0 = ctx.deferred_stats()
-        got_reads, got_final = prog.run(ctx)
-        s1 = ctx.deferred_stats()
-        ctx.set_deferred(False)   # the barrier: nothing pending, nothing tagged afterwards
-        s2 = ctx.deferred_stats()
-        assert s2["pending_ops"] == 0 and s2["nhwc_buffers"] == 0, (a.seed, n, s2)
+        want_reads, want_final, _, _ = prog.run(False)
+        got_reads, got_final, stats, kinds = prog.run(True)
+        ran.update(kinds)
         # a fused launch that folded a batch-norm rounds differently from ops.cu:150's double expression; everything
         # else is the literal kernels on the same values
-        folded_bn = any(st[0] == "bn" for st in prog.steps) and s1["fused_launches"] > s0["fused_launches"]
+        # (ops that a reopen step's destroy ran may have been fused launches: counted as if they were)
+        folded_bn = any(st[0] == "bn" for st in prog.steps) and stats["fused_launches"] + stats["unseen_ops"] > 0
         # (and a 3-channel convolution runs in its exact-K form when recorded, in the 4-channel / 8-slot form
         # literally: the same products grouped into other K tiles)
         folded_bn = folded_bn or any(st[0] == "conv" and prog.shapes[st[1]][1] <= 4 for st in prog.steps)
@@ -351,7 +451,8 @@ def main():
             assert close(got_final[i], want_final[i], not folded_bn), \
                 f"seed {a.seed} program {n}: final tensor {i} {prog.shapes[i]} differs\n{prog.steps}"
         n += 1
-        fused += s1["fused_launches"] - s0["fused_launches"]
+        fused += stats["fused_launches"]
+    print("step kinds: " + ", ".join(f"{k} {ran[k]}" for k in NEW_KINDS))
     print(f"{n} random programs on a deferred context ({fused} fused launches), every read and every final tensor "
           f"as the literal run's: all within tolerance")
 

@@ -43,9 +43,14 @@ def test_model_fuzz_short(dtype):
 
 def test_defer_fuzz_short():
     """Random programs of the seven reference ops on a deferred context (folding and non-folding chains, reads,
-    partial reads, rn_observe, writes into operands, frees, parameter updates) against the literal run."""
+    partial reads, rn_observe, writes into operands, frees, parameter updates; recorded and literal writes into
+    parameters, the route switched off and on, the context destroyed mid-program) against the literal run."""
     out = run_tool("defer_fuzz.py", "--seconds", "10", "--seed", "104")
     assert "all within tolerance" in out
+    kinds = [l for l in out.splitlines() if l.startswith("step kinds: ")]
+    assert len(kinds) == 1, out
+    ran = {k: int(v) for k, v in (item.split() for item in kinds[0][len("step kinds: "):].split(", "))}
+    assert set(ran) == {"devparam", "toggle", "reopen"} and min(ran.values()) >= 1, ran
 
 
 def test_view_fuzz_short():
